@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): gate-applies/s and statevectors/s of the
 data-reuploading Model hot path at n_qubits=24, batch=1024 per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -16,9 +16,9 @@ batch of 1024 parameter sets per GPU through the drop-in API (``Model.__call__``
 trailing CX layer into the observables -- every one of the 96 counted gates is applied to a
 statevector whose 2^24 amplitudes are all read, computed and stored in every HBM pass that
 follows the |0..0> initialisation (gate *fusion* stays on: three HBM passes instead of 96).
-``value``, ``ms_per_step`` and ``roofline`` come from that run.  The default engine (known-zero
-tracking + observable folding, exact but specific to what a shallow circuit leaves untouched)
-is reported under ``exact_shortcuts``; a deeper circuit (``k2_deep``: 24 qubits, 4 layers,
+``value``, ``ms_per_step`` and ``roofline`` come from that run.  With ``--full``, the default engine
+(known-zero tracking + observable folding, exact but specific to what a shallow circuit leaves
+untouched) is reported under ``exact_shortcuts``; a deeper circuit (``k2_deep``: 24 qubits, 4 layers,
 data re-uploading) with both flag sets beside it.
 
 Parameters are synthetic U[0, 2 pi) float32 from ``numpy.random.default_rng(1000)`` and are
@@ -32,20 +32,28 @@ simulates its own 1024 states and one RCCL all-gather returns the (1024 N, 24) e
 --nproc-per-node N --master-addr 127.0.0.1 ...`` on this same file as a CHILD process (never an
 exec), relays rank 0's JSON line and exits with the child's code.  Inside, ``world_size`` must equal
 ``--gpus`` and the backend must be ``nccl`` (= RCCL; ``QMLE_DIST_BACKEND=gloo`` only for rehearsals
-with several ranks on one GPU) or the run exits non-zero.  Besides the weak-scaling K2 step the line
-carries the strong-scaling legs BASELINE names: C3 (1024 Expressibility pairs split over the ranks)
-and C4 (the 4096-point Fourier grid, 512 points per GPU at N = 8).
+with several ranks on one GPU) or the run exits non-zero.  With ``--full``, besides the weak-scaling K2
+step the line carries the strong-scaling legs BASELINE names: C3 (1024 Expressibility pairs split over
+the ranks) and C4 (the 4096-point Fourier grid, 512 points per GPU at N = 8).
 
-Legs riding in the same line (N = 1; each with its own roofline object, parity check and CPU timing where a CPU form
-exists): `c2_model_20q_4l` (BASELINE config 2: rates against HBM and L2), `c3_…` / `c4_…` (configs 3 / 4, sharded over the
-ranks) with `c3_/c4_saturated_weak` companions and `collective_ms`, `mw_28q` (config 5), `k1_single_gate_28q` (RX RZ CX
-CRX CRZ CZ CPhase on every wire), `k2_unfused`, `k2_circuit19`, `k2_deep` (per-pass bound), `exact_shortcuts`,
-`lds_regime`, `adjoint_gradient_20q` -- and `summary`, the LAST key: one figure per leg in ~3 KB.
+A plain run does only what the headline needs: set-up, ``--warmup`` untimed steps, ``--steps`` timed
+steps, the line.  ``--dump-outputs DIR`` writes what the last timed step returned -- the (1024 N, 24)
+<Z> rows -- as ``DIR/expval.npy`` (float32; a fixed, seeded sample of rows above 64 MB), so that two
+builds can be compared output for output on the same seeded inputs.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-``roofline`` (dominant kernel, timed live with HIP events on the launch stream) and
-``cpu_baseline`` (the oracle's C/OpenMP port on a bounded sample, N=1 only; its <Z> values are
-compared with the GPU's rows for the same parameter sets and a mismatch fails the run).
+``--full`` adds the legs that take runs of their own (N = 1; each with its own roofline object, parity
+check and CPU timing where a CPU form exists): `c2_model_20q_4l` (BASELINE config 2: rates against HBM
+and L2), `c3_…` / `c4_…` (configs 3 / 4, sharded over the ranks) with `c3_/c4_saturated_weak`
+companions and `collective_ms`, `mw_28q` (config 5), `k1_single_gate_28q` (RX RZ CX CRX CRZ CZ CPhase on
+every wire), `k2_unfused`, `k2_autotuned`, `k2_one_stream`, `k2_three_pass`, `k2_circuit19`, `k2_deep`
+(per-pass bound), `exact_shortcuts`, `lds_regime`, `adjoint_gradient_20q`, `widened_rows` and
+``cpu_baseline`` (the oracle's C/OpenMP port on a bounded sample; its <Z> values are compared with the
+GPU's rows for the same parameter sets and a mismatch fails the run).
+
+Rank 0 prints ONE JSON line: ``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` and ``roofline`` (dominant kernel, timed live with HIP events on the launch stream
+during the timed steps), the legs above under ``--full``, and ``summary``, the LAST key: one figure
+per leg in ~3 KB.
 """
 from __future__ import annotations
 
@@ -79,8 +87,13 @@ def parse_args(argv=None):
     ap.add_argument("--n-qubits", type=int, default=24)
     ap.add_argument("--batch", type=int, default=1024, help="statevectors per GPU per step")
     ap.add_argument("--no-fusion", action="store_true", help="one HBM pass per reference gate")
-    ap.add_argument("--skip-aux", action="store_true", help="headline only (no K1 / deep / CPU legs)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every companion leg (C2-C5 configs, K1, deep / unfused / autotuned "
+                         "/ one-stream K2, LDS regime, CPU baselines and parity checks); off: headline only")
+    ap.add_argument("--skip-aux", action="store_true", help="with --full: headline only (no K1 / deep / CPU legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU baseline budget")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="start the ranks, run the one collective on a token tensor, print the line's "
                          "rank bookkeeping and stop (launcher / process-group plumbing; needs no GPU)")
@@ -1160,6 +1173,31 @@ def adjoint_gradient_wallclock(n=20, layers=4):
             "n_params": int(p.numel()), "finite": bool(torch.isfinite(g).all())}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write every array of `arrays` (name -> tensor / array) as out_dir/<name>.npy in float32 (float64 stays
+    float64).  When they hold more than `max_bytes` together, each keeps a fixed, seeded sample of its rows
+    (the same rows for the same shape, so that two builds can be compared file for file)."""
+    host = {}
+    for name, v in arrays.items():
+        if isinstance(v, torch.Tensor):
+            v = v.detach().cpu().numpy()
+        v = np.asarray(v)
+        host[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32, copy=False)
+    total = sum(v.nbytes for v in host.values())
+    if total > max_bytes:
+        for name, v in host.items():
+            keep = max(1, int(v.shape[0] * max_bytes // total))
+            rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=keep, replace=False))
+            host[name] = np.ascontiguousarray(v[rows])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in host.items()}
+
+
 def rank_bookkeeping(a, rank, size):
     """World checks shared by the full run and --rendezvous-only: the job must have exactly
     --gpus ranks on the nccl (RCCL) backend -- gloo only when QMLE_DIST_BACKEND asks for a rehearsal
@@ -1224,9 +1262,14 @@ def main(argv=None):
     DENSE = N.PLAN_NO_SPARSE | N.PLAN_NO_ABSORB
     head_flags = DENSE | (N.PLAN_NO_FUSION if a.no_fusion else 0)
     head = timed_k2(n, B, size, a.steps, a.warmup, head_flags)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        # the (B x ranks, n) <Z> rows the last timed call returned, on the seeded parameter sets
+        dumped = dump_outputs(a.dump_outputs, {"expval": head["out"].reshape(-1, n)})
 
+    aux = a.full and not a.skip_aux
     c3 = c4 = c3s = c4s = None
-    if not a.skip_aux:  # sharded over all ranks -> every rank takes part
+    if aux:  # sharded over all ranks -> every rank takes part
         c3 = expressibility_leg()
         c4 = fourier_grid_leg()
         c3s = expressibility_leg(samples=C3_SATURATED_PAIRS_PER_RANK * size, reps=7, warm=5, scaling="weak")
@@ -1252,7 +1295,7 @@ def main(argv=None):
         roofline["valu"] = valu_roofline(head, True)
         roofline["overlap_note"] = ("two chunks of 32 states are in flight, one stage apart, on two internal streams (the fill of one "
                                     "beside the measuring pass of the other): avg_launch_ms / achieved / frac above are live HIP-event "
-                                    "figures of launches that share the card; `isolated_launch` has the same kernel alone, "
+                                    "figures of launches that share the card; `isolated_launch` (--full) has the same kernel alone, "
                                     "step_moved_frac_of_8TBps the bytes of the whole step over its wall-clock")
         roofline["counters_note"] = ("SQ counters of the same plan (profiles/r05_k2_headline_sq.txt): the measuring k_tile2 pass "
                                      "issues vector instructions 69 % of its cycles (81 % of them the packed FMAs of its 11 dense "
@@ -1286,13 +1329,16 @@ def main(argv=None):
         "step_moved_GBps": hs["moved_GBps"], "step_moved_GBps_per_gpu": hs["moved_GBps_per_gpu"],
         "step_moved_frac_of_8TBps": hs["moved_frac_of_8TBps"],
         "roofline": roofline,
+        "full": a.full,
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
     if c3 is not None:
         result["c3_expressibility_12q_1024pairs"] = c3
         result["c4_fourier_10q_6l_4096grid"] = c4
         result["c3_saturated_weak"] = c3s
         result["c4_saturated_weak"] = c4s
-    if not a.skip_aux and size == 1 and not a.no_fusion:
+    if aux and size == 1 and not a.no_fusion:
         # SURVEY 8-d `achieved_unfused`: one HBM pass per reference gate, no 1-qubit merging
         try:
             uf = k2_unfused_leg(n, min(B, 128))
@@ -1433,7 +1479,7 @@ def main(argv=None):
             result["k2_deep"] = deep
         except Exception as e:  # pragma: no cover
             result["k2_deep"] = {"error": str(e)}
-    if not a.skip_aux and size == 1:
+    if aux and size == 1:
         gpu_rows = head["out"][:64].cpu().numpy()
         result["cpu_baseline"] = cpu_baseline(n, head["params"][:64], a.cpu_seconds, gpu_rows)
         try:

@@ -88,3 +88,40 @@ def test_committed_traffic_file_is_signed():
     for key in ("k_tile2:n24:dense", "meyer_wallach:n28"):
         assert key in doc, key
         assert len(doc[key].get("source_sha16", "")) == 16, key
+
+
+def test_plain_run_is_headline_only_and_full_is_opt_in():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline and nothing else; every companion leg
+    waits for --full, and --steps / --warmup are taken as given."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float_arrays_and_caps_the_size(tmp_path):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    expval = torch.linspace(-1, 1, 1024 * 24).reshape(1024, 24)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), {"expval": expval})
+    got = np.load(tmp_path / "a" / "expval.npy")
+    assert shapes == {"expval": [1024, 24]} and got.dtype == np.float32
+    assert np.array_equal(got, expval.numpy())
+    x64 = np.arange(12.0).reshape(4, 3)
+    bench.dump_outputs(str(tmp_path / "d"), {"x": x64})
+    assert np.load(tmp_path / "d" / "x.npy").dtype == np.float64
+    # above the cap: a seeded sample of rows, the same rows every time
+    cap = 24 * 4 * 100
+    shapes = bench.dump_outputs(str(tmp_path / "b"), {"expval": expval}, max_bytes=cap)
+    first = np.load(tmp_path / "b" / "expval.npy")
+    assert first.nbytes <= cap and shapes == {"expval": list(first.shape)} and first.shape[1] == 24
+    bench.dump_outputs(str(tmp_path / "c"), {"expval": expval}, max_bytes=cap)
+    assert np.array_equal(first, np.load(tmp_path / "c" / "expval.npy"))
+    assert all(any(np.array_equal(r, e) for e in expval.numpy()) for r in first[:5])

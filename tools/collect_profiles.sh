@@ -8,7 +8,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $OUT/bench.log 2> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench_n1.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- \
   python3 $R/bench.py --steps 2 --warmup 1 --skip-aux --cpu-seconds 0.5 > $OUT/stats.log 2>&1

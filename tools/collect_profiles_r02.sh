@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-echo "[1] bench line"; python3 $R/bench.py > $OUT/bench.log 2> $OUT/bench.err
+echo "[1] bench line"; python3 $R/bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench_n1.json
 echo "[2] kernel stats of the headline command"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- \

@@ -63,7 +63,7 @@ python3 tools/accum_probe.py 2>/dev/null | grep -v amdgpu.ids > $OUT/${TAG}_accu
 python3 tools/configs_bench.py 2>/dev/null | grep "^|" > $OUT/${TAG}_configs.md || true
 echo "[9] bench line (after the traffic records: its roofline.traffic is the PMC figure of THIS tree)"
 cd /tmp
-python3 $R/bench.py > $OUT/bench.log 2> $OUT/bench.err
+python3 $R/bench.py --full > $OUT/bench.log 2> $OUT/bench.err
 tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench_n1.json
 head -c 600 $OUT/${TAG}_bench_n1.json; echo
 head -n 8 $OUT/${TAG}_bench_kernel_stats.csv | cut -c1-160

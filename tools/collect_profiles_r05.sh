@@ -125,7 +125,7 @@ if has ab; then
 fi
 if has bench; then
   echo "[bench] bench line (after the traffic records: its roofline.traffic is the PMC figure of THIS tree)"
-  python3 $R/bench.py > $OUT/bench.log 2> $OUT/bench.err
+  python3 $R/bench.py --full > $OUT/bench.log 2> $OUT/bench.err
   tail -n 1 $OUT/bench.log > $OUT/${TAG}_bench_n1.json
   python3 -c "import json,sys; d=json.load(open('$OUT/${TAG}_bench_n1.json')); print(json.dumps(d['summary'])[:3000])"
 fi
