@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define QMLE_SV_VERSION 149 /* 0.1.4.8: qmle_adjoint_gradient_f64, k_direct_1q controlled-phase mode; 0.1.4.7: qmle_plan_executed (qmle_plan_expval_child = the folded child only); 0.1.4.6: qmle_plan_autotune; 0.1.4.5: QMLE_MEAS_MEYER_WALLACH; 0.1.4.4: qmle_philox_uniform_f32_device_key; 0.1.4.3: qmle_philox_uniform_f32_device; 0.1.4.2: qmle_apply_inplace_f64; 0.1.4.1: qmle_philox_uniform_f32 (host-side parameter sampler); 0.1.4: complex128 engine (qmle_run_batch_f64), qmle_meyer_wallach_reads, QMLE_ERR_INTERNAL; 0.1.3: fast tile path (no ABI change; a plan is bound to the device of its first run); 0.1.2: shot sampler; 0.1.1: qmle_op carries 4 wires (MAT4) */
+#define QMLE_SV_VERSION 149 /* (no version step: qmle_gram, qmle_gram_f64 and their workspace queries added); 0.1.4.8: qmle_adjoint_gradient_f64, k_direct_1q controlled-phase mode; 0.1.4.7: qmle_plan_executed (qmle_plan_expval_child = the folded child only); 0.1.4.6: qmle_plan_autotune; 0.1.4.5: QMLE_MEAS_MEYER_WALLACH; 0.1.4.4: qmle_philox_uniform_f32_device_key; 0.1.4.3: qmle_philox_uniform_f32_device; 0.1.4.2: qmle_apply_inplace_f64; 0.1.4.1: qmle_philox_uniform_f32 (host-side parameter sampler); 0.1.4: complex128 engine (qmle_run_batch_f64), qmle_meyer_wallach_reads, QMLE_ERR_INTERNAL; 0.1.3: fast tile path (no ABI change; a plan is bound to the device of its first run); 0.1.2: shot sampler; 0.1.1: qmle_op carries 4 wires (MAT4) */
 #define QMLE_MAX_QUBITS 32
 
 typedef struct qmle_plan qmle_plan;
@@ -426,6 +426,27 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
                               int n_grad_slots, void *d_workspace, size_t workspace_bytes,
                               qmle_stream stream);
 size_t qmle_adjoint_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch);
+
+/* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
+ * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:
+ * d_out complex128, row-major [n_groups][rows_a][rows_b].  Row r of group g starts at amplitude
+ * g * group_stride_a + r * 2^n_qubits of d_a (strides in amplitudes).  d_a == d_b with equal rows and
+ * strides is the Hermitian case: only the upper block triangle is computed, the rest is its mirror,
+ * the diagonal is real.  qmle_gram reads complex64 rows (v_mfma_f32_32x32x2_f32 over sub-slices of
+ * 32 amplitudes, each added in fp64); qmle_gram_f64 complex128 rows (fp64 FMA).  Long rows are cut
+ * into chunks whose fp64 partials (the workspace; 0 bytes when one chunk covers a row) are added in
+ * chunk order: the result is the same bit for bit from call to call.  QMLE_ERR_INVALID_ARG, decided
+ * before any device work, for rows outside 1..4096, n_qubits outside 1..30, n_groups outside
+ * 1..65535, overlapping groups, complex64 rows not 16-byte aligned, or a workspace smaller than the
+ * query's answer. */
+int qmle_gram(const void *d_a, const void *d_b, int n_qubits, int n_groups, int rows_a, int rows_b,
+              int64_t group_stride_a, int64_t group_stride_b, void *d_out, void *d_ws, size_t ws_bytes,
+              qmle_stream stream);
+size_t qmle_gram_workspace_bytes(int n_qubits, int n_groups, int rows_a, int rows_b);
+int qmle_gram_f64(const void *d_a, const void *d_b, int n_qubits, int n_groups, int rows_a, int rows_b,
+                  int64_t group_stride_a, int64_t group_stride_b, void *d_out, void *d_ws, size_t ws_bytes,
+                  qmle_stream stream);
+size_t qmle_gram_workspace_bytes_f64(int n_qubits, int n_groups, int rows_a, int rows_b);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,10 @@ SYMBOLS = [
     ("qmle_probs_diag_expval", _I, [_VP, _I, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), _VP, _I, _VP, _VP, _SZ, _VP]),
     ("qmle_probs_diag_expval_workspace_bytes", _SZ, [_I]),
+    ("qmle_gram", _I, [_VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, _VP, _VP, _SZ, _VP]),
+    ("qmle_gram_workspace_bytes", _SZ, [_I, _I, _I, _I]),
+    ("qmle_gram_f64", _I, [_VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, _VP, _VP, _SZ, _VP]),
+    ("qmle_gram_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
 ]
 
 
@@ -799,6 +803,42 @@ def overlap(a, b):
     check(lib().qmle_overlap(C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, B,
                              C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), wsb,
                              _stream_ptr()), "qmle_overlap")
+    return out
+
+
+GRAM_MAX_GROUPS = 65535  # qmle_gram: one grid row per group
+
+
+def gram(a, b=None):
+    """Gram matrices of groups of resident states: ``G[g, r, s] = <a[g, r] | b[g, s]>`` for ``a``
+    ``[G, Ra, 2^n]`` and ``b`` ``[G, Rb, 2^n]`` (complex64 -> ``qmle_gram``, complex128 ->
+    ``qmle_gram_f64``); ``b=None`` is the Hermitian ``a^H a``.  Returns complex128 ``[G, Ra, Rb]`` on the
+    device.  The result is the same bit for bit from call to call."""
+    torch = require_gpu()
+    herm = b is None
+    if a.dtype not in (torch.complex64, torch.complex128) or not a.is_cuda or a.dim() != 3:
+        raise ValueError("gram: a must be a complex64 / complex128 CUDA tensor [groups, rows, 2^n]")
+    a = a.contiguous()
+    b = a if herm else b.contiguous()
+    if b.dtype != a.dtype or b.dim() != 3 or b.shape[0] != a.shape[0] or b.shape[2] != a.shape[2]:
+        raise ValueError("gram: a and b must agree in dtype, groups and state length")
+    G, Ra, D = (int(x) for x in a.shape)
+    Rb = int(b.shape[1])
+    n = D.bit_length() - 1
+    if 1 << n != D:
+        raise ValueError(f"gram: state length {D} is not a power of two")
+    f64 = a.dtype == torch.complex128
+    fn, wsq = ((lib().qmle_gram_f64, lib().qmle_gram_workspace_bytes_f64) if f64
+               else (lib().qmle_gram, lib().qmle_gram_workspace_bytes))
+    out = torch.empty((G, Ra, Rb), dtype=torch.complex128, device=a.device)
+    for g0 in range(0, G, GRAM_MAX_GROUPS):
+        gc = min(GRAM_MAX_GROUPS, G - g0)
+        wsb = int(wsq(n, gc, Ra, Rb))
+        ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=a.device)
+        pa, pb = a[g0:g0 + gc], b[g0:g0 + gc]
+        check(fn(C.c_void_p(pa.data_ptr()), C.c_void_p(pb.data_ptr()), n, gc, Ra, Rb, Ra * D, Rb * D,
+                 C.c_void_p(out[g0:g0 + gc].data_ptr()), C.c_void_p(ws.data_ptr()), wsb, _stream_ptr()),
+              "qmle_gram_f64" if f64 else "qmle_gram")
     return out
 
 

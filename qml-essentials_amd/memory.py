@@ -111,3 +111,21 @@ def execute_chunked(run: Callable[[int, int], np.ndarray], batch_size: int,
             out = np.empty((batch_size,) + part.shape[1:], dtype=part.dtype)
         out[start:end] = part
     return out
+
+
+def metric_plan(n_qubits: int, n_rows: int, n_points: int, x64: bool = False,
+                memory_fraction: float = 0.8, max_groups: int = 65535) -> Tuple[int, int]:
+    """Chunking of a quantum-geometric-tensor call (:meth:`script.Script.quantum_geometric_tensor`):
+    every parameter point needs ``n_rows`` states (the unshifted and the shifted circuits) resident for
+    its Gram matrix.  Returns ``(points per chunk, row block)``: when one point's rows fit in
+    ``memory_fraction`` of free HBM, ``row block == n_rows`` and as many points as fit (at most
+    ``max_groups``) share one engine call; otherwise the rows are split into blocks of ``row block``
+    rows, two of which (one block-pair Gram) fit at a time."""
+    state = (2**n_qubits) * (2 * COMPLEX_BYTES if x64 else COMPLEX_BYTES)
+    avail = int(available_memory_bytes() * memory_fraction)
+    per_point = estimate_peak_bytes(n_qubits, n_rows, "state", x64=x64) + n_rows * n_rows * 16
+    if per_point <= avail:
+        return max(1, min(n_points, max_groups, avail // per_point)), n_rows
+    block = max(1, min(n_rows, (avail // 2) // max(1, int(1.1 * state))))
+    log.info("One point's %d states do not fit in HBM; Gram matrix in row blocks of %d.", n_rows, block)
+    return 1, block

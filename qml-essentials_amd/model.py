@@ -677,6 +677,45 @@ class Model:
             jac = jac.mean(axis=len([d for d in self.eff_batch_shape if d != 1]))
         return jac
 
+    def quantum_geometric_tensor(self, params=None, inputs=None, enc_params=None,
+                                 row_block=None) -> np.ndarray:
+        """Quantum geometric tensor of the model's state with respect to ``params`` at fixed
+        ``inputs`` / ``enc_params`` (:meth:`script.Script.quantum_geometric_tensor`): arguments and
+        batching of :meth:`gradient`, shape ``(*eff_batch_shape, P, P)`` with ``P = params[0].size``
+        (batch axes of size 1 dropped).  A model with noise returns the mixed-state QFI / 4 (real)."""
+        from .utils import x64_enabled, x64_scope
+
+        if self.x64 is not None and bool(self.x64) != x64_enabled():
+            with x64_scope(self.x64):
+                return self.quantum_geometric_tensor(params, inputs, enc_params, row_block)
+        params = self._params_validation(params)
+        inputs = self._inputs_validation(inputs)
+        enc_params = self._enc_params_validation(enc_params)
+        inputs, params = self._assimilate_batch(inputs, params)
+        B = int(np.prod(self.eff_batch_shape))
+        args = (params, inputs, None, None, np.asarray(enc_params, dtype=np.float64))
+        in_axes = (0 if self.batch_shape[1] > 1 else None, 0 if self.batch_shape[0] > 1 else None,
+                   None, None, None)
+        kwargs = dict(noise_params=self.noise_params, gate_mode="unitary")
+        q = self.script.quantum_geometric_tensor(args=args, kwargs=kwargs, in_axes=in_axes if B > 1 else None,
+                                                 argnums=(0,), row_block=row_block)
+        q = np.asarray(q).reshape(*self.eff_batch_shape, *q.shape[-2:])
+        return q.reshape([d for i, d in enumerate(q.shape)
+                          if not (i < len(self.eff_batch_shape) and d == 1)])
+
+    def fubini_study_metric(self, params=None, inputs=None, enc_params=None) -> np.ndarray:
+        """Fubini-Study metric ``Re Q`` of the model's pure state (:meth:`quantum_geometric_tensor`);
+        ``ValueError`` for a model with noise (the metric is defined for pure states only)."""
+        if self.noise_params is not None and any(v for v in dict(self.noise_params).values()):
+            raise ValueError("The Fubini-Study metric is only defined for pure states; this model has noise")
+        return np.real(self.quantum_geometric_tensor(params, inputs, enc_params))
+
+    def quantum_fisher_information(self, params=None, inputs=None, enc_params=None) -> np.ndarray:
+        """Quantum Fisher information with respect to ``params``: ``4 Re Q`` of the pure state, or the
+        symmetric-logarithmic-derivative QFI of the density matrix when the model has noise.  Shape
+        ``(*eff_batch_shape, P, P)`` as in :meth:`quantum_geometric_tensor`."""
+        return 4.0 * np.real(self.quantum_geometric_tensor(params, inputs, enc_params))
+
     def record_tape(self, params=None, inputs=None, enc_params=None):
         """Validate + batch the arguments exactly like ``__call__`` and return
         ``(tape, batch)`` without executing (host only; used by tests and tools)."""
@@ -701,10 +740,16 @@ class Model:
     def __call__(self, params=None, inputs=None, pulse_params=None, enc_params=None,
                  data_reupload=None, noise_params=None, execution_type: Optional[str] = None,
                  force_mean: bool = False, gate_mode: str = "unitary") -> np.ndarray:
-        return self._forward(params=params, inputs=inputs, pulse_params=pulse_params,
-                             enc_params=enc_params, data_reupload=data_reupload,
-                             noise_params=noise_params, execution_type=execution_type,
-                             force_mean=force_mean, gate_mode=gate_mode)
+        from .tape import captured_call
+
+        with captured_call(lambda: dict(kind="model", model=self, params=params, inputs=inputs,
+                                        enc_params=enc_params, noise_params=noise_params,
+                                        type=self.execution_type, force_mean=force_mean)) as cap:
+            cap["result"] = self._forward(params=params, inputs=inputs, pulse_params=pulse_params,
+                                          enc_params=enc_params, data_reupload=data_reupload,
+                                          noise_params=noise_params, execution_type=execution_type,
+                                          force_mean=force_mean, gate_mode=gate_mode)
+        return cap["result"]
 
     # ------------------------------------------------------------------ device-resident path
     @staticmethod

@@ -276,6 +276,14 @@ class Script:
                 args: tuple = (), kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
                 shots: Optional[int] = None, key=None, as_tensor: bool = False):
         """Execute the circuit; with ``in_axes`` the result has a leading batch axis."""
+        from .tape import captured_call
+
+        with captured_call(lambda: dict(kind="script", script=self, type=type, obs=obs, args=args,
+                                        kwargs=kwargs, in_axes=in_axes, shots=shots)) as cap:
+            cap["result"] = self._execute(type, obs, args, kwargs, in_axes, shots, key, as_tensor)
+        return cap["result"]
+
+    def _execute(self, type, obs, args, kwargs, in_axes, shots, key, as_tensor):
         obs = [] if obs is None else obs
         kwargs = {} if kwargs is None else kwargs
         if shots is not None and key is None:
@@ -360,10 +368,12 @@ class Script:
                  (-3 * np.pi / 2, (np.sqrt(2) - 1) / (4 * np.sqrt(2)))),
     }
 
-    def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums):
+    def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums, skip_channels: bool = False):
         """Record the tape with the ``argnums`` arguments as differentiable leaves.  Returns
         ``(tape, lowered tape, n_qubits, B, slots, leaf_shapes, batched)`` where ``slots`` lists
-        ``(angle slot, shift rule, tangent terms)`` for every angle that depends on a leaf."""
+        ``(angle slot, shift rule, tangent terms)`` for every angle that depends on a leaf.
+        ``skip_channels``: noise channels stay on the returned tape but take no part in the lowered
+        tape and the slot numbering (the mixed-state QFI)."""
         kwargs = {} if kwargs is None else kwargs
         args = tuple(to_numpy(a) for a in args)
         batched = in_axes is not None
@@ -391,11 +401,12 @@ class Script:
                 wrapped.append(a)
         tape = self._record(*wrapped, **kwargs)
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
-        low = simulation.LoweredTape(tape, n_qubits)
+        gates = [o for o in tape if not isinstance(o, KrausChannel)] if skip_channels else tape
+        low = simulation.LoweredTape(gates, n_qubits)
 
         # differentiable slots: (slot, rule, tangent terms)
         slots, s = [], 0
-        for op_ in tape:
+        for op_ in gates:
             lowered = op_.lower(n_qubits)
             if lowered is None:
                 continue
@@ -502,6 +513,183 @@ class Script:
                     g = grads[lid].reshape(B, len(obs), -1)
                     g[:, :, flat] += d * np.asarray(coef).reshape(-1, 1)
         out = tuple(grads[k] if batched else grads[k][0] for k in argnums)
+        return out
+
+    # ------------------------------------------------------------------ quantum geometric tensor
+    # State rules (operators, not expectation values):  dU/dtheta = sum_k coef_k U(theta + shift_k).
+    # Pauli rotations exp(-i theta G / 2), G^2 = I (RX/RY/RZ, Rot's factors, PauliRot, RXX/RYY/RZZ/RZX):
+    # U(theta + pi) = -sin(theta/2) - i cos(theta/2) G = 2 dU/dtheta.  Controlled rotations: the target block
+    # is a Pauli rotation and U(theta - pi) flips its sign only there.  CPhase: diag(.., e^{i phi}).
+    _STATE_RULES = {
+        "pauli": ((np.pi, 0.5),),
+        "controlled": ((np.pi, 0.25), (-np.pi, -0.25)),
+        "phase": ((np.pi / 2, 0.5), (-np.pi / 2, -0.5)),
+    }
+
+    @staticmethod
+    def state_rule(op_name: str, shift_rule: Optional[str]) -> str:
+        """Which entry of ``_STATE_RULES`` differentiates the state through a gate (``NotImplementedError``
+        for a gate without one)."""
+        if op_name in ("ControlledPhaseShift", "CPhase"):
+            return "phase"
+        if shift_rule == "four":
+            return "controlled"
+        if shift_rule == "two":
+            return "pauli"
+        raise NotImplementedError(f"{op_name}: no state derivative rule (quantum geometric tensor)")
+
+    @staticmethod
+    def fold_qgt(coef, gram):
+        """``Q = C Gamma C^T - (C Gamma)_{:,0} (C Gamma)_{:,0}^H`` for real ``coef`` ``(B, P, R+1)`` and
+        the Gram matrices ``gram`` ``(B, R+1, R+1)`` of the rows (row 0 = the unshifted state), fp64."""
+        coef = np.asarray(coef, dtype=np.float64)
+        gram = np.asarray(gram, dtype=np.complex128)
+        # real products of Re / Im, one point at a time (np.dot: BLAS, where a stacked complex matmul is not)
+        cg = np.empty(gram.shape[:1] + coef.shape[1:], dtype=np.complex128)
+        m = np.empty(coef.shape[:2] + coef.shape[1:2], dtype=np.complex128)
+        for b in range(coef.shape[0]):
+            cre, cim = np.dot(coef[b], gram[b].real), np.dot(coef[b], gram[b].imag)
+            cg[b] = cre + 1j * cim
+            m[b] = np.dot(cre, coef[b].T) + 1j * np.dot(cim, coef[b].T)
+        v = cg[:, :, 0]
+        return m - v[:, :, None] * np.conj(v)[:, None, :]
+
+    def _qgt_rows(self, tape, low, n_qubits, B, slots, leaf_shapes, argnums, mixed: bool = False):
+        """The shifted angle table ``(B, R+1, n_slots)`` (row 0 unshifted) and the fold coefficients
+        ``(B, P, R+1)``; ``mixed`` uses the expectation-value rules (they hold for rho itself)."""
+        from .utils import x64_enabled
+
+        base = low.angle_table(B, dtype=np.float64) if x64_enabled() else low.angle_table(B).astype(np.float64)
+        offsets, P = {}, 0
+        for k in argnums:
+            offsets[k] = P
+            P += int(np.prod(leaf_shapes[k])) if k in leaf_shapes else 0
+        shifts, terms = [], []  # per row: (slot, shift); per row: [(column of C, coef (B,))]
+        for slot, rule_name, tangent, op_name in slots:
+            if mixed:
+                if rule_name is None:
+                    raise NotImplementedError(f"{op_name} has no parameter-shift rule")
+                rule = self._SHIFT_RULES[rule_name]
+            else:
+                rule = self._STATE_RULES[self.state_rule(op_name, rule_name)]
+            for shift, c in rule:
+                shifts.append((slot, shift))
+                terms.append([(offsets[lid] + int(flat), c * np.broadcast_to(np.asarray(tc, dtype=np.float64),
+                                                                          (B,)))
+                              for lid, flat, tc in tangent if lid in offsets])
+        R1 = len(shifts) + 1
+        table = np.repeat(base[:, None, :], R1, axis=1)
+        coef = np.zeros((B, P, R1))
+        for r, ((slot, shift), tt) in enumerate(zip(shifts, terms), start=1):
+            table[:, r, slot] += shift
+            for col, c in tt:
+                coef[:, col, r] += c
+        return table, coef
+
+    def quantum_geometric_tensor(self, *, args: tuple = (), kwargs: Optional[dict] = None,
+                                 in_axes: Optional[Tuple] = None, argnums: Tuple[int, ...] = (0,),
+                                 row_block: Optional[int] = None):
+        """Quantum geometric tensor ``Q_ij = <d_i psi|d_j psi> - <d_i psi|psi><psi|d_j psi>`` of the
+        circuit's output state with respect to the flattened ``argnums`` arguments (the order of
+        :meth:`gradient`); ``Re Q`` is the Fubini-Study metric, ``4 Re Q`` the quantum Fisher information.
+
+        Every derivative state is a fixed real combination of shifted circuits (``_STATE_RULES``), so one
+        engine call runs the unshifted and the shifted rows of every point, ``qmle_gram`` forms their Gram
+        matrix ``Gamma = S^H S`` on the device and the fold ``C Gamma C^T`` (``fold_qgt``) runs on the host.
+        Noisy (density) tapes return the mixed-state QFI ``/ 4`` as a real tensor (:func:`math._qfi_density`
+        on ``d rho`` from the expectation-value shift rules, at most 7 qubits).
+
+        Returns complex ``(B, P, P)`` (no ``B`` axis without ``in_axes``).  ``row_block`` forces the split
+        of each point's rows into blocks of that many (the path taken when one point's states exceed
+        free HBM, :func:`memory.metric_plan`)."""
+        tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
+            [], args, kwargs, in_axes, argnums, skip_channels=True)
+        if any(isinstance(o, KrausChannel) for o in tape):
+            q = self._qfi_mixed(tape, low, n_qubits, B, slots, leaf_shapes, argnums) / 4.0
+            return q if batched else q[0]
+        from .utils import x64_enabled
+
+        x64 = x64_enabled()
+        torch = N.require_gpu()
+        table, coef = self._qgt_rows(tape, low, n_qubits, B, slots, leaf_shapes, argnums)
+        R1 = table.shape[1]
+        if x64:
+            plan = simulation.get_plan(low, (simulation.PLAN_FLAGS or 0) | N.PLAN_NO_MERGE)
+        else:
+            plan = simulation.get_plan(low)
+
+        def states(rows):  # rows of the angle table -> [len(rows), 2^n] states on the device
+            rows = np.ascontiguousarray(rows)
+            if x64:
+                return plan.run64(torch.from_numpy(rows).cuda(), "state")
+            return plan.run(torch.from_numpy(rows.astype(np.float32)).cuda(), "state")
+
+        chunk, block = memory.metric_plan(n_qubits, R1, B, x64=x64)
+        if row_block is not None:
+            block, chunk = max(1, min(int(row_block), R1)), 1 if int(row_block) < R1 else chunk
+        gram = np.empty((B, R1, R1), dtype=np.complex128)
+        D = 1 << n_qubits
+        if block >= R1:
+            for b0 in range(0, B, chunk):
+                b1 = min(B, b0 + chunk)
+                s = states(table[b0:b1].reshape(-1, table.shape[2]))
+                gram[b0:b1] = N.to_host(N.gram(s.reshape(b1 - b0, R1, D)))
+                del s
+        else:
+            cuts = list(range(0, R1, block)) + [R1]
+            for b in range(B):
+                for I in range(len(cuts) - 1):
+                    i0, i1 = cuts[I], cuts[I + 1]
+                    si = states(table[b, i0:i1]).reshape(1, i1 - i0, D)
+                    gram[b, i0:i1, i0:i1] = N.to_host(N.gram(si))[0]
+                    for J in range(I + 1, len(cuts) - 1):
+                        j0, j1 = cuts[J], cuts[J + 1]
+                        sj = states(table[b, j0:j1]).reshape(1, j1 - j0, D)
+                        g = N.to_host(N.gram(si, sj))[0]
+                        gram[b, i0:i1, j0:j1] = g
+                        gram[b, j0:j1, i0:i1] = np.conj(g.T)
+                        del sj
+                    del si
+        q = self.fold_qgt(coef, gram)
+        return q if batched else q[0]
+
+    def _qfi_mixed(self, tape, low, n_qubits, B, slots, leaf_shapes, argnums):
+        """QFI ``(B, P, P)`` of the output density matrix of a noisy tape: ``rho`` and every shifted
+        ``rho`` from one run of the density engine, ``d_i rho = sum_r C_ir rho_r``, then the SLD formula."""
+        from . import math as qmath
+        from .utils import x64_enabled
+
+        if n_qubits > qmath.MAX_MIXED_QFI_QUBITS:
+            raise ValueError(f"the mixed-state QFI is computed on the host from eigh(rho): at most "
+                             f"{qmath.MAX_MIXED_QFI_QUBITS} qubits (got {n_qubits})")
+        table, coef = self._qgt_rows(tape, low, n_qubits, B, slots, leaf_shapes, argnums, mixed=True)
+        R1 = table.shape[1]
+        rows = table.reshape(B * R1, -1)  # (b, r) row-major
+        # the recorded tape with every angle slot replaced by its column of the shifted table
+        shifted, s = [], 0
+        import copy
+
+        for op_ in tape:
+            lowered = op_.lower(n_qubits) if not isinstance(op_, KrausChannel) else None
+            new = copy.copy(op_)
+            if lowered is not None:
+                if "_tangents" in op_.__dict__:
+                    new._tangents = dict(op_._tangents)
+                for j in range(len(lowered[2])):
+                    new._store_param(op_._param_names[j], Batched(rows[:, s].copy(), []))
+                    s += 1
+            elif isinstance(op_, KrausChannel):
+                for name in getattr(op_, "_param_names", ()):
+                    v = getattr(op_, name, None)
+                    if isinstance(v, np.ndarray) and v.ndim and v.shape[0] == B:
+                        setattr(new, name, np.repeat(v, R1, axis=0))
+            shifted.append(new)
+        rho = simulation._simulate_mixed(shifted, n_qubits, "density", [], B * R1, x64=x64_enabled())
+        rho = np.asarray(N.to_host(rho), dtype=np.complex128).reshape(B, R1, 2**n_qubits, 2**n_qubits)
+        out = np.empty((B, coef.shape[1], coef.shape[1]))
+        for b in range(B):
+            drho = np.einsum("pr,rkl->klp", coef[b], rho[b])
+            out[b] = qmath._qfi_density(drho, rho[b, 0])
         return out
 
     def draw(self, *a, **k):

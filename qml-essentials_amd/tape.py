@@ -79,3 +79,54 @@ def batch_context(batch: int) -> Iterator[None]:
 
 def current_batch() -> int:
     return getattr(_tls, "batch", 1)
+
+
+# ---- call capture (math.quantum_fisher_information / fubini_study_metric) -------------------------
+# While a capture is open on this thread, every top-level Model.__call__ / Script.execute appends one
+# record (a dict with "kind", the callee, its arguments and its result); calls made from inside another
+# recorded call are not recorded again.
+
+
+def _captures() -> list:
+    st = getattr(_tls, "captures", None)
+    if st is None:
+        st = _tls.captures = []
+    return st
+
+
+@contextmanager
+def capturing() -> Iterator[list]:
+    """Collect the records of the calls made inside the block (innermost capture only)."""
+    st = _captures()
+    rec: list = []
+    st.append(rec)
+    depth, _tls.capture_depth = getattr(_tls, "capture_depth", 0), 0
+    try:
+        yield rec
+    finally:
+        _tls.capture_depth = depth
+        while st and st[-1] is not rec:
+            st.pop()
+        if st:
+            st.pop()
+
+
+@contextmanager
+def captured_call(make_record: Callable[[], dict]) -> Iterator[dict]:
+    """Around one Model.__call__ / Script.execute: yields a dict the caller puts ``result`` into; the
+    record is appended to the open capture when this call is not nested in another recorded one."""
+    st = _captures()
+    if not st:
+        yield {}
+        return
+    depth = getattr(_tls, "capture_depth", 0)
+    _tls.capture_depth = depth + 1
+    out: dict = {}
+    try:
+        yield out
+    finally:
+        _tls.capture_depth = depth
+    if depth == 0 and "result" in out:
+        rec = make_record()
+        rec["result"] = out["result"]
+        st[-1].append(rec)
