@@ -338,25 +338,36 @@ k_mw_final(const float4 *__restrict__ partial, int n, int n_blocks, int batch,
   if (threadIdx.x == 0) out[b] = (float)(2.0 * (1.0 - sum / n));
 }
 
-// numpy.histogram's bin of v over linspace(lo, hi, n_bins + 1), last bin right-inclusive; -1 = dropped
-__device__ __forceinline__ int hist_bin(float v, int n_bins, float lo, float hi) {
+// Edge k of np.linspace(lo, hi, n_bins + 1) in float64, rounding for rounding: fl(fl(k * step) + lo),
+// step = fl((hi - lo) / n_bins) (computed on the host), the last edge hi itself.  Separate rounded
+// product and sum: an FMA would round once and move the edge.  (__dmul_rn / __dadd_rn are a plain
+// * and + in this HIP build, which -ffp-contract=fast fuses; the pragma keeps them apart.)
+__device__ __forceinline__ double hist_edge(int k, int n_bins, double lo, double hi, double step) {
+#pragma clang fp contract(off)
+  const double prod = (double)k * step;
+  return k == n_bins ? hi : prod + lo;
+}
+
+// numpy.histogram's bin of v over linspace(lo, hi, n_bins + 1) (float64 edges), last bin
+// right-inclusive; -1 = dropped.  A float32 estimate, then moved until the float64 edges agree: a
+// float32 value just below a float64 edge can round onto the float32 edge.
+__device__ __forceinline__ int hist_bin(float v, int n_bins, float lo, float hi, double step) {
   if (!(v >= lo) || !(v <= hi)) return -1;  // numpy drops out-of-range and NaN
   const float scale = (float)n_bins / (hi - lo);
   int bin = (int)((v - lo) * scale);
-  if (bin >= n_bins) bin = n_bins - 1;     // right edge inclusive
-  // guard against rounding across an edge: edges are lo + k*(hi-lo)/n_bins
-  const float w = (hi - lo) / (float)n_bins;
-  if (bin > 0 && v < lo + bin * w) --bin;
-  else if (bin < n_bins - 1 && v >= lo + (bin + 1) * w) ++bin;
+  bin = bin < 0 ? 0 : bin >= n_bins ? n_bins - 1 : bin;  // right edge inclusive
+  const double x = v, dlo = lo, dhi = hi;
+  while (bin > 0 && x < hist_edge(bin, n_bins, dlo, dhi, step)) --bin;
+  while (bin < n_bins - 1 && x >= hist_edge(bin + 1, n_bins, dlo, dhi, step)) ++bin;
   return bin;
 }
 
 __global__ void __launch_bounds__(256)
-k_histogram(const float *__restrict__ values, int64_t count, int n_bins, float lo, float hi,
+k_histogram(const float *__restrict__ values, int64_t count, int n_bins, float lo, float hi, double step,
             int *__restrict__ counts) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-    const int bin = hist_bin(values[i], n_bins, lo, hi);
+    const int bin = hist_bin(values[i], n_bins, lo, hi, step);
     if (bin >= 0) atomicAdd(counts + bin, 1);
   }
 }
@@ -366,7 +377,7 @@ k_histogram(const float *__restrict__ values, int64_t count, int n_bins, float l
 // workgroup (SOLO, counts up to 2^16 values): the bins are stored, not added -- no memset launch.
 template <bool SOLO>
 __global__ void __launch_bounds__(1024)
-k_histogram_lds(const float *__restrict__ values, int64_t count, int n_bins, float lo, float hi,
+k_histogram_lds(const float *__restrict__ values, int64_t count, int n_bins, float lo, float hi, double step,
                 int *__restrict__ counts) {
   extern __shared__ float4 smem4[];
   int *bins = reinterpret_cast<int *>(smem4);
@@ -374,7 +385,7 @@ k_histogram_lds(const float *__restrict__ values, int64_t count, int n_bins, flo
   __syncthreads();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
-    const int bin = hist_bin(values[i], n_bins, lo, hi);
+    const int bin = hist_bin(values[i], n_bins, lo, hi, step);
     if (bin >= 0) atomicAdd(bins + bin, 1);
   }
   __syncthreads();
@@ -1864,10 +1875,11 @@ int qmle_histogram(const float *d_values, int64_t count, int n_bins, float lo, f
                    int32_t *d_counts, qmle_stream stream_) {
   if (!d_values || !d_counts || count < 0 || n_bins < 1 || !(hi > lo)) return QMLE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
+  const double step = ((double)hi - (double)lo) / n_bins;  // np.linspace's step (hist_edge)
   if (n_bins <= 4096 && count > 0 && count <= (1 << 16)) {  // one workgroup, one launch
     const int threads = count >= 1024 ? 1024 : count >= 256 ? 256 : 64;
     hipLaunchKernelGGL(k_histogram_lds<true>, dim3(1), dim3(threads), (size_t)n_bins * sizeof(int), stream,
-                       d_values, count, n_bins, lo, hi, d_counts);
+                       d_values, count, n_bins, lo, hi, step, d_counts);
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
@@ -1875,10 +1887,10 @@ int qmle_histogram(const float *d_values, int64_t count, int n_bins, float lo, f
   if (count > 0) {
     if (n_bins <= 4096)
       hipLaunchKernelGGL(k_histogram_lds<false>, dim3(grid_for((uint64_t)count, 1024 * 16, 1024)), dim3(1024),
-                         (size_t)n_bins * sizeof(int), stream, d_values, count, n_bins, lo, hi, d_counts);
+                         (size_t)n_bins * sizeof(int), stream, d_values, count, n_bins, lo, hi, step, d_counts);
     else
       hipLaunchKernelGGL(k_histogram, dim3(grid_for((uint64_t)count, 256, 1024)), dim3(256), 0,
-                         stream, d_values, count, n_bins, lo, hi, d_counts);
+                         stream, d_values, count, n_bins, lo, hi, step, d_counts);
   }
   HIPCHK(hipGetLastError());
   return QMLE_OK;
