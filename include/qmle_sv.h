@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define QMLE_SV_VERSION 149 /* (no version step: qmle_gram, qmle_gram_f64 and their workspace queries added); 0.1.4.8: qmle_adjoint_gradient_f64, k_direct_1q controlled-phase mode; 0.1.4.7: qmle_plan_executed (qmle_plan_expval_child = the folded child only); 0.1.4.6: qmle_plan_autotune; 0.1.4.5: QMLE_MEAS_MEYER_WALLACH; 0.1.4.4: qmle_philox_uniform_f32_device_key; 0.1.4.3: qmle_philox_uniform_f32_device; 0.1.4.2: qmle_apply_inplace_f64; 0.1.4.1: qmle_philox_uniform_f32 (host-side parameter sampler); 0.1.4: complex128 engine (qmle_run_batch_f64), qmle_meyer_wallach_reads, QMLE_ERR_INTERNAL; 0.1.3: fast tile path (no ABI change; a plan is bound to the device of its first run); 0.1.2: shot sampler; 0.1.1: qmle_op carries 4 wires (MAT4) */
+#define QMLE_SV_VERSION 150 /* 0.1.4.9: plan flag 16 reserved (the prefetching tile kernel is gone), qmle_plan_create rejects it; (no version step: qmle_gram, qmle_gram_f64 and their workspace queries added); 0.1.4.8: qmle_adjoint_gradient_f64, k_direct_1q controlled-phase mode; 0.1.4.7: qmle_plan_executed (qmle_plan_expval_child = the folded child only); 0.1.4.6: qmle_plan_autotune; 0.1.4.5: QMLE_MEAS_MEYER_WALLACH; 0.1.4.4: qmle_philox_uniform_f32_device_key; 0.1.4.3: qmle_philox_uniform_f32_device; 0.1.4.2: qmle_apply_inplace_f64; 0.1.4.1: qmle_philox_uniform_f32 (host-side parameter sampler); 0.1.4: complex128 engine (qmle_run_batch_f64), qmle_meyer_wallach_reads, QMLE_ERR_INTERNAL; 0.1.3: fast tile path (no ABI change; a plan is bound to the device of its first run); 0.1.2: shot sampler; 0.1.1: qmle_op carries 4 wires (MAT4) */
 #define QMLE_MAX_QUBITS 32
 
 typedef struct qmle_plan qmle_plan;
@@ -136,7 +136,7 @@ typedef enum qmle_meas {
 #define QMLE_PLAN_FORCE_GLOBAL 2u   /* never use the whole-state-in-LDS kernel        */
 #define QMLE_PLAN_FORCE_TILE 4u     /* never use the direct per-gate kernels          */
 #define QMLE_PLAN_NO_REGTILE 8u     /* one LDS sweep per gate inside a tile (debug/A-B) */
-#define QMLE_PLAN_PREFETCH 16u      /* experiment: double-buffered LDS-DMA tile kernel (slower) */
+                                    /* 16u: reserved -- qmle_plan_create returns QMLE_ERR_INVALID_ARG */
 #define QMLE_PLAN_NO_MERGE 64u      /* keep every 1-qubit gate its own operator (no RY.RZ.RY products):
                                        the fused adjoint sweep needs one generator per gate */
 #define QMLE_PLAN_NO_ABSORB 32u     /* <Z>: simulate trailing CX / SWAP / diagonal gates instead of

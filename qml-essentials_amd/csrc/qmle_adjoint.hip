@@ -65,7 +65,7 @@ __global__ void k_adjoint_lds(const AdjLdsArgs a) {
   __syncthreads();
   if (tid == 0) psi[sw(0)] = make_float2(1.f, 0.f);
   __syncthreads();
-  tile_compute<DENSE4, false>(a.fwd, psi, slots, b);
+  tile_compute<DENSE4>(a.fwd, psi, slots, b);
 
   const float *w = a.weights + (size_t)b * a.n_obs;
   for (uint32_t i = tid; i < cnt; i += nt) {
@@ -442,8 +442,7 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
     if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
 
   // ---- n <= 13: psi and lambda both fit in one workgroup's LDS -> a single launch ----------
-  static const bool lds_off = std::getenv("QMLE_ADJOINT_NO_LDS") != nullptr;  // A/B switch
-  bool lds_ok = !lds_off && fwd->whole_state_lds && n <= 13 && fwd->stages.size() == 1;
+  bool lds_ok = fwd->whole_state_lds && n <= 13 && fwd->stages.size() == 1;
   for (const LoweredOp &o : rev->lowered) lds_ok = lds_ok && o.kind != LK_4Q;
   if (lds_ok) {
     rc = ensure_device_plan(fwd);

@@ -1466,9 +1466,7 @@ static MwPlan mw_plan(int n, int batch) {
     while (q < want && (((uint64_t)batch * tiles) >> (q + 1)) >= 2048) ++q;
     return q;
   };
-  static const int q_env = std::getenv("QMLE_MW_Q") ? atoi(std::getenv("QMLE_MW_Q")) : -1;
   pl.q_first = pick_q(4);
-  if (q_env >= 0 && q_env <= 4 && (tiles >> q_env) >= 1) pl.q_first = q_env;
   pl.rows_first = tiles >> pl.q_first;
   int chunks[8], nc = 0;
   for (int c = kMwT; c < n; c += 4) chunks[nc++] = c + 4 <= n ? c : n - 4;
@@ -1485,7 +1483,6 @@ static MwPlan mw_plan(int n, int batch) {
     pl.lo[r] = a;
     pl.lo2[r] = b;
     pl.q[r] = pick_q(2);
-    if (q_env >= 0 && q_env <= 4 && (tiles >> q_env) >= 1) pl.q[r] = q_env < 2 ? q_env : 2;
     pl.rows_later[r] = tiles >> pl.q[r];
     for (int k = 0; k < 8; ++k) {
       const int p = k < 4 ? a + k : b + k - 4;
@@ -1509,7 +1506,6 @@ struct MwCover {
   int src_read[QMLE_MAX_QUBITS], src_col[QMLE_MAX_QUBITS];
   bool ok = true;
 };
-constexpr int kMwCoverPairing = 1;  // measured at n = 28 behind the K2-style last tile {0..6, 23..27}: 0.792 ms after the circuit (0: 0.801, 2: 0.801; profiles/r05_mw_pairing_nt.txt)
 static MwCover mw_cover(int n, uint32_t tile_mask, int batch) {
   MwCover cv;
   for (int p = 0; p < n; ++p) cv.src_read[p] = cv.src_col[p] = -1;
@@ -1529,14 +1525,10 @@ static MwCover mw_cover(int n, uint32_t tile_mask, int batch) {
     while (q < want && (((uint64_t)batch * tiles) >> (q + 1)) >= 2048) ++q;
     return q;
   };
-  // (four runs: which two share a read decides how the read streams -- tools/mw_lean_ab.py with QMLE_MW_PAIRING=0/1/2:
-  // 0 = outermost with innermost (the stand-alone reads' rule), 1 = neighbours, 2 = alternate)
-  if (nc == 4) {
-    const char *e = std::getenv("QMLE_MW_PAIRING");
-    const int mode = e ? atoi(e) : kMwCoverPairing;
-    if (mode == 1) std::swap(chunks[1], chunks[3]);        // (0,1) (2,3): loop pairs (c0,c3') = (0,1), (c1',c2) = (3,2)
-    else if (mode == 2) std::swap(chunks[2], chunks[3]);   // (0,2) (1,3)
-  }
+  // (four runs: which two share a read decides how the read streams.  Neighbours share one: measured at n = 28 behind
+  // the K2-style last tile {0..6, 23..27}, 0.792 ms after the circuit against 0.801 for outermost with innermost (the
+  // stand-alone reads' rule) or alternate runs, profiles/r05_mw_pairing_nt.txt)
+  if (nc == 4) std::swap(chunks[1], chunks[3]);  // (0,1) (2,3): loop pairs (c0,c3') = (0,1), (c1',c2) = (3,2)
   int i = 0, j = nc - 1;
   while (i <= j) {
     int a = chunks[i], b = i < j ? chunks[j] : -1;
@@ -1675,10 +1667,9 @@ int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int 
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
-  static const bool old_purity = std::getenv("QMLE_MW_OLD_PURITY") != nullptr;  // (A/B: the per-position walk)
   int colsum_w0 = kMwFusedRowA + (n - last.T - pa.lg > 0 ? n - last.T - pa.lg : 0), colsum_w = colsum_w0;
   for (int r = 0; r < 8 && pa.later[r]; ++r) colsum_w += (int)pa.later_stride[r];
-  if (last.T < n && !old_purity && 3 * last.T + 5 <= kMwFusedRowA && colsum_w0 <= 64 && colsum_w <= kMwColsMax) {
+  if (last.T < n && 3 * last.T + 5 <= kMwFusedRowA && colsum_w0 <= 64 && colsum_w <= kMwColsMax) {
     MwColsumArgs ca;
     std::memset(&ca, 0, sizeof(ca));
     uint32_t most = pa.rows_first;
@@ -1807,15 +1798,8 @@ int qmle_meyer_wallach(const void *d_states, int n_qubits, int batch, float *d_o
     // packed fmas + the population butterfly per 16 amplitudes) and is the one that suffers when
     // it starts on a chip that has just idled through the tiny reduction kernels of a previous
     // call (0.33 ms warm, 0.42 - 0.47 ms cold at n = 28); the later reads are bound by HBM
-    // alone.  So it runs LAST (QMLE_MW_FIRST_FIRST=1 for the A/B).
-    static const bool first_first = std::getenv("QMLE_MW_FIRST_FIRST") != nullptr;
-    auto launch_first = [&]() {
-      const dim3 grid(tiles >> a.q, batch);
-      if (nt) hipLaunchKernelGGL(k_mw_read_first<true>, grid, dim3(kMwThreads), lds, stream, a);
-      else hipLaunchKernelGGL(k_mw_read_first<false>, grid, dim3(kMwThreads), lds, stream, a);
-    };
+    // alone.  So it runs LAST.
     const MwReadArgs a_first = a;
-    if (first_first || pl.n_later == 0) launch_first();
     for (int r = 0; r < pl.n_later; ++r) {
       a.rows = ws;
       a.lo = pl.lo[r];
@@ -1828,9 +1812,10 @@ int qmle_meyer_wallach(const void *d_states, int n_qubits, int batch, float *d_o
       if (nt) hipLaunchKernelGGL(k_mw_read_later<true>, grid, dim3(kMwThreads), lds, stream, a);
       else hipLaunchKernelGGL(k_mw_read_later<false>, grid, dim3(kMwThreads), lds, stream, a);
     }
-    if (!first_first && pl.n_later > 0) {
-      a = a_first;
-      launch_first();
+    {
+      const dim3 grid(tiles >> a_first.q, batch);
+      if (nt) hipLaunchKernelGGL(k_mw_read_first<true>, grid, dim3(kMwThreads), lds, stream, a_first);
+      else hipLaunchKernelGGL(k_mw_read_first<false>, grid, dim3(kMwThreads), lds, stream, a_first);
     }
     for (int p = 0; p < n; ++p) { pa.src_read[p] = (int8_t)pl.src_read[p]; pa.src_col[p] = (int8_t)pl.src_col[p]; }
     float *d_pur = ws;

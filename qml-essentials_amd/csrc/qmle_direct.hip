@@ -252,13 +252,10 @@ k_init_zero(float4 *__restrict__ states, int n) {
 // zeros).  ONE plain store per thread and no loop: 6.79 TB/s on 4 GiB; four stores per thread
 // 6.29, sixteen 5.71, a grid-stride loop 5.35, hipMemsetAsync 6.59, non-temporal stores a little
 // below each (tools/fill_bench.hip) -- and one workgroup per 32 KiB tile inside k_tile2 6.0.
-template <bool NT>
 __global__ void __launch_bounds__(256) k_fill_zero(float4 *__restrict__ p, uint64_t count) {
   const uint64_t k = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (k < count) st4<NT>(p + k, make_float4(0.f, 0.f, 0.f, 0.f));
+  if (k < count) st4<false>(p + k, make_float4(0.f, 0.f, 0.f, 0.f));
 }
-
-constexpr bool kFillNtDefault = false;
 
 template <int MODE>
 void launch_direct_mode(bool diag, bool nt, dim3 grid, hipStream_t stream, float4 *st, int n,
@@ -284,13 +281,12 @@ int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const
   const int pt = op.t0, pc = op.c0;
   int mode;
   uint64_t items;
-  static const bool k1_plain = std::getenv("QMLE_K1_PLAIN") != nullptr;
   if (op.nc == 0) {
     if (pt >= 1) {
       mode = 0;
       items = diag ? chunks : chunks >> 1;
       // dense gate, state >= 2^12 chunks: lane exchange for bits 1..6, 4-row bursts for bits >= 21
-      if (!diag && !k1_plain && n >= 14) {
+      if (!diag && n >= 14) {
         if (pt <= 6) { mode = 5; items = chunks >> 1; }
         else if (pt >= 21) { mode = 6; items = chunks >> 3; }
       }
@@ -301,14 +297,14 @@ int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const
     else { mode = 4; items = diag ? chunks : chunks >> 1; }
     // control and target both inside a wave's 1 KiB: one contiguous float4 per lane (mode 7)
     // (controls on bits >= 4 select whole 128-byte lines: mode 2 moves half the state, 0.37 vs 0.65 ms)
-    if (!diag && !k1_plain && n >= 14 && pt >= 1 && pt <= 6 && pc >= 0 && pc <= 3) { mode = 7; items = chunks; }
+    if (!diag && n >= 14 && pt >= 1 && pt <= 6 && pc >= 0 && pc <= 3) { mode = 7; items = chunks; }
     // bursts of 4 rows per stream (mode 8) where control and target leave a wave's 4 KiB whole.  Which
     // positions gain is measured, not derived (n = 28, tools/k1_block_order.py with QMLE_K1_CTRL_BURST=0 / 9
     // for four control placements, profiles/r04_k1_ctrl_burst.txt): target position >= 21 always (0.35-0.42
     // -> 0.34-0.37 ms), target position 9 .. 11 (0.38-0.41 -> 0.35-0.37), and the neighbouring control below
     // the target from position 17 up (0.36-0.39 -> 0.34-0.35); target positions 12 .. 16 stream best one
     // pair per work item (+5 .. +9 % in bursts).  QMLE_K1_CTRL_BURST=<min target position | 0> overrides.
-    if (mode == 2 && !diag && !k1_plain && n >= 16 && pt >= 9 && pc >= 9) {
+    if (mode == 2 && !diag && n >= 16 && pt >= 9 && pc >= 9) {
       bool burst = n >= 24 && (pt >= 21 || pt <= 11 || (pc == pt - 1 && pt >= 17));
       if (const char *e = std::getenv("QMLE_K1_CTRL_BURST")) burst = atoi(e) > 0 && pt >= atoi(e);
       if (burst) {
@@ -318,7 +314,7 @@ int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const
     }
   }
   // CZ / CPhase with control and target on chunk bits: the |11> quarter only (mode 9)
-  if (diag && (op.flags & LF_PHASE) && op.nc == 1 && pc >= 1 && pt >= 1 && !k1_plain) { mode = 9; items = chunks >> 2; }
+  if (diag && (op.flags & LF_PHASE) && op.nc == 1 && pc >= 1 && pt >= 1) { mode = 9; items = chunks >> 2; }
   if (items == 0) items = 1;
   // streaming (non-temporal) accesses once the working set dwarfs the Infinity Cache
   const bool nt = ((size_t)batch << n) * sizeof(float2) >= ((size_t)1 << 30);
@@ -331,7 +327,6 @@ int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const
   // the whole state -- workgroup i takes block i * 4097 mod grid, ~32 MiB apart -- brings both to 0.38 ms
   // (tools/k1_block_order.py, profiles/r04_k1_block_order.txt); every other control position streams best
   // in ascending order (+2 ... +15 % with any multiplier), so only these two get it.
-  // QMLE_K1_BLOCK_MUL=<odd | 0> overrides (read per launch).
   uint32_t blk_mul = 0;
   if (op.nc && (mode == 2 || mode == 9) && (grid.x & (grid.x - 1u)) == 0 && items == (uint64_t)grid.x * 256u) {
     if (!diag && (pc == 7 || pc == 8) && n >= 24 && grid.x > 4097u) blk_mul = 4097u;
@@ -342,8 +337,6 @@ int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const
     // every 4 MiB off -- streams at 0.21-0.26 ms in ascending order where its neighbours take 0.17; workgroups 17
     // blocks apart: 0.19-0.20.  Every other pair is fastest ascending: profiles/r05_k1_cz_order.txt)
     if (mode == 9 && n >= 24 && grid.x > 4097u && pc >= 16 && pc <= 18 && pt >= 16 && pt <= 18) blk_mul = 17u;
-    const char *e = std::getenv("QMLE_K1_BLOCK_MUL");
-    if (e) blk_mul = atoi(e) > 0 ? ((uint32_t)atoi(e) | 1u) : 0u;
   }
   switch (mode) {
     case 0: launch_direct_mode<0>(diag, nt, grid, stream, st, n, pt, pc, mats, p->mat_floats, op.mat_off, items, blk_mul); break;
@@ -378,15 +371,8 @@ void launch_diag_all(float2 *states, int n, int batch, const float *marks, const
 void launch_fill_zero(float2 *states, uint64_t count, hipStream_t stream) {
   for (uint64_t done = 0; done < count;) {
     const uint64_t part = std::min<uint64_t>(count - done, (uint64_t)1 << 38);
-    // (QMLE_FILL_NT=1: streaming stores -- the fill by itself is a little slower with them, tools/fill_bench.hip; the
-    // pass that reads the zeros next does not run into their write-back.  Read per launch: A/B)
-    const char *e = std::getenv("QMLE_FILL_NT");
-    if (e ? atoi(e) != 0 : kFillNtDefault)
-      hipLaunchKernelGGL(k_fill_zero<true>, dim3((unsigned)((part + 255u) / 256u)), dim3(256), 0, stream,
-                         reinterpret_cast<float4 *>(states) + done, part);
-    else
-      hipLaunchKernelGGL(k_fill_zero<false>, dim3((unsigned)((part + 255u) / 256u)), dim3(256), 0, stream,
-                         reinterpret_cast<float4 *>(states) + done, part);
+    hipLaunchKernelGGL(k_fill_zero, dim3((unsigned)((part + 255u) / 256u)), dim3(256), 0, stream,
+                       reinterpret_cast<float4 *>(states) + done, part);
     done += part;
   }
 }

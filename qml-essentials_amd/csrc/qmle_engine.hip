@@ -135,11 +135,8 @@ int ensure_device_plan(qmle_plan *p) {
 }
 
 // A run that starts from |0..0> keeps track of the amplitudes that are still exactly zero
-// (Stage::zero_in); the prefetching experiment does not.
-bool plan_sparse(const qmle_plan *p) {
-  static const bool pf_env = std::getenv("QMLE_PREFETCH") != nullptr;
-  return !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH)) && !pf_env;
-}
+// (Stage::zero_in).
+bool plan_sparse(const qmle_plan *p) { return !(p->flags & QMLE_PLAN_NO_SPARSE); }
 
 // qmle_run_batch_map hands its angle map to the matrix builder of the batch it is about to run (this
 // thread's next launch_build_matrices of >= 64 samples): the angles are then formed inside the builder and
@@ -209,6 +206,7 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
   if (!out || n_ops < 0 || n_slots < 0 || n_consts < 0 || (n_ops > 0 && !ops))
     return QMLE_ERR_INVALID_ARG;
   *out = nullptr;
+  if (flags & 16u) return QMLE_ERR_INVALID_ARG;  // reserved (include/qmle_sv.h)
   qmle_plan *p = new (std::nothrow) qmle_plan();
   if (!p) return QMLE_ERR_INVALID_ARG;
   flags &= ~QMLE_PLAN_INTERNAL_ZERO_RUN;  // internal: set below on the plans only qmle_run_batch executes
@@ -226,8 +224,7 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
   // The same tape scheduled for runs from |0..0> only (wider first tile): what qmle_run_batch
   // executes in place of `p` when the pass-cost model prefers it.  qmle_apply_inplace and the
   // adjoint sweep apply stages to LIVE states and keep `p`'s own schedule.
-  static const bool no_wide = std::getenv("QMLE_NO_WIDE_FIRST") != nullptr;
-  if (!no_wide && !p->whole_state_lds && !(flags & (QMLE_PLAN_NO_FUSION | QMLE_PLAN_PREFETCH)) &&
+  if (!p->whole_state_lds && !(flags & QMLE_PLAN_NO_FUSION) &&
       !((flags >> 8) & 0xffffu) && p->stages.size() >= 2 && p->stages[0].kind == ST_TILE) {
     qmle_plan *v = new (std::nothrow) qmle_plan();
     if (v) {
@@ -270,8 +267,7 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
         // layers 8.9 vs 11.2.  The pass-cost model plus 17 (general-mask epilogue) resp. 12
         // (k_reg_measure on live input), in its units of 36 per read+write pass, picks the faster
         // plan in all of them; plans whose folded form ends in a known-zero special kernel keep it.
-        static const bool always_fold = std::getenv("QMLE_ALWAYS_FOLD") != nullptr;
-        if (p->expval_child && !always_fold && !c->stages.empty() && !c->whole_state_lds) {
+        if (p->expval_child && !c->stages.empty() && !c->whole_state_lds) {
           bool parity = false;
           for (int w = 0; w < p->n; ++w) {
             const uint32_t m = pull_back_z(p->absorbed, w);
@@ -371,15 +367,11 @@ static int default_states_in_flight(const qmle_plan *p, int batch) {
   // 8 / 4 / 2 GiB per launch (the read+write pass: 56.6 vs 51.6 us per state at 256 vs 64
   // states); the known-zero plans keep 32 GiB (3.0 vs 4.9 ms per step at 4 GiB).
   const size_t sb = (size_t)8 << p->n;
-  static const long env_mib = [] {
-    const char *e = getenv("QMLE_IN_FLIGHT_MIB");  // tuning knob; default from measurements
-    return e ? atol(e) : 0L;
-  }();
   bool whole_state_every_pass = p->stages.size() >= 2;
   if (plan_sparse(p))
     for (size_t si = 1; si < p->stages.size(); ++si)
       if (p->stages[si].zero_in != 0) whole_state_every_pass = false;
-  const size_t budget_mib = env_mib > 0 ? (size_t)env_mib : whole_state_every_pass ? 4096 : 32768;
+  const size_t budget_mib = whole_state_every_pass ? 4096 : 32768;
   size_t s = (budget_mib << 20) / sb;
   if (s < 1) s = 1;
   if (s > (size_t)batch) s = (size_t)batch;
@@ -404,23 +396,21 @@ static size_t expval_partial_rows(const qmle_plan *p) {
 // 0..3 to the first later read (lean epilogue) and streams its stores, so that the later reads do not run into its
 // write-back: 0.79 ms after the circuit against 0.92-1.0 for the stand-alone reads -- taken by default
 // (QMLE_MW_FUSE_TILED=0: the stand-alone reads; read per call: A/B, tests).
-static bool plan_mw_fusable(const qmle_plan *p, bool whatever_the_switches = false) {
+static bool plan_mw_fusable(const qmle_plan *p) {
   if (p->stages.empty()) return false;
   const Stage &last = p->stages.back();
-  if (!whatever_the_switches) {
-    if (std::getenv("QMLE_NO_MW_FUSION") != nullptr) return false;
-    // (round 5: tiled states fuse by default -- lean epilogue + streaming stores, n = 28: 0.81 ms after the circuit
-    // against 1.0 ms for the three stand-alone reads; QMLE_MW_FUSE_TILED=0 keeps the stand-alone reads: A/B, tests)
-    const char *ft = std::getenv("QMLE_MW_FUSE_TILED");
-    if (last.T < p->n && ft && atoi(ft) == 0) return false;
-  }
+  // (round 5: tiled states fuse by default -- lean epilogue + streaming stores, n = 28: 0.81 ms after the circuit
+  // against 1.0 ms for the three stand-alone reads)
+  const char *ft = std::getenv("QMLE_MW_FUSE_TILED");
+  if (last.T < p->n && ft && atoi(ft) == 0) return false;
   return mw_fusable(p->n, last);
 }
 // rows + purities of `batch` states (conservative per state: the rows per state shrink with the batch)
 static size_t mw_ws_bytes(const qmle_plan *p, int batch) {
-  // (enough for either route: the switches are read per call, a workspace sized before one was flipped stays valid)
+  // (enough for either route: QMLE_MW_FUSE_TILED is read per call, a workspace sized before it was flipped stays valid)
   size_t one = mw_resident_ws_bytes(p->n, 1);
-  if (plan_mw_fusable(p, true)) one = std::max(one, mw_fused_ws_bytes(p->n, 1, p->stages.back()));
+  if (!p->stages.empty() && mw_fusable(p->n, p->stages.back()))
+    one = std::max(one, mw_fused_ws_bytes(p->n, 1, p->stages.back()));
   return align_up(one, 256) * (size_t)batch;
 }
 
@@ -584,8 +574,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   // restrictions of those parities to T wires are T + 1 or T + 2 distinct ranges.)
   bool semi_single = false;
   uint32_t row_masks[QMLE_MAX_QUBITS];
-  static const bool no_semi = std::getenv("QMLE_NO_SEMI_SINGLE") != nullptr;
-  if (meas_type == QMLE_MEAS_EXPVAL_Z && !single_bits && !no_semi && !plan->stages.empty() &&
+  if (meas_type == QMLE_MEAS_EXPVAL_Z && !single_bits && !plan->stages.empty() &&
       plan->stages.back().kind == ST_TILE && !plan->whole_state_lds) {
     const Stage &ls = plan->stages.back();
     uint32_t tile_mask = 0;
@@ -685,7 +674,6 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   }
   if (in_flight > 65535) in_flight = 65535;
   // two slots (state buffer + partial sums each) when the batch has several chunks and the workspace has room
-  const float2 *const d_states0_dbg = d_states;
   SideStreams *side = nullptr;
   char *slot1 = nullptr;
   // (one streaming pass per gate -- QMLE_PLAN_NO_FUSION -- is HBM-bound in every pass: two of them at once share the
@@ -718,10 +706,6 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
   const size_t mw_bytes = meas_type == QMLE_MEAS_MEYER_WALLACH ? mw_ws_bytes(plan, in_flight) : 0;
 
-  if (std::getenv("QMLE_DBG_OVERLAP"))
-    fprintf(stderr, "[qmle] chunks of %d of %d states, overlap %s (slot1 %p, ws %zu bytes, used before the states %zu, two slots %zu)\n",
-            in_flight, batch, side ? "on" : "off", (void *)slot1, workspace_bytes,
-            (size_t)((char *)d_states0_dbg - (char *)d_workspace), 2 * (size_t)in_flight * per_state_ws_bytes(plan, meas_type));
   hipStream_t const caller_stream = stream;
   if (side) {  // fork: what the caller's stream has queued so far (the matrices, the angle table) comes first
     if (hipEventRecord(side->fork, caller_stream) != hipSuccess ||
@@ -991,7 +975,7 @@ int qmle_plan_autotune(qmle_plan *plan, int meas_type, int n_obs, int batch, int
   // the plan this measurement executes
   qmle_plan *owner = (meas_type == QMLE_MEAS_EXPVAL_Z && plan->expval_child) ? plan->expval_child : plan;
   qmle_plan *target = owner->zero_variant ? owner->zero_variant : owner;
-  if (target->whole_state_lds || target->cand_ranking.size() < 2 || (target->flags & (QMLE_PLAN_NO_FUSION | QMLE_PLAN_PREFETCH)) ||
+  if (target->whole_state_lds || target->cand_ranking.size() < 2 || (target->flags & QMLE_PLAN_NO_FUSION) ||
       ((target->flags >> 8) & 0xffffu))
     return QMLE_OK;  // one schedule only: nothing to tune
   const int batch_class = batch >= 256 ? 2 : batch >= 16 ? 1 : 0;
@@ -1130,9 +1114,8 @@ int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angl
   // The table is needed as a table only by the Golomb diagonal (QMLE_OP_DIAG_ALL reads its angle in the pass
   // itself); every other gate meets its angles in the matrix builder, which can form them from the map --
   // one kernel (5-9 us of the 0.17 ms analysis loops) and the table's round trip less.  From 64 samples on
-  // (whole waves per group); QMLE_NO_MAP_FUSION=1 keeps the two kernels (A/B, tests).
-  bool table = batch < 64 || std::getenv("QMLE_NO_MAP_FUSION") != nullptr || map->n_leaves < 0 || map->n_leaves > 8 ||
-               !map->d_ptr || !map->d_const;
+  // (whole waves per group).
+  bool table = batch < 64 || map->n_leaves < 0 || map->n_leaves > 8 || !map->d_ptr || !map->d_const;
   for (const qmle_op &o : plan->ops) table = table || o.opcode == QMLE_OP_DIAG_ALL;
   if (table) {
     const int rc = qmle_build_angles(map->d_leaves, map->leaf_strides, map->leaf_div, map->leaf_mod, map->n_leaves,

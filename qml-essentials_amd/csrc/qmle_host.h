@@ -7,6 +7,28 @@
 //   qmle_f64.hip       complex128 engine
 // Kernels stay private to their unit (anonymous namespaces); what crosses a unit boundary is a
 // plain host function that launches them.
+//
+// Environment switches: the library reads these nine and no others (tests/test_abi_cpu.py).  Unset,
+// each one leaves the measured default in place.
+//   QMLE_NO_CHUNK_OVERLAP=1  batch chunks run on the caller's stream alone instead of alternating
+//                            between two internal streams.  Read per call.  bench.py (k2_one_stream,
+//                            k2_three_pass), tests.
+//   QMLE_MW_FUSE_TILED=0     Meyer-Wallach of a tiled state: the stand-alone reads instead of the sums
+//                            of the producing pass.  Read per call.  bench.py, tests.
+//   QMLE_NO_TOP_FIRST=1      no schedule candidate whose first tile sits on the top positions.  Read
+//                            per plan compile.  bench.py (k2_three_pass), tests.
+//   QMLE_FORCE_CAND=<k>      run schedule candidate k instead of the pass-cost model's choice.  Read per
+//                            plan compile.  tests, tools/cand_sweep.py.
+//   QMLE_PAD_HIGH=<1 | p>    pad the last stage's tile from the top positions (p >= 2: position p
+//                            first).  Read per plan compile.  tests.
+//   QMLE_NO_MULTI_ZIN=1      k_tile2 keeps one tile per workgroup when the tile has known-zero local
+//                            bits.  Read per launch.  tests.
+//   QMLE_K1_CTRL_BURST=<p>   controlled direct passes take 4-row bursts from target position p on (0:
+//                            never).  Read per launch.  tests.
+//   QMLE_MW_NO_LEAN=1        the producing pass reports Meyer-Wallach positions 0..3 itself instead of
+//                            the first later read.  Read per call.  tests.
+//   QMLE_RNG_THREADS=<k>     host threads of the Philox parameter sampler (qmle_rng.cpp).  Read per
+//                            call.  Shared hosts.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -92,8 +92,6 @@ double algo_bytes(const qmle_op &op, int n) {
   }
 }
 
-constexpr bool kSmallLastTileDefault = true;  // (measured: profiles/r05_small_last_tile_ab.txt)
-
 // Partition the ops of one tile stage into register-tile groups (<= 4 tile-local bits
 // per group, dependency order preserved: an op may only move ahead of ops it shares no
 // bit with).  Rewrites dev_ops[st.op_begin, st.op_end) into group order.
@@ -108,10 +106,9 @@ static void group_stage_ops(qmle_plan *p, Stage &st) {
   std::vector<char> done(nops, 0);
   const bool regs_ok = st.T >= 4 && !(p->flags & QMLE_PLAN_NO_REGTILE);
   // (round 5: an uncontrolled dense 4x4 joins a register-tile run as well -- the noisy model's superoperators sit
-  // between every pair of gates and cost an LDS sweep each otherwise; QMLE_NO_REG2Q=1: A/B.  Plans that keep every
-  // gate its own operator (QMLE_PLAN_NO_MERGE: the adjoint sweep's, whose tile kernel knows GK_REG4 only) do not)
-  static const bool no_reg2q = std::getenv("QMLE_NO_REG2Q") != nullptr;
-  const bool reg2q = regs_ok && !no_reg2q && !(p->flags & QMLE_PLAN_NO_MERGE);
+  // between every pair of gates and cost an LDS sweep each otherwise.  Plans that keep every gate its own operator
+  // (QMLE_PLAN_NO_MERGE: the adjoint sweep's, whose tile kernel knows GK_REG4 only) do not)
+  const bool reg2q = regs_ok && !(p->flags & QMLE_PLAN_NO_MERGE);
   auto groupable = [&](const LoweredOp &o) {
     return regs_ok && ((o.kind == LK_1Q && o.nc <= 1) || (reg2q && o.kind == LK_2Q && o.nc == 0));
   };
@@ -293,14 +290,13 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   // profiles/r04_ws_sq_*.txt).  Only the lane bits are permuted: the wave index keeps the highest
   // positions, where the known zeros of a run from |0..0> sit (whole waves of idle work items skip).
   int pos_of[16];
-  static const bool no_bank_perm = std::getenv("QMLE_NO_BANK_PERM") != nullptr;
   auto choose_thread_bits = [&](uint32_t G, bool keep_order) {
     int freep[16], nf = 0;
     for (int j = 0; j < T; ++j)
       if (!(G & (1u << j))) freep[nf++] = j;
     for (int k = 0; k < nf; ++k) pos_of[k] = freep[k];
     const int lanes = nf < 6 ? nf : 6;
-    if (keep_order || no_bank_perm || lanes < 2) return;
+    if (keep_order || lanes < 2) return;
     uint32_t basis[8];
     int nb = 0;
     auto independent = [&](uint32_t v) {  // reduce v by the basis; keep it when something is left
@@ -337,7 +333,7 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
     for (int j = 0; j < T; ++j)
       if (G & (1u << j)) gb[k++] = j;
     // (the idle-work-item flags below are only read by tiled runs that track known zeros)
-    choose_thread_bits(G, (Z & ~G) != 0 && T < p->n && !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH)));
+    choose_thread_bits(G, (Z & ~G) != 0 && T < p->n && !(p->flags & QMLE_PLAN_NO_SPARSE));
     g.tbl = (uint32_t)p->tbl2.size();
     for (uint32_t t = 0; t < nt; ++t) {
       const uint32_t e = deposit(t, G);
@@ -669,9 +665,8 @@ int compile_plan(qmle_plan *p) {
     // two-qubit Pauli rotations): a 1-q gate on one of its wires multiplies onto it as U (x) I / I (x) U
     // (BuildOp::pad = 1 / 2), a 4x4 on the same ordered pair as a plain product, and a new 4x4 takes the
     // pending 1-q matrices of its two wires with it.  A noisy model's gate-channel-gate-channel run on one wire
-    // (U (x) conj U, superoperator, ...) becomes ONE 4x4 per sample.  QMLE_NO_MERGE_2Q=1: A/B.
-    static const bool no_merge_2q = std::getenv("QMLE_NO_MERGE_2Q") != nullptr;
-    const bool merge_2q = fuse && !(p->flags & QMLE_PLAN_NO_MERGE) && !no_merge_2q;
+    // (U (x) conj U, superoperator, ...) becomes ONE 4x4 per sample.
+    const bool merge_2q = fuse && !(p->flags & QMLE_PLAN_NO_MERGE);
     if (merge_2q && lo.kind == LK_1Q && lo.nc == 0) {
       const int prev = last_touch[lo.t0];
       if (prev >= 0) {
@@ -985,13 +980,9 @@ int compile_plan(qmle_plan *p) {
         }
         // The LAST stage of a 2^13-tile schedule whose gates need <= 12 positions takes a 2^12 tile: five 32 KiB
         // workgroups per CU overlap their loads and their groups where two 64 KiB ones do not (the measuring pass
-        // of the 4-layer n = 24 model: experiment QMLE_SMALL_LAST_TILE)
+        // of the 4-layer n = 24 model: DESIGN 9e, profiles/r05_small_last_tile_ab.txt)
         int Tpad = T;
-        {
-          const char *e = std::getenv("QMLE_SMALL_LAST_TILE");
-          const bool on = e ? atoi(e) != 0 : kSmallLastTileDefault;
-          if (on && T == 13 && !p->stages.empty() && n_done + members.size() == nl && popc(Q) <= 12 && !no_fusion) Tpad = 12;
-        }
+        if (T == 13 && !p->stages.empty() && n_done + members.size() == nl && popc(Q) <= 12 && !no_fusion) Tpad = 12;
         for (int b = 0; b < n && popc(Q) < Tpad; ++b) Q |= bit(b);
         st.T = popc(Q);
         int nt = 0, no = 0;
@@ -1094,7 +1085,7 @@ int compile_plan(qmle_plan *p) {
   // with 2 groups, 125 with 5, 192 with 7); a direct single-gate pass ~33
   // Known zeros scale both parts: a stage reads 2^-|zero_in| of the state, computes and (when
   // the next stage is a tile stage) stores only the tiles whose outer bits are live.
-  const bool sparse_model = !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH));
+  const bool sparse_model = !(p->flags & QMLE_PLAN_NO_SPARSE);
   // the plan is only ever run from |0..0> (qmle_run_batch): set on the variants / children that
   // qmle_plan_create compiles for that purpose, never on a plan handed to qmle_apply_inplace
   const bool zero_run = (p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) != 0;
@@ -1116,9 +1107,8 @@ int compile_plan(qmle_plan *p) {
       const bool last = si + 1 == p->stages.size();
       if (st.fast_ok) {
         // Fast kernel (k_tile2), round-3 model, fitted to per-pass HIP-event times of 1- and 4-layer
-        // circuits at n = 24 with and without their gate groups (tools/deep_anatomy.py,
-        // QMLE_DBG_T2=1; profiles/r03_pass_model.txt): a pass takes the LONGER of its memory time
-        // and its compute time plus a sixth of the shorter one.
+        // circuits at n = 24 with and without their gate groups (profiles/r03_pass_model.txt): a pass
+        // takes the LONGER of its memory time and its compute time plus a sixth of the shorter one.
         //   memory: 19.5 us write-only, 21 read-only, 50 read+write (5.4 TB/s: the mix costs);
         //   a read+write pass whose every load / store instruction spans positions 6 and 13 (byte
         //   address bits 9 and 16) and no other position below 8 -- a wave's 8 rows of 128 B are
@@ -1161,28 +1151,24 @@ int compile_plan(qmle_plan *p) {
     // carried + wide first stage, 3 position 6 carried.  Ties keep the lower index (round-2 schedules).
     int best = 0;
     double best_cost = 1e300;
-    static const bool no_lazy = std::getenv("QMLE_NO_LAZY_CX") != nullptr;
-    static const bool no_carry = std::getenv("QMLE_NO_CARRY6") != nullptr;
-    static const bool no_wide = std::getenv("QMLE_NO_WIDE_FIRST") != nullptr;
     // (round 5) variant 4, k in [48, 60): first tile of 2^14 amplitudes on the TOP positions (all-live runs from
     // |0..0>).  Such a schedule trades an HBM pass for arithmetic in the passes that are left: fewer bytes, less time, a
     // lower fraction of the HBM roofline.  QMLE_NO_TOP_FIRST=1: the round-4 candidates only.
-    const bool no_top = std::getenv("QMLE_NO_TOP_FIRST") != nullptr || std::getenv("QMLE_NO_INIT_FILL") != nullptr;  // (read per compile: bench.py's k2_three_pass leg)
+    const bool no_top = std::getenv("QMLE_NO_TOP_FIRST") != nullptr;  // (read per compile: bench.py's k2_three_pass leg)
     auto run_cand = [&](int k) {
       const int g = k % 6, lazy = (k / 6) % 2, v = k / 12;
       const bool wide = v == 1 || v == 2 || v == 4, carry6 = v == 2 || v == 3;
       schedule(cand[g][0], cand[g][1], lazy != 0, carry6 ? 6 : -1, wide ? kLdsMaxQubits : 0, v == 4);
     };
     auto allowed = [&](int k) {
-      const int g = k % 6, lazy = (k / 6) % 2, v = k / 12;
+      const int g = k % 6, v = k / 12;
       if (cand[g][0] >= n) return false;
-      if (lazy && no_lazy) return false;
       // (known-zero runs keep the round-2 schedules: their first passes are launch-bound special
       // kernels tuned for the (12, 4) geometry, and the wide first tile cost them 4-8 % at n = 24)
-      if (v >= 1 && sparse_model && std::getenv("QMLE_SPARSE_VARIANTS") == nullptr) return false;
-      if ((v == 1 || v == 2) && (!zero_run || no_wide)) return false;
-      if ((v == 2 || v == 3) && (no_carry || cand[g][1] != 4 || n < 16)) return false;
-      if (v == 4 && (!zero_run || sparse_model || no_top || n < 16 || n > 28 || (p->flags & QMLE_PLAN_PREFETCH))) return false;
+      if (v >= 1 && sparse_model) return false;
+      if ((v == 1 || v == 2) && !zero_run) return false;
+      if ((v == 2 || v == 3) && (cand[g][1] != 4 || n < 16)) return false;
+      if (v == 4 && (!zero_run || no_top || n < 16 || n > 28)) return false;
       return true;
     };
     p->cand_ranking.clear();
@@ -1228,8 +1214,6 @@ int compile_plan(qmle_plan *p) {
     p->n_groups_needed = 0;
     for (const BuildGroup &g : p->groups)
       if (!(g.dim == 2 && unread[g.mat_off])) ++p->n_groups_needed;
-    static const bool build_all = std::getenv("QMLE_BUILD_ALL_MATRICES") != nullptr;
-    if (build_all) p->n_groups_needed = (int)p->groups.size();
   }
   return QMLE_OK;
 }
@@ -1240,7 +1224,7 @@ int compile_plan(qmle_plan *p) {
 static double stage_read_bytes(const qmle_plan *p, size_t si) {
   const Stage &st = p->stages[si];
   const double D = std::ldexp(1.0, p->n);
-  const bool sparse = !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH));
+  const bool sparse = !(p->flags & QMLE_PLAN_NO_SPARSE);
   if (st.kind != ST_TILE) return st.kind == ST_DIRECT ? 0.5 * st.algo_bytes_per_state : 8.0 * D;
   if (si == 0) return 0.0;  // generated in LDS
   if (!sparse) return 8.0 * D;
@@ -1251,7 +1235,7 @@ static double stage_read_bytes(const qmle_plan *p, size_t si) {
 static double stage_write_bytes(const qmle_plan *p, size_t si) {
   const Stage &st = p->stages[si];
   const double D = std::ldexp(1.0, p->n);
-  const bool sparse = !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH));
+  const bool sparse = !(p->flags & QMLE_PLAN_NO_SPARSE);
   if (st.kind != ST_TILE) return st.kind == ST_DIRECT ? 0.5 * st.algo_bytes_per_state : 8.0 * D;
   if (!sparse || !st.next_tile) return 8.0 * D;
   uint32_t outer = 0;
@@ -1261,7 +1245,7 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
 
 int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
   const Stage &st = p->stages[si];
-  if (st.kind != ST_TILE || si == 0 || (p->flags & QMLE_PLAN_PREFETCH)) return 0;
+  if (st.kind != ST_TILE || si == 0) return 0;
   if (st.grp_end - st.grp_begin != 1 || p->op_groups[st.grp_begin].kind != GK_REG4) return 0;
   if (st.T < 10 || st.T > 14 || st.T >= p->n || (st.op_end - st.op_begin) > 1000) return 0;
   const OpGroup &g = p->op_groups[st.grp_begin];
@@ -1300,7 +1284,7 @@ static double stage_flops_per_state(const qmle_plan *p, const Stage &st, bool li
                         (p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) && (p->flags & QMLE_PLAN_NO_SPARSE);
   const double D = std::ldexp(1.0, one_tile ? st.T : p->n);
   double f = 0;
-  const bool sparse = live_only && !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH));
+  const bool sparse = live_only && !(p->flags & QMLE_PLAN_NO_SPARSE);
   uint32_t Z = sparse ? st.zero_in : 0u;
   // bit indices of a tile stage's ops: GROUP-local (0..3) inside a register-tile group, else tile-local
   std::vector<const OpGroup *> group_of(st.op_end > st.op_begin ? st.op_end - st.op_begin : 0, nullptr);
@@ -1373,7 +1357,7 @@ std::string describe_plan(const qmle_plan *p) {
        << ",\"zero_in\":" << st.zero_in << ",\"next_tile\":" << (st.next_tile ? "true" : "false")
        << ",\"product\":" << (st.product_ok ? "true" : "false") << ",\"expval_kernel\":\""
        << (const char *[]){"k_tile", "k_reg_measure", "k_reg_measure_fold", "k_reg_measure_mono"}
-              [expval_kernel_of(p, s, !(p->flags & (QMLE_PLAN_NO_SPARSE | QMLE_PLAN_PREFETCH)))]
+              [expval_kernel_of(p, s, !(p->flags & QMLE_PLAN_NO_SPARSE))]
        << "\",\"read_bytes_from_zero\":" << (unsigned long long)stage_read_bytes(p, s)
        << ",\"write_bytes_from_zero\":" << (unsigned long long)stage_write_bytes(p, s)
        << ",\"bits\":[";

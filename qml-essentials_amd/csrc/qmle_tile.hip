@@ -146,13 +146,13 @@ __global__ void k_tile(const TileArgs a) {
   }
   __syncthreads();
 
-  tile_compute<DENSE4, false>(a, s, slots, b);
+  tile_compute<DENSE4>(a, s, slots, b);
   if (MW) {
-    if (a.meas == TM_STORE_MW) tile_epilogue<false>(a, s, lut, red, tile, gridDim.x, b, base);  // (its TM_STORE branch)
+    if (a.meas == TM_STORE_MW) tile_epilogue(a, s, lut, red, tile, gridDim.x, b, base);  // (its TM_STORE branch)
     tile_mw_row(lds_offset_of(s), T, (uint32_t)tid, reinterpret_cast<float *>(s),
                 reinterpret_cast<float *>(a.out) + ((size_t)b * gridDim.x + tile) * kMwFusedRow, a.mw_lean != 0);
   } else {
-    tile_epilogue<false, false, true>(a, s, lut, red, tile, gridDim.x, b, base);
+    tile_epilogue<false, true>(a, s, lut, red, tile, gridDim.x, b, base);
   }
 }
 
@@ -351,8 +351,6 @@ struct Tile2Args {
   const uint32_t *tbl;      // qmle_plan::tbl2 on the device
   int n_groups;
   int n_ops_stage;          // ops of all the stage's groups (one contiguous stream in `ops`)
-  int dbg;                  // QMLE_DBG_T2 (timing anatomy only): 1 no groups, 2 no epilogue, 4 / 8: see tile2_groups,
-                            // 16 no global stores of a storing pass, 32 no global loads (constants instead)
   uint32_t gtab;            // index into tbl: per-lane global byte offset inside the tile
   uint32_t uoff8[8];        // byte offsets of the lane's 8 float4 (the tile's top three bits)
   // tile index -> amplitude offset of the tile: the outer bit positions as <= 6 contiguous runs
@@ -457,13 +455,6 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
       // scalar loads return out of order, so only lgkmcnt(0) can cover them: touching this
       // gate's operands HERE puts that wait in front of the next prefetch instead of behind it
       asm volatile("" : "+s"(M0.m00), "+s"(M0.m01), "+s"(M0.m10), "+s"(M0.m11), "+s"(w0.y), "+s"(w1.z) :: "memory");
-      if (f.dbg & 12) {  // timing anatomy only (wrong results): 4 = no per-gate scalar loads, 8 = + no dispatch
-        if (busy != 0) {
-          if (f.dbg & 8) f_dense<1>(r, M0);
-          else fast_dispatch(r, (int)(w0.y >> 24), M0);
-        }
-        continue;
-      }
       const u64 QMLE_CONSTANT *mn = mrow + (w1.z >> 1);
       const Mat2S Mn = {mn[0], mn[1], mn[2], mn[3]};
       const v4u w2 = op[k + 2 < last ? k + 2 : last];
@@ -830,10 +821,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   const uint32_t zl_m = MULTI ? (a.zin_local & ~1u) : 0u;
   const bool z0_m = MULTI && (a.zin_local & 1u) != 0;
   auto load_tile = [&](const char *p) {
-    if (f.dbg & 32) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = make_float4(1e-3f, 0.f, 1e-3f, 0.f);
-    } else if (MULTI && a.zin_local) {
+    if (MULTI && a.zin_local) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         v[u] = z4;
@@ -917,12 +905,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
     } else if (MEASURE && MULTI && MASKS) {  // (TM_EXPVAL_MASKS: launch_tile)
       if constexpr (MASKS) tile_m_accumulate(sbo, T, tid, tile + (uint32_t)i, a.n_obs, m_ol, m_oo, pacc);
     } else if (MEASURE && MULTI) {  // (TM_EXPVAL_PARTIAL only: launch_tile)
-      if (!(f.dbg & 2)) tile_z_accumulate(sbo, T, tid, i, zacc);
+      tile_z_accumulate(sbo, T, tid, i, zacc);
     } else if (MEASURE) {
-      if (!(f.dbg & 2)) {
-        if (a.meas == TM_EXPVAL) whole_state_expval(a, sl, soff, red, tid, nt, b);
-        else tile_epilogue<false>(a, s, nullptr, red, tile + (uint32_t)i, n_tiles, b, base_cur, qsrc);
-      }
+      if (a.meas == TM_EXPVAL) whole_state_expval(a, sl, soff, red, tid, nt, b);
+      else tile_epilogue(a, s, nullptr, red, tile + (uint32_t)i, n_tiles, b, base_cur, qsrc);
     } else if (a.meas == TM_STORE) {
       if (MULTI) {  // (the next tile's 8 float4 are live: two batches of four keep <= 96 VGPRs)
 #pragma unroll
@@ -931,14 +917,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
 #pragma unroll
           for (int u = 0; u < 4; ++u) w[u] = lds_ld128(sl ^ soff[h + u]);
 #pragma unroll
-          for (int u = 0; u < 4; ++u) if (!(f.dbg & 16) || w[u].x == 123.f) st4<NT>(reinterpret_cast<float4 *>(st_cur + uoff[h + u] + goff8), w[u]);
+          for (int u = 0; u < 4; ++u) st4<NT>(reinterpret_cast<float4 *>(st_cur + uoff[h + u] + goff8), w[u]);
         }
       } else {
         float4 w[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) w[u] = lds_ld128(sl ^ soff[u]);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) if (!(f.dbg & 16) || w[u].x == 123.f) st4<NT>(reinterpret_cast<float4 *>(st_cur + uoff[u] + goff8), w[u]);
+        for (int u = 0; u < 8; ++u) st4<NT>(reinterpret_cast<float4 *>(st_cur + uoff[u] + goff8), w[u]);
       }
     } else {
       char *po = reinterpret_cast<char *>(reinterpret_cast<float *>(a.out) + (size_t)b * D + base_cur);
@@ -957,7 +943,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   else if (MEASURE && MULTI && MASKS) {
     if constexpr (MASKS)
       tile_m_finish(reinterpret_cast<float *>(a.out), red, pacc, a.n_obs, m_ol, T, tid, nt, blockIdx.x, gridDim.x, b);
-  } else if (MEASURE && MULTI && !(f.dbg & 2))
+  } else if (MEASURE && MULTI)
     tile_z_finish(reinterpret_cast<float *>(a.out), red, zacc, qsrc, tid, nt, 31 - __builtin_clz((unsigned)tpw),
                   blockIdx.x, gridDim.x, b);
 }
@@ -1537,100 +1523,6 @@ __global__ void __launch_bounds__(256) k_product_stream(const ProductArgs a) {
       }
 }
 
-// ---- prefetching tile kernel ------------------------------------------------------------
-// EXPERIMENT, opt-in (QMLE_PLAN_PREFETCH): in k_tile a workgroup's HBM traffic stops while it
-// runs its gate groups.  k_tile_pf gives every workgroup a contiguous run of tiles and TWO
-// tile buffers: while the gate groups run on one buffer the next tile streams into the other
-// by LDS-DMA (global_load_lds_dwordx4, no VGPRs), so loads are in flight all the time.
-// Bit-identical to k_tile (tests), but slower on MI355X: see launch_tile and DESIGN.md 9.
-//
-// The DMA is issued from inline asm: hipcc drains a builtin LDS-DMA with vmcnt(0) in front of
-// every ds_read (it cannot tell the buffers apart), which would serialise exactly what this
-// kernel overlaps.  Ordering is therefore explicit: each wave waits for its own DMAs with a
-// counted vmcnt, then a barrier publishes the tile (read a staged buffer only after the
-// barrier behind the wait); barriers are raw (tile_sync<true>) so that nothing drains the
-// prefetch or the previous tile's stores.
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
-  unsigned keep;  // lds_dst: wave-uniform LDS byte address; lane l lands at lds_dst + 16 l
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(gsrc), "s"(lds_dst)
-      : "memory");
-}
-
-constexpr int kPfDmaPerWave = 8;  // 2^T * 8 B / (waves * 1 KiB) for T = 12 / 13 at 2^(T-4) threads
-
-// Issue this wave's share of the tile's loads into the LDS buffer at byte address lds_base.
-// Granule (16 B) position p of the buffer holds amplitude pair g = p ^ ((p >> 4) & 15): the
-// sw() layout expressed on the SOURCE address, since the DMA destination is lane-linear.
-__device__ __forceinline__ void pf_issue_tile(const TileArgs &a, const float2 *st, uint64_t base,
-                                              const uint32_t *lut, uint32_t lds_base) {
-  const uint32_t lane = threadIdx.x & (kWave - 1);
-  const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint32_t nw = blockDim.x >> 6;
-  const uint32_t lowmask = (1u << a.L) - 1u;
-#pragma unroll
-  for (int j = 0; j < kPfDmaPerWave; ++j) {
-    const uint32_t q = (uint32_t)j * nw + w;          // 1 KiB block of the buffer
-    const uint32_t p = q * 64u + lane;
-    const uint32_t e = (p ^ ((p >> 4) & 15u)) << 1;   // local amplitude index (even)
-    glds16(st + (base | lut[e >> a.L] | (e & lowmask)), lds_base + q * 1024u);
-  }
-}
-
-template <bool DENSE4>
-__global__ void __launch_bounds__(512)
-k_tile_pf(const TileArgs a, uint32_t n_tiles, uint32_t total, uint32_t chunk) {
-  extern __shared__ float4 smem4[];
-  const int T = a.T, L = a.L;
-  float2 *buf0 = reinterpret_cast<float2 *>(smem4);
-  float2 *buf1 = buf0 + (1u << T);
-  uint32_t *lut = reinterpret_cast<uint32_t *>(buf1 + (1u << T));
-  const uint32_t lut_n = (1u << (T - L)) < 4u ? 4u : (1u << (T - L));
-  float *red = reinterpret_cast<float *>(lut + lut_n);
-  OpSlot *slots = reinterpret_cast<OpSlot *>(red + 288);
-  const size_t D = (size_t)1 << a.n;
-  const uint32_t first = blockIdx.x * chunk;
-  const uint32_t last = first + chunk < total ? first + chunk : total;
-  if (first >= last) return;  // whole workgroup leaves together
-  const uint32_t lds0 = (uint32_t)(uintptr_t)buf0;  // low 32 bits of an LDS pointer = byte address
-  const uint32_t buf_bytes = 8u << T;
-
-  tile_build_lut(a, lut);
-  __syncthreads();
-  int cur = 0, staged_b = -1;
-  {
-    const int b = (int)(first / n_tiles);
-    pf_issue_tile(a, a.states + (size_t)b * D, tile_base(a, first % n_tiles), lut, lds0);
-  }
-  for (uint32_t f = first; f < last; ++f) {
-    const int b = (int)(f / n_tiles);
-    const uint32_t tile = f % n_tiles;
-    const uint64_t base = tile_base(a, tile);
-    if (b != staged_b) {  // (every wave passed the previous iteration's closing barrier)
-      tile_stage_slots(a, slots, b);
-      staged_b = b;
-    }
-    if (f + 1 < last) {
-      const int bn = (int)((f + 1) / n_tiles);
-      pf_issue_tile(a, a.states + (size_t)bn * D, tile_base(a, (f + 1) % n_tiles), lut,
-                    lds0 + (uint32_t)(cur ^ 1) * buf_bytes);
-      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // = kPfDmaPerWave: tile f has landed
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    tile_sync<true>();  // publishes tile f (and the slots)
-    float2 *s = cur ? buf1 : buf0;
-    tile_compute<DENSE4, true>(a, s, slots, b);
-    tile_epilogue<true>(a, s, lut, red, tile, n_tiles, b, base);
-    tile_sync<true>();  // buffer `cur` is free for the DMA of tile f + 2
-    cur ^= 1;
-  }
-}
-
-
 }  // namespace
 
 namespace qmle {
@@ -1657,26 +1549,22 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
                               from_zero);
   a.slots_in_lds = tile_lds_bytes(st.T, st.L, a.n_ops) <= 160 * 1024 ? 1 : 0;
-  static const bool no_nt = std::getenv("QMLE_TILE_NO_NT") != nullptr;
   // dense stages only (a stage that skips known zeros moves a fraction of the state, and what
   // it writes is read back at once): K2 dense 122.6 -> 119.8 ms per step
   // (the initialising pass only writes, and what it writes is read back by the next pass: plain
   // stores are 1.5 us per 2^24-amplitude state faster there, 22.9 vs 24.4)
-  a.nt = !no_nt && st.T < p->n && !(from_zero && st.zero_in) && !init_zero &&
-                 ((uint64_t)batch << (p->n + 3)) >= (1ull << 30)
-             ? 1 : 0;
+  a.nt = st.T < p->n && !(from_zero && st.zero_in) && !init_zero &&
+         ((uint64_t)batch << (p->n + 3)) >= (1ull << 30) ? 1 : 0;
   a.mw_lean = meas == TM_STORE_MW && mw_lean(p->n, st) ? 1 : 0;  // (run_mw_fused asks the same question)
   // the state this pass stores is read back by the later reads only after >= 1 GiB more has been written: streaming
   // stores keep it from lingering dirty in the Infinity Cache, where its write-back would run into the first
-  // later read (measured n = 28: that read 0.41 ms behind plain stores, 0.31 ms stand-alone) -- QMLE_MW_NT=0: A/B
+  // later read (measured n = 28: that read 0.41 ms behind plain stores, 0.31 ms stand-alone).
   // The same holds for the LAST storing pass of any run whose states exceed the caches (TM_STORE, no tile stage
   // behind it): whatever reads them next -- the stand-alone Meyer-Wallach reads, a <Z> sweep, the caller -- finds
-  // HBM idle instead of a write-back in progress.  QMLE_LAST_PASS_NT=0: A/B (read per launch).
-  if ((meas == TM_STORE_MW || (meas == TM_STORE && !st.next_tile && !init_zero)) && st.T < p->n && !no_nt &&
-      ((uint64_t)batch << (p->n + 3)) >= (1ull << 30)) {
-    const char *e = std::getenv("QMLE_LAST_PASS_NT");
-    if (!e || atoi(e) != 0) a.nt = 1;
-  }
+  // HBM idle instead of a write-back in progress.
+  if ((meas == TM_STORE_MW || (meas == TM_STORE && !st.next_tile && !init_zero)) && st.T < p->n &&
+      ((uint64_t)batch << (p->n + 3)) >= (1ull << 30))
+    a.nt = 1;
   const size_t lds = tile_lds_bytes(st.T, st.L, a.slots_in_lds ? a.n_ops : 0);
   if (FirstUse once{0}; once.first) {
     QMLE_LDS_BASE_CHECK(k_tile<false>);
@@ -1697,59 +1585,13 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
                             // common kernel keeps its register budget
   for (int g = st.grp_begin; g < st.grp_end; ++g) has_dense4 |= p->op_groups[g].kind == GK_DENSE4 || p->op_groups[g].kind == GK_REG4X;
   const unsigned tiles = 1u << (p->n - st.T);
-  // Prefetching variant: tiles are loaded (not generated), the geometry is the standard one
-  // (2^(T-4) threads, 8 DMAs per wave) and every workgroup gets a run of >= 4 tiles.
-  const uint64_t total = (uint64_t)tiles * (uint64_t)batch;
   const int threads = tile_threads(st.T);
-  const size_t lds_pf = lds + ((size_t)8 << st.T);
-  static int n_cu_of[kMaxDevices] = {};
-  int &n_cu = n_cu_of[current_device()];
-  if (!n_cu) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, current_device()) == hipSuccess && v > 0)
-      n_cu = v;
-    else
-      n_cu = 256;
-  }
-  const unsigned wg_per_cu = (unsigned)(160 * 1024 / lds_pf);
-  // Opt-in (plan flag or QMLE_PREFETCH=1): measured SLOWER than k_tile on MI355X (K2, n = 24:
-  // 354 vs 248 ms per 1024 states) -- two tile buffers leave room for 2 workgroups = 2 waves
-  // per SIMD, and the gate groups need >= 4 to hide their own LDS / VALU latencies.
-  static const bool pf_env_on = std::getenv("QMLE_PREFETCH") != nullptr;
-  const bool pf_ok = (pf_env_on || (p->flags & QMLE_PLAN_PREFETCH)) && !init_zero && meas != TM_EXPVAL && a.slots_in_lds && st.L >= 1 &&
-                     (st.T == 12 || st.T == 13) && threads == (1 << (st.T - 4)) &&
-                     wg_per_cu >= 1 && total < (1ull << 31) &&
-                     total >= 4ull * n_cu * wg_per_cu;
-  if (pf_ok) {
-    if (FirstUse once{1}; once.first) {
-      QMLE_LDS_BASE_CHECK(k_tile_pf<false>);
-      QMLE_LDS_BASE_CHECK(k_tile_pf<true>);
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile_pf<false>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile_pf<true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      once.done();
-    }
-    const unsigned wgs = (unsigned)n_cu * wg_per_cu;
-    const uint32_t chunk = (uint32_t)((total + wgs - 1) / wgs);
-    const unsigned gx = (unsigned)((total + chunk - 1) / chunk);
-    if (has_dense4)
-      hipLaunchKernelGGL(k_tile_pf<true>, dim3(gx), dim3(threads), lds_pf, stream, a, tiles,
-                         (uint32_t)total, chunk);
-    else
-      hipLaunchKernelGGL(k_tile_pf<false>, dim3(gx), dim3(threads), lds_pf, stream, a, tiles,
-                         (uint32_t)total, chunk);
-    HIPCHK(hipGetLastError());
-    return QMLE_OK;
-  }
   dim3 grid(tiles, (unsigned)batch);
   // All-live initialising pass (no known-zero bookkeeping downstream, so every tile must be
   // stored): the zeros come from a plain fill at the rate of a fill, tile 0 of every state from
   // the tile kernel behind it (15 us per 32 states) -- 22.4 -> 20.2 us per 2^24-amplitude state.
-  static const bool no_fill = std::getenv("QMLE_NO_INIT_FILL") != nullptr;
-  if (init_zero && !from_zero && meas == TM_STORE && st.T < p->n && !no_fill && tiles > 1 &&
-      (st.fast_ok || st.T == kLdsMaxQubits) && p->n <= 28 && threads == (1 << (st.T - 4)) &&
-      !(p->flags & QMLE_PLAN_PREFETCH)) {
+  if (init_zero && !from_zero && meas == TM_STORE && st.T < p->n && tiles > 1 &&
+      (st.fast_ok || st.T == kLdsMaxQubits) && p->n <= 28 && threads == (1 << (st.T - 4))) {
     launch_fill_zero(states, ((uint64_t)batch << p->n) / 2u /* float4 = two amplitudes */, stream);
     a.compact = 1;  // grid = the tiles that can be non-zero = tile 0
     a.tile_free = 0u;
@@ -1767,30 +1609,23 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       grid.x = 1u << __builtin_popcount(a.tile_free);
     }
   }
-  static const bool no_product = std::getenv("QMLE_NO_PRODUCT") != nullptr;
-  if (from_zero && cols && st.product_ok && !init_zero && meas == TM_STORE && !no_product &&
+  if (from_zero && cols && st.product_ok && !init_zero && meas == TM_STORE &&
       threads == (1 << (st.T - 4))) {
     const int G = st.grp_end - st.grp_begin;
     const int items = G * batch;
     hipLaunchKernelGGL(k_fold_columns, dim3((items + 63) / 64), dim3(64), 0, stream, p->dev.d_ops,
                        p->dev.d_op_groups + st.grp_begin, G, mats, p->mat_floats, cols, batch);
     // streaming layout when the pass may leave known-zero outputs unwritten, bit 0 is live and
-    // there are at least ~128 workgroups of 512 live amplitudes
+    // there are at least 128 workgroups of 512 live amplitudes (K2, 32 states = 256 workgroups:
+    // 49 vs 73 us in the tile layout)
     uint32_t live = ~st.zero_in & (p->n >= 32 ? ~0u : ((1u << p->n) - 1u));
     const int n_live = __builtin_popcount(live);
-    static const bool no_stream = std::getenv("QMLE_NO_PRODUCT_STREAM") != nullptr;
     uint32_t gm_global = 0;
     for (int g = 0; g < G; ++g)
       for (int i = 0; i < 4; ++i)
         gm_global |= 1u << st.tile_bits[p->op_groups[st.grp_begin + g].bits[i]];
     const bool zeros_may_stay = st.next_tile || (st.zero_in & ~gm_global) == 0;
-    static const uint64_t stream_min_wgs = [] {
-      const char *e = std::getenv("QMLE_STREAM_MIN_WGS");
-      const long v = e ? atol(e) : 0;
-      return (uint64_t)(v > 0 ? v : 128);  // K2, 32 states = 256 workgroups: 49 vs 73 us (tile layout)
-    }();
-    if (zeros_may_stay && (live & 1u) && n_live >= 9 && !no_stream &&
-        ((uint64_t)batch << (n_live - 9)) >= stream_min_wgs) {
+    if (zeros_may_stay && (live & 1u) && n_live >= 9 && ((uint64_t)batch << (n_live - 9)) >= 128) {
       ProductArgs pa;
       std::memset(&pa, 0, sizeof(pa));
       pa.states = states;
@@ -1824,12 +1659,9 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
   }
   // fast path: all-live stage of (controlled) 2x2 gates -- table-addressed groups, CX folded
   // into the LDS layout, SGPR matrices (k_tile2)
-  static const bool no_fast = std::getenv("QMLE_NO_FAST_TILE") != nullptr;
   // (k_tile2 addresses a tile with 32-bit byte offsets inside one state: n <= 28; a whole state
   // of 10..13 qubits is one tile per sample: T == n, <Z> through the TM_EXPVAL epilogue)
-  static const bool no_fast_whole = std::getenv("QMLE_NO_FAST_WHOLE") != nullptr;
-  if (!no_fast && st.fast_ok && p->n <= 28 && threads == (1 << (st.T - 4)) &&
-      (st.T < p->n ? meas != TM_EXPVAL : !no_fast_whole)) {
+  if (st.fast_ok && p->n <= 28 && threads == (1 << (st.T - 4)) && (st.T == p->n || meas != TM_EXPVAL)) {
     if (FirstUse once{2}; once.first) {
 #define QMLE_T2_LDS(NT, ME, MU)                                                   \
   QMLE_LDS_BASE_CHECK((k_tile2<NT, ME, MU>));                                      \
@@ -1911,19 +1743,17 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
     // registers), as long as the grid still fills the chip a few times over
     // (default 4 for storing passes, 8 for the measuring pass, whose per-workgroup reduction is
     // then shared by 8 tiles: K2 pass 3 29.2 / 24.5 / 23.8 / 23.6 us per state at 1 / 2 / 4 / 8)
-    static const int tpw_env = std::getenv("QMLE_T2_TPW") ? atoi(std::getenv("QMLE_T2_TPW")) : 0;
     // (Meyer-Wallach rows keep one tile per workgroup: a walk of 4-16 tiles that carries the ~40 sums in
     // registers and reduces once was built and measured at n = 28 -- 128 VGPRs + 64 B of scratch, no room
     // for the next tile's prefetch: 792 us for the pass against 678 with a row per tile, 473 without sums)
-    const int tpw_max = tpw_env > 0 ? tpw_env : (meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) ? 8 : 4;
+    const int tpw_max = (meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) ? 8 : 4;
     const uint64_t min_wgs = 5120;
     f.tpw = 1;
     f.tile_stride = 0;
     // (known zeros inside the tile are fine -- the walk's loads skip them; known-zero TILES are not)
     const bool multi_zin = std::getenv("QMLE_NO_MULTI_ZIN") == nullptr;  // (read per launch: the A/B test toggles it)
-    // (Z-parity observables walk too -- tile_m_accumulate -- when the caller can take rows per walk; QMLE_NO_MASKS_MULTI=1: A/B)
-    static const bool no_masks_multi = std::getenv("QMLE_NO_MASKS_MULTI") != nullptr;
-    const bool masks_walk = meas == TM_EXPVAL_MASKS && n_obs <= kMaskMultiObs && row_shift && st.T >= 10 && !no_masks_multi;
+    // (Z-parity observables walk too -- tile_m_accumulate -- when the caller can take rows per walk)
+    const bool masks_walk = meas == TM_EXPVAL_MASKS && n_obs <= kMaskMultiObs && row_shift && st.T >= 10;
     if (!a.init_zero && (!a.zin_local || multi_zin) && !a.zin_outer && !a.compact && st.T < p->n &&
         (meas == TM_STORE || meas == TM_PROBS || meas == TM_EXPVAL_PARTIAL || masks_walk)) {
       // (consecutive tile indices differ in the lowest run of outer bit positions only)
@@ -1944,29 +1774,21 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
         *row_shift = 31 - __builtin_clz((unsigned)f.tpw);
       }
     }
-    static const bool dbg_launch = std::getenv("QMLE_DBG_LAUNCH") != nullptr;
-    if (dbg_launch) fprintf(stderr, "[launch_tile] T=%d init_zero=%d zin_local=%x zin_outer=%x compact=%d meas=%d tpw=%d grid=(%u,%u)\n", st.T, a.init_zero, a.zin_local, a.zin_outer, a.compact, meas, f.tpw, grid.x, grid.y);
-    static const int dbg = std::getenv("QMLE_DBG_T2") ? atoi(std::getenv("QMLE_DBG_T2")) : 0;
-    f.dbg = dbg;
-    if (dbg & 1) f.n_groups = 0;
     // T >= 10: the per-tile epilogues' scratch fits inside the tile; the whole-state <Z> epilogue
     // reduces while amplitudes are still being read and gets its own 288 floats
     // (whole_state_expval: one float per observable and wave -- 128 B at 10 qubits instead of the
     // 1152 B of round 2's epilogue: 18-19 instead of 17 single-wave workgroups per CU)
-    // (QMLE_T2_LDS_PAD=<bytes>: occupancy experiment -- fewer workgroups per CU; read per launch)
-    const char *pad_env = std::getenv("QMLE_T2_LDS_PAD");
-    const size_t lds2 = ((size_t)8 << st.T) + (pad_env ? (size_t)atoi(pad_env) : 0) +
+    const size_t lds2 = ((size_t)8 << st.T) +
                         (meas == TM_EXPVAL ? (size_t)QMLE_MAX_QUBITS * (threads >= kWave ? threads / kWave : 1) * sizeof(float) : 0);
     const bool measure = !(meas == TM_STORE || meas == TM_PROBS);
 #define QMLE_T2_GO(NT, ME, MU) \
   hipLaunchKernelGGL((k_tile2<NT, ME, MU>), grid, dim3(threads), lds2, stream, a, f)
     const bool multi = f.tpw > 1;
-    static const bool no_ws = std::getenv("QMLE_NO_WS_KERNEL") != nullptr;  // (A/B: the generic instantiation)
     if (meas == TM_STORE_MW || meas == TM_MW_ONLY) {
       if (st.T == p->n) hipLaunchKernelGGL((k_tile2<false, true, false, true, true>), grid, dim3(threads), lds2, stream, a, f);
       else if (a.nt) hipLaunchKernelGGL((k_tile2<true, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
       else hipLaunchKernelGGL((k_tile2<false, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-    } else if (st.T == p->n && !multi && !a.nt && !no_ws) {  // the whole state in one tile (10..13 qubits)
+    } else if (st.T == p->n && !multi && !a.nt) {  // the whole state in one tile (10..13 qubits)
       if (measure) hipLaunchKernelGGL((k_tile2<false, true, false, true>), grid, dim3(threads), lds2, stream, a, f);
       else hipLaunchKernelGGL((k_tile2<false, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
     } else if (measure && multi && meas == TM_EXPVAL_MASKS) {
@@ -1996,8 +1818,7 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
 // k_reg_measure* takes the last pass of a <Z> run when all its gates share one register-tile
 // group (expval_kernel_of, qmle_plan.cpp)
 int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs) {
-  static const bool off = std::getenv("QMLE_NO_REG_MEASURE") != nullptr;
-  if (off || n_obs < 1 || n_obs > 32) return 0;
+  if (n_obs < 1 || n_obs > 32) return 0;
   return expval_kernel_of(p, si, plan_sparse(p));
 }
 
@@ -2034,8 +1855,7 @@ int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *st
     }
     hipLaunchKernelGGL(k_mono_coef, dim3((batch + 63) / 64), dim3(64), 0, stream, p->dev.d_ops,
                        p->dev.d_op_groups + st.grp_begin, mats, p->mat_floats, mo, n_obs, coef, batch);
-    static const bool no_pair = std::getenv("QMLE_NO_MONO_PAIR") != nullptr;
-    if (!no_pair && g.bits[0] != 0 && st.tile_bits[0] == 0 && !(a.zin_local & 1u) && st.T >= 11 &&
+    if (g.bits[0] != 0 && st.tile_bits[0] == 0 && !(a.zin_local & 1u) && st.T >= 11 &&
         n_outer >= 4) {
       q = 4;
       grid.x = 1u << (n_outer - q);

@@ -346,19 +346,6 @@ __device__ void lds_apply(float2 *__restrict__ s, int T, const LoweredOp op,
   }
 }
 
-// Workgroup barrier.  RAW: bare s_barrier behind an LDS-only wait -- no fence, so neither
-// outstanding global stores nor LDS-DMA prefetches in flight are drained (k_tile_pf);
-// the caller orders its LDS-DMA explicitly.
-template <bool RAW> __device__ __forceinline__ void tile_sync() {
-  if (RAW) {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  } else {
-    __syncthreads();
-  }
-}
-
 // Global bit positions of the tile's high local bits: lut[h] for h = local index >> L.
 __device__ __forceinline__ void tile_build_lut(const TileArgs &a, uint32_t *lut) {
   for (uint32_t h = threadIdx.x; h < (1u << (a.T - a.L)); h += blockDim.x) {
@@ -390,14 +377,14 @@ __device__ __forceinline__ uint64_t tile_base(const TileArgs &a, uint32_t tile) 
 }
 
 // All gate groups of the stage on the tile in `s`; ends with a barrier.
-template <bool DENSE4, bool RAW>
+template <bool DENSE4>
 __device__ __forceinline__ void tile_compute(const TileArgs &a, float2 *s, const OpSlot *slots,
                                              int b) {
   const int T = a.T;
   const float *mrow = a.mats + (size_t)b * a.mat_floats;
   const float *ang = a.angles + (size_t)b * a.n_slots;
-  // local bits still known-zero: work items holding only zeros rest (never set for k_tile_pf)
-  uint32_t z = RAW ? 0u : a.zin_local;
+  // local bits still known-zero: work items holding only zeros rest
+  uint32_t z = a.zin_local;
   for (int gi = 0; gi < a.n_groups; ++gi) {
     const OpGroup g = a.groups[gi];
     if (g.kind == GK_REG4) {
@@ -417,14 +404,14 @@ __device__ __forceinline__ void tile_compute(const TileArgs &a, float2 *s, const
       lds_apply(s, T, a.ops[g.op_begin], mrow, a.consts, ang);
       z = 0;
     }
-    tile_sync<RAW>();
+    __syncthreads();
   }
 }
 
 // Store / measure the finished tile.  n_tiles = tiles per state.
-template <bool RAW, bool PARTIAL_ONLY = false,  // PARTIAL_ONLY: a.meas is TM_EXPVAL_PARTIAL (k_tile2's
-                                                 // multi-tile instantiation keeps its register budget)
-          bool SHIFTED = false>                  // the caller may be handed a Stage::shift tile (k_tile only)
+template <bool PARTIAL_ONLY = false,  // PARTIAL_ONLY: a.meas is TM_EXPVAL_PARTIAL (k_tile2's
+                                       // multi-tile instantiation keeps its register budget)
+          bool SHIFTED = false>        // the caller may be handed a Stage::shift tile (k_tile only)
 __device__ __forceinline__ void tile_epilogue(const TileArgs &a, float2 *s, const uint32_t *lut,
                                               float *red, uint32_t tile, uint32_t n_tiles, int b,
                                               uint64_t base, int qsrc_of_thread = -1) {
@@ -514,13 +501,13 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs &a, float2 *s, cons
       for (int j = 0; j < 6; ++j) v[j] = ((lane >> j) & 1) ? -tot : tot;
       v[6] = h0; v[7] = h1; v[8] = h2; v[9] = h3; v[10] = tot;
       wave_sums_dpp63(v);
-      tile_sync<RAW>();  // k_tile2 keeps `red` INSIDE the tile buffer (32 KiB per workgroup = 5
-                         // workgroups per CU): every amplitude must have been read by now
+      __syncthreads();  // k_tile2 keeps `red` INSIDE the tile buffer (32 KiB per workgroup = 5
+                        // workgroups per CU): every amplitude must have been read by now
       if (lane == kWave - 1) {
 #pragma unroll
         for (int j = 0; j < 11; ++j) red[w * 11 + j] = v[j];
       }
-      tile_sync<RAW>();
+      __syncthreads();
       // thread q < n assembles <Z> of global bit position q itself (qsrc[q], filled on the host:
       // which of the 11 per-wave sums, or which tile-index bit for an outer position), thread 32
       // the total: no staging row, no serial walk over the position arrays
@@ -588,7 +575,7 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs &a, float2 *s, cons
       const uint16_t QMLE_CONSTANT *ol =
           (const uint16_t QMLE_CONSTANT *)((const char QMLE_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TileArgs, obs_local));
       const int n_obs = a.n_obs;
-      tile_sync<RAW>();  // all amplitudes have been read: the tile buffer becomes scratch
+      __syncthreads();  // all amplitudes have been read: the tile buffer becomes scratch
       float *C = reinterpret_cast<float *>(s);  // [n_obs][nw]
       for (int k0 = 0; k0 < n_obs; k0 += 8) {
         float v[8];
@@ -614,7 +601,7 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs &a, float2 *s, cons
             if (k0 + k < n_obs) C[(k0 + k) * nw + wv] = v[k];
         }
       }
-      tile_sync<RAW>();
+      __syncthreads();
       if (tid < n_obs) {
         const uint32_t m = a.obs_mask[tid];
         const uint32_t mw = ((uint32_t)ol[tid] >> 6) & ((1u << (T - 10)) - 1u);

@@ -11,9 +11,9 @@ from qml_essentials_amd import _native as N
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_library_loads_and_exports_header_symbols():
+def test_library_of_abi_150_loads_and_exports_header_symbols():
     lib = N.lib()
-    assert lib.qmle_sv_version() == 149
+    assert lib.qmle_sv_version() == 150
     header = open(os.path.join(ROOT, "include", "qmle_sv.h")).read()
     declared = set(re.findall(r"\b(qmle_[a-z_0-9]+)\s*\(", header))
     declared -= {"qmle_op", "qmle_plan"}
@@ -45,6 +45,27 @@ def test_plan_validation_errors_map_to_valueerror():
         N.Plan([("RX", [0], [2], -1)], 2, 1)
     with pytest.raises(ValueError):
         N.Plan([("Nope", [0], [], -1)], 2, 0)
+    # plan flag 16 is reserved: a plan that asks for it is refused, not run with another schedule
+    with pytest.raises(ValueError, match="qmle_plan_create"):
+        N.Plan([("RX", [0], [0], -1)], 2, 1, flags=16)
+
+
+def test_native_library_reads_only_the_documented_switches():
+    """libqmle_sv reads the nine environment switches documented in csrc/qmle_host.h and no
+    others: the A/B switches of finished experiments stay deleted."""
+    csrc = os.path.join(ROOT, "qml-essentials_amd", "csrc")
+    names = set()
+    for f in os.listdir(csrc):
+        path = os.path.join(csrc, f)
+        if os.path.isfile(path):
+            names |= set(re.findall(r'getenv\("(QMLE_[A-Z0-9_]*)"\)', open(path).read()))
+    survivors = {"QMLE_NO_CHUNK_OVERLAP", "QMLE_MW_FUSE_TILED", "QMLE_NO_TOP_FIRST", "QMLE_FORCE_CAND",
+                 "QMLE_PAD_HIGH", "QMLE_NO_MULTI_ZIN", "QMLE_K1_CTRL_BURST", "QMLE_MW_NO_LEAN",
+                 "QMLE_RNG_THREADS"}
+    assert names == survivors, names ^ survivors
+    host_h = open(os.path.join(csrc, "qmle_host.h")).read()
+    for name in survivors:
+        assert name in host_h, name
 
 
 def he_layer_ops(n):
@@ -133,8 +154,6 @@ def test_hot_kernels_have_no_scratch_and_keep_their_occupancy():
     for name, r in res.items():
         if "k_build_matrices" in name:  # fp64 products of <= 4x4 matrices, indexed at run time:
             continue                    # 20 us per 1024 x 47 matrices, not worth unrolling
-        if "k_tile_pf" in name:         # the opt-in LDS-DMA experiment (measured slower, kept
-            continue                    # for A/B only): its 16x16-operator variant spills 36 B at 512 threads
         assert r["ScratchSize"] == 0 and r["VGPRs Spill"] == 0, (name, r)
     tiles = {k: v for k, v in res.items() if "6k_tileILb" in k}
     assert len(tiles) == 4  # <DENSE4> x <MW>
@@ -178,7 +197,7 @@ def test_xor_addressed_tile_kernels_have_no_static_lds():
         G.build(force=True)
     res = json.load(open(G.RESOURCES))
     xor_kernels = {k: v for k, v in res.items()
-                   if any(t in k for t in ("6k_tileILb", "k_tile2", "k_tile_pf", "k_mw_tile2", "k_mw_read"))}
+                   if any(t in k for t in ("6k_tileILb", "k_tile2", "k_mw_tile2", "k_mw_read"))}
     assert len(xor_kernels) >= 14
     for name, r in xor_kernels.items():
         assert r["LDS Size"] == 0, (name, r)

@@ -256,8 +256,8 @@ def test_c4_fourier_grid_full_size_sampled_oracle():
 
 def test_fast_tile_kernel_equals_generic_kernel_on_cx_rich_tapes():
     """k_tile2 (host-built address tables, X / CX folded into the LDS layout, asm gate blocks)
-    against the generic k_tile (QMLE_NO_FAST_TILE is read once per process, so the generic side
-    is a plan the fast path refuses: NO_REGTILE) and against the oracle, on random tapes of
+    against the generic k_tile (the generic side is a plan the fast path refuses: NO_REGTILE)
+    and against the oracle, on random tapes of
     1-qubit / controlled gates dense in X / CX."""
     N = _N()
     from oracle import einsum_sim as OE

@@ -202,9 +202,8 @@ def test_golomb_encoding_adjoint_input_gradient():
 
 
 def test_adjoint_tiny_registers_and_streaming_path(monkeypatch):
-    """n = 1, 2 (LDS-resident sweep only) and the per-gate streaming sweep forced at n = 6
-    (QMLE_ADJOINT_NO_LDS is read once per process, so the streaming path is exercised through
-    a 15-qubit circuit instead)."""
+    """n = 1, 2 (LDS-resident sweep only) and the per-gate streaming sweep, exercised through a
+    15-qubit circuit (the LDS-resident sweep takes n <= 13)."""
     def one(th):
         op.RX(th[0], wires=0); op.RY(th[1], wires=0); op.RZ(th[2], wires=0); op.RX(th[3], wires=0)
 

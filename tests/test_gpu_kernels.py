@@ -485,11 +485,11 @@ def test_dense_4wire_operator_and_density_measurements():
 
 @pytest.mark.parametrize("n,B,tile_bits,low_bits", [(18, 40, 12, 4), (18, 33, 12, 7), (19, 17, 13, 5),
                                                      (20, 9, 12, 1)])
-def test_prefetching_tile_kernel_matches_plain_tile_kernel(n, B, tile_bits, low_bits):
-    """k_tile_pf (opt-in double-buffered LDS-DMA variant, one run of tiles per workgroup) against k_tile on the
-    same plan geometry, bit for bit (same arithmetic in the same order), for every epilogue:
+def test_tile_kernel_on_forced_geometry_matches_oracle(n, B, tile_bits, low_bits):
+    """k_tile on a forced plan geometry whose later passes load their tiles, for every epilogue:
     state store, fused all-qubit <Z> partials, probabilities; batch sizes that leave ragged
-    last chunks; and against the oracle for one sample."""
+    last chunks; against the oracle for one sample and the probabilities against the stored
+    state for every sample."""
     from qml_essentials_amd import _native as N
 
     rng = np.random.default_rng(n * 7 + B)
@@ -498,22 +498,20 @@ def test_prefetching_tile_kernel_matches_plain_tile_kernel(n, B, tile_bits, low_
     table = rng.uniform(0, 2 * np.pi, size=(B, len(angles))).astype(np.float32)
     table[0] = angles
     ang = torch.from_numpy(table).cuda()
-    res = {}
-    for name, pf in (("pf", True), ("plain", False)):
-        flags = N.plan_flags(force_global=True, force_tile=True, tile_bits=tile_bits,
-                             low_bits=low_bits, prefetch=pf)
-        plan = N.Plan(ops, n, len(angles), consts, flags)
-        res[name] = (plan.run(ang, "state").cpu().numpy(),
-                     plan.run(ang, "expval", list(range(n))).cpu().numpy(),
-                     plan.run(ang, "probs").cpu().numpy())
-        if name == "pf":
-            kinds = [s["kind"] for s in plan.describe()["stages"]]
-            assert kinds.count("tile") >= 2     # at least one pass loads its tiles
-    for got, want in zip(res["pf"], res["plain"]):
-        assert np.array_equal(got, want)
+    flags = N.plan_flags(force_global=True, force_tile=True, tile_bits=tile_bits, low_bits=low_bits)
+    plan = N.Plan(ops, n, len(angles), consts, flags)
+    state = plan.run(ang, "state").cpu().numpy()
+    ez = plan.run(ang, "expval", list(range(n))).cpu().numpy()
+    probs = plan.run(ang, "probs").cpu().numpy()
+    kinds = [s["kind"] for s in plan.describe()["stages"]]
+    assert kinds.count("tile") >= 2     # at least one pass loads its tiles
+    assert np.allclose(probs, np.abs(state) ** 2, atol=1e-6)
     psi = OE.simulate_pure(oracle_tape(tape, n), n, dtype=np.complex128)
-    assert np.allclose(res["pf"][0][0], psi, atol=2e-6)
-    assert np.allclose(res["pf"][2][0], np.abs(psi) ** 2, atol=1e-6)
+    assert np.allclose(state[0], psi, atol=2e-6)
+    assert np.allclose(probs[0], np.abs(psi) ** 2, atol=1e-6)
+    idx = np.arange(1 << n)
+    want_z = [((1 - 2 * ((idx >> (n - 1 - w)) & 1)) * np.abs(psi) ** 2).sum() for w in range(n)]
+    assert np.abs(ez[0] - want_z).max() < 1e-5
 
 
 def _tail_tape(n, rng, n_head, n_tail):
@@ -576,8 +574,7 @@ def test_parities_with_one_position_in_the_last_tile_take_the_33_sums_epilogue(n
     """Z-parities that meet the last tile pass in at most one bit position (all other factors sit
     on outer positions = bits of the tile index) are measured by the single-bit epilogue with
     per-row signs (run_batch_masks: `semi_single`) instead of the general-mask one: same numbers
-    as the general path (QMLE_NO_SEMI_SINGLE is read once per process, so the reference here is
-    the state + stand-alone parity kernel)."""
+    as the general path (the reference here is the state + stand-alone parity kernel)."""
     from qml_essentials_amd import _native as N
     from tests.test_abi_cpu import he_layer_ops
 

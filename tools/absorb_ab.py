@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """Observable folding as a choice: Hardware-Efficient circuits of 1-4 layers, <Z> on
 all wires, microseconds per state with the engine's own choice between folding the trailing CX
-layer into the observables and applying it, against QMLE_PLAN_NO_ABSORB (always applied).  Run
-with QMLE_ALWAYS_FOLD=1 for the folded side of every row.
+layer into the observables and applying it, against QMLE_PLAN_NO_ABSORB (always applied).
 
     python tools/absorb_ab.py
 """

@@ -54,10 +54,9 @@ tools/mw_tune 24 15 5 32 12,13,14,15,16,17,18,19:2: 6,13,14,15,16,17,18,19:2: 6,
   6,11,13,15,17,19,21,23:2: 6,8,13,14,15,16,17,18:2: 6,13,15,16,17,18,19,20:2: 4,6,13,14,15,16,17,18:2: 5,6,13,14,15,16,17,18:2: 6,7,13,15,16,17,18,19:2: \
   4,11,14,15,16,17,18,19:2: 5,12,14,15,16,17,18,19:2: 7,14,15,16,17,18,19,20:2: 12,13,14,15,20,21,22,23:2: 4,5,6,7,8,9,10,11:2: 16,17,18,19,20,21,22,23:2: \
   | grep "one tile" > $OUT/${TAG}_rw_tile_bits.txt 2>&1 || true
-for d in 0 1; do QMLE_DBG_T2=$d python3 tools/deep_anatomy.py 2>/dev/null | grep DBG; done > $OUT/${TAG}_pass_model.txt || true
+python3 tools/deep_anatomy.py 2>/dev/null | grep DBG > $OUT/${TAG}_pass_model.txt || true
 python3 tools/k2_passes.py 2>/dev/null >> $OUT/${TAG}_pass_model.txt || true
-QMLE_NO_WIDE_FIRST=1 QMLE_NO_CARRY6=1 python3 tools/k2_passes.py 2>/dev/null >> $OUT/${TAG}_pass_model.txt || true
-for nn in 24 22; do echo "n=$nn round-3 schedules"; SWEEP_N=$nn python3 tools/layers_sweep.py 2>/dev/null | grep layers | cut -c1-60; echo "n=$nn round-2 schedules (QMLE_NO_WIDE_FIRST=1 QMLE_NO_CARRY6=1)"; QMLE_NO_WIDE_FIRST=1 QMLE_NO_CARRY6=1 SWEEP_N=$nn python3 tools/layers_sweep.py 2>/dev/null | grep layers | cut -c1-60; done > $OUT/${TAG}_layers_sweep.txt || true
+for nn in 24 22; do echo "n=$nn"; SWEEP_N=$nn python3 tools/layers_sweep.py 2>/dev/null | grep layers | cut -c1-60; done > $OUT/${TAG}_layers_sweep.txt || true
 python3 tools/configs_bench.py 2>/dev/null | grep "^|" > $OUT/${TAG}_configs.md || true
 head -c 600 $OUT/${TAG}_bench_n1.json; echo
 head -n 8 $OUT/${TAG}_bench_kernel_stats.csv | cut -c1-160

@@ -104,10 +104,6 @@ if has rows; then
   cd $R
   python3 tools/next_rows_bench.py > $OUT/next_rows_now.md 2> $OUT/next_rows.err || true
   {
-    echo "== one LDS sweep per superoperator, gates unmerged (QMLE_NO_REG2Q=1 QMLE_NO_MERGE_2Q=1)"
-    QMLE_NO_REG2Q=1 QMLE_NO_MERGE_2Q=1 python3 tools/noise_plan_profile.py 2>&1 | grep -v amdgpu.ids
-    echo "== 4x4 operators in register-tile groups (QMLE_NO_MERGE_2Q=1)"
-    QMLE_NO_MERGE_2Q=1 python3 tools/noise_plan_profile.py 2>&1 | grep -v amdgpu.ids
     echo "== default: gates and channels merged into the 4x4 operators"
     python3 tools/noise_plan_profile.py 2>&1 | grep -v amdgpu.ids
     echo "== host profile of one noisy Model(10, 2) call, 64 parameter sets (compiled call)"

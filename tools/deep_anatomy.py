@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-pass HIP-event times of the all-live 4-layer data-re-uploading circuit at n = 24 (k2_deep of
-bench.py) -- run under QMLE_DBG_T2 = 0 / 4 / 8 / 1 to see what the gate loop's scalar side costs."""
+bench.py)."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -34,5 +34,5 @@ e1.record(); torch.cuda.synchronize()
 ms, cnt, _ = plan.profile_end()
 per = [m / reps / B * 1e3 for m in ms]
 print("   stages:", [(s["T"], s["L"], s["bits"][s["L"] if s["L"] < s["T"] else 0:], s.get("expval_kernel"), bin(s["zero_in"]).count("1")) for s in d["stages"]], "absorbed", top.describe().get("absorbed_ops"))
-print(f"DBG={os.environ.get('QMLE_DBG_T2', '0')}: {e0.elapsed_time(e1) / reps / B * 1e3:.1f} us/state; per pass (groups: us): ",
+print(f"DBG: {e0.elapsed_time(e1) / reps / B * 1e3:.1f} us/state; per pass (groups: us): ",
       [(len(s.get('fast_groups') or s.get('groups') or []), round(t, 1)) for s, t in zip(d["stages"], per)], flush=True)

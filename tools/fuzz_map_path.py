@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Differential check of the three routes a batched Model call can take to its gate matrices: CUDA-tensor
 arguments (qmle_run_batch_map: from 64 samples on the matrices are built straight from the affine angle
-map), the same with QMLE_NO_MAP_FUSION=1 (angle table, then matrices from the table) and host arrays (the
-table formed on the host in float64).  The first two must agree bit for bit, the third to 2e-6; every ansatz,
-random sizes / encodings / batch shapes with 64+ samples."""
+map) and host arrays (the angle table formed on the host in float64, then qmle_run_batch with the matrices
+built from the table).  They must agree to 2e-6; every ansatz, random sizes / encodings / batch shapes with
+64+ samples.  (The bit-for-bit comparison with qmle_build_angles + qmle_run_batch is
+tests/test_gpu_kernels.py's.)"""
 import os, sys, warnings
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,15 +40,12 @@ for trial in range(int(os.environ.get("FUZZ_N", "120"))):
         print("ERROR", kw, B_I, B_P, et, repr(e)[:200])
         bad += 1
         continue
-    os.environ["QMLE_NO_MAP_FUSION"] = "1"
-    b = m(params=pd, inputs=xd, execution_type=et)
-    del os.environ["QMLE_NO_MAP_FUSION"]
     c = m(params=p, inputs=x, execution_type=et)
-    a, b = a.cpu().numpy(), b.cpu().numpy()
+    a = a.cpu().numpy()
     ran += 1
-    ok = np.array_equal(a, b) and a.shape == np.shape(c) and np.abs(a - np.asarray(c)).max() < 2e-6
+    ok = a.shape == np.shape(c) and np.abs(a - np.asarray(c)).max() < 2e-6
     if not ok:
         bad += 1
-        print("MISMATCH", kw, B_I, B_P, et, a.shape, np.shape(c), float(np.abs(a - b).max()),
+        print("MISMATCH", kw, B_I, B_P, et, a.shape, np.shape(c),
               float(np.abs(a - np.asarray(c)).max()) if a.shape == np.shape(c) else None)
 print(f"{ran} models run, mismatches: {bad}")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Whole-state regime (n <= 14: one LDS tile per sample): states per second of the circuit +
-<Z> launch, HIP-event timed.  QMLE_NO_FAST_WHOLE=1 selects the generic k_tile for A/B."""
+<Z> launch, HIP-event timed."""
 import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
