@@ -361,12 +361,6 @@ k_adj_final(const float2 *__restrict__ partial, int n_blocks, int n_y, float coe
 }  // namespace
 
 // ---- adjoint gradient ------------------------------------------------------------------------
-static uint32_t wires_to_pos(uint32_t wires, int n) {
-  uint32_t m = 0;
-  for (int w = 0; w < n; ++w)
-    if (wires & (1u << w)) m |= 1u << (n - 1 - w);
-  return m;
-}
 static int adj_blocks(int n) {
   const uint64_t chunks = (uint64_t)1 << (n - 1);
   uint64_t b = (chunks + 256 * 8 - 1) / (256 * 8);
@@ -411,7 +405,7 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
                           const qmle_adjoint_term *terms, int n_terms, float *d_grad,
                           int n_grad_slots, void *d_workspace, size_t workspace_bytes,
                           qmle_stream stream_) {
-  if (!fwd || !rev || batch < 1 || 2 * batch > 65535 || !d_weights || !obs_wire_masks ||
+  if (!fwd || !rev || batch < 1 || 2 * batch > kMaxGridY || !d_weights || !obs_wire_masks ||
       n_obs < 1 || n_obs > QMLE_MAX_QUBITS || !terms || !d_grad || n_grad_slots < 1 ||
       !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
     return QMLE_ERR_INVALID_ARG;
@@ -432,12 +426,10 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
   int rc = ensure_device_plan(rev);
   if (rc != QMLE_OK) return rc;
   char *ws = (char *)d_workspace;
-  const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
   const AdjLayout L = adj_layout(fwd, rev, batch);
-  if (workspace_bytes < mis + L.total) return QMLE_ERR_WORKSPACE;
-  ws += mis;
+  if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
   for (int k = 0; k < n_obs; ++k)
-    if (obs_wire_masks[k] == 0 || (n < 32 && (obs_wire_masks[k] >> n))) return QMLE_ERR_WIRE_RANGE;
+    if (!valid_wire_mask(obs_wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
   for (int r = 0; r < n_terms; ++r)
     if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
 
@@ -466,10 +458,7 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
         return QMLE_ERR_INVALID_ARG;
     }
     // reverse tape + terms live in a blob owned by the reverse plan (uploaded when they change)
-    uint64_t hsh = 1469598103934665603ull;
-    for (size_t i = 0; i < tdev.size() * sizeof(AdjTermDev); ++i)
-      hsh = (hsh ^ ((const unsigned char *)tdev.data())[i]) * 1099511628211ull;
-    hsh ^= (uint64_t)R * 0x9E3779B97F4A7C15ull;
+    const uint64_t hsh = fnv1a(tdev.data(), tdev.size() * sizeof(AdjTermDev)) ^ ((uint64_t)R * 0x9E3779B97F4A7C15ull);
     const size_t ops_b = align_up((size_t)(R ? R : 1) * sizeof(LoweredOp), 256);
     if (!rev->adj_blob || rev->adj_hash != hsh) {
       if (rev->adj_blob) (void)hipFree(rev->adj_blob);
@@ -538,7 +527,7 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
 
   // forward: psi = U_N .. U_1 |0>
   rc = run_batch_masks(fwd, d_angles_fwd, batch, QMLE_MEAS_STATE, nullptr, 0, psi, ws + L.fwd_ws,
-                       workspace_bytes - mis - L.fwd_ws, stream);
+                       workspace_bytes - L.fwd_ws, stream);
   if (rc != QMLE_OK) return rc;
   // lambda = (sum_k w_k Z..Z_k) psi
   ZSumArgs z;
@@ -592,14 +581,10 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
       }
       st_n_terms.push_back(cnt);
     }
-    uint64_t hsh = 1469598103934665603ull;
-    auto mix = [&](const void *ptr, size_t bytes) {
-      for (size_t i = 0; i < bytes; ++i) hsh = (hsh ^ ((const unsigned char *)ptr)[i]) * 1099511628211ull;
-    };
-    mix(term_idx.data(), term_idx.size() * 4);
-    mix(gtype.data(), gtype.size() * 4);
-    mix(slot_of.data(), slot_of.size() * 4);
-    mix(coef_of.data(), coef_of.size() * 4);
+    uint64_t hsh = fnv1a(term_idx.data(), term_idx.size() * 4);
+    hsh = fnv1a(gtype.data(), gtype.size() * 4, hsh);
+    hsh = fnv1a(slot_of.data(), slot_of.size() * 4, hsh);
+    hsh = fnv1a(coef_of.data(), coef_of.size() * 4, hsh);
     const size_t nt_tot = slot_of.size() ? slot_of.size() : 1;
     const size_t o1 = align_up(term_idx.size() * 4, 256), o2 = o1 + align_up(gtype.size() * 4, 256),
                  o3 = o2 + align_up(nt_tot * 4, 256);

@@ -1254,7 +1254,7 @@ int qmle_expval_z(const void *d_states, int n_qubits, int batch, const int32_t *
                   int n_obs, float *d_out, void *d_workspace, size_t workspace_bytes,
                   qmle_stream stream) {
   if (!d_states || !d_out || !d_workspace || !obs_wires || n_qubits < 1 ||
-      n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > 65535)
+      n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > kMaxGridY)
     return QMLE_ERR_INVALID_ARG;
   if (n_obs < 1 || n_obs > QMLE_MAX_QUBITS) return QMLE_ERR_INVALID_ARG;
   int8_t bits[QMLE_MAX_QUBITS];
@@ -1269,19 +1269,15 @@ int qmle_expval_z(const void *d_states, int n_qubits, int batch, const int32_t *
 int qmle_probs(const void *d_states, int n_qubits, int batch, float *d_out, qmle_stream stream) {
   if (!d_states || !d_out || n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS || batch < 1)
     return QMLE_ERR_INVALID_ARG;
-  const uint64_t tc = (uint64_t)batch << (n_qubits - 1);
-  hipLaunchKernelGGL(k_probs, dim3(grid_for(tc, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const float4 *)d_states, (float2 *)d_out, tc);
+  launch_probs((const float2 *)d_states, d_out, (uint64_t)batch << (n_qubits - 1), (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
 
 int qmle_density(const void *d_states, int n_qubits, int batch, void *d_out, qmle_stream stream) {
-  if (!d_states || !d_out || n_qubits < 1 || batch < 1 || batch > 65535) return QMLE_ERR_INVALID_ARG;
+  if (!d_states || !d_out || n_qubits < 1 || batch < 1 || batch > kMaxGridY) return QMLE_ERR_INVALID_ARG;
   if (n_qubits > 15) return QMLE_ERR_UNSUPPORTED;
-  const uint64_t D = (uint64_t)1 << n_qubits;
-  hipLaunchKernelGGL(k_density, dim3(grid_for(D * D, 256, 1u << 20), batch), dim3(256), 0,
-                     (hipStream_t)stream, (const float2 *)d_states, (float2 *)d_out, n_qubits);
+  launch_density((const float2 *)d_states, (float2 *)d_out, n_qubits, batch, (hipStream_t)stream);
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
@@ -1289,7 +1285,7 @@ int qmle_density(const void *d_states, int n_qubits, int batch, void *d_out, qml
 int qmle_marginal_probs(const void *d_states, int n_qubits, int batch, const int32_t *keep_wires,
                         int n_keep, float *d_out, qmle_stream stream_) {
   if (!d_states || !d_out || !keep_wires || n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS ||
-      batch < 1 || batch > 65535 || n_keep < 1 || n_keep > n_qubits || n_keep > 24)
+      batch < 1 || batch > kMaxGridY || n_keep < 1 || n_keep > n_qubits || n_keep > 24)
     return QMLE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   // kept wires stay in ascending wire order regardless of `keep` order
@@ -1340,8 +1336,8 @@ int qmle_pair_fidelity(const void *d_states, int n_qubits, int n_pairs, float *d
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
-  for (int p0 = 0; p0 < n_pairs; p0 += 65535) {
-    const int pc = n_pairs - p0 < 65535 ? n_pairs - p0 : 65535;
+  for (int p0 = 0; p0 < n_pairs; p0 += kMaxGridY) {
+    const int pc = n_pairs - p0 < kMaxGridY ? n_pairs - p0 : kMaxGridY;
     // pairs (i, i + n_pairs): shift both halves by p0
     hipLaunchKernelGGL(k_overlap_partial, dim3(nb, pc), dim3(256), 0, stream,
                        (const float4 *)d_states + (size_t)p0 * chunks, n_qubits, n_pairs,
@@ -1356,7 +1352,7 @@ int qmle_pair_fidelity(const void *d_states, int n_qubits, int n_pairs, float *d
 int qmle_density_probs(const void *d_rho, int n_qubits, int batch, float *d_out,
                        qmle_stream stream) {
   if (!d_rho || !d_out || n_qubits < 1 || 2 * n_qubits > QMLE_MAX_QUBITS || batch < 1 ||
-      batch > 65535)
+      batch > kMaxGridY)
     return QMLE_ERR_INVALID_ARG;
   const uint64_t D = (uint64_t)1 << n_qubits;
   hipLaunchKernelGGL(k_density_probs, dim3(grid_for(D, 256), batch), dim3(256), 0,
@@ -1368,7 +1364,7 @@ int qmle_density_probs(const void *d_rho, int n_qubits, int batch, float *d_out,
 int qmle_density_expval_z(const void *d_rho, int n_qubits, int batch, const int32_t *obs_wires,
                           int n_obs, float *d_out, qmle_stream stream) {
   if (!d_rho || !d_out || !obs_wires || n_qubits < 1 || 2 * n_qubits > QMLE_MAX_QUBITS ||
-      batch < 1 || batch > 65535 || n_obs < 1 || n_obs > QMLE_MAX_QUBITS)
+      batch < 1 || batch > kMaxGridY || n_obs < 1 || n_obs > QMLE_MAX_QUBITS)
     return QMLE_ERR_INVALID_ARG;
   ObsBits ob;
   for (int k = 0; k < n_obs; ++k) {
@@ -1395,8 +1391,8 @@ int qmle_overlap(const void *d_a, const void *d_b, int n_qubits, int count, void
   if (workspace_bytes < (size_t)count * nb * sizeof(float2)) return QMLE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   const uint64_t chunks = (uint64_t)1 << (n_qubits - 1);
-  for (int p0 = 0; p0 < count; p0 += 65535) {
-    const int pc = count - p0 < 65535 ? count - p0 : 65535;
+  for (int p0 = 0; p0 < count; p0 += kMaxGridY) {
+    const int pc = count - p0 < kMaxGridY ? count - p0 : kMaxGridY;
     hipLaunchKernelGGL(k_overlap2_partial, dim3(nb, pc), dim3(256), 0, stream,
                        (const float4 *)d_a + (size_t)p0 * chunks,
                        (const float4 *)d_b + (size_t)p0 * chunks, n_qubits,
@@ -1417,31 +1413,16 @@ int qmle_expval_parity(const void *d_states, int n_qubits, int batch, const uint
                        int n_obs, float *d_out, void *d_workspace, size_t workspace_bytes,
                        qmle_stream stream_) {
   if (!d_states || !d_out || !d_workspace || !wire_masks || n_qubits < 1 ||
-      n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > 65535 || n_obs < 1)
+      n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > kMaxGridY || n_obs < 1)
     return QMLE_ERR_INVALID_ARG;
-  const int nb = overlap_blocks(n_qubits);
-  if (workspace_bytes < (size_t)batch * nb * 8 * sizeof(float)) return QMLE_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
-  for (int o0 = 0; o0 < n_obs; o0 += 8) {
-    ParityMasks pm;
-    pm.count = n_obs - o0 < 8 ? n_obs - o0 : 8;
-    for (int k = 0; k < 8; ++k) {
-      uint32_t bits = 0;
-      if (k < pm.count) {
-        const uint32_t wm = wire_masks[o0 + k];  // bit w set <=> wire w in the parity
-        if (n_qubits < 32 && (wm >> n_qubits)) return QMLE_ERR_WIRE_RANGE;
-        for (int w = 0; w < n_qubits; ++w)
-          if (wm & (1u << w)) bits |= 1u << (n_qubits - 1 - w);
-      }
-      pm.m[k] = bits;
-    }
-    hipLaunchKernelGGL(k_parity_partial, dim3(nb, batch), dim3(256), 0, stream,
-                       (const float4 *)d_states, n_qubits, pm, (float *)d_workspace);
-    hipLaunchKernelGGL(k_parity_final, dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                       (const float *)d_workspace, nb, pm.count, n_obs, o0, d_out);
+  std::vector<uint32_t> pos((size_t)n_obs);
+  for (int k = 0; k < n_obs; ++k) {
+    // bit w set <=> wire w in the parity (no wire at all is accepted here: the state's norm)
+    if (wire_masks[k] != 0 && !valid_wire_mask(wire_masks[k], n_qubits)) return QMLE_ERR_WIRE_RANGE;
+    pos[k] = wires_to_pos(wire_masks[k], n_qubits);
   }
-  HIPCHK(hipGetLastError());
-  return QMLE_OK;
+  return run_parity_pos((const float2 *)d_states, n_qubits, batch, pos.data(), n_obs, d_out, d_workspace,
+                        workspace_bytes, (hipStream_t)stream_);
 }
 
 }  // extern "C"
@@ -1611,7 +1592,7 @@ size_t mw_fused_ws_bytes(int n, int batch, const Stage &last) {
 // the purities follow it.  d_out [batch][n + 1] = (Q, purities by wire).
 int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int row_shift, void *ws_,
                  size_t ws_bytes, float *d_out, hipStream_t stream) {
-  if (batch < 1 || batch > 65535) return QMLE_ERR_INVALID_ARG;
+  if (batch < 1 || batch > kMaxGridY) return QMLE_ERR_INVALID_ARG;
   if (ws_bytes < mw_fused_ws_bytes(n, batch, last) - 512) return QMLE_ERR_WORKSPACE;
   float *ws = (float *)ws_;
   MwFusedArgs pa;
@@ -1758,7 +1739,7 @@ int qmle_meyer_wallach(const void *d_states, int n_qubits, int batch, float *d_o
                        float *d_purities, void *d_workspace, size_t workspace_bytes,
                        qmle_stream stream_) {
   if (!d_states || !d_out || !d_workspace || n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS ||
-      batch < 1 || batch > 65535)
+      batch < 1 || batch > kMaxGridY)
     return QMLE_ERR_INVALID_ARG;
   if (workspace_bytes + 256 < qmle_meyer_wallach_workspace_bytes(n_qubits, batch))
     return QMLE_ERR_WORKSPACE;
@@ -1890,7 +1871,7 @@ int qmle_sample_counts(const float *d_probs, int n_qubits, int batch, int shots,
                        uint64_t row_offset, int32_t *d_counts, float *d_est_probs,
                        void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
   if (!d_probs || !d_counts || !d_workspace || n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS ||
-      batch < 1 || batch > 65535 || shots < 1)
+      batch < 1 || batch > kMaxGridY || shots < 1)
     return QMLE_ERR_INVALID_ARG;
   if (workspace_bytes < qmle_sample_workspace_bytes(n_qubits, batch))
     return QMLE_ERR_WORKSPACE;
@@ -1920,8 +1901,8 @@ int qmle_probs_diag_expval(const float *d_probs, int n_qubits, int batch,
                            float *d_out, void *d_workspace, size_t workspace_bytes,
                            qmle_stream stream_) {
   if (!d_probs || !d_out || !obs_wires || !obs_n_wires || !obs_diag_off || !d_workspace ||
-      n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > 65535 || n_obs < 1 ||
-      n_obs > 65535)
+      n_qubits < 1 || n_qubits > QMLE_MAX_QUBITS || batch < 1 || batch > kMaxGridY || n_obs < 1 ||
+      n_obs > kMaxGridY)
     return QMLE_ERR_INVALID_ARG;
   if (workspace_bytes < (size_t)n_obs * sizeof(DiagObs)) return QMLE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;

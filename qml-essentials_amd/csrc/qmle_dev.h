@@ -262,6 +262,7 @@ inline unsigned grid_for(uint64_t items, unsigned block, unsigned cap = 1u << 30
   if (g > cap) g = cap;
   return (unsigned)g;
 }
+constexpr int kMaxGridY = 65535;  // grid.y (and grid.z) limit: states / pairs / groups per launch of a (x, batch) grid
 
 // hipFuncSetAttribute (160 KiB dynamic LDS) and the CU count are per DEVICE: a process that
 // drives several GPUs (one process per GPU is the supported layout, but nothing stops a caller)

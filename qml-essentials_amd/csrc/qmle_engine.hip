@@ -201,6 +201,20 @@ int qmle_device_count(void) {
   return c;
 }
 
+// a new plan, not yet compiled, for `ops` on `base`'s register: its slots and the constants its caller handed in
+// (without the permuted copies a compile appends).  NULL: out of memory.
+static qmle_plan *new_plan_like(const qmle_plan *base, const std::vector<qmle_op> &ops, unsigned flags) {
+  qmle_plan *c = new (std::nothrow) qmle_plan();
+  if (!c) return nullptr;
+  c->n = base->n;
+  c->n_slots = base->n_slots;
+  c->flags = flags;
+  c->ops = ops;
+  c->consts.assign(base->consts.begin(), base->consts.begin() + base->n_user_consts);
+  c->n_user_consts = base->n_user_consts;
+  return c;
+}
+
 int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
                      const float *consts, int n_consts, unsigned flags, qmle_plan **out) {
   if (!out || n_ops < 0 || n_slots < 0 || n_consts < 0 || (n_ops > 0 && !ops))
@@ -226,13 +240,8 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
   // adjoint sweep apply stages to LIVE states and keep `p`'s own schedule.
   if (!p->whole_state_lds && !(flags & QMLE_PLAN_NO_FUSION) &&
       !((flags >> 8) & 0xffffu) && p->stages.size() >= 2 && p->stages[0].kind == ST_TILE) {
-    qmle_plan *v = new (std::nothrow) qmle_plan();
+    qmle_plan *v = new_plan_like(p, p->ops, flags | QMLE_PLAN_INTERNAL_ZERO_RUN);
     if (v) {
-      v->n = n_qubits;
-      v->n_slots = n_slots;
-      v->flags = flags | QMLE_PLAN_INTERNAL_ZERO_RUN;
-      v->ops = p->ops;
-      v->consts.assign(p->consts.begin(), p->consts.begin() + (n_consts > 0 ? n_consts : 0));
       const bool forced = std::getenv("QMLE_FORCE_CAND") != nullptr;  // (tuning: always run the forced schedule)
       if (compile_plan(v) == QMLE_OK && v->mat_floats == p->mat_floats && (forced || v->model_cost < p->model_cost - 0.5))
         p->zero_variant = v;
@@ -246,13 +255,9 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
     std::vector<qmle_op> kept;
     split_expval_tail(p->ops, p->n, kept, p->absorbed);
     if (!p->absorbed.empty()) {
-      qmle_plan *c = new (std::nothrow) qmle_plan();
+      // (a child only ever runs from |0..0>)
+      qmle_plan *c = new_plan_like(p, kept, flags | QMLE_PLAN_NO_ABSORB | QMLE_PLAN_INTERNAL_ZERO_RUN);
       if (c) {
-        c->n = n_qubits;
-        c->n_slots = n_slots;
-        c->flags = flags | QMLE_PLAN_NO_ABSORB | QMLE_PLAN_INTERNAL_ZERO_RUN;  // a child only ever runs from |0..0>
-        c->ops = kept;
-        c->consts.assign(p->consts.begin(), p->consts.begin() + (n_consts > 0 ? n_consts : 0));
         for (const qmle_op &o : p->absorbed) p->absorbed_algo_bytes += algo_bytes(o, p->n);
         c->extra_algo_last_stage = p->absorbed_algo_bytes;
         if (compile_plan(c) == QMLE_OK) p->expval_child = c;
@@ -343,8 +348,6 @@ int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]) {
   return QMLE_OK;
 }
 
-// workspace layout: [matrices: batch * mat_floats] [states: S * D (if needed)]
-//                   [expval partials]
 static size_t ws_matrix_bytes(const qmle_plan *p, int batch) {
   return align_up((size_t)batch * (p->mat_floats ? p->mat_floats : 1) * sizeof(float), 256);
 }
@@ -451,30 +454,86 @@ static SideStreams *side_streams() {
   return &x;
 }
 
-static size_t per_state_ws_bytes(const qmle_plan *p, int meas_type) {
-  size_t b = align_up((size_t)8 << p->n, 256);
-  if (meas_type == QMLE_MEAS_EXPVAL_Z)
-    b += align_up(expval_partial_rows(p) * (QMLE_MAX_QUBITS + 1) * sizeof(float), 256);
-  if (meas_type == QMLE_MEAS_MEYER_WALLACH) b += mw_ws_bytes(p, 1);
-  return b;
+// Workspace of qmle_run_batch, from the first 256-byte boundary of the caller's pointer on:
+//   [matrix rows: batch * mat_floats] [columns of the product stages' groups] [k_mono_coef table]
+//   slot 0: [states of a chunk: in_flight * 2^n] [partial sums / Meyer-Wallach rows of the chunk]
+//   slot 1: the same again, when the chunks alternate between the two internal streams (ChunkPipeline)
+// One function fills it, for the size query and for the run.
+struct BatchLayout {
+  size_t cols = 0, coef = 0;  // fold columns (k_fold_columns), k_mono_coef table; the matrix rows sit at 0
+  bool in_lds = false;        // one launch simulates and measures: no state is stored (run_batch_lds)
+  int in_flight = 0;          // states per chunk
+  int slots = 1;
+  size_t states[2] = {}, partial[2] = {};  // per slot (states: not used when the chunks are rows of d_out)
+  size_t partial_bytes = 0;                // of one slot
+  size_t total = 0;                        // with the slack for aligning the caller's pointer
+};
+// handed == NULL: the layout for chunks of `asked` states (<= 0: the default), i.e. the size query.  Otherwise the
+// layout for a workspace of *handed bytes (a caller may hand in less than the query said): fewer states per chunk,
+// then one slot instead of two; false: not even one state fits.
+static bool batch_layout(const qmle_plan *plan, int batch, int meas_type, int asked, const size_t *handed,
+                         BatchLayout &L) {
+  L.cols = ws_matrix_bytes(plan, batch);
+  L.coef = L.cols + align_up((size_t)batch * (size_t)plan->fold_groups * 16 * sizeof(float2), 256);
+  const size_t base = ws_mats_bytes(plan, batch);
+  if (handed && *handed < base) return false;
+  const size_t room = handed ? *handed - base : ~(size_t)0;
+  L.total = base + 512;
+  L.states[0] = L.partial[0] = base;
+  // a chunk's partial sums: rows of the <Z> epilogues, or Meyer-Wallach rows + purities
+  const size_t partial_one =
+      meas_type == QMLE_MEAS_EXPVAL_Z ? align_up(expval_partial_rows(plan) * (QMLE_MAX_QUBITS + 1) * sizeof(float), 256)
+      : meas_type == QMLE_MEAS_MEYER_WALLACH ? mw_ws_bytes(plan, 1) : 0;
+  if (plan->whole_state_lds &&
+      (meas_type == QMLE_MEAS_STATE || meas_type == QMLE_MEAS_PROBS || meas_type == QMLE_MEAS_EXPVAL_Z ||
+       (meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan)))) {
+    // the state never leaves the LDS; the Meyer-Wallach sums come out of the tile as one block of rows
+    L.in_lds = true;
+    L.in_flight = handed ? std::min(batch, kMaxGridY) : batch;
+    L.partial_bytes = (size_t)L.in_flight * partial_one;
+    if (meas_type != QMLE_MEAS_MEYER_WALLACH) return true;
+    L.total += L.partial_bytes;
+    return room >= L.partial_bytes;
+  }
+  // QMLE_MEAS_STATE: every chunk is its own rows of d_out (sample-major: stay cache-resident)
+  const size_t state_one = align_up((size_t)8 << plan->n, 256);
+  const size_t per = meas_type == QMLE_MEAS_STATE ? 0 : state_one + partial_one;
+  const size_t dflt = (size_t)default_states_in_flight(plan, batch);
+  size_t s = handed || asked <= 0 ? dflt : (size_t)asked;
+  if (handed && per) s = std::min(s, room / per);
+  if (s < 1) return false;
+  s = std::min(s, (size_t)batch);
+  if (handed) s = std::min(s, (size_t)kMaxGridY);
+  // Two slots -- chunks alternate between two internal streams, each with its own state / partial buffers: the
+  // batch has several chunks, the overlap switch is on, the plan is not one streaming pass per gate
+  // (QMLE_PLAN_NO_FUSION is HBM-bound in every pass: two of them at once share the bandwidth and lose 2-3 % to the
+  // mix), the side streams exist, and there is room for two.  A workspace sized by the query holds two slots of the
+  // chunk it was asked for; one that holds less is split in two.
+  // The size query cannot ask for the streams, and it does not look at QMLE_PLAN_NO_FUSION either: for those plans
+  // it reserves a second slot that the run leaves unused.  Sizes stay as they are in this change.
+  bool two = s < (size_t)batch && chunk_overlap_on();
+  if (two && handed) {
+    size_t half = s;
+    if (per) half = std::min(std::min(room / per / 2, dflt), (size_t)kMaxGridY);
+    two = !(plan->flags & QMLE_PLAN_NO_FUSION) && half >= 1 && side_streams() != nullptr;
+    if (two) s = half;
+  }
+  L.in_flight = (int)s;
+  L.slots = two ? 2 : 1;
+  L.partial_bytes = s * partial_one;
+  for (int k = 0; k < L.slots; ++k) {
+    L.states[k] = base + (size_t)k * s * per;
+    L.partial[k] = L.states[k] + (per ? s * state_one : 0);
+  }
+  L.total += (size_t)L.slots * s * per;
+  return true;
 }
 
 size_t qmle::workspace_bytes_one(const qmle_plan *plan, int batch, int meas_type,
                                  int states_in_flight) {
-  size_t total = ws_mats_bytes(plan, batch) + 512;  // + alignment slack
-  const bool lds_direct_meas =
-      plan->whole_state_lds && (meas_type == QMLE_MEAS_PROBS || meas_type == QMLE_MEAS_EXPVAL_Z);
-  if (meas_type == QMLE_MEAS_MEYER_WALLACH && plan->whole_state_lds && plan_mw_fusable(plan))
-    return total + mw_ws_bytes(plan, batch);  // the sums come out of the LDS tile: no state is stored
-  if (meas_type != QMLE_MEAS_STATE && !lds_direct_meas) {
-    int s = states_in_flight > 0 ? states_in_flight : default_states_in_flight(plan, batch);
-    if (s > batch) s = batch;
-    // (a batch of several chunks runs them alternately on two internal streams, each with its own state / partial
-    // buffers -- chunk_overlap below; a caller that hands in less gets the one-stream loop)
-    const int slots = (s < batch && chunk_overlap_on()) ? 2 : 1;
-    total += (size_t)slots * (size_t)s * per_state_ws_bytes(plan, meas_type);
-  }
-  return total;
+  BatchLayout L;
+  batch_layout(plan, batch, meas_type, states_in_flight, nullptr, L);
+  return L.total;
 }
 
 size_t qmle_workspace_bytes(const qmle_plan *plan, int batch, int meas_type, int n_obs,
@@ -502,14 +561,11 @@ static int build_obs_masks(qmle_plan *plan, qmle_plan **exec, const uint32_t *wi
   *exec = plan->expval_child ? plan->expval_child : plan;
   for (int k = 0; k < n_obs; ++k) {
     const uint32_t in = wire_masks[k];
-    if (in == 0 || (n < 32 && (in >> n))) return QMLE_ERR_WIRE_RANGE;
+    if (!valid_wire_mask(in, n)) return QMLE_ERR_WIRE_RANGE;
     uint32_t wm = 0;  // a product of Z's pulls back to the XOR of the factors' pull-backs
     for (int w = 0; w < n; ++w)
       if (in & (1u << w)) wm ^= *exec == plan ? 1u << w : pull_back_z(plan->absorbed, w);
-    uint32_t pm = 0;
-    for (int w = 0; w < n; ++w)
-      if (wm & (1u << w)) pm |= 1u << (n - 1 - w);
-    masks[k] = pm;  // (never 0: the pull-back is an invertible linear map)
+    masks[k] = wires_to_pos(wm, n);  // (never 0: the pull-back is an invertible linear map)
   }
   return QMLE_OK;
 }
@@ -551,20 +607,21 @@ int qmle_run_batch_parity(qmle_plan *plan, const float *d_angles, int batch,
                          d_workspace, workspace_bytes, (hipStream_t)stream_);
 }
 
-// Simulate + measure; <Z> observables arrive as bit-position parity masks.
-int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
-                          const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
-                          size_t workspace_bytes, hipStream_t stream) {
-  if (plan->zero_variant) plan = plan->zero_variant;  // every run_batch starts from |0..0>
+// How a run reads its <Z> observables (bit-position parity masks).
+struct ObsClass {
+  bool single_bits = true;   // plain Z observables: the 33-sums epilogue serves them all
+  bool semi_single = false;  // parities that meet the last tile in at most one position (below)
+  ObsBits by_position;       // column of the 33-float row = the observable's position (+ row signs: semi_single)
+  ObsBits by_index;          // column k = observable k (general-mask epilogue, k_reg_measure)
+};
+static ObsClass classify_observables(const qmle_plan *plan, const uint32_t *obs_masks, int n_obs) {
+  ObsClass oc;
   const int n = plan->n;
-  bool single_bits = true;  // plain Z observables: the 33-sums epilogue serves them all
-  int8_t obs_bits[QMLE_MAX_QUBITS];
-  if (meas_type == QMLE_MEAS_EXPVAL_Z) {
-    for (int k = 0; k < n_obs; ++k) {
-      const uint32_t m = obs_masks[k];
-      if (m == 0 || (m & (m - 1))) single_bits = false;
-      obs_bits[k] = (int8_t)(m ? __builtin_ctz(m) : 0);
-    }
+  for (int k = 0; k < n_obs; ++k) {
+    const uint32_t m = obs_masks[k];
+    if (m == 0 || (m & (m - 1))) oc.single_bits = false;
+    oc.by_position.bits[k] = (int8_t)(m ? __builtin_ctz(m) : 0);
+    oc.by_index.bits[k] = (int8_t)k;
   }
   // Parities that touch the LAST tile in at most one position (the rest are outer positions =
   // bits of the tile index) also come out of the 33-sums epilogue: column of that position (or
@@ -572,226 +629,181 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   // epilogue costs 13 - 17 us per state at n = 24, this one 4 - 6.  (A CX tail that would make
   // every folded parity of an HE ring meet the last tile in one position does not exist: the
   // restrictions of those parities to T wires are T + 1 or T + 2 distinct ranges.)
-  bool semi_single = false;
-  uint32_t row_masks[QMLE_MAX_QUBITS];
-  if (meas_type == QMLE_MEAS_EXPVAL_Z && !single_bits && !plan->stages.empty() &&
-      plan->stages.back().kind == ST_TILE && !plan->whole_state_lds) {
+  if (!oc.single_bits && !plan->stages.empty() && plan->stages.back().kind == ST_TILE && !plan->whole_state_lds) {
     const Stage &ls = plan->stages.back();
     uint32_t tile_mask = 0;
     for (int j = 0; j < ls.T; ++j) tile_mask |= 1u << ls.tile_bits[j];
-    semi_single = true;
-    for (int k = 0; k < n_obs && semi_single; ++k) {
+    oc.semi_single = true;
+    for (int k = 0; k < n_obs && oc.semi_single; ++k) {
       const uint32_t m = obs_masks[k], in = m & tile_mask;
-      if (m == 0 || (in & (in - 1u))) { semi_single = false; break; }
-      obs_bits[k] = (int8_t)(in ? __builtin_ctz(in) : QMLE_MAX_QUBITS);  // column 32: the tile's total
+      if (m == 0 || (in & (in - 1u))) { oc.semi_single = false; break; }
+      oc.by_position.bits[k] = (int8_t)(in ? __builtin_ctz(in) : QMLE_MAX_QUBITS);  // column 32: the tile's total
       uint32_t rm = 0;
       for (int i = 0; i < n - ls.T; ++i)
         if ((m >> ls.outer_bits[i]) & 1u) rm |= 1u << i;
-      row_masks[k] = rm;
+      oc.by_position.row_mask[k] = rm;
     }
   }
+  return oc;
+}
+
+// The whole state lives in the LDS of one workgroup: one launch per chunk simulates and measures, and the state
+// is stored only when the state is what was asked for.  `rows`: the Meyer-Wallach rows of a chunk (L.partial_bytes).
+static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_mats, const float *d_angles, int batch,
+                         int meas_type, const uint32_t *obs_masks, int n_obs, void *d_out, void *rows,
+                         hipStream_t stream) {
+  const Stage &st = plan->stages[0];
+  const int n = plan->n;
+  const size_t D = (size_t)1 << n;
+  for (int b0 = 0; b0 < batch; b0 += L.in_flight) {
+    const int bc = std::min(batch - b0, L.in_flight);
+    const float *mats = d_mats + (size_t)b0 * plan->mat_floats;
+    const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
+    ProfScope prof_scope(plan, 0, stream);
+    int rc;
+    if (meas_type == QMLE_MEAS_STATE) {
+      rc = launch_tile(plan, st, (float2 *)d_out + (size_t)b0 * D, mats, ang, bc, true, TM_STORE, nullptr, nullptr, 0,
+                       stream);
+    } else if (meas_type == QMLE_MEAS_PROBS) {
+      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_PROBS, (float *)d_out + (size_t)b0 * D, nullptr, 0,
+                       stream);
+    } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
+      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_EXPVAL, (float *)d_out + (size_t)b0 * n_obs,
+                       obs_masks, n_obs, stream);
+    } else {  // circuit + Meyer-Wallach sums
+      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_MW_ONLY, rows, nullptr, 0, stream);
+      if (rc == QMLE_OK)
+        rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
+    }
+    if (rc != QMLE_OK) return rc;
+  }
+  return QMLE_OK;
+}
+
+// The two-stream pipeline of a batch's chunks (round 5, above SideStreams): chunk i runs on internal stream i & 1
+// with workspace slot i & 1.  The streams fork from the caller's stream -- what it has queued so far (the matrices,
+// the angle table) comes first -- and join it again when the object goes, on the error returns too.  Without side
+// streams (one slot, or a fork that failed) every chunk runs on the caller's stream in slot 0.
+class ChunkPipeline {
+ public:
+  ChunkPipeline(bool two_slots, size_t n_stages, hipStream_t caller_stream) : caller_(caller_stream) {
+    side_ = two_slots ? side_streams() : nullptr;
+    if (side_ && (hipEventRecord(side_->fork, caller_) != hipSuccess ||
+                  hipStreamWaitEvent(side_->s[0], side_->fork, 0) != hipSuccess ||
+                  hipStreamWaitEvent(side_->s[1], side_->fork, 0) != hipSuccess)) {
+      (void)hipGetLastError();
+      side_ = nullptr;
+    }
+    piped_ = side_ && n_stages <= (size_t)kPipeStages;
+  }
+  ChunkPipeline(const ChunkPipeline &) = delete;
+  ChunkPipeline &operator=(const ChunkPipeline &) = delete;
+  ~ChunkPipeline() {
+    if (!side_) return;
+    for (int k = 0; k < 2; ++k)
+      if (hipEventRecord(side_->join[k], side_->s[k]) == hipSuccess)
+        (void)hipStreamWaitEvent(caller_, side_->join[k], 0);
+  }
+  int slot(int chunk) const { return side_ ? chunk & 1 : 0; }
+  hipStream_t stream(int chunk) const { return side_ ? side_->s[chunk & 1] : caller_; }
+  // Stage k of chunk i starts behind stage k of chunk i - 1 (the other stream).  The result marks the stage as
+  // queued when it goes out of scope (any exit from the stage's iteration).
+  struct StageQueued {
+    hipEvent_t ev;
+    hipStream_t stream;
+    ~StageQueued() { if (ev) (void)hipEventRecord(ev, stream); }
+  };
+  StageQueued begin_stage(int chunk, size_t k) const {
+    if (piped_ && chunk > 0) (void)hipStreamWaitEvent(stream(chunk), side_->stage_done[(chunk - 1) & 1][k], 0);
+    return StageQueued{piped_ ? side_->stage_done[chunk & 1][k] : nullptr, stream(chunk)};
+  }
+
+ private:
+  SideStreams *side_;
+  hipStream_t caller_;
+  bool piped_;
+};
+
+// Simulate + measure; <Z> observables arrive as bit-position parity masks.
+int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                          const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
+                          size_t workspace_bytes, hipStream_t caller_stream) {
+  if (plan->zero_variant) plan = plan->zero_variant;  // every run_batch starts from |0..0>
+  const int n = plan->n;
+  ObsClass oc;
+  if (meas_type == QMLE_MEAS_EXPVAL_Z) oc = classify_observables(plan, obs_masks, n_obs);
   int rc = ensure_device_plan(plan);
   if (rc != QMLE_OK) return rc;
 
   char *ws = (char *)d_workspace;
-  {
-    const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
-    ws += mis;
-    if (workspace_bytes < mis) return QMLE_ERR_WORKSPACE;
-    workspace_bytes -= mis;
-  }
-  const size_t mats_b = ws_mats_bytes(plan, batch);
-  if (workspace_bytes < mats_b) return QMLE_ERR_WORKSPACE;
+  BatchLayout L;
+  if (!align_workspace(ws, workspace_bytes) || !batch_layout(plan, batch, meas_type, 0, &workspace_bytes, L))
+    return QMLE_ERR_WORKSPACE;
   float *d_mats = (float *)ws;
-  float2 *d_cols = plan->fold_groups ? (float2 *)(ws + ws_matrix_bytes(plan, batch)) : nullptr;
-  float *d_coef = (float *)(ws + ws_matrix_bytes(plan, batch) +
-                            align_up((size_t)batch * (size_t)plan->fold_groups * 16 * sizeof(float2), 256));
-  ws += mats_b;
-  workspace_bytes -= mats_b;
+  float2 *d_cols = plan->fold_groups ? (float2 *)(ws + L.cols) : nullptr;
+  float *d_coef = (float *)(ws + L.coef);
 
   // per-sample gate matrices for the whole batch (tiny)
-  rc = launch_build_matrices(plan, d_angles, d_mats, batch, stream, /*forward_only=*/true);
+  rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true);
   if (rc != QMLE_OK) return rc;
-
-  const size_t D = (size_t)1 << n;
-  const size_t sb = D * sizeof(float2);
-
-  // ---- whole state in LDS: one launch does simulate + measure ------------------
-  if (plan->whole_state_lds && meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan)) {
-    // circuit + Meyer-Wallach sums in one launch per chunk: the state never leaves the LDS
-    const Stage &st = plan->stages[0];
-    for (int b0 = 0; b0 < batch; b0 += 65535) {
-      const int bc = batch - b0 < 65535 ? batch - b0 : 65535;
-      if (workspace_bytes < mw_ws_bytes(plan, bc)) return QMLE_ERR_WORKSPACE;
-      ProfScope prof_scope(plan, 0, stream);
-      rc = launch_tile(plan, st, nullptr, d_mats + (size_t)b0 * plan->mat_floats,
-                       d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr, bc, true, TM_MW_ONLY, ws,
-                       nullptr, 0, stream);
-      if (rc == QMLE_OK)
-        rc = run_mw_fused(nullptr, n, bc, st, 0, ws, workspace_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
-      if (rc != QMLE_OK) return rc;
-    }
-    return QMLE_OK;
-  }
-  if (plan->whole_state_lds) {
-    const Stage &st = plan->stages[0];
-    if (meas_type == QMLE_MEAS_STATE || meas_type == QMLE_MEAS_PROBS ||
-        meas_type == QMLE_MEAS_EXPVAL_Z) {
-      for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int bc = batch - b0 < 65535 ? batch - b0 : 65535;
-        const float *mats = d_mats + (size_t)b0 * plan->mat_floats;
-        const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
-        ProfScope prof_scope(plan, 0, stream);
-        if (meas_type == QMLE_MEAS_STATE)
-          rc = launch_tile(plan, st, (float2 *)d_out + (size_t)b0 * D, mats, ang, bc, true,
-                           TM_STORE, nullptr, nullptr, 0, stream);
-        else if (meas_type == QMLE_MEAS_PROBS)
-          rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_PROBS,
-                           (float *)d_out + (size_t)b0 * D, nullptr, 0, stream);
-        else
-          rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_EXPVAL,
-                           (float *)d_out + (size_t)b0 * n_obs, obs_masks, n_obs, stream);
-        if (rc != QMLE_OK) return rc;
-      }
-      return QMLE_OK;
-    }
-  }
+  if (L.in_lds)
+    return run_batch_lds(plan, L, d_mats, d_angles, batch, meas_type, obs_masks, n_obs, d_out, ws + L.partial[0],
+                         caller_stream);
 
   // ---- general path: states resident in HBM, sample-major chunks ----------------
-  float2 *d_states;
-  int in_flight;
-  if (meas_type == QMLE_MEAS_STATE) {
-    d_states = (float2 *)d_out;
-    in_flight = default_states_in_flight(plan, batch);  // sample-major: stay cache-resident
-  } else {
-    in_flight = (int)(workspace_bytes / per_state_ws_bytes(plan, meas_type));
-    if (in_flight < 1) return QMLE_ERR_WORKSPACE;
-    if (in_flight > batch) in_flight = batch;
-    const int dflt = default_states_in_flight(plan, batch);
-    if (in_flight > dflt) in_flight = dflt;
-    d_states = (float2 *)ws;
-    ws += (size_t)in_flight * align_up(sb, 256);
-  }
-  if (in_flight > 65535) in_flight = 65535;
-  // two slots (state buffer + partial sums each) when the batch has several chunks and the workspace has room
-  SideStreams *side = nullptr;
-  char *slot1 = nullptr;
-  // (one streaming pass per gate -- QMLE_PLAN_NO_FUSION -- is HBM-bound in every pass: two of them at once share the
-  // bandwidth and lose 2-3 % to the mix; those plans keep the one-stream loop)
-  if (in_flight < batch && chunk_overlap_on() && !(plan->flags & QMLE_PLAN_NO_FUSION)) {
-    if (meas_type == QMLE_MEAS_STATE) {
-      // every chunk writes its own rows of d_out; partial sums are not used
-      side = side_streams();
-    } else {
-      // (`workspace_bytes` is what was left when the state buffers were carved: they start at d_states.  A workspace
-      // sized by qmle_workspace_bytes holds two slots of the chunk it was asked for; one that holds less is split in two)
-      const size_t per = per_state_ws_bytes(plan, meas_type);
-      int two = (int)std::min<size_t>(workspace_bytes / per / 2, 65535);
-      const int dflt = default_states_in_flight(plan, batch);
-      if (two > dflt) two = dflt;
-      if (two >= 1 && (side = side_streams()) != nullptr) {
-        // the partial sums sit behind the state block of `in_flight` states: re-carve slot 0 for `two`
-        in_flight = two;
-        slot1 = (char *)d_states + (size_t)two * per;
-        ws = (char *)d_states + (size_t)two * align_up(sb, 256);
-      }
-    }
-  }
-  void *d_partial = ws;
-  const size_t partial_bytes =
-      (size_t)in_flight * expval_partial_rows(plan) * (QMLE_MAX_QUBITS + 1) * sizeof(float);
+  const size_t D = (size_t)1 << n;
   // <Z> straight out of the last tile pass (no store of the final state, no extra read)
   const bool fuse_expval = meas_type == QMLE_MEAS_EXPVAL_Z && !plan->stages.empty() &&
                            plan->stages.back().kind == ST_TILE;
   const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
-  const size_t mw_bytes = meas_type == QMLE_MEAS_MEYER_WALLACH ? mw_ws_bytes(plan, in_flight) : 0;
-
-  hipStream_t const caller_stream = stream;
-  if (side) {  // fork: what the caller's stream has queued so far (the matrices, the angle table) comes first
-    if (hipEventRecord(side->fork, caller_stream) != hipSuccess ||
-        hipStreamWaitEvent(side->s[0], side->fork, 0) != hipSuccess ||
-        hipStreamWaitEvent(side->s[1], side->fork, 0) != hipSuccess) {
-      (void)hipGetLastError();
-      side = nullptr;
-    }
-  }
-  float2 *const d_states0 = d_states;
-  void *const d_partial0 = d_partial;
-  auto join_side = [&]() {
-    if (!side) return;
-    for (int k = 0; k < 2; ++k)
-      if (hipEventRecord(side->join[k], side->s[k]) == hipSuccess)
-        (void)hipStreamWaitEvent(caller_stream, side->join[k], 0);
-  };
-  struct JoinGuard {  // (also on the error returns inside the loop)
-    decltype(join_side) &f;
-    ~JoinGuard() { f(); }
-  } join_guard{join_side};
+  const bool by_position = oc.single_bits || oc.semi_single;
+  ChunkPipeline pipe(L.slots == 2, plan->stages.size(), caller_stream);
   int chunk_no = 0;
-  for (int b0 = 0; b0 < batch; b0 += in_flight, ++chunk_no) {
-    const int bc = batch - b0 < in_flight ? batch - b0 : in_flight;
-    if (side) {
-      stream = side->s[chunk_no & 1];
-      if (slot1 && (chunk_no & 1)) {
-        d_states = (float2 *)slot1;
-        d_partial = slot1 + ((char *)d_partial0 - (char *)d_states0);
-      } else {
-        d_states = d_states0;
-        d_partial = d_partial0;
-      }
-    }
-    float2 *stc = meas_type == QMLE_MEAS_STATE ? d_states + (size_t)b0 * D : d_states;
+  for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
+    const int bc = std::min(batch - b0, L.in_flight);
+    const hipStream_t stream = pipe.stream(chunk_no);
+    const int slot = pipe.slot(chunk_no);
+    float2 *stc = meas_type == QMLE_MEAS_STATE ? (float2 *)d_out + (size_t)b0 * D : (float2 *)(ws + L.states[slot]);
+    void *d_partial = ws + L.partial[slot];
     const float *mats = d_mats + (size_t)b0 * plan->mat_floats;
     const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
+    float2 *cols = d_cols ? d_cols + (size_t)b0 * plan->fold_groups * 16 : nullptr;
     bool initialised = false;
     int reg_q = -1;  // >= 0: the last pass ran as k_reg_measure with 2^reg_q tiles per row
     int tile_row_shift = 0;  // k_tile2's multi-tile measuring variant: 2^shift tiles per row
     for (size_t si = 0; si < plan->stages.size(); ++si) {
       const Stage &st = plan->stages[si];
-      const bool piped = side && plan->stages.size() <= (size_t)kPipeStages;
-      if (piped && chunk_no > 0)  // behind the same stage of the previous chunk (the other stream)
-        (void)hipStreamWaitEvent(stream, side->stage_done[(chunk_no - 1) & 1][si], 0);
-      struct StageDone {  // recorded when the stage's launches are queued (any exit from this iteration)
-        hipEvent_t ev; hipStream_t st_;
-        ~StageDone() { if (ev) (void)hipEventRecord(ev, st_); }
-      } stage_done{piped ? side->stage_done[chunk_no & 1][si] : nullptr, stream};
+      const ChunkPipeline::StageQueued stage_queued = pipe.begin_stage(chunk_no, si);
       ProfScope prof_scope(plan, (int)si, stream);
       if (st.kind == ST_TILE && fuse_mw && si + 1 == plan->stages.size()) {
         // the last pass stores the state AND reports its tile's Meyer-Wallach sums (one row per tile)
         rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, TM_STORE_MW, d_partial, nullptr, 0, stream,
-                         /*from_zero=*/true, d_cols ? d_cols + (size_t)b0 * plan->fold_groups * 16 : nullptr,
-                         &tile_row_shift);
+                         /*from_zero=*/true, cols, &tile_row_shift);
         initialised = true;
       } else if (st.kind == ST_TILE) {
         const bool last_fused = fuse_expval && si + 1 == plan->stages.size();
-        const int tm = !last_fused ? TM_STORE : (single_bits || semi_single) ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
+        const int tm = !last_fused ? TM_STORE : by_position ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
         reg_q = -1;
         int reg_kind = last_fused && initialised ? reg_measure_kind(plan, si, n_obs) : 0;
         // (k_reg_measure on live input is the slowest way to take parities; its known-zero forms
         // -- FOLD, mono -- keep priority)
-        if (reg_kind == 1 && semi_single) reg_kind = 0;
+        if (reg_kind == 1 && oc.semi_single) reg_kind = 0;
         if (reg_kind) {
           rc = launch_reg_measure(plan, st, reg_kind, stc, mats, ang, bc, d_partial, obs_masks,
                                   n_obs, stream, &reg_q, d_coef + (size_t)b0 * 32);
-        } else
-        rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, tm,
-                         last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
-                         last_fused ? n_obs : 0, stream, /*from_zero=*/true,
-                         d_cols ? d_cols + (size_t)b0 * plan->fold_groups * 16 : nullptr,
-                         last_fused && (single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr);
+        } else {
+          rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, tm,
+                           last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
+                           last_fused ? n_obs : 0, stream, /*from_zero=*/true, cols,
+                           last_fused && (oc.single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr);
+        }
         initialised = true;
       } else {
         if (!initialised) {
           launch_init_zero(stc, n, bc, stream);
           initialised = true;
         }
-        if (st.kind == ST_DIRECT) {
-          rc = launch_direct(plan, plan->dev_ops[st.op_begin], stc, mats, bc, stream);
-        } else {
-          const LoweredOp &o = plan->dev_ops[st.op_begin];
-          launch_diag_all(stc, n, bc, plan->dev.d_consts + o.mat_off, ang, plan->n_slots, o.slot, stream);
-          rc = QMLE_OK;
-        }
+        rc = run_stage_inplace(plan, st, stc, mats, ang, bc, stream);
       }
       if (rc != QMLE_OK) return rc;
     }
@@ -801,26 +813,21 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
       const uint64_t tc = (uint64_t)bc * (D / 2);
       launch_probs(stc, (float *)d_out + (size_t)b0 * D, tc, stream);
     } else if (meas_type == QMLE_MEAS_EXPVAL_Z && fuse_expval) {
-      ObsBits ob;  // column of the 33-float row: the bit's sum, or (masks) the observable's own
-      const bool by_position = (single_bits || semi_single) && reg_q < 0;
-      for (int k = 0; k < QMLE_MAX_QUBITS; ++k) ob.row_mask[k] = 0u;
-      for (int k = 0; k < n_obs; ++k) {
-        ob.bits[k] = by_position ? obs_bits[k] : (int8_t)k;
-        if (by_position && semi_single) ob.row_mask[k] = row_masks[k];
-      }
+      // column of the 33-float row: the bit's sum, or (masks, k_reg_measure) the observable's own
       const int tiles = (1 << (n - plan->stages.back().T)) >> (reg_q < 0 ? tile_row_shift : reg_q);
-      launch_expval_final((const float *)d_partial, tiles, bc, n_obs, ob, (float *)d_out + (size_t)b0 * n_obs, stream);
+      launch_expval_final((const float *)d_partial, tiles, bc, n_obs, by_position && reg_q < 0 ? oc.by_position : oc.by_index,
+                          (float *)d_out + (size_t)b0 * n_obs, stream);
     } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
-      rc = single_bits
-               ? run_expval(stc, n, bc, obs_bits, n_obs, (float *)d_out + (size_t)b0 * n_obs,
-                            d_partial, partial_bytes, stream)
+      rc = oc.single_bits
+               ? run_expval(stc, n, bc, oc.by_position.bits, n_obs, (float *)d_out + (size_t)b0 * n_obs,
+                            d_partial, L.partial_bytes, stream)
                : run_parity_pos(stc, n, bc, obs_masks, n_obs, (float *)d_out + (size_t)b0 * n_obs,
-                                d_partial, partial_bytes, stream);
+                                d_partial, L.partial_bytes, stream);
       if (rc != QMLE_OK) return rc;
     } else if (meas_type == QMLE_MEAS_MEYER_WALLACH) {
-      rc = fuse_mw ? run_mw_fused(stc, n, bc, plan->stages.back(), tile_row_shift, d_partial, mw_bytes,
+      rc = fuse_mw ? run_mw_fused(stc, n, bc, plan->stages.back(), tile_row_shift, d_partial, L.partial_bytes,
                                   (float *)d_out + (size_t)b0 * (n + 1), stream)
-                   : run_mw_resident(stc, n, bc, d_partial, mw_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
+                   : run_mw_resident(stc, n, bc, d_partial, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
       if (rc != QMLE_OK) return rc;
     } else if (meas_type == QMLE_MEAS_DENSITY) {
       if (n > 15) return QMLE_ERR_UNSUPPORTED;
@@ -848,7 +855,7 @@ int qmle::run_stage_inplace(qmle_plan *plan, const Stage &st, float2 *d_states, 
 
 int qmle_apply_inplace(qmle_plan *plan, const float *d_angles, int batch, void *d_states,
                        void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
-  if (!plan || batch < 1 || batch > 65535 || !d_states || !d_workspace) return QMLE_ERR_INVALID_ARG;
+  if (!plan || batch < 1 || batch > kMaxGridY || !d_states || !d_workspace) return QMLE_ERR_INVALID_ARG;
   if (plan->n_slots > 0 && !d_angles) return QMLE_ERR_INVALID_ARG;
   // (a schedule compiled for runs from |0..0> -- qmle_plan_executed's handle -- is not one for live states)
   if (plan->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) return QMLE_ERR_UNSUPPORTED;
@@ -856,9 +863,8 @@ int qmle_apply_inplace(qmle_plan *plan, const float *d_angles, int batch, void *
   int rc = ensure_device_plan(plan);
   if (rc != QMLE_OK) return rc;
   char *ws = (char *)d_workspace;
-  const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
-  if (workspace_bytes < mis + ws_mats_bytes(plan, batch)) return QMLE_ERR_WORKSPACE;
-  float *d_mats = (float *)(ws + mis);
+  if (!align_workspace(ws, workspace_bytes) || workspace_bytes < ws_mats_bytes(plan, batch)) return QMLE_ERR_WORKSPACE;
+  float *d_mats = (float *)ws;
   rc = launch_build_matrices(plan, d_angles, d_mats, batch, stream, /*forward_only=*/true);
   if (rc != QMLE_OK) return rc;
   int stage_idx = -1;
@@ -887,29 +893,14 @@ static std::mutex g_tuned_mu;
 static std::map<uint64_t, TunedChoice> g_tuned;
 
 static uint64_t tape_hash(const qmle_plan *p, int meas_class, int batch_class) {
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void *data, size_t bytes) {
-    const unsigned char *c = (const unsigned char *)data;
-    for (size_t i = 0; i < bytes; ++i) { h ^= c[i]; h *= 1099511628211ull; }
-  };
-  mix(p->ops.data(), p->ops.size() * sizeof(qmle_op));
-  const int v[5] = {p->n, p->n_slots, (int)p->flags, meas_class, batch_class};
-  mix(v, sizeof(v));
-  const int dev = current_device();
-  mix(&dev, sizeof(dev));
-  return h;
+  const int v[6] = {p->n, p->n_slots, (int)p->flags, meas_class, batch_class, current_device()};
+  return fnv1a(v, sizeof(v), fnv1a(p->ops.data(), p->ops.size() * sizeof(qmle_op)));
 }
 
 // a stand-alone compile of `base`'s tape with a forced candidate (no variant, no child)
 static qmle_plan *compile_candidate(const qmle_plan *base, int cand, int pad) {
-  qmle_plan *c = new (std::nothrow) qmle_plan();
+  qmle_plan *c = new_plan_like(base, base->ops, base->flags);
   if (!c) return nullptr;
-  c->n = base->n;
-  c->n_slots = base->n_slots;
-  c->flags = base->flags;
-  c->ops = base->ops;
-  c->consts.assign(base->consts.begin(), base->consts.begin() + base->n_user_consts);
-  c->n_user_consts = base->n_user_consts;
   c->force_candidate = cand;
   c->pad_high = pad;
   c->extra_algo_last_stage = base->extra_algo_last_stage;
@@ -1071,6 +1062,21 @@ int qmle_plan_autotune(qmle_plan *plan, int meas_type, int n_obs, int batch, int
   return rc;
 }
 
+// the ABI's leaf arrays -> the kernels' AngleLeaves (the caller has checked 0 <= n_leaves <= 8)
+static int fill_angle_leaves(AngleLeaves &lv, const float *const *d_leaves, const int64_t *leaf_strides,
+                             const int32_t *leaf_div, const int32_t *leaf_mod, int n_leaves) {
+  std::memset(&lv, 0, sizeof(lv));
+  for (int k = 0; k < n_leaves; ++k) {
+    // (a leaf without elements -- the parameters of an ansatz that has none -- may come as a NULL pointer: no term can refer to it)
+    if ((!d_leaves[k] && leaf_strides[k] != 0) || leaf_div[k] < 1 || leaf_mod[k] < 1) return QMLE_ERR_INVALID_ARG;
+    lv.ptr[k] = d_leaves[k];
+    lv.stride[k] = leaf_strides[k];
+    lv.div[k] = leaf_div[k];
+    lv.mod[k] = leaf_mod[k];
+  }
+  return QMLE_OK;
+}
+
 int qmle_build_angles(const float *const *d_leaves, const int64_t *leaf_strides,
                       const int32_t *leaf_div, const int32_t *leaf_mod, int n_leaves,
                       const int32_t *d_ptr, const int32_t *d_arg, const int32_t *d_idx,
@@ -1081,15 +1087,8 @@ int qmle_build_angles(const float *const *d_leaves, const int64_t *leaf_strides,
     return QMLE_ERR_INVALID_ARG;
   if (n_slots == 0) return QMLE_OK;
   AngleLeaves lv;
-  std::memset(&lv, 0, sizeof(lv));
-  for (int k = 0; k < n_leaves; ++k) {
-    // (a leaf without elements -- the parameters of an ansatz that has none -- may come as a NULL pointer: no term can refer to it)
-    if ((!d_leaves[k] && leaf_strides[k] != 0) || leaf_div[k] < 1 || leaf_mod[k] < 1) return QMLE_ERR_INVALID_ARG;
-    lv.ptr[k] = d_leaves[k];
-    lv.stride[k] = leaf_strides[k];
-    lv.div[k] = leaf_div[k];
-    lv.mod[k] = leaf_mod[k];
-  }
+  const int rc_lv = fill_angle_leaves(lv, d_leaves, leaf_strides, leaf_div, leaf_mod, n_leaves);
+  if (rc_lv != QMLE_OK) return rc_lv;
   const uint64_t total = (uint64_t)batch * (uint64_t)n_slots;
   if (total + 256 < (1ull << 32) && batch_offset >= 0 && (uint64_t)batch + (uint64_t)batch_offset < (1ull << 32))
     hipLaunchKernelGGL(k_build_angles<uint32_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, lv,
@@ -1127,13 +1126,8 @@ int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angl
   }
   AngleMapSrc src;
   std::memset(&src, 0, sizeof(src));
-  for (int k = 0; k < map->n_leaves; ++k) {
-    if ((!map->d_leaves[k] && map->leaf_strides[k] != 0) || map->leaf_div[k] < 1 || map->leaf_mod[k] < 1) return QMLE_ERR_INVALID_ARG;
-    src.lv.ptr[k] = map->d_leaves[k];
-    src.lv.stride[k] = map->leaf_strides[k];
-    src.lv.div[k] = map->leaf_div[k];
-    src.lv.mod[k] = map->leaf_mod[k];
-  }
+  const int rc_lv = fill_angle_leaves(src.lv, map->d_leaves, map->leaf_strides, map->leaf_div, map->leaf_mod, map->n_leaves);
+  if (rc_lv != QMLE_OK) return rc_lv;
   src.ptr = map->d_ptr; src.arg = map->d_arg; src.idx = map->d_idx;
   src.coef = map->d_coef; src.cst = map->d_const; src.period = map->d_period;
   src.b_offset = map->batch_offset;

@@ -308,13 +308,44 @@ static int ensure_f64(qmle_plan *p) {
   return QMLE_OK;
 }
 
-static size_t f64_states_in_flight(const qmle_plan *p, int batch) {
-  const size_t sb = (size_t)16 << p->n;
-  size_t s = ((size_t)4 << 30) / sb;  // 4 GiB of states per round of launches
+// samples per round of launches: 4 GiB of states (`amp_bytes` per amplitude: 16, or 32 for psi and lambda)
+static int f64_in_flight(int n, int batch, size_t amp_bytes) {
+  size_t s = ((size_t)4 << 30) / (amp_bytes << n);
   if (s < 1) s = 1;
   if (s > (size_t)batch) s = (size_t)batch;
-  if (s > 65535) s = 65535;
-  return s;
+  if (s > (size_t)kMaxGridY) s = kMaxGridY;
+  return (int)s;
+}
+// the matrix rows of a batch
+static size_t f64_mats_bytes(const qmle_plan *p, int batch) {
+  return align_up((size_t)batch * (p->mat_floats ? p->mat_floats : 1) * sizeof(double), 256);
+}
+// the plan's double constants, behind its lowered operators (ensure_f64)
+static const double *f64_consts(const qmle_plan *p) {
+  return (const double *)((char *)p->f64_blob + align_up(p->lowered.size() * sizeof(LoweredOp) + 16, 256));
+}
+// per-sample gate matrices for the whole batch: d_mats[b][mat_floats] from d_angles[b][n_slots]
+static void launch_build_matrices_f64(const qmle_plan *p, const double *d_angles, double *d_mats, int batch,
+                                      hipStream_t stream) {
+  if (p->groups.empty()) return;
+  const int ng = (int)p->groups.size();
+  if (batch >= 64)
+    hipLaunchKernelGGL(k_build_matrices_f64<true>, dim3(grid_for((uint64_t)ng * (((uint64_t)batch + 63) / 64) * 64, 64)),
+                       dim3(64), 0, stream, p->dev.d_build, p->dev.d_groups, ng, d_angles, p->n_slots, f64_consts(p),
+                       d_mats, p->mat_floats, batch);
+  else
+    hipLaunchKernelGGL(k_build_matrices_f64<false>, dim3(grid_for((uint64_t)batch * ng, 64)), dim3(64), 0, stream,
+                       p->dev.d_build, p->dev.d_groups, ng, d_angles, p->n_slots, f64_consts(p), d_mats, p->mat_floats,
+                       batch);
+}
+// <Z..Z> on wire masks (bit w = wire w) -> the kernels' position masks
+static int f64_obs(const uint32_t *wire_masks, int n_obs, int n, F64Obs &obs) {
+  std::memset(&obs, 0, sizeof(obs));
+  for (int k = 0; k < n_obs; ++k) {
+    if (!valid_wire_mask(wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
+    obs.mask[k] = wires_to_pos(wire_masks[k], n);
+  }
+  return QMLE_OK;
 }
 
 extern "C" {
@@ -329,10 +360,10 @@ int qmle_plan_set_consts_f64(qmle_plan *plan, const double *consts, int n_consts
 
 size_t qmle_workspace_bytes_f64(const qmle_plan *plan, int batch, int meas_type) {
   if (!plan || batch < 1) return 0;
-  size_t total = align_up((size_t)batch * (plan->mat_floats ? plan->mat_floats : 1) * sizeof(double), 256) + 512;
+  size_t total = f64_mats_bytes(plan, batch) + 512;
   const bool lds = plan->n <= 13;
   if (!lds || meas_type == QMLE_MEAS_DENSITY)
-    total += (lds ? (size_t)batch : f64_states_in_flight(plan, batch)) * align_up((size_t)16 << plan->n, 256);
+    total += (size_t)(lds ? batch : f64_in_flight(plan->n, batch, 16)) * align_up((size_t)16 << plan->n, 256);
   return total;
 }
 
@@ -341,31 +372,24 @@ size_t qmle_workspace_bytes_f64(const qmle_plan *plan, int batch, int meas_type)
 // between two Kraus channels (simulation.py:107-128, operations.py:485-512, 1551-1578)
 size_t qmle_apply_inplace_f64_workspace_bytes(const qmle_plan *plan, int batch) {  // the matrix rows
   if (!plan || batch < 1) return 0;
-  return align_up((size_t)batch * (plan->mat_floats ? plan->mat_floats : 1) * sizeof(double), 256) + 512;
+  return f64_mats_bytes(plan, batch) + 512;
 }
 int qmle_apply_inplace_f64(qmle_plan *plan, const double *d_angles, int batch, void *d_states,
                            void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
-  if (!plan || batch < 1 || batch > 65535 || !d_states || !d_workspace) return QMLE_ERR_INVALID_ARG;
+  if (!plan || batch < 1 || batch > kMaxGridY || !d_states || !d_workspace) return QMLE_ERR_INVALID_ARG;
   if (plan->n_slots > 0 && !d_angles) return QMLE_ERR_INVALID_ARG;
-  if (workspace_bytes < qmle_apply_inplace_f64_workspace_bytes(plan, batch)) return QMLE_ERR_WORKSPACE;
+  char *ws = (char *)d_workspace;
+  // (the size asked for includes the slack that aligning the pointer takes)
+  if (workspace_bytes < qmle_apply_inplace_f64_workspace_bytes(plan, batch) || !align_workspace(ws, workspace_bytes))
+    return QMLE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   int rc = ensure_device_plan(plan);
   if (rc != QMLE_OK) return rc;
   rc = ensure_f64(plan);
   if (rc != QMLE_OK) return rc;
-  const double *d_c64 = (const double *)((char *)plan->f64_blob + align_up(plan->lowered.size() * sizeof(LoweredOp) + 16, 256));
-  char *ws = (char *)d_workspace;
-  ws += (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
+  const double *d_c64 = f64_consts(plan);
   double *d_mats = (double *)ws;
-  if (!plan->groups.empty()) {
-    const int ng = (int)plan->groups.size();
-    if (batch >= 64)
-      hipLaunchKernelGGL(k_build_matrices_f64<true>, dim3(grid_for((uint64_t)ng * (((uint64_t)batch + 63) / 64) * 64, 64)), dim3(64), 0, stream, plan->dev.d_build,
-                       plan->dev.d_groups, ng, d_angles, plan->n_slots, d_c64, d_mats, plan->mat_floats, batch);
-    else
-      hipLaunchKernelGGL(k_build_matrices_f64<false>, dim3(grid_for((uint64_t)batch * ng, 64)), dim3(64), 0, stream, plan->dev.d_build,
-                       plan->dev.d_groups, ng, d_angles, plan->n_slots, d_c64, d_mats, plan->mat_floats, batch);
-  }
+  launch_build_matrices_f64(plan, d_angles, d_mats, batch, stream);
   const int n = plan->n;
   const unsigned gx = grid_for(((size_t)1 << n) / 2, 256, 1u << 16);
   for (size_t k = 0; k < plan->lowered.size(); ++k)
@@ -381,18 +405,17 @@ int qmle_run_batch_f64(qmle_plan *plan, const double *d_angles, int batch, int m
   if (!plan || batch < 1 || !d_out || !d_workspace) return QMLE_ERR_INVALID_ARG;
   if (meas_type < QMLE_MEAS_STATE || meas_type > QMLE_MEAS_DENSITY) return QMLE_ERR_MEAS_TYPE;
   if (plan->n_slots > 0 && !d_angles) return QMLE_ERR_INVALID_ARG;
-  if (workspace_bytes < qmle_workspace_bytes_f64(plan, batch, meas_type)) return QMLE_ERR_WORKSPACE;
+  char *ws = (char *)d_workspace;
+  // (the size asked for includes the slack that aligning the pointer takes)
+  if (workspace_bytes < qmle_workspace_bytes_f64(plan, batch, meas_type) || !align_workspace(ws, workspace_bytes))
+    return QMLE_ERR_WORKSPACE;
   const int n = plan->n;
   F64Obs obs;
   std::memset(&obs, 0, sizeof(obs));
   if (meas_type == QMLE_MEAS_EXPVAL_Z) {
     if (n_obs < 1 || n_obs > QMLE_MAX_QUBITS || !wire_masks) return QMLE_ERR_INVALID_ARG;
-    for (int k = 0; k < n_obs; ++k) {
-      const uint32_t in = wire_masks[k];
-      if (in == 0 || (n < 32 && (in >> n))) return QMLE_ERR_WIRE_RANGE;
-      for (int w = 0; w < n; ++w)
-        if (in & (1u << w)) obs.mask[k] |= 1u << (n - 1 - w);
-    }
+    const int rc_obs = f64_obs(wire_masks, n_obs, n, obs);
+    if (rc_obs != QMLE_OK) return rc_obs;
   }
   if (meas_type == QMLE_MEAS_DENSITY && n > 12) return QMLE_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
@@ -401,24 +424,12 @@ int qmle_run_batch_f64(qmle_plan *plan, const double *d_angles, int batch, int m
   rc = ensure_f64(plan);
   if (rc != QMLE_OK) return rc;
   const LoweredOp *d_low = (const LoweredOp *)plan->f64_blob;
-  const double *d_c64 = (const double *)((char *)plan->f64_blob + align_up(plan->lowered.size() * sizeof(LoweredOp) + 16, 256));
-  char *ws = (char *)d_workspace;
-  const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
-  ws += mis;
+  const double *d_c64 = f64_consts(plan);
   double *d_mats = (double *)ws;
-  ws += align_up((size_t)batch * (plan->mat_floats ? plan->mat_floats : 1) * sizeof(double), 256);
-  if (!plan->groups.empty()) {
-    const int ng = (int)plan->groups.size();
-    if (batch >= 64)
-      hipLaunchKernelGGL(k_build_matrices_f64<true>, dim3(grid_for((uint64_t)ng * (((uint64_t)batch + 63) / 64) * 64, 64)), dim3(64), 0, stream, plan->dev.d_build,
-                       plan->dev.d_groups, ng, d_angles, plan->n_slots, d_c64, d_mats, plan->mat_floats, batch);
-    else
-      hipLaunchKernelGGL(k_build_matrices_f64<false>, dim3(grid_for((uint64_t)batch * ng, 64)), dim3(64), 0, stream, plan->dev.d_build,
-                       plan->dev.d_groups, ng, d_angles, plan->n_slots, d_c64, d_mats, plan->mat_floats, batch);
-  }
+  launch_build_matrices_f64(plan, d_angles, d_mats, batch, stream);
   const size_t D = (size_t)1 << n;
   const int n_ops = (int)plan->lowered.size();
-  double2 *d_states = (double2 *)ws;
+  double2 *d_states = (double2 *)(ws + f64_mats_bytes(plan, batch));
   if (n <= 13) {
     if (FirstUse once{6}; once.first) {
       HIPCHK(hipFuncSetAttribute((const void *)k64_lds, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
@@ -428,15 +439,15 @@ int qmle_run_batch_f64(qmle_plan *plan, const double *d_angles, int batch, int m
     hipLaunchKernelGGL(k64_lds, dim3(batch), dim3(256), D * sizeof(double2), stream, d_low, n_ops, n, d_mats,
                        plan->mat_floats, d_c64, d_angles, plan->n_slots, meas_type, obs, n_obs, target);
     if (meas_type == QMLE_MEAS_DENSITY)
-      for (int b0 = 0; b0 < batch; b0 += 65535) {
-        const int bc = batch - b0 < 65535 ? batch - b0 : 65535;
+      for (int b0 = 0; b0 < batch; b0 += kMaxGridY) {
+        const int bc = std::min(batch - b0, kMaxGridY);
         hipLaunchKernelGGL(k64_density, dim3(grid_for(D * D, 256, 1u << 16), bc), dim3(256), 0, stream,
                            d_states + (size_t)b0 * D, n, (double2 *)d_out + (size_t)b0 * D * D);
       }
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
-  const int in_flight = (int)f64_states_in_flight(plan, batch);
+  const int in_flight = f64_in_flight(n, batch, 16);
   for (int b0 = 0; b0 < batch; b0 += in_flight) {
     const int bc = batch - b0 < in_flight ? batch - b0 : in_flight;
     double2 *stc = meas_type == QMLE_MEAS_STATE ? (double2 *)d_out + (size_t)b0 * D : d_states;
@@ -463,20 +474,13 @@ static int f64_adj_blocks(int n) {
   uint64_t b = (D + 256 * 8 - 1) / (256 * 8);
   return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b);
 }
-static int f64_adj_in_flight(int n, int batch) {  // psi and lambda of a round of samples: <= 4 GiB
-  size_t s = ((size_t)4 << 30) / ((size_t)32 << n);
-  if (s < 1) s = 1;
-  if (s > (size_t)batch) s = (size_t)batch;
-  if (s > 65535) s = 65535;
-  return (int)s;
-}
 struct F64AdjLayout { size_t fmats, rmats, partial, psi, lam, total; };
 static F64AdjLayout f64_adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
   F64AdjLayout L;
-  const int fl = f64_adj_in_flight(fwd->n, batch);
+  const int fl = f64_in_flight(fwd->n, batch, 32);  // psi and lambda of a round of samples
   L.fmats = 0;
-  L.rmats = align_up((size_t)batch * (fwd->mat_floats ? fwd->mat_floats : 1) * sizeof(double), 256);
-  L.partial = L.rmats + align_up((size_t)batch * (rev->mat_floats ? rev->mat_floats : 1) * sizeof(double), 256);
+  L.rmats = f64_mats_bytes(fwd, batch);
+  L.partial = L.rmats + f64_mats_bytes(rev, batch);
   L.psi = L.partial + align_up((size_t)fl * f64_adj_blocks(fwd->n) * sizeof(double2), 256);
   L.lam = L.psi + align_up((size_t)fl * ((size_t)16 << fwd->n), 256);
   L.total = L.lam + align_up((size_t)fl * ((size_t)16 << fwd->n), 256) + 512;
@@ -501,13 +505,8 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
   for (const auto &srcs : rev->lowered_src)
     if (srcs.size() != 1) return QMLE_ERR_INVALID_ARG;
   F64Obs obs;
-  std::memset(&obs, 0, sizeof(obs));
-  for (int k = 0; k < n_obs; ++k) {
-    const uint32_t in = obs_wire_masks[k];
-    if (in == 0 || (n < 32 && (in >> n))) return QMLE_ERR_WIRE_RANGE;
-    for (int w = 0; w < n; ++w)
-      if (in & (1u << w)) obs.mask[k] |= 1u << (n - 1 - w);
-  }
+  int rc = f64_obs(obs_wire_masks, n_obs, n, obs);
+  if (rc != QMLE_OK) return rc;
   for (int r = 0; r < n_terms; ++r) {
     if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
     if (terms[r].out_slot >= 0 && terms[r].marks_off >= 0 &&
@@ -516,39 +515,23 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
   }
   const F64AdjLayout L = f64_adj_layout(fwd, rev, batch);
   char *ws = (char *)d_workspace;
-  const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
-  if (workspace_bytes < mis + L.total) return QMLE_ERR_WORKSPACE;
-  ws += mis;
+  if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = ensure_device_plan(fwd);
+  rc = ensure_device_plan(fwd);
   if (rc == QMLE_OK) rc = ensure_device_plan(rev);
   if (rc == QMLE_OK) rc = ensure_f64(fwd);
   if (rc == QMLE_OK) rc = ensure_f64(rev);
   if (rc != QMLE_OK) return rc;
-  auto c64_of = [](const qmle_plan *p) {
-    return (const double *)((char *)p->f64_blob + align_up(p->lowered.size() * sizeof(LoweredOp) + 16, 256));
-  };
-  const double *fc = c64_of(fwd), *rcst = c64_of(rev);
+  const double *fc = f64_consts(fwd), *rcst = f64_consts(rev);
   double *fmats = (double *)(ws + L.fmats), *rmats = (double *)(ws + L.rmats);
-  auto build = [&](const qmle_plan *p, const double *ang, const double *c64, double *mats) {
-    if (p->groups.empty()) return;
-    const int ng = (int)p->groups.size();
-    if (batch >= 64)
-      hipLaunchKernelGGL(k_build_matrices_f64<true>, dim3(grid_for((uint64_t)ng * (((uint64_t)batch + 63) / 64) * 64, 64)),
-                         dim3(64), 0, stream, p->dev.d_build, p->dev.d_groups, ng, ang, p->n_slots, c64, mats,
-                         p->mat_floats, batch);
-    else
-      hipLaunchKernelGGL(k_build_matrices_f64<false>, dim3(grid_for((uint64_t)batch * ng, 64)), dim3(64), 0, stream,
-                         p->dev.d_build, p->dev.d_groups, ng, ang, p->n_slots, c64, mats, p->mat_floats, batch);
-  };
-  build(fwd, d_angles_fwd, fc, fmats);
-  build(rev, d_angles_rev, rcst, rmats);
+  launch_build_matrices_f64(fwd, d_angles_fwd, fmats, batch, stream);
+  launch_build_matrices_f64(rev, d_angles_rev, rmats, batch, stream);
   HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(double), stream));
   double2 *psi = (double2 *)(ws + L.psi), *lam = (double2 *)(ws + L.lam);
   double2 *partial = (double2 *)(ws + L.partial);
   const size_t D = (size_t)1 << n;
   const int nb = f64_adj_blocks(n);
-  const int in_flight = f64_adj_in_flight(n, batch);
+  const int in_flight = f64_in_flight(n, batch, 32);
   const unsigned gx = grid_for(D / 2 ? D / 2 : 1, 256, 1u << 16);
   for (int b0 = 0; b0 < batch; b0 += in_flight) {
     const int bc = batch - b0 < in_flight ? batch - b0 : in_flight;
@@ -566,12 +549,9 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
       const qmle_adjoint_term &t = terms[rev->lowered_src[r][0]];
       if (t.out_slot >= 0) {
         F64AdjTerm a;
-        a.xmask = a.zmask = a.pmask = 0;
-        for (int w = 0; w < n; ++w) {
-          if (t.x_wires & (1u << w)) a.xmask |= 1u << (n - 1 - w);
-          if (t.z_wires & (1u << w)) a.zmask |= 1u << (n - 1 - w);
-          if (t.proj_wires & (1u << w)) a.pmask |= 1u << (n - 1 - w);
-        }
+        a.xmask = wires_to_pos(t.x_wires, n);
+        a.zmask = wires_to_pos(t.z_wires, n);
+        a.pmask = wires_to_pos(t.proj_wires, n);
         a.marks = t.marks_off >= 0 ? rcst + t.marks_off : nullptr;
         hipLaunchKernelGGL(k64_adj_overlap, dim3(nb, bc), dim3(256), 0, stream, (const double2 *)psi,
                            (const double2 *)lam, n, a, partial);

@@ -30,7 +30,6 @@ constexpr int kGramStep = 16;        // complex amplitudes per row per wave iter
 constexpr int kGramTile64 = 32;      // output tile of the complex128 kernel
 constexpr int kGramK64 = 32;         // complex128 amplitudes per LDS stage
 constexpr int kGramMaxRows = 4096;
-constexpr int kGramMaxGroups = 65535;  // grid.y
 constexpr int64_t kGramTargetBlocks = 2048;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -269,7 +268,7 @@ int gram_run(const void *d_a, const void *d_b, int n_qubits, int n_groups, int r
              int64_t group_stride_a, int64_t group_stride_b, void *d_out, void *d_ws, size_t ws_bytes,
              qmle_stream stream_, bool f64) {
   if (!d_a || !d_b || !d_out || n_qubits < 1 || n_qubits > 30 || n_groups < 1 ||
-      n_groups > kGramMaxGroups || rows_a < 1 || rows_b < 1 || rows_a > kGramMaxRows ||
+      n_groups > kMaxGridY || rows_a < 1 || rows_b < 1 || rows_a > kGramMaxRows ||
       rows_b > kGramMaxRows || group_stride_a < 0 || group_stride_b < 0)
     return QMLE_ERR_INVALID_ARG;
   const int64_t d = (int64_t)1 << n_qubits;

@@ -1,12 +1,16 @@
 // Host-side interfaces between the translation units of libqmle_sv (not part of the ABI):
-//   qmle_engine.hip    plan objects on the device, angle / matrix builders, qmle_run_batch & co.
+//   qmle_engine.hip    plan objects on the device, angle / matrix builders, qmle_run_batch & co.: the layout
+//                      of its workspace (BatchLayout), the two-stream chunk pipeline (ChunkPipeline)
 //   qmle_tile.hip      LDS-tile passes (k_tile, k_tile2, k_reg_measure*, product passes)
 //   qmle_direct.hip    streaming passes (one gate in place, the Golomb diagonal, fills)
 //   qmle_analysis.hip  measurement / analysis kernels of resident states, samplers
 //   qmle_adjoint.hip   adjoint differentiation
-//   qmle_f64.hip       complex128 engine
+//   qmle_f64.hip       complex128 engine (its own matrix builder, constants and observable masks)
+//   qmle_gram.hip      Gram matrices of resident states
 // Kernels stay private to their unit (anonymous namespaces); what crosses a unit boundary is a
-// plain host function that launches them.
+// plain host function that launches them.  The host idioms every unit needs live here (wire masks ->
+// position masks and their range check, aligning a caller's workspace, FNV-1a); align_up, grid_for and
+// kMaxGridY sit in qmle_dev.h.
 //
 // Environment switches: the library reads these nine and no others (tests/test_abi_cpu.py).  Unset,
 // each one leaves the measured default in place.
@@ -77,6 +81,33 @@ struct ProfScope {  // records a start/stop event pair around one stage launch
     if (active) (void)hipEventRecord((hipEvent_t)p->prof.stop[slot], stream);
   }
 };
+
+// ---- host idioms every unit shares ----
+// wires (bit w = wire w) -> bit positions of the state index (wire w is position n - 1 - w)
+inline uint32_t wires_to_pos(uint32_t wires, int n) {
+  uint32_t m = 0;
+  for (int w = 0; w < n; ++w)
+    if (wires & (1u << w)) m |= 1u << (n - 1 - w);
+  return m;
+}
+// a product of Z's / a generator's support: at least one wire and none beyond the register; otherwise
+// QMLE_ERR_WIRE_RANGE.  (At n = 32 every bit is a wire, and a shift by n would be undefined.)
+inline bool valid_wire_mask(uint32_t wires, int n) { return wires != 0 && (n >= 32 || !(wires >> n)); }
+// The caller's workspace from its first 256-byte boundary on: moves `ws` there and takes the skipped bytes
+// off `bytes`.  false: the workspace ends before that boundary.
+inline bool align_workspace(char *&ws, size_t &bytes) {
+  const size_t mis = (size_t)(256 - ((uintptr_t)ws & 255)) & 255;
+  if (bytes < mis) return false;
+  ws += mis;
+  bytes -= mis;
+  return true;
+}
+// FNV-1a over a byte range; `h`: the hash so far, to run several ranges into one value
+inline uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603ull) {
+  const unsigned char *c = (const unsigned char *)data;
+  for (size_t i = 0; i < bytes; ++i) h = (h ^ c[i]) * 1099511628211ull;
+  return h;
+}
 
 // ---- qmle_engine.hip ----
 int ensure_device_plan(qmle_plan *p);
