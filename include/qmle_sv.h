@@ -189,7 +189,14 @@ qmle_plan *qmle_plan_expval_child(qmle_plan *plan);
  * QMLE_ERR_UNSUPPORTED).  Describe, count stages of and profile THIS handle. */
 qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
 /* JSON description of the compiled passes (for tests / DESIGN.md); returns the
- * number of bytes needed (excluding NUL); writes at most cap-1 bytes + NUL. */
+ * number of bytes needed (excluding NUL); writes at most cap-1 bytes + NUL.
+ * The description follows the handle's last run in two places: a schedule adopted by
+ * qmle_plan_autotune, and stage 0's "write_bytes_from_zero".  A qmle_run_batch whose chunks share
+ * workspace slots leaves out the zero fill of a chunk when the slot still holds the zeros of an
+ * earlier chunk of the same call (all-live plans of two passes, <Z> measurements); stage 0 then reports the
+ * bytes per state that run really wrote (its fills and first-tile stores over its states), and the
+ * fresh-buffer figure 8 * 2^n before any run and after a run that filled every chunk or failed.  Describe the
+ * handle of qmle_plan_executed, after the run. */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* counts: [0]=reference gates, [1]=HBM passes, [2]=whole-state-LDS(0/1),
  * [3]=tile qubits T, [4]=floats of per-sample matrices, [5]=direct passes */

@@ -724,6 +724,22 @@ class ChunkPipeline {
   bool piped_;
 };
 
+// Does a workspace slot still hold what the filled first pass of a chunk left in it -- zeros everywhere outside tile 0
+// of each state -- when the chunk is done?  Then the next chunk in that slot needs no fill (launch_tile).  True when
+// no launch of the chunk loop behind stage 0 stores into the chunk's state buffer.  Admitted, each read to take the
+// state as input only: the last tile pass of a two-stage plan with its <Z> epilogue -- launch_tile with
+// TM_EXPVAL_PARTIAL / TM_EXPVAL_MASKS (k_tile2's measuring instantiations, k_tile + tile_epilogue: rows of partial
+// sums to `out`) or launch_reg_measure (k_reg_measure, k_reg_measure_mono: const loads, rows to `out`) -- and
+// launch_expval_final behind it (reads the rows).
+// Every other run fills every chunk: any TM_STORE / TM_STORE_MW pass or run_stage_inplace behind stage 0 (so every
+// plan of three or more stages, and two-stage plans measured otherwise than by the fused <Z> epilogue), one-stage
+// plans, probabilities, the Meyer-Wallach reads and launch_density (read-only or not: not admitted here), and
+// QMLE_MEAS_STATE, whose chunks are rows of d_out and never share a buffer.
+static bool slot_stays_zeroed(const qmle_plan *plan, bool fuse_expval) {
+  // (fuse_expval: QMLE_MEAS_EXPVAL_Z, and the last stage is a tile stage that measures instead of storing)
+  return plan->stages.size() == 2 && plan->stages[0].kind == ST_TILE && fuse_expval;
+}
+
 // Simulate + measure; <Z> observables arrive as bit-position parity masks.
 int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                           const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
@@ -758,6 +774,14 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
   const bool by_position = oc.single_bits || oc.semi_single;
   ChunkPipeline pipe(L.slots == 2, plan->stages.size(), caller_stream);
+  // Clean slots: slot_fill[k].zeroed_states states of slot k hold zeros outside tile 0 of stage 0.  It lives and dies with this call
+  // (the caller owns the workspace between calls, so a slot's first chunk is always filled), and a slot is one
+  // buffer on one stream -- ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
+  const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
+  FillReuse slot_fill[2];
+  uint64_t filled_states = 0;  // states written by fills, all chunks
+  bool elided = false;         // a chunk ran without its fill
+  plan->stage0_written_last_run = 0;  // (a run that fails reports the fresh-buffer figure)
   int chunk_no = 0;
   for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
     const int bc = std::min(batch - b0, L.in_flight);
@@ -792,10 +816,13 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
           rc = launch_reg_measure(plan, st, reg_kind, stc, mats, ang, bc, d_partial, obs_masks,
                                   n_obs, stream, &reg_q, d_coef + (size_t)b0 * 32);
         } else {
+          FillReuse *const reuse = si == 0 && reuse_zeros ? &slot_fill[slot] : nullptr;
           rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, tm,
                            last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
                            last_fused ? n_obs : 0, stream, /*from_zero=*/true, cols,
-                           last_fused && (oc.single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr);
+                           last_fused && (oc.single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr, reuse);
+          if (reuse && reuse->filled) filled_states += (uint64_t)bc;
+          if (reuse && reuse->elided) elided = true;
         }
         initialised = true;
       } else {
@@ -835,6 +862,11 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
     }
     HIPCHK(hipGetLastError());
   }
+  // what qmle_plan_describe reports as stage 0's written bytes (a report: nothing in the engine reads it): the fills
+  // and tile-0 stores of this run per state when fills were left out, else 0 = the fresh-buffer figure
+  if (elided)
+    plan->stage0_written_last_run =
+        ((filled_states << (n + 3)) + ((uint64_t)batch << (plan->stages[0].T + 3))) / (uint64_t)batch;
   return QMLE_OK;
 }
 
@@ -949,6 +981,7 @@ static void adopt_schedule(qmle_plan *dst, qmle_plan *src) {
   std::swap(dst->algo_bytes_per_state, src->algo_bytes_per_state);
   dst->force_candidate = src->force_candidate;
   dst->pad_high = src->pad_high;
+  dst->stage0_written_last_run = 0;  // (the figure of a run of the old schedule)
   dst->autotuned = true;
 }
 

@@ -124,12 +124,20 @@ int run_stage_inplace(qmle_plan *plan, const Stage &st, float2 *d_states, const 
                       const float *d_angles, int batch, hipStream_t stream);
 
 // ---- qmle_tile.hip ----
+// What launch_tile's filled first pass may take for granted about `states` (run_batch_masks keeps one per workspace
+// slot, for one call): on entry the first `zeroed_states` states hold zeros everywhere outside this stage's tile 0.
+// The pass leaves out its fill when that covers `batch` (`elided`), else it fills (`filled`) and the count becomes
+// `batch`; a launch that is no filled first pass reports neither.
+struct FillReuse {
+  int zeroed_states = 0;
+  bool filled = false, elided = false;  // of the last launch
+};
 size_t tile_lds_bytes(int T, int L, int n_slots);
 int tile_threads(int T);
 int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream, bool from_zero = false,
-                float2 *cols = nullptr, int *row_shift = nullptr);
+                float2 *cols = nullptr, int *row_shift = nullptr, FillReuse *reuse = nullptr);
 int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs);
 int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *states,
                        const float *mats, const float *angles, int batch, void *out,

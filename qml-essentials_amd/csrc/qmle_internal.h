@@ -202,6 +202,11 @@ struct qmle_plan {
   bool whole_state_lds = false;
   int tile_T = 0, tile_L = 0;
   double algo_bytes_per_state = 0;
+  // Report only (describe_plan; the engine writes it once per qmle_run_batch and never reads it): bytes per state
+  // that stage 0 of the last batch run really wrote -- its fills and tile-0 stores over its states -- when that run
+  // left out fills of chunks whose workspace slot already held the zeros; 0 (also after a run that failed): the
+  // fresh-buffer figure applies
+  uint64_t stage0_written_last_run = 0;
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)

@@ -1237,6 +1237,8 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
   const double D = std::ldexp(1.0, p->n);
   const bool sparse = !(p->flags & QMLE_PLAN_NO_SPARSE);
   if (st.kind != ST_TILE) return st.kind == ST_DIRECT ? 0.5 * st.algo_bytes_per_state : 8.0 * D;
+  // (the plan's last batch run left out fills of zeros that were in memory already: what it wrote)
+  if (si == 0 && p->stage0_written_last_run) return (double)p->stage0_written_last_run;
   if (!sparse || !st.next_tile) return 8.0 * D;
   uint32_t outer = 0;
   for (int i = 0; i < p->n - st.T; ++i) outer |= 1u << st.outer_bits[i];

@@ -1542,9 +1542,10 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
 int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream,
-                bool from_zero, float2 *cols, int *row_shift) {
+                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse) {
   // *row_shift: TM_EXPVAL_PARTIAL rows cover 2^row_shift tiles each (multi-tile k_tile2)
   if (row_shift) *row_shift = 0;
+  if (reuse) reuse->filled = reuse->elided = false;
   from_zero = from_zero && plan_sparse(p);
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
                               from_zero);
@@ -1590,9 +1591,18 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
   // All-live initialising pass (no known-zero bookkeeping downstream, so every tile must be
   // stored): the zeros come from a plain fill at the rate of a fill, tile 0 of every state from
   // the tile kernel behind it (15 us per 32 states) -- 22.4 -> 20.2 us per 2^24-amplitude state.
+  // The compact launch stores all 2^T amplitudes of tile 0 of every state (k_tile2's TM_STORE branch, k_tile's
+  // tile_epilogue, shifted or not), whatever lay there before; so where the caller knows the zeros outside tile 0 to
+  // be in memory already (FillReuse: an earlier filled pass of this stage in the same buffer, nothing stored
+  // since) the fill would write zeros over zeros and is left out.
   if (init_zero && !from_zero && meas == TM_STORE && st.T < p->n && tiles > 1 &&
       (st.fast_ok || st.T == kLdsMaxQubits) && p->n <= 28 && threads == (1 << (st.T - 4))) {
-    launch_fill_zero(states, ((uint64_t)batch << p->n) / 2u /* float4 = two amplitudes */, stream);
+    if (reuse && reuse->zeroed_states >= batch) {
+      reuse->elided = true;
+    } else {
+      launch_fill_zero(states, ((uint64_t)batch << p->n) / 2u /* float4 = two amplitudes */, stream);
+      if (reuse) { reuse->zeroed_states = batch; reuse->filled = true; }
+    }
     a.compact = 1;  // grid = the tiles that can be non-zero = tile 0
     a.tile_free = 0u;
     grid.x = 1u;

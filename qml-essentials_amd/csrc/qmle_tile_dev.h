@@ -424,7 +424,8 @@ __device__ __forceinline__ void tile_epilogue(const TileArgs &a, float2 *s, cons
   if (!PARTIAL_ONLY && (a.meas == TM_STORE || a.meas == TM_STORE_MW)) {
     if (SHIFTED && a.shift) {
       // the one tile per state of a top-first schedule: its amplitudes sit 2^shift apart, one 8-byte store each
-      // (2^14 of them per state, behind the fill that wrote the zeros; launch_tile admits no other use)
+      // (2^14 of them per state, into a buffer whose other amplitudes are zeros: from the fill in front of this
+      // launch, or from an earlier one that nothing has stored over -- launch_tile admits no other use)
       for (uint32_t j = tid; j < (1u << T); j += nt) st[(uint64_t)j << a.shift] = s[sw(j)];
     } else if ((half % (8u * nt)) == 0) {
       for (uint32_t j0 = tid; j0 < half; j0 += 8u * nt) {
