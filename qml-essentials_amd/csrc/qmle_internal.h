@@ -137,7 +137,29 @@ struct Stage {
   int fast_begin = 0, fast_end = 0;  // range in qmle_plan::groups2
   uint32_t fast_gtab = 0;            // index into qmle_plan::tbl2: per-thread global byte offset of
                                      // the lane's first float4 inside the tile (k_tile2 prologue)
+  // <Z> of every tile position straight from the registers of the LAST Group2 (k_tile2's multi-tile measuring walk
+  // skips that group's scatter and the identity re-layout): behind the group and the X / CX peeled off it, amplitude
+  // c (0..15) of work item t sits at logical tile index f = M (e(t, c)) ^ m0, so bit j of f is a parity over bits of
+  // c and t plus a constant.  zreg[j] = c mask | t mask << 4 | constant << 15 (zreg_record below); the low six bits
+  // of the t mask are lane bits, the rest wave-index bits.  zreg_ok: the records are there (fast_ok, T < n; the last
+  // group may be the empty one that only moves the data).
+  bool zreg_ok = false;
+  uint16_t zreg[16] = {};
+  // report only (describe_plan): the group's positions (in-thread bit i), the positions of its thread bits and the
+  // X / CX behind it as (control or -1, target) pairs in tile-local positions -- what the records were derived from
+  int8_t zreg_bits[4] = {}, zreg_thread_bits[12] = {};
+  std::vector<int8_t> zreg_after;
 };
+// the parts of a Stage::zreg record
+struct ZregRecord {
+  uint32_t wht;   // in-thread bits: index into the 16-point Walsh-Hadamard transform of the squares
+  uint32_t lane;  // lane bits
+  uint32_t wave;  // wave-index bits
+  uint32_t neg;   // 1: the sum enters with a minus sign
+};
+static inline ZregRecord zreg_record(uint16_t r) {
+  return {(uint32_t)r & 15u, ((uint32_t)r >> 4) & 63u, ((uint32_t)r >> 10) & 31u, (uint32_t)r >> 15};
+}
 
 struct StageProfile {  // optional HIP-event timing of every stage launch (bench.py)
   bool on = false;
@@ -207,6 +229,10 @@ struct qmle_plan {
   // left out fills of chunks whose workspace slot already held the zeros; 0 (also after a run that failed): the
   // fresh-buffer figure applies
   uint64_t stage0_written_last_run = 0;
+  // Report only, the same way: tiles per workgroup of the last stage's fused <Z> pass in the last batch run (0: no
+  // such pass ran), and whether it took <Z> from the last group's registers (Stage::zreg)
+  int measure_tpw_last_run = 0;
+  bool measure_regs_last_run = false;
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)
@@ -241,6 +267,13 @@ std::string describe_plan(const qmle_plan *p);
 // from |0..0>: 0 k_tile epilogue, 1 k_reg_measure<false>, 2 k_reg_measure<true> (gates folded
 // into columns), 3 k_reg_measure_mono.  `sparse`: known-zero tracking is on for the run.
 int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse);
+// Stage `si` QUALIFIES for <Z> from the last group's registers (Stage::zreg): it is the last of several, has a k_tile2
+// description with records (any last Group2 will do, the empty data-moving one included) and no known-zero TILES on
+// input -- known zeros INSIDE the tile are fine, idle work items hand over zeros.  Whether a run takes that path is
+// decided per launch: only a multi-tile TM_EXPVAL_PARTIAL walk does (launch_tile); a run that hands the stage to
+// k_reg_measure*, measures folded-CX parities (TM_EXPVAL_MASKS) or has too few tiles for a walk does not, and
+// qmle_plan::measure_regs_last_run says which it was.
+bool qualifies_for_register_measure(const qmle_plan *p, size_t si);
 double algo_bytes(const qmle_op &op, int n);
 constexpr int kFastMinT = 10, kFastMaxT = 13;  // k_tile2: 2^(T-4) threads, 8 float4 per thread
 constexpr int kLdsMaxQubits = 14;       // 2^14 * 8 B = 128 KiB <= 160 KiB LDS/CU

@@ -254,7 +254,8 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   };
   // M: logical index in the frame of the last emitted group -> logical index now
   uint32_t Mcol[16], Mconst = 0;
-  auto M_reset = [&]() { for (int j = 0; j < T; ++j) Mcol[j] = 1u << j; Mconst = 0; };
+  st.zreg_after.clear();  // the X / CX that make up M, in order: (control or -1, target) pairs (describe_plan)
+  auto M_reset = [&]() { for (int j = 0; j < T; ++j) Mcol[j] = 1u << j; Mconst = 0; st.zreg_after.clear(); };
   M_reset();
   auto is_perm = [](const LoweredOp &o) { return (o.flags & LF_PERMX) != 0; };
   // known-zero tile-local bits along the stage's execution (runs from |0..0>, Stage::zero_in):
@@ -265,6 +266,8 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   auto apply_perm = [&](const LoweredOp &o) {
     Z &= ~(1u << o.t0);
     const int t = o.t0;
+    st.zreg_after.push_back(o.nc == 0 ? (int8_t)-1 : o.c0);
+    st.zreg_after.push_back(o.t0);
     if (o.nc == 0) {
       Lconst ^= Lcol[t];
       Mconst ^= 1u << t;
@@ -441,7 +444,7 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
       Group2 g;
       std::memset(&g, 0, sizeof(g));
       g.op_begin = (uint32_t)p->ops2.size();
-      G = 0xFu << (T >= 9 ? 5 : 0);
+      G = last_G = 0xFu << (T >= 9 ? 5 : 0);
       emit_tables(g, G);
       M_reset();
       last_group = (int)p->groups2.size();
@@ -469,6 +472,25 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
         g.off_out[c] = swz(M_lin(e)) << 3;
       }
     }
+  }
+  // <Z> from the last group's registers (Stage::zreg): amplitude c of work item t holds index e(t, c) of the group's
+  // frame (thread bit k at position pos_of[k], in-thread bit i at the group's i-th position) and ends at logical
+  // index M e ^ Mconst; bit j of that is the parity of e under row j of M, plus bit j of Mconst
+  st.zreg_ok = false;
+  std::memset(st.zreg, 0, sizeof(st.zreg));
+  if (T < p->n) {  // (last_group: a gate group, or the empty one that only moves the data)
+    int gb[4], k = 0;
+    for (int j = 0; j < T; ++j)
+      if (last_G & (1u << j)) gb[k++] = j;
+    for (int j = 0; j < T; ++j) {
+      uint32_t rec = ((Mconst >> j) & 1u) << 15;
+      for (int i = 0; i < 4; ++i) rec |= ((Mcol[gb[i]] >> j) & 1u) << i;
+      for (int t = 0; t < T - 4; ++t) rec |= ((Mcol[pos_of[t]] >> j) & 1u) << (4 + t);
+      st.zreg[j] = (uint16_t)rec;
+    }
+    for (int i = 0; i < 4; ++i) st.zreg_bits[i] = (int8_t)gb[i];
+    for (int t = 0; t < T - 4; ++t) st.zreg_thread_bits[t] = (int8_t)pos_of[t];
+    st.zreg_ok = true;
   }
   (void)ops2_mark; (void)tbl_mark;
   // global byte offset of every lane's first float4 inside the tile: local index 2 t with its
@@ -1245,6 +1267,15 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
   return 8.0 * std::ldexp(1.0, p->n - __builtin_popcount(st.zero_in & outer));
 }
 
+bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
+  const Stage &st = p->stages[si];
+  if (st.kind != ST_TILE || !st.fast_ok || !st.zreg_ok || si == 0 || si + 1 != p->stages.size()) return false;
+  if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
+  for (int i = 0; i < p->n - st.T; ++i)  // known-zero TILES keep one tile per workgroup and its epilogue
+    if (st.zero_in & (1u << st.outer_bits[i])) return false;
+  return true;
+}
+
 int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
   const Stage &st = p->stages[si];
   if (st.kind != ST_TILE || si == 0) return 0;
@@ -1375,7 +1406,30 @@ std::string describe_plan(const qmle_plan *p) {
     for (int g = st.fast_begin; g < st.fast_end; ++g)
       os << (g > st.fast_begin ? "," : "") << "{\"n_ops\":" << p->groups2[g].n_ops
          << ",\"relayout\":" << (int)p->groups2[g].relayout << "}";
-    os << "],\"src_ops\":[";
+    // <Z> from the last group's registers (k_tile2's multi-tile measuring walk): whether the stage QUALIFIES
+    // (qualifies_for_register_measure: last of several, k_tile2 records, no known-zero tiles; what a run really did
+    // is in the _last_run fields below), the records, and what they were derived from
+    const bool from_regs = qualifies_for_register_measure(p, s);
+    os << "],\"register_measure_qualifies\":" << (from_regs ? "true" : "false");
+    if (from_regs) {
+      os << ",\"measure_records\":[";
+      for (int j = 0; j < st.T; ++j) {
+        const ZregRecord r = zreg_record(st.zreg[j]);
+        os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
+      }
+      os << "],\"measure_group_bits\":[";
+      for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_bits[i];
+      os << "],\"measure_thread_bits\":[";
+      for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_thread_bits[t];
+      os << "],\"measure_after\":[";
+      for (size_t i = 0; i + 1 < st.zreg_after.size(); i += 2)
+        os << (i ? "," : "") << "[" << (int)st.zreg_after[i] << "," << (int)st.zreg_after[i + 1] << "]";
+      os << "]";
+    }
+    if (s + 1 == p->stages.size())
+      os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run
+         << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false");
+    os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";
   }

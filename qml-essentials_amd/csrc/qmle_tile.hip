@@ -364,6 +364,7 @@ struct Tile2Args {
   int tpw;                  // consecutive tiles per workgroup (plain all-live stages; else 1)
   uint32_t tile_stride;     // amplitudes between consecutive tiles of a workgroup (2^lowest outer bit)
 };
+constexpr int kZrTotal = 13, kZrWalk = 14, kZrCols = 17;  // columns of tile_zr_finish's per-wave sums
 
 __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Args &f, uint32_t tile) {
   if (f.n_runs < 0) return tile_base(a, tile);
@@ -391,9 +392,15 @@ __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Arg
 // to spare, the HBM-regime instantiations live on a 96-VGPR budget.  solo: the workgroup is ONE wave
 // (10 qubits) -- its LDS operations execute in order, so a gather that follows a scatter needs no
 // barrier and no drain of the LDS queue, only the compiler kept from reordering them.
-template <bool KEEP>
+// ZR (the multi-tile TM_EXPVAL_PARTIAL instantiations): the LAST group's 16 amplitudes go to on_last instead of
+// being scattered -- no store, no identity re-layout, no trailing barrier: the caller squares them where they are
+// (tile_zr_accumulate) and synchronises before the tile buffer is written again.  (A work item of an idle wave --
+// known zeros -- hands over zeros.)  on_last runs INSIDE the last group's iteration: handed back through a reference,
+// the 16 amplitudes became loop-carried values -- 16 v_mov_b64 per group and 32 more live registers.
+template <bool KEEP, bool ZR = false, class OnLast = int>
 __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const Tile2Args &f,
-                                             const u64 QMLE_CONSTANT *mrow, int tid, bool use_skip, bool solo) {
+                                             const u64 QMLE_CONSTANT *mrow, int tid, bool use_skip, bool solo,
+                                             OnLast on_last = OnLast()) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   const Group2 QMLE_CONSTANT *grp = as_constant(f.groups);
   if (f.n_groups <= 0) return;
@@ -439,13 +446,17 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
         QMLE_X16(QMLE_LD)
 #undef QMLE_LD
       }
+    } else if constexpr (ZR) {
+      if (gi + 1 >= f.n_groups) r = A16{0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     }
     // (!KEEP) the 16 slot addresses are re-derived for the scatter (16 v_xor) instead of living in 16
     // VGPRs across the gates: the kernel stays within 96 VGPRs = 5 waves per SIMD
     if (!KEEP) asm volatile("" : "+v"(addr));
     const bool more = gi + 1 < f.n_groups;
     uint32_t addr_next = 0;
-    if (relayout) addr_next = f.tbl[grp->tbl_out + tid];
+    if (ZR && !more) {
+      // (the last group of the measuring walk is not scattered: no table entry to fetch, re-layout or not)
+    } else if (relayout) addr_next = f.tbl[grp->tbl_out + tid];
     else if (more) addr_next = f.tbl[grp[1].tbl + tid];
     // next group's header and basis offsets: in flight while this group's gates run
     const Group2 QMLE_CONSTANT *nx = more ? grp + 1 : grp;
@@ -463,6 +474,12 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
       w0 = w1;
       w1 = w2;
       M0 = Mn;
+    }
+    if constexpr (ZR) {
+      if (!more) {
+        on_last(r);
+        return;
+      }
     }
     if (relayout) {
       if (solo) asm volatile("" ::: "memory");
@@ -493,75 +510,98 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
 #undef QMLE_OFF
 }
 
-// <Z> of every bit for the multi-tile measuring variant: the per-tile part only squares and adds
-// (pruned Walsh-Hadamard butterfly over the four in-thread bits); the sums stay per work item
-// across the tiles a workgroup walks -- acc = {total, h0..h3, total signed by bit 0 / 1 / 2 of
-// the tile's index inside the walk} -- and the cross-lane reduction, the row assembly and the
-// store run once per workgroup (`tile_z_finish`): no barrier, no DPP chain, no global store per
-// tile.
-__device__ __forceinline__ void tile_z_accumulate(uint32_t sbo, int T, int tid, int i, float (&acc)[8]) {
-  uint32_t tid_e = (uint32_t)tid;
-  asm volatile("" : "+v"(tid_e));  // (keeps the 16 addresses out of loop-carried registers)
-  const uint32_t e0 = (sw(tid_e) << 3) + sbo;
-  float pr[16];
-#pragma unroll
-  for (int h = 0; h < 16; h += 8) {
-    u64 amp[8];
-#pragma unroll
-    for (int it = 0; it < 8; ++it) amp[it] = lds_ld64(e0 ^ (sw((uint32_t)(h + it) << (T - 4)) << 3));
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int it = 0; it < 8; ++it)
-      pr[h + it] = norm2(make_float2(__uint_as_float((uint32_t)amp[it]), __uint_as_float((uint32_t)(amp[it] >> 32))));
-    __builtin_amdgcn_sched_barrier(0);
+// <Z> of every bit for the multi-tile measuring variant, without the tile in LDS: the last group's amplitudes are
+// squared in the registers they were computed in (tile2_groups<.., ZR>); the sums stay per work item across the tiles
+// a workgroup walks, and the cross-lane reduction, the row assembly and the store run once per workgroup.  Which bit
+// of the tile index an in-thread / lane / wave bit stands for depends on the group and on the X / CX behind it
+// (Stage::zreg), so the per-tile part is layout-blind: sq[c] += |r_c|^2 -- 32 FMAs -- and the running total of sq,
+// whose increments give the walk-bit sums.  The Walsh-Hadamard butterfly over the four in-thread bits runs ONCE per
+// walk (tile_zr_finish), where every position picks the one sum its record names.
+__device__ __forceinline__ float pick16(const float (&w)[16], uint32_t i);
+// (The two FMAs per amplitude are asm: written as fmaf() the SLP vectoriser pairs the sums of neighbouring amplitudes
+// into v_pk_fma_f32 and pays for it with four v_mov_b32 per pair to line the operands up -- 6 instructions where 4
+// do -- and with 16 more live registers, which cost the kernel its budget.  Not volatile: the compiler schedules
+// them freely among the last gate's instructions.)
+__device__ __forceinline__ void tile_zr_accumulate(const A16 &r, int i, float (&sq)[16], float (&wk)[4]) {
+#define QMLE_SQ(c)                                                            \
+  {                                                                           \
+    const float re = __uint_as_float((uint32_t)r.v##c), im = __uint_as_float((uint32_t)(r.v##c >> 32)); \
+    asm("v_fmac_f32 %0, %1, %1\n\tv_fmac_f32 %0, %2, %2" : "+v"(sq[c]) : "v"(re), "v"(im)); \
   }
-  float h0 = 0.f, h1 = 0.f, h2 = 0.f, s1[8], s2[4], s3[2];
+  QMLE_X16(QMLE_SQ)
+#undef QMLE_SQ
+  float s8[8], s4[4];
 #pragma unroll
-  for (int k = 0; k < 8; ++k) { s1[k] = pr[2 * k] + pr[2 * k + 1]; h0 += pr[2 * k] - pr[2 * k + 1]; }
+  for (int k = 0; k < 8; ++k) s8[k] = sq[2 * k] + sq[2 * k + 1];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) { s2[k] = s1[2 * k] + s1[2 * k + 1]; h1 += s1[2 * k] - s1[2 * k + 1]; }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) { s3[k] = s2[2 * k] + s2[2 * k + 1]; h2 += s2[2 * k] - s2[2 * k + 1]; }
-  const float tot = s3[0] + s3[1];
-  acc[0] += tot;
-  acc[1] += h0;
-  acc[2] += h1;
-  acc[3] += h2;
-  acc[4] += s3[0] - s3[1];
-  acc[5] += (i & 1) ? -tot : tot;  // (i is wave-uniform)
-  acc[6] += (i & 2) ? -tot : tot;
-  acc[7] += (i & 4) ? -tot : tot;
+  for (int k = 0; k < 4; ++k) s4[k] = s8[2 * k] + s8[2 * k + 1];
+  const float run = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+  const float tot = run - wk[0];  // this tile's share (wk[0]: the running total behind the previous tile)
+  wk[0] = run;
+  wk[1] += (i & 1) ? -tot : tot;  // (i is wave-uniform)
+  wk[2] += (i & 2) ? -tot : tot;
+  wk[3] += (i & 4) ? -tot : tot;
 }
-// Row [33] of workgroup `row` of sample b: thread q < n assembles <Z> of position q from qsrc
-// (see TileArgs::qsrc): lane bit, in-thread bit, wave bit, or outer position = bit of the tile
-// index -- one of the `lg` walk bits (own signed sums) or a bit of the workgroup index.
-__device__ __forceinline__ void tile_z_finish(float *out, float *red, float (&acc)[8], int qsrc, int tid,
-                                              int nt, int lg, uint32_t row, uint32_t n_rows, int b) {
-  const int lane = tid & (kWave - 1), w = tid / kWave, nw = (nt + kWave - 1) / kWave;
-  float v[14];
+// Row [33] of workgroup `row` of sample b: thread q <= 32 assembles <Z> of position q (q = 32: the total) from the
+// per-wave sums -- column TileArgs::qsrc, outer positions from the walk-bit sums or the workgroup index.  zr:
+// Stage::zreg in the kernel-argument segment (TileArgs::obs_local) -- the picks and lane masks are wave-uniform scalar
+// reads, thread q reads the wave mask and sign of its own position.
+__device__ __forceinline__ void tile_zr_finish(float *out, float *red, float (&w)[16], const float (&wk)[4],
+                                               const uint16_t QMLE_CONSTANT *zr, int T, int qsrc, int tid, int nt,
+                                               int lg, uint32_t row, uint32_t n_rows, int b) {
+  const int lane = tid & (kWave - 1), wv = tid / kWave, nw = (nt + kWave - 1) / kWave;
 #pragma unroll
-  for (int j = 0; j < 6; ++j) v[j] = ((lane >> j) & 1) ? -acc[0] : acc[0];
-  v[6] = acc[1]; v[7] = acc[2]; v[8] = acc[3]; v[9] = acc[4]; v[10] = acc[0];
-  v[11] = acc[5]; v[12] = acc[6]; v[13] = acc[7];
-  wave_sums_dpp63(v);
-  __syncthreads();  // every amplitude of the last tile has been read: the tile buffer is scratch
-  if (lane == kWave - 1) {
+  for (int h = 1; h < 16; h <<= 1) {
 #pragma unroll
-    for (int j = 0; j < 14; ++j) red[w * 14 + j] = v[j];
+    for (int i = 0; i < 16; ++i) {
+      if (i & h) continue;
+      const float x = w[i], y = w[i | h];
+      w[i] = x + y;
+      w[i | h] = x - y;
+    }
+  }
+  __syncthreads();  // every gather of the last tile is done: the tile buffer is scratch
+  // (six columns per round of wave sums: a round of all 17 costs the kernel its register budget)
+  static_for<2>([&](auto h) {
+    float v[6];
+    static_for<6>([&](auto k) {
+      constexpr int j = 6 * (int)h + (int)k;
+      v[k] = 0.f;
+      if (j < T) {  // (wave-uniform)
+        const uint32_t rec = zr[j];
+        const float sel = pick16(w, rec & 15u);
+        v[k] = (__popc((uint32_t)lane & (rec >> 4) & 63u) & 1) ? -sel : sel;
+      }
+    });
+    wave_sums_dpp63(v);
+    if (lane == kWave - 1) static_for<6>([&](auto k) { red[wv * kZrCols + 6 * (int)h + (int)k] = v[k]; });
+  });
+  {
+    float v[5] = {0.f, w[0], wk[1], wk[2], wk[3]};
+    if (12 < T) {
+      const uint32_t rec = zr[12];
+      const float sel = pick16(w, rec & 15u);
+      v[0] = (__popc((uint32_t)lane & (rec >> 4) & 63u) & 1) ? -sel : sel;
+    }
+    wave_sums_dpp63(v);
+    if (lane == kWave - 1) static_for<5>([&](auto k) { red[wv * kZrCols + 12 + (int)k] = v[k]; });
   }
   __syncthreads();
   if (tid <= QMLE_MAX_QUBITS) {
     float r = 0.f;
-    if (qsrc < 16) {
-      for (int k = 0; k < nw; ++k) r += red[k * 14 + qsrc];
-    } else if (qsrc < 32) {
-      for (int k = 0; k < nw; ++k) r += ((k >> (qsrc - 16)) & 1) ? -red[k * 14 + 10] : red[k * 14 + 10];
-    } else if (qsrc < 64) {
+    if (qsrc < kZrTotal) {
+      const uint32_t rec = zr[qsrc];
+      const uint32_t mw = (rec >> 10) & 31u;
+      for (int k = 0; k < nw; ++k) r += (__popc((uint32_t)k & mw) & 1) ? -red[k * kZrCols + qsrc] : red[k * kZrCols + qsrc];
+      if (rec >> 15) r = -r;
+    } else if (qsrc == kZrTotal) {
+      for (int k = 0; k < nw; ++k) r += red[k * kZrCols + kZrTotal];
+    } else if (qsrc >= 32 && qsrc < 64) {
       const int t = qsrc - 32;
       if (t < lg) {
-        for (int k = 0; k < nw; ++k) r += red[k * 14 + 11 + t];
+        for (int k = 0; k < nw; ++k) r += red[k * kZrCols + kZrWalk + t];
       } else {
-        for (int k = 0; k < nw; ++k) r += red[k * 14 + 10];
+        for (int k = 0; k < nw; ++k) r += red[k * kZrCols + kZrTotal];
         if ((row >> (t - lg)) & 1u) r = -r;
       }
     }
@@ -732,7 +772,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   // Plain all-live stages give a workgroup `tpw` consecutive tiles (MULTI).  Storing passes keep
   // the next tile's 8 float4 per lane in flight in registers while this tile's gates run;
   // measuring passes walk without that prefetch but keep their <Z> sums in registers across the
-  // walk and reduce once (tile_z_accumulate / tile_z_finish).  Both save the workgroup turnover
+  // walk and reduce once (tile_zr_accumulate / tile_zr_finish).  Both save the workgroup turnover
   // (launch gap + prologue) per tile.  K2 at n = 24: read+write pass 54 -> 51 us per state,
   // measuring pass 29 -> 23.6.  Known-zero stages keep one tile per workgroup.
   const int tpw = MULTI ? f.tpw : 1;
@@ -810,6 +850,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
     const int8_t QMLE_CONSTANT *ka = (const int8_t QMLE_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr();
     qsrc = tid <= QMLE_MAX_QUBITS ? (int)ka[offsetof(TileArgs, qsrc) + tid] : 64;
   }
+  // ZR: the multi-tile TM_EXPVAL_PARTIAL walk takes <Z> from the last group's registers (tile_zr_accumulate; the
+  // records -- Stage::zreg -- travel in TileArgs::obs_local, which no other TM_EXPVAL_PARTIAL path reads)
+  constexpr bool ZR = MEASURE && MULTI && !WS && !MW && !MASKS;
   const bool plain = MULTI || (!a.init_zero && !a.zin_local);
   float4 v[8];
   // the 8 loads of a tile.  Multi-tile walks over a stage with known zeros INSIDE the tile
@@ -835,9 +878,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
       for (int u = 0; u < 8; ++u) v[u] = ld4<NT>(reinterpret_cast<const float4 *>(p + uoff[u] + goff8));
     }
   };
-  if (plain) load_tile(st);
+  // (the measuring walk loads every tile inside the loop: loaded here, the first tile's 32 registers become
+  // loop-carried values that stay allocated across the gate groups of every tile)
+  if (plain && !ZR) load_tile(st);
   const uint32_t sl_outer = sl;
-  float zacc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // MEASURE && MULTI: tile_z_accumulate
+  float zsq[ZR ? 16 : 1], zwk[4] = {0.f, 0.f, 0.f, 0.f};
+  if (ZR) static_for<16>([&](auto c) { zsq[ZR ? (int)c : 0] = 0.f; });
   float pacc[MASKS ? kMaskMultiObs : 1];                      // MASKS: tile_m_accumulate
   if (MASKS) static_for<kMaskMultiObs>([&](auto k) { pacc[MASKS ? (int)k : 0] = 0.f; });
   const uint16_t QMLE_CONSTANT *m_ol =
@@ -849,11 +895,13 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   for (int i = 0; i < tpw; ++i) {
     uint32_t sl = sl_outer;  // (opaque per tile: keeps the 8 staging addresses out of loop-carried registers)
     if (MULTI) asm volatile("" : "+v"(sl));
-    if (MULTI && MEASURE && i > 0) {
+    if (MULTI && MEASURE && (ZR || i > 0)) {
       // measuring passes walk their tiles without prefetch (measured with it, before and after
       // the sums moved into registers: no gain)
-      base += f.tile_stride;
-      st += f.tile_stride * sizeof(float2);
+      if (i > 0) {
+        base += f.tile_stride;
+        st += f.tile_stride * sizeof(float2);
+      }
       load_tile(st);
     }
     if (!MULTI && a.init_zero) {
@@ -888,7 +936,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
       load_tile(st);
     }
 
-    tile2_groups<WS>(sbo, addr, f, mrow, tid, a.zin_local != 0, WS && nt <= kWave);  // known zeros: Stage::zero_in
+    if constexpr (ZR) {
+      tile2_groups<WS, true>(sbo, addr, f, mrow, tid, a.zin_local != 0, false,
+                             [&](const A16 &last) { tile_zr_accumulate(last, i, zsq, zwk); });
+    } else {
+      tile2_groups<WS>(sbo, addr, f, mrow, tid, a.zin_local != 0, WS && nt <= kWave);  // known zeros: Stage::zero_in
+    }
 
     if (MW) {
       if (a.meas == TM_STORE_MW) {
@@ -904,8 +957,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
       tile_mw_accumulate(sbo, T, (uint32_t)tid, (uint32_t)i, macc, a.mw_lean != 0);
     } else if (MEASURE && MULTI && MASKS) {  // (TM_EXPVAL_MASKS: launch_tile)
       if constexpr (MASKS) tile_m_accumulate(sbo, T, tid, tile + (uint32_t)i, a.n_obs, m_ol, m_oo, pacc);
-    } else if (MEASURE && MULTI) {  // (TM_EXPVAL_PARTIAL only: launch_tile)
-      tile_z_accumulate(sbo, T, tid, i, zacc);
+    } else if (MEASURE && MULTI) {  // (TM_EXPVAL_PARTIAL only: launch_tile; accumulated above)
     } else if (MEASURE) {
       if (a.meas == TM_EXPVAL) whole_state_expval(a, sl, soff, red, tid, nt, b);
       else tile_epilogue(a, s, nullptr, red, tile + (uint32_t)i, n_tiles, b, base_cur, qsrc);
@@ -943,9 +995,11 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   else if (MEASURE && MULTI && MASKS) {
     if constexpr (MASKS)
       tile_m_finish(reinterpret_cast<float *>(a.out), red, pacc, a.n_obs, m_ol, T, tid, nt, blockIdx.x, gridDim.x, b);
-  } else if (MEASURE && MULTI)
-    tile_z_finish(reinterpret_cast<float *>(a.out), red, zacc, qsrc, tid, nt, 31 - __builtin_clz((unsigned)tpw),
-                  blockIdx.x, gridDim.x, b);
+  } else if (MEASURE && MULTI) {
+    if constexpr (ZR)
+      tile_zr_finish(reinterpret_cast<float *>(a.out), red, zsq, zwk, m_ol, T, qsrc, tid, nt,
+                     31 - __builtin_clz((unsigned)tpw), blockIdx.x, gridDim.x, b);
+  }
 }
 
 // ---- measuring pass in registers -----------------------------------------------------------
@@ -1542,9 +1596,10 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
 int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream,
-                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse) {
+                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs) {
   // *row_shift: TM_EXPVAL_PARTIAL rows cover 2^row_shift tiles each (multi-tile k_tile2)
   if (row_shift) *row_shift = 0;
+  if (from_regs) *from_regs = false;
   if (reuse) reuse->filled = reuse->elided = false;
   from_zero = from_zero && plan_sparse(p);
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
@@ -1783,6 +1838,16 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       } else {
         *row_shift = 31 - __builtin_clz((unsigned)f.tpw);
       }
+    }
+    // The measuring walk takes <Z> from the last group's registers (tile_zr_accumulate): thread q finds local
+    // position j in column j of the per-wave sums, the total in column kZrTotal (outer positions keep 32 + i)
+    if (meas == TM_EXPVAL_PARTIAL && f.tpw > 1 && !st.zreg_ok) return QMLE_ERR_INTERNAL;  // (build_fast_groups sets it)
+    if (meas == TM_EXPVAL_PARTIAL && f.tpw > 1) {
+      static_assert(sizeof(st.zreg) <= sizeof(a.obs_local), "the records travel in TileArgs::obs_local");
+      std::memcpy(a.obs_local, st.zreg, sizeof(st.zreg));
+      for (int j = 0; j < st.T; ++j) a.qsrc[(int)st.tile_bits[j]] = (uint8_t)j;
+      a.qsrc[QMLE_MAX_QUBITS] = (uint8_t)kZrTotal;
+      if (from_regs) *from_regs = true;
     }
     // T >= 10: the per-tile epilogues' scratch fits inside the tile; the whole-state <Z> epilogue
     // reduces while amplitudes are still being read and gets its own 288 floats

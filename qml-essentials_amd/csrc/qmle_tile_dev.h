@@ -244,10 +244,15 @@ struct TileArgs {
   int8_t outer_bits[QMLE_MAX_QUBITS];
   uint32_t obs_mask[QMLE_MAX_QUBITS];  // per observable: bit p set <=> Z on bit position p
   uint16_t obs_local[QMLE_MAX_QUBITS]; // the same restricted to the tile, in LOCAL bits (bit j <=> Z on tile_bits[j])
+                                       // (k_tile2's multi-tile TM_EXPVAL_PARTIAL walk: Stage::zreg[j] per local bit j)
   uint32_t obs_outer[QMLE_MAX_QUBITS]; // ... and to the outer positions, in TILE-INDEX bits (bit i <=> Z on outer_bits[i])
   // TM_EXPVAL_PARTIAL, full-size tiles: where thread q finds <Z> of global bit position q among the
   // per-wave sums: 0..5 lane bit, 6..9 iteration bit, 10 total (q = 32), 16 + k wave-index bit k,
   // 32 + i outer position i (sign = tile-index bit i), 64 unused
+  // k_tile2's multi-tile walk (tile_zr_finish, launch_tile overwrites the coding above): j = 0..12 column j of the
+  // per-wave sums = tile-local position j (its wave mask and sign: Stage::zreg[j] in obs_local), 13 the total
+  // (kZrTotal, q = 32), 32 + i outer position i -- walk bit i < log2(tpw): column 14 + i (kZrWalk), else the total
+  // signed by bit i - log2(tpw) of the workgroup index --, 64 unused; kZrCols = 17 columns per wave
   uint8_t qsrc[QMLE_MAX_QUBITS + 1];
 };
 
