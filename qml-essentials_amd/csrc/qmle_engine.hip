@@ -784,6 +784,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   plan->stage0_written_last_run = 0;  // (a run that fails reports the fresh-buffer figure)
   plan->measure_tpw_last_run = 0;     // (reports as well: how the last stage's fused <Z> pass ran)
   plan->measure_regs_last_run = false;
+  plan->wave_private_last_run = false;
   int chunk_no = 0;
   for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
     const int bc = std::min(batch - b0, L.in_flight);
@@ -828,6 +829,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
           if (last_fused) {
             plan->measure_tpw_last_run = 1 << tile_row_shift;
             plan->measure_regs_last_run = from_regs;
+            plan->wave_private_last_run = from_regs && st.wave_private;
           }
           if (reuse && reuse->filled) filled_states += (uint64_t)bc;
           if (reuse && reuse->elided) elided = true;

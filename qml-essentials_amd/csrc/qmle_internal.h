@@ -98,7 +98,7 @@ struct Group2 {
   uint32_t op_begin;   // first op in qmle_plan::ops2
   uint16_t n_ops;
   uint8_t relayout;
-  uint8_t pad;
+  uint8_t sync;        // bit 0: the measuring walk needs a workgroup barrier in front of this group's gather (Stage::fast_info)
   uint32_t tbl;        // index into qmle_plan::tbl2 (one uint32 per thread of the workgroup)
   uint32_t tbl_out;    // relayout: scatter table
   uint32_t off[16];
@@ -149,6 +149,23 @@ struct Stage {
   // X / CX behind it as (control or -1, target) pairs in tile-local positions -- what the records were derived from
   int8_t zreg_bits[4] = {}, zreg_thread_bits[12] = {};
   std::vector<int8_t> zreg_after;
+  // Wave-private phases of the measuring walk (k_tile2's register-measuring instantiations).  A phase --
+  // staging the loaded tile, a group's gather / gates / in-place scatter -- partitions the tile's 2^T slots among the
+  // workgroup's waves; a barrier between two consecutive phases is needed exactly when their partitions differ
+  // (Group2::sync bit 0: in front of that group's gather; sync_tile_end: between the last group's gather and the next
+  // tile's staging).  slab_load: the tile is loaded and staged so that wave w owns the 2^10 slots whose top T - 10
+  // bits are w (lane bits at local bits 1..6, the lane's 8 float4 at 7..9), which is the partition of a first group
+  // that leaves the top positions to the wave index; fast_gtab_slab: its per-thread global offsets.  wave_private:
+  // no barrier is left in the tile loop.  Computed on the tables as emitted (mark_wave_private_phases), for stages
+  // that qualify for the register measurement; every other stage keeps all its barriers.
+  struct FastGroupInfo {   // report only: what a group's tables were emitted from (describe_plan)
+    uint8_t bits[4];       // the group's positions (in-thread bit i)
+    int8_t thread_bits[12];  // position of thread-index bit k
+    uint32_t cols[16], cnst; // layout map at that point: logical index e -> slot XOR_{j in e} cols[j] ^ cnst (before sw())
+  };
+  std::vector<FastGroupInfo> fast_info;  // one per Group2 of [fast_begin, fast_end)
+  bool slab_load = false, sync_tile_end = true, wave_private = false;
+  uint32_t fast_gtab_slab = 0;
 };
 // the parts of a Stage::zreg record
 struct ZregRecord {
@@ -233,6 +250,7 @@ struct qmle_plan {
   // such pass ran), and whether it took <Z> from the last group's registers (Stage::zreg)
   int measure_tpw_last_run = 0;
   bool measure_regs_last_run = false;
+  bool wave_private_last_run = false;     // ... and ran its tile loop without a workgroup barrier (Stage::wave_private)
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)

@@ -227,10 +227,30 @@ static void group_stage_ops(qmle_plan *p, Stage &st) {
 // Layout map: logical tile index e lives at physical slot L(e) = XOR_{j in e} Lcol[j] ^ Lconst.
 static inline uint32_t swz(uint32_t e) { return e ^ (((e >> 5) & 15u) << 1); }  // = sw() in qmle_dev.h
 
+static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured);
+
+// What qualifies_for_register_measure asks of a stage's place and input, known while the stage is being built: it is
+// the last of several, a tile smaller than the state, and no known-zero TILES come in (`zero_in`: Stage::zero_in).
+static bool placed_for_register_measure(const qmle_plan *p, const Stage &st, uint32_t zero_in, bool first, bool last) {
+  if (first || !last || st.T >= p->n) return false;
+  if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
+  for (int i = 0; i < p->n - st.T; ++i)  // known-zero TILES keep one tile per workgroup and its epilogue
+    if (zero_in & (1u << st.outer_bits[i])) return false;
+  return true;
+}
+
+// measured: the stage qualifies for <Z> from the last group's registers (qualifies_for_register_measure).  Its X / CX
+// that would hand a slot of one wave's slab to another wave -- the target's layout column holds one of the top
+// T - 10 slot bits -- and whose bits no later op of the stage touches are kept back and applied behind the last group,
+// where they only change the records (Stage::zreg); the groups in front then keep one partition of the tile among the
+// waves and the walk needs no barrier between them (mark_wave_private_phases).
 static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<LoweredOp> &src,
-                              uint32_t zin_local) {
+                              uint32_t zin_local, bool measured) {
   st.fast_ok = false;
   st.fast_begin = st.fast_end = (int)p->groups2.size();
+  st.fast_info.clear();
+  st.slab_load = st.wave_private = false;
+  st.sync_tile_end = true;
   const int T = st.T;
   if (T < kFastMinT || T > kFastMaxT || (p->flags & QMLE_PLAN_NO_REGTILE)) return;
   for (const LoweredOp &o : src)
@@ -337,6 +357,13 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
       if (G & (1u << j)) gb[k++] = j;
     // (the idle-work-item flags below are only read by tiled runs that track known zeros)
     choose_thread_bits(G, (Z & ~G) != 0 && T < p->n && !(p->flags & QMLE_PLAN_NO_SPARSE));
+    g.sync = 1;
+    Stage::FastGroupInfo info{};
+    for (int j = 0; j < 4; ++j) info.bits[j] = (uint8_t)gb[j];
+    for (int t = 0; t < T - 4; ++t) info.thread_bits[t] = (int8_t)pos_of[t];
+    for (int j = 0; j < T; ++j) info.cols[j] = Lcol[j];
+    info.cnst = Lconst;
+    st.fast_info.push_back(info);
     g.tbl = (uint32_t)p->tbl2.size();
     for (uint32_t t = 0; t < nt; ++t) {
       const uint32_t e = deposit(t, G);
@@ -353,6 +380,18 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   int n_done = 0;
   int last_group = -1;
   uint32_t last_G = 0;
+  std::vector<int> held;  // X / CX kept back for behind the last group
+  const uint32_t slab_bits = T > 10 ? ((1u << T) - 1u) & ~1023u : 0u;
+  // (Correctness rests on the scan alone: an X / CX that no later op touches commutes with everything behind it.  The
+  // column test only says when waiting pays: X[t] XORs column t into the constant, CX[c -> t] into column c, so a
+  // column t that holds a slab bit is what would move slots between slabs.)
+  auto keeps_back = [&](int i) {
+    if (!measured || !(Lcol[(int)src[i].t0] & slab_bits)) return false;
+    const uint32_t m = mask_of(src[i]);
+    for (int j = i + 1; j < nops; ++j)
+      if (!done[j] && (mask_of(src[j]) & m)) return false;
+    return true;
+  };
   while (n_done < nops) {
     uint32_t G = 0, touched = 0, blocked = 0;
     std::vector<int> mem, after;  // `after`: X / CX applied to the layout behind the group
@@ -362,7 +401,8 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
       if (m & blocked) { blocked |= m; continue; }
       if (is_perm(src[i])) {
         if (!(m & touched)) {  // independent of the group: layout only, before the group
-          apply_perm(src[i]);
+          if (keeps_back(i)) held.push_back(i);
+          else apply_perm(src[i]);
           done[i] = 1;
           ++n_done;
         } else if ((m & ~G) == 0 && mem.size() < 4000) {
@@ -429,7 +469,8 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
     }
     M_reset();
     for (int i : trailing) {
-      apply_perm(src[i]);
+      if (keeps_back(i)) held.push_back(i);
+      else apply_perm(src[i]);
       done[i] = 1;
       ++n_done;
     }
@@ -437,19 +478,20 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
     last_G = G;
     p->groups2.push_back(g);
   }
+  if (last_group < 0) {  // nothing but layout changes (or no gate at all): an empty group moves the data
+    Group2 g;
+    std::memset(&g, 0, sizeof(g));
+    g.op_begin = (uint32_t)p->ops2.size();
+    last_G = 0xFu << (T >= 9 ? 5 : 0);
+    emit_tables(g, last_G);
+    M_reset();
+    last_group = (int)p->groups2.size();
+    p->groups2.push_back(g);
+  }
+  for (int i : held) apply_perm(src[i]);  // (they commute with every op behind them: tape order among themselves)
   // the epilogue (store / measure) reads the tile in the identity layout
-  if (!L_is_identity() || last_group < 0) {
-    uint32_t G = last_G;
-    if (last_group < 0) {  // nothing but layout changes (or no gate at all): an empty group moves the data
-      Group2 g;
-      std::memset(&g, 0, sizeof(g));
-      g.op_begin = (uint32_t)p->ops2.size();
-      G = last_G = 0xFu << (T >= 9 ? 5 : 0);
-      emit_tables(g, G);
-      M_reset();
-      last_group = (int)p->groups2.size();
-      p->groups2.push_back(g);
-    }
+  {
+    const uint32_t G = last_G;
     Group2 &g = p->groups2[last_group];
     if (!L_is_identity()) {
       // a thread holds logical index e of the group's frame; its final logical index is M(e)
@@ -505,6 +547,53 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   }
   st.fast_end = (int)p->groups2.size();
   st.fast_ok = true;
+  mark_wave_private_phases(p, st, measured);
+}
+
+// Which wave touches which slot in every phase of the measuring walk, read off the tables as emitted; sets
+// Group2::sync, Stage::slab_load / sync_tile_end / wave_private (Stage::fast_info) and emits the slab load map's
+// global offsets.  The walk hands the last group's registers to the measurement, so no re-layout scatter is a phase.
+static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured) {
+  const int T = st.T, ng = st.fast_end - st.fast_begin;
+  if (!measured || ng <= 0 || T < 10) return;
+  const uint32_t nt = 1u << (T - 4), size = 1u << T;
+  auto staging = [&](bool slab) {  // a lane's 8 float4 = 16 slots (qmle_tile.hip, k_tile2)
+    std::vector<uint8_t> own(size);
+    for (uint32_t t = 0; t < nt; ++t)
+      for (uint32_t u = 0; u < 8; ++u) {
+        const uint32_t e = slab ? (2u * (t & 63u)) | (u << 7) | ((t >> 6) << 10) : (2u * t) | (u << (T - 3));
+        own[swz(e)] = own[swz(e) ^ 1u] = (uint8_t)(t >> 6);
+      }
+    return own;
+  };
+  auto gather = [&](const Group2 &g) {
+    std::vector<uint8_t> own(size);
+    for (uint32_t t = 0; t < nt; ++t)
+      for (int c = 0; c < 16; ++c) own[((p->tbl2[g.tbl + t] ^ g.off[c]) >> 3) & (size - 1u)] = (uint8_t)(t >> 6);
+    return own;
+  };
+  std::vector<std::vector<uint8_t>> part;
+  for (int g = 0; g < ng; ++g) part.push_back(gather(p->groups2[st.fast_begin + g]));
+  st.slab_load = part[0] == staging(true);
+  const std::vector<uint8_t> staged = staging(st.slab_load);
+  bool any = false;
+  for (int g = 0; g < ng; ++g) {
+    const bool sync = part[g] != (g ? part[g - 1] : staged);
+    p->groups2[st.fast_begin + g].sync = sync ? 1 : 0;
+    any |= sync;
+  }
+  st.sync_tile_end = part[ng - 1] != staged;
+  st.wave_private = !any && !st.sync_tile_end;
+  if (st.slab_load) {
+    st.fast_gtab_slab = (uint32_t)p->tbl2.size();
+    for (uint32_t t = 0; t < nt; ++t) {
+      const uint32_t jl = (2u * (t & 63u)) | ((t >> 6) << 10);
+      uint32_t g = 0;
+      for (int j = 0; j < T; ++j)
+        if (jl & (1u << j)) g |= 1u << st.tile_bits[j];
+      p->tbl2.push_back(g << 3);
+    }
+  }
 }
 
 // ---- observable absorption ---------------------------------------------------------------
@@ -1041,7 +1130,9 @@ int compile_plan(qmle_plan *p) {
         uint32_t zin_local = 0;  // known-zero bits when this stage starts, tile-local
         for (int j = 0; j < st.T; ++j)
           if (Zrun & (1u << st.tile_bits[j])) zin_local |= 1u << j;
-        build_fast_groups(p, st, tile_local, zin_local);
+        // (what qualifies_for_register_measure will ask of the finished plan; Zrun is this stage's zero_in)
+        const bool measured = placed_for_register_measure(p, st, Zrun, p->stages.empty(), n_done + members.size() == nl);
+        build_fast_groups(p, st, tile_local, zin_local, measured);
         group_stage_ops(p, st);
       }
       for (int mi : members) {
@@ -1269,11 +1360,8 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
 
 bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
   const Stage &st = p->stages[si];
-  if (st.kind != ST_TILE || !st.fast_ok || !st.zreg_ok || si == 0 || si + 1 != p->stages.size()) return false;
-  if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
-  for (int i = 0; i < p->n - st.T; ++i)  // known-zero TILES keep one tile per workgroup and its epilogue
-    if (st.zero_in & (1u << st.outer_bits[i])) return false;
-  return true;
+  if (st.kind != ST_TILE || !st.fast_ok || !st.zreg_ok) return false;
+  return placed_for_register_measure(p, st, st.zero_in, si == 0, si + 1 == p->stages.size());
 }
 
 int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
@@ -1403,14 +1491,31 @@ std::string describe_plan(const qmle_plan *p) {
          << (int)og.bits[2] << "," << (int)og.bits[3] << "]}";
     }
     os << "],\"fast\":" << (st.fast_ok ? "true" : "false") << ",\"fast_groups\":[";
-    for (int g = st.fast_begin; g < st.fast_end; ++g)
+    for (int g = st.fast_begin; g < st.fast_end; ++g) {
       os << (g > st.fast_begin ? "," : "") << "{\"n_ops\":" << p->groups2[g].n_ops
-         << ",\"relayout\":" << (int)p->groups2[g].relayout << "}";
+         << ",\"relayout\":" << (int)p->groups2[g].relayout
+         << ",\"sync_before\":" << ((p->groups2[g].sync & 1) ? "true" : "false");
+      // what the group's tables were emitted from: slot of amplitude c of work item t = sw(XOR of the columns of
+      // e(t, c) ^ const), thread bit k of t at position thread_bits[k], bit i of c at position bits[i]
+      const Stage::FastGroupInfo &fi = st.fast_info[g - st.fast_begin];
+      os << ",\"bits\":[";
+      for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)fi.bits[i];
+      os << "],\"thread_bits\":[";
+      for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)fi.thread_bits[t];
+      os << "],\"layout_cols\":[";
+      for (int j = 0; j < st.T; ++j) os << (j ? "," : "") << fi.cols[j];
+      os << "],\"layout_const\":" << fi.cnst << "}";
+    }
     // <Z> from the last group's registers (k_tile2's multi-tile measuring walk): whether the stage QUALIFIES
     // (qualifies_for_register_measure: last of several, k_tile2 records, no known-zero tiles; what a run really did
     // is in the _last_run fields below), the records, and what they were derived from
     const bool from_regs = qualifies_for_register_measure(p, s);
     os << "],\"register_measure_qualifies\":" << (from_regs ? "true" : "false");
+    // the measuring walk's barriers (Stage::fast_info): which load map it stages with, whether a barrier stays between
+    // the last group and the next tile's staging, and whether none is left in the tile loop
+    if (st.fast_ok)
+      os << ",\"load_map\":\"" << (st.slab_load ? "slab" : "rows") << "\",\"sync_tile_end\":"
+         << (st.sync_tile_end ? "true" : "false") << ",\"wave_private_walk\":" << (st.wave_private ? "true" : "false");
     if (from_regs) {
       os << ",\"measure_records\":[";
       for (int j = 0; j < st.T; ++j) {
@@ -1428,7 +1533,8 @@ std::string describe_plan(const qmle_plan *p) {
     }
     if (s + 1 == p->stages.size())
       os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run
-         << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false");
+         << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false")
+         << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false");
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";

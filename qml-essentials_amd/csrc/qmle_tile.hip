@@ -363,7 +363,13 @@ struct Tile2Args {
   uint32_t in_off[4], in_mask[4], in_pos[4];
   int tpw;                  // consecutive tiles per workgroup (plain all-live stages; else 1)
   uint32_t tile_stride;     // amplitudes between consecutive tiles of a workgroup (2^lowest outer bit)
+  // register-measuring walk only (Stage::fast_info): kWalkSlab -- in_* / gtab / uoff8 describe the slab-owning load
+  // map (lane bits at local bits 1..6, the 8 float4 at 7..9, the wave index on top); kWalkSyncStaged / kWalkSyncTileEnd
+  // -- a workgroup barrier is needed behind the staging stores / before the next tile's.  (Last member: no other
+  // kernel's argument offsets move.)
+  uint32_t walk;
 };
+constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u;
 constexpr int kZrTotal = 13, kZrWalk = 14, kZrCols = 17;  // columns of tile_zr_finish's per-wave sums
 
 __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Args &f, uint32_t tile) {
@@ -397,6 +403,8 @@ __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Arg
 // (tile_zr_accumulate) and synchronises before the tile buffer is written again.  (A work item of an idle wave --
 // known zeros -- hands over zeros.)  on_last runs INSIDE the last group's iteration: handed back through a reference,
 // the 16 amplitudes became loop-carried values -- 16 v_mov_b64 per group and 32 more live registers.
+// ZR walks also honour Group2::sync: where the next group's waves own the slots they owned in this one, the barrier
+// between the two becomes the compiler-only fence of the solo form.
 template <bool KEEP, bool ZR = false, class OnLast = int>
 __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const Tile2Args &f,
                                              const u64 QMLE_CONSTANT *mrow, int tid, bool use_skip, bool solo,
@@ -416,7 +424,7 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     const u64 QMLE_CONSTANT *m = mrow + (w0.z >> 1);
     M0 = {m[0], m[1], m[2], m[3]};
   }
-  // header word (n_ops | relayout << 16) and the four basis offsets of the first group
+  // header word (n_ops | relayout << 16 | sync << 24) and the four basis offsets of the first group
   uint32_t hdr = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(grp)[1];
   uint32_t o1 = grp->off[1], o2 = grp->off[2], o4 = grp->off[4], o8 = grp->off[8];
 #define QMLE_OFF(c, b1, b2, b4, b8) \
@@ -504,7 +512,7 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     addr = addr_next;
     hdr = hdr_n;
     o1 = n1; o2 = n2; o4 = n4; o8 = n8;
-    if (solo) asm volatile("" ::: "memory");
+    if (solo || (ZR && !((hdr_n >> 24) & 1u))) asm volatile("" ::: "memory");  // (uniform: the header sits in SGPRs)
     else __syncthreads();
   }
 #undef QMLE_OFF
@@ -796,7 +804,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   // come from tid, the top three from u (wave-uniform)
   // (both come precomputed: indexing the int8 position arrays of the kernel arguments with
   // run-time indices costs a chain of vector loads in front of the tile's own loads)
-  const uint32_t jl = 2u * tid;
+  // (ZR -- the register-measuring walk -- may be told to take the slab-owning map instead: Tile2Args::walk)
+  constexpr bool ZR = MEASURE && MULTI && !WS && !MW && !MASKS;
+  const uint32_t walk = ZR ? f.walk : (kWalkSyncStaged | kWalkSyncTileEnd);
+  const bool slab = ZR && (walk & kWalkSlab) != 0;
+  const uint32_t jl = slab ? (2u * (tid & (kWave - 1))) | ((uint32_t)(tid / kWave) << 10) : 2u * tid;
+  const int ush = slab ? 7 : T - 3;  // local bit of u's lowest bit
   uint32_t goff8;  // < 2^31 for n <= 28
   if (f.n_in_runs < 0) {
     goff8 = f.tbl[f.gtab + tid];
@@ -811,7 +824,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
 #pragma unroll
   for (int u = 0; u < 8; ++u) {
     uoff[u] = f.uoff8[u];
-    soff[u] = sw((uint32_t)u << (T - 3)) << 3;  // LDS byte offset; sw() is linear over XOR
+    soff[u] = sw((uint32_t)u << ush) << 3;  // LDS byte offset; sw() is linear over XOR
   }
   const uint32_t sl = (sw(jl) << 3) + sbo;
   const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -852,7 +865,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   }
   // ZR: the multi-tile TM_EXPVAL_PARTIAL walk takes <Z> from the last group's registers (tile_zr_accumulate; the
   // records -- Stage::zreg -- travel in TileArgs::obs_local, which no other TM_EXPVAL_PARTIAL path reads)
-  constexpr bool ZR = MEASURE && MULTI && !WS && !MW && !MASKS;
   const bool plain = MULTI || (!a.init_zero && !a.zin_local);
   float4 v[8];
   // the 8 loads of a tile.  Multi-tile walks over a stage with known zeros INSIDE the tile
@@ -868,7 +880,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         v[u] = z4;
-        if (((jl | ((uint32_t)u << (T - 3))) & zl_m) == 0) {
+        if (((jl | ((uint32_t)u << ush)) & zl_m) == 0) {
           v[u] = ld4<NT>(reinterpret_cast<const float4 *>(p + uoff[u] + goff8));
           if (z0_m) v[u].z = v[u].w = 0.f;
         }
@@ -927,7 +939,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
 #pragma unroll
       for (int u = 0; u < 8; ++u) lds_st128(sl ^ soff[u], v[u]);
     }
-    __syncthreads();
+    if (ZR && !(walk & kWalkSyncStaged)) asm volatile("" ::: "memory");  // the first group's waves gather what they staged
+    else __syncthreads();
     char *st_cur = st;
     const uint64_t base_cur = base;
     if (!MEASURE && i + 1 < tpw) {  // (plain storing stages only) the next tile: loads in flight from here on
@@ -987,7 +1000,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
             make_float2(w.x * w.x + w.y * w.y, w.z * w.z + w.w * w.w);
       }
     }
-    if (i + 1 < tpw) __syncthreads();  // the tile buffer (and the epilogue's scratch in it) is reused
+    // the tile buffer (and the epilogue's scratch in it) is reused (a wave-private walk: by the wave that read it)
+    if (ZR && !(walk & kWalkSyncTileEnd)) asm volatile("" ::: "memory");
+    else if (i + 1 < tpw) __syncthreads();
   }
   if (MW)  // one row per workgroup (= per tile: launch_tile keeps these stages at one tile per workgroup)
     tile_mw_finish(macc, T, (uint32_t)tid, reinterpret_cast<float *>(s),
@@ -1784,9 +1799,10 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       }
       f.n_runs = r <= 6 ? r : -1;
       for (int k = r < 6 ? r : 6; k < 6; ++k) f.run_off[k] = f.run_mask[k] = f.run_pos[k] = 0;
-      // local bits 0 .. T-4 (bit 0 of 2 tid is always clear, harmless) as runs
-      r = 0;
-      const int top = st.T - 4;
+    }
+    // local bits 0 .. top of a lane's index (bits it never sets are harmless) -> global positions, as runs
+    auto lane_runs = [&](int top) {
+      int r = 0;
       for (int j = 0; j <= top && r <= 4;) {
         int len = 1;
         while (j + len <= top && st.tile_bits[j + len] == st.tile_bits[j] + len) ++len;
@@ -1800,10 +1816,12 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       }
       f.n_in_runs = r <= 4 ? r : -1;
       for (int k = r < 4 ? r : 4; k < 4; ++k) f.in_off[k] = f.in_mask[k] = f.in_pos[k] = 0;
-    }
+    };
+    lane_runs(st.T - 4);  // index 2 tid
     for (unsigned u = 0; u < 8; ++u)
       f.uoff8[u] = (((u & 1u) << st.tile_bits[st.T - 3]) | (((u >> 1) & 1u) << st.tile_bits[st.T - 2]) |
                     (((u >> 2) & 1u) << st.tile_bits[st.T - 1])) << 3;
+    f.walk = kWalkSyncStaged | kWalkSyncTileEnd;
     // plain all-live stages: several consecutive tiles per workgroup (next tile prefetched into
     // registers), as long as the grid still fills the chip a few times over
     // (default 4 for storing passes, 8 for the measuring pass, whose per-workgroup reduction is
@@ -1848,6 +1866,16 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       for (int j = 0; j < st.T; ++j) a.qsrc[(int)st.tile_bits[j]] = (uint8_t)j;
       a.qsrc[QMLE_MAX_QUBITS] = (uint8_t)kZrTotal;
       if (from_regs) *from_regs = true;
+      // ... and elides the barriers between phases in which every wave keeps its slots (mark_wave_private_phases)
+      f.walk = (p->groups2[st.fast_begin].sync & 1 ? kWalkSyncStaged : 0u) | (st.sync_tile_end ? kWalkSyncTileEnd : 0u);
+      if (st.slab_load) {  // the lane's local index has bits 1..6 and 10..T-1 set, its 8 float4 are local bits 7..9
+        f.walk |= kWalkSlab;
+        f.gtab = st.fast_gtab_slab;
+        lane_runs(st.T - 1);
+        for (unsigned u = 0; u < 8; ++u)
+          f.uoff8[u] = (((u & 1u) << st.tile_bits[7]) | (((u >> 1) & 1u) << st.tile_bits[8]) |
+                        (((u >> 2) & 1u) << st.tile_bits[9])) << 3;
+      }
     }
     // T >= 10: the per-tile epilogues' scratch fits inside the tile; the whole-state <Z> epilogue
     // reduces while amplitudes are still being read and gets its own 288 floats
