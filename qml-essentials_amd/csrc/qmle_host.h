@@ -138,7 +138,8 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream, bool from_zero = false,
                 float2 *cols = nullptr, int *row_shift = nullptr, FillReuse *reuse = nullptr,
-                bool *from_regs = nullptr);  // *from_regs: <Z> came from the last group's registers (Stage::zreg)
+                bool *from_regs = nullptr,   // *from_regs: <Z> came from the last group's registers (Stage::zreg)
+                bool *by_dma = nullptr);     // *by_dma: ... and the walk staged its tiles by LDS DMA (Stage::dma_tables)
 int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs);
 int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *states,
                        const float *mats, const float *angles, int batch, void *out,

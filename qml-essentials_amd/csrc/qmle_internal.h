@@ -166,7 +166,19 @@ struct Stage {
   std::vector<FastGroupInfo> fast_info;  // one per Group2 of [fast_begin, fast_end)
   bool slab_load = false, sync_tile_end = true, wave_private = false;
   uint32_t fast_gtab_slab = 0;
+  // Staging by LDS DMA: a wave whose slab nobody else touches between its last gather of one tile and its
+  // first gather of the next (slab_load, no barrier in front of the first group, none at the tile's end) lets
+  // global_load_lds write the next tile's eight 1 KiB pieces straight into the slab.  Piece u of wave w lands
+  // lane-linear at slots u << 7 | w << 10 .. + 127, so lane l fetches the pair whose SWIZZLED index is that slot:
+  // local index sw(2 l | u << 7 | w << 10) = sw(2 l | w << 10) ^ u << 7 ^ (u & 3) << 3.  fast_gtab_dma: the global
+  // byte offset of sw(2 l | w << 10) per work item; dma_delta[k]: that of local index k << 3 (XORed in per piece).
+  // dma_tables: what the tables allow; a run also needs an input without known zeros inside the tile.
+  bool dma_tables = false;
+  uint32_t fast_gtab_dma = 0, dma_delta[4] = {};
 };
+// A stage's lane offsets as runs: local bits 0 .. top -> global positions, contiguous stretches (off, mask, pos).
+// Returns their number, or -1 when there are more than four (k_tile2 then reads the offsets from its table).
+int stage_lane_runs(const Stage &st, int top, uint32_t off[4], uint32_t mask[4], uint32_t pos[4]);
 // the parts of a Stage::zreg record
 struct ZregRecord {
   uint32_t wht;   // in-thread bits: index into the 16-point Walsh-Hadamard transform of the squares
@@ -251,6 +263,7 @@ struct qmle_plan {
   int measure_tpw_last_run = 0;
   bool measure_regs_last_run = false;
   bool wave_private_last_run = false;     // ... and ran its tile loop without a workgroup barrier (Stage::wave_private)
+  bool staging_dma_last_run = false;      // ... and staged its tiles by LDS DMA (Stage::dma_tables)
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)
@@ -292,6 +305,8 @@ int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse);
 // k_reg_measure*, measures folded-CX parities (TM_EXPVAL_MASKS) or has too few tiles for a walk does not, and
 // qmle_plan::measure_regs_last_run says which it was.
 bool qualifies_for_register_measure(const qmle_plan *p, size_t si);
+// ... and its walk stages by LDS DMA whenever it runs: Stage::dma_tables, and no known zeros inside the tile.
+bool stages_by_dma(const qmle_plan *p, size_t si);
 double algo_bytes(const qmle_op &op, int n);
 constexpr int kFastMinT = 10, kFastMaxT = 13;  // k_tile2: 2^(T-4) threads, 8 float4 per thread
 constexpr int kLdsMaxQubits = 14;       // 2^14 * 8 B = 128 KiB <= 160 KiB LDS/CU

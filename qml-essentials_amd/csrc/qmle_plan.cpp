@@ -249,7 +249,7 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   st.fast_ok = false;
   st.fast_begin = st.fast_end = (int)p->groups2.size();
   st.fast_info.clear();
-  st.slab_load = st.wave_private = false;
+  st.slab_load = st.wave_private = st.dma_tables = false;
   st.sync_tile_end = true;
   const int T = st.T;
   if (T < kFastMinT || T > kFastMaxT || (p->flags & QMLE_PLAN_NO_REGTILE)) return;
@@ -594,6 +594,38 @@ static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured) {
       p->tbl2.push_back(g << 3);
     }
   }
+  // LDS DMA in place of register staging (Stage::dma_tables): the wave that gathered a slot last stages it next, and
+  // gathers it first.  The DMA's destination is lane-linear, so the swizzle goes on the source index (swz is its own
+  // inverse and stays inside a 1 KiB piece): the per-lane part of it here, bits 3 and 4 of the piece's part as deltas.
+  st.dma_tables = st.slab_load && !(p->groups2[st.fast_begin].sync & 1) && !st.sync_tile_end;
+  if (st.dma_tables) {
+    auto global_of = [&](uint32_t e) {
+      uint32_t g = 0;
+      for (int j = 0; j < T; ++j)
+        if (e & (1u << j)) g |= 1u << st.tile_bits[j];
+      return g << 3;
+    };
+    st.fast_gtab_dma = (uint32_t)p->tbl2.size();
+    for (uint32_t t = 0; t < nt; ++t) p->tbl2.push_back(global_of(swz((2u * (t & 63u)) | ((t >> 6) << 10))));
+    for (uint32_t k = 0; k < 4; ++k) st.dma_delta[k] = global_of(k << 3);
+  }
+}
+
+int stage_lane_runs(const Stage &st, int top, uint32_t off[4], uint32_t mask[4], uint32_t pos[4]) {
+  int r = 0;
+  for (int j = 0; j <= top && r <= 4;) {
+    int len = 1;
+    while (j + len <= top && st.tile_bits[j + len] == st.tile_bits[j] + len) ++len;
+    if (r < 4) {
+      off[r] = (uint32_t)j;
+      mask[r] = (1u << len) - 1u;
+      pos[r] = (uint32_t)st.tile_bits[j];
+    }
+    ++r;
+    j += len;
+  }
+  for (int k = r < 4 ? r : 4; k < 4; ++k) off[k] = mask[k] = pos[k] = 0;
+  return r <= 4 ? r : -1;
 }
 
 // ---- observable absorption ---------------------------------------------------------------
@@ -1364,6 +1396,15 @@ bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
   return placed_for_register_measure(p, st, st.zero_in, si == 0, si + 1 == p->stages.size());
 }
 
+bool stages_by_dma(const qmle_plan *p, size_t si) {
+  const Stage &st = p->stages[si];
+  if (!qualifies_for_register_measure(p, si) || !st.dma_tables) return false;
+  if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
+  for (int j = 0; j < st.T; ++j)  // known zeros inside the tile: the walk zero-fills and loads selectively
+    if (st.zero_in & (1u << st.tile_bits[j])) return false;
+  return true;
+}
+
 int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
   const Stage &st = p->stages[si];
   if (st.kind != ST_TILE || si == 0) return 0;
@@ -1516,6 +1557,27 @@ std::string describe_plan(const qmle_plan *p) {
     if (st.fast_ok)
       os << ",\"load_map\":\"" << (st.slab_load ? "slab" : "rows") << "\",\"sync_tile_end\":"
          << (st.sync_tile_end ? "true" : "false") << ",\"wave_private_walk\":" << (st.wave_private ? "true" : "false");
+    // how the walk stages a tile (Stage::dma_tables) and, for the DMA form, its source map: the byte offset of work
+    // item t's pair inside the tile (the table, and the runs the kernel takes instead when there are at most four,
+    // applied to sw(2 lane | wave << 10)), XOR the delta of piece u & 3, plus the offset of u's three bits
+    if (st.fast_ok) {
+      const bool dma = stages_by_dma(p, s);
+      os << ",\"staging\":\"" << (dma ? "dma" : "registers") << "\"";
+      if (dma) {
+        os << ",\"dma_deltas\":[" << st.dma_delta[0] << "," << st.dma_delta[1] << "," << st.dma_delta[2] << ","
+           << st.dma_delta[3] << "],\"dma_lane_offsets\":[";
+        for (uint32_t t = 0; t < (1u << (st.T - 4)); ++t) os << (t ? "," : "") << p->tbl2[st.fast_gtab_dma + t];
+        uint32_t off[4], mask[4], pos[4];
+        const int nr = stage_lane_runs(st, st.T - 1, off, mask, pos);
+        os << "],\"dma_lane_runs\":";
+        if (nr < 0) os << "null";
+        else {
+          os << "[";
+          for (int r = 0; r < nr; ++r) os << (r ? "," : "") << "[" << off[r] << "," << mask[r] << "," << pos[r] << "]";
+          os << "]";
+        }
+      }
+    }
     if (from_regs) {
       os << ",\"measure_records\":[";
       for (int j = 0; j < st.T; ++j) {
@@ -1534,7 +1596,8 @@ std::string describe_plan(const qmle_plan *p) {
     if (s + 1 == p->stages.size())
       os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run
          << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false")
-         << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false");
+         << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false")
+         << ",\"staging_dma_last_run\":" << (p->staging_dma_last_run ? "true" : "false");
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";

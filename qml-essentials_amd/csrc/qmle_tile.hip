@@ -365,11 +365,14 @@ struct Tile2Args {
   uint32_t tile_stride;     // amplitudes between consecutive tiles of a workgroup (2^lowest outer bit)
   // register-measuring walk only (Stage::fast_info): kWalkSlab -- in_* / gtab / uoff8 describe the slab-owning load
   // map (lane bits at local bits 1..6, the 8 float4 at 7..9, the wave index on top); kWalkSyncStaged / kWalkSyncTileEnd
-  // -- a workgroup barrier is needed behind the staging stores / before the next tile's.  (Last member: no other
-  // kernel's argument offsets move.)
+  // -- a workgroup barrier is needed behind the staging stores / before the next tile's.  kWalkDma (with kWalkSlab and
+  // neither barrier; Stage::dma_tables): the tile is staged by LDS DMA, one tile ahead -- in_* / gtab give the lane's
+  // offset for the SWIZZLED index sw(2 lane | wave << 10), dma_delta[u & 3] is XORed in for piece u.  (Last members:
+  // no other kernel's argument offsets move.)
   uint32_t walk;
+  uint32_t dma_delta[4];
 };
-constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u;
+constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u, kWalkDma = 8u;
 constexpr int kZrTotal = 13, kZrWalk = 14, kZrCols = 17;  // columns of tile_zr_finish's per-wave sums
 
 __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Args &f, uint32_t tile) {
@@ -405,10 +408,12 @@ __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Arg
 // the 16 amplitudes became loop-carried values -- 16 v_mov_b64 per group and 32 more live registers.
 // ZR walks also honour Group2::sync: where the next group's waves own the slots they owned in this one, the barrier
 // between the two becomes the compiler-only fence of the solo form.
-template <bool KEEP, bool ZR = false, class OnLast = int>
+// ZR, on_gathered: runs in the last group's iteration once its gather has RETURNED (the wave's LDS reads are retired),
+// in front of its gates: from there on nothing reads the tile, and the DMA walk issues the next tile into it.
+template <bool KEEP, bool ZR = false, class OnLast = int, class OnGathered = int>
 __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const Tile2Args &f,
                                              const u64 QMLE_CONSTANT *mrow, int tid, bool use_skip, bool solo,
-                                             OnLast on_last = OnLast()) {
+                                             OnLast on_last = OnLast(), OnGathered on_gathered = OnGathered()) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   const Group2 QMLE_CONSTANT *grp = as_constant(f.groups);
   if (f.n_groups <= 0) return;
@@ -470,6 +475,9 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     const Group2 QMLE_CONSTANT *nx = more ? grp + 1 : grp;
     const uint32_t hdr_n = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(nx)[1];
     const uint32_t n1 = nx->off[1], n2 = nx->off[2], n4 = nx->off[4], n8 = nx->off[8];
+    if constexpr (ZR) {
+      if (!more) on_gathered();
+    }
     for (int j = 0; j < n_ops; ++j, ++k) {
       // scalar loads return out of order, so only lgkmcnt(0) can cover them: touching this
       // gate's operands HERE puts that wait in front of the next prefetch instead of behind it
@@ -808,16 +816,18 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   constexpr bool ZR = MEASURE && MULTI && !WS && !MW && !MASKS;
   const uint32_t walk = ZR ? f.walk : (kWalkSyncStaged | kWalkSyncTileEnd);
   const bool slab = ZR && (walk & kWalkSlab) != 0;
+  const bool dma = ZR && (walk & kWalkDma) != 0;  // (comes with kWalkSlab and neither kWalkSync bit: launch_tile)
   const uint32_t jl = slab ? (2u * (tid & (kWave - 1))) | ((uint32_t)(tid / kWave) << 10) : 2u * tid;
   const int ush = slab ? 7 : T - 3;  // local bit of u's lowest bit
   uint32_t goff8;  // < 2^31 for n <= 28
   if (f.n_in_runs < 0) {
     goff8 = f.tbl[f.gtab + tid];
   } else {
+    const uint32_t jg = dma ? sw(jl) : jl;  // (the DMA's destination is lane-linear: the swizzle goes on the source)
     uint32_t g = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      if (r < f.n_in_runs) g |= ((jl >> f.in_off[r]) & f.in_mask[r]) << f.in_pos[r];
+      if (r < f.n_in_runs) g |= ((jg >> f.in_off[r]) & f.in_mask[r]) << f.in_pos[r];
     goff8 = g << 3;
   }
   uint32_t uoff[8], soff[8];
@@ -852,6 +862,32 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
     }
     return;
   }
+  // The DMA walk (kWalkDma): the tile at `p` goes into LDS as eight 1 KiB pieces per wave, written by the loads
+  // themselves -- no register in between, no ds_write.  Piece u of wave w lands lane-linear at byte (w << 13) + (u << 10)
+  // of the tile, which is where the register-staged slab form puts the pairs sw(2 lane | u << 7 | w << 10): goff8
+  // holds the lane's part of that source index, the piece adds local bits 3 and 4 (XOR: the lane's part may hold them)
+  // and its own three bits.  A wave issues into its own slab only, and only when its last reads of it have returned.
+  auto dma_tile = [&](const char *p) {
+    if constexpr (ZR) {
+      const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(tid / kWave);
+      __attribute__((address_space(3))) char *slab0 =
+          (__attribute__((address_space(3))) char *)reinterpret_cast<char *>(smem4) + (wv << 13);
+      // (scalar base + 32-bit lane offset, both opaque: left to itself the loop keeps eight 64-bit addresses per lane
+      // alive across the tiles, 16 registers)
+      asm volatile("" : "+s"(p));
+      uint32_t vo[4];
+      static_for<4>([&](auto k) {
+        vo[(int)k] = goff8 ^ f.dma_delta[(int)k];
+        asm volatile("" : "+v"(vo[(int)k]));
+      });
+      static_for<8>([&](auto u) {
+        const char *src = p + uoff[(int)u] + vo[(int)u & 3];
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, slab0 + ((int)u << 10), 16, 0,
+                                         NT ? 2 : 0);  // (aux 2 = nt, the policy of ld4<true>)
+      });
+    }
+  };
+  if (dma) dma_tile(st);  // the first tile: in flight while the tables and the matrix row are fetched
   const Group2 QMLE_CONSTANT *grp = as_constant(f.groups);
   const uint32_t addr = f.n_groups > 0 ? f.tbl[grp->tbl + tid] : 0u;  // in flight beside the tile
   const u64 QMLE_CONSTANT *mrow = as_constant(reinterpret_cast<const u64 *>(a.mats + (size_t)b * a.mat_floats));
@@ -914,9 +950,12 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
         base += f.tile_stride;
         st += f.tile_stride * sizeof(float2);
       }
-      load_tile(st);
+      if (!dma) load_tile(st);
     }
-    if (!MULTI && a.init_zero) {
+    if (dma) {
+      // this tile was issued one tile ago (the first: in the prologue) by this wave into its own slab
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else if (!MULTI && a.init_zero) {
 #pragma unroll
       for (int u = 0; u < 8; ++u) lds_st128(sl ^ soff[u], z4);
       __syncthreads();
@@ -950,8 +989,14 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
     }
 
     if constexpr (ZR) {
-      tile2_groups<WS, true>(sbo, addr, f, mrow, tid, a.zin_local != 0, false,
-                             [&](const A16 &last) { tile_zr_accumulate(last, i, zsq, zwk); });
+      tile2_groups<WS, true>(
+          sbo, addr, f, mrow, tid, a.zin_local != 0, false, [&](const A16 &last) { tile_zr_accumulate(last, i, zsq, zwk); },
+          [&] {  // (nothing behind the walk's last tile: tile_zr_finish's scratch aliases the tile)
+            if (dma && i + 1 < tpw) {
+              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the gather has returned: the slab is dead
+              dma_tile(st + f.tile_stride * sizeof(float2));
+            }
+          });
     } else {
       tile2_groups<WS>(sbo, addr, f, mrow, tid, a.zin_local != 0, WS && nt <= kWave);  // known zeros: Stage::zero_in
     }
@@ -1611,10 +1656,11 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
 int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream,
-                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs) {
+                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs, bool *by_dma) {
   // *row_shift: TM_EXPVAL_PARTIAL rows cover 2^row_shift tiles each (multi-tile k_tile2)
   if (row_shift) *row_shift = 0;
   if (from_regs) *from_regs = false;
+  if (by_dma) *by_dma = false;
   if (reuse) reuse->filled = reuse->elided = false;
   from_zero = from_zero && plan_sparse(p);
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
@@ -1801,27 +1847,13 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       for (int k = r < 6 ? r : 6; k < 6; ++k) f.run_off[k] = f.run_mask[k] = f.run_pos[k] = 0;
     }
     // local bits 0 .. top of a lane's index (bits it never sets are harmless) -> global positions, as runs
-    auto lane_runs = [&](int top) {
-      int r = 0;
-      for (int j = 0; j <= top && r <= 4;) {
-        int len = 1;
-        while (j + len <= top && st.tile_bits[j + len] == st.tile_bits[j] + len) ++len;
-        if (r < 4) {
-          f.in_off[r] = (uint32_t)j;
-          f.in_mask[r] = (1u << len) - 1u;
-          f.in_pos[r] = (uint32_t)st.tile_bits[j];
-        }
-        ++r;
-        j += len;
-      }
-      f.n_in_runs = r <= 4 ? r : -1;
-      for (int k = r < 4 ? r : 4; k < 4; ++k) f.in_off[k] = f.in_mask[k] = f.in_pos[k] = 0;
-    };
+    auto lane_runs = [&](int top) { f.n_in_runs = stage_lane_runs(st, top, f.in_off, f.in_mask, f.in_pos); };
     lane_runs(st.T - 4);  // index 2 tid
     for (unsigned u = 0; u < 8; ++u)
       f.uoff8[u] = (((u & 1u) << st.tile_bits[st.T - 3]) | (((u >> 1) & 1u) << st.tile_bits[st.T - 2]) |
                     (((u >> 2) & 1u) << st.tile_bits[st.T - 1])) << 3;
     f.walk = kWalkSyncStaged | kWalkSyncTileEnd;
+    for (int k = 0; k < 4; ++k) f.dma_delta[k] = 0;
     // plain all-live stages: several consecutive tiles per workgroup (next tile prefetched into
     // registers), as long as the grid still fills the chip a few times over
     // (default 4 for storing passes, 8 for the measuring pass, whose per-workgroup reduction is
@@ -1875,6 +1907,14 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
         for (unsigned u = 0; u < 8; ++u)
           f.uoff8[u] = (((u & 1u) << st.tile_bits[7]) | (((u >> 1) & 1u) << st.tile_bits[8]) |
                         (((u >> 2) & 1u) << st.tile_bits[9])) << 3;
+        // ... and by LDS DMA where each wave's slab stays its own from one tile's last gather to the next tile's
+        // first, and every amplitude of the tile is loaded (known-zero walks zero-fill and load selectively)
+        if (st.dma_tables && !a.zin_local) {
+          f.walk |= kWalkDma;
+          f.gtab = st.fast_gtab_dma;
+          for (int k = 0; k < 4; ++k) f.dma_delta[k] = st.dma_delta[k];
+          if (by_dma) *by_dma = true;
+        }
       }
     }
     // T >= 10: the per-tile epilogues' scratch fits inside the tile; the whole-state <Z> epilogue
