@@ -340,6 +340,40 @@ int qmle_expval_parity(const void *d_states, int n_qubits, int batch, const uint
                        int n_obs, float *d_out, void *d_workspace, size_t workspace_bytes,
                        qmle_stream stream);
 size_t qmle_expval_parity_workspace_bytes(int n_qubits, int batch);
+/* Pauli-word observables in one pass over the state (X / Y / Hermitian observables, operations.py:421-460
+ * and simulation.py:263-269, any wire count): every such observable is a real-weighted sum of words.
+ *   d_out[b][o] = sum over terms t with obs == o of coef_t * <psi_b| P_t |psi_b>,
+ *   P = i^popcount(x & z) * X^x * Z^z   (so Y = i X Z per wire);  a column without a term is 0.
+ * `terms` is a HOST array of 1..65536 entries, n_obs 1..4096, n_qubits 1..30, any batch (cut into launches
+ * inside).  d_out float32 (complex64 states) / float64 (complex128 states) [batch][n_obs].  Terms whose X/Y
+ * factors together touch at most 8 bit positions above the lowest 4 share ONE read of the state (up to 12
+ * qubits: always one); a word with more X/Y factors than that is streamed with its partner amplitudes (two
+ * reads per distinct x mask, shared by every term with that mask).  Partial sums -- one fp64 slot per wave of
+ * a 2^12-amplitude tile, n_obs * max(1, 2^(n_qubits - 12)) * 4 slots per state of a launch (at most 65535 states)
+ * -- go to the workspace and are added in fixed order in fp64: the same bits from call to call.  The workspace
+ * therefore grows with n_obs * 2^n_qubits / 128 bytes per state (6 MiB for 47 observables at 24 qubits, 512 MiB
+ * for 4096): callers with many observables on large registers pass fewer states per call.  QMLE_ERR_INVALID_ARG, before any device work, for NULL pointers,
+ * counts out of range, an `obs` outside [0, n_obs) and a workspace smaller than the query's answer;
+ * QMLE_ERR_WIRE_RANGE for a mask bit at or above n_qubits. */
+typedef struct qmle_pauli_term {
+  uint32_t x_wires, z_wires; /* bit w = wire w; X: x only, Z: z only, Y: both */
+  int32_t obs;               /* which output column this term adds to */
+  double coef;               /* real weight */
+} qmle_pauli_term;
+int qmle_expval_pauli(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms,
+                      int n_terms, int n_obs, float *d_out, void *d_ws, size_t ws_bytes, qmle_stream stream);
+int qmle_expval_pauli_f64(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms,
+                          int n_terms, int n_obs, double *d_out, void *d_ws, size_t ws_bytes,
+                          qmle_stream stream);
+size_t qmle_expval_pauli_workspace_bytes(int n_qubits, int batch, int n_terms, int n_obs);
+size_t qmle_expval_pauli_workspace_bytes_f64(int n_qubits, int batch, int n_terms, int n_obs);
+/* host only, like qmle_meyer_wallach_reads: how many times the call streams the state from HBM (or the
+ * negative status the call itself would return for these terms) */
+int qmle_expval_pauli_reads(int n_qubits, const qmle_pauli_term *terms, int n_terms, int f64);
+/* Tr(P rho) on vec(rho) (2n-wire register, ket wires first, complex64); terms name the n system wires.
+ * d_out float32 [batch][n_obs]; the same argument checks, 2 * n_qubits <= QMLE_MAX_QUBITS. */
+int qmle_density_expval_pauli(const void *d_rho, int n_qubits, int batch, const qmle_pauli_term *terms,
+                              int n_terms, int n_obs, float *d_out, qmle_stream stream);
 /* Meyer-Wallach: d_out[b] = 2 (1 - 1/n sum_j Tr rho_j^2), Tr rho_j^2 = a^2+d^2+2|c|^2
  * (entanglement.py:86-101 via the Schmidt identity).
  * d_purities (optional, may be NULL): [batch][n] float32 */

@@ -120,6 +120,11 @@ class AngleMapArgs:
         return self
 
 
+class QmlePauliTerm(C.Structure):
+    """qmle_pauli_term (include/qmle_sv.h): one weighted Pauli word of an observable."""
+    _fields_ = [("x_wires", C.c_uint32), ("z_wires", C.c_uint32), ("obs", C.c_int32), ("coef", C.c_double)]
+
+
 _lib = None
 
 # Opt-in plan autotuner (QMLE_AUTOTUNE=1 or set_autotune(True)): a plan's first "state" / "expval" run on
@@ -171,6 +176,12 @@ SYMBOLS = [
     ("qmle_overlap_workspace_bytes", _SZ, [_I, _I]),
     ("qmle_expval_parity", _I, [_VP, _I, _I, C.POINTER(C.c_uint32), _I, _VP, _VP, _SZ, _VP]),
     ("qmle_expval_parity_workspace_bytes", _SZ, [_I, _I]),
+    ("qmle_expval_pauli", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_expval_pauli_f64", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_expval_pauli_workspace_bytes", _SZ, [_I, _I, _I, _I]),
+    ("qmle_expval_pauli_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
+    ("qmle_expval_pauli_reads", _I, [_I, C.POINTER(QmlePauliTerm), _I, _I]),
+    ("qmle_density_expval_pauli", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP]),
     ("qmle_meyer_wallach", _I, [_VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     ("qmle_meyer_wallach_workspace_bytes", _SZ, [_I, _I]),
     ("qmle_meyer_wallach_reads", _I, [_I]),
@@ -860,6 +871,89 @@ def expval_parity(states, wire_groups):
     check(lib().qmle_expval_parity(C.c_void_p(states.data_ptr()), n, B, arr, len(masks),
                                    C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), wsb,
                                    _stream_ptr()), "qmle_expval_parity")
+    return out
+
+
+def pauli_term_array(terms):
+    """``[(coef, x_wire_mask, z_wire_mask, obs)]`` -> a ctypes array of ``qmle_pauli_term``."""
+    arr = (QmlePauliTerm * max(1, len(terms)))()
+    for k, (coef, x, z, ob) in enumerate(terms):
+        if (int(x) | int(z)) >> 32 or int(x) < 0 or int(z) < 0:  # (ctypes would truncate the mask silently)
+            check(-4, "qmle_pauli_term: a wire beyond 31")
+        arr[k] = QmlePauliTerm(int(x), int(z), int(ob), float(coef))
+    return arr
+
+
+def pauli_terms_supported(n_qubits: int, terms) -> bool:
+    """Whether ``qmle_expval_pauli`` takes this term list for an ``n_qubits`` register: the library's own
+    argument check (term, observable and qubit counts, wire range), asked through its host-only planner."""
+    if not terms or any((int(x) | int(z)) >> 32 for _, x, z, _ in terms):
+        return False
+    return int(lib().qmle_expval_pauli_reads(int(n_qubits), pauli_term_array(terms), len(terms), 0)) > 0
+
+
+PAULI_WORKSPACE_BYTES = 256 << 20  # expval_pauli: states per native call are cut so that its workspace stays below
+
+
+def expval_pauli(states, terms, n_obs: int):
+    """Weighted Pauli words of resident states: ``out[b, o] = sum_t coef_t <psi_b|P_t|psi_b>`` over the
+    ``terms`` ``(coef, x_wire_mask, z_wire_mask, o)``.  complex64 states -> float32 (``qmle_expval_pauli``),
+    complex128 -> float64 (``qmle_expval_pauli_f64``); any batch size; owns its workspace."""
+    torch = require_gpu()
+    if states.dtype not in (torch.complex64, torch.complex128) or not states.is_cuda:
+        raise ValueError("states must be a complex64 / complex128 CUDA tensor [B, 2^n]")
+    states = states.contiguous()
+    if states.dim() == 1:
+        states = states.unsqueeze(0)
+    B, D = int(states.shape[0]), int(states.shape[1])
+    n = D.bit_length() - 1
+    if 1 << n != D:
+        raise ValueError(f"state length {D} is not a power of two")
+    f64 = states.dtype == torch.complex128
+    out = torch.empty((B, int(n_obs)), dtype=torch.float64 if f64 else torch.float32, device=states.device)
+    if B == 0 or n_obs == 0:
+        return out
+    if not terms:
+        return out.zero_()
+    fn, wsq = ((lib().qmle_expval_pauli_f64, lib().qmle_expval_pauli_workspace_bytes_f64) if f64
+               else (lib().qmle_expval_pauli, lib().qmle_expval_pauli_workspace_bytes))
+    arr = pauli_term_array(terms)
+    # the partial table is n_obs * 2^n / 128 bytes per state: many observables on a large register go through
+    # in slices of the batch (at least one state per call) instead of a workspace that outgrows the states
+    per_state = max(1, int(wsq(n, 2, len(terms), int(n_obs))) - int(wsq(n, 1, len(terms), int(n_obs))))
+    rows = max(1, min(B, PAULI_WORKSPACE_BYTES // per_state))
+    wsb = int(wsq(n, rows, len(terms), int(n_obs)))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=states.device)
+    for b0 in range(0, B, rows):
+        bc = min(rows, B - b0)
+        check(fn(C.c_void_p(states[b0:b0 + bc].data_ptr()), n, bc, arr, len(terms), int(n_obs),
+                 C.c_void_p(out[b0:b0 + bc].data_ptr()), C.c_void_p(ws.data_ptr()), wsb, _stream_ptr()),
+              "qmle_expval_pauli_f64" if f64 else "qmle_expval_pauli")
+    return out
+
+
+def pauli_reads(n_qubits: int, terms, f64: bool = False) -> int:
+    """HBM reads of the state per ``expval_pauli`` call with these terms (host only)."""
+    r = int(lib().qmle_expval_pauli_reads(int(n_qubits), pauli_term_array(terms), len(terms), int(f64)))
+    check(min(r, 0), "qmle_expval_pauli_reads")
+    return r
+
+
+def density_expval_pauli(rho_vec, n_qubits: int, terms, n_obs: int):
+    """``Tr(P rho)``-weighted sums per observable from vec(rho) ``[B, 4^n]`` complex64 -> float32
+    ``[B, n_obs]``; ``terms`` as for :func:`expval_pauli`."""
+    torch = require_gpu()
+    rho_vec = rho_vec.contiguous()
+    B = int(rho_vec.shape[0])
+    out = torch.empty((B, int(n_obs)), dtype=torch.float32, device=rho_vec.device)
+    if B == 0 or n_obs == 0:
+        return out
+    if not terms:
+        return out.zero_()
+    check(lib().qmle_density_expval_pauli(C.c_void_p(rho_vec.data_ptr()), int(n_qubits), B,
+                                          pauli_term_array(terms), len(terms), int(n_obs),
+                                          C.c_void_p(out.data_ptr()), _stream_ptr()),
+          "qmle_density_expval_pauli")
     return out
 
 

@@ -7,6 +7,7 @@
 //   qmle_adjoint.hip   adjoint differentiation
 //   qmle_f64.hip       complex128 engine (its own matrix builder, constants and observable masks)
 //   qmle_gram.hip      Gram matrices of resident states
+//   qmle_pauli.hip     Pauli-word observables of resident states and of vec(rho), their host planner
 // Kernels stay private to their unit (anonymous namespaces); what crosses a unit boundary is a
 // plain host function that launches them.  The host idioms every unit needs live here (wire masks ->
 // position masks and their range check, aligning a caller's workspace, FNV-1a); align_up, grid_for and

@@ -616,6 +616,69 @@ def z_parity_mask(ob: Operation) -> Optional[List[int]]:
     return None
 
 
+MAX_PAULI_WIRES = 6  # pauli_decompose: at most 4^6 words per observable
+
+
+def pauli_decompose(matrix, wires) -> List[Tuple[float, int, int]]:
+    """``[(coef, x_wire_mask, z_wire_mask)]`` with ``sum coef * P = (M + M^+) / 2`` on ``wires`` (first
+    wire = most significant bit of the matrix index, ``operations.py:38-50``), ``P = i^ny X^x Z^z`` (Y = iXZ
+    per wire; bit w of a mask = wire w) and ``coef = Re tr(P M) / 2^k``.  The real part is all an
+    expectation value needs: ``<P>`` is real, so ``Re<psi|M psi> = sum coef <P>`` for any M.  Terms with
+    ``|coef| <= 1e-14 max|coef|`` -- float64 round-off of a trace over at most 64 entries -- are dropped."""
+    wires = _wire_list(wires)
+    k = len(wires)
+    m = np.asarray(matrix, dtype=np.complex128)
+    if k > MAX_PAULI_WIRES:
+        raise ValueError(f"pauli_decompose takes at most {MAX_PAULI_WIRES} wires, got {k}")
+    if m.shape != (2**k, 2**k):
+        raise ValueError(f"matrix shape {m.shape} does not match {k} wire(s)")
+    d = 2**k
+    idx = np.arange(d)
+    popc = np.array([bin(i).count("1") for i in range(d)])
+    hadamard = 1.0 - 2.0 * (popc[idx[:, None] & idx[None, :]] & 1)   # (-1)^popc(z & s)
+    # P[r, r ^ x] = i^ny (-1)^popc((r ^ x) & z): tr(P M) = i^ny sum_s (-1)^popc(s & z) M[s, s ^ x]
+    coefs = np.empty((d, d))  # [x, z]
+    for x in range(d):
+        tr = hadamard @ m[idx, idx ^ x]
+        coefs[x] = np.real((1j ** (popc[x & idx] & 3)) * tr) / d
+    top = np.max(np.abs(coefs))
+    out = []
+    for x in range(d):
+        for z in range(d):
+            c = coefs[x, z]
+            if abs(c) <= 1e-14 * top:
+                continue
+            xw = sum(((x >> (k - 1 - j)) & 1) << wires[j] for j in range(k))
+            zw = sum(((z >> (k - 1 - j)) & 1) << wires[j] for j in range(k))
+            out.append((float(c), xw, zw))
+    return out
+
+
+def pauli_terms(ob: Operation) -> Optional[List[Tuple[float, int, int]]]:
+    """The observable as weighted Pauli words ``[(coef, x_wire_mask, z_wire_mask)]`` -- what
+    ``qmle_expval_pauli`` measures in one pass -- or None where it has none here (a batched matrix, a
+    parametrised operation, a channel, more than ``MAX_PAULI_WIRES`` wires): those keep the route that
+    applies the observable as a gate."""
+    if isinstance(ob, KrausChannel) or ob._param_names:
+        return None
+    if isinstance(ob, Id):
+        return [(1.0, 0, 0)]
+    parity = z_parity_mask(ob)
+    if parity is not None:
+        return [(1.0, 0, sum(1 << w for w in parity))]
+    if isinstance(ob, (PauliX, PauliY)):
+        bit = 1 << ob.wires[0]
+        return [(1.0, bit, bit if isinstance(ob, PauliY) else 0)]
+    try:
+        m = np.asarray(ob.matrix)
+    except NotImplementedError:
+        return None
+    k = len(ob.wires)
+    if m.ndim != 2 or k > MAX_PAULI_WIRES or m.shape != (2**k, 2**k):
+        return None
+    return pauli_decompose(m, ob.wires)
+
+
 # ---- noise channels ---------------------------------------------------------------------------
 _SUPEROPERATORS: dict = {}  # KrausChannel.superoperator
 

@@ -156,12 +156,16 @@ class CompiledCall:
                 return self.plan.run(angles, "expval", arg)
             if how == "parity":
                 return self.plan.run_parity(angles, arg)
-            return simulation._general_expval(self.plan.run(angles, "state"), self.n_qubits, self.obs)
+            states = self.plan.run(angles, "state")
+            if how == "pauli":
+                return N.expval_pauli(states, arg, len(self.obs))
+            return simulation._general_expval(states, self.n_qubits, self.obs)
         return self.plan.run(angles, self.type)
 
     def _measure(self):
         """How the observables are measured (fixed per compiled call): ("z", wires) for plain Z's,
-        ("parity", wire groups) for Z-parities, ("general", None) otherwise."""
+        ("parity", wire groups) for Z-parities, ("pauli", term list) when every observable is a sum of
+        Pauli words (one pass over the stored states), ("general", None) otherwise."""
         m = getattr(self, "_meas", None)
         if m is None:
             masks = [z_parity_mask(o) for o in self.obs]
@@ -170,7 +174,8 @@ class CompiledCall:
             elif self.obs and all(k is not None for k in masks) and len(masks) <= 32:
                 m = ("parity", masks)
             else:
-                m = ("general", None)
+                terms = simulation.pauli_term_list(self.obs, self.n_qubits)
+                m = ("pauli", terms) if terms is not None else ("general", None)
             self._meas = m
         return m
 

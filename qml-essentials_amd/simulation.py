@@ -17,7 +17,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _native as N
-from .operations import _CONJ_NEGATE, Barrier, KrausChannel, Operation, conj_lower, z_parity_mask
+from .operations import (_CONJ_NEGATE, Barrier, KrausChannel, Operation, conj_lower, pauli_terms,
+                         z_parity_mask)
 
 MEAS_TYPES = ("expval", "probs", "state", "density")
 _PLAN_CACHE: "OrderedDict[tuple, N.Plan]" = OrderedDict()
@@ -221,6 +222,9 @@ def _density_expval(rho_vec, n_qubits: int, obs: Sequence[Operation]):
     masks = [z_parity_mask(o) for o in obs]
     if obs and all(m is not None and len(m) == 1 for m in masks):
         return N.density_expval_z(rho_vec, n_qubits, [m[0] for m in masks])
+    terms = pauli_term_list(obs, n_qubits)
+    if terms is not None:  # every observable is a sum of Pauli words: 2^n gathered elements per word
+        return N.density_expval_pauli(rho_vec, n_qubits, terms, len(obs))
     out = torch.empty((B, len(obs)), dtype=torch.float32, device=rho_vec.device)
     diag = None
     for k, (ob, m) in enumerate(zip(obs, masks)):
@@ -401,8 +405,34 @@ def _tape_batch(tape: Sequence[Operation]) -> int:
     return b
 
 
+def pauli_term_list(obs: Sequence[Operation], n_qubits: int):
+    """The observables as ONE term list ``[(coef, x_wire_mask, z_wire_mask, column)]`` for
+    ``N.expval_pauli`` / ``N.density_expval_pauli`` -- Z's and parities are its x = 0 terms -- or None when
+    one of them has no Pauli terms (``operations.pauli_terms``) or the library's argument check refuses the
+    list (its limits on terms, observables and qubits: ``N.pauli_terms_supported``)."""
+    out = []
+    for col, ob in enumerate(obs):
+        terms = pauli_terms(ob)
+        if terms is None:
+            return None
+        out.extend((c, x, z, col) for c, x, z in terms)
+    return out if N.pauli_terms_supported(n_qubits, out) else None
+
+
+def observables_expval(states, n_qubits: int, obs: Sequence[Operation]):
+    """<psi|O|psi> per observable of resident states (complex64 -> float32, complex128 -> float64), for
+    observable lists that are not all Z / Z-parity: sums of Pauli words in one call of the Pauli-word
+    kernels, anything else by the routes that apply the observable to a copy of the states."""
+    terms = pauli_term_list(obs, n_qubits)
+    if terms is not None:
+        return N.expval_pauli(states, terms, len(obs))
+    if states.is_complex() and states.element_size() == 16:
+        return _x64_observables(states, n_qubits, obs, [z_parity_mask(o) for o in obs])
+    return _general_expval(states, n_qubits, obs)
+
+
 def _general_expval(states, n_qubits: int, obs: Sequence[Operation]):
-    """<psi|O|psi> for arbitrary observables, matrix-free: parities natively, anything
+    """<psi|O|psi> for observables without Pauli terms, matrix-free: parities natively, anything
     else as Re<psi|O psi> with O applied by the gate kernels (``simulation.py:263-269``)."""
     torch = N.require_gpu()
     B = states.shape[0]
@@ -507,7 +537,7 @@ def simulate_and_measure(tape: Sequence[Operation], n_qubits: int, type: str,
         elif all(m is not None for m in masks) and len(obs) <= 32:
             res = plan.run_parity(angles, masks)  # Z (x) Z ..: out of the last pass as well
         else:
-            res = _general_expval(plan.run(angles, "state"), n_qubits, obs)
+            res = observables_expval(plan.run(angles, "state"), n_qubits, obs)
     else:
         res = plan.run(angles, type)
     if as_tensor:
@@ -529,7 +559,7 @@ def _simulate_x64(plan: N.Plan, low: "LoweredTape", B: int, n_qubits: int, type:
     masks = [z_parity_mask(o) for o in obs]
     if all(m is not None for m in masks) and len(obs) <= 32:
         return plan.run64(angles, "expval", masks)
-    return _x64_observables(plan.run64(angles, "state"), n_qubits, obs, masks)
+    return observables_expval(plan.run64(angles, "state"), n_qubits, obs)
 
 
 def _x64_observables(states, n_qubits: int, obs, masks):
@@ -579,7 +609,7 @@ def run_expval_table(plan: N.Plan, table: np.ndarray, obs: Sequence[Operation], 
             if parity:
                 out.append(plan.run64(ang, "expval", masks).cpu().numpy())
             else:  # PauliX / Hermitian ...: contracted with the complex128 states, like _simulate_x64
-                out.append(_x64_observables(plan.run64(ang, "state"), n_qubits, list(obs), masks).cpu().numpy())
+                out.append(observables_expval(plan.run64(ang, "state"), n_qubits, list(obs)).cpu().numpy())
         return np.concatenate(out, axis=0)
     chunk = memory.compute_chunk_size(n_qubits, min(max_rows, table.shape[0]),
                                       "expval" if (single_z or parity) else "state", False, len(obs),
@@ -591,6 +621,6 @@ def run_expval_table(plan: N.Plan, table: np.ndarray, obs: Sequence[Operation], 
         elif parity:
             res = plan.run_parity(ang, masks)
         else:
-            res = _general_expval(plan.run(ang, "state"), n_qubits, list(obs))
+            res = observables_expval(plan.run(ang, "state"), n_qubits, list(obs))
         out.append(res.cpu().numpy())
     return np.concatenate(out, axis=0)
