@@ -196,7 +196,12 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * earlier chunk of the same call (all-live plans of two passes, <Z> measurements); stage 0 then reports the
  * bytes per state that run really wrote (its fills and first-tile stores over its states), and the
  * fresh-buffer figure 8 * 2^n before any run and after a run that filled every chunk or failed.  Describe the
- * handle of qmle_plan_executed, after the run. */
+ * handle of qmle_plan_executed, after the run.
+ * The last stage also reports how the handle's last batch run went ("..._last_run"), among them
+ * "chunk_loop_last_run": how that run ordered its chunks -- "one_stream" (one chunk, the whole state in the
+ * LDS, QMLE_NO_CHUNK_OVERLAP=1, or no room for two slots), "staged" (two streams, stage k of a chunk behind
+ * stage k of the chunk before it), "free" (two streams and no order between them: the runs that fill a slot once
+ * per call, see qmle_workspace_bytes), "none" before the first run. */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* counts: [0]=reference gates, [1]=HBM passes, [2]=whole-state-LDS(0/1),
  * [3]=tile qubits T, [4]=floats of per-sample matrices, [5]=direct passes */
@@ -208,7 +213,9 @@ int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);
  * `stream` by an event and join it again before the call returns its last launch: to the caller the call is
  * ordered on `stream` like any other); the figure returned includes the second set of state buffers.  A
  * smaller workspace is legal: the engine splits what it gets in two, or keeps one chunk on `stream` alone.
- * QMLE_NO_CHUNK_OVERLAP=1 (read per call): always the one-stream loop. */
+ * Runs that fill a workspace slot once per call (two tile passes, <Z> out of the second) let the two streams run
+ * free instead: each takes its chunks back to back, and the end of one chunk's measuring pass is covered by the
+ * other stream's.  QMLE_NO_CHUNK_OVERLAP=1 (read per call): always the one-stream loop. */
 size_t qmle_workspace_bytes(const qmle_plan *plan, int batch, int meas_type,
                             int n_obs, int states_in_flight);
 

@@ -393,6 +393,11 @@ class Plan:
         return child
 
     def describe(self) -> dict:
+        """``qmle_plan_describe`` as a dict.  The last stage carries the reports of the handle's last batch run
+        (``measure_tiles_per_workgroup_last_run``, ``measured_from_registers_last_run``,
+        ``wave_private_walk_last_run``, ``staging_dma_last_run``, and ``chunk_loop_last_run``: ``"one_stream"``,
+        ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run):
+        describe ``executed(meas)``, after the run."""
         L = lib()
         need = L.qmle_plan_describe(self._h, None, 0)
         buf = C.create_string_buffer(need + 1)

@@ -684,9 +684,19 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
 // with workspace slot i & 1.  The streams fork from the caller's stream -- what it has queued so far (the matrices,
 // the angle table) comes first -- and join it again when the object goes, on the error returns too.  Without side
 // streams (one slot, or a fork that failed) every chunk runs on the caller's stream in slot 0.
+//
+// Between the two streams, two loop forms (form(), reported as chunk_loop_last_run):
+//   staged  stage k of chunk i + 1 waits, by event, for stage k of chunk i: at most one launch of each stage in flight,
+//           the chunks one stage apart.  Every run whose chunks are filled one by one.
+//   free    no event between the streams: each stream runs its chunks back to back, and the tail of one chunk's
+//           measuring pass -- the last walks draining, the launch of the next kernel -- is covered by the other
+//           stream's pass.  For runs whose slots stay zeroed (slot_stays_zeroed: one fill per slot and call, so in
+//           steady state the staged rule only put one measuring pass behind the other).  What orders such a run: a
+//           slot is one buffer on one stream; the matrix rows, the plan's tables and the observables are read-only;
+//           output rows, partial sums, fold columns and the k_mono_coef rows are per chunk or per slot.
 class ChunkPipeline {
  public:
-  ChunkPipeline(bool two_slots, size_t n_stages, hipStream_t caller_stream) : caller_(caller_stream) {
+  ChunkPipeline(bool two_slots, size_t n_stages, bool free_running, hipStream_t caller_stream) : caller_(caller_stream) {
     side_ = two_slots ? side_streams() : nullptr;
     if (side_ && (hipEventRecord(side_->fork, caller_) != hipSuccess ||
                   hipStreamWaitEvent(side_->s[0], side_->fork, 0) != hipSuccess ||
@@ -694,7 +704,7 @@ class ChunkPipeline {
       (void)hipGetLastError();
       side_ = nullptr;
     }
-    piped_ = side_ && n_stages <= (size_t)kPipeStages;
+    piped_ = side_ && !free_running && n_stages <= (size_t)kPipeStages;
   }
   ChunkPipeline(const ChunkPipeline &) = delete;
   ChunkPipeline &operator=(const ChunkPipeline &) = delete;
@@ -706,8 +716,8 @@ class ChunkPipeline {
   }
   int slot(int chunk) const { return side_ ? chunk & 1 : 0; }
   hipStream_t stream(int chunk) const { return side_ ? side_->s[chunk & 1] : caller_; }
-  // Stage k of chunk i starts behind stage k of chunk i - 1 (the other stream).  The result marks the stage as
-  // queued when it goes out of scope (any exit from the stage's iteration).
+  // Staged form: stage k of chunk i starts behind stage k of chunk i - 1 (the other stream).  The result marks the
+  // stage as queued when it goes out of scope (any exit from the stage's iteration).  Free form: nothing to do.
   struct StageQueued {
     hipEvent_t ev;
     hipStream_t stream;
@@ -717,6 +727,8 @@ class ChunkPipeline {
     if (piped_ && chunk > 0) (void)hipStreamWaitEvent(stream(chunk), side_->stage_done[(chunk - 1) & 1][k], 0);
     return StageQueued{piped_ ? side_->stage_done[chunk & 1][k] : nullptr, stream(chunk)};
   }
+  // how this run orders its chunks (qmle_plan::chunk_loop_last_run)
+  int form() const { return !side_ ? kChunkLoopOneStream : piped_ ? kChunkLoopStaged : kChunkLoopFree; }
 
  private:
   SideStreams *side_;
@@ -762,6 +774,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   // per-sample gate matrices for the whole batch (tiny)
   rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true);
   if (rc != QMLE_OK) return rc;
+  plan->chunk_loop_last_run = kChunkLoopOneStream;
   if (L.in_lds)
     return run_batch_lds(plan, L, d_mats, d_angles, batch, meas_type, obs_masks, n_obs, d_out, ws + L.partial[0],
                          caller_stream);
@@ -773,11 +786,12 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
                            plan->stages.back().kind == ST_TILE;
   const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
   const bool by_position = oc.single_bits || oc.semi_single;
-  ChunkPipeline pipe(L.slots == 2, plan->stages.size(), caller_stream);
+  const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
+  ChunkPipeline pipe(L.slots == 2, plan->stages.size(), /*free_running=*/reuse_zeros, caller_stream);
+  plan->chunk_loop_last_run = pipe.form();
   // Clean slots: slot_fill[k].zeroed_states states of slot k hold zeros outside tile 0 of stage 0.  It lives and dies with this call
   // (the caller owns the workspace between calls, so a slot's first chunk is always filled), and a slot is one
   // buffer on one stream -- ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
-  const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
   FillReuse slot_fill[2];
   uint64_t filled_states = 0;  // states written by fills, all chunks
   bool elided = false;         // a chunk ran without its fill

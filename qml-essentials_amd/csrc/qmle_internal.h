@@ -211,6 +211,10 @@ struct DevicePlan {  // lazily created by the first run on a device
   uint32_t *d_tbl2 = nullptr;
 };
 
+// How a batch run ordered its chunks (ChunkPipeline, qmle_engine.hip; qmle_plan::chunk_loop_last_run)
+enum { kChunkLoopNone = 0, kChunkLoopOneStream, kChunkLoopStaged, kChunkLoopFree };
+constexpr const char *kChunkLoopNames[] = {"none", "one_stream", "staged", "free"};
+
 }  // namespace qmle
 
 struct qmle_plan {
@@ -264,6 +268,9 @@ struct qmle_plan {
   bool measure_regs_last_run = false;
   bool wave_private_last_run = false;     // ... and ran its tile loop without a workgroup barrier (Stage::wave_private)
   bool staging_dma_last_run = false;      // ... and staged its tiles by LDS DMA (Stage::dma_tables)
+  // ... and how the last batch run ordered its chunks (ChunkPipeline::form; a run with one chunk, or with the whole
+  // state in the LDS, is a one-stream run)
+  int chunk_loop_last_run = qmle::kChunkLoopNone;
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)

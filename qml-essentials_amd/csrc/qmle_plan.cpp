@@ -1597,7 +1597,8 @@ std::string describe_plan(const qmle_plan *p) {
       os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run
          << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false")
          << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false")
-         << ",\"staging_dma_last_run\":" << (p->staging_dma_last_run ? "true" : "false");
+         << ",\"staging_dma_last_run\":" << (p->staging_dma_last_run ? "true" : "false")
+         << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->chunk_loop_last_run] << "\"";
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";
