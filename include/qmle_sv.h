@@ -201,8 +201,22 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * "chunk_loop_last_run": how that run ordered its chunks -- "one_stream" (one chunk, the whole state in the
  * LDS, QMLE_NO_CHUNK_OVERLAP=1, or no room for two slots), "staged" (two streams, stage k of a chunk behind
  * stage k of the chunk before it), "free" (two streams and no order between them: the runs that fill a slot once
- * per call, see qmle_workspace_bytes), "none" before the first run. */
+ * per call, see qmle_workspace_bytes), "none" before the first run.
+ * Every tile stage lists "fast_ops", the ops of its fast-kernel stream (the concatenated "fast_groups") as
+ * [dispatch code, float offset of the op's record in the per-sample matrix row], "unit_form_ops", the indices into
+ * that stream of the ops applied in unit-pivot form, and "scale_carriers", the ops that take the product of the
+ * pivots in front of them (see qmle_unit_form_chain).  "mat_floats_old" is the part of the row ("mat_floats") that
+ * holds one plain record per operator, as every other kernel reads it; the records of unit-form ops and carriers
+ * follow it. */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
+/* Host only: the matrix builder's unit-pivot chain for `n` given 2x2 matrices u[i] = {m00, m01, m10, m11} as
+ * (re, im) doubles.  The fast tile kernel applies an eligible gate as U / pivot, a matrix with a literal 1 (48
+ * packed instructions instead of 64), and the product P of a chain's pivots is folded into the chain's last gate,
+ * the carrier.  Members 0 .. n-2 are unit-form ops (diag[i] != 0: a diagonal one; diag may be NULL), member n-1 is
+ * the carrier.  records[i] = the 8 numbers of member i's record: dense {x, y, z, (form, 0)} with form 1 =
+ * [[1, x], [y, z]] (pivot m00, taken when |m00| >= |m01|) and form 2 = [[x, 1], [y, z]] (pivot m01); diagonal
+ * {1, 0, 0, m11 / m00}.  pivots[i] = member i's pivot (re, im); carrier = P u[n-1], plain layout. */
+int qmle_unit_form_chain(const double *u, const int *diag, int n, double *records, double *pivots, double *carrier);
 /* counts: [0]=reference gates, [1]=HBM passes, [2]=whole-state-LDS(0/1),
  * [3]=tile qubits T, [4]=floats of per-sample matrices, [5]=direct passes */
 int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);

@@ -150,6 +150,8 @@ SYMBOLS = [
     ("qmle_plan_expval_child", _VP, [_VP]),
     ("qmle_plan_executed", _VP, [_VP, _I]),
     ("qmle_plan_describe", _I, [_VP, C.c_char_p, _SZ]),
+    ("qmle_unit_form_chain", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("qmle_plan_stats", _I, [_VP, C.POINTER(C.c_int64)]),
     ("qmle_plan_autotune", _I, [_VP, _I, _I, _I, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double)]),

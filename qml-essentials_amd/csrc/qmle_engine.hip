@@ -243,7 +243,7 @@ int qmle_plan_create(const qmle_op *ops, int n_ops, int n_qubits, int n_slots,
     qmle_plan *v = new_plan_like(p, p->ops, flags | QMLE_PLAN_INTERNAL_ZERO_RUN);
     if (v) {
       const bool forced = std::getenv("QMLE_FORCE_CAND") != nullptr;  // (tuning: always run the forced schedule)
-      if (compile_plan(v) == QMLE_OK && v->mat_floats == p->mat_floats && (forced || v->model_cost < p->model_cost - 0.5))
+      if (compile_plan(v) == QMLE_OK && v->mat_floats_old == p->mat_floats_old && (forced || v->model_cost < p->model_cost - 0.5))
         p->zero_variant = v;
       else
         delete v;
@@ -319,6 +319,24 @@ int qmle_plan_destroy(qmle_plan *plan) {
   if (plan->f64_blob) (void)hipFree(plan->f64_blob);
   if (plan->dev.blob) (void)hipFree(plan->dev.blob);
   delete plan;
+  return QMLE_OK;
+}
+
+// the matrix builder's chain walk (unit_chain_step, qmle_matrices.h) on the host, for given 2x2 matrices
+int qmle_unit_form_chain(const double *u, const int *diag, int n, double *records, double *pivots, double *carrier) {
+  if (!u || n < 1 || !carrier || (n > 1 && (!records || !pivots))) return QMLE_ERR_INVALID_ARG;
+  cd P = {1.0, 0.0};
+  for (int i = 0; i < n; ++i) {
+    const double *m = u + 8 * (size_t)i;
+    const M2 U = {{m[0], m[1]}, {m[2], m[3]}, {m[4], m[5]}, {m[6], m[7]}};
+    if (i + 1 == n) {
+      (void)unit_chain_step(U, CM_CARRIER, P, carrier);
+    } else {
+      const cd piv = unit_chain_step(U, diag && diag[i] ? CM_UNIT_DIAG : CM_UNIT_DENSE, P, records + 8 * (size_t)i);
+      pivots[2 * i] = piv.re;
+      pivots[2 * i + 1] = piv.im;
+    }
+  }
   return QMLE_OK;
 }
 
@@ -997,6 +1015,7 @@ static void adopt_schedule(qmle_plan *dst, qmle_plan *src) {
   dst->stages.swap(src->stages);
   dst->cand_ranking.swap(src->cand_ranking);
   std::swap(dst->mat_floats, src->mat_floats);
+  std::swap(dst->mat_floats_old, src->mat_floats_old);
   std::swap(dst->n_groups_needed, src->n_groups_needed);
   std::swap(dst->fold_groups, src->fold_groups);
   std::swap(dst->model_cost, src->model_cost);

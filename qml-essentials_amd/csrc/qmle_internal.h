@@ -71,11 +71,18 @@ struct BuildOp {
 static_assert(sizeof(BuildOp) == 24, "BuildOp layout");
 
 // A matrix = product of build ops [begin,end) in tape order (later gate on the left).
+// dim = kBuildChain: a chain of unit-pivot records (build_matrices_body).  [begin, end) then holds the source gates of
+// the chain's members in stream order, each member closed by a marker (opcode kChainMark, pad = ChainMember,
+// const_off = float offset of the member's record in the matrix row); the last member is the carrier.
 struct BuildGroup {
   uint32_t begin, end;
   uint32_t mat_off;
-  uint32_t dim;  // 2 or 4
+  uint32_t dim;  // 2 or 4; kBuildChain
 };
+constexpr uint32_t kBuildChain = 1;
+constexpr uint16_t kChainMark = 0xffffu;
+enum ChainMember : uint16_t { CM_UNIT_DENSE = 0, CM_UNIT_DIAG = 1, CM_CARRIER = 2 };
+constexpr int kMaxChainUnits = 32;  // unit-form ops per chain: |1 / pivot| <= sqrt 2, so a state is scaled by <= 2^16
 
 // ---- fast tile path (k_tile2) ---------------------------------------------------------------
 // A register-tile group whose LDS addressing is a host-built table: thread t gathers its 16
@@ -92,7 +99,11 @@ enum FastCode : uint8_t {
   FC_CDIAG = 20,    // + 3 * cb + ..
   FC_X = 32,        // + tb                      in-register Pauli-X (pairs swapped)
   FC_CX = 36,       // + 3 * cb + ..             in-register CX
-  FC_COUNT = 48
+  // unit-pivot forms (assign_unit_forms, qmle_plan.cpp): the record holds U / pivot, the pivots of a stage's chain
+  // are multiplied into its carrier gate
+  FC_UDENSE = 48,   // + tb                      [[1, x], [y, z]] or [[x, 1], [y, z]] (the record's form word says which)
+  FC_UDIAG = 52,    // + tb                      diag(1, m11 / m00)
+  FC_COUNT = 56
 };
 struct Group2 {
   uint32_t op_begin;   // first op in qmle_plan::ops2
@@ -175,6 +186,9 @@ struct Stage {
   // dma_tables: what the tables allow; a run also needs an input without known zeros inside the tile.
   bool dma_tables = false;
   uint32_t fast_gtab_dma = 0, dma_delta[4] = {};
+  // report only (describe_plan): indices into the stage's ops2 stream of the ops that run in unit-pivot form and of
+  // the carriers that take their chains' pivots (assign_unit_forms)
+  std::vector<int> unit_form_ops, scale_carriers;
 };
 // A stage's lane offsets as runs: local bits 0 .. top -> global positions, contiguous stretches (off, mask, pos).
 // Returns their number, or -1 when there are more than four (k_tile2 then reads the offsets from its table).
@@ -235,6 +249,8 @@ struct qmle_plan {
   int n_groups_needed = 0;
   std::vector<qmle::Stage> stages;
   uint32_t mat_floats = 0;                // per-sample matrix row length
+  uint32_t mat_floats_old = 0;            // ... of which the plain records, one per lowered operator (a function of the
+                                          // tape and the flags alone); the unit-form records of ops2 follow
   int fold_groups = 0;                    // most gate groups of any Stage::product_ok stage
   double model_cost = 0.0;                // pass-cost model of the chosen schedule (us per state at n = 24 scale)
   int chosen_candidate = -1;              // index of the schedule candidate the model picked (compile_plan)

@@ -12,14 +12,54 @@ namespace {
 struct cd {
   double re, im;
 };
-__device__ __forceinline__ cd cdmul(cd a, cd b) {
+__host__ __device__ __forceinline__ cd cdmul(cd a, cd b) {
   return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re};
 }
 
-__device__ __forceinline__ cd cdadd(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
+__host__ __device__ __forceinline__ cd cdadd(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
+__host__ __device__ __forceinline__ cd cddiv(cd a, cd b) {
+  const double d = b.re * b.re + b.im * b.im;
+  return {(a.re * b.re + a.im * b.im) / d, (a.im * b.re - a.re * b.im) / d};
+}
 struct M2 {
   cd a, b, c, d;  // [[a, b], [c, d]]
 };
+
+// ---------------------------------------------------------------------------
+// unit-pivot form (k_tile2's FC_UDENSE / FC_UDIAG): U = pivot * U' with a literal 1 in U', so that the gate costs 6
+// packed instructions per amplitude pair instead of 8; the pivots of a chain are multiplied into P and handed to the
+// chain's last member, the carrier, which is stored as P U in the plain layout (a scalar commutes with every gate in
+// between).  One member of a chain: writes its 8-float record to `out`, updates P, returns the pivot it divided by.
+//   CM_UNIT_DENSE  pivot = m00 if |m00| >= |m01| (form 1: [[1, x], [y, z]]), else m01 (form 2: [[x, 1], [y, z]]);
+//                  record {x, y, z, (form, 0)} -- the form word is the float 1 or 2.  A unitary 2x2 has
+//                  |m00|^2 + |m01|^2 = 1, so |pivot| >= 1 / sqrt 2 and m00 = 0 (RY(pi)) is form 2
+//   CM_UNIT_DIAG   pivot = m00 (modulus 1): record diag(1, m11 / m00) in the plain layout
+//   CM_CARRIER     record P U in the plain layout; P starts again at 1
+// ---------------------------------------------------------------------------
+template <class OT>
+__host__ __device__ __forceinline__ cd unit_chain_step(const M2 &U, int member, cd &P, OT *out) {
+  if (member == CM_CARRIER) {
+    const cd a = cdmul(P, U.a), b = cdmul(P, U.b), c = cdmul(P, U.c), d = cdmul(P, U.d);
+    out[0] = (OT)a.re; out[1] = (OT)a.im; out[2] = (OT)b.re; out[3] = (OT)b.im;
+    out[4] = (OT)c.re; out[5] = (OT)c.im; out[6] = (OT)d.re; out[7] = (OT)d.im;
+    P = {1.0, 0.0};
+    return {1.0, 0.0};
+  }
+  if (member == CM_UNIT_DIAG) {
+    const cd piv = U.a, w = cddiv(U.d, piv);
+    out[0] = (OT)1; out[1] = (OT)0; out[2] = (OT)0; out[3] = (OT)0;
+    out[4] = (OT)0; out[5] = (OT)0; out[6] = (OT)w.re; out[7] = (OT)w.im;
+    P = cdmul(P, piv);
+    return piv;
+  }
+  const bool form1 = U.a.re * U.a.re + U.a.im * U.a.im >= U.b.re * U.b.re + U.b.im * U.b.im;
+  const cd piv = form1 ? U.a : U.b;
+  const cd x = cddiv(form1 ? U.b : U.a, piv), y = cddiv(U.c, piv), z = cddiv(U.d, piv);
+  out[0] = (OT)x.re; out[1] = (OT)x.im; out[2] = (OT)y.re; out[3] = (OT)y.im;
+  out[4] = (OT)z.re; out[5] = (OT)z.im; out[6] = (OT)(form1 ? 1 : 2); out[7] = (OT)0;
+  P = cdmul(P, piv);
+  return piv;
+}
 // the 2x2 source gates of source_matrix(), entries in registers
 // ANG: anything indexable by slot -- a row of the angle table (`const float *` / `const double *`) or an
 // AngleMapRow that forms the angle from the leaves on the fly (same arithmetic as k_build_angles)
@@ -209,6 +249,31 @@ __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ 
   const BuildGroup grp = groups[g];
   const auto ang = angle_row(angles, b, n_slots);
   const int dim = (int)grp.dim;
+  if (grp.dim == kBuildChain) {
+    // one work item per (sample, chain): the members' fused 2x2 in stream order, each closed by its marker
+    // (the walk is the same for every sample: under GMAJOR a wave diverges on the form of a pivot only)
+    cd P = {1.0, 0.0};
+    M2 M = {{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}};
+    bool first = true;
+    for (uint32_t k = grp.begin; k < grp.end; ++k) {
+      const BuildOp bo = build[k];
+      if (bo.opcode == kChainMark) {
+        (void)unit_chain_step(M, (int)bo.pad, P, mats + (size_t)b * mat_floats + (uint32_t)bo.const_off);
+        first = true;
+        continue;
+      }
+      const M2 S = source_2x2(bo, ang, consts);  // later gate on the left: M <- S M
+      if (first) {
+        M = S;
+        first = false;
+        continue;
+      }
+      const cd a = cdadd(cdmul(S.a, M.a), cdmul(S.b, M.c)), bb = cdadd(cdmul(S.a, M.b), cdmul(S.b, M.d));
+      const cd c = cdadd(cdmul(S.c, M.a), cdmul(S.d, M.c)), d = cdadd(cdmul(S.c, M.b), cdmul(S.d, M.d));
+      M = {a, bb, c, d};
+    }
+    return;
+  }
   if (dim == 2) {
     // 2x2 groups (all but the two-qubit Pauli rotations / SWAP / explicit 4x4): four named
     // entries in registers -- the generic path below indexes its arrays at run time and lives in

@@ -611,6 +611,97 @@ static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured) {
   }
 }
 
+// ---- unit-pivot forms of the fast tile path (FC_UDENSE / FC_UDIAG) ------------------------------
+// A dense 2x2 on 16 amplitudes is 64 packed instructions in k_tile2, a quarter of which multiply by a number that
+// can be factored out: U = pivot * U' with a literal 1 in U' costs 48.  A scalar commutes with every gate, so the
+// pivots of a stage's unit-form ops are multiplied into ONE later gate of the same stage, the carrier (P U, plain
+// form): the stage leaves the state it left before, up to rounding.  Per fast stage, over its ops2 stream in order:
+//   * eligible: an uncontrolled dense or diagonal op whose source gates all come from the fixed / parametrised
+//     unitary gate set (a caller's constant matrix need not be unitary: |pivot| >= 1 / sqrt 2 rests on that; a
+//     controlled gate acts on half the amplitudes, where a factor is not a scalar);
+//   * the last eligible dense op is the carrier, eligible ops in front of it take the unit form, eligible diagonal
+//     ops behind it stay plain (their pivot, a phase, would have no carrier);
+//   * a chain holds at most kMaxChainUnits unit-form ops: behind that the next eligible dense op is a carrier too.
+// The records of unit-form ops and carriers are APPENDED to the matrix row (ops2[].mat_off; one build item per chain,
+// BuildGroup::dim = kBuildChain); the plain records stay where every other reader finds them -- k_tile, k_direct_1q,
+// k_reg_measure*, the product kernels, the adjoint sweep and the complex128 engine read dev_ops / lowered.
+static void assign_unit_forms(qmle_plan *p) {
+  p->mat_floats_old = p->mat_floats;
+  std::vector<int> group_at(p->mat_floats / 8 + 1, -1);  // plain record -> its 2x2 build group
+  for (size_t g = 0; g < p->groups.size(); ++g)
+    if (p->groups[g].dim == 2) group_at[p->groups[g].mat_off / 8] = (int)g;
+  auto eligible = [&](const LoweredOp &o) {
+    if (o.kind != LK_1Q || o.nc != 0) return false;
+    const bool dense = o.pad < FC_CDENSE, diag = o.pad >= FC_DIAG && o.pad < FC_CDIAG;
+    if (!dense && !diag) return false;
+    const int g = o.mat_off / 8 < group_at.size() ? group_at[o.mat_off / 8] : -1;
+    if (g < 0) return false;
+    for (uint32_t k = p->groups[g].begin; k < p->groups[g].end; ++k)
+      switch (p->build_ops[k].opcode) {
+        case QMLE_OP_ID: case QMLE_OP_X: case QMLE_OP_Y: case QMLE_OP_Z: case QMLE_OP_H: case QMLE_OP_S:
+        case QMLE_OP_RX: case QMLE_OP_RY: case QMLE_OP_RZ: case QMLE_OP_ROT: break;
+        default: return false;
+      }
+    return true;
+  };
+  for (Stage &st : p->stages) {
+    st.unit_form_ops.clear();
+    st.scale_carriers.clear();
+    if (st.kind != ST_TILE || !st.fast_ok || st.fast_end <= st.fast_begin) continue;
+    const uint32_t ob = p->groups2[st.fast_begin].op_begin;
+    uint32_t n_ops = 0;
+    for (int g = st.fast_begin; g < st.fast_end; ++g) n_ops += p->groups2[g].n_ops;
+    int last_dense = -1, n_elig = 0;
+    std::vector<char> elig(n_ops, 0);
+    for (uint32_t i = 0; i < n_ops; ++i) {
+      elig[i] = eligible(p->ops2[ob + i]) ? 1 : 0;
+      if (elig[i] && p->ops2[ob + i].pad < FC_CDENSE) last_dense = (int)i;
+    }
+    for (int i = 0; i <= last_dense; ++i) n_elig += elig[i];
+    if (n_elig < 2) continue;
+    std::vector<int> chain;  // unit-form members of the open chain (stream indices)
+    auto close_chain = [&](int carrier) {
+      if (chain.empty()) return;  // (nothing to carry: the op stays as it is)
+      BuildGroup bg{(uint32_t)p->build_ops.size(), 0, p->mat_floats, kBuildChain};
+      chain.push_back(carrier);
+      for (size_t m = 0; m < chain.size(); ++m) {
+        LoweredOp &o = p->ops2[ob + chain[m]];
+        const BuildGroup src = p->groups[group_at[o.mat_off / 8]];
+        for (uint32_t k = src.begin; k < src.end; ++k) {
+          const BuildOp b = p->build_ops[k];
+          p->build_ops.push_back(b);
+        }
+        const bool is_carrier = m + 1 == chain.size(), diag = o.pad >= FC_DIAG;
+        BuildOp mark{};
+        mark.opcode = kChainMark;
+        mark.pad = is_carrier ? CM_CARRIER : diag ? CM_UNIT_DIAG : CM_UNIT_DENSE;
+        mark.slot[0] = mark.slot[1] = mark.slot[2] = -1;
+        mark.const_off = (int32_t)p->mat_floats;
+        p->build_ops.push_back(mark);
+        o.mat_off = p->mat_floats;
+        p->mat_floats += 8;
+        if (is_carrier) {
+          st.scale_carriers.push_back(chain[m]);
+        } else {
+          o.pad = (uint8_t)((diag ? FC_UDIAG : FC_UDENSE) + o.t0);
+          st.unit_form_ops.push_back(chain[m]);
+        }
+      }
+      bg.end = (uint32_t)p->build_ops.size();
+      p->groups.push_back(bg);
+      chain.clear();
+    };
+    for (int i = 0; i <= last_dense; ++i) {
+      if (!elig[i]) continue;
+      const bool dense = p->ops2[ob + i].pad < FC_CDENSE;
+      if (i == last_dense) close_chain(i);
+      else if ((int)chain.size() < kMaxChainUnits) chain.push_back(i);
+      else if (dense) close_chain(i);
+      // (else: a diagonal op behind a full chain stays plain)
+    }
+  }
+}
+
 int stage_lane_runs(const Stage &st, int top, uint32_t off[4], uint32_t mask[4], uint32_t pos[4]) {
   int r = 0;
   for (int j = 0; j <= top && r <= 4;) {
@@ -1338,6 +1429,7 @@ int compile_plan(qmle_plan *p) {
     p->chosen_candidate = best;
   }
   p->model_cost = cost();
+  assign_unit_forms(p);
   // ---- matrices no forward kernel reads --------------------------------------------------------
   // An X / CX inside a register-tile group is a swap of amplitudes (reg_dispatch<2>, f_x / f_cx) or a
   // change of the LDS layout map (build_fast_groups); its 2x2 matrix is never read by a tile pass.  The
@@ -1501,7 +1593,7 @@ std::string describe_plan(const qmle_plan *p) {
      << ",\"model_cost\":" << p->model_cost << ",\"candidate\":" << p->chosen_candidate
      << ",\"autotuned\":" << (p->autotuned ? "true" : "false")
      << ",\"zero_run\":" << ((p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) ? "true" : "false") << ",\"tile_bits\":" << p->tile_T << ",\"low_bits\":" << p->tile_L
-     << ",\"mat_floats\":" << p->mat_floats
+     << ",\"mat_floats\":" << p->mat_floats << ",\"mat_floats_old\":" << p->mat_floats_old
      << ",\"build_groups\":" << p->groups.size() << ",\"build_groups_needed\":" << p->n_groups_needed
      << ",\"algo_bytes_per_state\":" << p->algo_bytes_per_state
      << ",\"flops_per_state\":" << plan_flops_per_state(p) << ",\"stages\":[";
@@ -1591,6 +1683,23 @@ std::string describe_plan(const qmle_plan *p) {
       os << "],\"measure_after\":[";
       for (size_t i = 0; i + 1 < st.zreg_after.size(); i += 2)
         os << (i ? "," : "") << "[" << (int)st.zreg_after[i] << "," << (int)st.zreg_after[i + 1] << "]";
+      os << "]";
+    }
+    if (st.kind == ST_TILE) {
+      // ops of the stage's fast stream (concatenated fast_groups) that run in unit-pivot form, and the carriers that
+      // take their chains' pivots (assign_unit_forms); fast_ops: each op's dispatch code and matrix-row offset
+      os << ",\"unit_form_ops\":[";
+      for (size_t i = 0; i < st.unit_form_ops.size(); ++i) os << (i ? "," : "") << st.unit_form_ops[i];
+      os << "],\"scale_carriers\":[";
+      for (size_t i = 0; i < st.scale_carriers.size(); ++i) os << (i ? "," : "") << st.scale_carriers[i];
+      os << "],\"fast_ops\":[";
+      if (st.fast_ok && st.fast_end > st.fast_begin) {
+        uint32_t k = p->groups2[st.fast_begin].op_begin;
+        bool any = false;
+        for (int g = st.fast_begin; g < st.fast_end; ++g)
+          for (int j = 0; j < (int)p->groups2[g].n_ops; ++j, ++k, any = true)
+            os << (any ? "," : "") << "[" << (int)p->ops2[k].pad << "," << p->ops2[k].mat_off << "]";
+      }
       os << "]";
     }
     if (s + 1 == p->stages.size())

@@ -189,6 +189,26 @@ __global__ void k_tile(const TileArgs a) {
       "v_pk_fma_f32 %3, %11, %3, %7 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"         \
       : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)       \
       : "s"(m00), "s"(m01), "s"(m10), "s"(m11))
+// The same for a matrix with a literal 1 (unit-pivot form, FC_UDENSE): b0 = u0 + x u1, b1 = y a0 + z a1, where
+// (u0, u1) = (a0, a1) for [[1, x], [y, z]] and (a1, a0) for [[x, 1], [y, z]] (U0 / U1: operand numbers).  6 packed
+// instructions per pair, 12 here, in 4 chains -- two of 4 (b1) and two of 2 (b0) -- interleaved so that an instruction
+// is >= 3 behind the one it depends on; b0 is written once b1's chain has read a0, and reads a1 before b1 lands there.
+#define QMLE_UPAIR2(a0, a1, a2, a3, U0, U1, V0, V1)                                              \
+  asm volatile(                                                                                  \
+      "v_pk_mul_f32 %5, %9, %0 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_mul_f32 %7, %9, %2 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_fma_f32 %4, %8, %" #U1 ", %" #U0 " op_sel_hi:[0,1,1]\n\t"                            \
+      "v_pk_fma_f32 %5, %9, %0, %5 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %7, %9, %2, %7 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %6, %8, %" #V1 ", %" #V0 " op_sel_hi:[0,1,1]\n\t"                            \
+      "v_pk_fma_f32 %5, %10, %1, %5 op_sel_hi:[0,1,1]\n\t"                                       \
+      "v_pk_fma_f32 %7, %10, %3, %7 op_sel_hi:[0,1,1]\n\t"                                       \
+      "v_pk_fma_f32 %0, %8, %" #U1 ", %4 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"    \
+      "v_pk_fma_f32 %1, %10, %1, %5 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"         \
+      "v_pk_fma_f32 %2, %8, %" #V1 ", %6 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"    \
+      "v_pk_fma_f32 %3, %10, %3, %7 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"         \
+      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)       \
+      : "s"(ux), "s"(uy), "s"(uz))
 // four amplitudes times the same complex number
 #define QMLE_CMUL4(a0, a1, a2, a3, m)                                                            \
   asm volatile(                                                                                  \
@@ -276,6 +296,40 @@ __device__ __forceinline__ void f_diag(A16 &a, const Mat2S &M) {
   QMLE_CMUL4(at<QMLE_I(4) | S>(a), at<QMLE_I(5) | S>(a), at<QMLE_I(6) | S>(a), at<QMLE_I(7) | S>(a), m11);
 #undef QMLE_I
 }
+// unit-pivot forms (qmle_matrices.h, unit_chain_step): the record {x, y, z, form} sits where a plain matrix has
+// {m00, m01, m10, m11}; ANTI: form 2, the 1 stands in place of m01
+template <int TB, bool ANTI>
+__device__ __forceinline__ void f_udense(A16 &a, const Mat2S &M) {
+  const u64 ux = M.m00, uy = M.m01, uz = M.m10;
+  u64 t0, t1, t2, t3;
+  constexpr int S = 1 << TB;
+#define QMLE_P(q) at<pair_idx<TB>(q)>(a), at<pair_idx<TB>(q) | S>(a)
+#define QMLE_UPAIR2X(...) QMLE_UPAIR2(__VA_ARGS__)
+  if constexpr (ANTI) {
+    QMLE_UPAIR2X(QMLE_P(0), QMLE_P(1), 1, 0, 3, 2);
+    QMLE_UPAIR2X(QMLE_P(2), QMLE_P(3), 1, 0, 3, 2);
+    QMLE_UPAIR2X(QMLE_P(4), QMLE_P(5), 1, 0, 3, 2);
+    QMLE_UPAIR2X(QMLE_P(6), QMLE_P(7), 1, 0, 3, 2);
+  } else {
+    QMLE_UPAIR2X(QMLE_P(0), QMLE_P(1), 0, 1, 2, 3);
+    QMLE_UPAIR2X(QMLE_P(2), QMLE_P(3), 0, 1, 2, 3);
+    QMLE_UPAIR2X(QMLE_P(4), QMLE_P(5), 0, 1, 2, 3);
+    QMLE_UPAIR2X(QMLE_P(6), QMLE_P(7), 0, 1, 2, 3);
+  }
+#undef QMLE_UPAIR2X
+#undef QMLE_P
+}
+// diag(1, w): the target = 1 half only (the record is that matrix in the plain layout)
+template <int TB>
+__device__ __forceinline__ void f_udiag(A16 &a, const Mat2S &M) {
+  const u64 m11 = M.m11;
+  u64 t0, t1, t2, t3;
+  constexpr int S = 1 << TB;
+#define QMLE_I(q) pair_idx<TB>(q)
+  QMLE_CMUL4(at<QMLE_I(0) | S>(a), at<QMLE_I(1) | S>(a), at<QMLE_I(2) | S>(a), at<QMLE_I(3) | S>(a), m11);
+  QMLE_CMUL4(at<QMLE_I(4) | S>(a), at<QMLE_I(5) | S>(a), at<QMLE_I(6) | S>(a), at<QMLE_I(7) | S>(a), m11);
+#undef QMLE_I
+}
 template <int CB, int TB>
 __device__ __forceinline__ void f_cdiag(A16 &a, const Mat2S &M) {
   const u64 m00 = M.m00, m11 = M.m11;
@@ -322,6 +376,19 @@ __device__ __forceinline__ void fast_dispatch(A16 &a, int code, const Mat2S &M) 
   case base + 10: F<3, 1>(__VA_ARGS__); break; case base + 11: F<3, 2>(__VA_ARGS__); break;
   // (the uncontrolled dense gate is what deep circuits are made of: two scalar branches to reach
   // it instead of the six of a balanced tree over all 48 codes)
+  // (and most of those run in unit-pivot form: reached first; the form word -- the float 1 or 2 -- came into SGPRs
+  // with the record, and the record is per state, so it is wave-uniform: one scalar compare and branch)
+  if (code >= FC_UDENSE && code < FC_UDIAG) {
+    const bool anti = (uint32_t)M.m11 == 0x40000000u;
+    if (code < FC_UDENSE + 2) {
+      if (code == FC_UDENSE) { if (anti) f_udense<0, true>(a, M); else f_udense<0, false>(a, M); }
+      else { if (anti) f_udense<1, true>(a, M); else f_udense<1, false>(a, M); }
+    } else {
+      if (code == FC_UDENSE + 2) { if (anti) f_udense<2, true>(a, M); else f_udense<2, false>(a, M); }
+      else { if (anti) f_udense<3, true>(a, M); else f_udense<3, false>(a, M); }
+    }
+    return;
+  }
   if (code < FC_CDENSE) {
     if (code < 2) { if (code == 0) f_dense<0>(a, M); else f_dense<1>(a, M); }
     else { if (code == 2) f_dense<2>(a, M); else f_dense<3>(a, M); }
@@ -334,6 +401,10 @@ __device__ __forceinline__ void fast_dispatch(A16 &a, int code, const Mat2S &M) 
     case FC_DIAG + 2: f_diag<2>(a, M); break;
     case FC_DIAG + 3: f_diag<3>(a, M); break;
     QMLE_C12(f_cdiag, FC_CDIAG, a, M)
+    case FC_UDIAG + 0: f_udiag<0>(a, M); break;
+    case FC_UDIAG + 1: f_udiag<1>(a, M); break;
+    case FC_UDIAG + 2: f_udiag<2>(a, M); break;
+    case FC_UDIAG + 3: f_udiag<3>(a, M); break;
     case FC_X + 0: f_x<0>(a); break;
     case FC_X + 1: f_x<1>(a); break;
     case FC_X + 2: f_x<2>(a); break;
