@@ -391,6 +391,31 @@ size_t qmle_expval_pauli_workspace_bytes_f64(int n_qubits, int batch, int n_term
 /* host only, like qmle_meyer_wallach_reads: how many times the call streams the state from HBM (or the
  * negative status the call itself would return for these terms) */
 int qmle_expval_pauli_reads(int n_qubits, const qmle_pauli_term *terms, int n_terms, int f64);
+/* Applying a weighted sum of words to resident states -- lambda = H psi, the seed of the adjoint sweep for any
+ * observable list that qmle_expval_pauli measures:
+ *   d_out[b] = (sum_t d_weights[b][terms[t].obs] * terms[t].coef * P_t) d_states[b],
+ *   (P psi)[i] = i^ny * (-1)^popcount((i ^ x) & z) * psi[i ^ x],  ny = popcount(x & z)  (x, z as bit positions).
+ * d_weights [batch][n_obs] float32 (float64 for _f64) on the DEVICE, d_out complex64 (complex128) [batch][2^n];
+ * `terms` as above (HOST array, 1..65536 entries, n_obs 1..4096, n_qubits 1..30), any batch (cut into launches of at
+ * most 65535 states inside).  Terms with equal (x, z) are merged into unique words; a small kernel adds the
+ * per-sample coefficient of every word in fp64 (stored in the precision of the states); a word whose terms cancel
+ * and a column without a term contribute zero.  The words go through the planner of qmle_expval_pauli: a list
+ * that is measured in one pass is applied in one pass (one read of psi, one write of lambda), every further pass
+ * and every streamed x mask reads psi once more and reads and rewrites lambda.  No atomics: the same bits from
+ * call to call.  The word and coefficient tables live in the workspace (about terms * (48 + 4 or 8 * states of a launch)
+ * bytes, see the query).  The argument checks and statuses of qmle_expval_pauli, before any device work; in
+ * addition d_out == d_states is QMLE_ERR_INVALID_ARG (partners are read after neighbours are written). */
+int qmle_apply_pauli_sum(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms, int n_terms,
+                         int n_obs, const float *d_weights, void *d_out, void *d_ws, size_t ws_bytes,
+                         qmle_stream stream);
+int qmle_apply_pauli_sum_f64(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms,
+                             int n_terms, int n_obs, const double *d_weights, void *d_out, void *d_ws,
+                             size_t ws_bytes, qmle_stream stream);
+size_t qmle_apply_pauli_sum_workspace_bytes(int n_qubits, int batch, int n_terms, int n_obs);
+size_t qmle_apply_pauli_sum_workspace_bytes_f64(int n_qubits, int batch, int n_terms, int n_obs);
+/* host only: reads of the state per call -- passes + 2 per streamed x mask, counted on the merged words (or the
+ * negative status the call itself would return for these terms) */
+int qmle_apply_pauli_sum_reads(int n_qubits, const qmle_pauli_term *terms, int n_terms, int f64);
 /* Tr(P rho) on vec(rho) (2n-wire register, ket wires first, complex64); terms name the n system wires.
  * d_out float32 [batch][n_obs]; the same argument checks, 2 * n_qubits <= QMLE_MAX_QUBITS. */
 int qmle_density_expval_pauli(const void *d_rho, int n_qubits, int batch, const qmle_pauli_term *terms,
@@ -488,6 +513,28 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
                               int n_grad_slots, void *d_workspace, size_t workspace_bytes,
                               qmle_stream stream);
 size_t qmle_adjoint_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch);
+
+/* The same sweeps for observables that are sums of Pauli words (X / Y / Hermitian observables, products, and any
+ * number of Z parities as x = 0 words):  C = sum_b sum_o d_weights[b][o] <H_o>(b),  H_o = sum of the `obs_terms`
+ * with obs == o.  Only the seed differs: lambda = (sum_t w[b][obs_t] coef_t P_t) psi, by the kernels of
+ * qmle_apply_pauli_sum (inside the single launch when the whole sweep runs in LDS).  `obs_terms` is a HOST array
+ * with the limits and the argument checks of qmle_apply_pauli_sum (checked first, before any device work; a
+ * workspace smaller than the query's answer is QMLE_ERR_INVALID_ARG); everything else, the batch limits
+ * included, as for the function each one extends. */
+int qmle_adjoint_gradient_pauli(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
+                                const float *d_angles_rev, int batch, const float *d_weights,
+                                const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                                const qmle_adjoint_term *terms, int n_terms, float *d_grad,
+                                int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_pauli_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                          int n_obs_terms, int n_obs);
+int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
+                                    const double *d_angles_rev, int batch, const double *d_weights,
+                                    const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                                    const qmle_adjoint_term *terms, int n_terms, double *d_grad,
+                                    int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                              int n_obs_terms, int n_obs);
 
 /* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
  * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:

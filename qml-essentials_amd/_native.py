@@ -183,6 +183,11 @@ SYMBOLS = [
     ("qmle_expval_pauli_workspace_bytes", _SZ, [_I, _I, _I, _I]),
     ("qmle_expval_pauli_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
     ("qmle_expval_pauli_reads", _I, [_I, C.POINTER(QmlePauliTerm), _I, _I]),
+    ("qmle_apply_pauli_sum", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    ("qmle_apply_pauli_sum_f64", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP, _VP, _SZ, _VP]),
+    ("qmle_apply_pauli_sum_workspace_bytes", _SZ, [_I, _I, _I, _I]),
+    ("qmle_apply_pauli_sum_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
+    ("qmle_apply_pauli_sum_reads", _I, [_I, C.POINTER(QmlePauliTerm), _I, _I]),
     ("qmle_density_expval_pauli", _I, [_VP, _I, _I, C.POINTER(QmlePauliTerm), _I, _I, _VP, _VP]),
     ("qmle_meyer_wallach", _I, [_VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     ("qmle_meyer_wallach_workspace_bytes", _SZ, [_I, _I]),
@@ -202,6 +207,12 @@ SYMBOLS = [
     ("qmle_adjoint_gradient_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), _I, _VP, _I,
                                        _VP, _I, _VP, _SZ, _VP]),
     ("qmle_adjoint_workspace_bytes_f64", _SZ, [_VP, _VP, _I]),
+    ("qmle_adjoint_gradient_pauli", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(QmlePauliTerm), _I, _I, _VP, _I,
+                                         _VP, _I, _VP, _SZ, _VP]),
+    ("qmle_adjoint_pauli_workspace_bytes", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_gradient_pauli_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(QmlePauliTerm), _I, _I, _VP,
+                                             _I, _VP, _I, _VP, _SZ, _VP]),
+    ("qmle_adjoint_pauli_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I]),
     ("qmle_sample_counts", _I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _SZ,
                                 _VP]),
     ("qmle_sample_workspace_bytes", _SZ, [_I, _I]),
@@ -946,6 +957,49 @@ def pauli_reads(n_qubits: int, terms, f64: bool = False) -> int:
     return r
 
 
+def apply_pauli_sum(states, terms, weights):
+    """``out[b] = (sum_t weights[b, o_t] * coef_t * P_t) states[b]`` over the ``terms`` ``(coef, x_wire_mask,
+    z_wire_mask, o)`` -- H psi for a weighted sum of observables, the seed of the adjoint sweep.  complex64 states
+    and float32 weights (``qmle_apply_pauli_sum``) or complex128 and float64 (``qmle_apply_pauli_sum_f64``), chosen
+    by the states' dtype; ``weights`` ``[B, n_obs]``; any batch size; owns its workspace.  Returns a new tensor."""
+    torch = require_gpu()
+    if states.dtype not in (torch.complex64, torch.complex128) or not states.is_cuda:
+        raise ValueError("states must be a complex64 / complex128 CUDA tensor [B, 2^n]")
+    states = states.contiguous()
+    if states.dim() == 1:
+        states = states.unsqueeze(0)
+    B, D = int(states.shape[0]), int(states.shape[1])
+    n = D.bit_length() - 1
+    if 1 << n != D:
+        raise ValueError(f"state length {D} is not a power of two")
+    f64 = states.dtype == torch.complex128
+    weights = torch.as_tensor(weights, dtype=torch.float64 if f64 else torch.float32, device=states.device).contiguous()
+    if weights.dim() != 2 or weights.shape[0] != B:
+        raise ValueError(f"weights must be [{B}, n_obs], got {tuple(weights.shape)}")
+    n_obs = int(weights.shape[1])
+    out = torch.empty_like(states)
+    if B == 0:
+        return out
+    if not terms or n_obs == 0:
+        return out.zero_()
+    fn, wsq = ((lib().qmle_apply_pauli_sum_f64, lib().qmle_apply_pauli_sum_workspace_bytes_f64) if f64
+               else (lib().qmle_apply_pauli_sum, lib().qmle_apply_pauli_sum_workspace_bytes))
+    arr = pauli_term_array(terms)
+    wsb = int(wsq(n, B, len(terms), n_obs))
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=states.device)
+    check(fn(C.c_void_p(states.data_ptr()), n, B, arr, len(terms), n_obs, C.c_void_p(weights.data_ptr()),
+             C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), wsb, _stream_ptr()),
+          "qmle_apply_pauli_sum_f64" if f64 else "qmle_apply_pauli_sum")
+    return out
+
+
+def apply_pauli_reads(n_qubits: int, terms, f64: bool = False) -> int:
+    """HBM reads of the state per ``apply_pauli_sum`` call with these terms (host only)."""
+    r = int(lib().qmle_apply_pauli_sum_reads(int(n_qubits), pauli_term_array(terms), len(terms), int(f64)))
+    check(min(r, 0), "qmle_apply_pauli_sum_reads")
+    return r
+
+
 def density_expval_pauli(rho_vec, n_qubits: int, terms, n_obs: int):
     """``Tr(P rho)``-weighted sums per observable from vec(rho) ``[B, 4^n]`` complex64 -> float32
     ``[B, n_obs]``; ``terms`` as for :func:`expval_pauli`."""
@@ -1084,19 +1138,57 @@ class AdjointTerm(C.Structure):
                 ("marks_off", C.c_int32)]
 
 
+def _adjoint_term_array(terms):
+    arr = (AdjointTerm * max(1, len(terms)))()
+    for i, t in enumerate(terms):
+        (arr[i].out_slot, arr[i].x_wires, arr[i].z_wires, arr[i].proj_wires, arr[i].n_y,
+         arr[i].coef, arr[i].marks_off) = t
+    return arr
+
+
+def _adjoint_gradient_pauli(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights, obs_terms, terms,
+                            n_grad_slots: int):
+    """The term-list form of :func:`adjoint_gradient` (rows already cut to the engine's limit)."""
+    torch = require_gpu()
+    f64 = weights.dtype == torch.float64
+    B, n_obs = int(weights.shape[0]), int(weights.shape[1])
+    oarr, arr = pauli_term_array(obs_terms), _adjoint_term_array(terms)
+    fn, wsq, what = ((lib().qmle_adjoint_gradient_pauli_f64, lib().qmle_adjoint_pauli_workspace_bytes_f64,
+                      "qmle_adjoint_gradient_pauli_f64") if f64
+                     else (lib().qmle_adjoint_gradient_pauli, lib().qmle_adjoint_pauli_workspace_bytes,
+                           "qmle_adjoint_gradient_pauli"))
+    dev = weights.device
+    out = torch.empty((B, n_grad_slots), dtype=torch.float64 if f64 else torch.float32, device=dev)
+    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, len(obs_terms), n_obs))), dtype=torch.uint8, device=dev)
+    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
+             C.c_void_p(weights.data_ptr()), oarr, len(obs_terms), n_obs, arr, len(terms),
+             C.c_void_p(out.data_ptr()), int(n_grad_slots), C.c_void_p(ws.data_ptr()),
+             C.c_size_t(ws.numel()), _stream_ptr()), what)
+    return out
+
+
 @_row_chunked(2, 3, 4, max_rows=32767)  # (psi and lambda of a sample share a launch: 2 B <= 65535)
 def adjoint_gradient(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
-                     wire_groups: Sequence[Sequence[int]], terms, n_grad_slots: int):
-    """One backward sweep: d/d(angle) of sum_k weights[b, k] <Z..Z>_k -> float32 [B, n_grad_slots]
+                     wire_groups: Optional[Sequence[Sequence[int]]], terms, n_grad_slots: int, obs_terms=None):
+    """One backward sweep: d/d(angle) of sum_k weights[b, k] <O_k> -> float32 [B, n_grad_slots]
     (float64 tensors in: the complex128 sweep, ``qmle_adjoint_gradient_f64``, float64 out).
+    The observables are either Z / Z-parities, ``wire_groups`` (at most 32), or -- ``wire_groups`` None --
+    the term list ``obs_terms`` ``[(coef, x_wire_mask, z_wire_mask, k)]`` of ``simulation.pauli_term_list``
+    (``qmle_adjoint_gradient_pauli`` / ``_f64``; the columns are those of ``weights``).
     ``terms``: one ``(out_slot, x_wires, z_wires, proj_wires, n_y, coef, marks_off)`` per op of
     ``rev`` (the reversed, daggered NO_FUSION plan)."""
     torch = require_gpu()
     f64 = weights.dtype == torch.float64
     if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
         raise ValueError("the complex128 sweep takes float64 angle tables")
+    if (wire_groups is None) == (obs_terms is None):
+        raise ValueError("pass either wire_groups or obs_terms")
+    if weights.dim() != 2:
+        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
+    if wire_groups is None:
+        return _adjoint_gradient_pauli(fwd, rev, angles_fwd, angles_rev, weights, obs_terms, terms, n_grad_slots)
     B, n_obs = int(weights.shape[0]), len(wire_groups)
-    if weights.dim() != 2 or weights.shape[1] != n_obs:
+    if weights.shape[1] != n_obs:
         raise ValueError(f"weights must be [B, {n_obs}], got {tuple(weights.shape)}")
     masks = (C.c_uint32 * max(1, n_obs))()
     for k, grp in enumerate(wire_groups):
@@ -1106,10 +1198,7 @@ def adjoint_gradient(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
                 raise ValueError(f"wire {wq} out of range for {fwd.n_qubits} qubits")
             m |= 1 << int(wq)
         masks[k] = m
-    arr = (AdjointTerm * max(1, len(terms)))()
-    for i, t in enumerate(terms):
-        (arr[i].out_slot, arr[i].x_wires, arr[i].z_wires, arr[i].proj_wires, arr[i].n_y,
-         arr[i].coef, arr[i].marks_off) = t
+    arr = _adjoint_term_array(terms)
     dev = weights.device
     if f64:
         out = torch.empty((B, n_grad_slots), dtype=torch.float64, device=dev)

@@ -1,5 +1,6 @@
-"""Adjoint differentiation: the gradient of a weighted sum of Z / Z-parity expectation values
-with respect to EVERY gate angle in one backward sweep (``qmle_adjoint_gradient``).
+"""Adjoint differentiation: the gradient of a weighted sum of expectation values -- Z / Z-parities
+(``qmle_adjoint_gradient``) or any observables that are sums of Pauli words, X / Y / Hermitian ones included
+(``qmle_adjoint_gradient_pauli``) -- with respect to EVERY gate angle in one backward sweep.
 
 What ``jax.grad`` through ``Script.execute`` gives the reference (``tests/test_jaqsi.py:131-141``,
 ``tests/test_model.py:1097-1145``, ``docs/training.md``).  Cost: one forward simulation, then
@@ -122,26 +123,31 @@ REV_FLAGS_FUSED = (N.PLAN_NO_MERGE | N.PLAN_FORCE_GLOBAL | N.PLAN_NO_ABSORB
                    | N.plan_flags(tile_bits=12, low_bits=4))
 
 
-def run_sweep(fwd_plan, rev: LoweredTape, a_f, a_r, w, obs_groups, terms, n_grad_slots):
+def run_sweep(fwd_plan, rev: LoweredTape, a_f, a_r, w, obs_groups, terms, n_grad_slots, obs_terms=None):
     """The backward sweep with fused tile passes where the engine supports the tape (1-qubit and
     controlled 1-qubit gates), else with one streaming pass per gate.  float64 tables: the
-    complex128 sweep (one streaming launch per operator, like the complex128 forward engine)."""
+    complex128 sweep (one streaming launch per operator, like the complex128 forward engine).
+    The observables: Z-parity wire groups ``obs_groups``, or (``obs_groups`` None) the Pauli term list
+    ``obs_terms`` -- the same routes, another seed."""
     if w.dtype == N.require_gpu().float64:
-        return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS), a_f, a_r, w, obs_groups, terms, n_grad_slots)
+        return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS), a_f, a_r, w, obs_groups, terms, n_grad_slots,
+                                  obs_terms=obs_terms)
     try:
         return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS_FUSED), a_f, a_r, w, obs_groups,
-                                  terms, n_grad_slots)
+                                  terms, n_grad_slots, obs_terms=obs_terms)
     except N.Unsupported:
         return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS), a_f, a_r, w, obs_groups,
-                                  terms, n_grad_slots)
+                                  terms, n_grad_slots, obs_terms=obs_terms)
 
 
 _REV_CACHE: "OrderedDict[tuple, tuple]" = OrderedDict()
 
 
 def adjoint_slot_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_groups,
-                          weights: np.ndarray, want: Sequence[bool], x64: bool = False) -> np.ndarray:
-    """d/d(angle slot) of sum_k weights[b, k] <Z..Z>_k for every forward slot -> [B, n_slots]
+                          weights: np.ndarray, want: Sequence[bool], x64: bool = False,
+                          obs_terms=None) -> np.ndarray:
+    """d/d(angle slot) of sum_k weights[b, k] <O_k> for every forward slot -> [B, n_slots]; the observables are
+    the Z / Z-parity wire groups ``obs_groups`` or, with ``obs_groups`` None, the Pauli term list ``obs_terms``
     (columns of slots that are not wanted stay zero; ``weights`` of shape [K * B, n_obs] -- K cotangents per
     sample, sample-minor -- give [K * B, n_slots] from one sweep over K * B states).  The reversed tape depends only on the
     STRUCTURE of the forward tape (its angles are the negated forward columns), so it is built
@@ -172,4 +178,4 @@ def adjoint_slot_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_group
         a_r = torch.zeros((batch, 1), dtype=ft, device=a_f.device)
     w = torch.from_numpy(np.ascontiguousarray(weights, dtype=fn)).cuda()
     return run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed,
-                     max(1, low.n_slots)).cpu().numpy()[:, : low.n_slots]
+                     max(1, low.n_slots), obs_terms=obs_terms).cpu().numpy()[:, : low.n_slots]

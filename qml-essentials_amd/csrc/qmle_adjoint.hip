@@ -20,8 +20,9 @@ namespace {
 
 // ---- whole-circuit adjoint in LDS (n <= 13) ----------------------------------------------
 // One workgroup per sample keeps psi AND lambda in LDS: forward circuit (fused gate groups),
-// lambda = (sum_k w_k Z_k) psi, then for every gate of the reversed, daggered tape the
-// generator overlap and the inverse gate on both vectors.  No HBM traffic beyond the angle
+// lambda = (sum_k w_k Z_k) psi -- or, <PAULI>, lambda = sum_words c[b][word] ph (-1)^popc(i & z) psi[i ^ x] from
+// the flat word table and the coefficient rows of qmle_pauli.hip -- then for every gate of the reversed, daggered
+// tape the generator overlap and the inverse gate on both vectors.  No HBM traffic beyond the angle
 // tables and the gradient row; one launch instead of ~(2 gates + 2 angles) launches.
 struct AdjTermDev {
   int32_t out_slot;
@@ -42,13 +43,20 @@ struct AdjLdsArgs {
   int rev_n_slots;
   const float *rev_consts;
   const float *weights;          // [B][n_obs]
-  uint32_t zmask[QMLE_MAX_QUBITS];
+  union {                        // the seed: Z-parity masks, or <PAULI> words and their coefficient rows
+    uint32_t zmask[QMLE_MAX_QUBITS];
+    struct {
+      const PauliWordDev *words;
+      const float *coef;         // [B][n_words]
+      int n_words;
+    } pw;
+  };
   int n_obs;
   float *grad;
   int n_grad_slots;
 };
 
-template <bool DENSE4>
+template <bool DENSE4, bool PAULI>
 __global__ void k_adjoint_lds(const AdjLdsArgs a) {
   extern __shared__ float4 smem4[];
   const int T = a.fwd.T;
@@ -67,12 +75,32 @@ __global__ void k_adjoint_lds(const AdjLdsArgs a) {
   __syncthreads();
   tile_compute<DENSE4>(a.fwd, psi, slots, b);
 
-  const float *w = a.weights + (size_t)b * a.n_obs;
-  for (uint32_t i = tid; i < cnt; i += nt) {
-    float d = 0.f;
-    for (int o = 0; o < a.n_obs; ++o) d += (__popc(i & a.zmask[o]) & 1) ? -w[o] : w[o];
-    const float2 v = psi[sw(i)];
-    lam[sw(i)] = make_float2(d * v.x, d * v.y);
+  if constexpr (PAULI) {
+    const float *cf = a.pw.coef + (size_t)b * a.pw.n_words;
+    for (uint32_t i = tid; i < cnt; i += nt) {
+      float2 acc = make_float2(0.f, 0.f);
+      for (int k = 0; k < a.pw.n_words; ++k) {
+        const PauliWordDev wd = a.pw.words[k];
+        const float c = (__popc(i & wd.z) & 1) ? -cf[k] : cf[k];
+        const float2 v = psi[sw(i ^ wd.x)];
+        if (wd.im) {  // -i v
+          acc.x = fmaf(c, v.y, acc.x);
+          acc.y = fmaf(-c, v.x, acc.y);
+        } else {
+          acc.x = fmaf(c, v.x, acc.x);
+          acc.y = fmaf(c, v.y, acc.y);
+        }
+      }
+      lam[sw(i)] = acc;
+    }
+  } else {
+    const float *w = a.weights + (size_t)b * a.n_obs;
+    for (uint32_t i = tid; i < cnt; i += nt) {
+      float d = 0.f;
+      for (int o = 0; o < a.n_obs; ++o) d += (__popc(i & a.zmask[o]) & 1) ? -w[o] : w[o];
+      const float2 v = psi[sw(i)];
+      lam[sw(i)] = make_float2(d * v.x, d * v.y);
+    }
   }
   __syncthreads();
 
@@ -392,21 +420,28 @@ static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batc
   return L;
 }
 
-extern "C" {
+// The observables of a sweep: Z-parity wire masks (qmle_adjoint_gradient) or a list of weighted Pauli words
+// (qmle_adjoint_gradient_pauli: obs_terms != nullptr, checked by the caller); the sweeps differ in the seed alone.
+struct AdjObs {
+  const uint32_t *wire_masks;
+  const qmle_pauli_term *obs_terms;
+  int n_obs_terms, n_obs;
+};
+struct SeedHold {  // ends the seed's host plan on every way out
+  PauliSeed *sd = nullptr;
+  ~SeedHold() { pauli_seed_end(sd); }
+};
 
-size_t qmle_adjoint_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
-  if (!fwd || !rev || batch < 1) return 0;
-  return adj_layout(fwd, rev, batch).total + 256;
-}
-
-int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
-                          const float *d_angles_rev, int batch, const float *d_weights,
-                          const uint32_t *obs_wire_masks, int n_obs,
-                          const qmle_adjoint_term *terms, int n_terms, float *d_grad,
-                          int n_grad_slots, void *d_workspace, size_t workspace_bytes,
-                          qmle_stream stream_) {
-  if (!fwd || !rev || batch < 1 || 2 * batch > kMaxGridY || !d_weights || !obs_wire_masks ||
-      n_obs < 1 || n_obs > QMLE_MAX_QUBITS || !terms || !d_grad || n_grad_slots < 1 ||
+static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
+                       const float *d_angles_rev, int batch, const float *d_weights, const AdjObs &obs,
+                       const qmle_adjoint_term *terms, int n_terms, float *d_grad,
+                       int n_grad_slots, void *d_workspace, size_t workspace_bytes,
+                       qmle_stream stream_) {
+  const uint32_t *obs_wire_masks = obs.wire_masks;
+  const int n_obs = obs.n_obs;
+  const bool pauli = obs.obs_terms != nullptr;
+  if (!fwd || !rev || batch < 1 || 2 * batch > kMaxGridY || !d_weights || (!pauli && !obs_wire_masks) ||
+      n_obs < 1 || (!pauli && n_obs > QMLE_MAX_QUBITS) || !terms || !d_grad || n_grad_slots < 1 ||
       !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
     return QMLE_ERR_INVALID_ARG;
   if ((fwd->n_slots > 0 && !d_angles_fwd) || (rev->n_slots > 0 && !d_angles_rev))
@@ -428,10 +463,15 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
   char *ws = (char *)d_workspace;
   const AdjLayout L = adj_layout(fwd, rev, batch);
   if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
-  for (int k = 0; k < n_obs; ++k)
+  for (int k = 0; !pauli && k < n_obs; ++k)
     if (!valid_wire_mask(obs_wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
   for (int r = 0; r < n_terms; ++r)
     if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
+  // the seed's tables: behind everything the Z sweep lays out
+  char *seed_ws = ws + L.total;
+  const size_t seed_bytes = workspace_bytes - L.total;
+  if (pauli && seed_bytes < pauli_seed_ws_bytes(batch, obs.n_obs_terms, false)) return QMLE_ERR_WORKSPACE;
+  SeedHold seed;
 
   // ---- n <= 13: psi and lambda both fit in one workgroup's LDS -> a single launch ----------
   bool lds_ok = fwd->whole_state_lds && n <= 13 && fwd->stages.size() == 1;
@@ -496,14 +536,20 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
     a.rev_consts = rev->dev.d_consts;
     a.weights = d_weights;
     a.n_obs = n_obs;
-    for (int k = 0; k < n_obs; ++k) a.zmask[k] = wires_to_pos(obs_wire_masks[k], n);
+    if (pauli) {  // word table and coefficient rows from global memory; the coefficient kernel runs first
+      rc = pauli_seed_begin(&seed.sd, n, batch, obs.obs_terms, obs.n_obs_terms, n_obs, false, true, seed_ws,
+                            seed_bytes, stream);
+      if (rc == QMLE_OK) rc = pauli_seed_flat(seed.sd, batch, d_weights, stream, &a.pw.words, &a.pw.coef, &a.pw.n_words);
+      if (rc != QMLE_OK) return rc;
+    } else {
+      for (int k = 0; k < n_obs; ++k) a.zmask[k] = wires_to_pos(obs_wire_masks[k], n);
+    }
     a.grad = d_grad;
     a.n_grad_slots = n_grad_slots;
     if (FirstUse once{3}; once.first) {
-      HIPCHK(hipFuncSetAttribute((const void *)k_adjoint_lds<false>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_adjoint_lds<true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      for (const void *k : {(const void *)k_adjoint_lds<false, false>, (const void *)k_adjoint_lds<true, false>,
+                            (const void *)k_adjoint_lds<false, true>, (const void *)k_adjoint_lds<true, true>})
+        HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       once.done();
     }
     bool has_dense4 = false;
@@ -512,8 +558,9 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
     // work items of the forward groups: one 64-lane wave per 256 amplitudes, at least 4 waves
     int threads = tile_threads(n);
     if (threads < 256 && n >= 8) threads = 256;
-    if (has_dense4) hipLaunchKernelGGL(k_adjoint_lds<true>, dim3(1, batch), dim3(threads), lds, stream, a);
-    else hipLaunchKernelGGL(k_adjoint_lds<false>, dim3(1, batch), dim3(threads), lds, stream, a);
+    auto *kernel = pauli ? (has_dense4 ? k_adjoint_lds<true, true> : k_adjoint_lds<false, true>)
+                         : (has_dense4 ? k_adjoint_lds<true, false> : k_adjoint_lds<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(1, batch), dim3(threads), lds, stream, a);
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
@@ -529,12 +576,18 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
   rc = run_batch_masks(fwd, d_angles_fwd, batch, QMLE_MEAS_STATE, nullptr, 0, psi, ws + L.fwd_ws,
                        workspace_bytes - L.fwd_ws, stream);
   if (rc != QMLE_OK) return rc;
-  // lambda = (sum_k w_k Z..Z_k) psi
-  ZSumArgs z;
-  z.n_obs = n_obs;
-  for (int k = 0; k < n_obs; ++k) z.mask[k] = wires_to_pos(obs_wire_masks[k], n);
-  hipLaunchKernelGGL(k_zsum_apply, dim3(grid_for(D / 2, 256, 4096), batch), dim3(256), 0, stream,
-                     (const float4 *)psi, (float4 *)lam, n, d_weights, z);
+  if (pauli) {  // lambda = (sum of weighted words) psi
+    rc = pauli_seed_begin(&seed.sd, n, batch, obs.obs_terms, obs.n_obs_terms, n_obs, false, false, seed_ws,
+                          seed_bytes, stream);
+    if (rc == QMLE_OK) rc = pauli_seed_apply(seed.sd, psi, lam, batch, d_weights, stream);
+    if (rc != QMLE_OK) return rc;
+  } else {  // lambda = (sum_k w_k Z..Z_k) psi
+    ZSumArgs z;
+    z.n_obs = n_obs;
+    for (int k = 0; k < n_obs; ++k) z.mask[k] = wires_to_pos(obs_wire_masks[k], n);
+    hipLaunchKernelGGL(k_zsum_apply, dim3(grid_for(D / 2, 256, 4096), batch), dim3(256), 0, stream,
+                       (const float4 *)psi, (float4 *)lam, n, d_weights, z);
+  }
   HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(float), stream));
   // the backward gates act on [psi; lambda] as one batch of 2B states: duplicate the angles
   if (rev->n_slots > 0) {
@@ -658,6 +711,41 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
   }
   HIPCHK(hipGetLastError());
   return QMLE_OK;
+}
+
+extern "C" {
+
+size_t qmle_adjoint_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
+  if (!fwd || !rev || batch < 1) return 0;
+  return adj_layout(fwd, rev, batch).total + 256;
+}
+size_t qmle_adjoint_pauli_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
+                                          int n_obs) {
+  if (!fwd || !rev || batch < 1 || n_obs_terms < 1 || n_obs < 1) return 0;
+  return adj_layout(fwd, rev, batch).total + 256 + pauli_seed_ws_bytes(batch, n_obs_terms, false);
+}
+
+int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
+                          const float *d_angles_rev, int batch, const float *d_weights,
+                          const uint32_t *obs_wire_masks, int n_obs,
+                          const qmle_adjoint_term *terms, int n_terms, float *d_grad,
+                          int n_grad_slots, void *d_workspace, size_t workspace_bytes,
+                          qmle_stream stream) {
+  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {obs_wire_masks, nullptr, 0, n_obs},
+                     terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream);
+}
+
+int qmle_adjoint_gradient_pauli(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
+                                const float *d_angles_rev, int batch, const float *d_weights,
+                                const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                                const qmle_adjoint_term *terms, int n_terms, float *d_grad,
+                                int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
+  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws) return QMLE_ERR_INVALID_ARG;
+  const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
+  if (rc != QMLE_OK) return rc;
+  if (ws_bytes < qmle_adjoint_pauli_workspace_bytes(fwd, rev, batch, n_obs_terms, n_obs)) return QMLE_ERR_INVALID_ARG;
+  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {nullptr, obs_terms, n_obs_terms, n_obs},
+                     terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -491,12 +491,25 @@ size_t qmle_adjoint_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *r
   if (!fwd || !rev || batch < 1 || fwd->n != rev->n) return 0;
   return f64_adj_layout(fwd, rev, batch).total;
 }
+size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
+                                              int n_obs) {
+  if (!fwd || !rev || batch < 1 || fwd->n != rev->n || n_obs_terms < 1 || n_obs < 1) return 0;
+  return f64_adj_layout(fwd, rev, batch).total + 256 +
+         pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true);
+}
 
-int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
-                              int batch, const double *d_weights, const uint32_t *obs_wire_masks, int n_obs,
-                              const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
-                              void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
-  if (!fwd || !rev || batch < 1 || !d_weights || !obs_wire_masks || n_obs < 1 || n_obs > QMLE_MAX_QUBITS || !terms ||
+}  // extern "C"
+
+// Both complex128 sweeps: Z-parity masks (obs_terms == nullptr) or a list of weighted Pauli words, checked by the
+// caller; they differ in the seed alone (k64_zsum_apply / the seed kernels of qmle_pauli.hip per round of samples).
+static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
+                           int batch, const double *d_weights, const uint32_t *obs_wire_masks,
+                           const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                           const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
+                           void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
+  const bool pauli = obs_terms != nullptr;
+  if (!fwd || !rev || batch < 1 || !d_weights || (!pauli && !obs_wire_masks) || n_obs < 1 ||
+      (!pauli && n_obs > QMLE_MAX_QUBITS) || !terms ||
       !d_grad || n_grad_slots < 1 || !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
     return QMLE_ERR_INVALID_ARG;
   if ((fwd->n_slots > 0 && !d_angles_fwd) || (rev->n_slots > 0 && !d_angles_rev)) return QMLE_ERR_INVALID_ARG;
@@ -504,8 +517,8 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
   // one source gate (one generator) per operator of the reverse plan: NO_FUSION or NO_MERGE plans
   for (const auto &srcs : rev->lowered_src)
     if (srcs.size() != 1) return QMLE_ERR_INVALID_ARG;
-  F64Obs obs;
-  int rc = f64_obs(obs_wire_masks, n_obs, n, obs);
+  F64Obs obs = {};
+  int rc = pauli ? QMLE_OK : f64_obs(obs_wire_masks, n_obs, n, obs);
   if (rc != QMLE_OK) return rc;
   for (int r = 0; r < n_terms; ++r) {
     if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
@@ -533,6 +546,17 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
   const int nb = f64_adj_blocks(n);
   const int in_flight = f64_in_flight(n, batch, 32);
   const unsigned gx = grid_for(D / 2 ? D / 2 : 1, 256, 1u << 16);
+  struct SeedHold {
+    PauliSeed *sd = nullptr;
+    ~SeedHold() { pauli_seed_end(sd); }
+  } seed;
+  if (pauli) {  // the seed's tables: behind everything the Z sweep lays out
+    const size_t need = pauli_seed_ws_bytes(in_flight, n_obs_terms, true);
+    if (workspace_bytes - L.total < need) return QMLE_ERR_WORKSPACE;
+    rc = pauli_seed_begin(&seed.sd, n, in_flight, obs_terms, n_obs_terms, n_obs, true, false, ws + L.total,
+                          workspace_bytes - L.total, stream);
+    if (rc != QMLE_OK) return rc;
+  }
   for (int b0 = 0; b0 < batch; b0 += in_flight) {
     const int bc = batch - b0 < in_flight ? batch - b0 : in_flight;
     const double *af = d_angles_fwd ? d_angles_fwd + (size_t)b0 * fwd->n_slots : nullptr;
@@ -542,9 +566,13 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
     for (const LoweredOp &op : fwd->lowered)
       hipLaunchKernelGGL(k64_op, dim3(gx, bc), dim3(256), 0, stream, psi, n, op, fmats + (size_t)b0 * fwd->mat_floats,
                          fwd->mat_floats, fc, af, fwd->n_slots);
-    // lambda = (sum_k w_k Z..Z_k) psi
-    hipLaunchKernelGGL(k64_zsum_apply, dim3(gx, bc), dim3(256), 0, stream, (const double2 *)psi, lam, n,
-                       d_weights + (size_t)b0 * n_obs, obs, n_obs);
+    if (pauli) {  // lambda = (sum of weighted words) psi
+      rc = pauli_seed_apply(seed.sd, psi, lam, bc, d_weights + (size_t)b0 * n_obs, stream);
+      if (rc != QMLE_OK) return rc;
+    } else {  // lambda = (sum_k w_k Z..Z_k) psi
+      hipLaunchKernelGGL(k64_zsum_apply, dim3(gx, bc), dim3(256), 0, stream, (const double2 *)psi, lam, n,
+                         d_weights + (size_t)b0 * n_obs, obs, n_obs);
+    }
     for (size_t r = 0; r < rev->lowered.size(); ++r) {
       const qmle_adjoint_term &t = terms[rev->lowered_src[r][0]];
       if (t.out_slot >= 0) {
@@ -565,6 +593,30 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
     HIPCHK(hipGetLastError());
   }
   return QMLE_OK;
+}
+
+extern "C" {
+
+int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
+                              int batch, const double *d_weights, const uint32_t *obs_wire_masks, int n_obs,
+                              const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
+                              void *d_workspace, size_t workspace_bytes, qmle_stream stream) {
+  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, nullptr, 0, n_obs,
+                         terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream);
+}
+
+int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
+                                    const double *d_angles_rev, int batch, const double *d_weights,
+                                    const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                                    const qmle_adjoint_term *terms, int n_terms, double *d_grad,
+                                    int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
+  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws) return QMLE_ERR_INVALID_ARG;
+  const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
+  if (rc != QMLE_OK) return rc;
+  if (ws_bytes < qmle_adjoint_pauli_workspace_bytes_f64(fwd, rev, batch, n_obs_terms, n_obs))
+    return QMLE_ERR_INVALID_ARG;
+  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, nullptr, obs_terms, n_obs_terms,
+                         n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@
 //   qmle_adjoint.hip   adjoint differentiation
 //   qmle_f64.hip       complex128 engine (its own matrix builder, constants and observable masks)
 //   qmle_gram.hip      Gram matrices of resident states
-//   qmle_pauli.hip     Pauli-word observables of resident states and of vec(rho), their host planner
+//   qmle_pauli.hip     Pauli-word observables of resident states and of vec(rho), their host planner; applying a
+//                      weighted sum of words to resident states (the seed of the adjoint sweep)
 // Kernels stay private to their unit (anonymous namespaces); what crosses a unit boundary is a
 // plain host function that launches them.  The host idioms every unit needs live here (wire masks ->
 // position masks and their range check, aligning a caller's workspace, FNV-1a); align_up, grid_for and
@@ -177,5 +178,28 @@ int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int 
 size_t mw_resident_ws_bytes(int n, int batch);
 int run_mw_resident(const float2 *states, int n, int batch, void *ws, size_t ws_bytes, float *d_out,
                     hipStream_t stream);
+
+// ---- qmle_pauli.hip ----
+// lambda = (sum_t weights[b][terms[t].obs] * terms[t].coef * P_t) psi_b, the seed of the adjoint sweep for observables
+// that are sums of Pauli words.  pauli_seed_begin merges the terms into unique words and puts the word tables and
+// the CSR of their terms into the workspace (pauli_seed_ws_bytes; sized for at most `max_batch` states per
+// pauli_seed_apply / pauli_seed_flat); complex128 states and float64 weights with f64.  `flat`: the table is one
+// PauliWordDev per word (what k_adjoint_lds walks) and only pauli_seed_flat may follow -- it computes the
+// coefficient rows coef[b][word] of `batch` samples and hands out both tables.
+struct PauliSeed;
+struct PauliWordDev {
+  uint32_t x, z;  // bit positions
+  int32_t im;     // ny odd: the phase left beside the coefficient is -i, else 1
+  int32_t pad;
+};
+int pauli_seed_check(int n_qubits, const qmle_pauli_term *terms, int n_terms, int n_obs);
+size_t pauli_seed_ws_bytes(int batch, int n_terms, bool f64);
+int pauli_seed_begin(PauliSeed **out, int n, int max_batch, const qmle_pauli_term *terms, int n_terms, int n_obs,
+                     bool f64, bool flat, void *d_ws, size_t ws_bytes, hipStream_t stream);
+int pauli_seed_apply(const PauliSeed *sd, const void *d_psi, void *d_lam, int batch, const void *d_weights,
+                     hipStream_t stream);
+int pauli_seed_flat(const PauliSeed *sd, int batch, const float *d_weights, hipStream_t stream,
+                    const PauliWordDev **d_words, const float **d_coef, int *n_words);
+void pauli_seed_end(PauliSeed *sd);
 
 }  // namespace qmle

@@ -1,5 +1,5 @@
 // libqmle_sv, Pauli-word observables of resident states: qmle_expval_pauli (complex64), its complex128
-// twin and qmle_density_expval_pauli.  Every X / Y / Hermitian observable is a real-weighted sum of
+// twin and qmle_density_expval_pauli; qmle_apply_pauli_sum and the seed of the adjoint sweep.  Every X / Y / Hermitian observable is a real-weighted sum of
 // words P = i^ny X^x Z^z, and
 //   <psi|P|psi> = Re[(-i)^ny S],   S = sum_i conj(psi_i) (-1)^popc(i & z) psi_{i ^ x}
 // needs every amplitude and its partner i ^ x once.  (The sign is taken at the row index i; the
@@ -25,10 +25,23 @@
 // every slot has one writer per pass; a streamed launch covers 2^12 contiguous amplitudes per workgroup
 // and adds into the same slots).  k_pauli_final adds the slots of a column in fixed order in fp64:
 // no atomics, the same bits from call to call.
+//
+// Applying a sum of words (qmle_apply_pauli_sum, the seed lambda = H psi of the adjoint sweep): with the sign
+// taken at the row index as above,  (P psi)[i] = (-i)^ny (-1)^popc(i & z) psi[i ^ x].  Terms with equal (x, z)
+// are merged on the host into unique WORDS, numbered in (x, z) order; k_pauli_coef adds, per sample and word, the
+// products weight[b][obs] * coef * (-1)^(ny >> 1) of the word's terms in fp64 (a CSR over the terms).  What is
+// left of the phase is 1 (ny even) or -i (ny odd).  The words go through the SAME planner (a word is a "term"
+// whose column is its own number), so the tiles and the streamed masks are those of the measurement:
+// k_pauli_apply_tile stages a tile of psi, keeps 16 complex output accumulators per work item and walks the
+// pass's words; k_pauli_apply_stream forms, per distinct wide x mask, the signed sum d_x(i) of that mask's
+// coefficients and adds d_x(i) psi[i ^ x].  The first launch of a call stores lambda, later ones add to it: one
+// writer per element per launch, launches ordered on the stream -- no atomics, the same bits from call to call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <memory>
+#include <new>
 #include <vector>
 
 #include "qmle_sv.h"
@@ -254,6 +267,181 @@ k_pauli_final(const double *__restrict__ part, int n_rows, int n_obs, R *__restr
   if (threadIdx.x == 0) out[col] = (R)tot;
 }
 
+// ---- lambda = (sum of weighted words) psi ----
+// coef[b][w] = sum over the terms e of word w of weights[b][obs_e] * c_e, in fp64 and in term order; grid
+// (words / 256, states).  c_e carries the term's coefficient and the sign (-1)^(ny >> 1) of its word.
+template <class R>
+__global__ void __launch_bounds__(256)
+k_pauli_coef(const R *__restrict__ weights, int n_obs, const int32_t *__restrict__ ptr,
+             const int32_t *__restrict__ obs, const double *__restrict__ c, int n_words, R *__restrict__ coef) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (w >= n_words) return;
+  const R *row = weights + (size_t)b * n_obs;
+  double acc = 0.0;
+  for (int e = ptr[w]; e < ptr[w + 1]; ++e) acc = fma((double)row[obs[e]], c[e], acc);
+  coef[(size_t)b * n_words + w] = (R)acc;
+}
+
+// acc += s * ph * v,  ph = -i (ny odd) or 1
+template <class C, class R>
+__device__ __forceinline__ void add_word(C &acc, R s, bool im, C v) {
+  if (im) {
+    acc.x = fma(s, v.y, acc.x);
+    acc.y = fma(-s, v.x, acc.y);
+  } else {
+    acc.x = fma(s, v.x, acc.x);
+    acc.y = fma(s, v.y, acc.y);
+  }
+}
+__device__ __forceinline__ float4 pack(const float2 (&a)[2]) { return make_float4(a[0].x, a[0].y, a[1].x, a[1].y); }
+__device__ __forceinline__ double2 pack(const double2 (&a)[1]) { return a[0]; }
+
+// One pass: the geometry, the staging and the index arithmetic of k_pauli_tile.  `words` are the pass's words
+// (PauliTermDev::obs = the word's column of coef [states][n_coef]; w is not read, the sign it holds is in the
+// coefficient).  LDS: the tile of psi alone.  first != 0: out is stored, else added to.
+template <class R>
+__global__ void __launch_bounds__(256)
+k_pauli_apply_tile(const typename Cx<R>::chunk *__restrict__ states, typename Cx<R>::chunk *__restrict__ out,
+                   PauliTile g, const PauliTermDev *__restrict__ words, int n_words,
+                   const R *__restrict__ coef, int n_coef, int first) {
+  typedef typename Cx<R>::type C;
+  typedef typename Cx<R>::chunk Chunk;
+  constexpr int A = (int)(sizeof(Chunk) / sizeof(C)), LB = A == 2 ? 1 : 0, NCH = 16 / A;
+  extern __shared__ __attribute__((aligned(16))) char pauli_lds[];
+  Chunk *tile = reinterpret_cast<Chunk *>(pauli_lds);
+  const uint32_t t = threadIdx.x, b = blockIdx.y;
+  const uint32_t n_chunks = (1u << g.T) >> LB;
+
+  uint32_t tile_mask = 0, base = 0;
+  for (int k = 0; k < g.T; ++k) tile_mask |= 1u << g.pos[k];
+  for (int p = 0, q = 0; p < g.n; ++p)
+    if (!((tile_mask >> p) & 1u)) base |= ((blockIdx.x >> q++) & 1u) << p;
+  uint32_t mine = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (LB + k < g.T) mine |= ((t >> k) & 1u) << g.pos[LB + k];
+
+  const size_t state_off = ((size_t)b << g.n) >> LB;
+  uint32_t gidx[NCH];  // chunk index of this work item's chunk ch in its state
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const uint32_t cl = t | ((uint32_t)ch << 8);
+    uint32_t idx = base | mine;
+#pragma unroll
+    for (int k = 0; k < 4 - LB; ++k)
+      if (LB + 8 + k < g.T) idx |= (((uint32_t)ch >> k) & 1u) << g.pos[LB + 8 + k];
+    gidx[ch] = idx >> LB;
+    if (cl < n_chunks) tile[cl] = states[state_off + gidx[ch]];
+  }
+  __syncthreads();
+
+  const auto *tc = as_constant(words);
+  const auto *cf = as_constant(coef + (size_t)b * n_coef);
+  C acc[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) acc[u].x = acc[u].y = (R)0;
+  for (int k = 0; k < n_words; ++k) {
+    const uint32_t xl = tc[k].xl, zl = tc[k].zl;
+    R s = cf[tc[k].obs];
+    if (s == (R)0) continue;  // (a word whose terms cancel, a sample whose weights leave it out)
+    if (__popc(base & tc[k].zo) & 1) s = -s;
+    const bool im = tc[k].im != 0;
+    if (__popc((t << LB) & zl) & 1) s = -s;
+    // a work item beyond a small tile (it stores nothing) reads some chunk of the tile
+    const uint32_t pt = (t ^ ((xl >> LB) & 255u)) & (n_chunks - 1u);
+    const bool swap = LB && (xl & 1u);
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      const uint32_t pc = (((uint32_t)ch << 8) ^ ((xl >> LB) & ~255u)) & (n_chunks - 1u);
+      Chunk q = tile[pt | pc];
+      if (swap) q = swap_halves(q);
+      C e[A];
+      unpack(q, e);
+#pragma unroll
+      for (int j = 0; j < A; ++j) {
+        const uint32_t lu = (((uint32_t)ch << 8) << LB) | (uint32_t)j;
+        add_word(acc[ch * A + j], (__popc(lu & zl) & 1) ? -s : s, im, e[j]);
+      }
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const uint32_t cl = t | ((uint32_t)ch << 8);
+    if (cl >= n_chunks) continue;
+    C e[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) e[j] = acc[ch * A + j];
+    if (!first) {
+      C old[A];
+      unpack(out[state_off + gidx[ch]], old);
+#pragma unroll
+      for (int j = 0; j < A; ++j) {
+        e[j].x += old[j].x;
+        e[j].y += old[j].y;
+      }
+    }
+    out[state_off + gidx[ch]] = pack(e);
+  }
+}
+
+// The words of one x mask too wide for a tile (n >= 13), the shape of k_pauli_stream: a workgroup covers 2^12
+// contiguous amplitudes, a work item first adds the mask's coefficients into d_x(i) for its 16 amplitudes
+// (local z = the 12 low positions, outer z = the rest), then out[i] (+)= d_x(i) psi[i ^ x], one 16-byte
+// partner chunk at a time.
+template <class R>
+__global__ void __launch_bounds__(256)
+k_pauli_apply_stream(const typename Cx<R>::chunk *__restrict__ states, typename Cx<R>::chunk *__restrict__ out,
+                     int n, uint32_t x, const PauliTermDev *__restrict__ words, int n_words,
+                     const R *__restrict__ coef, int n_coef, int first) {
+  typedef typename Cx<R>::type C;
+  typedef typename Cx<R>::chunk Chunk;
+  constexpr int A = (int)(sizeof(Chunk) / sizeof(C)), LB = A == 2 ? 1 : 0, NCH = 16 / A;
+  const uint32_t t = threadIdx.x, b = blockIdx.y;
+  const uint32_t base = blockIdx.x << kPauliTileBits;
+  const size_t state_off = ((size_t)b << n) >> LB;
+  const auto *tc = as_constant(words);
+  const auto *cf = as_constant(coef + (size_t)b * n_coef);
+  C d[16];
+#pragma unroll
+  for (int u = 0; u < 16; ++u) d[u].x = d[u].y = (R)0;
+  for (int k = 0; k < n_words; ++k) {
+    const uint32_t zl = tc[k].zl;
+    R s = cf[tc[k].obs];
+    if (__popc(base & tc[k].zo) & 1) s = -s;
+    if (__popc((t << LB) & zl) & 1) s = -s;
+    const bool im = tc[k].im != 0;
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+      const uint32_t lu = (((uint32_t)(u / A) << 8) << LB) | (uint32_t)(u % A);
+      const R v = (__popc(lu & zl) & 1) ? -s : s;
+      if (im) d[u].y -= v; else d[u].x += v;
+    }
+  }
+  const uint32_t xc = x >> LB;
+  const bool swap = LB && (x & 1u);
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    const uint32_t c = (base >> LB) | ((uint32_t)ch << 8) | t;
+    Chunk q = states[state_off + (c ^ xc)];
+    if (swap) q = swap_halves(q);
+    C par[A], e[A];
+    unpack(q, par);
+    if (first) {
+#pragma unroll
+      for (int j = 0; j < A; ++j) e[j].x = e[j].y = (R)0;
+    } else {
+      unpack(out[state_off + c], e);
+    }
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+      const C dd = d[ch * A + j];
+      e[j].x = fma(dd.x, par[j].x, fma(-dd.y, par[j].y, e[j].x));
+      e[j].y = fma(dd.x, par[j].y, fma(dd.y, par[j].x, e[j].y));
+    }
+    out[state_off + c] = pack(e);
+  }
+}
+
 // Tr(P rho) = sum_j i^ny (-1)^popc((j ^ x) & z) rho[j ^ x][j] for the terms of one launch; grid (states,
 // observables of the launch).  Terms arrive sorted by observable, 64 per launch; d_out is zeroed by the call and a
 // launch adds its fp64 sum (an observable of more than 64 words is therefore added in float32 across launches,
@@ -458,6 +646,190 @@ int run_pauli(const void *d_states, int n, int batch, const qmle_pauli_term *ter
   return QMLE_OK;
 }
 
+// ---- lambda = (sum of weighted words) psi: host ----
+struct SeedLayout {
+  int chunk;  // states per launch
+  size_t table, ptr, obs, c, coef, total;
+};
+// (every table is sized by the term count, which bounds the word count: the query needs no plan)
+SeedLayout seed_layout(int batch, int n_terms, bool f64) {
+  SeedLayout L;
+  L.chunk = batch < kMaxGridY ? batch : kMaxGridY;
+  L.table = 0;
+  L.ptr = L.table + align_up((size_t)n_terms * sizeof(PauliTermDev), 256);
+  L.obs = L.ptr + align_up(((size_t)n_terms + 1) * sizeof(int32_t), 256);
+  L.c = L.obs + align_up((size_t)n_terms * sizeof(int32_t), 256);
+  L.coef = L.c + align_up((size_t)n_terms * sizeof(double), 256);
+  L.total = L.coef + align_up((size_t)L.chunk * n_terms * (f64 ? 8 : 4), 256) + 256;
+  return L;
+}
+
+// unique words in (x, z) order of their position masks, as planner input (column = the word's number, weight 1),
+// and the CSR of their terms
+struct SeedWords {
+  std::vector<qmle_pauli_term> words;
+  std::vector<int32_t> ptr, obs;
+  std::vector<double> c;
+};
+SeedWords seed_words(int n, const qmle_pauli_term *terms, int n_terms) {
+  const std::vector<PTerm> pos = to_positions(n, terms, n_terms);
+  std::vector<int> order((size_t)n_terms);
+  for (int k = 0; k < n_terms; ++k) order[k] = k;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+    return pos[a].x != pos[b].x ? pos[a].x < pos[b].x : pos[a].z < pos[b].z;
+  });
+  SeedWords sw;
+  for (int k : order) {
+    if (sw.words.empty() || sw.words.back().x_wires != terms[k].x_wires || sw.words.back().z_wires != terms[k].z_wires) {
+      sw.words.push_back({terms[k].x_wires, terms[k].z_wires, (int32_t)sw.words.size(), 1.0});
+      sw.ptr.push_back((int32_t)sw.obs.size());
+    }
+    sw.obs.push_back(terms[k].obs);
+    sw.c.push_back(pos[k].w);  // coef * (-1)^(ny >> 1)
+  }
+  sw.ptr.push_back((int32_t)sw.obs.size());
+  return sw;
+}
+PPlan seed_plan(int n, const SeedWords &sw) { return pauli_plan(n, sw.words.data(), (int)sw.words.size()); }
+
+}  // namespace
+
+namespace qmle {
+
+struct PauliSeed {
+  int n, n_words, n_obs;
+  bool f64;
+  SeedLayout L;
+  char *ws;
+  PPlan plan;                       // empty for the flat table of the whole-sweep-in-LDS kernel
+  std::vector<size_t> pass_off;     // first table entry of every pass, then of every streamed mask
+};
+
+int pauli_seed_check(int n_qubits, const qmle_pauli_term *terms, int n_terms, int n_obs) {
+  return check_terms(n_qubits, terms, n_terms, n_obs, kPauliMaxQubits);
+}
+size_t pauli_seed_ws_bytes(int batch, int n_terms, bool f64) { return seed_layout(batch, n_terms, f64).total; }
+
+int pauli_seed_begin(PauliSeed **out, int n, int max_batch, const qmle_pauli_term *terms, int n_terms, int n_obs,
+                     bool f64, bool flat, void *d_ws, size_t ws_bytes, hipStream_t stream) {
+  *out = nullptr;
+  char *ws = (char *)d_ws;
+  const SeedLayout L = seed_layout(max_batch, n_terms, f64);
+  if (!align_workspace(ws, ws_bytes) || ws_bytes < L.total - 256) return QMLE_ERR_INVALID_ARG;
+  const SeedWords sw = seed_words(n, terms, n_terms);
+  PauliSeed *sd = new (std::nothrow) PauliSeed{n, (int)sw.words.size(), n_obs, f64, L, ws, {}, {}};
+  if (!sd) return QMLE_ERR_INTERNAL;
+  std::unique_ptr<PauliSeed> hold(sd);
+  if (flat) {
+    std::vector<PauliWordDev> table;
+    for (const qmle_pauli_term &w : sw.words) {
+      const uint32_t x = wires_to_pos(w.x_wires, n), z = wires_to_pos(w.z_wires, n);
+      table.push_back({x, z, __builtin_popcount(x & z) & 1, 0});
+    }
+    HIPCHK(hipMemcpyAsync(ws + L.table, table.data(), table.size() * sizeof(PauliWordDev), hipMemcpyHostToDevice, stream));
+  } else {
+    sd->plan = seed_plan(n, sw);
+    std::vector<PauliTermDev> table;
+    for (const PPass &ps : sd->plan.passes) {
+      sd->pass_off.push_back(table.size());
+      table.insert(table.end(), ps.terms.begin(), ps.terms.end());
+    }
+    for (const PStream &ps : sd->plan.streams) {
+      sd->pass_off.push_back(table.size());
+      table.insert(table.end(), ps.terms.begin(), ps.terms.end());
+    }
+    HIPCHK(hipMemcpyAsync(ws + L.table, table.data(), table.size() * sizeof(PauliTermDev), hipMemcpyHostToDevice, stream));
+    if (f64) {
+      if (FirstUse once{1}; once.first) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_pauli_apply_tile<double>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double2) << kPauliTileBits)));
+        once.done();
+      }
+    }
+  }
+  HIPCHK(hipMemcpyAsync(ws + L.ptr, sw.ptr.data(), sw.ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(ws + L.obs, sw.obs.data(), sw.obs.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+  HIPCHK(hipMemcpyAsync(ws + L.c, sw.c.data(), sw.c.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  *out = hold.release();
+  return QMLE_OK;
+}
+void pauli_seed_end(PauliSeed *sd) { delete sd; }
+
+template <class R>
+static void seed_coef(const PauliSeed *sd, int batch, const void *d_weights, hipStream_t stream) {
+  hipLaunchKernelGGL(k_pauli_coef<R>, dim3(grid_for((uint64_t)sd->n_words, 256), batch), dim3(256), 0, stream,
+                     (const R *)d_weights, sd->n_obs, (const int32_t *)(sd->ws + sd->L.ptr),
+                     (const int32_t *)(sd->ws + sd->L.obs), (const double *)(sd->ws + sd->L.c), sd->n_words,
+                     (R *)(sd->ws + sd->L.coef));
+}
+
+int pauli_seed_flat(const PauliSeed *sd, int batch, const float *d_weights, hipStream_t stream,
+                    const PauliWordDev **d_words, const float **d_coef, int *n_words) {
+  if (batch > sd->L.chunk || sd->f64) return QMLE_ERR_INTERNAL;
+  seed_coef<float>(sd, batch, d_weights, stream);
+  HIPCHK(hipGetLastError());
+  *d_words = (const PauliWordDev *)(sd->ws + sd->L.table);
+  *d_coef = (const float *)(sd->ws + sd->L.coef);
+  *n_words = sd->n_words;
+  return QMLE_OK;
+}
+
+template <class R>
+static int seed_apply(const PauliSeed *sd, const void *d_psi, void *d_lam, int batch, const void *d_weights,
+                      hipStream_t stream) {
+  typedef typename Cx<R>::type C;
+  typedef typename Cx<R>::chunk Chunk;
+  const int n = sd->n;
+  const size_t lds = sizeof(C) << (n < kPauliTileBits ? n : kPauliTileBits);
+  const unsigned tiles = n > kPauliTileBits ? 1u << (n - kPauliTileBits) : 1u;
+  const PauliTermDev *d_table = (const PauliTermDev *)(sd->ws + sd->L.table);
+  const R *d_coef = (const R *)(sd->ws + sd->L.coef);
+  for (int b0 = 0; b0 < batch; b0 += sd->L.chunk) {
+    const int bc = batch - b0 < sd->L.chunk ? batch - b0 : sd->L.chunk;
+    const Chunk *st = (const Chunk *)((const C *)d_psi + ((size_t)b0 << n));
+    Chunk *lam = (Chunk *)((C *)d_lam + ((size_t)b0 << n));
+    seed_coef<R>(sd, bc, (const R *)d_weights + (size_t)b0 * sd->n_obs, stream);
+    size_t k = 0;
+    int first = 1;
+    for (const PPass &ps : sd->plan.passes) {
+      hipLaunchKernelGGL(k_pauli_apply_tile<R>, dim3(tiles, bc), dim3(256), lds, stream, st, lam, ps.geo,
+                         d_table + sd->pass_off[k++], (int)ps.terms.size(), d_coef, sd->n_words, first);
+      first = 0;
+    }
+    for (const PStream &ps : sd->plan.streams) {
+      hipLaunchKernelGGL(k_pauli_apply_stream<R>, dim3(tiles, bc), dim3(256), 0, stream, st, lam, n, ps.x,
+                         d_table + sd->pass_off[k++], (int)ps.terms.size(), d_coef, sd->n_words, first);
+      first = 0;
+    }
+    HIPCHK(hipGetLastError());
+  }
+  return QMLE_OK;
+}
+int pauli_seed_apply(const PauliSeed *sd, const void *d_psi, void *d_lam, int batch, const void *d_weights,
+                     hipStream_t stream) {
+  if (sd->plan.passes.empty() && sd->plan.streams.empty()) return QMLE_ERR_INTERNAL;
+  return sd->f64 ? seed_apply<double>(sd, d_psi, d_lam, batch, d_weights, stream)
+                 : seed_apply<float>(sd, d_psi, d_lam, batch, d_weights, stream);
+}
+
+}  // namespace qmle
+
+namespace {
+
+int run_apply(const void *d_states, int n, int batch, const qmle_pauli_term *terms, int n_terms, int n_obs,
+              const void *d_weights, void *d_out, void *d_ws, size_t ws_bytes, bool f64, hipStream_t stream) {
+  if (!d_states || !d_out || !d_weights || !d_ws || batch < 1 || d_out == d_states) return QMLE_ERR_INVALID_ARG;
+  int rc = check_terms(n, terms, n_terms, n_obs, kPauliMaxQubits);
+  if (rc != QMLE_OK) return rc;
+  if (ws_bytes < seed_layout(batch, n_terms, f64).total) return QMLE_ERR_INVALID_ARG;
+  PauliSeed *sd = nullptr;
+  rc = pauli_seed_begin(&sd, n, batch, terms, n_terms, n_obs, f64, false, d_ws, ws_bytes, stream);
+  if (rc != QMLE_OK) return rc;
+  rc = pauli_seed_apply(sd, d_states, d_out, batch, d_weights, stream);
+  pauli_seed_end(sd);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -488,6 +860,33 @@ int qmle_expval_pauli_reads(int n_qubits, const qmle_pauli_term *terms, int n_te
   const int rc = check_terms(n_qubits, terms, n_terms, kPauliMaxObs, kPauliMaxQubits);
   if (rc != QMLE_OK) return rc;
   return pauli_plan(n_qubits, terms, n_terms).reads();
+}
+
+size_t qmle_apply_pauli_sum_workspace_bytes(int n_qubits, int batch, int n_terms, int n_obs) {
+  if (n_qubits < 1 || n_qubits > kPauliMaxQubits || batch < 1 || n_terms < 1 || n_obs < 1) return 0;
+  return seed_layout(batch, n_terms, false).total;
+}
+size_t qmle_apply_pauli_sum_workspace_bytes_f64(int n_qubits, int batch, int n_terms, int n_obs) {
+  if (n_qubits < 1 || n_qubits > kPauliMaxQubits || batch < 1 || n_terms < 1 || n_obs < 1) return 0;
+  return seed_layout(batch, n_terms, true).total;
+}
+int qmle_apply_pauli_sum(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms, int n_terms,
+                         int n_obs, const float *d_weights, void *d_out, void *d_ws, size_t ws_bytes,
+                         qmle_stream stream) {
+  return run_apply(d_states, n_qubits, batch, terms, n_terms, n_obs, d_weights, d_out, d_ws, ws_bytes, false,
+                   (hipStream_t)stream);
+}
+int qmle_apply_pauli_sum_f64(const void *d_states, int n_qubits, int batch, const qmle_pauli_term *terms,
+                             int n_terms, int n_obs, const double *d_weights, void *d_out, void *d_ws,
+                             size_t ws_bytes, qmle_stream stream) {
+  return run_apply(d_states, n_qubits, batch, terms, n_terms, n_obs, d_weights, d_out, d_ws, ws_bytes, true,
+                   (hipStream_t)stream);
+}
+int qmle_apply_pauli_sum_reads(int n_qubits, const qmle_pauli_term *terms, int n_terms, int f64) {
+  (void)f64;  // both engines cut the same tiles
+  const int rc = check_terms(n_qubits, terms, n_terms, kPauliMaxObs, kPauliMaxQubits);
+  if (rc != QMLE_OK) return rc;
+  return seed_plan(n_qubits, seed_words(n_qubits, terms, n_terms)).reads();
 }
 
 int qmle_density_expval_pauli(const void *d_rho, int n_qubits, int batch, const qmle_pauli_term *terms,

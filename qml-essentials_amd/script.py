@@ -16,7 +16,7 @@ import numpy as np
 from . import _native as N
 from . import distributed, memory, simulation
 from .batching import Batched, to_numpy
-from .operations import KrausChannel, Operation, z_parity_mask
+from .operations import MAX_PAULI_WIRES, KrausChannel, Operation, pauli_terms, z_parity_mask
 from .tape import batch_context, recording
 from .utils import PRNGKey
 
@@ -429,23 +429,44 @@ class Script:
 
     def vjp(self, obs: List[Operation], cotangent, *, args: tuple = (),
             kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
-            argnums: Tuple[int, ...] = (0,)):
+            argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False):
         """Gradient of ``sum_k cotangent[b, k] * <obs_k>_b`` with respect to the array arguments
         ``argnums`` by ADJOINT differentiation: one backward sweep for all angles
-        (:mod:`adjoint`).  ``obs`` must be Z / Z-parity observables; ``cotangent`` has shape
+        (:mod:`adjoint`).  ``obs``: at most 32 Z / Z-parity observables seed the sweep from their wire masks.
+        With ``pauli_seed=True`` any other list that is a sum of Pauli words (``simulation.pauli_term_list``:
+        PauliX / PauliY, products, Hermitian matrices on up to ``MAX_PAULI_WIRES`` wires) seeds it with
+        ``lambda = H psi`` from the Pauli-word kernels; more than 32 Z parities take that seed in any case, as
+        x = 0 words.  Without the flag an observable with an X / Y / Hermitian factor raises
+        ``AdjointUnsupported`` as it always did (callers rely on that refusal to fall back to the parameter-shift
+        Jacobian).  A batched matrix, a parametrised observable and a wider Hermitian have no term list:
+        ``AdjointUnsupported`` either way, as for noisy circuits.  ``cotangent`` has shape
         ``(B, n_obs)`` (``(n_obs,)`` without ``in_axes``).  Returns one array per ``argnums``
         entry of shape ``(B, *arg_shape)`` (no ``B`` axis without ``in_axes``).  A ``cotangent`` with a
         leading axis of K cotangents, ``(K, B, n_obs)``, is served by one trace and one sweep over K * B
         states and returns ``(K, B, *arg_shape)`` (a Jacobian: K = n_obs one-hot rows)."""
         from . import adjoint
 
+        if not obs:
+            raise adjoint.AdjointUnsupported("adjoint differentiation needs at least one observable")
         masks = [z_parity_mask(o) for o in obs]
-        if not obs or any(m is None for m in masks):
-            raise adjoint.AdjointUnsupported("adjoint differentiation needs Z / Z-parity observables")
+        if any(m is None for m in masks) and not pauli_seed:
+            kinds = sorted({type(o).__name__ for o, m in zip(obs, masks) if m is None})
+            raise adjoint.AdjointUnsupported(
+                "adjoint differentiation needs Z / Z-parity observables; pauli_seed=True seeds the sweep with "
+                "H psi for sums of Pauli words (got " + ", ".join(kinds) + ")")
         tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
             obs, args, kwargs, in_axes, argnums)
         if any(isinstance(o, KrausChannel) for o in tape):
             raise adjoint.AdjointUnsupported("adjoint differentiation of noisy circuits")
+        obs_terms = None
+        if any(m is None for m in masks) or len(obs) > 32:  # not the Z seed: the observables as weighted Pauli words
+            masks, obs_terms = None, simulation.pauli_term_list(obs, n_qubits)
+            if obs_terms is None:
+                kinds = sorted({type(o).__name__ for o in obs if pauli_terms(o) is None})
+                raise adjoint.AdjointUnsupported(
+                    "adjoint differentiation needs observables that are sums of Pauli words: "
+                    + (", ".join(kinds) + " has none (a batched matrix, a parametrised observable or more than "
+                       f"{MAX_PAULI_WIRES} wires)" if kinds else "the term list exceeds the library's limits"))
         from .utils import x64_enabled
 
         x64 = x64_enabled()  # complex128 sweep, float64 tables (jax.grad with jax_enable_x64, test_jaqsi.py:57)
@@ -458,7 +479,8 @@ class Script:
             want[s_] = True
         grads = {k: np.zeros((K, B) + tuple(shp)) for k, shp in leaf_shapes.items()}
         if slots:
-            d = adjoint.adjoint_slot_gradient(low, n_qubits, B, masks, w, want, x64=x64)  # [K * B, n_slots]
+            d = adjoint.adjoint_slot_gradient(low, n_qubits, B, masks, w, want, x64=x64,
+                                              obs_terms=obs_terms)  # [K * B, n_slots]
             d = d.reshape(K, B, -1)
             for s_, _rule, tangent, _name in slots:
                 for lid, flat, coef in tangent:  # gate angles are scalars: one leaf element each
