@@ -408,7 +408,8 @@ class Plan:
     def describe(self) -> dict:
         """``qmle_plan_describe`` as a dict.  The last stage carries the reports of the handle's last batch run
         (``measure_tiles_per_workgroup_last_run``, ``measured_from_registers_last_run``,
-        ``wave_private_walk_last_run``, ``staging_dma_last_run``, and ``chunk_loop_last_run``: ``"one_stream"``,
+        ``wave_private_walk_last_run``, ``staging_dma_last_run``, ``last_group_lane_swap_last_run``, and
+        ``chunk_loop_last_run``: ``"one_stream"``,
         ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run):
         describe ``executed(meas)``, after the run."""
         L = lib()

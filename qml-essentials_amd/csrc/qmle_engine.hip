@@ -818,6 +818,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   plan->measure_regs_last_run = false;
   plan->wave_private_last_run = false;
   plan->staging_dma_last_run = false;
+  plan->lane_swap_last_run = false;
   int chunk_no = 0;
   for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
     const int bc = std::min(batch - b0, L.in_flight);
@@ -853,17 +854,18 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
                                   n_obs, stream, &reg_q, d_coef + (size_t)b0 * 32);
         } else {
           FillReuse *const reuse = si == 0 && reuse_zeros ? &slot_fill[slot] : nullptr;
-          bool from_regs = false, by_dma = false;
+          bool from_regs = false, by_dma = false, by_lane_swap = false;
           rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, tm,
                            last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
                            last_fused ? n_obs : 0, stream, /*from_zero=*/true, cols,
                            last_fused && (oc.single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr, reuse,
-                           &from_regs, &by_dma);
+                           &from_regs, &by_dma, &by_lane_swap);
           if (last_fused) {
             plan->measure_tpw_last_run = 1 << tile_row_shift;
             plan->measure_regs_last_run = from_regs;
             plan->wave_private_last_run = from_regs && st.wave_private;
             plan->staging_dma_last_run = by_dma;
+            plan->lane_swap_last_run = by_lane_swap;
           }
           if (reuse && reuse->filled) filled_states += (uint64_t)bc;
           if (reuse && reuse->elided) elided = true;

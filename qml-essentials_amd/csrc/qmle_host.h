@@ -141,7 +141,8 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream, bool from_zero = false,
                 float2 *cols = nullptr, int *row_shift = nullptr, FillReuse *reuse = nullptr,
                 bool *from_regs = nullptr,   // *from_regs: <Z> came from the last group's registers (Stage::zreg)
-                bool *by_dma = nullptr);     // *by_dma: ... and the walk staged its tiles by LDS DMA (Stage::dma_tables)
+                bool *by_dma = nullptr,      // *by_dma: ... and the walk staged its tiles by LDS DMA (Stage::dma_tables)
+                bool *by_lane_swap = nullptr);  // ... and ran its last group through lane swaps (Stage::lane_swap_last)
 int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs);
 int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *states,
                        const float *mats, const float *angles, int batch, void *out,

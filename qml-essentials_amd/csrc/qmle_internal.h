@@ -186,6 +186,20 @@ struct Stage {
   // dma_tables: what the tables allow; a run also needs an input without known zeros inside the tile.
   bool dma_tables = false;
   uint32_t fast_gtab_dma = 0, dma_delta[4] = {};
+  // The last group through lane swaps: a wave-private DMA walk of >= 2 groups whose last group holds only
+  // uncontrolled 1-qubit ops on the positions that are lane bits 4 and 5 of the group in front of it, at in-thread
+  // indices 2 and 3, one each (so ops2's codes serve both forms).  The kernel then runs both groups on one gather: behind the
+  // first it trades in-thread bit 2 for lane bit 4 and in-thread bit 3 for lane bit 5 (v_permlane16_swap /
+  // v_permlane32_swap) and applies the last group's ops where the amplitudes are; the X / CX that the table form puts
+  // into the layout between the two groups share no bit with those ops and move behind them, into the records.
+  // lane_swap_cross: the targets sit the other way round -- in-thread index 3 on lane bit 4 (the 23-qubit layer's one
+  // op), index 2 on lane bit 5 -- and the swaps pair up accordingly.
+  // zreg_swap: Stage::zreg for the frame a work item holds then -- in-thread bit i at position zreg_swap_bits[i],
+  // thread bit k at zreg_swap_thread_bits[k].  The table form's tables and records stay: known-zero walks take them.
+  bool lane_swap_last = false, lane_swap_cross = false;
+  uint16_t zreg_swap[16] = {};
+  int8_t zreg_swap_bits[4] = {}, zreg_swap_thread_bits[12] = {};
+  std::vector<int8_t> zreg_between;  // report only: the X / CX between the last two groups, as zreg_after's pairs
   // report only (describe_plan): indices into the stage's ops2 stream of the ops that run in unit-pivot form and of
   // the carriers that take their chains' pivots (assign_unit_forms)
   std::vector<int> unit_form_ops, scale_carriers;
@@ -284,6 +298,7 @@ struct qmle_plan {
   bool measure_regs_last_run = false;
   bool wave_private_last_run = false;     // ... and ran its tile loop without a workgroup barrier (Stage::wave_private)
   bool staging_dma_last_run = false;      // ... and staged its tiles by LDS DMA (Stage::dma_tables)
+  bool lane_swap_last_run = false;        // ... and ran its last group through lane swaps (Stage::lane_swap_last)
   // ... and how the last batch run ordered its chunks (ChunkPipeline::form; a run with one chunk, or with the whole
   // state in the LDS, is a one-stream run)
   int chunk_loop_last_run = qmle::kChunkLoopNone;

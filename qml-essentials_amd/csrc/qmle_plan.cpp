@@ -249,7 +249,7 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   st.fast_ok = false;
   st.fast_begin = st.fast_end = (int)p->groups2.size();
   st.fast_info.clear();
-  st.slab_load = st.wave_private = st.dma_tables = false;
+  st.slab_load = st.wave_private = st.dma_tables = st.lane_swap_last = st.lane_swap_cross = false;
   st.sync_tile_end = true;
   const int T = st.T;
   if (T < kFastMinT || T > kFastMaxT || (p->flags & QMLE_PLAN_NO_REGTILE)) return;
@@ -381,6 +381,10 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   int last_group = -1;
   uint32_t last_G = 0;
   std::vector<int> held;  // X / CX kept back for behind the last group
+  // M as it stood when the newest group was emitted -- the X / CX between that group and the one in front of it --
+  // and their (control or -1, target) pairs (Stage::lane_swap_last)
+  uint32_t Ncol[16], Nconst = 0;
+  std::vector<int8_t> between;
   const uint32_t slab_bits = T > 10 ? ((1u << T) - 1u) & ~1023u : 0u;
   // (Correctness rests on the scan alone: an X / CX that no later op touches commutes with everything behind it.  The
   // column test only says when waiting pays: X[t] XORs column t into the constant, CX[c -> t] into column c, so a
@@ -467,6 +471,9 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
       done[i] = 1;
       ++n_done;
     }
+    std::memcpy(Ncol, Mcol, sizeof(Ncol));
+    Nconst = Mconst;
+    between = st.zreg_after;
     M_reset();
     for (int i : trailing) {
       if (keeps_back(i)) held.push_back(i);
@@ -548,6 +555,56 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   st.fast_end = (int)p->groups2.size();
   st.fast_ok = true;
   mark_wave_private_phases(p, st, measured);
+  // The last group through lane swaps (Stage::lane_swap_last).  Behind the ops of the group in front of it, work item t
+  // holds amplitude c at index e(t, c) of THAT group's frame.  The X / CX between the two groups (N) touch none of
+  // the last group's positions, so its ops commute to the front of them: they run in that frame, on the positions
+  // the two swaps brought in-thread, and a record is a row of M N -- N first, then everything behind the last group.
+  st.lane_swap_last = st.lane_swap_cross = false;
+  st.zreg_between.clear();
+  std::memset(st.zreg_swap, 0, sizeof(st.zreg_swap));
+  const int ng = st.fast_end - st.fast_begin;
+  if (measured && st.zreg_ok && st.wave_private && st.dma_tables && ng >= 2) {
+    const Group2 &gl = p->groups2[st.fast_end - 1];
+    const Stage::FastGroupInfo &pi = st.fast_info[ng - 2], &li = st.fast_info[ng - 1];
+    bool ok = gl.n_ops >= 1, straight = true, cross = true;  // which lane bit in-thread index 2 / 3 trades with
+    uint32_t members = 0;
+    for (int k = 0; k < (int)gl.n_ops && ok; ++k) {
+      const LoweredOp &o = p->ops2[gl.op_begin + k];  // (t0: the in-thread index, which the dispatch code carries)
+      ok = o.kind == LK_1Q && o.nc == 0 && !(o.flags & LF_PERMX) && (o.t0 == 2 || o.t0 == 3);
+      if (!ok) break;
+      const int pos = (int)li.bits[(int)o.t0];
+      straight = straight && pos == (int)pi.thread_bits[o.t0 + 2];
+      cross = cross && pos == (int)pi.thread_bits[7 - o.t0];
+      members |= 1u << pos;
+    }
+    ok = ok && (straight || cross);
+    cross = !straight;
+    for (size_t i = 0; i + 1 < between.size() && ok; i += 2)
+      if (members & ((1u << between[i + 1]) | (between[i] >= 0 ? 1u << between[i] : 0u))) ok = false;
+    if (ok) {
+      auto M_lin = [&](uint32_t e) {
+        uint32_t v = 0;
+        for (int j = 0; j < T; ++j)
+          if (e & (1u << j)) v ^= Mcol[j];
+        return v;
+      };
+      // in-thread index i = 2, 3 trades with lane bit lane_of(i)
+      auto lane_of = [&](int i) { return cross ? 7 - i : i + 2; };
+      for (int i = 0; i < 4; ++i) st.zreg_swap_bits[i] = (int8_t)(i < 2 ? (int)pi.bits[i] : (int)pi.thread_bits[lane_of(i)]);
+      for (int t = 0; t < T - 4; ++t) st.zreg_swap_thread_bits[t] = pi.thread_bits[t];
+      for (int i = 2; i < 4; ++i) st.zreg_swap_thread_bits[lane_of(i)] = (int8_t)pi.bits[i];
+      const uint32_t cnst = M_lin(Nconst) ^ Mconst;
+      for (int j = 0; j < T; ++j) {
+        uint32_t rec = ((cnst >> j) & 1u) << 15;
+        for (int i = 0; i < 4; ++i) rec |= ((M_lin(Ncol[(int)st.zreg_swap_bits[i]]) >> j) & 1u) << i;
+        for (int t = 0; t < T - 4; ++t) rec |= ((M_lin(Ncol[(int)st.zreg_swap_thread_bits[t]]) >> j) & 1u) << (4 + t);
+        st.zreg_swap[j] = (uint16_t)rec;
+      }
+      st.zreg_between = between;
+      st.lane_swap_last = true;
+      st.lane_swap_cross = cross;
+    }
+  }
 }
 
 // Which wave touches which slot in every phase of the measuring walk, read off the tables as emitted; sets
@@ -1670,6 +1727,27 @@ std::string describe_plan(const qmle_plan *p) {
         }
       }
     }
+    // the last group through lane swaps (Stage::lane_swap_last; like the DMA form it rides on, a run also needs an input
+    // without known zeros inside the tile): the records of the frame behind the swaps, the positions of its in-thread
+    // bits and of its thread bits; the X / CX behind it: `measure_between` (between the last two groups), then
+    // `measure_after`
+    const bool lane_swap = st.fast_ok && st.lane_swap_last && stages_by_dma(p, s);
+    os << ",\"last_group_lane_swap\":" << (lane_swap ? "true" : "false");
+    if (lane_swap) {
+      os << ",\"lane_swap_crossed\":" << (st.lane_swap_cross ? "true" : "false") << ",\"measure_records_swap\":[";
+      for (int j = 0; j < st.T; ++j) {
+        const ZregRecord r = zreg_record(st.zreg_swap[j]);
+        os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
+      }
+      os << "],\"measure_swap_bits\":[";
+      for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_swap_bits[i];
+      os << "],\"measure_swap_thread_bits\":[";
+      for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_swap_thread_bits[t];
+      os << "],\"measure_between\":[";
+      for (size_t i = 0; i + 1 < st.zreg_between.size(); i += 2)
+        os << (i ? "," : "") << "[" << (int)st.zreg_between[i] << "," << (int)st.zreg_between[i + 1] << "]";
+      os << "]";
+    }
     if (from_regs) {
       os << ",\"measure_records\":[";
       for (int j = 0; j < st.T; ++j) {
@@ -1707,6 +1785,7 @@ std::string describe_plan(const qmle_plan *p) {
          << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false")
          << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false")
          << ",\"staging_dma_last_run\":" << (p->staging_dma_last_run ? "true" : "false")
+         << ",\"last_group_lane_swap_last_run\":" << (p->lane_swap_last_run ? "true" : "false")
          << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->chunk_loop_last_run] << "\"";
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];

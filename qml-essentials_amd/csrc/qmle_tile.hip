@@ -415,6 +415,23 @@ __device__ __forceinline__ void fast_dispatch(A16 &a, int code, const Mat2S &M) 
 #undef QMLE_C12
 }
 
+// In-thread bit 2 of the 16 amplitudes <-> lane bit 4, in-thread bit 3 <-> lane bit 5: v_permlane16_swap trades the
+// odd 16-lane rows of its first operand with the even rows of its second, v_permlane32_swap lanes 32..63 of the first
+// with lanes 0..31 of the second -- one instruction per 32-bit half of an amplitude pair, 32 in all, no LDS.  (The
+// builtins, so that hipcc places the wait states the swaps need behind a vector write of their operands.)
+template <int I, int J, bool ROW> __device__ __forceinline__ void swap_lane_bit(A16 &a) {
+  u64 &x = at<I>(a), &y = at<J>(a);
+  const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32), yl = (uint32_t)y, yh = (uint32_t)(y >> 32);
+  const auto lo = ROW ? __builtin_amdgcn_permlane16_swap(xl, yl, false, false) : __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
+  const auto hi = ROW ? __builtin_amdgcn_permlane16_swap(xh, yh, false, false) : __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
+  x = (u64)lo[0] | ((u64)hi[0] << 32);
+  y = (u64)lo[1] | ((u64)hi[1] << 32);
+}
+// CROSS: in-thread bit 3 <-> lane bit 4, in-thread bit 2 <-> lane bit 5 (Stage::lane_swap_cross).
+template <bool CROSS> __device__ __forceinline__ void swap_lanes_45(A16 &a) {
+  static_for<8>([&](auto q) { swap_lane_bit<pair_idx<2>((int)q), pair_idx<2>((int)q) | 4, !CROSS>(a); });
+  static_for<8>([&](auto q) { swap_lane_bit<pair_idx<3>((int)q), pair_idx<3>((int)q) | 8, CROSS>(a); });
+}
 
 struct Tile2Args {
   const Group2 *groups;     // this stage's Group2 range
@@ -438,12 +455,15 @@ struct Tile2Args {
   // map (lane bits at local bits 1..6, the 8 float4 at 7..9, the wave index on top); kWalkSyncStaged / kWalkSyncTileEnd
   // -- a workgroup barrier is needed behind the staging stores / before the next tile's.  kWalkDma (with kWalkSlab and
   // neither barrier; Stage::dma_tables): the tile is staged by LDS DMA, one tile ahead -- in_* / gtab give the lane's
-  // offset for the SWIZZLED index sw(2 lane | wave << 10), dma_delta[u & 3] is XORed in for piece u.  (Last members:
-  // no other kernel's argument offsets move.)
+  // offset for the SWIZZLED index sw(2 lane | wave << 10), dma_delta[u & 3] is XORed in for piece u.  kWalkLaneSwap
+  // (with kWalkDma only; Stage::lane_swap_last, kWalkLaneSwapCross: Stage::lane_swap_cross): the last two groups run on ONE gather, two lane swaps between them
+  // (tile2_groups), and TileArgs::obs_local holds the records of that frame.  (Last members: no other kernel's
+  // argument offsets move.)
   uint32_t walk;
   uint32_t dma_delta[4];
 };
-constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u, kWalkDma = 8u;
+constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u, kWalkDma = 8u, kWalkLaneSwap = 16u,
+                   kWalkLaneSwapCross = 32u;
 constexpr int kZrTotal = 13, kZrWalk = 14, kZrCols = 17;  // columns of tile_zr_finish's per-wave sums
 
 __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Args &f, uint32_t tile) {
@@ -481,10 +501,16 @@ __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Arg
 // between the two becomes the compiler-only fence of the solo form.
 // ZR, on_gathered: runs in the last group's iteration once its gather has RETURNED (the wave's LDS reads are retired),
 // in front of its gates: from there on nothing reads the tile, and the DMA walk issues the next tile into it.
+// ZR, lane_swap (kWalkLaneSwap; wave-uniform; 2: kWalkLaneSwapCross): the last group's targets are lane bits 4 and 5 of the group in front
+// of it.  That group's iteration then is the walk's last: nothing reads the tile behind ITS gather (on_gathered runs
+// there, a whole group earlier), it fetches no table entry (a per-lane load behind the DMA's pieces: vmcnt counts in
+// order, the wait for it would drain them), and its gate loop runs on through the last group's ops -- the op stream
+// is contiguous -- with swap_lanes_45 in front of the first of them.  No scatter, no second gather.
 template <bool KEEP, bool ZR = false, class OnLast = int, class OnGathered = int>
 __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const Tile2Args &f,
                                              const u64 QMLE_CONSTANT *mrow, int tid, bool use_skip, bool solo,
-                                             OnLast on_last = OnLast(), OnGathered on_gathered = OnGathered()) {
+                                             OnLast on_last = OnLast(), OnGathered on_gathered = OnGathered(),
+                                             int lane_swap = 0) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   const Group2 QMLE_CONSTANT *grp = as_constant(f.groups);
   if (f.n_groups <= 0) return;
@@ -531,12 +557,14 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
 #undef QMLE_LD
       }
     } else if constexpr (ZR) {
-      if (gi + 1 >= f.n_groups) r = A16{0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+      if (gi + 1 >= f.n_groups || (lane_swap != 0 && gi + 2 == f.n_groups)) r = A16{0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     }
     // (!KEEP) the 16 slot addresses are re-derived for the scatter (16 v_xor) instead of living in 16
     // VGPRs across the gates: the kernel stays within 96 VGPRs = 5 waves per SIMD
     if (!KEEP) asm volatile("" : "+v"(addr));
-    const bool more = gi + 1 < f.n_groups;
+    // (ZR) this iteration ends the tile: the last group, or -- lane_swap -- the one in front of it, which runs both
+    const bool fused = ZR && lane_swap != 0 && gi + 2 == f.n_groups;
+    const bool more = gi + 1 < f.n_groups && !fused;
     uint32_t addr_next = 0;
     if (ZR && !more) {
       // (the last group of the measuring walk is not scattered: no table entry to fetch, re-layout or not)
@@ -549,7 +577,14 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     if constexpr (ZR) {
       if (!more) on_gathered();
     }
-    for (int j = 0; j < n_ops; ++j, ++k) {
+    const int n_run = fused ? f.n_ops_stage - k : n_ops;  // (fused: the rest of the stage's stream)
+    for (int j = 0; j < n_run; ++j, ++k) {
+      if constexpr (ZR) {
+        if (fused && j == n_ops) {  // (uniform: one scalar compare per gate; both groups hold >= 1 op)
+          if (lane_swap == 2) swap_lanes_45<true>(r);
+          else swap_lanes_45<false>(r);
+        }
+      }
       // scalar loads return out of order, so only lgkmcnt(0) can cover them: touching this
       // gate's operands HERE puts that wait in front of the next prefetch instead of behind it
       asm volatile("" : "+s"(M0.m00), "+s"(M0.m01), "+s"(M0.m10), "+s"(M0.m11), "+s"(w0.y), "+s"(w1.z) :: "memory");
@@ -1067,7 +1102,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
               asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the gather has returned: the slab is dead
               dma_tile(st + f.tile_stride * sizeof(float2));
             }
-          });
+          },
+          (walk & kWalkLaneSwap) ? ((walk & kWalkLaneSwapCross) ? 2 : 1) : 0);
     } else {
       tile2_groups<WS>(sbo, addr, f, mrow, tid, a.zin_local != 0, WS && nt <= kWave);  // known zeros: Stage::zero_in
     }
@@ -1727,11 +1763,13 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
 int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
                 const float *angles, int batch, bool init_zero, int meas, void *out,
                 const uint32_t *obs_masks, int n_obs, hipStream_t stream,
-                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs, bool *by_dma) {
+                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs, bool *by_dma,
+                bool *by_lane_swap) {
   // *row_shift: TM_EXPVAL_PARTIAL rows cover 2^row_shift tiles each (multi-tile k_tile2)
   if (row_shift) *row_shift = 0;
   if (from_regs) *from_regs = false;
   if (by_dma) *by_dma = false;
+  if (by_lane_swap) *by_lane_swap = false;
   if (reuse) reuse->filled = reuse->elided = false;
   from_zero = from_zero && plan_sparse(p);
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
@@ -1985,6 +2023,14 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
           f.gtab = st.fast_gtab_dma;
           for (int k = 0; k < 4; ++k) f.dma_delta[k] = st.dma_delta[k];
           if (by_dma) *by_dma = true;
+          // ... and its last group runs where the group in front of it left the amplitudes, two lane swaps apart
+          // (Stage::lane_swap_last): the records of that frame travel in place of the table form's
+          if (st.lane_swap_last) {
+            f.walk |= kWalkLaneSwap | (st.lane_swap_cross ? kWalkLaneSwapCross : 0u);
+            static_assert(sizeof(st.zreg_swap) == sizeof(st.zreg), "one record layout");
+            std::memcpy(a.obs_local, st.zreg_swap, sizeof(st.zreg_swap));
+            if (by_lane_swap) *by_lane_swap = true;
+          }
         }
       }
     }
