@@ -155,11 +155,31 @@ def layered(n):
     return circuit, 4 * n - 1
 
 
+def watch_sweeps(monkeypatch):
+    """Wrap ``N.adjoint_gradient``: the returned list gets, per call, the ``N.Unsupported`` it raised or None.
+    ``adjoint.run_sweep`` hides a refusal of the fused plan behind the streaming sweep; this shows it."""
+    calls, inner = [], N.adjoint_gradient
+
+    def wrapped(*args, **kwargs):
+        try:
+            out = inner(*args, **kwargs)
+        except N.Unsupported as e:
+            calls.append(e)
+            raise
+        calls.append(None)
+        return out
+
+    monkeypatch.setattr(N, "adjoint_gradient", wrapped)
+    return calls
+
+
 @pytest.mark.parametrize("n", [1, 2, 4, 13, 14, 15])
-def test_vjp_equals_parameter_shift_jacobian(n):
+def test_vjp_equals_parameter_shift_jacobian(n, monkeypatch):
     """The comparison of tests/test_gpu_gradients.py for Z, with its tolerances: 4e-6 max(1, sum|cot|) where
     the whole sweep runs in LDS (n <= 13), 1e-5 max(1, sum|cot|) from 14 qubits on (n = 14: fused k_tile_adj
-    passes; n = 15: the per-gate streaming sweep, the tape has gates the fused passes do not take)."""
+    passes -- the sweep's first call is not refused; n = 15: the per-gate streaming sweep, the tape has gates the
+    fused passes do not take)."""
+    calls = watch_sweeps(monkeypatch)
     rng = np.random.default_rng(40 + n)
     circuit, n_th = (big15, 34) if n == 15 else layered(n)
     s = Script(circuit, n_qubits=n)
@@ -172,6 +192,7 @@ def test_vjp_equals_parameter_shift_jacobian(n):
     err = np.abs(g - cot @ jac).max()
     print("n", n, "max |vjp - cot @ jacobian|", err, "atol", atol)
     assert g.shape == (n_th,) and err <= atol
+    assert calls and (n != 14 or calls[0] is None), calls
 
 
 # ---- Script.vjp against an independent oracle --------------------------------------------------------------
@@ -191,7 +212,11 @@ def oracle_tape(n, th):
 
 def oracle_cost(n, th, mats, cot):
     """sum_o cot_o <psi| M_o |psi> with psi from the einsum oracle (complex128) and <M> by NumPy"""
-    psi = OE.simulate_and_measure(oracle_tape(n, th), n, "state", (), np.complex128)
+    return state_cost(OE.simulate_and_measure(oracle_tape(n, th), n, "state", (), np.complex128), n, mats, cot)
+
+
+def state_cost(psi, n, mats, cot):
+    """sum_o cot_o <psi| M_o |psi> of a complex128 state of 2^n amplitudes (tests/adjoint_reference.py shares it)"""
     t = psi.reshape((2,) * n)
     c = 0.0
     for (m, wires), w in zip(mats, cot):

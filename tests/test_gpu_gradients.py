@@ -233,10 +233,14 @@ def test_adjoint_tiny_registers_and_streaming_path(monkeypatch):
 
 @pytest.mark.parametrize("ansatz,n", [("Hardware_Efficient", 14), ("Strongly_Entangling", 15),
                                       ("Circuit_9", 14), ("Circuit_19", 16)])
-def test_fused_adjoint_tile_passes_match_parameter_shift(ansatz, n):
+def test_fused_adjoint_tile_passes_match_parameter_shift(ansatz, n, monkeypatch):
     """n >= 14: the sweep runs as fused tile passes over [psi; lambda] (k_tile_adj) -- RX/RY/RZ,
     Rot (split), CX, CZ, CRX generators and inverses inside register groups; compare with the
-    parameter-shift Jacobian for parameters, inputs and encoding weights."""
+    parameter-shift Jacobian for parameters, inputs and encoding weights.  The fused plan is not refused:
+    no sweep falls back to the streaming kernels."""
+    from tests.test_gpu_adjoint_pauli import watch_sweeps
+
+    calls = watch_sweeps(monkeypatch)
     model = Model(n_qubits=n, n_layers=1, circuit_type=ansatz)
     rng = np.random.default_rng(n)
     x = rng.uniform(0, 2 * np.pi, (2, 1))
@@ -245,3 +249,5 @@ def test_fused_adjoint_tile_passes_match_parameter_shift(ansatz, n):
         jac = np.asarray(model.gradient(inputs=x, wrt=wrt))
         vjp = np.asarray(model.gradient(inputs=x, wrt=wrt, method="adjoint", cotangent=cot))
         assert np.allclose(vjp, np.einsum("bk,bk...->b...", cot, jac), atol=1e-5), wrt
+        assert calls and calls[0] is None, (wrt, calls)
+        del calls[:]
