@@ -207,7 +207,10 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * that stream of the ops applied in unit-pivot form, and "scale_carriers", the ops that take the product of the
  * pivots in front of them (see qmle_unit_form_chain).  "mat_floats_old" is the part of the row ("mat_floats") that
  * holds one plain record per operator, as every other kernel reads it; the records of unit-form ops and carriers
- * follow it. */
+ * follow it and end at "mat_floats".  Behind them sit the product-form records of the fast groups: per stage,
+ * "product_form_groups"[g] says whether fast group g runs in product form and "product_form_records"[g] gives the
+ * float offset of its record (-1: none; see qmle_group_product_form); "mat_row_floats" is the row's stride.  A tile stage reports "group_product_form_last_run": its last launch ran those groups in
+ * product form (the fast tile kernel always does; the generic tile kernel applies the plain records). */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* Host only: the matrix builder's unit-pivot chain for `n` given 2x2 matrices u[i] = {m00, m01, m10, m11} as
  * (re, im) doubles.  The fast tile kernel applies an eligible gate as U / pivot, a matrix with a literal 1 (48
@@ -217,6 +220,16 @@ int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
  * [[1, x], [y, z]] (pivot m00, taken when |m00| >= |m01|) and form 2 = [[x, 1], [y, z]] (pivot m01); diagonal
  * {1, 0, 0, m11 / m00}.  pivots[i] = member i's pivot (re, im); carrier = P u[n-1], plain layout. */
 int qmle_unit_form_chain(const double *u, const int *diag, int n, double *records, double *pivots, double *carrier);
+/* Host only: the matrix builder's product form of one register-tile group.  The group's n (1..4) uncontrolled
+ * one-qubit operators u[i] = {m00, m01, m10, m11} as (re, im) doubles, each a scalar times a unitary, sit on the
+ * distinct in-thread bits bits[i] (0..3) of a work item's 16 amplitudes.  Each factors as
+ * g diag(1, l) [[c, -s], [s, c]] diag(1, r) with c, s >= 0; record (80 doubles): [0, 32) the opening diagonal, 16
+ * complex numbers, the product of the r over the set bits of the amplitude's index; [32 + 2 b, 34 + 2 b) the real step
+ * of bit b -- form 1 (c >= s, direct): (-t, u) with t = s / c, u = t / (1 + t^2), applied as a0 -= t a1, a1 += u a0;
+ * form 2 (c < s, mirrored): (t', 0) with t' = c / s, applied as [[t', -1], [1, t']] --; [40 + b] the form of bit b
+ * (0: no operator there); [48, 80) the closing diagonal, which carries g, l and the scales the real steps leave out.
+ * forms[i] (may be NULL) = the form of operator i. */
+int qmle_group_product_form(const double *u, const int *bits, int n, double *record, int *forms);
 /* counts: [0]=reference gates, [1]=HBM passes, [2]=whole-state-LDS(0/1),
  * [3]=tile qubits T, [4]=floats of per-sample matrices, [5]=direct passes */
 int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);

@@ -152,6 +152,8 @@ SYMBOLS = [
     ("qmle_plan_describe", _I, [_VP, C.c_char_p, _SZ]),
     ("qmle_unit_form_chain", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("qmle_group_product_form", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int)]),
     ("qmle_plan_stats", _I, [_VP, C.POINTER(C.c_int64)]),
     ("qmle_plan_autotune", _I, [_VP, _I, _I, _I, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double)]),
@@ -411,7 +413,8 @@ class Plan:
         ``wave_private_walk_last_run``, ``staging_dma_last_run``, ``last_group_lane_swap_last_run``, and
         ``chunk_loop_last_run``: ``"one_stream"``,
         ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run):
-        describe ``executed(meas)``, after the run."""
+        describe ``executed(meas)``, after the run.  Every tile stage carries ``group_product_form_last_run``: its
+        last launch ran the groups that ``product_form_groups`` marks in product form."""
         L = lib()
         need = L.qmle_plan_describe(self._h, None, 0)
         buf = C.create_string_buffer(need + 1)

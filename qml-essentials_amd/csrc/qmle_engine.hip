@@ -39,6 +39,22 @@ k_build_matrices_map(const BuildOp *__restrict__ build, const BuildGroup *__rest
                                                               mat_floats, batch);
 }
 
+// the product-form records of the fast groups (build_matrices_body<.., PRODUCT>): `groups` = those items only
+template <bool GMAJOR>
+__global__ void __launch_bounds__(64)
+k_build_matrices_product(const BuildOp *__restrict__ build, const BuildGroup *__restrict__ groups, int n_groups,
+                const float *__restrict__ angles, int n_slots, const float *__restrict__ consts,
+                float *__restrict__ mats, uint32_t mat_floats, int batch) {
+  build_matrices_body<const float *, float, float, GMAJOR, true>(build, groups, n_groups, angles, n_slots, consts, mats, mat_floats, batch);
+}
+__global__ void __launch_bounds__(64)
+k_build_matrices_product_map(const BuildOp *__restrict__ build, const BuildGroup *__restrict__ groups, int n_groups,
+                    const AngleMapSrc map, int n_slots, const float *__restrict__ consts,
+                    float *__restrict__ mats, uint32_t mat_floats, int batch) {
+  build_matrices_body<const AngleMapSrc &, float, float, true, true>(build, groups, n_groups, map, n_slots, consts, mats,
+                                                                    mat_floats, batch);
+}
+
 // ---------------------------------------------------------------------------
 // angle table from device-resident leaves:  table[b][s] = c[s] + sum_t coef[t] * leaf_{arg[t]}[row][idx[t]]
 // (gate angles are affine in params / inputs, ansaetze.py:323-371, model.py:804-816); the row
@@ -148,21 +164,40 @@ int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_ma
                           bool forward_only) {
   const int ng = forward_only ? p->n_groups_needed : (int)p->groups.size();
   if (ng <= 0) return QMLE_OK;
+  // the product-form records of the fast groups: the last needed items, in a kernel of their own (the common
+  // builder passes over them)
+  const int npg = p->n_product_groups, pg0 = p->n_groups_needed - npg;
+  const int ngc = forward_only ? pg0 : ng;  // items the common builder has work in
   if (tls_angle_map && batch >= 64) {
-    const uint64_t waves = (uint64_t)ng * (((uint64_t)batch + 63) / 64);
-    hipLaunchKernelGGL(k_build_matrices_map, dim3(grid_for(waves * 64, 64)), dim3(64), 0, stream, p->dev.d_build,
-                       p->dev.d_groups, ng, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+    const uint64_t per = ((uint64_t)batch + 63) / 64;
+    if (ngc > 0)
+      hipLaunchKernelGGL(k_build_matrices_map, dim3(grid_for((uint64_t)ngc * per * 64, 64)), dim3(64), 0, stream, p->dev.d_build,
+                         p->dev.d_groups, ngc, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+    if (npg > 0)
+      hipLaunchKernelGGL(k_build_matrices_product_map, dim3(grid_for((uint64_t)npg * per * 64, 64)), dim3(64), 0, stream, p->dev.d_build,
+                         p->dev.d_groups + pg0, npg, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
+  if (npg > 0) {
+    const uint64_t pitems = batch >= 64 ? (uint64_t)npg * (((uint64_t)batch + 63) / 64) * 64 : (uint64_t)batch * (uint64_t)npg;
+    if (batch >= 64)
+      hipLaunchKernelGGL(k_build_matrices_product<true>, dim3(grid_for(pitems, 64)), dim3(64), 0, stream, p->dev.d_build,
+                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+    else
+      hipLaunchKernelGGL(k_build_matrices_product<false>, dim3(grid_for(pitems, 64)), dim3(64), 0, stream, p->dev.d_build,
+                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+    HIPCHK(hipGetLastError());
+    if (ngc <= 0) return QMLE_OK;
+  }
   // one work item per (sample, group); from 64 samples on, whole waves per group (build_matrices_body)
-  const uint64_t items = batch >= 64 ? (uint64_t)ng * (((uint64_t)batch + 63) / 64) * 64 : (uint64_t)batch * (uint64_t)ng;
+  const uint64_t items = batch >= 64 ? (uint64_t)ngc * (((uint64_t)batch + 63) / 64) * 64 : (uint64_t)batch * (uint64_t)ngc;
   if (batch >= 64)
     hipLaunchKernelGGL(k_build_matrices<true>, dim3(grid_for(items, 64)), dim3(64), 0, stream, p->dev.d_build,
-                       p->dev.d_groups, ng, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+                       p->dev.d_groups, ngc, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
   else
     hipLaunchKernelGGL(k_build_matrices<false>, dim3(grid_for(items, 64)), dim3(64), 0, stream, p->dev.d_build,
-                       p->dev.d_groups, ng, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+                       p->dev.d_groups, ngc, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
@@ -337,6 +372,22 @@ int qmle_unit_form_chain(const double *u, const int *diag, int n, double *record
       pivots[2 * i + 1] = piv.im;
     }
   }
+  return QMLE_OK;
+}
+
+// the matrix builder's product form of a group (product_form_group, qmle_matrices.h) on the host: n <= 4 matrices
+// (8 doubles each, row-major re / im) on the distinct in-thread bits `bits`; record: kProductRecFloats doubles
+int qmle_group_product_form(const double *u, const int *bits, int n, double *record, int *forms) {
+  if (!u || !bits || !record || n < 1 || n > 4) return QMLE_ERR_INVALID_ARG;
+  M2 m[4];
+  unsigned seen = 0;
+  for (int i = 0; i < n; ++i) {
+    if (bits[i] < 0 || bits[i] > 3 || (seen & (1u << bits[i]))) return QMLE_ERR_INVALID_ARG;
+    seen |= 1u << bits[i];
+    const double *x = u + 8 * (size_t)i;
+    m[i] = {{x[0], x[1]}, {x[2], x[3]}, {x[4], x[5]}, {x[6], x[7]}};
+  }
+  product_form_group(m, bits, n, record, forms);
   return QMLE_OK;
 }
 
@@ -1018,7 +1069,9 @@ static void adopt_schedule(qmle_plan *dst, qmle_plan *src) {
   dst->cand_ranking.swap(src->cand_ranking);
   std::swap(dst->mat_floats, src->mat_floats);
   std::swap(dst->mat_floats_old, src->mat_floats_old);
+  std::swap(dst->mat_floats_unit, src->mat_floats_unit);
   std::swap(dst->n_groups_needed, src->n_groups_needed);
+  std::swap(dst->n_product_groups, src->n_product_groups);
   std::swap(dst->fold_groups, src->fold_groups);
   std::swap(dst->model_cost, src->model_cost);
   std::swap(dst->chosen_candidate, src->chosen_candidate);

@@ -79,9 +79,18 @@ struct BuildGroup {
   uint32_t mat_off;
   uint32_t dim;  // 2 or 4; kBuildChain
 };
-constexpr uint32_t kBuildChain = 1;
+// dim = kBuildProduct: the product-form record of one Group2 (assign_product_forms; qmle_matrices.h, product_form_group).
+// [begin, end) holds the source gates of the group's members in stream order, each closed by a marker as in a chain:
+// pad = what the op's ops2 record holds (ChainMember; CM_PLAIN: the operator itself), const_off = the member's
+// in-thread bit -- or -1 for a unit-form member of the carrier's chain that sits in an earlier group: its pivot enters
+// P, nothing else.  mat_off = float offset of the record (kProductRecFloats floats) in the matrix row.
+constexpr uint32_t kBuildChain = 1, kBuildProduct = 3;
 constexpr uint16_t kChainMark = 0xffffu;
-enum ChainMember : uint16_t { CM_UNIT_DENSE = 0, CM_UNIT_DIAG = 1, CM_CARRIER = 2 };
+enum ChainMember : uint16_t { CM_UNIT_DENSE = 0, CM_UNIT_DIAG = 1, CM_CARRIER = 2, CM_PLAIN = 3 };
+// Product-form record, in floats: [0, 32) the opening diagonal (16 complex, entry 0 = 1), [32, 40) per in-thread bit
+// the pair (-t, u) of the direct real step or (t', 0) of the mirrored one, [40, 44) per in-thread bit the form word --
+// the float 0 (no member on that bit), 1 (direct) or 2 (mirrored) --, [48, 80) the closing diagonal (16 complex).
+constexpr uint32_t kProductRecFloats = 80, kProductRecSteps = 32, kProductRecForms = 40, kProductRecClose = 48;
 constexpr int kMaxChainUnits = 32;  // unit-form ops per chain: |1 / pivot| <= sqrt 2, so a state is scaled by <= 2^16
 
 // ---- fast tile path (k_tile2) ---------------------------------------------------------------
@@ -110,12 +119,17 @@ struct Group2 {
   uint16_t n_ops;
   uint8_t relayout;
   uint8_t sync;        // bit 0: the measuring walk needs a workgroup barrier in front of this group's gather (Stage::fast_info)
+                       // bit 1 (kGroupProduct): the group runs in product form, its record at prod_off
+                       // bit 2 (kGroupProductLow1): ... and no member sits on in-thread bit 0 or 1 (opening entries 0..3 are 1)
   uint32_t tbl;        // index into qmle_plan::tbl2 (one uint32 per thread of the workgroup)
   uint32_t tbl_out;    // relayout: scatter table
   uint32_t off[16];
   uint32_t off_out[16];
+  uint32_t prod_off;   // product form: float offset of the group's record in the matrix row (behind qmle_plan::mat_floats_unit)
+  uint32_t pad[3];
 };
-static_assert(sizeof(Group2) == 144, "Group2 layout");
+static_assert(sizeof(Group2) == 160, "Group2 layout");
+constexpr uint8_t kGroupProduct = 2, kGroupProductLow1 = 4;
 
 enum StageKind : int { ST_DIRECT = 0, ST_TILE = 1, ST_DIAG_ALL = 2 };
 
@@ -203,6 +217,9 @@ struct Stage {
   // report only (describe_plan): indices into the stage's ops2 stream of the ops that run in unit-pivot form and of
   // the carriers that take their chains' pivots (assign_unit_forms)
   std::vector<int> unit_form_ops, scale_carriers;
+  // report only: the last launch of this stage ran its product-form groups (every k_tile2 launch does; k_tile and the
+  // other readers of dev_ops apply the plain records).  Written by launch_tile.
+  mutable bool product_form_last_run = false;
 };
 // A stage's lane offsets as runs: local bits 0 .. top -> global positions, contiguous stretches (off, mask, pos).
 // Returns their number, or -1 when there are more than four (k_tile2 then reads the offsets from its table).
@@ -261,8 +278,11 @@ struct qmle_plan {
   std::vector<qmle::BuildOp> build_ops;
   std::vector<qmle::BuildGroup> groups;   // needed-first: [0, n_groups_needed) are read by the forward tile / direct kernels
   int n_groups_needed = 0;
+  int n_product_groups = 0;               // ... the last of which build product-form records (kBuildProduct; a kernel of their own)
   std::vector<qmle::Stage> stages;
-  uint32_t mat_floats = 0;                // per-sample matrix row length
+  uint32_t mat_floats = 0;                // per-sample matrix row length (the stride of the rows)
+  uint32_t mat_floats_unit = 0;           // ... end of the unit-form records (describe_plan's "mat_floats"); the product-form
+                                          // records of Group2 groups follow (assign_product_forms)
   uint32_t mat_floats_old = 0;            // ... of which the plain records, one per lowered operator (a function of the
                                           // tape and the flags alone); the unit-form records of ops2 follow
   int fold_groups = 0;                    // most gate groups of any Stage::product_ok stage

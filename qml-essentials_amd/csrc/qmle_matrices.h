@@ -60,6 +60,103 @@ __host__ __device__ __forceinline__ cd unit_chain_step(const M2 &U, int member, 
   P = cdmul(P, piv);
   return piv;
 }
+// the operator a chain member's ops2 record applies: U / pivot (unit forms; the pivot enters P), P U (the carrier; P
+// starts again at 1), U (CM_PLAIN) -- the arithmetic of unit_chain_step, without the record
+__host__ __device__ __forceinline__ M2 unit_chain_operator(const M2 &U, int member, cd &P) {
+  if (member == CM_CARRIER) {
+    const M2 R = {cdmul(P, U.a), cdmul(P, U.b), cdmul(P, U.c), cdmul(P, U.d)};
+    P = {1.0, 0.0};
+    return R;
+  }
+  if (member == CM_PLAIN) return U;
+  cd piv = U.a;
+  if (member == CM_UNIT_DENSE && !(U.a.re * U.a.re + U.a.im * U.a.im >= U.b.re * U.b.re + U.b.im * U.b.im)) piv = U.b;
+  P = cdmul(P, piv);
+  return {cddiv(U.a, piv), cddiv(U.b, piv), cddiv(U.c, piv), cddiv(U.d, piv)};
+}
+
+// ---------------------------------------------------------------------------
+// product form of a group (k_tile2's product_group).  A 2x2 matrix that is a scalar times a unitary is
+//   M = g diag(1, l) [[c, -s], [s, c]] diag(1, r),   c = |m00| / |g|, s = |m10| / |g| >= 0, |g|^2 = |m00|^2 + |m10|^2,
+// l, r and g / |g| unit phases (moduli and divisions only).  Where s = 0 the phase is split as r = 1, l = m11 / g;
+// where c = 0 as l = 1, g = m10 / s.  The real middle step runs without its scale:
+//   c >= s (form 1, direct)    t = s / c:  a0 -= t a1;  a1 += u a0,  u = t / (1 + t^2)  -- leaves
+//                              diag(1, 1 / (1 + t^2)) [[1, -t], [t, 1]] (a0, a1); the record holds (-t, u) and the
+//                              closing factors are g c and g l c (1 + t^2)
+//   c <  s (form 2, mirrored)  t' = c / s: [[t', -1], [1, t']]; the record holds (t', 0), closing factors g s and g l s
+// Over the n <= 4 members of a group, on distinct in-thread bits: opening entry e = product of r_q over the members
+// whose bit is set in e, closing entry e = product of the members' factor for their bit of e.  fp64 throughout, rounded
+// once on the store; layout: kProductRec* (qmle_internal.h).  forms (optional): the form of each member.
+// ---------------------------------------------------------------------------
+template <class OT>
+__host__ __device__ inline void product_form_group(const M2 *m, const int *bit, int n, OT *out, int *forms = nullptr) {
+  cd open[16], close[16];
+  for (int e = 0; e < 16; ++e) open[e] = close[e] = {1.0, 0.0};
+  for (uint32_t i = kProductRecSteps; i < kProductRecClose; ++i) out[i] = (OT)0;
+  for (int q = 0; q < n; ++q) {
+    const M2 &M = m[q];
+    const double n00 = M.a.re * M.a.re + M.a.im * M.a.im, n10 = M.c.re * M.c.re + M.c.im * M.c.im;
+    const double N = sqrt(n00 + n10), c = sqrt(n00) / N, s = sqrt(n10) / N;
+    const bool direct = c >= s;
+    cd g, l, r;
+    if (direct) {
+      g = {M.a.re / c, M.a.im / c};
+      if (s > 0.0) {
+        const cd gs = {g.re * s, g.im * s};
+        l = cddiv(M.c, gs);
+        r = cddiv({-M.b.re, -M.b.im}, gs);
+      } else {
+        l = cddiv(M.d, g);
+        r = {1.0, 0.0};
+      }
+    } else {
+      const cd h = {M.c.re / s, M.c.im / s};  // g l
+      if (c > 0.0) {
+        g = {M.a.re / c, M.a.im / c};
+        l = cddiv(h, g);
+      } else {
+        g = h;
+        l = {1.0, 0.0};
+      }
+      r = cddiv({-M.b.re, -M.b.im}, {g.re * s, g.im * s});
+    }
+    const cd gl = cdmul(g, l);
+    cd lo, hi;
+    double w0, w1;
+    if (direct) {
+      const double t = s / c;
+      w0 = -t;
+      w1 = t / (1.0 + t * t);
+      lo = {g.re * c, g.im * c};
+      hi = {gl.re * (c * (1.0 + t * t)), gl.im * (c * (1.0 + t * t))};
+    } else {
+      w0 = c / s;
+      w1 = 0.0;
+      lo = {g.re * s, g.im * s};
+      hi = {gl.re * s, gl.im * s};
+    }
+    const int b = bit[q];
+    out[kProductRecSteps + 2 * b] = (OT)w0;
+    out[kProductRecSteps + 2 * b + 1] = (OT)w1;
+    out[kProductRecForms + b] = (OT)(direct ? 1 : 2);
+    if (forms) forms[q] = direct ? 1 : 2;
+    for (int e = 0; e < 16; ++e) {
+      if ((e >> b) & 1) {
+        open[e] = cdmul(open[e], r);
+        close[e] = cdmul(close[e], hi);
+      } else {
+        close[e] = cdmul(close[e], lo);
+      }
+    }
+  }
+  for (int e = 0; e < 16; ++e) {
+    out[2 * e] = (OT)open[e].re;
+    out[2 * e + 1] = (OT)open[e].im;
+    out[kProductRecClose + 2 * e] = (OT)close[e].re;
+    out[kProductRecClose + 2 * e + 1] = (OT)close[e].im;
+  }
+}
+
 // the 2x2 source gates of source_matrix(), entries in registers
 // ANG: anything indexable by slot -- a row of the angle table (`const float *` / `const double *`) or an
 // AngleMapRow that forms the angle from the leaves on the fly (same arithmetic as k_build_angles)
@@ -221,7 +318,10 @@ __device__ __forceinline__ AngleMapRow angle_row(const AngleMapSrc &m, int b, in
 // GMAJOR: whole waves per group (launch side: batch >= 64, blocks of one wave) -- the group index is then
 // provably wave-uniform and the descriptors come through the scalar cache
 // ASRC: `const AT *` (the angle table) or `const AngleMapSrc &`
-template <class ASRC, class CT, class OT, bool GMAJOR = false>
+// PRODUCT: the launch builds the product-form records of the fast groups (BuildGroup::dim = kBuildProduct, the
+// n_product_groups last needed items) and nothing else; every other launch leaves those items out -- a kernel of their
+// own, so that the 32 fp64 complex numbers of the two diagonals do not set the register count of the common builder
+template <class ASRC, class CT, class OT, bool GMAJOR = false, bool PRODUCT = false>
 __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ build,
                                                     const BuildGroup *__restrict__ groups, int n_groups,
                                                     ASRC angles, int n_slots,
@@ -272,6 +372,38 @@ __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ 
       const cd c = cdadd(cdmul(S.c, M.a), cdmul(S.d, M.c)), d = cdadd(cdmul(S.c, M.b), cdmul(S.d, M.d));
       M = {a, bb, c, d};
     }
+    return;
+  }
+  if ((grp.dim == kBuildProduct) != PRODUCT) return;
+  if constexpr (PRODUCT) {
+    // one work item per (sample, product-form group): the members' fused 2x2 in stream order, turned into the operator
+    // their ops2 record applies (the chain's P walks along), then the group's record
+    cd P = {1.0, 0.0};
+    M2 M = {{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}, mem[4];
+    int bit[4], n_mem = 0;
+    bool first = true;
+    for (uint32_t k = grp.begin; k < grp.end; ++k) {
+      const BuildOp bo = build[k];
+      if (bo.opcode == kChainMark) {
+        const M2 E = unit_chain_operator(M, (int)bo.pad, P);
+        if (bo.const_off >= 0 && n_mem < 4) {
+          mem[n_mem] = E;
+          bit[n_mem++] = bo.const_off;
+        }
+        first = true;
+        continue;
+      }
+      const M2 S = source_2x2(bo, ang, consts);  // later gate on the left: M <- S M
+      if (first) {
+        M = S;
+        first = false;
+        continue;
+      }
+      const cd a = cdadd(cdmul(S.a, M.a), cdmul(S.b, M.c)), bb = cdadd(cdmul(S.a, M.b), cdmul(S.b, M.d));
+      const cd c = cdadd(cdmul(S.c, M.a), cdmul(S.d, M.c)), d = cdadd(cdmul(S.c, M.b), cdmul(S.d, M.d));
+      M = {a, bb, c, d};
+    }
+    product_form_group(mem, bit, n_mem, mats + (size_t)b * mat_floats + grp.mat_off);
     return;
   }
   if (dim == 2) {

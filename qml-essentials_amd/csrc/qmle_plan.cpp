@@ -682,7 +682,17 @@ static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured) {
 // The records of unit-form ops and carriers are APPENDED to the matrix row (ops2[].mat_off; one build item per chain,
 // BuildGroup::dim = kBuildChain); the plain records stay where every other reader finds them -- k_tile, k_direct_1q,
 // k_reg_measure*, the product kernels, the adjoint sweep and the complex128 engine read dev_ops / lowered.
-static void assign_unit_forms(qmle_plan *p) {
+// what assign_product_forms needs to know about the ops of ops2: the 2x2 build group an eligible op's matrix comes from
+// (-1: not eligible), what its ops2 record holds (ChainMember) and, for a carrier, the unit-form members of its chain
+struct FastOpForms {
+  std::vector<int> src_group;
+  std::vector<uint16_t> role;
+  std::vector<std::vector<int>> chain_units;  // per ops2 index of a carrier (empty elsewhere)
+};
+static void assign_unit_forms(qmle_plan *p, FastOpForms &forms) {
+  forms.src_group.assign(p->ops2.size(), -1);
+  forms.role.assign(p->ops2.size(), (uint16_t)CM_PLAIN);
+  forms.chain_units.assign(p->ops2.size(), {});
   p->mat_floats_old = p->mat_floats;
   std::vector<int> group_at(p->mat_floats / 8 + 1, -1);  // plain record -> its 2x2 build group
   for (size_t g = 0; g < p->groups.size(); ++g)
@@ -712,6 +722,7 @@ static void assign_unit_forms(qmle_plan *p) {
     std::vector<char> elig(n_ops, 0);
     for (uint32_t i = 0; i < n_ops; ++i) {
       elig[i] = eligible(p->ops2[ob + i]) ? 1 : 0;
+      if (elig[i]) forms.src_group[ob + i] = group_at[p->ops2[ob + i].mat_off / 8];
       if (elig[i] && p->ops2[ob + i].pad < FC_CDENSE) last_dense = (int)i;
     }
     for (int i = 0; i <= last_dense; ++i) n_elig += elig[i];
@@ -737,8 +748,10 @@ static void assign_unit_forms(qmle_plan *p) {
         p->build_ops.push_back(mark);
         o.mat_off = p->mat_floats;
         p->mat_floats += 8;
+        forms.role[ob + chain[m]] = mark.pad;
         if (is_carrier) {
           st.scale_carriers.push_back(chain[m]);
+          for (size_t u = 0; u + 1 < chain.size(); ++u) forms.chain_units[ob + chain[m]].push_back((int)ob + chain[u]);
         } else {
           o.pad = (uint8_t)((diag ? FC_UDIAG : FC_UDENSE) + o.t0);
           st.unit_form_ops.push_back(chain[m]);
@@ -755,6 +768,62 @@ static void assign_unit_forms(qmle_plan *p) {
       else if ((int)chain.size() < kMaxChainUnits) chain.push_back(i);
       else if (dense) close_chain(i);
       // (else: a diagonal op behind a full chain stays plain)
+    }
+  }
+}
+
+// ---- product form of a Group2 ----------------------------------------------------------
+// The uncontrolled one-qubit operators of a group sit on distinct in-thread bits and commute: the group applies their
+// tensor product.  Each factors as M = g diag(1, l) [[c, -s], [s, c]] diag(1, r) with c, s >= 0 real and l, r, g / |g|
+// unit phases; the right factors of the group multiply into one opening diagonal over the 16 amplitudes, the left
+// factors and every scale into one closing diagonal, and what stays per gate is a REAL step, in which one packed FMA
+// handles both halves of a complex amplitude: 16 packed instructions (c >= s) or 24 (c < s) where the unit-pivot form
+// takes 48 (product_form_group, qmle_matrices.h; the kernel side: product_group, qmle_tile.hip).
+// A group qualifies when it holds >= 2 ops, every one of them eligible for assign_unit_forms (plain, unit-form or
+// carrier), no two on one bit.  Its record is APPENDED behind the unit-form records (Group2::prod_off); it factors the
+// operators the ops2 records hold -- U / pivot, P U, U -- so that product-form and ordinary groups mix inside a stage
+// and a chain's scaling stays what it was.  The ops2 records themselves stay: qmle_plan::mat_floats_unit is where they
+// end, mat_floats the stride of the row.
+static void assign_product_forms(qmle_plan *p, const FastOpForms &forms) {
+  p->mat_floats_unit = p->mat_floats;
+  for (Stage &st : p->stages) {
+    if (st.kind != ST_TILE || !st.fast_ok) continue;
+    for (int gi = st.fast_begin; gi < st.fast_end; ++gi) {
+      Group2 &g = p->groups2[gi];
+      if (g.n_ops < 2) continue;
+      uint32_t bits = 0;
+      bool ok = true;
+      for (uint32_t i = g.op_begin; i < g.op_begin + g.n_ops && ok; ++i) {
+        const LoweredOp &o = p->ops2[i];
+        ok = forms.src_group[i] >= 0 && o.t0 >= 0 && o.t0 < 4 && !(bits & (1u << o.t0));
+        if (ok) bits |= 1u << o.t0;
+      }
+      if (!ok) continue;
+      BuildGroup bg{(uint32_t)p->build_ops.size(), 0, p->mat_floats, kBuildProduct};
+      auto member = [&](int i, int bit) {
+        const BuildGroup src = p->groups[forms.src_group[i]];
+        for (uint32_t k = src.begin; k < src.end; ++k) {
+          const BuildOp b = p->build_ops[k];
+          p->build_ops.push_back(b);
+        }
+        BuildOp mark{};
+        mark.opcode = kChainMark;
+        mark.pad = forms.role[i];
+        mark.slot[0] = mark.slot[1] = mark.slot[2] = -1;
+        mark.const_off = bit;
+        p->build_ops.push_back(mark);
+      };
+      for (uint32_t i = g.op_begin; i < g.op_begin + g.n_ops; ++i) {
+        // (a carrier's P: the pivots of its chain's members in earlier groups, then of those in this one)
+        for (int u : forms.chain_units[i])
+          if ((uint32_t)u < g.op_begin) member(u, -1);
+        member((int)i, (int)p->ops2[i].t0);
+      }
+      bg.end = (uint32_t)p->build_ops.size();
+      p->groups.push_back(bg);
+      g.prod_off = p->mat_floats;
+      g.sync |= kGroupProduct | ((bits & 3u) ? 0 : kGroupProductLow1);
+      p->mat_floats += kProductRecFloats;
     }
   }
 }
@@ -1486,7 +1555,11 @@ int compile_plan(qmle_plan *p) {
     p->chosen_candidate = best;
   }
   p->model_cost = cost();
-  assign_unit_forms(p);
+  {
+    FastOpForms forms;
+    assign_unit_forms(p, forms);
+    assign_product_forms(p, forms);
+  }
   // ---- matrices no forward kernel reads --------------------------------------------------------
   // An X / CX inside a register-tile group is a swap of amplitudes (reg_dispatch<2>, f_x / f_cx) or a
   // change of the LDS layout map (build_fast_groups); its 2x2 matrix is never read by a tile pass.  The
@@ -1506,8 +1579,11 @@ int compile_plan(qmle_plan *p) {
     std::stable_partition(p->groups.begin(), p->groups.end(),
                           [&](const BuildGroup &g) { return !(g.dim == 2 && unread[g.mat_off]); });
     p->n_groups_needed = 0;
-    for (const BuildGroup &g : p->groups)
+    p->n_product_groups = 0;
+    for (const BuildGroup &g : p->groups) {
       if (!(g.dim == 2 && unread[g.mat_off])) ++p->n_groups_needed;
+      if (g.dim == kBuildProduct) ++p->n_product_groups;  // (appended last, and needed: they close the needed range)
+    }
   }
   return QMLE_OK;
 }
@@ -1650,7 +1726,8 @@ std::string describe_plan(const qmle_plan *p) {
      << ",\"model_cost\":" << p->model_cost << ",\"candidate\":" << p->chosen_candidate
      << ",\"autotuned\":" << (p->autotuned ? "true" : "false")
      << ",\"zero_run\":" << ((p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) ? "true" : "false") << ",\"tile_bits\":" << p->tile_T << ",\"low_bits\":" << p->tile_L
-     << ",\"mat_floats\":" << p->mat_floats << ",\"mat_floats_old\":" << p->mat_floats_old
+     << ",\"mat_floats\":" << p->mat_floats_unit << ",\"mat_floats_old\":" << p->mat_floats_old
+     << ",\"mat_row_floats\":" << p->mat_floats
      << ",\"build_groups\":" << p->groups.size() << ",\"build_groups_needed\":" << p->n_groups_needed
      << ",\"algo_bytes_per_state\":" << p->algo_bytes_per_state
      << ",\"flops_per_state\":" << plan_flops_per_state(p) << ",\"stages\":[";
@@ -1778,7 +1855,15 @@ std::string describe_plan(const qmle_plan *p) {
           for (int j = 0; j < (int)p->groups2[g].n_ops; ++j, ++k, any = true)
             os << (any ? "," : "") << "[" << (int)p->ops2[k].pad << "," << p->ops2[k].mat_off << "]";
       }
-      os << "]";
+      // per fast group (the entries of "fast_groups" stay what they were): whether it runs in product form
+      // (assign_product_forms) and the float offset of its record in the matrix row (-1: none)
+      os << "],\"product_form_groups\":[";
+      for (int g = st.fast_begin; g < st.fast_end; ++g)
+        os << (g > st.fast_begin ? "," : "") << ((p->groups2[g].sync & kGroupProduct) ? "true" : "false");
+      os << "],\"product_form_records\":[";
+      for (int g = st.fast_begin; g < st.fast_end; ++g)
+        os << (g > st.fast_begin ? "," : "") << ((p->groups2[g].sync & kGroupProduct) ? (long long)p->groups2[g].prod_off : -1ll);
+      os << "],\"group_product_form_last_run\":" << (st.product_form_last_run ? "true" : "false");
     }
     if (s + 1 == p->stages.size())
       os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run

@@ -415,6 +415,139 @@ __device__ __forceinline__ void fast_dispatch(A16 &a, int code, const Mat2S &M) 
 #undef QMLE_C12
 }
 
+// ---- product form of a group (the record: product_form_group, qmle_matrices.h) ----
+// four (three) amplitudes times four (three) different complex numbers, 8 (6) SGPRs
+#define QMLE_CMUL4D(a0, a1, a2, a3, m0, m1, m2, m3)                                              \
+  asm volatile(                                                                                  \
+      "v_pk_mul_f32 %4, %8, %0 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_mul_f32 %5, %9, %1 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_mul_f32 %6, %10, %2 op_sel_hi:[0,1]\n\t"                                             \
+      "v_pk_mul_f32 %7, %11, %3 op_sel_hi:[0,1]\n\t"                                             \
+      "v_pk_fma_f32 %0, %8, %0, %4 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %1, %9, %1, %5 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %2, %10, %2, %6 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"         \
+      "v_pk_fma_f32 %3, %11, %3, %7 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"         \
+      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)       \
+      : "s"(m0), "s"(m1), "s"(m2), "s"(m3))
+#define QMLE_CMUL3D(a0, a1, a2, m0, m1, m2)                                                      \
+  asm volatile(                                                                                  \
+      "v_pk_mul_f32 %3, %6, %0 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_mul_f32 %4, %7, %1 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_mul_f32 %5, %8, %2 op_sel_hi:[0,1]\n\t"                                              \
+      "v_pk_fma_f32 %0, %6, %0, %3 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %1, %7, %1, %4 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      "v_pk_fma_f32 %2, %8, %2, %5 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]\n\t"          \
+      : "+v"(a0), "+v"(a1), "+v"(a2), "=&v"(t0), "=&v"(t1), "=&v"(t2)                            \
+      : "s"(m0), "s"(m1), "s"(m2))
+// The real step of in-thread bit TB, direct form: a0 -= t a1, then a1 += u a0, on the 8 pairs; tu = (-t, u).  One
+// packed FMA works on (re, im) at once; the second FMA of a pair sits 8 instructions behind the first.
+template <int TB>
+__device__ __forceinline__ void f_shear(A16 &a, u64 tu) {
+  constexpr int S = 1 << TB;
+#define QMLE_P(q) "+v"(at<pair_idx<TB>(q)>(a)), "+v"(at<pair_idx<TB>(q) | S>(a))
+  asm volatile(
+      "v_pk_fma_f32 %0, %16, %1, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %2, %16, %3, %2 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %4, %16, %5, %4 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %6, %16, %7, %6 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %8, %16, %9, %8 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %10, %16, %11, %10 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %12, %16, %13, %12 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %14, %16, %15, %14 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %16, %0, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %3, %16, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %5, %16, %4, %5 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %7, %16, %6, %7 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %9, %16, %8, %9 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %11, %16, %10, %11 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %13, %16, %12, %13 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %15, %16, %14, %15 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      : QMLE_P(0), QMLE_P(1), QMLE_P(2), QMLE_P(3), QMLE_P(4), QMLE_P(5), QMLE_P(6), QMLE_P(7)
+      : "s"(tu));
+#undef QMLE_P
+}
+// ... mirrored form: (a0, a1) <- (t' a0 - a1, a0 + t' a1); tu = (t', 0).  A copy and two FMAs per pair, four pairs
+// per statement.  (The in-place two-shear form would divide by t': both diagonal entries are small here.)
+#define QMLE_MIRROR4(a0, a1, a2, a3, a4, a5, a6, a7)                                             \
+  asm volatile(                                                                                  \
+      "v_mov_b64 %8, %0\n\t"                                                                     \
+      "v_mov_b64 %9, %2\n\t"                                                                     \
+      "v_mov_b64 %10, %4\n\t"                                                                    \
+      "v_mov_b64 %11, %6\n\t"                                                                    \
+      "v_pk_fma_f32 %0, %12, %0, %1 op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"         \
+      "v_pk_fma_f32 %2, %12, %2, %3 op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"         \
+      "v_pk_fma_f32 %4, %12, %4, %5 op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"         \
+      "v_pk_fma_f32 %6, %12, %6, %7 op_sel_hi:[0,1,1] neg_lo:[0,0,1] neg_hi:[0,0,1]\n\t"         \
+      "v_pk_fma_f32 %1, %12, %1, %8 op_sel_hi:[0,1,1]\n\t"                                       \
+      "v_pk_fma_f32 %3, %12, %3, %9 op_sel_hi:[0,1,1]\n\t"                                       \
+      "v_pk_fma_f32 %5, %12, %5, %10 op_sel_hi:[0,1,1]\n\t"                                      \
+      "v_pk_fma_f32 %7, %12, %7, %11 op_sel_hi:[0,1,1]\n\t"                                      \
+      : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7),          \
+        "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3)                                               \
+      : "s"(tu))
+template <int TB>
+__device__ __forceinline__ void f_mirror(A16 &a, u64 tu) {
+  u64 t0, t1, t2, t3;
+  constexpr int S = 1 << TB;
+#define QMLE_P(q) at<pair_idx<TB>(q)>(a), at<pair_idx<TB>(q) | S>(a)
+#define QMLE_MIRROR4X(...) QMLE_MIRROR4(__VA_ARGS__)
+  QMLE_MIRROR4X(QMLE_P(0), QMLE_P(1), QMLE_P(2), QMLE_P(3));
+  QMLE_MIRROR4X(QMLE_P(4), QMLE_P(5), QMLE_P(6), QMLE_P(7));
+#undef QMLE_MIRROR4X
+#undef QMLE_P
+}
+// the form word of a bit (the float 0, 1 or 2; per state, so wave-uniform: a scalar compare and branch)
+template <int TB>
+__device__ __forceinline__ void f_real_step(A16 &a, uint32_t form, u64 tu) {
+  if (form == 0x3f800000u) f_shear<TB>(a, tu);
+  else if (form == 0x40000000u) f_mirror<TB>(a, tu);
+}
+// One product-form group on the 16 amplitudes of a work item, straight-line: opening diagonal (entry 0 is a literal
+// 1: 30 packed instructions; low1 -- no member on in-thread bit 0 or 1 -- entries 0..3 are: 24), one real step per
+// member (16 or 24), closing diagonal (32).  The record streams through SGPRs 4 entries at a time, two loads ahead of
+// the one being consumed; touching a load's registers puts the wait for it in front of the next load's issue, as in
+// the gate loop of tile2_groups.
+__device__ __forceinline__ void product_group(A16 &a, const u64 QMLE_CONSTANT *rec, bool low1) {
+  u64 t0, t1, t2, t3;
+#define QMLE_LD4(x, i) u64 x##0 = rec[i], x##1 = rec[(i) + 1], x##2 = rec[(i) + 2], x##3 = rec[(i) + 3]
+#define QMLE_IN4(x) asm volatile("" : "+s"(x##0), "+s"(x##1), "+s"(x##2), "+s"(x##3)::"memory")
+  constexpr int kSteps = kProductRecSteps / 2, kForms = kProductRecForms / 2, kClose = kProductRecClose / 2;
+  QMLE_LD4(oa, 0);
+  QMLE_LD4(ob, 4);
+  QMLE_IN4(oa);
+  QMLE_LD4(oc, 8);
+  if (!low1) QMLE_CMUL3D(a.v1, a.v2, a.v3, oa1, oa2, oa3);
+  QMLE_IN4(ob);
+  QMLE_LD4(od, 12);
+  QMLE_CMUL4D(a.v4, a.v5, a.v6, a.v7, ob0, ob1, ob2, ob3);
+  QMLE_IN4(oc);
+  QMLE_LD4(st, kSteps);
+  u64 f01 = rec[kForms], f23 = rec[kForms + 1];
+  QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, oc0, oc1, oc2, oc3);
+  QMLE_IN4(od);
+  QMLE_LD4(ca, kClose);
+  QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, od0, od1, od2, od3);
+  QMLE_IN4(st);
+  asm volatile("" : "+s"(f01), "+s"(f23)::"memory");
+  QMLE_LD4(cb, kClose + 4);
+  f_real_step<0>(a, (uint32_t)f01, st0);
+  f_real_step<1>(a, (uint32_t)(f01 >> 32), st1);
+  f_real_step<2>(a, (uint32_t)f23, st2);
+  f_real_step<3>(a, (uint32_t)(f23 >> 32), st3);
+  QMLE_IN4(ca);
+  QMLE_LD4(cc, kClose + 8);
+  QMLE_CMUL4D(a.v0, a.v1, a.v2, a.v3, ca0, ca1, ca2, ca3);
+  QMLE_IN4(cb);
+  QMLE_LD4(cd_, kClose + 12);
+  QMLE_CMUL4D(a.v4, a.v5, a.v6, a.v7, cb0, cb1, cb2, cb3);
+  QMLE_IN4(cc);
+  QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, cc0, cc1, cc2, cc3);
+  QMLE_IN4(cd_);
+  QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, cd_0, cd_1, cd_2, cd_3);
+#undef QMLE_LD4
+#undef QMLE_IN4
+}
+
 // In-thread bit 2 of the 16 amplitudes <-> lane bit 4, in-thread bit 3 <-> lane bit 5: v_permlane16_swap trades the
 // odd 16-lane rows of its first operand with the even rows of its second, v_permlane32_swap lanes 32..63 of the first
 // with lanes 0..31 of the second -- one instruction per 32-bit half of an amplitude pair, 32 in all, no LDS.  (The
@@ -528,6 +661,8 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
   }
   // header word (n_ops | relayout << 16 | sync << 24) and the four basis offsets of the first group
   uint32_t hdr = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(grp)[1];
+  uint32_t prec = grp->prod_off;  // (product form: the group's record, float offset in the matrix row)
+  int stale = 0;                  // the op pipeline (w0, w1, M0) is not primed for op k: a product-form group went by
   uint32_t o1 = grp->off[1], o2 = grp->off[2], o4 = grp->off[4], o8 = grp->off[8];
 #define QMLE_OFF(c, b1, b2, b4, b8) \
   ((((c) & 1) ? (b1) : 0u) ^ (((c) & 2) ? (b2) : 0u) ^ (((c) & 4) ? (b4) : 0u) ^ (((c) & 8) ? (b8) : 0u))
@@ -574,28 +709,59 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     const Group2 QMLE_CONSTANT *nx = more ? grp + 1 : grp;
     const uint32_t hdr_n = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(nx)[1];
     const uint32_t n1 = nx->off[1], n2 = nx->off[2], n4 = nx->off[4], n8 = nx->off[8];
+    const uint32_t prec_n = nx->prod_off;
+    // (fused: the iteration runs the last group too -- its header and record)
+    uint32_t hdr_l = 0u, prec_l = 0u;
     if constexpr (ZR) {
+      if (fused) {
+        hdr_l = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(grp + 1)[1];
+        prec_l = grp[1].prod_off;
+      }
       if (!more) on_gathered();
     }
-    const int n_run = fused ? f.n_ops_stage - k : n_ops;  // (fused: the rest of the stage's stream)
-    for (int j = 0; j < n_run; ++j, ++k) {
-      if constexpr (ZR) {
-        if (fused && j == n_ops) {  // (uniform: one scalar compare per gate; both groups hold >= 1 op)
-          if (lane_swap == 2) swap_lanes_45<true>(r);
-          else swap_lanes_45<false>(r);
+    // the group's ops -- as one product-form body, or gate by gate; fused: then the lane swaps and the last group's
+    uint32_t hdr_c = hdr, prec_c = prec;
+    int n_run = n_ops;
+#pragma nounroll
+    for (int part = 0;; ++part) {
+      if ((hdr_c >> 24) & kGroupProduct) {
+        asm volatile("" : "+s"(busy));
+        if (busy != 0) product_group(r, mrow + (prec_c >> 1), ((hdr_c >> 24) & kGroupProductLow1) != 0);
+        k += n_run;
+        // (the pipeline's registers are free across the body: whoever needs them next primes them again)
+        stale = 1;
+        w0 = w1 = (v4u){0u, 0u, 0u, 0u};
+        M0 = {0ull, 0ull, 0ull, 0ull};
+      } else {
+        if (stale != 0 && n_run > 0) {
+          w0 = op[k < last ? k : last];
+          w1 = op[k + 1 < last ? k + 1 : last];
+          const u64 QMLE_CONSTANT *m = mrow + (w0.z >> 1);
+          M0 = {m[0], m[1], m[2], m[3]};
+          stale = 0;
+        }
+        for (int j = 0; j < n_run; ++j, ++k) {
+          // scalar loads return out of order, so only lgkmcnt(0) can cover them: touching this
+          // gate's operands HERE puts that wait in front of the next prefetch instead of behind it
+          asm volatile("" : "+s"(M0.m00), "+s"(M0.m01), "+s"(M0.m10), "+s"(M0.m11), "+s"(w0.y), "+s"(w1.z) :: "memory");
+          const u64 QMLE_CONSTANT *mn = mrow + (w1.z >> 1);
+          const Mat2S Mn = {mn[0], mn[1], mn[2], mn[3]};
+          const v4u w2 = op[k + 2 < last ? k + 2 : last];
+          asm volatile("" : "+s"(busy));  // (re-read per gate: hoisted out of the loop the compare becomes a lane mask again)
+          if (busy != 0) fast_dispatch(r, (int)(w0.y >> 24), M0);
+          w0 = w1;
+          w1 = w2;
+          M0 = Mn;
         }
       }
-      // scalar loads return out of order, so only lgkmcnt(0) can cover them: touching this
-      // gate's operands HERE puts that wait in front of the next prefetch instead of behind it
-      asm volatile("" : "+s"(M0.m00), "+s"(M0.m01), "+s"(M0.m10), "+s"(M0.m11), "+s"(w0.y), "+s"(w1.z) :: "memory");
-      const u64 QMLE_CONSTANT *mn = mrow + (w1.z >> 1);
-      const Mat2S Mn = {mn[0], mn[1], mn[2], mn[3]};
-      const v4u w2 = op[k + 2 < last ? k + 2 : last];
-      asm volatile("" : "+s"(busy));  // (re-read per gate: hoisted out of the loop the compare becomes a lane mask again)
-      if (busy != 0) fast_dispatch(r, (int)(w0.y >> 24), M0);
-      w0 = w1;
-      w1 = w2;
-      M0 = Mn;
+      if (!fused || part != 0) break;
+      if constexpr (ZR) {  // (both groups of a fused iteration hold >= 1 op)
+        if (lane_swap == 2) swap_lanes_45<true>(r);
+        else swap_lanes_45<false>(r);
+      }
+      hdr_c = hdr_l;
+      prec_c = prec_l;
+      n_run = f.n_ops_stage - k;  // (the rest of the stage's stream)
     }
     if constexpr (ZR) {
       if (!more) {
@@ -625,6 +791,7 @@ __device__ __forceinline__ void tile2_groups(uint32_t sb, uint32_t addr, const T
     }
     addr = addr_next;
     hdr = hdr_n;
+    prec = prec_n;
     o1 = n1; o2 = n2; o4 = n4; o8 = n8;
     if (solo || (ZR && !((hdr_n >> 24) & 1u))) asm volatile("" ::: "memory");  // (uniform: the header sits in SGPRs)
     else __syncthreads();
@@ -1770,6 +1937,7 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
   if (from_regs) *from_regs = false;
   if (by_dma) *by_dma = false;
   if (by_lane_swap) *by_lane_swap = false;
+  st.product_form_last_run = false;  // (report only: set where k_tile2 is launched)
   if (reuse) reuse->filled = reuse->elided = false;
   from_zero = from_zero && plan_sparse(p);
   TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
@@ -1931,6 +2099,8 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
       once.done();
     }
     Tile2Args f;
+    for (int g = st.fast_begin; g < st.fast_end; ++g)
+      if (p->groups2[g].sync & kGroupProduct) st.product_form_last_run = true;  // (every k_tile2 instantiation takes the form)
     f.groups = p->dev.d_groups2 + st.fast_begin;
     f.ops = p->dev.d_ops2;
     f.tbl = p->dev.d_tbl2;
