@@ -212,6 +212,28 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * float offset of its record (-1: none; see qmle_group_product_form); "mat_row_floats" is the row's stride.  A tile stage reports "group_product_form_last_run": its last launch ran those groups in
  * product form (the fast tile kernel always does; the generic tile kernel applies the plain records). */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
+/* Host only (no GPU needed): how tile stage `stage` of `plan` would run for a request -- the launch policy of the
+ * tile passes as JSON, written like qmle_plan_describe (returns the bytes needed, or an error < 0: no tile stage
+ * there, batch or meas out of range).  `meas`: what the pass does with the finished tile -- 0 store, 1
+ * probabilities, 2 whole-state <Z>, 3 per-tile <Z> sums of every position, 4 per-tile Z-parity sums, 5 store +
+ * Meyer-Wallach rows, 6 Meyer-Wallach rows alone.  `request_flags`: what the caller of the pass knows, QMLE_ROUTE_*.
+ * Keys: "status" (0, or the error the launch would return), "family" (the kernel) and its instantiation ("dense4",
+ * "mw", "nt", "measure", "multi", "ws", "masks", "mono_q", "pair"), "grid", "threads", "lds_bytes", "compact",
+ * "tile_free", "mw_lean", "slots_in_lds", "fill" / "fill_elided" (a zero fill precedes the launch / is left out
+ * because the zeros are in place), "tiles_per_workgroup", "row_shift" (a partial row covers 2^row_shift tiles),
+ * the walk ("walk_slab", "walk_sync_staged", "walk_sync_tile_end", "staging_dma", "lane_swap",
+ * "lane_swap_crossed"), "from_registers", "wave_private", "product_form".  A batch run reports what it did in the
+ * "..._last_run" keys of qmle_plan_describe. */
+#define QMLE_ROUTE_INIT_ZERO      1u   /* the pass starts from |0..0> instead of reading the states */
+#define QMLE_ROUTE_FROM_ZERO      2u   /* the run started from |0..0> (every qmle_run_batch) */
+#define QMLE_ROUTE_FOLD_COLS      4u   /* the fold-column buffer is there (every qmle_run_batch of a plan that wants it) */
+#define QMLE_ROUTE_MULTI_ROWS     8u   /* the caller takes partial rows that cover several tiles */
+#define QMLE_ROUTE_ZEROS_IN_PLACE 16u  /* the states already hold zeros outside tile 0 (an earlier chunk's fill) */
+#define QMLE_ROUTE_SEMI_SINGLE    32u  /* each observable meets the last tile in at most one position */
+#define QMLE_ROUTE_NO_MULTI_ZIN   64u  /* as if QMLE_NO_MULTI_ZIN were set */
+#define QMLE_ROUTE_NO_MW_LEAN     128u /* as if QMLE_MW_NO_LEAN were set */
+int qmle_plan_tile_route(const qmle_plan *plan, int stage, int batch, int meas, int n_obs, unsigned request_flags,
+                         char *buf, size_t cap);
 /* Host only: the matrix builder's unit-pivot chain for `n` given 2x2 matrices u[i] = {m00, m01, m10, m11} as
  * (re, im) doubles.  The fast tile kernel applies an eligible gate as U / pivot, a matrix with a literal 1 (48
  * packed instructions instead of 64), and the product P of a chain's pivots is folded into the chain's last gate,

@@ -154,6 +154,7 @@ SYMBOLS = [
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("qmle_group_product_form", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
                                      C.POINTER(C.c_int)]),
+    ("qmle_plan_tile_route", _I, [_VP, _I, _I, _I, _I, C.c_uint, C.c_char_p, _SZ]),
     ("qmle_plan_stats", _I, [_VP, C.POINTER(C.c_int64)]),
     ("qmle_plan_autotune", _I, [_VP, _I, _I, _I, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double)]),
@@ -406,6 +407,22 @@ class Plan:
         child.n_qubits, child.n_slots, child.flags = self.n_qubits, self.n_slots, self.flags
         child.n_ops = child.stats()["n_ops"]
         return child
+
+    # what a tile pass does with the finished tile (``tile_route``'s ``meas``)
+    TM_STORE, TM_PROBS, TM_EXPVAL, TM_EXPVAL_PARTIAL, TM_EXPVAL_MASKS, TM_STORE_MW, TM_MW_ONLY = range(7)
+    # ``tile_route``'s ``flags`` (QMLE_ROUTE_*)
+    ROUTE_INIT_ZERO, ROUTE_FROM_ZERO, ROUTE_FOLD_COLS, ROUTE_MULTI_ROWS = 1, 2, 4, 8
+    ROUTE_ZEROS_IN_PLACE, ROUTE_SEMI_SINGLE, ROUTE_NO_MULTI_ZIN, ROUTE_NO_MW_LEAN = 16, 32, 64, 128
+
+    def tile_route(self, stage: int, batch: int, meas: int = 0, n_obs: int = 0, flags: int = 0) -> dict:
+        """``qmle_plan_tile_route`` as a dict: how tile stage ``stage`` would run for this request -- kernel family
+        and instantiation, launch shape, fill, walk -- decided on the host, no GPU needed.  A refused request comes
+        back with its error code in ``status``; a stage that is no tile stage raises."""
+        L = lib()
+        buf = C.create_string_buffer(1024)
+        need = L.qmle_plan_tile_route(self._h, int(stage), int(batch), int(meas), int(n_obs), int(flags), buf, 1024)
+        check(min(need, 0), "qmle_plan_tile_route")
+        return json.loads(buf.value.decode())
 
     def describe(self) -> dict:
         """``qmle_plan_describe`` as a dict.  The last stage carries the reports of the handle's last batch run

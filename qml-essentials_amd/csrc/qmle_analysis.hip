@@ -1561,9 +1561,10 @@ bool mw_fusable(int n, const Stage &last) {
 
 // Tiled state: positions 0..3 sit in the producing tile AND in the tile of every later read; the later reads are
 // bound by HBM, the producing pass by its arithmetic -- so the first later read reports them (QMLE_MW_NO_LEAN=1: A/B).
-bool mw_lean(int n, const Stage &last) {
+bool mw_no_lean_switch() { return std::getenv("QMLE_MW_NO_LEAN") != nullptr; }  // (read per call)
+bool mw_lean(int n, const Stage &last) { return mw_lean_layout(n, last) && !mw_no_lean_switch(); }
+bool mw_lean_layout(int n, const Stage &last) {
   if (last.kind != ST_TILE || last.T >= n || last.T < 10) return false;
-  if (std::getenv("QMLE_MW_NO_LEAN") != nullptr) return false;  // (read per call)
   for (int j = 0; j < 4; ++j)
     if (last.tile_bits[j] != j) return false;
   const MwCover cv = mw_cover(n, stage_tile_mask(last), 1);

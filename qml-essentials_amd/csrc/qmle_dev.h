@@ -266,7 +266,8 @@ constexpr int kMaxGridY = 65535;  // grid.y (and grid.z) limit: states / pairs /
 
 // hipFuncSetAttribute (160 KiB dynamic LDS) and the CU count are per DEVICE: a process that
 // drives several GPUs (one process per GPU is the supported layout, but nothing stops a caller)
-// must set them on each.  `slot` = a distinct small integer per call site.
+// must set them on each.  `slot` = a distinct small integer per call site of one
+// translation unit: the table of flags sits in this unit-private struct, so every unit numbers its own from 0.
 constexpr int kMaxDevices = 64;
 static inline int current_device() {
   int dev = 0;

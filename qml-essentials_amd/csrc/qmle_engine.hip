@@ -716,6 +716,11 @@ static ObsClass classify_observables(const qmle_plan *plan, const uint32_t *obs_
   return oc;
 }
 
+// LastRun: whether the last launch of tile stage `si` ran its product-form groups
+static void note_product_form(qmle_plan *plan, size_t si, const TileRoute &route) {
+  if (si < 64) plan->last_run.product_form_stages = (plan->last_run.product_form_stages & ~(1ull << si)) | ((uint64_t)route.product_form << si);
+}
+
 // The whole state lives in the LDS of one workgroup: one launch per chunk simulates and measures, and the state
 // is stored only when the state is what was asked for.  `rows`: the Meyer-Wallach rows of a chunk (L.partial_bytes).
 static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_mats, const float *d_angles, int batch,
@@ -729,21 +734,30 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
     const float *mats = d_mats + (size_t)b0 * plan->mat_floats;
     const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
     ProfScope prof_scope(plan, 0, stream);
-    int rc;
+    TileBuffers tb{nullptr, mats, ang};
+    TileRequest rq;
+    rq.batch = bc;
+    rq.init_zero = true;
     if (meas_type == QMLE_MEAS_STATE) {
-      rc = launch_tile(plan, st, (float2 *)d_out + (size_t)b0 * D, mats, ang, bc, true, TM_STORE, nullptr, nullptr, 0,
-                       stream);
+      tb.states = (float2 *)d_out + (size_t)b0 * D;
+      rq.meas = TM_STORE;
     } else if (meas_type == QMLE_MEAS_PROBS) {
-      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_PROBS, (float *)d_out + (size_t)b0 * D, nullptr, 0,
-                       stream);
+      tb.out = (float *)d_out + (size_t)b0 * D;
+      rq.meas = TM_PROBS;
     } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
-      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_EXPVAL, (float *)d_out + (size_t)b0 * n_obs,
-                       obs_masks, n_obs, stream);
+      tb.out = (float *)d_out + (size_t)b0 * n_obs;
+      tb.obs_masks = obs_masks;
+      rq.meas = TM_EXPVAL;
+      rq.n_obs = n_obs;
     } else {  // circuit + Meyer-Wallach sums
-      rc = launch_tile(plan, st, nullptr, mats, ang, bc, true, TM_MW_ONLY, rows, nullptr, 0, stream);
-      if (rc == QMLE_OK)
-        rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
+      tb.out = rows;
+      rq.meas = TM_MW_ONLY;
     }
+    TileRoute route;
+    int rc = launch_tile(plan, 0, tb, rq, stream, &route);
+    note_product_form(plan, 0, route);
+    if (rc == QMLE_OK && meas_type == QMLE_MEAS_MEYER_WALLACH)
+      rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
     if (rc != QMLE_OK) return rc;
   }
   return QMLE_OK;
@@ -796,7 +810,7 @@ class ChunkPipeline {
     if (piped_ && chunk > 0) (void)hipStreamWaitEvent(stream(chunk), side_->stage_done[(chunk - 1) & 1][k], 0);
     return StageQueued{piped_ ? side_->stage_done[chunk & 1][k] : nullptr, stream(chunk)};
   }
-  // how this run orders its chunks (qmle_plan::chunk_loop_last_run)
+  // how this run orders its chunks (LastRun::chunk_loop)
   int form() const { return !side_ ? kChunkLoopOneStream : piped_ ? kChunkLoopStaged : kChunkLoopFree; }
 
  private:
@@ -810,7 +824,7 @@ class ChunkPipeline {
 // no launch of the chunk loop behind stage 0 stores into the chunk's state buffer.  Admitted, each read to take the
 // state as input only: the last tile pass of a two-stage plan with its <Z> epilogue -- launch_tile with
 // TM_EXPVAL_PARTIAL / TM_EXPVAL_MASKS (k_tile2's measuring instantiations, k_tile + tile_epilogue: rows of partial
-// sums to `out`) or launch_reg_measure (k_reg_measure, k_reg_measure_mono: const loads, rows to `out`) -- and
+// sums to `out`) or routed to k_reg_measure* (k_reg_measure, k_reg_measure_mono: const loads, rows to `out`) -- and
 // launch_expval_final behind it (reads the rows).
 // Every other run fills every chunk: any TM_STORE / TM_STORE_MW pass or run_stage_inplace behind stage 0 (so every
 // plan of three or more stages, and two-stage plans measured otherwise than by the fused <Z> epilogue), one-stage
@@ -826,6 +840,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
                           const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
                           size_t workspace_bytes, hipStream_t caller_stream) {
   if (plan->zero_variant) plan = plan->zero_variant;  // every run_batch starts from |0..0>
+  plan->last_run = LastRun();  // (a run that fails reports the fresh-buffer figure and no measuring pass)
   const int n = plan->n;
   ObsClass oc;
   if (meas_type == QMLE_MEAS_EXPVAL_Z) oc = classify_observables(plan, obs_masks, n_obs);
@@ -843,7 +858,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   // per-sample gate matrices for the whole batch (tiny)
   rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true);
   if (rc != QMLE_OK) return rc;
-  plan->chunk_loop_last_run = kChunkLoopOneStream;
+  plan->last_run.chunk_loop = kChunkLoopOneStream;
   if (L.in_lds)
     return run_batch_lds(plan, L, d_mats, d_angles, batch, meas_type, obs_masks, n_obs, d_out, ws + L.partial[0],
                          caller_stream);
@@ -857,19 +872,13 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   const bool by_position = oc.single_bits || oc.semi_single;
   const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
   ChunkPipeline pipe(L.slots == 2, plan->stages.size(), /*free_running=*/reuse_zeros, caller_stream);
-  plan->chunk_loop_last_run = pipe.form();
-  // Clean slots: slot_fill[k].zeroed_states states of slot k hold zeros outside tile 0 of stage 0.  It lives and dies with this call
+  plan->last_run.chunk_loop = pipe.form();
+  // Clean slots: slot_zeroed[k] states of slot k hold zeros outside tile 0 of stage 0.  It lives and dies with this call
   // (the caller owns the workspace between calls, so a slot's first chunk is always filled), and a slot is one
   // buffer on one stream -- ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
-  FillReuse slot_fill[2];
+  int slot_zeroed[2] = {0, 0};
   uint64_t filled_states = 0;  // states written by fills, all chunks
   bool elided = false;         // a chunk ran without its fill
-  plan->stage0_written_last_run = 0;  // (a run that fails reports the fresh-buffer figure)
-  plan->measure_tpw_last_run = 0;     // (reports as well: how the last stage's fused <Z> pass ran)
-  plan->measure_regs_last_run = false;
-  plan->wave_private_last_run = false;
-  plan->staging_dma_last_run = false;
-  plan->lane_swap_last_run = false;
   int chunk_no = 0;
   for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
     const int bc = std::min(batch - b0, L.in_flight);
@@ -881,46 +890,43 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
     const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
     float2 *cols = d_cols ? d_cols + (size_t)b0 * plan->fold_groups * 16 : nullptr;
     bool initialised = false;
-    int reg_q = -1;  // >= 0: the last pass ran as k_reg_measure with 2^reg_q tiles per row
-    int tile_row_shift = 0;  // k_tile2's multi-tile measuring variant: 2^shift tiles per row
+    TileRoute route;  // of the chunk's latest tile pass
     for (size_t si = 0; si < plan->stages.size(); ++si) {
       const Stage &st = plan->stages[si];
       const ChunkPipeline::StageQueued stage_queued = pipe.begin_stage(chunk_no, si);
       ProfScope prof_scope(plan, (int)si, stream);
-      if (st.kind == ST_TILE && fuse_mw && si + 1 == plan->stages.size()) {
-        // the last pass stores the state AND reports its tile's Meyer-Wallach sums (one row per tile)
-        rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, TM_STORE_MW, d_partial, nullptr, 0, stream,
-                         /*from_zero=*/true, cols, &tile_row_shift);
-        initialised = true;
-      } else if (st.kind == ST_TILE) {
-        const bool last_fused = fuse_expval && si + 1 == plan->stages.size();
-        const int tm = !last_fused ? TM_STORE : by_position ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
-        reg_q = -1;
-        int reg_kind = last_fused && initialised ? reg_measure_kind(plan, si, n_obs) : 0;
-        // (k_reg_measure on live input is the slowest way to take parities; its known-zero forms
-        // -- FOLD, mono -- keep priority)
-        if (reg_kind == 1 && oc.semi_single) reg_kind = 0;
-        if (reg_kind) {
-          rc = launch_reg_measure(plan, st, reg_kind, stc, mats, ang, bc, d_partial, obs_masks,
-                                  n_obs, stream, &reg_q, d_coef + (size_t)b0 * 32);
-        } else {
-          FillReuse *const reuse = si == 0 && reuse_zeros ? &slot_fill[slot] : nullptr;
-          bool from_regs = false, by_dma = false, by_lane_swap = false;
-          rc = launch_tile(plan, st, stc, mats, ang, bc, !initialised, tm,
-                           last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
-                           last_fused ? n_obs : 0, stream, /*from_zero=*/true, cols,
-                           last_fused && (oc.single_bits || tm == TM_EXPVAL_MASKS) ? &tile_row_shift : nullptr, reuse,
-                           &from_regs, &by_dma, &by_lane_swap);
-          if (last_fused) {
-            plan->measure_tpw_last_run = 1 << tile_row_shift;
-            plan->measure_regs_last_run = from_regs;
-            plan->wave_private_last_run = from_regs && st.wave_private;
-            plan->staging_dma_last_run = by_dma;
-            plan->lane_swap_last_run = by_lane_swap;
-          }
-          if (reuse && reuse->filled) filled_states += (uint64_t)bc;
-          if (reuse && reuse->elided) elided = true;
+      if (st.kind == ST_TILE) {
+        const bool last = si + 1 == plan->stages.size();
+        // the last pass stores the state AND reports its tile's Meyer-Wallach sums (one row per tile), or measures
+        // <Z> instead of storing
+        const bool last_mw = fuse_mw && last, last_fused = !fuse_mw && fuse_expval && last;
+        const TileBuffers tb{stc, mats, ang, last_mw || last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
+                             cols, d_coef + (size_t)b0 * 32};
+        TileRequest rq;
+        rq.batch = bc;
+        rq.init_zero = !initialised;
+        rq.meas = last_mw ? TM_STORE_MW : !last_fused ? TM_STORE : by_position ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
+        rq.n_obs = last_fused ? n_obs : 0;
+        rq.from_zero = true;
+        rq.fold_cols = cols != nullptr;
+        rq.multi_rows = last_mw || (last_fused && (oc.single_bits || rq.meas == TM_EXPVAL_MASKS));
+        rq.semi_single = oc.semi_single;
+        const bool reuse = !last_mw && si == 0 && reuse_zeros;
+        if (reuse) rq.zeroed_states = slot_zeroed[slot];
+        rc = launch_tile(plan, si, tb, rq, stream, &route);
+        note_product_form(plan, si, route);
+        if (last_fused && !is_reg_measure(route.family)) {  // (k_reg_measure* is no tile walk: the report stays "no such pass")
+          plan->last_run.measure_tpw = 1 << route.row_shift;
+          plan->last_run.measure_regs = route.from_regs;
+          plan->last_run.wave_private = route.wave_private;
+          plan->last_run.staging_dma = (route.walk & kWalkDma) != 0;
+          plan->last_run.lane_swap = (route.walk & kWalkLaneSwap) != 0;
         }
+        if (reuse && route.fill) {
+          slot_zeroed[slot] = bc;
+          filled_states += (uint64_t)bc;
+        }
+        if (reuse && route.fill_elided) elided = true;
         initialised = true;
       } else {
         if (!initialised) {
@@ -938,8 +944,9 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
       launch_probs(stc, (float *)d_out + (size_t)b0 * D, tc, stream);
     } else if (meas_type == QMLE_MEAS_EXPVAL_Z && fuse_expval) {
       // column of the 33-float row: the bit's sum, or (masks, k_reg_measure) the observable's own
-      const int tiles = (1 << (n - plan->stages.back().T)) >> (reg_q < 0 ? tile_row_shift : reg_q);
-      launch_expval_final((const float *)d_partial, tiles, bc, n_obs, by_position && reg_q < 0 ? oc.by_position : oc.by_index,
+      const bool reg_measure = is_reg_measure(route.family);
+      const int tiles = (1 << (n - plan->stages.back().T)) >> route.row_shift;
+      launch_expval_final((const float *)d_partial, tiles, bc, n_obs, by_position && !reg_measure ? oc.by_position : oc.by_index,
                           (float *)d_out + (size_t)b0 * n_obs, stream);
     } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
       rc = oc.single_bits
@@ -949,7 +956,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
                                 d_partial, L.partial_bytes, stream);
       if (rc != QMLE_OK) return rc;
     } else if (meas_type == QMLE_MEAS_MEYER_WALLACH) {
-      rc = fuse_mw ? run_mw_fused(stc, n, bc, plan->stages.back(), tile_row_shift, d_partial, L.partial_bytes,
+      rc = fuse_mw ? run_mw_fused(stc, n, bc, plan->stages.back(), route.row_shift, d_partial, L.partial_bytes,
                                   (float *)d_out + (size_t)b0 * (n + 1), stream)
                    : run_mw_resident(stc, n, bc, d_partial, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
       if (rc != QMLE_OK) return rc;
@@ -962,7 +969,7 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   // what qmle_plan_describe reports as stage 0's written bytes (a report: nothing in the engine reads it): the fills
   // and tile-0 stores of this run per state when fills were left out, else 0 = the fresh-buffer figure
   if (elided)
-    plan->stage0_written_last_run =
+    plan->last_run.stage0_written =
         ((filled_states << (n + 3)) + ((uint64_t)batch << (plan->stages[0].T + 3))) / (uint64_t)batch;
   return QMLE_OK;
 }
@@ -972,9 +979,16 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
 // One stage of a plan applied in place to resident states.
 int qmle::run_stage_inplace(qmle_plan *plan, const Stage &st, float2 *d_states, const float *d_mats,
                             const float *d_angles, int batch, hipStream_t stream) {
-  if (st.kind == ST_TILE)
-    return launch_tile(plan, st, d_states, d_mats, d_angles, batch, false, TM_STORE, nullptr,
-                       nullptr, 0, stream);
+  if (st.kind == ST_TILE) {
+    const size_t si = (size_t)(&st - plan->stages.data());
+    const TileBuffers tb{d_states, d_mats, d_angles};
+    TileRequest rq;
+    rq.batch = batch;
+    TileRoute route;
+    const int rc = launch_tile(plan, si, tb, rq, stream, &route);
+    note_product_form(plan, si, route);
+    return rc;
+  }
   if (st.kind == ST_DIRECT)
     return launch_direct(plan, plan->dev_ops[st.op_begin], d_states, d_mats, batch, stream);
   const LoweredOp &o = plan->dev_ops[st.op_begin];
@@ -1081,7 +1095,7 @@ static void adopt_schedule(qmle_plan *dst, qmle_plan *src) {
   std::swap(dst->algo_bytes_per_state, src->algo_bytes_per_state);
   dst->force_candidate = src->force_candidate;
   dst->pad_high = src->pad_high;
-  dst->stage0_written_last_run = 0;  // (the figure of a run of the old schedule)
+  dst->last_run.stage0_written = 0;  // (the figure of a run of the old schedule)
   dst->autotuned = true;
 }
 

@@ -126,28 +126,66 @@ int run_stage_inplace(qmle_plan *plan, const Stage &st, float2 *d_states, const 
                       const float *d_angles, int batch, hipStream_t stream);
 
 // ---- qmle_tile.hip ----
-// What launch_tile's filled first pass may take for granted about `states` (run_batch_masks keeps one per workspace
-// slot, for one call): on entry the first `zeroed_states` states hold zeros everywhere outside this stage's tile 0.
-// The pass leaves out its fill when that covers `batch` (`elided`), else it fills (`filled`) and the count becomes
-// `batch`; a launch that is no filled first pass reports neither.
-struct FillReuse {
-  int zeroed_states = 0;
-  bool filled = false, elided = false;  // of the last launch
-};
 size_t tile_lds_bytes(int T, int L, int n_slots);
 int tile_threads(int T);
-int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
-                const float *angles, int batch, bool init_zero, int meas, void *out,
-                const uint32_t *obs_masks, int n_obs, hipStream_t stream, bool from_zero = false,
-                float2 *cols = nullptr, int *row_shift = nullptr, FillReuse *reuse = nullptr,
-                bool *from_regs = nullptr,   // *from_regs: <Z> came from the last group's registers (Stage::zreg)
-                bool *by_dma = nullptr,      // *by_dma: ... and the walk staged its tiles by LDS DMA (Stage::dma_tables)
-                bool *by_lane_swap = nullptr);  // ... and ran its last group through lane swaps (Stage::lane_swap_last)
-int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs);
-int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *states,
-                       const float *mats, const float *angles, int batch, void *out,
-                       const uint32_t *obs_masks, int n_obs, hipStream_t stream, int *q_out,
-                       float *coef);
+// walk flags of k_tile2 (Tile2Args::walk)
+constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u, kWalkDma = 8u, kWalkLaneSwap = 16u,
+                   kWalkLaneSwapCross = 32u;
+// What the caller of a tile pass knows (route_tile's input beside the plan).
+struct TileRequest {
+  int batch = 1;
+  bool init_zero = false;   // the pass starts from |0..0> instead of reading the states
+  int meas = TM_STORE;      // TileMeas
+  int n_obs = 0;
+  bool from_zero = false;   // the run started from |0..0>: Stage::zero_in holds (with known-zero tracking on)
+  bool fold_cols = false;   // the fold-column buffer is there (product passes)
+  bool multi_rows = false;  // the caller takes partial rows that cover several tiles (TileRoute::row_shift)
+  int zeroed_states = 0;    // a filled first pass: that many states of the buffer already hold zeros outside tile 0
+  bool semi_single = false; // the observables meet the last tile in at most one position each (classify_observables)
+  bool no_multi_zin = false;  // QMLE_NO_MULTI_ZIN is set
+  bool no_mw_lean = false;    // QMLE_MW_NO_LEAN is set
+};
+// How a tile stage runs: everything launch_tile decides, as a value.  route_tile computes it from the plan and the
+// request alone (no HIP call, no environment, no global state, no allocation); launch_tile issues it.
+struct TileRoute {
+  int status = QMLE_OK;     // != QMLE_OK: the request is refused and nothing is launched
+  TileFamily family = TF_TILE;
+  // instantiation (the template parameters the family has)
+  bool dense4 = false, mw = false;                                 // k_tile; mw: k_tile2 as well
+  bool measure = false, multi = false, ws = false, masks = false;  // k_tile2
+  int mono_q = 0;                                                  // k_reg_measure_mono: Q, PAIR
+  bool pair = false;
+  bool nt = false;  // non-temporal policy: TileArgs::nt (k_tile, k_tile2 -- there also the NT parameter --,
+                    // k_tile_product), the NT parameter of k_product_stream and k_reg_measure_mono
+  // launch shape
+  unsigned grid_x = 1, grid_y = 1, threads = 64;
+  size_t lds_bytes = 0;
+  // TileArgs fields beside nt
+  bool compact = false;
+  uint32_t tile_free = 0;
+  bool mw_lean = false, slots_in_lds = false;
+  // a zero fill of the states precedes the launch / would have, but the zeros are in place (TileRequest::zeroed_states)
+  bool fill = false, fill_elided = false;
+  // rows and walk: tiles per workgroup; a partial row covers 2^row_shift tiles (the tile walk and k_reg_measure*)
+  int tpw = 1, row_shift = 0;
+  uint32_t walk = 0;  // kWalk* (k_tile2)
+  // <Z> from the last group's registers; ... in a tile loop without a workgroup barrier; product-form groups run
+  bool from_regs = false, wave_private = false, product_form = false;
+};
+TileRoute route_tile(const qmle_plan *p, size_t stage, const TileRequest &rq);
+// the device pointers of a tile pass
+struct TileBuffers {
+  float2 *states = nullptr;
+  const float *mats = nullptr, *angles = nullptr;
+  void *out = nullptr;
+  const uint32_t *obs_masks = nullptr;
+  float2 *cols = nullptr;  // fold columns (TileRequest::fold_cols)
+  float *coef = nullptr;   // k_mono_coef's rows (k_reg_measure_mono)
+};
+// Route, then issue: first-use setup, the optional fill and the kernel of route_tile(p, stage, rq).  `rq`'s two
+// switches are read here, per launch.  *taken: the route (also when it was refused).
+int launch_tile(const qmle_plan *p, size_t stage, const TileBuffers &b, TileRequest rq, hipStream_t stream,
+                TileRoute *taken = nullptr);
 
 // ---- qmle_direct.hip ----
 int launch_direct(const qmle_plan *p, const LoweredOp &op, float2 *states, const float *mats,
@@ -172,7 +210,10 @@ void launch_density(const float2 *states, float2 *d_out, int n, int batch, hipSt
 // row per tile at the start of `ws` (TM_STORE_MW / TM_MW_ONLY); d_out [batch][n + 1] = (Q, purities by wire)
 bool mw_fusable(int n, const Stage &last);
 // tiled state: the producing pass leaves the cross terms of positions 0..3 to the first later read (TileArgs::mw_lean)
+// (mw_lean_layout: what the stage allows; mw_no_lean_switch: QMLE_MW_NO_LEAN is set; mw_lean: both)
 bool mw_lean(int n, const Stage &last);
+bool mw_lean_layout(int n, const Stage &last);
+bool mw_no_lean_switch();
 size_t mw_fused_ws_bytes(int n, int batch, const Stage &last);
 int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int row_shift, void *ws,
                  size_t ws_bytes, float *d_out, hipStream_t stream);  // a row covers 2^row_shift tiles

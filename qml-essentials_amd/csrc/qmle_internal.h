@@ -217,9 +217,6 @@ struct Stage {
   // report only (describe_plan): indices into the stage's ops2 stream of the ops that run in unit-pivot form and of
   // the carriers that take their chains' pivots (assign_unit_forms)
   std::vector<int> unit_form_ops, scale_carriers;
-  // report only: the last launch of this stage ran its product-form groups (every k_tile2 launch does; k_tile and the
-  // other readers of dev_ops apply the plain records).  Written by launch_tile.
-  mutable bool product_form_last_run = false;
 };
 // A stage's lane offsets as runs: local bits 0 .. top -> global positions, contiguous stretches (off, mask, pos).
 // Returns their number, or -1 when there are more than four (k_tile2 then reads the offsets from its table).
@@ -256,9 +253,30 @@ struct DevicePlan {  // lazily created by the first run on a device
   uint32_t *d_tbl2 = nullptr;
 };
 
-// How a batch run ordered its chunks (ChunkPipeline, qmle_engine.hip; qmle_plan::chunk_loop_last_run)
+// How a batch run ordered its chunks (ChunkPipeline, qmle_engine.hip; LastRun::chunk_loop)
 enum { kChunkLoopNone = 0, kChunkLoopOneStream, kChunkLoopStaged, kChunkLoopFree };
 constexpr const char *kChunkLoopNames[] = {"none", "one_stream", "staged", "free"};
+
+// What the plan's last run did (describe_plan's *_last_run keys).  Report only: the engine writes it from
+// the routes launch_tile returns (TileRoute, qmle_host.h) and never reads it.  run_batch_masks resets all of it first.
+struct LastRun {
+  // bytes per state that stage 0 of the last batch run really wrote -- its fills and tile-0 stores over its states --
+  // when that run left out fills of chunks whose workspace slot already held the zeros; 0 (also after a run that
+  // failed): the fresh-buffer figure applies
+  uint64_t stage0_written = 0;
+  // the last stage's fused <Z> pass in the last batch run: tiles per workgroup (0: no such pass ran), whether it took
+  // <Z> from the last group's registers (Stage::zreg), ... in a tile loop without a workgroup barrier
+  // (Stage::wave_private), ... staged its tiles by LDS DMA (Stage::dma_tables), ... and ran its last group through lane
+  // swaps (Stage::lane_swap_last)
+  int measure_tpw = 0;
+  bool measure_regs = false, wave_private = false, staging_dma = false, lane_swap = false;
+  // how the last batch run ordered its chunks (ChunkPipeline::form; a run with one chunk, or with the whole state in
+  // the LDS, is a one-stream run)
+  int chunk_loop = kChunkLoopNone;
+  // bit s: the last launch of tile stage s (batch run or in place; stages 0..63) ran its product-form groups -- every
+  // k_tile2 launch does; k_tile and the other readers of dev_ops apply the plain records
+  uint64_t product_form_stages = 0;
+};
 
 }  // namespace qmle
 
@@ -307,21 +325,7 @@ struct qmle_plan {
   bool whole_state_lds = false;
   int tile_T = 0, tile_L = 0;
   double algo_bytes_per_state = 0;
-  // Report only (describe_plan; the engine writes it once per qmle_run_batch and never reads it): bytes per state
-  // that stage 0 of the last batch run really wrote -- its fills and tile-0 stores over its states -- when that run
-  // left out fills of chunks whose workspace slot already held the zeros; 0 (also after a run that failed): the
-  // fresh-buffer figure applies
-  uint64_t stage0_written_last_run = 0;
-  // Report only, the same way: tiles per workgroup of the last stage's fused <Z> pass in the last batch run (0: no
-  // such pass ran), and whether it took <Z> from the last group's registers (Stage::zreg)
-  int measure_tpw_last_run = 0;
-  bool measure_regs_last_run = false;
-  bool wave_private_last_run = false;     // ... and ran its tile loop without a workgroup barrier (Stage::wave_private)
-  bool staging_dma_last_run = false;      // ... and staged its tiles by LDS DMA (Stage::dma_tables)
-  bool lane_swap_last_run = false;        // ... and ran its last group through lane swaps (Stage::lane_swap_last)
-  // ... and how the last batch run ordered its chunks (ChunkPipeline::form; a run with one chunk, or with the whole
-  // state in the LDS, is a one-stream run)
-  int chunk_loop_last_run = qmle::kChunkLoopNone;
+  qmle::LastRun last_run;                 // report only (describe_plan)
   qmle::DevicePlan dev;
   qmle::StageProfile prof;
   // <Z> measurements only: trailing gates that map basis states to basis states (CX, SWAP)
@@ -352,19 +356,37 @@ void split_expval_tail(const std::vector<qmle_op> &ops, int n, std::vector<qmle_
 // Z on `wire` pulled back through the absorbed gates: bit w set <=> Z_w in the parity.
 uint32_t pull_back_z(const std::vector<qmle_op> &absorbed, int wire);
 std::string describe_plan(const qmle_plan *p);
-// Which kernel measures <Z> / Z parities out of stage `si` when it is the last one of a run
-// from |0..0>: 0 k_tile epilogue, 1 k_reg_measure<false>, 2 k_reg_measure<true> (gates folded
-// into columns), 3 k_reg_measure_mono.  `sparse`: known-zero tracking is on for the run.
-int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse);
+// Which kernel runs a tile stage.  The first four are what expval_kernel_of answers (and index describe_plan's names).
+enum TileFamily : int {
+  TF_TILE = 0,              // k_tile<DENSE4, MW>
+  TF_REG_MEASURE = 1,       // k_reg_measure<false>
+  TF_REG_MEASURE_FOLD = 2,  // k_reg_measure<true>: gates folded into columns
+  TF_REG_MEASURE_MONO = 3,  // k_reg_measure_mono<Q, PAIR, NT>
+  TF_TILE2 = 4,             // k_tile2<NT, MEASURE, MULTI, WS, MW, MASKS>
+  TF_TILE_PRODUCT = 5,      // k_tile_product
+  TF_PRODUCT_STREAM = 6,    // k_product_stream<NT>
+};
+constexpr const char *kTileFamilyNames[] = {"k_tile",  "k_reg_measure",  "k_reg_measure_fold", "k_reg_measure_mono",
+                                            "k_tile2", "k_tile_product", "k_product_stream"};
+inline bool is_reg_measure(TileFamily f) { return f >= TF_REG_MEASURE && f <= TF_REG_MEASURE_MONO; }
+// Which kernel measures <Z> / Z parities out of stage `si` when it is the last one of a run from |0..0>: TF_TILE (the
+// tile kernels' epilogues) or one of k_reg_measure*.  `sparse`: known-zero tracking is on for the run.
+TileFamily expval_kernel_of(const qmle_plan *p, size_t si, bool sparse);
 // Stage `si` QUALIFIES for <Z> from the last group's registers (Stage::zreg): it is the last of several, has a k_tile2
 // description with records (any last Group2 will do, the empty data-moving one included) and no known-zero TILES on
 // input -- known zeros INSIDE the tile are fine, idle work items hand over zeros.  Whether a run takes that path is
 // decided per launch: only a multi-tile TM_EXPVAL_PARTIAL walk does (launch_tile); a run that hands the stage to
 // k_reg_measure*, measures folded-CX parities (TM_EXPVAL_MASKS) or has too few tiles for a walk does not, and
-// qmle_plan::measure_regs_last_run says which it was.
+// LastRun::measure_regs says which it was.
 bool qualifies_for_register_measure(const qmle_plan *p, size_t si);
-// ... and its walk stages by LDS DMA whenever it runs: Stage::dma_tables, and no known zeros inside the tile.
+// Stage::zero_in as a tile pass sees it: *local = tile-local bits, *outer = tile-index bits that are known zero
+void stage_known_zeros(const qmle_plan *p, const Stage &st, uint32_t *local, uint32_t *outer);
+// ... and its walk stages by LDS DMA whenever it runs: Stage::dma_tables, and no known zeros inside the tile
+// (walk_by_dma: the same with the known-zero local bits of the launch in hand).
+bool walk_by_dma(const Stage &st, uint32_t zin_local);
 bool stages_by_dma(const qmle_plan *p, size_t si);
+// ... and its last group runs through lane swaps then (Stage::lane_swap_last rides on the DMA form)
+inline bool walk_by_lane_swap(const Stage &st, bool by_dma) { return st.fast_ok && st.lane_swap_last && by_dma; }
 double algo_bytes(const qmle_op &op, int n);
 constexpr int kFastMinT = 10, kFastMaxT = 13;  // k_tile2: 2^(T-4) threads, 8 float4 per thread
 constexpr int kLdsMaxQubits = 14;       // 2^14 * 8 B = 128 KiB <= 160 KiB LDS/CU

@@ -1608,7 +1608,7 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
   const bool sparse = !(p->flags & QMLE_PLAN_NO_SPARSE);
   if (st.kind != ST_TILE) return st.kind == ST_DIRECT ? 0.5 * st.algo_bytes_per_state : 8.0 * D;
   // (the plan's last batch run left out fills of zeros that were in memory already: what it wrote)
-  if (si == 0 && p->stage0_written_last_run) return (double)p->stage0_written_last_run;
+  if (si == 0 && p->last_run.stage0_written) return (double)p->last_run.stage0_written;
   if (!sparse || !st.next_tile) return 8.0 * D;
   uint32_t outer = 0;
   for (int i = 0; i < p->n - st.T; ++i) outer |= 1u << st.outer_bits[i];
@@ -1621,26 +1621,36 @@ bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
   return placed_for_register_measure(p, st, st.zero_in, si == 0, si + 1 == p->stages.size());
 }
 
-bool stages_by_dma(const qmle_plan *p, size_t si) {
-  const Stage &st = p->stages[si];
-  if (!qualifies_for_register_measure(p, si) || !st.dma_tables) return false;
-  if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
-  for (int j = 0; j < st.T; ++j)  // known zeros inside the tile: the walk zero-fills and loads selectively
-    if (st.zero_in & (1u << st.tile_bits[j])) return false;
-  return true;
+void stage_known_zeros(const qmle_plan *p, const Stage &st, uint32_t *local, uint32_t *outer) {
+  *local = *outer = 0;
+  for (int j = 0; j < st.T; ++j)
+    if (st.zero_in & (1u << st.tile_bits[j])) *local |= 1u << j;
+  for (int i = 0; i < p->n - st.T; ++i)
+    if (st.zero_in & (1u << st.outer_bits[i])) *outer |= 1u << i;
 }
 
-int expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
+// (known zeros inside the tile: the walk zero-fills and loads selectively)
+bool walk_by_dma(const Stage &st, uint32_t zin_local) { return st.dma_tables && !zin_local; }
+
+bool stages_by_dma(const qmle_plan *p, size_t si) {
   const Stage &st = p->stages[si];
-  if (st.kind != ST_TILE || si == 0) return 0;
-  if (st.grp_end - st.grp_begin != 1 || p->op_groups[st.grp_begin].kind != GK_REG4) return 0;
-  if (st.T < 10 || st.T > 14 || st.T >= p->n || (st.op_end - st.op_begin) > 1000) return 0;
+  if (!qualifies_for_register_measure(p, si)) return false;
+  uint32_t local = 0, outer = 0;
+  if (!(p->flags & QMLE_PLAN_NO_SPARSE)) stage_known_zeros(p, st, &local, &outer);
+  return walk_by_dma(st, local);
+}
+
+TileFamily expval_kernel_of(const qmle_plan *p, size_t si, bool sparse) {
+  const Stage &st = p->stages[si];
+  if (st.kind != ST_TILE || si == 0) return TF_TILE;
+  if (st.grp_end - st.grp_begin != 1 || p->op_groups[st.grp_begin].kind != GK_REG4) return TF_TILE;
+  if (st.T < 10 || st.T > 14 || st.T >= p->n || (st.op_end - st.op_begin) > 1000) return TF_TILE;
   const OpGroup &g = p->op_groups[st.grp_begin];
   int live_bits = 0;  // register bits that are not known-zero on input
   for (int j = 0; j < 4; ++j)
     live_bits += !(sparse && ((st.zero_in >> st.tile_bits[g.bits[j]]) & 1u));
-  if (live_bits == 0 && p->n - st.T >= 5) return 3;
-  return live_bits <= 2 && g.n_ops > 0 ? 2 : 1;
+  if (live_bits == 0 && p->n - st.T >= 5) return TF_REG_MEASURE_MONO;
+  return live_bits <= 2 && g.n_ops > 0 ? TF_REG_MEASURE_FOLD : TF_REG_MEASURE;
 }
 
 // fp32 flops per state of the operators the plan really applies (after 1-qubit merging): a dense
@@ -1744,8 +1754,7 @@ std::string describe_plan(const qmle_plan *p) {
        << ",\"flops_live_per_state\":" << stage_flops_per_state(p, st, true)
        << ",\"zero_in\":" << st.zero_in << ",\"next_tile\":" << (st.next_tile ? "true" : "false")
        << ",\"product\":" << (st.product_ok ? "true" : "false") << ",\"expval_kernel\":\""
-       << (const char *[]){"k_tile", "k_reg_measure", "k_reg_measure_fold", "k_reg_measure_mono"}
-              [expval_kernel_of(p, s, !(p->flags & QMLE_PLAN_NO_SPARSE))]
+       << kTileFamilyNames[expval_kernel_of(p, s, !(p->flags & QMLE_PLAN_NO_SPARSE))]
        << "\",\"read_bytes_from_zero\":" << (unsigned long long)stage_read_bytes(p, s)
        << ",\"write_bytes_from_zero\":" << (unsigned long long)stage_write_bytes(p, s)
        << ",\"bits\":[";
@@ -1808,7 +1817,7 @@ std::string describe_plan(const qmle_plan *p) {
     // without known zeros inside the tile): the records of the frame behind the swaps, the positions of its in-thread
     // bits and of its thread bits; the X / CX behind it: `measure_between` (between the last two groups), then
     // `measure_after`
-    const bool lane_swap = st.fast_ok && st.lane_swap_last && stages_by_dma(p, s);
+    const bool lane_swap = walk_by_lane_swap(st, stages_by_dma(p, s));
     os << ",\"last_group_lane_swap\":" << (lane_swap ? "true" : "false");
     if (lane_swap) {
       os << ",\"lane_swap_crossed\":" << (st.lane_swap_cross ? "true" : "false") << ",\"measure_records_swap\":[";
@@ -1863,15 +1872,15 @@ std::string describe_plan(const qmle_plan *p) {
       os << "],\"product_form_records\":[";
       for (int g = st.fast_begin; g < st.fast_end; ++g)
         os << (g > st.fast_begin ? "," : "") << ((p->groups2[g].sync & kGroupProduct) ? (long long)p->groups2[g].prod_off : -1ll);
-      os << "],\"group_product_form_last_run\":" << (st.product_form_last_run ? "true" : "false");
+      os << "],\"group_product_form_last_run\":" << (s < 64 && ((p->last_run.product_form_stages >> s) & 1u) ? "true" : "false");
     }
     if (s + 1 == p->stages.size())
-      os << ",\"measure_tiles_per_workgroup_last_run\":" << p->measure_tpw_last_run
-         << ",\"measured_from_registers_last_run\":" << (p->measure_regs_last_run ? "true" : "false")
-         << ",\"wave_private_walk_last_run\":" << (p->wave_private_last_run ? "true" : "false")
-         << ",\"staging_dma_last_run\":" << (p->staging_dma_last_run ? "true" : "false")
-         << ",\"last_group_lane_swap_last_run\":" << (p->lane_swap_last_run ? "true" : "false")
-         << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->chunk_loop_last_run] << "\"";
+      os << ",\"measure_tiles_per_workgroup_last_run\":" << p->last_run.measure_tpw
+         << ",\"measured_from_registers_last_run\":" << (p->last_run.measure_regs ? "true" : "false")
+         << ",\"wave_private_walk_last_run\":" << (p->last_run.wave_private ? "true" : "false")
+         << ",\"staging_dma_last_run\":" << (p->last_run.staging_dma ? "true" : "false")
+         << ",\"last_group_lane_swap_last_run\":" << (p->last_run.lane_swap ? "true" : "false")
+         << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->last_run.chunk_loop] << "\"";
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";

@@ -6,21 +6,22 @@
 // (float4 = 2 amplitudes) global accesses everywhere, one workgroup per LDS tile.
 //
 // Kernels
-//   k_build_matrices   per-sample 2x2 / 4x4 gate matrices from the angle table
-//   k_tile             load 2^T-amplitude tile -> LDS, apply a list of gates,
+//   k_tile<DENSE4, MW> load 2^T-amplitude tile -> LDS, apply a list of gates,
 //                      store / measure   (whole state in LDS when n <= 14)
-//   k_direct_1q        one (controlled) 2x2 gate streamed through HBM in place
-//   k_diag_all         full-register diagonal (Golomb encoding)
+//   k_tile2<NT, MEASURE, MULTI, WS, MW, MASKS>
+//                      the fast tile kernel: stages of (controlled) 2x2 gates as table-addressed register-tile
+//                      groups, several tiles per workgroup, <Z> from the last group's registers
 //   k_reg_measure<FOLD>, k_reg_measure_mono (+ k_mono_coef)
 //                      measuring last pass in registers: <Z> / Z parities accumulated
 //                      across tiles per work item, gates on known zeros folded away
 //   k_product_stream, k_tile_product (+ k_fold_columns)
 //                      pass whose gate groups all act on known-zero bits:
 //                      out = in (x) prod_g U_g e_0, written without staging amplitudes
-//   k_expval_partial / k_expval_final   all-qubit <Z> in ONE read of the state
-//   k_probs, k_density, k_marginal, k_overlap_*, k_cross_*, k_histogram
-//   k_mw_tile*         Meyer-Wallach purities; k_adjoint_lds, k_tile_adj, k_adj_*: adjoint
-//   k_cdf, k_sample, k_probs_diag_expval: shot sampling; k_build_angles: device angle table
+// Host side
+//   route_tile         decides how a tile stage runs (TileRoute, qmle_host.h): kernel, instantiation, launch shape,
+//                      fill, walk -- a pure function of the plan and the request
+//   launch_tile        routes, then issues: first-use setup, the optional fill, the kernel arguments, one launch
+//   qmle_plan_tile_route  the route as JSON (host only)
 //
 // Runs from |0..0> track the bit positions whose amplitudes are still exactly zero
 // (Stage::zero_in, qmle_plan.cpp): they are neither read nor computed nor stored.
@@ -595,8 +596,6 @@ struct Tile2Args {
   uint32_t walk;
   uint32_t dma_delta[4];
 };
-constexpr uint32_t kWalkSlab = 1u, kWalkSyncStaged = 2u, kWalkSyncTileEnd = 4u, kWalkDma = 8u, kWalkLaneSwap = 16u,
-                   kWalkLaneSwapCross = 32u;
 constexpr int kZrTotal = 13, kZrWalk = 14, kZrCols = 17;  // columns of tile_zr_finish's per-wave sums
 
 __device__ __forceinline__ uint64_t tile2_base(const TileArgs &a, const Tile2Args &f, uint32_t tile) {
@@ -1927,29 +1926,92 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
   return t;
 }
 
-int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float *mats,
-                const float *angles, int batch, bool init_zero, int meas, void *out,
-                const uint32_t *obs_masks, int n_obs, hipStream_t stream,
-                bool from_zero, float2 *cols, int *row_shift, FillReuse *reuse, bool *from_regs, bool *by_dma,
-                bool *by_lane_swap) {
-  // *row_shift: TM_EXPVAL_PARTIAL rows cover 2^row_shift tiles each (multi-tile k_tile2)
-  if (row_shift) *row_shift = 0;
-  if (from_regs) *from_regs = false;
-  if (by_dma) *by_dma = false;
-  if (by_lane_swap) *by_lane_swap = false;
-  st.product_form_last_run = false;  // (report only: set where k_tile2 is launched)
-  if (reuse) reuse->filled = reuse->elided = false;
-  from_zero = from_zero && plan_sparse(p);
-  TileArgs a = fill_tile_args(p, st, states, mats, angles, init_zero, meas, out, obs_masks, n_obs,
-                              from_zero);
-  a.slots_in_lds = tile_lds_bytes(st.T, st.L, a.n_ops) <= 160 * 1024 ? 1 : 0;
+// The instantiations of the two tile kernels, once: first use (LDS-base check, 160 KiB attribute) and the launch
+// switches of issue_tile expand these lists, and nothing else names an instantiation.
+//                    NT     MEASURE MULTI  WS     MW     MASKS
+#define QMLE_TILE2_INSTANCES(X)                    \
+  X(false, false, false, false, false, false)      \
+  X(true,  false, false, false, false, false)      \
+  X(false, true,  false, false, false, false)      \
+  X(true,  true,  false, false, false, false)      \
+  X(false, false, true,  false, false, false)      \
+  X(true,  false, true,  false, false, false)      \
+  X(false, true,  true,  false, false, false)      \
+  X(true,  true,  true,  false, false, false)      \
+  X(false, true,  true,  false, false, true)       \
+  X(true,  true,  true,  false, false, true)       \
+  X(false, false, false, true,  false, false)      \
+  X(false, true,  false, true,  false, false)      \
+  X(false, true,  false, false, true,  false)      \
+  X(true,  true,  false, false, true,  false)      \
+  X(false, true,  false, true,  true,  false)
+#define QMLE_TILE2(NT, ME, MU, WS, MW, MA) (k_tile2<NT, ME, MU, WS, MW, MA>)
+//                   DENSE4 MW
+#define QMLE_TILE_INSTANCES(X) X(false, false) X(true, false) X(false, true) X(true, true)
+#define QMLE_TILE1(D4, MW) (k_tile<D4, MW>)
+
+// k_reg_measure* takes the last pass of a <Z> run when all its gates share one register-tile group (expval_kernel_of,
+// qmle_plan.cpp): 2^row_shift tiles per workgroup and partial row
+static TileRoute route_reg_measure(const qmle_plan *p, const Stage &st, TileFamily family, int batch) {
+  TileRoute r;
+  r.family = family;
+  r.slots_in_lds = true;
+  const int n_outer = p->n - st.T;
+  // ~4096 workgroups per launch when the batch allows, at most 64 tiles per workgroup
+  int q = 0;
+  while (q < 6 && q < n_outer && (((uint64_t)batch << n_outer) >> (q + 1)) >= 4096) ++q;
+  r.threads = 1u << (st.T - 4);
+  r.lds_bytes = (size_t)(st.op_end - st.op_begin) * sizeof(OpSlot) + (132 + 16 * 32 + 128) * sizeof(uint32_t);
+  if (family == TF_REG_MEASURE_MONO) {
+    q = 5;
+    r.mono_q = 5;
+    r.lds_bytes = 16 * 32 * sizeof(float);
+    uint32_t zin_local = 0, zin_outer = 0;
+    if (plan_sparse(p) && st.zero_in) stage_known_zeros(p, st, &zin_local, &zin_outer);
+    const OpGroup &g = p->op_groups[st.grp_begin];
+    if (g.bits[0] != 0 && st.tile_bits[0] == 0 && !(zin_local & 1u) && st.T >= 11 && n_outer >= 4) {
+      q = 4;
+      r.mono_q = 4;
+      r.pair = true;
+      r.threads = 1u << (st.T - 5);
+      // live amplitudes per launch >= 1 GiB: stream them past the caches (0.427 -> 0.38 ms per
+      // 256 states of K2; k_direct_1q's measurements say the opposite below the cache size)
+      const int n_live = p->n - __builtin_popcount(st.zero_in);
+      r.nt = ((uint64_t)batch << (n_live + 3)) >= (1ull << 30);
+    }
+  }
+  r.grid_x = 1u << (n_outer - q);
+  r.grid_y = (unsigned)batch;
+  r.row_shift = q;
+  r.tpw = 1 << q;
+  return r;
+}
+
+// The launch policy of a tile stage: every threshold below is a measured one.
+TileRoute route_tile(const qmle_plan *p, size_t si, const TileRequest &rq) {
+  const Stage &st = p->stages[si];
+  const int meas = rq.meas, batch = rq.batch, n_obs = rq.n_obs;
+  const bool init_zero = rq.init_zero;
+  if ((meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) && !init_zero && n_obs >= 1 && n_obs <= 32) {
+    TileFamily k = expval_kernel_of(p, si, plan_sparse(p));
+    // (k_reg_measure on live input is the slowest way to take parities; its known-zero forms
+    // -- FOLD, mono -- keep priority)
+    if (k == TF_REG_MEASURE && rq.semi_single) k = TF_TILE;
+    if (k != TF_TILE) return route_reg_measure(p, st, k, batch);
+  }
+  TileRoute r;
+  const bool from_zero = rq.from_zero && plan_sparse(p);
+  uint32_t zin_local = 0, zin_outer = 0;
+  if (from_zero && st.zero_in && !init_zero) stage_known_zeros(p, st, &zin_local, &zin_outer);
+  const int n_ops = st.op_end - st.op_begin;
+  r.slots_in_lds = tile_lds_bytes(st.T, st.L, n_ops) <= 160 * 1024;
   // dense stages only (a stage that skips known zeros moves a fraction of the state, and what
   // it writes is read back at once): K2 dense 122.6 -> 119.8 ms per step
   // (the initialising pass only writes, and what it writes is read back by the next pass: plain
   // stores are 1.5 us per 2^24-amplitude state faster there, 22.9 vs 24.4)
-  a.nt = st.T < p->n && !(from_zero && st.zero_in) && !init_zero &&
-         ((uint64_t)batch << (p->n + 3)) >= (1ull << 30) ? 1 : 0;
-  a.mw_lean = meas == TM_STORE_MW && mw_lean(p->n, st) ? 1 : 0;  // (run_mw_fused asks the same question)
+  r.nt = st.T < p->n && !(from_zero && st.zero_in) && !init_zero &&
+         ((uint64_t)batch << (p->n + 3)) >= (1ull << 30);
+  r.mw_lean = meas == TM_STORE_MW && !rq.no_mw_lean && mw_lean_layout(p->n, st);
   // the state this pass stores is read back by the later reads only after >= 1 GiB more has been written: streaming
   // stores keep it from lingering dirty in the Infinity Cache, where its write-back would run into the first
   // later read (measured n = 28: that read 0.41 ms behind plain stores, 0.31 ms stand-alone).
@@ -1958,70 +2020,50 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
   // HBM idle instead of a write-back in progress.
   if ((meas == TM_STORE_MW || (meas == TM_STORE && !st.next_tile && !init_zero)) && st.T < p->n &&
       ((uint64_t)batch << (p->n + 3)) >= (1ull << 30))
-    a.nt = 1;
-  const size_t lds = tile_lds_bytes(st.T, st.L, a.slots_in_lds ? a.n_ops : 0);
-  if (FirstUse once{0}; once.first) {
-    QMLE_LDS_BASE_CHECK(k_tile<false>);
-    QMLE_LDS_BASE_CHECK(k_tile<true>);
-    QMLE_LDS_BASE_CHECK((k_tile<false, true>));
-    QMLE_LDS_BASE_CHECK((k_tile<true, true>));
-    HIPCHK(hipFuncSetAttribute((const void *)k_tile<false>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_tile<true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_tile<false, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    HIPCHK(hipFuncSetAttribute((const void *)k_tile<true, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    once.done();
-  }
-  bool has_dense4 = false;  // 16x16 Kraus superoperators: separate instantiation, so that the
-                            // common kernel keeps its register budget
-  for (int g = st.grp_begin; g < st.grp_end; ++g) has_dense4 |= p->op_groups[g].kind == GK_DENSE4 || p->op_groups[g].kind == GK_REG4X;
+    r.nt = true;
+  // 16x16 Kraus superoperators: separate instantiation, so that the common kernel keeps its register budget
+  for (int g = st.grp_begin; g < st.grp_end; ++g)
+    r.dense4 |= p->op_groups[g].kind == GK_DENSE4 || p->op_groups[g].kind == GK_REG4X;
   const unsigned tiles = 1u << (p->n - st.T);
   const int threads = tile_threads(st.T);
-  dim3 grid(tiles, (unsigned)batch);
+  r.threads = (unsigned)threads;
+  r.grid_x = tiles;
+  r.grid_y = (unsigned)batch;
   // All-live initialising pass (no known-zero bookkeeping downstream, so every tile must be
   // stored): the zeros come from a plain fill at the rate of a fill, tile 0 of every state from
   // the tile kernel behind it (15 us per 32 states) -- 22.4 -> 20.2 us per 2^24-amplitude state.
   // The compact launch stores all 2^T amplitudes of tile 0 of every state (k_tile2's TM_STORE branch, k_tile's
   // tile_epilogue, shifted or not), whatever lay there before; so where the caller knows the zeros outside tile 0 to
-  // be in memory already (FillReuse: an earlier filled pass of this stage in the same buffer, nothing stored
-  // since) the fill would write zeros over zeros and is left out.
+  // be in memory already (TileRequest::zeroed_states: an earlier filled pass of this stage in the same buffer, nothing
+  // stored since) the fill would write zeros over zeros and is left out.
   if (init_zero && !from_zero && meas == TM_STORE && st.T < p->n && tiles > 1 &&
       (st.fast_ok || st.T == kLdsMaxQubits) && p->n <= 28 && threads == (1 << (st.T - 4))) {
-    if (reuse && reuse->zeroed_states >= batch) {
-      reuse->elided = true;
-    } else {
-      launch_fill_zero(states, ((uint64_t)batch << p->n) / 2u /* float4 = two amplitudes */, stream);
-      if (reuse) { reuse->zeroed_states = batch; reuse->filled = true; }
-    }
-    a.compact = 1;  // grid = the tiles that can be non-zero = tile 0
-    a.tile_free = 0u;
-    grid.x = 1u;
+    if (rq.zeroed_states >= batch) r.fill_elided = true;
+    else r.fill = true;
+    r.compact = true;  // grid = the tiles that can be non-zero = tile 0
+    r.tile_free = 0u;
+    r.grid_x = 1u;
   } else if (st.shift) {
-    return QMLE_ERR_UNSUPPORTED;  // a top-first tile exists as the filled first pass of a run from |0..0> only
+    r.status = QMLE_ERR_UNSUPPORTED;  // a top-first tile exists as the filled first pass of a run from |0..0> only
+    return r;
   }
   if (from_zero && meas == TM_STORE && st.next_tile) {
     // the zero tiles are not even launched: the next tile stage never reads them
     const uint32_t all_outer = tiles - 1u;
-    const uint32_t zo = init_zero ? all_outer : a.zin_outer;
+    const uint32_t zo = init_zero ? all_outer : zin_outer;
     if (zo) {
-      a.compact = 1;
-      a.tile_free = all_outer & ~zo;
-      grid.x = 1u << __builtin_popcount(a.tile_free);
+      r.compact = true;
+      r.tile_free = all_outer & ~zo;
+      r.grid_x = 1u << __builtin_popcount(r.tile_free);
     }
   }
-  if (from_zero && cols && st.product_ok && !init_zero && meas == TM_STORE &&
+  if (from_zero && rq.fold_cols && st.product_ok && !init_zero && meas == TM_STORE &&
       threads == (1 << (st.T - 4))) {
     const int G = st.grp_end - st.grp_begin;
-    const int items = G * batch;
-    hipLaunchKernelGGL(k_fold_columns, dim3((items + 63) / 64), dim3(64), 0, stream, p->dev.d_ops,
-                       p->dev.d_op_groups + st.grp_begin, G, mats, p->mat_floats, cols, batch);
     // streaming layout when the pass may leave known-zero outputs unwritten, bit 0 is live and
     // there are at least 128 workgroups of 512 live amplitudes (K2, 32 states = 256 workgroups:
     // 49 vs 73 us in the tile layout)
-    uint32_t live = ~st.zero_in & (p->n >= 32 ? ~0u : ((1u << p->n) - 1u));
+    const uint32_t live = ~st.zero_in & (p->n >= 32 ? ~0u : ((1u << p->n) - 1u));
     const int n_live = __builtin_popcount(live);
     uint32_t gm_global = 0;
     for (int g = 0; g < G; ++g)
@@ -2029,110 +2071,32 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
         gm_global |= 1u << st.tile_bits[p->op_groups[st.grp_begin + g].bits[i]];
     const bool zeros_may_stay = st.next_tile || (st.zero_in & ~gm_global) == 0;
     if (zeros_may_stay && (live & 1u) && n_live >= 9 && ((uint64_t)batch << (n_live - 9)) >= 128) {
-      ProductArgs pa;
-      std::memset(&pa, 0, sizeof(pa));
-      pa.states = states;
-      pa.cols = cols;
-      pa.live_mask = live;
-      pa.n = p->n;
-      pa.G = G;
-      for (int g = 0; g < G; ++g)
-        for (int i = 0; i < 4; ++i)
-          pa.gpos[g][i] = (uint32_t)st.tile_bits[p->op_groups[st.grp_begin + g].bits[i]];
-      const dim3 pgrid(1u << (n_live - 9), (unsigned)batch);
+      r.family = TF_PRODUCT_STREAM;
+      r.grid_x = 1u << (n_live - 9);
+      r.threads = 256;
       const int n_out = n_live + 4 * G;  // amplitudes written per state = 2^n_out
       // >= 1 GiB written per launch: non-temporal stores (the pass itself is no faster, the
       // measuring pass that follows is: 3.13 -> 2.99 ms per K2 step)
-      if (((uint64_t)batch << (n_out + 3)) >= (1ull << 30))
-        hipLaunchKernelGGL(k_product_stream<true>, pgrid, dim3(256), 0, stream, pa);
-      else
-        hipLaunchKernelGGL(k_product_stream<false>, pgrid, dim3(256), 0, stream, pa);
-      HIPCHK(hipGetLastError());
-      return QMLE_OK;
+      r.nt = ((uint64_t)batch << (n_out + 3)) >= (1ull << 30);
+      return r;
     }
-    const size_t lds_p = 64 * sizeof(float2) + ((size_t)8 << (st.T - 4 * G)) +
-                         ((size_t)4 << (st.T - st.L)) + 64;
-    const uint32_t n_tiles = grid.x;
-    int tpw = 1;  // tiles per workgroup: the index tables are built once
-    while (tpw < 8 && (uint64_t)(n_tiles / (2 * tpw)) * batch >= 2048) tpw *= 2;
-    grid.x = (n_tiles + tpw - 1) / tpw;
-    hipLaunchKernelGGL(k_tile_product, grid, dim3(threads), lds_p, stream, a, cols, tpw, n_tiles);
-    HIPCHK(hipGetLastError());
-    return QMLE_OK;
+    r.family = TF_TILE_PRODUCT;
+    r.lds_bytes = 64 * sizeof(float2) + ((size_t)8 << (st.T - 4 * G)) + ((size_t)4 << (st.T - st.L)) + 64;
+    const uint32_t n_tiles = r.grid_x;
+    // tiles per workgroup: the index tables are built once
+    while (r.tpw < 8 && (uint64_t)(n_tiles / (2 * r.tpw)) * batch >= 2048) r.tpw *= 2;
+    r.grid_x = (n_tiles + r.tpw - 1) / r.tpw;
+    return r;
   }
   // fast path: all-live stage of (controlled) 2x2 gates -- table-addressed groups, CX folded
   // into the LDS layout, SGPR matrices (k_tile2)
   // (k_tile2 addresses a tile with 32-bit byte offsets inside one state: n <= 28; a whole state
   // of 10..13 qubits is one tile per sample: T == n, <Z> through the TM_EXPVAL epilogue)
   if (st.fast_ok && p->n <= 28 && threads == (1 << (st.T - 4)) && (st.T == p->n || meas != TM_EXPVAL)) {
-    if (FirstUse once{2}; once.first) {
-#define QMLE_T2_LDS(NT, ME, MU)                                                   \
-  QMLE_LDS_BASE_CHECK((k_tile2<NT, ME, MU>));                                      \
-  HIPCHK(hipFuncSetAttribute((const void *)k_tile2<NT, ME, MU>,                    \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
-      QMLE_T2_LDS(false, false, false); QMLE_T2_LDS(true, false, false);
-      QMLE_T2_LDS(false, true, false); QMLE_T2_LDS(true, true, false);
-      QMLE_T2_LDS(false, false, true); QMLE_T2_LDS(true, false, true);
-      QMLE_T2_LDS(false, true, true); QMLE_T2_LDS(true, true, true);
-#undef QMLE_T2_LDS
-      QMLE_LDS_BASE_CHECK((k_tile2<true, true, true, false, false, true>));
-      QMLE_LDS_BASE_CHECK((k_tile2<false, true, true, false, false, true>));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<true, true, true, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<false, true, true, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      QMLE_LDS_BASE_CHECK((k_tile2<false, false, false, true>));
-      QMLE_LDS_BASE_CHECK((k_tile2<false, true, false, true>));
-      QMLE_LDS_BASE_CHECK((k_tile2<false, true, false, false, true>));
-      QMLE_LDS_BASE_CHECK((k_tile2<true, true, false, false, true>));
-      QMLE_LDS_BASE_CHECK((k_tile2<false, true, false, true, true>));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<false, true, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<true, true, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<false, true, false, true, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<false, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile2<false, true, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      once.done();
-    }
-    Tile2Args f;
+    r.family = TF_TILE2;
     for (int g = st.fast_begin; g < st.fast_end; ++g)
-      if (p->groups2[g].sync & kGroupProduct) st.product_form_last_run = true;  // (every k_tile2 instantiation takes the form)
-    f.groups = p->dev.d_groups2 + st.fast_begin;
-    f.ops = p->dev.d_ops2;
-    f.tbl = p->dev.d_tbl2;
-    f.n_groups = st.fast_end - st.fast_begin;
-    f.n_ops_stage = 0;
-    for (int g = st.fast_begin; g < st.fast_end; ++g) f.n_ops_stage += p->groups2[g].n_ops;
-    f.gtab = st.fast_gtab;
-    {  // outer bit positions (ascending) as contiguous runs
-      int r = 0;
-      const int n_outer = p->n - st.T;
-      for (int i = 0; i < n_outer && r <= 6;) {
-        int len = 1;
-        while (i + len < n_outer && st.outer_bits[i + len] == st.outer_bits[i] + len) ++len;
-        if (r < 6) {
-          f.run_off[r] = (uint32_t)i;
-          f.run_mask[r] = len >= 32 ? 0xffffffffu : ((1u << len) - 1u);
-          f.run_pos[r] = (uint32_t)st.outer_bits[i];
-        }
-        ++r;
-        i += len;
-      }
-      f.n_runs = r <= 6 ? r : -1;
-      for (int k = r < 6 ? r : 6; k < 6; ++k) f.run_off[k] = f.run_mask[k] = f.run_pos[k] = 0;
-    }
-    // local bits 0 .. top of a lane's index (bits it never sets are harmless) -> global positions, as runs
-    auto lane_runs = [&](int top) { f.n_in_runs = stage_lane_runs(st, top, f.in_off, f.in_mask, f.in_pos); };
-    lane_runs(st.T - 4);  // index 2 tid
-    for (unsigned u = 0; u < 8; ++u)
-      f.uoff8[u] = (((u & 1u) << st.tile_bits[st.T - 3]) | (((u >> 1) & 1u) << st.tile_bits[st.T - 2]) |
-                    (((u >> 2) & 1u) << st.tile_bits[st.T - 1])) << 3;
-    f.walk = kWalkSyncStaged | kWalkSyncTileEnd;
-    for (int k = 0; k < 4; ++k) f.dma_delta[k] = 0;
+      if (p->groups2[g].sync & kGroupProduct) r.product_form = true;  // (every k_tile2 instantiation takes the form)
+    r.walk = kWalkSyncStaged | kWalkSyncTileEnd;
     // plain all-live stages: several consecutive tiles per workgroup (next tile prefetched into
     // registers), as long as the grid still fills the chip a few times over
     // (default 4 for storing passes, 8 for the measuring pass, whose per-workgroup reduction is
@@ -2142,136 +2106,102 @@ int launch_tile(const qmle_plan *p, const Stage &st, float2 *states, const float
     // for the next tile's prefetch: 792 us for the pass against 678 with a row per tile, 473 without sums)
     const int tpw_max = (meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) ? 8 : 4;
     const uint64_t min_wgs = 5120;
-    f.tpw = 1;
-    f.tile_stride = 0;
     // (known zeros inside the tile are fine -- the walk's loads skip them; known-zero TILES are not)
-    const bool multi_zin = std::getenv("QMLE_NO_MULTI_ZIN") == nullptr;  // (read per launch: the A/B test toggles it)
+    const bool multi_zin = !rq.no_multi_zin;
     // (Z-parity observables walk too -- tile_m_accumulate -- when the caller can take rows per walk)
-    const bool masks_walk = meas == TM_EXPVAL_MASKS && n_obs <= kMaskMultiObs && row_shift && st.T >= 10;
-    if (!a.init_zero && (!a.zin_local || multi_zin) && !a.zin_outer && !a.compact && st.T < p->n &&
+    const bool masks_walk = meas == TM_EXPVAL_MASKS && n_obs <= kMaskMultiObs && rq.multi_rows && st.T >= 10;
+    if (!init_zero && (!zin_local || multi_zin) && !zin_outer && !r.compact && st.T < p->n &&
         (meas == TM_STORE || meas == TM_PROBS || meas == TM_EXPVAL_PARTIAL || masks_walk)) {
       // (consecutive tile indices differ in the lowest run of outer bit positions only)
       int run0 = 1;
       while (run0 < p->n - st.T && st.outer_bits[run0] == st.outer_bits[0] + run0) ++run0;
-      f.tile_stride = 1u << st.outer_bits[0];
-      while (f.tpw * 2 <= tpw_max && f.tpw * 2 <= (1 << run0) && grid.x % 2u == 0 &&
-             (uint64_t)(grid.x / 2u) * grid.y >= min_wgs) {
-        f.tpw *= 2;
-        grid.x /= 2u;
+      while (r.tpw * 2 <= tpw_max && r.tpw * 2 <= (1 << run0) && r.grid_x % 2u == 0 &&
+             (uint64_t)(r.grid_x / 2u) * r.grid_y >= min_wgs) {
+        r.tpw *= 2;
+        r.grid_x /= 2u;
       }
     }
-    if ((meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) && f.tpw > 1) {
-      if (!row_shift || f.tpw > 8) {  // the caller must know the row layout
-        grid.x *= (unsigned)f.tpw;
-        f.tpw = 1;
+    if ((meas == TM_EXPVAL_PARTIAL || meas == TM_EXPVAL_MASKS) && r.tpw > 1) {
+      if (!rq.multi_rows || r.tpw > 8) {  // the caller must know the row layout
+        r.grid_x *= (unsigned)r.tpw;
+        r.tpw = 1;
       } else {
-        *row_shift = 31 - __builtin_clz((unsigned)f.tpw);
+        r.row_shift = 31 - __builtin_clz((unsigned)r.tpw);
       }
     }
-    // The measuring walk takes <Z> from the last group's registers (tile_zr_accumulate): thread q finds local
-    // position j in column j of the per-wave sums, the total in column kZrTotal (outer positions keep 32 + i)
-    if (meas == TM_EXPVAL_PARTIAL && f.tpw > 1 && !st.zreg_ok) return QMLE_ERR_INTERNAL;  // (build_fast_groups sets it)
-    if (meas == TM_EXPVAL_PARTIAL && f.tpw > 1) {
-      static_assert(sizeof(st.zreg) <= sizeof(a.obs_local), "the records travel in TileArgs::obs_local");
-      std::memcpy(a.obs_local, st.zreg, sizeof(st.zreg));
-      for (int j = 0; j < st.T; ++j) a.qsrc[(int)st.tile_bits[j]] = (uint8_t)j;
-      a.qsrc[QMLE_MAX_QUBITS] = (uint8_t)kZrTotal;
-      if (from_regs) *from_regs = true;
+    // The measuring walk takes <Z> from the last group's registers (tile_zr_accumulate)
+    if (meas == TM_EXPVAL_PARTIAL && r.tpw > 1) {
+      if (!st.zreg_ok) {  // (build_fast_groups sets it)
+        r.status = QMLE_ERR_INTERNAL;
+        return r;
+      }
+      r.from_regs = true;
       // ... and elides the barriers between phases in which every wave keeps its slots (mark_wave_private_phases)
-      f.walk = (p->groups2[st.fast_begin].sync & 1 ? kWalkSyncStaged : 0u) | (st.sync_tile_end ? kWalkSyncTileEnd : 0u);
-      if (st.slab_load) {  // the lane's local index has bits 1..6 and 10..T-1 set, its 8 float4 are local bits 7..9
-        f.walk |= kWalkSlab;
-        f.gtab = st.fast_gtab_slab;
-        lane_runs(st.T - 1);
-        for (unsigned u = 0; u < 8; ++u)
-          f.uoff8[u] = (((u & 1u) << st.tile_bits[7]) | (((u >> 1) & 1u) << st.tile_bits[8]) |
-                        (((u >> 2) & 1u) << st.tile_bits[9])) << 3;
+      r.wave_private = st.wave_private;
+      r.walk = (p->groups2[st.fast_begin].sync & 1 ? kWalkSyncStaged : 0u) | (st.sync_tile_end ? kWalkSyncTileEnd : 0u);
+      if (st.slab_load) {
+        r.walk |= kWalkSlab;
         // ... and by LDS DMA where each wave's slab stays its own from one tile's last gather to the next tile's
         // first, and every amplitude of the tile is loaded (known-zero walks zero-fill and load selectively)
-        if (st.dma_tables && !a.zin_local) {
-          f.walk |= kWalkDma;
-          f.gtab = st.fast_gtab_dma;
-          for (int k = 0; k < 4; ++k) f.dma_delta[k] = st.dma_delta[k];
-          if (by_dma) *by_dma = true;
-          // ... and its last group runs where the group in front of it left the amplitudes, two lane swaps apart
-          // (Stage::lane_swap_last): the records of that frame travel in place of the table form's
-          if (st.lane_swap_last) {
-            f.walk |= kWalkLaneSwap | (st.lane_swap_cross ? kWalkLaneSwapCross : 0u);
-            static_assert(sizeof(st.zreg_swap) == sizeof(st.zreg), "one record layout");
-            std::memcpy(a.obs_local, st.zreg_swap, sizeof(st.zreg_swap));
-            if (by_lane_swap) *by_lane_swap = true;
-          }
-        }
+        const bool dma = walk_by_dma(st, zin_local);
+        if (dma) r.walk |= kWalkDma;
+        // ... and its last group runs where the group in front of it left the amplitudes, two lane swaps apart
+        if (walk_by_lane_swap(st, dma)) r.walk |= kWalkLaneSwap | (st.lane_swap_cross ? kWalkLaneSwapCross : 0u);
       }
     }
     // T >= 10: the per-tile epilogues' scratch fits inside the tile; the whole-state <Z> epilogue
     // reduces while amplitudes are still being read and gets its own 288 floats
     // (whole_state_expval: one float per observable and wave -- 128 B at 10 qubits instead of the
     // 1152 B of round 2's epilogue: 18-19 instead of 17 single-wave workgroups per CU)
-    const size_t lds2 = ((size_t)8 << st.T) +
-                        (meas == TM_EXPVAL ? (size_t)QMLE_MAX_QUBITS * (threads >= kWave ? threads / kWave : 1) * sizeof(float) : 0);
-    const bool measure = !(meas == TM_STORE || meas == TM_PROBS);
-#define QMLE_T2_GO(NT, ME, MU) \
-  hipLaunchKernelGGL((k_tile2<NT, ME, MU>), grid, dim3(threads), lds2, stream, a, f)
-    const bool multi = f.tpw > 1;
-    if (meas == TM_STORE_MW || meas == TM_MW_ONLY) {
-      if (st.T == p->n) hipLaunchKernelGGL((k_tile2<false, true, false, true, true>), grid, dim3(threads), lds2, stream, a, f);
-      else if (a.nt) hipLaunchKernelGGL((k_tile2<true, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-      else hipLaunchKernelGGL((k_tile2<false, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-    } else if (st.T == p->n && !multi && !a.nt) {  // the whole state in one tile (10..13 qubits)
-      if (measure) hipLaunchKernelGGL((k_tile2<false, true, false, true>), grid, dim3(threads), lds2, stream, a, f);
-      else hipLaunchKernelGGL((k_tile2<false, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-    } else if (measure && multi && meas == TM_EXPVAL_MASKS) {
-      if (a.nt) hipLaunchKernelGGL((k_tile2<true, true, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-      else hipLaunchKernelGGL((k_tile2<false, true, true, false, false, true>), grid, dim3(threads), lds2, stream, a, f);
-    } else if (measure) {
-      if (multi) { if (a.nt) QMLE_T2_GO(true, true, true); else QMLE_T2_GO(false, true, true); }
-      else { if (a.nt) QMLE_T2_GO(true, true, false); else QMLE_T2_GO(false, true, false); }
-    } else {
-      if (multi) { if (a.nt) QMLE_T2_GO(true, false, true); else QMLE_T2_GO(false, false, true); }
-      else { if (a.nt) QMLE_T2_GO(true, false, false); else QMLE_T2_GO(false, false, false); }
-    }
-#undef QMLE_T2_GO
-    HIPCHK(hipGetLastError());
-    return QMLE_OK;
+    r.lds_bytes = ((size_t)8 << st.T) +
+                  (meas == TM_EXPVAL ? (size_t)QMLE_MAX_QUBITS * (threads >= kWave ? threads / kWave : 1) * sizeof(float) : 0);
+    r.measure = !(meas == TM_STORE || meas == TM_PROBS);
+    r.multi = r.tpw > 1;
+    r.mw = meas == TM_STORE_MW || meas == TM_MW_ONLY;
+    // the whole state in one tile (10..13 qubits)
+    r.ws = r.mw ? st.T == p->n : st.T == p->n && !r.multi && !r.nt;
+    r.masks = !r.mw && !r.ws && r.measure && r.multi && meas == TM_EXPVAL_MASKS;
+    return r;
   }
+  r.lds_bytes = tile_lds_bytes(st.T, st.L, r.slots_in_lds ? n_ops : 0);
   if (meas == TM_STORE_MW || meas == TM_MW_ONLY) {
-    if (st.T < 10 || threads != (1 << (st.T - 4))) return QMLE_ERR_UNSUPPORTED;  // (callers check mw_fusable)
-    if (has_dense4) hipLaunchKernelGGL((k_tile<true, true>), grid, dim3(threads), lds, stream, a);
-    else hipLaunchKernelGGL((k_tile<false, true>), grid, dim3(threads), lds, stream, a);
-  } else if (has_dense4) hipLaunchKernelGGL(k_tile<true>, grid, dim3(threads), lds, stream, a);
-  else hipLaunchKernelGGL(k_tile<false>, grid, dim3(threads), lds, stream, a);
-  HIPCHK(hipGetLastError());
-  return QMLE_OK;
+    if (st.T < 10 || threads != (1 << (st.T - 4))) {  // (callers check mw_fusable)
+      r.status = QMLE_ERR_UNSUPPORTED;
+      return r;
+    }
+    r.mw = true;
+  }
+  return r;
 }
 
-// k_reg_measure* takes the last pass of a <Z> run when all its gates share one register-tile
-// group (expval_kernel_of, qmle_plan.cpp)
-int reg_measure_kind(const qmle_plan *p, size_t si, int n_obs) {
-  if (n_obs < 1 || n_obs > 32) return 0;
-  return expval_kernel_of(p, si, plan_sparse(p));
+namespace {
+
+// the route's share of the kernel arguments
+TileArgs route_tile_args(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq,
+                         const TileRoute &r) {
+  TileArgs a = fill_tile_args(p, st, b.states, b.mats, b.angles, rq.init_zero, rq.meas, b.out, b.obs_masks, rq.n_obs,
+                              rq.from_zero && plan_sparse(p));
+  a.slots_in_lds = r.slots_in_lds;
+  a.nt = r.nt;
+  a.mw_lean = r.mw_lean;
+  a.compact = r.compact;
+  a.tile_free = r.tile_free;
+  return a;
 }
 
-int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *states,
-                              const float *mats, const float *angles, int batch, void *out,
-                              const uint32_t *obs_masks, int n_obs, hipStream_t stream, int *q_out,
-                              float *coef) {
-  TileArgs a = fill_tile_args(p, st, states, mats, angles, false, TM_EXPVAL_MASKS, out, obs_masks,
-                              n_obs, plan_sparse(p));
+int issue_reg_measure(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq,
+                      const TileRoute &r, hipStream_t stream) {
+  const int batch = rq.batch, n_obs = rq.n_obs, n_outer = p->n - st.T;
+  TileArgs a = fill_tile_args(p, st, b.states, b.mats, b.angles, false, TM_EXPVAL_MASKS, b.out, b.obs_masks, n_obs,
+                              plan_sparse(p));
   a.slots_in_lds = 1;
-  const int n_outer = p->n - st.T;
-  // ~4096 workgroups per launch when the batch allows, at most 64 tiles per workgroup
-  int q = 0;
-  while (q < 6 && q < n_outer && (((uint64_t)batch << n_outer) >> (q + 1)) >= 4096) ++q;
-  if (kind == 3) q = 5;
-  const size_t lds = (size_t)a.n_ops * sizeof(OpSlot) + (132 + 16 * 32 + 128) * sizeof(uint32_t);
-  dim3 grid(1u << (n_outer - q), (unsigned)batch);
-  if (kind == 3) {
+  const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
+  if (r.family == TF_REG_MEASURE_MONO) {
     const OpGroup &g = p->op_groups[st.grp_begin];
     MonoObs mo;
     std::memset(&mo, 0, sizeof(mo));
     for (int k = 0; k < n_obs; ++k) {
-      const uint32_t m = obs_masks[k];
+      const uint32_t m = b.obs_masks[k];
       int tb = 0;
       for (int j = 0; j < st.T; ++j) {
         const uint32_t bitv = (m >> st.tile_bits[j]) & 1u;
@@ -2284,32 +2214,210 @@ int launch_reg_measure(const qmle_plan *p, const Stage &st, int kind, float2 *st
       for (int j = 0; j < n_outer; ++j) mo.out[k] |= ((m >> st.outer_bits[j]) & 1u) << j;
     }
     hipLaunchKernelGGL(k_mono_coef, dim3((batch + 63) / 64), dim3(64), 0, stream, p->dev.d_ops,
-                       p->dev.d_op_groups + st.grp_begin, mats, p->mat_floats, mo, n_obs, coef, batch);
-    if (g.bits[0] != 0 && st.tile_bits[0] == 0 && !(a.zin_local & 1u) && st.T >= 11 &&
-        n_outer >= 4) {
-      q = 4;
-      grid.x = 1u << (n_outer - q);
-      // live amplitudes per launch >= 1 GiB: stream them past the caches (0.427 -> 0.38 ms per
-      // 256 states of K2; k_direct_1q's measurements say the opposite below the cache size)
-      const int n_live = p->n - __builtin_popcount(st.zero_in);
-      const bool nt = ((uint64_t)batch << (n_live + 3)) >= (1ull << 30);
-      if (nt)
-        hipLaunchKernelGGL((k_reg_measure_mono<4, true, true>), grid, dim3(1u << (st.T - 5)),
-                           16 * 32 * sizeof(float), stream, a, mo, coef);
-      else
-        hipLaunchKernelGGL((k_reg_measure_mono<4, true, false>), grid, dim3(1u << (st.T - 5)),
-                           16 * 32 * sizeof(float), stream, a, mo, coef);
-    } else {
-      hipLaunchKernelGGL((k_reg_measure_mono<5, false, false>), grid, dim3(1u << (st.T - 4)),
-                         16 * 32 * sizeof(float), stream, a, mo, coef);
-    }
-  } else if (kind == 2)
-    hipLaunchKernelGGL(k_reg_measure<true>, grid, dim3(1u << (st.T - 4)), lds, stream, a, q);
+                       p->dev.d_op_groups + st.grp_begin, b.mats, p->mat_floats, mo, n_obs, b.coef, batch);
+    if (r.pair && r.nt)
+      hipLaunchKernelGGL((k_reg_measure_mono<4, true, true>), grid, block, r.lds_bytes, stream, a, mo, b.coef);
+    else if (r.pair)
+      hipLaunchKernelGGL((k_reg_measure_mono<4, true, false>), grid, block, r.lds_bytes, stream, a, mo, b.coef);
+    else
+      hipLaunchKernelGGL((k_reg_measure_mono<5, false, false>), grid, block, r.lds_bytes, stream, a, mo, b.coef);
+  } else if (r.family == TF_REG_MEASURE_FOLD)
+    hipLaunchKernelGGL(k_reg_measure<true>, grid, block, r.lds_bytes, stream, a, r.row_shift);
   else
-    hipLaunchKernelGGL(k_reg_measure<false>, grid, dim3(1u << (st.T - 4)), lds, stream, a, q);
+    hipLaunchKernelGGL(k_reg_measure<false>, grid, block, r.lds_bytes, stream, a, r.row_shift);
   HIPCHK(hipGetLastError());
-  *q_out = q;
   return QMLE_OK;
 }
 
+int issue_product(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq, const TileRoute &r,
+                  hipStream_t stream) {
+  const int G = st.grp_end - st.grp_begin, batch = rq.batch;
+  hipLaunchKernelGGL(k_fold_columns, dim3((G * batch + 63) / 64), dim3(64), 0, stream, p->dev.d_ops,
+                     p->dev.d_op_groups + st.grp_begin, G, b.mats, p->mat_floats, b.cols, batch);
+  const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
+  if (r.family == TF_PRODUCT_STREAM) {
+    ProductArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    pa.states = b.states;
+    pa.cols = b.cols;
+    pa.live_mask = ~st.zero_in & (p->n >= 32 ? ~0u : ((1u << p->n) - 1u));
+    pa.n = p->n;
+    pa.G = G;
+    for (int g = 0; g < G; ++g)
+      for (int i = 0; i < 4; ++i)
+        pa.gpos[g][i] = (uint32_t)st.tile_bits[p->op_groups[st.grp_begin + g].bits[i]];
+    if (r.nt) hipLaunchKernelGGL(k_product_stream<true>, grid, block, 0, stream, pa);
+    else hipLaunchKernelGGL(k_product_stream<false>, grid, block, 0, stream, pa);
+  } else {
+    const TileArgs a = route_tile_args(p, st, b, rq, r);
+    const uint32_t n_tiles = r.compact ? 1u << __builtin_popcount(r.tile_free) : 1u << (p->n - st.T);
+    hipLaunchKernelGGL(k_tile_product, grid, block, r.lds_bytes, stream, a, b.cols, r.tpw, n_tiles);
+  }
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int issue_tile(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq, const TileRoute &r,
+               hipStream_t stream) {
+  if (FirstUse once{0}; once.first) {
+#define QMLE_X(D4, MW)                      \
+  QMLE_LDS_BASE_CHECK(QMLE_TILE1(D4, MW)); \
+  HIPCHK(hipFuncSetAttribute((const void *)QMLE_TILE1(D4, MW), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    QMLE_TILE_INSTANCES(QMLE_X)
+#undef QMLE_X
+    once.done();
+  }
+  const TileArgs a = route_tile_args(p, st, b, rq, r);
+  const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
+#define QMLE_X(D4, MW) \
+  if (r.dense4 == D4 && r.mw == MW) hipLaunchKernelGGL(QMLE_TILE1(D4, MW), grid, block, r.lds_bytes, stream, a); else
+  QMLE_TILE_INSTANCES(QMLE_X) return QMLE_ERR_INTERNAL;
+#undef QMLE_X
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int issue_tile2(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq, const TileRoute &r,
+                hipStream_t stream) {
+  if (FirstUse once{1}; once.first) {
+#define QMLE_X(NT, ME, MU, WS, MW, MA)                      \
+  QMLE_LDS_BASE_CHECK(QMLE_TILE2(NT, ME, MU, WS, MW, MA)); \
+  HIPCHK(hipFuncSetAttribute((const void *)QMLE_TILE2(NT, ME, MU, WS, MW, MA), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    QMLE_TILE2_INSTANCES(QMLE_X)
+#undef QMLE_X
+    once.done();
+  }
+  TileArgs a = route_tile_args(p, st, b, rq, r);
+  Tile2Args f;
+  f.groups = p->dev.d_groups2 + st.fast_begin;
+  f.ops = p->dev.d_ops2;
+  f.tbl = p->dev.d_tbl2;
+  f.n_groups = st.fast_end - st.fast_begin;
+  f.n_ops_stage = 0;
+  for (int g = st.fast_begin; g < st.fast_end; ++g) f.n_ops_stage += p->groups2[g].n_ops;
+  f.gtab = st.fast_gtab;
+  {  // outer bit positions (ascending) as contiguous runs
+    int nr = 0;
+    const int n_outer = p->n - st.T;
+    for (int i = 0; i < n_outer && nr <= 6;) {
+      int len = 1;
+      while (i + len < n_outer && st.outer_bits[i + len] == st.outer_bits[i] + len) ++len;
+      if (nr < 6) {
+        f.run_off[nr] = (uint32_t)i;
+        f.run_mask[nr] = len >= 32 ? 0xffffffffu : ((1u << len) - 1u);
+        f.run_pos[nr] = (uint32_t)st.outer_bits[i];
+      }
+      ++nr;
+      i += len;
+    }
+    f.n_runs = nr <= 6 ? nr : -1;
+    for (int k = nr < 6 ? nr : 6; k < 6; ++k) f.run_off[k] = f.run_mask[k] = f.run_pos[k] = 0;
+  }
+  // local bits 0 .. top of a lane's index (bits it never sets are harmless) -> global positions, as runs
+  auto lane_runs = [&](int top) { f.n_in_runs = stage_lane_runs(st, top, f.in_off, f.in_mask, f.in_pos); };
+  lane_runs(st.T - 4);  // index 2 tid
+  for (unsigned u = 0; u < 8; ++u)
+    f.uoff8[u] = (((u & 1u) << st.tile_bits[st.T - 3]) | (((u >> 1) & 1u) << st.tile_bits[st.T - 2]) |
+                  (((u >> 2) & 1u) << st.tile_bits[st.T - 1])) << 3;
+  f.walk = r.walk;
+  for (int k = 0; k < 4; ++k) f.dma_delta[k] = 0;
+  f.tpw = r.tpw;
+  // (consecutive tile indices of a walk differ in the lowest run of outer bit positions only)
+  f.tile_stride = r.tpw > 1 ? 1u << st.outer_bits[0] : 0u;
+  if (r.from_regs) {
+    // thread q finds local position j in column j of the per-wave sums, the total in column kZrTotal (outer positions
+    // keep 32 + i)
+    static_assert(sizeof(st.zreg) <= sizeof(a.obs_local), "the records travel in TileArgs::obs_local");
+    std::memcpy(a.obs_local, st.zreg, sizeof(st.zreg));
+    for (int j = 0; j < st.T; ++j) a.qsrc[(int)st.tile_bits[j]] = (uint8_t)j;
+    a.qsrc[QMLE_MAX_QUBITS] = (uint8_t)kZrTotal;
+    if (r.walk & kWalkSlab) {  // the lane's local index has bits 1..6 and 10..T-1 set, its 8 float4 are local bits 7..9
+      f.gtab = st.fast_gtab_slab;
+      lane_runs(st.T - 1);
+      for (unsigned u = 0; u < 8; ++u)
+        f.uoff8[u] = (((u & 1u) << st.tile_bits[7]) | (((u >> 1) & 1u) << st.tile_bits[8]) |
+                      (((u >> 2) & 1u) << st.tile_bits[9])) << 3;
+    }
+    if (r.walk & kWalkDma) {
+      f.gtab = st.fast_gtab_dma;
+      for (int k = 0; k < 4; ++k) f.dma_delta[k] = st.dma_delta[k];
+    }
+    if (r.walk & kWalkLaneSwap) {  // (Stage::lane_swap_last): the records of that frame travel in place of the table form's
+      static_assert(sizeof(st.zreg_swap) == sizeof(st.zreg), "one record layout");
+      std::memcpy(a.obs_local, st.zreg_swap, sizeof(st.zreg_swap));
+    }
+  }
+  const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
+#define QMLE_X(NT, ME, MU, WS, MW, MA)                                                                         \
+  if (r.nt == NT && r.measure == ME && r.multi == MU && r.ws == WS && r.mw == MW && r.masks == MA)             \
+    hipLaunchKernelGGL(QMLE_TILE2(NT, ME, MU, WS, MW, MA), grid, block, r.lds_bytes, stream, a, f);           \
+  else
+  QMLE_TILE2_INSTANCES(QMLE_X) return QMLE_ERR_INTERNAL;
+#undef QMLE_X
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+}  // namespace
+
+int launch_tile(const qmle_plan *p, size_t stage, const TileBuffers &b, TileRequest rq, hipStream_t stream,
+                TileRoute *taken) {
+  const Stage &st = p->stages[stage];
+  rq.no_multi_zin = std::getenv("QMLE_NO_MULTI_ZIN") != nullptr;  // (read per launch: the A/B test toggles it)
+  rq.no_mw_lean = rq.meas == TM_STORE_MW && mw_no_lean_switch();  // (run_mw_fused asks mw_lean, the same question)
+  const TileRoute r = route_tile(p, stage, rq);
+  if (taken) *taken = r;
+  if (r.status != QMLE_OK) return r.status;
+  if (r.fill) launch_fill_zero(b.states, ((uint64_t)rq.batch << p->n) / 2u /* float4 = two amplitudes */, stream);
+  switch (r.family) {
+    case TF_TILE: return issue_tile(p, st, b, rq, r, stream);
+    case TF_TILE2: return issue_tile2(p, st, b, rq, r, stream);
+    case TF_TILE_PRODUCT:
+    case TF_PRODUCT_STREAM: return issue_product(p, st, b, rq, r, stream);
+    default: return issue_reg_measure(p, st, b, rq, r, stream);
+  }
+}
+
 }  // namespace qmle
+
+// Host only: route_tile's answer as JSON (the launch policy, testable without a GPU).
+int qmle_plan_tile_route(const qmle_plan *plan, int stage, int batch, int meas, int n_obs, unsigned request_flags,
+                         char *buf, size_t cap) {
+  using namespace qmle;
+  if (!plan || stage < 0 || (size_t)stage >= plan->stages.size() || plan->stages[stage].kind != ST_TILE || batch < 1 ||
+      batch > kMaxGridY || meas < TM_STORE || meas > TM_MW_ONLY || n_obs < 0 || n_obs > QMLE_MAX_QUBITS)
+    return QMLE_ERR_INVALID_ARG;
+  TileRequest rq;
+  rq.batch = batch;
+  rq.meas = meas;
+  rq.n_obs = n_obs;
+  rq.init_zero = request_flags & QMLE_ROUTE_INIT_ZERO;
+  rq.from_zero = request_flags & QMLE_ROUTE_FROM_ZERO;
+  rq.fold_cols = request_flags & QMLE_ROUTE_FOLD_COLS;
+  rq.multi_rows = request_flags & QMLE_ROUTE_MULTI_ROWS;
+  rq.zeroed_states = (request_flags & QMLE_ROUTE_ZEROS_IN_PLACE) ? batch : 0;
+  rq.semi_single = request_flags & QMLE_ROUTE_SEMI_SINGLE;
+  rq.no_multi_zin = request_flags & QMLE_ROUTE_NO_MULTI_ZIN;
+  rq.no_mw_lean = request_flags & QMLE_ROUTE_NO_MW_LEAN;
+  const TileRoute r = route_tile(plan, (size_t)stage, rq);
+  auto tf = [](bool v) { return v ? "true" : "false"; };
+  char js[1024];
+  const int len = std::snprintf(
+      js, sizeof(js),
+      "{\"status\":%d,\"family\":\"%s\",\"dense4\":%s,\"mw\":%s,\"nt\":%s,\"measure\":%s,\"multi\":%s,\"ws\":%s,"
+      "\"masks\":%s,\"mono_q\":%d,\"pair\":%s,\"grid\":[%u,%u],\"threads\":%u,\"lds_bytes\":%zu,\"compact\":%s,"
+      "\"tile_free\":%u,\"mw_lean\":%s,\"slots_in_lds\":%s,\"fill\":%s,\"fill_elided\":%s,\"tiles_per_workgroup\":%d,"
+      "\"row_shift\":%d,\"walk_slab\":%s,\"walk_sync_staged\":%s,\"walk_sync_tile_end\":%s,\"staging_dma\":%s,"
+      "\"lane_swap\":%s,\"lane_swap_crossed\":%s,\"from_registers\":%s,\"wave_private\":%s,\"product_form\":%s}",
+      r.status, kTileFamilyNames[r.family], tf(r.dense4), tf(r.mw), tf(r.nt), tf(r.measure), tf(r.multi), tf(r.ws),
+      tf(r.masks), r.mono_q, tf(r.pair), r.grid_x, r.grid_y, r.threads, r.lds_bytes, tf(r.compact), r.tile_free,
+      tf(r.mw_lean), tf(r.slots_in_lds), tf(r.fill), tf(r.fill_elided), r.tpw, r.row_shift, tf(r.walk & kWalkSlab),
+      tf(r.walk & kWalkSyncStaged), tf(r.walk & kWalkSyncTileEnd), tf(r.walk & kWalkDma), tf(r.walk & kWalkLaneSwap),
+      tf(r.walk & kWalkLaneSwapCross), tf(r.from_regs), tf(r.wave_private), tf(r.product_form));
+  if (buf && cap > 0) {
+    const size_t nc = (size_t)len < cap - 1 ? (size_t)len : cap - 1;
+    std::memcpy(buf, js, nc);
+    buf[nc] = 0;
+  }
+  return len;
+}
