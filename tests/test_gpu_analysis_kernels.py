@@ -399,11 +399,12 @@ def test_expval_parity_groups_of_eight(n, groups):
 
 
 # ---- measurements of vectorised density matrices -------------------------------------------------------------------
-@pytest.mark.parametrize("n", list(range(1, 11)))
+@pytest.mark.parametrize("n", list(range(1, 12)))
 def test_density_probs_and_expval_of_mixed_states(n):
+    """n = 11: one vec(rho) is 32 MiB, a batch of 2."""
     N = _N()
     rng = np.random.default_rng(1100 + n)
-    B, K = 3, 4
+    B, K = (3 if n < 11 else 2), 4
     rho = np.zeros((B, 1 << n, 1 << n), dtype=np.complex128)
     for b in range(B):
         w = rng.random(K)

@@ -206,8 +206,28 @@ def test_two_calls_give_the_same_bits(dtype):
     assert torch.equal(a, b)
 
 
-@pytest.mark.parametrize("n", [1, 2, 5])
+def _index_mask(n, wire_mask):
+    """Wire mask (bit w = wire w) -> mask of the basis index, whose most significant bit is wire 0."""
+    return sum(((wire_mask >> w) & 1) << (n - 1 - w) for w in range(n))
+
+
+def trace_of_word(rho, n, x, z):
+    """Re Tr(P rho) per matrix, P = i^ny X^x Z^z: P[j ^ x, j] = i^ny (-1)^(j . z) are its only entries, so the trace
+    gathers the 2^n elements rho[j, j ^ x] -- no 2^n x 2^n word matrix."""
+    j = np.arange(1 << n)
+    xi, zi = _index_mask(n, x), _index_mask(n, z)
+    parity = np.zeros_like(j)
+    for b in range(n):
+        parity ^= ((j & zi) >> b) & 1
+    sign = 1.0 - 2.0 * parity
+    ny = bin(x & z).count("1")
+    return np.real((1j ** ny) * (rho[:, j, j ^ xi].astype(np.complex128) * sign).sum(axis=1))
+
+
+@pytest.mark.parametrize("n", [1, 2, 5, 9, 10])
 def test_density_words_against_the_trace(n):
+    """n = 9, 10: D = 2^n > 256 threads, so the kernel's loop over j makes two and four trips, with 200 random words
+    whose x masks have high bits set."""
     from test_pauli_observables_cpu import word_matrix
 
     N = _N()
@@ -215,14 +235,34 @@ def test_density_words_against_the_trace(n):
     D, B = 1 << n, 3
     rho = (rng.standard_normal((B, D, D)) + 1j * rng.standard_normal((B, D, D))).astype(np.complex64)
     rho /= np.abs(rho).sum(axis=(1, 2), keepdims=True)   # sum |rho_ij| = 1: every word is at most 1
-    words = [(x, z) for x, z in single_words(n)]
-    terms = [(1.0, x, z, k % 5) for k, (x, z) in enumerate(words)]
+    if n <= 5:
+        words = [(x, z) for x, z in single_words(n)]
+    else:
+        # a random word of a random matrix is a sum of 2^n signed elements of size 4^-n: nothing to compare.  Most of
+        # rho is therefore a product of 2 x 2 matrices, one per wire, each with one diagonal and one off-diagonal entry
+        # of size 1/2 and a random phase: |Tr(P m)| = 1/2 for all four P, every word of the product has size 2^-n, and
+        # an observable of 40 words comes to several 1e-3; sum |rho_ij| stays at most 1
+        prod = np.ones((B, 1, 1), dtype=np.complex128)
+        for _ in range(n):
+            m = np.zeros((B, 2, 2), dtype=np.complex128)
+            for b in range(B):
+                d, r, c = rng.integers(0, 2, size=3)
+                m[b, d, d], m[b, r, 1 - r] = 0.5 * np.exp(2j * np.pi * rng.random(2))
+            prod = np.einsum("bij,bkl->bikjl", prod, m).reshape(B, 2 * prod.shape[1], 2 * prod.shape[2])
+        rho = (0.1 * rho + 0.9 * prod).astype(np.complex64)
+        words = [(int(x), int(z)) for x, z in rng.integers(0, 1 << n, size=(200, 2))]
+        words[:3] = [(D - 1, 0), (D - 1, D - 1), (1 << (n - 1), 1)]  # X and Y on every wire; the index's low bit
+    terms = [(1.0, x, z, k % 5) for k, (x, z) in enumerate(words)]   # every column's words straddle the launches
     terms += [(-0.125, x, z, 5) for x, z in words] * 4   # more terms than one launch takes
     want = np.zeros((B, 7))
     wires = list(range(n))
     for coef, x, z, col in terms:
-        P = word_matrix(x, z, wires)
-        want[:, col] += coef * np.real(np.trace(P[None] @ rho.astype(np.complex128), axis1=1, axis2=2))
+        tr = trace_of_word(rho, n, x, z)
+        if n <= 5:  # the gather is the trace with the word's matrix
+            P = word_matrix(x, z, wires)
+            full = np.real(np.trace(P[None] @ rho.astype(np.complex128), axis1=1, axis2=2))
+            assert np.abs(tr - full).max() < 1e-14
+        want[:, col] += coef * tr
     got = N.density_expval_pauli(torch.from_numpy(rho.reshape(B, D * D)).cuda(), n, terms, 7).cpu().numpy()
     err = np.abs(got - want).max()
     print(f"density n={n} max err {err:.3e}")
