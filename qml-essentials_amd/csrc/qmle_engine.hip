@@ -1028,7 +1028,7 @@ int qmle_apply_inplace(qmle_plan *plan, const float *d_angles, int batch, void *
 // `top_k` candidates (x the two paddings of the last stage) ON THE DEVICE with the caller's batch size and
 // measurement, and re-schedules the plan that qmle_run_batch executes to the fastest.  Every candidate is
 // the same tape under another order of commuting gates / another tile geometry: results equal to float32
-// rounding (tests/test_gpu_kernels.py runs all 48).  Choices are remembered per (tape, flags, device).
+// rounding (tests/test_gpu_kernels.py runs every one of them).  Choices are remembered per (tape, flags, device).
 namespace {
 
 struct TunedChoice { int cand, pad; };

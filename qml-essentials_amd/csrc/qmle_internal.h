@@ -305,7 +305,7 @@ struct qmle_plan {
                                           // tape and the flags alone); the unit-form records of ops2 follow
   int fold_groups = 0;                    // most gate groups of any Stage::product_ok stage
   double model_cost = 0.0;                // pass-cost model of the chosen schedule (us per state at n = 24 scale)
-  int chosen_candidate = -1;              // index of the schedule candidate the model picked (compile_plan)
+  int chosen_candidate = -1;              // number of the schedule candidate the model picked (choose_schedule, candidate_of)
   // plan autotuner (qmle_plan_autotune): a forced candidate / last-stage padding for this compile (-1: the
   // cost model resp. the QMLE_FORCE_CAND / QMLE_PAD_HIGH tuning switches), and every allowed candidate with
   // its model cost, cheapest first
@@ -349,7 +349,7 @@ struct qmle_plan {
 #define QMLE_PLAN_INTERNAL_ZERO_RUN (1u << 25)
 
 namespace qmle {
-int compile_plan(qmle_plan *p);  // qmle_plan.cpp
+int compile_plan(qmle_plan *p);  // qmle_plan.cpp: validate_tape, lower_tape, reorder_low_bits_first, choose_schedule, ...
 // Split `ops` into the gates a <Z> measurement needs (`kept`) and the absorbable tail.
 void split_expval_tail(const std::vector<qmle_op> &ops, int n, std::vector<qmle_op> &kept,
                        std::vector<qmle_op> &absorbed);

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cmath>
+#include <functional>
 #include <sstream>
 
 #include "qmle_internal.h"
@@ -75,6 +76,24 @@ uint64_t op_mask(const LoweredOp &o, int n) {
   if (o.c1 >= 0) m |= bit(o.c1);
   return m;
 }
+
+// the positions outside a stage's tile, as a mask
+uint32_t outer_mask(const Stage &st, int n) {
+  uint32_t m = 0;
+  for (int i = 0; i < n - st.T; ++i) m |= 1u << st.outer_bits[i];
+  return m;
+}
+
+// bit j of the result = bit pos[j] of v, for j < count
+uint32_t gather_bits(uint32_t v, const int8_t *pos, int count) {
+  uint32_t out = 0;
+  for (int j = 0; j < count; ++j)
+    if (v & (1u << pos[j])) out |= 1u << j;
+  return out;
+}
+
+// the gate of the tape that lowered operator i stands for, -1 when it is a product of several
+int single_src(const qmle_plan *p, size_t i) { return p->lowered_src[i].size() == 1 ? p->lowered_src[i][0] : -1; }
 
 }  // namespace
 
@@ -224,7 +243,6 @@ static void group_stage_ops(qmle_plan *p, Stage &st) {
 //   * one at the END of a group's op list is peeled off and applied to the layout map after the
 //     group (its scatter stays in place);
 //   * only an X / CX sandwiched between the group's dense gates runs in registers (8 moves).
-// Layout map: logical tile index e lives at physical slot L(e) = XOR_{j in e} Lcol[j] ^ Lconst.
 static inline uint32_t swz(uint32_t e) { return e ^ (((e >> 5) & 15u) << 1); }  // = sw() in qmle_dev.h
 
 static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured);
@@ -234,9 +252,381 @@ static void mark_wave_private_phases(qmle_plan *p, Stage &st, bool measured);
 static bool placed_for_register_measure(const qmle_plan *p, const Stage &st, uint32_t zero_in, bool first, bool last) {
   if (first || !last || st.T >= p->n) return false;
   if (p->flags & QMLE_PLAN_NO_SPARSE) return true;
-  for (int i = 0; i < p->n - st.T; ++i)  // known-zero TILES keep one tile per workgroup and its epilogue
-    if (zero_in & (1u << st.outer_bits[i])) return false;
-  return true;
+  return !(zero_in & outer_mask(st, p->n));  // known-zero TILES keep one tile per workgroup and its epilogue
+}
+
+// The two GF(2)-affine maps of a stage's tile indices that build_fast_groups keeps while it forms the groups:
+//   L, the layout map: logical tile index e lives at physical slot L(e) = XOR_{j in e} Lcol[j] ^ Lconst;
+//   M: logical index in the frame of the last emitted group -> logical index now, and `since`, the X / CX that make
+//   up M, in order: (control or -1, target) pairs (describe_plan).
+struct LayoutMaps {
+  int T;
+  uint32_t Lcol[16], Lconst = 0, Mcol[16], Mconst = 0;
+  std::vector<int8_t> since;
+  explicit LayoutMaps(int T_) : T(T_) {
+    for (int j = 0; j < 16; ++j) Lcol[j] = Mcol[j] = 1u << j;
+  }
+  void reset_M() {
+    for (int j = 0; j < T; ++j) Mcol[j] = 1u << j;
+    Mconst = 0;
+    since.clear();
+  }
+  uint32_t L_of(uint32_t e) const {
+    uint32_t v = Lconst;
+    for (int j = 0; j < T; ++j)
+      if (e & (1u << j)) v ^= Lcol[j];
+    return v;
+  }
+  uint32_t M_lin(uint32_t e) const {  // the linear part of M
+    uint32_t v = 0;
+    for (int j = 0; j < T; ++j)
+      if (e & (1u << j)) v ^= Mcol[j];
+    return v;
+  }
+  bool is_identity() const {  // (the layout map)
+    if (Lconst) return false;
+    for (int j = 0; j < T; ++j)
+      if (Lcol[j] != (1u << j)) return false;
+    return true;
+  }
+  void apply_perm(const LoweredOp &o) {  // an X / CX behind everything applied so far
+    const int t = o.t0;
+    since.push_back(o.nc == 0 ? (int8_t)-1 : o.c0);
+    since.push_back(o.t0);
+    if (o.nc == 0) {
+      Lconst ^= Lcol[t];
+      Mconst ^= 1u << t;
+    } else {
+      const int c = o.c0;
+      Lcol[c] ^= Lcol[t];
+      for (int j = 0; j < T; ++j) Mcol[j] ^= ((Mcol[j] >> c) & 1u) << t;
+      Mconst ^= ((Mconst >> c) & 1u) << t;
+    }
+  }
+};
+
+static void group_positions(uint32_t G, int T, int gb[4]) {  // the four positions of a group, ascending
+  int k = 0;
+  for (int j = 0; j < T && k < 4; ++j)
+    if (G & (1u << j)) gb[k++] = j;
+}
+
+// What build_fast_groups keeps while it forms a stage's groups, and what its epilogues read of it.
+struct FastGroupBuilder {
+  qmle_plan *p;
+  Stage &st;
+  const std::vector<LoweredOp> &src;
+  const bool measured;
+  const int T, nops;
+  const uint32_t nt;
+  LayoutMaps maps;
+  // the maps as they stood when the newest group was emitted: its M is the X / CX between that group and the one in
+  // front of it (Stage::lane_swap_last)
+  LayoutMaps before_last;
+  // known-zero tile-local bits along the stage's execution (runs from |0..0>, Stage::zero_in):
+  // a gate that is not diagonal takes its target out of the set, controls stay.  A work item
+  // whose base index meets the set outside its group's bits holds 16 exact zeros: bit 0 of its
+  // table entry says so (the kernel honours it only in runs that track known zeros).
+  uint32_t Z;
+  int pos_of[16];  // thread index bit k of the newest group's work items -> tile-local position (choose_thread_bits)
+  std::vector<char> done;
+  int n_done = 0;
+  std::vector<int> held;  // X / CX kept back for behind the last group
+  int last_group = -1;
+  uint32_t last_G = 0;
+  const uint32_t slab_bits;
+
+  FastGroupBuilder(qmle_plan *p_, Stage &st_, const std::vector<LoweredOp> &src_, uint32_t zin_local, bool measured_)
+      : p(p_), st(st_), src(src_), measured(measured_), T(st_.T), nops((int)src_.size()), nt(1u << (st_.T - 4)),
+        maps(st_.T), before_last(st_.T), Z(zin_local), done(src_.size(), 0),
+        slab_bits(st_.T > 10 ? ((1u << st_.T) - 1u) & ~1023u : 0u) {}
+
+  static bool is_perm(const LoweredOp &o) { return (o.flags & LF_PERMX) != 0; }
+  static uint32_t mask_of(const LoweredOp &o) {
+    uint32_t m = 1u << o.t0;
+    if (o.c0 >= 0) m |= 1u << o.c0;
+    return m;
+  }
+  void choose_thread_bits(uint32_t G, bool keep_order);
+  uint32_t deposit(uint32_t t) const {  // bits of t into the positions outside the newest group's
+    uint32_t e = 0;
+    for (int k = 0; k < T - 4; ++k) e |= ((t >> k) & 1u) << pos_of[k];
+    return e;
+  }
+  void emit_tables(Group2 &g, uint32_t G);
+  // (Correctness rests on the scan alone: an X / CX that no later op touches commutes with everything behind it.  The
+  // column test only says when waiting pays: X[t] XORs column t into the constant, CX[c -> t] into column c, so a
+  // column t that holds a slab bit is what would move slots between slabs.)
+  bool keeps_back(int i) const {
+    if (!measured || !(maps.Lcol[(int)src[i].t0] & slab_bits)) return false;
+    const uint32_t m = mask_of(src[i]);
+    for (int j = i + 1; j < nops; ++j)
+      if (!done[j] && (mask_of(src[j]) & m)) return false;
+    return true;
+  }
+  void apply_perm(const LoweredOp &o) {
+    Z &= ~(1u << o.t0);
+    maps.apply_perm(o);
+  }
+  void to_layout(int i) {  // X / CX number i leaves the op list for the layout map, now or behind the last group
+    if (keeps_back(i)) held.push_back(i);
+    else apply_perm(src[i]);
+    done[i] = 1;
+    ++n_done;
+  }
+  void emit_group(const std::vector<int> &mem, const std::vector<int> &trailing);
+  void form_groups();
+};
+
+// Thread index bit k of a group's work items -> tile-local position pos_of[k] (outside the group's
+// bits).  Any bijection is correct; WHICH one decides the LDS bank conflicts of the group's 32
+// accesses: slot(thread, c) = P(thread) ^ Q(c) with P linear over GF(2), so a ds_write_b64's 16-lane
+// groups are conflict-free iff thread bits 0..3 land on columns that are independent in slot bits
+// 0..3 (16 slots = 32 banks), and a ds_read_b64's 32-lane groups iff bits 0..4 are independent in
+// slot bits 0..4 (MI355X_MICROARCH.md, LDS table).  Ascending order -- the round-2 choice -- left
+// 33-38 % of the LDS cycles of the whole-state kernels to conflicts (SQ_LDS_BANK_CONFLICT,
+// profiles/r04_ws_sq_*.txt).  Only the lane bits are permuted: the wave index keeps the highest
+// positions, where the known zeros of a run from |0..0> sit (whole waves of idle work items skip).
+void FastGroupBuilder::choose_thread_bits(uint32_t G, bool keep_order) {
+  const uint32_t *Lcol = maps.Lcol;
+  int freep[16], nf = 0;
+  for (int j = 0; j < T; ++j)
+    if (!(G & (1u << j))) freep[nf++] = j;
+  for (int k = 0; k < nf; ++k) pos_of[k] = freep[k];
+  const int lanes = nf < 6 ? nf : 6;
+  if (keep_order || lanes < 2) return;
+  uint32_t basis[8];
+  int nb = 0;
+  auto independent = [&](uint32_t v) {  // reduce v by the basis; keep it when something is left
+    for (int i = 0; i < nb; ++i)
+      if ((v ^ basis[i]) < v) v ^= basis[i];
+    if (!v) return false;
+    basis[nb++] = v;
+    for (int i = nb - 1; i > 0 && basis[i] > basis[i - 1]; --i) std::swap(basis[i], basis[i - 1]);
+    return true;
+  };
+  bool used[16] = {};
+  int order[16], no = 0;
+  for (int k = 0; k < lanes && no < 4; ++k)  // four columns independent in slot bits 0..3
+    if (independent(swz(Lcol[freep[k]]) & 0xFu)) { order[no++] = k; used[k] = true; }
+  nb = 0;
+  for (int i = 0; i < no; ++i) (void)independent(swz(Lcol[freep[order[i]]]) & 0x1Fu);
+  const int first4 = no;
+  for (int k = 0; k < lanes && no < first4 + 1; ++k)  // a fifth, independent in slot bits 0..4
+    if (!used[k] && independent(swz(Lcol[freep[k]]) & 0x1Fu)) { order[no++] = k; used[k] = true; }
+  // fewer than four independent columns exist: the group's own bits own those banks -- fill up
+  // (thread bits 4 / 5 only choose the lane group of a write, bit 5 that of a read)
+  for (int k = 0; k < lanes; ++k)
+    if (!used[k]) order[no++] = k;
+  for (int k = 0; k < lanes; ++k) pos_of[k] = freep[order[k]];
+}
+
+void FastGroupBuilder::emit_tables(Group2 &g, uint32_t G) {
+  int gb[4];
+  group_positions(G, T, gb);
+  // (the idle-work-item flags below are only read by tiled runs that track known zeros)
+  choose_thread_bits(G, (Z & ~G) != 0 && T < p->n && !(p->flags & QMLE_PLAN_NO_SPARSE));
+  g.sync = 1;
+  Stage::FastGroupInfo info{};
+  for (int j = 0; j < 4; ++j) info.bits[j] = (uint8_t)gb[j];
+  for (int t = 0; t < T - 4; ++t) info.thread_bits[t] = (int8_t)pos_of[t];
+  for (int j = 0; j < T; ++j) info.cols[j] = maps.Lcol[j];
+  info.cnst = maps.Lconst;
+  st.fast_info.push_back(info);
+  g.tbl = (uint32_t)p->tbl2.size();
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t e = deposit(t);
+    p->tbl2.push_back((swz(maps.L_of(e)) << 3) | ((e & Z & ~G) ? 1u : 0u));
+  }
+  for (int c = 0; c < 16; ++c) {
+    uint32_t v = 0;
+    for (int j = 0; j < 4; ++j)
+      if (c & (1 << j)) v ^= maps.Lcol[gb[j]];
+    g.off[c] = swz(v) << 3;
+  }
+}
+
+// One group: its tables, its members `mem` with group-local bits and their dispatch codes, then the X / CX `trailing`
+// behind it.
+void FastGroupBuilder::emit_group(const std::vector<int> &mem, const std::vector<int> &trailing) {
+  uint32_t G = 0;
+  for (int i : mem) G |= mask_of(src[i]);
+  for (int b = 5; b < T && __builtin_popcount(G) < 4; ++b) G |= 1u << b;
+  for (int b = 0; b < T && __builtin_popcount(G) < 4; ++b) G |= 1u << b;
+  int8_t local_of[16];
+  for (int b = 0, k = 0; b < T; ++b) local_of[b] = (G & (1u << b)) ? (int8_t)k++ : (int8_t)-1;
+  Group2 g;
+  std::memset(&g, 0, sizeof(g));
+  g.op_begin = (uint32_t)p->ops2.size();
+  g.n_ops = (uint16_t)mem.size();
+  emit_tables(g, G);
+  for (int i : mem)
+    if (!(src[i].flags & LF_DIAG)) Z &= ~(1u << src[i].t0);
+  for (int i : mem) {
+    LoweredOp o = src[i];
+    o.t0 = local_of[(int)o.t0];
+    if (o.c0 >= 0) o.c0 = local_of[(int)o.c0];
+    const int base = is_perm(o) ? (o.nc ? FC_CX : FC_X)
+                     : (o.flags & LF_DIAG) ? (o.nc ? FC_CDIAG : FC_DIAG)
+                                           : (o.nc ? FC_CDENSE : FC_DENSE);
+    o.pad = (uint8_t)(base + (o.nc ? 3 * o.c0 + (o.t0 - (o.t0 > o.c0 ? 1 : 0)) : o.t0));
+    p->ops2.push_back(o);
+    done[i] = 1;
+    ++n_done;
+  }
+  before_last = maps;
+  maps.reset_M();
+  for (int i : trailing) to_layout(i);
+  last_group = (int)p->groups2.size();
+  last_G = G;
+  p->groups2.push_back(g);
+}
+
+void FastGroupBuilder::form_groups() {
+  while (n_done < nops) {
+    uint32_t G = 0, touched = 0, blocked = 0;
+    std::vector<int> mem, after;  // `after`: X / CX applied to the layout behind the group
+    for (int i = 0; i < nops; ++i) {
+      if (done[i]) continue;
+      const uint32_t m = mask_of(src[i]);
+      if (m & blocked) { blocked |= m; continue; }
+      if (is_perm(src[i])) {
+        if (!(m & touched)) {  // independent of the group: layout only, before the group
+          to_layout(i);
+        } else if ((m & ~G) == 0 && mem.size() < 4000) {
+          mem.push_back(i);  // inside the group's bits: stays in registers unless peeled below
+        } else {             // would cost the group a bit position: behind the group instead
+          after.push_back(i);
+          blocked |= m;
+        }
+        continue;
+      }
+      if (__builtin_popcount(G | m) <= 4 && mem.size() < 4000) {
+        G |= m;
+        touched |= m;
+        mem.push_back(i);
+      } else {
+        blocked |= m;
+      }
+    }
+    if (mem.empty()) continue;  // only layout changes were left (`after` needs a member: empty too)
+    // an X / CX that commutes with every later member of the group leaves it for the layout
+    uint32_t later = 0;
+    std::vector<int> keep;
+    for (size_t k = mem.size(); k-- > 0;) {
+      const int i = mem[k];
+      const uint32_t m = mask_of(src[i]);
+      if (is_perm(src[i]) && !(m & later)) {
+        after.push_back(i);
+      } else {
+        later |= m;
+        keep.insert(keep.begin(), i);
+      }
+    }
+    std::sort(after.begin(), after.end());
+    emit_group(keep, after);
+  }
+  if (last_group < 0) {  // nothing but layout changes (or no gate at all): an empty group moves the data
+    Group2 g;
+    std::memset(&g, 0, sizeof(g));
+    g.op_begin = (uint32_t)p->ops2.size();
+    last_G = 0xFu << (T >= 9 ? 5 : 0);
+    emit_tables(g, last_G);
+    maps.reset_M();
+    last_group = (int)p->groups2.size();
+    p->groups2.push_back(g);
+  }
+  for (int i : held) apply_perm(src[i]);  // (they commute with every op behind them: tape order among themselves)
+}
+
+// The epilogue (store / measure) reads the tile in the identity layout: the last group scatters through a table of its
+// own.  A thread holds logical index e of the group's frame; its final logical index is M(e).
+static void emit_relayout(const FastGroupBuilder &b) {
+  if (b.maps.is_identity()) return;
+  qmle_plan *p = b.p;
+  Group2 &g = p->groups2[b.last_group];
+  int gb[4];
+  group_positions(b.last_G, b.T, gb);
+  g.relayout = 1;
+  g.tbl_out = (uint32_t)p->tbl2.size();
+  for (uint32_t t = 0; t < b.nt; ++t) p->tbl2.push_back(swz(b.maps.M_lin(b.deposit(t)) ^ b.maps.Mconst) << 3);
+  for (int c = 0; c < 16; ++c) {
+    uint32_t e = 0;
+    for (int j = 0; j < 4; ++j)
+      if (c & (1 << j)) e |= 1u << gb[j];
+    g.off_out[c] = swz(b.maps.M_lin(e)) << 3;
+  }
+}
+
+// <Z> from the last group's registers (Stage::zreg): amplitude c of work item t holds index e(t, c) of the group's
+// frame (thread bit k at position pos_of[k], in-thread bit i at the group's i-th position) and ends at logical
+// index M e ^ Mconst; bit j of that is the parity of e under row j of M, plus bit j of Mconst
+static void emit_zreg_records(const FastGroupBuilder &b, Stage &st) {
+  const int T = b.T;
+  const LayoutMaps &m = b.maps;
+  st.zreg_ok = false;
+  std::memset(st.zreg, 0, sizeof(st.zreg));
+  if (T >= b.p->n) return;  // (last_group: a gate group, or the empty one that only moves the data)
+  int gb[4];
+  group_positions(b.last_G, T, gb);
+  for (int j = 0; j < T; ++j) {
+    uint32_t rec = ((m.Mconst >> j) & 1u) << 15;
+    for (int i = 0; i < 4; ++i) rec |= ((m.Mcol[gb[i]] >> j) & 1u) << i;
+    for (int t = 0; t < T - 4; ++t) rec |= ((m.Mcol[b.pos_of[t]] >> j) & 1u) << (4 + t);
+    st.zreg[j] = (uint16_t)rec;
+  }
+  for (int i = 0; i < 4; ++i) st.zreg_bits[i] = (int8_t)gb[i];
+  for (int t = 0; t < T - 4; ++t) st.zreg_thread_bits[t] = (int8_t)b.pos_of[t];
+  st.zreg_ok = true;
+}
+
+// The last group through lane swaps (Stage::lane_swap_last).  Behind the ops of the group in front of it, work item t
+// holds amplitude c at index e(t, c) of THAT group's frame.  The X / CX between the two groups (N) touch none of
+// the last group's positions, so its ops commute to the front of them: they run in that frame, on the positions
+// the two swaps brought in-thread, and a record is a row of M N -- N first, then everything behind the last group.
+static void qualify_lane_swap(const FastGroupBuilder &b, Stage &st) {
+  const qmle_plan *p = b.p;
+  const int T = b.T;
+  st.lane_swap_last = st.lane_swap_cross = false;
+  st.zreg_between.clear();
+  std::memset(st.zreg_swap, 0, sizeof(st.zreg_swap));
+  const int ng = st.fast_end - st.fast_begin;
+  if (!(b.measured && st.zreg_ok && st.wave_private && st.dma_tables && ng >= 2)) return;
+  const Group2 &gl = p->groups2[st.fast_end - 1];
+  const Stage::FastGroupInfo &pi = st.fast_info[ng - 2], &li = st.fast_info[ng - 1];
+  bool ok = gl.n_ops >= 1, straight = true, cross = true;  // which lane bit in-thread index 2 / 3 trades with
+  uint32_t members = 0;
+  for (int k = 0; k < (int)gl.n_ops && ok; ++k) {
+    const LoweredOp &o = p->ops2[gl.op_begin + k];  // (t0: the in-thread index, which the dispatch code carries)
+    ok = o.kind == LK_1Q && o.nc == 0 && !(o.flags & LF_PERMX) && (o.t0 == 2 || o.t0 == 3);
+    if (!ok) break;
+    const int pos = (int)li.bits[(int)o.t0];
+    straight = straight && pos == (int)pi.thread_bits[o.t0 + 2];
+    cross = cross && pos == (int)pi.thread_bits[7 - o.t0];
+    members |= 1u << pos;
+  }
+  ok = ok && (straight || cross);
+  cross = !straight;
+  const std::vector<int8_t> &between = b.before_last.since;
+  for (size_t i = 0; i + 1 < between.size() && ok; i += 2)
+    if (members & ((1u << between[i + 1]) | (between[i] >= 0 ? 1u << between[i] : 0u))) ok = false;
+  if (!ok) return;
+  const LayoutMaps &m = b.maps, &nm = b.before_last;
+  // in-thread index i = 2, 3 trades with lane bit lane_of(i)
+  auto lane_of = [&](int i) { return cross ? 7 - i : i + 2; };
+  for (int i = 0; i < 4; ++i) st.zreg_swap_bits[i] = (int8_t)(i < 2 ? (int)pi.bits[i] : (int)pi.thread_bits[lane_of(i)]);
+  for (int t = 0; t < T - 4; ++t) st.zreg_swap_thread_bits[t] = pi.thread_bits[t];
+  for (int i = 2; i < 4; ++i) st.zreg_swap_thread_bits[lane_of(i)] = (int8_t)pi.bits[i];
+  const uint32_t cnst = m.M_lin(nm.Mconst) ^ m.Mconst;
+  for (int j = 0; j < T; ++j) {
+    uint32_t rec = ((cnst >> j) & 1u) << 15;
+    for (int i = 0; i < 4; ++i) rec |= ((m.M_lin(nm.Mcol[(int)st.zreg_swap_bits[i]]) >> j) & 1u) << i;
+    for (int t = 0; t < T - 4; ++t) rec |= ((m.M_lin(nm.Mcol[(int)st.zreg_swap_thread_bits[t]]) >> j) & 1u) << (4 + t);
+    st.zreg_swap[j] = (uint16_t)rec;
+  }
+  st.zreg_between = between;
+  st.lane_swap_last = true;
+  st.lane_swap_cross = cross;
 }
 
 // measured: the stage qualifies for <Z> from the last group's registers (qualifies_for_register_measure).  Its X / CX
@@ -255,297 +645,15 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   if (T < kFastMinT || T > kFastMaxT || (p->flags & QMLE_PLAN_NO_REGTILE)) return;
   for (const LoweredOp &o : src)
     if (o.kind != LK_1Q || o.nc > 1) return;
-  const int nops = (int)src.size();
-  const uint32_t nt = 1u << (T - 4);
-  const size_t ops2_mark = p->ops2.size(), tbl_mark = p->tbl2.size();
-  uint32_t Lcol[16], Lconst = 0;
-  for (int j = 0; j < T; ++j) Lcol[j] = 1u << j;
-  auto L_of = [&](uint32_t e) {
-    uint32_t v = Lconst;
-    for (int j = 0; j < T; ++j)
-      if (e & (1u << j)) v ^= Lcol[j];
-    return v;
-  };
-  auto L_is_identity = [&]() {
-    if (Lconst) return false;
-    for (int j = 0; j < T; ++j)
-      if (Lcol[j] != (1u << j)) return false;
-    return true;
-  };
-  // M: logical index in the frame of the last emitted group -> logical index now
-  uint32_t Mcol[16], Mconst = 0;
-  st.zreg_after.clear();  // the X / CX that make up M, in order: (control or -1, target) pairs (describe_plan)
-  auto M_reset = [&]() { for (int j = 0; j < T; ++j) Mcol[j] = 1u << j; Mconst = 0; st.zreg_after.clear(); };
-  M_reset();
-  auto is_perm = [](const LoweredOp &o) { return (o.flags & LF_PERMX) != 0; };
-  // known-zero tile-local bits along the stage's execution (runs from |0..0>, Stage::zero_in):
-  // a gate that is not diagonal takes its target out of the set, controls stay.  A work item
-  // whose base index meets the set outside its group's bits holds 16 exact zeros: bit 0 of its
-  // table entry says so (the kernel honours it only in runs that track known zeros).
-  uint32_t Z = zin_local;
-  auto apply_perm = [&](const LoweredOp &o) {
-    Z &= ~(1u << o.t0);
-    const int t = o.t0;
-    st.zreg_after.push_back(o.nc == 0 ? (int8_t)-1 : o.c0);
-    st.zreg_after.push_back(o.t0);
-    if (o.nc == 0) {
-      Lconst ^= Lcol[t];
-      Mconst ^= 1u << t;
-    } else {
-      const int c = o.c0;
-      Lcol[c] ^= Lcol[t];
-      for (int j = 0; j < T; ++j) Mcol[j] ^= ((Mcol[j] >> c) & 1u) << t;
-      Mconst ^= ((Mconst >> c) & 1u) << t;
-    }
-  };
-  auto mask_of = [](const LoweredOp &o) {
-    uint32_t m = 1u << o.t0;
-    if (o.c0 >= 0) m |= 1u << o.c0;
-    return m;
-  };
-  // Thread index bit k of a group's work items -> tile-local position pos_of[k] (outside the group's
-  // bits).  Any bijection is correct; WHICH one decides the LDS bank conflicts of the group's 32
-  // accesses: slot(thread, c) = P(thread) ^ Q(c) with P linear over GF(2), so a ds_write_b64's 16-lane
-  // groups are conflict-free iff thread bits 0..3 land on columns that are independent in slot bits
-  // 0..3 (16 slots = 32 banks), and a ds_read_b64's 32-lane groups iff bits 0..4 are independent in
-  // slot bits 0..4 (MI355X_MICROARCH.md, LDS table).  Ascending order -- the round-2 choice -- left
-  // 33-38 % of the LDS cycles of the whole-state kernels to conflicts (SQ_LDS_BANK_CONFLICT,
-  // profiles/r04_ws_sq_*.txt).  Only the lane bits are permuted: the wave index keeps the highest
-  // positions, where the known zeros of a run from |0..0> sit (whole waves of idle work items skip).
-  int pos_of[16];
-  auto choose_thread_bits = [&](uint32_t G, bool keep_order) {
-    int freep[16], nf = 0;
-    for (int j = 0; j < T; ++j)
-      if (!(G & (1u << j))) freep[nf++] = j;
-    for (int k = 0; k < nf; ++k) pos_of[k] = freep[k];
-    const int lanes = nf < 6 ? nf : 6;
-    if (keep_order || lanes < 2) return;
-    uint32_t basis[8];
-    int nb = 0;
-    auto independent = [&](uint32_t v) {  // reduce v by the basis; keep it when something is left
-      for (int i = 0; i < nb; ++i)
-        if ((v ^ basis[i]) < v) v ^= basis[i];
-      if (!v) return false;
-      basis[nb++] = v;
-      for (int i = nb - 1; i > 0 && basis[i] > basis[i - 1]; --i) std::swap(basis[i], basis[i - 1]);
-      return true;
-    };
-    bool used[16] = {};
-    int order[16], no = 0;
-    for (int k = 0; k < lanes && no < 4; ++k)  // four columns independent in slot bits 0..3
-      if (independent(swz(Lcol[freep[k]]) & 0xFu)) { order[no++] = k; used[k] = true; }
-    nb = 0;
-    for (int i = 0; i < no; ++i) (void)independent(swz(Lcol[freep[order[i]]]) & 0x1Fu);
-    const int first4 = no;
-    for (int k = 0; k < lanes && no < first4 + 1; ++k)  // a fifth, independent in slot bits 0..4
-      if (!used[k] && independent(swz(Lcol[freep[k]]) & 0x1Fu)) { order[no++] = k; used[k] = true; }
-    // fewer than four independent columns exist: the group's own bits own those banks -- fill up
-    // (thread bits 4 / 5 only choose the lane group of a write, bit 5 that of a read)
-    for (int k = 0; k < lanes; ++k)
-      if (!used[k]) order[no++] = k;
-    for (int k = 0; k < lanes; ++k) pos_of[k] = freep[order[k]];
-  };
-  auto deposit = [&](uint32_t t, uint32_t G) {  // bits of t into the positions outside G
-    (void)G;
-    uint32_t e = 0;
-    for (int k = 0; k < T - 4; ++k) e |= ((t >> k) & 1u) << pos_of[k];
-    return e;
-  };
-  auto emit_tables = [&](Group2 &g, uint32_t G) {
-    int gb[4], k = 0;
-    for (int j = 0; j < T; ++j)
-      if (G & (1u << j)) gb[k++] = j;
-    // (the idle-work-item flags below are only read by tiled runs that track known zeros)
-    choose_thread_bits(G, (Z & ~G) != 0 && T < p->n && !(p->flags & QMLE_PLAN_NO_SPARSE));
-    g.sync = 1;
-    Stage::FastGroupInfo info{};
-    for (int j = 0; j < 4; ++j) info.bits[j] = (uint8_t)gb[j];
-    for (int t = 0; t < T - 4; ++t) info.thread_bits[t] = (int8_t)pos_of[t];
-    for (int j = 0; j < T; ++j) info.cols[j] = Lcol[j];
-    info.cnst = Lconst;
-    st.fast_info.push_back(info);
-    g.tbl = (uint32_t)p->tbl2.size();
-    for (uint32_t t = 0; t < nt; ++t) {
-      const uint32_t e = deposit(t, G);
-      p->tbl2.push_back((swz(L_of(e)) << 3) | ((e & Z & ~G) ? 1u : 0u));
-    }
-    for (int c = 0; c < 16; ++c) {
-      uint32_t v = 0;
-      for (int j = 0; j < 4; ++j)
-        if (c & (1 << j)) v ^= Lcol[gb[j]];
-      g.off[c] = swz(v) << 3;
-    }
-  };
-  std::vector<char> done(nops, 0);
-  int n_done = 0;
-  int last_group = -1;
-  uint32_t last_G = 0;
-  std::vector<int> held;  // X / CX kept back for behind the last group
-  // M as it stood when the newest group was emitted -- the X / CX between that group and the one in front of it --
-  // and their (control or -1, target) pairs (Stage::lane_swap_last)
-  uint32_t Ncol[16], Nconst = 0;
-  std::vector<int8_t> between;
-  const uint32_t slab_bits = T > 10 ? ((1u << T) - 1u) & ~1023u : 0u;
-  // (Correctness rests on the scan alone: an X / CX that no later op touches commutes with everything behind it.  The
-  // column test only says when waiting pays: X[t] XORs column t into the constant, CX[c -> t] into column c, so a
-  // column t that holds a slab bit is what would move slots between slabs.)
-  auto keeps_back = [&](int i) {
-    if (!measured || !(Lcol[(int)src[i].t0] & slab_bits)) return false;
-    const uint32_t m = mask_of(src[i]);
-    for (int j = i + 1; j < nops; ++j)
-      if (!done[j] && (mask_of(src[j]) & m)) return false;
-    return true;
-  };
-  while (n_done < nops) {
-    uint32_t G = 0, touched = 0, blocked = 0;
-    std::vector<int> mem, after;  // `after`: X / CX applied to the layout behind the group
-    for (int i = 0; i < nops; ++i) {
-      if (done[i]) continue;
-      const uint32_t m = mask_of(src[i]);
-      if (m & blocked) { blocked |= m; continue; }
-      if (is_perm(src[i])) {
-        if (!(m & touched)) {  // independent of the group: layout only, before the group
-          if (keeps_back(i)) held.push_back(i);
-          else apply_perm(src[i]);
-          done[i] = 1;
-          ++n_done;
-        } else if ((m & ~G) == 0 && mem.size() < 4000) {
-          mem.push_back(i);  // inside the group's bits: stays in registers unless peeled below
-        } else {             // would cost the group a bit position: behind the group instead
-          after.push_back(i);
-          blocked |= m;
-        }
-        continue;
-      }
-      if (__builtin_popcount(G | m) <= 4 && mem.size() < 4000) {
-        G |= m;
-        touched |= m;
-        mem.push_back(i);
-      } else {
-        blocked |= m;
-      }
-    }
-    if (mem.empty()) continue;  // only layout changes were left (`after` needs a member: empty too)
-    {  // an X / CX that commutes with every later member of the group leaves it for the layout
-      uint32_t later = 0;
-      std::vector<int> keep;
-      for (size_t k = mem.size(); k-- > 0;) {
-        const int i = mem[k];
-        const uint32_t m = mask_of(src[i]);
-        if (is_perm(src[i]) && !(m & later)) {
-          after.push_back(i);
-        } else {
-          later |= m;
-          keep.insert(keep.begin(), i);
-        }
-      }
-      mem.swap(keep);
-      std::sort(after.begin(), after.end());
-    }
-    const std::vector<int> &trailing = after;
-    G = 0;
-    for (int i : mem) G |= mask_of(src[i]);
-    for (int b = 5; b < T && __builtin_popcount(G) < 4; ++b) G |= 1u << b;
-    for (int b = 0; b < T && __builtin_popcount(G) < 4; ++b) G |= 1u << b;
-    int8_t local_of[16];
-    {
-      int k = 0;
-      for (int b = 0; b < T; ++b) local_of[b] = (G & (1u << b)) ? (int8_t)k++ : (int8_t)-1;
-    }
-    Group2 g;
-    std::memset(&g, 0, sizeof(g));
-    g.op_begin = (uint32_t)p->ops2.size();
-    g.n_ops = (uint16_t)mem.size();
-    emit_tables(g, G);
-    for (int i : mem)
-      if (!(src[i].flags & LF_DIAG)) Z &= ~(1u << src[i].t0);
-    for (int i : mem) {
-      LoweredOp o = src[i];
-      o.t0 = local_of[(int)o.t0];
-      if (o.c0 >= 0) o.c0 = local_of[(int)o.c0];
-      const int base = is_perm(o) ? (o.nc ? FC_CX : FC_X)
-                       : (o.flags & LF_DIAG) ? (o.nc ? FC_CDIAG : FC_DIAG)
-                                             : (o.nc ? FC_CDENSE : FC_DENSE);
-      o.pad = (uint8_t)(base + (o.nc ? 3 * o.c0 + (o.t0 - (o.t0 > o.c0 ? 1 : 0)) : o.t0));
-      p->ops2.push_back(o);
-      done[i] = 1;
-      ++n_done;
-    }
-    std::memcpy(Ncol, Mcol, sizeof(Ncol));
-    Nconst = Mconst;
-    between = st.zreg_after;
-    M_reset();
-    for (int i : trailing) {
-      if (keeps_back(i)) held.push_back(i);
-      else apply_perm(src[i]);
-      done[i] = 1;
-      ++n_done;
-    }
-    last_group = (int)p->groups2.size();
-    last_G = G;
-    p->groups2.push_back(g);
-  }
-  if (last_group < 0) {  // nothing but layout changes (or no gate at all): an empty group moves the data
-    Group2 g;
-    std::memset(&g, 0, sizeof(g));
-    g.op_begin = (uint32_t)p->ops2.size();
-    last_G = 0xFu << (T >= 9 ? 5 : 0);
-    emit_tables(g, last_G);
-    M_reset();
-    last_group = (int)p->groups2.size();
-    p->groups2.push_back(g);
-  }
-  for (int i : held) apply_perm(src[i]);  // (they commute with every op behind them: tape order among themselves)
-  // the epilogue (store / measure) reads the tile in the identity layout
-  {
-    const uint32_t G = last_G;
-    Group2 &g = p->groups2[last_group];
-    if (!L_is_identity()) {
-      // a thread holds logical index e of the group's frame; its final logical index is M(e)
-      int gb[4], k = 0;
-      for (int j = 0; j < T; ++j)
-        if (G & (1u << j)) gb[k++] = j;
-      auto M_lin = [&](uint32_t e) {
-        uint32_t v = 0;
-        for (int j = 0; j < T; ++j)
-          if (e & (1u << j)) v ^= Mcol[j];
-        return v;
-      };
-      g.relayout = 1;
-      g.tbl_out = (uint32_t)p->tbl2.size();
-      for (uint32_t t = 0; t < nt; ++t) p->tbl2.push_back(swz(M_lin(deposit(t, G)) ^ Mconst) << 3);
-      for (int c = 0; c < 16; ++c) {
-        uint32_t e = 0;
-        for (int j = 0; j < 4; ++j)
-          if (c & (1 << j)) e |= 1u << gb[j];
-        g.off_out[c] = swz(M_lin(e)) << 3;
-      }
-    }
-  }
-  // <Z> from the last group's registers (Stage::zreg): amplitude c of work item t holds index e(t, c) of the group's
-  // frame (thread bit k at position pos_of[k], in-thread bit i at the group's i-th position) and ends at logical
-  // index M e ^ Mconst; bit j of that is the parity of e under row j of M, plus bit j of Mconst
-  st.zreg_ok = false;
-  std::memset(st.zreg, 0, sizeof(st.zreg));
-  if (T < p->n) {  // (last_group: a gate group, or the empty one that only moves the data)
-    int gb[4], k = 0;
-    for (int j = 0; j < T; ++j)
-      if (last_G & (1u << j)) gb[k++] = j;
-    for (int j = 0; j < T; ++j) {
-      uint32_t rec = ((Mconst >> j) & 1u) << 15;
-      for (int i = 0; i < 4; ++i) rec |= ((Mcol[gb[i]] >> j) & 1u) << i;
-      for (int t = 0; t < T - 4; ++t) rec |= ((Mcol[pos_of[t]] >> j) & 1u) << (4 + t);
-      st.zreg[j] = (uint16_t)rec;
-    }
-    for (int i = 0; i < 4; ++i) st.zreg_bits[i] = (int8_t)gb[i];
-    for (int t = 0; t < T - 4; ++t) st.zreg_thread_bits[t] = (int8_t)pos_of[t];
-    st.zreg_ok = true;
-  }
-  (void)ops2_mark; (void)tbl_mark;
+  FastGroupBuilder b(p, st, src, zin_local, measured);
+  b.form_groups();
+  st.zreg_after = b.maps.since;
+  emit_relayout(b);
+  emit_zreg_records(b, st);
   // global byte offset of every lane's first float4 inside the tile: local index 2 t with its
   // bits deposited at the tile's global positions (bits below L are contiguous)
   st.fast_gtab = (uint32_t)p->tbl2.size();
-  for (uint32_t t = 0; t < nt; ++t) {
+  for (uint32_t t = 0; t < b.nt; ++t) {
     const uint32_t jl = 2u * t;
     uint32_t g = 0;
     for (int j = 0; j <= T - 4; ++j)
@@ -555,56 +663,7 @@ static void build_fast_groups(qmle_plan *p, Stage &st, const std::vector<Lowered
   st.fast_end = (int)p->groups2.size();
   st.fast_ok = true;
   mark_wave_private_phases(p, st, measured);
-  // The last group through lane swaps (Stage::lane_swap_last).  Behind the ops of the group in front of it, work item t
-  // holds amplitude c at index e(t, c) of THAT group's frame.  The X / CX between the two groups (N) touch none of
-  // the last group's positions, so its ops commute to the front of them: they run in that frame, on the positions
-  // the two swaps brought in-thread, and a record is a row of M N -- N first, then everything behind the last group.
-  st.lane_swap_last = st.lane_swap_cross = false;
-  st.zreg_between.clear();
-  std::memset(st.zreg_swap, 0, sizeof(st.zreg_swap));
-  const int ng = st.fast_end - st.fast_begin;
-  if (measured && st.zreg_ok && st.wave_private && st.dma_tables && ng >= 2) {
-    const Group2 &gl = p->groups2[st.fast_end - 1];
-    const Stage::FastGroupInfo &pi = st.fast_info[ng - 2], &li = st.fast_info[ng - 1];
-    bool ok = gl.n_ops >= 1, straight = true, cross = true;  // which lane bit in-thread index 2 / 3 trades with
-    uint32_t members = 0;
-    for (int k = 0; k < (int)gl.n_ops && ok; ++k) {
-      const LoweredOp &o = p->ops2[gl.op_begin + k];  // (t0: the in-thread index, which the dispatch code carries)
-      ok = o.kind == LK_1Q && o.nc == 0 && !(o.flags & LF_PERMX) && (o.t0 == 2 || o.t0 == 3);
-      if (!ok) break;
-      const int pos = (int)li.bits[(int)o.t0];
-      straight = straight && pos == (int)pi.thread_bits[o.t0 + 2];
-      cross = cross && pos == (int)pi.thread_bits[7 - o.t0];
-      members |= 1u << pos;
-    }
-    ok = ok && (straight || cross);
-    cross = !straight;
-    for (size_t i = 0; i + 1 < between.size() && ok; i += 2)
-      if (members & ((1u << between[i + 1]) | (between[i] >= 0 ? 1u << between[i] : 0u))) ok = false;
-    if (ok) {
-      auto M_lin = [&](uint32_t e) {
-        uint32_t v = 0;
-        for (int j = 0; j < T; ++j)
-          if (e & (1u << j)) v ^= Mcol[j];
-        return v;
-      };
-      // in-thread index i = 2, 3 trades with lane bit lane_of(i)
-      auto lane_of = [&](int i) { return cross ? 7 - i : i + 2; };
-      for (int i = 0; i < 4; ++i) st.zreg_swap_bits[i] = (int8_t)(i < 2 ? (int)pi.bits[i] : (int)pi.thread_bits[lane_of(i)]);
-      for (int t = 0; t < T - 4; ++t) st.zreg_swap_thread_bits[t] = pi.thread_bits[t];
-      for (int i = 2; i < 4; ++i) st.zreg_swap_thread_bits[lane_of(i)] = (int8_t)pi.bits[i];
-      const uint32_t cnst = M_lin(Nconst) ^ Mconst;
-      for (int j = 0; j < T; ++j) {
-        uint32_t rec = ((cnst >> j) & 1u) << 15;
-        for (int i = 0; i < 4; ++i) rec |= ((M_lin(Ncol[(int)st.zreg_swap_bits[i]]) >> j) & 1u) << i;
-        for (int t = 0; t < T - 4; ++t) rec |= ((M_lin(Ncol[(int)st.zreg_swap_thread_bits[t]]) >> j) & 1u) << (4 + t);
-        st.zreg_swap[j] = (uint16_t)rec;
-      }
-      st.zreg_between = between;
-      st.lane_swap_last = true;
-      st.lane_swap_cross = cross;
-    }
-  }
+  qualify_lane_swap(b, st);
 }
 
 // Which wave touches which slot in every phase of the measuring walk, read off the tables as emitted; sets
@@ -894,26 +953,11 @@ uint32_t pull_back_z(const std::vector<qmle_op> &absorbed, int wire) {
   return m;
 }
 
-constexpr uint8_t kLoweredDead = 255;  // LoweredOp::kind of an operator merged away during lowering
-
-int compile_plan(qmle_plan *p) {
+// ---- 1. validate + lower ---------------------------------------------------------------------------
+// The per-op checks, in tape order: the first failing op decides the error code.
+static int validate_tape(const qmle_plan *p) {
   const int n = p->n;
-  if (n < 1 || n > QMLE_MAX_QUBITS) return QMLE_ERR_INVALID_ARG;
-
-  // ---- 1. validate + lower -------------------------------------------------
-  std::vector<int> last_touch(n, -1);  // lowered index that last touched bit p
-  p->lowered.clear(); p->lowered_src.clear(); p->build_ops.clear(); p->groups.clear();
-  p->algo_bytes_per_state = 0;
-  p->mat_floats = 0;
-  const bool fuse = !(p->flags & QMLE_PLAN_NO_FUSION);
-  const bool no_fusion_flag = !fuse;
-  const size_t n_user_consts = p->consts.size();
-  std::vector<std::vector<BuildOp>> group_ops;            // source gates per matrix
-  std::vector<std::pair<uint32_t, uint32_t>> group_meta;  // (mat_off, dim)
-  std::vector<int> group_of;                              // lowered index -> group
-
-  for (size_t i = 0; i < p->ops.size(); ++i) {
-    const qmle_op &op = p->ops[i];
+  for (const qmle_op &op : p->ops) {
     OpInfo info;
     if (!op_info(op.opcode, &info)) return QMLE_ERR_UNKNOWN_OP;
     int nw = 0;
@@ -937,654 +981,772 @@ int compile_plan(qmle_plan *p) {
     }
     for (int a = 0; a < info.n_params; ++a)
       if (op.slot[a] < 0 || op.slot[a] >= p->n_slots) return QMLE_ERR_SLOT_RANGE;
+  }
+  return QMLE_OK;
+}
 
-    p->algo_bytes_per_state += algo_bytes(op, n);
-    if (op.opcode == QMLE_OP_ID) continue;  // identity: nothing to do
+constexpr uint8_t kLoweredDead = 255;  // LoweredOp::kind of an operator merged away during lowering
 
-    auto pos = [n](int w) { return (int8_t)(n - 1 - w); };
-    LoweredOp lo{};
-    lo.t1 = lo.c0 = lo.c1 = -1;
-    lo.slot = -1;
-    lo.flags = is_diag_opcode(op.opcode) ? LF_DIAG : 0;
-    if (op.opcode == QMLE_OP_X || op.opcode == QMLE_OP_CX || op.opcode == QMLE_OP_CCX)
-      lo.flags |= LF_PERMX;
-    if (op.opcode == QMLE_OP_CZ || op.opcode == QMLE_OP_CPHASE) lo.flags |= LF_PHASE;  // (operations.py:1100, 1171-1201)
-    BuildOp bo{};
-    bo.opcode = op.opcode;
-    for (int a = 0; a < 3; ++a) bo.slot[a] = op.slot[a];
-    bo.const_off = op.mat_off;
-
-    if (op.opcode == QMLE_OP_DIAG_ALL) {
+// One gate of a validated tape as a lowered operator on bit positions (wire w = position n - 1 - w); a dense
+// operator's matrix offset is assigned when it is pushed.
+static LoweredOp lowered_form(const qmle_op &op, int n) {
+  auto pos = [n](int w) { return (int8_t)(n - 1 - w); };
+  LoweredOp lo{};
+  lo.t1 = lo.c0 = lo.c1 = -1;
+  lo.slot = -1;
+  lo.flags = is_diag_opcode(op.opcode) ? LF_DIAG : 0;
+  if (op.opcode == QMLE_OP_X || op.opcode == QMLE_OP_CX || op.opcode == QMLE_OP_CCX)
+    lo.flags |= LF_PERMX;
+  if (op.opcode == QMLE_OP_CZ || op.opcode == QMLE_OP_CPHASE) lo.flags |= LF_PHASE;  // (operations.py:1100, 1171-1201)
+  switch (op.opcode) {
+    case QMLE_OP_DIAG_ALL:
       lo.kind = LK_DIAG_ALL;
       lo.t0 = 0;
       lo.mat_off = (uint32_t)op.mat_off;
       lo.slot = op.slot[0];
-      for (int b = 0; b < n; ++b) last_touch[b] = (int)p->lowered.size();
-      group_of.resize(p->lowered.size() + 1, -1);
-      p->lowered.push_back(lo);
-      p->lowered_src.push_back({(int)i});
-      continue;
-    }
-
-    if (op.opcode == QMLE_OP_MAT4) {
+      break;
+    case QMLE_OP_MAT4:
       lo.kind = LK_4Q;
       lo.t0 = pos(op.wire[0]); lo.t1 = pos(op.wire[1]);
       lo.c0 = pos(op.wire[2]); lo.c1 = pos(op.wire[3]);
       lo.nc = 0;
       lo.mat_off = (uint32_t)op.mat_off;  // const blob; permuted copy is made per stage
-      const int idx4 = (int)p->lowered.size();
-      const uint64_t m4 = op_mask(lo, n);
-      for (int b = 0; b < n; ++b)
-        if (m4 & bit(b)) last_touch[b] = idx4;
-      group_of.resize(idx4 + 1, -1);
-      p->lowered.push_back(lo);
-      p->lowered_src.push_back({(int)i});
+      break;
+    case QMLE_OP_CX: case QMLE_OP_CY: case QMLE_OP_CZ: case QMLE_OP_CRX:
+    case QMLE_OP_CRY: case QMLE_OP_CRZ: case QMLE_OP_CPHASE:
+      lo.kind = LK_1Q; lo.nc = 1; lo.c0 = pos(op.wire[0]); lo.t0 = pos(op.wire[1]);
+      break;
+    case QMLE_OP_CCX:
+      lo.kind = LK_1Q; lo.nc = 2; lo.c0 = pos(op.wire[0]); lo.c1 = pos(op.wire[1]);
+      lo.t0 = pos(op.wire[2]);
+      break;
+    case QMLE_OP_CSWAP:
+      lo.kind = LK_2Q; lo.nc = 1; lo.c0 = pos(op.wire[0]); lo.t0 = pos(op.wire[1]);
+      lo.t1 = pos(op.wire[2]);
+      break;
+    case QMLE_OP_SWAP: case QMLE_OP_RXX: case QMLE_OP_RYY: case QMLE_OP_RZZ:
+    case QMLE_OP_RZX: case QMLE_OP_MAT2:
+      lo.kind = LK_2Q; lo.nc = 0; lo.t0 = pos(op.wire[0]); lo.t1 = pos(op.wire[1]);
+      break;
+    default:  // uncontrolled 1-qubit
+      lo.kind = LK_1Q; lo.nc = 0; lo.t0 = pos(op.wire[0]);
+      break;
+  }
+  return lo;
+}
+
+// What lower_tape keeps while it walks the tape.
+struct Lowering {
+  qmle_plan *p;
+  std::vector<int> last_touch;                            // lowered index that last touched bit position b
+  std::vector<std::vector<BuildOp>> group_ops;            // source gates per matrix
+  std::vector<std::pair<uint32_t, uint32_t>> group_meta;  // (mat_off, dim)
+  std::vector<int> group_of;                              // lowered index -> group
+
+  explicit Lowering(qmle_plan *p_) : p(p_), last_touch(p_->n, -1) {}
+
+  // a new operator behind everything lowered so far, made of the tape's gates `src`; -> its index
+  int push(const LoweredOp &lo, std::vector<int> src) {
+    const int idx = (int)p->lowered.size();
+    const uint64_t m = op_mask(lo, p->n);
+    for (int b = 0; b < p->n; ++b)
+      if (m & bit(b)) last_touch[b] = idx;
+    group_of.resize(idx + 1, -1);
+    p->lowered.push_back(lo);
+    p->lowered_src.push_back(std::move(src));
+    return idx;
+  }
+  // gate `i` of the tape (`lo`, built by `bo`) multiplies onto operator `prev`: as U (x) I / I (x) U onto a 4x4
+  // (BuildOp::pad = 1 / 2), else as a plain product (pad 0); `clear`: the flags a product cannot keep
+  void multiply_onto(int prev, const LoweredOp &lo, BuildOp bo, int i, int pad, uint8_t clear) {
+    LoweredOp &pl = p->lowered[prev];
+    bo.pad = (uint16_t)pad;
+    group_ops[group_of[prev]].push_back(bo);
+    if (!(lo.flags & LF_DIAG)) pl.flags &= ~LF_DIAG;
+    pl.flags &= ~clear;
+    p->lowered_src[prev].push_back(i);
+  }
+  bool merge(const LoweredOp &lo, const BuildOp &bo, int i);
+  void take_pending(LoweredOp &lo, std::vector<BuildOp> &taken, std::vector<int> &taken_src);
+};
+
+// Commutation-aware merge: an uncontrolled 1-q gate multiplies onto the previous uncontrolled 1-q matrix on the same
+// wire if nothing touched that wire in between (gates on disjoint wires commute).
+// Round 5: the same holds around an uncontrolled dense 4x4 (the Kraus superoperators of vec(rho) on [w, n + w],
+// two-qubit Pauli rotations): a 1-q gate on one of its wires multiplies onto it as U (x) I / I (x) U
+// (BuildOp::pad = 1 / 2), a 4x4 on the same ordered pair as a plain product, and a new 4x4 takes the
+// pending 1-q matrices of its two wires with it (take_pending).  A noisy model's gate-channel-gate-channel run on one
+// wire (U (x) conj U, superoperator, ...) becomes ONE 4x4 per sample.
+bool Lowering::merge(const LoweredOp &lo, const BuildOp &bo, int i) {
+  if (lo.nc != 0 || (lo.kind != LK_1Q && lo.kind != LK_2Q)) return false;
+  const int prev = last_touch[lo.t0];
+  if (prev < 0) return false;
+  const LoweredOp &pl = p->lowered[prev];
+  if (lo.kind == LK_1Q) {
+    if (pl.kind == LK_1Q && pl.nc == 0 && pl.t0 == lo.t0) {
+      multiply_onto(prev, lo, bo, i, 0, LF_PERMX);  // a product of gates is a general 2x2
+      return true;
+    }
+    if (pl.kind == LK_2Q && pl.nc == 0 && (pl.t0 == lo.t0 || pl.t1 == lo.t0)) {
+      multiply_onto(prev, lo, bo, i, pl.t0 == lo.t0 ? 1 : 2, 0);
+      return true;
+    }
+    return false;
+  }
+  if (prev == last_touch[lo.t1] && pl.kind == LK_2Q && pl.nc == 0 && pl.t0 == lo.t0 && pl.t1 == lo.t1) {
+    multiply_onto(prev, lo, bo, i, 0, 0);
+    return true;
+  }
+  return false;
+}
+
+// the pending 1-q matrices a new uncontrolled 4x4 absorbs (they act first)
+void Lowering::take_pending(LoweredOp &lo, std::vector<BuildOp> &taken, std::vector<int> &taken_src) {
+  for (int side = 0; side < 2; ++side) {
+    const int t = side == 0 ? lo.t0 : lo.t1;
+    const int prev = last_touch[t];
+    if (prev < 0) continue;
+    LoweredOp &pl = p->lowered[prev];
+    if (!(pl.kind == LK_1Q && pl.nc == 0 && pl.t0 == t)) continue;
+    for (BuildOp b1 : group_ops[group_of[prev]]) {
+      b1.pad = (uint16_t)(side + 1);
+      taken.push_back(b1);
+    }
+    if (!(pl.flags & LF_DIAG)) lo.flags &= ~LF_DIAG;
+    for (int s_ : p->lowered_src[prev]) taken_src.push_back(s_);
+    group_ops[group_of[prev]].clear();  // (its matrix slot stays allocated, nothing builds or reads it)
+    pl.kind = kLoweredDead;             // removed when the tape is through
+  }
+}
+
+// Opcodes -> lowered operators (p->lowered, p->lowered_src) and the source gates of their matrices (p->build_ops,
+// p->groups).  The tape has passed validate_tape.
+static void lower_tape(qmle_plan *p) {
+  const int n = p->n;
+  p->lowered.clear(); p->lowered_src.clear(); p->build_ops.clear(); p->groups.clear();
+  p->algo_bytes_per_state = 0;
+  p->mat_floats = 0;
+  const bool merging = !(p->flags & (QMLE_PLAN_NO_FUSION | QMLE_PLAN_NO_MERGE));
+  Lowering lw(p);
+  for (size_t i = 0; i < p->ops.size(); ++i) {
+    const qmle_op &op = p->ops[i];
+    p->algo_bytes_per_state += algo_bytes(op, n);
+    if (op.opcode == QMLE_OP_ID) continue;  // identity: nothing to do
+    LoweredOp lo = lowered_form(op, n);
+    if (lo.kind == LK_DIAG_ALL || lo.kind == LK_4Q) {  // (their numbers come from the const blob: no build group)
+      lw.push(lo, {(int)i});
       continue;
     }
-
-    switch (op.opcode) {
-      case QMLE_OP_CX: case QMLE_OP_CY: case QMLE_OP_CZ: case QMLE_OP_CRX:
-      case QMLE_OP_CRY: case QMLE_OP_CRZ: case QMLE_OP_CPHASE:
-        lo.kind = LK_1Q; lo.nc = 1; lo.c0 = pos(op.wire[0]); lo.t0 = pos(op.wire[1]);
-        break;
-      case QMLE_OP_CCX:
-        lo.kind = LK_1Q; lo.nc = 2; lo.c0 = pos(op.wire[0]); lo.c1 = pos(op.wire[1]);
-        lo.t0 = pos(op.wire[2]);
-        break;
-      case QMLE_OP_CSWAP:
-        lo.kind = LK_2Q; lo.nc = 1; lo.c0 = pos(op.wire[0]); lo.t0 = pos(op.wire[1]);
-        lo.t1 = pos(op.wire[2]);
-        break;
-      case QMLE_OP_SWAP: case QMLE_OP_RXX: case QMLE_OP_RYY: case QMLE_OP_RZZ:
-      case QMLE_OP_RZX: case QMLE_OP_MAT2:
-        lo.kind = LK_2Q; lo.nc = 0; lo.t0 = pos(op.wire[0]); lo.t1 = pos(op.wire[1]);
-        break;
-      default:  // uncontrolled 1-qubit
-        lo.kind = LK_1Q; lo.nc = 0; lo.t0 = pos(op.wire[0]);
-        break;
-    }
-
-    // commutation-aware merge: an uncontrolled 1-q gate multiplies onto the
-    // previous uncontrolled 1-q matrix on the same wire if nothing touched that
-    // wire in between (gates on disjoint wires commute).
-    if (fuse && !(p->flags & QMLE_PLAN_NO_MERGE) && lo.kind == LK_1Q && lo.nc == 0) {
-      const int prev = last_touch[lo.t0];
-      if (prev >= 0) {
-        LoweredOp &pl = p->lowered[prev];
-        if (pl.kind == LK_1Q && pl.nc == 0 && pl.t0 == lo.t0) {
-          group_ops[group_of[prev]].push_back(bo);
-          if (!(lo.flags & LF_DIAG)) pl.flags &= ~LF_DIAG;
-          pl.flags &= ~LF_PERMX;  // a product of gates is a general 2x2
-          p->lowered_src[prev].push_back((int)i);
-          continue;
-        }
-      }
-    }
-
-    // Round 5: the same holds around an uncontrolled dense 4x4 (the Kraus superoperators of vec(rho) on [w, n + w],
-    // two-qubit Pauli rotations): a 1-q gate on one of its wires multiplies onto it as U (x) I / I (x) U
-    // (BuildOp::pad = 1 / 2), a 4x4 on the same ordered pair as a plain product, and a new 4x4 takes the
-    // pending 1-q matrices of its two wires with it.  A noisy model's gate-channel-gate-channel run on one wire
-    // (U (x) conj U, superoperator, ...) becomes ONE 4x4 per sample.
-    const bool merge_2q = fuse && !(p->flags & QMLE_PLAN_NO_MERGE);
-    if (merge_2q && lo.kind == LK_1Q && lo.nc == 0) {
-      const int prev = last_touch[lo.t0];
-      if (prev >= 0) {
-        LoweredOp &pl = p->lowered[prev];
-        if (pl.kind == LK_2Q && pl.nc == 0 && (pl.t0 == lo.t0 || pl.t1 == lo.t0)) {
-          bo.pad = pl.t0 == lo.t0 ? 1 : 2;
-          group_ops[group_of[prev]].push_back(bo);
-          if (!(lo.flags & LF_DIAG)) pl.flags &= ~LF_DIAG;
-          p->lowered_src[prev].push_back((int)i);
-          continue;
-        }
-      }
-    }
-    std::vector<BuildOp> taken;      // pending 1-q matrices a new 4x4 absorbs (they act first)
+    BuildOp bo{};
+    bo.opcode = op.opcode;
+    for (int a = 0; a < 3; ++a) bo.slot[a] = op.slot[a];
+    bo.const_off = op.mat_off;
+    if (merging && lw.merge(lo, bo, (int)i)) continue;
+    std::vector<BuildOp> taken;
     std::vector<int> taken_src;
-    if (merge_2q && lo.kind == LK_2Q && lo.nc == 0) {
-      const int pa = last_touch[lo.t0], pb = last_touch[lo.t1];
-      if (pa >= 0 && pa == pb) {
-        LoweredOp &pl = p->lowered[pa];
-        if (pl.kind == LK_2Q && pl.nc == 0 && pl.t0 == lo.t0 && pl.t1 == lo.t1) {
-          group_ops[group_of[pa]].push_back(bo);
-          if (!(lo.flags & LF_DIAG)) pl.flags &= ~LF_DIAG;
-          p->lowered_src[pa].push_back((int)i);
-          continue;
-        }
-      }
-      for (int side = 0; side < 2; ++side) {
-        const int t = side == 0 ? lo.t0 : lo.t1;
-        const int prev = last_touch[t];
-        if (prev < 0) continue;
-        LoweredOp &pl = p->lowered[prev];
-        if (!(pl.kind == LK_1Q && pl.nc == 0 && pl.t0 == t)) continue;
-        for (BuildOp b1 : group_ops[group_of[prev]]) {
-          b1.pad = (uint16_t)(side + 1);
-          taken.push_back(b1);
-        }
-        if (!(pl.flags & LF_DIAG)) lo.flags &= ~LF_DIAG;
-        for (int s_ : p->lowered_src[prev]) taken_src.push_back(s_);
-        group_ops[group_of[prev]].clear();  // (its matrix slot stays allocated, nothing builds or reads it)
-        pl.kind = kLoweredDead;             // removed below
-      }
-    }
-
+    if (merging && lo.kind == LK_2Q && lo.nc == 0) lw.take_pending(lo, taken, taken_src);
     const uint32_t dim = lo.kind == LK_2Q ? 4u : 2u;
     lo.mat_off = p->mat_floats;
     p->mat_floats += dim * dim * 2;
-    const int idx = (int)p->lowered.size();
-    group_of.resize(idx + 1, -1);
-    group_of[idx] = (int)group_ops.size();
     taken.push_back(bo);
-    group_ops.push_back(taken);
-    group_meta.push_back({lo.mat_off, dim});
-    const uint64_t m = op_mask(lo, n);
-    for (int b = 0; b < n; ++b)
-      if (m & bit(b)) last_touch[b] = idx;
-    p->lowered.push_back(lo);
     taken_src.push_back((int)i);
     std::sort(taken_src.begin(), taken_src.end());
-    p->lowered_src.push_back(taken_src);
+    const int idx = lw.push(lo, taken_src);
+    lw.group_of[idx] = (int)lw.group_ops.size();
+    lw.group_ops.push_back(taken);
+    lw.group_meta.push_back({lo.mat_off, dim});
   }
-  {  // drop the 1-q operators a 4x4 absorbed
-    size_t w = 0;
-    for (size_t r = 0; r < p->lowered.size(); ++r) {
-      if (p->lowered[r].kind == kLoweredDead) continue;
-      if (w != r) {
-        p->lowered[w] = p->lowered[r];
-        p->lowered_src[w] = std::move(p->lowered_src[r]);
-      }
-      ++w;
+  size_t w = 0;  // drop the 1-q operators a 4x4 absorbed
+  for (size_t r = 0; r < p->lowered.size(); ++r) {
+    if (p->lowered[r].kind == kLoweredDead) continue;
+    if (w != r) {
+      p->lowered[w] = p->lowered[r];
+      p->lowered_src[w] = std::move(p->lowered_src[r]);
     }
-    p->lowered.resize(w);
-    p->lowered_src.resize(w);
+    ++w;
   }
+  p->lowered.resize(w);
+  p->lowered_src.resize(w);
   // flatten the per-matrix source lists (tape order inside each group)
-  for (size_t g = 0; g < group_ops.size(); ++g) {
-    if (group_ops[g].empty()) continue;
-    BuildGroup bg{(uint32_t)p->build_ops.size(), 0, group_meta[g].first, group_meta[g].second};
-    for (const BuildOp &b : group_ops[g]) p->build_ops.push_back(b);
+  for (size_t g = 0; g < lw.group_ops.size(); ++g) {
+    if (lw.group_ops[g].empty()) continue;
+    BuildGroup bg{(uint32_t)p->build_ops.size(), 0, lw.group_meta[g].first, lw.group_meta[g].second};
+    for (const BuildOp &b : lw.group_ops[g]) p->build_ops.push_back(b);
     bg.end = (uint32_t)p->build_ops.size();
     p->groups.push_back(bg);
   }
+}
 
-  // ---- 1b. low bit positions first ---------------------------------------------
-  // Gates that share no wire commute: among the gates that are ready (no earlier gate on any
-  // of their wires pending) take the one whose highest bit position is lowest.  The passes
-  // then work their way up from the low bits, and a run from |0..0> keeps its known-zero
-  // bits at the TOP: the amplitudes that can be non-zero stay one contiguous block (the
-  // measuring pass of K2 reads 8 MiB in one piece instead of 128-byte runs every 2 KiB).
-  if (fuse && !(p->flags & QMLE_PLAN_TAPE_ORDER) && p->lowered.size() > 1 && p->lowered.size() <= 16384) {
-    const size_t nl = p->lowered.size();
-    std::vector<std::vector<int>> queue(n);  // per bit: ops touching it, tape order
-    std::vector<size_t> head(n, 0);
-    std::vector<uint64_t> masks(nl);
-    for (size_t i = 0; i < nl; ++i) {
-      masks[i] = op_mask(p->lowered[i], n);
-      for (int b = 0; b < n; ++b)
-        if (masks[i] & bit(b)) queue[b].push_back((int)i);
-    }
-    auto ready = [&](int i) {
-      for (int b = 0; b < n; ++b)
-        if ((masks[i] & bit(b)) && queue[b][head[b]] != i) return false;
-      return true;
-    };
-    std::vector<std::pair<int, int>> heap;  // (highest bit, index), min-heap
-    auto cmp = [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x > y; };
-    std::vector<char> queued(nl, 0);
-    auto push_if_ready = [&](int i) {
-      if (queued[i] || !ready(i)) return;
-      queued[i] = 1;
-      heap.push_back({63 - __builtin_clzll(masks[i] ? masks[i] : 1ull), i});
-      std::push_heap(heap.begin(), heap.end(), cmp);
-    };
-    for (size_t i = 0; i < nl; ++i) push_if_ready((int)i);
-    std::vector<int> order;
-    order.reserve(nl);
-    while (!heap.empty()) {
-      std::pop_heap(heap.begin(), heap.end(), cmp);
-      const int i = heap.back().second;
-      heap.pop_back();
-      order.push_back(i);
-      for (int b = 0; b < n; ++b)
-        if (masks[i] & bit(b)) ++head[b];
-      for (int b = 0; b < n; ++b)
-        if ((masks[i] & bit(b)) && head[b] < queue[b].size()) push_if_ready(queue[b][head[b]]);
-    }
-    if (order.size() == nl) {
-      std::vector<LoweredOp> lo2(nl);
-      std::vector<std::vector<int>> src2(nl);
-      for (size_t k = 0; k < nl; ++k) {
-        lo2[k] = p->lowered[order[k]];
-        src2[k] = std::move(p->lowered_src[order[k]]);
+// ---- 1b. low bit positions first ---------------------------------------------
+// Gates that share no wire commute: among the gates that are ready (no earlier gate on any
+// of their wires pending) take the one whose highest bit position is lowest.  The passes
+// then work their way up from the low bits, and a run from |0..0> keeps its known-zero
+// bits at the TOP: the amplitudes that can be non-zero stay one contiguous block (the
+// measuring pass of K2 reads 8 MiB in one piece instead of 128-byte runs every 2 KiB).
+static void reorder_low_bits_first(qmle_plan *p) {
+  const int n = p->n;
+  const size_t nl = p->lowered.size();
+  if ((p->flags & (QMLE_PLAN_NO_FUSION | QMLE_PLAN_TAPE_ORDER)) || nl <= 1 || nl > 16384) return;
+  std::vector<std::vector<int>> queue(n);  // per bit: ops touching it, tape order
+  std::vector<size_t> head(n, 0);
+  std::vector<uint64_t> masks(nl);
+  for (size_t i = 0; i < nl; ++i) {
+    masks[i] = op_mask(p->lowered[i], n);
+    for (int b = 0; b < n; ++b)
+      if (masks[i] & bit(b)) queue[b].push_back((int)i);
+  }
+  std::vector<std::pair<int, int>> heap;  // (highest bit, index), min-heap
+  const std::greater<std::pair<int, int>> cmp;
+  std::vector<char> queued(nl, 0);
+  auto push_if_ready = [&](int i) {  // ready: at the head of the queue of every bit it touches
+    if (queued[i]) return;
+    for (int b = 0; b < n; ++b)
+      if ((masks[i] & bit(b)) && queue[b][head[b]] != i) return;
+    queued[i] = 1;
+    heap.push_back({63 - __builtin_clzll(masks[i] ? masks[i] : 1ull), i});
+    std::push_heap(heap.begin(), heap.end(), cmp);
+  };
+  for (size_t i = 0; i < nl; ++i) push_if_ready((int)i);
+  std::vector<int> order;
+  order.reserve(nl);
+  while (!heap.empty()) {
+    std::pop_heap(heap.begin(), heap.end(), cmp);
+    const int i = heap.back().second;
+    heap.pop_back();
+    order.push_back(i);
+    for (int b = 0; b < n; ++b)
+      if (masks[i] & bit(b)) ++head[b];
+    for (int b = 0; b < n; ++b)
+      if ((masks[i] & bit(b)) && head[b] < queue[b].size()) push_if_ready(queue[b][head[b]]);
+  }
+  if (order.size() != nl) return;
+  std::vector<LoweredOp> lo2(nl);
+  std::vector<std::vector<int>> src2(nl);
+  for (size_t k = 0; k < nl; ++k) {
+    lo2[k] = p->lowered[order[k]];
+    src2[k] = std::move(p->lowered_src[order[k]]);
+  }
+  p->lowered.swap(lo2);
+  p->lowered_src.swap(src2);
+}
+
+// ---- 3. schedule into stages (for one tile geometry) ---------------------------
+// A schedule candidate: the tile geometry (T tile positions, the lowest L of them contiguous) and what varies it.
+// lazy: X / CX whose wires are not in the tile yet wait (the fast tile path folds them into
+// the LDS layout for free, so they should never claim a tile bit a dense gate could use);
+// whatever room is left after the first sweep is filled by a second, plain greedy sweep.
+// HE layer at n = 24: dense gates per pass 12/7/5 -> 12/8/4, the measuring pass drops from
+// two register-tile groups to one.
+// carry >= 0: every tile after the first also holds bit position `carry` (position 6 = byte
+// address bit 9: a read+write pass whose tile holds it moves two 128-byte rows 512 B apart with
+// every load / store instruction and runs 12-15 % faster -- 51 -> 44 us per state at n = 24,
+// profiles/r03_rw_tile_bits.txt; the price is one of the tile's 8 free positions).
+// T_first > T: the first stage of a run from |0..0> computes ONE tile per state (everything else
+// is zeros whatever the tile size), so it may stage up to 2^14 amplitudes at no cost in traffic.
+// top_first (round 5, tuner candidates only): the first stage of a run from |0..0> -- ONE tile per state wherever
+// that tile sits -- takes the TOP T_first positions instead of the low ones: every gate that lives inside that
+// window runs on one tile per state, and what is left (the low positions plus whatever a deferred gate reaches
+// up to) is scheduled as usual, on tiles with long contiguous rows.  The n = 24 headline layer: {10..23} first,
+// then ONE measuring pass on {0..10, 23} -- two passes where the low-first schedule needs three.  The tile is a
+// contiguous run of positions (Stage::shift): local index << shift is the address, no rows, no LUT.
+// Such a schedule trades an HBM pass for arithmetic in the passes that are left: fewer bytes, less time, a
+// lower fraction of the HBM roofline.
+enum ScheduleVariant : int {
+  SV_PLAIN = 0,             // the round-2 schedules
+  SV_WIDE_FIRST = 1,        // wide first stage
+  SV_CARRY_WIDE_FIRST = 2,  // position 6 carried + wide first stage
+  SV_CARRY = 3,             // position 6 carried
+  SV_TOP_FIRST = 4,         // first tile of 2^14 amplitudes on the TOP positions (all-live runs from |0..0>)
+  kScheduleVariants = 5
+};
+constexpr int kGeometries[][2] = {{13, 7}, {13, 5}, {12, 4}, {13, 4}, {12, 5}, {13, 6}};  // (T, L)
+constexpr int kNumGeometries = (int)(sizeof(kGeometries) / sizeof(kGeometries[0]));
+constexpr int kCarriedPosition = 6;
+struct ScheduleCandidate {
+  int T, L;
+  bool lazy;
+  int carry;
+  int T_first;
+  bool top_first;
+  int variant;
+};
+// Candidate number k (qmle_plan::chosen_candidate, QMLE_FORCE_CAND) = geometry x [eager, lazy CX] x variant, the
+// geometry running fastest.  Ties between candidates keep the lower number.
+constexpr int kCandidatesPerVariant = 2 * kNumGeometries;
+constexpr int kNumCandidates = kCandidatesPerVariant * kScheduleVariants;
+static int variant_of(int k) { return k / kCandidatesPerVariant; }
+static ScheduleCandidate candidate_of(int k) {
+  const int g = k % kNumGeometries, v = variant_of(k);
+  const bool wide = v == SV_WIDE_FIRST || v == SV_CARRY_WIDE_FIRST || v == SV_TOP_FIRST;
+  const bool carried = v == SV_CARRY_WIDE_FIRST || v == SV_CARRY;
+  return {kGeometries[g][0], kGeometries[g][1], (k / kNumGeometries) % 2 != 0, carried ? kCarriedPosition : -1,
+          wide ? kLdsMaxQubits : 0, v == SV_TOP_FIRST, v};
+}
+
+static inline int popc(uint64_t x) { return __builtin_popcountll(x); }
+static inline uint64_t all_positions(int n) { return n >= 64 ? ~0ull : bit(n) - 1; }
+
+// One run of schedule_stages: the candidate, and how far the lowered operators have been placed.
+struct ScheduleRun {
+  qmle_plan *p;
+  ScheduleCandidate c;  // (T and L clamped to the register)
+  int pad_high;         // QMLE_PAD_HIGH / qmle_plan::pad_high
+  std::vector<char> done;
+  size_t n_done = 0;
+  uint32_t zeros;  // known-zero positions so far (|0..0> start)
+  bool is_last(const std::vector<int> &members) const { return n_done + members.size() == p->lowered.size(); }
+};
+
+// Members of a top-first first stage on the window Q of the top T positions: every operator that lives inside it and
+// has no operator in front of it that does not.  false: nothing lives up there (or everything does: one stage,
+// nothing to gain).
+static bool select_top_window(const qmle_plan *p, int T, std::vector<int> &members, uint64_t &Q) {
+  const int n = p->n;
+  const size_t nl = p->lowered.size();
+  const uint64_t all_mask = all_positions(n), W = all_mask & ~(bit(n - T) - 1);
+  uint64_t blocked = 0;
+  for (size_t i = 0; i < nl; ++i) {
+    const LoweredOp &o = p->lowered[i];
+    const uint64_t m = op_mask(o, n);
+    if (o.kind == LK_DIAG_ALL || (m & blocked) || (m & ~W)) blocked |= m;
+    else members.push_back((int)i);
+    if ((blocked & all_mask) == all_mask) break;
+  }
+  if (members.empty() || members.size() == nl) {
+    members.clear();
+    return false;
+  }
+  Q = W;
+  return true;
+}
+
+// Members of a tile of T positions behind the operators placed so far, `first` the first pending one (no DIAG_ALL):
+// greedy sweeps over the pending operators, the first of them lazy when the candidate says so.  Q: the positions the
+// tile must hold; stageL: its contiguous low positions (fewer than the candidate's when the first operator needs room).
+static void select_greedy(const ScheduleRun &r, size_t first, int T, std::vector<int> &members, uint64_t &Q, int &stageL) {
+  const qmle_plan *p = r.p;
+  const int n = p->n, carry = r.c.carry;
+  const bool lazy = r.c.lazy, no_fusion = (p->flags & QMLE_PLAN_NO_FUSION) != 0;
+  const size_t nl = p->lowered.size();
+  const uint64_t all_mask = all_positions(n);
+  // first pending op decides whether the default low-bit count fits
+  const uint64_t fm = op_mask(p->lowered[first], n);
+  while (stageL > 1 && popc((bit(stageL) - 1) | fm) > T) --stageL;
+  Q = bit(stageL) - 1;
+  if (carry >= stageL && carry < n && !p->stages.empty() && popc(Q | fm | bit(carry)) <= T) Q |= bit(carry);
+  std::vector<char> taken;
+  if (lazy) taken.assign(nl, 0);
+  for (int sweep = lazy ? 0 : 1; sweep < 2; ++sweep) {
+    uint64_t blocked = 0;
+    for (size_t i = first; i < nl; ++i) {
+      if (r.done[i] || (lazy && taken[i])) continue;
+      const LoweredOp &o = p->lowered[i];
+      const uint64_t m = op_mask(o, n);
+      const bool wait = sweep == 0 && o.kind == LK_1Q && o.nc <= 1 && (o.flags & LF_PERMX) &&
+                        (m & ~Q) != 0;
+      if (o.kind == LK_DIAG_ALL || (m & blocked)) {
+        blocked |= m;
+      } else if (!wait && popc(Q | m) <= T) {
+        Q |= m;
+        members.push_back((int)i);
+        if (lazy) taken[i] = 1;
+        if (no_fusion) break;
+      } else {
+        blocked |= m;
       }
-      p->lowered.swap(lo2);
-      p->lowered_src.swap(src2);
+      if ((blocked & all_mask) == all_mask) break;
+    }
+    if (popc(Q) >= T) break;
+  }
+  // (an op taken by the second sweep never shares a wire with a LATER op of the first: that
+  // one would have been blocked behind it -- so index order is a valid execution order)
+  if (lazy) std::sort(members.begin(), members.end());
+}
+
+// A stage of one operator `m0` that the streaming kernel (k_direct_1q) runs, without a tile.
+// a control on bits 1..3 selects 16/32/64-byte runs inside every 128-byte line: the
+// streaming kernel would move whole lines for half the work (measured 2-4x slower
+// than a tile pass at n = 28), so those go through the LDS tile instead
+// (round 2: with the target on bits 1..6 too, the lane-exchange mode of the streaming
+// kernel takes those controls: k_direct_1q mode 7)
+static bool runs_direct(const qmle_plan *p, const LoweredOp &m0) {
+  if (p->whole_state_lds || (p->flags & QMLE_PLAN_FORCE_TILE) || m0.kind != LK_1Q) return false;
+  return m0.nc == 0 ||
+         (m0.nc == 1 && (m0.c0 == 0 || m0.c0 >= 4 ||
+                         (!(m0.flags & LF_DIAG) && p->n >= 14 && m0.t0 >= 1 && m0.t0 <= 6) ||
+                         // a controlled PHASE rewrites the |11> quarter only (k_direct_1q mode 9):
+                         // with the target above the line that is half the lines, not all of them
+                         ((m0.flags & LF_PHASE) && m0.t0 >= 4)));
+}
+
+// The tile of a stage: the positions Q its members need, padded to T, as tile_bits / outer_bits, and the members
+// with tile-local positions at the end of dev_ops.
+static void place_tile(const ScheduleRun &r, Stage &st, const std::vector<int> &members, uint64_t Q, int T, int stageL,
+                       bool top_stage) {
+  qmle_plan *p = r.p;
+  const int n = p->n, carry = r.c.carry;
+  const bool last = !p->stages.empty() && r.is_last(members);  // the last stage of several
+  // pad the tile with the lowest free bit positions
+  // (tuning: QMLE_PAD_HIGH=1 pads the LAST stage from the top instead)
+  if (r.pad_high && last) {
+    if (carry >= stageL && carry < n && (Q & bit(carry))) {  // the carried position serves read+write passes
+      uint64_t need = 0;
+      for (int mi : members) need |= op_mask(p->lowered[mi], n);
+      if (!(need & bit(carry))) Q &= ~bit(carry);
+    }
+    if (r.pad_high >= 2 && popc(Q) < T) Q |= bit(r.pad_high);  // (one chosen low position)
+    for (int b = n - 1; b >= 0 && popc(Q) < T; --b) Q |= bit(b);
+  }
+  // The LAST stage of a 2^13-tile schedule whose gates need <= 12 positions takes a 2^12 tile: five 32 KiB
+  // workgroups per CU overlap their loads and their groups where two 64 KiB ones do not (the measuring pass
+  // of the 4-layer n = 24 model: DESIGN 9e, profiles/r05_small_last_tile_ab.txt)
+  int Tpad = T;
+  if (T == 13 && last && popc(Q) <= 12 && !(p->flags & QMLE_PLAN_NO_FUSION)) Tpad = 12;
+  for (int b = 0; b < n && popc(Q) < Tpad; ++b) Q |= bit(b);
+  st.T = popc(Q);
+  int nt = 0, no = 0;
+  int8_t local_of[64];
+  for (int b = 0; b < n; ++b) {
+    if (Q & bit(b)) { local_of[b] = (int8_t)nt; st.tile_bits[nt++] = (int8_t)b; }
+    else { local_of[b] = -1; st.outer_bits[no++] = (int8_t)b; }
+  }
+  // contiguous low run actually present
+  int run = 0;
+  while (run < st.T && st.tile_bits[run] == run) ++run;
+  st.L = run < 1 ? 1 : run;
+  if (top_stage) {  // a contiguous run of positions that does not start at 0: address = local index << shift
+    st.shift = n - st.T;
+    st.L = st.T;
+  }
+  for (int mi : members) {
+    LoweredOp o = p->lowered[mi];
+    if (o.kind != LK_DIAG_ALL) {
+      o.t0 = local_of[(int)o.t0];
+      if (o.t1 >= 0) o.t1 = local_of[(int)o.t1];
+      if (o.c0 >= 0) o.c0 = local_of[(int)o.c0];
+      if (o.c1 >= 0) o.c1 = local_of[(int)o.c1];
+    }
+    p->dev_ops.push_back(o);
+    p->dev_src.push_back(single_src(p, mi));
+  }
+}
+
+// The members leave the pending set: the positions they mix, the tape's gates they cover, their SURVEY 8-d bytes.
+static void record_members(ScheduleRun &r, Stage &st, const std::vector<int> &members) {
+  const qmle_plan *p = r.p;
+  for (int mi : members) {
+    r.done[mi] = 1;
+    ++r.n_done;
+    const LoweredOp &lo = p->lowered[mi];  // global positions
+    if (lo.kind == LK_4Q) {
+      st.touched |= (1u << lo.t0) | (1u << lo.t1) | (1u << lo.c0) | (1u << lo.c1);
+    } else if (lo.kind != LK_DIAG_ALL && !(lo.flags & LF_DIAG)) {
+      st.touched |= 1u << lo.t0;  // controls keep their known-zero status
+      if (lo.t1 >= 0) st.touched |= 1u << lo.t1;
+    }
+    for (int s : p->lowered_src[mi]) {
+      st.src_ops.push_back(s);
+      st.algo_bytes_per_state += algo_bytes(p->ops[s], p->n);
     }
   }
+}
 
-  // ---- 2. choose regime ------------------------------------------------------
-  const int forced_T = (int)((p->flags >> 8) & 0xff);
-  const int forced_L = (int)((p->flags >> 16) & 0xff);
-  p->whole_state_lds = (n <= kLdsMaxQubits) && !(p->flags & QMLE_PLAN_FORCE_GLOBAL) &&
-                       (forced_T == 0 || forced_T >= n);
-  if (!p->whole_state_lds && forced_T != 0 && forced_T < 4 && forced_T < n)
-    return QMLE_ERR_INVALID_ARG;
+static void push_stage(ScheduleRun &r, Stage &st) {  // (Stage::zero_in: the known zeros along the execution order)
+  st.zero_in = r.zeros;
+  r.zeros &= ~st.touched;
+  r.p->stages.push_back(st);
+}
 
-  // ---- 3. schedule into stages (for one tile geometry) ---------------------------
-  // lazy: X / CX whose wires are not in the tile yet wait (the fast tile path folds them into
-  // the LDS layout for free, so they should never claim a tile bit a dense gate could use);
-  // whatever room is left after the first sweep is filled by a second, plain greedy sweep.
-  // HE layer at n = 24: dense gates per pass 12/7/5 -> 12/8/4, the measuring pass drops from
-  // two register-tile groups to one.
-  // carry >= 0: every tile after the first also holds bit position `carry` (position 6 = byte
-  // address bit 9: a read+write pass whose tile holds it moves two 128-byte rows 512 B apart with
-  // every load / store instruction and runs 12-15 % faster -- 51 -> 44 us per state at n = 24,
-  // profiles/r03_rw_tile_bits.txt; the price is one of the tile's 8 free positions).
-  // T_first > T: the first stage of a run from |0..0> computes ONE tile per state (everything else
-  // is zeros whatever the tile size), so it may stage up to 2^14 amplitudes at no cost in traffic.
-  // top_first (round 5, tuner candidates only): the first stage of a run from |0..0> -- ONE tile per state wherever
-  // that tile sits -- takes the TOP T_first positions instead of the low ones: every gate that lives inside that
-  // window runs on one tile per state, and what is left (the low positions plus whatever a deferred gate reaches
-  // up to) is scheduled as usual, on tiles with long contiguous rows.  The n = 24 headline layer: {10..23} first,
-  // then ONE measuring pass on {0..10, 23} -- two passes where the low-first schedule needs three.  The tile is a
-  // contiguous run of positions (Stage::shift): local index << shift is the address, no rows, no LUT.
-  auto schedule = [&](int T, int L, bool lazy = false, int carry = -1, int T_first = 0, bool top_first = false) {
-    if (p->whole_state_lds) T = n;
-    if (T > kLdsMaxQubits) T = kLdsMaxQubits;
-    if (T > n) T = n;
-    if (L > T) L = T;
-    if (L < 1) L = 1;
-    p->tile_T = T;
-    p->tile_L = L;
-    p->stages.clear();
-    p->dev_ops.clear();
-    p->dev_src.clear();
-    p->op_groups.clear();
-    p->ops2.clear();
-    p->groups2.clear();
-    p->tbl2.clear();
-    p->consts.resize(n_user_consts);  // drop permuted-matrix copies of a previous candidate
-    const size_t nl = p->lowered.size();
-    std::vector<char> done(nl, 0);
-    size_t n_done = 0;
-    const bool no_fusion = (p->flags & QMLE_PLAN_NO_FUSION) != 0;
-    const bool force_tile = (p->flags & QMLE_PLAN_FORCE_TILE) != 0;
-    const uint64_t all_mask = n >= 64 ? ~0ull : bit(n) - 1;
-    uint32_t Zrun = n >= 32 ? ~0u : ((1u << n) - 1u);  // known-zero positions so far (|0..0> start)
+static void push_diag_all_stage(ScheduleRun &r, size_t i) {  // a full-register diagonal is a stage of its own
+  qmle_plan *p = r.p;
+  Stage st;
+  st.kind = ST_DIAG_ALL;
+  st.op_begin = (int)p->dev_ops.size();
+  p->dev_ops.push_back(p->lowered[i]);
+  p->dev_src.push_back(single_src(p, i));
+  st.op_end = (int)p->dev_ops.size();
+  st.src_ops = p->lowered_src[i];
+  r.done[i] = 1;
+  ++r.n_done;
+  push_stage(r, st);
+}
 
-    auto popc = [](uint64_t x) { return __builtin_popcountll(x); };
-
-    const int T_plan = T;
-    while (n_done < nl) {
-      std::vector<int> members;
-      uint64_t Q = 0;
-      int stageL = L;
-      T = T_plan;
-      if (!p->whole_state_lds && p->stages.empty() && T_first > T_plan) {
-        T = T_first;
-        if (T > kLdsMaxQubits) T = kLdsMaxQubits;
-        if (T > n - 1) T = n - 1;
-        if (T < T_plan) T = T_plan;
+// What a stage's neighbours and its known-zero input decide: Stage::next_tile, Stage::product_ok, fold_groups.
+static void mark_known_zeros(qmle_plan *p) {
+  p->fold_groups = 0;
+  for (size_t si = 0; si < p->stages.size(); ++si) {
+    Stage &st = p->stages[si];
+    st.next_tile = si + 1 < p->stages.size() && p->stages[si + 1].kind == ST_TILE;
+    st.product_ok = false;
+    if (st.kind != ST_TILE || si == 0 || st.grp_end <= st.grp_begin || st.T < 8) continue;
+    uint32_t seen = 0;
+    bool ok = true;
+    for (int g = st.grp_begin; g < st.grp_end && ok; ++g) {
+      const OpGroup &og = p->op_groups[g];
+      ok = og.kind == GK_REG4;
+      for (int j = 0; j < 4 && ok; ++j) {
+        const uint32_t lb = 1u << og.bits[j];
+        ok = !(seen & lb) && ((st.zero_in >> st.tile_bits[og.bits[j]]) & 1u);
+        seen |= lb;
       }
-      bool top_stage = false;
-      if (top_first && !p->whole_state_lds && p->stages.empty() && T < n && n <= 28 && !no_fusion && !force_tile) {
-        const uint64_t W = all_mask & ~(bit(n - T) - 1);
-        uint64_t blocked = 0;
-        for (size_t i = 0; i < nl; ++i) {
-          const LoweredOp &o = p->lowered[i];
-          const uint64_t m = op_mask(o, n);
-          if (o.kind == LK_DIAG_ALL || (m & blocked) || (m & ~W)) blocked |= m;
-          else members.push_back((int)i);
-          if ((blocked & all_mask) == all_mask) break;
-        }
-        if (!members.empty() && members.size() < nl) {
-          top_stage = true;
-          Q = W;
-        } else {
-          members.clear();  // nothing lives up there (or everything does: one stage, nothing to gain)
-        }
-      }
-      if (top_stage) {
-        // (members chosen above)
-      } else if (p->whole_state_lds) {
-        for (size_t i = 0; i < nl; ++i) members.push_back((int)i);
-        Q = all_mask;
-      } else {
-        // first pending op decides whether the default low-bit count fits
-        size_t first = 0;
-        while (done[first]) ++first;
-        const LoweredOp &fo = p->lowered[first];
-        if (fo.kind == LK_DIAG_ALL) {
-          Stage st;
-          st.kind = ST_DIAG_ALL;
-          st.op_begin = (int)p->dev_ops.size();
-          p->dev_ops.push_back(fo);
-          p->dev_src.push_back(p->lowered_src[first].size() == 1 ? p->lowered_src[first][0] : -1);
-          st.op_end = (int)p->dev_ops.size();
-          st.src_ops = p->lowered_src[first];
-          p->stages.push_back(st);
-          done[first] = 1;
-          ++n_done;
-          continue;
-        }
-        const uint64_t fm = op_mask(fo, n);
-        while (stageL > 1 && popc((bit(stageL) - 1) | fm) > T) --stageL;
-        Q = bit(stageL) - 1;
-        if (carry >= stageL && carry < n && !p->stages.empty() && popc(Q | fm | bit(carry)) <= T) Q |= bit(carry);
-        std::vector<char> taken;
-        if (lazy) taken.assign(nl, 0);
-        for (int sweep = lazy ? 0 : 1; sweep < 2; ++sweep) {
-          uint64_t blocked = 0;
-          for (size_t i = first; i < nl; ++i) {
-            if (done[i] || (lazy && taken[i])) continue;
-            const LoweredOp &o = p->lowered[i];
-            const uint64_t m = op_mask(o, n);
-            const bool wait = sweep == 0 && o.kind == LK_1Q && o.nc <= 1 && (o.flags & LF_PERMX) &&
-                              (m & ~Q) != 0;
-            if (o.kind == LK_DIAG_ALL || (m & blocked)) {
-              blocked |= m;
-            } else if (!wait && popc(Q | m) <= T) {
-              Q |= m;
-              members.push_back((int)i);
-              if (lazy) taken[i] = 1;
-              if (no_fusion) break;
-            } else {
-              blocked |= m;
-            }
-            if ((blocked & all_mask) == all_mask) break;
-          }
-          if (popc(Q) >= T) break;
-        }
-        // (an op taken by the second sweep never shares a wire with a LATER op of the first: that
-        // one would have been blocked behind it -- so index order is a valid execution order)
-        if (lazy) std::sort(members.begin(), members.end());
-      }
-
-      Stage st;
-      st.L = stageL;
-      st.op_begin = (int)p->dev_ops.size();
-      const LoweredOp &m0 = p->lowered[members[0]];
-      // a control on bits 1..3 selects 16/32/64-byte runs inside every 128-byte line: the
-      // streaming kernel would move whole lines for half the work (measured 2-4x slower
-      // than a tile pass at n = 28), so those go through the LDS tile instead
-      // (round 2: with the target on bits 1..6 too, the lane-exchange mode of the streaming
-      // kernel takes those controls: k_direct_1q mode 7)
-      const bool direct_ok = !top_stage && !p->whole_state_lds && !force_tile && members.size() == 1 &&
-                             m0.kind == LK_1Q &&
-                             (m0.nc == 0 ||
-                              (m0.nc == 1 && (m0.c0 == 0 || m0.c0 >= 4 ||
-                                              (!(m0.flags & LF_DIAG) && n >= 14 && m0.t0 >= 1 && m0.t0 <= 6) ||
-                                              // a controlled PHASE rewrites the |11> quarter only (k_direct_1q mode 9):
-                                              // with the target above the line that is half the lines, not all of them
-                                              ((m0.flags & LF_PHASE) && m0.t0 >= 4))));
-      if (direct_ok) {
-        st.kind = ST_DIRECT;
-        p->dev_ops.push_back(m0);
-        p->dev_src.push_back(p->lowered_src[members[0]].size() == 1 ? p->lowered_src[members[0]][0] : -1);
-      } else {
-        st.kind = ST_TILE;
-        // pad the tile with the lowest free bit positions
-        // (tuning: QMLE_PAD_HIGH=1 pads the LAST stage from the top instead)
-        const int pad_high_env = p->pad_high >= 0 ? p->pad_high
-                                 : std::getenv("QMLE_PAD_HIGH") ? atoi(std::getenv("QMLE_PAD_HIGH")) : 0;
-        if (pad_high_env && !p->stages.empty() && n_done + members.size() == nl) {
-          if (carry >= stageL && carry < n && (Q & bit(carry))) {  // the carried position serves read+write passes
-            uint64_t need = 0;
-            for (int mi : members) need |= op_mask(p->lowered[mi], n);
-            if (!(need & bit(carry))) Q &= ~bit(carry);
-          }
-          if (pad_high_env >= 2 && popc(Q) < T) Q |= bit(pad_high_env);  // (one chosen low position)
-          for (int b = n - 1; b >= 0 && popc(Q) < T; --b) Q |= bit(b);
-        }
-        // The LAST stage of a 2^13-tile schedule whose gates need <= 12 positions takes a 2^12 tile: five 32 KiB
-        // workgroups per CU overlap their loads and their groups where two 64 KiB ones do not (the measuring pass
-        // of the 4-layer n = 24 model: DESIGN 9e, profiles/r05_small_last_tile_ab.txt)
-        int Tpad = T;
-        if (T == 13 && !p->stages.empty() && n_done + members.size() == nl && popc(Q) <= 12 && !no_fusion) Tpad = 12;
-        for (int b = 0; b < n && popc(Q) < Tpad; ++b) Q |= bit(b);
-        st.T = popc(Q);
-        int nt = 0, no = 0;
-        int8_t local_of[64];
-        for (int b = 0; b < n; ++b) {
-          if (Q & bit(b)) { local_of[b] = (int8_t)nt; st.tile_bits[nt++] = (int8_t)b; }
-          else { local_of[b] = -1; st.outer_bits[no++] = (int8_t)b; }
-        }
-        // contiguous low run actually present
-        int run = 0;
-        while (run < st.T && st.tile_bits[run] == run) ++run;
-        st.L = run < 1 ? 1 : run;
-        if (top_stage) {  // a contiguous run of positions that does not start at 0: address = local index << shift
-          st.shift = n - st.T;
-          st.L = st.T;
-        }
-        for (int mi : members) {
-          LoweredOp o = p->lowered[mi];
-          if (o.kind != LK_DIAG_ALL) {
-            o.t0 = local_of[(int)o.t0];
-            if (o.t1 >= 0) o.t1 = local_of[(int)o.t1];
-            if (o.c0 >= 0) o.c0 = local_of[(int)o.c0];
-            if (o.c1 >= 0) o.c1 = local_of[(int)o.c1];
-          }
-          p->dev_ops.push_back(o);
-          p->dev_src.push_back(p->lowered_src[mi].size() == 1 ? p->lowered_src[mi][0] : -1);
-        }
-      }
-      st.op_end = (int)p->dev_ops.size();
-      st.n_tile_ops = st.op_end - st.op_begin;
-      if (st.kind == ST_TILE) {
-        const std::vector<LoweredOp> tile_local(p->dev_ops.begin() + st.op_begin,
-                                                p->dev_ops.begin() + st.op_end);
-        uint32_t zin_local = 0;  // known-zero bits when this stage starts, tile-local
-        for (int j = 0; j < st.T; ++j)
-          if (Zrun & (1u << st.tile_bits[j])) zin_local |= 1u << j;
-        // (what qualifies_for_register_measure will ask of the finished plan; Zrun is this stage's zero_in)
-        const bool measured = placed_for_register_measure(p, st, Zrun, p->stages.empty(), n_done + members.size() == nl);
-        build_fast_groups(p, st, tile_local, zin_local, measured);
-        group_stage_ops(p, st);
-      }
-      for (int mi : members) {
-        done[mi] = 1;
-        ++n_done;
-        const LoweredOp &lo = p->lowered[mi];  // global positions
-        if (lo.kind == LK_4Q) {
-          st.touched |= (1u << lo.t0) | (1u << lo.t1) | (1u << lo.c0) | (1u << lo.c1);
-        } else if (lo.kind != LK_DIAG_ALL && !(lo.flags & LF_DIAG)) {
-          st.touched |= 1u << lo.t0;  // controls keep their known-zero status
-          if (lo.t1 >= 0) st.touched |= 1u << lo.t1;
-        }
-        for (int s : p->lowered_src[mi]) {
-          st.src_ops.push_back(s);
-          st.algo_bytes_per_state += algo_bytes(p->ops[s], n);
-        }
-      }
-      Zrun &= ~st.touched;
-      p->stages.push_back(st);
     }
-    if (p->whole_state_lds && p->stages.empty()) {
-      // empty circuit: still need one stage to produce |0...0>
-      Stage st;
+    st.product_ok = ok;
+    if (ok && st.grp_end - st.grp_begin > p->fold_groups) p->fold_groups = st.grp_end - st.grp_begin;
+  }
+}
+
+// The lowered operators as HBM passes under candidate `c`: whatever an earlier candidate left in the plan goes.
+static void schedule_stages(qmle_plan *p, ScheduleCandidate c, int pad_high) {
+  const int n = p->n;
+  if (p->whole_state_lds) c.T = n;
+  if (c.T > kLdsMaxQubits) c.T = kLdsMaxQubits;
+  if (c.T > n) c.T = n;
+  if (c.L > c.T) c.L = c.T;
+  if (c.L < 1) c.L = 1;
+  p->tile_T = c.T;
+  p->tile_L = c.L;
+  p->stages.clear();
+  p->dev_ops.clear();
+  p->dev_src.clear();
+  p->op_groups.clear();
+  p->ops2.clear();
+  p->groups2.clear();
+  p->tbl2.clear();
+  p->consts.resize(p->n_user_consts);  // drop permuted-matrix copies of a previous candidate
+  const size_t nl = p->lowered.size();
+  ScheduleRun r{p, c, pad_high, std::vector<char>(nl, 0), 0, n >= 32 ? ~0u : ((1u << n) - 1u)};
+  const bool top_first = c.top_first && !p->whole_state_lds && n <= 28 &&
+                         !(p->flags & (QMLE_PLAN_NO_FUSION | QMLE_PLAN_FORCE_TILE));
+  while (r.n_done < nl) {
+    std::vector<int> members;
+    uint64_t Q = 0;
+    int stageL = c.L, T = c.T;
+    if (!p->whole_state_lds && p->stages.empty() && c.T_first > c.T)
+      T = std::max(c.T, std::min(std::min(c.T_first, kLdsMaxQubits), n - 1));
+    const bool top_stage = top_first && p->stages.empty() && T < n && select_top_window(p, T, members, Q);
+    if (!top_stage && p->whole_state_lds) {
+      for (size_t i = 0; i < nl; ++i) members.push_back((int)i);
+      Q = all_positions(n);
+    } else if (!top_stage) {
+      size_t first = 0;
+      while (r.done[first]) ++first;
+      if (p->lowered[first].kind == LK_DIAG_ALL) {
+        push_diag_all_stage(r, first);
+        continue;
+      }
+      select_greedy(r, first, T, members, Q, stageL);
+    }
+    Stage st;
+    st.L = stageL;
+    st.op_begin = (int)p->dev_ops.size();
+    if (!top_stage && members.size() == 1 && runs_direct(p, p->lowered[members[0]])) {
+      st.kind = ST_DIRECT;
+      p->dev_ops.push_back(p->lowered[members[0]]);
+      p->dev_src.push_back(single_src(p, members[0]));
+    } else {
       st.kind = ST_TILE;
-      st.T = n;
-      st.L = L;
-      for (int b = 0; b < n; ++b) st.tile_bits[b] = (int8_t)b;
-      p->stages.push_back(st);
+      place_tile(r, st, members, Q, T, stageL, top_stage);
     }
-    // known-zero bit positions along the execution order (|0..0> start)
-    uint32_t Z = n >= 32 ? ~0u : ((1u << n) - 1u);
-    for (size_t si = 0; si < p->stages.size(); ++si) {
-      Stage &st = p->stages[si];
-      st.zero_in = Z;
-      Z &= ~st.touched;
-      st.next_tile = si + 1 < p->stages.size() && p->stages[si + 1].kind == ST_TILE;
-      st.product_ok = false;
-      if (st.kind == ST_TILE && si > 0 && st.grp_end > st.grp_begin && st.T >= 8) {
-        uint32_t seen = 0;
-        bool ok = true;
-        for (int g = st.grp_begin; g < st.grp_end && ok; ++g) {
-          const OpGroup &og = p->op_groups[g];
-          ok = og.kind == GK_REG4;
-          for (int j = 0; j < 4 && ok; ++j) {
-            const uint32_t lb = 1u << og.bits[j];
-            ok = !(seen & lb) && ((st.zero_in >> st.tile_bits[og.bits[j]]) & 1u);
-            seen |= lb;
-          }
-        }
-        st.product_ok = ok;
-      }
+    st.op_end = (int)p->dev_ops.size();
+    st.n_tile_ops = st.op_end - st.op_begin;
+    if (st.kind == ST_TILE) {
+      const std::vector<LoweredOp> tile_local(p->dev_ops.begin() + st.op_begin, p->dev_ops.begin() + st.op_end);
+      // (what qualifies_for_register_measure will ask of the finished plan; r.zeros is this stage's zero_in)
+      const bool measured = placed_for_register_measure(p, st, r.zeros, p->stages.empty(), r.is_last(members));
+      build_fast_groups(p, st, tile_local, gather_bits(r.zeros, st.tile_bits, st.T), measured);
+      group_stage_ops(p, st);
     }
-    p->fold_groups = 0;
-    for (const Stage &st : p->stages)
-      if (st.product_ok && st.grp_end - st.grp_begin > p->fold_groups)
-        p->fold_groups = st.grp_end - st.grp_begin;
+    record_members(r, st, members);
+    push_stage(r, st);
+  }
+  if (p->whole_state_lds && p->stages.empty()) {
+    // empty circuit: still need one stage to produce |0...0>
+    Stage st;
+    st.kind = ST_TILE;
+    st.T = n;
+    st.L = c.L;
+    for (int b = 0; b < n; ++b) st.tile_bits[b] = (int8_t)b;
+    push_stage(r, st);
+  }
+  mark_known_zeros(p);
+}
 
-  };
+// ---- pass-cost model ----------------------------------------------------------------------------
+// Fast kernel (k_tile2), round-3 model, fitted to per-pass HIP-event times of 1- and 4-layer
+// circuits at n = 24 with and without their gate groups (profiles/r03_pass_model.txt): a pass
+// takes the LONGER of its memory time and its compute time plus a sixth of the shorter one.
+//   memory: 19.5 us write-only, 21 read-only, 50 read+write (5.4 TB/s: the mix costs);
+//   a read+write pass whose every load / store instruction spans positions 6 and 13 (byte
+//   address bits 9 and 16) and no other position below 8 -- a wave's 8 rows of 128 B are
+//   the tile's three lowest high positions -- runs 15 % faster (51.3 -> 43.3 us, K2 pass
+//   2; 54 -> 45 in the bare pass for every tile {6, 13, x >= 8, ...} and for no other pair
+//   tried); every pair of high positions 8 apart costs ~4.5 us (54 -> 71 for {12-15,
+//   20-23}).  The HBM channel hash behind both is not documented: modelled as measured.
+//   compute: 5 + 9.5 per register-tile group, + 10 for the <Z> sums of a measuring pass.
+// rd, wr, tiles: the fractions of the state the pass reads, writes and computes.
+static double fast_pass_cost(const qmle_plan *p, const Stage &st, bool first, bool last, double rd, double wr,
+                             double tiles) {
+  double rw = (first ? 0.0 : 21.0 * rd) + (last ? 0.0 : 19.5 * wr);
+  if (!first && !last) {
+    rw += 9.5 * (rd < wr ? rd : wr);
+    double shape = 0.0;
+    if (st.L == 4 && st.T >= 12) {
+      const int h0 = st.tile_bits[4], h1 = st.tile_bits[5], h2 = st.tile_bits[6];
+      if (h0 == 6 && h1 >= 8 && (h1 == 13 || h2 == 13)) shape -= 7.5;
+    }
+    uint32_t hi = 0;
+    for (int j = st.L; j < st.T; ++j) hi |= 1u << st.tile_bits[j];
+    shape += 4.5 * __builtin_popcount(hi & (hi >> 8));
+    rw += shape * (rd < wr ? rd : wr);
+  }
+  const double cmp = (5.0 + 9.5 * (st.fast_end - st.fast_begin) + (last ? 10.0 : 0.0)) * tiles;
+  return 1.5 + 0.8 * std::ldexp(1.0, 24 - p->n) + (rw > cmp ? rw + cmp / 6.0 : cmp + rw / 6.0);
+}
 
-  // pass-cost model (microseconds per state at n = 24; measured on MI355X, dense passes of 1-
-  // and 3-layer HE circuits, tools/stage_profile.py): a tile pass costs ~11 for its HBM round
-  // trip and ~25 per register-tile group (the gate arithmetic is what a pass is made of: 62 us
-  // with 2 groups, 125 with 5, 192 with 7); a direct single-gate pass ~33
-  // Known zeros scale both parts: a stage reads 2^-|zero_in| of the state, computes and (when
-  // the next stage is a tile stage) stores only the tiles whose outer bits are live.
+// pass-cost model (microseconds per state at n = 24; measured on MI355X, dense passes of 1-
+// and 3-layer HE circuits, tools/stage_profile.py): a tile pass costs ~11 for its HBM round
+// trip and ~25 per register-tile group (the gate arithmetic is what a pass is made of: 62 us
+// with 2 groups, 125 with 5, 192 with 7); a direct single-gate pass ~33
+// Known zeros scale both parts: a stage reads 2^-|zero_in| of the state, computes and (when
+// the next stage is a tile stage) stores only the tiles whose outer bits are live.
+static double schedule_cost(const qmle_plan *p) {
+  const int n = p->n;
   const bool sparse_model = !(p->flags & QMLE_PLAN_NO_SPARSE);
   // the plan is only ever run from |0..0> (qmle_run_batch): set on the variants / children that
   // qmle_plan_create compiles for that purpose, never on a plan handed to qmle_apply_inplace
   const bool zero_run = (p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) != 0;
-  auto cost = [&]() {
-    double c = 0;
-    for (size_t si = 0; si < p->stages.size(); ++si) {
-      const Stage &st = p->stages[si];
-      if (st.kind != ST_TILE) { c += 33.0; continue; }
-      double rd = si == 0 ? 0.0 : 1.0, wr = 1.0, tiles = 1.0;
-      if (sparse_model && st.zero_in) {
-        uint32_t outer = 0;
-        for (int i = 0; i < n - st.T; ++i) outer |= 1u << st.outer_bits[i];
-        tiles = std::ldexp(1.0, -__builtin_popcount(st.zero_in & outer));
-        if (si > 0) rd = std::ldexp(1.0, -__builtin_popcount(st.zero_in));
-        if (st.next_tile) wr = tiles;
-      }
-      // the first stage of a run from |0..0> runs its gates on one tile per state (the rest is a fill)
-      if (si == 0 && zero_run && !sparse_model) tiles = std::ldexp(1.0, st.T - n);
-      const bool last = si + 1 == p->stages.size();
-      if (st.fast_ok) {
-        // Fast kernel (k_tile2), round-3 model, fitted to per-pass HIP-event times of 1- and 4-layer
-        // circuits at n = 24 with and without their gate groups (profiles/r03_pass_model.txt): a pass
-        // takes the LONGER of its memory time and its compute time plus a sixth of the shorter one.
-        //   memory: 19.5 us write-only, 21 read-only, 50 read+write (5.4 TB/s: the mix costs);
-        //   a read+write pass whose every load / store instruction spans positions 6 and 13 (byte
-        //   address bits 9 and 16) and no other position below 8 -- a wave's 8 rows of 128 B are
-        //   the tile's three lowest high positions -- runs 15 % faster (51.3 -> 43.3 us, K2 pass
-        //   2; 54 -> 45 in the bare pass for every tile {6, 13, x >= 8, ...} and for no other pair
-        //   tried); every pair of high positions 8 apart costs ~4.5 us (54 -> 71 for {12-15,
-        //   20-23}).  The HBM channel hash behind both is not documented: modelled as measured.
-        //   compute: 5 + 9.5 per register-tile group, + 10 for the <Z> sums of a measuring pass.
-        double rw = (si == 0 ? 0.0 : 21.0 * rd) + (last ? 0.0 : 19.5 * wr);
-        if (si > 0 && !last) {
-          rw += 9.5 * (rd < wr ? rd : wr);
-          double shape = 0.0;
-          if (st.L == 4 && st.T >= 12) {
-            const int h0 = st.tile_bits[4], h1 = st.tile_bits[5], h2 = st.tile_bits[6];
-            if (h0 == 6 && h1 >= 8 && (h1 == 13 || h2 == 13)) shape -= 7.5;
-          }
-          uint32_t hi = 0;
-          for (int j = st.L; j < st.T; ++j) hi |= 1u << st.tile_bits[j];
-          shape += 4.5 * __builtin_popcount(hi & (hi >> 8));
-          rw += shape * (rd < wr ? rd : wr);
-        }
-        const double cmp = (5.0 + 9.5 * (st.fast_end - st.fast_begin) + (last ? 10.0 : 0.0)) * tiles;
-        c += 1.5 + 0.8 * std::ldexp(1.0, 24 - n) + (rw > cmp ? rw + cmp / 6.0 : cmp + rw / 6.0);
-        continue;
-      }
-      const double mem = rd + (last ? 0.0 : wr);
-      c += 2.0 + 0.8 * std::ldexp(1.0, 24 - n) + 6.0 * mem +
-           25.0 * (st.grp_end - st.grp_begin) * tiles;
+  double c = 0;
+  for (size_t si = 0; si < p->stages.size(); ++si) {
+    const Stage &st = p->stages[si];
+    if (st.kind != ST_TILE) { c += 33.0; continue; }
+    double rd = si == 0 ? 0.0 : 1.0, wr = 1.0, tiles = 1.0;
+    if (sparse_model && st.zero_in) {
+      tiles = std::ldexp(1.0, -__builtin_popcount(st.zero_in & outer_mask(st, n)));
+      if (si > 0) rd = std::ldexp(1.0, -__builtin_popcount(st.zero_in));
+      if (st.next_tile) wr = tiles;
     }
-    // a schedule that ends in a streaming pass leaves the measurement to a pass of its own (one
-    // more read of the state), where a tile pass measures on the fly
-    if (!p->stages.empty() && p->stages.back().kind != ST_TILE) c += 21.0;
-    return c;
-  };
-  if (p->whole_state_lds || forced_T != 0 || forced_L != 0 || no_fusion_flag) {
-    schedule(forced_T ? forced_T : kDefaultTileBits, forced_L ? forced_L : kDefaultLowBits);
-  } else {
-    static const int cand[][2] = {{13, 7}, {13, 5}, {12, 4}, {13, 4}, {12, 5}, {13, 6}};
-    // k = geometry (6) x [eager, lazy CX] (2) x variant (4): 0 plain, 1 wide first stage, 2 position 6
-    // carried + wide first stage, 3 position 6 carried.  Ties keep the lower index (round-2 schedules).
-    int best = 0;
-    double best_cost = 1e300;
-    // (round 5) variant 4, k in [48, 60): first tile of 2^14 amplitudes on the TOP positions (all-live runs from
-    // |0..0>).  Such a schedule trades an HBM pass for arithmetic in the passes that are left: fewer bytes, less time, a
-    // lower fraction of the HBM roofline.  QMLE_NO_TOP_FIRST=1: the round-4 candidates only.
-    const bool no_top = std::getenv("QMLE_NO_TOP_FIRST") != nullptr;  // (read per compile: bench.py's k2_three_pass leg)
-    auto run_cand = [&](int k) {
-      const int g = k % 6, lazy = (k / 6) % 2, v = k / 12;
-      const bool wide = v == 1 || v == 2 || v == 4, carry6 = v == 2 || v == 3;
-      schedule(cand[g][0], cand[g][1], lazy != 0, carry6 ? 6 : -1, wide ? kLdsMaxQubits : 0, v == 4);
-    };
-    auto allowed = [&](int k) {
-      const int g = k % 6, v = k / 12;
-      if (cand[g][0] >= n) return false;
-      // (known-zero runs keep the round-2 schedules: their first passes are launch-bound special
-      // kernels tuned for the (12, 4) geometry, and the wide first tile cost them 4-8 % at n = 24)
-      if (v >= 1 && sparse_model) return false;
-      if ((v == 1 || v == 2) && !zero_run) return false;
-      if ((v == 2 || v == 3) && (cand[g][1] != 4 || n < 16)) return false;
-      if (v == 4 && (!zero_run || no_top || n < 16 || n > 28)) return false;
-      return true;
-    };
-    p->cand_ranking.clear();
-    for (int k = 0; k < 60; ++k) {
-      if (!allowed(k)) continue;
-      run_cand(k);
-      if (k >= 48 && (p->stages.empty() || p->stages[0].shift == 0)) continue;  // (no top-first stage came of it)
-      const double c = cost();
-      p->cand_ranking.push_back({c, k});
-      // (the round-3 variants must win by 2 %: the model knows their effect from two circuits; a top-first schedule
-      // by 5 % -- it wins by dropping a whole pass or not at all: K2 headline 58.2 against 92.5 predicted, 60.5 against
-      // 88.5 ms measured)
-      const double margin = k >= 48 ? (best < 48 ? 0.95 : 1.0) : (k >= 12 && best < 12 ? 0.98 : 1.0);
-      if (c < best_cost * margin - 1e-9) { best_cost = c; best = k; }
+    // the first stage of a run from |0..0> runs its gates on one tile per state (the rest is a fill)
+    if (si == 0 && zero_run && !sparse_model) tiles = std::ldexp(1.0, st.T - n);
+    const bool last = si + 1 == p->stages.size();
+    if (st.fast_ok) {
+      c += fast_pass_cost(p, st, si == 0, last, rd, wr, tiles);
+      continue;
     }
-    // (tuning only: force one of the candidates to measure it against the model's choice)
-    std::sort(p->cand_ranking.begin(), p->cand_ranking.end());
-    const int force = p->force_candidate >= 0 ? p->force_candidate
-                      : std::getenv("QMLE_FORCE_CAND") ? atoi(std::getenv("QMLE_FORCE_CAND")) : -1;  // (read per compile: tools/cand_sweep.py)
-    if (force >= 0 && force < 60 && (force < 48 || allowed(force)) && cand[force % 6][0] < n && (force < 12 || zero_run)) best = force;
-    run_cand(best);
-    p->chosen_candidate = best;
+    const double mem = rd + (last ? 0.0 : wr);
+    c += 2.0 + 0.8 * std::ldexp(1.0, 24 - n) + 6.0 * mem +
+         25.0 * (st.grp_end - st.grp_begin) * tiles;
   }
-  p->model_cost = cost();
-  {
-    FastOpForms forms;
-    assign_unit_forms(p, forms);
-    assign_product_forms(p, forms);
+  // a schedule that ends in a streaming pass leaves the measurement to a pass of its own (one
+  // more read of the state), where a tile pass measures on the fly
+  if (!p->stages.empty() && p->stages.back().kind != ST_TILE) c += 21.0;
+  return c;
+}
+
+// May the search (or QMLE_FORCE_CAND, for a top-first candidate) take candidate `c`?
+static bool candidate_allowed(const qmle_plan *p, const ScheduleCandidate &c, bool no_top) {
+  const int n = p->n, v = c.variant;
+  const bool sparse_model = !(p->flags & QMLE_PLAN_NO_SPARSE), zero_run = (p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) != 0;
+  if (c.T >= n) return false;
+  // (known-zero runs keep the round-2 schedules: their first passes are launch-bound special
+  // kernels tuned for the (12, 4) geometry, and the wide first tile cost them 4-8 % at n = 24)
+  if (v != SV_PLAIN && sparse_model) return false;
+  if ((v == SV_WIDE_FIRST || v == SV_CARRY_WIDE_FIRST) && !zero_run) return false;
+  if (c.carry >= 0 && (c.L != 4 || n < 16)) return false;
+  if (v == SV_TOP_FIRST && (!zero_run || no_top || n < 16 || n > 28)) return false;
+  return true;
+}
+
+// The schedule of the plan: the forced geometry, or the cheapest candidate of the pass-cost model (p->cand_ranking:
+// every candidate with its cost), or the candidate the tuning switches force.
+static void choose_schedule(qmle_plan *p) {
+  const int n = p->n;
+  const int forced_T = (int)((p->flags >> 8) & 0xff), forced_L = (int)((p->flags >> 16) & 0xff);
+  const int pad_high = p->pad_high >= 0 ? p->pad_high
+                       : std::getenv("QMLE_PAD_HIGH") ? atoi(std::getenv("QMLE_PAD_HIGH")) : 0;
+  if (p->whole_state_lds || forced_T != 0 || forced_L != 0 || (p->flags & QMLE_PLAN_NO_FUSION)) {
+    schedule_stages(p, {forced_T ? forced_T : kDefaultTileBits, forced_L ? forced_L : kDefaultLowBits, false, -1, 0,
+                        false, SV_PLAIN}, pad_high);
+    return;
   }
-  // ---- matrices no forward kernel reads --------------------------------------------------------
-  // An X / CX inside a register-tile group is a swap of amplitudes (reg_dispatch<2>, f_x / f_cx) or a
-  // change of the LDS layout map (build_fast_groups); its 2x2 matrix is never read by a tile pass.  The
-  // per-sample matrix builder spent 46 % of its groups on them in the Fourier-grid model (60 CX of 130
-  // groups, a fifth of a saturated 10-qubit batch with the rest of the builder).  The
-  // build groups are ordered needed-first; the forward engine builds [0, n_groups_needed), the adjoint
-  // sweep and the complex128 engine (which apply a CX through its matrix) all of them.
-  {
-    std::vector<char> unread(p->mat_floats + 1, 0);
-    for (const Stage &st : p->stages) {
-      if (st.kind != ST_TILE || st.T < 4 || (p->flags & QMLE_PLAN_NO_REGTILE)) continue;  // (group_stage_ops: regs_ok)
-      for (int i = st.op_begin; i < st.op_end; ++i) {
-        const LoweredOp &o = p->dev_ops[i];
-        if (o.kind == LK_1Q && o.nc <= 1 && (o.flags & LF_PERMX)) unread[o.mat_off] = 1;
-      }
-    }
-    std::stable_partition(p->groups.begin(), p->groups.end(),
-                          [&](const BuildGroup &g) { return !(g.dim == 2 && unread[g.mat_off]); });
-    p->n_groups_needed = 0;
-    p->n_product_groups = 0;
-    for (const BuildGroup &g : p->groups) {
-      if (!(g.dim == 2 && unread[g.mat_off])) ++p->n_groups_needed;
-      if (g.dim == kBuildProduct) ++p->n_product_groups;  // (appended last, and needed: they close the needed range)
+  // QMLE_NO_TOP_FIRST=1: the round-4 candidates only.
+  const bool no_top = std::getenv("QMLE_NO_TOP_FIRST") != nullptr;  // (read per compile: bench.py's k2_three_pass leg)
+  const bool zero_run = (p->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) != 0;
+  int best = 0;
+  double best_cost = 1e300;
+  p->cand_ranking.clear();
+  for (int k = 0; k < kNumCandidates; ++k) {
+    const ScheduleCandidate c = candidate_of(k);
+    if (!candidate_allowed(p, c, no_top)) continue;
+    schedule_stages(p, c, pad_high);
+    if (c.top_first && (p->stages.empty() || p->stages[0].shift == 0)) continue;  // (no top-first stage came of it)
+    const double cost = schedule_cost(p);
+    p->cand_ranking.push_back({cost, k});
+    // (the round-3 variants must win by 2 %: the model knows their effect from two circuits; a top-first schedule
+    // by 5 % -- it wins by dropping a whole pass or not at all: K2 headline 58.2 against 92.5 predicted, 60.5 against
+    // 88.5 ms measured)
+    const int vb = variant_of(best);
+    const double margin = c.variant == SV_TOP_FIRST ? (vb != SV_TOP_FIRST ? 0.95 : 1.0)
+                                                    : (c.variant != SV_PLAIN && vb == SV_PLAIN ? 0.98 : 1.0);
+    if (cost < best_cost * margin - 1e-9) { best_cost = cost; best = k; }
+  }
+  std::sort(p->cand_ranking.begin(), p->cand_ranking.end());
+  // (tuning only: force one of the candidates to measure it against the model's choice)
+  const int force = p->force_candidate >= 0 ? p->force_candidate
+                    : std::getenv("QMLE_FORCE_CAND") ? atoi(std::getenv("QMLE_FORCE_CAND")) : -1;  // (read per compile: tools/cand_sweep.py)
+  if (force >= 0 && force < kNumCandidates) {
+    const ScheduleCandidate c = candidate_of(force);
+    if ((c.variant != SV_TOP_FIRST || candidate_allowed(p, c, no_top)) && c.T < n && (c.variant == SV_PLAIN || zero_run))
+      best = force;
+  }
+  schedule_stages(p, candidate_of(best), pad_high);
+  p->chosen_candidate = best;
+}
+
+// ---- matrices no forward kernel reads --------------------------------------------------------
+// An X / CX inside a register-tile group is a swap of amplitudes (reg_dispatch<2>, f_x / f_cx) or a
+// change of the LDS layout map (build_fast_groups); its 2x2 matrix is never read by a tile pass.  The
+// per-sample matrix builder spent 46 % of its groups on them in the Fourier-grid model (60 CX of 130
+// groups, a fifth of a saturated 10-qubit batch with the rest of the builder).  The
+// build groups are ordered needed-first; the forward engine builds [0, n_groups_needed), the adjoint
+// sweep and the complex128 engine (which apply a CX through its matrix) all of them.
+static void order_build_groups(qmle_plan *p) {
+  std::vector<char> unread(p->mat_floats + 1, 0);
+  for (const Stage &st : p->stages) {
+    if (st.kind != ST_TILE || st.T < 4 || (p->flags & QMLE_PLAN_NO_REGTILE)) continue;  // (group_stage_ops: regs_ok)
+    for (int i = st.op_begin; i < st.op_end; ++i) {
+      const LoweredOp &o = p->dev_ops[i];
+      if (o.kind == LK_1Q && o.nc <= 1 && (o.flags & LF_PERMX)) unread[o.mat_off] = 1;
     }
   }
+  auto needed = [&](const BuildGroup &g) { return !(g.dim == 2 && unread[g.mat_off]); };
+  std::stable_partition(p->groups.begin(), p->groups.end(), needed);
+  p->n_groups_needed = 0;
+  p->n_product_groups = 0;
+  for (const BuildGroup &g : p->groups) {
+    if (needed(g)) ++p->n_groups_needed;
+    if (g.dim == kBuildProduct) ++p->n_product_groups;  // (appended last, and needed: they close the needed range)
+  }
+}
+
+int compile_plan(qmle_plan *p) {
+  const int n = p->n;
+  if (n < 1 || n > QMLE_MAX_QUBITS) return QMLE_ERR_INVALID_ARG;
+  const int rc = validate_tape(p);
+  if (rc != QMLE_OK) return rc;
+  lower_tape(p);
+  reorder_low_bits_first(p);
+  // ---- 2. choose regime ------------------------------------------------------
+  const int forced_T = (int)((p->flags >> 8) & 0xff);
+  p->whole_state_lds = (n <= kLdsMaxQubits) && !(p->flags & QMLE_PLAN_FORCE_GLOBAL) &&
+                       (forced_T == 0 || forced_T >= n);
+  if (!p->whole_state_lds && forced_T != 0 && forced_T < 4 && forced_T < n)
+    return QMLE_ERR_INVALID_ARG;
+  choose_schedule(p);
+  p->model_cost = schedule_cost(p);
+  FastOpForms forms;
+  assign_unit_forms(p, forms);
+  assign_product_forms(p, forms);
+  order_build_groups(p);
   return QMLE_OK;
 }
 
@@ -1610,9 +1772,7 @@ static double stage_write_bytes(const qmle_plan *p, size_t si) {
   // (the plan's last batch run left out fills of zeros that were in memory already: what it wrote)
   if (si == 0 && p->last_run.stage0_written) return (double)p->last_run.stage0_written;
   if (!sparse || !st.next_tile) return 8.0 * D;
-  uint32_t outer = 0;
-  for (int i = 0; i < p->n - st.T; ++i) outer |= 1u << st.outer_bits[i];
-  return 8.0 * std::ldexp(1.0, p->n - __builtin_popcount(st.zero_in & outer));
+  return 8.0 * std::ldexp(1.0, p->n - __builtin_popcount(st.zero_in & outer_mask(st, p->n)));
 }
 
 bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
@@ -1622,11 +1782,8 @@ bool qualifies_for_register_measure(const qmle_plan *p, size_t si) {
 }
 
 void stage_known_zeros(const qmle_plan *p, const Stage &st, uint32_t *local, uint32_t *outer) {
-  *local = *outer = 0;
-  for (int j = 0; j < st.T; ++j)
-    if (st.zero_in & (1u << st.tile_bits[j])) *local |= 1u << j;
-  for (int i = 0; i < p->n - st.T; ++i)
-    if (st.zero_in & (1u << st.outer_bits[i])) *outer |= 1u << i;
+  *local = gather_bits(st.zero_in, st.tile_bits, st.T);
+  *outer = gather_bits(st.zero_in, st.outer_bits, p->n - st.T);
 }
 
 // (known zeros inside the tile: the walk zero-fills and loads selectively)
@@ -1728,6 +1885,78 @@ static double stage_flops_per_state(const qmle_plan *p, const Stage &st, bool li
   return f;
 }
 
+// The measuring walk of stage `s` in describe_plan's words.
+static void describe_measuring(std::ostringstream &os, const qmle_plan *p, size_t s) {
+  const Stage &st = p->stages[s];
+  // <Z> from the last group's registers (k_tile2's multi-tile measuring walk): whether the stage QUALIFIES
+  // (qualifies_for_register_measure: last of several, k_tile2 records, no known-zero tiles; what a run really did
+  // is in the _last_run fields below), the records, and what they were derived from
+  const bool from_regs = qualifies_for_register_measure(p, s);
+  os << ",\"register_measure_qualifies\":" << (from_regs ? "true" : "false");
+  // the measuring walk's barriers (Stage::fast_info): which load map it stages with, whether a barrier stays between
+  // the last group and the next tile's staging, and whether none is left in the tile loop
+  if (st.fast_ok)
+    os << ",\"load_map\":\"" << (st.slab_load ? "slab" : "rows") << "\",\"sync_tile_end\":"
+       << (st.sync_tile_end ? "true" : "false") << ",\"wave_private_walk\":" << (st.wave_private ? "true" : "false");
+  // how the walk stages a tile (Stage::dma_tables) and, for the DMA form, its source map: the byte offset of work
+  // item t's pair inside the tile (the table, and the runs the kernel takes instead when there are at most four,
+  // applied to sw(2 lane | wave << 10)), XOR the delta of piece u & 3, plus the offset of u's three bits
+  if (st.fast_ok) {
+    const bool dma = stages_by_dma(p, s);
+    os << ",\"staging\":\"" << (dma ? "dma" : "registers") << "\"";
+    if (dma) {
+      os << ",\"dma_deltas\":[" << st.dma_delta[0] << "," << st.dma_delta[1] << "," << st.dma_delta[2] << ","
+         << st.dma_delta[3] << "],\"dma_lane_offsets\":[";
+      for (uint32_t t = 0; t < (1u << (st.T - 4)); ++t) os << (t ? "," : "") << p->tbl2[st.fast_gtab_dma + t];
+      uint32_t off[4], mask[4], pos[4];
+      const int nr = stage_lane_runs(st, st.T - 1, off, mask, pos);
+      os << "],\"dma_lane_runs\":";
+      if (nr < 0) os << "null";
+      else {
+        os << "[";
+        for (int r = 0; r < nr; ++r) os << (r ? "," : "") << "[" << off[r] << "," << mask[r] << "," << pos[r] << "]";
+        os << "]";
+      }
+    }
+  }
+  // the last group through lane swaps (Stage::lane_swap_last; like the DMA form it rides on, a run also needs an input
+  // without known zeros inside the tile): the records of the frame behind the swaps, the positions of its in-thread
+  // bits and of its thread bits; the X / CX behind it: `measure_between` (between the last two groups), then
+  // `measure_after`
+  const bool lane_swap = walk_by_lane_swap(st, stages_by_dma(p, s));
+  os << ",\"last_group_lane_swap\":" << (lane_swap ? "true" : "false");
+  if (lane_swap) {
+    os << ",\"lane_swap_crossed\":" << (st.lane_swap_cross ? "true" : "false") << ",\"measure_records_swap\":[";
+    for (int j = 0; j < st.T; ++j) {
+      const ZregRecord r = zreg_record(st.zreg_swap[j]);
+      os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
+    }
+    os << "],\"measure_swap_bits\":[";
+    for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_swap_bits[i];
+    os << "],\"measure_swap_thread_bits\":[";
+    for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_swap_thread_bits[t];
+    os << "],\"measure_between\":[";
+    for (size_t i = 0; i + 1 < st.zreg_between.size(); i += 2)
+      os << (i ? "," : "") << "[" << (int)st.zreg_between[i] << "," << (int)st.zreg_between[i + 1] << "]";
+    os << "]";
+  }
+  if (from_regs) {
+    os << ",\"measure_records\":[";
+    for (int j = 0; j < st.T; ++j) {
+      const ZregRecord r = zreg_record(st.zreg[j]);
+      os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
+    }
+    os << "],\"measure_group_bits\":[";
+    for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_bits[i];
+    os << "],\"measure_thread_bits\":[";
+    for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_thread_bits[t];
+    os << "],\"measure_after\":[";
+    for (size_t i = 0; i + 1 < st.zreg_after.size(); i += 2)
+      os << (i ? "," : "") << "[" << (int)st.zreg_after[i] << "," << (int)st.zreg_after[i + 1] << "]";
+    os << "]";
+  }
+}
+
 std::string describe_plan(const qmle_plan *p) {
   std::ostringstream os;
   os << "{\"n_qubits\":" << p->n << ",\"n_ops\":" << p->ops.size()
@@ -1782,73 +2011,8 @@ std::string describe_plan(const qmle_plan *p) {
       for (int j = 0; j < st.T; ++j) os << (j ? "," : "") << fi.cols[j];
       os << "],\"layout_const\":" << fi.cnst << "}";
     }
-    // <Z> from the last group's registers (k_tile2's multi-tile measuring walk): whether the stage QUALIFIES
-    // (qualifies_for_register_measure: last of several, k_tile2 records, no known-zero tiles; what a run really did
-    // is in the _last_run fields below), the records, and what they were derived from
-    const bool from_regs = qualifies_for_register_measure(p, s);
-    os << "],\"register_measure_qualifies\":" << (from_regs ? "true" : "false");
-    // the measuring walk's barriers (Stage::fast_info): which load map it stages with, whether a barrier stays between
-    // the last group and the next tile's staging, and whether none is left in the tile loop
-    if (st.fast_ok)
-      os << ",\"load_map\":\"" << (st.slab_load ? "slab" : "rows") << "\",\"sync_tile_end\":"
-         << (st.sync_tile_end ? "true" : "false") << ",\"wave_private_walk\":" << (st.wave_private ? "true" : "false");
-    // how the walk stages a tile (Stage::dma_tables) and, for the DMA form, its source map: the byte offset of work
-    // item t's pair inside the tile (the table, and the runs the kernel takes instead when there are at most four,
-    // applied to sw(2 lane | wave << 10)), XOR the delta of piece u & 3, plus the offset of u's three bits
-    if (st.fast_ok) {
-      const bool dma = stages_by_dma(p, s);
-      os << ",\"staging\":\"" << (dma ? "dma" : "registers") << "\"";
-      if (dma) {
-        os << ",\"dma_deltas\":[" << st.dma_delta[0] << "," << st.dma_delta[1] << "," << st.dma_delta[2] << ","
-           << st.dma_delta[3] << "],\"dma_lane_offsets\":[";
-        for (uint32_t t = 0; t < (1u << (st.T - 4)); ++t) os << (t ? "," : "") << p->tbl2[st.fast_gtab_dma + t];
-        uint32_t off[4], mask[4], pos[4];
-        const int nr = stage_lane_runs(st, st.T - 1, off, mask, pos);
-        os << "],\"dma_lane_runs\":";
-        if (nr < 0) os << "null";
-        else {
-          os << "[";
-          for (int r = 0; r < nr; ++r) os << (r ? "," : "") << "[" << off[r] << "," << mask[r] << "," << pos[r] << "]";
-          os << "]";
-        }
-      }
-    }
-    // the last group through lane swaps (Stage::lane_swap_last; like the DMA form it rides on, a run also needs an input
-    // without known zeros inside the tile): the records of the frame behind the swaps, the positions of its in-thread
-    // bits and of its thread bits; the X / CX behind it: `measure_between` (between the last two groups), then
-    // `measure_after`
-    const bool lane_swap = walk_by_lane_swap(st, stages_by_dma(p, s));
-    os << ",\"last_group_lane_swap\":" << (lane_swap ? "true" : "false");
-    if (lane_swap) {
-      os << ",\"lane_swap_crossed\":" << (st.lane_swap_cross ? "true" : "false") << ",\"measure_records_swap\":[";
-      for (int j = 0; j < st.T; ++j) {
-        const ZregRecord r = zreg_record(st.zreg_swap[j]);
-        os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
-      }
-      os << "],\"measure_swap_bits\":[";
-      for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_swap_bits[i];
-      os << "],\"measure_swap_thread_bits\":[";
-      for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_swap_thread_bits[t];
-      os << "],\"measure_between\":[";
-      for (size_t i = 0; i + 1 < st.zreg_between.size(); i += 2)
-        os << (i ? "," : "") << "[" << (int)st.zreg_between[i] << "," << (int)st.zreg_between[i + 1] << "]";
-      os << "]";
-    }
-    if (from_regs) {
-      os << ",\"measure_records\":[";
-      for (int j = 0; j < st.T; ++j) {
-        const ZregRecord r = zreg_record(st.zreg[j]);
-        os << (j ? "," : "") << "[" << r.wht << "," << r.lane << "," << r.wave << "," << r.neg << "]";
-      }
-      os << "],\"measure_group_bits\":[";
-      for (int i = 0; i < 4; ++i) os << (i ? "," : "") << (int)st.zreg_bits[i];
-      os << "],\"measure_thread_bits\":[";
-      for (int t = 0; t < st.T - 4; ++t) os << (t ? "," : "") << (int)st.zreg_thread_bits[t];
-      os << "],\"measure_after\":[";
-      for (size_t i = 0; i + 1 < st.zreg_after.size(); i += 2)
-        os << (i ? "," : "") << "[" << (int)st.zreg_after[i] << "," << (int)st.zreg_after[i + 1] << "]";
-      os << "]";
-    }
+    os << "]";
+    describe_measuring(os, p, s);
     if (st.kind == ST_TILE) {
       // ops of the stage's fast stream (concatenated fast_groups) that run in unit-pivot form, and the carriers that
       // take their chains' pivots (assign_unit_forms); fast_ops: each op's dispatch code and matrix-row offset
