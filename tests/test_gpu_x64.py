@@ -30,9 +30,10 @@ def _plan_and_angles(tape, n):
 @pytest.mark.parametrize("n", [1, 2, 3, 5, 8, 11, 13, 14, 16])
 def test_random_circuits_state_probs_expval_vs_complex128_oracle(n):
     """Every gate kind of the random tape generator; LDS regime (n <= 13) and the streaming
-    regime (14, 16)."""
+    regime (14, 16).  The generator emits no explicit matrix and no Golomb diagonal: MAT1, MAT2, MAT4 and
+    DIAG_ALL, batches of more than one row and every wire order are covered by tests/test_gpu_x64_routes.py."""
     rng = np.random.default_rng(640 + n)
-    tape = [g for g in random_tape(n, 40 if n > 1 else 10, rng) if g[0] not in ("MAT1", "MAT2")]
+    tape = random_tape(n, 40 if n > 1 else 10, rng)
     want = OE.simulate_pure(tape, n, np.complex128)
     plan, ang = _plan_and_angles(tape, n)
     got = plan.run64(ang, "state").cpu().numpy()[0]
