@@ -100,7 +100,10 @@ typedef enum qmle_opcode {
   QMLE_OP_MAT4 = 27,   /* dense 16x16 on 4 wires, batch-constant; mat_off -> 512 floats.
                           Superoperator of a 2-qubit Kraus channel on vec(rho)
                           (KrausChannel.apply_to_density, operations.py:1551-1578)   */
-  QMLE_OP__COUNT = 28
+  QMLE_OP_MAT1_ROW = 28, /* Operation(matrix=[B,2,2]): one 2x2 per sample.  Its 8 numbers (row-major, re then im)
+                            are the angle-table columns slot[0] .. slot[0] + 7; no reduction mod 4 pi */
+  QMLE_OP_MAT2_ROW = 29, /* Operation(matrix=[B,4,4]): the same with 32 columns from slot[0] on */
+  QMLE_OP__COUNT = 30
 } qmle_opcode;
 
 /* One tape entry.  Barriers (operations.py:964) are not sent: simulate_pure skips
@@ -108,7 +111,8 @@ typedef enum qmle_opcode {
 typedef struct qmle_op {
   uint16_t opcode;  /* qmle_opcode */
   int16_t wire[4];  /* reference wire order; unused = -1 */
-  int32_t slot[3];  /* column of the angle table per parameter; unused = -1 */
+  int32_t slot[3];  /* column of the angle table per parameter; unused = -1 (MAT1_ROW / MAT2_ROW: slot[0] = first
+                       of 8 / 32 consecutive columns) */
   int32_t mat_off;  /* float offset into `consts` for MAT1/MAT2/DIAG_ALL, else -1 */
 } qmle_op;
 
@@ -591,6 +595,32 @@ int qmle_gram_f64(const void *d_a, const void *d_b, int n_qubits, int n_groups, 
                   int64_t group_stride_a, int64_t group_stride_b, void *d_out, void *d_ws, size_t ws_bytes,
                   qmle_stream stream);
 size_t qmle_gram_workspace_bytes_f64(int n_qubits, int n_groups, int rows_a, int rows_b);
+
+/* ---- Hamiltonian time evolution (Hermitian.evolve / ParametrizedHamiltonian.evolve) ----------
+ * U[r] = the solution at the end of the grid of  dU/dt = -i sum_i f_i(t) H_i U,  U = I at the start, for `rows`
+ * independent rows and dim = 2 or 4, on the fixed grid of the reference's commutator-free Magnus integrators
+ * (qml_essentials/evolution.py:204-231) with step d_h[r]:
+ *   order 2: U <- exp(h A(t_n + h/2)) U, one node per step;
+ *   order 4: U <- exp(h (a2 A1 + a1 A2)) exp(h (a1 A1 + a2 A2)) U with A_k = A(t_n + c_k h), c_1,2 = 1/2 -+ sqrt(3)/6,
+ *            a_1,2 = 1/4 +- sqrt(3)/6, two nodes per step (c_1 first);
+ *   A(t) = -i sum_i c_i(t) H_i.
+ * h_terms (HOST): n_terms (1..16) matrices, complex128 row-major; they are taken as Hermitian -- the real diagonal
+ * and the entries above it are read.  d_coef: float64 [rows][n_steps * nodes per step][n_terms], the coefficient
+ * functions at the node times in node order: the library evaluates no coefficient function, and where a row's grid
+ * starts matters to the caller's table alone.  d_h: float64 [rows].  d_out [rows][dim * dim], row-major, complex128
+ * (out_f64 = 1) or complex64 (0); the arithmetic is float64 either way.
+ * lanes_per_row in {1, 4, 16, 64}: a row's steps are cut into that many contiguous runs, one per lane of a wave; the
+ * partial products are multiplied in time order through lane shifts.  The result depends on the split through
+ * rounding only.  0: the library chooses (what the second function returns: 1 when the rows alone fill the card,
+ * else the widest split that fills it and leaves no lane without a step).
+ * The 4x4 exponentials are Taylor series applied to the columns of U, the exponent cut into ceil(norm / 0.5) parts;
+ * a row whose h * |sum_i c_i H_i| (largest absolute row sum) exceeds 2^15 or is not finite comes back as NaN.
+ * QMLE_ERR_UNSUPPORTED for dim outside {2, 4} or order outside {2, 4}; QMLE_ERR_INVALID_ARG for NULL pointers,
+ * n_terms outside 1..16, rows < 1, n_steps < 1, another lanes_per_row, out_f64 outside {0, 1} or rows * lanes
+ * beyond 2^31 -- all before any device work. */
+int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double *d_coef, const double *d_h, int rows,
+                       int order, int n_steps, int lanes_per_row, int out_f64, void *d_out, qmle_stream stream);
+int qmle_evolve_lanes(int rows, int n_steps);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ OPCODES = {
     "CPhase": 16, "ControlledPhaseShift": 16, "SWAP": 17,
     "RXX": 18, "RYY": 19, "RZZ": 20, "RZX": 21, "CCX": 22, "CSWAP": 23,
     "MAT1": 24, "MAT2": 25, "DIAG_ALL": 26, "MAT4": 27,
+    "MAT1_ROW": 28, "MAT2_ROW": 29,  # one matrix per sample: its entries are 8 / 32 consecutive angle-table columns
 }
 MEAS = {"state": 0, "probs": 1, "expval": 2, "density": 3, "mw": 4}
 
@@ -226,6 +227,8 @@ SYMBOLS = [
     ("qmle_gram_workspace_bytes", _SZ, [_I, _I, _I, _I]),
     ("qmle_gram_f64", _I, [_VP, _VP, _I, _I, _I, _I, C.c_int64, C.c_int64, _VP, _VP, _SZ, _VP]),
     ("qmle_gram_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
+    ("qmle_evolve_magnus", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("qmle_evolve_lanes", _I, [_I, _I]),
 ]
 
 
@@ -888,6 +891,41 @@ def gram(a, b=None):
         check(fn(C.c_void_p(pa.data_ptr()), C.c_void_p(pb.data_ptr()), n, gc, Ra, Rb, Ra * D, Rb * D,
                  C.c_void_p(out[g0:g0 + gc].data_ptr()), C.c_void_p(ws.data_ptr()), wsb, _stream_ptr()),
               "qmle_gram_f64" if f64 else "qmle_gram")
+    return out
+
+
+EVOLVE_MAX_TERMS = 16  # qmle_evolve_magnus: the Hermitian terms travel as kernel arguments
+
+
+def evolve_magnus(h_terms, coef, h, order: int, lanes_per_row: int = 0, complex64: bool = False):
+    """Propagators of ``dU/dt = -i sum_i f_i(t) H_i U`` on the fixed Magnus grid (``qmle_evolve_magnus``):
+    ``h_terms`` ``[n_terms, d, d]`` Hermitian (d = 2 or 4, host), ``coef`` ``[rows, nodes, n_terms]`` float64 -- the
+    coefficient functions at the node times, ``nodes`` = steps (order 2) or 2 * steps (order 4) -- and ``h``
+    ``[rows]`` float64, both host arrays or CUDA tensors.  Returns ``[rows, d, d]`` complex128 (complex64 when
+    asked: the arithmetic is float64 either way) on the device."""
+    torch = require_gpu()
+    H = np.ascontiguousarray(h_terms, dtype=np.complex128)
+    if H.ndim != 3 or H.shape[1] != H.shape[2]:
+        raise ValueError(f"evolve_magnus: terms must be [n_terms, d, d], got {H.shape}")
+    dev = current_device()
+
+    def on_device(x):
+        if not hasattr(x, "is_cuda"):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
+        return x.to(device=dev, dtype=torch.float64).contiguous()
+
+    coef, h = on_device(coef), on_device(h)
+    n_terms, d = int(H.shape[0]), int(H.shape[1])
+    per_step = 2 if order == 4 else 1
+    if coef.dim() != 3 or coef.shape[2] != n_terms or coef.shape[1] % per_step or h.shape != (coef.shape[0],):
+        raise ValueError(f"evolve_magnus: coef {tuple(coef.shape)} / h {tuple(h.shape)} do not fit {n_terms} term(s) "
+                         f"of order {order}")
+    rows, n_steps = int(coef.shape[0]), int(coef.shape[1]) // per_step
+    out = torch.empty((rows, d, d), dtype=torch.complex64 if complex64 else torch.complex128, device=dev)
+    check(lib().qmle_evolve_magnus(C.c_void_p(H.ctypes.data), n_terms, d, C.c_void_p(coef.data_ptr()),
+                                   C.c_void_p(h.data_ptr()), rows, int(order), n_steps, int(lanes_per_row),
+                                   0 if complex64 else 1, C.c_void_p(out.data_ptr()), _stream_ptr()),
+          "qmle_evolve_magnus")
     return out
 
 

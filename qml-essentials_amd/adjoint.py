@@ -67,6 +67,9 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
     rotations so that every primitive has at most one angle."""
     prims = []  # forward order: (name, wires, fwd_slot | None, blob)
     for (name, wires, slots, _off), blob in zip(low.ops, blobs):
+        if name in ("MAT1_ROW", "MAT2_ROW"):
+            raise AdjointUnsupported(f"no adjoint rule for {name}: a per-sample matrix (an evolved unitary) has no "
+                                     "generator the sweep could differentiate or invert by negating an angle")
         if name == "Rot":
             prims += [("RZ", wires, slots[0], None), ("RY", wires, slots[1], None),
                       ("RZ", wires, slots[2], None)]

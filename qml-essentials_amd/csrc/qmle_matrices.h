@@ -163,6 +163,13 @@ __host__ __device__ inline void product_form_group(const M2 *m, const int *bit, 
 template <class ANG, class CT>
 __device__ __forceinline__ M2 source_2x2(const BuildOp &b, ANG ang, const CT *__restrict__ consts) {
   const cd z = {0.0, 0.0}, one = {1.0, 0.0};
+  // (ahead of the switch, not an arm of it: with this source as one more arm, hipcc 7 built CRX / CRZ / CPhase
+  // matrices that were wrong by 0.6 in the state -- tests/test_gpu_evolution.py keeps a circuit with all of them)
+  if (b.opcode == QMLE_OP_MAT1_ROW) {  // the sample's own 2x2: 8 consecutive columns of its table row
+    const int s0 = b.slot[0];
+    return {{(double)ang[s0 + 0], (double)ang[s0 + 1]}, {(double)ang[s0 + 2], (double)ang[s0 + 3]},
+            {(double)ang[s0 + 4], (double)ang[s0 + 5]}, {(double)ang[s0 + 6], (double)ang[s0 + 7]}};
+  }
   double th = 0.0, c = 1.0, s = 0.0;
   if (b.slot[0] >= 0) {
     th = (double)ang[b.slot[0]];
@@ -205,6 +212,10 @@ __device__ void source_matrix(const BuildOp &b, ANG ang,
                               const CT *__restrict__ consts, cd *M, int dim) {
   const int nn = dim * dim;
   for (int i = 0; i < nn; ++i) M[i] = {0.0, 0.0};
+  if (b.opcode == QMLE_OP_MAT1_ROW || b.opcode == QMLE_OP_MAT2_ROW) {  // the sample's own matrix
+    for (int i = 0; i < nn; ++i) M[i] = {(double)ang[b.slot[0] + 2 * i], (double)ang[b.slot[0] + 2 * i + 1]};
+    return;
+  }
   double th = 0.0, c = 1.0, s = 0.0;
   if (b.slot[0] >= 0) {
     th = (double)ang[b.slot[0]];

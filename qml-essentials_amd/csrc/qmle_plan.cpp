@@ -47,6 +47,10 @@ bool op_info(int opcode, OpInfo *info) {
       *info = {1, 0, true}; return true;
     case QMLE_OP_MAT2:
       *info = {2, 0, true}; return true;
+    case QMLE_OP_MAT1_ROW:  // (slot[0]: the first of 8 / 32 columns -- validate_tape checks where they end)
+      *info = {1, 1, false}; return true;
+    case QMLE_OP_MAT2_ROW:
+      *info = {2, 1, false}; return true;
     case QMLE_OP_DIAG_ALL:
       *info = {-1, 1, true}; return true;
     case QMLE_OP_MAT4:
@@ -981,6 +985,10 @@ static int validate_tape(const qmle_plan *p) {
     }
     for (int a = 0; a < info.n_params; ++a)
       if (op.slot[a] < 0 || op.slot[a] >= p->n_slots) return QMLE_ERR_SLOT_RANGE;
+    if (op.opcode == QMLE_OP_MAT1_ROW || op.opcode == QMLE_OP_MAT2_ROW) {  // the matrix entries: consecutive columns
+      const int need = op.opcode == QMLE_OP_MAT1_ROW ? 8 : 32;
+      if ((long long)op.slot[0] + need > (long long)p->n_slots) return QMLE_ERR_SLOT_RANGE;
+    }
   }
   return QMLE_OK;
 }
@@ -1025,7 +1033,7 @@ static LoweredOp lowered_form(const qmle_op &op, int n) {
       lo.t1 = pos(op.wire[2]);
       break;
     case QMLE_OP_SWAP: case QMLE_OP_RXX: case QMLE_OP_RYY: case QMLE_OP_RZZ:
-    case QMLE_OP_RZX: case QMLE_OP_MAT2:
+    case QMLE_OP_RZX: case QMLE_OP_MAT2: case QMLE_OP_MAT2_ROW:
       lo.kind = LK_2Q; lo.nc = 0; lo.t0 = pos(op.wire[0]); lo.t1 = pos(op.wire[1]);
       break;
     default:  // uncontrolled 1-qubit

@@ -1,6 +1,6 @@
 """Entry-point namespace (``import qml_essentials_amd.jaqsi as js``).
 
-Mirror of the hot-path part of ``qml_essentials/jaqsi.py``: ``Script`` re-export,
+Mirror of the hot-path part of ``qml_essentials/jaqsi.py``: ``Script`` and ``Evolution`` re-exports,
 ``partial_trace`` (:60-103), ``marginalize_probs`` (:106-146) and
 ``build_parity_observable`` (:149-167).  These helpers act on small host arrays
 (reduced density matrices, marginals); the 2^n-sized work stays in ``libqmle_sv``
@@ -13,7 +13,8 @@ from typing import List, Sequence
 
 import numpy as np
 
-from .operations import Hermitian, PauliZ  # noqa: F401
+from .evolution import Evolution  # noqa: F401
+from .operations import Hermitian, ParametrizedHamiltonian, PauliZ  # noqa: F401
 from .script import Script  # noqa: F401
 
 

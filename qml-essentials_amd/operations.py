@@ -11,13 +11,16 @@ Noise channels (``KrausChannel`` and subclasses, ``operations.py:1490-1929``) ar
 too: on the engine a channel is the superoperator ``sum_k K_k (x) conj(K_k)`` acting on the
 ket and bra copies of its wires in the vectorised density matrix (see ``simulation.py``).
 
-Out of scope here: ``ParametrizedHamiltonian``, ``PauliWord``
-algebra, pulse evolution.
+``Hermitian.evolve`` / ``ParametrizedHamiltonian`` (``operations.py:563-716``) hand a Hamiltonian to
+:mod:`evolution`, whose solver runs on the GPU; the evolved unitary comes back as an ordinary explicit-matrix
+``Operation`` -- batch-constant, or one matrix per sample (``[B, d, d]``, d <= 4).
+
+Out of scope here: ``PauliWord`` algebra, ``PulseGates`` / ``gate_mode="pulse"``.
 """
 from __future__ import annotations
 
 from functools import reduce
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import Callable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -97,7 +100,21 @@ class Operation:
     @property
     def parameter_tangents(self) -> list:
         t = self.__dict__.get("_tangents", {})
+        cols = self.matrix_columns()
+        if cols:  # one lowered parameter per matrix entry, all with the matrix's tangent state
+            return [self.__dict__.get("_matrix_tangent", [])] * len(cols)
         return [t.get(n, []) for n in self._param_names]
+
+    def matrix_columns(self) -> list:
+        """The lowered parameters of a per-sample explicit matrix ``[B, d, d]``: its entries in row-major order,
+        real then imaginary part, each a ``(B,)`` float64 column (8 for a 2x2, 32 for a 4x4).  Empty for every
+        other operation."""
+        m = self._matrix
+        if self._native is not None or not isinstance(m, np.ndarray) or m.ndim != 3:
+            return []
+        flat = np.asarray(m, dtype=np.complex128).reshape(m.shape[0], -1)
+        return [part for k in range(flat.shape[1]) for part in (np.ascontiguousarray(flat[:, k].real),
+                                                                np.ascontiguousarray(flat[:, k].imag))]
 
     def __init__(self, wires: Union[int, Sequence[int]] = 0, matrix=None, record: bool = True,
                  name: Optional[str] = None) -> None:
@@ -132,7 +149,8 @@ class Operation:
 
     @property
     def is_batched(self) -> bool:
-        return any(isinstance(p, np.ndarray) and p.ndim > 0 for p in self.parameters)
+        return (any(isinstance(p, np.ndarray) and p.ndim > 0 for p in self.parameters)
+                or bool(self.matrix_columns()))
 
     def __repr__(self) -> str:
         ps = self.parameters
@@ -228,11 +246,19 @@ class Operation:
         if self._native is not None:
             return self._native, self.wires, list(self.parameters), None
         m = np.asarray(self.matrix)
+        k = len(self.wires)
+        if m.ndim == 3 and self._matrix is not None:
+            # one matrix per sample (an evolved unitary with batched arguments): its entries are columns of the
+            # angle table, which LoweredTape never reduces mod 4 pi
+            if m.shape[1:] != (2**k, 2**k):
+                raise ValueError(f"{self.name}: matrix shape {m.shape[1:]} does not match {k} wire(s)")
+            if k > 2:
+                raise NotImplementedError(f"{self.name}: generic {k}-qubit matrices are not supported")
+            return ("MAT1_ROW" if k == 1 else "MAT2_ROW"), self.wires, self.matrix_columns(), None
         if m.ndim != 2:
             raise NotImplementedError(
                 f"{self.name}: explicit matrices must be batch-constant for the HIP engine"
             )
-        k = len(self.wires)
         if m.shape != (2**k, 2**k):
             raise ValueError(f"{self.name}: matrix shape {m.shape} does not match {k} wire(s)")
         if k > 2:
@@ -261,6 +287,9 @@ def conj_lower(op_: "Operation", n_qubits: int, offset: int):
         return None
     name, wires, params, blob = low
     wires = [w + offset for w in wires]
+    if name in ("MAT1_ROW", "MAT2_ROW"):
+        raise NotImplementedError(f"{op_.name}: per-sample matrices (evolved unitaries with batched arguments) are "
+                                  "not available in density-matrix mode")
     if name in _CONJ_NEGATE:
         neg = _CONJ_NEGATE[name]
         return name, wires, [(-p if j in neg else p) for j, p in enumerate(params)], None
@@ -298,11 +327,94 @@ def embed_matrix(mat: np.ndarray, wires: Sequence[int], all_wires: Sequence[int]
     return full.reshape(2**n, 2**n)
 
 
+def _drop_from_tape(op_: "Operation") -> None:
+    """A Hermitian that turns out to be a Hamiltonian term is no gate: take it off the active tape."""
+    tape = active_tape()
+    if tape is not None:
+        for i in range(len(tape) - 1, -1, -1):
+            if tape[i] is op_:
+                del tape[i]
+                break
+
+
 class Hermitian(Operation):
     """Generic Hermitian observable / explicit-matrix gate (``operations.py:515``)."""
 
     def __init__(self, matrix, wires=0, record: bool = True, **kw) -> None:
         super().__init__(wires=wires, matrix=matrix, record=record, **kw)
+
+    def __rmul__(self, coeff_fn: Callable) -> "ParametrizedHamiltonian":
+        """``coeff_fn * Hermitian`` -> one-term :class:`ParametrizedHamiltonian` (``operations.py:543-561``);
+        ``coeff_fn(params, t)`` gives the term's time-dependent coefficient."""
+        if not callable(coeff_fn):
+            raise TypeError(f"Left operand of `* Hermitian` must be callable, got {type(coeff_fn)}")
+        _drop_from_tape(self)
+        return ParametrizedHamiltonian(terms=[(coeff_fn, self.matrix, self.wires)])
+
+    def evolve(self, name: Optional[str] = None, **kw) -> Callable:
+        """Gate factory ``(t, wires=0) -> Operation`` for ``U = exp(-i t H)``; see :meth:`evolution.Evolution.evolve`.
+        The Hamiltonian itself leaves the tape: only the evolved gate is recorded."""
+        from .evolution import Evolution  # deferred: circular import
+
+        _drop_from_tape(self)
+        return Evolution.evolve(self, name=name, **kw)
+
+
+class ParametrizedHamiltonian:
+    """``H(t) = sum_i f_i(params_i, t) H_i`` as a list of ``(coeff_fn, H_mat, wires)`` terms
+    (``operations.py:581-716``).  Built as ``coeff_fn * Hermitian(matrix, wires)``; ``+``, ``-`` and unary minus
+    compose terms, which must all act on the same wires with matrices of one shape.  Not an operation: nothing of
+    it is recorded on a tape."""
+
+    def __init__(self, terms) -> None:
+        terms = list(terms)
+        if not terms:
+            raise ValueError("ParametrizedHamiltonian needs at least one term.")
+        first_wires = _wire_list(terms[0][2])
+        first_shape = np.asarray(terms[0][1]).shape
+        for _, H, w in terms[1:]:
+            if _wire_list(w) != first_wires:
+                raise ValueError("All terms of a ParametrizedHamiltonian must currently act on the same wires; got "
+                                 f"{_wire_list(w)} vs. {first_wires}.")
+            if np.asarray(H).shape != first_shape:
+                raise ValueError(f"All term matrices must have the same shape; got {np.asarray(H).shape} vs. "
+                                 f"{first_shape}.")
+        self._terms = tuple((fn, np.asarray(H, dtype=np.complex128), _wire_list(w)) for fn, H, w in terms)
+        self.wires: List[int] = list(first_wires)
+
+    @property
+    def coeff_fns(self) -> Tuple[Callable, ...]:
+        return tuple(fn for fn, _, _ in self._terms)
+
+    @property
+    def H_mats(self) -> Tuple[np.ndarray, ...]:
+        return tuple(H for _, H, _ in self._terms)
+
+    @property
+    def n_terms(self) -> int:
+        return len(self._terms)
+
+    def __add__(self, other):
+        if not isinstance(other, ParametrizedHamiltonian):
+            return NotImplemented
+        return ParametrizedHamiltonian(terms=list(self._terms) + list(other._terms))
+
+    def __neg__(self) -> "ParametrizedHamiltonian":
+        return ParametrizedHamiltonian(
+            terms=[((lambda f: lambda p, t: -f(p, t))(fn), H, w) for fn, H, w in self._terms])
+
+    def __sub__(self, other):
+        if not isinstance(other, ParametrizedHamiltonian):
+            return NotImplemented
+        return self + (-other)
+
+    def evolve(self, name: Optional[str] = None, **kw) -> Callable:
+        """Gate factory ``(coeff_args, T) -> Operation`` for ``dU/dt = -i [sum_i f_i(p_i, t) H_i] U``; solver options
+        (``atol``, ``rtol``, ``max_steps``, ``throw``, ``solver``, ``magnus_steps``) as in
+        :meth:`evolution.Evolution.evolve`."""
+        from .evolution import Evolution  # deferred: circular import
+
+        return Evolution.evolve(self, name=name, **kw)
 
 
 class Id(Operation):

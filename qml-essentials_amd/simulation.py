@@ -330,7 +330,9 @@ class LoweredTape:
             for p in params:
                 slots.append(len(self.values))
                 self.values.append(p)
-                self.ops_periodic.append(name != "DIAG_ALL")  # Golomb: exp(-i marks x), any marks
+                # (Golomb: exp(-i marks x), any marks; MAT1_ROW / MAT2_ROW: the columns are matrix entries, never
+                # reduced mod 4 pi)
+                self.ops_periodic.append(name not in ("DIAG_ALL", "MAT1_ROW", "MAT2_ROW"))
             off = -1
             if blob is not None:
                 off = const_len
@@ -397,7 +399,7 @@ def clear_plan_cache() -> None:
 def _tape_batch(tape: Sequence[Operation]) -> int:
     b = 1
     for op in tape:
-        for p in op.parameters:
+        for p in list(op.parameters) + list(op.matrix_columns()):  # (a per-sample matrix: its entries)
             if isinstance(p, np.ndarray) and p.ndim > 0:
                 if b not in (1, p.shape[0]):
                     raise ValueError(f"inconsistent batch sizes on the tape: {b} vs {p.shape[0]}")
