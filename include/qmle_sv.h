@@ -268,7 +268,17 @@ int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);
  * smaller workspace is legal: the engine splits what it gets in two, or keeps one chunk on `stream` alone.
  * Runs that fill a workspace slot once per call (two tile passes, <Z> out of the second) let the two streams run
  * free instead: each takes its chunks back to back, and the end of one chunk's measuring pass is covered by the
- * other stream's.  QMLE_NO_CHUNK_OVERLAP=1 (read per call): always the one-stream loop. */
+ * other stream's.  QMLE_NO_CHUNK_OVERLAP=1 (read per call): always the one-stream loop.
+ * Between calls the caller owns the workspace, so every call fills its slots again -- unless the caller hands the
+ * zeros back: qmle_run_batch_w / qmle_run_batch_map_w take `ws_token`, a HOST pointer (in / out, may be NULL) to a
+ * value that is opaque to the caller.  A call that returns QMLE_OK writes the token of the workspace as it leaves it;
+ * every error return writes 0.  Passing a non-zero token asserts two things: nobody wrote the workspace since the
+ * call that produced the token, and this call is ordered behind that call (same stream, or an event between them).
+ * Then the slots start as that call left them and the fills they no longer need are left out (the runs above that
+ * fill a slot once per call: none is left).  The token carries a fingerprint of the schedule (qmle_plan_autotune
+ * changes it), n, batch, measurement, the chunk size and slots, and the size and address of the aligned workspace;
+ * a token with another fingerprint counts as 0, and NULL or 0 gives the behaviour of the entries without it.  The
+ * engine keeps no record of workspaces: the token is all there is, and it belongs to the buffer it was made for. */
 size_t qmle_workspace_bytes(const qmle_plan *plan, int batch, int meas_type,
                             int n_obs, int states_in_flight);
 
@@ -277,6 +287,10 @@ size_t qmle_workspace_bytes(const qmle_plan *plan, int batch, int meas_type,
 int qmle_run_batch(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                    const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
                    size_t workspace_bytes, qmle_stream stream);
+/* qmle_run_batch with the workspace token of qmle_workspace_bytes (above); ws_token == NULL: qmle_run_batch. */
+int qmle_run_batch_w(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                     const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
+                     size_t workspace_bytes, qmle_stream stream, uint64_t *ws_token);
 /* Same, for Z (x) Z (x) .. parity observables (jaqsi.py:149-167; Model with tuple
  * output_qubit, model.py:980-990): wire_masks[k] (HOST) has bit w set iff wire w takes part.
  * Measured like QMLE_MEAS_EXPVAL_Z -- out of the last pass, no stored state; d_out
@@ -284,6 +298,11 @@ int qmle_run_batch(qmle_plan *plan, const float *d_angles, int batch, int meas_t
 int qmle_run_batch_parity(qmle_plan *plan, const float *d_angles, int batch,
                           const uint32_t *wire_masks, int n_obs, float *d_out, void *d_workspace,
                           size_t workspace_bytes, qmle_stream stream);
+/* ... with the workspace token (qmle_workspace_bytes); ws_token == NULL: qmle_run_batch_parity.  Plain Z's and
+ * parities of one plan, batch and workspace share their tokens: the measurement type is the same. */
+int qmle_run_batch_parity_w(qmle_plan *plan, const float *d_angles, int batch,
+                            const uint32_t *wire_masks, int n_obs, float *d_out, void *d_workspace,
+                            size_t workspace_bytes, qmle_stream stream, uint64_t *ws_token);
 
 /* Angle table from DEVICE-resident arguments: out[b][s] = const[s] + sum_t coef[t] *
  * leaf_{arg[t]}[row_k(b)][idx[t]], terms of slot s = [ptr[s], ptr[s+1]); row_k(b) =
@@ -323,6 +342,10 @@ typedef struct qmle_angle_map {
 int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angles, int batch,
                        int meas_type, const int32_t *obs_wires, int n_obs, void *d_out,
                        void *d_workspace, size_t workspace_bytes, qmle_stream stream);
+/* ... with the workspace token (qmle_workspace_bytes); ws_token == NULL: qmle_run_batch_map. */
+int qmle_run_batch_map_w(qmle_plan *plan, const qmle_angle_map *map, float *d_angles, int batch,
+                         int meas_type, const int32_t *obs_wires, int n_obs, void *d_out,
+                         void *d_workspace, size_t workspace_bytes, qmle_stream stream, uint64_t *ws_token);
 
 /* Apply the plan's passes in place to resident states [batch][2^n] complex64 (no
  * initialisation, no measurement) -- the per-gate loop simulation.py:102-103 alone.

@@ -161,11 +161,16 @@ SYMBOLS = [
                                 C.POINTER(C.c_double)]),
     ("qmle_workspace_bytes", _SZ, [_VP, _I, _I, _I, _I]),
     ("qmle_run_batch", _I, [_VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_run_batch_w", _I, [_VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP, C.POINTER(C.c_uint64)]),
     ("qmle_run_batch_parity", _I, [_VP, _VP, _I, C.POINTER(C.c_uint32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_run_batch_parity_w", _I, [_VP, _VP, _I, C.POINTER(C.c_uint32), _I, _VP, _VP, _SZ, _VP,
+                                 C.POINTER(C.c_uint64)]),
     ("qmle_build_angles", _I, [C.POINTER(_VP), C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                C.POINTER(C.c_int32), _I, _VP, _VP, _VP, _VP, _VP, _VP, _I,
                                C.c_int64, C.c_int64, _VP, _VP]),
     ("qmle_run_batch_map", _I, [_VP, _VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_run_batch_map_w", _I, [_VP, _VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP,
+                              C.POINTER(C.c_uint64)]),
     ("qmle_apply_inplace", _I, [_VP, _VP, _I, _VP, _VP, _SZ, _VP]),
     ("qmle_profile_begin", _I, [_VP, _I]),
     ("qmle_profile_end", _I, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
@@ -537,9 +542,21 @@ class Plan:
             tuned.add(meas)
         return True  # (a workspace sized for the old schedule is void)
 
+    def _kept_workspace(self, workspace, token, tuned: bool, B, meas, n_obs, states_in_flight, dev):
+        """The workspace of a run and the token that goes with it: the caller's token holds only for the caller's own
+        tensor under the schedule it was made for -- a workspace allocated here, or any after a re-schedule, starts
+        at token 0."""
+        ws = self._workspace(B, meas, n_obs, states_in_flight, None if tuned else workspace, dev)
+        return ws, C.c_uint64(int(token) if ws is workspace else 0)
+
     def run(self, angles, meas: str, obs_wires: Sequence[int] = (), out=None, workspace=None,
-            states_in_flight: int = 0):
-        """simulate_and_measure for a batch.  ``angles``: float32 cuda tensor [B, n_slots]."""
+            states_in_flight: int = 0, token: Optional[int] = None):
+        """simulate_and_measure for a batch.  ``angles``: float32 cuda tensor [B, n_slots].
+
+        ``token`` (with ``workspace=``; ``qmle_run_batch_w``): the workspace token that the previous run on this
+        workspace returned, or 0.  Passing it says that nobody wrote the workspace since that run and that this run is
+        ordered behind it; the zero fills that the workspace no longer needs are then left out.  With a token the
+        result is ``(out, workspace, token)``: the workspace really used and the token to hand to the next run."""
         torch = require_gpu()
         if meas not in MEAS:
             raise ValueError(f"Unknown measurement type: {meas!r}")  # simulation.py:271
@@ -554,7 +571,17 @@ class Plan:
         n_obs = len(obs_wires)
         if out is None:
             out = self._out(B, meas, n_obs, dev)
-        if self._tune_once(meas, n_obs, B):
+        tuned = self._tune_once(meas, n_obs, B)
+        if token is not None:
+            workspace, tok = self._kept_workspace(workspace, token, tuned, B, meas, n_obs, states_in_flight, dev)
+            rc = lib().qmle_run_batch_w(
+                self._h, C.c_void_p(angles.data_ptr()), B, MEAS[meas], _i32(obs_wires), n_obs,
+                C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                C.c_size_t(workspace.numel()), _stream_ptr(), C.byref(tok),
+            )
+            check(rc, "qmle_run_batch_w")
+            return out, workspace, int(tok.value)
+        if tuned:
             workspace = None
         workspace = self._workspace(B, meas, n_obs, states_in_flight, workspace, dev)
         rc = lib().qmle_run_batch(
@@ -566,9 +593,10 @@ class Plan:
         return out
 
     def run_map(self, amap: "AngleMapArgs", B: int, meas: str, obs_wires: Sequence[int] = (), out=None,
-                workspace=None):
+                workspace=None, token: Optional[int] = None):
         """:meth:`run` with the angle table built inside the same native call (qmle_run_batch_map):
-        ``amap`` holds the affine map and this call's leaves; the table itself is scratch."""
+        ``amap`` holds the affine map and this call's leaves; the table itself is scratch.  ``token``: as in
+        :meth:`run` (``qmle_run_batch_map_w``; the result is then ``(out, workspace, token)``)."""
         torch = require_gpu()
         if meas not in MEAS:
             raise ValueError(f"Unknown measurement type: {meas!r}")  # simulation.py:271
@@ -577,7 +605,17 @@ class Plan:
         angles = torch.empty((B, max(1, self.n_slots)), dtype=torch.float32, device=dev)
         if out is None:
             out = self._out(B, meas, n_obs, dev)
-        if self._tune_once(meas, n_obs, B):
+        tuned = self._tune_once(meas, n_obs, B)
+        if token is not None:
+            workspace, tok = self._kept_workspace(workspace, token, tuned, B, meas, n_obs, 0, dev)
+            rc = lib().qmle_run_batch_map_w(
+                self._h, amap.ref, C.c_void_p(angles.data_ptr()), B, MEAS[meas], _i32(obs_wires), n_obs,
+                C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                C.c_size_t(workspace.numel()), _stream_ptr(), C.byref(tok),
+            )
+            check(rc, "qmle_run_batch_map_w")
+            return out, workspace, int(tok.value)
+        if tuned:
             workspace = None
         workspace = self._workspace(B, meas, n_obs, 0, workspace, dev)
         rc = lib().qmle_run_batch_map(
@@ -626,9 +664,9 @@ class Plan:
               "qmle_plan_set_consts_f64")
 
     def run_parity(self, angles, wire_groups: Sequence[Sequence[int]], workspace=None,
-                   states_in_flight: int = 0):
+                   states_in_flight: int = 0, token: Optional[int] = None):
         """<Z..Z> over every wire group, measured out of the last pass (no stored state).
-        Returns float32 [B, len(wire_groups)]."""
+        Returns float32 [B, len(wire_groups)]; with ``token`` (as in :meth:`run`) ``(out, workspace, token)``."""
         torch = require_gpu()
         dev = current_device()
         if angles is None:
@@ -646,6 +684,13 @@ class Plan:
                 m |= 1 << int(w)
             masks[k] = m
         out = torch.empty((B, n_obs), dtype=torch.float32, device=dev)
+        if token is not None:
+            workspace, tok = self._kept_workspace(workspace, token, False, B, "expval", n_obs, states_in_flight, dev)
+            check(lib().qmle_run_batch_parity_w(
+                self._h, C.c_void_p(angles.data_ptr()), B, masks, n_obs, C.c_void_p(out.data_ptr()),
+                C.c_void_p(workspace.data_ptr()), C.c_size_t(workspace.numel()), _stream_ptr(), C.byref(tok)),
+                "qmle_run_batch_parity_w")
+            return out, workspace, int(tok.value)
         workspace = self._workspace(B, "expval", n_obs, states_in_flight, workspace, dev)
         check(lib().qmle_run_batch_parity(
             self._h, C.c_void_p(angles.data_ptr()), B, masks, n_obs, C.c_void_p(out.data_ptr()),

@@ -639,9 +639,34 @@ static int build_obs_masks(qmle_plan *plan, qmle_plan **exec, const uint32_t *wi
   return QMLE_OK;
 }
 
+static int run_batch_checked(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                             const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
+                             size_t workspace_bytes, qmle_stream stream_, uint64_t *ws_token);
+
 int qmle_run_batch(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                    const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
                    size_t workspace_bytes, qmle_stream stream_) {
+  return qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
+                          stream_, nullptr);
+}
+
+// every error return voids the caller's token (run_batch_masks does the same for its own)
+static int void_token(uint64_t *ws_token, int rc) {
+  if (ws_token) *ws_token = 0;
+  return rc;
+}
+
+int qmle_run_batch_w(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                     const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
+                     size_t workspace_bytes, qmle_stream stream_, uint64_t *ws_token) {
+  const int rc = run_batch_checked(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace,
+                                   workspace_bytes, stream_, ws_token);
+  return rc == QMLE_OK ? rc : void_token(ws_token, rc);
+}
+
+static int run_batch_checked(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                             const int32_t *obs_wires, int n_obs, void *d_out, void *d_workspace,
+                             size_t workspace_bytes, qmle_stream stream_, uint64_t *ws_token) {
   if (!plan || batch < 1 || !d_out || !d_workspace) return QMLE_ERR_INVALID_ARG;
   if (meas_type < QMLE_MEAS_STATE || meas_type > QMLE_MEAS_MEYER_WALLACH) return QMLE_ERR_MEAS_TYPE;
   if (plan->n_slots > 0 && !d_angles) return QMLE_ERR_INVALID_ARG;
@@ -658,22 +683,29 @@ int qmle_run_batch(qmle_plan *plan, const float *d_angles, int batch, int meas_t
     if (rc != QMLE_OK) return rc;
   }
   return run_batch_masks(exec, d_angles, batch, meas_type, masks, n_obs, d_out, d_workspace,
-                         workspace_bytes, (hipStream_t)stream_);
+                         workspace_bytes, (hipStream_t)stream_, ws_token);
 }
 
 int qmle_run_batch_parity(qmle_plan *plan, const float *d_angles, int batch,
                           const uint32_t *wire_masks, int n_obs, float *d_out, void *d_workspace,
                           size_t workspace_bytes, qmle_stream stream_) {
+  return qmle_run_batch_parity_w(plan, d_angles, batch, wire_masks, n_obs, d_out, d_workspace, workspace_bytes,
+                                 stream_, nullptr);
+}
+
+int qmle_run_batch_parity_w(qmle_plan *plan, const float *d_angles, int batch,
+                            const uint32_t *wire_masks, int n_obs, float *d_out, void *d_workspace,
+                            size_t workspace_bytes, qmle_stream stream_, uint64_t *ws_token) {
   if (!plan || batch < 1 || !d_out || !d_workspace || !wire_masks || n_obs < 1 ||
       n_obs > QMLE_MAX_QUBITS)
-    return QMLE_ERR_INVALID_ARG;
-  if (plan->n_slots > 0 && !d_angles) return QMLE_ERR_INVALID_ARG;
+    return void_token(ws_token, QMLE_ERR_INVALID_ARG);
+  if (plan->n_slots > 0 && !d_angles) return void_token(ws_token, QMLE_ERR_INVALID_ARG);
   uint32_t masks[QMLE_MAX_QUBITS];
   qmle_plan *exec = plan;
   const int rc = build_obs_masks(plan, &exec, wire_masks, n_obs, masks);
-  if (rc != QMLE_OK) return rc;
+  if (rc != QMLE_OK) return void_token(ws_token, rc);
   return run_batch_masks(exec, d_angles, batch, QMLE_MEAS_EXPVAL_Z, masks, n_obs, d_out,
-                         d_workspace, workspace_bytes, (hipStream_t)stream_);
+                         d_workspace, workspace_bytes, (hipStream_t)stream_, ws_token);
 }
 
 // How a run reads its <Z> observables (bit-position parity masks).
@@ -835,10 +867,55 @@ static bool slot_stays_zeroed(const qmle_plan *plan, bool fuse_expval) {
   return plan->stages.size() == 2 && plan->stages[0].kind == ST_TILE && fuse_expval;
 }
 
-// Simulate + measure; <Z> observables arrive as bit-position parity masks.
+static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                            const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
+                            size_t workspace_bytes, hipStream_t caller_stream, uint64_t token_in, uint64_t *token_out);
+
+// The workspace token of qmle_run_batch_w (include/qmle_sv.h): what a call that returned QMLE_OK tells the next call
+// on the same workspace about the zeros it left in the slots.  Bits 0..1 / 2..3: how many states of slot 0 / 1 hold
+// zeros outside tile 0 of stage 0 -- 0 none, 1 a whole chunk (L.in_flight), 2 the batch's short last chunk -- the only
+// counts a run's fills leave behind.  Bits 4..63: a fingerprint of everything that decides where those zeros lie and
+// whether anything behind stage 0 stores into a slot: the schedule (every stage's kind and tile placement, the chosen
+// candidate and padding, how often qmle_plan_autotune re-scheduled the plan), n, batch, measurement, the fill rule, the
+// chunk size, the slots and where they start, the size and the address of the aligned workspace.  The engine keeps
+// nothing: a token that does not carry the fingerprint of the call it is handed to counts as 0, and a run that leaves
+// no zeros behind (every run that fills chunk by chunk, the whole-state-in-LDS runs) answers 0.
+static uint64_t ws_fingerprint(const qmle_plan *plan, int batch, int meas_type, bool reuse_zeros, const BatchLayout &L,
+                               const char *ws, size_t ws_bytes) {
+  uint64_t h = fnv1a(&plan->n, sizeof(int));
+  for (const Stage &st : plan->stages) {
+    const int v[3] = {(int)st.kind, st.T, st.shift ? 1 : 0};
+    h = fnv1a(v, sizeof(v), h);
+    if (st.kind == ST_TILE) h = fnv1a(st.tile_bits, (size_t)st.T * sizeof(st.tile_bits[0]), h);
+  }
+  const uint64_t v[] = {(uint64_t)plan->chosen_candidate, (uint64_t)plan->pad_high, plan->schedule_serial,
+                        plan->mat_floats, plan->flags, (uint64_t)batch, (uint64_t)meas_type, reuse_zeros ? 1u : 0u,
+                        (uint64_t)L.in_flight, (uint64_t)L.slots, L.states[0], L.states[1], ws_bytes,
+                        (uint64_t)(uintptr_t)ws};
+  return (fnv1a(v, sizeof(v), h) << 4) | 16u;  // (never 0)
+}
+static int ws_token_states(uint64_t code, int batch, const BatchLayout &L) {
+  return code == 1 ? L.in_flight : code == 2 ? batch % L.in_flight : 0;
+}
+static uint64_t ws_token_code(int zeroed, int batch, const BatchLayout &L) {
+  return zeroed <= 0 ? 0u : zeroed == L.in_flight ? 1u : zeroed == batch % L.in_flight ? 2u : 0u;
+}
+
+// Simulate + measure; <Z> observables arrive as bit-position parity masks.  ws_token: qmle_run_batch_w's (may be NULL).
 int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                           const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
-                          size_t workspace_bytes, hipStream_t caller_stream) {
+                          size_t workspace_bytes, hipStream_t caller_stream, uint64_t *ws_token) {
+  const uint64_t token_in = ws_token ? *ws_token : 0;
+  uint64_t token_out = 0;
+  const int rc = run_batch_chunks(plan, d_angles, batch, meas_type, obs_masks, n_obs, d_out, d_workspace,
+                                  workspace_bytes, caller_stream, token_in, &token_out);
+  if (ws_token) *ws_token = rc == QMLE_OK ? token_out : 0;
+  return rc;
+}
+
+static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
+                            const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
+                            size_t workspace_bytes, hipStream_t caller_stream, uint64_t token_in, uint64_t *token_out) {
   if (plan->zero_variant) plan = plan->zero_variant;  // every run_batch starts from |0..0>
   plan->last_run = LastRun();  // (a run that fails reports the fresh-buffer figure and no measuring pass)
   const int n = plan->n;
@@ -873,10 +950,15 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
   ChunkPipeline pipe(L.slots == 2, plan->stages.size(), /*free_running=*/reuse_zeros, caller_stream);
   plan->last_run.chunk_loop = pipe.form();
-  // Clean slots: slot_zeroed[k] states of slot k hold zeros outside tile 0 of stage 0.  It lives and dies with this call
-  // (the caller owns the workspace between calls, so a slot's first chunk is always filled), and a slot is one
-  // buffer on one stream -- ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
+  // Clean slots: slot_zeroed[k] states of slot k hold zeros outside tile 0 of stage 0.  The caller owns the workspace
+  // between calls, so a slot's first chunk is filled -- unless the caller hands back the token of the call before
+  // (qmle_run_batch_w: nobody wrote the workspace since, and this call is ordered behind that one) and the token carries
+  // this call's fingerprint: then the slots start as that call left them.  A slot is one buffer on one stream --
+  // ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
+  const uint64_t fingerprint = ws_fingerprint(plan, batch, meas_type, reuse_zeros, L, ws, workspace_bytes);
   int slot_zeroed[2] = {0, 0};
+  if (reuse_zeros && (token_in & ~(uint64_t)15) == fingerprint)
+    for (int k = 0; k < L.slots; ++k) slot_zeroed[k] = ws_token_states((token_in >> (2 * k)) & 3u, batch, L);
   uint64_t filled_states = 0;  // states written by fills, all chunks
   bool elided = false;         // a chunk ran without its fill
   int chunk_no = 0;
@@ -971,6 +1053,10 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   if (elided)
     plan->last_run.stage0_written =
         ((filled_states << (n + 3)) + ((uint64_t)batch << (plan->stages[0].T + 3))) / (uint64_t)batch;
+  uint64_t codes = 0;
+  if (reuse_zeros)
+    for (int k = 0; k < L.slots; ++k) codes |= ws_token_code(slot_zeroed[k], batch, L) << (2 * k);
+  *token_out = codes ? fingerprint | codes : 0;  // (no zeros to hand on: no token)
   return QMLE_OK;
 }
 
@@ -1096,6 +1182,7 @@ static void adopt_schedule(qmle_plan *dst, qmle_plan *src) {
   dst->force_candidate = src->force_candidate;
   dst->pad_high = src->pad_high;
   dst->last_run.stage0_written = 0;  // (the figure of a run of the old schedule)
+  dst->schedule_serial++;            // (... and so are the zeros a run of it left in a workspace: ws_fingerprint)
   dst->autotuned = true;
 }
 
@@ -1252,11 +1339,18 @@ int qmle_build_angles(const float *const *d_leaves, const int64_t *leaf_strides,
 int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angles, int batch,
                        int meas_type, const int32_t *obs_wires, int n_obs, void *d_out,
                        void *d_workspace, size_t workspace_bytes, qmle_stream stream) {
-  if (!plan || !map || batch < 1) return QMLE_ERR_INVALID_ARG;
+  return qmle_run_batch_map_w(plan, map, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace,
+                              workspace_bytes, stream, nullptr);
+}
+
+int qmle_run_batch_map_w(qmle_plan *plan, const qmle_angle_map *map, float *d_angles, int batch,
+                         int meas_type, const int32_t *obs_wires, int n_obs, void *d_out,
+                         void *d_workspace, size_t workspace_bytes, qmle_stream stream, uint64_t *ws_token) {
+  if (!plan || !map || batch < 1) return void_token(ws_token, QMLE_ERR_INVALID_ARG);
   if (plan->n_slots == 0)
-    return qmle_run_batch(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
-                          stream);
-  if (!d_angles) return QMLE_ERR_INVALID_ARG;
+    return qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
+                            stream, ws_token);
+  if (!d_angles) return void_token(ws_token, QMLE_ERR_INVALID_ARG);
   // The table is needed as a table only by the Golomb diagonal (QMLE_OP_DIAG_ALL reads its angle in the pass
   // itself); every other gate meets its angles in the matrix builder, which can form them from the map --
   // one kernel (5-9 us of the 0.17 ms analysis loops) and the table's round trip less.  From 64 samples on
@@ -1267,21 +1361,21 @@ int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angl
     const int rc = qmle_build_angles(map->d_leaves, map->leaf_strides, map->leaf_div, map->leaf_mod, map->n_leaves,
                                      map->d_ptr, map->d_arg, map->d_idx, map->d_coef, map->d_const, map->d_period,
                                      plan->n_slots, batch, map->batch_offset, d_angles, stream);
-    if (rc != QMLE_OK) return rc;
-    return qmle_run_batch(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
-                          stream);
+    if (rc != QMLE_OK) return void_token(ws_token, rc);
+    return qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
+                            stream, ws_token);
   }
   AngleMapSrc src;
   std::memset(&src, 0, sizeof(src));
   const int rc_lv = fill_angle_leaves(src.lv, map->d_leaves, map->leaf_strides, map->leaf_div, map->leaf_mod, map->n_leaves);
-  if (rc_lv != QMLE_OK) return rc_lv;
+  if (rc_lv != QMLE_OK) return void_token(ws_token, rc_lv);
   src.ptr = map->d_ptr; src.arg = map->d_arg; src.idx = map->d_idx;
   src.coef = map->d_coef; src.cst = map->d_const; src.period = map->d_period;
   src.b_offset = map->batch_offset;
   src.small = map->batch_offset >= 0 && (uint64_t)batch + (uint64_t)map->batch_offset < (1ull << 32);
   tls_angle_map = &src;
-  const int rc = qmle_run_batch(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace,
-                                workspace_bytes, stream);
+  const int rc = qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace,
+                                  workspace_bytes, stream, ws_token);
   tls_angle_map = nullptr;
   return rc;
 }

@@ -122,7 +122,7 @@ int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_ma
                           bool forward_only = false);
 int run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                     const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
-                    size_t workspace_bytes, hipStream_t stream);
+                    size_t workspace_bytes, hipStream_t stream, uint64_t *ws_token = nullptr);
 int run_stage_inplace(qmle_plan *plan, const Stage &st, float2 *d_states, const float *d_mats,
                       const float *d_angles, int batch, hipStream_t stream);
 

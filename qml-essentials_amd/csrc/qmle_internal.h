@@ -312,6 +312,7 @@ struct qmle_plan {
   int force_candidate = -1, pad_high = -1;
   std::vector<std::pair<double, int>> cand_ranking;
   bool autotuned = false;
+  uint64_t schedule_serial = 0;           // times qmle_plan_autotune gave this plan another schedule (adopt_schedule)
   // The same tape compiled for runs from |0..0> only (qmle_run_batch): its first stage may stage a
   // wider tile (it computes one tile per state whatever the size).  Owned; used by run_batch_masks
   // in place of this plan; qmle_apply_inplace / the adjoint sweep keep using this plan's stages.

@@ -9,6 +9,7 @@ once with :class:`batching.Batched` arguments and hands the tape + angle table t
 """
 from __future__ import annotations
 
+import weakref
 from typing import Any, Callable, List, Optional, Tuple
 
 import numpy as np
@@ -34,6 +35,8 @@ class CompiledCall:
     from the resident ``params`` / ``inputs`` tensors), the plan's passes, the measurement --
     and nothing per sample on the host.
     """
+
+    _holder = None  # weak reference to the call that keeps a workspace (_run_kept)
 
     def __init__(self, script: "Script", type: str, obs, args: tuple, leaf_ids: Tuple[int, ...],
                  kwargs: dict):
@@ -104,6 +107,43 @@ class CompiledCall:
         self._low, self._map = low, (ptr, arg, idx, coef)   # host copies for the adjoint path
         self._leaf_sizes = {order[k]: int(np.prod(np.shape(args[k]))) for k in leaf_ids}
         self._adj = None
+        self._kept = None  # (key, workspace, token, True) of the latest run worth keeping (_run_kept)
+
+    def _run_kept(self, batch: int, kind: str, n_obs: int, run):
+        """``run(workspace, token) -> (out, workspace, token)`` on the workspace this call keeps.
+
+        One ``(workspace tensor, token)`` pair is kept, for the latest ``(batch, measurement, n_obs)`` on the current
+        stream, and only when the executed plan reports that run's chunk loop as ``"free"``: the runs whose workspace
+        slots stay zeroed, so that the next call fills nothing (``qmle_run_batch_w``).  Every other run leaves nothing
+        behind and allocates as before.  Only one call per process holds a pair at a time.  The pair goes when the key
+        changes (before the new run allocates), when the autotuner re-schedules the plan (``Plan.run`` then answers with
+        a workspace and token of its own) and on any exception."""
+        # only <Z> out of a tiled plan's last pass can leave zeroed slots behind: everything else runs as it always
+        # did, without a token (the analysis loops are bound by the host's time per call)
+        if kind != "expval":
+            return run(None, None)
+        tiled = self.__dict__.get("_z_tiled")
+        if tiled is None:
+            tiled = self._z_tiled = not self.plan.executed("expval").stats()["whole_state_lds"]
+        if not tiled:
+            return run(None, None)
+        import torch
+
+        key = (batch, kind, n_obs, torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+        kept, self._kept = self._kept, None
+        ws, tok, free = (kept[1], kept[2], kept[3]) if kept is not None and kept[0] == key else (None, 0, None)
+        del kept
+        out, ws_used, tok = run(ws, tok)
+        if tok and (free is None or ws_used is not ws):  # (a token of 0: the run left nothing to keep)
+            free = self.plan.executed(kind).describe()["stages"][-1].get("chunk_loop_last_run") == "free"
+        if tok and free:
+            # one kept workspace per process: the call that held the last one lets go of it
+            last = CompiledCall._holder() if CompiledCall._holder is not None else None
+            if last is not None and last is not self:
+                last._kept = None
+            CompiledCall._holder = weakref.ref(self)
+            self._kept = (key, ws_used, tok, True)
+        return out
 
     def run(self, leaves, divs, mods, batch: int, batch_offset: int = 0, meas: Optional[str] = None,
             shots: Optional[int] = None, key=None):
@@ -141,7 +181,9 @@ class CompiledCall:
             if am is None:
                 am = self._amap = N.AngleMapArgs(len(self.leaf_ids), self.d_ptr, self.d_arg, self.d_idx, self.d_coef,
                                                  self.d_const, self.d_period)
-            return self.plan.run_map(am.set(leaves, strides, divs, mods, batch_offset), batch, kind, arg)
+            amap = am.set(leaves, strides, divs, mods, batch_offset)
+            return self._run_kept(batch, kind, len(arg), lambda ws, tok: self.plan.run_map(
+                amap, batch, kind, arg, workspace=ws, token=tok))
         angles = N.build_angles(leaves, strides, divs, mods, self.d_ptr, self.d_arg, self.d_idx,
                                 self.d_coef, self.d_const, self.n_slots, batch, batch_offset,
                                 d_period=self.d_period)
@@ -153,9 +195,11 @@ class CompiledCall:
         if self.type == "expval":
             how, arg = self._measure()
             if how == "z":
-                return self.plan.run(angles, "expval", arg)
+                return self._run_kept(batch, "expval", len(arg), lambda ws, tok: self.plan.run(
+                    angles, "expval", arg, workspace=ws, token=tok))
             if how == "parity":
-                return self.plan.run_parity(angles, arg)
+                return self._run_kept(batch, "expval", -len(arg), lambda ws, tok: self.plan.run_parity(
+                    angles, arg, workspace=ws, token=tok))
             states = self.plan.run(angles, "state")
             if how == "pauli":
                 return N.expval_pauli(states, arg, len(self.obs))
