@@ -645,6 +645,33 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
                        int order, int n_steps, int lanes_per_row, int out_f64, void *d_out, qmle_stream stream);
 int qmle_evolve_lanes(int rows, int n_steps);
 
+/* ---- pulse-level gates (pulses.PulseGates.RX / RY): every pulse solve of a tape in one launch -----------------------
+ * U[s] of dU/dt = -i (cx(t) X + cy(t) Y) U on [0, S], U(0) = I, for n_solves independent 2x2 solves on the fixed
+ * Magnus grid described above (order 2 or 4, n_steps equal steps).  d_solves: float64 [n_solves][8], the columns
+ * p0, p1, p2, w, T, axis (0 = RX, anything else = RY) and two of padding.  The library evaluates the coefficients
+ * itself, at absolute node times, with the envelope centre t_c = t / 2 of the reference (t the running time):
+ *   envelope 0 gaussian  A exp(-(t / 2 sigma)^2 / 2)           p = A, sigma
+ *            1 square    A while t <= width, else 0            p = A, width
+ *            2 cosine    A cos(pi clip(t / (2 width), +-1/2))  p = A, width
+ *            3 drag      g (1 - beta (t / 2) / sigma^2), g the gaussian of (A, sigma)   p = A, beta, sigma
+ *            4 sech      A / cosh(t / 2 sigma)                 p = A, sigma
+ *   mode 0 rwa:   RX (cx, cy) = (env w / 2, 0), RY (0, env w / 2);
+ *        1 lab:   cx = env cos(omega_c t + phi) cos(omega_q t) w, cy = -env cos(omega_c t + phi) sin(omega_q t) w,
+ *                 phi = 0 (RX) or pi / 2 (RY);
+ *        2 drive: the same coefficients through the product-to-sum identities (omega_c -+ omega_q).
+ * S is the envelope's support inside the pulse: min(T, width) for square and cosine, T otherwise.
+ * d_out [n_solves][4] row-major, complex128 (out_f64 = 1) or complex64 (0); float64 arithmetic either way.
+ * d_prev (may be NULL): a result of the same format, normally that of the grid of half the steps; d_err (may be NULL,
+ * needs d_prev): float64 [n_solves] <- max over the four entries of |U - U_prev|, NaN when an entry is NaN.
+ * lanes_per_solve as lanes_per_row of qmle_evolve_magnus (0: qmle_evolve_lanes(n_solves, n_steps)).  A solve with a
+ * step whose |h cx| + |h cy| exceeds 2^15 or is not finite comes back as NaN.
+ * QMLE_ERR_UNSUPPORTED for order outside {2, 4}, envelope outside 0..4 or mode outside 0..2; QMLE_ERR_INVALID_ARG for
+ * NULL d_solves / d_out, n_solves < 1, n_steps < 1, another lanes_per_solve, out_f64 outside {0, 1}, d_err without
+ * d_prev, a frequency that is not finite, or n_solves * lanes beyond 2^31 -- all before any device work. */
+int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int mode, double omega_c, double omega_q,
+                         int order, int n_steps, int lanes_per_solve, int out_f64, void *d_out, const void *d_prev,
+                         double *d_err, qmle_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

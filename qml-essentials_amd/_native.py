@@ -234,6 +234,7 @@ SYMBOLS = [
     ("qmle_gram_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
     ("qmle_evolve_magnus", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     ("qmle_evolve_lanes", _I, [_I, _I]),
+    ("qmle_pulse_unitaries", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
 ]
 
 
@@ -972,6 +973,45 @@ def evolve_magnus(h_terms, coef, h, order: int, lanes_per_row: int = 0, complex6
                                    0 if complex64 else 1, C.c_void_p(out.data_ptr()), _stream_ptr()),
           "qmle_evolve_magnus")
     return out
+
+
+PULSE_ENVELOPES = ("gaussian", "square", "cosine", "drag", "sech")  # envelope ids of qmle_pulse_unitaries
+PULSE_MODES = ("rwa", "lab", "drive")
+
+
+def pulse_unitaries(solves, envelope: str, mode: str, omega_c: float, omega_q: float, order: int, n_steps: int,
+                    lanes_per_solve: int = 0, complex64: bool = False, prev=None, want_err: bool = False):
+    """Every RX / RY pulse solve of a tape in one launch (``qmle_pulse_unitaries``): ``solves`` ``[n, 8]`` float64
+    (``p0, p1, p2, w, T, axis``, padding; host array or CUDA tensor).  Returns ``U`` ``[n, 2, 2]`` complex128
+    (complex64 when asked) on the device, or ``(U, err)`` with ``want_err``: ``err`` ``[n]`` float64 =
+    ``max |U - prev|`` for ``prev``, a result of the same format."""
+    torch = require_gpu()
+    if envelope not in PULSE_ENVELOPES:
+        raise ValueError(f"pulse_unitaries: unknown envelope {envelope!r}; expected one of {PULSE_ENVELOPES}")
+    if mode not in PULSE_MODES:
+        raise ValueError(f"pulse_unitaries: unknown mode {mode!r}; expected one of {PULSE_MODES}")
+    dev = current_device()
+    if not hasattr(solves, "is_cuda"):
+        solves = torch.from_numpy(np.ascontiguousarray(solves, dtype=np.float64))
+    solves = solves.to(device=dev, dtype=torch.float64).contiguous()
+    if solves.dim() != 2 or solves.shape[1] != 8 or solves.shape[0] < 1:
+        raise ValueError(f"pulse_unitaries: solves must be [n >= 1, 8], got {tuple(solves.shape)}")
+    n = int(solves.shape[0])
+    cdtype = torch.complex64 if complex64 else torch.complex128
+    if want_err and prev is None:
+        raise ValueError("pulse_unitaries: want_err needs prev")
+    if prev is not None and (not prev.is_cuda or prev.dtype != cdtype or tuple(prev.shape) != (n, 2, 2)):
+        raise ValueError(f"pulse_unitaries: prev must be a CUDA {cdtype} tensor [{n}, 2, 2]")
+    if prev is not None:
+        prev = prev.contiguous()
+    out = torch.empty((n, 2, 2), dtype=cdtype, device=dev)
+    err = torch.empty((n,), dtype=torch.float64, device=dev) if want_err else None
+    check(lib().qmle_pulse_unitaries(
+        C.c_void_p(solves.data_ptr()), n, PULSE_ENVELOPES.index(envelope), PULSE_MODES.index(mode), float(omega_c),
+        float(omega_q), int(order), int(n_steps), int(lanes_per_solve), 0 if complex64 else 1,
+        C.c_void_p(out.data_ptr()), C.c_void_p(prev.data_ptr()) if prev is not None else None,
+        C.c_void_p(err.data_ptr()) if err is not None else None, _stream_ptr()), "qmle_pulse_unitaries")
+    return (out, err) if want_err else out
 
 
 @_row_chunked(0)

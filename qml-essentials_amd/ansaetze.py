@@ -16,7 +16,7 @@ from typing import Any, Callable, List, Optional, Tuple, Union
 
 import numpy as np
 
-from .gates import Gates
+from .gates import Gates, PulseInformation
 from .topologies import Topology
 
 log = logging.getLogger(__name__)
@@ -30,7 +30,8 @@ class Circuit(ABC):
         raise NotImplementedError("n_params_per_layer method is not implemented")
 
     def n_pulse_params_per_layer(self, n_qubits: int) -> int:
-        raise NotImplementedError("pulse-level simulation is outside the MI355X hot path")
+        """Pulse parameters per layer; circuits that are never run in pulse mode need not define it."""
+        raise NotImplementedError("n_pulse_params_per_layer method is not implemented")
 
     @abstractmethod
     def get_control_indices(self, n_qubits: int) -> Optional[List[int]]:
@@ -46,8 +47,15 @@ class Circuit(ABC):
         return np.asarray(w)[np.asarray(idx)]
 
     def _build(self, w, n_qubits: int, **kwargs: Any) -> Any:
-        if kwargs.get("gate_mode", "unitary") == "pulse":
-            raise NotImplementedError("gate_mode='pulse' is outside the MI355X hot path")
+        """One layer; in pulse mode with ``pulse_params`` the layer's scalers are handed out gate by gate through
+        the pulse manager (``ansaetze.py:96-133``)."""
+        if kwargs.get("gate_mode", "unitary") == "pulse" and "pulse_params" in kwargs:
+            expected = self.n_pulse_params_per_layer(n_qubits)
+            if len(kwargs["pulse_params"]) != expected:
+                raise ValueError(f"Pulse params length {len(kwargs['pulse_params'])} does not match expected "
+                                 f"{expected} for {n_qubits} qubits")
+            with Gates.pulse_manager_context(kwargs["pulse_params"]):
+                return self.build(w, n_qubits, **kwargs)
         return self.build(w, n_qubits, **kwargs)
 
     @abstractmethod
@@ -114,7 +122,15 @@ class Block:
         return 3 * n_qubits if self.gate.__name__ == "Rot" else n_qubits
 
     def n_pulse_params(self, n_qubits: int) -> int:
-        raise NotImplementedError("pulse-level simulation is outside the MI355X hot path")
+        """Pulse parameters of the block: those of its gate, once per wire or per pair."""
+        assert n_qubits > 0, "Number of qubits must be positive"
+        per_gate = PulseInformation.num_params(self.gate)
+        if self.is_entangling:
+            if not self.enough_qubits(n_qubits):
+                self._warn_skip(n_qubits)
+                return 0
+            return per_gate * len(self._pairs(n_qubits))
+        return per_gate * n_qubits
 
     def apply(self, n_qubits: int, w=None, w_idx: Optional[int] = None, **kwargs) -> int:
         """Record the block; weights are consumed in wire / pair order
@@ -158,7 +174,7 @@ class DeclarativeCircuit(Circuit):
 
     @classmethod
     def n_pulse_params_per_layer(cls, n_qubits: int) -> int:
-        raise NotImplementedError("pulse-level simulation is outside the MI355X hot path")
+        return sum(b.n_pulse_params(n_qubits) for b in cls.structure())
 
     @classmethod
     def get_control_indices(cls, n_qubits: int) -> Optional[List]:
@@ -247,6 +263,10 @@ class _GHZ(DeclarativeCircuit):
         Gates.H(wires=0, **kwargs)
         for q in range(n_qubits - 1):
             Gates.CX(wires=[q, q + 1], **kwargs)
+
+    @classmethod
+    def n_pulse_params_per_layer(cls, n_qubits: int) -> int:
+        return PulseInformation.num_params("H") + (n_qubits - 1) * PulseInformation.num_params(Gates.CX)  # one H
 
 
 _GHZ.__name__ = "GHZ"

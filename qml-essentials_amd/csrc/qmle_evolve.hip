@@ -5,7 +5,8 @@
 //            A_k = A(t_n + c_k h), c_1,2 = 1/2 -+ sqrt(3)/6, a_1,2 = 1/4 +- sqrt(3)/6       two nodes per step
 // with A(t) = -i sum_i c_i(t) H_i.  The kernel evaluates no coefficient function: it reads c_i at the node times from
 // a table coef[row][node][term], in node order.  float64 throughout; the result is rounded once when it is stored as
-// complex64.
+// complex64.  k_pulse_unitaries (further down) solves the RX / RY leaves of pulse-level gates on the same grids with
+// the same work split, but evaluates its two coefficients itself instead of reading a table.
 //
 // Work split.  A row's steps are cut into `lanes` contiguous runs (1, 4, 16 or 64 neighbouring lanes of one wave).
 // Every lane forms the ordered product of its run from the identity; the partial products are then multiplied in
@@ -277,6 +278,176 @@ __global__ __launch_bounds__(kEvolveThreads) void k_evolve_magnus(const EvolveTe
   }
 }
 
+// ---- pulse-level gates: every RX / RY pulse solve of a tape in one launch -------------------------------------------
+// One solve per (request, row): d_solves[solve] = {p0, p1, p2, w, T, axis, -, -}.  The Hamiltonian is
+// cx(t) X + cy(t) Y with the reference's interaction-picture coefficients (qml_essentials/pulses.py:446-630), which the
+// lanes evaluate at their own node times in float64 -- no coefficient table.  The envelope centre is t_c = t / 2 with t
+// the RUNNING time (the reference's definition, which its optimised defaults assume), so
+//   gaussian  A exp(-(t / 2 sigma)^2 / 2)          p = {A, sigma}
+//   square    A for t <= width, else 0             p = {A, width}
+//   cosine    A cos(pi clip(t / (2 width), +-1/2)) p = {A, width}
+//   drag      g (1 - beta (t / 2) / sigma^2), g the gaussian   p = {A, beta, sigma}
+//   sech      A / cosh(t / 2 sigma)                p = {A, sigma}
+// Node times are absolute (the carrier phase depends on t).  The grid covers the envelope's support: [0, min(T, width)]
+// for square and cosine, whose coefficient is identically zero beyond it -- a grid over [0, T] would straddle the jump
+// (square) or the kink (cosine) and lose the order of the scheme -- and [0, T] otherwise.
+enum { kEnvGaussian = 0, kEnvSquare = 1, kEnvCosine = 2, kEnvDrag = 3, kEnvSech = 4, kEnvCount = 5 };
+enum { kModeRwa = 0, kModeLab = 1, kModeDrive = 2, kModeCount = 3 };
+constexpr double kPi = 3.14159265358979323846;
+
+struct PulseLaunch {
+  int envelope, mode, n_solves, n_steps, lanes, out_f64;
+  double omega_c, omega_q;
+};
+
+template <int ENV>
+__host__ __device__ __forceinline__ double pulse_envelope(double p0, double p1, double p2, double t) {
+  const double tc = 0.5 * t;  // t - t_c
+  if constexpr (ENV == kEnvGaussian) {
+    const double x = tc / p1;
+    return p0 * exp(-0.5 * (x * x));
+  } else if constexpr (ENV == kEnvSquare) {
+    return fabs(tc) <= 0.5 * p1 ? p0 : 0.0;
+  } else if constexpr (ENV == kEnvCosine) {
+    const double x = fmin(fmax(tc / p1, -0.5), 0.5);
+    return p0 * cos(kPi * x);
+  } else if constexpr (ENV == kEnvDrag) {
+    const double x = tc / p2, g = p0 * exp(-0.5 * (x * x));
+    return g + p1 * (g * (-tc / (p2 * p2)));
+  } else {
+    const double e = exp(-fabs(tc / p1));  // 1 / cosh x = 2 e^-|x| / (1 + e^-2|x|): one exponential, no overflow
+    return p0 * (2.0 * e / fma(e, e, 1.0));
+  }
+}
+
+// sin and cos of two arguments through ONE copy of the fp64 argument reduction (the loop stays rolled: the
+// transcendental code and its constants are what fills the scalar registers of these kernels)
+__host__ __device__ __forceinline__ void sincos_pair(double a0, double a1, double &s0, double &c0, double &s1, double &c1) {
+  s0 = c0 = s1 = c1 = 0.0;
+#pragma nounroll
+  for (int k = 0; k < 2; ++k) {
+    double sn, cs;
+    sincos(k ? a1 : a0, &sn, &cs);
+    if (k) s1 = sn, c1 = cs;
+    else s0 = sn, c0 = cs;
+  }
+}
+
+// the X and Y coefficients at time t; axis_y: the RY pulse (carrier phase +pi/2)
+template <int ENV, int MODE>
+__host__ __device__ __forceinline__ void pulse_coefficients(const PulseLaunch &L, double p0, double p1, double p2, double w,
+                                                   bool axis_y, double t, double &cx, double &cy) {
+#pragma clang fp contract(off)  // omega t + phi reaches 160 rad: a fused multiply-add would move the phase by an ulp of it
+  const double env = pulse_envelope<ENV>(p0, p1, p2, t);
+  if constexpr (MODE == kModeRwa) {
+    const double c = 0.5 * env * w;
+    cx = axis_y ? 0.0 : c;
+    cy = axis_y ? c : 0.0;
+  } else if constexpr (MODE == kModeLab) {
+    double sq, cq, sc, carrier;
+    sincos_pair(L.omega_q * t, L.omega_c * t + (axis_y ? 0.5 * kPi : 0.0), sq, cq, sc, carrier);
+    cx = env * carrier * cq * w;
+    cy = -env * carrier * sq * w;
+  } else {  // product-to-sum form of the same coefficients
+    double sd, cd, ss, cs;
+    sincos_pair((L.omega_c - L.omega_q) * t, (L.omega_c + L.omega_q) * t, sd, cd, ss, cs);
+    const double mx = axis_y ? -0.5 * (ss + sd) : 0.5 * (cd + cs);
+    const double my = axis_y ? -0.5 * (cs - cd) : -0.5 * (ss - sd);
+    cx = env * mx * w;
+    cy = env * my * w;
+  }
+}
+
+// U <- exp(-i (gx X + gy Y)) U; false when the exponent's norm is not finite or beyond kEvolveMaxNorm
+__host__ __device__ __forceinline__ bool pulse_step(double gx, double gy, CMat<2> &U) {
+  Herm<2> G;
+  G.d[0] = G.d[1] = 0.0;
+  G.re[0] = gx;
+  G.im[0] = -gy;
+  apply_exp(G, U);
+  return fabs(gx) + fabs(gy) <= kEvolveMaxNorm;
+}
+
+// One work item per (solve, lane of the solve); a block holds kEvolveThreads / lanes solves.
+template <int ORDER, int ENV, int MODE>
+__global__ __launch_bounds__(kEvolveThreads) void k_pulse_unitaries(const double *__restrict__ solves, const PulseLaunch L,
+                                                                    void *__restrict__ out,
+                                                                    const void *__restrict__ prev,
+                                                                    double *__restrict__ err) {
+  const int lanes = L.lanes, n_steps = L.n_steps;
+  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
+  const long long solve_ll = gid / lanes;
+  const int lane = (int)(gid - solve_ll * lanes);
+  const bool live = solve_ll < L.n_solves;  // (a solve's lanes are live or idle together: lanes divides the block)
+  const int solve = live ? (int)solve_ll : L.n_solves - 1;
+  const double *__restrict__ q = solves + (size_t)solve * 8;
+  const double p0 = q[0], p1 = q[1], p2 = q[2], w = q[3], T = q[4];
+  const bool axis_y = q[5] != 0.0;
+  const double span = (ENV == kEnvSquare || ENV == kEnvCosine) ? fmin(T, p1) : T;
+  const double h = span / (double)n_steps;
+  const int s_begin = (int)((long long)lane * n_steps / lanes), s_end = (int)((long long)(lane + 1) * n_steps / lanes);
+  constexpr double kC1 = 0.5 - 0.28867513459481288225, kC2 = 0.5 + 0.28867513459481288225;  // 1/2 -+ sqrt(3)/6
+  constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;  // 1/4 +- sqrt(3)/6
+  CMat<2> U;
+  set_identity(U);
+  bool ok = true;
+  for (int s = s_begin; s < s_end; ++s) {
+    double ax, ay;
+    if constexpr (ORDER == 2) {
+      pulse_coefficients<ENV, MODE>(L, p0, p1, p2, w, axis_y, ((double)s + 0.5) * h, ax, ay);
+      ok &= pulse_step(h * ax, h * ay, U);
+    } else {
+      double bx = 0.0, by = 0.0;
+      ax = ay = 0.0;
+#pragma nounroll  // (one copy of the transcendental code serves both nodes)
+      for (int node = 0; node < 2; ++node) {
+        double x, y;
+        pulse_coefficients<ENV, MODE>(L, p0, p1, p2, w, axis_y, ((double)s + (node ? kC2 : kC1)) * h, x, y);
+        if (node) bx = x, by = y;
+        else ax = x, ay = y;
+      }
+      const double h1 = h * kA1, h2 = h * kA2;
+#pragma nounroll
+      for (int half = 0; half < 2; ++half) {  // Omega_a first, then Omega_b
+        const double wa = half ? h2 : h1, wb = half ? h1 : h2;
+        ok &= pulse_step(fma(wb, bx, wa * ax), fma(wb, by, wa * ay), U);
+      }
+    }
+  }
+  if (!ok) {  // (the combine carries the NaN into lane 0)
+    const double bad = __builtin_nan("");
+#pragma unroll
+    for (int k = 0; k < 4; ++k) U.re[k] = U.im[k] = bad;
+  }
+  for (int delta = 1; delta < lanes; delta <<= 1) combine_with_later(U, delta, lanes);  // lane 0 ends with the solve
+  if (!live || lane != 0) return;
+  double worst = 0.0;  // max |U - U_prev|; NaN once an entry is NaN
+  if (L.out_f64) {
+    double2 *o = (double2 *)out + (size_t)solve * 4;
+    const double2 *pv = prev ? (const double2 *)prev + (size_t)solve * 4 : nullptr;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (pv) {
+        const double dr = U.re[k] - pv[k].x, di = U.im[k] - pv[k].y, a = sqrt(dr * dr + di * di);
+        worst = (a > worst || a != a) ? a : worst;
+      }
+      o[k] = make_double2(U.re[k], U.im[k]);
+    }
+  } else {
+    float2 *o = (float2 *)out + (size_t)solve * 4;
+    const float2 *pv = prev ? (const float2 *)prev + (size_t)solve * 4 : nullptr;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (pv) {
+        const double dr = U.re[k] - (double)pv[k].x, di = U.im[k] - (double)pv[k].y, a = sqrt(dr * dr + di * di);
+        worst = (a > worst || a != a) ? a : worst;
+      }
+      o[k] = make_float2((float)U.re[k], (float)U.im[k]);
+    }
+  }
+  if (err) err[solve] = worst;
+}
+
 // lanes_per_row = 0: one lane per row when the rows alone fill the card (256 CUs x 4 SIMDs x 2 waves), else the
 // widest split that stays within that many lanes and leaves every lane at least one step
 int evolve_auto_lanes(int rows, int n_steps) {
@@ -339,6 +510,48 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
   else if (order == 2) QMLE_EVOLVE_LAUNCH(4, 2);
   else QMLE_EVOLVE_LAUNCH(4, 4);
 #undef QMLE_EVOLVE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int mode, double omega_c, double omega_q,
+                         int order, int n_steps, int lanes_per_solve, int out_f64, void *d_out, const void *d_prev,
+                         double *d_err, qmle_stream stream_) {
+  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
+  if (envelope < 0 || envelope >= kEnvCount || mode < 0 || mode >= kModeCount) return QMLE_ERR_UNSUPPORTED;
+  if (!d_solves || !d_out || n_solves < 1 || n_steps < 1 || (out_f64 != 0 && out_f64 != 1) || (d_err && !d_prev) ||
+      !(fabs(omega_c) <= 1e300) || !(fabs(omega_q) <= 1e300))
+    return QMLE_ERR_INVALID_ARG;
+  if (lanes_per_solve != 0 && lanes_per_solve != 1 && lanes_per_solve != 4 && lanes_per_solve != 16 &&
+      lanes_per_solve != 64)
+    return QMLE_ERR_INVALID_ARG;
+  const int lanes = lanes_per_solve ? lanes_per_solve : evolve_auto_lanes(n_solves, n_steps);
+  const long long items = (long long)n_solves * lanes;
+  if (items > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
+  const PulseLaunch L{envelope, mode, n_solves, n_steps, lanes, out_f64, omega_c, omega_q};
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
+#define QMLE_PULSE_LAUNCH(O, E, M) \
+  hipLaunchKernelGGL((k_pulse_unitaries<O, E, M>), grid, block, 0, stream, d_solves, L, d_out, d_prev, d_err)
+#define QMLE_PULSE_MODES(O, E)                       \
+  do {                                               \
+    if (mode == kModeRwa) QMLE_PULSE_LAUNCH(O, E, kModeRwa); \
+    else if (mode == kModeLab) QMLE_PULSE_LAUNCH(O, E, kModeLab); \
+    else QMLE_PULSE_LAUNCH(O, E, kModeDrive);        \
+  } while (0)
+#define QMLE_PULSE_ENVELOPES(O)                                        \
+  switch (envelope) {                                                  \
+    case kEnvGaussian: QMLE_PULSE_MODES(O, kEnvGaussian); break;       \
+    case kEnvSquare: QMLE_PULSE_MODES(O, kEnvSquare); break;           \
+    case kEnvCosine: QMLE_PULSE_MODES(O, kEnvCosine); break;           \
+    case kEnvDrag: QMLE_PULSE_MODES(O, kEnvDrag); break;               \
+    default: QMLE_PULSE_MODES(O, kEnvSech); break;                     \
+  }
+  if (order == 2) QMLE_PULSE_ENVELOPES(2)
+  else QMLE_PULSE_ENVELOPES(4)
+#undef QMLE_PULSE_ENVELOPES
+#undef QMLE_PULSE_MODES
+#undef QMLE_PULSE_LAUNCH
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }

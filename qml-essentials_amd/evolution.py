@@ -16,8 +16,11 @@ exceeds ``max_steps``.  If no grid is accepted -- always the case for ``max_step
 
 Gradients.  Tangents are dropped through ``evolve``: an evolved gate whose arguments depend on a differentiated leaf
 carries "derivative unknown", and ``Script.gradient`` refuses it as it refuses every untracked transformation.
-Differentiating through the solver is out of scope, as are ``PulseGates`` / ``gate_mode="pulse"`` and matrices
-larger than 4x4.
+Differentiating through the solver is out of scope, as are matrices larger than 4x4.
+
+Pulse-level gates (:mod:`pulses`) do not come through ``evolve``: their RX / RY leaves are solved by a kernel of their
+own that evaluates the envelopes on the device, all leaves of a tape in one launch.  They share the solver defaults
+below and the step-doubling rule (``_doubling``).
 """
 from __future__ import annotations
 
@@ -244,14 +247,26 @@ class Evolution:
         return _apply
 
     @staticmethod
-    def _doubling(fixed: Callable, rows: int, dim: int, tol: float, max_steps: int):
-        """-> (U of the last grid tried, accepted [rows], its steps); see the module docstring."""
+    def _doubling(fixed: Callable, rows: int, dim: int, tol: float, max_steps: int, on_device: bool = False):
+        """-> (U of the last grid tried, accepted [rows], its steps), host arrays; see the module docstring.
+        ``on_device``: ``fixed(n, 4)`` returns a device tensor and ``fixed(n, 4, prev)`` the pair ``(U_n, max |U_n -
+        prev| per row)``, both on the device (the pulse solver): the previous grid never leaves it, one number -- the
+        worst row's distance, NaN if any row is NaN -- crosses to the host per round and the matrices once at the end."""
         if max_steps < _FIRST_GRID:
             return np.full((rows, dim, dim), np.nan + 0j), np.zeros(rows, dtype=bool), 0
         prev, n = fixed(_FIRST_GRID // 2, 4), _FIRST_GRID
         while True:
-            cur = fixed(n, 4)
-            ok = np.max(np.abs(cur - prev), axis=(1, 2)) / 15.0 <= tol
-            if ok.all() or 2 * n > max_steps:
-                return cur, ok, n
+            if on_device:
+                import torch
+
+                cur, err = fixed(n, 4, prev)
+                accepted = float(torch.amax(err)) / 15.0 <= tol
+            else:
+                cur = fixed(n, 4)
+                err = np.max(np.abs(cur - prev), axis=(1, 2))
+                accepted = bool((err / 15.0 <= tol).all())
+            if accepted or 2 * n > max_steps:
+                if on_device:
+                    cur, err = cur.cpu().numpy(), err.cpu().numpy()
+                return cur, err / 15.0 <= tol, n
             prev, n = cur, 2 * n

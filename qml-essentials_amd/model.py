@@ -6,7 +6,10 @@ gate order (``_variational`` ``:818-963``, ``_iec`` ``:746-816``), observables
 (``_build_obs`` ``:965-998``), result shaping (``_forward`` ``:1572-1737``) and
 ``initialize_params`` (``:631-722``).  Results are NumPy arrays (the reference
 returns ``jnp`` arrays); the 2^n arithmetic runs in ``libqmle_sv`` via
-:class:`script.Script`.  Out of scope: noise, pulses, drawing, ``exact_spectrum``.
+:class:`script.Script`.  ``gate_mode="pulse"`` records the ansatz (and the state preparation) through
+:mod:`pulses` and runs the recorded tape -- every pulse solve of it in one kernel launch; ``pulse_params`` are
+per-layer scalers of the optimised pulse parameters, shape ``(1, layers, n_pulse_params_per_layer)`` (a batch axis
+larger than 1 is not supported, nor is noise in pulse mode).  Out of scope: drawing, ``exact_spectrum``.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ from . import operations as op
 from .tape import recording
 from .ansaetze import Ansaetze, Circuit, Encoding
 from .batching import to_numpy
-from .gates import Gates
+from .gates import Gates, PulseInformation
 from ._native import to_host as N_to_host
 from .utils import (PRNGKey, as_key, device_sampling, safe_random_split, uniform,
                     uniform_device)
@@ -71,10 +74,17 @@ class Model:
         self.repeat_batch_axis = list(repeat_batch_axis)
         self.gate_mode = "unitary"
 
+        PulseInformation.set_envelope(pulse_shape)
+
         try:
             self._sp = Gates.parse_gates(state_preparation, Gates)
         except ValueError as e:
             raise ValueError(f"Error parsing encodings: {e}")
+        # state preparation always runs on the optimised pulses; None: the gate has no pulse parametrisation
+        self.sp_pulse_params = []
+        for sp in self._sp:
+            info = PulseInformation.gate_by_name(getattr(sp, "__name__", str(sp)))
+            self.sp_pulse_params.append(None if info is None else info.params)
 
         self._enc = encoding if isinstance(encoding, Encoding) else Encoding("hamming", encoding)
         if self._enc.is_golomb:
@@ -93,7 +103,12 @@ class Model:
         else:
             self.pqc = circuit_type()
         self._params_shape = (impl_layers, self.pqc.n_params_per_layer(n_qubits))
-        self._pulse_params_shape = (impl_layers, 0)
+        try:
+            self._pulse_params_shape = (impl_layers, self.pqc.n_pulse_params_per_layer(n_qubits))
+            self._pulse_capable = True
+        except NotImplementedError:  # a custom Circuit without pulse parameter count: unitary mode only
+            self._pulse_params_shape = (impl_layers, 0)
+            self._pulse_capable = False
 
         self._batch_shape = None
         self._inialization_strategy = initialization
@@ -396,6 +411,16 @@ class Model:
                 RuntimeWarning,
             )
             noise_params = self.noise_params
+        pulse = gate_mode == "pulse"
+        if pulse and pulse_params is None:
+            warnings.warn(
+                "Explicit call to `_circuit` or `_variational` detected: "
+                "`pulse_params` is None, using `self.pulse_params` instead.",
+                RuntimeWarning,
+            )
+            pulse_params = self.pulse_params
+        if pulse and len(pulse_params.shape) > 2 and pulse_params.shape[0] == 1:
+            pulse_params = pulse_params[0]
         if noise_params is not None:
             if random_key is None:
                 warnings.warn(
@@ -406,14 +431,18 @@ class Model:
                 random_key = self.random_key
             self._apply_state_prep_noise(noise_params=noise_params)
 
+        def layer_kw(layer: int) -> dict:  # (pulse mode: this layer's scalers go to the ansatz' pulse manager)
+            return dict(pulse_params=pulse_params[layer]) if pulse else {}
+
         for q in range(self.n_qubits):
-            for prep in self._sp:
+            for prep, sp_pulse_params in zip(self._sp, self.sp_pulse_params):
                 random_key, sub_key = safe_random_split(random_key)
-                prep(wires=q, noise_params=noise_params, random_key=sub_key, gate_mode=gate_mode)
+                prep(wires=q, noise_params=noise_params, random_key=sub_key, gate_mode=gate_mode,
+                     **(dict(pulse_params=sp_pulse_params) if pulse else {}))
         for layer in range(self.n_layers):
             random_key, sub_key = safe_random_split(random_key)
             self.pqc(params[layer], self.n_qubits, noise_params=noise_params,
-                     random_key=sub_key, gate_mode=gate_mode)
+                     random_key=sub_key, gate_mode=gate_mode, **layer_kw(layer))
             random_key, sub_key = safe_random_split(random_key)
             self._iec(inputs, data_reupload=self.data_reupload[layer], enc=self._enc,
                       enc_params=enc_params[layer], noise_params=noise_params,
@@ -421,7 +450,7 @@ class Model:
         if self.has_dru:
             random_key, sub_key = safe_random_split(random_key)
             self.pqc(params[self.n_layers], self.n_qubits, noise_params=noise_params,
-                     random_key=sub_key, gate_mode=gate_mode)
+                     random_key=sub_key, gate_mode=gate_mode, **layer_kw(self.n_layers))
         if noise_params is not None:
             self._apply_general_noise(noise_params=noise_params)
 
@@ -519,6 +548,20 @@ class Model:
             params = np.expand_dims(params, axis=0)
         self.params = params
         return params
+
+    def _pulse_params_validation(self, pulse_params) -> np.ndarray:
+        """``(batch, layers, n_pulse_params_per_layer)`` scalers (``model.py:1257-1285``); the batch axis must be 1."""
+        if pulse_params is None:
+            pulse_params = self.pulse_params
+        else:
+            pulse_params = to_numpy(pulse_params)
+            if len(pulse_params.shape) == 2:
+                pulse_params = np.expand_dims(pulse_params, axis=0)
+            self.pulse_params = pulse_params
+        if pulse_params.shape[0] > 1:
+            raise NotImplementedError("a batch axis in pulse_params is not supported: pass one set of scalers, shape "
+                                      f"(1, {self._pulse_params_shape[0]}, {self._pulse_params_shape[1]})")
+        return pulse_params
 
     def _enc_params_validation(self, enc_params) -> np.ndarray:
         if enc_params is None:
@@ -1106,7 +1149,13 @@ class Model:
                 "Either switch gate_mode='pulse' or do not pass pulse_params."
             )
         if gate_mode == "pulse":
-            raise NotImplementedError("gate_mode='pulse' is outside the MI355X hot path")
+            if self.noise_params is not None:
+                raise ValueError("noise_params were provided but gate_mode is 'pulse'. "
+                                 "Noise is not supported in pulse mode.")
+            if not self._pulse_capable:
+                raise NotImplementedError(f"{type(self.pqc).__name__} does not define n_pulse_params_per_layer: "
+                                          "gate_mode='pulse' is not available for it")
+            pulse_params = self._pulse_params_validation(pulse_params)
         if data_reupload is not None:
             self.data_reupload = data_reupload
 
@@ -1134,8 +1183,8 @@ class Model:
 
         # one key for the whole batch: GateError draws B values per gate from it (the
         # reference vmaps over B split keys, model.py:1678-1691)
-        args = (params, inputs, None, sub_key if self.noise_params is not None else None,
-                enc_params)
+        args = (params, inputs, pulse_params if gate_mode == "pulse" else None,
+                sub_key if self.noise_params is not None else None, enc_params)
         if B > 1:
             in_axes = (0 if self.batch_shape[1] > 1 else None,
                        0 if self.batch_shape[0] > 1 else None, None, None, None)

@@ -15,7 +15,10 @@ ket and bra copies of its wires in the vectorised density matrix (see ``simulati
 :mod:`evolution`, whose solver runs on the GPU; the evolved unitary comes back as an ordinary explicit-matrix
 ``Operation`` -- batch-constant, or one matrix per sample (``[B, d, d]``, d <= 4).
 
-Out of scope here: ``PauliWord`` algebra, ``PulseGates`` / ``gate_mode="pulse"``.
+Pulse-level gates (:mod:`pulses`) record ordinary operations for their closed-form leaves and a
+``pulses.PulseRotation`` -- an ``Operation`` whose matrix is a pulse solve still to be run -- for RX / RY.
+
+Out of scope here: ``PauliWord`` algebra.
 """
 from __future__ import annotations
 

@@ -15,7 +15,7 @@ from typing import Any, Callable, List, Optional, Tuple
 import numpy as np
 
 from . import _native as N
-from . import distributed, memory, simulation
+from . import distributed, memory, pulses, simulation
 from .batching import Batched, to_numpy
 from .operations import MAX_PAULI_WIRES, KrausChannel, Operation, pauli_terms, z_parity_mask
 from .tape import batch_context, recording
@@ -340,6 +340,7 @@ class Script:
         if in_axes is not None:
             return self._execute_batched(type, obs, args, kwargs, in_axes, shots, key, as_tensor)
         tape = self._record(*[to_numpy(a) for a in args], **kwargs)
+        pulses.resolve(tape)  # every pulse leaf of the tape in one launch
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         res = simulation.simulate_and_measure(
             tape, n_qubits, type, obs, simulation.uses_density(tape, type), shots=shots, key=key,
@@ -369,6 +370,7 @@ class Script:
                     wrapped.append(Batched(np.moveaxis(np.asarray(a), ax, 0)[start:end]))
             with batch_context(end - start):
                 tape = self._record(*wrapped, **kwargs)
+            pulses.resolve(tape)
             n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
             return simulation.simulate_and_measure(
                 tape, n_qubits, type, obs, simulation.uses_density(tape, type), shots=shots,

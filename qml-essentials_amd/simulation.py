@@ -17,6 +17,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _native as N
+from . import pulses
 from .operations import (_CONJ_NEGATE, Barrier, KrausChannel, Operation, conj_lower, pauli_terms,
                          z_parity_mask)
 
@@ -316,6 +317,7 @@ class LoweredTape:
     """Engine view of a tape: op list, per-slot values, const blob, structure key."""
 
     def __init__(self, tape: Sequence[Operation], n_qubits: int):
+        pulses.resolve(tape)  # (pulse leaves that nobody resolved yet: all of them in one launch)
         self.ops, self.values, blobs, blobs64 = [], [], [], []
         self.ops_periodic = []  # per slot: the gate is 4 pi-periodic in this angle
         h = hashlib.blake2b(digest_size=16)

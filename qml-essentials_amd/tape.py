@@ -2,8 +2,9 @@
 
 Behavioural mirror of ``qml_essentials/tape.py:10-55,92-138``: instantiating an
 ``Operation`` while a ``recording()`` block is active appends it to the innermost
-tape of the current thread.  Pulse-event tapes (``tape.py:58-89``) are out of
-scope (pulse-level simulation is not on the hot path).
+tape of the current thread.  Pulse-level gates (:mod:`pulses`) record on this same
+tape; the pulse-EVENT tapes that feed the reference's pulse-schedule drawing
+(``tape.py:58-89``) are out of scope.
 """
 from __future__ import annotations
 
