@@ -672,6 +672,31 @@ int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int
                          int order, int n_steps, int lanes_per_solve, int out_f64, void *d_out, const void *d_prev,
                          double *d_err, qmle_stream stream);
 
+/* ---- pulse solves with parameter sensitivities (quantum optimal control) ---------------------------------------------
+ * The solves of qmle_pulse_unitaries -- same d_solves, envelopes, modes, frequencies, grids and lane split -- together
+ * with the EXACT derivative of the fixed-grid Magnus result (discretise, then differentiate: neither a finite
+ * difference nor a second ODE).  d_out [n_solves][6][4] row-major complex128:
+ *   slot 0 U;  slots 1..5  dU/dp0, dU/dp1, dU/dp2, dU/dw, dU/dT  (the p2 slot is zero for the two-parameter envelopes).
+ * Per step U <- E(g) U and dU_k <- dE_k U + E dU_k, E = cos r I - i (sin r / r)(gx X + gy Y), r = |g|, with
+ * (cos r - sin r / r) / r^2 from its series for r < 0.05.  The exponents are g = h sum_j a_j c(t_j), h = S / n_steps,
+ * t_j = (s + c_j) h, so that besides the envelope's own partial derivatives
+ *   d/dw  is the coefficient without its factor w (finite and exact at w = 0);
+ *   d/dT  is dh/dT sum_j a_j (c(t_j) + t_j dc/dt(t_j)): the step grows AND the node times move (nothing else depends
+ *         on T: the envelope is centred on the running time).
+ * Conventions for square and cosine, whose grid ends at S = min(T, width): width < T gives dS/dwidth = 1, dS/dT = 0;
+ * otherwise dS/dwidth = 0, dS/dT = 1 -- the tie width == T counts as the T side.  The width derivative therefore has
+ * the grid term dh/dwidth sum_j a_j (c + t dc/dt) beside (cosine) the envelope's own.  Square's amplitude is piecewise
+ * constant in width; its derivative is taken almost everywhere (zero).
+ * A solve with a step whose |gx| + |gy| exceeds 2^15 or is not finite comes back as NaN in all six slots; its
+ * neighbours are untouched.  (A finite U whose envelope has a non-finite partial derivative, sigma = 0 for one, keeps
+ * its U and gets that slot non-finite.)
+ * Status codes as qmle_pulse_unitaries: QMLE_ERR_UNSUPPORTED for order outside {2, 4}, envelope outside 0..4 or mode
+ * outside 0..2; QMLE_ERR_INVALID_ARG for NULL d_solves / d_out, n_solves < 1, n_steps < 1, another lanes_per_solve, a
+ * frequency that is not finite, or n_solves * lanes beyond 2^31 -- all before any device work. */
+int qmle_pulse_unitaries_jac(const double *d_solves, int n_solves, int envelope, int mode, double omega_c,
+                             double omega_q, int order, int n_steps, int lanes_per_solve, void *d_out,
+                             qmle_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

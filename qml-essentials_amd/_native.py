@@ -235,6 +235,7 @@ SYMBOLS = [
     ("qmle_evolve_magnus", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     ("qmle_evolve_lanes", _I, [_I, _I]),
     ("qmle_pulse_unitaries", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
+    ("qmle_pulse_unitaries_jac", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _VP, _VP]),
 ]
 
 
@@ -1012,6 +1013,31 @@ def pulse_unitaries(solves, envelope: str, mode: str, omega_c: float, omega_q: f
         C.c_void_p(out.data_ptr()), C.c_void_p(prev.data_ptr()) if prev is not None else None,
         C.c_void_p(err.data_ptr()) if err is not None else None, _stream_ptr()), "qmle_pulse_unitaries")
     return (out, err) if want_err else out
+
+
+def pulse_unitaries_jac(solves, envelope: str, mode: str, omega_c: float, omega_q: float, order: int, n_steps: int,
+                        lanes_per_solve: int = 0):
+    """The solves of :func:`pulse_unitaries` with their sensitivities in one launch (``qmle_pulse_unitaries_jac``).
+    Returns ``[n, 6, 2, 2]`` complex128 on the device: slot 0 is ``U``, slots 1..5 are its exact grid derivatives by
+    ``p0, p1, p2, w, T`` (the ``p2`` slot is zero for the two-parameter envelopes)."""
+    torch = require_gpu()
+    if envelope not in PULSE_ENVELOPES:
+        raise ValueError(f"pulse_unitaries_jac: unknown envelope {envelope!r}; expected one of {PULSE_ENVELOPES}")
+    if mode not in PULSE_MODES:
+        raise ValueError(f"pulse_unitaries_jac: unknown mode {mode!r}; expected one of {PULSE_MODES}")
+    dev = current_device()
+    if not hasattr(solves, "is_cuda"):
+        solves = torch.from_numpy(np.ascontiguousarray(solves, dtype=np.float64))
+    solves = solves.to(device=dev, dtype=torch.float64).contiguous()
+    if solves.dim() != 2 or solves.shape[1] != 8 or solves.shape[0] < 1:
+        raise ValueError(f"pulse_unitaries_jac: solves must be [n >= 1, 8], got {tuple(solves.shape)}")
+    n = int(solves.shape[0])
+    out = torch.empty((n, 6, 2, 2), dtype=torch.complex128, device=dev)
+    check(lib().qmle_pulse_unitaries_jac(
+        C.c_void_p(solves.data_ptr()), n, PULSE_ENVELOPES.index(envelope), PULSE_MODES.index(mode), float(omega_c),
+        float(omega_q), int(order), int(n_steps), int(lanes_per_solve), C.c_void_p(out.data_ptr()), _stream_ptr()),
+        "qmle_pulse_unitaries_jac")
+    return out
 
 
 @_row_chunked(0)

@@ -448,6 +448,287 @@ __global__ __launch_bounds__(kEvolveThreads) void k_pulse_unitaries(const double
   if (err) err[solve] = worst;
 }
 
+// ---- pulse solves with parameter sensitivities ------------------------------------------------------------------------
+// The same solves with the exact derivative of the grid's result by the five arguments theta = p0, p1, p2, w, T
+// (include/qmle_sv.h has the conventions).  A step's exponent is g = h sum_j a_j c(t_j), t_j = (s + c_j) h, so
+//   dg/dtheta_k = h sum_j a_j dc/dtheta_k (t_j) + dh/dtheta_k sum_j a_j (c(t_j) + t_j dc/dt (t_j)),
+// the second sum -- step length and moving nodes -- for T, or for the width of a square / cosine pulse that ends
+// inside T.  Every lane carries (P, dP_1..5), 48 doubles, for its run of steps.
+constexpr int kJacSlots = 6;  // U and its five derivatives
+
+// e = {env, d env / d p0, d env / d p1, d env / d p2, d env / dt} at time t
+template <int ENV>
+__host__ __device__ __forceinline__ void pulse_envelope_jac(double p0, double p1, double p2, double t, double (&e)[5]) {
+  const double tc = 0.5 * t;  // t - t_c, d tc / dt = 1 / 2
+  e[3] = 0.0;
+  if constexpr (ENV == kEnvGaussian) {
+    const double x = tc / p1, f = exp(-0.5 * (x * x)), g = p0 * f;
+    e[0] = g;
+    e[1] = f;
+    e[2] = g * (x * x) / p1;
+    e[4] = -0.5 * g * x / p1;
+  } else if constexpr (ENV == kEnvSquare) {
+    const double on = fabs(tc) <= 0.5 * p1 ? 1.0 : 0.0;
+    e[0] = p0 * on;
+    e[1] = on;
+    e[2] = e[4] = 0.0;  // piecewise constant: the derivative almost everywhere
+  } else if constexpr (ENV == kEnvCosine) {
+    const double x = tc / p1;
+    double sn, cs;
+    sincos(kPi * fmin(fmax(x, -0.5), 0.5), &sn, &cs);
+    const double dx = fabs(x) <= 0.5 ? -kPi * p0 * sn : 0.0;  // d env / dx; the clipped part is flat
+    e[0] = p0 * cs;
+    e[1] = cs;
+    e[2] = dx * (-x / p1);
+    e[4] = dx * (0.5 / p1);
+  } else if constexpr (ENV == kEnvDrag) {
+    const double x = tc / p2, f = exp(-0.5 * (x * x)), g = p0 * f, u = tc / (p2 * p2), k = 1.0 - p1 * u;
+    e[0] = g + p1 * (g * (-u));
+    e[1] = f * k;
+    e[2] = -g * u;
+    e[3] = g * (x * x) / p2 * k + 2.0 * g * p1 * u / p2;
+    e[4] = 0.5 * (-g * u * k - g * p1 / (p2 * p2));
+  } else {
+    const double u = tc / p1, ex = exp(-fabs(u)), den = fma(ex, ex, 1.0), sech = 2.0 * ex / den;
+    const double th = copysign((1.0 - ex * ex) / den, u);  // tanh u
+    e[0] = p0 * sech;
+    e[1] = sech;
+    e[2] = p0 * sech * th * u / p1;
+    e[4] = -0.5 * p0 * sech * th / p1;
+  }
+}
+
+// the carrier factors (kx, ky) of the X and Y coefficients, c = env k w, and their time derivatives
+template <int MODE>
+__host__ __device__ __forceinline__ void pulse_carrier_jac(const PulseLaunch &L, bool axis_y, double t, double (&k)[2],
+                                                  double (&kt)[2]) {
+#pragma clang fp contract(off)  // (as in pulse_coefficients)
+  if constexpr (MODE == kModeRwa) {
+    k[0] = axis_y ? 0.0 : 0.5;
+    k[1] = axis_y ? 0.5 : 0.0;
+    kt[0] = kt[1] = 0.0;
+  } else if constexpr (MODE == kModeLab) {
+    double sq, cq, sc, cc;
+    sincos_pair(L.omega_q * t, L.omega_c * t + (axis_y ? 0.5 * kPi : 0.0), sq, cq, sc, cc);
+    k[0] = cc * cq;
+    k[1] = -cc * sq;
+    kt[0] = -L.omega_c * sc * cq - L.omega_q * cc * sq;
+    kt[1] = L.omega_c * sc * sq - L.omega_q * cc * cq;
+  } else {
+    const double od = L.omega_c - L.omega_q, os = L.omega_c + L.omega_q;
+    double sd, cd, ss, cs;
+    sincos_pair(od * t, os * t, sd, cd, ss, cs);
+    k[0] = axis_y ? -0.5 * (ss + sd) : 0.5 * (cd + cs);
+    k[1] = axis_y ? -0.5 * (cs - cd) : -0.5 * (ss - sd);
+    kt[0] = axis_y ? -0.5 * (os * cs + od * cd) : -0.5 * (od * sd + os * ss);
+    kt[1] = axis_y ? 0.5 * (os * ss - od * sd) : -0.5 * (os * cs - od * cd);
+  }
+}
+
+// What a node adds to the sums of a step, each an (X, Y) pair: v[0] = m, the coefficient without w (c = m w);
+// v[1..3] = dc / dp0, p1, p2;  v[4] = c + t dc/dt
+template <int ENV, int MODE>
+__host__ __device__ __forceinline__ void pulse_node_jac(const PulseLaunch &L, double p0, double p1, double p2, double w,
+                                               bool axis_y, double t, double (&v)[5][2]) {
+#pragma clang fp contract(off)
+  double e[5], k[2], kt[2];
+  pulse_envelope_jac<ENV>(p0, p1, p2, t, e);
+  pulse_carrier_jac<MODE>(L, axis_y, t, k, kt);
+#pragma unroll
+  for (int a = 0; a < 2; ++a) {
+    v[0][a] = e[0] * k[a];
+    v[1][a] = e[1] * k[a] * w;
+    v[2][a] = e[2] * k[a] * w;
+    v[3][a] = e[3] * k[a] * w;
+    v[4][a] = (v[0][a] + t * (e[4] * k[a] + e[0] * kt[a])) * w;
+  }
+}
+
+// R += A B
+__host__ __device__ __forceinline__ void multiply_add(const CMat<2> &A, const CMat<2> &B, CMat<2> &R) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      double xr = R.re[2 * i + j], xi = R.im[2 * i + j];
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        xr = fma(A.re[2 * i + k], B.re[2 * k + j], xr);
+        xr = fma(-A.im[2 * i + k], B.im[2 * k + j], xr);
+        xi = fma(A.re[2 * i + k], B.im[2 * k + j], xi);
+        xi = fma(A.im[2 * i + k], B.re[2 * k + j], xi);
+      }
+      R.re[2 * i + j] = xr;
+      R.im[2 * i + j] = xi;
+    }
+}
+__host__ __device__ __forceinline__ void set_zero(CMat<2> &R) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) R.re[k] = R.im[k] = 0.0;
+}
+
+struct PulseJac {
+  CMat<2> U, d[5];
+};
+
+// U <- E U and d_k <- dE_k U + E d_k for E = exp(-i (gx X + gy Y)) and the directions (dgx[k], dgy[k]):
+//   E = cos r I - i sinc (gx X + gy Y),  dE = -sinc rho I - i ((kappa rho gx + sinc dgx) X + (kappa rho gy + sinc dgy) Y)
+// with rho = gx dgx + gy dgy and kappa = (cos r - sinc) / r^2, from its series where the difference would cancel.
+// TANGENTS: bit k set = direction k is carried (the others stay zero).  false as pulse_step.
+template <unsigned TANGENTS>
+__host__ __device__ __forceinline__ bool pulse_step_jac(double gx, double gy, const double (&dgx)[5],
+                                               const double (&dgy)[5], PulseJac &J) {
+  const double r2 = gx * gx + gy * gy, r = sqrt(r2);
+  double s, c;
+  sincos(r, &s, &c);
+  const bool small = r < 0.05;
+  const double sinc = small ? 1.0 - r2 * (1.0 / 6.0) * (1.0 - r2 * 0.05 * (1.0 - r2 * (1.0 / 42.0))) : s / r;
+  const double kappa =
+      small ? -1.0 / 3.0 + r2 * (1.0 / 30.0 - r2 * (1.0 / 840.0 - r2 * (1.0 / 45360.0 - r2 * (1.0 / 3991680.0))))
+            : (c - sinc) / r2;
+  CMat<2> E;
+  E.re[0] = E.re[3] = c;
+  E.re[1] = -sinc * gy;
+  E.re[2] = sinc * gy;
+  E.im[0] = E.im[3] = 0.0;
+  E.im[1] = E.im[2] = -sinc * gx;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    if (!(TANGENTS >> k & 1u)) continue;
+    const double rho = gx * dgx[k] + gy * dgy[k];
+    const double vx = fma(kappa * rho, gx, sinc * dgx[k]), vy = fma(kappa * rho, gy, sinc * dgy[k]);
+    CMat<2> dE, R;
+    dE.re[0] = dE.re[3] = -sinc * rho;
+    dE.re[1] = -vy;
+    dE.re[2] = vy;
+    dE.im[0] = dE.im[3] = 0.0;
+    dE.im[1] = dE.im[2] = -vx;
+    set_zero(R);
+    multiply_add(dE, J.U, R);
+    multiply_add(E, J.d[k], R);
+    J.d[k] = R;
+  }
+  multiply_left(E, J.U);
+  return fabs(gx) + fabs(gy) <= kEvolveMaxNorm;
+}
+
+// (P, dP_k) <- (L P, dL_k P + L dP_k) for the later partial product held `delta` lanes up: one tangent is fetched
+// and folded at a time, so that beside the lane's own 48 doubles only L and one dL are alive
+template <unsigned TANGENTS> __device__ __forceinline__ void combine_with_later_jac(PulseJac &J, int delta, int lanes) {
+  CMat<2> Lm;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    Lm.re[k] = __shfl_down(J.U.re[k], delta, lanes);
+    Lm.im[k] = __shfl_down(J.U.im[k], delta, lanes);
+  }
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    if (!(TANGENTS >> t & 1u)) continue;
+    CMat<2> dL, R;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      dL.re[k] = __shfl_down(J.d[t].re[k], delta, lanes);
+      dL.im[k] = __shfl_down(J.d[t].im[k], delta, lanes);
+    }
+    set_zero(R);
+    multiply_add(dL, J.U, R);
+    multiply_add(Lm, J.d[t], R);
+    J.d[t] = R;
+  }
+  multiply_left(Lm, J.U);
+}
+
+// One work item per (solve, lane of the solve), as k_pulse_unitaries.
+template <int ORDER, int ENV, int MODE>
+__global__ __launch_bounds__(kEvolveThreads) void k_pulse_jac(const double *__restrict__ solves,
+                                                                        const PulseLaunch L,
+                                                                        double2 *__restrict__ out) {
+  constexpr unsigned TANGENTS = ENV == kEnvDrag ? 0x1fu : 0x1bu;  // (no p2 without a third envelope parameter)
+  constexpr bool kSupport = ENV == kEnvSquare || ENV == kEnvCosine;
+  const int lanes = L.lanes, n_steps = L.n_steps;
+  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
+  const long long solve_ll = gid / lanes;
+  const int lane = (int)(gid - solve_ll * lanes);
+  const bool live = solve_ll < L.n_solves;
+  const int solve = live ? (int)solve_ll : L.n_solves - 1;
+  const double *__restrict__ q = solves + (size_t)solve * 8;
+  const double p0 = q[0], p1 = q[1], p2 = q[2], w = q[3], T = q[4];
+  const bool axis_y = q[5] != 0.0;
+  const bool width_ends = kSupport && p1 < T;  // the grid ends at the width; a tie counts as T
+  const double span = kSupport ? fmin(T, p1) : T;
+  const double h = span / (double)n_steps, dh = 1.0 / (double)n_steps;
+  const double dh_p1 = width_ends ? dh : 0.0, dh_T = width_ends ? 0.0 : dh;
+  const int s_begin = (int)((long long)lane * n_steps / lanes), s_end = (int)((long long)(lane + 1) * n_steps / lanes);
+  constexpr double kC1 = 0.5 - 0.28867513459481288225, kC2 = 0.5 + 0.28867513459481288225;
+  constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;
+  PulseJac J;
+  set_identity(J.U);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) set_zero(J.d[k]);
+  bool ok = true;
+  for (int s = s_begin; s < s_end; ++s) {
+    double sa[5][2], sb[5][2];  // the weighted node sums of Omega_a and Omega_b (order 2: sa alone)
+    if constexpr (ORDER == 2) {
+      pulse_node_jac<ENV, MODE>(L, p0, p1, p2, w, axis_y, ((double)s + 0.5) * h, sa);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) sa[k][0] = sa[k][1] = sb[k][0] = sb[k][1] = 0.0;
+#pragma nounroll  // (one copy of the transcendental code serves both nodes)
+      for (int node = 0; node < 2; ++node) {
+        double v[5][2];
+        pulse_node_jac<ENV, MODE>(L, p0, p1, p2, w, axis_y, ((double)s + (node ? kC2 : kC1)) * h, v);
+        const double wa = node ? kA2 : kA1, wb = node ? kA1 : kA2;
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+#pragma unroll
+          for (int a = 0; a < 2; ++a) {
+            sa[k][a] = fma(wa, v[k][a], sa[k][a]);
+            sb[k][a] = fma(wb, v[k][a], sb[k][a]);
+          }
+      }
+    }
+#pragma nounroll
+    for (int half = 0; half < (ORDER == 4 ? 2 : 1); ++half) {  // Omega_a first, then Omega_b
+      double g[2], dg[2][5];
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        double m, d0, d1, d2, mv;
+        if (ORDER == 4 && half) m = sb[0][a], d0 = sb[1][a], d1 = sb[2][a], d2 = sb[3][a], mv = sb[4][a];
+        else m = sa[0][a], d0 = sa[1][a], d1 = sa[2][a], d2 = sa[3][a], mv = sa[4][a];
+        g[a] = h * m * w;
+        dg[a][0] = h * d0;
+        dg[a][1] = fma(dh_p1, mv, h * d1);
+        dg[a][2] = h * d2;
+        dg[a][3] = h * m;
+        dg[a][4] = dh_T * mv;
+      }
+      ok &= pulse_step_jac<TANGENTS>(g[0], g[1], dg[0], dg[1], J);
+    }
+  }
+  int bad_run = ok ? 0 : 1;  // (folded beside the products: the p2 slot of a two-parameter envelope is not carried)
+  for (int delta = 1; delta < lanes; delta <<= 1) {
+    combine_with_later_jac<TANGENTS>(J, delta, lanes);
+    bad_run |= __shfl_down(bad_run, delta, lanes);
+  }
+  if (!live || lane != 0) return;
+  if (bad_run) {
+    const double bad = __builtin_nan("");
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      J.U.re[k] = J.U.im[k] = bad;
+#pragma unroll
+      for (int t = 0; t < 5; ++t) J.d[t].re[k] = J.d[t].im[k] = bad;
+    }
+  }
+  double2 *o = out + (size_t)solve * (kJacSlots * 4);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    o[k] = make_double2(J.U.re[k], J.U.im[k]);
+#pragma unroll
+    for (int t = 0; t < 5; ++t) o[4 * (t + 1) + k] = make_double2(J.d[t].re[k], J.d[t].im[k]);
+  }
+}
+
 // lanes_per_row = 0: one lane per row when the rows alone fill the card (256 CUs x 4 SIMDs x 2 waves), else the
 // widest split that stays within that many lanes and leaves every lane at least one step
 int evolve_auto_lanes(int rows, int n_steps) {
@@ -533,6 +814,47 @@ int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int
   const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
 #define QMLE_PULSE_LAUNCH(O, E, M) \
   hipLaunchKernelGGL((k_pulse_unitaries<O, E, M>), grid, block, 0, stream, d_solves, L, d_out, d_prev, d_err)
+#define QMLE_PULSE_MODES(O, E)                       \
+  do {                                               \
+    if (mode == kModeRwa) QMLE_PULSE_LAUNCH(O, E, kModeRwa); \
+    else if (mode == kModeLab) QMLE_PULSE_LAUNCH(O, E, kModeLab); \
+    else QMLE_PULSE_LAUNCH(O, E, kModeDrive);        \
+  } while (0)
+#define QMLE_PULSE_ENVELOPES(O)                                        \
+  switch (envelope) {                                                  \
+    case kEnvGaussian: QMLE_PULSE_MODES(O, kEnvGaussian); break;       \
+    case kEnvSquare: QMLE_PULSE_MODES(O, kEnvSquare); break;           \
+    case kEnvCosine: QMLE_PULSE_MODES(O, kEnvCosine); break;           \
+    case kEnvDrag: QMLE_PULSE_MODES(O, kEnvDrag); break;               \
+    default: QMLE_PULSE_MODES(O, kEnvSech); break;                     \
+  }
+  if (order == 2) QMLE_PULSE_ENVELOPES(2)
+  else QMLE_PULSE_ENVELOPES(4)
+#undef QMLE_PULSE_ENVELOPES
+#undef QMLE_PULSE_MODES
+#undef QMLE_PULSE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int qmle_pulse_unitaries_jac(const double *d_solves, int n_solves, int envelope, int mode, double omega_c,
+                             double omega_q, int order, int n_steps, int lanes_per_solve, void *d_out,
+                             qmle_stream stream_) {
+  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
+  if (envelope < 0 || envelope >= kEnvCount || mode < 0 || mode >= kModeCount) return QMLE_ERR_UNSUPPORTED;
+  if (!d_solves || !d_out || n_solves < 1 || n_steps < 1 || !(fabs(omega_c) <= 1e300) || !(fabs(omega_q) <= 1e300))
+    return QMLE_ERR_INVALID_ARG;
+  if (lanes_per_solve != 0 && lanes_per_solve != 1 && lanes_per_solve != 4 && lanes_per_solve != 16 &&
+      lanes_per_solve != 64)
+    return QMLE_ERR_INVALID_ARG;
+  const int lanes = lanes_per_solve ? lanes_per_solve : evolve_auto_lanes(n_solves, n_steps);
+  const long long items = (long long)n_solves * lanes;
+  if (items > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
+  const PulseLaunch L{envelope, mode, n_solves, n_steps, lanes, 1, omega_c, omega_q};
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
+#define QMLE_PULSE_LAUNCH(O, E, M) \
+  hipLaunchKernelGGL((k_pulse_jac<O, E, M>), grid, block, 0, stream, d_solves, L, (double2 *)d_out)
 #define QMLE_PULSE_MODES(O, E)                       \
   do {                                               \
     if (mode == kModeRwa) QMLE_PULSE_LAUNCH(O, E, kModeRwa); \

@@ -29,9 +29,11 @@ Its optimised default parameters are tuned to exactly this definition, which is 
 The support rule.  ``square`` and ``cosine`` vanish identically for ``t > width``; the grid covers ``[0, min(T,
 width)]`` for them (``[0, T]`` otherwise), so that neither the jump nor the kink falls inside a step.
 
-Gradients are not carried through the solver: a request whose arguments depend on a differentiated leaf has "derivative
-unknown" and ``Script.gradient`` refuses it, as for ``evolve()``.  Out of scope: ``qoc``, pulse-event tapes /
-``draw_pulse``, ``PulseInformation.update_params`` from CSV, ``PauliRot``.
+Gradients are not carried through the solver by ``Script.gradient`` / ``vjp`` / ``Model``: a request whose arguments
+depend on a differentiated leaf has "derivative unknown" and ``Script.gradient`` refuses it, as for ``evolve()``.
+:func:`solve_with_jacobian` returns the solves together with their exact grid sensitivities; :mod:`qoc` composes
+them into the gradients of its cost functions.  Out of scope: pulse-event tapes / ``draw_pulse``,
+``PulseInformation.update_params`` from CSV, ``PauliRot``.
 """
 from __future__ import annotations
 
@@ -44,7 +46,7 @@ import numpy as np
 
 from . import _native as N
 from . import operations as op
-from .batching import Batched, as_param
+from .batching import Batched, as_param, param_tangent
 from .evolution import Evolution, _tangent_state
 from .operations import Operation
 from .unitary import UnitaryGates
@@ -487,6 +489,9 @@ class PulseRotation(Operation):
         self.env_params = [as_param(v) for v in values[:n_env]]
         self.T, self.w = as_param(values[n_env]), as_param(values[n_env + 1])
         self._matrix_tangent = _tangent_state(values)
+        # per argument (envelope parameters..., T, w): the leaf elements it depends on -- what ``qoc`` maps the
+        # columns of the solve's Jacobian onto; ``Script.gradient`` does not read it
+        self._arg_tangents = [param_tangent(v) for v in values]
         self.evolve_steps = None
         super().__init__(wires=wires, record=record, name="R" + axis)
 
@@ -555,6 +560,29 @@ def _launch_all(table: np.ndarray, envelope: str, mode: str, omega_c: float, ome
                 "tolerances")
         U[~ok] = np.nan
     return U, steps
+
+
+def solve_with_jacobian(table: np.ndarray, envelope: str, mode: str, omega_c: float, omega_q: float):
+    """Every solve of ``table`` ``[n, 8]`` with its sensitivities -> ``(U [n, 2, 2], J [n, 5, 2, 2], steps)`` on the
+    host, complex128; ``J[:, k]`` is the derivative of ``U`` by ``p0, p1, p2, w, T`` (``qmle_pulse_unitaries_jac``: the
+    exact derivative of the grid's result, conventions in ``include/qmle_sv.h``).  Under ``magnus2`` / ``magnus4`` the
+    grid has ``magnus_steps`` steps; under an adaptive solver name the step doubling of :func:`_launch_all` chooses
+    the grid by ``U`` and ONE sensitivity launch follows on the accepted grid.  The Jacobian has no error control of
+    its own: it is exact for the grid that ``U`` was accepted on, not bounded against the continuous problem."""
+    atol, rtol, max_steps, throw, solver, magnus_steps = Evolution._options({})
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if solver in ("magnus2", "magnus4"):
+        order, steps = (2 if solver == "magnus2" else 4), magnus_steps
+    else:
+        order = 4
+        accepted, steps = _launch_all(table, envelope, mode, omega_c, omega_q)
+        if steps < 1:  # (max_steps below the first grid and throw off: nothing was accepted)
+            nan = np.full((table.shape[0], 6, 2, 2), np.nan + 0j)
+            return nan[:, 0], nan[:, 1:], steps
+    out = N.pulse_unitaries_jac(table, envelope, mode, omega_c, omega_q, order, steps).cpu().numpy()
+    if solver not in ("magnus2", "magnus4"):
+        out[np.isnan(accepted).any(axis=(1, 2))] = np.nan  # (solves that the doubling rejected, throw off)
+    return out[:, 0].copy(), out[:, 1:].copy(), steps
 
 
 def resolve(tape: Sequence[Operation]) -> int:
