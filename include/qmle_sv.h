@@ -688,8 +688,11 @@ int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int
  * the grid term dh/dwidth sum_j a_j (c + t dc/dt) beside (cosine) the envelope's own.  Square's amplitude is piecewise
  * constant in width; its derivative is taken almost everywhere (zero).
  * A solve with a step whose |gx| + |gy| exceeds 2^15 or is not finite comes back as NaN in all six slots; its
- * neighbours are untouched.  (A finite U whose envelope has a non-finite partial derivative, sigma = 0 for one, keeps
- * its U and gets that slot non-finite.)
+ * neighbours are untouched.  A finite U whose envelope has non-finite partial derivatives keeps its U and gets every
+ * slot that reads one of them non-finite: gaussian or sech with sigma = 0 has the envelope 0 at every node, U = I, and
+ * 0 x inf for the envelope's derivatives by sigma AND by t, so the p1 slot and the T slot (which carries t dc/dt) are
+ * not finite while the p0, p2 and w slots are.  drag with sigma = 0 has 0 x inf in the envelope itself: that solve
+ * fails the norm check and is NaN in all six slots.  T = 0, or width = 0 for square, is finite everywhere with U = I.
  * Status codes as qmle_pulse_unitaries: QMLE_ERR_UNSUPPORTED for order outside {2, 4}, envelope outside 0..4 or mode
  * outside 0..2; QMLE_ERR_INVALID_ARG for NULL d_solves / d_out, n_solves < 1, n_steps < 1, another lanes_per_solve, a
  * frequency that is not finite, or n_solves * lanes beyond 2^31 -- all before any device work. */

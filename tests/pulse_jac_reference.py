@@ -27,7 +27,13 @@ VARIANTS = {
     "one_term_product": "dU <- dE U alone, without E dU",
     "w_ratio": "d/dw as c / w (wrong, and not finite, at w = 0)",
     "drag_dsigma_sign": "the sign of drag's sigma derivative",
+    "lab_kt_swapped": "omega_c and omega_q exchanged in the time derivative of lab's carrier",
+    "drive_no_difference_term": "the (omega_c - omega_q) terms of the time derivative of drive's carrier dropped",
+    "drive_sd_sign": "the sign of sin((omega_c - omega_q) t) in drive's carrier",
 }
+# These three differ from the right scheme at omega_c != omega_q alone (on resonance the term they get wrong is
+# multiplied by an exact zero, or the exchange is of two equal numbers): tests/test_pulse_mp_reference_cpu.py.
+DETUNED_VARIANTS = ("lab_kt_swapped", "drive_no_difference_term", "drive_sd_sign")
 
 
 def variant_applies(name: str, envelope: str, mode: str) -> bool:
@@ -39,7 +45,18 @@ def variant_applies(name: str, envelope: str, mode: str) -> bool:
         return envelope == "square"
     if name == "drag_dsigma_sign":
         return envelope == "drag"
+    if name == "lab_kt_swapped":
+        return mode == "lab"
+    if name in ("drive_no_difference_term", "drive_sd_sign"):
+        return mode == "drive"
     return True
+
+
+def column_scale(ref):
+    """[6]: what a slot's distance is divided by -- 1 for U, max(1, max |column|) for the derivative slots."""
+    s = np.maximum(1.0, np.abs(ref).max(axis=(0, 2, 3)))
+    s[0] = 1.0
+    return s
 
 
 def envelope_jac(envelope: str, p0, p1, p2, t, variant=None):
@@ -79,7 +96,7 @@ def envelope_jac(envelope: str, p0, p1, p2, t, variant=None):
     raise ValueError(envelope)
 
 
-def carrier_jac(mode: str, axis, t, omega_c, omega_q):
+def carrier_jac(mode: str, axis, t, omega_c, omega_q, variant=None):
     """(kx, ky, dkx/dt, dky/dt): c = env k w.  axis: bool [n, 1]."""
     ty = t.dtype.type
     pi, oc, oq = ty(np.pi), ty(omega_c), ty(omega_q)
@@ -89,12 +106,16 @@ def carrier_jac(mode: str, axis, t, omega_c, omega_q):
     if mode == "lab":
         a = oc * t + np.where(axis, pi / 2, ty(0))
         cc, sc, cq, sq = np.cos(a), np.sin(a), np.cos(oq * t), np.sin(oq * t)
-        return cc * cq, -cc * sq, -oc * sc * cq - oq * cc * sq, oc * sc * sq - oq * cc * cq
+        dc, dq = (oq, oc) if variant == "lab_kt_swapped" else (oc, oq)
+        return cc * cq, -cc * sq, -dc * sc * cq - dq * cc * sq, dc * sc * sq - dq * cc * cq
     if mode == "drive":
         od, os_ = oc - oq, oc + oq
         sd, cd, ss, cs = np.sin(od * t), np.cos(od * t), np.sin(os_ * t), np.cos(os_ * t)
-        kx = np.where(axis, -(ss + sd) / 2, (cd + cs) / 2)
-        ky = np.where(axis, -(cs - cd) / 2, -(ss - sd) / 2)
+        sk = -sd if variant == "drive_sd_sign" else sd
+        kx = np.where(axis, -(ss + sk) / 2, (cd + cs) / 2)
+        ky = np.where(axis, -(cs - cd) / 2, -(ss - sk) / 2)
+        if variant == "drive_no_difference_term":
+            od = ty(0)
         kxt = np.where(axis, -(os_ * cs + od * cd) / 2, -(od * sd + os_ * ss) / 2)
         kyt = np.where(axis, (os_ * ss - od * sd) / 2, -(os_ * cs - od * cd) / 2)
         return kx, ky, kxt, kyt
@@ -147,7 +168,7 @@ def scheme_jac(envelope: str, mode: str, solves, order: int, n_steps: int, lanes
     for off in offs:
         t = (steps + off) * h  # [n, steps]
         e0, e1, e2, e3, e4 = envelope_jac(envelope, p0, p1, p2, t, variant)
-        kx, ky, kxt, kyt = carrier_jac(mode, axis, t, omega_c, omega_q)
+        kx, ky, kxt, kyt = carrier_jac(mode, axis, t, omega_c, omega_q, variant)
         v = {}
         for a, (k, kt) in enumerate(((kx, kxt), (ky, kyt))):
             m = e0 * k

@@ -23,10 +23,16 @@ VARIANTS = {
     "drag_sign": "the derivative term of drag added with the opposite sign",
     "ry_phase": "RY without the carrier phase +pi/2 (exact forms)",
     "full_span": "the grid over [0, T] for square / cosine instead of their support [0, min(T, width)]",
+    "drive_sd_sign": "the sign of sin((omega_c - omega_q) t) in the product-to-sum form (drive, off resonance)",
 }
 
 
 def variant_applies(name: str, envelope: str, mode: str, axis: int, solve) -> bool:
+    """Whether the variant changes this solve AT THE DEFAULT FREQUENCIES (omega_c = omega_q)."""
+    if name == "drive_sd_sign":
+        # sin(0 t) = 0: exactly invisible on resonance.  tests/test_pulse_mp_reference_cpu.py tells it apart at
+        # omega_c != omega_q.
+        return False
     if name == "drag_sign":
         return envelope == "drag"
     if name == "ry_phase":
@@ -86,8 +92,9 @@ def coefficients(envelope: str, mode: str, solve, t, omega_c=OMEGA, omega_q=OMEG
     elif mode == "drive":
         od, os_ = omega_c - omega_q, omega_c + omega_q
         y = axis & phase_on
-        mx = np.where(y, -0.5 * (np.sin(os_ * t) + np.sin(od * t)), 0.5 * (np.cos(od * t) + np.cos(os_ * t)))
-        my = np.where(y, -0.5 * (np.cos(os_ * t) - np.cos(od * t)), -0.5 * (np.sin(os_ * t) - np.sin(od * t)))
+        sd = -np.sin(od * t) if variant == "drive_sd_sign" else np.sin(od * t)
+        mx = np.where(y, -0.5 * (np.sin(os_ * t) + sd), 0.5 * (np.cos(od * t) + np.cos(os_ * t)))
+        my = np.where(y, -0.5 * (np.cos(os_ * t) - np.cos(od * t)), -0.5 * (np.sin(os_ * t) - sd))
         cx, cy = env * mx * w, env * my * w
     else:
         raise ValueError(mode)

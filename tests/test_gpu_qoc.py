@@ -14,6 +14,7 @@ import pytest
 
 import pulse_jac_reference as PJ
 import pulse_reference as P
+from pulse_jac_reference import column_scale
 from qml_essentials_amd import _native as N
 from qml_essentials_amd import pulses, qoc, utils
 from qml_essentials_amd.evolution import Evolution
@@ -34,13 +35,6 @@ def _default_state():
     Evolution._solver_defaults.update(prev)
     PulseInformation.reset_defaults()
     utils.enable_x64(False)
-
-
-def column_scale(ref):
-    """[6]: 1 for U, max(1, max |column|) for the derivative slots."""
-    s = np.maximum(1.0, np.abs(ref).max(axis=(0, 2, 3)))
-    s[0] = 1.0
-    return s
 
 
 def jac(solves, envelope, mode, order, steps, lanes=0):

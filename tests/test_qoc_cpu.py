@@ -102,9 +102,10 @@ def test_lane_splits_change_rounding_only(envelope):
                 assert (np.abs(split - J) / scale).max() <= 1e-13, (mode, order, lanes)
 
 
-@pytest.mark.parametrize("variant", sorted(PJ.VARIANTS))
+@pytest.mark.parametrize("variant", sorted(set(PJ.VARIANTS) - set(PJ.DETUNED_VARIANTS)))
 def test_every_wrong_variant_is_told_apart(variant):
-    """By at least 100 x the bar of the cross-check above, in the slot that the variant gets wrong."""
+    """By at least 100 x the bar of the cross-check above, in the slot that the variant gets wrong.  (The variants that
+    show at omega_c != omega_q alone: tests/test_pulse_mp_reference_cpu.py.)"""
     slot = {"no_node_shift": 5, "no_span_width": 2, "one_term_product": None, "w_ratio": 4, "drag_dsigma_sign": 3}[variant]
     seen = 0
     for envelope in P.ENVELOPES:
