@@ -700,6 +700,73 @@ int qmle_pulse_unitaries_jac(const double *d_solves, int n_solves, int envelope,
                              double omega_q, int order, int n_steps, int lanes_per_solve, void *d_out,
                              qmle_stream stream);
 
+/* ---- composition of small circuits (quantum optimal control: the evaluator's product rule on the device) ------------
+ * Many circuits on 1 or 2 wires (d = 2 or 4) for n_candidates candidates in ONE launch, float64 / complex128.  Per
+ * circuit k and candidate c:  U = I, dU_p = 0 (p < n_params), and for every op of the circuit in table order
+ *     dU_p <- M dU_p + dM_p U  (every p),   U <- M U.
+ * The three structure tables and the row indices are HOST arrays: the library validates every index they hold, then
+ * copies them into the caller's device workspace on the stream.  The value pools are DEVICE arrays with their lengths.
+ *   qmle_compose_circuit  op_begin..op_end: its ops; n_wires 1 or 2; n_params P_k >= 0; target_off: offset of its
+ *       target V_k (d x d row-major) in d_targets, or -1; ov_off / dov_off: where ov[c] and dov[c][p] go in d_ov;
+ *       u_off / du_off: where U[c][d][d] and dU[c][p][d][d] go in d_full.  All offsets count complex128 elements.
+ *       The output blocks (ov, dov, U, dU of every circuit) must not overlap one another: checked.
+ *   qmle_compose_op  kind:
+ *       CONST   M from d_mats, no derivative (no terms allowed);
+ *       PULSE   M = slot 0 and the derivatives slots 1..5 of row rows[mat_off + c] of d_jac, the result
+ *               [n_solves][6][4] of the sensitivity entry point above (mat_off indexes `rows` here; mat_stride unused);
+ *       ROT_X / ROT_Y / ROT_Z   M from d_mats, generator derivative (-i/2) sigma M;
+ *       CPHASE  M from d_mats (4 x 4), generator derivative i |11><11| M.
+ *     For the kinds that read d_mats the matrix of candidate c is at mat_off + c * mat_stride (stride 0: shared).
+ *     placement: 0 the wire of a 1-wire circuit; 1 wire 0 of 2; 2 wire 1 of 2; 3 wires [0, 1]; 4 wires [1, 0] (wire 0
+ *     is the most significant).  PULSE and ROT_* are 2 x 2 (placements 0..2), CPHASE is 4 x 4 (3, 4), CONST either.
+ *     term_begin..term_end: its tangent terms.
+ *   qmle_compose_term  the op's derivative by parameter `param` gains d_coefs[coef_off + c] x (slot 1 + `slot` of the
+ *       row for PULSE, slot in 0..4 | the generator derivative for ROT_* and CPHASE, slot 0).  Several terms of one op
+ *       may name one parameter; a parameter may occur in many ops or in none (its column is then zero).
+ * Outputs (either may be NULL, not both):
+ *   d_ov    for every circuit with a target, with bit j of column_mask selecting column j:
+ *           ov[c] = sum_{j in mask} sum_i conj(V[i][j]) U[i][j], dov[c][p] the same sum over dU_p.  Circuits without a
+ *           target write nothing there.
+ *   d_full  U and dU of every circuit.
+ * One lane per (circuit, candidate, p or "U only", column): columns are summed in a fixed order between neighbouring
+ * lanes, no atomics -- results are bit-reproducible and do not depend on n_candidates.  A NaN row of d_jac reaches
+ * only the outputs of the (circuit, candidate) pairs that read it.
+ * d_workspace: at least what the second function returns, 16-byte aligned.
+ * Lifetime of the host tables: they are copied by asynchronous host-to-device copies on `stream`.  From ordinary
+ * (pageable) memory the HIP runtime stages the source before the copy call returns, so such tables may be changed or
+ * freed as soon as this function returns; the library's own lane table relies on the same property.  Tables in
+ * page-locked (hipHostMalloc / registered) memory are read when the stream reaches the copy and must stay unchanged
+ * until then.
+ * QMLE_ERR_UNSUPPORTED for n_wires outside {1, 2}, an unknown kind or placement; QMLE_ERR_WORKSPACE for a workspace
+ * that is missing or too small; QMLE_ERR_INVALID_ARG for NULL tables, n_circuits < 1, n_candidates < 1, both outputs
+ * NULL, column_mask without a bit below 4 -- or, with d_ov, without a bit below d of a circuit that has a target --, output
+ * blocks that overlap, any op / term / matrix / coefficient / row / target / output range outside its
+ * table or pool, a row index >= n_solves, a placement that does not fit the circuit's n_wires or the kind's size, terms on
+ * a CONST op, a slot outside the kind's range, param >= n_params, a pool that is needed and NULL, or more than 2^31
+ * lanes -- all before any device work. */
+enum { QMLE_COMPOSE_CONST = 0, QMLE_COMPOSE_PULSE = 1, QMLE_COMPOSE_ROT_X = 2, QMLE_COMPOSE_ROT_Y = 3,
+       QMLE_COMPOSE_ROT_Z = 4, QMLE_COMPOSE_CPHASE = 5 };
+typedef struct {
+  int32_t op_begin, op_end, n_wires, n_params;
+  int64_t target_off, ov_off, dov_off, u_off, du_off;
+} qmle_compose_circuit;
+typedef struct {
+  int32_t kind, placement;
+  int64_t mat_off, mat_stride;
+  int32_t term_begin, term_end;
+} qmle_compose_op;
+typedef struct {
+  int32_t slot, param;
+  int64_t coef_off;
+} qmle_compose_term;
+int qmle_compose_circuits(const qmle_compose_circuit *circuits, int n_circuits, const qmle_compose_op *ops, int n_ops,
+                          const qmle_compose_term *terms, int n_terms, const int32_t *rows, int64_t n_rows,
+                          int n_candidates, const void *d_mats, int64_t n_mats, const double *d_coefs, int64_t n_coefs,
+                          const void *d_targets, int64_t n_targets, const void *d_jac, int n_solves,
+                          unsigned column_mask, void *d_ov, int64_t ov_len, void *d_full, int64_t full_len,
+                          void *d_workspace, size_t workspace_bytes, qmle_stream stream);
+size_t qmle_compose_workspace_bytes(int n_circuits, int n_ops, int n_terms, int64_t n_rows);
+
 #ifdef __cplusplus
 }
 #endif

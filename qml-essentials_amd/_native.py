@@ -236,6 +236,9 @@ SYMBOLS = [
     ("qmle_evolve_lanes", _I, [_I, _I]),
     ("qmle_pulse_unitaries", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     ("qmle_pulse_unitaries_jac", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _VP, _VP]),
+    ("qmle_compose_circuits", _I, [_VP, _I, _VP, _I, _VP, _I, _VP, C.c_int64, _I, _VP, C.c_int64, _VP, C.c_int64, _VP,
+                                   C.c_int64, _VP, _I, C.c_uint, _VP, C.c_int64, _VP, C.c_int64, _VP, _SZ, _VP]),
+    ("qmle_compose_workspace_bytes", _SZ, [_I, _I, _I, C.c_int64]),
 ]
 
 
@@ -1038,6 +1041,55 @@ def pulse_unitaries_jac(solves, envelope: str, mode: str, omega_c: float, omega_
         float(omega_q), int(order), int(n_steps), int(lanes_per_solve), C.c_void_p(out.data_ptr()), _stream_ptr()),
         "qmle_pulse_unitaries_jac")
     return out
+
+
+# qmle_compose_circuits: the structure tables as numpy records (the layout of the structs in include/qmle_sv.h)
+COMPOSE_KINDS = {"CONST": 0, "PULSE": 1, "ROT_X": 2, "ROT_Y": 3, "ROT_Z": 4, "CPHASE": 5}
+COMPOSE_CIRCUIT = np.dtype([("op_begin", "<i4"), ("op_end", "<i4"), ("n_wires", "<i4"), ("n_params", "<i4"),
+                            ("target_off", "<i8"), ("ov_off", "<i8"), ("dov_off", "<i8"), ("u_off", "<i8"),
+                            ("du_off", "<i8")])
+COMPOSE_OP = np.dtype([("kind", "<i4"), ("placement", "<i4"), ("mat_off", "<i8"), ("mat_stride", "<i8"),
+                       ("term_begin", "<i4"), ("term_end", "<i4")])
+COMPOSE_TERM = np.dtype([("slot", "<i4"), ("param", "<i4"), ("coef_off", "<i8")])
+
+
+def compose_circuits(circuits, ops, terms, rows, n_candidates: int, mats, coefs, targets, jac, column_mask: int,
+                     ov_len: int = 0, full_len: int = 0):
+    """Compose many 1- and 2-wire circuits for ``n_candidates`` candidates in one launch (``qmle_compose_circuits``,
+    conventions in ``include/qmle_sv.h``).  ``circuits`` / ``ops`` / ``terms``: host records of
+    :data:`COMPOSE_CIRCUIT` / :data:`COMPOSE_OP` / :data:`COMPOSE_TERM`; ``rows``: host int32.  ``mats``, ``coefs``,
+    ``targets``, ``jac`` ``[n_solves, 6, 2, 2]``: the value pools, host arrays (uploaded) or CUDA tensors, ``None`` for
+    a pool that nothing reads.  Returns ``(ov, full)``: flat complex128 CUDA tensors of ``ov_len`` / ``full_len``
+    elements laid out by the circuits' offsets, ``None`` for a length of 0."""
+    torch = require_gpu()
+    dev = current_device()
+    circuits = np.ascontiguousarray(circuits, dtype=COMPOSE_CIRCUIT)
+    ops = np.ascontiguousarray(ops, dtype=COMPOSE_OP)
+    terms = np.ascontiguousarray(terms, dtype=COMPOSE_TERM)
+    rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+
+    def pool(x, dtype):
+        if x is None:
+            return None
+        if not hasattr(x, "is_cuda"):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.complex128 if dtype.is_complex else np.float64))
+        return x.to(device=dev, dtype=dtype).contiguous().reshape(-1)
+
+    mats, targets, jac = (pool(x, torch.complex128) for x in (mats, targets, jac))
+    coefs = pool(coefs, torch.float64)
+    ov = torch.empty((ov_len,), dtype=torch.complex128, device=dev) if ov_len else None
+    full = torch.empty((full_len,), dtype=torch.complex128, device=dev) if full_len else None
+    need = lib().qmle_compose_workspace_bytes(len(circuits), len(ops), len(terms), len(rows))
+    workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+    host = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    count = lambda t: int(t.numel()) if t is not None else 0  # noqa: E731
+    check(lib().qmle_compose_circuits(
+        host(circuits), len(circuits), host(ops), len(ops), host(terms), len(terms), host(rows), len(rows),
+        int(n_candidates), ptr(mats), count(mats), ptr(coefs), count(coefs), ptr(targets), count(targets), ptr(jac),
+        count(jac) // 24, int(column_mask), ptr(ov), int(ov_len), ptr(full), int(full_len), ptr(workspace),
+        int(workspace.numel()), _stream_ptr()), "qmle_compose_circuits")
+    return ov, full
 
 
 @_row_chunked(0)

@@ -6,7 +6,9 @@
 // with A(t) = -i sum_i c_i(t) H_i.  The kernel evaluates no coefficient function: it reads c_i at the node times from
 // a table coef[row][node][term], in node order.  float64 throughout; the result is rounded once when it is stored as
 // complex64.  k_pulse_unitaries (further down) solves the RX / RY leaves of pulse-level gates on the same grids with
-// the same work split, but evaluates its two coefficients itself instead of reading a table.
+// the same work split, but evaluates its two coefficients itself instead of reading a table.  k_compose_circuits (last)
+// multiplies such 2x2 results and constant gates into the unitaries of 1- and 2-wire circuits with their parameter
+// derivatives: its own comment block.
 //
 // Work split.  A row's steps are cut into `lanes` contiguous runs (1, 4, 16 or 64 neighbouring lanes of one wave).
 // Every lane forms the ordered product of its run from the identity; the partial products are then multiplied in
@@ -25,6 +27,9 @@
 // m = ceil(nu / 0.5) equal parts (m = 1 on any grid that resolves the pulse) and each part's series runs until the
 // bound (nu / m)^k / k! of the next term falls below 1e-19, at most 24 terms: the count follows from the norm, decided
 // before the first product, never from the iterates.  Rows whose nu is not finite or exceeds 2^15 come back as NaN.
+#include <algorithm>
+#include <vector>
+
 #include "qmle_host.h"
 #include "qmle_dev.h"
 
@@ -729,6 +734,205 @@ __global__ __launch_bounds__(kEvolveThreads) void k_pulse_jac(const double *__re
   }
 }
 
+// ---- composition of small circuits ------------------------------------------------------------------------------------
+// The product rule of qoc.circuit_unitaries on the device: per circuit and candidate U = I, dU_p = 0 and per op
+// dU_p <- M dU_p + dM_p U, U <- M U.  Left multiplication acts on every column on its own and dU_p needs only U and
+// itself, so ONE lane carries column j of U and of ONE dU_p (or of none: the "U only" lane q = 0) -- 2 x DIM complex
+// numbers -- and recomputes its U column beside the P other lanes that hold the same one.  The lanes of a circuit are
+// ordered (candidate, q, column) with the column fastest and every circuit starts at a multiple of 4 lanes, so the DIM
+// lanes of one (candidate, q) are neighbours inside a wave: the column sum of the overlap is DIM lane reads in a fixed
+// order.  A lane's parameter selects its tangent terms by comparison and select (lanes of different p share a wave);
+// what branches is the op's kind and placement, which every lane of a circuit shares.  DIM is a template parameter
+// and every loop over matrix entries is unrolled: no private array is indexed at run time.
+struct ComposeLaunch {
+  const qmle_compose_circuit *circuits;
+  const qmle_compose_op *ops;
+  const qmle_compose_term *terms;
+  const int32_t *rows;
+  const long long *lane_begin;  // [n_circuits + 1], multiples of 4
+  const double2 *mats;
+  const double *coefs;
+  const double2 *targets;
+  const double2 *jac;
+  double2 *ov, *full;
+  int n_circuits, n_candidates;
+  unsigned column_mask;
+};
+
+// acc += a b
+__device__ __forceinline__ void cfma(const double2 a, const double2 b, double2 &acc) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(-a.y, b.y, acc.x);
+  acc.y = fma(a.x, b.y, acc.y);
+  acc.y = fma(a.y, b.x, acc.y);
+}
+__device__ __forceinline__ double2 cselect(bool take, const double2 a, const double2 b) {
+  return make_double2(take ? a.x : b.x, take ? a.y : b.y);
+}
+
+template <int DIM>
+__device__ __forceinline__ void compose_lane(const ComposeLaunch &L, const qmle_compose_circuit K, int c, int q, int j,
+                                             bool live) {
+  const int p = q - 1, P = K.n_params;
+  const double2 zero = make_double2(0.0, 0.0);
+  double2 u[DIM], du[DIM];
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    u[i] = make_double2(i == j ? 1.0 : 0.0, 0.0);
+    du[i] = zero;
+  }
+  for (int oi = K.op_begin; oi < K.op_end; ++oi) {
+    const qmle_compose_op o = L.ops[oi];
+    const bool pulse = o.kind == QMLE_COMPOSE_PULSE;
+    const double2 *__restrict__ mp =
+        pulse ? L.jac + (size_t)L.rows[o.mat_off + c] * (kJacSlots * 4) : L.mats + (o.mat_off + (long long)c * o.mat_stride);
+    const bool has_terms = o.term_end > o.term_begin;
+    if (DIM == 4 && (o.placement == 1 || o.placement == 4)) {  // the other wire order: exchange |01> and |10>
+      const double2 a = u[1 % DIM], b = du[1 % DIM];
+      u[1 % DIM] = u[2 % DIM], u[2 % DIM] = a;
+      du[1 % DIM] = du[2 % DIM], du[2 % DIM] = b;
+    }
+    if (DIM == 2 || o.placement <= 2) {  // a 2 x 2 matrix on one wire (of DIM = 4: on the pairs (0, 1) and (2, 3))
+      double2 m[4], dm[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) m[k] = mp[k], dm[k] = zero;
+      if (has_terms) {
+        if (pulse) {
+          for (int t = o.term_begin; t < o.term_end; ++t) {
+            const qmle_compose_term T = L.terms[t];
+            const bool mine = T.param == p;
+            const double w = L.coefs[T.coef_off + c];
+            const double2 *__restrict__ g = mp + 4 * (1 + T.slot);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const double2 v = g[k];
+              dm[k].x += mine ? w * v.x : 0.0;
+              dm[k].y += mine ? w * v.y : 0.0;
+            }
+          }
+        } else {  // (-i/2) sigma M, weighted by the sum of this lane's coefficients
+          double w = 0.0;
+          for (int t = o.term_begin; t < o.term_end; ++t) {
+            const qmle_compose_term T = L.terms[t];
+            w += T.param == p ? L.coefs[T.coef_off + c] : 0.0;
+          }
+          const double h = 0.5 * w;
+          if (o.kind == QMLE_COMPOSE_ROT_X) {  // -i/2 (m1; m0)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              dm[k] = make_double2(h * m[2 + k].y, -h * m[2 + k].x);
+              dm[2 + k] = make_double2(h * m[k].y, -h * m[k].x);
+            }
+          } else if (o.kind == QMLE_COMPOSE_ROT_Y) {  // 1/2 (-m1; m0)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              dm[k] = make_double2(-h * m[2 + k].x, -h * m[2 + k].y);
+              dm[2 + k] = make_double2(h * m[k].x, h * m[k].y);
+            }
+          } else {  // i/2 (-m0; m1)
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              dm[k] = make_double2(h * m[k].y, -h * m[k].x);
+              dm[2 + k] = make_double2(-h * m[2 + k].y, h * m[2 + k].x);
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int b = 0; b < DIM; b += 2) {
+        double2 n0 = zero, n1 = zero, d0 = zero, d1 = zero;
+        cfma(m[0], du[b], d0), cfma(m[1], du[b + 1], d0);
+        cfma(m[2], du[b], d1), cfma(m[3], du[b + 1], d1);
+        if (has_terms) {
+          cfma(dm[0], u[b], d0), cfma(dm[1], u[b + 1], d0);
+          cfma(dm[2], u[b], d1), cfma(dm[3], u[b + 1], d1);
+        }
+        cfma(m[0], u[b], n0), cfma(m[1], u[b + 1], n0);
+        cfma(m[2], u[b], n1), cfma(m[3], u[b + 1], n1);
+        u[b] = n0, u[b + 1] = n1, du[b] = d0, du[b + 1] = d1;
+      }
+    } else if constexpr (DIM == 4) {  // a 4 x 4 matrix on both wires
+      double2 m[16], nu[4], nd[4];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) m[k] = mp[k];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) {
+        nu[a] = nd[a] = zero;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) cfma(m[4 * a + b], u[b], nu[a]), cfma(m[4 * a + b], du[b], nd[a]);
+      }
+      if (has_terms) {  // CPHASE: i |11><11| M, weighted: row 3 alone
+        double w = 0.0;
+        for (int t = o.term_begin; t < o.term_end; ++t) {
+          const qmle_compose_term T = L.terms[t];
+          w += T.param == p ? L.coefs[T.coef_off + c] : 0.0;
+        }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) cfma(make_double2(-w * m[12 + b].y, w * m[12 + b].x), u[b], nd[3]);
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a) u[a] = nu[a], du[a] = nd[a];
+    }
+    if (DIM == 4 && (o.placement == 1 || o.placement == 4)) {
+      const double2 a = u[1 % DIM], b = du[1 % DIM];
+      u[1 % DIM] = u[2 % DIM], u[2 % DIM] = a;
+      du[1 % DIM] = du[2 % DIM], du[2 % DIM] = b;
+    }
+  }
+  const bool u_lane = q == 0;
+  // the overlap with the target: this lane's column, then the DIM columns in index order
+  const bool with_target = K.target_off >= 0 && L.ov != nullptr;
+  double2 part = zero;
+  if (with_target) {
+    const double2 *__restrict__ V = L.targets + K.target_off;
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      const double2 v = V[i * DIM + j];
+      cfma(make_double2(v.x, -v.y), cselect(u_lane, u[i], du[i]), part);
+    }
+  }
+  part = cselect((L.column_mask >> j & 1u) != 0, part, zero);
+  const int first = (int)(threadIdx.x & (kWave - 1)) - j;
+  double2 sum = zero;
+#pragma unroll
+  for (int k = 0; k < DIM; ++k) {
+    sum.x += __shfl(part.x, first + k);
+    sum.y += __shfl(part.y, first + k);
+  }
+  if (!live) return;
+  if (with_target && j == 0) {
+    if (u_lane) L.ov[K.ov_off + c] = sum;
+    else L.ov[K.dov_off + (long long)c * P + p] = sum;
+  }
+  if (L.full != nullptr) {
+    double2 *__restrict__ out =
+        L.full + (u_lane ? K.u_off + (long long)c * (DIM * DIM) : K.du_off + ((long long)c * P + p) * (DIM * DIM));
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) out[i * DIM + j] = cselect(u_lane, u[i], du[i]);
+  }
+}
+
+__global__ __launch_bounds__(kEvolveThreads) void k_compose_circuits(const ComposeLaunch L) {
+  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
+  int lo = 0, hi = L.n_circuits;  // the circuit k with lane_begin[k] <= gid < lane_begin[k + 1] (the last one past the end)
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (L.lane_begin[mid] <= gid) lo = mid;
+    else hi = mid;
+  }
+  const qmle_compose_circuit K = L.circuits[lo];
+  const int dim = 1 << K.n_wires;
+  const long long local = gid - L.lane_begin[lo];
+  const int j = (int)(local & (dim - 1));
+  const long long item = local / dim;
+  const int q = (int)(item % (K.n_params + 1));
+  const long long c_ll = item / (K.n_params + 1);
+  const bool live = c_ll < L.n_candidates;  // (padding lanes redo the last candidate and store nothing)
+  const int c = live ? (int)c_ll : L.n_candidates - 1;
+  if (dim == 2) compose_lane<2>(L, K, c, q, j, live);
+  else compose_lane<4>(L, K, c, q, j, live);
+}
+
 // lanes_per_row = 0: one lane per row when the rows alone fill the card (256 CUs x 4 SIMDs x 2 waves), else the
 // widest split that stays within that many lanes and leaves every lane at least one step
 int evolve_auto_lanes(int rows, int n_steps) {
@@ -874,6 +1078,125 @@ int qmle_pulse_unitaries_jac(const double *d_solves, int n_solves, int envelope,
 #undef QMLE_PULSE_ENVELOPES
 #undef QMLE_PULSE_MODES
 #undef QMLE_PULSE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+size_t qmle_compose_workspace_bytes(int n_circuits, int n_ops, int n_terms, int64_t n_rows) {
+  if (n_circuits < 1 || n_ops < 0 || n_terms < 0 || n_rows < 0) return 0;
+  return align_up((size_t)n_circuits * sizeof(qmle_compose_circuit), 16) +
+         align_up((size_t)n_ops * sizeof(qmle_compose_op), 16) + align_up((size_t)n_terms * sizeof(qmle_compose_term), 16) +
+         align_up((size_t)n_rows * sizeof(int32_t), 16) + align_up((size_t)(n_circuits + 1) * sizeof(long long), 16);
+}
+
+int qmle_compose_circuits(const qmle_compose_circuit *circuits, int n_circuits, const qmle_compose_op *ops, int n_ops,
+                          const qmle_compose_term *terms, int n_terms, const int32_t *rows, int64_t n_rows,
+                          int n_candidates, const void *d_mats, int64_t n_mats, const double *d_coefs, int64_t n_coefs,
+                          const void *d_targets, int64_t n_targets, const void *d_jac, int n_solves,
+                          unsigned column_mask, void *d_ov, int64_t ov_len, void *d_full, int64_t full_len,
+                          void *d_workspace, size_t workspace_bytes, qmle_stream stream_) {
+  // every index a lane dereferences is checked here, against the table or pool it points into
+  if (!circuits || n_circuits < 1 || n_candidates < 1 || n_ops < 0 || n_terms < 0 || n_rows < 0 || (n_ops && !ops) ||
+      (n_terms && !terms) || (n_rows && !rows) || n_mats < 0 || n_coefs < 0 || n_targets < 0 || n_solves < 0 ||
+      ov_len < 0 || full_len < 0 || (!d_ov && !d_full) || !(column_mask & 0xfu))
+    return QMLE_ERR_INVALID_ARG;
+  const long long C = n_candidates;
+  constexpr long long kMaxParams = 1 << 20;
+  // [off, off + len) inside a pool of n elements
+  auto inside = [](long long off, long long len, long long n) { return off >= 0 && len >= 0 && off <= n && len <= n - off; };
+  for (int64_t r = 0; r < n_rows; ++r)
+    if (rows[r] < 0 || rows[r] >= n_solves) return QMLE_ERR_INVALID_ARG;
+  for (int i = 0; i < n_ops; ++i) {
+    const qmle_compose_op &o = ops[i];
+    if (o.kind < QMLE_COMPOSE_CONST || o.kind > QMLE_COMPOSE_CPHASE || o.placement < 0 || o.placement > 4)
+      return QMLE_ERR_UNSUPPORTED;
+  }
+  for (int i = 0; i < n_ops; ++i) {
+    const qmle_compose_op &o = ops[i];
+    const bool wide = o.placement >= 3;
+    const bool pulse = o.kind == QMLE_COMPOSE_PULSE;
+    if ((pulse || (o.kind >= QMLE_COMPOSE_ROT_X && o.kind <= QMLE_COMPOSE_ROT_Z)) && wide) return QMLE_ERR_INVALID_ARG;
+    if (o.kind == QMLE_COMPOSE_CPHASE && !wide) return QMLE_ERR_INVALID_ARG;
+    if (pulse) {
+      if (!d_jac || !inside(o.mat_off, C, n_rows)) return QMLE_ERR_INVALID_ARG;
+    } else {
+      const long long size = wide ? 16 : 4;
+      if (!d_mats || o.mat_stride < 0 || (o.mat_stride > 0 && C - 1 > n_mats / o.mat_stride) || !inside(o.mat_off, (C - 1) * o.mat_stride + size, n_mats))
+        return QMLE_ERR_INVALID_ARG;
+    }
+    if (!inside(o.term_begin, (long long)o.term_end - o.term_begin, n_terms)) return QMLE_ERR_INVALID_ARG;
+    if (o.kind == QMLE_COMPOSE_CONST && o.term_end != o.term_begin) return QMLE_ERR_INVALID_ARG;
+    for (int t = o.term_begin; t < o.term_end; ++t) {
+      const qmle_compose_term &T = terms[t];
+      if (T.slot < 0 || T.slot > (pulse ? 4 : 0) || T.param < 0 || !d_coefs || !inside(T.coef_off, C, n_coefs))
+        return QMLE_ERR_INVALID_ARG;
+    }
+  }
+  std::vector<long long> lane_begin((size_t)n_circuits + 1);
+  std::vector<std::pair<long long, long long>> ov_ranges, full_ranges;  // [begin, end) of every output block
+  long long lanes = 0;
+  for (int k = 0; k < n_circuits; ++k) {
+    const qmle_compose_circuit &K = circuits[k];
+    if (K.n_wires != 1 && K.n_wires != 2) return QMLE_ERR_UNSUPPORTED;
+    const long long d = 1ll << K.n_wires, P = K.n_params;
+    if (P < 0 || P > kMaxParams || !inside(K.op_begin, (long long)K.op_end - K.op_begin, n_ops)) return QMLE_ERR_INVALID_ARG;
+    if (K.target_off != -1 && (!d_targets || !inside(K.target_off, d * d, n_targets))) return QMLE_ERR_INVALID_ARG;
+    if (d_ov && K.target_off != -1) {
+      if (!inside(K.ov_off, C, ov_len) || !inside(K.dov_off, C * P, ov_len)) return QMLE_ERR_INVALID_ARG;
+      if (!(column_mask & ((1u << d) - 1u))) return QMLE_ERR_INVALID_ARG;  // no column of this circuit selected
+      ov_ranges.emplace_back(K.ov_off, K.ov_off + C);
+      if (P) ov_ranges.emplace_back(K.dov_off, K.dov_off + C * P);
+    }
+    if (d_full) {
+      if (!inside(K.u_off, C * d * d, full_len) || !inside(K.du_off, C * P * d * d, full_len)) return QMLE_ERR_INVALID_ARG;
+      full_ranges.emplace_back(K.u_off, K.u_off + C * d * d);
+      if (P) full_ranges.emplace_back(K.du_off, K.du_off + C * P * d * d);
+    }
+    for (int i = K.op_begin; i < K.op_end; ++i) {
+      const qmle_compose_op &o = ops[i];
+      if ((o.placement == 0) != (K.n_wires == 1)) return QMLE_ERR_INVALID_ARG;
+      for (int t = o.term_begin; t < o.term_end; ++t)
+        if (terms[t].param >= P) return QMLE_ERR_INVALID_ARG;
+    }
+    lane_begin[k] = lanes;
+    lanes += align_up((size_t)(C * (P + 1) * d), 4);
+    if (lanes > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
+  }
+  lane_begin[n_circuits] = lanes;
+  for (auto *ranges : {&ov_ranges, &full_ranges}) {  // two lanes must never store to one element
+    std::sort(ranges->begin(), ranges->end());
+    for (size_t i = 1; i < ranges->size(); ++i)
+      if ((*ranges)[i].first < (*ranges)[i - 1].second) return QMLE_ERR_INVALID_ARG;
+  }
+  const size_t need = qmle_compose_workspace_bytes(n_circuits, n_ops, n_terms, n_rows);
+  if (!d_workspace || workspace_bytes < need || ((uintptr_t)d_workspace & 15u)) return QMLE_ERR_WORKSPACE;
+
+  // the tables travel as asynchronous copies from pageable memory, which the runtime stages before the copy call
+  // returns (as the term tables of the Pauli entry points; the header states what that asks of the caller)
+  hipStream_t stream = (hipStream_t)stream_;
+  char *at = (char *)d_workspace;
+  auto upload = [&](const void *src, size_t bytes, const void **dst) -> hipError_t {
+    *dst = at;
+    at += align_up(bytes, 16);
+    return bytes ? hipMemcpyAsync((void *)*dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess;
+  };
+  ComposeLaunch L{};
+  HIPCHK(upload(circuits, (size_t)n_circuits * sizeof(qmle_compose_circuit), (const void **)&L.circuits));
+  HIPCHK(upload(ops, (size_t)n_ops * sizeof(qmle_compose_op), (const void **)&L.ops));
+  HIPCHK(upload(terms, (size_t)n_terms * sizeof(qmle_compose_term), (const void **)&L.terms));
+  HIPCHK(upload(rows, (size_t)n_rows * sizeof(int32_t), (const void **)&L.rows));
+  HIPCHK(upload(lane_begin.data(), lane_begin.size() * sizeof(long long), (const void **)&L.lane_begin));
+  L.mats = (const double2 *)d_mats;
+  L.coefs = d_coefs;
+  L.targets = (const double2 *)d_targets;
+  L.jac = (const double2 *)d_jac;
+  L.ov = (double2 *)d_ov;
+  L.full = (double2 *)d_full;
+  L.n_circuits = n_circuits;
+  L.n_candidates = n_candidates;
+  L.column_mask = column_mask;
+  hipLaunchKernelGGL(k_compose_circuits, dim3(grid_for((uint64_t)lanes, kEvolveThreads)), dim3(kEvolveThreads), 0, stream,
+                     L);
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }

@@ -562,26 +562,42 @@ def _launch_all(table: np.ndarray, envelope: str, mode: str, omega_c: float, ome
     return U, steps
 
 
-def solve_with_jacobian(table: np.ndarray, envelope: str, mode: str, omega_c: float, omega_q: float):
+def solve_with_jacobian(table: np.ndarray, envelope: str, mode: str, omega_c: float, omega_q: float,
+                        on_device: bool = False):
     """Every solve of ``table`` ``[n, 8]`` with its sensitivities -> ``(U [n, 2, 2], J [n, 5, 2, 2], steps)`` on the
     host, complex128; ``J[:, k]`` is the derivative of ``U`` by ``p0, p1, p2, w, T`` (``qmle_pulse_unitaries_jac``: the
     exact derivative of the grid's result, conventions in ``include/qmle_sv.h``).  Under ``magnus2`` / ``magnus4`` the
     grid has ``magnus_steps`` steps; under an adaptive solver name the step doubling of :func:`_launch_all` chooses
     the grid by ``U`` and ONE sensitivity launch follows on the accepted grid.  The Jacobian has no error control of
-    its own: it is exact for the grid that ``U`` was accepted on, not bounded against the continuous problem."""
+    its own: it is exact for the grid that ``U`` was accepted on, not bounded against the continuous problem.
+    ``on_device=True`` returns ``(result [n, 6, 4] complex128 on the device, steps)`` instead -- slot 0 ``U``, slots
+    1..5 ``J``, the layout ``qmle_compose_circuits`` reads -- without a copy to the host; the rejected solves of the
+    adaptive path are masked there."""
     atol, rtol, max_steps, throw, solver, magnus_steps = Evolution._options({})
     table = np.ascontiguousarray(table, dtype=np.float64)
+    n = table.shape[0]
     if solver in ("magnus2", "magnus4"):
         order, steps = (2 if solver == "magnus2" else 4), magnus_steps
     else:
         order = 4
         accepted, steps = _launch_all(table, envelope, mode, omega_c, omega_q)
         if steps < 1:  # (max_steps below the first grid and throw off: nothing was accepted)
-            nan = np.full((table.shape[0], 6, 2, 2), np.nan + 0j)
+            if on_device:
+                torch = N.require_gpu()
+                return torch.full((n, 6, 4), float("nan"), dtype=torch.complex128, device=N.current_device()), steps
+            nan = np.full((n, 6, 2, 2), np.nan + 0j)
             return nan[:, 0], nan[:, 1:], steps
-    out = N.pulse_unitaries_jac(table, envelope, mode, omega_c, omega_q, order, steps).cpu().numpy()
+    out = N.pulse_unitaries_jac(table, envelope, mode, omega_c, omega_q, order, steps)
+    rejected = None
     if solver not in ("magnus2", "magnus4"):
-        out[np.isnan(accepted).any(axis=(1, 2))] = np.nan  # (solves that the doubling rejected, throw off)
+        rejected = np.isnan(accepted).any(axis=(1, 2))  # (solves that the doubling rejected, throw off)
+    if on_device:
+        if rejected is not None and rejected.any():
+            out[N.require_gpu().from_numpy(rejected).to(out.device)] = float("nan")
+        return out.reshape(n, 6, 4), steps
+    out = out.cpu().numpy()
+    if rejected is not None:
+        out[rejected] = np.nan
     return out[:, 0].copy(), out[:, 1:].copy(), steps
 
 

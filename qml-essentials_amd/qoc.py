@@ -25,8 +25,16 @@ All candidates of a stage-0 scan step and all restarts of a stage-1 step advance
 The optimiser is AdamW with optax's defaults, global-norm clipping per candidate row and the warmup-cosine schedule,
 written out in NumPy; parameters optimised in log space use ``d/d log p = p d/dp``.
 
-Not included: ``joint_unitary_cost_fn``, ``optimize_joint``, ``optimize_all``, plots, the command line,
-``profile_pulse_pipeline``, ``create_CPhase``; derivatives inside ``Script.gradient`` / ``vjp`` / ``Model``.
+Composition on the device (``compose="device"``).  Steps 3 and 4 also exist as one launch of
+``qmle_compose_circuits``: :func:`_compose_tables` turns the recorded tapes of any number of jobs into a circuit, an op
+and a tangent-term table, the solver's ``[n, 6, 4]`` result stays on the device, and only overlaps (the cost
+functions) or matrices (:func:`circuit_unitaries`) come back -- :data:`COMPOSE_LAUNCHES` counts these launches.  The
+per-gate entry points default to ``"host"``; the joint path (:func:`joint_unitary_cost_fn`, ``QOC.optimize_joint``:
+one shared leaf vector against the weighted unitary costs of several target gates) defaults to ``"device"`` with the
+default solver and evaluates all its gates with one solver call and one composition launch.
+
+Not included: plots, the command line, ``profile_pulse_pipeline``; derivatives inside ``Script.gradient`` / ``vjp`` /
+``Model``.
 """
 from __future__ import annotations
 
@@ -52,6 +60,7 @@ from .utils import as_key
 log = logging.getLogger(__name__)
 
 LAUNCH_GROUPS = 0  # calls of the solver since import (one per evaluation and launch group)
+COMPOSE_LAUNCHES = 0  # launches of qmle_compose_circuits since import (one per evaluation with compose="device")
 
 _PAULI = {"X": np.array([[0, 1], [1, 0]], dtype=np.complex128), "Y": np.array([[0, -1j], [1j, 0]]),
           "Z": np.array([[1, 0], [0, -1]], dtype=np.complex128)}
@@ -120,15 +129,242 @@ def _op_matrices(o: Operation, solved: Optional[tuple], n_params: int, C: int):
     return m, d_m
 
 
+def _check_compose(compose: str) -> str:
+    if compose not in ("host", "device"):
+        raise ValueError(f"compose must be 'host' or 'device', got {compose!r}")
+    return compose
+
+
+class _ComposeTables:
+    """The tables of ``qmle_compose_circuits`` for a list of jobs, and the solve table of every launch group."""
+
+    def __init__(self, C: int):
+        from . import _native as N
+
+        self.N, self.C = N, C
+        self.circuits, self.ops, self.terms, self.rows = [], [], [], []
+        self.mats, self.coefs, self.targets = [], [], []
+        self._n_mats = self._n_coefs = self._n_targets = 0
+        self._mat_at: Dict[bytes, int] = {}
+        self._coef_at: Dict = {}
+        self.groups: Dict[tuple, list] = {}   # launch group -> [(row offset of the op, its solves [1 or C, 8])]
+        self.index: List[List[List[int]]] = []  # [job][script][angle] -> circuit
+        self.ov_len = self.full_len = 0
+
+    def matrix(self, m: np.ndarray) -> Tuple[int, int]:
+        """(offset, per-candidate stride) of ``m`` ``[k, k]`` or ``[1 or C, k, k]`` in the matrix pool."""
+        m = np.ascontiguousarray(m, dtype=np.complex128)
+        if m.ndim == 3 and m.shape[0] == 1:
+            m = m[0]
+        if m.ndim == 3 and m.shape[0] != self.C:
+            raise ValueError(f"qoc: a matrix batch of {m.shape[0]} does not fit {self.C} candidates")
+        key = m.tobytes()
+        if key not in self._mat_at:
+            self._mat_at[key] = self._n_mats
+            self.mats.append(m.reshape(-1))
+            self._n_mats += m.size
+        return self._mat_at[key], (m.shape[-1] * m.shape[-2] if m.ndim == 3 else 0)
+
+    def coef(self, coef: np.ndarray) -> int:
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64).reshape(-1), (self.C,)))
+        key = float(coef[0]) if (coef == coef[0]).all() else coef.tobytes()
+        if key not in self._coef_at:
+            self._coef_at[key] = self._n_coefs
+            self.coefs.append(coef)
+            self._n_coefs += self.C
+        return self._coef_at[key]
+
+    def target(self, V: Optional[np.ndarray]) -> int:
+        if V is None:
+            return -1
+        V = np.ascontiguousarray(V, dtype=np.complex128).reshape(-1)
+        self.targets.append(V)
+        self._n_targets += V.size
+        return self._n_targets - V.size
+
+    def add_op(self, o: Operation, n: int) -> None:
+        wires = list(o.wires)
+        if n == 1 and wires == [0]:
+            placement = 0
+        elif n == 2 and wires in ([0], [1], [0, 1], [1, 0]):
+            placement = {(0,): 1, (1,): 2, (0, 1): 3, (1, 0): 4}[tuple(wires)]
+        else:
+            raise NotImplementedError(f"qoc evaluates circuits on 1 or 2 wires; got wires {wires} of {n}")
+        kinds, t0, terms = self.N.COMPOSE_KINDS, len(self.terms), []
+        if isinstance(o, PulseRotation):
+            kind, stride, at = kinds["PULSE"], 0, len(self.rows)
+            solves = o.solves()
+            self.rows.append(None)  # (filled in once the launch group's table is known)
+            self.groups.setdefault(o.group(), []).append((at, solves))
+            slots = list(range(len(o.env_params))) + [_SLOT_T, _SLOT_W]
+            for slot, tans in zip(slots, o._arg_tangents):
+                terms += [(slot, index, coef) for _, index, coef in _tangent_terms(tans, f"an argument of {o!r}")]
+            at *= self.C
+        else:
+            for name, tans in o.__dict__.get("_tangents", {}).items():
+                terms += [(0, index, coef) for _, index, coef in _tangent_terms(tans, f"{name} of {o!r}")]
+            if not terms:
+                kind = kinds["CONST"]
+            elif isinstance(o, _Rotation):
+                kind = kinds["ROT_" + o._axis]
+            elif isinstance(o, ControlledPhaseShift):
+                kind = kinds["CPHASE"]
+            else:
+                raise NotImplementedError(f"qoc: no derivative rule for {o!r} with parameters that depend on the pulse "
+                                          "parameters")
+            at, stride = self.matrix(o.matrix)
+        for slot, index, coef in terms:
+            self.terms.append((slot, int(index), self.coef(coef)))
+        self.ops.append((kind, placement, at, stride, t0, len(self.terms)))
+
+    def add_circuit(self, tape: Sequence[Operation], n: int, P: int, V: Optional[np.ndarray]) -> int:
+        b, d, C = len(self.ops), 2 ** n, self.C
+        for o in tape:
+            self.add_op(o, n)
+        ov, dov = self.ov_len, self.ov_len + C
+        u, du = self.full_len, self.full_len + C * d * d
+        self.ov_len += C * (1 + P)
+        self.full_len += C * (1 + P) * d * d
+        self.circuits.append((b, len(self.ops), n, P, self.target(V), ov, dov, u, du))
+        return len(self.circuits) - 1
+
+    def solve_tables(self):
+        """-> [(launch group, its table of distinct solves)]; fills ``rows`` with indices into the tables stacked in
+        that order."""
+        out, base = [], 0
+        for key, requests in self.groups.items():
+            table, inverse = np.unique(np.concatenate([s for _, s in requests]), axis=0, return_inverse=True)
+            inverse = np.asarray(inverse).reshape(-1)
+            at = 0
+            for slot, solves in requests:
+                idx = inverse[at:at + len(solves)] + base
+                at += len(solves)
+                self.rows[slot] = np.broadcast_to(idx, (self.C,)).astype(np.int32)
+            out.append((key, table))
+            base += len(table)
+        return out
+
+    def arrays(self):
+        N = self.N
+        cat = lambda parts, dtype: np.concatenate(parts) if parts else np.zeros(0, dtype=dtype)  # noqa: E731
+        return (np.array(self.circuits, dtype=N.COMPOSE_CIRCUIT), np.array(self.ops, dtype=N.COMPOSE_OP),
+                np.array(self.terms, dtype=N.COMPOSE_TERM), cat(self.rows, np.int32), cat(self.mats, np.complex128),
+                cat(self.coefs, np.float64), cat(self.targets, np.complex128))
+
+
+def _record_tapes(scripts: Sequence[Script], ws: np.ndarray, pulse_params: Optional[np.ndarray], C: int):
+    tapes = []
+    for script in scripts:
+        per_angle = []
+        for w in ws:
+            with batch_context(C):
+                tape = (script._record(float(w), Batched.leaf(pulse_params, 0)) if pulse_params is not None
+                        else script._record(float(w)))
+            per_angle.append([o for o in tape if not isinstance(o, Barrier)])
+        tapes.append(per_angle)
+    return tapes
+
+
+def _n_wires(script: Script, per_angle) -> int:
+    return script._n_qubits or 1 + max(w for tape in per_angle for o in tape for w in o.wires)
+
+
+def _compose_tables(jobs: Sequence[tuple], ws: np.ndarray) -> _ComposeTables:
+    """Record the tapes of every job ``(scripts, pulse_params [C, P_g])`` or ``(scripts, pulse_params, targets)`` --
+    ``targets[i]`` ``[S, d, d]`` the target unitaries of script i -- at the angles ``ws`` and emit ONE set of tables:
+    a circuit per (job, script, angle), every pulse request of every job in one solve table per launch group."""
+    C = int(np.asarray(jobs[0][1]).shape[0])
+    tab = _ComposeTables(C)
+    for job in jobs:
+        scripts, pp = job[0], np.asarray(job[1], dtype=np.float64)
+        targets = job[2] if len(job) > 2 else None
+        if pp.ndim != 2 or pp.shape[0] != C:
+            raise ValueError(f"qoc: every job needs pulse_params [{C}, P], got shape {pp.shape}")
+        per_script = []
+        for i, (script, per_angle) in enumerate(zip(scripts, _record_tapes(scripts, ws, pp, C))):
+            n = _n_wires(script, per_angle)
+            per_script.append([tab.add_circuit(tape, n, pp.shape[1], None if targets is None else targets[i][s])
+                               for s, tape in enumerate(per_angle)])
+        tab.index.append(per_script)
+    return tab
+
+
+def _solve_tables(tab: _ComposeTables, solver: Optional[Callable]) -> list:
+    """ONE solver call per launch group of ``tab`` -> the groups' ``[n, 6, 4]`` results in the order that ``tab.rows``
+    indexes: device tensors from the default solver, host arrays from an injected one."""
+    global LAUNCH_GROUPS
+    parts = []
+    for (envelope, mode, omega_c, omega_q), table in tab.solve_tables():
+        LAUNCH_GROUPS += 1
+        if solver is None:
+            parts.append(pulses.solve_with_jacobian(table, envelope, mode, omega_c, omega_q, on_device=True)[0])
+        else:
+            U, J, _ = solver(table, envelope, mode, omega_c, omega_q)
+            host = np.concatenate([np.asarray(U)[:, None], np.asarray(J)], axis=1).reshape(len(table), 6, 4)
+            parts.append(np.ascontiguousarray(host, dtype=np.complex128))
+    return parts
+
+
+def _compose_on_device(tab: _ComposeTables, solver: Optional[Callable], column_mask: int, want_ov: bool,
+                       want_full: bool):
+    """Solve every launch group of ``tab`` (:func:`_solve_tables`; an injected solver's host result is uploaded) and
+    compose in ONE launch.  -> (ov, full) host arrays or None."""
+    global COMPOSE_LAUNCHES
+    N = tab.N
+    torch = N.require_gpu()
+    parts = [x if hasattr(x, "is_cuda") else torch.from_numpy(x).to(N.current_device())
+             for x in _solve_tables(tab, solver)]
+    jac = None if not parts else (parts[0] if len(parts) == 1 else torch.cat(parts))
+    circuits, ops, terms, rows, mats, coefs, targets = tab.arrays()
+    COMPOSE_LAUNCHES += 1
+    ov, full = N.compose_circuits(circuits, ops, terms, rows, tab.C, mats if mats.size else None,
+                                  coefs if coefs.size else None, targets if targets.size else None, jac, column_mask,
+                                  ov_len=tab.ov_len if want_ov else 0, full_len=tab.full_len if want_full else 0)
+    return (None if ov is None else N.to_host(ov)), (None if full is None else N.to_host(full))
+
+
+def _overlaps_on_device(jobs: Sequence[tuple], ws: np.ndarray, solver: Optional[Callable], column_mask: int):
+    """For jobs ``(scripts, pulse_params, targets)``: per job and script ``(ov [C, S], dov [C, S, P])``, the overlaps
+    ``sum_{j in mask} sum_i conj(V[i][j]) U[i][j]`` of :func:`_compose_on_device`."""
+    tab = _compose_tables(jobs, ws)
+    ov, _ = _compose_on_device(tab, solver, column_mask, True, False)
+    C, out = tab.C, []
+    for job, per_script in zip(jobs, tab.index):
+        P = np.asarray(job[1]).shape[1]
+        res = []
+        for ids in per_script:
+            at = [tab.circuits[k][5] for k in ids]
+            res.append((np.stack([ov[a:a + C] for a in at], axis=1),
+                        np.stack([ov[a + C:a + C * (1 + P)].reshape(C, P) for a in at], axis=1)))
+        out.append(res)
+    return out
+
+
 def circuit_unitaries(scripts: Sequence[Script], ws: np.ndarray, pulse_params: Optional[np.ndarray],
-                      solver: Optional[Callable] = None) -> List[Tuple[np.ndarray, Optional[np.ndarray]]]:
+                      solver: Optional[Callable] = None, compose: str = "host"
+                      ) -> List[Tuple[np.ndarray, Optional[np.ndarray]]]:
     """The unitaries of ``scripts`` at the rotation angles ``ws`` ``[S]``.  With ``pulse_params`` ``[C, P]`` a script
     is called as ``f(w, pulse_params)`` and gives ``(U [C, S, d, d], dU [C, S, P, d, d])``; with ``None`` it is
     called as ``f(w)`` and gives ``(U [S, d, d], None)``.  Every pulse solve of the call goes through ONE call of
-    ``solver(table, envelope, mode, omega_c, omega_q) -> (U, J, steps)`` per launch group."""
+    ``solver(table, envelope, mode, omega_c, omega_q) -> (U, J, steps)`` per launch group.  ``compose``: ``"host"``
+    composes in NumPy, ``"device"`` in one launch of ``qmle_compose_circuits`` (circuits without pulse parameters
+    have nothing to differentiate and are composed on the host either way)."""
     global LAUNCH_GROUPS
-    solver = pulses.solve_with_jacobian if solver is None else solver
+    _check_compose(compose)
     ws = np.asarray(ws, dtype=np.float64).reshape(-1)
+    if compose == "device" and pulse_params is not None:
+        pulse_params = np.asarray(pulse_params, dtype=np.float64)
+        (C, P), S = pulse_params.shape, len(ws)
+        tab = _compose_tables([(scripts, pulse_params)], ws)
+        _, full = _compose_on_device(tab, solver, 1, False, True)
+        out = []
+        for ids in tab.index[0]:
+            d = 2 ** tab.circuits[ids[0]][2]
+            U = np.stack([full[tab.circuits[k][7]:][:C * d * d].reshape(C, d, d) for k in ids], axis=1)
+            dU = np.stack([full[tab.circuits[k][8]:][:C * P * d * d].reshape(C, P, d, d) for k in ids], axis=1)
+            out.append((U, dU.reshape(C, S, P, d, d)))
+        return out
+    solver = pulses.solve_with_jacobian if solver is None else solver
     with_pp = pulse_params is not None
     if with_pp:
         pulse_params = np.asarray(pulse_params, dtype=np.float64)
@@ -238,7 +474,7 @@ def _overlap_losses(ov: np.ndarray, dov: np.ndarray, scale: float):
 
 
 def fidelity_cost_fn(pulse_params, pulse_scripts, target_scripts, n_samples: int, value_and_grad: bool = False,
-                     solver: Optional[Callable] = None):
+                     solver: Optional[Callable] = None, compose: str = "host"):
     """``(1 - fidelity, 1 - cos(phase difference))`` of the states that the pulse and the target circuits prepare from
     ``|0..0>``, averaged over the rotation angles and over the (pulse, target) script pairs (``qoc.py:171-256``)."""
     if not isinstance(pulse_scripts, (list, tuple)):
@@ -250,13 +486,18 @@ def fidelity_cost_fn(pulse_params, pulse_scripts, target_scripts, n_samples: int
         f"{len(target_scripts)}).")
     params, single = _candidates(pulse_params)
     ws = _sample_rotation_angles(n_samples)
-    pulse = circuit_unitaries(pulse_scripts, ws, params, solver)
     target = circuit_unitaries(target_scripts, ws, None, solver)
     values, grads = [], []
-    for (U, dU), (V, _) in zip(pulse, target):
-        psi, dpsi, phi = U[..., 0], dU[..., 0], V[..., 0]  # the columns of |0..0>
-        ov = np.einsum("csd,sd->cs", np.conj(psi), phi)
-        dov = np.einsum("cspd,sd->csp", np.conj(dpsi), phi)
+    if _check_compose(compose) == "device":  # <phi|psi> from the kernel's column 0; this cost reads <psi|phi>
+        (overlaps,) = _overlaps_on_device([(pulse_scripts, params, [V for V, _ in target])], ws, solver, 0b1)
+        overlaps = [(np.conj(ov), np.conj(dov)) for ov, dov in overlaps]
+    else:
+        overlaps = []
+        for (U, dU), (V, _) in zip(circuit_unitaries(pulse_scripts, ws, params, solver), target):
+            psi, dpsi, phi = U[..., 0], dU[..., 0], V[..., 0]  # the columns of |0..0>
+            overlaps.append((np.einsum("csd,sd->cs", np.conj(psi), phi),
+                             np.einsum("cspd,sd->csp", np.conj(dpsi), phi)))
+    for ov, dov in overlaps:
         v, g = _overlap_losses(ov, dov, 1.0)
         values.append(v)
         grads.append(g)
@@ -265,7 +506,8 @@ def fidelity_cost_fn(pulse_params, pulse_scripts, target_scripts, n_samples: int
 
 
 def unitary_cost_fn(pulse_params, pulse_basis_scripts, target_basis_scripts, n_samples: int, n_qubits: int,
-                    value_and_grad: bool = False, solver: Optional[Callable] = None):
+                    value_and_grad: bool = False, solver: Optional[Callable] = None, compose: str = "host",
+                    target_unitaries: Optional[np.ndarray] = None):
     """``(1 - |Tr E|^2 / d^2, 1 - cos(angle(Tr E)))`` for ``E = U_target^+ U_pulse``, averaged over the rotation
     angles (``qoc.py:259-341``); column k of a unitary is the state that the k-th basis script gives.  Scripts that
     :func:`_with_basis_prep` built from ONE circuit (what :meth:`QOC.optimize` passes) prepare ``|k>`` and apply that
@@ -281,17 +523,120 @@ def unitary_cost_fn(pulse_params, pulse_basis_scripts, target_basis_scripts, n_s
 
     def unitaries(scripts, pp):
         if _one_circuit_with_basis_preps(scripts, n_qubits):
-            return circuit_unitaries(scripts[:1], ws, pp, solver)[0]
-        cols = circuit_unitaries(scripts, ws, pp, solver)  # column 0 of script k is column k
+            return circuit_unitaries(scripts[:1], ws, pp, solver, compose)[0]
+        cols = circuit_unitaries(scripts, ws, pp, solver, compose)  # column 0 of script k is column k
         U = np.stack([u[..., 0] for u, _ in cols], axis=-1)
         return U, (np.stack([du[..., 0] for _, du in cols], axis=-1) if pp is not None else None)
 
-    U, dU = unitaries(pulse_basis_scripts, params)
-    V, _ = unitaries(target_basis_scripts, None)
-    tr = np.einsum("sji,csji->cs", np.conj(V), U)
-    dtr = np.einsum("sji,cspji->csp", np.conj(V), dU)
+    _check_compose(compose)
+    # (the targets do not depend on the pulse parameters: a caller that evaluates often may pass them, [S, d, d])
+    V = unitaries(target_basis_scripts, None)[0] if target_unitaries is None else np.asarray(target_unitaries)
+    if compose == "device" and _one_circuit_with_basis_preps(pulse_basis_scripts, n_qubits):
+        tr, dtr = _overlaps_on_device([(pulse_basis_scripts[:1], params, [V])], ws, solver, (1 << d) - 1)[0][0]
+    else:
+        U, dU = unitaries(pulse_basis_scripts, params)
+        tr = np.einsum("sji,csji->cs", np.conj(V), U)
+        dtr = np.einsum("sji,cspji->csp", np.conj(V), dU)
     values, grads = _overlap_losses(tr, dtr, float(d) ** 2)
     return _result(values, grads, single, value_and_grad)
+
+
+class _JointAssembler:
+    """``theta -> the flat pulse parameters of one gate`` (``QOC._assemble_for_gate`` as an index map): parameter k of
+    the gate is ``theta[..., gather[k]]``, or the constant ``frozen[k]`` of a leaf outside the joint vector where
+    ``gather[k] == -1``.  ``scatter`` is its transpose: per-gate gradients ``[C, P_g]`` added into ``[C, T]``."""
+
+    def __init__(self, pp_obj, leaf_slices: Dict[str, slice]):
+        gather, frozen = [], []
+
+        def walk(node):
+            if not node.is_leaf:
+                for child in node.childs:
+                    walk(child)
+                return
+            sl = leaf_slices.get(node.name)
+            values = np.asarray(node.params, dtype=np.float64).reshape(-1)
+            gather.extend([-1] * len(values) if sl is None else range(sl.start, sl.stop))
+            frozen.extend(values if sl is None else [0.0] * (sl.stop - sl.start))
+
+        walk(pp_obj)
+        self.gather, self.frozen = np.array(gather, dtype=np.int64), np.array(frozen, dtype=np.float64)
+
+    def __call__(self, theta):
+        theta = np.asarray(theta, dtype=np.float64)
+        live = self.gather >= 0
+        return np.where(live, theta[..., np.where(live, self.gather, 0)], self.frozen)
+
+    def scatter(self, grads: np.ndarray, n_theta: int) -> np.ndarray:
+        grads = np.asarray(grads, dtype=np.float64)
+        out = np.zeros(grads.shape[:-1] + (n_theta,), dtype=np.float64)
+        for k, at in enumerate(self.gather):  # (in parameter order: a tied element sums its members')
+            if at >= 0:
+                out[..., at] += grads[..., k]
+        return out
+
+
+def _target_unitaries(scripts, ws: np.ndarray, n_qubits: int) -> np.ndarray:
+    """``[S, d, d]``: column k from basis script k (all from script 0 when the scripts are basis preparations of one
+    circuit)."""
+    if _one_circuit_with_basis_preps(scripts, n_qubits):
+        return circuit_unitaries(scripts[:1], ws, None)[0][0]
+    return np.stack([u[..., 0] for u, _ in circuit_unitaries(scripts, ws, None)], axis=-1)
+
+
+def _spec_targets(spec: dict, n_samples: int) -> np.ndarray:
+    """The target unitaries ``[S, d, d]`` of a joint spec at the ``n_samples`` rotation angles: the spec's optional
+    entry ``"target_unitaries": (n_samples, V)`` (what ``QOC._joint_specs`` computes once) when it is for these
+    angles, else computed here.  The spec is not modified."""
+    given = spec.get("target_unitaries")
+    if given is not None and given[0] == n_samples:
+        return given[1]
+    return _target_unitaries(spec["target_basis_scripts"], _sample_rotation_angles(n_samples), spec["n_qubits"])
+
+
+def joint_unitary_cost_fn(pulse_params, gate_specs: List[dict], n_samples: int, value_and_grad: bool = False,
+                          solver: Optional[Callable] = None, compose: Optional[str] = None):
+    """The unitary cost of several target gates that share the joint leaf vector ``theta`` (``qoc.py:344-403``): both
+    components are ``sum_g w_g loss_g / sum_g w_g``.  A spec is ``{"name", "n_qubits", "weight", "assembler",
+    "pulse_basis_scripts", "target_basis_scripts"}`` and optionally ``"target_unitaries": (n_samples, V [S, d, d])``,
+    the targets computed ahead (they do not depend on ``theta``; both routes use them); the assembler maps ``theta``
+    ``[T]`` or ``[C, T]`` to the gate's flat parameters.  Gradients need an assembler that exposes its index map (``scatter``, see
+    :class:`_JointAssembler`): the gradient by ``theta`` is the scatter-add of the per-gate gradients.  ``compose``:
+    ``"device"`` (the default with the default solver) evaluates ALL gates with one solver call per launch group and
+    one composition launch; ``"host"`` (the default with an injected solver) one gate after the other in NumPy."""
+    theta, single = _candidates(pulse_params)
+    compose = _check_compose(compose if compose is not None else ("device" if solver is None else "host"))
+    if value_and_grad and not all(hasattr(spec["assembler"], "scatter") for spec in gate_specs):
+        raise NotImplementedError("joint_unitary_cost_fn: a gradient needs assemblers that expose their index map "
+                                  "(the specs of QOC.optimize_joint do); a plain callable cannot be differentiated")
+    per_gate = [np.asarray(spec["assembler"](theta), dtype=np.float64) for spec in gate_specs]
+    parts = []  # per gate ((process, phase) [C], their gradients [C, P_g])
+    if compose == "device" and gate_specs and all(
+            _one_circuit_with_basis_preps(spec["pulse_basis_scripts"], spec["n_qubits"]) for spec in gate_specs):
+        ws = _sample_rotation_angles(n_samples)
+        jobs = []
+        for spec, pp in zip(gate_specs, per_gate):
+            jobs.append((spec["pulse_basis_scripts"][:1], pp, [_spec_targets(spec, n_samples)]))
+        for spec, res in zip(gate_specs, _overlaps_on_device(jobs, ws, solver, 0xf)):
+            parts.append(_overlap_losses(res[0][0], res[0][1], float(2 ** spec["n_qubits"]) ** 2))
+    else:
+        for spec, pp in zip(gate_specs, per_gate):
+            parts.append(unitary_cost_fn(pp, spec["pulse_basis_scripts"], spec["target_basis_scripts"], n_samples,
+                                         spec["n_qubits"], value_and_grad=True, solver=solver, compose=compose,
+                                         target_unitaries=_spec_targets(spec, n_samples)))
+    C, T = theta.shape
+    values, grads = [np.zeros(C), np.zeros(C)], [np.zeros((C, T)), np.zeros((C, T))]
+    total_w = 0.0
+    for spec, (v, g) in zip(gate_specs, parts):
+        w = float(spec["weight"])
+        total_w += w
+        for k in range(2):
+            values[k] = values[k] + w * v[k]
+            if value_and_grad:
+                grads[k] = grads[k] + w * spec["assembler"].scatter(g[k], T)
+    if total_w > 0:
+        values, grads = [v / total_w for v in values], [g / total_w for g in grads]
+    return _result(tuple(values), tuple(grads), single, value_and_grad)
 
 
 def pulse_width_cost_fn(pulse_params, envelope: str, value_and_grad: bool = False):
@@ -422,9 +767,12 @@ class CostFnRegistry:
 
     _REGISTRY: Dict[str, dict] = {
         "fidelity": {"fn": fidelity_cost_fn, "default_weight": (0.5, 0.5),
-                     "ckwargs_keys": ["pulse_scripts", "target_scripts", "n_samples", "solver"]},
+                     "ckwargs_keys": ["pulse_scripts", "target_scripts", "n_samples", "solver", "compose"]},
         "unitary": {"fn": unitary_cost_fn, "default_weight": (0.5, 0.5),
-                    "ckwargs_keys": ["pulse_basis_scripts", "target_basis_scripts", "n_samples", "n_qubits", "solver"]},
+                    "ckwargs_keys": ["pulse_basis_scripts", "target_basis_scripts", "n_samples", "n_qubits", "solver",
+                                     "compose"]},
+        "joint_unitary": {"fn": joint_unitary_cost_fn, "default_weight": (0.5, 0.5),
+                          "ckwargs_keys": ["gate_specs", "n_samples", "solver", "compose"]},
         "pulse_width": {"fn": pulse_width_cost_fn, "default_weight": 1.0, "ckwargs_keys": ["envelope"]},
         "evolution_time": {"fn": evolution_time_cost_fn, "default_weight": 1.0, "ckwargs_keys": ["t_target"]},
         "spectral_density": {"fn": spectral_density_cost_fn, "default_weight": 1.0, "ckwargs_keys": ["envelope"]},
@@ -580,9 +928,12 @@ class QOC:
                  restart_noise_scale: float = 0.5, grad_clip: float = 1.0, random_seed: int = 42, scan_steps: int = 0,
                  scan_grid_size: int = 5, scan_ranges: Optional[List[Tuple[float, float]]] = None,
                  log_scale_params: Optional[List[int]] = None, early_stop_patience: int = 0,
-                 early_stop_min_delta: float = 0.0, plot: bool = False, solver: Optional[Callable] = None):
-        """The reference's arguments (``qoc.py:656-777``) and ``solver``: the pulse solver of the evaluator (default
-        :func:`pulses.solve_with_jacobian`).  ``plot`` is stored and not acted on."""
+                 early_stop_min_delta: float = 0.0, plot: bool = False, solver: Optional[Callable] = None,
+                 compose: Optional[str] = None):
+        """The reference's arguments (``qoc.py:656-777``), ``solver``: the pulse solver of the evaluator (default
+        :func:`pulses.solve_with_jacobian`), and ``compose``: where circuits are composed -- ``None`` keeps the
+        defaults (``"host"`` per gate; joint: ``"device"`` with the default solver, else ``"host"``).  ``plot`` is
+        stored and not acted on."""
         self.envelope = envelope
         self.n_steps = n_steps
         self.n_samples = n_samples
@@ -601,6 +952,7 @@ class QOC:
         self.scan_grid_size = scan_grid_size
         self.scan_ranges = scan_ranges
         self.solver = solver
+        self.compose = None if compose is None else _check_compose(compose)
         n_env = PulseEnvelope.get(envelope)["n_envelope_params"]
         if log_scale_params is not None:
             self.log_scale_params = log_scale_params
@@ -849,6 +1201,7 @@ class QOC:
                     "n_qubits": wires,
                     "t_target": self.t_target,
                     "solver": self.solver,
+                    "compose": self.compose or "host",
                 }
                 gate_name = create_circuits.__name__.split("_")[1]
                 if init_pulse_params is None:
@@ -901,6 +1254,211 @@ class QOC:
             return self._gate_factories()[gate_name]
         except KeyError as exc:
             raise ValueError(f"No factory for gate {gate_name!r}.") from exc
+
+
+    def create_CPhase(self) -> Tuple[Callable, Callable]:
+        """``(pulse circuit, target circuit)`` of CPhase, both wires prepared in ``|+>`` (``qoc.py:2101-2114``)."""
+        def pulse_circuit(w, pulse_params):
+            op.H(wires=0)
+            op.H(wires=1)
+            Gates.CPhase(w, wires=[0, 1], pulse_params=pulse_params, gate_mode="pulse")
+
+        def target_circuit(w):
+            op.H(wires=0)
+            op.H(wires=1)
+            op.ControlledPhaseShift(w, wires=[0, 1])
+
+        return pulse_circuit, target_circuit
+
+    def optimize_all(self, sel_gates: str, make_log: bool) -> Dict[str, list]:
+        """The per-gate loop (``qoc.py:2116-2145``): optimise every gate of ``GATES_1Q + GATES_2Q`` that ``sel_gates``
+        (comma-separated names, a list of names, or ``"all"``) names -- whole names: the reference tests
+        ``gate in sel_gates`` on the string itself, so that its ``"CRX"`` selects RX as well; with ``make_log`` the loss histories go to ``qoc_logs.csv``
+        under ``file_dir``, one column per gate.  Returns the histories."""
+        log_history: Dict[str, list] = {}
+        selected = [g.strip() for g in sel_gates.split(",")] if isinstance(sel_gates, str) else list(sel_gates)
+        for gate in self.GATES_1Q + self.GATES_2Q:
+            if gate in selected or "all" in selected:
+                n_wires = 1 if gate in self.GATES_1Q else 2
+                log.info(f"Optimizing {gate} gate...")
+                best_params, history = self.optimize(wires=n_wires)(getattr(self, f"create_{gate}"))()
+                log.info(f"Optimized parameters for {gate}: {best_params}")
+                log.info(f"Best achieved fidelity: {(1 - min(float(h) for h in history)) * 100:.5f}%")
+                log_history[gate] = log_history.get(gate, []) + [float(h) for h in history]
+        if make_log:
+            os.makedirs(self.file_dir, exist_ok=True)
+            with open(os.path.join(self.file_dir, "qoc_logs.csv"), "w", newline="") as f:
+                writer = csv.writer(f)
+                writer.writerow(log_history.keys())
+                writer.writerows(zip(*log_history.values()))
+        return log_history
+
+    # -- joint optimisation: one shared leaf vector against a weighted sum of target gates (``qoc.py:2147-2605``)
+    JOINT_LEAVES_DEFAULT: Tuple[str, ...] = ("RX", "RY", "RZ", "CZ")  # (the order lays out theta)
+    JOINT_TARGETS_DEFAULT: Tuple[str, ...] = ("RX", "RY", "RZ", "H", "CX", "CRX", "CRY", "CRZ")
+    JOINT_WEIGHTS_DEFAULT: Dict[str, float] = {"RX": 0.3, "RY": 0.3, "RZ": 0.3, "H": 1.0, "CX": 2.0, "CRX": 3.0,
+                                               "CRY": 3.0, "CRZ": 3.0}
+    JOINT_TIED_GROUPS_DEFAULT: Tuple[Tuple[str, ...], ...] = (("RX", "RY"),)  # same envelope, carrier phase apart
+
+    def _build_joint_layout(self, leaf_names: Sequence[str],
+                            tied_groups: Optional[Sequence[Sequence[str]]] = None):
+        """``(init_theta, leaf_slices, log_scale_indices)``: the leaves' current parameters concatenated in the given
+        order.  The present members of a tied group (two or more) share ONE slice, initialised with their mean; only
+        the RX / RY amplitude and evolution time are optimised in log space."""
+        tied_groups = self.JOINT_TIED_GROUPS_DEFAULT if tied_groups is None else tied_groups
+        rep_of = {name: name for name in leaf_names}
+        for group in tied_groups:
+            present = [name for name in group if name in rep_of]
+            for member in present[1:] if len(present) >= 2 else []:
+                rep_of[member] = present[0]
+                log.info(f"  Joint layout: tying leaf {member!r} to {present[0]!r} (shared slice in theta).")
+        n_env = PulseEnvelope.get(self.envelope)["n_envelope_params"]
+        leaf_slices: Dict[str, slice] = {}
+        chunks, log_idx, offset = [], [], 0
+        for name in leaf_names:
+            if rep_of[name] != name:
+                leaf_slices[name] = leaf_slices[rep_of[name]]
+                continue
+            pp = PulseInformation.gate_by_name(name)
+            assert pp is not None and pp.is_leaf, f"_build_joint_layout: {name!r} is not a leaf gate"
+            members = [m for m in leaf_names if rep_of[m] == name]
+            chunk = np.mean(np.stack([np.asarray(PulseInformation.gate_by_name(m).params, dtype=np.float64)
+                                      for m in members]), axis=0) if len(members) > 1 else \
+                np.asarray(pp.params, dtype=np.float64)
+            leaf_slices[name] = slice(offset, offset + len(chunk))
+            chunks.append(chunk)
+            if name in ("RX", "RY") and n_env >= 2:
+                log_idx += [offset, offset + len(chunk) - 1]
+            offset += len(chunk)
+        return np.concatenate(chunks), leaf_slices, log_idx
+
+    @staticmethod
+    def _assemble_for_gate(theta, pp_obj, leaf_slices: Dict[str, slice]) -> np.ndarray:
+        """The gate's flat parameters from ``theta`` ``[T]`` or ``[C, T]``: the slice of every leaf occurrence in
+        tree order; a leaf without a slice is frozen at its ``PulseInformation`` value."""
+        return _JointAssembler(pp_obj, leaf_slices)(theta)
+
+    @staticmethod
+    def _joint_gate_factories() -> Dict[str, Tuple[Callable, Callable]]:
+        """``{gate: (pulse circuit, target circuit)}`` without preparations: the unitary cost sees every column, and
+        a preparation can hide an error (``qoc.py:1998-2057``).  No ``Rot`` and no ``CY``."""
+        def pulse(name, with_angle, wires):
+            if with_angle:
+                return lambda w, pp: getattr(Gates, name)(w, wires=wires, pulse_params=pp, gate_mode="pulse")
+            return lambda w, pp: getattr(Gates, name)(wires=wires, pulse_params=pp, gate_mode="pulse")
+
+        pair = lambda name, with_angle, wires, target: _make_gate_pair(pulse(name, with_angle, wires), target)  # noqa: E731
+        return {
+            "RX": pair("RX", True, 0, lambda w: op.RX(w, wires=0)),
+            "RY": pair("RY", True, 0, lambda w: op.RY(w, wires=0)),
+            "RZ": pair("RZ", True, 0, lambda w: op.RZ(w, wires=0)),
+            "H": pair("H", False, 0, lambda w: op.H(wires=0)),
+            "CZ": pair("CZ", False, [0, 1], lambda w: op.CZ(wires=[0, 1])),
+            "CX": pair("CX", False, [0, 1], lambda w: op.CX(wires=[0, 1])),
+            "CRX": pair("CRX", True, [0, 1], lambda w: op.CRX(w, wires=[0, 1])),
+            "CRY": pair("CRY", True, [0, 1], lambda w: op.CRY(w, wires=[0, 1])),
+            "CRZ": pair("CRZ", True, [0, 1], lambda w: op.CRZ(w, wires=[0, 1])),
+        }
+
+    def _create_joint_pair_for(self, gate_name: str) -> Tuple[Callable, Callable]:
+        table = self._joint_gate_factories()
+        if gate_name in table:
+            return table[gate_name]
+        log.warning(f"_create_joint_pair_for: no prep-free factory for {gate_name!r}; falling back to "
+                    f"create_{gate_name} (preps may hide errors).")
+        return self._create_pair(gate_name)
+
+    def _joint_stage_0_coord_descent(self, init_theta: np.ndarray, leaf_slices: Dict[str, slice],
+                                     total_cost: Callable) -> np.ndarray:
+        """Coordinate descent over the leaves: per unique slice the multiplicative grid of :meth:`_build_scan_grid`
+        around the current values, everything else held.  Within one leaf every trial overwrites the same slice, so
+        the reference's candidate-by-candidate greedy loop equals: evaluate the whole grid as ONE ``[C, T]`` batch,
+        take its first minimum, accept it if it is below the best so far.  One evaluation per unique slice plus one
+        for the start; non-finite losses count as +inf; the solver runs with ``throw=False`` meanwhile."""
+        current = np.array(init_theta, dtype=np.float64)
+        if self.scan_steps <= 0:
+            log.info("Joint Stage 0: scan disabled (scan_steps=0); skipping.")
+            return current
+        prev = Evolution.set_solver_defaults(throw=False)
+        try:
+            with np.errstate(all="ignore"):
+                best_loss = float(_safe(np.asarray(total_cost(current[None]), dtype=np.float64).reshape(-1))[0])
+                log.info(f"Joint Stage 0: coordinate-descent over {len(leaf_slices)} leaves, init_loss={best_loss:.6e}")
+                seen = set()
+                for leaf_name, sl in leaf_slices.items():
+                    if (sl.start, sl.stop) in seen or sl.stop == sl.start:
+                        continue
+                    seen.add((sl.start, sl.stop))
+                    grid, _ = self._build_scan_grid(sl.stop - sl.start, init_pulse_params=current[sl])
+                    batch = np.repeat(current[None], len(grid), axis=0)
+                    batch[:, sl] = grid
+                    losses = _safe(np.asarray(total_cost(batch), dtype=np.float64).reshape(-1))
+                    first = int(np.argmin(losses))
+                    if losses[first] < best_loss:
+                        best_loss, current = float(losses[first]), batch[first].copy()
+                    log.info(f"  Joint scan after leaf {leaf_name} ({len(grid)} candidates): best_loss={best_loss:.6e}")
+        finally:
+            if prev:
+                Evolution.set_solver_defaults(**prev)
+        return current
+
+    def _joint_specs(self, target_gates: Sequence[str], leaf_slices: Dict[str, slice],
+                     weights: Dict[str, float]) -> List[dict]:
+        """The specs of :func:`joint_unitary_cost_fn` for ``target_gates``: prep-free basis scripts, the gate's weight
+        (1 where ``weights`` has none), its assembler over ``leaf_slices`` and its target unitaries at this object's
+        ``n_samples`` angles."""
+        gate_specs: List[dict] = []
+        for name in target_gates:
+            pp_obj = PulseInformation.gate_by_name(name)
+            if pp_obj is None:
+                log.warning(f"  Skipping unknown gate {name!r}.")
+                continue
+            n_wires = 1 if name in self.GATES_1Q else 2
+            pulse_circuit, target_circuit = self._create_joint_pair_for(name)
+            gate_specs.append({
+                "name": name, "n_qubits": n_wires, "weight": float(weights.get(name, 1.0)),
+                "assembler": _JointAssembler(pp_obj, leaf_slices),
+                "pulse_basis_scripts": [Script(_with_basis_prep(pulse_circuit, k, n_wires), n_qubits=n_wires)
+                                        for k in range(2 ** n_wires)],
+                "target_basis_scripts": [Script(_with_basis_prep(target_circuit, k, n_wires), n_qubits=n_wires)
+                                         for k in range(2 ** n_wires)],
+            })
+            spec = gate_specs[-1]  # the targets once, for every evaluation of either route
+            spec["target_unitaries"] = (self.n_samples, _target_unitaries(
+                spec["target_basis_scripts"], _sample_rotation_angles(self.n_samples), n_wires))
+        return gate_specs
+
+    def optimize_joint(self, target_gates: Optional[Sequence[str]] = None, leaf_names: Optional[Sequence[str]] = None,
+                       weights: Optional[Dict[str, float]] = None):
+        """Tune ONE shared vector ``theta`` -- the parameters of ``leaf_names`` (default ``JOINT_LEAVES_DEFAULT``) --
+        against the weighted unitary costs of ``target_gates`` (default ``JOINT_TARGETS_DEFAULT``; ``weights`` are
+        merged over ``JOINT_WEIGHTS_DEFAULT``): coordinate-descent scan, then :meth:`stage_1_opt` unchanged with
+        ``log_scale_params`` pointing at the joint indices meanwhile.  Writes one CSV row per leaf (with the joint
+        fidelity), updates ``PulseInformation`` in place and returns ``(best_theta, leaf_slices, loss history)``."""
+        target_gates = list(target_gates) if target_gates else list(self.JOINT_TARGETS_DEFAULT)
+        leaf_names = list(leaf_names) if leaf_names else list(self.JOINT_LEAVES_DEFAULT)
+        merged = dict(self.JOINT_WEIGHTS_DEFAULT)
+        merged.update({k: float(v) for k, v in (weights or {}).items()})
+        log.info(f"Joint optimisation: leaves={leaf_names}, targets={target_gates}")
+        init_theta, leaf_slices, joint_log_idx = self._build_joint_layout(tuple(leaf_names))
+        gate_specs = self._joint_specs(target_gates, leaf_slices, merged)
+        weight = next((w for n, w in self.cost_fns if n == "unitary"), (0.5, 0.5))
+        joint_cost = Cost(cost=joint_unitary_cost_fn, weight=weight,
+                          ckwargs={"gate_specs": gate_specs, "n_samples": self.n_samples, "solver": self.solver,
+                                   "compose": self.compose})
+        prev_log_scale = self.log_scale_params
+        self.log_scale_params = joint_log_idx
+        try:
+            best_scan_theta = self._joint_stage_0_coord_descent(init_theta, leaf_slices, joint_cost)
+            best_theta, history, best_loss = self.stage_1_opt(best_scan_theta, joint_cost)
+        finally:
+            self.log_scale_params = prev_log_scale
+        log.info(f"Joint optimisation done. final loss={float(best_loss):.6e}")
+        for leaf_name, sl in leaf_slices.items():
+            self.save_results(gate=leaf_name, fidelity=float(1.0 - best_loss), pulse_params=best_theta[sl])
+        for leaf_name, sl in leaf_slices.items():
+            PulseInformation.gate_by_name(leaf_name).params = np.array(best_theta[sl])
+        return best_theta, leaf_slices, history
 
 
 def _factory(gate_name: str):
