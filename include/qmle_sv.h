@@ -767,6 +767,55 @@ int qmle_compose_circuits(const qmle_compose_circuit *circuits, int n_circuits, 
                           void *d_workspace, size_t workspace_bytes, qmle_stream stream);
 size_t qmle_compose_workspace_bytes(int n_circuits, int n_ops, int n_terms, int64_t n_rows);
 
+/* ---- analytic Fourier coefficients: the sine-cosine tree of a Pauli-rotation circuit, merged into a DAG -------------
+ * (coefficients.FourierTree.)  Node j stands for a bare Pauli word in front of the rotations 0..k of the canonical
+ * circuit, k its LEVEL.  Its value V_j is a function on the frequency grid: dims[0] x .. x dims[n_axes - 1] points,
+ * every dims[a] odd, axis 0 slowest, F their product; the point with coordinates (g_0, ..) is the frequency vector
+ * omega_a = g_a - (dims[a] - 1) / 2.  n_axes = 0 is the grid of the single point omega = () (F = 1): plain numbers.
+ * A child slot holds a node index >= 0, QMLE_FOURIER_ONE (the function that is 1 at omega = 0 and 0 elsewhere: a
+ * diagonal word in front of no rotation) or QMLE_FOURIER_ZERO (the zero function).  With a = V[cos_child],
+ * b = V[sin_child] and p = power (0..3) the value of a node on level k is, for every sample,
+ *     kind QMLE_FOURIER_ANGLE   V = cos(t) a + i^(1+p) sin(t) b,         t = d_angles[sample][column]
+ *     kind QMLE_FOURIER_SHIFT   V = (T+ a + T- a) / 2 + i^p (T+ b - T- b) / 2
+ * where (T+ f)(omega) = f(omega - shift e_axis), (T- f)(omega) = f(omega + shift e_axis), and f is 0 outside the grid:
+ * the second line is the first with t = shift x_axis, written in the coefficients of e^{i omega x}.  The result is
+ *     d_out[sample][r][g] = i^root_phase[r] V[roots[r]][g],     complex128, [batch][n_roots][F].
+ *   qmle_fourier_node   cos_child, sin_child, power, and a pad that is not read.
+ *   qmle_fourier_level  node_begin..node_end: the nodes of the level; kind; column (ANGLE) or axis and shift (SHIFT,
+ *       shift a signed integer != 0).  The levels are in circuit order and tile the node table: level 0 begins at
+ *       node 0, every level begins where the one before it ends (a level may be empty), the last ends at n_nodes.
+ *       Every child of a node lies on a lower level.  n_levels = 0 with n_nodes = 0 is allowed (the roots are
+ *       terminals then).
+ * The node, level, root and dims tables are HOST arrays: the library checks every index in them and copies them into
+ * the workspace on the stream (lifetime as for qmle_compose_circuits).  d_angles is a DEVICE array [batch][n_columns]
+ * of float64; sin and cos are evaluated on the device, in float64 like everything else.
+ * One workgroup per sample walks the levels in order with a workgroup barrier between them; its lanes are spread over
+ * (node, grid point) of the level.  Every value has one writer and every sum a fixed order: no atomics, the output of
+ * a call is bit-reproducible and does not depend on batch.  The values of a sample live in its slice of the workspace,
+ * n_nodes x F complex128: a call with one sample and a large DAG runs on one compute unit.
+ * d_workspace: at least what the second function returns, 16-byte aligned.
+ * QMLE_ERR_WORKSPACE for a workspace that is missing, misaligned or too small; QMLE_ERR_UNSUPPORTED for an unknown
+ * kind or n_axes outside 0..QMLE_FOURIER_MAX_AXES; QMLE_ERR_INVALID_ARG for a NULL table that is needed, batch < 1,
+ * n_roots < 1, n_nodes or n_levels < 0, an even or non-positive dims entry, F or a level's (nodes x F) at or beyond
+ * 2^31, levels that do not tile the node table, a child or root that is neither a terminal code nor a node index below
+ * the level's node_begin (below n_nodes for a root), a power or root phase outside 0..3, a column outside
+ * 0..n_columns-1, an axis outside 0..n_axes-1, a shift that is 0 or whose magnitude reaches dims[axis], NULL d_angles
+ * while a level reads a column, or NULL d_out -- all before any device work. */
+enum { QMLE_FOURIER_ONE = -1, QMLE_FOURIER_ZERO = -2 };
+enum { QMLE_FOURIER_ANGLE = 0, QMLE_FOURIER_SHIFT = 1 };
+#define QMLE_FOURIER_MAX_AXES 8
+typedef struct {
+  int32_t cos_child, sin_child, power, pad;
+} qmle_fourier_node;
+typedef struct {
+  int32_t node_begin, node_end, kind, column, axis, shift;
+} qmle_fourier_level;
+int qmle_fourier_dag(const qmle_fourier_node *nodes, int n_nodes, const qmle_fourier_level *levels, int n_levels,
+                     const int32_t *roots, const int32_t *root_phase, int n_roots, const int32_t *dims, int n_axes,
+                     const double *d_angles, int n_columns, int batch, void *d_out, void *d_workspace,
+                     size_t workspace_bytes, qmle_stream stream);
+size_t qmle_fourier_workspace_bytes(int n_nodes, int n_levels, int n_roots, int64_t grid_points, int batch);
+
 #ifdef __cplusplus
 }
 #endif

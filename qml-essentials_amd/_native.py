@@ -239,6 +239,8 @@ SYMBOLS = [
     ("qmle_compose_circuits", _I, [_VP, _I, _VP, _I, _VP, _I, _VP, C.c_int64, _I, _VP, C.c_int64, _VP, C.c_int64, _VP,
                                    C.c_int64, _VP, _I, C.c_uint, _VP, C.c_int64, _VP, C.c_int64, _VP, _SZ, _VP]),
     ("qmle_compose_workspace_bytes", _SZ, [_I, _I, _I, C.c_int64]),
+    ("qmle_fourier_dag", _I, [_VP, _I, _VP, _I, _VP, _VP, _I, _VP, _I, _VP, _I, _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_fourier_workspace_bytes", _SZ, [_I, _I, _I, C.c_int64, _I]),
 ]
 
 
@@ -1090,6 +1092,53 @@ def compose_circuits(circuits, ops, terms, rows, n_candidates: int, mats, coefs,
         count(jac) // 24, int(column_mask), ptr(ov), int(ov_len), ptr(full), int(full_len), ptr(workspace),
         int(workspace.numel()), _stream_ptr()), "qmle_compose_circuits")
     return ov, full
+
+
+# qmle_fourier_dag: the tables as numpy records (the layout of the structs in include/qmle_sv.h)
+FOURIER_ONE, FOURIER_ZERO = -1, -2
+FOURIER_KINDS = {"ANGLE": 0, "SHIFT": 1}
+FOURIER_NODE = np.dtype([("cos_child", "<i4"), ("sin_child", "<i4"), ("power", "<i4"), ("pad", "<i4")])
+FOURIER_LEVEL = np.dtype([("node_begin", "<i4"), ("node_end", "<i4"), ("kind", "<i4"), ("column", "<i4"),
+                          ("axis", "<i4"), ("shift", "<i4")])
+
+
+def fourier_workspace_bytes(n_nodes: int, n_levels: int, n_roots: int, grid_points: int, batch: int) -> int:
+    """Bytes of device workspace one call of :func:`fourier_dag` needs for ``batch`` samples (0: sizes out of range);
+    decided on the host, no GPU needed."""
+    return int(lib().qmle_fourier_workspace_bytes(int(n_nodes), int(n_levels), int(n_roots), int(grid_points),
+                                                  int(batch)))
+
+
+def fourier_dag(nodes, levels, roots, root_phase, dims, angles, workspace=None):
+    """Walk a sine-cosine DAG for every row of ``angles`` in ONE launch (``qmle_fourier_dag``, conventions in
+    ``include/qmle_sv.h``).  ``nodes`` / ``levels``: host records of :data:`FOURIER_NODE` / :data:`FOURIER_LEVEL`;
+    ``roots`` / ``root_phase`` / ``dims``: host int32; ``angles`` ``[B, n_columns]`` float64, a host array (uploaded)
+    or a CUDA tensor.  Returns the complex128 CUDA tensor ``[B, n_roots, F]``."""
+    torch = require_gpu()
+    dev = current_device()
+    nodes = np.ascontiguousarray(nodes, dtype=FOURIER_NODE)
+    levels = np.ascontiguousarray(levels, dtype=FOURIER_LEVEL)
+    roots = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
+    root_phase = np.ascontiguousarray(root_phase, dtype=np.int32).reshape(-1)
+    dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
+    if not hasattr(angles, "is_cuda"):
+        angles = torch.from_numpy(np.ascontiguousarray(angles, dtype=np.float64))
+    angles = angles.to(device=dev, dtype=torch.float64).contiguous()
+    if angles.ndim != 2:
+        raise ValueError(f"fourier_dag: angles must be [B, n_columns], got shape {tuple(angles.shape)}")
+    B, n_columns = int(angles.shape[0]), int(angles.shape[1])
+    F = int(np.prod(dims, dtype=np.int64)) if dims.size else 1
+    need = fourier_workspace_bytes(len(nodes), len(levels), len(roots), F, B)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    out = torch.empty((B, len(roots), F), dtype=torch.complex128, device=dev)
+    host = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
+    check(lib().qmle_fourier_dag(
+        host(nodes), len(nodes), host(levels), len(levels), host(roots), host(root_phase), len(roots), host(dims),
+        len(dims), C.c_void_p(angles.data_ptr()) if angles.numel() else None, n_columns, B, C.c_void_p(out.data_ptr()),
+        C.c_void_p(workspace.data_ptr()), int(workspace.numel() * workspace.element_size()), _stream_ptr()),
+        "qmle_fourier_dag")
+    return out
 
 
 @_row_chunked(0)

@@ -10,6 +10,8 @@
 //   qmle_evolve.hip    Hamiltonian time evolution: 2x2 / 4x4 propagators on the fixed Magnus grids (qmle_evolve_magnus)
 //                      the pulse solves with and without sensitivities, and the composition of small circuits
 //                      from them (qmle_compose_circuits)
+//   qmle_fourier.hip   analytic Fourier coefficients: the merged sine-cosine DAG of a Pauli-rotation circuit walked
+//                      level by level, one workgroup per parameter set (qmle_fourier_dag)
 //   qmle_pauli.hip     Pauli-word observables of resident states and of vec(rho), their host planner; applying a
 //                      weighted sum of words to resident states (the seed of the adjoint sweep)
 // Kernels stay private to their unit (anonymous namespaces); what crosses a unit boundary is a

@@ -9,7 +9,8 @@ returns ``jnp`` arrays); the 2^n arithmetic runs in ``libqmle_sv`` via
 :class:`script.Script`.  ``gate_mode="pulse"`` records the ansatz (and the state preparation) through
 :mod:`pulses` and runs the recorded tape -- every pulse solve of it in one kernel launch; ``pulse_params`` are
 per-layer scalers of the optimised pulse parameters, shape ``(1, layers, n_pulse_params_per_layer)`` (a batch axis
-larger than 1 is not supported, nor is noise in pulse mode).  Out of scope: drawing, ``exact_spectrum``.
+larger than 1 is not supported, nor is noise in pulse mode).  ``exact_spectrum`` (``:532-591``) asks
+``coefficients.FourierTree`` for the symbolic frequency support.  Out of scope: drawing.
 """
 from __future__ import annotations
 
@@ -293,6 +294,24 @@ class Model:
     @frequencies.setter
     def frequencies(self, value: Tuple) -> None:
         self._frequencies = value
+
+    def exact_spectrum(self, method: str = "tree") -> Tuple[np.ndarray, ...]:
+        """The exact Fourier spectrum per input feature: the sorted integer frequencies whose coefficient is not
+        identically zero, a subset of the encoding's naive estimate :attr:`frequencies`, derived symbolically by
+        :meth:`coefficients.FourierTree.get_exact_support` (no sampling).  ``method="tree"`` enumerates the leaves of
+        the sine-cosine tree and also sees coefficients that cancel across paths; ``method="dp"`` walks the merged
+        DAG, scales to deep circuits (one feature, unit scaling) and may keep such a cancelled frequency.  The
+        circuit must consist of Pauli rotations and Clifford gates (``NotImplementedError`` otherwise)."""
+        from .coefficients import FourierTree  # (coefficients imports this module)
+
+        tree = FourierTree(self)
+        position = {feat: i for i, feat in enumerate(tree.features)}
+        support = set()
+        for freqs in tree.get_exact_support(method=method):
+            freqs = np.asarray(freqs)
+            support |= {(int(v),) if freqs.ndim == 1 else tuple(int(x) for x in v) for v in freqs}
+        return tuple(np.array(sorted({k[position[feat]] for k in support}) if support and feat in position else [0],
+                              dtype=int) for feat in range(self.n_input_feat))
 
     @property
     def has_dru(self) -> bool:

@@ -18,7 +18,8 @@ ket and bra copies of its wires in the vectorised density matrix (see ``simulati
 Pulse-level gates (:mod:`pulses`) record ordinary operations for their closed-form leaves and a
 ``pulses.PulseRotation`` -- an ``Operation`` whose matrix is a pulse solve still to be run -- for RX / RY.
 
-Out of scope here: ``PauliWord`` algebra.
+``PauliWord`` (``operations.py:2174-2521``) is the symbolic Pauli algebra -- bit arrays and a power of i -- that
+:mod:`pauli` and ``coefficients.FourierTree`` stand on; it stays on the host.
 """
 from __future__ import annotations
 
@@ -462,6 +463,12 @@ CSWAP = _fixed_gate("CSWAP", _controlled(np.eye(4, dtype=np.complex128)[[0, 2, 1
                     clifford=False, controlled=True, doc="Fredkin, wires=[control,t0,t1]")
 
 
+def _gate_arg(p):
+    """A stored gate parameter as a constructor argument: a ``(B,)`` column goes back into the batched scalar it came
+    from (decompositions of batched tapes)."""
+    return Batched(p) if np.ndim(p) else p
+
+
 def _cz_decompose(self):
     c, t = self.wires
     return [H(wires=t, record=False), CX(wires=[c, t], record=False), H(wires=t, record=False)]
@@ -524,8 +531,8 @@ class Rot(Operation):
 
     def decompose(self):
         w = self.wires[0]
-        return [RZ(self.phi, wires=w, record=False), RY(self.theta, wires=w, record=False),
-                RZ(self.omega, wires=w, record=False)]
+        return [RZ(_gate_arg(self.phi), wires=w, record=False), RY(_gate_arg(self.theta), wires=w, record=False),
+                RZ(_gate_arg(self.omega), wires=w, record=False)]
 
 
 class ControlledPhaseShift(Operation):
@@ -572,6 +579,23 @@ class PauliRot(Operation):
 
     def generator(self) -> Operation:
         return Hermitian(_pauli_word_matrix(self.pauli_word), wires=self.wires, record=False)
+
+    def decompose(self) -> List["Operation"]:
+        """``V^+ exp(-i theta/2 Z..Z) V``: per wire V turns the word's letter into Z (H for X, RX(pi/2) for Y), and the
+        Z..Z rotation is an RZ on the last acting wire between two CX ladders.  The RZ keeps this gate's tangents.
+        This is how the engine runs words on more than two wires (``Script._record_for_engine``)."""
+        acting = [(c, w) for c, w in zip(self.pauli_word, self.wires) if c != "I"]
+        if not acting:
+            raise NotImplementedError("PauliRot of the identity word is a global phase: nothing to decompose")
+        into = [H(wires=w, record=False) if c == "X" else RX(np.pi / 2, wires=w, record=False)
+                for c, w in acting if c != "Z"]
+        back = [H(wires=w, record=False) if c == "X" else RX(-np.pi / 2, wires=w, record=False)
+                for c, w in acting if c != "Z"]
+        last = acting[-1][1]
+        ladder = [CX(wires=[w, last], record=False) for _, w in acting[:-1]]
+        core = RZ(_gate_arg(self.theta), wires=last, record=False)
+        core._tangents = {"theta": self.__dict__.get("_tangents", {}).get("theta", [])}
+        return into + ladder + [core] + ladder[::-1] + back[::-1]
 
     def lower(self, n_qubits: int):
         native = self._NATIVE_WORDS.get(self.pauli_word)
@@ -639,7 +663,7 @@ def _controlled_rotation(name: str, axis: str):
 
     def decompose(self):
         c, t = self.wires
-        th = self.theta
+        th = _gate_arg(self.theta)
         core = [RZ(th / 2, wires=t, record=False), CX(wires=[c, t], record=False),
                 RZ(-th / 2, wires=t, record=False), CX(wires=[c, t], record=False)]
         if axis == "Z":
@@ -983,3 +1007,200 @@ class QubitChannel(KrausChannel):
 
     def kraus_matrices(self):
         return self._kraus_ops
+
+
+# ---- symbolic Pauli words ---------------------------------------------------------------------
+_LABEL_BITS = {"I": (0, 0), "X": (1, 0), "Y": (1, 1), "Z": (0, 1)}
+_BITS_LABEL = {bits: label for label, bits in _LABEL_BITS.items()}
+_ROTATION_AXES = {"RX": "X", "RY": "Y", "RZ": "Z"}
+_PAULI_GATES = {"PauliX": "X", "PauliY": "Y", "PauliZ": "Z", "Id": "I", "I": "I"}
+
+# what the Cliffords with a tableau rule do to the generators: gate -> {(generator, slot of the gate's wire list):
+# image as (sign exponent of i, ((label, slot), ...))}; generators that are not listed stay as they are.  The
+# entries are C G C^dagger; "S_adj" holds S^dagger G S, every other listed gate is its own inverse.
+_CLIFFORD_IMAGES = {
+    "H": {("X", 0): (0, (("Z", 0),)), ("Z", 0): (0, (("X", 0),))},
+    "S": {("X", 0): (0, (("Y", 0),))},
+    "S_adj": {("X", 0): (2, (("Y", 0),))},
+    "CX": {("X", 0): (0, (("X", 0), ("X", 1))), ("Z", 1): (0, (("Z", 0), ("Z", 1)))},
+    "CZ": {("X", 0): (0, (("X", 0), ("Z", 1))), ("X", 1): (0, (("Z", 0), ("X", 1)))},
+    "SWAP": {("X", 0): (0, (("X", 1),)), ("X", 1): (0, (("X", 0),)),
+             ("Z", 0): (0, (("Z", 1),)), ("Z", 1): (0, (("Z", 0),))},
+}
+
+
+class PauliWord:
+    """Symbolic n-qubit Pauli operator ``i^phase prod_q X_q^x[q] Z_q^z[q]`` (``operations.py:2174-2521``): two bit
+    arrays and a power of i, so ``I = (0, 0)``, ``X = (1, 0)``, ``Z = (0, 1)`` and ``Y = i X Z`` is the bits
+    ``(1, 1)`` with one more power of i.  Products, commutation and conjugation by Clifford gates are integer
+    bookkeeping; nothing here touches a matrix except the fallback for Cliffords without a tableau rule and the
+    explicit conversions.  Host only: :class:`pauli.PauliCircuit` and :class:`coefficients.FourierTree` use it to
+    set up what the GPU then evaluates."""
+
+    __slots__ = ("x", "z", "phase")
+
+    def __init__(self, x, z, phase: int = 0) -> None:
+        self.x = np.asarray(x, dtype=np.int8) & 1
+        self.z = np.asarray(z, dtype=np.int8) & 1
+        self.phase = int(phase) % 4
+
+    # ---- constructors -----------------------------------------------------------------
+    @classmethod
+    def identity(cls, n_qubits: int) -> "PauliWord":
+        return cls(np.zeros(n_qubits, dtype=np.int8), np.zeros(n_qubits, dtype=np.int8), 0)
+
+    @classmethod
+    def from_pauli_string(cls, pauli_string: str, wires: Sequence[int], n_qubits: int) -> "PauliWord":
+        """The word with ``pauli_string[j]`` on ``wires[j]`` and identities elsewhere."""
+        x = np.zeros(n_qubits, dtype=np.int8)
+        z = np.zeros(n_qubits, dtype=np.int8)
+        for label, w in zip(pauli_string, _wire_list(wires)):
+            x[w], z[w] = _LABEL_BITS[label]
+        return cls(x, z, pauli_string.count("Y"))  # (each Y = i X Z brings one power of i)
+
+    @classmethod
+    def from_operation(cls, op_: "Operation", n_qubits: int) -> "PauliWord":
+        """The word of a Pauli gate / observable, the generator of a Pauli rotation, an operation tagged with a
+        ``_pauli_word`` or ``_pauli_label``, or an explicit matrix that is a Pauli word up to a power of i."""
+        cached = getattr(op_, "_pauli_word", None)
+        if isinstance(cached, PauliWord) and cached.n_qubits == n_qubits:
+            return cached
+        label = getattr(op_, "pauli_word", None) if isinstance(op_, PauliRot) else None
+        if label is None:
+            label = _ROTATION_AXES.get(op_.name) or _PAULI_GATES.get(op_.name) or getattr(op_, "_pauli_label", None)
+        if label is not None and len(label) == len(op_.wires):
+            return cls.from_pauli_string(label, op_.wires, n_qubits)
+        local = cls.from_matrix(op_.matrix)
+        if local.n_qubits != len(op_.wires):
+            raise ValueError(f"{op_.name}: matrix does not match {len(op_.wires)} wire(s)")
+        word = cls.identity(n_qubits)
+        for j, w in enumerate(op_.wires):
+            word.x[w], word.z[w] = local.x[j], local.z[j]
+        word.phase = local.phase
+        return word
+
+    # ---- structure --------------------------------------------------------------------
+    @property
+    def n_qubits(self) -> int:
+        return int(self.x.shape[0])
+
+    @property
+    def xy_mask(self) -> np.ndarray:
+        """True where the word carries an X or a Y."""
+        return self.x.astype(bool)
+
+    @property
+    def is_diagonal(self) -> bool:
+        return not self.x.any()
+
+    # ---- algebra ----------------------------------------------------------------------
+    def commutes_with(self, other: "PauliWord") -> bool:
+        """Two words commute iff their symplectic product ``x . z' + z . x'`` is even."""
+        return (int(self.x @ other.z) + int(self.z @ other.x)) % 2 == 0
+
+    def compose(self, other: "PauliWord") -> "PauliWord":
+        """The operator product ``self @ other``: moving ``other``'s X bits left past ``self``'s Z bits costs a
+        sign per crossing."""
+        crossings = int(self.z.astype(np.int64) @ other.x.astype(np.int64))
+        return PauliWord(self.x ^ other.x, self.z ^ other.z, self.phase + other.phase + 2 * crossings)
+
+    def conjugate_by_clifford(self, clifford: "Operation", adjoint_left: bool = False) -> "PauliWord":
+        """``C P C^dagger`` (``adjoint_left=False``) or ``C^dagger P C`` (``True``).  H, S, CX, CZ, SWAP and the Pauli
+        gates are done on the bits: conjugation is multiplicative, so the word is rebuilt from the images of its
+        generators in their own order.  Any other Clifford goes through its matrix."""
+        n, name = self.n_qubits, clifford.name
+        if name in ("PauliX", "PauliY", "PauliZ"):  # (Hermitian: both sides are Q P Q)
+            q = PauliWord.from_operation(clifford, n)
+            return q.compose(self).compose(q)
+        if name in ("Id", "I"):
+            return PauliWord(self.x, self.z, self.phase)
+        rule = _CLIFFORD_IMAGES.get("S_adj" if name == "S" and adjoint_left else name)
+        if rule is None:
+            return self._conjugate_via_matrix(clifford, adjoint_left)
+        wires = clifford.wires
+        slot = {w: j for j, w in enumerate(wires)}
+        out = PauliWord.identity(n)
+        out.phase = self.phase
+        for q in range(n):
+            for label, bit in (("X", self.x[q]), ("Z", self.z[q])):
+                if not bit:
+                    continue
+                power, image = rule.get((label, slot.get(q, -1)), (0, ((label, None),)))
+                factor = PauliWord.from_pauli_string("".join(lb for lb, _ in image),
+                                                     [q if s is None else wires[s] for _, s in image], n)
+                factor.phase = (factor.phase + power) % 4
+                out = out.compose(factor)
+        return out
+
+    def _conjugate_via_matrix(self, clifford: "Operation", adjoint_left: bool) -> "PauliWord":
+        """Dense conjugation, exact for any Clifford, at ``O(4^n)`` cost."""
+        n = self.n_qubits
+        c = embed_matrix(clifford.matrix, clifford.wires, list(range(n)))
+        cd = np.conj(c).T
+        m = self.to_matrix()
+        return PauliWord.from_matrix(cd @ m @ c if adjoint_left else c @ m @ cd)
+
+    # ---- values and conversions ---------------------------------------------------------
+    def zero_expectation(self) -> complex:
+        """``<0..0| P |0..0>``: ``i^phase`` for a diagonal word (Z on |0> is +1), 0 otherwise."""
+        return complex(1j ** self.phase) if self.is_diagonal else 0j
+
+    def to_pauli_string(self) -> str:
+        return "".join(_BITS_LABEL[(int(a), int(b))] for a, b in zip(self.x, self.z))
+
+    def leading_phase(self) -> complex:
+        """``c`` with ``P = c * (the bare string)``; the string's own Y's already hold ``i^n_Y``."""
+        n_y = int(np.sum(self.x & self.z))
+        return complex(1j ** ((self.phase - n_y) % 4))
+
+    def to_pauli_string_and_phase(self) -> Tuple[str, complex]:
+        return self.to_pauli_string(), self.leading_phase()
+
+    @classmethod
+    def from_string_and_phase(cls, pauli_string: str, phase: complex = 1.0) -> "PauliWord":
+        """Inverse of :meth:`to_pauli_string_and_phase` (``phase`` one of 1, i, -1, -i)."""
+        word = cls.from_pauli_string(pauli_string, list(range(len(pauli_string))), len(pauli_string))
+        word.phase = (word.phase + int(round(np.angle(complex(phase)) / (np.pi / 2)))) % 4
+        return word
+
+    def to_matrix(self) -> np.ndarray:
+        """Dense ``i^phase (x)_q X^x[q] Z^z[q]``, wire 0 the most significant bit."""
+        mat = np.ones((1, 1), dtype=np.complex128)
+        for a, b in zip(self.x, self.z):
+            mat = np.kron(mat, (_X if a else _I2) @ (_Z if b else _I2))
+        return (1j ** self.phase) * mat
+
+    @classmethod
+    def from_matrix(cls, matrix) -> "PauliWord":
+        """The word of a ``2^n x 2^n`` matrix that is a Pauli word times a power of i.  ``X^x Z^z |c> =
+        (-1)^(z.c) |c xor x>``: column 0 holds ``i^phase`` in row ``x``, and the column of a single set bit tells
+        that wire's z."""
+        m = np.asarray(matrix, dtype=np.complex128)
+        n = int(round(np.log2(m.shape[0])))
+        if m.shape != (2**n, 2**n):
+            raise ValueError(f"not a 2^n x 2^n matrix: shape {m.shape}")
+        row = int(np.argmax(np.abs(m[:, 0])))
+        lead = m[row, 0]
+        phase = int(round(np.angle(lead) / (np.pi / 2))) % 4
+        x = [(row >> (n - 1 - q)) & 1 for q in range(n)]
+        z = [int(np.real(m[row ^ (1 << (n - 1 - q)), 1 << (n - 1 - q)] / lead) < 0) for q in range(n)]
+        word = cls(x, z, phase)
+        if not np.allclose(word.to_matrix(), m, atol=1e-9):
+            raise ValueError("matrix is not a Pauli word up to a power of i")
+        return word
+
+    def to_list_repr(self) -> np.ndarray:
+        """Legacy integer form: I = -1, X = 0, Y = 1, Z = 2."""
+        code = {"I": -1, "X": 0, "Y": 1, "Z": 2}
+        return np.array([code[c] for c in self.to_pauli_string()], dtype=int)
+
+    def __eq__(self, other: object) -> bool:
+        if not isinstance(other, PauliWord):
+            return NotImplemented
+        return (self.phase == other.phase and np.array_equal(self.x, other.x)
+                and np.array_equal(self.z, other.z))
+
+    __hash__ = None
+
+    def __repr__(self) -> str:
+        return f"PauliWord({('+', '+i', '-', '-i')[self.phase]}{self.to_pauli_string()})"

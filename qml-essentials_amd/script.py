@@ -17,7 +17,7 @@ import numpy as np
 from . import _native as N
 from . import distributed, memory, pulses, simulation
 from .batching import Batched, to_numpy
-from .operations import MAX_PAULI_WIRES, KrausChannel, Operation, pauli_terms, z_parity_mask
+from .operations import MAX_PAULI_WIRES, KrausChannel, Operation, PauliRot, pauli_terms, z_parity_mask
 from .tape import batch_context, recording
 from .utils import PRNGKey
 
@@ -50,7 +50,7 @@ class CompiledCall:
             pr = np.stack([row, row + rng.uniform(0.1, 1.0, row.shape)])
             probes[k] = pr
             wrapped[k] = Batched.leaf(pr, k)
-        tape = script._record(*wrapped, **kwargs)
+        tape = script._record_for_engine(*wrapped, **kwargs)
         self.n_qubits = script._n_qubits or simulation.infer_n_qubits(tape, obs)
         # A tape with noise channels runs on vec(rho), a pure "state" of the doubled register
         # (simulation.doubled_tape): the same plan / angle-map machinery, measured as a density matrix.
@@ -314,6 +314,23 @@ class Script:
             self.f(*args, **kwargs)
         return tape
 
+    def _record_for_engine(self, *args, **kwargs) -> List[Operation]:
+        """The recorded tape as the engine takes it.  A Pauli rotation whose word has no opcode goes as an explicit
+        matrix if it is batch-constant on at most two wires; on more wires, or with a per-sample angle, it is replaced
+        by its decomposition (one- and two-wire gates, the angle and its tangents on one RZ)."""
+        tape = self._record(*args, **kwargs)
+
+        def wide(o) -> bool:
+            return (isinstance(o, PauliRot) and o.pauli_word not in PauliRot._NATIVE_WORDS
+                    and (len(o.wires) > 2 or np.ndim(o.theta) > 0))
+
+        if not any(wide(o) for o in tape):
+            return tape
+        out: List[Operation] = []
+        for o in tape:
+            out.extend(o.decompose() if wide(o) else [o])
+        return out
+
     @staticmethod
     def _batch_size(args: tuple, in_axes: Tuple) -> int:
         for a, ax in zip(args, in_axes):
@@ -339,7 +356,7 @@ class Script:
             key = PRNGKey(0)  # script.py:189-190
         if in_axes is not None:
             return self._execute_batched(type, obs, args, kwargs, in_axes, shots, key, as_tensor)
-        tape = self._record(*[to_numpy(a) for a in args], **kwargs)
+        tape = self._record_for_engine(*[to_numpy(a) for a in args], **kwargs)
         pulses.resolve(tape)  # every pulse leaf of the tape in one launch
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         res = simulation.simulate_and_measure(
@@ -369,7 +386,7 @@ class Script:
                 else:
                     wrapped.append(Batched(np.moveaxis(np.asarray(a), ax, 0)[start:end]))
             with batch_context(end - start):
-                tape = self._record(*wrapped, **kwargs)
+                tape = self._record_for_engine(*wrapped, **kwargs)
             pulses.resolve(tape)
             n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
             return simulation.simulate_and_measure(
@@ -384,7 +401,7 @@ class Script:
         if n_qubits is None or kwargs.get("noise_params"):
             probe = [a if ax is None or a is None else Batched(np.moveaxis(np.asarray(a), ax, 0)[:1])
                      for a, ax in zip(args, in_axes)]
-            tape = self._record(*probe, **kwargs)
+            tape = self._record_for_engine(*probe, **kwargs)
             n_qubits = n_qubits or simulation.infer_n_qubits(tape, obs)
             n_ops = len(tape)
             use_density = any(isinstance(o, KrausChannel) for o in tape)
@@ -450,7 +467,7 @@ class Script:
                 wrapped.append(Batched(data, []))  # batched, but a constant for this gradient
             else:
                 wrapped.append(a)
-        tape = self._record(*wrapped, **kwargs)
+        tape = self._record_for_engine(*wrapped, **kwargs)
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         gates = [o for o in tape if not isinstance(o, KrausChannel)] if skip_channels else tape
         low = simulation.LoweredTape(gates, n_qubits)
