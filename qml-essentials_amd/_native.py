@@ -352,6 +352,20 @@ def _i32(values: Sequence[int]):
     return arr
 
 
+def _device_tensor(x, dtype):
+    """Host array (uploaded as float64 / complex128) or tensor -> contiguous ``dtype`` tensor on the current device;
+    no copy when ``x`` already is one."""
+    torch = require_gpu()
+    if not hasattr(x, "is_cuda"):
+        x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.complex128 if dtype.is_complex else np.float64))
+    return x.to(device=current_device(), dtype=dtype).contiguous()
+
+
+def _host_ptr(a: np.ndarray):
+    """Pointer to a contiguous host array, NULL for an empty one."""
+    return C.c_void_p(a.ctypes.data) if a.size else None
+
+
 class Plan:
     """A compiled tape (``qmle_plan``).  Host-only until the first ``run``.
 
@@ -960,13 +974,7 @@ def evolve_magnus(h_terms, coef, h, order: int, lanes_per_row: int = 0, complex6
     if H.ndim != 3 or H.shape[1] != H.shape[2]:
         raise ValueError(f"evolve_magnus: terms must be [n_terms, d, d], got {H.shape}")
     dev = current_device()
-
-    def on_device(x):
-        if not hasattr(x, "is_cuda"):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64))
-        return x.to(device=dev, dtype=torch.float64).contiguous()
-
-    coef, h = on_device(coef), on_device(h)
+    coef, h = _device_tensor(coef, torch.float64), _device_tensor(h, torch.float64)
     n_terms, d = int(H.shape[0]), int(H.shape[1])
     per_step = 2 if order == 4 else 1
     if coef.dim() != 3 or coef.shape[2] != n_terms or coef.shape[1] % per_step or h.shape != (coef.shape[0],):
@@ -985,6 +993,19 @@ PULSE_ENVELOPES = ("gaussian", "square", "cosine", "drag", "sech")  # envelope i
 PULSE_MODES = ("rwa", "lab", "drive")
 
 
+def _pulse_call_args(name: str, solves, envelope: str, mode: str):
+    """What both pulse wrappers check and upload: ``(solves [n, 8] on the device, n, envelope id, mode id)``."""
+    torch = require_gpu()
+    if envelope not in PULSE_ENVELOPES:
+        raise ValueError(f"{name}: unknown envelope {envelope!r}; expected one of {PULSE_ENVELOPES}")
+    if mode not in PULSE_MODES:
+        raise ValueError(f"{name}: unknown mode {mode!r}; expected one of {PULSE_MODES}")
+    solves = _device_tensor(solves, torch.float64)
+    if solves.dim() != 2 or solves.shape[1] != 8 or solves.shape[0] < 1:
+        raise ValueError(f"{name}: solves must be [n >= 1, 8], got {tuple(solves.shape)}")
+    return solves, int(solves.shape[0]), PULSE_ENVELOPES.index(envelope), PULSE_MODES.index(mode)
+
+
 def pulse_unitaries(solves, envelope: str, mode: str, omega_c: float, omega_q: float, order: int, n_steps: int,
                     lanes_per_solve: int = 0, complex64: bool = False, prev=None, want_err: bool = False):
     """Every RX / RY pulse solve of a tape in one launch (``qmle_pulse_unitaries``): ``solves`` ``[n, 8]`` float64
@@ -992,17 +1013,8 @@ def pulse_unitaries(solves, envelope: str, mode: str, omega_c: float, omega_q: f
     (complex64 when asked) on the device, or ``(U, err)`` with ``want_err``: ``err`` ``[n]`` float64 =
     ``max |U - prev|`` for ``prev``, a result of the same format."""
     torch = require_gpu()
-    if envelope not in PULSE_ENVELOPES:
-        raise ValueError(f"pulse_unitaries: unknown envelope {envelope!r}; expected one of {PULSE_ENVELOPES}")
-    if mode not in PULSE_MODES:
-        raise ValueError(f"pulse_unitaries: unknown mode {mode!r}; expected one of {PULSE_MODES}")
+    solves, n, envelope_id, mode_id = _pulse_call_args("pulse_unitaries", solves, envelope, mode)
     dev = current_device()
-    if not hasattr(solves, "is_cuda"):
-        solves = torch.from_numpy(np.ascontiguousarray(solves, dtype=np.float64))
-    solves = solves.to(device=dev, dtype=torch.float64).contiguous()
-    if solves.dim() != 2 or solves.shape[1] != 8 or solves.shape[0] < 1:
-        raise ValueError(f"pulse_unitaries: solves must be [n >= 1, 8], got {tuple(solves.shape)}")
-    n = int(solves.shape[0])
     cdtype = torch.complex64 if complex64 else torch.complex128
     if want_err and prev is None:
         raise ValueError("pulse_unitaries: want_err needs prev")
@@ -1013,7 +1025,7 @@ def pulse_unitaries(solves, envelope: str, mode: str, omega_c: float, omega_q: f
     out = torch.empty((n, 2, 2), dtype=cdtype, device=dev)
     err = torch.empty((n,), dtype=torch.float64, device=dev) if want_err else None
     check(lib().qmle_pulse_unitaries(
-        C.c_void_p(solves.data_ptr()), n, PULSE_ENVELOPES.index(envelope), PULSE_MODES.index(mode), float(omega_c),
+        C.c_void_p(solves.data_ptr()), n, envelope_id, mode_id, float(omega_c),
         float(omega_q), int(order), int(n_steps), int(lanes_per_solve), 0 if complex64 else 1,
         C.c_void_p(out.data_ptr()), C.c_void_p(prev.data_ptr()) if prev is not None else None,
         C.c_void_p(err.data_ptr()) if err is not None else None, _stream_ptr()), "qmle_pulse_unitaries")
@@ -1026,20 +1038,10 @@ def pulse_unitaries_jac(solves, envelope: str, mode: str, omega_c: float, omega_
     Returns ``[n, 6, 2, 2]`` complex128 on the device: slot 0 is ``U``, slots 1..5 are its exact grid derivatives by
     ``p0, p1, p2, w, T`` (the ``p2`` slot is zero for the two-parameter envelopes)."""
     torch = require_gpu()
-    if envelope not in PULSE_ENVELOPES:
-        raise ValueError(f"pulse_unitaries_jac: unknown envelope {envelope!r}; expected one of {PULSE_ENVELOPES}")
-    if mode not in PULSE_MODES:
-        raise ValueError(f"pulse_unitaries_jac: unknown mode {mode!r}; expected one of {PULSE_MODES}")
-    dev = current_device()
-    if not hasattr(solves, "is_cuda"):
-        solves = torch.from_numpy(np.ascontiguousarray(solves, dtype=np.float64))
-    solves = solves.to(device=dev, dtype=torch.float64).contiguous()
-    if solves.dim() != 2 or solves.shape[1] != 8 or solves.shape[0] < 1:
-        raise ValueError(f"pulse_unitaries_jac: solves must be [n >= 1, 8], got {tuple(solves.shape)}")
-    n = int(solves.shape[0])
-    out = torch.empty((n, 6, 2, 2), dtype=torch.complex128, device=dev)
+    solves, n, envelope_id, mode_id = _pulse_call_args("pulse_unitaries_jac", solves, envelope, mode)
+    out = torch.empty((n, 6, 2, 2), dtype=torch.complex128, device=current_device())
     check(lib().qmle_pulse_unitaries_jac(
-        C.c_void_p(solves.data_ptr()), n, PULSE_ENVELOPES.index(envelope), PULSE_MODES.index(mode), float(omega_c),
+        C.c_void_p(solves.data_ptr()), n, envelope_id, mode_id, float(omega_c),
         float(omega_q), int(order), int(n_steps), int(lanes_per_solve), C.c_void_p(out.data_ptr()), _stream_ptr()),
         "qmle_pulse_unitaries_jac")
     return out
@@ -1070,13 +1072,7 @@ def compose_circuits(circuits, ops, terms, rows, n_candidates: int, mats, coefs,
     terms = np.ascontiguousarray(terms, dtype=COMPOSE_TERM)
     rows = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
 
-    def pool(x, dtype):
-        if x is None:
-            return None
-        if not hasattr(x, "is_cuda"):
-            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.complex128 if dtype.is_complex else np.float64))
-        return x.to(device=dev, dtype=dtype).contiguous().reshape(-1)
-
+    pool = lambda x, dtype: None if x is None else _device_tensor(x, dtype).reshape(-1)  # noqa: E731
     mats, targets, jac = (pool(x, torch.complex128) for x in (mats, targets, jac))
     coefs = pool(coefs, torch.float64)
     ov = torch.empty((ov_len,), dtype=torch.complex128, device=dev) if ov_len else None
@@ -1084,12 +1080,11 @@ def compose_circuits(circuits, ops, terms, rows, n_candidates: int, mats, coefs,
     need = lib().qmle_compose_workspace_bytes(len(circuits), len(ops), len(terms), len(rows))
     workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
     ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
-    host = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
     count = lambda t: int(t.numel()) if t is not None else 0  # noqa: E731
     check(lib().qmle_compose_circuits(
-        host(circuits), len(circuits), host(ops), len(ops), host(terms), len(terms), host(rows), len(rows),
-        int(n_candidates), ptr(mats), count(mats), ptr(coefs), count(coefs), ptr(targets), count(targets), ptr(jac),
-        count(jac) // 24, int(column_mask), ptr(ov), int(ov_len), ptr(full), int(full_len), ptr(workspace),
+        _host_ptr(circuits), len(circuits), _host_ptr(ops), len(ops), _host_ptr(terms), len(terms), _host_ptr(rows),
+        len(rows), int(n_candidates), ptr(mats), count(mats), ptr(coefs), count(coefs), ptr(targets), count(targets),
+        ptr(jac), count(jac) // 24, int(column_mask), ptr(ov), int(ov_len), ptr(full), int(full_len), ptr(workspace),
         int(workspace.numel()), _stream_ptr()), "qmle_compose_circuits")
     return ov, full
 
@@ -1121,9 +1116,7 @@ def fourier_dag(nodes, levels, roots, root_phase, dims, angles, workspace=None):
     roots = np.ascontiguousarray(roots, dtype=np.int32).reshape(-1)
     root_phase = np.ascontiguousarray(root_phase, dtype=np.int32).reshape(-1)
     dims = np.ascontiguousarray(dims, dtype=np.int32).reshape(-1)
-    if not hasattr(angles, "is_cuda"):
-        angles = torch.from_numpy(np.ascontiguousarray(angles, dtype=np.float64))
-    angles = angles.to(device=dev, dtype=torch.float64).contiguous()
+    angles = _device_tensor(angles, torch.float64)
     if angles.ndim != 2:
         raise ValueError(f"fourier_dag: angles must be [B, n_columns], got shape {tuple(angles.shape)}")
     B, n_columns = int(angles.shape[0]), int(angles.shape[1])
@@ -1132,12 +1125,11 @@ def fourier_dag(nodes, levels, roots, root_phase, dims, angles, workspace=None):
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
     out = torch.empty((B, len(roots), F), dtype=torch.complex128, device=dev)
-    host = lambda a: C.c_void_p(a.ctypes.data) if a.size else None  # noqa: E731
     check(lib().qmle_fourier_dag(
-        host(nodes), len(nodes), host(levels), len(levels), host(roots), host(root_phase), len(roots), host(dims),
-        len(dims), C.c_void_p(angles.data_ptr()) if angles.numel() else None, n_columns, B, C.c_void_p(out.data_ptr()),
-        C.c_void_p(workspace.data_ptr()), int(workspace.numel() * workspace.element_size()), _stream_ptr()),
-        "qmle_fourier_dag")
+        _host_ptr(nodes), len(nodes), _host_ptr(levels), len(levels), _host_ptr(roots), _host_ptr(root_phase),
+        len(roots), _host_ptr(dims), len(dims), C.c_void_p(angles.data_ptr()) if angles.numel() else None, n_columns, B,
+        C.c_void_p(out.data_ptr()), C.c_void_p(workspace.data_ptr()),
+        int(workspace.numel() * workspace.element_size()), _stream_ptr()), "qmle_fourier_dag")
     return out
 
 

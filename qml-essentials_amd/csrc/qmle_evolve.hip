@@ -28,6 +28,7 @@
 // bound (nu / m)^k / k! of the next term falls below 1e-19, at most 24 terms: the count follows from the norm, decided
 // before the first product, never from the iterates.  Rows whose nu is not finite or exceeds 2^15 come back as NaN.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "qmle_host.h"
@@ -39,6 +40,9 @@ constexpr int kEvolveMaxTerms = 16;     // Hermitian terms per call (they travel
 constexpr int kEvolveThreads = 256;
 constexpr double kEvolveTheta = 0.5;    // norm of one part of the exponent
 constexpr double kEvolveMaxNorm = 32768.0;
+// the two Gauss-Legendre nodes of an order-4 step and their weights in Omega_a (Omega_b: exchanged)
+constexpr double kC1 = 0.5 - 0.28867513459481288225, kC2 = 0.5 + 0.28867513459481288225;    // 1/2 -+ sqrt(3)/6
+constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;  // 1/4 +- sqrt(3)/6
 
 // the terms, packed per term as DIM real diagonal entries, then the real and the imaginary parts of the DIM (DIM - 1) / 2
 // entries above the diagonal in row-major order -- DIM * DIM doubles
@@ -255,7 +259,6 @@ __global__ __launch_bounds__(kEvolveThreads) void k_evolve_magnus(const EvolveTe
   constexpr int NODES = ORDER == 4 ? 2 : 1;
   const double h = h_rows[row];
   const double *__restrict__ c = coef + ((size_t)row * n_steps * NODES + (size_t)s_begin * NODES) * n_terms;
-  constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;  // 1/4 +- sqrt(3)/6
   CMat<DIM> U;
   set_identity(U);
   Herm<DIM> G;
@@ -373,6 +376,26 @@ __host__ __device__ __forceinline__ bool pulse_step(double gx, double gy, CMat<2
   return fabs(gx) + fabs(gy) <= kEvolveMaxNorm;
 }
 
+// what a work item of the pulse kernels is: its solve's row, its lane of the solve and that lane's run of steps
+struct PulseItem {
+  double p0, p1, p2, w, T;
+  bool axis_y, live;  // (a solve's lanes are live or idle together: lanes divides the block)
+  int solve, lane, s_begin, s_end;
+};
+__device__ __forceinline__ PulseItem pulse_item(const double *__restrict__ solves, const PulseLaunch &L) {
+  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
+  const long long solve_ll = gid / L.lanes;
+  PulseItem I;
+  I.lane = (int)(gid - solve_ll * L.lanes);
+  I.live = solve_ll < L.n_solves;
+  I.solve = I.live ? (int)solve_ll : L.n_solves - 1;
+  const double *__restrict__ q = solves + (size_t)I.solve * 8;
+  I.p0 = q[0], I.p1 = q[1], I.p2 = q[2], I.w = q[3], I.T = q[4], I.axis_y = q[5] != 0.0;
+  I.s_begin = (int)((long long)I.lane * L.n_steps / L.lanes);
+  I.s_end = (int)((long long)(I.lane + 1) * L.n_steps / L.lanes);
+  return I;
+}
+
 // One work item per (solve, lane of the solve); a block holds kEvolveThreads / lanes solves.
 template <int ORDER, int ENV, int MODE>
 __global__ __launch_bounds__(kEvolveThreads) void k_pulse_unitaries(const double *__restrict__ solves, const PulseLaunch L,
@@ -380,19 +403,9 @@ __global__ __launch_bounds__(kEvolveThreads) void k_pulse_unitaries(const double
                                                                     const void *__restrict__ prev,
                                                                     double *__restrict__ err) {
   const int lanes = L.lanes, n_steps = L.n_steps;
-  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
-  const long long solve_ll = gid / lanes;
-  const int lane = (int)(gid - solve_ll * lanes);
-  const bool live = solve_ll < L.n_solves;  // (a solve's lanes are live or idle together: lanes divides the block)
-  const int solve = live ? (int)solve_ll : L.n_solves - 1;
-  const double *__restrict__ q = solves + (size_t)solve * 8;
-  const double p0 = q[0], p1 = q[1], p2 = q[2], w = q[3], T = q[4];
-  const bool axis_y = q[5] != 0.0;
+  const auto [p0, p1, p2, w, T, axis_y, live, solve, lane, s_begin, s_end] = pulse_item(solves, L);
   const double span = (ENV == kEnvSquare || ENV == kEnvCosine) ? fmin(T, p1) : T;
   const double h = span / (double)n_steps;
-  const int s_begin = (int)((long long)lane * n_steps / lanes), s_end = (int)((long long)(lane + 1) * n_steps / lanes);
-  constexpr double kC1 = 0.5 - 0.28867513459481288225, kC2 = 0.5 + 0.28867513459481288225;  // 1/2 -+ sqrt(3)/6
-  constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;  // 1/4 +- sqrt(3)/6
   CMat<2> U;
   set_identity(U);
   bool ok = true;
@@ -651,21 +664,11 @@ __global__ __launch_bounds__(kEvolveThreads) void k_pulse_jac(const double *__re
   constexpr unsigned TANGENTS = ENV == kEnvDrag ? 0x1fu : 0x1bu;  // (no p2 without a third envelope parameter)
   constexpr bool kSupport = ENV == kEnvSquare || ENV == kEnvCosine;
   const int lanes = L.lanes, n_steps = L.n_steps;
-  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
-  const long long solve_ll = gid / lanes;
-  const int lane = (int)(gid - solve_ll * lanes);
-  const bool live = solve_ll < L.n_solves;
-  const int solve = live ? (int)solve_ll : L.n_solves - 1;
-  const double *__restrict__ q = solves + (size_t)solve * 8;
-  const double p0 = q[0], p1 = q[1], p2 = q[2], w = q[3], T = q[4];
-  const bool axis_y = q[5] != 0.0;
+  const auto [p0, p1, p2, w, T, axis_y, live, solve, lane, s_begin, s_end] = pulse_item(solves, L);
   const bool width_ends = kSupport && p1 < T;  // the grid ends at the width; a tie counts as T
   const double span = kSupport ? fmin(T, p1) : T;
   const double h = span / (double)n_steps, dh = 1.0 / (double)n_steps;
   const double dh_p1 = width_ends ? dh : 0.0, dh_T = width_ends ? 0.0 : dh;
-  const int s_begin = (int)((long long)lane * n_steps / lanes), s_end = (int)((long long)(lane + 1) * n_steps / lanes);
-  constexpr double kC1 = 0.5 - 0.28867513459481288225, kC2 = 0.5 + 0.28867513459481288225;
-  constexpr double kA1 = 0.25 + 0.28867513459481288225, kA2 = 0.25 - 0.28867513459481288225;
   PulseJac J;
   set_identity(J.U);
 #pragma unroll
@@ -958,6 +961,47 @@ template <int DIM> void pack_terms(const double *h_terms, int n_terms, EvolveTer
   }
 }
 
+// the lanes of a row (lanes_per_row, 0 = evolve_auto_lanes) and the grid of one work item per (row, lane); false for
+// another lane count or more blocks than grid.x holds.  rows and n_steps are >= 1.
+bool evolve_launch_shape(int rows, int n_steps, int lanes_per_row, int &lanes, dim3 &grid) {
+  if (lanes_per_row != 0 && lanes_per_row != 1 && lanes_per_row != 4 && lanes_per_row != 16 && lanes_per_row != 64)
+    return false;
+  lanes = lanes_per_row ? lanes_per_row : evolve_auto_lanes(rows, n_steps);
+  const long long items = (long long)rows * lanes;
+  grid = dim3(grid_for((uint64_t)items, kEvolveThreads));
+  return items <= (1ll << 31) - kEvolveThreads;
+}
+
+// what both pulse entry points refuse (QMLE_OK or the error code), then L.lanes and the grid
+int pulse_launch(const double *d_solves, const void *d_out, int order, int lanes_per_solve, PulseLaunch &L, dim3 &grid) {
+  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
+  if (L.envelope < 0 || L.envelope >= kEnvCount || L.mode < 0 || L.mode >= kModeCount) return QMLE_ERR_UNSUPPORTED;
+  if (!d_solves || !d_out || L.n_solves < 1 || L.n_steps < 1 || !(fabs(L.omega_c) <= 1e300) || !(fabs(L.omega_q) <= 1e300))
+    return QMLE_ERR_INVALID_ARG;
+  return evolve_launch_shape(L.n_solves, L.n_steps, lanes_per_solve, L.lanes, grid) ? QMLE_OK : QMLE_ERR_INVALID_ARG;
+}
+
+// f(order, envelope, mode) with the three run-time values as std::integral_constant, for the kernels' template arguments
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F> void dispatch_pulse(int order, int envelope, int mode, F f) {
+  auto by_mode = [&](auto o, auto e) {
+    if (mode == kModeRwa) f(o, e, Int<kModeRwa>{});
+    else if (mode == kModeLab) f(o, e, Int<kModeLab>{});
+    else f(o, e, Int<kModeDrive>{});
+  };
+  auto by_envelope = [&](auto o) {
+    switch (envelope) {
+      case kEnvGaussian: by_mode(o, Int<kEnvGaussian>{}); break;
+      case kEnvSquare: by_mode(o, Int<kEnvSquare>{}); break;
+      case kEnvCosine: by_mode(o, Int<kEnvCosine>{}); break;
+      case kEnvDrag: by_mode(o, Int<kEnvDrag>{}); break;
+      default: by_mode(o, Int<kEnvSech>{}); break;
+    }
+  };
+  if (order == 2) by_envelope(Int<2>{});
+  else by_envelope(Int<4>{});
+}
+
 }  // namespace
 
 extern "C" {
@@ -974,20 +1018,18 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
   if (!h_terms || !d_coef || !d_h || !d_out || n_terms < 1 || n_terms > kEvolveMaxTerms || rows < 1 || n_steps < 1 ||
       (out_f64 != 0 && out_f64 != 1))
     return QMLE_ERR_INVALID_ARG;
-  if (lanes_per_row != 0 && lanes_per_row != 1 && lanes_per_row != 4 && lanes_per_row != 16 && lanes_per_row != 64)
-    return QMLE_ERR_INVALID_ARG;
   if ((long long)n_steps * (order == 4 ? 2 : 1) * n_terms > (1ll << 31) - 1) return QMLE_ERR_INVALID_ARG;
-  const int lanes = lanes_per_row ? lanes_per_row : evolve_auto_lanes(rows, n_steps);
-  const long long items = (long long)rows * lanes;
-  if (items > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
+  int lanes;
+  dim3 grid;
+  if (!evolve_launch_shape(rows, n_steps, lanes_per_row, lanes, grid)) return QMLE_ERR_INVALID_ARG;
   EvolveTerms T;
   if (dim == 2) pack_terms<2>(h_terms, n_terms, T);
   else pack_terms<4>(h_terms, n_terms, T);
   for (int t = n_terms; t < kEvolveMaxTerms; ++t)
     for (int k = 0; k < 16; ++k) T.h[t][k] = 0.0;
   hipStream_t stream = (hipStream_t)stream_;
-  const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
-#define QMLE_EVOLVE_LAUNCH(D, O)                                                                                  \
+  const dim3 block(kEvolveThreads);
+#define QMLE_EVOLVE_LAUNCH(D, O)                                                                                \
   hipLaunchKernelGGL((k_evolve_magnus<D, O>), grid, block, 0, stream, T, n_terms, d_coef, d_h, rows, n_steps, lanes, \
                      out_f64, d_out)
   if (dim == 2 && order == 2) QMLE_EVOLVE_LAUNCH(2, 2);
@@ -1002,41 +1044,15 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
 int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int mode, double omega_c, double omega_q,
                          int order, int n_steps, int lanes_per_solve, int out_f64, void *d_out, const void *d_prev,
                          double *d_err, qmle_stream stream_) {
-  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
-  if (envelope < 0 || envelope >= kEnvCount || mode < 0 || mode >= kModeCount) return QMLE_ERR_UNSUPPORTED;
-  if (!d_solves || !d_out || n_solves < 1 || n_steps < 1 || (out_f64 != 0 && out_f64 != 1) || (d_err && !d_prev) ||
-      !(fabs(omega_c) <= 1e300) || !(fabs(omega_q) <= 1e300))
-    return QMLE_ERR_INVALID_ARG;
-  if (lanes_per_solve != 0 && lanes_per_solve != 1 && lanes_per_solve != 4 && lanes_per_solve != 16 &&
-      lanes_per_solve != 64)
-    return QMLE_ERR_INVALID_ARG;
-  const int lanes = lanes_per_solve ? lanes_per_solve : evolve_auto_lanes(n_solves, n_steps);
-  const long long items = (long long)n_solves * lanes;
-  if (items > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
-  const PulseLaunch L{envelope, mode, n_solves, n_steps, lanes, out_f64, omega_c, omega_q};
+  PulseLaunch L{envelope, mode, n_solves, n_steps, 0, out_f64, omega_c, omega_q};
+  dim3 grid;
+  if (const int bad = pulse_launch(d_solves, d_out, order, lanes_per_solve, L, grid)) return bad;
+  if ((out_f64 != 0 && out_f64 != 1) || (d_err && !d_prev)) return QMLE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
-#define QMLE_PULSE_LAUNCH(O, E, M) \
-  hipLaunchKernelGGL((k_pulse_unitaries<O, E, M>), grid, block, 0, stream, d_solves, L, d_out, d_prev, d_err)
-#define QMLE_PULSE_MODES(O, E)                       \
-  do {                                               \
-    if (mode == kModeRwa) QMLE_PULSE_LAUNCH(O, E, kModeRwa); \
-    else if (mode == kModeLab) QMLE_PULSE_LAUNCH(O, E, kModeLab); \
-    else QMLE_PULSE_LAUNCH(O, E, kModeDrive);        \
-  } while (0)
-#define QMLE_PULSE_ENVELOPES(O)                                        \
-  switch (envelope) {                                                  \
-    case kEnvGaussian: QMLE_PULSE_MODES(O, kEnvGaussian); break;       \
-    case kEnvSquare: QMLE_PULSE_MODES(O, kEnvSquare); break;           \
-    case kEnvCosine: QMLE_PULSE_MODES(O, kEnvCosine); break;           \
-    case kEnvDrag: QMLE_PULSE_MODES(O, kEnvDrag); break;               \
-    default: QMLE_PULSE_MODES(O, kEnvSech); break;                     \
-  }
-  if (order == 2) QMLE_PULSE_ENVELOPES(2)
-  else QMLE_PULSE_ENVELOPES(4)
-#undef QMLE_PULSE_ENVELOPES
-#undef QMLE_PULSE_MODES
-#undef QMLE_PULSE_LAUNCH
+  dispatch_pulse(order, envelope, mode, [&](auto o, auto e, auto m) {
+    hipLaunchKernelGGL((k_pulse_unitaries<o(), e(), m()>), grid, dim3(kEvolveThreads), 0, stream, d_solves, L, d_out,
+                       d_prev, d_err);
+  });
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
@@ -1044,40 +1060,14 @@ int qmle_pulse_unitaries(const double *d_solves, int n_solves, int envelope, int
 int qmle_pulse_unitaries_jac(const double *d_solves, int n_solves, int envelope, int mode, double omega_c,
                              double omega_q, int order, int n_steps, int lanes_per_solve, void *d_out,
                              qmle_stream stream_) {
-  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
-  if (envelope < 0 || envelope >= kEnvCount || mode < 0 || mode >= kModeCount) return QMLE_ERR_UNSUPPORTED;
-  if (!d_solves || !d_out || n_solves < 1 || n_steps < 1 || !(fabs(omega_c) <= 1e300) || !(fabs(omega_q) <= 1e300))
-    return QMLE_ERR_INVALID_ARG;
-  if (lanes_per_solve != 0 && lanes_per_solve != 1 && lanes_per_solve != 4 && lanes_per_solve != 16 &&
-      lanes_per_solve != 64)
-    return QMLE_ERR_INVALID_ARG;
-  const int lanes = lanes_per_solve ? lanes_per_solve : evolve_auto_lanes(n_solves, n_steps);
-  const long long items = (long long)n_solves * lanes;
-  if (items > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;  // grid.x
-  const PulseLaunch L{envelope, mode, n_solves, n_steps, lanes, 1, omega_c, omega_q};
+  PulseLaunch L{envelope, mode, n_solves, n_steps, 0, 1, omega_c, omega_q};
+  dim3 grid;
+  if (const int bad = pulse_launch(d_solves, d_out, order, lanes_per_solve, L, grid)) return bad;
   hipStream_t stream = (hipStream_t)stream_;
-  const dim3 grid(grid_for((uint64_t)items, kEvolveThreads)), block(kEvolveThreads);
-#define QMLE_PULSE_LAUNCH(O, E, M) \
-  hipLaunchKernelGGL((k_pulse_jac<O, E, M>), grid, block, 0, stream, d_solves, L, (double2 *)d_out)
-#define QMLE_PULSE_MODES(O, E)                       \
-  do {                                               \
-    if (mode == kModeRwa) QMLE_PULSE_LAUNCH(O, E, kModeRwa); \
-    else if (mode == kModeLab) QMLE_PULSE_LAUNCH(O, E, kModeLab); \
-    else QMLE_PULSE_LAUNCH(O, E, kModeDrive);        \
-  } while (0)
-#define QMLE_PULSE_ENVELOPES(O)                                        \
-  switch (envelope) {                                                  \
-    case kEnvGaussian: QMLE_PULSE_MODES(O, kEnvGaussian); break;       \
-    case kEnvSquare: QMLE_PULSE_MODES(O, kEnvSquare); break;           \
-    case kEnvCosine: QMLE_PULSE_MODES(O, kEnvCosine); break;           \
-    case kEnvDrag: QMLE_PULSE_MODES(O, kEnvDrag); break;               \
-    default: QMLE_PULSE_MODES(O, kEnvSech); break;                     \
-  }
-  if (order == 2) QMLE_PULSE_ENVELOPES(2)
-  else QMLE_PULSE_ENVELOPES(4)
-#undef QMLE_PULSE_ENVELOPES
-#undef QMLE_PULSE_MODES
-#undef QMLE_PULSE_LAUNCH
+  dispatch_pulse(order, envelope, mode, [&](auto o, auto e, auto m) {
+    hipLaunchKernelGGL((k_pulse_jac<o(), e(), m()>), grid, dim3(kEvolveThreads), 0, stream, d_solves, L,
+                       (double2 *)d_out);
+  });
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }

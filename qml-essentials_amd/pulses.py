@@ -467,6 +467,19 @@ def _first(pulse_params):
     return float(np.asarray(pulse_params, dtype=np.float64).reshape(-1)[0])
 
 
+def _tracked_terms(terms, what: str):
+    """The tangent terms ``[(leaf, index, coef)]`` of a recorded argument, refused when the recorder lost track."""
+    if terms is None:
+        raise NotImplementedError(f"qoc: {what} depends on the pulse parameters in a way the tape recorder does not "
+                                  "track (only sums, constant factors and products are)")
+    return terms
+
+
+# kernel slot (0-based among the five derivatives p0, p1, p2, w, T) of the PulseRotation arguments T and w; the
+# envelope parameters come first, in order (PulseRotation._arg_tangents: envelope parameters, then T, then w)
+_SLOT_T, _SLOT_W = 4, 3
+
+
 class PulseRotation(Operation):
     """An RX / RY pulse leaf: the request ``(axis, envelope parameters, w, T)`` under the envelope, the coefficient
     mode (``"rwa"``, ``"lab"`` or ``"drive"``) and the frequencies that were active when it was recorded.  Its matrix
@@ -521,6 +534,13 @@ class PulseRotation(Operation):
             t[:, k] = v
         t[:, 3], t[:, 4], t[:, 5] = self.w, self.T, 0.0 if self.axis == "X" else 1.0
         return t
+
+    def jacobian_terms(self) -> list:
+        """``[(slot, index, coef)]``: the solve's derivative in kernel slot ``slot``, times ``coef`` ``[C]``, adds to
+        the derivative by leaf element ``index`` -- argument by argument (envelope parameters, ``T``, ``w``)."""
+        slots = list(range(len(self.env_params))) + [_SLOT_T, _SLOT_W]
+        return [(slot, index, coef) for slot, terms in zip(slots, self._arg_tangents)
+                for _, index, coef in _tracked_terms(terms, f"an argument of {self!r}")]
 
     def _resolved(self) -> None:
         if self._matrix is None:

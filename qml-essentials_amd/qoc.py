@@ -10,14 +10,17 @@ the one expensive ingredient -- the pulse solves -- comes with its exact grid se
 The evaluator (:func:`circuit_unitaries`).  A <= 2-qubit pulse circuit is recorded once per rotation angle with the
 ordinary tape recorder; the pulse parameters pass as a ``Batched.leaf`` whose batch axis holds the candidates, so the
 closed-form leaves (``RZ(2 p w)``, ``ControlledPhaseShift(-pi^2 p)``) carry their linear tangents as they always do.
-Then
-  1. every ``PulseRotation`` request of all scripts, angles and candidates goes into one table, identical rows once;
-  2. the table is solved by the ``solver`` callable (default :func:`pulses.solve_with_jacobian`; tests inject a NumPy
-     one) -- :data:`LAUNCH_GROUPS` counts these calls, normally one per evaluation whatever the number of candidates;
-  3. a request's five argument derivatives are mapped onto the leaf indices its arguments came from
-     (``PulseRotation._arg_tangents``);
+Both routes share steps 1 and 2 and the classification of step 3; step 4 exists twice, on purpose:
+  1. :func:`_record_tapes` records, and every ``PulseRotation`` request of all scripts, angles and candidates goes
+     into one table per launch group, identical rows once (:func:`_unique_solves`);
+  2. the tables are solved by the ``solver`` callable (default :func:`pulses.solve_with_jacobian`; tests inject a
+     NumPy one) in :func:`_solve_groups` -- :data:`LAUNCH_GROUPS` counts these calls, normally one per evaluation
+     whatever the number of candidates;
+  3. :func:`_op_terms` names an op's kind and maps its derivatives onto the leaf indices its arguments came from (a
+     request's five argument derivatives: ``PulseRotation.jacobian_terms``), :func:`_placement` its wires;
   4. the circuit's ``d x d`` unitary and its ``[P, d, d]`` Jacobian are composed densely in NumPy complex128 by the
-     product rule.
+     product rule (:func:`_op_matrices` and the loop of :func:`circuit_unitaries`: the independent check of the
+     device route's tables and kernel).
 Basis-state preparations are columns of that unitary and ``|+>`` preparations ordinary constant gates of the tape: no
 script is executed ``2^n`` times.
 
@@ -25,10 +28,11 @@ All candidates of a stage-0 scan step and all restarts of a stage-1 step advance
 The optimiser is AdamW with optax's defaults, global-norm clipping per candidate row and the warmup-cosine schedule,
 written out in NumPy; parameters optimised in log space use ``d/d log p = p d/dp``.
 
-Composition on the device (``compose="device"``).  Steps 3 and 4 also exist as one launch of
+Composition on the device (``compose="device"``).  Step 4 also exists as one launch of
 ``qmle_compose_circuits``: :func:`_compose_tables` turns the recorded tapes of any number of jobs into a circuit, an op
 and a tangent-term table, the solver's ``[n, 6, 4]`` result stays on the device, and only overlaps (the cost
-functions) or matrices (:func:`circuit_unitaries`) come back -- :data:`COMPOSE_LAUNCHES` counts these launches.  The
+functions, through :func:`_overlaps` on either route) or matrices (:func:`circuit_unitaries`) come back --
+:data:`COMPOSE_LAUNCHES` counts these launches.  The
 per-gate entry points default to ``"host"``; the joint path (:func:`joint_unitary_cost_fn`, ``QOC.optimize_joint``:
 one shared leaf vector against the weighted unitary costs of several target gates) defaults to ``"device"`` with the
 default solver and evaluates all its gates with one solver call and one composition launch.
@@ -52,7 +56,7 @@ from .batching import Batched
 from .evolution import Evolution
 from .gates import Gates, PulseEnvelope, PulseInformation
 from .operations import Barrier, ControlledPhaseShift, Operation, _Rotation
-from .pulses import PulseRotation
+from .pulses import PulseRotation, _tracked_terms
 from .script import Script
 from .tape import batch_context
 from .utils import as_key
@@ -64,68 +68,69 @@ COMPOSE_LAUNCHES = 0  # launches of qmle_compose_circuits since import (one per 
 
 _PAULI = {"X": np.array([[0, 1], [1, 0]], dtype=np.complex128), "Y": np.array([[0, -1j], [1j, 0]]),
           "Z": np.array([[1, 0], [0, -1]], dtype=np.complex128)}
-# kernel slot (0-based among the five derivatives p0, p1, p2, w, T) of a PulseRotation argument: the envelope
-# parameters in order, then T, then w (the order of PulseRotation._arg_tangents)
-_SLOT_T, _SLOT_W = 4, 3
 
 
 # ---- the evaluator ----------------------------------------------------------------------------------------------------
+# (wires of the circuit, wires of the op) -> ``qmle_compose_op.placement``: 0 the one wire of a 1-wire circuit; of two
+# wires 1 / 2 wire 0 / 1 and 3 / 4 the pair in the order (0, 1) / (1, 0)
+_PLACEMENTS = {(1, (0,)): 0, (2, (0,)): 1, (2, (1,)): 2, (2, (0, 1)): 3, (2, (1, 0)): 4}
+
+
+def _placement(wires: Sequence[int], n: int) -> int:
+    at = _PLACEMENTS.get((n, tuple(wires)))
+    if at is None:
+        raise NotImplementedError(f"qoc evaluates circuits on 1 or 2 wires; got wires {list(wires)} of {n}")
+    return at
+
+
 def _embed(m: np.ndarray, wires: Sequence[int], n: int) -> np.ndarray:
     """``[..., 2^k, 2^k]`` on ``wires`` -> ``[..., 2^n, 2^n]`` on wires 0..n-1 (wire 0 the most significant)."""
-    wires = list(wires)
-    if wires == list(range(n)):
+    at = _placement(wires, n)
+    if at in (0, 3):
         return m
-    eye = np.eye(2, dtype=np.complex128)
-    if n == 2 and wires == [0]:
-        return np.einsum("...ab,cd->...acbd", m, eye).reshape(m.shape[:-2] + (4, 4))
-    if n == 2 and wires == [1]:
-        return np.einsum("ab,...cd->...acbd", eye, m).reshape(m.shape[:-2] + (4, 4))
-    if n == 2 and wires == [1, 0]:
+    if at == 4:
         t = m.reshape(m.shape[:-2] + (2, 2, 2, 2))
         return np.swapaxes(np.swapaxes(t, -4, -3), -2, -1).reshape(m.shape[:-2] + (4, 4))
-    raise NotImplementedError(f"qoc evaluates circuits on 1 or 2 wires; got wires {wires} of {n}")
+    eye = np.eye(2, dtype=np.complex128)
+    if at == 1:
+        return np.einsum("...ab,cd->...acbd", m, eye).reshape(m.shape[:-2] + (4, 4))
+    return np.einsum("ab,...cd->...acbd", eye, m).reshape(m.shape[:-2] + (4, 4))
 
 
-def _tangent_terms(terms, what: str):
-    if terms is None:
-        raise NotImplementedError(f"qoc: {what} depends on the pulse parameters in a way the tape recorder does not "
-                                  "track (only sums, constant factors and products are)")
-    return terms
+def _op_terms(o: Operation):
+    """``(kind, [(slot, index, coef)])`` of one recorded operation: its name among ``_native.COMPOSE_KINDS`` and the
+    leaf elements its matrix depends on (slot: the solve's derivative for a pulse, 0 otherwise)."""
+    if isinstance(o, PulseRotation):
+        return "PULSE", o.jacobian_terms()
+    terms = [(0, index, coef) for name, tans in o.__dict__.get("_tangents", {}).items()
+             for _, index, coef in _tracked_terms(tans, f"{name} of {o!r}")]
+    if not terms:
+        return "CONST", terms
+    if isinstance(o, _Rotation):
+        return "ROT_" + o._axis, terms
+    if isinstance(o, ControlledPhaseShift):
+        return "CPHASE", terms
+    raise NotImplementedError(f"qoc: no derivative rule for {o!r} with parameters that depend on the pulse parameters")
 
 
 def _op_matrices(o: Operation, solved: Optional[tuple], n_params: int, C: int):
     """(M [1 or C, dk, dk], {param index: dM [C, dk, dk]}) of one recorded operation."""
     d_m: Dict[int, np.ndarray] = {}
-
-    def add(index: int, term: np.ndarray) -> None:
-        term = np.broadcast_to(term, (C,) + term.shape[-2:])
-        d_m[index] = d_m[index] + term if index in d_m else np.array(term)
-
-    if isinstance(o, PulseRotation):
-        U, J = solved
-        n_env = len(o.env_params)
-        slots = list(range(n_env)) + [_SLOT_T, _SLOT_W]
-        for slot, terms in zip(slots, o._arg_tangents):
-            for _, index, coef in _tangent_terms(terms, f"an argument of {o!r}"):
-                add(index, coef[:, None, None] * J[:, slot])
-        return U, d_m
-    m = np.asarray(o.matrix, dtype=np.complex128)
-    m = m[None] if m.ndim == 2 else m
-    tangents = o.__dict__.get("_tangents", {})
-    for name, terms in tangents.items():
-        terms = _tangent_terms(terms, f"{name} of {o!r}")
-        if not terms:
-            continue
-        if isinstance(o, _Rotation):
-            dm = (-0.5j * _PAULI[o._axis]) @ m
-        elif isinstance(o, ControlledPhaseShift):
+    kind, terms = _op_terms(o)
+    if kind == "PULSE":
+        m, J = solved
+    else:
+        m = np.asarray(o.matrix, dtype=np.complex128)
+        m = m[None] if m.ndim == 2 else m
+        if kind == "CPHASE":
             dm = np.zeros_like(m)
             dm[..., 3, 3] = 1j * m[..., 3, 3]
-        else:
-            raise NotImplementedError(f"qoc: no derivative rule for {o!r} with parameters that depend on the pulse "
-                                      "parameters")
-        for _, index, coef in terms:
-            add(index, coef[:, None, None] * dm)
+        elif terms:
+            dm = (-0.5j * _PAULI[o._axis]) @ m
+    for slot, index, coef in terms:
+        term = coef[:, None, None] * (J[:, slot] if kind == "PULSE" else dm)
+        term = np.broadcast_to(term, (C,) + term.shape[-2:])
+        d_m[index] = d_m[index] + term if index in d_m else np.array(term)
     return m, d_m
 
 
@@ -147,7 +152,7 @@ class _ComposeTables:
         self._n_mats = self._n_coefs = self._n_targets = 0
         self._mat_at: Dict[bytes, int] = {}
         self._coef_at: Dict = {}
-        self.groups: Dict[tuple, list] = {}   # launch group -> [(row offset of the op, its solves [1 or C, 8])]
+        self.requests: List[PulseRotation] = []  # the pulse ops, in the order of their entries in ``rows``
         self.index: List[List[List[int]]] = []  # [job][script][angle] -> circuit
         self.ov_len = self.full_len = 0
 
@@ -183,39 +188,16 @@ class _ComposeTables:
         return self._n_targets - V.size
 
     def add_op(self, o: Operation, n: int) -> None:
-        wires = list(o.wires)
-        if n == 1 and wires == [0]:
-            placement = 0
-        elif n == 2 and wires in ([0], [1], [0, 1], [1, 0]):
-            placement = {(0,): 1, (1,): 2, (0, 1): 3, (1, 0): 4}[tuple(wires)]
+        placement, t0 = _placement(o.wires, n), len(self.terms)
+        kind, terms = _op_terms(o)
+        if kind == "PULSE":
+            at, stride = len(self.requests) * self.C, 0  # (its C entries of ``rows``, which solve_tables fills)
+            self.requests.append(o)
         else:
-            raise NotImplementedError(f"qoc evaluates circuits on 1 or 2 wires; got wires {wires} of {n}")
-        kinds, t0, terms = self.N.COMPOSE_KINDS, len(self.terms), []
-        if isinstance(o, PulseRotation):
-            kind, stride, at = kinds["PULSE"], 0, len(self.rows)
-            solves = o.solves()
-            self.rows.append(None)  # (filled in once the launch group's table is known)
-            self.groups.setdefault(o.group(), []).append((at, solves))
-            slots = list(range(len(o.env_params))) + [_SLOT_T, _SLOT_W]
-            for slot, tans in zip(slots, o._arg_tangents):
-                terms += [(slot, index, coef) for _, index, coef in _tangent_terms(tans, f"an argument of {o!r}")]
-            at *= self.C
-        else:
-            for name, tans in o.__dict__.get("_tangents", {}).items():
-                terms += [(0, index, coef) for _, index, coef in _tangent_terms(tans, f"{name} of {o!r}")]
-            if not terms:
-                kind = kinds["CONST"]
-            elif isinstance(o, _Rotation):
-                kind = kinds["ROT_" + o._axis]
-            elif isinstance(o, ControlledPhaseShift):
-                kind = kinds["CPHASE"]
-            else:
-                raise NotImplementedError(f"qoc: no derivative rule for {o!r} with parameters that depend on the pulse "
-                                          "parameters")
             at, stride = self.matrix(o.matrix)
         for slot, index, coef in terms:
             self.terms.append((slot, int(index), self.coef(coef)))
-        self.ops.append((kind, placement, at, stride, t0, len(self.terms)))
+        self.ops.append((self.N.COMPOSE_KINDS[kind], placement, at, stride, t0, len(self.terms)))
 
     def add_circuit(self, tape: Sequence[Operation], n: int, P: int, V: Optional[np.ndarray]) -> int:
         b, d, C = len(self.ops), 2 ** n, self.C
@@ -231,18 +213,10 @@ class _ComposeTables:
     def solve_tables(self):
         """-> [(launch group, its table of distinct solves)]; fills ``rows`` with indices into the tables stacked in
         that order."""
-        out, base = [], 0
-        for key, requests in self.groups.items():
-            table, inverse = np.unique(np.concatenate([s for _, s in requests]), axis=0, return_inverse=True)
-            inverse = np.asarray(inverse).reshape(-1)
-            at = 0
-            for slot, solves in requests:
-                idx = inverse[at:at + len(solves)] + base
-                at += len(solves)
-                self.rows[slot] = np.broadcast_to(idx, (self.C,)).astype(np.int32)
-            out.append((key, table))
-            base += len(table)
-        return out
+        tables, rows = _unique_solves(self.requests)
+        base = np.cumsum([0] + [len(table) for _, table in tables])
+        self.rows = [np.broadcast_to(idx + base[g], (self.C,)).astype(np.int32) for g, idx in rows]
+        return tables
 
     def arrays(self):
         N = self.N
@@ -269,6 +243,40 @@ def _n_wires(script: Script, per_angle) -> int:
     return script._n_qubits or 1 + max(w for tape in per_angle for o in tape for w in o.wires)
 
 
+def _unique_solves(requests: Sequence[PulseRotation]):
+    """Every request of an evaluation in one table per launch group, identical rows once -> ``([(launch group, its
+    table of distinct solves)], per request (number of its table, indices of its rows in that table))``."""
+    groups: Dict[tuple, list] = {}
+    for k, o in enumerate(requests):
+        groups.setdefault(o.group(), []).append((k, o.solves()))
+    tables, rows = [], [None] * len(requests)
+    for g, (key, members) in enumerate(groups.items()):
+        table, inverse = np.unique(np.concatenate([s for _, s in members]), axis=0, return_inverse=True)
+        inverse = np.asarray(inverse).reshape(-1)
+        at = 0
+        for k, solves in members:
+            rows[k] = (g, inverse[at:at + len(solves)])
+            at += len(solves)
+        tables.append((key, table))
+    return tables, rows
+
+
+def _solve_groups(tables, solver: Optional[Callable], on_device: bool = False) -> list:
+    """ONE solver call per launch group of :func:`_unique_solves`, counted in :data:`LAUNCH_GROUPS` -> per group
+    ``(U [n, 2, 2], J [n, 5, 2, 2])`` on the host; ``on_device`` (the default solver only): the ``[n, 6, 4]`` device
+    tensor of :func:`pulses.solve_with_jacobian` instead."""
+    global LAUNCH_GROUPS
+    parts = []
+    for (envelope, mode, omega_c, omega_q), table in tables:
+        LAUNCH_GROUPS += 1
+        if on_device:
+            parts.append(pulses.solve_with_jacobian(table, envelope, mode, omega_c, omega_q, on_device=True)[0])
+        else:
+            U, J, _ = (solver or pulses.solve_with_jacobian)(table, envelope, mode, omega_c, omega_q)
+            parts.append((np.asarray(U), np.asarray(J)))
+    return parts
+
+
 def _compose_tables(jobs: Sequence[tuple], ws: np.ndarray) -> _ComposeTables:
     """Record the tapes of every job ``(scripts, pulse_params [C, P_g])`` or ``(scripts, pulse_params, targets)`` --
     ``targets[i]`` ``[S, d, d]`` the target unitaries of script i -- at the angles ``ws`` and emit ONE set of tables:
@@ -292,17 +300,10 @@ def _compose_tables(jobs: Sequence[tuple], ws: np.ndarray) -> _ComposeTables:
 def _solve_tables(tab: _ComposeTables, solver: Optional[Callable]) -> list:
     """ONE solver call per launch group of ``tab`` -> the groups' ``[n, 6, 4]`` results in the order that ``tab.rows``
     indexes: device tensors from the default solver, host arrays from an injected one."""
-    global LAUNCH_GROUPS
-    parts = []
-    for (envelope, mode, omega_c, omega_q), table in tab.solve_tables():
-        LAUNCH_GROUPS += 1
-        if solver is None:
-            parts.append(pulses.solve_with_jacobian(table, envelope, mode, omega_c, omega_q, on_device=True)[0])
-        else:
-            U, J, _ = solver(table, envelope, mode, omega_c, omega_q)
-            host = np.concatenate([np.asarray(U)[:, None], np.asarray(J)], axis=1).reshape(len(table), 6, 4)
-            parts.append(np.ascontiguousarray(host, dtype=np.complex128))
-    return parts
+    if solver is None:
+        return _solve_groups(tab.solve_tables(), None, on_device=True)
+    return [np.ascontiguousarray(np.concatenate([U[:, None], J], axis=1).reshape(len(U), 6, 4), dtype=np.complex128)
+            for U, J in _solve_groups(tab.solve_tables(), solver)]
 
 
 def _compose_on_device(tab: _ComposeTables, solver: Optional[Callable], column_mask: int, want_ov: bool,
@@ -323,12 +324,23 @@ def _compose_on_device(tab: _ComposeTables, solver: Optional[Callable], column_m
     return (None if ov is None else N.to_host(ov)), (None if full is None else N.to_host(full))
 
 
-def _overlaps_on_device(jobs: Sequence[tuple], ws: np.ndarray, solver: Optional[Callable], column_mask: int):
+def _overlaps(jobs: Sequence[tuple], ws: np.ndarray, solver: Optional[Callable], column_mask: int, compose: str):
     """For jobs ``(scripts, pulse_params, targets)``: per job and script ``(ov [C, S], dov [C, S, P])``, the overlaps
-    ``sum_{j in mask} sum_i conj(V[i][j]) U[i][j]`` of :func:`_compose_on_device`."""
+    ``sum_{j in mask} sum_i conj(V[i][j]) U[i][j]`` -- of :func:`_compose_on_device` for all jobs at once, or
+    contracted here from the host route's unitaries, job by job."""
+    out = []
+    if compose == "host":
+        for scripts, pp, targets in jobs:
+            res = []
+            for (U, dU), V in zip(circuit_unitaries(scripts, ws, pp, solver, "host"), targets):
+                k = min(U.shape[-1], int(column_mask).bit_length())  # up to the last selected column: views, no copy
+                Vc = np.conj(np.asarray(V)[..., :k]) * [column_mask >> j & 1 for j in range(k)]
+                res.append((np.einsum("sij,csij->cs", Vc, U[..., :k]), np.einsum("sij,cspij->csp", Vc, dU[..., :k])))
+            out.append(res)
+        return out
     tab = _compose_tables(jobs, ws)
     ov, _ = _compose_on_device(tab, solver, column_mask, True, False)
-    C, out = tab.C, []
+    C = tab.C
     for job, per_script in zip(jobs, tab.index):
         P = np.asarray(job[1]).shape[1]
         res = []
@@ -349,7 +361,6 @@ def circuit_unitaries(scripts: Sequence[Script], ws: np.ndarray, pulse_params: O
     ``solver(table, envelope, mode, omega_c, omega_q) -> (U, J, steps)`` per launch group.  ``compose``: ``"host"``
     composes in NumPy, ``"device"`` in one launch of ``qmle_compose_circuits`` (circuits without pulse parameters
     have nothing to differentiate and are composed on the host either way)."""
-    global LAUNCH_GROUPS
     _check_compose(compose)
     ws = np.asarray(ws, dtype=np.float64).reshape(-1)
     if compose == "device" and pulse_params is not None:
@@ -364,45 +375,20 @@ def circuit_unitaries(scripts: Sequence[Script], ws: np.ndarray, pulse_params: O
             dU = np.stack([full[tab.circuits[k][8]:][:C * P * d * d].reshape(C, P, d, d) for k in ids], axis=1)
             out.append((U, dU.reshape(C, S, P, d, d)))
         return out
-    solver = pulses.solve_with_jacobian if solver is None else solver
     with_pp = pulse_params is not None
     if with_pp:
         pulse_params = np.asarray(pulse_params, dtype=np.float64)
         C, P = pulse_params.shape
     else:
         C, P = 1, 0
-    tapes = []
-    for script in scripts:
-        per_angle = []
-        for w in ws:
-            with batch_context(C):
-                tape = script._record(float(w), Batched.leaf(pulse_params, 0)) if with_pp else script._record(float(w))
-            per_angle.append([o for o in tape if not isinstance(o, Barrier)])
-        tapes.append(per_angle)
-    # 1. one table per launch group
-    groups: Dict[tuple, list] = {}
-    for per_angle in tapes:
-        for tape in per_angle:
-            for o in tape:
-                if isinstance(o, PulseRotation):
-                    groups.setdefault(o.group(), []).append(o)
-    solved: Dict[int, tuple] = {}
-    for (envelope, mode, omega_c, omega_q), ops in groups.items():
-        rows = [o.solves() for o in ops]
-        table, inverse = np.unique(np.concatenate(rows), axis=0, return_inverse=True)
-        inverse = np.asarray(inverse).reshape(-1)
-        # 2. one solver call
-        LAUNCH_GROUPS += 1
-        U, J, _ = solver(table, envelope, mode, omega_c, omega_q)
-        at = 0
-        for o, r in zip(ops, rows):
-            idx = inverse[at:at + len(r)]
-            at += len(r)
-            solved[id(o)] = (U[idx], J[idx])
-    # 3. + 4. compose
+    tapes = _record_tapes(scripts, ws, pulse_params, C)
+    requests = [o for per_angle in tapes for tape in per_angle for o in tape if isinstance(o, PulseRotation)]
+    tables, rows = _unique_solves(requests)
+    parts = _solve_groups(tables, solver)
+    solved = {id(o): (parts[g][0][idx], parts[g][1][idx]) for o, (g, idx) in zip(requests, rows)}
     out = []
     for script, per_angle in zip(scripts, tapes):
-        n = script._n_qubits or 1 + max(w for tape in per_angle for o in tape for w in o.wires)
+        n = _n_wires(script, per_angle)
         d = 2 ** n
         U_all = np.empty((C, len(ws), d, d), dtype=np.complex128)
         dU_all = np.zeros((C, len(ws), P, d, d), dtype=np.complex128) if with_pp else None
@@ -488,17 +474,10 @@ def fidelity_cost_fn(pulse_params, pulse_scripts, target_scripts, n_samples: int
     ws = _sample_rotation_angles(n_samples)
     target = circuit_unitaries(target_scripts, ws, None, solver)
     values, grads = [], []
-    if _check_compose(compose) == "device":  # <phi|psi> from the kernel's column 0; this cost reads <psi|phi>
-        (overlaps,) = _overlaps_on_device([(pulse_scripts, params, [V for V, _ in target])], ws, solver, 0b1)
-        overlaps = [(np.conj(ov), np.conj(dov)) for ov, dov in overlaps]
-    else:
-        overlaps = []
-        for (U, dU), (V, _) in zip(circuit_unitaries(pulse_scripts, ws, params, solver), target):
-            psi, dpsi, phi = U[..., 0], dU[..., 0], V[..., 0]  # the columns of |0..0>
-            overlaps.append((np.einsum("csd,sd->cs", np.conj(psi), phi),
-                             np.einsum("cspd,sd->csp", np.conj(dpsi), phi)))
+    # column 0, of |0..0>, gives <phi|psi>; this cost reads <psi|phi>
+    (overlaps,) = _overlaps([(pulse_scripts, params, [V for V, _ in target])], ws, solver, 0b1, _check_compose(compose))
     for ov, dov in overlaps:
-        v, g = _overlap_losses(ov, dov, 1.0)
+        v, g = _overlap_losses(np.conj(ov), np.conj(dov), 1.0)
         values.append(v)
         grads.append(g)
     mean = lambda k, parts: np.mean(np.stack([p[k] for p in parts]), axis=0)  # noqa: E731
@@ -531,8 +510,8 @@ def unitary_cost_fn(pulse_params, pulse_basis_scripts, target_basis_scripts, n_s
     _check_compose(compose)
     # (the targets do not depend on the pulse parameters: a caller that evaluates often may pass them, [S, d, d])
     V = unitaries(target_basis_scripts, None)[0] if target_unitaries is None else np.asarray(target_unitaries)
-    if compose == "device" and _one_circuit_with_basis_preps(pulse_basis_scripts, n_qubits):
-        tr, dtr = _overlaps_on_device([(pulse_basis_scripts[:1], params, [V])], ws, solver, (1 << d) - 1)[0][0]
+    if _one_circuit_with_basis_preps(pulse_basis_scripts, n_qubits):
+        tr, dtr = _overlaps([(pulse_basis_scripts[:1], params, [V])], ws, solver, (1 << d) - 1, compose)[0][0]
     else:
         U, dU = unitaries(pulse_basis_scripts, params)
         tr = np.einsum("sji,csji->cs", np.conj(V), U)
@@ -611,13 +590,13 @@ def joint_unitary_cost_fn(pulse_params, gate_specs: List[dict], n_samples: int, 
                                   "(the specs of QOC.optimize_joint do); a plain callable cannot be differentiated")
     per_gate = [np.asarray(spec["assembler"](theta), dtype=np.float64) for spec in gate_specs]
     parts = []  # per gate ((process, phase) [C], their gradients [C, P_g])
-    if compose == "device" and gate_specs and all(
+    if gate_specs and all(
             _one_circuit_with_basis_preps(spec["pulse_basis_scripts"], spec["n_qubits"]) for spec in gate_specs):
         ws = _sample_rotation_angles(n_samples)
         jobs = []
         for spec, pp in zip(gate_specs, per_gate):
             jobs.append((spec["pulse_basis_scripts"][:1], pp, [_spec_targets(spec, n_samples)]))
-        for spec, res in zip(gate_specs, _overlaps_on_device(jobs, ws, solver, 0xf)):
+        for spec, res in zip(gate_specs, _overlaps(jobs, ws, solver, 0xf, compose)):
             parts.append(_overlap_losses(res[0][0], res[0][1], float(2 ** spec["n_qubits"]) ** 2))
     else:
         for spec, pp in zip(gate_specs, per_gate):

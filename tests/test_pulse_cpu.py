@@ -329,6 +329,23 @@ def test_batched_arguments_make_per_sample_requests_and_keep_rz_tangents():
     assert np.allclose(ry.solves()[:, :3], PulseInformation.RY.params[:3])
 
 
+@pytest.mark.parametrize("envelope", P.ENVELOPES)
+def test_jacobian_terms_map_the_kernel_slots_onto_the_leaf_indices(envelope):
+    """Arguments in the order envelope parameters, T, w sit in the kernel's derivative slots 0..n_env-1, 4, 3."""
+    PulseInformation.set_envelope(envelope)
+    n_env = PulseEnvelope.get(envelope)["n_envelope_params"]
+    leaf = Batched.leaf(np.random.default_rng(5).uniform(0.5, 1.5, size=(2, n_env + 2)), 0)  # C = 2 candidates
+    with recording() as tape:
+        PulseGates.RX(leaf[n_env + 1], wires=0, pulse_params=leaf[:n_env + 1])
+        PulseGates.RX(np.cos(leaf[n_env + 1]), wires=0, pulse_params=leaf[:n_env + 1])
+    terms = tape[0].jacobian_terms()
+    assert [slot for slot, _, _ in terms] == list(range(n_env)) + [4, 3]
+    assert [index for _, index, _ in terms] == list(range(n_env + 2))
+    assert all(np.array_equal(coef, np.ones(2)) for _, _, coef in terms)
+    with pytest.raises(NotImplementedError, match="does not track"):
+        tape[1].jacobian_terms()
+
+
 # ---- the ABI (no device work: every call below is refused before the first one) ---------------------------------------
 def test_pulse_entry_point_refuses_bad_arguments_before_touching_a_device():
     import ctypes as C
