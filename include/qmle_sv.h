@@ -309,10 +309,11 @@ int qmle_run_batch_parity_w(qmle_plan *plan, const float *d_angles, int batch,
  * ((b + batch_offset) / div_k) % mod_k  (cartesian inputs x params batch, model.py:1449-1481).
  * d_leaves / strides / div / mod are HOST arrays of n_leaves <= 8 entries; everything d_* is
  * device memory.  The sum runs in fp64; d_period (may be NULL) holds one double per slot: where
- * > 0 the angle is reduced into (-period/2, period/2] before the float32 store (4 pi for the
- * rotation gates, which depend on angle / 2 only -- binary / ternary encodings scale inputs
+ * > 0, a sum beyond +-period is reduced into [-period/2, period/2] before the float32 store; a sum
+ * within +-period, the bounds included, is stored as it is (4 pi for the rotation gates, which depend on angle / 2 only -- binary / ternary encodings scale inputs
  * by up to 3^(n-1), ansaetze/encodings of model.py:804-816).  Replaces the host-side angle
- * arithmetic when params / inputs already live in HBM. */
+ * arithmetic when params / inputs already live in HBM.  batch_offset < 0: QMLE_ERR_INVALID_ARG
+ * (qmle_run_batch_map / _w answer the same for map->batch_offset < 0), before any launch. */
 int qmle_build_angles(const float *const *d_leaves, const int64_t *leaf_strides,
                       const int32_t *leaf_div, const int32_t *leaf_mod, int n_leaves,
                       const int32_t *d_ptr, const int32_t *d_arg, const int32_t *d_idx,

@@ -458,7 +458,8 @@ class Plan:
         (``measure_tiles_per_workgroup_last_run``, ``measured_from_registers_last_run``,
         ``wave_private_walk_last_run``, ``staging_dma_last_run``, ``last_group_lane_swap_last_run``, and
         ``chunk_loop_last_run``: ``"one_stream"``,
-        ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run):
+        ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run; and
+        ``matrices_from_map_last_run``: the matrix builder formed its angles from the affine map, not from a table):
         describe ``executed(meas)``, after the run.  Every tile stage carries ``group_product_form_last_run``: its
         last launch ran the groups that ``product_form_groups`` marks in product form."""
         L = lib()
@@ -723,7 +724,8 @@ class Plan:
 def build_angles(leaves, strides, divs, mods, d_ptr, d_arg, d_idx, d_coef, d_const, n_slots,
                  batch, batch_offset=0, out=None, d_period=None):
     """Angle table [batch, n_slots] on device from device-resident leaf tensors;
-    ``d_period`` [n_slots] float64: slots reduced into (-period/2, period/2]."""
+    ``d_period`` [n_slots] float64: where > 0, a sum beyond +-period is reduced into [-period/2, period/2];
+    a sum within +-period, the bounds included, is stored as it is.  ``batch_offset`` >= 0."""
     torch = require_gpu()
     k = len(leaves)
     dev = d_const.device

@@ -76,9 +76,10 @@ k_build_angles(AngleLeaves lv, const int *__restrict__ ptr, const int *__restric
   const IDX b = i / (IDX)n_slots;
   const int s = (int)(i - b * (IDX)n_slots);
   const IDX gb = b + (IDX)b_offset;
-  // fp64 accumulation, then reduction into (-period/2, period/2] (4 pi for a rotation gate, which
-  // depends on angle / 2 only): binary / ternary encodings scale inputs by up to 3^(n-1), and a
-  // float32 angle of ~1500 rad would carry 1e-4 rad of rounding into the gate matrices
+  // fp64 accumulation; a sum beyond +-period is then reduced into [-period/2, period/2] (4 pi for a rotation
+  // gate, which depends on angle / 2 only; a sum within +-period, the bounds included, stays as it is): binary /
+  // ternary encodings scale inputs by up to 3^(n-1), and a float32 angle of ~1500 rad would carry 1e-4 rad of
+  // rounding into the gate matrices
   double acc = (double)cst[s];
   for (int t = ptr[s]; t < ptr[s + 1]; ++t) {
     const int k = arg[t];
@@ -158,6 +159,8 @@ bool plan_sparse(const qmle_plan *p) { return !(p->flags & QMLE_PLAN_NO_SPARSE);
 // thread's next launch_build_matrices of >= 64 samples): the angles are then formed inside the builder and
 // the table is never written
 static thread_local const AngleMapSrc *tls_angle_map = nullptr;
+// whether this thread's next builder launch for `batch` samples takes its angles from the map (LastRun::matrices_from_map)
+static bool builds_from_map(int batch) { return tls_angle_map && batch >= 64; }
 
 // per-sample gate matrices for the whole batch: d_mats[b][mat_floats] from d_angles[b][n_slots]
 int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_mats, int batch, hipStream_t stream,
@@ -168,7 +171,7 @@ int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_ma
   // builder passes over them)
   const int npg = p->n_product_groups, pg0 = p->n_groups_needed - npg;
   const int ngc = forward_only ? pg0 : ng;  // items the common builder has work in
-  if (tls_angle_map && batch >= 64) {
+  if (builds_from_map(batch)) {
     const uint64_t per = ((uint64_t)batch + 63) / 64;
     if (ngc > 0)
       hipLaunchKernelGGL(k_build_matrices_map, dim3(grid_for((uint64_t)ngc * per * 64, 64)), dim3(64), 0, stream, p->dev.d_build,
@@ -935,6 +938,7 @@ static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, i
   // per-sample gate matrices for the whole batch (tiny)
   rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true);
   if (rc != QMLE_OK) return rc;
+  plan->last_run.matrices_from_map = plan->n_groups_needed > 0 && qmle::builds_from_map(batch);
   plan->last_run.chunk_loop = kChunkLoopOneStream;
   if (L.in_lds)
     return run_batch_lds(plan, L, d_mats, d_angles, batch, meas_type, obs_masks, n_obs, d_out, ws + L.partial[0],
@@ -1317,14 +1321,15 @@ int qmle_build_angles(const float *const *d_leaves, const int64_t *leaf_strides,
                       const float *d_coef, const float *d_const, const double *d_period,
                       int n_slots, int64_t batch, int64_t batch_offset, float *d_out,
                       qmle_stream stream) {
-  if (n_leaves < 0 || n_leaves > 8 || n_slots < 0 || batch < 1 || !d_out || !d_ptr || !d_const)
+  // (a negative offset would wrap as an unsigned row)
+  if (n_leaves < 0 || n_leaves > 8 || n_slots < 0 || batch < 1 || batch_offset < 0 || !d_out || !d_ptr || !d_const)
     return QMLE_ERR_INVALID_ARG;
   if (n_slots == 0) return QMLE_OK;
   AngleLeaves lv;
   const int rc_lv = fill_angle_leaves(lv, d_leaves, leaf_strides, leaf_div, leaf_mod, n_leaves);
   if (rc_lv != QMLE_OK) return rc_lv;
   const uint64_t total = (uint64_t)batch * (uint64_t)n_slots;
-  if (total + 256 < (1ull << 32) && batch_offset >= 0 && (uint64_t)batch + (uint64_t)batch_offset < (1ull << 32))
+  if (total + 256 < (1ull << 32) && (uint64_t)batch + (uint64_t)batch_offset < (1ull << 32))
     hipLaunchKernelGGL(k_build_angles<uint32_t>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, lv,
                        d_ptr, d_arg, d_idx, d_coef, d_const, d_period, n_slots, (long long)batch,
                        (long long)batch_offset, d_out);
@@ -1346,7 +1351,7 @@ int qmle_run_batch_map(qmle_plan *plan, const qmle_angle_map *map, float *d_angl
 int qmle_run_batch_map_w(qmle_plan *plan, const qmle_angle_map *map, float *d_angles, int batch,
                          int meas_type, const int32_t *obs_wires, int n_obs, void *d_out,
                          void *d_workspace, size_t workspace_bytes, qmle_stream stream, uint64_t *ws_token) {
-  if (!plan || !map || batch < 1) return void_token(ws_token, QMLE_ERR_INVALID_ARG);
+  if (!plan || !map || batch < 1 || map->batch_offset < 0) return void_token(ws_token, QMLE_ERR_INVALID_ARG);
   if (plan->n_slots == 0)
     return qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace, workspace_bytes,
                             stream, ws_token);
@@ -1372,7 +1377,7 @@ int qmle_run_batch_map_w(qmle_plan *plan, const qmle_angle_map *map, float *d_an
   src.ptr = map->d_ptr; src.arg = map->d_arg; src.idx = map->d_idx;
   src.coef = map->d_coef; src.cst = map->d_const; src.period = map->d_period;
   src.b_offset = map->batch_offset;
-  src.small = map->batch_offset >= 0 && (uint64_t)batch + (uint64_t)map->batch_offset < (1ull << 32);
+  src.small = (uint64_t)batch + (uint64_t)map->batch_offset < (1ull << 32);
   tls_angle_map = &src;
   const int rc = qmle_run_batch_w(plan, d_angles, batch, meas_type, obs_wires, n_obs, d_out, d_workspace,
                                   workspace_bytes, stream, ws_token);

@@ -276,6 +276,9 @@ struct LastRun {
   // bit s: the last launch of tile stage s (batch run or in place; stages 0..63) ran its product-form groups -- every
   // k_tile2 launch does; k_tile and the other readers of dev_ops apply the plain records
   uint64_t product_form_stages = 0;
+  // the last batch run's matrix builder formed its angles from the affine map (qmle_run_batch_map from 64 samples on:
+  // k_build_matrices_map / k_build_matrices_product_map); false: it read the angle table
+  bool matrices_from_map = false;
 };
 
 }  // namespace qmle

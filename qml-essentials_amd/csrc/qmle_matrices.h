@@ -286,8 +286,8 @@ __device__ void source_matrix(const BuildOp &b, ANG ang,
 }
 
 // Angle table computed on the fly: table[b][s] = c[s] + sum_t coef[t] * leaf_{arg[t]}[row_k(b)][idx[t]],
-// row_k(b) = ((b + b_offset) / div_k) % mod_k, fp64 sum, reduced into (-period/2, period/2], rounded to
-// float32 -- bit for bit what k_build_angles stores (qmle_engine.hip); qmle_run_batch_map uses it to skip
+// row_k(b) = ((b + b_offset) / div_k) % mod_k, fp64 sum, reduced into [-period/2, period/2] where it lies beyond
+// +-period (and only there), rounded to float32 -- bit for bit what k_build_angles stores (qmle_engine.hip); qmle_run_batch_map uses it to skip
 // that kernel and the table's round trip when nothing but the matrix builder reads angles.
 struct AngleLeaves {
   const float *ptr[8];

@@ -39,9 +39,9 @@ class CompiledCall:
     _holder = None  # weak reference to the call that keeps a workspace (_run_kept)
 
     def __init__(self, script: "Script", type: str, obs, args: tuple, leaf_ids: Tuple[int, ...],
-                 kwargs: dict):
-        import torch
-
+                 kwargs: dict, upload: bool = True):
+        """``upload=False``: the host half only -- the plan and the affine map (``_map``, ``_const``, ``_period``)
+        without their device arrays; such a call cannot run (it needs no GPU: the tests read the map from it)."""
         self.type, self.obs = type, list(obs)
         rng = np.random.default_rng(12345)
         probes, wrapped = {}, list(args)
@@ -95,19 +95,23 @@ class CompiledCall:
                 const.append(c0)
                 ptr.append(len(arg))
                 slot += 1
+        self.leaf_ids = leaf_ids
+        self._low, self._map = low, (ptr, arg, idx, coef)   # host copies for the adjoint path
+        # rotation angles wrap at 4 pi (the gates depend on angle / 2); a DIAG_ALL scale does not
+        self._const, self._period = const, [4.0 * np.pi if per else 0.0 for per in low.ops_periodic]
+        self._leaf_sizes = {order[k]: int(np.prod(np.shape(args[k]))) for k in leaf_ids}
+        self._adj = None
+        self._kept = None  # (key, workspace, token, True) of the latest run worth keeping (_run_kept)
+        if not upload:
+            return
+        import torch
+
         dev = torch.device("cuda", torch.cuda.current_device())
         i32 = lambda v: torch.tensor(v if len(v) else [0], dtype=torch.int32, device=dev)
         f32 = lambda v: torch.tensor(v if len(v) else [0.0], dtype=torch.float32, device=dev)
         self.d_ptr, self.d_arg, self.d_idx = i32(ptr), i32(arg), i32(idx)
         self.d_coef, self.d_const = f32(coef), f32(const)
-        # rotation angles wrap at 4 pi (the gates depend on angle / 2); a DIAG_ALL scale does not
-        self.d_period = torch.tensor([4.0 * np.pi if per else 0.0 for per in low.ops_periodic] or [0.0],
-                                     dtype=torch.float64, device=dev)
-        self.leaf_ids = leaf_ids
-        self._low, self._map = low, (ptr, arg, idx, coef)   # host copies for the adjoint path
-        self._leaf_sizes = {order[k]: int(np.prod(np.shape(args[k]))) for k in leaf_ids}
-        self._adj = None
-        self._kept = None  # (key, workspace, token, True) of the latest run worth keeping (_run_kept)
+        self.d_period = torch.tensor(self._period or [0.0], dtype=torch.float64, device=dev)
 
     def _run_kept(self, batch: int, kind: str, n_obs: int, run):
         """``run(workspace, token) -> (out, workspace, token)`` on the workspace this call keeps.
