@@ -214,7 +214,10 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * follow it and end at "mat_floats".  Behind them sit the product-form records of the fast groups: per stage,
  * "product_form_groups"[g] says whether fast group g runs in product form and "product_form_records"[g] gives the
  * float offset of its record (-1: none; see qmle_group_product_form); "mat_row_floats" is the row's stride.  A tile stage reports "group_product_form_last_run": its last launch ran those groups in
- * product form (the fast tile kernel always does; the generic tile kernel applies the plain records). */
+ * product form (the fast tile kernel always does; the generic tile kernel applies the plain records).
+ * "closing_free_groups"[g]: a run that ends the stage in |amplitude|^2 only may build group g's record without a
+ * closing diagonal (see qmle_group_product_form_measured); "measured_form_last_run": the last batch run did so for
+ * its last stage and ran those records (false on every other stage and after every other kind of run). */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* Host only (no GPU needed): how tile stage `stage` of `plan` would run for a request -- the launch policy of the
  * tile passes as JSON, written like qmle_plan_describe (returns the bytes needed, or an error < 0: no tile stage
@@ -256,6 +259,14 @@ int qmle_unit_form_chain(const double *u, const int *diag, int n, double *record
  * (0: no operator there); [48, 80) the closing diagonal, which carries g, l and the scales the real steps leave out.
  * forms[i] (may be NULL) = the form of operator i. */
 int qmle_group_product_form(const double *u, const int *bits, int n, double *record, int *forms);
+/* Host only: the same record in measured mode, as a <Z> or Z-parity batch run builds it for the groups of its last
+ * stage that "closing_free_groups" marks (only basis permutations and |amplitude|^2 follow the group's wires, and no
+ * unit-pivot chain is split).  The opening diagonal is the same; the real step of bit b is (-tau, s), tau = s / (1 + c)
+ * <= 1, applied as a0 -= tau a1, a1 += s a0, a0 -= tau a1 -- the rotation itself, exactly; every form is 3; the
+ * closing diagonal holds exact ones and record[44] = 1 says that it is not applied.  The record applies
+ * D (x)_i u[i] / |g_i| for a diagonal D of unit phases.  "measured_form_last_run" of a plan's last stage reports
+ * whether the last batch run built and ran such records. */
+int qmle_group_product_form_measured(const double *u, const int *bits, int n, double *record, int *forms);
 /* counts: [0]=reference gates, [1]=HBM passes, [2]=whole-state-LDS(0/1),
  * [3]=tile qubits T, [4]=floats of per-sample matrices, [5]=direct passes */
 int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);

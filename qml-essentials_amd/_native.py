@@ -155,6 +155,8 @@ SYMBOLS = [
                                   C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("qmle_group_product_form", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
                                      C.POINTER(C.c_int)]),
+    ("qmle_group_product_form_measured", _I, [C.POINTER(C.c_double), C.POINTER(C.c_int), _I, C.POINTER(C.c_double),
+                                              C.POINTER(C.c_int)]),
     ("qmle_plan_tile_route", _I, [_VP, _I, _I, _I, _I, C.c_uint, C.c_char_p, _SZ]),
     ("qmle_plan_stats", _I, [_VP, C.POINTER(C.c_int64)]),
     ("qmle_plan_autotune", _I, [_VP, _I, _I, _I, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_double),
@@ -461,7 +463,9 @@ class Plan:
         ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run; and
         ``matrices_from_map_last_run``: the matrix builder formed its angles from the affine map, not from a table):
         describe ``executed(meas)``, after the run.  Every tile stage carries ``group_product_form_last_run``: its
-        last launch ran the groups that ``product_form_groups`` marks in product form."""
+        last launch ran the groups that ``product_form_groups`` marks in product form; and
+        ``measured_form_last_run``, true on the last stage when the last batch run built the records of its
+        ``closing_free_groups`` without closing diagonals and ran them."""
         L = lib()
         need = L.qmle_plan_describe(self._h, None, 0)
         buf = C.create_string_buffer(need + 1)

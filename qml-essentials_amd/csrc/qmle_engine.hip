@@ -44,15 +44,16 @@ template <bool GMAJOR>
 __global__ void __launch_bounds__(64)
 k_build_matrices_product(const BuildOp *__restrict__ build, const BuildGroup *__restrict__ groups, int n_groups,
                 const float *__restrict__ angles, int n_slots, const float *__restrict__ consts,
-                float *__restrict__ mats, uint32_t mat_floats, int batch) {
-  build_matrices_body<const float *, float, float, GMAJOR, true>(build, groups, n_groups, angles, n_slots, consts, mats, mat_floats, batch);
+                float *__restrict__ mats, uint32_t mat_floats, int batch, uint32_t measured_from) {
+  build_matrices_body<const float *, float, float, GMAJOR, true>(build, groups, n_groups, angles, n_slots, consts, mats, mat_floats, batch,
+                                                                 measured_from);
 }
 __global__ void __launch_bounds__(64)
 k_build_matrices_product_map(const BuildOp *__restrict__ build, const BuildGroup *__restrict__ groups, int n_groups,
                     const AngleMapSrc map, int n_slots, const float *__restrict__ consts,
-                    float *__restrict__ mats, uint32_t mat_floats, int batch) {
+                    float *__restrict__ mats, uint32_t mat_floats, int batch, uint32_t measured_from) {
   build_matrices_body<const AngleMapSrc &, float, float, true, true>(build, groups, n_groups, map, n_slots, consts, mats,
-                                                                    mat_floats, batch);
+                                                                    mat_floats, batch, measured_from);
 }
 
 // ---------------------------------------------------------------------------
@@ -162,9 +163,22 @@ static thread_local const AngleMapSrc *tls_angle_map = nullptr;
 // whether this thread's next builder launch for `batch` samples takes its angles from the map (LastRun::matrices_from_map)
 static bool builds_from_map(int batch) { return tls_angle_map && batch >= 64; }
 
+// "this run's last stage ends in |amplitude|^2 only" (qmle_host.h), as the float offset its measured-mode records start at
+uint32_t measured_records_from(const qmle_plan *p, int meas_type) {
+  if (meas_type != QMLE_MEAS_EXPVAL_Z || p->stages.empty()) return 0xffffffffu;
+  const Stage &st = p->stages.back();
+  if (st.kind != ST_TILE || !st.fast_ok) return 0xffffffffu;
+  uint32_t from = 0xffffffffu;
+  for (int g = st.fast_begin; g < st.fast_end; ++g)
+    if ((p->groups2[g].sync & kGroupProduct) && (p->groups2[g].sync & kGroupClosingFree) && p->groups2[g].prod_off < from)
+      from = p->groups2[g].prod_off;
+  // (records are appended stage by stage: the last stage's are the last of the row)
+  return from;
+}
+
 // per-sample gate matrices for the whole batch: d_mats[b][mat_floats] from d_angles[b][n_slots]
 int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_mats, int batch, hipStream_t stream,
-                          bool forward_only) {
+                          bool forward_only, uint32_t measured_from) {
   const int ng = forward_only ? p->n_groups_needed : (int)p->groups.size();
   if (ng <= 0) return QMLE_OK;
   // the product-form records of the fast groups: the last needed items, in a kernel of their own (the common
@@ -178,7 +192,7 @@ int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_ma
                          p->dev.d_groups, ngc, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
     if (npg > 0)
       hipLaunchKernelGGL(k_build_matrices_product_map, dim3(grid_for((uint64_t)npg * per * 64, 64)), dim3(64), 0, stream, p->dev.d_build,
-                         p->dev.d_groups + pg0, npg, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+                         p->dev.d_groups + pg0, npg, *tls_angle_map, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch, measured_from);
     HIPCHK(hipGetLastError());
     return QMLE_OK;
   }
@@ -186,10 +200,10 @@ int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_ma
     const uint64_t pitems = batch >= 64 ? (uint64_t)npg * (((uint64_t)batch + 63) / 64) * 64 : (uint64_t)batch * (uint64_t)npg;
     if (batch >= 64)
       hipLaunchKernelGGL(k_build_matrices_product<true>, dim3(grid_for(pitems, 64)), dim3(64), 0, stream, p->dev.d_build,
-                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch, measured_from);
     else
       hipLaunchKernelGGL(k_build_matrices_product<false>, dim3(grid_for(pitems, 64)), dim3(64), 0, stream, p->dev.d_build,
-                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch);
+                         p->dev.d_groups + pg0, npg, d_angles, p->n_slots, p->dev.d_consts, d_mats, p->mat_floats, batch, measured_from);
     HIPCHK(hipGetLastError());
     if (ngc <= 0) return QMLE_OK;
   }
@@ -380,7 +394,7 @@ int qmle_unit_form_chain(const double *u, const int *diag, int n, double *record
 
 // the matrix builder's product form of a group (product_form_group, qmle_matrices.h) on the host: n <= 4 matrices
 // (8 doubles each, row-major re / im) on the distinct in-thread bits `bits`; record: kProductRecFloats doubles
-int qmle_group_product_form(const double *u, const int *bits, int n, double *record, int *forms) {
+static int group_product_form(const double *u, const int *bits, int n, double *record, int *forms, bool measured) {
   if (!u || !bits || !record || n < 1 || n > 4) return QMLE_ERR_INVALID_ARG;
   M2 m[4];
   unsigned seen = 0;
@@ -390,8 +404,15 @@ int qmle_group_product_form(const double *u, const int *bits, int n, double *rec
     const double *x = u + 8 * (size_t)i;
     m[i] = {{x[0], x[1]}, {x[2], x[3]}, {x[4], x[5]}, {x[6], x[7]}};
   }
-  product_form_group(m, bits, n, record, forms);
+  product_form_group(m, bits, n, record, forms, measured);
   return QMLE_OK;
+}
+int qmle_group_product_form(const double *u, const int *bits, int n, double *record, int *forms) {
+  return group_product_form(u, bits, n, record, forms, /*measured=*/false);
+}
+// ... in measured mode: the record of a run in which only basis permutations and |amplitude|^2 follow the group
+int qmle_group_product_form_measured(const double *u, const int *bits, int n, double *record, int *forms) {
+  return group_product_form(u, bits, n, record, forms, /*measured=*/true);
 }
 
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap) {
@@ -755,6 +776,12 @@ static ObsClass classify_observables(const qmle_plan *plan, const uint32_t *obs_
 static void note_product_form(qmle_plan *plan, size_t si, const TileRoute &route) {
   if (si < 64) plan->last_run.product_form_stages = (plan->last_run.product_form_stages & ~(1ull << si)) | ((uint64_t)route.product_form << si);
 }
+// ... of a batch run: whether its last stage ran records the builder wrote in measured mode (LastRun::measured_form)
+static void note_product_form(qmle_plan *plan, size_t si, const TileRoute &route, int meas_type) {
+  note_product_form(plan, si, route);
+  if (si + 1 == plan->stages.size())
+    plan->last_run.measured_form = route.product_form && measured_records_from(plan, meas_type) != 0xffffffffu;
+}
 
 // The whole state lives in the LDS of one workgroup: one launch per chunk simulates and measures, and the state
 // is stored only when the state is what was asked for.  `rows`: the Meyer-Wallach rows of a chunk (L.partial_bytes).
@@ -790,7 +817,7 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
     }
     TileRoute route;
     int rc = launch_tile(plan, 0, tb, rq, stream, &route);
-    note_product_form(plan, 0, route);
+    note_product_form(plan, 0, route, meas_type);
     if (rc == QMLE_OK && meas_type == QMLE_MEAS_MEYER_WALLACH)
       rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
     if (rc != QMLE_OK) return rc;
@@ -936,7 +963,9 @@ static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, i
   float *d_coef = (float *)(ws + L.coef);
 
   // per-sample gate matrices for the whole batch (tiny)
-  rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true);
+  // (the records of the last stage's closing-free groups: without closing diagonals when the run ends in |amplitude|^2)
+  const uint32_t measured_from = measured_records_from(plan, meas_type);
+  rc = launch_build_matrices(plan, d_angles, d_mats, batch, caller_stream, /*forward_only=*/true, measured_from);
   if (rc != QMLE_OK) return rc;
   plan->last_run.matrices_from_map = plan->n_groups_needed > 0 && qmle::builds_from_map(batch);
   plan->last_run.chunk_loop = kChunkLoopOneStream;
@@ -1000,7 +1029,7 @@ static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, i
         const bool reuse = !last_mw && si == 0 && reuse_zeros;
         if (reuse) rq.zeroed_states = slot_zeroed[slot];
         rc = launch_tile(plan, si, tb, rq, stream, &route);
-        note_product_form(plan, si, route);
+        note_product_form(plan, si, route, meas_type);
         if (last_fused && !is_reg_measure(route.family)) {  // (k_reg_measure* is no tile walk: the report stays "no such pass")
           plan->last_run.measure_tpw = 1 << route.row_shift;
           plan->last_run.measure_regs = route.from_regs;

@@ -122,8 +122,14 @@ bool plan_sparse(const qmle_plan *p);  // known-zero tracking is on for runs of 
 size_t ws_mats_bytes(const qmle_plan *p, int batch);
 size_t workspace_bytes_one(const qmle_plan *plan, int batch, int meas_type, int states_in_flight);
 // forward_only: just the matrices the forward tile / direct kernels read (qmle_plan::n_groups_needed)
+// measured_from: measured_records_from(p, meas_type) of a batch run; every other caller keeps the phase-exact records
 int launch_build_matrices(const qmle_plan *p, const float *d_angles, float *d_mats, int batch, hipStream_t stream,
-                          bool forward_only = false);
+                          bool forward_only = false, uint32_t measured_from = 0xffffffffu);
+// Where in the matrix row the records start that a run of `p` with this measurement builds in measured mode (DESIGN
+// 9n): the product-form records of its last stage, when that stage is a tile stage with closing-free groups and the run
+// ends it in |amplitude|^2 only -- QMLE_MEAS_EXPVAL_Z, which is also what the Z-parity entries run as -- and for nothing
+// else; 0xffffffff: none.  A function of the plan and the measurement alone (no HIP call, no environment).
+uint32_t measured_records_from(const qmle_plan *p, int meas_type);
 int run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                     const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
                     size_t workspace_bytes, hipStream_t stream, uint64_t *ws_token = nullptr);

@@ -83,14 +83,19 @@ struct BuildGroup {
 // [begin, end) holds the source gates of the group's members in stream order, each closed by a marker as in a chain:
 // pad = what the op's ops2 record holds (ChainMember; CM_PLAIN: the operator itself), const_off = the member's
 // in-thread bit -- or -1 for a unit-form member of the carrier's chain that sits in an earlier group: its pivot enters
-// P, nothing else.  mat_off = float offset of the record (kProductRecFloats floats) in the matrix row.
+// P, nothing else.  mat_off = float offset of the record (kProductRecFloats floats) in the matrix row.  The markers of a
+// group with kGroupClosingFree carry pad2 = 1: the builder may write the record in measured mode.
 constexpr uint32_t kBuildChain = 1, kBuildProduct = 3;
 constexpr uint16_t kChainMark = 0xffffu;
 enum ChainMember : uint16_t { CM_UNIT_DENSE = 0, CM_UNIT_DIAG = 1, CM_CARRIER = 2, CM_PLAIN = 3 };
 // Product-form record, in floats: [0, 32) the opening diagonal (16 complex, entry 0 = 1), [32, 40) per in-thread bit
 // the pair (-t, u) of the direct real step or (t', 0) of the mirrored one, [40, 44) per in-thread bit the form word --
 // the float 0 (no member on that bit), 1 (direct) or 2 (mirrored) --, [48, 80) the closing diagonal (16 complex).
+// Measured mode (product_form_group): the pair is (-tau, s) of the three-shear rotation, the form word the
+// float 3, the closing diagonal exact ones, and float 44 (kProductRecNoClose) the float 1: "no closing diagonal" -- 0
+// in every other record.  The record alone tells the kernel which mode it is in.
 constexpr uint32_t kProductRecFloats = 80, kProductRecSteps = 32, kProductRecForms = 40, kProductRecClose = 48;
+constexpr uint32_t kProductRecNoClose = 44;
 constexpr int kMaxChainUnits = 32;  // unit-form ops per chain: |1 / pivot| <= sqrt 2, so a state is scaled by <= 2^16
 
 // ---- fast tile path (k_tile2) ---------------------------------------------------------------
@@ -121,6 +126,8 @@ struct Group2 {
   uint8_t sync;        // bit 0: the measuring walk needs a workgroup barrier in front of this group's gather (Stage::fast_info)
                        // bit 1 (kGroupProduct): the group runs in product form, its record at prod_off
                        // bit 2 (kGroupProductLow1): ... and no member sits on in-thread bit 0 or 1 (opening entries 0..3 are 1)
+                       // bit 3 (kGroupClosingFree): ... and a run that ends this stage in |amplitude|^2 may build its record
+                       // in measured mode (mark_closing_free_groups; a property of the plan, read by the host only)
   uint32_t tbl;        // index into qmle_plan::tbl2 (one uint32 per thread of the workgroup)
   uint32_t tbl_out;    // relayout: scatter table
   uint32_t off[16];
@@ -129,7 +136,7 @@ struct Group2 {
   uint32_t pad[3];
 };
 static_assert(sizeof(Group2) == 160, "Group2 layout");
-constexpr uint8_t kGroupProduct = 2, kGroupProductLow1 = 4;
+constexpr uint8_t kGroupProduct = 2, kGroupProductLow1 = 4, kGroupClosingFree = 8;
 
 enum StageKind : int { ST_DIRECT = 0, ST_TILE = 1, ST_DIAG_ALL = 2 };
 
@@ -279,6 +286,9 @@ struct LastRun {
   // the last batch run's matrix builder formed its angles from the affine map (qmle_run_batch_map from 64 samples on:
   // k_build_matrices_map / k_build_matrices_product_map); false: it read the angle table
   bool matrices_from_map = false;
+  // the last batch run's builder wrote measured-mode records (no closing diagonals) for the closing-free
+  // groups of its last stage, and that stage's launch ran its product-form groups
+  bool measured_form = false;
 };
 
 }  // namespace qmle
@@ -294,6 +304,8 @@ struct qmle_plan {
   std::vector<int> dev_src;               // source op of every dev_op (-1 if merged from several)
   std::vector<qmle::OpGroup> op_groups;   // register-tile groups of the tile stages
   std::vector<qmle::LoweredOp> ops2;      // fast tile path: ops of the Group2 groups
+  std::vector<uint8_t> ops2_perm_tail;    // ... per op: only X / CX follow on its wire and on the wires they spread it to
+                                          // (the stage's op order; build_fast_groups, for mark_closing_free_groups)
   std::vector<qmle::Group2> groups2;
   std::vector<uint32_t> tbl2;             // per-thread LDS byte addresses of the Group2 groups
   std::vector<qmle::BuildOp> build_ops;

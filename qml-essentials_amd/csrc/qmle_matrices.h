@@ -87,12 +87,21 @@ __host__ __device__ __forceinline__ M2 unit_chain_operator(const M2 &U, int memb
 // Over the n <= 4 members of a group, on distinct in-thread bits: opening entry e = product of r_q over the members
 // whose bit is set in e, closing entry e = product of the members' factor for their bit of e.  fp64 throughout, rounded
 // once on the store; layout: kProductRec* (qmle_internal.h).  forms (optional): the form of each member.
+// measured: the record of a run in which only basis permutations and |amplitude|^2 follow the group.  The
+// phases g / |g| and l are then invisible, and the rotation is applied exactly, as three shears that need no scale:
+//   [[c, -s], [s, c]] = [[1, -tau], [0, 1]] [[1, 0], [s, 1]] [[1, -tau], [0, 1]],  tau = s / (1 + c) <= 1   (form 3)
+// -- a0 -= tau a1; a1 += s a0; a0 -= tau a1; the record holds (-tau, s).  No mirrored case, the closing entries are
+// exact ones, and the word kProductRecNoClose tells the kernel to leave them out.  What such a record applies is
+// D (x)_q M_q / |g_q| for a diagonal D of unit phases: |g_q| is dropped too (1 for a unitary; the pivots of a
+// unit-pivot chain cancel over the chain's members, which is why a chain is measured as a whole or not at all).
 // ---------------------------------------------------------------------------
 template <class OT>
-__host__ __device__ inline void product_form_group(const M2 *m, const int *bit, int n, OT *out, int *forms = nullptr) {
+__host__ __device__ inline void product_form_group(const M2 *m, const int *bit, int n, OT *out, int *forms = nullptr,
+                                                   bool measured = false) {
   cd open[16], close[16];
   for (int e = 0; e < 16; ++e) open[e] = close[e] = {1.0, 0.0};
   for (uint32_t i = kProductRecSteps; i < kProductRecClose; ++i) out[i] = (OT)0;
+  if (measured) out[kProductRecNoClose] = (OT)1;
   for (int q = 0; q < n; ++q) {
     const M2 &M = m[q];
     const double n00 = M.a.re * M.a.re + M.a.im * M.a.im, n10 = M.c.re * M.c.re + M.c.im * M.c.im;
@@ -123,7 +132,13 @@ __host__ __device__ inline void product_form_group(const M2 *m, const int *bit, 
     const cd gl = cdmul(g, l);
     cd lo, hi;
     double w0, w1;
-    if (direct) {
+    int form = direct ? 1 : 2;
+    if (measured) {
+      w0 = -s / (1.0 + c);
+      w1 = s;
+      lo = hi = {1.0, 0.0};
+      form = 3;
+    } else if (direct) {
       const double t = s / c;
       w0 = -t;
       w1 = t / (1.0 + t * t);
@@ -138,8 +153,8 @@ __host__ __device__ inline void product_form_group(const M2 *m, const int *bit, 
     const int b = bit[q];
     out[kProductRecSteps + 2 * b] = (OT)w0;
     out[kProductRecSteps + 2 * b + 1] = (OT)w1;
-    out[kProductRecForms + b] = (OT)(direct ? 1 : 2);
-    if (forms) forms[q] = direct ? 1 : 2;
+    out[kProductRecForms + b] = (OT)form;
+    if (forms) forms[q] = form;
     for (int e = 0; e < 16; ++e) {
       if ((e >> b) & 1) {
         open[e] = cdmul(open[e], r);
@@ -332,12 +347,17 @@ __device__ __forceinline__ AngleMapRow angle_row(const AngleMapSrc &m, int b, in
 // PRODUCT: the launch builds the product-form records of the fast groups (BuildGroup::dim = kBuildProduct, the
 // n_product_groups last needed items) and nothing else; every other launch leaves those items out -- a kernel of their
 // own, so that the 32 fp64 complex numbers of the two diagonals do not set the register count of the common builder
+// measured_from (PRODUCT): records at this float offset of the row and behind it -- the last stage's, in a run that
+// ends in |amplitude|^2 only -- are built in measured mode where their group allows it (the markers' pad2);
+// kNoMeasuredRecords: none, every record is phase-exact
+constexpr uint32_t kNoMeasuredRecords = 0xffffffffu;
 template <class ASRC, class CT, class OT, bool GMAJOR = false, bool PRODUCT = false>
 __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ build,
                                                     const BuildGroup *__restrict__ groups, int n_groups,
                                                     ASRC angles, int n_slots,
                                                     const CT *__restrict__ consts, OT *__restrict__ mats,
-                                                    uint32_t mat_floats, int batch) {
+                                                    uint32_t mat_floats, int batch,
+                                                    uint32_t measured_from = kNoMeasuredRecords) {
   // one work item per (sample, group).  batch >= 64 (blocks of ONE wave): a wave takes 64 consecutive
   // samples of the SAME group -- every lane then walks the same source gates through the same branches
   // of the opcode switch.  With the samples-then-groups flattening used below that, neighbouring lanes
@@ -392,10 +412,11 @@ __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ 
     cd P = {1.0, 0.0};
     M2 M = {{1.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {1.0, 0.0}}, mem[4];
     int bit[4], n_mem = 0;
-    bool first = true;
+    bool first = true, closing_free = false;
     for (uint32_t k = grp.begin; k < grp.end; ++k) {
       const BuildOp bo = build[k];
       if (bo.opcode == kChainMark) {
+        closing_free = bo.pad2 != 0;
         const M2 E = unit_chain_operator(M, (int)bo.pad, P);
         if (bo.const_off >= 0 && n_mem < 4) {
           mem[n_mem] = E;
@@ -414,7 +435,8 @@ __device__ __forceinline__ void build_matrices_body(const BuildOp *__restrict__ 
       const cd c = cdadd(cdmul(S.c, M.a), cdmul(S.d, M.c)), d = cdadd(cdmul(S.c, M.b), cdmul(S.d, M.d));
       M = {a, bb, c, d};
     }
-    product_form_group(mem, bit, n_mem, mats + (size_t)b * mat_floats + grp.mat_off);
+    product_form_group(mem, bit, n_mem, mats + (size_t)b * mat_floats + grp.mat_off, nullptr,
+                       closing_free && grp.mat_off >= measured_from);
     return;
   }
   if (dim == 2) {

@@ -368,6 +368,19 @@ struct FastGroupBuilder {
       if (!done[j] && (mask_of(src[j]) & m)) return false;
     return true;
   }
+  // Rule 1 of mark_closing_free_groups for op i alone (the rule of a group is the AND over its members: the spread
+  // of a union of wires is the union of the spreads): in the stage's op order, every op behind i that touches a wire
+  // i's result has reached is an X / CX -- which hands it on to its other wire
+  bool perm_tail(int i) const {
+    uint32_t taint = mask_of(src[i]);
+    for (int j = i + 1; j < nops; ++j) {
+      const uint32_t m = mask_of(src[j]);
+      if (!(m & taint)) continue;
+      if (!is_perm(src[j])) return false;
+      taint |= m;
+    }
+    return true;
+  }
   void apply_perm(const LoweredOp &o) {
     Z &= ~(1u << o.t0);
     maps.apply_perm(o);
@@ -475,6 +488,7 @@ void FastGroupBuilder::emit_group(const std::vector<int> &mem, const std::vector
                                            : (o.nc ? FC_CDENSE : FC_DENSE);
     o.pad = (uint8_t)(base + (o.nc ? 3 * o.c0 + (o.t0 - (o.t0 > o.c0 ? 1 : 0)) : o.t0));
     p->ops2.push_back(o);
+    p->ops2_perm_tail.push_back(perm_tail(i) ? 1 : 0);
     done[i] = 1;
     ++n_done;
   }
@@ -888,6 +902,60 @@ static void assign_product_forms(qmle_plan *p, const FastOpForms &forms) {
       g.sync |= kGroupProduct | ((bits & 3u) ? 0 : kGroupProductLow1);
       p->mat_floats += kProductRecFloats;
     }
+  }
+}
+
+// ---- product-form groups without closing diagonals -----------------------------------------
+// A closing diagonal holds unit phases and the real scales the two-shear step leaves out.  Where nothing follows a
+// group's wires but basis permutations and |amplitude|^2, the phases are invisible, and a rotation written as three
+// shears has no scale: the record's measured mode (product_form_group) needs no closing diagonal.  kGroupClosingFree
+// says a group MAY run that way -- in a run whose last stage this is and which ends in |amplitude|^2 only
+// (measured_records_from, qmle_engine.hip); which mode a record is built in is decided per run.
+//   Rule 1: every member's FastGroupBuilder::perm_tail holds.
+//   Rule 2: the measured mode drops |g| per member, and the pivots of a unit-pivot chain cancel against its carrier's P
+//           only when all of them are dropped: a chain with a member in a marked group has all its members in marked
+//           groups (of the same stage: a chain never leaves its stage).  Iterated to the fixed point.
+static void mark_closing_free_groups(qmle_plan *p, const FastOpForms &forms) {
+  for (Stage &st : p->stages) {
+    if (st.kind != ST_TILE || !st.fast_ok || st.fast_end <= st.fast_begin) continue;
+    const uint32_t ob = p->groups2[st.fast_begin].op_begin;
+    uint32_t oe = ob;
+    std::vector<int> group_of;  // per op of the stage's stream
+    for (int gi = st.fast_begin; gi < st.fast_end; ++gi) {
+      Group2 &g = p->groups2[gi];
+      bool ok = (g.sync & kGroupProduct) != 0;
+      for (uint32_t i = g.op_begin; i < g.op_begin + g.n_ops; ++i) {
+        ok = ok && p->ops2_perm_tail[i];
+        group_of.push_back(gi);
+      }
+      oe += g.n_ops;
+      if (ok) g.sync |= kGroupClosingFree;
+    }
+    auto marked = [&](uint32_t i) { return (p->groups2[group_of[i - ob]].sync & kGroupClosingFree) != 0; };
+    for (bool changed = true; changed;) {
+      changed = false;
+      for (uint32_t c = ob; c < oe; ++c) {
+        if (forms.chain_units[c].empty()) continue;
+        bool any = marked(c), all = any;
+        for (int u : forms.chain_units[c]) {
+          any = any || marked((uint32_t)u);
+          all = all && marked((uint32_t)u);
+        }
+        if (!any || all) continue;
+        p->groups2[group_of[c - ob]].sync &= (uint8_t)~kGroupClosingFree;
+        for (int u : forms.chain_units[c]) p->groups2[group_of[(uint32_t)u - ob]].sync &= (uint8_t)~kGroupClosingFree;
+        changed = true;
+      }
+    }
+  }
+  // the builder reads the bit off the group's markers (BuildOp::pad2)
+  std::vector<char> free_at(p->mat_floats / kProductRecFloats + 2, 0);  // (records are kProductRecFloats apart from mat_floats_unit on)
+  for (const Group2 &g : p->groups2)
+    if ((g.sync & kGroupProduct) && (g.sync & kGroupClosingFree)) free_at[(g.prod_off - p->mat_floats_unit) / kProductRecFloats] = 1;
+  for (const BuildGroup &bg : p->groups) {
+    if (bg.dim != kBuildProduct || !free_at[(bg.mat_off - p->mat_floats_unit) / kProductRecFloats]) continue;
+    for (uint32_t k = bg.begin; k < bg.end; ++k)
+      if (p->build_ops[k].opcode == kChainMark) p->build_ops[k].pad2 = 1;
   }
 }
 
@@ -1518,6 +1586,7 @@ static void schedule_stages(qmle_plan *p, ScheduleCandidate c, int pad_high) {
   p->dev_src.clear();
   p->op_groups.clear();
   p->ops2.clear();
+  p->ops2_perm_tail.clear();
   p->groups2.clear();
   p->tbl2.clear();
   p->consts.resize(p->n_user_consts);  // drop permuted-matrix copies of a previous candidate
@@ -1754,6 +1823,7 @@ int compile_plan(qmle_plan *p) {
   FastOpForms forms;
   assign_unit_forms(p, forms);
   assign_product_forms(p, forms);
+  mark_closing_free_groups(p, forms);
   order_build_groups(p);
   return QMLE_OK;
 }
@@ -2044,7 +2114,13 @@ std::string describe_plan(const qmle_plan *p) {
       os << "],\"product_form_records\":[";
       for (int g = st.fast_begin; g < st.fast_end; ++g)
         os << (g > st.fast_begin ? "," : "") << ((p->groups2[g].sync & kGroupProduct) ? (long long)p->groups2[g].prod_off : -1ll);
-      os << "],\"group_product_form_last_run\":" << (s < 64 && ((p->last_run.product_form_stages >> s) & 1u) ? "true" : "false");
+      // ... and whether a run that ends this stage in |amplitude|^2 may build that record without a closing diagonal
+      // (mark_closing_free_groups); measured_form_last_run: the last batch run did, for its last stage, and ran them
+      os << "],\"closing_free_groups\":[";
+      for (int g = st.fast_begin; g < st.fast_end; ++g)
+        os << (g > st.fast_begin ? "," : "") << ((p->groups2[g].sync & kGroupClosingFree) ? "true" : "false");
+      os << "],\"group_product_form_last_run\":" << (s < 64 && ((p->last_run.product_form_stages >> s) & 1u) ? "true" : "false")
+         << ",\"measured_form_last_run\":" << (s + 1 == p->stages.size() && p->last_run.measured_form ? "true" : "false");
     }
     if (s + 1 == p->stages.size())
       os << ",\"measure_tiles_per_workgroup_last_run\":" << p->last_run.measure_tpw

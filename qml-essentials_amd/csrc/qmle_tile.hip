@@ -497,17 +497,61 @@ __device__ __forceinline__ void f_mirror(A16 &a, u64 tu) {
 #undef QMLE_MIRROR4X
 #undef QMLE_P
 }
-// the form word of a bit (the float 0, 1 or 2; per state, so wave-uniform: a scalar compare and branch)
+// ... measured form: the rotation itself as three shears, a0 -= tau a1; a1 += s a0; a0 -= tau a1 on the 8
+// pairs; tu = (-tau, s).  In place, no temporaries; the three dependent FMAs of a pair sit 8 instructions apart.
 template <int TB>
+__device__ __forceinline__ void f_shear3(A16 &a, u64 tu) {
+  constexpr int S = 1 << TB;
+#define QMLE_P(q) "+v"(at<pair_idx<TB>(q)>(a)), "+v"(at<pair_idx<TB>(q) | S>(a))
+  asm volatile(
+      "v_pk_fma_f32 %0, %16, %1, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %2, %16, %3, %2 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %4, %16, %5, %4 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %6, %16, %7, %6 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %8, %16, %9, %8 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %10, %16, %11, %10 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %12, %16, %13, %12 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %14, %16, %15, %14 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %1, %16, %0, %1 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %3, %16, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %5, %16, %4, %5 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %7, %16, %6, %7 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %9, %16, %8, %9 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %11, %16, %10, %11 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %13, %16, %12, %13 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %15, %16, %14, %15 op_sel:[1,0,0] op_sel_hi:[1,1,1]\n\t"
+      "v_pk_fma_f32 %0, %16, %1, %0 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %2, %16, %3, %2 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %4, %16, %5, %4 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %6, %16, %7, %6 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %8, %16, %9, %8 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %10, %16, %11, %10 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %12, %16, %13, %12 op_sel_hi:[0,1,1]\n\t"
+      "v_pk_fma_f32 %14, %16, %15, %14 op_sel_hi:[0,1,1]\n\t"
+      : QMLE_P(0), QMLE_P(1), QMLE_P(2), QMLE_P(3), QMLE_P(4), QMLE_P(5), QMLE_P(6), QMLE_P(7)
+      : "s"(tu));
+#undef QMLE_P
+}
+// the form word of a bit (the float 0, 1, 2 or 3; per state, so wave-uniform: a scalar compare and branch).  A record
+// holds either the two-shear forms 1 / 2 and a closing diagonal, or the form 3 and none (product_form_group): the side
+// of product_group's branch on the record's flag word says which words can occur (CLOSED: 1 and 2).
+template <int TB, bool CLOSED>
 __device__ __forceinline__ void f_real_step(A16 &a, uint32_t form, u64 tu) {
-  if (form == 0x3f800000u) f_shear<TB>(a, tu);
-  else if (form == 0x40000000u) f_mirror<TB>(a, tu);
+  if constexpr (CLOSED) {
+    if (form == 0x3f800000u) f_shear<TB>(a, tu);
+    else if (form == 0x40000000u) f_mirror<TB>(a, tu);
+  } else {
+    if (form == 0x40400000u) f_shear3<TB>(a, tu);
+  }
 }
 // One product-form group on the 16 amplitudes of a work item, straight-line: opening diagonal (entry 0 is a literal
 // 1: 30 packed instructions; low1 -- no member on in-thread bit 0 or 1 -- entries 0..3 are: 24), one real step per
-// member (16 or 24), closing diagonal (32).  The record streams through SGPRs 4 entries at a time, two loads ahead of
-// the one being consumed; touching a load's registers puts the wait for it in front of the next load's issue, as in
-// the gate loop of tile2_groups.
+// member (16 or 24; measured form: 24), closing diagonal (32) -- unless the record says it has none (measured mode,
+// kProductRecNoClose; per state, so wave-uniform: one scalar branch): then neither its loads nor its multiplies are
+// issued.  The record streams through SGPRs 4 entries at a time, two loads ahead of the one being consumed; touching a
+// load's registers puts the wait for it in front of the next load's issue, as in the gate loop of tile2_groups.  (The
+// flag word rides with the third load and is spent at the branch, in front of the steps' load: at no point are more
+// SGPRs live than the 28 of the record's widest stretch.)
 __device__ __forceinline__ void product_group(A16 &a, const u64 QMLE_CONSTANT *rec, bool low1) {
   u64 t0, t1, t2, t3;
 #define QMLE_LD4(x, i) u64 x##0 = rec[i], x##1 = rec[(i) + 1], x##2 = rec[(i) + 2], x##3 = rec[(i) + 3]
@@ -520,31 +564,48 @@ __device__ __forceinline__ void product_group(A16 &a, const u64 QMLE_CONSTANT *r
   if (!low1) QMLE_CMUL3D(a.v1, a.v2, a.v3, oa1, oa2, oa3);
   QMLE_IN4(ob);
   QMLE_LD4(od, 12);
+  uint32_t no_close = reinterpret_cast<const uint32_t QMLE_CONSTANT *>(rec)[kProductRecNoClose];
   QMLE_CMUL4D(a.v4, a.v5, a.v6, a.v7, ob0, ob1, ob2, ob3);
   QMLE_IN4(oc);
-  QMLE_LD4(st, kSteps);
-  u64 f01 = rec[kForms], f23 = rec[kForms + 1];
-  QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, oc0, oc1, oc2, oc3);
-  QMLE_IN4(od);
-  QMLE_LD4(ca, kClose);
-  QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, od0, od1, od2, od3);
-  QMLE_IN4(st);
-  asm volatile("" : "+s"(f01), "+s"(f23)::"memory");
-  QMLE_LD4(cb, kClose + 4);
-  f_real_step<0>(a, (uint32_t)f01, st0);
-  f_real_step<1>(a, (uint32_t)(f01 >> 32), st1);
-  f_real_step<2>(a, (uint32_t)f23, st2);
-  f_real_step<3>(a, (uint32_t)(f23 >> 32), st3);
-  QMLE_IN4(ca);
-  QMLE_LD4(cc, kClose + 8);
-  QMLE_CMUL4D(a.v0, a.v1, a.v2, a.v3, ca0, ca1, ca2, ca3);
-  QMLE_IN4(cb);
-  QMLE_LD4(cd_, kClose + 12);
-  QMLE_CMUL4D(a.v4, a.v5, a.v6, a.v7, cb0, cb1, cb2, cb3);
-  QMLE_IN4(cc);
-  QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, cc0, cc1, cc2, cc3);
-  QMLE_IN4(cd_);
-  QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, cd_0, cd_1, cd_2, cd_3);
+  // (the wait for `oc` covers the flag word, which was issued behind it: scalar loads return out of order)
+  asm volatile("" : "+s"(no_close));
+  if (no_close == 0u) {
+    QMLE_LD4(st, kSteps);
+    u64 f01 = rec[kForms], f23 = rec[kForms + 1];
+    QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, oc0, oc1, oc2, oc3);
+    QMLE_IN4(od);
+    QMLE_LD4(ca, kClose);
+    QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, od0, od1, od2, od3);
+    QMLE_IN4(st);
+    asm volatile("" : "+s"(f01), "+s"(f23)::"memory");
+    QMLE_LD4(cb, kClose + 4);
+    f_real_step<0, true>(a, (uint32_t)f01, st0);
+    f_real_step<1, true>(a, (uint32_t)(f01 >> 32), st1);
+    f_real_step<2, true>(a, (uint32_t)f23, st2);
+    f_real_step<3, true>(a, (uint32_t)(f23 >> 32), st3);
+    QMLE_IN4(ca);
+    QMLE_LD4(cc, kClose + 8);
+    QMLE_CMUL4D(a.v0, a.v1, a.v2, a.v3, ca0, ca1, ca2, ca3);
+    QMLE_IN4(cb);
+    QMLE_LD4(cd_, kClose + 12);
+    QMLE_CMUL4D(a.v4, a.v5, a.v6, a.v7, cb0, cb1, cb2, cb3);
+    QMLE_IN4(cc);
+    QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, cc0, cc1, cc2, cc3);
+    QMLE_IN4(cd_);
+    QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, cd_0, cd_1, cd_2, cd_3);
+  } else {
+    QMLE_LD4(st, kSteps);
+    u64 f01 = rec[kForms], f23 = rec[kForms + 1];
+    QMLE_CMUL4D(a.v8, a.v9, a.v10, a.v11, oc0, oc1, oc2, oc3);
+    QMLE_IN4(od);
+    QMLE_CMUL4D(a.v12, a.v13, a.v14, a.v15, od0, od1, od2, od3);
+    QMLE_IN4(st);
+    asm volatile("" : "+s"(f01), "+s"(f23)::"memory");
+    f_real_step<0, false>(a, (uint32_t)f01, st0);
+    f_real_step<1, false>(a, (uint32_t)(f01 >> 32), st1);
+    f_real_step<2, false>(a, (uint32_t)f23, st2);
+    f_real_step<3, false>(a, (uint32_t)(f23 >> 32), st3);
+  }
 #undef QMLE_LD4
 #undef QMLE_IN4
 }
