@@ -217,7 +217,9 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * product form (the fast tile kernel always does; the generic tile kernel applies the plain records).
  * "closing_free_groups"[g]: a run that ends the stage in |amplitude|^2 only may build group g's record without a
  * closing diagonal (see qmle_group_product_form_measured); "measured_form_last_run": the last batch run did so for
- * its last stage and ran those records (false on every other stage and after every other kind of run). */
+ * its last stage and ran those records (false on every other stage and after every other kind of run).
+ * "walk_kernel_last_run" (last stage): the fused <Z> pass of the last batch run ran in the straight-line kernel of
+ * measuring walks whose groups all run in product form (see "walk_kernel" of qmle_plan_tile_route). */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* Host only (no GPU needed): how tile stage `stage` of `plan` would run for a request -- the launch policy of the
  * tile passes as JSON, written like qmle_plan_describe (returns the bytes needed, or an error < 0: no tile stage
@@ -229,8 +231,10 @@ int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
  * "tile_free", "mw_lean", "slots_in_lds", "fill" / "fill_elided" (a zero fill precedes the launch / is left out
  * because the zeros are in place), "tiles_per_workgroup", "row_shift" (a partial row covers 2^row_shift tiles),
  * the walk ("walk_slab", "walk_sync_staged", "walk_sync_tile_end", "staging_dma", "lane_swap",
- * "lane_swap_crossed"), "from_registers", "wave_private", "product_form".  A batch run reports what it did in the
- * "..._last_run" keys of qmle_plan_describe. */
+ * "lane_swap_crossed"), "from_registers", "wave_private", "product_form", "walk_kernel" (the DMA walk with the last
+ * group through lane swaps runs in a kernel of its own, because every group of the stage runs in product form; family,
+ * instantiation keys, launch shape and rows stay those of the fast tile kernel).  A batch run reports what it did in
+ * the "..._last_run" keys of qmle_plan_describe. */
 #define QMLE_ROUTE_INIT_ZERO      1u   /* the pass starts from |0..0> instead of reading the states */
 #define QMLE_ROUTE_FROM_ZERO      2u   /* the run started from |0..0> (every qmle_run_batch) */
 #define QMLE_ROUTE_FOLD_COLS      4u   /* the fold-column buffer is there (every qmle_run_batch of a plan that wants it) */

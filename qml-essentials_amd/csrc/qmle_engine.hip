@@ -1036,6 +1036,7 @@ static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, i
           plan->last_run.wave_private = route.wave_private;
           plan->last_run.staging_dma = (route.walk & kWalkDma) != 0;
           plan->last_run.lane_swap = (route.walk & kWalkLaneSwap) != 0;
+          plan->last_run.walk_kernel = route.walk_kernel;
         }
         if (reuse && route.fill) {
           slot_zeroed[slot] = bc;

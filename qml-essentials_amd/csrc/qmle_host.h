@@ -182,6 +182,9 @@ struct TileRoute {
   uint32_t walk = 0;  // kWalk* (k_tile2)
   // <Z> from the last group's registers; ... in a tile loop without a workgroup barrier; product-form groups run
   bool from_regs = false, wave_private = false, product_form = false;
+  // the DMA walk with the last group through lane swaps runs in k_measure_walk: every group in product form, none that
+  // scatters re-layouts, 1..3 gathered groups, swaps straight or crossed (family, instantiation fields, launch shape and rows stay k_tile2's)
+  bool walk_kernel = false;
 };
 TileRoute route_tile(const qmle_plan *p, size_t stage, const TileRequest &rq);
 // the device pointers of a tile pass

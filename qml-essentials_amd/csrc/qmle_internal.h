@@ -277,6 +277,7 @@ struct LastRun {
   // swaps (Stage::lane_swap_last)
   int measure_tpw = 0;
   bool measure_regs = false, wave_private = false, staging_dma = false, lane_swap = false;
+  bool walk_kernel = false;  // ... by k_measure_walk, the straight-line kernel of all-product-form stages (TileRoute::walk_kernel)
   // how the last batch run ordered its chunks (ChunkPipeline::form; a run with one chunk, or with the whole state in
   // the LDS, is a one-stream run)
   int chunk_loop = kChunkLoopNone;

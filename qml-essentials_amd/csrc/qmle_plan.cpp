@@ -2129,7 +2129,8 @@ std::string describe_plan(const qmle_plan *p) {
          << ",\"staging_dma_last_run\":" << (p->last_run.staging_dma ? "true" : "false")
          << ",\"last_group_lane_swap_last_run\":" << (p->last_run.lane_swap ? "true" : "false")
          << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->last_run.chunk_loop] << "\""
-         << ",\"matrices_from_map_last_run\":" << (p->last_run.matrices_from_map ? "true" : "false");
+         << ",\"matrices_from_map_last_run\":" << (p->last_run.matrices_from_map ? "true" : "false")
+         << ",\"walk_kernel_last_run\":" << (p->last_run.walk_kernel ? "true" : "false");
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";

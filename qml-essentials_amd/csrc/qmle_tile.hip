@@ -11,6 +11,9 @@
 //   k_tile2<NT, MEASURE, MULTI, WS, MW, MASKS>
 //                      the fast tile kernel: stages of (controlled) 2x2 gates as table-addressed register-tile
 //                      groups, several tiles per workgroup, <Z> from the last group's registers
+//   k_measure_walk<NT, G, CROSS>
+//                      k_tile2's DMA measuring walk for stages whose groups all run in product form: G gathered groups
+//                      and the lane-swapped last group, straight-line (TileRoute::walk_kernel)
 //   k_reg_measure<FOLD>, k_reg_measure_mono (+ k_mono_coef)
 //                      measuring last pass in registers: <Z> / Z parities accumulated
 //                      across tiles per work item, gates on known zeros folded away
@@ -1096,6 +1099,29 @@ __device__ __forceinline__ void whole_state_expval(const TileArgs &a, uint32_t s
   }
 }
 
+// The eight pieces of one tile of the DMA walk (kWalkDma; k_tile2 and k_measure_walk): the tile at `p` goes into the
+// issuing wave's slab, lane offset `goff8`, piece u at uoff[u] with delta[u & 3] XORed into the lane's part.
+template <bool NT>
+__device__ __forceinline__ void dma_tile_pieces(float4 *smem4, const char *p, int tid, uint32_t goff8,
+                                                const uint32_t (&uoff)[8], const uint32_t (&delta)[4]) {
+  const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(tid / kWave);
+  __attribute__((address_space(3))) char *slab0 =
+      (__attribute__((address_space(3))) char *)reinterpret_cast<char *>(smem4) + (wv << 13);
+  // (scalar base + 32-bit lane offset, both opaque: left to itself the loop keeps eight 64-bit addresses per lane
+  // alive across the tiles, 16 registers)
+  asm volatile("" : "+s"(p));
+  uint32_t vo[4];
+  static_for<4>([&](auto k) {
+    vo[(int)k] = goff8 ^ delta[(int)k];
+    asm volatile("" : "+v"(vo[(int)k]));
+  });
+  static_for<8>([&](auto u) {
+    const char *src = p + uoff[(int)u] + vo[(int)u & 3];
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, slab0 + ((int)u << 10), 16, 0,
+                                     NT ? 2 : 0);  // (aux 2 = nt, the policy of ld4<true>)
+  });
+}
+
 // MEASURE: a.meas is one of the TM_EXPVAL_* epilogues (own instantiation: the storing kernel keeps
 // a small register budget).  MULTI: several tiles per workgroup (f.tpw), plain all-live stages
 // with the TM_STORE / TM_PROBS / TM_EXPVAL_PARTIAL epilogues only.
@@ -1201,24 +1227,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
   // holds the lane's part of that source index, the piece adds local bits 3 and 4 (XOR: the lane's part may hold them)
   // and its own three bits.  A wave issues into its own slab only, and only when its last reads of it have returned.
   auto dma_tile = [&](const char *p) {
-    if constexpr (ZR) {
-      const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(tid / kWave);
-      __attribute__((address_space(3))) char *slab0 =
-          (__attribute__((address_space(3))) char *)reinterpret_cast<char *>(smem4) + (wv << 13);
-      // (scalar base + 32-bit lane offset, both opaque: left to itself the loop keeps eight 64-bit addresses per lane
-      // alive across the tiles, 16 registers)
-      asm volatile("" : "+s"(p));
-      uint32_t vo[4];
-      static_for<4>([&](auto k) {
-        vo[(int)k] = goff8 ^ f.dma_delta[(int)k];
-        asm volatile("" : "+v"(vo[(int)k]));
-      });
-      static_for<8>([&](auto u) {
-        const char *src = p + uoff[(int)u] + vo[(int)u & 3];
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src, slab0 + ((int)u << 10), 16, 0,
-                                         NT ? 2 : 0);  // (aux 2 = nt, the policy of ld4<true>)
-      });
-    }
+    if constexpr (ZR) dma_tile_pieces<NT>(smem4, p, tid, goff8, uoff, f.dma_delta);
   };
   if (dma) dma_tile(st);  // the first tile: in flight while the tables and the matrix row are fetched
   const Group2 QMLE_CONSTANT *grp = as_constant(f.groups);
@@ -1395,6 +1404,129 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MASKS 
                      31 - __builtin_clz((unsigned)tpw), blockIdx.x, gridDim.x, b);
   }
 }
+
+// ---- the measuring walk of an all-product-form stage, straight-line -----------------
+// k_tile2<NT, true, true>'s DMA walk with the last group through lane swaps, for stages whose groups all run in product
+// form and never re-layout (route_tile: TileRoute::walk_kernel): G gathered groups, then the stage's last group behind
+// swap_lanes_45<CROSS> (Stage::lane_swap_cross: choose_thread_bits may order the front group's lane bits 4 and 5 either
+// way round, so a last group of two members comes straight or crossed).  What tile2_groups reads, tests and re-derives per
+// tile and group -- headers, basis offsets, record offsets, the next group's table entry (a per-lane load beside the
+// DMA's pieces), the op-stream index, the pipeline registers of the gate-by-gate path -- is known when the walk starts:
+// the argument holds it per group, the prologue loads the table entries once while tile 0's pieces are in flight, and
+// the tile loop is the arithmetic, the LDS traffic and the DMA issue.  Same device functions, same order of operations:
+// bit for bit k_tile2's rows.
+struct WalkGroup {
+  uint32_t tbl;       // Group2::tbl
+  uint32_t off[4];    // Group2::off[1], [2], [4], [8]
+  uint32_t prod_off;  // Group2::prod_off
+  uint32_t flags;     // bit 0: kGroupProductLow1; bit 1: a workgroup barrier in front of the group's gather (Group2::sync bit 0)
+};
+struct WalkArgs {
+  const float2 *states;
+  const float *mats;
+  float *out;
+  const uint32_t *tbl;
+  uint32_t mat_floats;
+  int n, T, tpw;
+  uint32_t tile_stride;
+  int n_runs;  // 0..6: Tile2Args::run_*
+  uint32_t run_off[6], run_mask[6], run_pos[6];
+  int n_in_runs;  // Tile2Args::in_* / gtab of the DMA form
+  uint32_t in_off[4], in_mask[4], in_pos[4], gtab;
+  uint32_t uoff8[8], dma_delta[4];
+  WalkGroup g[3];                    // the gathered groups
+  uint32_t last_prod_off, last_low1;  // the group behind the lane swaps
+  uint16_t zreg[16];                 // Stage::zreg_swap
+  uint8_t qsrc[QMLE_MAX_QUBITS + 1];  // TileArgs::qsrc of the register-measuring walk
+};
+#define QMLE_WOFF(c, g) \
+  ((((c) & 1) ? (g).off[0] : 0u) ^ (((c) & 2) ? (g).off[1] : 0u) ^ (((c) & 4) ? (g).off[2] : 0u) ^ (((c) & 8) ? (g).off[3] : 0u))
+template <bool NT, int G, bool CROSS>
+__global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(5))) k_measure_walk(const WalkArgs w) {
+  static_assert(G >= 1 && G <= 3, "gathered groups");
+  extern __shared__ float4 smem4[];
+  const uint32_t sbo = lds_offset_of(smem4);  // (0: issue_walk checks, as for k_tile2)
+  float *red = reinterpret_cast<float *>(smem4);
+  const int tid = threadIdx.x, nt = blockDim.x, b = blockIdx.y, T = w.T, tpw = w.tpw;
+  uint64_t base = 0;
+  {
+    const uint32_t tile = blockIdx.x * (uint32_t)tpw;
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+      if (r < w.n_runs) base |= (uint64_t)((tile >> w.run_off[r]) & w.run_mask[r]) << w.run_pos[r];
+  }
+  const char *st = reinterpret_cast<const char *>(w.states + ((size_t)b << w.n) + base);
+  uint32_t goff8;
+  if (w.n_in_runs < 0) {
+    goff8 = w.tbl[w.gtab + tid];
+  } else {
+    const uint32_t jg = sw((2u * (tid & (kWave - 1))) | ((uint32_t)(tid / kWave) << 10));
+    uint32_t g = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      if (r < w.n_in_runs) g |= ((jg >> w.in_off[r]) & w.in_mask[r]) << w.in_pos[r];
+    goff8 = g << 3;
+  }
+  uint32_t uoff[8];
+#pragma unroll
+  for (int u = 0; u < 8; ++u) uoff[u] = w.uoff8[u];
+  dma_tile_pieces<NT>(smem4, st, tid, goff8, uoff, w.dma_delta);  // tile 0: in flight while the tables are fetched
+  uint32_t addr[G];
+  static_for<G>([&](auto k) { addr[(int)k] = (w.tbl[w.g[(int)k].tbl + tid] & ~7u) + sbo; });
+  const u64 QMLE_CONSTANT *mrow = as_constant(reinterpret_cast<const u64 *>(w.mats + (size_t)b * w.mat_floats));
+  const char QMLE_CONSTANT *ka = (const char QMLE_CONSTANT *)__builtin_amdgcn_kernarg_segment_ptr();
+  const int qsrc = tid <= QMLE_MAX_QUBITS ? (int)(uint8_t)ka[offsetof(WalkArgs, qsrc) + tid] : 64;
+  const uint16_t QMLE_CONSTANT *zr = (const uint16_t QMLE_CONSTANT *)(ka + offsetof(WalkArgs, zreg));
+  float zsq[16], zwk[4] = {0.f, 0.f, 0.f, 0.f};
+  static_for<16>([&](auto c) { zsq[(int)c] = 0.f; });
+  for (int i = 0; i < tpw; ++i) {
+    if (i > 0) st += w.tile_stride * sizeof(float2);
+    // this tile was issued one tile ago (the first: above) by this wave into its own slab
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    A16 r;
+    // one gathered group: g is its WalkGroup, sync_next whether a workgroup barrier stands in front of the next gather
+    auto group = [&](auto k, const auto &g, bool sync_next) {
+      uint32_t ad = addr[(int)k];
+      asm volatile("" : "+v"(ad));  // (per tile: keeps the 16 slot addresses out of loop-carried registers)
+#define QMLE_LD(c) r.v##c = lds_ld64(ad ^ QMLE_WOFF(c, g));
+      QMLE_X16(QMLE_LD)
+#undef QMLE_LD
+      if constexpr ((int)k + 1 == G) {
+        if (i + 1 < tpw) {  // (nothing behind the walk's last tile: tile_zr_finish's scratch aliases the tile)
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the gather has returned: the slab is dead
+          dma_tile_pieces<NT>(smem4, st + w.tile_stride * sizeof(float2), tid, goff8, uoff, w.dma_delta);
+        }
+      }
+      product_group(r, mrow + (g.prod_off >> 1), (g.flags & 1u) != 0);
+      if constexpr ((int)k + 1 < G) {
+        asm volatile("" : "+v"(ad));  // (the addresses are re-derived for the scatter: 96 VGPRs, as tile2_groups)
+#define QMLE_ST(c) lds_st64(ad ^ QMLE_WOFF(c, g), r.v##c);
+        QMLE_X16(QMLE_ST)
+#undef QMLE_ST
+        if (sync_next) __syncthreads();
+        else asm volatile("" ::: "memory");
+      }
+    };
+    static_for<G>([&](auto k) {
+      if constexpr (G == 3) {
+        // (the words and XOR closures of two groups stay in SGPRs across the walk; those of three do not fit beside a
+        // record's 28 and would go to VGPR lanes: there each group's words come from the argument segment per tile,
+        // through a pointer the loop cannot see through, and the closure is rebuilt from them)
+        const WalkGroup QMLE_CONSTANT *kg = (const WalkGroup QMLE_CONSTANT *)(ka + offsetof(WalkArgs, g)) + (int)k;
+        asm volatile("" : "+s"(kg));
+        group(k, kg[0], (int)k + 1 < G && (kg[(int)k + 1 < G ? 1 : 0].flags & 2u) != 0);
+      } else {
+        group(k, w.g[(int)k], (int)k + 1 < G && (w.g[(int)k + 1 < G ? (int)k + 1 : 0].flags & 2u) != 0);
+      }
+    });
+    swap_lanes_45<CROSS>(r);
+    product_group(r, mrow + (w.last_prod_off >> 1), w.last_low1 != 0);
+    tile_zr_accumulate(r, i, zsq, zwk);
+    asm volatile("" ::: "memory");  // the tile buffer is reused by the wave that read it
+  }
+  tile_zr_finish(w.out, red, zsq, zwk, zr, T, qsrc, tid, nt, 31 - __builtin_clz((unsigned)tpw), blockIdx.x, gridDim.x, b);
+}
+#undef QMLE_WOFF
 
 // ---- measuring pass in registers -----------------------------------------------------------
 // Last pass of a <Z> / Z-parity run whose gates all sit on <= 4 bit positions (ONE register-tile
@@ -2007,6 +2139,11 @@ int tile_threads(int T) {  // one register-tile work item (16 amplitudes) per th
   X(true,  true,  false, false, true,  false)      \
   X(false, true,  false, true,  true,  false)
 #define QMLE_TILE2(NT, ME, MU, WS, MW, MA) (k_tile2<NT, ME, MU, WS, MW, MA>)
+//                   NT     G  CROSS
+#define QMLE_WALK_INSTANCES(X)                                                                       \
+  X(false, 1, false) X(true, 1, false) X(false, 2, false) X(true, 2, false) X(false, 3, false) X(true, 3, false) \
+  X(false, 1, true) X(true, 1, true) X(false, 2, true) X(true, 2, true) X(false, 3, true) X(true, 3, true)
+#define QMLE_WALK(NT, G, CR) (k_measure_walk<NT, G, CR>)
 //                   DENSE4 MW
 #define QMLE_TILE_INSTANCES(X) X(false, false) X(true, false) X(false, true) X(true, true)
 #define QMLE_TILE1(D4, MW) (k_tile<D4, MW>)
@@ -2046,6 +2183,43 @@ static TileRoute route_reg_measure(const qmle_plan *p, const Stage &st, TileFami
   r.row_shift = q;
   r.tpw = 1 << q;
   return r;
+}
+
+// A stage's outer bit positions (ascending) as contiguous runs (Tile2Args::run_*): their number, -1 for more than six
+// (k_tile2 then walks the positions one by one).  Any array may be null.
+static int stage_outer_runs(const qmle_plan *p, const Stage &st, uint32_t *off, uint32_t *mask, uint32_t *pos) {
+  int nr = 0;
+  const int n_outer = p->n - st.T;
+  for (int i = 0; i < n_outer && nr <= 6;) {
+    int len = 1;
+    while (i + len < n_outer && st.outer_bits[i + len] == st.outer_bits[i] + len) ++len;
+    if (nr < 6 && off && mask && pos) {
+      off[nr] = (uint32_t)i;
+      mask[nr] = len >= 32 ? 0xffffffffu : ((1u << len) - 1u);
+      pos[nr] = (uint32_t)st.outer_bits[i];
+    }
+    ++nr;
+    i += len;
+  }
+  if (off && mask && pos)
+    for (int k = nr < 6 ? nr : 6; k < 6; ++k) off[k] = mask[k] = pos[k] = 0;
+  return nr <= 6 ? nr : -1;
+}
+
+// k_measure_walk takes a k_tile2 route: the register-measuring DMA walk with the last group through lane
+// swaps, straight or crossed, every group of the stage in product form, 1..3 gathered groups in front of the swapped
+// one, none of which re-layouts on its scatter.  (Group2::relayout of the last two groups is not asked: the last gathered
+// group scatters nothing and the swapped group neither gathers nor scatters -- a measuring stage's last group carries
+// the flag for the storing walks, which do scatter it.  A walk is >= 2 tiles per workgroup; the kernel computes the tile
+// base from the outer runs only, so a stage with more than six of them keeps k_tile2.)
+static bool walk_kernel_serves(const qmle_plan *p, const Stage &st, const TileRoute &r, uint32_t zin_local) {
+  if (r.family != TF_TILE2 || !r.from_regs || !(r.walk & kWalkDma) || !(r.walk & kWalkLaneSwap)) return false;
+  if ((r.walk & (kWalkSyncStaged | kWalkSyncTileEnd)) || zin_local != 0 || r.tpw < 2) return false;
+  const int gathered = st.fast_end - st.fast_begin - 1;
+  if (gathered < 1 || gathered > 3) return false;
+  for (int g = st.fast_begin; g < st.fast_end; ++g)
+    if (!(p->groups2[g].sync & kGroupProduct) || (g + 2 < st.fast_end && p->groups2[g].relayout)) return false;
+  return stage_outer_runs(p, st, nullptr, nullptr, nullptr) >= 0;
 }
 
 // The launch policy of a tile stage: every threshold below is a measured one.
@@ -2222,6 +2396,7 @@ TileRoute route_tile(const qmle_plan *p, size_t si, const TileRequest &rq) {
     // the whole state in one tile (10..13 qubits)
     r.ws = r.mw ? st.T == p->n : st.T == p->n && !r.multi && !r.nt;
     r.masks = !r.mw && !r.ws && r.measure && r.multi && meas == TM_EXPVAL_MASKS;
+    r.walk_kernel = walk_kernel_serves(p, st, r, zin_local);
     return r;
   }
   r.lds_bytes = tile_lds_bytes(st.T, st.L, r.slots_in_lds ? n_ops : 0);
@@ -2338,6 +2513,63 @@ int issue_tile(const qmle_plan *p, const Stage &st, const TileBuffers &b, const 
   return QMLE_OK;
 }
 
+// TileRoute::walk_kernel: k_measure_walk on what issue_tile2 derived for k_tile2 -- the same tables, records, launch
+// shape and rows; the argument holds per group what tile2_groups reads from Group2 per tile.
+int issue_walk(const qmle_plan *p, const Stage &st, const TileArgs &a, const Tile2Args &f, const TileRoute &r,
+               hipStream_t stream) {
+  if (FirstUse once{2}; once.first) {
+#define QMLE_X(NT, G, CR)                      \
+  QMLE_LDS_BASE_CHECK(QMLE_WALK(NT, G, CR)); \
+  HIPCHK(hipFuncSetAttribute((const void *)QMLE_WALK(NT, G, CR), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    QMLE_WALK_INSTANCES(QMLE_X)
+#undef QMLE_X
+    once.done();
+  }
+  WalkArgs w;
+  std::memset(&w, 0, sizeof(w));
+  w.states = a.states;
+  w.mats = a.mats;
+  w.out = reinterpret_cast<float *>(a.out);
+  w.tbl = f.tbl;
+  w.mat_floats = a.mat_floats;
+  w.n = a.n;
+  w.T = a.T;
+  w.tpw = f.tpw;
+  w.tile_stride = f.tile_stride;
+  w.n_runs = stage_outer_runs(p, st, w.run_off, w.run_mask, w.run_pos);  // (0..6: walk_kernel_serves)
+  w.n_in_runs = f.n_in_runs;
+  w.gtab = f.gtab;
+  std::memcpy(w.in_off, f.in_off, sizeof(w.in_off));
+  std::memcpy(w.in_mask, f.in_mask, sizeof(w.in_mask));
+  std::memcpy(w.in_pos, f.in_pos, sizeof(w.in_pos));
+  std::memcpy(w.uoff8, f.uoff8, sizeof(w.uoff8));
+  std::memcpy(w.dma_delta, f.dma_delta, sizeof(w.dma_delta));
+  const int gathered = st.fast_end - st.fast_begin - 1;  // (1..3: walk_kernel_serves; anything else finds no instantiation below)
+  for (int k = 0; k < gathered && k < 3; ++k) {
+    const Group2 &g = p->groups2[st.fast_begin + k];
+    w.g[k].tbl = g.tbl;
+    for (int j = 0; j < 4; ++j) w.g[k].off[j] = g.off[1 << j];
+    w.g[k].prod_off = g.prod_off;
+    w.g[k].flags = ((g.sync & kGroupProductLow1) ? 1u : 0u) | ((g.sync & 1) ? 2u : 0u);
+  }
+  const Group2 &last = p->groups2[st.fast_end - 1];
+  w.last_prod_off = last.prod_off;
+  w.last_low1 = (last.sync & kGroupProductLow1) ? 1u : 0u;
+  static_assert(sizeof(w.zreg) <= sizeof(a.obs_local) && sizeof(w.qsrc) == sizeof(a.qsrc), "the records of TileArgs");
+  std::memcpy(w.zreg, a.obs_local, sizeof(w.zreg));
+  std::memcpy(w.qsrc, a.qsrc, sizeof(w.qsrc));
+  const bool cross = (r.walk & kWalkLaneSwapCross) != 0;
+  const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
+#define QMLE_X(NT, G, CR)                                                          \
+  if (r.nt == NT && gathered == G && cross == CR && w.n_runs >= 0)                 \
+    hipLaunchKernelGGL(QMLE_WALK(NT, G, CR), grid, block, r.lds_bytes, stream, w); \
+  else
+  QMLE_WALK_INSTANCES(QMLE_X) return QMLE_ERR_INTERNAL;
+#undef QMLE_X
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
 int issue_tile2(const qmle_plan *p, const Stage &st, const TileBuffers &b, const TileRequest &rq, const TileRoute &r,
                 hipStream_t stream) {
   if (FirstUse once{1}; once.first) {
@@ -2357,23 +2589,7 @@ int issue_tile2(const qmle_plan *p, const Stage &st, const TileBuffers &b, const
   f.n_ops_stage = 0;
   for (int g = st.fast_begin; g < st.fast_end; ++g) f.n_ops_stage += p->groups2[g].n_ops;
   f.gtab = st.fast_gtab;
-  {  // outer bit positions (ascending) as contiguous runs
-    int nr = 0;
-    const int n_outer = p->n - st.T;
-    for (int i = 0; i < n_outer && nr <= 6;) {
-      int len = 1;
-      while (i + len < n_outer && st.outer_bits[i + len] == st.outer_bits[i] + len) ++len;
-      if (nr < 6) {
-        f.run_off[nr] = (uint32_t)i;
-        f.run_mask[nr] = len >= 32 ? 0xffffffffu : ((1u << len) - 1u);
-        f.run_pos[nr] = (uint32_t)st.outer_bits[i];
-      }
-      ++nr;
-      i += len;
-    }
-    f.n_runs = nr <= 6 ? nr : -1;
-    for (int k = nr < 6 ? nr : 6; k < 6; ++k) f.run_off[k] = f.run_mask[k] = f.run_pos[k] = 0;
-  }
+  f.n_runs = stage_outer_runs(p, st, f.run_off, f.run_mask, f.run_pos);
   // local bits 0 .. top of a lane's index (bits it never sets are harmless) -> global positions, as runs
   auto lane_runs = [&](int top) { f.n_in_runs = stage_lane_runs(st, top, f.in_off, f.in_mask, f.in_pos); };
   lane_runs(st.T - 4);  // index 2 tid
@@ -2408,6 +2624,7 @@ int issue_tile2(const qmle_plan *p, const Stage &st, const TileBuffers &b, const
       std::memcpy(a.obs_local, st.zreg_swap, sizeof(st.zreg_swap));
     }
   }
+  if (r.walk_kernel) return issue_walk(p, st, a, f, r, stream);
   const dim3 grid(r.grid_x, r.grid_y), block(r.threads);
 #define QMLE_X(NT, ME, MU, WS, MW, MA)                                                                         \
   if (r.nt == NT && r.measure == ME && r.multi == MU && r.ws == WS && r.mw == MW && r.masks == MA)             \
@@ -2469,12 +2686,14 @@ int qmle_plan_tile_route(const qmle_plan *plan, int stage, int batch, int meas, 
       "\"masks\":%s,\"mono_q\":%d,\"pair\":%s,\"grid\":[%u,%u],\"threads\":%u,\"lds_bytes\":%zu,\"compact\":%s,"
       "\"tile_free\":%u,\"mw_lean\":%s,\"slots_in_lds\":%s,\"fill\":%s,\"fill_elided\":%s,\"tiles_per_workgroup\":%d,"
       "\"row_shift\":%d,\"walk_slab\":%s,\"walk_sync_staged\":%s,\"walk_sync_tile_end\":%s,\"staging_dma\":%s,"
-      "\"lane_swap\":%s,\"lane_swap_crossed\":%s,\"from_registers\":%s,\"wave_private\":%s,\"product_form\":%s}",
+      "\"lane_swap\":%s,\"lane_swap_crossed\":%s,\"from_registers\":%s,\"wave_private\":%s,\"product_form\":%s,"
+      "\"walk_kernel\":%s}",
       r.status, kTileFamilyNames[r.family], tf(r.dense4), tf(r.mw), tf(r.nt), tf(r.measure), tf(r.multi), tf(r.ws),
       tf(r.masks), r.mono_q, tf(r.pair), r.grid_x, r.grid_y, r.threads, r.lds_bytes, tf(r.compact), r.tile_free,
       tf(r.mw_lean), tf(r.slots_in_lds), tf(r.fill), tf(r.fill_elided), r.tpw, r.row_shift, tf(r.walk & kWalkSlab),
       tf(r.walk & kWalkSyncStaged), tf(r.walk & kWalkSyncTileEnd), tf(r.walk & kWalkDma), tf(r.walk & kWalkLaneSwap),
-      tf(r.walk & kWalkLaneSwapCross), tf(r.from_regs), tf(r.wave_private), tf(r.product_form));
+      tf(r.walk & kWalkLaneSwapCross), tf(r.from_regs), tf(r.wave_private), tf(r.product_form),
+      tf(r.walk_kernel));
   if (buf && cap > 0) {
     const size_t nc = (size_t)len < cap - 1 ? (size_t)len : cap - 1;
     std::memcpy(buf, js, nc);
