@@ -614,6 +614,42 @@ int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double
 size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                               int n_obs_terms, int n_obs);
 
+/* The same sweeps, also returning MATRIX COTANGENTS: the sensitivity of C to the entries of one-wire matrix gates
+ * (QMLE_OP_MAT1, QMLE_OP_MAT1_ROW), from which a caller that knows dU/dtheta forms any dC/dtheta (pulse gates: the
+ * Jacobian of the pulse solve).  With lambda_k = lambda with all later gates undone and phi_k = the state in FRONT of
+ * the gate at reverse position r on wire q,
+ *   G[a][c] = sum_rest conj(lambda_k[a, rest]) phi_k[c, rest]     (a, c = value of wire q),
+ *   dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta.
+ * One read of psi and lambda gives all eight numbers: the 2x2 moment on the states behind the gate, times the
+ * transpose of the reverse op's own matrix U^+.
+ *   mat_out[r]  HOST array, one entry per op of `rev` (n_terms of them): index < n_mat of the 2x2 that reverse op r
+ *               reports, or -1.  >= 0 on anything but a one-wire matrix operator: QMLE_ERR_UNSUPPORTED (two-wire
+ *               matrices are not served); >= n_mat: QMLE_ERR_SLOT_RANGE.
+ *   d_cot       [batch][n_mat][2][2][re, im], float / double, zeroed by the call.
+ * The seed: exactly one of obs_wire_masks (Z parities, n_obs of them; n_obs_terms ignored) and obs_terms (Pauli
+ * words, as for qmle_adjoint_gradient_pauli) is non-NULL, else QMLE_ERR_INVALID_ARG.  d_grad and `terms` as for the
+ * functions above: angle gradients and cotangents come from ONE sweep.  The workspace has a query of its own (pass
+ * n_obs_terms = 0 for the Z seed); a smaller one is QMLE_ERR_INVALID_ARG.  Routes: the whole sweep in LDS (n <= 13)
+ * and one streaming pass per gate serve the request; a `rev` plan compiled for fused tile passes
+ * (QMLE_PLAN_NO_MERGE) that does not fit LDS returns QMLE_ERR_UNSUPPORTED -- compile `rev` with
+ * QMLE_PLAN_NO_FUSION instead. */
+int qmle_adjoint_cotangent(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
+                           int batch, const float *d_weights, const uint32_t *obs_wire_masks,
+                           const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                           const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
+                           const int32_t *mat_out, int n_mat, float *d_cot, void *d_ws, size_t ws_bytes,
+                           qmle_stream stream);
+size_t qmle_adjoint_cotangent_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                              int n_obs_terms, int n_obs);
+int qmle_adjoint_cotangent_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
+                               const double *d_angles_rev, int batch, const double *d_weights,
+                               const uint32_t *obs_wire_masks, const qmle_pauli_term *obs_terms, int n_obs_terms,
+                               int n_obs, const qmle_adjoint_term *terms, int n_terms, double *d_grad,
+                               int n_grad_slots, const int32_t *mat_out, int n_mat, double *d_cot, void *d_ws,
+                               size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                  int n_obs_terms, int n_obs);
+
 /* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
  * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:
  * d_out complex128, row-major [n_groups][rows_a][rows_b].  Row r of group g starts at amplitude

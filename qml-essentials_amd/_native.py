@@ -224,6 +224,12 @@ SYMBOLS = [
     ("qmle_adjoint_gradient_pauli_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(QmlePauliTerm), _I, _I, _VP,
                                              _I, _VP, _I, _VP, _SZ, _VP]),
     ("qmle_adjoint_pauli_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_cotangent", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm), _I, _I,
+                                    _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_adjoint_cotangent_workspace_bytes", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_cotangent_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm), _I,
+                                        _I, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_adjoint_cotangent_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I]),
     ("qmle_sample_counts", _I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _SZ,
                                 _VP]),
     ("qmle_sample_workspace_bytes", _SZ, [_I, _I]),
@@ -1415,6 +1421,18 @@ def _adjoint_term_array(terms):
     return arr
 
 
+def _wire_group_masks(wire_groups, n_qubits: int):
+    masks = (C.c_uint32 * max(1, len(wire_groups)))()
+    for k, grp in enumerate(wire_groups):
+        m = 0
+        for wq in grp:
+            if not 0 <= int(wq) < n_qubits:
+                raise ValueError(f"wire {wq} out of range for {n_qubits} qubits")
+            m |= 1 << int(wq)
+        masks[k] = m
+    return masks
+
+
 def _adjoint_gradient_pauli(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights, obs_terms, terms,
                             n_grad_slots: int):
     """The term-list form of :func:`adjoint_gradient` (rows already cut to the engine's limit)."""
@@ -1459,14 +1477,7 @@ def adjoint_gradient(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
     B, n_obs = int(weights.shape[0]), len(wire_groups)
     if weights.shape[1] != n_obs:
         raise ValueError(f"weights must be [B, {n_obs}], got {tuple(weights.shape)}")
-    masks = (C.c_uint32 * max(1, n_obs))()
-    for k, grp in enumerate(wire_groups):
-        m = 0
-        for wq in grp:
-            if not 0 <= int(wq) < fwd.n_qubits:
-                raise ValueError(f"wire {wq} out of range for {fwd.n_qubits} qubits")
-            m |= 1 << int(wq)
-        masks[k] = m
+    masks = _wire_group_masks(wire_groups, fwd.n_qubits)
     arr = _adjoint_term_array(terms)
     dev = weights.device
     if f64:
@@ -1487,3 +1498,47 @@ def adjoint_gradient(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
         C.c_void_p(out.data_ptr()), int(n_grad_slots), C.c_void_p(ws.data_ptr()),
         C.c_size_t(ws.numel()), _stream_ptr()), "qmle_adjoint_gradient")
     return out
+
+
+@_row_chunked(2, 3, 4, max_rows=32767)
+def adjoint_cotangent(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
+                      wire_groups: Optional[Sequence[Sequence[int]]], terms, n_grad_slots: int, mat_out, n_mat: int,
+                      obs_terms=None):
+    """:func:`adjoint_gradient` that also returns matrix cotangents (``qmle_adjoint_cotangent`` / ``_f64``):
+    ``mat_out[r]`` is, per op of ``rev``, the index of the 2x2 that reverse op r -- a one-wire matrix gate, ``MAT1`` or
+    ``MAT1_ROW`` -- reports, or -1.  -> ``(grad [B, n_grad_slots], G [B, n_mat, 2, 2] complex)`` with
+    ``G[b, k, a, c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` on the states in front of the gate, so that
+    ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  Seeds and precisions as for :func:`adjoint_gradient`; a
+    ``rev`` plan compiled for fused tile passes raises :class:`Unsupported` unless the sweep runs in LDS."""
+    torch = require_gpu()
+    f64 = weights.dtype == torch.float64
+    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
+        raise ValueError("the complex128 sweep takes float64 angle tables")
+    if (wire_groups is None) == (obs_terms is None):
+        raise ValueError("pass either wire_groups or obs_terms")
+    if weights.dim() != 2:
+        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
+    if len(mat_out) != len(terms) or n_mat < 1:
+        raise ValueError("mat_out holds one entry per reverse op, and at least one matrix is asked for")
+    B, n_obs = int(weights.shape[0]), int(weights.shape[1])
+    if wire_groups is not None and n_obs != len(wire_groups):
+        raise ValueError(f"weights must be [B, {len(wire_groups)}], got {tuple(weights.shape)}")
+    masks = _wire_group_masks(wire_groups, fwd.n_qubits) if wire_groups is not None else None
+    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
+    n_ot = len(obs_terms) if obs_terms is not None else 0
+    arr = _adjoint_term_array(terms)
+    marr = (C.c_int32 * len(mat_out))(*[int(m) for m in mat_out])
+    fn, wsq, what = ((lib().qmle_adjoint_cotangent_f64, lib().qmle_adjoint_cotangent_workspace_bytes_f64,
+                      "qmle_adjoint_cotangent_f64") if f64
+                     else (lib().qmle_adjoint_cotangent, lib().qmle_adjoint_cotangent_workspace_bytes,
+                           "qmle_adjoint_cotangent"))
+    dev = weights.device
+    ft = torch.float64 if f64 else torch.float32
+    out = torch.empty((B, n_grad_slots), dtype=ft, device=dev)
+    cot = torch.empty((B, int(n_mat), 2, 2, 2), dtype=ft, device=dev)
+    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, n_ot, n_obs))), dtype=torch.uint8, device=dev)
+    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
+             C.c_void_p(weights.data_ptr()), masks, oarr, n_ot, n_obs, arr, len(terms),
+             C.c_void_p(out.data_ptr()), int(n_grad_slots), marr, int(n_mat), C.c_void_p(cot.data_ptr()),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
+    return out, torch.view_as_complex(cot)

@@ -8,13 +8,18 @@ per gate one inverse-gate pass over [psi; lambda] and, per differentiable angle,
 ``Im <lambda| G |psi>`` -- O(gates + angles) passes instead of the 2 x angles full circuits of
 the parameter-shift rule.
 
+One-wire MATRIX gates (constant ``MAT1``, per-sample ``MAT1_ROW``) have no generator; for them the same sweep returns the
+matrix cotangent ``G[a][c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` on the state in front of the gate
+(:func:`adjoint_slot_and_matrix_gradient`), from which a caller that knows ``dU/dtheta`` -- the pulse front end: the
+solver's Jacobian -- forms ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  Two-wire matrices are refused.
+
 This module only prepares the REVERSED, DAGGERED tape and the generator table; the sweep itself
 runs in the engine.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -58,32 +63,74 @@ def _op_blobs(low: LoweredTape, x64: bool = False) -> List[Optional[np.ndarray]]
     return out
 
 
-def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Sequence[bool]):
+def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Sequence[bool],
+                  want_mat: Optional[Sequence[bool]] = None):
     """From the forward lowered tape: the reversed, daggered primitive tape (as ``_Lowered`` ops),
     its per-slot values (negated forward columns) and one generator term per reverse op.
 
     ``blobs[k]``: constant blob of forward op k (or None); ``want[s]``: forward slot s needs a
     derivative.  Rot(phi, theta, omega) = RZ(omega) RY(theta) RZ(phi) is split into its three
-    rotations so that every primitive has at most one angle."""
-    prims = []  # forward order: (name, wires, fwd_slot | None, blob)
-    for (name, wires, slots, _off), blob in zip(low.ops, blobs):
-        if name in ("MAT1_ROW", "MAT2_ROW"):
-            raise AdjointUnsupported(f"no adjoint rule for {name}: a per-sample matrix (an evolved unitary) has no "
-                                     "generator the sweep could differentiate or invert by negating an angle")
+    rotations so that every primitive has at most one angle.
+
+    -> ``(rev_ops, terms, rev_src)``: reverse slot j holds MINUS forward column ``rev_src[j]``.  That rule cannot
+    invert a per-sample matrix, so in this form a ``MAT1_ROW`` is refused (``CompiledCall`` keeps this form).
+
+    ``want_mat`` (one flag per forward op, True only on one-wire matrix gates ``MAT1`` / ``MAT1_ROW``) asks for the
+    form that serves matrix gates -> ``(rev_ops, terms, rev_src, rev_sign, mat_out)``: reverse slot j holds
+    ``rev_sign[j] *`` forward column ``rev_src[j]``.  The reverse of a ``MAT1_ROW`` is a ``MAT1_ROW`` on the daggered
+    columns -- entry (r, c, re) is the forward entry (c, r, re), sign +1; entry (r, c, im) the forward entry
+    (c, r, im), sign -1 -- and every angle keeps sign -1.  ``mat_out[r]``: per REVERSE op the index of the matrix
+    cotangent it reports (flagged forward ops numbered in tape order), or -1.  ``MAT2_ROW`` stays refused."""
+    with_mat = want_mat is not None
+    if with_mat and len(want_mat) != len(low.ops):
+        raise ValueError("want_mat holds one flag per forward op")
+    prims = []  # forward order: (name, wires, fwd_slot | None (MAT1_ROW: its 8 slots), blob, matrix index | -1)
+    n_mat = 0
+    for k, ((name, wires, slots, _off), blob) in enumerate(zip(low.ops, blobs)):
+        k_mat = -1
+        if with_mat and want_mat[k]:
+            if name not in ("MAT1", "MAT1_ROW"):
+                raise AdjointUnsupported(f"no matrix cotangent for {name}: the sweep reports them for one-wire matrix "
+                                         "gates only (two-wire matrices are not served)")
+            k_mat = n_mat
+            n_mat += 1
+        if name == "MAT2_ROW":
+            raise AdjointUnsupported("no adjoint rule for MAT2_ROW: the sweep inverts per-sample matrices on one wire "
+                                     "only; two-wire matrices (evolved two-wire unitaries) are not served")
+        if name == "MAT1_ROW":
+            if not with_mat:
+                raise AdjointUnsupported("no adjoint rule for MAT1_ROW in the angle-only form: a per-sample matrix is "
+                                         "not inverted by negating its columns (build_reverse(..., want_mat=...) "
+                                         "returns the sign vector that does it)")
+            prims.append((name, wires, list(slots), None, k_mat))
+            continue
         if name == "Rot":
-            prims += [("RZ", wires, slots[0], None), ("RY", wires, slots[1], None),
-                      ("RZ", wires, slots[2], None)]
+            prims += [("RZ", wires, slots[0], None, -1), ("RY", wires, slots[1], None, -1),
+                      ("RZ", wires, slots[2], None, -1)]
         elif len(slots) > 1:
             raise AdjointUnsupported(f"{name}: more than one angle per gate")
         else:
-            prims.append((name, wires, slots[0] if slots else None, blob))
-    rev_ops, rev_src, terms = [], [], []
-    for name, wires, fslot, blob in reversed(prims):
+            prims.append((name, wires, slots[0] if slots else None, blob, k_mat))
+    rev_ops, rev_src, rev_sign, terms, mat_out = [], [], [], [], []
+    for name, wires, fslot, blob, k_mat in reversed(prims):
         params, out_blob, term = [], None, _term()
         bit = lambda ws: sum(1 << int(w) for w in ws)  # noqa: E731
+        mat_out.append(k_mat)
+        if name == "MAT1_ROW":  # U^+: reverse column (r, c, part) <- forward column (c, r, part), imaginary parts negated
+            for r in range(2):
+                for c in range(2):
+                    for part, sign in ((0, 1.0), (1, -1.0)):
+                        src = fslot[(c * 2 + r) * 2 + part]
+                        params.append(sign * np.asarray(low.values[src], dtype=np.float64))
+                        rev_src.append(src)
+                        rev_sign.append(sign)
+            rev_ops.append(_Lowered((name, list(wires), params, None)))
+            terms.append(term)
+            continue
         if fslot is not None:
             params = [-np.asarray(low.values[fslot], dtype=np.float64)]
             rev_src.append(fslot)
+            rev_sign.append(-1.0)
         d = want[fslot] if fslot is not None else False
         if name in _ROT:
             ctrl, word = _ROT[name]
@@ -109,6 +156,8 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
             raise AdjointUnsupported(f"no adjoint rule for {name}")
         rev_ops.append(_Lowered((name, list(wires), params, out_blob)))
         terms.append(term)
+    if with_mat:
+        return rev_ops, terms, rev_src, rev_sign, mat_out
     return rev_ops, terms, rev_src
 
 
@@ -126,24 +175,75 @@ REV_FLAGS_FUSED = (N.PLAN_NO_MERGE | N.PLAN_FORCE_GLOBAL | N.PLAN_NO_ABSORB
                    | N.plan_flags(tile_bits=12, low_bits=4))
 
 
-def run_sweep(fwd_plan, rev: LoweredTape, a_f, a_r, w, obs_groups, terms, n_grad_slots, obs_terms=None):
+def run_sweep(fwd_plan, rev: LoweredTape, a_f, a_r, w, obs_groups, terms, n_grad_slots, obs_terms=None,
+              mat_out=None, n_mat=0):
     """The backward sweep with fused tile passes where the engine supports the tape (1-qubit and
     controlled 1-qubit gates), else with one streaming pass per gate.  float64 tables: the
     complex128 sweep (one streaming launch per operator, like the complex128 forward engine).
     The observables: Z-parity wire groups ``obs_groups``, or (``obs_groups`` None) the Pauli term list
-    ``obs_terms`` -- the same routes, another seed."""
+    ``obs_terms`` -- the same routes, another seed.  ``mat_out`` (per reverse op the index of the matrix cotangent
+    it reports, or -1; ``n_mat`` of them): -> ``(gradient, cotangents)`` from the same sweep; the fused tile passes
+    refuse such a request, so above 13 qubits it takes the streaming route."""
+    if mat_out is None:
+        call = lambda flags: N.adjoint_gradient(fwd_plan, get_plan(rev, flags), a_f, a_r, w, obs_groups, terms,  # noqa: E731
+                                                n_grad_slots, obs_terms=obs_terms)
+    else:
+        call = lambda flags: N.adjoint_cotangent(fwd_plan, get_plan(rev, flags), a_f, a_r, w, obs_groups, terms,  # noqa: E731
+                                                 n_grad_slots, mat_out, n_mat, obs_terms=obs_terms)
     if w.dtype == N.require_gpu().float64:
-        return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS), a_f, a_r, w, obs_groups, terms, n_grad_slots,
-                                  obs_terms=obs_terms)
+        return call(REV_FLAGS)
     try:
-        return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS_FUSED), a_f, a_r, w, obs_groups,
-                                  terms, n_grad_slots, obs_terms=obs_terms)
+        return call(REV_FLAGS_FUSED)
     except N.Unsupported:
-        return N.adjoint_gradient(fwd_plan, get_plan(rev, REV_FLAGS), a_f, a_r, w, obs_groups,
-                                  terms, n_grad_slots, obs_terms=obs_terms)
+        return call(REV_FLAGS)
+
+
+class RevTables(NamedTuple):
+    """What turns the forward angle table into the reverse one, and which reverse ops report a matrix cotangent."""
+    perm: object            # int64 CUDA tensor: reverse slot j reads forward column perm[j] ...
+    sign: object            # ... times sign[j] (float64 CUDA tensor): -1 for angles, +1 for real parts of matrices
+    mat_out: tuple          # per reverse op: index of its matrix cotangent, or -1
+    n_mat: int
 
 
 _REV_CACHE: "OrderedDict[tuple, tuple]" = OrderedDict()
+
+
+def _sweep(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights, want, want_mat, x64, obs_terms):
+    torch = N.require_gpu()
+    ft, fn = (torch.float64, np.float64) if x64 else (torch.float32, np.float32)
+    want_mat = tuple(bool(x) for x in want_mat) if want_mat is not None else (False,) * len(low.ops)
+    key = (low.key, tuple(bool(x) for x in want), bool(x64)) + ((want_mat,) if any(want_mat) else ())
+    hit = _REV_CACHE.get(key)
+    if hit is None:
+        rev_ops, terms, rev_src, rev_sign, mat_out = build_reverse(low, _op_blobs(low, x64), want, want_mat)
+        rev = LoweredTape(rev_ops, n_qubits)
+        hit = (rev, patch_marks(rev, terms),
+               RevTables(torch.tensor(rev_src if rev_src else [0], dtype=torch.int64, device="cuda"),
+                         torch.tensor(rev_sign if rev_sign else [-1.0], dtype=torch.float64, device="cuda"),
+                         tuple(mat_out), sum(want_mat)))
+        _REV_CACHE[key] = hit
+        if len(_REV_CACHE) > 64:
+            _REV_CACHE.popitem(last=False)
+    else:
+        _REV_CACHE.move_to_end(key)
+    rev, fixed, tab = hit
+    a_f = torch.from_numpy(low.angle_table(batch, dtype=np.float64) if x64 else low.angle_table(batch)).cuda()
+    rep = int(np.shape(weights)[0]) // max(1, batch)
+    if rep > 1:  # several cotangents per sample (a Jacobian: one row of weights per output) in ONE sweep
+        a_f = a_f.repeat(rep, 1)
+        batch = batch * rep
+    if rev.n_slots:
+        a_r = (a_f.index_select(1, tab.perm) * tab.sign.to(ft)).contiguous()
+    else:
+        a_r = torch.zeros((batch, 1), dtype=ft, device=a_f.device)
+    w = torch.from_numpy(np.ascontiguousarray(weights, dtype=fn)).cuda()
+    if not tab.n_mat:
+        return run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed, max(1, low.n_slots),
+                         obs_terms=obs_terms).cpu().numpy()[:, : low.n_slots], None
+    g, cot = run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed, max(1, low.n_slots), obs_terms=obs_terms,
+                       mat_out=list(tab.mat_out), n_mat=tab.n_mat)
+    return g.cpu().numpy()[:, : low.n_slots], cot.cpu().numpy()
 
 
 def adjoint_slot_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_groups,
@@ -153,32 +253,23 @@ def adjoint_slot_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_group
     the Z / Z-parity wire groups ``obs_groups`` or, with ``obs_groups`` None, the Pauli term list ``obs_terms``
     (columns of slots that are not wanted stay zero; ``weights`` of shape [K * B, n_obs] -- K cotangents per
     sample, sample-minor -- give [K * B, n_slots] from one sweep over K * B states).  The reversed tape depends only on the
-    STRUCTURE of the forward tape (its angles are the negated forward columns), so it is built
+    STRUCTURE of the forward tape (its angles are the forward columns, negated -- the real parts of a per-sample
+    one-wire matrix, whose columns are its entries, are not), so it is built
     once per structure.  ``x64``: float64 angle table, complex128 states, float64 gradients."""
-    torch = N.require_gpu()
-    ft, fn = (torch.float64, np.float64) if x64 else (torch.float32, np.float32)
-    key = (low.key, tuple(bool(x) for x in want), bool(x64))
-    hit = _REV_CACHE.get(key)
-    if hit is None:
-        rev_ops, terms, rev_src = build_reverse(low, _op_blobs(low, x64), want)
-        rev = LoweredTape(rev_ops, n_qubits)
-        hit = (rev, patch_marks(rev, terms),
-               torch.tensor(rev_src if rev_src else [0], dtype=torch.int64, device="cuda"))
-        _REV_CACHE[key] = hit
-        if len(_REV_CACHE) > 64:
-            _REV_CACHE.popitem(last=False)
-    else:
-        _REV_CACHE.move_to_end(key)
-    rev, fixed, perm = hit
-    a_f = torch.from_numpy(low.angle_table(batch, dtype=np.float64) if x64 else low.angle_table(batch)).cuda()
-    rep = int(np.shape(weights)[0]) // max(1, batch)
-    if rep > 1:  # several cotangents per sample (a Jacobian: one row of weights per output) in ONE sweep
-        a_f = a_f.repeat(rep, 1)
-        batch = batch * rep
-    if rev.n_slots:
-        a_r = (-a_f.index_select(1, perm)).contiguous()
-    else:
-        a_r = torch.zeros((batch, 1), dtype=ft, device=a_f.device)
-    w = torch.from_numpy(np.ascontiguousarray(weights, dtype=fn)).cuda()
-    return run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed,
-                     max(1, low.n_slots), obs_terms=obs_terms).cpu().numpy()[:, : low.n_slots]
+    return _sweep(low, n_qubits, batch, obs_groups, weights, want, None, x64, obs_terms)[0]
+
+
+def adjoint_slot_and_matrix_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights: np.ndarray,
+                                     want: Sequence[bool], want_mat: Sequence[bool], x64: bool = False,
+                                     obs_terms=None) -> Tuple[np.ndarray, np.ndarray]:
+    """:func:`adjoint_slot_gradient` that also returns the MATRIX COTANGENTS of the forward ops flagged in
+    ``want_mat`` (one flag per op of ``low.ops``; one-wire matrix gates only, constant ``MAT1`` or per-sample
+    ``MAT1_ROW``) -> ``(slot gradients [K * B, n_slots], G [K * B, n_mat, 2, 2] complex)``, the flagged ops numbered
+    in tape order, from ONE sweep.  With phi the state in front of the gate and lambda the seed with every later gate
+    undone, ``G[a][c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` over the other wires, so that for any
+    parameter of the gate's matrix ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  complex64, or complex128
+    with ``x64``.  Nothing flagged: ``G`` has shape ``[K * B, 0, 2, 2]``."""
+    g, cot = _sweep(low, n_qubits, batch, obs_groups, weights, want, want_mat, x64, obs_terms)
+    if cot is None:
+        cot = np.zeros((g.shape[0], 0, 2, 2), dtype=np.complex128 if x64 else np.complex64)
+    return g, cot

@@ -9,7 +9,8 @@ returns ``jnp`` arrays); the 2^n arithmetic runs in ``libqmle_sv`` via
 :class:`script.Script`.  ``gate_mode="pulse"`` records the ansatz (and the state preparation) through
 :mod:`pulses` and runs the recorded tape -- every pulse solve of it in one kernel launch; ``pulse_params`` are
 per-layer scalers of the optimised pulse parameters, shape ``(1, layers, n_pulse_params_per_layer)`` (a batch axis
-larger than 1 is not supported, nor is noise in pulse mode).  ``exact_spectrum`` (``:532-591``) asks
+larger than 1 is not supported, nor is noise in pulse mode); ``gradient(gate_mode="pulse", method="adjoint")``
+differentiates through the pulse solves, ``wrt="pulse_params"`` included.  ``exact_spectrum`` (``:532-591``) asks
 ``coefficients.FourierTree`` for the symbolic frequency support.  Out of scope: drawing.
 """
 from __future__ import annotations
@@ -648,9 +649,10 @@ class Model:
             params = p.reshape(B, *params.shape[1:])
         return inputs, params
 
-    def gradient(self, params=None, inputs=None, enc_params=None, wrt: str = "params",
+    def gradient(self, params=None, inputs=None, enc_params=None, wrt="params",
                  force_mean: bool = False, data_reupload=None,
-                 method: str = "parameter-shift", cotangent=None) -> np.ndarray:
+                 method: str = "parameter-shift", cotangent=None, pulse_params=None,
+                 gate_mode: str = "unitary") -> np.ndarray:
         """d<Z_q>/d``wrt`` for every output qubit by the parameter-shift rule
         (:meth:`script.Script.gradient`); ``wrt`` in {"params", "inputs", "enc_params"}.
 
@@ -668,6 +670,16 @@ class Model:
         i.e. the gradient of any cost whose derivative with respect to the outputs is
         ``cotangent``.  Same numbers as the parameter-shift rule at O(gates) instead of
         O(gates x angles) cost.
+
+        ``gate_mode="pulse"`` differentiates the pulse-level circuit (``pulse_params`` as in ``__call__``: one set
+        of scalers, default ``self.pulse_params``) and adds ``wrt="pulse_params"``; the gradient has the shape of
+        ``self.pulse_params`` behind the batch axes.  Pulse solves enter through the matrix cotangents of the
+        backward sweep and the solver's own Jacobian (:mod:`pulses`), so ``method`` must be ``"adjoint"`` or
+        ``"auto"`` (which then means adjoint); a pulse leaf has no shift rule and ``"parameter-shift"`` raises
+        ``NotImplementedError``.  ``wrt`` may be a tuple, e.g. ``("params", "pulse_params")``: a tuple of
+        gradients from ONE trace and ONE sweep.  ``Model(x64=True)`` / ``x64_scope`` take the complex128 sweep.
+        Not served in pulse mode: noise, a batch axis in ``pulse_params``, the torch bridge and the compiled
+        device path.
         """
         from .utils import x64_enabled, x64_scope
 
@@ -675,7 +687,29 @@ class Model:
             with x64_scope(self.x64):
                 return self.gradient(params=params, inputs=inputs, enc_params=enc_params, wrt=wrt,
                                      force_mean=force_mean, data_reupload=data_reupload,
-                                     method=method, cotangent=cotangent)
+                                     method=method, cotangent=cotangent, pulse_params=pulse_params,
+                                     gate_mode=gate_mode)
+        many = isinstance(wrt, (tuple, list))
+        wrts = tuple(wrt) if many else (wrt,)
+        pulse = gate_mode == "pulse"
+        if gate_mode not in ("unitary", "pulse"):
+            raise ValueError(f"gate_mode must be 'unitary' or 'pulse', got {gate_mode!r}")
+        if pulse_params is not None and not pulse:
+            raise ValueError("pulse_params were provided but gate_mode is not 'pulse'. "
+                             "Either switch gate_mode='pulse' or do not pass pulse_params.")
+        if pulse:
+            if method == "parameter-shift":
+                raise NotImplementedError(
+                    "gate_mode='pulse' has no parameter-shift gradient: a pulse leaf is the solution of a driven "
+                    "Schroedinger equation, not exp(-i theta G / 2), so it has no shift rule; use method='adjoint'")
+            if method == "auto":
+                method = "adjoint"
+            if self.noise_params is not None:
+                raise ValueError("noise_params were provided but gate_mode is 'pulse'. "
+                                 "Noise is not supported in pulse mode.")
+            if not self._pulse_capable:
+                raise NotImplementedError(f"{type(self.pqc).__name__} does not define n_pulse_params_per_layer: "
+                                          "gate_mode='pulse' is not available for it")
         if method == "auto":  # measured (profiles/r01_gradients.md): from 14 qubits the fused
             # backward sweep beats the batched parameter shift 5-40x; below, psi and lambda live
             # in LDS and the single-launch sweep wins once there is a batch to spread over the CUs
@@ -687,8 +721,18 @@ class Model:
                 f"method must be 'parameter-shift', 'adjoint' or 'auto', got {method!r}")
         if cotangent is not None and method != "adjoint":
             raise ValueError("cotangent needs method='adjoint'")
-        if wrt not in ("params", "inputs", "enc_params"):
-            raise ValueError(f"wrt must be 'params', 'inputs' or 'enc_params', got {wrt!r}")
+        for one in wrts:
+            if one == "pulse_params" and not pulse:
+                raise ValueError("wrt='pulse_params' needs gate_mode='pulse'")
+            if one not in ("params", "inputs", "enc_params", "pulse_params"):
+                raise ValueError(f"wrt must be 'params', 'inputs', 'enc_params' or 'pulse_params' (or a tuple of "
+                                 f"them), got {one!r}")
+        if not wrts or len(set(wrts)) != len(wrts):
+            raise ValueError(f"wrt names every argument once, got {wrt!r}")
+        if many and method != "adjoint":
+            raise ValueError("a tuple of wrt needs method='adjoint' (one trace, one backward sweep)")
+        if pulse:
+            pulse_params = np.asarray(self._pulse_params_validation(pulse_params), dtype=np.float64)
         if data_reupload is not None:  # call-time override, as in __call__ (model.py:1633-1634)
             self.data_reupload = data_reupload
         self.execution_type = "expval"
@@ -697,47 +741,51 @@ class Model:
         enc_params = self._enc_params_validation(enc_params)
         inputs, params = self._assimilate_batch(inputs, params)
         if self.remove_zero_encoding and self._zero_inputs and self.batch_shape[0] == 1 \
-                and wrt != "params":
+                and any(one in ("inputs", "enc_params") for one in wrts):
             raise ValueError("inputs are all zero and remove_zero_encoding=True: the encoding "
                              "gates are not on the tape; pass remove_zero_encoding=False")
         _, obs = self._build_obs()
         B = int(np.prod(self.eff_batch_shape))
-        args = (params, inputs, None, None, np.asarray(enc_params, dtype=np.float64))
+        args = (params, inputs, pulse_params if pulse else None, None, np.asarray(enc_params, dtype=np.float64))
         in_axes = (0 if self.batch_shape[1] > 1 else None, 0 if self.batch_shape[0] > 1 else None,
                    None, None, None)
-        argnum = {"params": 0, "inputs": 1, "enc_params": 4}[wrt]
-        kwargs = dict(noise_params=self.noise_params, gate_mode="unitary")
+        argnums = tuple({"params": 0, "inputs": 1, "pulse_params": 2, "enc_params": 4}[one] for one in wrts)
+        argnum = argnums[0]
+        kwargs = dict(noise_params=self.noise_params, gate_mode=gate_mode)
         if method == "adjoint":  # (x64 mode: Script.vjp runs the complex128 sweep, qmle_adjoint_gradient_f64)
             n_out = len(obs)
             ax = in_axes if B > 1 else None
             if cotangent is not None or force_mean:
                 w = (np.full((B, n_out), 1.0 / n_out) if cotangent is None
                      else np.asarray(cotangent, dtype=np.float64).reshape(B, n_out))
-                (g,) = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax,
-                                       argnums=(argnum,))
-                jac = (g if B > 1 else g[None])[:, None]       # (B, 1, *leaf)
+                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums)
+                jacs = [(g if B > 1 else g[None])[:, None] for g in gs]  # (B, 1, *leaf)
                 force_mean = True                              # the output axis is already reduced
             else:
                 # the Jacobian: one one-hot cotangent per output, all of them in ONE trace and ONE sweep over
                 # n_out * B states (round 5; before: n_out calls, each re-recording the tape)
                 w = np.zeros((n_out, B, n_out))
                 w[np.arange(n_out), :, np.arange(n_out)] = 1.0
-                (g,) = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=(argnum,))
-                jac = np.moveaxis(g if B > 1 else g[:, None], 0, 1)   # (B, n_out, *leaf)
+                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums)
+                jacs = [np.moveaxis(g if B > 1 else g[:, None], 0, 1) for g in gs]   # (B, n_out, *leaf)
         else:
             (jac,) = self.script.gradient(obs, args=args, kwargs=kwargs,
                                           in_axes=in_axes if B > 1 else None, argnums=(argnum,))
             if B == 1:
                 jac = jac[None]
-        leaf = jac.shape[2:]
-        if wrt in ("params", "inputs") and in_axes[argnum] is None and leaf and leaf[0] == 1:
-            jac = jac.reshape(jac.shape[:2] + leaf[1:])  # drop the dummy batch axis of the arg
-        jac = jac.reshape(*self.eff_batch_shape, *jac.shape[1:])
-        jac = jac.reshape([d for i, d in enumerate(jac.shape)
-                           if not (i < len(self.eff_batch_shape) and d == 1)])
-        if force_mean:
-            jac = jac.mean(axis=len([d for d in self.eff_batch_shape if d != 1]))
-        return jac
+            jacs = [jac]
+        out = []
+        for one, num, jac in zip(wrts, argnums, jacs):
+            leaf = jac.shape[2:]
+            if one in ("params", "inputs") and in_axes[num] is None and leaf and leaf[0] == 1:
+                jac = jac.reshape(jac.shape[:2] + leaf[1:])  # drop the dummy batch axis of the arg
+            jac = jac.reshape(*self.eff_batch_shape, *jac.shape[1:])
+            jac = jac.reshape([d for i, d in enumerate(jac.shape)
+                               if not (i < len(self.eff_batch_shape) and d == 1)])
+            if force_mean:
+                jac = jac.mean(axis=len([d for d in self.eff_batch_shape if d != 1]))
+            out.append(jac)
+        return tuple(out) if many else out[0]
 
     def quantum_geometric_tensor(self, params=None, inputs=None, enc_params=None,
                                  row_block=None) -> np.ndarray:

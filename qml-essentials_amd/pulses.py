@@ -29,11 +29,17 @@ Its optimised default parameters are tuned to exactly this definition, which is 
 The support rule.  ``square`` and ``cosine`` vanish identically for ``t > width``; the grid covers ``[0, min(T,
 width)]`` for them (``[0, T]`` otherwise), so that neither the jump nor the kink falls inside a step.
 
-Gradients are not carried through the solver by ``Script.gradient`` / ``vjp`` / ``Model``: a request whose arguments
-depend on a differentiated leaf has "derivative unknown" and ``Script.gradient`` refuses it, as for ``evolve()``.
-:func:`solve_with_jacobian` returns the solves together with their exact grid sensitivities; :mod:`qoc` composes
-them into the gradients of its cost functions.  Out of scope: pulse-event tapes / ``draw_pulse``,
-``PulseInformation.update_params`` from CSV, ``PauliRot``.
+Gradients.  ``Script.vjp`` and ``Model.gradient(gate_mode="pulse", method="adjoint")`` differentiate through a pulse
+solve: a request whose arguments depend on a differentiated leaf reports itself as a MATRIX-COTANGENT op
+(:attr:`PulseRotation.wants_matrix_cotangent`), :func:`resolve_for_gradient` fills ``U`` and keeps the exact grid
+sensitivities ``J = dU/d(p0, p1, p2, w, T)`` of all such requests of a tape from one :func:`solve_with_jacobian` call
+per launch group, the backward sweep returns ``G`` with ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``
+(:func:`adjoint.adjoint_slot_and_matrix_gradient`), and :meth:`PulseRotation.leaf_jacobian_terms` is the chain rule
+onto the leaves.  The virtual ``RZ`` and the ``ControlledPhaseShift`` of ``CZ`` are ordinary angle slots of the same
+sweep.  Everywhere else -- ``Script.gradient`` (parameter shift: a pulse leaf has no shift rule), the quantum
+geometric tensor, the compiled device path, the torch bridge -- such a request still has "derivative unknown" and is
+refused, as for ``evolve()``.  :mod:`qoc` composes the same sensitivities into the gradients of its cost functions.
+Out of scope: pulse-event tapes / ``draw_pulse``, ``PulseInformation.update_params`` from CSV, ``PauliRot``.
 """
 from __future__ import annotations
 
@@ -501,10 +507,13 @@ class PulseRotation(Operation):
         self.omega_c, self.omega_q = float(PulseGates.omega_c), float(PulseGates.omega_q)
         self.env_params = [as_param(v) for v in values[:n_env]]
         self.T, self.w = as_param(values[n_env]), as_param(values[n_env + 1])
+        # (None = "derivative unknown" for every consumer that differentiates angles only: parameter shift, the
+        # quantum geometric tensor, compiled calls; ``Script.vjp`` reads ``wants_matrix_cotangent`` instead)
         self._matrix_tangent = _tangent_state(values)
-        # per argument (envelope parameters..., T, w): the leaf elements it depends on -- what ``qoc`` maps the
-        # columns of the solve's Jacobian onto; ``Script.gradient`` does not read it
+        # per argument (envelope parameters..., T, w): the leaf elements it depends on -- what ``qoc`` and
+        # ``Script.vjp`` map the columns of the solve's Jacobian onto
         self._arg_tangents = [param_tangent(v) for v in values]
+        self._jacobian = None  # [rows, 5, 2, 2] complex128 once resolve_for_gradient solved the request
         self.evolve_steps = None
         super().__init__(wires=wires, record=record, name="R" + axis)
 
@@ -535,12 +544,32 @@ class PulseRotation(Operation):
         t[:, 3], t[:, 4], t[:, 5] = self.w, self.T, 0.0 if self.axis == "X" else 1.0
         return t
 
-    def jacobian_terms(self) -> list:
-        """``[(slot, index, coef)]``: the solve's derivative in kernel slot ``slot``, times ``coef`` ``[C]``, adds to
-        the derivative by leaf element ``index`` -- argument by argument (envelope parameters, ``T``, ``w``)."""
+    @property
+    def wants_matrix_cotangent(self) -> bool:
+        """True when an argument depends on a differentiated leaf: the gradient of a cost by that leaf goes through
+        the matrix cotangent of this gate and :meth:`leaf_jacobian_terms` (also when the recorder lost track of
+        the dependence -- the chain rule then raises)."""
+        return self._matrix_tangent is None
+
+    def leaf_jacobian_terms(self) -> list:
+        """``[(leaf, slot, index, coef)]``: the solve's derivative in kernel slot ``slot``, times ``coef`` ``[C]``,
+        adds to the derivative by element ``index`` of leaf ``leaf`` -- argument by argument (envelope parameters,
+        ``T``, ``w``)."""
         slots = list(range(len(self.env_params))) + [_SLOT_T, _SLOT_W]
-        return [(slot, index, coef) for slot, terms in zip(slots, self._arg_tangents)
-                for _, index, coef in _tracked_terms(terms, f"an argument of {self!r}")]
+        return [(leaf, slot, index, coef) for slot, terms in zip(slots, self._arg_tangents)
+                for leaf, index, coef in _tracked_terms(terms, f"an argument of {self!r}")]
+
+    def jacobian_terms(self) -> list:
+        """:meth:`leaf_jacobian_terms` without the leaf (``qoc``: one leaf) -> ``[(slot, index, coef)]``."""
+        return [(slot, index, coef) for _leaf, slot, index, coef in self.leaf_jacobian_terms()]
+
+    @property
+    def jacobian(self) -> np.ndarray:
+        """``[rows, 5, 2, 2]`` complex128: ``dU/d(p0, p1, p2, w, T)`` per solve, kept by
+        :func:`resolve_for_gradient`."""
+        if self._jacobian is None:
+            resolve_for_gradient([self])
+        return self._jacobian
 
     def _resolved(self) -> None:
         if self._matrix is None:
@@ -650,6 +679,42 @@ def resolve(tape: Sequence[Operation]) -> int:
         U, steps = _launch_all(np.concatenate(blocks), envelope, mode, omega_c, omega_q)
         for o, (lo, hi) in zip(ops, where):
             o._matrix = U[lo].copy() if hi is None else U[lo:hi].copy()
+            o.evolve_steps = steps
+        total += n
+    return total
+
+
+def resolve_for_gradient(tape: Sequence[Operation]) -> int:
+    """The gradient-time :func:`resolve`: every :class:`PulseRotation` of ``tape`` that wants a matrix cotangent and
+    has no Jacobian yet is solved WITH its sensitivities -- all of them in one :func:`solve_with_jacobian` call per
+    launch group (under an adaptive solver name: the step doubling, then one sensitivity launch on the accepted
+    grid) -- and keeps ``U`` ``[rows, 2, 2]`` and ``J`` ``[rows, 5, 2, 2]``.  A request whose rows are all the same
+    (a leaf shared by the whole batch) is solved once.  Requests without leaf dependence are left to
+    :func:`resolve`.  Returns the number of solves."""
+    pending = []
+    for o in tape:
+        if isinstance(o, PulseRotation) and o.wants_matrix_cotangent and o._jacobian is None \
+                and not any(o is seen for seen in pending):
+            pending.append(o)
+    groups: Dict[tuple, list] = {}
+    for o in pending:
+        groups.setdefault(o.group(), []).append(o)
+    total = 0
+    for (envelope, mode, omega_c, omega_q), ops in groups.items():
+        blocks, where, n = [], [], 0
+        for o in ops:
+            t = o.solves()
+            rows = t.shape[0]
+            if rows > 1 and not (t != t[:1]).any():
+                t = t[:1]
+            where.append((n, n + t.shape[0], rows))
+            blocks.append(t)
+            n += t.shape[0]
+        U, J, steps = solve_with_jacobian(np.concatenate(blocks), envelope, mode, omega_c, omega_q)
+        for o, (lo, hi, rows) in zip(ops, where):
+            rep_ = rows if hi - lo == 1 and rows > 1 else 1
+            o._matrix = np.repeat(U[lo:hi], rep_, axis=0)
+            o._jacobian = np.repeat(J[lo:hi], rep_, axis=0)
             o.evolve_steps = steps
         total += n
     return total

@@ -37,8 +37,9 @@ per-gate entry points default to ``"host"``; the joint path (:func:`joint_unitar
 one shared leaf vector against the weighted unitary costs of several target gates) defaults to ``"device"`` with the
 default solver and evaluates all its gates with one solver call and one composition launch.
 
-Not included: plots, the command line, ``profile_pulse_pipeline``; derivatives inside ``Script.gradient`` / ``vjp`` /
-``Model``.
+Not included: plots, the command line, ``profile_pulse_pipeline``.  (Gradients of a CIRCUIT's expectation values by
+pulse parameters are not this module's: ``Script.vjp`` / ``Model.gradient(gate_mode="pulse")`` serve them from the
+backward sweep's matrix cotangents and the same solver Jacobian, :mod:`pulses`.)
 """
 from __future__ import annotations
 

@@ -228,7 +228,10 @@ class CompiledCall:
         return m
 
     def _adjoint_setup(self):
-        """Reverse tape, generator terms and the chain-rule matrices -- built once."""
+        """Reverse tape, generator terms and the chain-rule matrices -- built once.  The compiled path keeps the
+        angle-only form of ``adjoint.build_reverse`` (every reverse column is minus a forward column), which refuses
+        per-sample matrices: a tape with a ``MAT1_ROW`` raises ``AdjointUnsupported`` here, and pulse leaves that
+        depend on an argument do not compile in the first place."""
         import torch
 
         from . import adjoint
@@ -440,12 +443,17 @@ class Script:
                  (-3 * np.pi / 2, (np.sqrt(2) - 1) / (4 * np.sqrt(2)))),
     }
 
-    def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums, skip_channels: bool = False):
+    def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums, skip_channels: bool = False,
+                            mat_ops: Optional[list] = None):
         """Record the tape with the ``argnums`` arguments as differentiable leaves.  Returns
         ``(tape, lowered tape, n_qubits, B, slots, leaf_shapes, batched)`` where ``slots`` lists
         ``(angle slot, shift rule, tangent terms)`` for every angle that depends on a leaf.
         ``skip_channels``: noise channels stay on the returned tape but take no part in the lowered
-        tape and the slot numbering (the mixed-state QFI)."""
+        tape and the slot numbering (the mixed-state QFI).
+        ``mat_ops``: a list that receives ``(index in the lowered tape's ops, operation)`` for every matrix gate
+        whose matrix depends on a leaf through a known Jacobian (pulse leaves: ``wants_matrix_cotangent``); such a
+        gate is then solved with its sensitivities here and does not count as "non-linear".  Only a caller that
+        asks the sweep for matrix cotangents passes it (:meth:`vjp`)."""
         kwargs = {} if kwargs is None else kwargs
         args = tuple(to_numpy(a) for a in args)
         batched = in_axes is not None
@@ -474,13 +482,20 @@ class Script:
         tape = self._record_for_engine(*wrapped, **kwargs)
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         gates = [o for o in tape if not isinstance(o, KrausChannel)] if skip_channels else tape
+        if mat_ops is not None:  # U and dU/d(arguments) of every pulse leaf that depends on a leaf: one launch group
+            pulses.resolve_for_gradient(gates)
         low = simulation.LoweredTape(gates, n_qubits)
 
         # differentiable slots: (slot, rule, tangent terms)
-        slots, s = [], 0
+        slots, s, k_op = [], 0, -1
         for op_ in gates:
             lowered = op_.lower(n_qubits)
             if lowered is None:
+                continue
+            k_op += 1
+            if mat_ops is not None and getattr(op_, "wants_matrix_cotangent", False):
+                mat_ops.append((k_op, op_))  # (its lowered parameters are matrix entries, not angles)
+                s += len(lowered[2])
                 continue
             tans = op_.parameter_tangents
             for j in range(len(lowered[2])):  # one angle slot per lowered parameter
@@ -510,7 +525,14 @@ class Script:
         ``(B, n_obs)`` (``(n_obs,)`` without ``in_axes``).  Returns one array per ``argnums``
         entry of shape ``(B, *arg_shape)`` (no ``B`` axis without ``in_axes``).  A ``cotangent`` with a
         leading axis of K cotangents, ``(K, B, n_obs)``, is served by one trace and one sweep over K * B
-        states and returns ``(K, B, *arg_shape)`` (a Jacobian: K = n_obs one-hot rows)."""
+        states and returns ``(K, B, *arg_shape)`` (a Jacobian: K = n_obs one-hot rows).
+
+        Pulse leaves (:class:`pulses.PulseRotation`) whose arguments depend on a leaf are differentiated too: they
+        are solved with their sensitivities (``pulses.resolve_for_gradient``), the same sweep returns their matrix
+        cotangents ``G`` beside the angle gradients, and ``2 Re sum_ac G[a][c] J[slot][a][c] coef`` is added for every
+        ``(leaf, slot, index, coef)`` of ``leaf_jacobian_terms()``.  An argument the recorder lost track of raises
+        ``NotImplementedError``; an evolved gate (a per-sample matrix that is no pulse leaf) on the tape raises
+        ``AdjointUnsupported``, as before."""
         from . import adjoint
 
         if not obs:
@@ -521,10 +543,20 @@ class Script:
             raise adjoint.AdjointUnsupported(
                 "adjoint differentiation needs Z / Z-parity observables; pauli_seed=True seeds the sweep with "
                 "H psi for sums of Pauli words (got " + ", ".join(kinds) + ")")
+        mat_ops: list = []
         tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
-            obs, args, kwargs, in_axes, argnums)
+            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops)
         if any(isinstance(o, KrausChannel) for o in tape):
             raise adjoint.AdjointUnsupported("adjoint differentiation of noisy circuits")
+        for o in tape:  # evolved gates stay out of scope here: the sweep could invert one, nothing differentiates it
+            m = getattr(o, "_matrix", None)
+            if not isinstance(o, pulses.PulseRotation) and getattr(o, "_native", None) is None \
+                    and isinstance(m, np.ndarray) and m.ndim == 3:
+                raise adjoint.AdjointUnsupported(
+                    f"no adjoint rule for {o.name} (MAT1_ROW / MAT2_ROW): a per-sample matrix that is not a pulse "
+                    "leaf (an evolved unitary) has no generator and no Jacobian the sweep could differentiate")
+        # the chain rule of every pulse leaf, before any device work (an argument the recorder lost track of raises)
+        mat_terms = [o.leaf_jacobian_terms() for _k, o in mat_ops]
         obs_terms = None
         if any(m is None for m in masks) or len(obs) > 32:  # not the Z seed: the observables as weighted Pauli words
             masks, obs_terms = None, simulation.pauli_term_list(obs, n_qubits)
@@ -545,9 +577,24 @@ class Script:
         for s_, _rule, _t, _name in slots:
             want[s_] = True
         grads = {k: np.zeros((K, B) + tuple(shp)) for k, shp in leaf_shapes.items()}
-        if slots:
+        if mat_ops:  # angle slots and matrix cotangents from ONE sweep
+            want_mat = [False] * len(low.ops)
+            for k_op, _o in mat_ops:
+                want_mat[k_op] = True
+            d, cot = adjoint.adjoint_slot_and_matrix_gradient(low, n_qubits, B, masks, w, want, want_mat, x64=x64,
+                                                              obs_terms=obs_terms)  # [K * B, n_mat, 2, 2]
+            cot = np.asarray(cot, dtype=np.complex128).reshape(K, B, len(mat_ops), 4)
+            for m, ((_k, o), terms) in enumerate(zip(mat_ops, mat_terms)):
+                jac = np.asarray(o.jacobian, dtype=np.complex128).reshape(-1, 5, 4)  # [B or 1, 5, 4]
+                # dC/d(slot) = 2 Re sum_ac G[a][c] dU[a][c]/d(slot)  -> [K, B, 5]
+                per_slot = 2.0 * np.real(np.einsum("kbe,bse->kbs", cot[:, :, m], np.broadcast_to(jac, (B, 5, 4))))
+                for lid, slot, flat, coef in terms:
+                    g = grads[lid].reshape(K, B, -1)
+                    g[:, :, int(flat)] += per_slot[:, :, slot] * np.asarray(coef, dtype=np.float64).reshape(1, -1)
+        elif slots:
             d = adjoint.adjoint_slot_gradient(low, n_qubits, B, masks, w, want, x64=x64,
                                               obs_terms=obs_terms)  # [K * B, n_slots]
+        if slots:
             d = d.reshape(K, B, -1)
             for s_, _rule, tangent, _name in slots:
                 for lid, flat, coef in tangent:  # gate angles are scalars: one leaf element each
