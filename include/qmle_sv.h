@@ -632,7 +632,11 @@ size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_p
  * n_obs_terms = 0 for the Z seed); a smaller one is QMLE_ERR_INVALID_ARG.  Routes: the whole sweep in LDS (n <= 13)
  * and one streaming pass per gate serve the request; a `rev` plan compiled for fused tile passes
  * (QMLE_PLAN_NO_MERGE) that does not fit LDS returns QMLE_ERR_UNSUPPORTED -- compile `rev` with
- * QMLE_PLAN_NO_FUSION instead. */
+ * QMLE_PLAN_NO_FUSION instead.
+ * These two are wrappers of qmle_adjoint_cotangent_at / _f64 below with offsets 8 * index.  NULL and shape errors are
+ * QMLE_ERR_INVALID_ARG as before; the codes for mat_out (QMLE_ERR_SLOT_RANGE, QMLE_ERR_UNSUPPORTED) are now decided
+ * before the workspace size is looked at; two flagged ops that share one index, which used to overwrite each other,
+ * are QMLE_ERR_SLOT_RANGE (overlapping blocks). */
 int qmle_adjoint_cotangent(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
                            int batch, const float *d_weights, const uint32_t *obs_wire_masks,
                            const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
@@ -649,6 +653,40 @@ int qmle_adjoint_cotangent_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_a
                                size_t ws_bytes, qmle_stream stream);
 size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                                   int n_obs_terms, int n_obs);
+
+/* Matrix cotangents of one- AND two-wire matrix gates (QMLE_OP_MAT1 / MAT1_ROW / MAT2 / MAT2_ROW) from the same
+ * sweep; the two functions above are thin wrappers of these with offsets 8 * index.  For a gate on wires (w0, w1),
+ * in the index convention of its own matrix (row = 2 * value of w0 + value of w1),
+ *   M[a][c] = sum_rest conj(lambda[a, rest]) psi[c, rest]   behind the gate,     G = M (U^+)^T,
+ *   dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta   with U as the caller passed it: 16 complex numbers from one
+ * read of psi and lambda.
+ *   cot_off[r]  HOST array, one entry per op of `rev`: offset, in scalars, of reverse op r's block inside a sample's
+ *               row of cot_stride scalars, or -1.  A block is 8 scalars ([2][2][re, im]) for a one-wire matrix gate
+ *               and 32 ([4][4][re, im]) for a two-wire one.  A block that ends outside the row or overlaps another:
+ *               QMLE_ERR_SLOT_RANGE; >= 0 on anything but the four matrix opcodes: QMLE_ERR_UNSUPPORTED; on an op
+ *               that was merged into a neighbour or carries a control: QMLE_ERR_INVALID_ARG.  All of this is
+ *               checked before any device work.
+ *   d_cot       [batch][cot_stride], float / double, zeroed by the call.
+ * The workspace queries take `two_wire` != 0 when a two-wire block is requested (16 complex partial sums per block
+ * of the streaming route instead of 4).  Routes: the LDS launch (n <= 13) takes the 4x4 moment one row at a time;
+ * the streaming route runs one moment kernel over float2 / double2 amplitudes and one finishing kernel; fused tile
+ * passes return QMLE_ERR_UNSUPPORTED as above. */
+int qmle_adjoint_cotangent_at(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
+                              int batch, const float *d_weights, const uint32_t *obs_wire_masks,
+                              const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                              const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
+                              const int32_t *cot_off, int cot_stride, float *d_cot, void *d_ws, size_t ws_bytes,
+                              qmle_stream stream);
+size_t qmle_adjoint_cotangent_at_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                 int n_obs_terms, int n_obs, int two_wire);
+int qmle_adjoint_cotangent_at_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
+                                  const double *d_angles_rev, int batch, const double *d_weights,
+                                  const uint32_t *obs_wire_masks, const qmle_pauli_term *obs_terms, int n_obs_terms,
+                                  int n_obs, const qmle_adjoint_term *terms, int n_terms, double *d_grad,
+                                  int n_grad_slots, const int32_t *cot_off, int cot_stride, double *d_cot, void *d_ws,
+                                  size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_cotangent_at_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                     int n_obs_terms, int n_obs, int two_wire);
 
 /* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
  * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:
@@ -696,6 +734,26 @@ size_t qmle_gram_workspace_bytes_f64(int n_qubits, int n_groups, int rows_a, int
 int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double *d_coef, const double *d_h, int rows,
                        int order, int n_steps, int lanes_per_row, int out_f64, void *d_out, qmle_stream stream);
 int qmle_evolve_lanes(int rows, int n_steps);
+
+/* The same solve with the EXACT derivative of the fixed grid's result in n_dirs (1..64) directions: the scheme is
+ * discretised, then differentiated -- neither a finite difference nor a second ODE.  The first arguments are those of
+ * qmle_evolve_magnus.  d_dcoef: float64 [rows][n_dirs][n_steps * nodes per step][n_terms], the derivative of the
+ * coefficient table in direction k (where a node moves with the direction -- a derivative by an end of the interval --
+ * the caller adds f'(t_j) dt_j here: the library evaluates no function).  d_dh: float64 [rows][n_dirs], the derivative
+ * of the step.  d_out: complex128 [rows][1 + n_dirs][dim * dim]: slot 0 is U, slot 1 + k its derivative in direction
+ * k.  Per exponential factor Omega = h sum_j a_j A(t_j):  dOmega = dh sum_j a_j A(t_j) + h sum_j a_j dA(t_j),
+ * U <- E U, dU <- dE U + E dU; dim = 2 in closed form, dim = 4 by the column series with its derivative term by term
+ * (the same cut and term count, taken from Omega).  One (row, direction) is one unit of work that recomputes U, so
+ * slot 1 + k does not depend on which other directions share the call (bit for bit, at equal lanes_per_row).
+ * lanes_per_row as above; at dim = 4 a run of steps takes four lanes (one per column of U), so 64 is refused and
+ * 0 never chooses it; 0 chooses qmle_evolve_lanes(rows * n_dirs, n_steps) within that.
+ * A row whose norm check fails or whose exponent is not finite comes back NaN in every slot; a direction whose
+ * dOmega is not finite comes back NaN in its own slot.
+ * The status codes of qmle_evolve_magnus; QMLE_ERR_INVALID_ARG also for NULL d_dcoef / d_dh, n_dirs outside 1..64
+ * and rows * n_dirs * lanes beyond 2^31 -- all before any device work. */
+int qmle_evolve_magnus_jac(const double *h_terms, int n_terms, int dim, const double *d_coef, const double *d_h,
+                           const double *d_dcoef, const double *d_dh, int rows, int n_dirs, int order, int n_steps,
+                           int lanes_per_row, void *d_out, qmle_stream stream);
 
 /* ---- pulse-level gates (pulses.PulseGates.RX / RY): every pulse solve of a tape in one launch -----------------------
  * U[s] of dU/dt = -i (cx(t) X + cy(t) Y) U on [0, S], U(0) = I, for n_solves independent 2x2 solves on the fixed

@@ -230,6 +230,12 @@ SYMBOLS = [
     ("qmle_adjoint_cotangent_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm), _I,
                                         _I, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
     ("qmle_adjoint_cotangent_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_cotangent_at", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm), _I,
+                                       _I, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_adjoint_cotangent_at_workspace_bytes", _SZ, [_VP, _VP, _I, _I, _I, _I]),
+    ("qmle_adjoint_cotangent_at_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm),
+                                           _I, _I, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_adjoint_cotangent_at_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I, _I]),
     ("qmle_sample_counts", _I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _SZ,
                                 _VP]),
     ("qmle_sample_workspace_bytes", _SZ, [_I, _I]),
@@ -242,6 +248,7 @@ SYMBOLS = [
     ("qmle_gram_workspace_bytes_f64", _SZ, [_I, _I, _I, _I]),
     ("qmle_evolve_magnus", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     ("qmle_evolve_lanes", _I, [_I, _I]),
+    ("qmle_evolve_magnus_jac", _I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     ("qmle_pulse_unitaries", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     ("qmle_pulse_unitaries_jac", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _VP, _VP]),
     ("qmle_compose_circuits", _I, [_VP, _I, _VP, _I, _VP, _I, _VP, C.c_int64, _I, _VP, C.c_int64, _VP, C.c_int64, _VP,
@@ -1001,6 +1008,40 @@ def evolve_magnus(h_terms, coef, h, order: int, lanes_per_row: int = 0, complex6
     return out
 
 
+EVOLVE_MAX_DIRS = 64  # qmle_evolve_magnus_jac: directions per call
+
+
+def evolve_magnus_jac(h_terms, coef, h, dcoef, dh, order: int, lanes_per_row: int = 0):
+    """:func:`evolve_magnus` with the exact derivative of the grid's result in ``n_dirs`` directions
+    (``qmle_evolve_magnus_jac``): ``dcoef`` ``[rows, n_dirs, nodes, n_terms]`` float64, the derivative of the
+    coefficient table, and ``dh`` ``[rows, n_dirs]``, that of the step.  Returns ``[rows, 1 + n_dirs, d, d]``
+    complex128 on the device: slot 0 is ``U``, slot ``1 + k`` its derivative in direction ``k``."""
+    torch = require_gpu()
+    H = np.ascontiguousarray(h_terms, dtype=np.complex128)
+    if H.ndim != 3 or H.shape[1] != H.shape[2]:
+        raise ValueError(f"evolve_magnus_jac: terms must be [n_terms, d, d], got {H.shape}")
+    dev = current_device()
+    coef, h = _device_tensor(coef, torch.float64), _device_tensor(h, torch.float64)
+    dcoef, dh = _device_tensor(dcoef, torch.float64), _device_tensor(dh, torch.float64)
+    n_terms, d = int(H.shape[0]), int(H.shape[1])
+    per_step = 2 if order == 4 else 1
+    if coef.dim() != 3 or coef.shape[2] != n_terms or coef.shape[1] % per_step or h.shape != (coef.shape[0],):
+        raise ValueError(f"evolve_magnus_jac: coef {tuple(coef.shape)} / h {tuple(h.shape)} do not fit {n_terms} "
+                         f"term(s) of order {order}")
+    rows, n_steps = int(coef.shape[0]), int(coef.shape[1]) // per_step
+    if dh.dim() != 2 or dh.shape[0] != rows or tuple(dcoef.shape) != (rows, dh.shape[1]) + tuple(coef.shape[1:]):
+        raise ValueError(f"evolve_magnus_jac: dcoef {tuple(dcoef.shape)} / dh {tuple(dh.shape)} do not fit coef "
+                         f"{tuple(coef.shape)}")
+    n_dirs = int(dh.shape[1])
+    out = torch.empty((rows, 1 + n_dirs, d, d), dtype=torch.complex128, device=dev)
+    check(lib().qmle_evolve_magnus_jac(C.c_void_p(H.ctypes.data), n_terms, d, C.c_void_p(coef.data_ptr()),
+                                       C.c_void_p(h.data_ptr()), C.c_void_p(dcoef.data_ptr()),
+                                       C.c_void_p(dh.data_ptr()), rows, n_dirs, int(order), n_steps,
+                                       int(lanes_per_row), C.c_void_p(out.data_ptr()), _stream_ptr()),
+          "qmle_evolve_magnus_jac")
+    return out
+
+
 PULSE_ENVELOPES = ("gaussian", "square", "cosine", "drag", "sech")  # envelope ids of qmle_pulse_unitaries
 PULSE_MODES = ("rwa", "lab", "drive")
 
@@ -1542,3 +1583,48 @@ def adjoint_cotangent(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
              C.c_void_p(out.data_ptr()), int(n_grad_slots), marr, int(n_mat), C.c_void_p(cot.data_ptr()),
              C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
     return out, torch.view_as_complex(cot)
+
+
+@_row_chunked(2, 3, 4, max_rows=32767)
+def adjoint_cotangent_at(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
+                         wire_groups: Optional[Sequence[Sequence[int]]], terms, n_grad_slots: int, cot_off,
+                         cot_stride: int, two_wire: bool, obs_terms=None):
+    """:func:`adjoint_cotangent` for one- and two-wire matrix gates (``qmle_adjoint_cotangent_at`` / ``_f64``):
+    ``cot_off[r]`` is, per op of ``rev``, the offset in scalars of reverse op r's block in a sample's row of
+    ``cot_stride`` scalars, or -1 -- 8 scalars for ``MAT1`` / ``MAT1_ROW``, 32 for ``MAT2`` / ``MAT2_ROW``;
+    ``two_wire``: a 32-scalar block is among them (sizes the workspace).  -> ``(grad [B, n_grad_slots],
+    rows [B, cot_stride])`` real; block ``[d][d][re, im]`` holds ``G`` with
+    ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta`` in the index convention of the gate's own matrix."""
+    torch = require_gpu()
+    f64 = weights.dtype == torch.float64
+    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
+        raise ValueError("the complex128 sweep takes float64 angle tables")
+    if (wire_groups is None) == (obs_terms is None):
+        raise ValueError("pass either wire_groups or obs_terms")
+    if weights.dim() != 2:
+        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
+    if len(cot_off) != len(terms) or cot_stride < 1:
+        raise ValueError("cot_off holds one entry per reverse op, and the row holds at least one block")
+    B, n_obs = int(weights.shape[0]), int(weights.shape[1])
+    if wire_groups is not None and n_obs != len(wire_groups):
+        raise ValueError(f"weights must be [B, {len(wire_groups)}], got {tuple(weights.shape)}")
+    masks = _wire_group_masks(wire_groups, fwd.n_qubits) if wire_groups is not None else None
+    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
+    n_ot = len(obs_terms) if obs_terms is not None else 0
+    arr = _adjoint_term_array(terms)
+    carr = (C.c_int32 * len(cot_off))(*[int(m) for m in cot_off])
+    fn, wsq, what = ((lib().qmle_adjoint_cotangent_at_f64, lib().qmle_adjoint_cotangent_at_workspace_bytes_f64,
+                      "qmle_adjoint_cotangent_at_f64") if f64
+                     else (lib().qmle_adjoint_cotangent_at, lib().qmle_adjoint_cotangent_at_workspace_bytes,
+                           "qmle_adjoint_cotangent_at"))
+    dev = weights.device
+    ft = torch.float64 if f64 else torch.float32
+    out = torch.empty((B, n_grad_slots), dtype=ft, device=dev)
+    cot = torch.empty((B, int(cot_stride)), dtype=ft, device=dev)
+    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, n_ot, n_obs, int(bool(two_wire))))), dtype=torch.uint8,
+                     device=dev)
+    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
+             C.c_void_p(weights.data_ptr()), masks, oarr, n_ot, n_obs, arr, len(terms),
+             C.c_void_p(out.data_ptr()), int(n_grad_slots), carr, int(cot_stride), C.c_void_p(cot.data_ptr()),
+             C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
+    return out, cot

@@ -11,7 +11,8 @@ the parameter-shift rule.
 One-wire MATRIX gates (constant ``MAT1``, per-sample ``MAT1_ROW``) have no generator; for them the same sweep returns the
 matrix cotangent ``G[a][c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` on the state in front of the gate
 (:func:`adjoint_slot_and_matrix_gradient`), from which a caller that knows ``dU/dtheta`` -- the pulse front end: the
-solver's Jacobian -- forms ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  Two-wire matrices are refused.
+solver's Jacobian -- forms ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  :func:`adjoint_slot_and_matrices_gradient` does the same for
+matrix gates on two wires (``MAT2`` / ``MAT2_ROW``: 4x4 cotangents) beside the one-wire ones.
 
 This module only prepares the REVERSED, DAGGERED tape and the generator table; the sweep itself
 runs in the engine.
@@ -64,7 +65,7 @@ def _op_blobs(low: LoweredTape, x64: bool = False) -> List[Optional[np.ndarray]]
 
 
 def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Sequence[bool],
-                  want_mat: Optional[Sequence[bool]] = None):
+                  want_mat: Optional[Sequence[bool]] = None, two_wire: bool = False):
     """From the forward lowered tape: the reversed, daggered primitive tape (as ``_Lowered`` ops),
     its per-slot values (negated forward columns) and one generator term per reverse op.
 
@@ -80,8 +81,17 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
     ``rev_sign[j] *`` forward column ``rev_src[j]``.  The reverse of a ``MAT1_ROW`` is a ``MAT1_ROW`` on the daggered
     columns -- entry (r, c, re) is the forward entry (c, r, re), sign +1; entry (r, c, im) the forward entry
     (c, r, im), sign -1 -- and every angle keeps sign -1.  ``mat_out[r]``: per REVERSE op the index of the matrix
-    cotangent it reports (flagged forward ops numbered in tape order), or -1.  ``MAT2_ROW`` stays refused."""
+    cotangent it reports (flagged forward ops numbered in tape order), or -1.  ``MAT2_ROW`` stays refused.
+
+    ``two_wire`` (with ``want_mat``): ``MAT2_ROW`` is accepted too -- its reverse is a ``MAT2_ROW`` on the daggered
+    columns, the same rule on 32 columns -- and flags may sit on ``MAT2`` / ``MAT2_ROW``
+    -> ``(rev_ops, terms, rev_src, rev_sign, mat_out, mat_dim)``, ``mat_dim[k]`` in (2, 4) per flagged op."""
     with_mat = want_mat is not None
+    if two_wire and not with_mat:
+        raise ValueError("two_wire goes with want_mat")
+    row_dim = {"MAT1_ROW": 2, "MAT2_ROW": 4} if two_wire else {"MAT1_ROW": 2}
+    flaggable = ("MAT1", "MAT1_ROW", "MAT2", "MAT2_ROW") if two_wire else ("MAT1", "MAT1_ROW")
+    mat_dim = []
     if with_mat and len(want_mat) != len(low.ops):
         raise ValueError("want_mat holds one flag per forward op")
     prims = []  # forward order: (name, wires, fwd_slot | None (MAT1_ROW: its 8 slots), blob, matrix index | -1)
@@ -89,15 +99,18 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
     for k, ((name, wires, slots, _off), blob) in enumerate(zip(low.ops, blobs)):
         k_mat = -1
         if with_mat and want_mat[k]:
-            if name not in ("MAT1", "MAT1_ROW"):
+            if name not in flaggable:
                 raise AdjointUnsupported(f"no matrix cotangent for {name}: the sweep reports them for one-wire matrix "
-                                         "gates only (two-wire matrices are not served)")
+                                         "gates only (two-wire matrices are not served)" if not two_wire else
+                                         f"no matrix cotangent for {name}: the sweep reports them for one-wire matrix "
+                                         "and two-wire matrix gates only")
             k_mat = n_mat
             n_mat += 1
-        if name == "MAT2_ROW":
+            mat_dim.append(4 if name.startswith("MAT2") else 2)
+        if name == "MAT2_ROW" and not two_wire:
             raise AdjointUnsupported("no adjoint rule for MAT2_ROW: the sweep inverts per-sample matrices on one wire "
                                      "only; two-wire matrices (evolved two-wire unitaries) are not served")
-        if name == "MAT1_ROW":
+        if name in row_dim:
             if not with_mat:
                 raise AdjointUnsupported("no adjoint rule for MAT1_ROW in the angle-only form: a per-sample matrix is "
                                          "not inverted by negating its columns (build_reverse(..., want_mat=...) "
@@ -116,11 +129,12 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
         params, out_blob, term = [], None, _term()
         bit = lambda ws: sum(1 << int(w) for w in ws)  # noqa: E731
         mat_out.append(k_mat)
-        if name == "MAT1_ROW":  # U^+: reverse column (r, c, part) <- forward column (c, r, part), imaginary parts negated
-            for r in range(2):
-                for c in range(2):
+        if name in row_dim:  # U^+: reverse column (r, c, part) <- forward column (c, r, part), imaginary parts negated
+            dim = row_dim[name]
+            for r in range(dim):
+                for c in range(dim):
                     for part, sign in ((0, 1.0), (1, -1.0)):
-                        src = fslot[(c * 2 + r) * 2 + part]
+                        src = fslot[(c * dim + r) * 2 + part]
                         params.append(sign * np.asarray(low.values[src], dtype=np.float64))
                         rev_src.append(src)
                         rev_sign.append(sign)
@@ -156,6 +170,8 @@ def build_reverse(low: LoweredTape, blobs: List[Optional[np.ndarray]], want: Seq
             raise AdjointUnsupported(f"no adjoint rule for {name}")
         rev_ops.append(_Lowered((name, list(wires), params, out_blob)))
         terms.append(term)
+    if two_wire:
+        return rev_ops, terms, rev_src, rev_sign, mat_out, mat_dim
     if with_mat:
         return rev_ops, terms, rev_src, rev_sign, mat_out
     return rev_ops, terms, rev_src
@@ -176,17 +192,22 @@ REV_FLAGS_FUSED = (N.PLAN_NO_MERGE | N.PLAN_FORCE_GLOBAL | N.PLAN_NO_ABSORB
 
 
 def run_sweep(fwd_plan, rev: LoweredTape, a_f, a_r, w, obs_groups, terms, n_grad_slots, obs_terms=None,
-              mat_out=None, n_mat=0):
+              mat_out=None, n_mat=0, cot_stride=0, two_wire=False):
     """The backward sweep with fused tile passes where the engine supports the tape (1-qubit and
     controlled 1-qubit gates), else with one streaming pass per gate.  float64 tables: the
     complex128 sweep (one streaming launch per operator, like the complex128 forward engine).
     The observables: Z-parity wire groups ``obs_groups``, or (``obs_groups`` None) the Pauli term list
     ``obs_terms`` -- the same routes, another seed.  ``mat_out`` (per reverse op the index of the matrix cotangent
     it reports, or -1; ``n_mat`` of them): -> ``(gradient, cotangents)`` from the same sweep; the fused tile passes
-    refuse such a request, so above 13 qubits it takes the streaming route."""
+    refuse such a request, so above 13 qubits it takes the streaming route.  ``cot_stride`` > 0: ``mat_out`` holds
+    block OFFSETS in a row of that many scalars instead (one- and two-wire matrices, ``N.adjoint_cotangent_at``)
+    -> ``(gradient, rows [B, cot_stride])``."""
     if mat_out is None:
         call = lambda flags: N.adjoint_gradient(fwd_plan, get_plan(rev, flags), a_f, a_r, w, obs_groups, terms,  # noqa: E731
                                                 n_grad_slots, obs_terms=obs_terms)
+    elif cot_stride:
+        call = lambda flags: N.adjoint_cotangent_at(fwd_plan, get_plan(rev, flags), a_f, a_r, w, obs_groups, terms,  # noqa: E731
+                                                    n_grad_slots, mat_out, cot_stride, two_wire, obs_terms=obs_terms)
     else:
         call = lambda flags: N.adjoint_cotangent(fwd_plan, get_plan(rev, flags), a_f, a_r, w, obs_groups, terms,  # noqa: E731
                                                  n_grad_slots, mat_out, n_mat, obs_terms=obs_terms)
@@ -204,24 +225,28 @@ class RevTables(NamedTuple):
     sign: object            # ... times sign[j] (float64 CUDA tensor): -1 for angles, +1 for real parts of matrices
     mat_out: tuple          # per reverse op: index of its matrix cotangent, or -1
     n_mat: int
+    mat_dim: tuple = ()     # the two-wire form: 2 or 4 per flagged op, in tape order
 
 
 _REV_CACHE: "OrderedDict[tuple, tuple]" = OrderedDict()
 
 
-def _sweep(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights, want, want_mat, x64, obs_terms):
+def _sweep(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights, want, want_mat, x64, obs_terms,
+           two_wire=False):
     torch = N.require_gpu()
     ft, fn = (torch.float64, np.float64) if x64 else (torch.float32, np.float32)
     want_mat = tuple(bool(x) for x in want_mat) if want_mat is not None else (False,) * len(low.ops)
-    key = (low.key, tuple(bool(x) for x in want), bool(x64)) + ((want_mat,) if any(want_mat) else ())
+    key = ((low.key, tuple(bool(x) for x in want), bool(x64)) + ((want_mat,) if any(want_mat) else ())
+           + (("two_wire",) if two_wire else ()))
     hit = _REV_CACHE.get(key)
     if hit is None:
-        rev_ops, terms, rev_src, rev_sign, mat_out = build_reverse(low, _op_blobs(low, x64), want, want_mat)
+        rev_ops, terms, rev_src, rev_sign, mat_out, *dims = build_reverse(low, _op_blobs(low, x64), want, want_mat,
+                                                                          **({"two_wire": True} if two_wire else {}))
         rev = LoweredTape(rev_ops, n_qubits)
         hit = (rev, patch_marks(rev, terms),
                RevTables(torch.tensor(rev_src if rev_src else [0], dtype=torch.int64, device="cuda"),
                          torch.tensor(rev_sign if rev_sign else [-1.0], dtype=torch.float64, device="cuda"),
-                         tuple(mat_out), sum(want_mat)))
+                         tuple(mat_out), sum(want_mat), tuple(dims[0]) if dims else ()))
         _REV_CACHE[key] = hit
         if len(_REV_CACHE) > 64:
             _REV_CACHE.popitem(last=False)
@@ -238,6 +263,14 @@ def _sweep(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights, wan
     else:
         a_r = torch.zeros((batch, 1), dtype=ft, device=a_f.device)
     w = torch.from_numpy(np.ascontiguousarray(weights, dtype=fn)).cuda()
+    if two_wire and tab.n_mat:  # blocks of 8 and 32 scalars in one row, in tape order
+        starts = np.concatenate([[0], np.cumsum([2 * d * d for d in tab.mat_dim])]).astype(int)
+        g, rows = run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed, max(1, low.n_slots),
+                            obs_terms=obs_terms, mat_out=[int(starts[k]) if k >= 0 else -1 for k in tab.mat_out],
+                            cot_stride=int(starts[-1]), two_wire=4 in tab.mat_dim)
+        rows = rows.cpu().numpy()
+        mats = [rows[:, starts[k]:starts[k + 1]].reshape(-1, d, d, 2) for k, d in enumerate(tab.mat_dim)]
+        return g.cpu().numpy()[:, : low.n_slots], [m[..., 0] + 1j * m[..., 1] for m in mats]
     if not tab.n_mat:
         return run_sweep(get_plan(low), rev, a_f, a_r, w, obs_groups, fixed, max(1, low.n_slots),
                          obs_terms=obs_terms).cpu().numpy()[:, : low.n_slots], None
@@ -273,3 +306,16 @@ def adjoint_slot_and_matrix_gradient(low: LoweredTape, n_qubits: int, batch: int
     if cot is None:
         cot = np.zeros((g.shape[0], 0, 2, 2), dtype=np.complex128 if x64 else np.complex64)
     return g, cot
+
+
+def adjoint_slot_and_matrices_gradient(low: LoweredTape, n_qubits: int, batch: int, obs_groups, weights: np.ndarray,
+                                       want: Sequence[bool], want_mat: Sequence[bool], x64: bool = False,
+                                       obs_terms=None) -> Tuple[np.ndarray, List[np.ndarray]]:
+    """:func:`adjoint_slot_and_matrix_gradient` for matrix gates on one AND two wires: ``want_mat`` may flag ``MAT1``,
+    ``MAT1_ROW``, ``MAT2`` and ``MAT2_ROW`` ops, and a tape may hold ``MAT2_ROW`` (evolved two-wire unitaries)
+    -> ``(slot gradients [K * B, n_slots], [G_k])``: one ``[K * B, d, d]`` complex array per flagged op, in tape
+    order, d = 2 or 4, from ONE sweep (``qmle_adjoint_cotangent_at``).  ``G_k`` is written in the index convention of
+    the gate's own matrix (row = 2 * value of its first wire + value of its second), so that
+    ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta`` with ``U`` as the tape holds it."""
+    g, cot = _sweep(low, n_qubits, batch, obs_groups, weights, want, want_mat, x64, obs_terms, two_wire=True)
+    return g, (cot if cot is not None else [])

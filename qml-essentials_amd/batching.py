@@ -11,10 +11,39 @@ table describes the full batch -- exactly the input the HIP engine wants.
 """
 from __future__ import annotations
 
+import contextlib
 import numbers
 from typing import Any, Tuple
 
 import numpy as np
+
+# elementwise (non-linear) tangent rules: off unless a caller that can use them asks (elementwise_tangents)
+_elementwise = 0
+
+# f -> f' for the ufuncs of one argument whose tangent the context tracks: d f(x) = f'(x) dx
+_UFUNC_DERIVATIVES = {
+    np.sin: np.cos, np.cos: lambda x: -np.sin(x), np.tan: lambda x: 1.0 / np.cos(x) ** 2,
+    np.exp: np.exp, np.expm1: np.exp, np.log: lambda x: 1.0 / x, np.log1p: lambda x: 1.0 / (1.0 + x),
+    np.sqrt: lambda x: 0.5 / np.sqrt(x), np.square: lambda x: 2.0 * x, np.reciprocal: lambda x: -1.0 / (x * x),
+    np.sinh: np.cosh, np.cosh: np.sinh, np.tanh: lambda x: 1.0 - np.tanh(x) ** 2,
+    np.arctan: lambda x: 1.0 / (1.0 + x * x),
+}
+
+
+@contextlib.contextmanager
+def elementwise_tangents():
+    """While active, :class:`Batched` applies the chain rule to the ufuncs of ``_UFUNC_DERIVATIVES`` (sin, cos, tan,
+    exp, expm1, log, log1p, sqrt, square, reciprocal, sinh, cosh, tanh, arctan), to powers with a constant exponent
+    and to division by a tracked value, instead of marking the result "derivative unknown".  Gate angles must stay
+    (bi)linear in the leaves for the parameter-shift rule, so the rules are off by default; the coefficient functions
+    of an evolved gate are evaluated with them (:mod:`evolution`).  A ufunc outside the list, or one with more than one
+    tracked input, stays unknown."""
+    global _elementwise
+    _elementwise += 1
+    try:
+        yield
+    finally:
+        _elementwise -= 1
 
 
 class Batched:
@@ -156,8 +185,13 @@ class Batched:
                 tan = self._scaled(self.tan, b, shp) + self._scaled(o_tan, a, shp)
             elif kind == "div" and not swap and not o_tan:
                 tan = self._scaled(self.tan, 1.0 / b, shp)
+            elif kind == "div" and _elementwise:  # the quotient rule (swap: a constant over self)
+                tan = (self._scaled(self.tan, -b / (a * a), shp) if swap
+                       else self._scaled(self.tan, 1.0 / b, shp) + self._scaled(o_tan, -a / (b * b), shp))
             elif kind == "div":
                 tan = None
+            elif kind == "pow" and not swap and not isinstance(other, Batched) and _elementwise:
+                tan = self._scaled(self.tan, b * np.power(a, b - 1.0), shp)
         return Batched(res, tan)
 
     def __add__(self, o): return self._bin(o, np.add, kind="add")
@@ -167,8 +201,8 @@ class Batched:
     def __mul__(self, o): return self._bin(o, np.multiply, kind="mul")
     def __rmul__(self, o): return self._bin(o, np.multiply, True, kind="mul")
     def __truediv__(self, o): return self._bin(o, np.divide, kind="div")
-    def __rtruediv__(self, o): return self._bin(o, np.divide, True)
-    def __pow__(self, o): return self._bin(o, np.power)
+    def __rtruediv__(self, o): return self._bin(o, np.divide, True, kind="div")
+    def __pow__(self, o): return self._bin(o, np.power, kind="pow")
     def __neg__(self):
         return Batched(-self.data,
                        None if self.tan is None else self._scaled(self.tan, -1.0, self.data.shape))
@@ -186,6 +220,13 @@ class Batched:
             if isinstance(x, Batched):
                 return getattr(x, table[ufunc])(y)
             return getattr(y, "__r" + table[ufunc][2:])(x)
+        if _elementwise and ufunc is np.power and len(inputs) == 2 and not kwargs and not isinstance(inputs[1], Batched):
+            return inputs[0] ** inputs[1]
+        if _elementwise and ufunc in _UFUNC_DERIVATIVES and len(inputs) == 1 and not kwargs \
+                and inputs[0].tan is not None:
+            x = inputs[0]
+            res = ufunc(x.data)
+            return Batched(res, self._scaled(x.tan, _UFUNC_DERIVATIVES[ufunc](x.data), res.shape) if x.tan else [])
         batch = self.batch
         arrs = []
         nd = max((x.ndim if isinstance(x, Batched) else np.ndim(x)) for x in inputs)

@@ -30,7 +30,7 @@ struct AdjTermDev {
   int32_t n_y;
   float coef;
   int32_t marks_off;             // offset in the reverse plan's const blob, or -1
-  int32_t mat_out;               // index of the matrix cotangent this op reports (a one-wire matrix gate), or -1
+  int32_t cot_off;               // offset, in floats, of the matrix cotangent this op reports in the sample's row, or -1
 };
 struct AdjLdsArgs {
   TileArgs fwd;                  // the forward plan's whole-state stage
@@ -54,31 +54,10 @@ struct AdjLdsArgs {
   int n_obs;
   float *grad;
   int n_grad_slots;
-  float *cot;                    // [B][n_mat][2][2][re, im] matrix cotangents, or nullptr
-  int n_mat;
+  float *cot;                    // [B][cot_stride] matrix cotangents (blocks of 8 or 32 floats), or nullptr
+  int cot_stride;
 };
 
-// G = M (U^+)^T for the moment M[a][c] = sum conj(lambda[a]) psi[c] taken BEHIND the gate: phi = U^+ psi is the state
-// in front of it, so G[a][c] = sum conj(lambda[a]) phi[c] = sum_d M[a][d] U^+[c][d].  `ud`: the reverse op's own
-// matrix (U^+), `m`: M as (re, im) pairs, row-major; T: float or double.
-template <class T, class MT>
-__device__ __forceinline__ void cot_finish(const T (&m)[8], const MT *__restrict__ ud, T *__restrict__ out) {
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      T re = 0, im = 0;
-#pragma unroll
-      for (int d = 0; d < 2; ++d) {
-        const T mr = m[(a * 2 + d) * 2], mi = m[(a * 2 + d) * 2 + 1];
-        const T ur = (T)ud[(c * 2 + d) * 2], ui = (T)ud[(c * 2 + d) * 2 + 1];
-        re += mr * ur - mi * ui;
-        im += mr * ui + mi * ur;
-      }
-      out[(a * 2 + c) * 2] = re;
-      out[(a * 2 + c) * 2 + 1] = im;
-    }
-}
 // m[(a * 2 + c) * 2 + {0, 1}] += conj(l_a) p_c for the pair (l0, l1), (p0, p1) of one value of the other wires
 template <class T, class V>
 __device__ __forceinline__ void cot_accumulate(T (&m)[8], const V l0, const V l1, const V p0, const V p1) {
@@ -86,6 +65,25 @@ __device__ __forceinline__ void cot_accumulate(T (&m)[8], const V l0, const V l1
   m[2] += l0.x * p1.x + l0.y * p1.y; m[3] += l0.x * p1.y - l0.y * p1.x;
   m[4] += l1.x * p0.x + l1.y * p0.y; m[5] += l1.x * p0.y - l1.y * p0.x;
   m[6] += l1.x * p1.x + l1.y * p1.y; m[7] += l1.x * p1.y - l1.y * p1.x;
+}
+
+// eight per-thread sums -> their workgroup totals, valid in thread 0; `red`: eight floats per wave
+__device__ __forceinline__ void block_sum8(float (&m)[8], float *red) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave, nw = (blockDim.x + kWave - 1) / kWave;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) m[k] = wave_sum(m[k]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[wv * 8 + k] = m[k];
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int i = 1; i < nw; ++i) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) m[k] += red[i * 8 + k];
+    }
+  }
 }
 
 template <bool DENSE4, bool PAULI>
@@ -160,29 +158,33 @@ __global__ void k_adjoint_lds(const AdjLdsArgs a) {
       }
     }
     const LoweredOp o = a.rev_ops[r];
-    if (t.mat_out >= 0) {  // a one-wire matrix gate (checked on the host): all eight numbers from one read of both
+    if (t.cot_off >= 0 && o.kind == LK_1Q) {  // a one-wire matrix gate: all eight numbers from one read of both
       const uint32_t tb = 1u << o.t0;
       float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       for (uint32_t i = tid; i < (cnt >> 1); i += nt) {
         const uint32_t j0 = ins0(i, o.t0), j1 = j0 | tb;
         cot_accumulate(m, lam[sw(j0)], lam[sw(j1)], psi[sw(j0)], psi[sw(j1)]);
       }
-      const int lane = tid & (kWave - 1), wv = tid / kWave, nw = (nt + kWave - 1) / kWave;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m[k] = wave_sum(m[k]);
-      __syncthreads();
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) red[wv * 8 + k] = m[k];
-      }
-      __syncthreads();
-      if (tid == 0) {
-        for (int i = 1; i < nw; ++i) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) m[k] += red[i * 8 + k];
+      block_sum8(m, red);
+      if (tid == 0) cot_finish<2>(m, mrow + o.mat_off, a.cot + (size_t)b * a.cot_stride + t.cot_off);
+    } else if (t.cot_off >= 0) {  // a two-wire one (kinds checked on the host): one row of the 4x4 moment per pass
+      const uint32_t b0 = 1u << o.t0, b1 = 1u << o.t1;
+      const int plo = o.t0 < o.t1 ? o.t0 : o.t1, phi = o.t0 < o.t1 ? o.t1 : o.t0;
+#pragma unroll 1
+      for (int row = 0; row < 4; ++row) {
+        const uint32_t la = ((row & 2) ? b0 : 0u) | ((row & 1) ? b1 : 0u);
+        float m[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (uint32_t i = tid; i < (cnt >> 2); i += nt) {
+          const uint32_t j = ins0(ins0(i, plo), phi);
+          cot_row4(m, lam[sw(j | la)], psi[sw(j)], psi[sw(j | b1)], psi[sw(j | b0)], psi[sw(j | b0 | b1)]);
         }
-        cot_finish(m, mrow + o.mat_off, a.cot + ((size_t)b * a.n_mat + t.mat_out) * 8);
+        block_sum8(m, red);
+        if (tid == 0) {  // (behind the per-wave sums: red holds 288 floats)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) red[256 + row * 8 + k] = m[k];
+        }
       }
+      if (tid == 0) cot_finish<4>((const float *)(red + 256), mrow + o.mat_off, a.cot + (size_t)b * a.cot_stride + t.cot_off);
     }
     lds_apply(psi, T, o, mrow, a.rev_consts, ang);
     lds_apply(lam, T, o, mrow, a.rev_consts, ang);
@@ -488,7 +490,7 @@ k_adj_moment(const float4 *__restrict__ psi_all, const float4 *__restrict__ lam_
 // cot[b][k] = (sum_blocks partial[b][block]) (U^+)^T, summed in double; U^+ = the reverse op's matrix of sample b
 __global__ void __launch_bounds__(256)
 k_adj_cot_final(const float2 *__restrict__ partial, int n_blocks, const float *__restrict__ mats, uint32_t mat_floats,
-                uint32_t mat_off, float *__restrict__ cot, int n_mat, int k_mat) {
+                uint32_t mat_off, float *__restrict__ cot, int cot_stride, int cot_off) {
   __shared__ double red[16];
   const int b = blockIdx.x;
   double m[8];
@@ -503,10 +505,7 @@ k_adj_cot_final(const float2 *__restrict__ partial, int n_blocks, const float *_
     m[2 * e + 1] = block_sum_d(im, red);
   }
   if (threadIdx.x == 0) {
-    double g[8];
-    cot_finish(m, mats + (size_t)b * mat_floats + mat_off, g);
-    float *out = cot + ((size_t)b * n_mat + k_mat) * 8;
-    for (int e = 0; e < 8; ++e) out[e] = (float)g[e];
+    cot_finish<2>(m, mats + (size_t)b * mat_floats + mat_off, cot + (size_t)b * cot_stride + cot_off);
   }
 }
 
@@ -521,8 +520,8 @@ static int adj_blocks(int n) {
   return (int)b;
 }
 struct AdjLayout { size_t states, lam, mats, ang2, partial, fwd_ws, lds_ops, lds_terms, lds_fmats, tile_partial, total; };
-// cot: the sweep also returns matrix cotangents (four complex partials per block instead of one)
-static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch, bool cot = false) {
+// cot: complex partials per block -- 1, or 4 with one-wire matrix cotangents, or 16 with a two-wire one among them
+static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch, int cot = 1) {
   AdjLayout L;
   const size_t sb = (size_t)batch * ((size_t)8 << fwd->n);
   L.states = 0;
@@ -530,7 +529,7 @@ static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batc
   L.mats = align_up(2 * sb, 256);
   L.ang2 = L.mats + ws_mats_bytes(rev, 2 * batch);
   L.partial = L.ang2 + align_up((size_t)2 * batch * (rev->n_slots ? rev->n_slots : 1) * sizeof(float), 256);
-  L.fwd_ws = L.partial + align_up((size_t)batch * adj_blocks(fwd->n) * sizeof(float2) * (cot ? 4 : 1), 256);
+  L.fwd_ws = L.partial + align_up((size_t)batch * adj_blocks(fwd->n) * sizeof(float2) * cot, 256);
   L.lds_ops = L.fwd_ws + workspace_bytes_one(fwd, batch, QMLE_MEAS_STATE, 0) + 256;
   L.lds_terms = L.lds_ops + align_up(rev->lowered.size() * sizeof(LoweredOp) + 16, 256);
   L.lds_fmats = L.lds_terms + align_up(rev->lowered.size() * sizeof(AdjTermDev) + 16, 256);
@@ -552,30 +551,6 @@ struct AdjObs {
   const qmle_pauli_term *obs_terms;
   int n_obs_terms, n_obs;
 };
-// A request for matrix cotangents beside the angle gradients: mat_out[r] = index of the 2x2 that reverse op r (a
-// one-wire matrix gate) reports, or -1; d_cot [batch][n_mat][2][2][re, im].  mat_out == nullptr: no request.
-struct AdjCot {
-  const int32_t *mat_out;
-  int n_mat;
-  float *d_cot;
-};
-// The request against the reverse tape; low_of[r] <- the lowered operator of reverse op r (or -1).
-static int adj_cot_check(const qmle_plan *rev, const int32_t *mat_out, int n_mat, const void *d_cot,
-                         std::vector<int> &low_of) {
-  if (n_mat < 1 || !d_cot) return QMLE_ERR_INVALID_ARG;
-  low_of.assign(rev->ops.size(), -1);
-  for (size_t l = 0; l < rev->lowered_src.size(); ++l)
-    if (rev->lowered_src[l].size() == 1) low_of[rev->lowered_src[l][0]] = (int)l;
-  for (size_t r = 0; r < rev->ops.size(); ++r) {
-    if (mat_out[r] < 0) continue;
-    if (mat_out[r] >= n_mat) return QMLE_ERR_SLOT_RANGE;
-    const int oc = rev->ops[r].opcode;
-    if (oc != QMLE_OP_MAT1 && oc != QMLE_OP_MAT1_ROW) return QMLE_ERR_UNSUPPORTED;  // (two-wire matrices: not served)
-    if (low_of[r] < 0 || rev->lowered[low_of[r]].kind != LK_1Q || rev->lowered[low_of[r]].nc != 0)
-      return QMLE_ERR_INVALID_ARG;
-  }
-  return QMLE_OK;
-}
 struct SeedHold {  // ends the seed's host plan on every way out
   PauliSeed *sd = nullptr;
   ~SeedHold() { pauli_seed_end(sd); }
@@ -585,7 +560,7 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
                        const float *d_angles_rev, int batch, const float *d_weights, const AdjObs &obs,
                        const qmle_adjoint_term *terms, int n_terms, float *d_grad,
                        int n_grad_slots, void *d_workspace, size_t workspace_bytes,
-                       qmle_stream stream_, const AdjCot &cot = {nullptr, 0, nullptr}) {
+                       qmle_stream stream_, const CotRequest &cot = {nullptr, 0, nullptr}) {
   const uint32_t *obs_wire_masks = obs.wire_masks;
   const int n_obs = obs.n_obs;
   const bool pauli = obs.obs_terms != nullptr;
@@ -607,17 +582,16 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
   for (const auto &srcs : rev->lowered_src)
     if (srcs.size() != 1) return QMLE_ERR_INVALID_ARG;
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = ensure_device_plan(rev);
+  const bool want_cot = cot.off != nullptr;
+  float *const d_cot = (float *)cot.d_cot;
+  std::vector<int> low_of;
+  int rc = want_cot ? cot_request_check(rev, cot, low_of) : QMLE_OK;  // (host only: before any device work)
+  if (rc != QMLE_OK) return rc;
+  rc = ensure_device_plan(rev);
   if (rc != QMLE_OK) return rc;
   char *ws = (char *)d_workspace;
-  const bool want_cot = cot.mat_out != nullptr;
-  const AdjLayout L = adj_layout(fwd, rev, batch, want_cot);
+  const AdjLayout L = adj_layout(fwd, rev, batch, !want_cot ? 1 : cot_has_two_wire(rev, cot.off) ? 16 : 4);
   if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
-  std::vector<int> low_of;
-  if (want_cot) {
-    rc = adj_cot_check(rev, cot.mat_out, cot.n_mat, cot.d_cot, low_of);
-    if (rc != QMLE_OK) return rc;
-  }
   for (int k = 0; !pauli && k < n_obs; ++k)
     if (!valid_wire_mask(obs_wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
   for (int r = 0; r < n_terms; ++r)
@@ -648,7 +622,7 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
       d.n_y = t.n_y;
       d.coef = t.coef;
       d.marks_off = t.marks_off;
-      d.mat_out = want_cot ? cot.mat_out[rev->lowered_src[r][0]] : -1;
+      d.cot_off = want_cot ? cot.off[rev->lowered_src[r][0]] : -1;
       if (t.marks_off >= 0 && (size_t)t.marks_off + ((size_t)1 << n) > rev->consts.size())
         return QMLE_ERR_INVALID_ARG;
     }
@@ -672,7 +646,7 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
     float *fmats = (float *)(ws + L.lds_fmats);
     float *rmats = (float *)(ws + L.mats);
     HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(float), stream));
-    if (want_cot) HIPCHK(hipMemsetAsync(cot.d_cot, 0, (size_t)batch * cot.n_mat * 8 * sizeof(float), stream));
+    if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(float), stream));
     rc = launch_build_matrices(fwd, d_angles_fwd, fmats, batch, stream);
     if (rc == QMLE_OK) rc = launch_build_matrices(rev, d_angles_rev, rmats, batch, stream);
     if (rc != QMLE_OK) return rc;
@@ -702,8 +676,8 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
     }
     a.grad = d_grad;
     a.n_grad_slots = n_grad_slots;
-    a.cot = cot.d_cot;
-    a.n_mat = cot.n_mat;
+    a.cot = d_cot;
+    a.cot_stride = cot.stride;
     if (FirstUse once{3}; once.first) {
       for (const void *k : {(const void *)k_adjoint_lds<false, false>, (const void *)k_adjoint_lds<true, false>,
                             (const void *)k_adjoint_lds<false, true>, (const void *)k_adjoint_lds<true, true>})
@@ -750,7 +724,7 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
                        (const float4 *)psi, (float4 *)lam, n, d_weights, z);
   }
   HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(float), stream));
-  if (want_cot) HIPCHK(hipMemsetAsync(cot.d_cot, 0, (size_t)batch * cot.n_mat * 8 * sizeof(float), stream));
+  if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(float), stream));
   // the backward gates act on [psi; lambda] as one batch of 2B states: duplicate the angles
   if (rev->n_slots > 0) {
     const size_t ab = (size_t)batch * rev->n_slots * sizeof(float);
@@ -868,13 +842,21 @@ static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd
                          (const float2 *)partial, nb, t.n_y, t.coef, d_grad, n_grad_slots,
                          t.out_slot);
     }
-    if (want_cot && cot.mat_out[r] >= 0) {
-      const LoweredOp &lo = rev->lowered[low_of[r]];  // (bit position and plain record: checked by adj_cot_check)
-      hipLaunchKernelGGL(k_adj_moment, dim3(nb, batch), dim3(256), 0, stream, (const float4 *)psi,
-                         (const float4 *)lam, n, (int)lo.t0, partial);
-      hipLaunchKernelGGL(k_adj_cot_final, dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                         (const float2 *)partial, nb, (const float *)mats, rev->mat_floats, lo.mat_off, cot.d_cot,
-                         cot.n_mat, cot.mat_out[r]);
+    if (want_cot && cot.off[r] >= 0) {
+      const LoweredOp &lo = rev->lowered[low_of[r]];  // (bit positions and plain record: checked by cot_request_check)
+      if (lo.kind == LK_2Q) {
+        hipLaunchKernelGGL((k_adj_moment2<float2, float>), dim3(nb, batch), dim3(256), 0, stream, (const float2 *)psi,
+                           (const float2 *)lam, n, (int)lo.t0, (int)lo.t1, partial);
+        hipLaunchKernelGGL((k_adj_cot2_final<float2, float>), dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
+                           (const float2 *)partial, nb, (const float *)mats, rev->mat_floats, lo.mat_off, d_cot,
+                           cot.stride, cot.off[r]);
+      } else {
+        hipLaunchKernelGGL(k_adj_moment, dim3(nb, batch), dim3(256), 0, stream, (const float4 *)psi,
+                           (const float4 *)lam, n, (int)lo.t0, partial);
+        hipLaunchKernelGGL(k_adj_cot_final, dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
+                           (const float2 *)partial, nb, (const float *)mats, rev->mat_floats, lo.mat_off, d_cot,
+                           cot.stride, cot.off[r]);
+      }
     }
     rc = run_stage_inplace(rev, st, psi, mats, ang2, 2 * batch, stream);
     if (rc != QMLE_OK) return rc;
@@ -919,31 +901,55 @@ int qmle_adjoint_gradient_pauli(qmle_plan *fwd, qmle_plan *rev, const float *d_a
 }
 
 
-size_t qmle_adjoint_cotangent_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
-                                              int n_obs) {
+size_t qmle_adjoint_cotangent_at_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                 int n_obs_terms, int n_obs, int two_wire) {
   if (!fwd || !rev || batch < 1 || n_obs_terms < 0 || n_obs < 1) return 0;
-  return adj_layout(fwd, rev, batch, true).total + 256 +
+  return adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total + 256 +
          (n_obs_terms > 0 ? pauli_seed_ws_bytes(batch, n_obs_terms, false) : 0);
 }
+size_t qmle_adjoint_cotangent_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
+                                              int n_obs) {
+  return qmle_adjoint_cotangent_at_workspace_bytes(fwd, rev, batch, n_obs_terms, n_obs, 0);
+}
 
+int qmle_adjoint_cotangent_at(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
+                              int batch, const float *d_weights, const uint32_t *obs_wire_masks,
+                              const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                              const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
+                              const int32_t *cot_off, int cot_stride, float *d_cot, void *d_ws, size_t ws_bytes,
+                              qmle_stream stream) {
+  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !cot_off || !d_cot || cot_stride < 1 ||
+      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
+    return QMLE_ERR_INVALID_ARG;
+  if (obs_terms) {
+    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
+    if (rc != QMLE_OK) return rc;
+  }
+  if (ws_bytes < qmle_adjoint_cotangent_at_workspace_bytes(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs,
+                                                           cot_has_two_wire(rev, cot_off)))
+    return QMLE_ERR_INVALID_ARG;
+  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                     {obs_wire_masks, obs_terms, obs_terms ? n_obs_terms : 0, n_obs}, terms, n_terms, d_grad,
+                     n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot});
+}
+
+// the form with one index per 2x2: offsets 8 * index into rows of 8 * n_mat floats
 int qmle_adjoint_cotangent(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
                            int batch, const float *d_weights, const uint32_t *obs_wire_masks,
                            const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                            const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
                            const int32_t *mat_out, int n_mat, float *d_cot, void *d_ws, size_t ws_bytes,
                            qmle_stream stream) {
+  // (the argument checks of the function below first, so that a call that is bad in two ways keeps its old code)
   if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !mat_out || !d_cot || n_mat < 1 ||
-      (obs_wire_masks != nullptr) == (obs_terms != nullptr))
+      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
     return QMLE_ERR_INVALID_ARG;
-  if (obs_terms) {
-    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-    if (rc != QMLE_OK) return rc;
-  }
-  if (ws_bytes < qmle_adjoint_cotangent_workspace_bytes(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs))
-    return QMLE_ERR_INVALID_ARG;
-  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
-                     {obs_wire_masks, obs_terms, obs_terms ? n_obs_terms : 0, n_obs}, terms, n_terms, d_grad,
-                     n_grad_slots, d_ws, ws_bytes, stream, {mat_out, n_mat, d_cot});
+  std::vector<int32_t> off;
+  const int rc = cot_offsets_of_indices(rev, mat_out, n_mat, off);
+  if (rc != QMLE_OK) return rc;
+  return qmle_adjoint_cotangent_at(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, obs_terms,
+                                   n_obs_terms, n_obs, terms, n_terms, d_grad, n_grad_slots, off.data(), 8 * n_mat,
+                                   d_cot, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,9 @@
 // with A(t) = -i sum_i c_i(t) H_i.  The kernel evaluates no coefficient function: it reads c_i at the node times from
 // a table coef[row][node][term], in node order.  float64 throughout; the result is rounded once when it is stored as
 // complex64.  k_pulse_unitaries (further down) solves the RX / RY leaves of pulse-level gates on the same grids with
-// the same work split, but evaluates its two coefficients itself instead of reading a table.  k_compose_circuits (last)
+// the same work split, but evaluates its two coefficients itself instead of reading a table; k_pulse_jac adds its
+// parameter sensitivities and k_evolve_magnus_jac the directional derivatives of the table-driven solve (their own
+// comment blocks).  k_compose_circuits (last)
 // multiplies such 2x2 results and constant gates into the unitaries of 1- and 2-wire circuits with their parameter
 // derivatives: its own comment block.
 //
@@ -69,14 +71,16 @@ template <int DIM> __host__ __device__ __forceinline__ void set_identity(CMat<DI
   }
 }
 
-// G = sum_i w_i H_i for the weights w (already times h)
-template <int DIM>
-__host__ __device__ __forceinline__ void weighted_sum(const EvolveTerms &T, int n_terms, const double *__restrict__ c0,
-                                             const double *__restrict__ c1, double w0, double w1, Herm<DIM> &G) {
+template <int DIM> __host__ __device__ __forceinline__ void set_zero(Herm<DIM> &G) {
 #pragma unroll
   for (int k = 0; k < DIM; ++k) G.d[k] = 0.0;
 #pragma unroll
   for (int k = 0; k < Herm<DIM>::NU; ++k) G.re[k] = G.im[k] = 0.0;
+}
+// G += sum_i w_i H_i for the weights w (already times h)
+template <int DIM>
+__host__ __device__ __forceinline__ void weighted_add(const EvolveTerms &T, int n_terms, const double *__restrict__ c0,
+                                             const double *__restrict__ c1, double w0, double w1, Herm<DIM> &G) {
   for (int t = 0; t < n_terms; ++t) {
     double w = w0 * c0[t];
     if (c1) w = fma(w1, c1[t], w);
@@ -89,6 +93,13 @@ __host__ __device__ __forceinline__ void weighted_sum(const EvolveTerms &T, int 
       G.im[k] = fma(w, H[DIM + Herm<DIM>::NU + k], G.im[k]);
     }
   }
+}
+// G = sum_i w_i H_i
+template <int DIM>
+__host__ __device__ __forceinline__ void weighted_sum(const EvolveTerms &T, int n_terms, const double *__restrict__ c0,
+                                             const double *__restrict__ c1, double w0, double w1, Herm<DIM> &G) {
+  set_zero(G);
+  weighted_add<DIM>(T, n_terms, c0, c1, w0, w1, G);
 }
 
 // U <- exp(-i G) U, G = g0 I + a . sigma:  exp(-i G) = e^{-i g0} (cos |a| I - i sin |a| / |a| (a . sigma))
@@ -126,12 +137,13 @@ __host__ __device__ __forceinline__ void apply_exp(const Herm<2> &G, CMat<2> &U)
   U = R;
 }
 
-// y = G v for the packed Hermitian G and one complex column v
+// y = G v (ACC: y += G v) for the packed Hermitian G and one complex column v
+template <bool ACC = false>
 __host__ __device__ __forceinline__ void herm_matvec(const Herm<4> &G, const double (&vr)[4], const double (&vi)[4],
                                             double (&yr)[4], double (&yi)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    double xr = G.d[i] * vr[i], xi = G.d[i] * vi[i];
+    double xr = ACC ? fma(G.d[i], vr[i], yr[i]) : G.d[i] * vr[i], xi = ACC ? fma(G.d[i], vi[i], yi[i]) : G.d[i] * vi[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (j == i) continue;
@@ -147,8 +159,8 @@ __host__ __device__ __forceinline__ void herm_matvec(const Herm<4> &G, const dou
   }
 }
 
-// U <- exp(-i G) U, column by column (see the head of this file)
-__host__ __device__ __forceinline__ void apply_exp(const Herm<4> &G, CMat<4> &U) {
+// the largest absolute row sum of a packed Hermitian matrix
+__host__ __device__ __forceinline__ double herm_row_norm(const Herm<4> &G) {
   double nu = 0.0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -159,18 +171,41 @@ __host__ __device__ __forceinline__ void apply_exp(const Herm<4> &G, CMat<4> &U)
       const int u = j > i ? upper_index<4>(i, j) : upper_index<4>(j, i);
       row += fabs(G.re[u]) + fabs(G.im[u]);
     }
-    nu = fmax(nu, row);
+    nu = (row > nu || row != row) ? row : nu;  // (a NaN stays)
   }
-  if (!(nu <= kEvolveMaxNorm)) {  // (also a NaN)
+  return nu;
+}
+// How the series of exp(-i G) runs, from the norm alone (the head of this file): the forward kernel and the Jacobian
+// kernel take it from here, so slot 0 of the latter repeats the former bit for bit.
+struct SeriesCut {
+  bool ok;            // the norm is finite and within kEvolveMaxNorm
+  int parts;          // equal parts the exponent is cut into
+  double inv_parts;
+  int n_series;       // terms behind the column itself
+};
+__host__ __device__ __forceinline__ SeriesCut series_cut(const Herm<4> &G) {
+  const double nu = herm_row_norm(G);
+  SeriesCut c;
+  c.ok = nu <= kEvolveMaxNorm;  // (false for a NaN)
+  c.parts = c.ok && nu > kEvolveTheta ? (int)ceil(nu / kEvolveTheta) : 1;
+  c.inv_parts = 1.0 / (double)c.parts;
+  const double nu_part = nu * c.inv_parts;
+  c.n_series = 1;
+  for (double bound = nu_part; c.n_series < 24 && bound >= 1e-19; ++c.n_series) bound *= nu_part / (double)(c.n_series + 1);
+  return c;
+}
+
+// U <- exp(-i G) U, column by column (see the head of this file)
+__host__ __device__ __forceinline__ void apply_exp(const Herm<4> &G, CMat<4> &U) {
+  const SeriesCut cut = series_cut(G);
+  if (!cut.ok) {
     const double bad = __builtin_nan("");
 #pragma unroll
     for (int k = 0; k < 16; ++k) U.re[k] = U.im[k] = bad;
     return;
   }
-  const int parts = nu > kEvolveTheta ? (int)ceil(nu / kEvolveTheta) : 1;
-  const double inv_parts = 1.0 / (double)parts, nu_part = nu * inv_parts;
-  int n_series = 1;  // terms behind the column itself
-  for (double bound = nu_part; n_series < 24 && bound >= 1e-19; ++n_series) bound *= nu_part / (double)(n_series + 1);
+  const int parts = cut.parts, n_series = cut.n_series;
+  const double inv_parts = cut.inv_parts;
 #pragma unroll
   for (int col = 0; col < 4; ++col) {
     double vr[4], vi[4];
@@ -589,6 +624,18 @@ struct PulseJac {
   CMat<2> U, d[5];
 };
 
+// c = cos r, sinc = sin r / r and kappa = (cos r - sinc) / r^2 for r = sqrt(r2), the last two from their series where
+// the quotient would cancel: what the derivative of exp(-i a . sigma) is made of (pulse_step_jac, exp_su2_jac)
+__host__ __device__ __forceinline__ void sinc_kappa(double r2, double &c, double &sinc, double &kappa) {
+  const double r = sqrt(r2);
+  double s;
+  sincos(r, &s, &c);
+  const bool small = r < 0.05;
+  sinc = small ? 1.0 - r2 * (1.0 / 6.0) * (1.0 - r2 * 0.05 * (1.0 - r2 * (1.0 / 42.0))) : s / r;
+  kappa = small ? -1.0 / 3.0 + r2 * (1.0 / 30.0 - r2 * (1.0 / 840.0 - r2 * (1.0 / 45360.0 - r2 * (1.0 / 3991680.0))))
+                : (c - sinc) / r2;
+}
+
 // U <- E U and d_k <- dE_k U + E d_k for E = exp(-i (gx X + gy Y)) and the directions (dgx[k], dgy[k]):
 //   E = cos r I - i sinc (gx X + gy Y),  dE = -sinc rho I - i ((kappa rho gx + sinc dgx) X + (kappa rho gy + sinc dgy) Y)
 // with rho = gx dgx + gy dgy and kappa = (cos r - sinc) / r^2, from its series where the difference would cancel.
@@ -596,14 +643,9 @@ struct PulseJac {
 template <unsigned TANGENTS>
 __host__ __device__ __forceinline__ bool pulse_step_jac(double gx, double gy, const double (&dgx)[5],
                                                const double (&dgy)[5], PulseJac &J) {
-  const double r2 = gx * gx + gy * gy, r = sqrt(r2);
-  double s, c;
-  sincos(r, &s, &c);
-  const bool small = r < 0.05;
-  const double sinc = small ? 1.0 - r2 * (1.0 / 6.0) * (1.0 - r2 * 0.05 * (1.0 - r2 * (1.0 / 42.0))) : s / r;
-  const double kappa =
-      small ? -1.0 / 3.0 + r2 * (1.0 / 30.0 - r2 * (1.0 / 840.0 - r2 * (1.0 / 45360.0 - r2 * (1.0 / 3991680.0))))
-            : (c - sinc) / r2;
+  const double r2 = gx * gx + gy * gy;
+  double c, sinc, kappa;
+  sinc_kappa(r2, c, sinc, kappa);
   CMat<2> E;
   E.re[0] = E.re[3] = c;
   E.re[1] = -sinc * gy;
@@ -735,6 +777,210 @@ __global__ __launch_bounds__(kEvolveThreads) void k_pulse_jac(const double *__re
 #pragma unroll
     for (int t = 0; t < 5; ++t) o[4 * (t + 1) + k] = make_double2(J.d[t].re[k], J.d[t].im[k]);
   }
+}
+
+// ---- the table-driven solve with directional derivatives ---------------------------------------------------------------
+// k_evolve_magnus with the EXACT derivative of the grid's result in n_dirs directions (discretise, then differentiate,
+// as k_pulse_jac).  A direction is a derivative of the coefficient table, dcoef[row][dir][node][term], and of the
+// step, dh[row][dir]; per exponential factor Omega = h sum_j a_j A(t_j) it gives
+//   dOmega = dh sum_j a_j A(t_j) + h sum_j a_j dA(t_j)
+// (a moving node's f'(t_j) dt_j arrives inside dcoef: the kernel evaluates no function), and U <- E U,
+// dU <- dE U + E dU.  One (row, direction) is one unit of work that recomputes U, so a direction's result does not
+// depend on which others share the call; direction 0's unit stores U.
+//
+// DIM = 2: a lane holds U and dU (16 doubles); E = exp(-i (g0 I + a . sigma)) and dE in closed form (exp_su2_jac).
+// DIM = 4: ONE COLUMN of U and dU per lane -- exp(Omega) U acts on columns independently, so the 4 neighbouring lanes
+// of a unit's run share the exponent and never talk until the combine.  A lane that held the whole of U and dU beside
+// both packed exponents and a column's series with its derivative would need near 280 live registers: one wave per SIMD.
+// A column per lane needs 32 + 32 for the exponents and 48 for the series, stays under 256 VGPRs at two waves per SIMD
+// and runs four times as many lanes; the price is that a unit's runs times 4 must fit a wave: lanes in {1, 4, 16}.
+// The column's series carries its derivative term by term, v_{k+1} = Omega v_k / (k + 1), dv_{k+1} = (dOmega v_k +
+// Omega dv_k) / (k + 1), with the cut and the term count of apply_exp (from nu of Omega alone); the parts of a cut
+// exponent chain through (v, dv), which is the product rule across them.
+// NC columns per lane, CL = DIM / NC lanes per run; u / d: column c of U / dU, entry i
+template <int DIM, int NC> struct JacCols {
+  double ur[NC][DIM], ui[NC][DIM], dr[NC][DIM], di[NC][DIM];
+};
+
+// E = exp(-i G) and its derivative in the direction dG, G = g0 I + a . sigma:  E = e^{-i g0} M,
+//   M = cos r I - i sinc (a . sigma),  dM = -sinc rho I - i ((kappa rho a + sinc da) . sigma),  rho = a . da,
+//   dE = e^{-i g0} (dM - i dg0 M)
+__host__ __device__ __forceinline__ void exp_su2_jac(const Herm<2> &G, const Herm<2> &dG, CMat<2> &E, CMat<2> &dE) {
+  const double g0 = 0.5 * (G.d[0] + G.d[1]), az = 0.5 * (G.d[0] - G.d[1]), ax = G.re[0], ay = -G.im[0];
+  const double dg0 = 0.5 * (dG.d[0] + dG.d[1]), daz = 0.5 * (dG.d[0] - dG.d[1]), dax = dG.re[0], day = -dG.im[0];
+  double c, sinc, kappa, ps, pc;
+  sinc_kappa(ax * ax + ay * ay + az * az, c, sinc, kappa);
+  sincos(g0, &ps, &pc);
+  const double rho = ax * dax + ay * day + az * daz, kr = kappa * rho;
+  const double vx = fma(kr, ax, sinc * dax), vy = fma(kr, ay, sinc * day), vz = fma(kr, az, sinc * daz);
+  const double m_re[4] = {c, -sinc * ay, sinc * ay, c}, m_im[4] = {-sinc * az, -sinc * ax, -sinc * ax, sinc * az};
+  const double n_re[4] = {-sinc * rho, -vy, vy, -sinc * rho}, n_im[4] = {-vz, -vx, -vx, vz};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double dr = fma(dg0, m_im[k], n_re[k]), di = fma(-dg0, m_re[k], n_im[k]);
+    E.re[k] = pc * m_re[k] + ps * m_im[k];
+    E.im[k] = pc * m_im[k] - ps * m_re[k];
+    dE.re[k] = pc * dr + ps * di;
+    dE.im[k] = pc * di - ps * dr;
+  }
+}
+
+// (U, dU) <- (E U, dE U + E dU), E = exp(-i G) -> bit 0: G is not finite, bit 1: dG is not
+__host__ __device__ __forceinline__ int step_jac(const Herm<2> &G, const Herm<2> &dG, JacCols<2, 2> &S) {
+  CMat<2> E, dE;
+  exp_su2_jac(G, dG, E, dE);
+#pragma unroll
+  for (int col = 0; col < 2; ++col) {
+    double nur[2], nui[2], ndr[2], ndi[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      double xr = 0.0, xi = 0.0, yr = 0.0, yi = 0.0;
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const double er = E.re[2 * i + k], ei = E.im[2 * i + k], fr = dE.re[2 * i + k], fi = dE.im[2 * i + k];
+        xr = fma(er, S.ur[col][k], xr), xr = fma(-ei, S.ui[col][k], xr);
+        xi = fma(er, S.ui[col][k], xi), xi = fma(ei, S.ur[col][k], xi);
+        yr = fma(fr, S.ur[col][k], yr), yr = fma(-fi, S.ui[col][k], yr);
+        yi = fma(fr, S.ui[col][k], yi), yi = fma(fi, S.ur[col][k], yi);
+        yr = fma(er, S.dr[col][k], yr), yr = fma(-ei, S.di[col][k], yr);
+        yi = fma(er, S.di[col][k], yi), yi = fma(ei, S.dr[col][k], yi);
+      }
+      nur[i] = xr, nui[i] = xi, ndr[i] = yr, ndi[i] = yi;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) S.ur[col][i] = nur[i], S.ui[col][i] = nui[i], S.dr[col][i] = ndr[i], S.di[col][i] = ndi[i];
+  }
+  const double ng = fabs(G.d[0]) + fabs(G.d[1]) + fabs(G.re[0]) + fabs(G.im[0]);
+  const double nd = fabs(dG.d[0]) + fabs(dG.d[1]) + fabs(dG.re[0]) + fabs(dG.im[0]);
+  return (ng <= 1.7e308 ? 0 : 1) | (nd <= 1.7e308 ? 0 : 2);
+}
+
+// the lane's column: (v, dv) <- (exp(-i G) v, d exp(-i G) v + exp(-i G) dv) by the series of apply_exp with its
+// derivative -> bit 0: the norm of G is not finite or beyond kEvolveMaxNorm (nothing is changed), bit 1: dG is not finite
+__host__ __device__ __forceinline__ int step_jac(const Herm<4> &G, const Herm<4> &dG, JacCols<4, 1> &S) {
+  const SeriesCut cut = series_cut(G);
+  const int bad_d = herm_row_norm(dG) <= 1.7e308 ? 0 : 2;
+  if (!cut.ok) return 1 | bad_d;
+  const int parts = cut.parts, n_series = cut.n_series;
+  const double inv_parts = cut.inv_parts;
+  for (int p = 0; p < parts; ++p) {
+    double tr[4], ti[4], er[4], ei[4];  // the running term and its derivative
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tr[i] = S.ur[0][i], ti[i] = S.ui[0][i], er[i] = S.dr[0][i], ei[i] = S.di[0][i];
+    for (int k = 1; k <= n_series; ++k) {
+      double yr[4], yi[4], zr[4], zi[4];
+      herm_matvec(dG, tr, ti, zr, zi);
+      herm_matvec<true>(G, er, ei, zr, zi);
+      herm_matvec(G, tr, ti, yr, yi);
+      const double f = inv_parts / (double)k;  // term <- (-i G / parts) term / k
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        tr[i] = f * yi[i], ti[i] = -f * yr[i];
+        er[i] = f * zi[i], ei[i] = -f * zr[i];
+        S.ur[0][i] += tr[i], S.ui[0][i] += ti[i];
+        S.dr[0][i] += er[i], S.di[0][i] += ei[i];
+      }
+    }
+  }
+  return bad_d;
+}
+
+// (P, dP) <- (L P, dL P + L dP) for the later partial product (L, dL), held by the CL lanes that start delta * CL
+// lanes up.  Entry (i, k) of L sits in lane k / NC of them, column k % NC: every lane reads the 4 * DIM * DIM doubles
+// it needs, then overwrites its own.  A lane whose later run lies outside its unit reads another unit's and ends with
+// a product nobody uses (as combine_with_later: lanes is a power of two and run 0 only ever reads runs that are whole).
+template <int DIM, int NC> __device__ __forceinline__ void combine_with_later_jac(JacCols<DIM, NC> &S, int delta) {
+  constexpr int CL = DIM / NC;
+  const int wave_lane = (int)(threadIdx.x & (kWave - 1)), first = wave_lane - (wave_lane & (CL - 1)) + delta * CL;
+  JacCols<DIM, NC> R;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) R.ur[c][i] = R.ui[c][i] = R.dr[c][i] = R.di[c][i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < DIM; ++i)
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) {
+      const int src = (first + k / NC) & (kWave - 1);
+      const double lr = __shfl(S.ur[k % NC][i], src), li = __shfl(S.ui[k % NC][i], src);
+      const double mr = __shfl(S.dr[k % NC][i], src), mi = __shfl(S.di[k % NC][i], src);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        R.ur[c][i] = fma(lr, S.ur[c][k], R.ur[c][i]), R.ur[c][i] = fma(-li, S.ui[c][k], R.ur[c][i]);
+        R.ui[c][i] = fma(lr, S.ui[c][k], R.ui[c][i]), R.ui[c][i] = fma(li, S.ur[c][k], R.ui[c][i]);
+        R.dr[c][i] = fma(mr, S.ur[c][k], R.dr[c][i]), R.dr[c][i] = fma(-mi, S.ui[c][k], R.dr[c][i]);
+        R.di[c][i] = fma(mr, S.ui[c][k], R.di[c][i]), R.di[c][i] = fma(mi, S.ur[c][k], R.di[c][i]);
+        R.dr[c][i] = fma(lr, S.dr[c][k], R.dr[c][i]), R.dr[c][i] = fma(-li, S.di[c][k], R.dr[c][i]);
+        R.di[c][i] = fma(lr, S.di[c][k], R.di[c][i]), R.di[c][i] = fma(li, S.dr[c][k], R.di[c][i]);
+      }
+    }
+  S = R;
+}
+
+// One work item per (row, direction, run of the steps, column lane); a block holds kEvolveThreads / (lanes * CL) units.
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(kEvolveThreads) void k_evolve_magnus_jac(const EvolveTerms terms, int n_terms,
+                                                                      const double *__restrict__ coef,
+                                                                      const double *__restrict__ h_rows,
+                                                                      const double *__restrict__ dcoef,
+                                                                      const double *__restrict__ dh_rows, int rows,
+                                                                      int n_dirs, int n_steps, int lanes,
+                                                                      double2 *__restrict__ out) {
+  constexpr int NC = DIM == 2 ? 2 : 1, CL = DIM / NC, NODES = ORDER == 4 ? 2 : 1;
+  const long long gid = (long long)blockIdx.x * kEvolveThreads + threadIdx.x;
+  const int col_lane = (int)(gid & (CL - 1));
+  const long long item = gid / CL, unit_ll = item / lanes, n_units = (long long)rows * n_dirs;
+  const int run = (int)(item - unit_ll * lanes);
+  const bool live = unit_ll < n_units;  // (a unit's lanes are live or idle together: lanes * CL divides the block)
+  const int unit = (int)(live ? unit_ll : n_units - 1), row = unit / n_dirs, dir = unit - row * n_dirs;
+  const int s_begin = (int)((long long)run * n_steps / lanes), s_end = (int)((long long)(run + 1) * n_steps / lanes);
+  const double h = h_rows[row], dh = dh_rows[unit];
+  const size_t node_stride = (size_t)NODES * n_terms;
+  const double *__restrict__ c = coef + ((size_t)row * n_steps + s_begin) * node_stride;
+  const double *__restrict__ dc = dcoef + ((size_t)unit * n_steps + s_begin) * node_stride;
+  JacCols<DIM, NC> S;
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      S.ur[k][i] = (i == col_lane * NC + k) ? 1.0 : 0.0;
+      S.ui[k][i] = S.dr[k][i] = S.di[k][i] = 0.0;
+    }
+  Herm<DIM> G, dG;
+  int bad = 0;
+  for (int s = s_begin; s < s_end; ++s, c += node_stride, dc += node_stride) {
+    if constexpr (ORDER == 2) {
+      weighted_sum<DIM>(terms, n_terms, c, nullptr, h, 0.0, G);
+      weighted_sum<DIM>(terms, n_terms, c, nullptr, dh, 0.0, dG);
+      weighted_add<DIM>(terms, n_terms, dc, nullptr, h, 0.0, dG);
+      bad |= step_jac(G, dG, S);
+    } else {
+#pragma nounroll
+      for (int half = 0; half < 2; ++half) {  // Omega_a first, then Omega_b: the weights exchanged
+        const double w1 = half ? kA2 : kA1, w2 = half ? kA1 : kA2;
+        weighted_sum<DIM>(terms, n_terms, c, c + n_terms, h * w1, h * w2, G);
+        weighted_sum<DIM>(terms, n_terms, c, c + n_terms, dh * w1, dh * w2, dG);
+        weighted_add<DIM>(terms, n_terms, dc, dc + n_terms, h * w1, h * w2, dG);
+        bad |= step_jac(G, dG, S);
+      }
+    }
+  }
+  for (int delta = 1; delta < lanes; delta <<= 1) {  // run 0 ends with the unit
+    combine_with_later_jac(S, delta);
+    bad |= __shfl(bad, (int)((threadIdx.x + delta * CL) & (kWave - 1)));
+  }
+  if (!live || run != 0) return;
+  const double nan = __builtin_nan("");
+  double2 *__restrict__ o = out + (size_t)row * (1 + n_dirs) * (DIM * DIM);
+  double2 *__restrict__ od = o + (size_t)(1 + dir) * (DIM * DIM);
+#pragma unroll
+  for (int k = 0; k < NC; ++k)
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      const int e = i * DIM + col_lane * NC + k;
+      if (dir == 0) o[e] = (bad & 1) ? make_double2(nan, nan) : make_double2(S.ur[k][i], S.ui[k][i]);
+      od[e] = bad ? make_double2(nan, nan) : make_double2(S.dr[k][i], S.di[k][i]);
+    }
 }
 
 // ---- composition of small circuits ------------------------------------------------------------------------------------
@@ -1032,6 +1278,45 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
 #define QMLE_EVOLVE_LAUNCH(D, O)                                                                                \
   hipLaunchKernelGGL((k_evolve_magnus<D, O>), grid, block, 0, stream, T, n_terms, d_coef, d_h, rows, n_steps, lanes, \
                      out_f64, d_out)
+  if (dim == 2 && order == 2) QMLE_EVOLVE_LAUNCH(2, 2);
+  else if (dim == 2) QMLE_EVOLVE_LAUNCH(2, 4);
+  else if (order == 2) QMLE_EVOLVE_LAUNCH(4, 2);
+  else QMLE_EVOLVE_LAUNCH(4, 4);
+#undef QMLE_EVOLVE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int qmle_evolve_magnus_jac(const double *h_terms, int n_terms, int dim, const double *d_coef, const double *d_h,
+                           const double *d_dcoef, const double *d_dh, int rows, int n_dirs, int order, int n_steps,
+                           int lanes_per_row, void *d_out, qmle_stream stream_) {
+  if (dim != 2 && dim != 4) return QMLE_ERR_UNSUPPORTED;
+  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
+  if (!h_terms || !d_coef || !d_h || !d_dcoef || !d_dh || !d_out || n_terms < 1 || n_terms > kEvolveMaxTerms ||
+      rows < 1 || n_steps < 1 || n_dirs < 1 || n_dirs > 64)
+    return QMLE_ERR_INVALID_ARG;
+  if ((long long)n_steps * (order == 4 ? 2 : 1) * n_terms > (1ll << 31) - 1) return QMLE_ERR_INVALID_ARG;
+  if (lanes_per_row != 0 && lanes_per_row != 1 && lanes_per_row != 4 && lanes_per_row != 16 && lanes_per_row != 64)
+    return QMLE_ERR_INVALID_ARG;
+  const int column_lanes = dim == 4 ? 4 : 1;  // a run's lanes: one per column of a 4x4 U
+  if (lanes_per_row * column_lanes > kWave) return QMLE_ERR_INVALID_ARG;  // a unit's lanes share a wave
+  const long long units = (long long)rows * n_dirs;
+  int lanes = lanes_per_row;
+  if (!lanes) {
+    lanes = units <= (1ll << 30) ? evolve_auto_lanes((int)units, n_steps) : 1;
+    if (lanes * column_lanes > kWave) lanes = kWave / column_lanes;
+  }
+  if (units * lanes > (1ll << 31) - kEvolveThreads) return QMLE_ERR_INVALID_ARG;
+  EvolveTerms T;
+  if (dim == 2) pack_terms<2>(h_terms, n_terms, T);
+  else pack_terms<4>(h_terms, n_terms, T);
+  for (int t = n_terms; t < kEvolveMaxTerms; ++t)
+    for (int k = 0; k < 16; ++k) T.h[t][k] = 0.0;
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(grid_for((uint64_t)(units * lanes * column_lanes), kEvolveThreads)), block(kEvolveThreads);
+#define QMLE_EVOLVE_LAUNCH(D, O)                                                                                     \
+  hipLaunchKernelGGL((k_evolve_magnus_jac<D, O>), grid, block, 0, stream, T, n_terms, d_coef, d_h, d_dcoef, d_dh, rows, \
+                     n_dirs, n_steps, lanes, (double2 *)d_out)
   if (dim == 2 && order == 2) QMLE_EVOLVE_LAUNCH(2, 2);
   else if (dim == 2) QMLE_EVOLVE_LAUNCH(2, 4);
   else if (order == 2) QMLE_EVOLVE_LAUNCH(4, 2);

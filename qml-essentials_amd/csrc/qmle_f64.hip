@@ -302,11 +302,10 @@ k64_adj_moment(const double2 *__restrict__ psi_all, const double2 *__restrict__ 
     if (threadIdx.x == 0) partial[((size_t)b * gridDim.x + blockIdx.x) * 4 + e] = make_double2(r, s);
   }
 }
-// cot[b][k] = (sum_blocks partial[b][block]) (U^+)^T: phi = U^+ psi is the state in front of the gate, so
-// G[a][c] = sum conj(lambda[a]) phi[c] = sum_d M[a][d] U^+[c][d]; U^+ = the reverse op's matrix of sample b
+// cot[b][off ..] = (sum_blocks partial[b][block]) (U^+)^T (cot_finish); U^+ = the reverse op's matrix of sample b
 __global__ void __launch_bounds__(256)
 k64_adj_cot_final(const double2 *__restrict__ partial, int n_blocks, const double *__restrict__ mats,
-                  uint32_t mat_floats, uint32_t mat_off, double *__restrict__ cot, int n_mat, int k_mat) {
+                  uint32_t mat_floats, uint32_t mat_off, double *__restrict__ cot, int cot_stride, int cot_off) {
   __shared__ double red[16];
   const int b = blockIdx.x;
   double m[8];
@@ -321,25 +320,8 @@ k64_adj_cot_final(const double2 *__restrict__ partial, int n_blocks, const doubl
     m[2 * e] = block_sum_d(re, red);
     m[2 * e + 1] = block_sum_d(im, red);
   }
-  if (threadIdx.x == 0) {
-    const double *ud = mats + (size_t)b * mat_floats + mat_off;
-    double *out = cot + ((size_t)b * n_mat + k_mat) * 8;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        double re = 0.0, im = 0.0;
-#pragma unroll
-        for (int d = 0; d < 2; ++d) {
-          const double mr = m[(a * 2 + d) * 2], mi = m[(a * 2 + d) * 2 + 1];
-          const double ur = ud[(c * 2 + d) * 2], ui = ud[(c * 2 + d) * 2 + 1];
-          re += mr * ur - mi * ui;
-          im += mr * ui + mi * ur;
-        }
-        out[(a * 2 + c) * 2] = re;
-        out[(a * 2 + c) * 2 + 1] = im;
-      }
-  }
+  if (threadIdx.x == 0)
+    cot_finish<2>((const double *)m, mats + (size_t)b * mat_floats + mat_off, cot + (size_t)b * cot_stride + cot_off);
 }
 
 }  // namespace
@@ -539,14 +521,14 @@ static int f64_adj_blocks(int n) {
   return (int)(b < 1 ? 1 : b > 1024 ? 1024 : b);
 }
 struct F64AdjLayout { size_t fmats, rmats, partial, psi, lam, total; };
-// cot: the sweep also returns matrix cotangents (four complex partials per block instead of one)
-static F64AdjLayout f64_adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch, bool cot = false) {
+// cot: complex partials per block -- 1, or 4 with one-wire matrix cotangents, or 16 with a two-wire one among them
+static F64AdjLayout f64_adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch, int cot = 1) {
   F64AdjLayout L;
   const int fl = f64_in_flight(fwd->n, batch, 32);  // psi and lambda of a round of samples
   L.fmats = 0;
   L.rmats = f64_mats_bytes(fwd, batch);
   L.partial = L.rmats + f64_mats_bytes(rev, batch);
-  L.psi = L.partial + align_up((size_t)fl * f64_adj_blocks(fwd->n) * sizeof(double2) * (cot ? 4 : 1), 256);
+  L.psi = L.partial + align_up((size_t)fl * f64_adj_blocks(fwd->n) * sizeof(double2) * cot, 256);
   L.lam = L.psi + align_up((size_t)fl * ((size_t)16 << fwd->n), 256);
   L.total = L.lam + align_up((size_t)fl * ((size_t)16 << fwd->n), 256) + 512;
   return L;
@@ -562,11 +544,15 @@ size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_p
   return f64_adj_layout(fwd, rev, batch).total + 256 +
          pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true);
 }
+size_t qmle_adjoint_cotangent_at_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                     int n_obs_terms, int n_obs, int two_wire) {
+  if (!fwd || !rev || batch < 1 || fwd->n != rev->n || n_obs_terms < 0 || n_obs < 1) return 0;
+  return f64_adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total + 256 +
+         (n_obs_terms > 0 ? pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true) : 0);
+}
 size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                                   int n_obs_terms, int n_obs) {
-  if (!fwd || !rev || batch < 1 || fwd->n != rev->n || n_obs_terms < 0 || n_obs < 1) return 0;
-  return f64_adj_layout(fwd, rev, batch, true).total + 256 +
-         (n_obs_terms > 0 ? pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true) : 0);
+  return qmle_adjoint_cotangent_at_workspace_bytes_f64(fwd, rev, batch, n_obs_terms, n_obs, 0);
 }
 
 }  // extern "C"
@@ -578,9 +564,10 @@ static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angle
                            const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                            const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
                            void *d_workspace, size_t workspace_bytes, qmle_stream stream_,
-                           const int32_t *mat_out = nullptr, int n_mat = 0, double *d_cot = nullptr) {
+                           const CotRequest &cot = {nullptr, 0, nullptr}) {
   const bool pauli = obs_terms != nullptr;
-  const bool want_cot = mat_out != nullptr;  // matrix cotangents of one-wire matrix gates beside the angle gradients
+  const bool want_cot = cot.off != nullptr;  // matrix cotangents beside the angle gradients
+  double *const d_cot = (double *)cot.d_cot;
   if (!fwd || !rev || batch < 1 || !d_weights || (!pauli && !obs_wire_masks) || n_obs < 1 ||
       (!pauli && n_obs > QMLE_MAX_QUBITS) || !terms ||
       !d_grad || n_grad_slots < 1 || !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
@@ -599,20 +586,12 @@ static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angle
         (size_t)terms[r].marks_off + ((size_t)1 << n) > rev->n_user_consts)
       return QMLE_ERR_INVALID_ARG;
   }
-  std::vector<int> low_of(rev->ops.size(), -1);  // reverse op -> its lowered operator
+  std::vector<int> low_of;  // reverse op -> its lowered operator
   if (want_cot) {
-    if (n_mat < 1 || !d_cot) return QMLE_ERR_INVALID_ARG;
-    for (size_t l = 0; l < rev->lowered_src.size(); ++l) low_of[rev->lowered_src[l][0]] = (int)l;
-    for (size_t r = 0; r < rev->ops.size(); ++r) {
-      if (mat_out[r] < 0) continue;
-      if (mat_out[r] >= n_mat) return QMLE_ERR_SLOT_RANGE;
-      const int oc = rev->ops[r].opcode;
-      if (oc != QMLE_OP_MAT1 && oc != QMLE_OP_MAT1_ROW) return QMLE_ERR_UNSUPPORTED;  // (two-wire matrices: not served)
-      if (low_of[r] < 0 || rev->lowered[low_of[r]].kind != LK_1Q || rev->lowered[low_of[r]].nc != 0)
-        return QMLE_ERR_INVALID_ARG;
-    }
+    rc = cot_request_check(rev, cot, low_of);
+    if (rc != QMLE_OK) return rc;
   }
-  const F64AdjLayout L = f64_adj_layout(fwd, rev, batch, want_cot);
+  const F64AdjLayout L = f64_adj_layout(fwd, rev, batch, !want_cot ? 1 : cot_has_two_wire(rev, cot.off) ? 16 : 4);
   char *ws = (char *)d_workspace;
   if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
@@ -626,7 +605,7 @@ static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angle
   launch_build_matrices_f64(fwd, d_angles_fwd, fmats, batch, stream);
   launch_build_matrices_f64(rev, d_angles_rev, rmats, batch, stream);
   HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(double), stream));
-  if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * n_mat * 8 * sizeof(double), stream));
+  if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(double), stream));
   double2 *psi = (double2 *)(ws + L.psi), *lam = (double2 *)(ws + L.lam);
   double2 *partial = (double2 *)(ws + L.partial);
   const size_t D = (size_t)1 << n;
@@ -673,14 +652,22 @@ static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angle
         hipLaunchKernelGGL(k64_adj_final, dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream, (const double2 *)partial, nb,
                            t.n_y, (double)t.coef, d_grad + (size_t)b0 * n_grad_slots, n_grad_slots, t.out_slot);
       }
-      const int k_mat = want_cot ? mat_out[rev->lowered_src[r][0]] : -1;
-      if (k_mat >= 0) {
+      const int c_off = want_cot ? cot.off[rev->lowered_src[r][0]] : -1;
+      if (c_off >= 0) {
         const LoweredOp &lo = rev->lowered[r];
-        hipLaunchKernelGGL(k64_adj_moment, dim3(nb, bc), dim3(256), 0, stream, (const double2 *)psi,
-                           (const double2 *)lam, n, (int)lo.t0, partial);
-        hipLaunchKernelGGL(k64_adj_cot_final, dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                           (const double2 *)partial, nb, (const double *)(rmats + (size_t)b0 * rev->mat_floats),
-                           rev->mat_floats, lo.mat_off, d_cot + (size_t)b0 * n_mat * 8, n_mat, k_mat);
+        const double *mr = rmats + (size_t)b0 * rev->mat_floats;
+        double *out = d_cot + (size_t)b0 * cot.stride;
+        if (lo.kind == LK_2Q) {
+          hipLaunchKernelGGL((k_adj_moment2<double2, double>), dim3(nb, bc), dim3(256), 0, stream,
+                             (const double2 *)psi, (const double2 *)lam, n, (int)lo.t0, (int)lo.t1, partial);
+          hipLaunchKernelGGL((k_adj_cot2_final<double2, double>), dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream,
+                             (const double2 *)partial, nb, mr, rev->mat_floats, lo.mat_off, out, cot.stride, c_off);
+        } else {
+          hipLaunchKernelGGL(k64_adj_moment, dim3(nb, bc), dim3(256), 0, stream, (const double2 *)psi,
+                             (const double2 *)lam, n, (int)lo.t0, partial);
+          hipLaunchKernelGGL(k64_adj_cot_final, dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream,
+                             (const double2 *)partial, nb, mr, rev->mat_floats, lo.mat_off, out, cot.stride, c_off);
+        }
       }
       for (double2 *st : {psi, lam})
         hipLaunchKernelGGL(k64_op, dim3(gx, bc), dim3(256), 0, stream, st, n, rev->lowered[r],
@@ -715,24 +702,44 @@ int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double
                          n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes, stream);
 }
 
+int qmle_adjoint_cotangent_at_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
+                                  const double *d_angles_rev, int batch, const double *d_weights,
+                                  const uint32_t *obs_wire_masks, const qmle_pauli_term *obs_terms, int n_obs_terms,
+                                  int n_obs, const qmle_adjoint_term *terms, int n_terms, double *d_grad,
+                                  int n_grad_slots, const int32_t *cot_off, int cot_stride, double *d_cot, void *d_ws,
+                                  size_t ws_bytes, qmle_stream stream) {
+  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !cot_off || !d_cot || cot_stride < 1 ||
+      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
+    return QMLE_ERR_INVALID_ARG;
+  if (obs_terms) {
+    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
+    if (rc != QMLE_OK) return rc;
+  }
+  if (ws_bytes < qmle_adjoint_cotangent_at_workspace_bytes_f64(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs,
+                                                               cot_has_two_wire(rev, cot_off)))
+    return QMLE_ERR_INVALID_ARG;
+  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, obs_terms,
+                         obs_terms ? n_obs_terms : 0, n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes,
+                         stream, {cot_off, cot_stride, d_cot});
+}
+
+// the form with one index per 2x2: offsets 8 * index into rows of 8 * n_mat doubles
 int qmle_adjoint_cotangent_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
                                int batch, const double *d_weights, const uint32_t *obs_wire_masks,
                                const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                                const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
                                const int32_t *mat_out, int n_mat, double *d_cot, void *d_ws, size_t ws_bytes,
                                qmle_stream stream) {
+  // (the argument checks of the function below first, so that a call that is bad in two ways keeps its old code)
   if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !mat_out || !d_cot || n_mat < 1 ||
-      (obs_wire_masks != nullptr) == (obs_terms != nullptr))
+      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
     return QMLE_ERR_INVALID_ARG;
-  if (obs_terms) {
-    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-    if (rc != QMLE_OK) return rc;
-  }
-  if (ws_bytes < qmle_adjoint_cotangent_workspace_bytes_f64(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs))
-    return QMLE_ERR_INVALID_ARG;
-  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, obs_terms,
-                         obs_terms ? n_obs_terms : 0, n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes,
-                         stream, mat_out, n_mat, d_cot);
+  std::vector<int32_t> off;
+  const int rc = cot_offsets_of_indices(rev, mat_out, n_mat, off);
+  if (rc != QMLE_OK) return rc;
+  return qmle_adjoint_cotangent_at_f64(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks,
+                                       obs_terms, n_obs_terms, n_obs, terms, n_terms, d_grad, n_grad_slots, off.data(),
+                                       8 * n_mat, d_cot, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -14,9 +14,19 @@ DIFFERENT integrator: step doubling on the order-4 grid.  N starts at 32 and dou
 exceeds ``max_steps``.  If no grid is accepted -- always the case for ``max_steps < 32`` -- the solve fails:
 ``RuntimeError`` naming ``max_steps`` with ``throw=True``, NaN-filled rows with ``throw=False``.
 
-Gradients.  Tangents are dropped through ``evolve``: an evolved gate whose arguments depend on a differentiated leaf
-carries "derivative unknown", and ``Script.gradient`` refuses it as it refuses every untracked transformation.
-Differentiating through the solver is out of scope, as are matrices larger than 4x4.
+Gradients.  By default tangents are dropped through ``evolve``: an evolved gate whose arguments depend on a
+differentiated leaf carries "derivative unknown", and ``Script.gradient`` (parameter shift) refuses it as it refuses
+every untracked transformation.  ``Script.vjp(..., through_evolve=True)`` records its tape inside
+:func:`gradient_trace`; an evolved gate whose arguments depend on a leaf is then solved by ``qmle_evolve_magnus_jac``
+-- the same grid with the EXACT derivative of its result, one launch per gate call -- and recorded as an
+:class:`EvolvedGate` that carries the Jacobian ``dU / d(leaf element)`` for the sweep's matrix cotangent.  The
+directions are the distinct leaf elements the coefficient table or the step depends on (at most 64 per gate): the
+evolution time and the interval ends keep their tangents, the node times ``t0 + (n + c) h`` are built as tracked
+values -- so a coefficient function's own time dependence carries the moving-node term -- and every ``f_i(params_i,
+t)`` is evaluated under ``batching.elementwise_tangents()``, ONE call with the array of node times (no per-node
+fallback).  A coefficient the recorder cannot track raises ``NotImplementedError`` before any device work.  Adaptive
+solver names run the doubling as always, then one Jacobian launch on the accepted grid.  Matrices larger than 4x4 are
+out of scope.
 
 Pulse-level gates (:mod:`pulses`) do not come through ``evolve``: their RX / RY leaves are solved by a kernel of their
 own that evaluates the envelopes on the device, all leaves of a tape in one launch.  They share the solver defaults
@@ -24,17 +34,96 @@ below and the step-doubling rule (``_doubling``).
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Any, Callable, Optional, Union
 
 import numpy as np
 
 from . import _native as N
-from .batching import Batched
+from .batching import Batched, elementwise_tangents
 from .operations import Hermitian, Operation, ParametrizedHamiltonian
 
 _SQRT3 = np.sqrt(3.0)
 _C1, _C2 = 0.5 - _SQRT3 / 6.0, 0.5 + _SQRT3 / 6.0
 _FIRST_GRID = 32  # step doubling starts here
+
+
+_gradient_trace = 0  # > 0 while a tape is recorded for Script.vjp(through_evolve=True)
+
+_TRACKED = ("sums, products, quotients, powers with a constant exponent and sin, cos, tan, exp, expm1, log, log1p, "
+            "sqrt, square, reciprocal, sinh, cosh, tanh, arctan of one tracked value")
+
+
+@contextlib.contextmanager
+def gradient_trace():
+    """While active, ``evolve`` keeps the tangents of its arguments and records gates that carry the Jacobian of
+    their solve (module docstring).  Only a caller that asks the adjoint sweep for matrix cotangents enters it."""
+    global _gradient_trace
+    _gradient_trace += 1
+    try:
+        yield
+    finally:
+        _gradient_trace -= 1
+
+
+class EvolvedGate(Operation):
+    """An evolved unitary whose arguments depend on differentiated leaves: one matrix per sample, ``jacobian``
+    ``[rows, D, d, d]`` = its exact grid derivative by the leaf elements ``directions`` ``[(leaf, flat index)]``."""
+
+    wants_matrix_cotangent = True
+
+    def __init__(self, U: np.ndarray, wires, name, jacobian: np.ndarray, directions: list, steps: int,
+                 record: bool = True) -> None:
+        super().__init__(wires=wires, matrix=U, name=name or "Operation", record=record)
+        self._matrix_tangent = None  # (every consumer that differentiates angles only refuses it, as before)
+        self.jacobian, self.directions, self.evolve_steps = jacobian, list(directions), steps
+
+    def leaf_jacobian_terms(self) -> list:
+        """``[(leaf, direction, flat index, 1.0)]``: slot ``direction`` of ``jacobian`` is the derivative by that
+        element of that leaf."""
+        return [(leaf, k, flat, 1.0) for k, (leaf, flat) in enumerate(self.directions)]
+
+    def dagger(self) -> "EvolvedGate":
+        new = EvolvedGate(np.conj(np.swapaxes(self.matrix, -1, -2)), self.wires, self.name,
+                          np.conj(np.swapaxes(self.jacobian, -1, -2)), self.directions, self.evolve_steps, record=False)
+        self._replace_on_tape(new)
+        return new
+
+    def power(self, power: int):
+        raise NotImplementedError("a power of an evolved gate inside a gradient trace: its Jacobian is not carried")
+
+    def __mul__(self, other):
+        raise NotImplementedError("a multiple of an evolved gate inside a gradient trace: its Jacobian is not carried")
+
+    __rmul__ = __mul__
+
+
+def _tracked_nodes(t0, h, n_steps: int, order: int):
+    """The node times of ``_node_times`` from a start and a step that may be tracked 0-d ``Batched`` values ->
+    a ``Batched`` of visible shape ``[nodes]`` (a plain array when neither is batched)."""
+    n = np.arange(n_steps, dtype=np.float64)
+    if order == 2:
+        offs = n + 0.5
+    else:
+        offs = np.empty(2 * n_steps, dtype=np.float64)
+        offs[0::2], offs[1::2] = n + _C1, n + _C2
+    return t0 + offs * h
+
+
+def _tracked_table(res, rows: int, nodes: int, what: str):
+    """A coefficient function's result or a time -> ``(values [rows, nodes], tangent terms)``; the index arrays
+    of the terms are broadcast to ``[nodes]`` and their coefficients to ``[rows, nodes]``."""
+    if not isinstance(res, Batched):
+        return np.broadcast_to(np.asarray(res, dtype=np.float64), (rows, nodes)).copy(), []
+    if res.tan is None:
+        raise NotImplementedError(f"evolve(): {what} depends on a differentiated argument through an operation the "
+                                  f"recorder does not track; tracked are {_TRACKED}")
+    if res.ndim > 1 or res.batch not in (1, rows):
+        raise ValueError(f"evolve(): {what} has shape {res.shape}; expected a scalar or one value per node")
+    terms = [(lid, np.broadcast_to(np.asarray(idx).reshape(-1), (nodes,)),
+              np.broadcast_to(np.asarray(coef, dtype=np.float64).reshape(res.batch, -1), (rows, nodes)))
+             for lid, idx, coef in res.tan]
+    return np.broadcast_to(np.asarray(res.data, dtype=np.float64).reshape(res.batch, -1), (rows, nodes)).copy(), terms
 
 
 def _rows_of(values) -> int:
@@ -192,12 +281,51 @@ class Evolution:
         return op_
 
     @classmethod
+    def _with_jacobian(cls, H: np.ndarray, tables: list, step, order: int, wires, name, steps: int,
+                       failed=None) -> Operation:
+        """One launch of the solver with its derivatives -> the :class:`EvolvedGate`.  ``tables``: per term ``(values
+        [rows, nodes], tangent terms)`` of :func:`_tracked_table`; ``step``: the same for the step, ``[rows, 1]``.  The
+        directions are the distinct ``(leaf, flat index)`` pairs of all tangent terms, in order of appearance.
+        ``failed``: rows the step doubling did not accept (NaN in every slot)."""
+        if H.shape[-1] not in (2, 4):
+            raise NotImplementedError(f"evolve(): Hamiltonians on {H.shape[-1]}x{H.shape[-1]} matrices are not "
+                                      "supported (1 or 2 wires)")
+        if H.shape[0] > N.EVOLVE_MAX_TERMS:
+            raise NotImplementedError(f"evolve(): at most {N.EVOLVE_MAX_TERMS} terms, got {H.shape[0]}")
+        rows, nodes = tables[0][0].shape
+        directions: dict = {}
+        for _vals, terms in tables + [step]:
+            for lid, idx, _coef in terms:
+                for v in np.unique(idx):
+                    directions.setdefault((lid, int(v)), len(directions))
+        if len(directions) > N.EVOLVE_MAX_DIRS:
+            raise NotImplementedError(f"evolve(): {name or 'the gate'} depends on {len(directions)} leaf elements; at "
+                                      f"most {N.EVOLVE_MAX_DIRS} per evolved gate are differentiated")
+        D = max(1, len(directions))  # (a gate whose tangents are all empty: one zero direction)
+        coef = np.stack([vals for vals, _terms in tables], axis=-1)
+        dcoef, dh = np.zeros((rows, D, nodes, len(tables))), np.zeros((rows, D))
+        for i, (_vals, terms) in enumerate(tables):
+            for lid, idx, c in terms:
+                for v in np.unique(idx):
+                    m = idx == v
+                    dcoef[:, directions[lid, int(v)], m, i] += c[:, m]
+        for lid, idx, c in step[1]:
+            dh[:, directions[lid, int(idx[0])]] += c[:, 0]
+        out = N.evolve_magnus_jac(H, coef, step[0][:, 0], dcoef, dh, order).cpu().numpy()
+        if failed is not None:
+            out[failed] = np.nan
+        return EvolvedGate(out[:, 0], wires, name, out[:, 1:1 + len(directions)], list(directions), steps)
+
+    @classmethod
     def _evolve_static(cls, hermitian: Hermitian, name: Optional[str]) -> Callable:
         H = np.asarray(hermitian.matrix, dtype=np.complex128)[None]
 
         def _apply(t, wires=0) -> Operation:
             rows = _rows_of([t])
             h = _per_row(t, rows)
+            if _gradient_trace and _tangent_state([t]) is None:  # one step of order 2, dcoef = 0, dh = dt
+                return cls._with_jacobian(H, [(np.ones((rows, 1)), [])], _tracked_table(t, rows, 1, "the time t"), 2,
+                                          wires, name, 1)
             U = cls._solve(H, np.ones((rows, 1, 1)), h, 2)
             return cls._operation(U, isinstance(t, Batched), wires, name, _tangent_state([t]), 1)
 
@@ -229,10 +357,36 @@ class Evolution:
                 coef = np.stack([_coefficients(f, p, t, per_row_times) for f, p in zip(fns, params)], axis=-1)
                 return cls._solve(H, coef, h, order)
 
+            def tracked_tables(n_steps: int, order: int):
+                """(per term (values, tangent terms), the same for the step): host work only; raises what the
+                recorder cannot track."""
+                if any(isinstance(x, Batched) and x.tan is None for x in span):
+                    raise NotImplementedError("evolve(): the evolution time depends on a differentiated argument "
+                                              f"through an operation the recorder does not track; tracked are {_TRACKED}")
+                a, b = (span[0], span[1]) if len(span) == 2 else (0.0, span[0])
+                step = (b - a) / n_steps
+                t = _tracked_nodes(a, step, n_steps, order)
+                nodes = n_steps * (2 if order == 4 else 1)
+                tables = []
+                for i, (f, p_) in enumerate(zip(fns, params)):
+                    with elementwise_tangents():
+                        res = f(p_, t)
+                    tables.append(_tracked_table(res, rows, nodes, f"the coefficient of term {i} of {name or 'the gate'}"))
+                return tables, _tracked_table(step, rows, 1, "the step")
+
+            def with_jacobian(n_steps: int, order: int, failed=None) -> Operation:
+                tables, step = tracked_tables(n_steps, order)
+                return cls._with_jacobian(H, tables, step, order, wires, name, n_steps, failed)
+
+            tracked = _gradient_trace and _tangent_state(list(params) + span) is None
             steps = magnus_steps
             if solver in ("magnus2", "magnus4"):
+                if tracked:
+                    return with_jacobian(magnus_steps, 2 if solver == "magnus2" else 4)
                 U = fixed(magnus_steps, 2 if solver == "magnus2" else 4)
             else:
+                if tracked:  # what cannot be differentiated is refused before any device work
+                    tracked_tables(_FIRST_GRID // 2, 4)
                 U, ok, steps = cls._doubling(fixed, rows, H.shape[-1], atol + rtol, max_steps)
                 if not ok.all():
                     if throw:
@@ -241,6 +395,13 @@ class Evolution:
                             f"{atol + rtol:.3g} ({int((~ok).sum())} of {rows} row(s)); raise max_steps or loosen "
                             "the tolerances")
                     U[~ok] = np.nan
+                if tracked and not steps:  # (throw=False and max_steps below the first grid: no grid was ever run)
+                    raise RuntimeError(
+                        f"evolve() inside a gradient trace: the solve failed before any grid ran (max_steps={max_steps} "
+                        f"is below the first grid of {_FIRST_GRID} steps), so there is no grid to differentiate; raise "
+                        "max_steps")
+                if tracked:  # the accepted grid once more, with its derivatives
+                    return with_jacobian(steps, 4, ~ok)
             return cls._operation(U, _has_batched(list(params) + span), wires, name,
                                   _tangent_state(list(params) + span), steps)
 

@@ -444,7 +444,7 @@ class Script:
     }
 
     def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums, skip_channels: bool = False,
-                            mat_ops: Optional[list] = None):
+                            mat_ops: Optional[list] = None, through_evolve: bool = False):
         """Record the tape with the ``argnums`` arguments as differentiable leaves.  Returns
         ``(tape, lowered tape, n_qubits, B, slots, leaf_shapes, batched)`` where ``slots`` lists
         ``(angle slot, shift rule, tangent terms)`` for every angle that depends on a leaf.
@@ -453,7 +453,9 @@ class Script:
         ``mat_ops``: a list that receives ``(index in the lowered tape's ops, operation)`` for every matrix gate
         whose matrix depends on a leaf through a known Jacobian (pulse leaves: ``wants_matrix_cotangent``); such a
         gate is then solved with its sensitivities here and does not count as "non-linear".  Only a caller that
-        asks the sweep for matrix cotangents passes it (:meth:`vjp`)."""
+        asks the sweep for matrix cotangents passes it (:meth:`vjp`).
+        ``through_evolve``: the tape is recorded inside ``evolution.gradient_trace()``, so that evolved gates whose
+        arguments depend on a leaf are solved with their Jacobian and want a matrix cotangent too."""
         kwargs = {} if kwargs is None else kwargs
         args = tuple(to_numpy(a) for a in args)
         batched = in_axes is not None
@@ -479,7 +481,13 @@ class Script:
                 wrapped.append(Batched(data, []))  # batched, but a constant for this gradient
             else:
                 wrapped.append(a)
-        tape = self._record_for_engine(*wrapped, **kwargs)
+        if through_evolve:
+            from . import evolution
+
+            with evolution.gradient_trace():
+                tape = self._record_for_engine(*wrapped, **kwargs)
+        else:
+            tape = self._record_for_engine(*wrapped, **kwargs)
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         gates = [o for o in tape if not isinstance(o, KrausChannel)] if skip_channels else tape
         if mat_ops is not None:  # U and dU/d(arguments) of every pulse leaf that depends on a leaf: one launch group
@@ -511,7 +519,7 @@ class Script:
 
     def vjp(self, obs: List[Operation], cotangent, *, args: tuple = (),
             kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
-            argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False):
+            argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False, through_evolve: bool = False):
         """Gradient of ``sum_k cotangent[b, k] * <obs_k>_b`` with respect to the array arguments
         ``argnums`` by ADJOINT differentiation: one backward sweep for all angles
         (:mod:`adjoint`).  ``obs``: at most 32 Z / Z-parity observables seed the sweep from their wire masks.
@@ -532,7 +540,15 @@ class Script:
         cotangents ``G`` beside the angle gradients, and ``2 Re sum_ac G[a][c] J[slot][a][c] coef`` is added for every
         ``(leaf, slot, index, coef)`` of ``leaf_jacobian_terms()``.  An argument the recorder lost track of raises
         ``NotImplementedError``; an evolved gate (a per-sample matrix that is no pulse leaf) on the tape raises
-        ``AdjointUnsupported``, as before."""
+        ``AdjointUnsupported``, as before -- unless ``through_evolve=True``.
+
+        ``through_evolve=True`` differentiates through ``Hermitian.evolve()`` / ``ParametrizedHamiltonian.evolve()``
+        gates in the same ONE sweep: the tape is recorded inside ``evolution.gradient_trace()``, every evolved gate
+        whose time, interval ends or coefficient parameters depend on a leaf is solved with the exact Jacobian of its
+        grid (``qmle_evolve_magnus_jac``) and contributes ``2 Re sum_ac G[a][c] dU[a][c]/d(leaf element)`` like a pulse
+        leaf; an evolved gate that is a constant for this gradient is just inverted by the sweep.  Evolved gates on one
+        and on two wires are served (2x2 and 4x4 cotangents from ``adjoint.adjoint_slot_and_matrices_gradient``);
+        Hamiltonians on more wires are refused by ``evolve()`` itself."""
         from . import adjoint
 
         if not obs:
@@ -545,13 +561,14 @@ class Script:
                 "H psi for sums of Pauli words (got " + ", ".join(kinds) + ")")
         mat_ops: list = []
         tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
-            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops)
+            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops, through_evolve=through_evolve)
         if any(isinstance(o, KrausChannel) for o in tape):
             raise adjoint.AdjointUnsupported("adjoint differentiation of noisy circuits")
-        for o in tape:  # evolved gates stay out of scope here: the sweep could invert one, nothing differentiates it
+        for o in tape:  # without through_evolve evolved gates stay out of scope: nothing differentiates one
             m = getattr(o, "_matrix", None)
-            if not isinstance(o, pulses.PulseRotation) and getattr(o, "_native", None) is None \
-                    and isinstance(m, np.ndarray) and m.ndim == 3:
+            per_sample = not isinstance(o, pulses.PulseRotation) and getattr(o, "_native", None) is None \
+                and isinstance(m, np.ndarray) and m.ndim == 3
+            if per_sample and not through_evolve:
                 raise adjoint.AdjointUnsupported(
                     f"no adjoint rule for {o.name} (MAT1_ROW / MAT2_ROW): a per-sample matrix that is not a pulse "
                     "leaf (an evolved unitary) has no generator and no Jacobian the sweep could differentiate")
@@ -577,17 +594,27 @@ class Script:
         for s_, _rule, _t, _name in slots:
             want[s_] = True
         grads = {k: np.zeros((K, B) + tuple(shp)) for k, shp in leaf_shapes.items()}
-        if mat_ops:  # angle slots and matrix cotangents from ONE sweep
+        # a per-sample matrix that nothing is asked of (an evolved gate that is a constant for this gradient) still
+        # needs the form of the reverse tape that inverts it
+        row_ops = through_evolve and any(name in ("MAT1_ROW", "MAT2_ROW") for name, _w, _s, _off in low.ops)
+        if mat_ops or (row_ops and slots):  # angle slots and matrix cotangents from ONE sweep
             want_mat = [False] * len(low.ops)
             for k_op, _o in mat_ops:
                 want_mat[k_op] = True
-            d, cot = adjoint.adjoint_slot_and_matrix_gradient(low, n_qubits, B, masks, w, want, want_mat, x64=x64,
-                                                              obs_terms=obs_terms)  # [K * B, n_mat, 2, 2]
-            cot = np.asarray(cot, dtype=np.complex128).reshape(K, B, len(mat_ops), 4)
+            if through_evolve:  # one [K * B, d, d] per flagged op, d = 2 or 4
+                d, cots = adjoint.adjoint_slot_and_matrices_gradient(low, n_qubits, B, masks, w, want, want_mat,
+                                                                     x64=x64, obs_terms=obs_terms)
+            else:
+                d, cot = adjoint.adjoint_slot_and_matrix_gradient(low, n_qubits, B, masks, w, want, want_mat, x64=x64,
+                                                                  obs_terms=obs_terms)  # [K * B, n_mat, 2, 2]
+                cots = [cot[:, m] for m in range(len(mat_ops))]
             for m, ((_k, o), terms) in enumerate(zip(mat_ops, mat_terms)):
-                jac = np.asarray(o.jacobian, dtype=np.complex128).reshape(-1, 5, 4)  # [B or 1, 5, 4]
-                # dC/d(slot) = 2 Re sum_ac G[a][c] dU[a][c]/d(slot)  -> [K, B, 5]
-                per_slot = 2.0 * np.real(np.einsum("kbe,bse->kbs", cot[:, :, m], np.broadcast_to(jac, (B, 5, 4))))
+                jac = np.asarray(o.jacobian, dtype=np.complex128)  # [B or 1, D, d, d]: D = 5 for a pulse leaf
+                jac = jac.reshape(jac.shape[0], jac.shape[1], -1)
+                g_m = np.asarray(cots[m], dtype=np.complex128).reshape(K, B, jac.shape[-1])  # (the op's own d * d)
+                # dC/d(slot) = 2 Re sum_ac G[a][c] dU[a][c]/d(slot)  -> [K, B, D]
+                per_slot = 2.0 * np.real(np.einsum("kbe,bse->kbs", g_m,
+                                                   np.broadcast_to(jac, (B,) + jac.shape[1:])))
                 for lid, slot, flat, coef in terms:
                     g = grads[lid].reshape(K, B, -1)
                     g[:, :, int(flat)] += per_slot[:, :, slot] * np.asarray(coef, dtype=np.float64).reshape(1, -1)
