@@ -1474,25 +1474,49 @@ def _wire_group_masks(wire_groups, n_qubits: int):
     return masks
 
 
-def _adjoint_gradient_pauli(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights, obs_terms, terms,
-                            n_grad_slots: int):
-    """The term-list form of :func:`adjoint_gradient` (rows already cut to the engine's limit)."""
+def _adjoint_sweep(name: str, fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights, wire_groups, obs_terms, terms,
+                   n_grad_slots: int, request=None, request_error: str = "", cot_shape=(), ws_args=()):
+    """What the adjoint entry points below share: the checks, the marshalling, the choice of precision, the buffers
+    and the call of ``qmle_adjoint_<name>`` / ``_f64`` (workspace: ``qmle_adjoint_<name>_workspace_bytes``).
+    ``request``: ``(one entry per reverse op, count or stride)`` of a cotangent form, whose functions take both seeds
+    (the absent one as NULL) and return ``cot_shape`` scalars per sample beside the gradient; None: a gradient alone,
+    from the function of its seed (``gradient`` with ``wire_groups``, ``gradient_pauli`` with ``obs_terms``)."""
     torch = require_gpu()
     f64 = weights.dtype == torch.float64
+    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
+        raise ValueError("the complex128 sweep takes float64 angle tables")
+    if (wire_groups is None) == (obs_terms is None):
+        raise ValueError("pass either wire_groups or obs_terms")
+    if weights.dim() != 2:
+        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
+    if request is not None and (len(request[0]) != len(terms) or request[1] < 1):
+        raise ValueError(request_error)
     B, n_obs = int(weights.shape[0]), int(weights.shape[1])
-    oarr, arr = pauli_term_array(obs_terms), _adjoint_term_array(terms)
-    fn, wsq, what = ((lib().qmle_adjoint_gradient_pauli_f64, lib().qmle_adjoint_pauli_workspace_bytes_f64,
-                      "qmle_adjoint_gradient_pauli_f64") if f64
-                     else (lib().qmle_adjoint_gradient_pauli, lib().qmle_adjoint_pauli_workspace_bytes,
-                           "qmle_adjoint_gradient_pauli"))
-    dev = weights.device
-    out = torch.empty((B, n_grad_slots), dtype=torch.float64 if f64 else torch.float32, device=dev)
-    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, len(obs_terms), n_obs))), dtype=torch.uint8, device=dev)
-    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
-             C.c_void_p(weights.data_ptr()), oarr, len(obs_terms), n_obs, arr, len(terms),
-             C.c_void_p(out.data_ptr()), int(n_grad_slots), C.c_void_p(ws.data_ptr()),
-             C.c_size_t(ws.numel()), _stream_ptr()), what)
-    return out
+    if wire_groups is not None and n_obs != len(wire_groups):
+        raise ValueError(f"weights must be [B, {len(wire_groups)}], got {tuple(weights.shape)}")
+    masks = _wire_group_masks(wire_groups, fwd.n_qubits) if wire_groups is not None else None
+    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
+    n_ot = len(obs_terms) if obs_terms is not None else 0
+    if request is not None:
+        seed, ws_seed, ws_name = (masks, oarr, n_ot, n_obs), (n_ot, n_obs), name + "_"
+        req = ((C.c_int32 * len(request[0]))(*[int(m) for m in request[0]]), int(request[1]))
+    elif wire_groups is not None:
+        seed, ws_seed, ws_name, req = (masks, n_obs), (), "", ()
+    else:
+        name, seed, ws_seed, ws_name, req = name + "_pauli", (oarr, n_ot, n_obs), (n_ot, n_obs), "pauli_", ()
+    suffix = "_f64" if f64 else ""
+    what, wsq = "qmle_adjoint_" + name + suffix, getattr(lib(), "qmle_adjoint_" + ws_name + "workspace_bytes" + suffix)
+    ft, dev = torch.float64 if f64 else torch.float32, weights.device
+    out = torch.empty((B, n_grad_slots), dtype=ft, device=dev)
+    cot = torch.empty((B, *cot_shape), dtype=ft, device=dev) if request is not None else None
+    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, *ws_seed, *ws_args))), dtype=torch.uint8, device=dev)
+    arr = _adjoint_term_array(terms)
+    check(getattr(lib(), what)(
+        fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
+        C.c_void_p(weights.data_ptr()), *seed, arr, len(terms), C.c_void_p(out.data_ptr()), int(n_grad_slots), *req,
+        *((C.c_void_p(cot.data_ptr()),) if cot is not None else ()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+        _stream_ptr()), what)
+    return out, cot
 
 
 @_row_chunked(2, 3, 4, max_rows=32767)  # (psi and lambda of a sample share a launch: 2 B <= 65535)
@@ -1505,40 +1529,8 @@ def adjoint_gradient(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
     (``qmle_adjoint_gradient_pauli`` / ``_f64``; the columns are those of ``weights``).
     ``terms``: one ``(out_slot, x_wires, z_wires, proj_wires, n_y, coef, marks_off)`` per op of
     ``rev`` (the reversed, daggered NO_FUSION plan)."""
-    torch = require_gpu()
-    f64 = weights.dtype == torch.float64
-    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
-        raise ValueError("the complex128 sweep takes float64 angle tables")
-    if (wire_groups is None) == (obs_terms is None):
-        raise ValueError("pass either wire_groups or obs_terms")
-    if weights.dim() != 2:
-        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
-    if wire_groups is None:
-        return _adjoint_gradient_pauli(fwd, rev, angles_fwd, angles_rev, weights, obs_terms, terms, n_grad_slots)
-    B, n_obs = int(weights.shape[0]), len(wire_groups)
-    if weights.shape[1] != n_obs:
-        raise ValueError(f"weights must be [B, {n_obs}], got {tuple(weights.shape)}")
-    masks = _wire_group_masks(wire_groups, fwd.n_qubits)
-    arr = _adjoint_term_array(terms)
-    dev = weights.device
-    if f64:
-        out = torch.empty((B, n_grad_slots), dtype=torch.float64, device=dev)
-        ws = torch.empty(lib().qmle_adjoint_workspace_bytes_f64(fwd._h, rev._h, B), dtype=torch.uint8, device=dev)
-        check(lib().qmle_adjoint_gradient_f64(
-            fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
-            C.c_void_p(weights.data_ptr()), masks, n_obs, arr, len(terms),
-            C.c_void_p(out.data_ptr()), int(n_grad_slots), C.c_void_p(ws.data_ptr()),
-            C.c_size_t(ws.numel()), _stream_ptr()), "qmle_adjoint_gradient_f64")
-        return out
-    out = torch.empty((B, n_grad_slots), dtype=torch.float32, device=dev)
-    ws = torch.empty(lib().qmle_adjoint_workspace_bytes(fwd._h, rev._h, B), dtype=torch.uint8,
-                     device=dev)
-    check(lib().qmle_adjoint_gradient(
-        fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
-        C.c_void_p(weights.data_ptr()), masks, n_obs, arr, len(terms),
-        C.c_void_p(out.data_ptr()), int(n_grad_slots), C.c_void_p(ws.data_ptr()),
-        C.c_size_t(ws.numel()), _stream_ptr()), "qmle_adjoint_gradient")
-    return out
+    return _adjoint_sweep("gradient", fwd, rev, angles_fwd, angles_rev, weights, wire_groups, obs_terms, terms,
+                          n_grad_slots)[0]
 
 
 @_row_chunked(2, 3, 4, max_rows=32767)
@@ -1551,38 +1543,11 @@ def adjoint_cotangent(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
     ``G[b, k, a, c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` on the states in front of the gate, so that
     ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  Seeds and precisions as for :func:`adjoint_gradient`; a
     ``rev`` plan compiled for fused tile passes raises :class:`Unsupported` unless the sweep runs in LDS."""
-    torch = require_gpu()
-    f64 = weights.dtype == torch.float64
-    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
-        raise ValueError("the complex128 sweep takes float64 angle tables")
-    if (wire_groups is None) == (obs_terms is None):
-        raise ValueError("pass either wire_groups or obs_terms")
-    if weights.dim() != 2:
-        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
-    if len(mat_out) != len(terms) or n_mat < 1:
-        raise ValueError("mat_out holds one entry per reverse op, and at least one matrix is asked for")
-    B, n_obs = int(weights.shape[0]), int(weights.shape[1])
-    if wire_groups is not None and n_obs != len(wire_groups):
-        raise ValueError(f"weights must be [B, {len(wire_groups)}], got {tuple(weights.shape)}")
-    masks = _wire_group_masks(wire_groups, fwd.n_qubits) if wire_groups is not None else None
-    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
-    n_ot = len(obs_terms) if obs_terms is not None else 0
-    arr = _adjoint_term_array(terms)
-    marr = (C.c_int32 * len(mat_out))(*[int(m) for m in mat_out])
-    fn, wsq, what = ((lib().qmle_adjoint_cotangent_f64, lib().qmle_adjoint_cotangent_workspace_bytes_f64,
-                      "qmle_adjoint_cotangent_f64") if f64
-                     else (lib().qmle_adjoint_cotangent, lib().qmle_adjoint_cotangent_workspace_bytes,
-                           "qmle_adjoint_cotangent"))
-    dev = weights.device
-    ft = torch.float64 if f64 else torch.float32
-    out = torch.empty((B, n_grad_slots), dtype=ft, device=dev)
-    cot = torch.empty((B, int(n_mat), 2, 2, 2), dtype=ft, device=dev)
-    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, n_ot, n_obs))), dtype=torch.uint8, device=dev)
-    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
-             C.c_void_p(weights.data_ptr()), masks, oarr, n_ot, n_obs, arr, len(terms),
-             C.c_void_p(out.data_ptr()), int(n_grad_slots), marr, int(n_mat), C.c_void_p(cot.data_ptr()),
-             C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
-    return out, torch.view_as_complex(cot)
+    out, cot = _adjoint_sweep(
+        "cotangent", fwd, rev, angles_fwd, angles_rev, weights, wire_groups, obs_terms, terms, n_grad_slots,
+        (mat_out, n_mat), "mat_out holds one entry per reverse op, and at least one matrix is asked for",
+        (int(n_mat), 2, 2, 2))
+    return out, require_gpu().view_as_complex(cot)
 
 
 @_row_chunked(2, 3, 4, max_rows=32767)
@@ -1595,36 +1560,8 @@ def adjoint_cotangent_at(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
     ``two_wire``: a 32-scalar block is among them (sizes the workspace).  -> ``(grad [B, n_grad_slots],
     rows [B, cot_stride])`` real; block ``[d][d][re, im]`` holds ``G`` with
     ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta`` in the index convention of the gate's own matrix."""
-    torch = require_gpu()
-    f64 = weights.dtype == torch.float64
-    if f64 and (angles_fwd.dtype != torch.float64 or angles_rev.dtype != torch.float64):
-        raise ValueError("the complex128 sweep takes float64 angle tables")
-    if (wire_groups is None) == (obs_terms is None):
-        raise ValueError("pass either wire_groups or obs_terms")
-    if weights.dim() != 2:
-        raise ValueError(f"weights must be [B, n_obs], got {tuple(weights.shape)}")
-    if len(cot_off) != len(terms) or cot_stride < 1:
-        raise ValueError("cot_off holds one entry per reverse op, and the row holds at least one block")
-    B, n_obs = int(weights.shape[0]), int(weights.shape[1])
-    if wire_groups is not None and n_obs != len(wire_groups):
-        raise ValueError(f"weights must be [B, {len(wire_groups)}], got {tuple(weights.shape)}")
-    masks = _wire_group_masks(wire_groups, fwd.n_qubits) if wire_groups is not None else None
-    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
-    n_ot = len(obs_terms) if obs_terms is not None else 0
-    arr = _adjoint_term_array(terms)
-    carr = (C.c_int32 * len(cot_off))(*[int(m) for m in cot_off])
-    fn, wsq, what = ((lib().qmle_adjoint_cotangent_at_f64, lib().qmle_adjoint_cotangent_at_workspace_bytes_f64,
-                      "qmle_adjoint_cotangent_at_f64") if f64
-                     else (lib().qmle_adjoint_cotangent_at, lib().qmle_adjoint_cotangent_at_workspace_bytes,
-                           "qmle_adjoint_cotangent_at"))
-    dev = weights.device
-    ft = torch.float64 if f64 else torch.float32
-    out = torch.empty((B, n_grad_slots), dtype=ft, device=dev)
-    cot = torch.empty((B, int(cot_stride)), dtype=ft, device=dev)
-    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, n_ot, n_obs, int(bool(two_wire))))), dtype=torch.uint8,
-                     device=dev)
-    check(fn(fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B,
-             C.c_void_p(weights.data_ptr()), masks, oarr, n_ot, n_obs, arr, len(terms),
-             C.c_void_p(out.data_ptr()), int(n_grad_slots), carr, int(cot_stride), C.c_void_p(cot.data_ptr()),
-             C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
-    return out, cot
+    return _adjoint_sweep(
+        "cotangent_at", fwd, rev, angles_fwd, angles_rev, weights, wire_groups, obs_terms, terms, n_grad_slots,
+        (cot_off, cot_stride), "cot_off holds one entry per reverse op, and the row holds at least one block",
+        (int(cot_stride),), (int(bool(two_wire)),))
+

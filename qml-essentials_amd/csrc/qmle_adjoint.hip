@@ -1,5 +1,8 @@
-// libqmle_sv, adjoint differentiation: the whole sweep in LDS (n <= 13), fused tile passes over
-// psi and lambda (n >= 14), per-gate streaming overlaps, and qmle_adjoint_gradient.
+// libqmle_sv, adjoint differentiation in complex64.  adjoint_run checks a call, lays out its workspace and takes one
+// of three routes: the whole sweep in LDS (n <= 13, adj_run_lds), or the forward run and the seed followed by the
+// reverse plan's stages (adj_run_stages) -- fused tile passes over psi and lambda (n >= 14, tables from
+// adj_fused_tables) or one streaming overlap per gate.  The kernels, checks, launch pairs and entry-point bodies that
+// the complex128 sweep of qmle_f64.hip has too sit in qmle_adjoint_dev.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +17,7 @@
 #include "qmle_internal.h"
 #include "qmle_host.h"
 #include "qmle_dev.h"
+#include "qmle_adjoint_dev.h"
 #include "qmle_tile_dev.h"
 
 namespace {
@@ -44,7 +48,7 @@ struct AdjLdsArgs {
   const float *rev_consts;
   const float *weights;          // [B][n_obs]
   union {                        // the seed: Z-parity masks, or <PAULI> words and their coefficient rows
-    uint32_t zmask[QMLE_MAX_QUBITS];
+    ZMasks z;
     struct {
       const PauliWordDev *words;
       const float *coef;         // [B][n_words]
@@ -57,15 +61,6 @@ struct AdjLdsArgs {
   float *cot;                    // [B][cot_stride] matrix cotangents (blocks of 8 or 32 floats), or nullptr
   int cot_stride;
 };
-
-// m[(a * 2 + c) * 2 + {0, 1}] += conj(l_a) p_c for the pair (l0, l1), (p0, p1) of one value of the other wires
-template <class T, class V>
-__device__ __forceinline__ void cot_accumulate(T (&m)[8], const V l0, const V l1, const V p0, const V p1) {
-  m[0] += l0.x * p0.x + l0.y * p0.y; m[1] += l0.x * p0.y - l0.y * p0.x;
-  m[2] += l0.x * p1.x + l0.y * p1.y; m[3] += l0.x * p1.y - l0.y * p1.x;
-  m[4] += l1.x * p0.x + l1.y * p0.y; m[5] += l1.x * p0.y - l1.y * p0.x;
-  m[6] += l1.x * p1.x + l1.y * p1.y; m[7] += l1.x * p1.y - l1.y * p1.x;
-}
 
 // eight per-thread sums -> their workgroup totals, valid in thread 0; `red`: eight floats per wave
 __device__ __forceinline__ void block_sum8(float (&m)[8], float *red) {
@@ -127,7 +122,7 @@ __global__ void k_adjoint_lds(const AdjLdsArgs a) {
     const float *w = a.weights + (size_t)b * a.n_obs;
     for (uint32_t i = tid; i < cnt; i += nt) {
       float d = 0.f;
-      for (int o = 0; o < a.n_obs; ++o) d += (__popc(i & a.zmask[o]) & 1) ? -w[o] : w[o];
+      for (int o = 0; o < a.n_obs; ++o) d += (__popc(i & a.z.mask[o]) & 1) ? -w[o] : w[o];
       const float2 v = psi[sw(i)];
       lam[sw(i)] = make_float2(d * v.x, d * v.y);
     }
@@ -151,11 +146,7 @@ __global__ void k_adjoint_lds(const AdjLdsArgs a) {
       }
       const float sr = block_sum(re, red);
       const float si = block_sum(im, red);
-      if (tid == 0) {
-        const int q = t.n_y & 3;
-        const float v = q == 0 ? si : q == 1 ? sr : q == 2 ? -si : -sr;
-        a.grad[(size_t)b * a.n_grad_slots + t.out_slot] = t.coef * v;
-      }
+      if (tid == 0) a.grad[(size_t)b * a.n_grad_slots + t.out_slot] = t.coef * adj_phase(t.n_y, sr, si);
     }
     const LoweredOp o = a.rev_ops[r];
     if (t.cot_off >= 0 && o.kind == LK_1Q) {  // a one-wire matrix gate: all eight numbers from one read of both
@@ -356,22 +347,18 @@ k_adj_tile_final(const float *__restrict__ partial, int n_tiles, int n_terms,
 }
 
 // ---- adjoint differentiation -------------------------------------------------------------
-struct ZSumArgs {
-  uint32_t mask[QMLE_MAX_QUBITS];  // bit-position parity masks
-  int n_obs;
-};
 // lambda[b][i] = (sum_k w[b][k] (-1)^{|i & mask_k|}) psi[b][i]
 __global__ void __launch_bounds__(256)
 k_zsum_apply(const float4 *__restrict__ psi, float4 *__restrict__ lam, int n,
-             const float *__restrict__ weights, ZSumArgs z) {
+             const float *__restrict__ weights, ZMasks z, int n_obs) {
   const int b = blockIdx.y;
   const uint64_t chunks = (uint64_t)1 << (n - 1);
-  const float *w = weights + (size_t)b * z.n_obs;
+  const float *w = weights + (size_t)b * n_obs;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < chunks; k += stride) {
     const uint32_t i0 = (uint32_t)(k << 1);
     float d0 = 0.f, d1 = 0.f;
-    for (int o = 0; o < z.n_obs; ++o) {
+    for (int o = 0; o < n_obs; ++o) {
       const float wk = w[o];
       d0 += (__popc(i0 & z.mask[o]) & 1) ? -wk : wk;
       d1 += (__popc((i0 | 1u) & z.mask[o]) & 1) ? -wk : wk;
@@ -381,14 +368,10 @@ k_zsum_apply(const float4 *__restrict__ psi, float4 *__restrict__ lam, int n,
   }
 }
 
-struct AdjTerm {
-  uint32_t xmask, zmask, pmask;  // bit positions: flipped / sign / projected onto 1
-  const float *marks;            // != nullptr: G = diag(marks)
-};
-// partial[b][block] = sum_i conj(lambda_i) (X^x Z^z Pi_p psi)_i   (phase i^n_y applied later)
+// partial[b][block] = sum_i conj(lambda_i) (X^x Z^z Pi_p psi)_i   (the phase i^n_y is applied by k_adj_final)
 __global__ void __launch_bounds__(256)
 k_adj_overlap(const float4 *__restrict__ psi_all, const float4 *__restrict__ lam_all, int n,
-              AdjTerm t, float2 *__restrict__ partial) {
+              AdjTerm<float> t, float2 *__restrict__ partial) {
   __shared__ float red[16];
   const int b = blockIdx.y;
   const uint64_t chunks = (uint64_t)1 << (n - 1);
@@ -421,26 +404,6 @@ k_adj_overlap(const float4 *__restrict__ psi_all, const float4 *__restrict__ lam
   const float r = block_sum(re, red);
   const float i = block_sum(im, red);
   if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = make_float2(r, i);
-}
-// grad[b][slot] = coef * Im(i^n_y * sum)
-__global__ void __launch_bounds__(256)
-k_adj_final(const float2 *__restrict__ partial, int n_blocks, int n_y, float coef,
-            float *__restrict__ grad, int n_grad_slots, int slot) {
-  __shared__ double red[16];
-  const int b = blockIdx.x;
-  double re = 0.0, im = 0.0;
-  for (int k = threadIdx.x; k < n_blocks; k += blockDim.x) {
-    const float2 v = partial[(size_t)b * n_blocks + k];
-    re += v.x;
-    im += v.y;
-  }
-  const double r = block_sum_d(re, red);
-  const double i = block_sum_d(im, red);
-  if (threadIdx.x == 0) {
-    const int q = n_y & 3;
-    const double v = q == 0 ? i : q == 1 ? r : q == 2 ? -i : -r;
-    grad[(size_t)b * n_grad_slots + slot] = (float)(coef * v);
-  }
 }
 
 // The 2x2 moment of a one-wire matrix gate on bit position t: partial[b][block][a * 2 + c] = sum_rest conj(lambda[a,
@@ -487,31 +450,10 @@ k_adj_moment(const float4 *__restrict__ psi_all, const float4 *__restrict__ lam_
     partial[((size_t)b * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = make_float2(re, im);
   }
 }
-// cot[b][k] = (sum_blocks partial[b][block]) (U^+)^T, summed in double; U^+ = the reverse op's matrix of sample b
-__global__ void __launch_bounds__(256)
-k_adj_cot_final(const float2 *__restrict__ partial, int n_blocks, const float *__restrict__ mats, uint32_t mat_floats,
-                uint32_t mat_off, float *__restrict__ cot, int cot_stride, int cot_off) {
-  __shared__ double red[16];
-  const int b = blockIdx.x;
-  double m[8];
-  for (int e = 0; e < 4; ++e) {
-    double re = 0.0, im = 0.0;
-    for (int k = threadIdx.x; k < n_blocks; k += blockDim.x) {
-      const float2 v = partial[((size_t)b * n_blocks + k) * 4 + e];
-      re += v.x;
-      im += v.y;
-    }
-    m[2 * e] = block_sum_d(re, red);
-    m[2 * e + 1] = block_sum_d(im, red);
-  }
-  if (threadIdx.x == 0) {
-    cot_finish<2>(m, mats + (size_t)b * mat_floats + mat_off, cot + (size_t)b * cot_stride + cot_off);
-  }
-}
 
 }  // namespace
 
-// ---- adjoint gradient ------------------------------------------------------------------------
+// ---- adjoint gradient: the workspace ---------------------------------------------------------------------------
 static int adj_blocks(int n) {
   const uint64_t chunks = (uint64_t)1 << (n - 1);
   uint64_t b = (chunks + 256 * 8 - 1) / (256 * 8);
@@ -520,7 +462,7 @@ static int adj_blocks(int n) {
   return (int)b;
 }
 struct AdjLayout { size_t states, lam, mats, ang2, partial, fwd_ws, lds_ops, lds_terms, lds_fmats, tile_partial, total; };
-// cot: complex partials per block -- 1, or 4 with one-wire matrix cotangents, or 16 with a two-wire one among them
+// cot: complex partials per block (cot_partials)
 static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batch, int cot = 1) {
   AdjLayout L;
   const size_t sb = (size_t)batch * ((size_t)8 << fwd->n);
@@ -544,337 +486,351 @@ static AdjLayout adj_layout(const qmle_plan *fwd, const qmle_plan *rev, int batc
   return L;
 }
 
-// The observables of a sweep: Z-parity wire masks (qmle_adjoint_gradient) or a list of weighted Pauli words
-// (qmle_adjoint_gradient_pauli: obs_terms != nullptr, checked by the caller); the sweeps differ in the seed alone.
-struct AdjObs {
-  const uint32_t *wire_masks;
-  const qmle_pauli_term *obs_terms;
-  int n_obs_terms, n_obs;
-};
-struct SeedHold {  // ends the seed's host plan on every way out
-  PauliSeed *sd = nullptr;
-  ~SeedHold() { pauli_seed_end(sd); }
-};
-
-static int adjoint_run(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
-                       const float *d_angles_rev, int batch, const float *d_weights, const AdjObs &obs,
-                       const qmle_adjoint_term *terms, int n_terms, float *d_grad,
-                       int n_grad_slots, void *d_workspace, size_t workspace_bytes,
-                       qmle_stream stream_, const CotRequest &cot = {nullptr, 0, nullptr}) {
-  const uint32_t *obs_wire_masks = obs.wire_masks;
-  const int n_obs = obs.n_obs;
-  const bool pauli = obs.obs_terms != nullptr;
-  if (!fwd || !rev || batch < 1 || 2 * batch > kMaxGridY || !d_weights || (!pauli && !obs_wire_masks) ||
-      n_obs < 1 || (!pauli && n_obs > QMLE_MAX_QUBITS) || !terms || !d_grad || n_grad_slots < 1 ||
-      !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
-    return QMLE_ERR_INVALID_ARG;
-  if ((fwd->n_slots > 0 && !d_angles_fwd) || (rev->n_slots > 0 && !d_angles_rev))
-    return QMLE_ERR_INVALID_ARG;
-  // (the sweep applies stages to LIVE states: a schedule compiled for runs from |0..0> only is refused)
-  if ((fwd->flags | rev->flags) & QMLE_PLAN_INTERNAL_ZERO_RUN) return QMLE_ERR_UNSUPPORTED;
-  const int n = fwd->n;
-  // rev is either a NO_FUSION plan (one streaming pass per gate) or a NO_MERGE plan (fused tile
-  // passes); both keep one source gate per lowered operator
-  const bool fused = (rev->flags & QMLE_PLAN_NO_MERGE) && !(rev->flags & QMLE_PLAN_NO_FUSION);
-  if (!fused)
-    for (const Stage &st : rev->stages)
-      if (st.src_ops.size() != 1) return QMLE_ERR_INVALID_ARG;
-  for (const auto &srcs : rev->lowered_src)
-    if (srcs.size() != 1) return QMLE_ERR_INVALID_ARG;
-  hipStream_t stream = (hipStream_t)stream_;
-  const bool want_cot = cot.off != nullptr;
-  float *const d_cot = (float *)cot.d_cot;
+// A checked call on its way through a route: the aligned workspace and its layout, the Z seed's position masks, the
+// lowered operator of every reverse op of a cotangent request.
+struct AdjCtx {
+  const AdjCall<float> &c;
+  char *ws;
+  size_t ws_bytes;
+  AdjLayout L;
+  ZMasks z;
   std::vector<int> low_of;
-  int rc = want_cot ? cot_request_check(rev, cot, low_of) : QMLE_OK;  // (host only: before any device work)
-  if (rc != QMLE_OK) return rc;
-  rc = ensure_device_plan(rev);
-  if (rc != QMLE_OK) return rc;
-  char *ws = (char *)d_workspace;
-  const AdjLayout L = adj_layout(fwd, rev, batch, !want_cot ? 1 : cot_has_two_wire(rev, cot.off) ? 16 : 4);
-  if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
-  for (int k = 0; !pauli && k < n_obs; ++k)
-    if (!valid_wire_mask(obs_wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
-  for (int r = 0; r < n_terms; ++r)
-    if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
-  // the seed's tables: behind everything the Z sweep lays out
-  char *seed_ws = ws + L.total;
-  const size_t seed_bytes = workspace_bytes - L.total;
-  if (pauli && seed_bytes < pauli_seed_ws_bytes(batch, obs.n_obs_terms, false)) return QMLE_ERR_WORKSPACE;
-  SeedHold seed;
-
-  // ---- n <= 13: psi and lambda both fit in one workgroup's LDS -> a single launch ----------
-  bool lds_ok = fwd->whole_state_lds && n <= 13 && fwd->stages.size() == 1;
-  for (const LoweredOp &o : rev->lowered) lds_ok = lds_ok && o.kind != LK_4Q;
-  if (lds_ok) {
-    rc = ensure_device_plan(fwd);
-    if (rc != QMLE_OK) return rc;
-    const Stage &fst = fwd->stages[0];
-    const int R = (int)rev->lowered.size();
-    std::vector<AdjTermDev> tdev((size_t)(R ? R : 1));
-    for (int r = 0; r < R; ++r) {
-      if (rev->lowered_src[r].size() != 1) return QMLE_ERR_INVALID_ARG;
-      const qmle_adjoint_term &t = terms[rev->lowered_src[r][0]];
-      AdjTermDev &d = tdev[r];
-      d.out_slot = t.out_slot;
-      d.xmask = wires_to_pos(t.x_wires, n);
-      d.zmask = wires_to_pos(t.z_wires, n);
-      d.pmask = wires_to_pos(t.proj_wires, n);
-      d.n_y = t.n_y;
-      d.coef = t.coef;
-      d.marks_off = t.marks_off;
-      d.cot_off = want_cot ? cot.off[rev->lowered_src[r][0]] : -1;
-      if (t.marks_off >= 0 && (size_t)t.marks_off + ((size_t)1 << n) > rev->consts.size())
-        return QMLE_ERR_INVALID_ARG;
-    }
-    // reverse tape + terms live in a blob owned by the reverse plan (uploaded when they change)
-    const uint64_t hsh = fnv1a(tdev.data(), tdev.size() * sizeof(AdjTermDev)) ^ ((uint64_t)R * 0x9E3779B97F4A7C15ull);
-    const size_t ops_b = align_up((size_t)(R ? R : 1) * sizeof(LoweredOp), 256);
-    if (!rev->adj_blob || rev->adj_hash != hsh) {
-      if (rev->adj_blob) (void)hipFree(rev->adj_blob);
-      rev->adj_blob = nullptr;
-      HIPCHK(hipMalloc(&rev->adj_blob, ops_b + (size_t)(R ? R : 1) * sizeof(AdjTermDev)));
-      if (R) {
-        HIPCHK(hipMemcpy(rev->adj_blob, rev->lowered.data(), (size_t)R * sizeof(LoweredOp),
-                         hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((char *)rev->adj_blob + ops_b, tdev.data(), (size_t)R * sizeof(AdjTermDev),
-                         hipMemcpyHostToDevice));
-      }
-      rev->adj_hash = hsh;
-    }
-    LoweredOp *d_rops = (LoweredOp *)rev->adj_blob;
-    AdjTermDev *d_terms = (AdjTermDev *)((char *)rev->adj_blob + ops_b);
-    float *fmats = (float *)(ws + L.lds_fmats);
-    float *rmats = (float *)(ws + L.mats);
-    HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(float), stream));
-    if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(float), stream));
-    rc = launch_build_matrices(fwd, d_angles_fwd, fmats, batch, stream);
-    if (rc == QMLE_OK) rc = launch_build_matrices(rev, d_angles_rev, rmats, batch, stream);
-    if (rc != QMLE_OK) return rc;
-    AdjLdsArgs a;
-    a.fwd = fill_tile_args(fwd, fst, nullptr, fmats, d_angles_fwd, true, TM_STORE, nullptr,
-                           nullptr, 0);
-    const size_t lds_base = ((size_t)16 << n) + 288 * sizeof(float);
-    a.fwd.slots_in_lds = lds_base + (size_t)a.fwd.n_ops * sizeof(OpSlot) <= 160 * 1024 ? 1 : 0;
-    const size_t lds = lds_base + (a.fwd.slots_in_lds ? (size_t)a.fwd.n_ops * sizeof(OpSlot) : 0);
-    a.rev_ops = d_rops;
-    a.terms = d_terms;
-    a.n_rev = R;
-    a.rev_mats = rmats;
-    a.rev_mat_floats = rev->mat_floats;
-    a.rev_angles = d_angles_rev;
-    a.rev_n_slots = rev->n_slots;
-    a.rev_consts = rev->dev.d_consts;
-    a.weights = d_weights;
-    a.n_obs = n_obs;
-    if (pauli) {  // word table and coefficient rows from global memory; the coefficient kernel runs first
-      rc = pauli_seed_begin(&seed.sd, n, batch, obs.obs_terms, obs.n_obs_terms, n_obs, false, true, seed_ws,
-                            seed_bytes, stream);
-      if (rc == QMLE_OK) rc = pauli_seed_flat(seed.sd, batch, d_weights, stream, &a.pw.words, &a.pw.coef, &a.pw.n_words);
-      if (rc != QMLE_OK) return rc;
-    } else {
-      for (int k = 0; k < n_obs; ++k) a.zmask[k] = wires_to_pos(obs_wire_masks[k], n);
-    }
-    a.grad = d_grad;
-    a.n_grad_slots = n_grad_slots;
-    a.cot = d_cot;
-    a.cot_stride = cot.stride;
-    if (FirstUse once{3}; once.first) {
-      for (const void *k : {(const void *)k_adjoint_lds<false, false>, (const void *)k_adjoint_lds<true, false>,
-                            (const void *)k_adjoint_lds<false, true>, (const void *)k_adjoint_lds<true, true>})
-        HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      once.done();
-    }
-    bool has_dense4 = false;
-    for (int g = fst.grp_begin; g < fst.grp_end; ++g) has_dense4 |= fwd->op_groups[g].kind == GK_DENSE4 || fwd->op_groups[g].kind == GK_REG4X;
-    // all loops are strided, so the sweeps may use more threads than the 2^(n-4) register-tile
-    // work items of the forward groups: one 64-lane wave per 256 amplitudes, at least 4 waves
-    int threads = tile_threads(n);
-    if (threads < 256 && n >= 8) threads = 256;
-    auto *kernel = pauli ? (has_dense4 ? k_adjoint_lds<true, true> : k_adjoint_lds<false, true>)
-                         : (has_dense4 ? k_adjoint_lds<true, false> : k_adjoint_lds<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(1, batch), dim3(threads), lds, stream, a);
-    HIPCHK(hipGetLastError());
+  bool pauli() const { return c.obs.obs_terms != nullptr; }
+  bool want_cot() const { return c.cot.off != nullptr; }
+  hipStream_t stream() const { return (hipStream_t)c.stream; }
+  // the Pauli seed's tables: behind everything the Z sweep lays out
+  int seed_begin(SeedHold &seed, bool flat) const {
+    return pauli_seed_begin(&seed.sd, c.fwd->n, c.batch, c.obs.obs_terms, c.obs.n_obs_terms, c.obs.n_obs, false, flat,
+                            ws + L.total, ws_bytes - L.total, stream());
+  }
+  int zero_outputs() const {
+    HIPCHK(hipMemsetAsync(c.d_grad, 0, (size_t)c.batch * c.n_grad_slots * sizeof(float), stream()));
+    if (want_cot()) HIPCHK(hipMemsetAsync(c.cot.d_cot, 0, (size_t)c.batch * c.cot.stride * sizeof(float), stream()));
     return QMLE_OK;
   }
-  if (n < 3) return QMLE_ERR_UNSUPPORTED;  // the per-gate streaming kernels move float4 pairs
-  // the fused tile pass takes generator overlaps only: said here, not by skipping the request (the caller falls
-  // back to one streaming pass per gate)
-  if (fused && want_cot) return QMLE_ERR_UNSUPPORTED;
-  float2 *psi = (float2 *)(ws + L.states);
-  float2 *lam = (float2 *)(ws + L.lam);
-  float *mats = (float *)(ws + L.mats);
-  float *ang2 = (float *)(ws + L.ang2);
-  float2 *partial = (float2 *)(ws + L.partial);
-  const size_t D = (size_t)1 << n;
+};
 
-  // forward: psi = U_N .. U_1 |0>
-  rc = run_batch_masks(fwd, d_angles_fwd, batch, QMLE_MEAS_STATE, nullptr, 0, psi, ws + L.fwd_ws,
-                       workspace_bytes - L.fwd_ws, stream);
+// Tables a route keeps on the reverse plan: uploaded when their hash `want` differs from the one stored with the
+// blob.  A failed upload leaves no blob behind, so the next call uploads again.
+struct BlobPiece {
+  size_t off;
+  const void *src;
+  size_t bytes;
+};
+static int upload_cached(void *&blob, uint64_t &hash, uint64_t want, size_t total, std::initializer_list<BlobPiece> pieces) {
+  if (blob && hash == want) return QMLE_OK;
+  if (blob) (void)hipFree(blob);
+  blob = nullptr;
+  hipError_t err = hipMalloc(&blob, total);
+  for (const BlobPiece &p : pieces)
+    if (err == hipSuccess && p.bytes) err = hipMemcpy((char *)blob + p.off, p.src, p.bytes, hipMemcpyHostToDevice);
+  if (err != hipSuccess) {
+    if (blob) (void)hipFree(blob);
+    blob = nullptr;
+    g_last_hip_error = (int)err;
+    return QMLE_ERR_HIP;
+  }
+  hash = want;
+  return QMLE_OK;
+}
+
+// ---- route 1, n <= 13: psi and lambda both fit in one workgroup's LDS -> a single launch ------------------------
+static bool adj_lds_route(const qmle_plan *fwd, const qmle_plan *rev) {
+  bool ok = fwd->whole_state_lds && fwd->n <= 13 && fwd->stages.size() == 1;
+  for (const LoweredOp &o : rev->lowered) ok = ok && o.kind != LK_4Q;
+  return ok;
+}
+// the reverse tape and its terms, in a blob owned by the reverse plan
+static int adj_lds_tables(const AdjCtx &x, const LoweredOp **d_rops, const AdjTermDev **d_terms) {
+  const AdjCall<float> &c = x.c;
+  qmle_plan *rev = c.rev;
+  const int n = rev->n, R = (int)rev->lowered.size();
+  std::vector<AdjTermDev> tdev((size_t)(R ? R : 1));
+  for (int r = 0; r < R; ++r) {
+    const int src = rev->lowered_src[r][0];  // (one per operator: adj_check_one_source)
+    const qmle_adjoint_term &t = c.terms[src];
+    if (!adj_marks_in_bounds(t, n, rev->consts.size())) return QMLE_ERR_INVALID_ARG;
+    tdev[r] = {t.out_slot, wires_to_pos(t.x_wires, n), wires_to_pos(t.z_wires, n), wires_to_pos(t.proj_wires, n),
+               t.n_y,      t.coef,                     t.marks_off,                 x.want_cot() ? c.cot.off[src] : -1};
+  }
+  const uint64_t hsh = fnv1a(tdev.data(), tdev.size() * sizeof(AdjTermDev)) ^ ((uint64_t)R * 0x9E3779B97F4A7C15ull);
+  const size_t ops_b = align_up((size_t)(R ? R : 1) * sizeof(LoweredOp), 256);
+  const int rc = upload_cached(rev->adj_blob, rev->adj_hash, hsh, ops_b + tdev.size() * sizeof(AdjTermDev),
+                               {{0, rev->lowered.data(), (size_t)R * sizeof(LoweredOp)},
+                                {ops_b, tdev.data(), (size_t)R * sizeof(AdjTermDev)}});
+  *d_rops = (const LoweredOp *)rev->adj_blob;
+  *d_terms = (const AdjTermDev *)((char *)rev->adj_blob + ops_b);
+  return rc;
+}
+static int adj_run_lds(const AdjCtx &x) {
+  const AdjCall<float> &c = x.c;
+  qmle_plan *fwd = c.fwd, *rev = c.rev;
+  const int n = fwd->n;
+  int rc = ensure_device_plan(fwd);
   if (rc != QMLE_OK) return rc;
-  if (pauli) {  // lambda = (sum of weighted words) psi
-    rc = pauli_seed_begin(&seed.sd, n, batch, obs.obs_terms, obs.n_obs_terms, n_obs, false, false, seed_ws,
-                          seed_bytes, stream);
-    if (rc == QMLE_OK) rc = pauli_seed_apply(seed.sd, psi, lam, batch, d_weights, stream);
+  AdjLdsArgs a;
+  rc = adj_lds_tables(x, &a.rev_ops, &a.terms);
+  if (rc != QMLE_OK) return rc;
+  float *fmats = (float *)(x.ws + x.L.lds_fmats);
+  float *rmats = (float *)(x.ws + x.L.mats);
+  rc = x.zero_outputs();
+  if (rc == QMLE_OK) rc = launch_build_matrices(fwd, c.d_angles_fwd, fmats, c.batch, x.stream());
+  if (rc == QMLE_OK) rc = launch_build_matrices(rev, c.d_angles_rev, rmats, c.batch, x.stream());
+  if (rc != QMLE_OK) return rc;
+  const Stage &fst = fwd->stages[0];
+  a.fwd = fill_tile_args(fwd, fst, nullptr, fmats, c.d_angles_fwd, true, TM_STORE, nullptr, nullptr, 0);
+  const size_t lds_base = ((size_t)16 << n) + 288 * sizeof(float);
+  a.fwd.slots_in_lds = lds_base + (size_t)a.fwd.n_ops * sizeof(OpSlot) <= 160 * 1024 ? 1 : 0;
+  const size_t lds = lds_base + (a.fwd.slots_in_lds ? (size_t)a.fwd.n_ops * sizeof(OpSlot) : 0);
+  a.n_rev = (int)rev->lowered.size();
+  a.rev_mats = rmats;
+  a.rev_mat_floats = rev->mat_floats;
+  a.rev_angles = c.d_angles_rev;
+  a.rev_n_slots = rev->n_slots;
+  a.rev_consts = rev->dev.d_consts;
+  a.weights = c.d_weights;
+  a.n_obs = c.obs.n_obs;
+  SeedHold seed;
+  if (x.pauli()) {  // word table and coefficient rows from global memory; the coefficient kernel runs first
+    rc = x.seed_begin(seed, true);
+    if (rc == QMLE_OK)
+      rc = pauli_seed_flat(seed.sd, c.batch, c.d_weights, x.stream(), &a.pw.words, &a.pw.coef, &a.pw.n_words);
     if (rc != QMLE_OK) return rc;
-  } else {  // lambda = (sum_k w_k Z..Z_k) psi
-    ZSumArgs z;
-    z.n_obs = n_obs;
-    for (int k = 0; k < n_obs; ++k) z.mask[k] = wires_to_pos(obs_wire_masks[k], n);
-    hipLaunchKernelGGL(k_zsum_apply, dim3(grid_for(D / 2, 256, 4096), batch), dim3(256), 0, stream,
-                       (const float4 *)psi, (float4 *)lam, n, d_weights, z);
+  } else {
+    a.z = x.z;
   }
-  HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(float), stream));
-  if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(float), stream));
-  // the backward gates act on [psi; lambda] as one batch of 2B states: duplicate the angles
-  if (rev->n_slots > 0) {
-    const size_t ab = (size_t)batch * rev->n_slots * sizeof(float);
-    HIPCHK(hipMemcpyAsync(ang2, d_angles_rev, ab, hipMemcpyDeviceToDevice, stream));
-    HIPCHK(hipMemcpyAsync((char *)ang2 + ab, d_angles_rev, ab, hipMemcpyDeviceToDevice, stream));
+  a.grad = c.d_grad;
+  a.n_grad_slots = c.n_grad_slots;
+  a.cot = (float *)c.cot.d_cot;
+  a.cot_stride = c.cot.stride;
+  if (FirstUse once{3}; once.first) {
+    for (const void *k : {(const void *)k_adjoint_lds<false, false>, (const void *)k_adjoint_lds<true, false>,
+                          (const void *)k_adjoint_lds<false, true>, (const void *)k_adjoint_lds<true, true>})
+      HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    once.done();
   }
-  rc = launch_build_matrices(rev, ang2, mats, 2 * batch, stream);
-  if (rc != QMLE_OK) return rc;
-  const int nb = adj_blocks(n);
-  // ---- fused plan: per-dev_op bookkeeping for the tile passes (cached on the reverse plan) ----
-  std::vector<int> st_term_begin, st_n_terms;
+  bool has_dense4 = false;
+  for (int g = fst.grp_begin; g < fst.grp_end; ++g)
+    has_dense4 |= fwd->op_groups[g].kind == GK_DENSE4 || fwd->op_groups[g].kind == GK_REG4X;
+  // all loops are strided, so the sweeps may use more threads than the 2^(n-4) register-tile
+  // work items of the forward groups: one 64-lane wave per 256 amplitudes, at least 4 waves
+  int threads = tile_threads(n);
+  if (threads < 256 && n >= 8) threads = 256;
+  auto *kernel = x.pauli() ? (has_dense4 ? k_adjoint_lds<true, true> : k_adjoint_lds<false, true>)
+                           : (has_dense4 ? k_adjoint_lds<true, false> : k_adjoint_lds<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(1, c.batch), dim3(threads), lds, x.stream(), a);
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+// ---- routes 2 and 3, the reverse plan stage by stage: fused tile passes (n >= 14) or one streaming pass per gate --
+// The fused route's bookkeeping, cached on the reverse plan: per dev_op the stage-local index of its derivative (or
+// -1) and its generator; per derivative its gradient slot and coefficient; per stage where its derivatives begin and
+// how many they are.
+struct FusedTables {
   const int32_t *d_term_idx = nullptr, *d_gtype = nullptr, *d_slot_of = nullptr;
   const float *d_coef_of = nullptr;
-  if (fused) {
-    const size_t nd = rev->dev_ops.size();
-    std::vector<int32_t> term_idx(nd ? nd : 1, -1), gtype(nd ? nd : 1, 0), slot_of;
-    std::vector<float> coef_of;
-    for (const Stage &st : rev->stages) {
-      st_term_begin.push_back((int)slot_of.size());
-      int cnt = 0;
-      if (st.kind == ST_TILE) {
-        if ((size_t)16 << st.T > (size_t)150 * 1024 || st.L < 1) return QMLE_ERR_UNSUPPORTED;
-        for (int g = st.grp_begin; g < st.grp_end; ++g)
-          if (rev->op_groups[g].kind != GK_REG4) return QMLE_ERR_UNSUPPORTED;
-        for (int k = st.op_begin; k < st.op_end; ++k) {
-          const int src = rev->dev_src[k];
-          if (src < 0) return QMLE_ERR_INVALID_ARG;
-          const qmle_adjoint_term &t = terms[src];
-          if (t.out_slot < 0) continue;
-          const LoweredOp &o = rev->dev_ops[k];
-          // a single-target generator whose projector is exactly the gate's control
-          const int nx = __builtin_popcount(t.x_wires), nz = __builtin_popcount(t.z_wires);
-          int gt;
-          if (t.marks_off >= 0 || nx > 1 || nz > 1 || (nx && nz && t.x_wires != t.z_wires))
-            return QMLE_ERR_UNSUPPORTED;
-          if (nx && nz) gt = AG_Y; else if (nx) gt = AG_X; else if (nz) gt = AG_Z; else gt = AG_P1;
-          if (o.kind != LK_1Q || o.nc > 1) return QMLE_ERR_UNSUPPORTED;
-          term_idx[k] = cnt++;
-          gtype[k] = gt;
-          slot_of.push_back(t.out_slot);
-          coef_of.push_back(t.coef);
-        }
+  std::vector<int> term_begin, n_terms;
+};
+static int adj_fused_tables(qmle_plan *rev, const qmle_adjoint_term *terms, FusedTables &ft) {
+  const size_t nd = rev->dev_ops.size();
+  std::vector<int32_t> term_idx(nd ? nd : 1, -1), gtype(nd ? nd : 1, 0), slot_of;
+  std::vector<float> coef_of;
+  for (const Stage &st : rev->stages) {
+    ft.term_begin.push_back((int)slot_of.size());
+    int cnt = 0;
+    if (st.kind == ST_TILE) {
+      if ((size_t)16 << st.T > (size_t)150 * 1024 || st.L < 1) return QMLE_ERR_UNSUPPORTED;
+      for (int g = st.grp_begin; g < st.grp_end; ++g)
+        if (rev->op_groups[g].kind != GK_REG4) return QMLE_ERR_UNSUPPORTED;
+      for (int k = st.op_begin; k < st.op_end; ++k) {
+        const int src = rev->dev_src[k];
+        if (src < 0) return QMLE_ERR_INVALID_ARG;
+        const qmle_adjoint_term &t = terms[src];
+        if (t.out_slot < 0) continue;
+        const LoweredOp &o = rev->dev_ops[k];
+        // a single-target generator whose projector is exactly the gate's control
+        const int nx = __builtin_popcount(t.x_wires), nz = __builtin_popcount(t.z_wires);
+        if (t.marks_off >= 0 || nx > 1 || nz > 1 || (nx && nz && t.x_wires != t.z_wires)) return QMLE_ERR_UNSUPPORTED;
+        if (o.kind != LK_1Q || o.nc > 1) return QMLE_ERR_UNSUPPORTED;
+        term_idx[k] = cnt++;
+        gtype[k] = nx && nz ? AG_Y : nx ? AG_X : nz ? AG_Z : AG_P1;
+        slot_of.push_back(t.out_slot);
+        coef_of.push_back(t.coef);
       }
-      st_n_terms.push_back(cnt);
     }
-    uint64_t hsh = fnv1a(term_idx.data(), term_idx.size() * 4);
-    hsh = fnv1a(gtype.data(), gtype.size() * 4, hsh);
-    hsh = fnv1a(slot_of.data(), slot_of.size() * 4, hsh);
-    hsh = fnv1a(coef_of.data(), coef_of.size() * 4, hsh);
-    const size_t nt_tot = slot_of.size() ? slot_of.size() : 1;
-    const size_t o1 = align_up(term_idx.size() * 4, 256), o2 = o1 + align_up(gtype.size() * 4, 256),
-                 o3 = o2 + align_up(nt_tot * 4, 256);
-    if (!rev->adjf_blob || rev->adjf_hash != hsh) {
-      if (rev->adjf_blob) (void)hipFree(rev->adjf_blob);
-      rev->adjf_blob = nullptr;
-      HIPCHK(hipMalloc(&rev->adjf_blob, o3 + align_up(nt_tot * 4, 256)));
-      HIPCHK(hipMemcpy(rev->adjf_blob, term_idx.data(), term_idx.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy((char *)rev->adjf_blob + o1, gtype.data(), gtype.size() * 4, hipMemcpyHostToDevice));
-      if (!slot_of.empty()) {
-        HIPCHK(hipMemcpy((char *)rev->adjf_blob + o2, slot_of.data(), slot_of.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy((char *)rev->adjf_blob + o3, coef_of.data(), coef_of.size() * 4, hipMemcpyHostToDevice));
-      }
-      rev->adjf_hash = hsh;
-    }
-    d_term_idx = (const int32_t *)rev->adjf_blob;
-    d_gtype = (const int32_t *)((char *)rev->adjf_blob + o1);
-    d_slot_of = (const int32_t *)((char *)rev->adjf_blob + o2);
-    d_coef_of = (const float *)((char *)rev->adjf_blob + o3);
-    if (FirstUse once{4}; once.first) {
-      HIPCHK(hipFuncSetAttribute((const void *)k_tile_adj,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      once.done();
-    }
+    ft.n_terms.push_back(cnt);
   }
-  float *tile_partial = (float *)(ws + L.tile_partial);
+  uint64_t hsh = fnv1a(term_idx.data(), term_idx.size() * 4);
+  hsh = fnv1a(gtype.data(), gtype.size() * 4, hsh);
+  hsh = fnv1a(slot_of.data(), slot_of.size() * 4, hsh);
+  hsh = fnv1a(coef_of.data(), coef_of.size() * 4, hsh);
+  const size_t nt_tot = slot_of.size() ? slot_of.size() : 1;
+  const size_t o1 = align_up(term_idx.size() * 4, 256), o2 = o1 + align_up(gtype.size() * 4, 256),
+               o3 = o2 + align_up(nt_tot * 4, 256);
+  const int rc = upload_cached(rev->adjf_blob, rev->adjf_hash, hsh, o3 + align_up(nt_tot * 4, 256),
+                               {{0, term_idx.data(), term_idx.size() * 4}, {o1, gtype.data(), gtype.size() * 4},
+                                {o2, slot_of.data(), slot_of.size() * 4}, {o3, coef_of.data(), coef_of.size() * 4}});
+  if (rc != QMLE_OK) return rc;
+  ft.d_term_idx = (const int32_t *)rev->adjf_blob;
+  ft.d_gtype = (const int32_t *)((char *)rev->adjf_blob + o1);
+  ft.d_slot_of = (const int32_t *)((char *)rev->adjf_blob + o2);
+  ft.d_coef_of = (const float *)((char *)rev->adjf_blob + o3);
+  if (FirstUse once{4}; once.first) {
+    HIPCHK(hipFuncSetAttribute((const void *)k_tile_adj, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    once.done();
+  }
+  return QMLE_OK;
+}
+// one fused tile pass over psi and lambda: stage `stage_i` of the reverse plan and the gradients of its gates
+static int adj_launch_tile_stage(const AdjCtx &x, const Stage &st, size_t stage_i, const FusedTables &ft, float2 *psi,
+                                 const float *mats, const float *ang2) {
+  const AdjCall<float> &c = x.c;
+  float *tile_partial = (float *)(x.ws + x.L.tile_partial);
+  AdjTileArgs A;
+  A.t = fill_tile_args(c.rev, st, psi, mats, ang2, false, TM_STORE, nullptr, nullptr, 0);
+  A.t.slots_in_lds = 1;
+  A.lam = (float2 *)(x.ws + x.L.lam);
+  A.term_idx = ft.d_term_idx + st.op_begin;
+  A.gtype = ft.d_gtype + st.op_begin;
+  A.partial = tile_partial;
+  A.n_terms = ft.n_terms[stage_i];
+  const int threads = 256;
+  const size_t lut_n = ((size_t)1 << (st.T - st.L)) < 4 ? 4 : ((size_t)1 << (st.T - st.L));
+  const size_t lds = ((size_t)16 << st.T) + 4 * lut_n + (size_t)A.t.n_ops * sizeof(OpSlot) +
+                     (size_t)(threads / kWave) * (A.n_terms ? A.n_terms : 1) * sizeof(float);
+  if (lds > 160 * 1024) return QMLE_ERR_UNSUPPORTED;
+  const unsigned tiles = 1u << (c.rev->n - st.T);
+  hipLaunchKernelGGL(k_tile_adj, dim3(tiles, c.batch), dim3(threads), lds, x.stream(), A);
+  if (A.n_terms)
+    hipLaunchKernelGGL(k_adj_tile_final, dim3(c.batch, A.n_terms), dim3(256), 0, x.stream(),
+                       (const float *)tile_partial, (int)tiles, A.n_terms, ft.d_slot_of + ft.term_begin[stage_i],
+                       ft.d_coef_of + ft.term_begin[stage_i], c.d_grad, c.n_grad_slots);
+  return QMLE_OK;
+}
+// psi = U_N .. U_1 |0>, lambda = (the observables) psi, zeroed outputs, and the reverse plan's matrices for [psi;
+// lambda] as one batch of 2B states
+static int adj_prepare_states(const AdjCtx &x, float2 *psi, float2 *lam, float *mats, float *ang2) {
+  const AdjCall<float> &c = x.c;
+  const int n = c.fwd->n;
+  int rc = run_batch_masks(c.fwd, c.d_angles_fwd, c.batch, QMLE_MEAS_STATE, nullptr, 0, psi, x.ws + x.L.fwd_ws,
+                           x.ws_bytes - x.L.fwd_ws, x.stream());
+  if (rc != QMLE_OK) return rc;
+  if (x.pauli()) {  // lambda = (sum of weighted words) psi
+    SeedHold seed;
+    rc = x.seed_begin(seed, false);
+    if (rc == QMLE_OK) rc = pauli_seed_apply(seed.sd, psi, lam, c.batch, c.d_weights, x.stream());
+    if (rc != QMLE_OK) return rc;
+  } else {  // lambda = (sum_k w_k Z..Z_k) psi
+    hipLaunchKernelGGL(k_zsum_apply, dim3(grid_for(((size_t)1 << n) / 2, 256, 4096), c.batch), dim3(256), 0, x.stream(),
+                       (const float4 *)psi, (float4 *)lam, n, c.d_weights, x.z, c.obs.n_obs);
+  }
+  rc = x.zero_outputs();
+  if (rc != QMLE_OK) return rc;
+  if (c.rev->n_slots > 0) {  // (the angles of psi's half and of lambda's half)
+    const size_t ab = (size_t)c.batch * c.rev->n_slots * sizeof(float);
+    HIPCHK(hipMemcpyAsync(ang2, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, x.stream()));
+    HIPCHK(hipMemcpyAsync((char *)ang2 + ab, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, x.stream()));
+  }
+  return launch_build_matrices(c.rev, ang2, mats, 2 * c.batch, x.stream());
+}
+static int adj_run_stages(const AdjCtx &x, bool fused) {
+  const AdjCall<float> &c = x.c;
+  qmle_plan *rev = c.rev;
+  const int n = rev->n;
+  float2 *psi = (float2 *)(x.ws + x.L.states);
+  float *mats = (float *)(x.ws + x.L.mats);
+  float *ang2 = (float *)(x.ws + x.L.ang2);
+  const SweepView<float2> s = {psi, (float2 *)(x.ws + x.L.lam), (float2 *)(x.ws + x.L.partial), n, adj_blocks(n),
+                               c.batch, x.stream()};
+  int rc = adj_prepare_states(x, s.psi, s.lam, mats, ang2);
+  if (rc != QMLE_OK) return rc;
+  FusedTables ft;
+  if (fused) {
+    rc = adj_fused_tables(rev, c.terms, ft);
+    if (rc != QMLE_OK) return rc;
+  }
   size_t si = 0;
   for (const Stage &st : rev->stages) {
     const size_t stage_i = si++;
     if (fused && st.kind == ST_TILE) {
-      AdjTileArgs A;
-      A.t = fill_tile_args(rev, st, psi, mats, ang2, false, TM_STORE, nullptr, nullptr, 0);
-      A.t.slots_in_lds = 1;
-      A.lam = lam;
-      A.term_idx = d_term_idx + st.op_begin;
-      A.gtype = d_gtype + st.op_begin;
-      A.partial = tile_partial;
-      A.n_terms = st_n_terms[stage_i];
-      const int threads = 256;
-      const size_t lut_n = ((size_t)1 << (st.T - st.L)) < 4 ? 4 : ((size_t)1 << (st.T - st.L));
-      const size_t lds = ((size_t)16 << st.T) + 4 * lut_n + (size_t)A.t.n_ops * sizeof(OpSlot) +
-                         (size_t)(threads / kWave) * (A.n_terms ? A.n_terms : 1) * sizeof(float);
-      if (lds > 160 * 1024) return QMLE_ERR_UNSUPPORTED;
-      const unsigned tiles = 1u << (n - st.T);
-      hipLaunchKernelGGL(k_tile_adj, dim3(tiles, batch), dim3(threads), lds, stream, A);
-      if (A.n_terms)
-        hipLaunchKernelGGL(k_adj_tile_final, dim3(batch, A.n_terms), dim3(256), 0, stream,
-                           (const float *)tile_partial, (int)tiles, A.n_terms,
-                           d_slot_of + st_term_begin[stage_i], d_coef_of + st_term_begin[stage_i],
-                           d_grad, n_grad_slots);
+      rc = adj_launch_tile_stage(x, st, stage_i, ft, psi, mats, ang2);
+      if (rc != QMLE_OK) return rc;
       continue;
     }
     const int r = fused ? rev->dev_src[st.op_begin] : st.src_ops[0];
     if (r < 0) return QMLE_ERR_INVALID_ARG;
-    const qmle_adjoint_term &t = terms[r];
+    const qmle_adjoint_term &t = c.terms[r];
     if (t.out_slot >= 0) {
-      AdjTerm a;
-      a.xmask = wires_to_pos(t.x_wires, n);
-      a.zmask = wires_to_pos(t.z_wires, n);
-      a.pmask = wires_to_pos(t.proj_wires, n);
-      a.marks = t.marks_off >= 0 ? rev->dev.d_consts + t.marks_off : nullptr;
-      if (t.marks_off >= 0 && (size_t)t.marks_off + D > rev->consts.size()) return QMLE_ERR_INVALID_ARG;
-      hipLaunchKernelGGL(k_adj_overlap, dim3(nb, batch), dim3(256), 0, stream, (const float4 *)psi,
-                         (const float4 *)lam, n, a, partial);
-      hipLaunchKernelGGL(k_adj_final, dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                         (const float2 *)partial, nb, t.n_y, t.coef, d_grad, n_grad_slots,
-                         t.out_slot);
+      if (!adj_marks_in_bounds(t, n, rev->consts.size())) return QMLE_ERR_INVALID_ARG;
+      adj_launch_overlap(k_adj_overlap, s, t, (const float *)rev->dev.d_consts, c.d_grad, c.n_grad_slots);
     }
-    if (want_cot && cot.off[r] >= 0) {
-      const LoweredOp &lo = rev->lowered[low_of[r]];  // (bit positions and plain record: checked by cot_request_check)
-      if (lo.kind == LK_2Q) {
-        hipLaunchKernelGGL((k_adj_moment2<float2, float>), dim3(nb, batch), dim3(256), 0, stream, (const float2 *)psi,
-                           (const float2 *)lam, n, (int)lo.t0, (int)lo.t1, partial);
-        hipLaunchKernelGGL((k_adj_cot2_final<float2, float>), dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                           (const float2 *)partial, nb, (const float *)mats, rev->mat_floats, lo.mat_off, d_cot,
-                           cot.stride, cot.off[r]);
-      } else {
-        hipLaunchKernelGGL(k_adj_moment, dim3(nb, batch), dim3(256), 0, stream, (const float4 *)psi,
-                           (const float4 *)lam, n, (int)lo.t0, partial);
-        hipLaunchKernelGGL(k_adj_cot_final, dim3(batch), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                           (const float2 *)partial, nb, (const float *)mats, rev->mat_floats, lo.mat_off, d_cot,
-                           cot.stride, cot.off[r]);
-      }
-    }
-    rc = run_stage_inplace(rev, st, psi, mats, ang2, 2 * batch, stream);
+    // (the operator's positions and its plain record: checked by cot_request_check)
+    if (x.want_cot() && c.cot.off[r] >= 0)
+      adj_launch_cotangent(k_adj_moment, s, rev->lowered[x.low_of[r]], (const float *)mats, rev->mat_floats,
+                           (float *)c.cot.d_cot, c.cot.stride, c.cot.off[r]);
+    rc = run_stage_inplace(rev, st, psi, mats, ang2, 2 * c.batch, x.stream());
     if (rc != QMLE_OK) return rc;
   }
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
 
+// Both complex64 sweeps and their cotangent forms: the checks, the workspace, the route.
+static int adjoint_run(const AdjCall<float> &c) {
+  int rc = adj_check_args(c, kMaxGridY / 2);  // (psi and lambda of a sample share a launch: 2 B <= kMaxGridY)
+  if (rc != QMLE_OK) return rc;
+  qmle_plan *fwd = c.fwd, *rev = c.rev;
+  // (the sweep applies stages to LIVE states: a schedule compiled for runs from |0..0> only is refused)
+  if ((fwd->flags | rev->flags) & QMLE_PLAN_INTERNAL_ZERO_RUN) return QMLE_ERR_UNSUPPORTED;
+  // rev is either a NO_FUSION plan (one streaming pass per gate) or a NO_MERGE plan (fused tile
+  // passes); both keep one source gate per lowered operator
+  const bool fused = (rev->flags & QMLE_PLAN_NO_MERGE) && !(rev->flags & QMLE_PLAN_NO_FUSION);
+  if (!fused)
+    for (const Stage &st : rev->stages)
+      if (st.src_ops.size() != 1) return QMLE_ERR_INVALID_ARG;
+  rc = adj_check_one_source(rev);
+  if (rc != QMLE_OK) return rc;
+  AdjCtx x = {c, (char *)c.d_ws, c.ws_bytes, {}, {}, {}};
+  rc = x.want_cot() ? cot_request_check(rev, c.cot, x.low_of) : QMLE_OK;  // (host only: before any device work)
+  if (rc != QMLE_OK) return rc;
+  rc = ensure_device_plan(rev);
+  if (rc != QMLE_OK) return rc;
+  x.L = adj_layout(fwd, rev, c.batch, cot_partials(rev, c.cot));
+  if (!align_workspace(x.ws, x.ws_bytes) || x.ws_bytes < x.L.total) return QMLE_ERR_WORKSPACE;
+  rc = x.pauli() ? QMLE_OK : zmasks_fill(c.obs.wire_masks, c.obs.n_obs, fwd->n, x.z);
+  if (rc != QMLE_OK) return rc;
+  for (int r = 0; r < c.n_terms; ++r)
+    if (!adj_slot_in_range(c.terms[r], c.n_grad_slots)) return QMLE_ERR_SLOT_RANGE;
+  if (x.pauli() && x.ws_bytes - x.L.total < pauli_seed_ws_bytes(c.batch, c.obs.n_obs_terms, false))
+    return QMLE_ERR_WORKSPACE;
+  if (adj_lds_route(fwd, rev)) return adj_run_lds(x);
+  if (fwd->n < 3) return QMLE_ERR_UNSUPPORTED;  // the per-gate streaming kernels move float4 pairs
+  // the fused tile pass takes generator overlaps only: said here, not by skipping the request (the caller falls
+  // back to one streaming pass per gate)
+  if (fused && x.want_cot()) return QMLE_ERR_UNSUPPORTED;
+  return adj_run_stages(x, fused);
+}
+
 extern "C" {
 
 size_t qmle_adjoint_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
-  if (!fwd || !rev || batch < 1) return 0;
+  if (!adj_ws_query_ok(fwd, rev, batch)) return 0;
   return adj_layout(fwd, rev, batch).total + 256;
 }
 size_t qmle_adjoint_pauli_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
                                           int n_obs) {
-  if (!fwd || !rev || batch < 1 || n_obs_terms < 1 || n_obs < 1) return 0;
-  return adj_layout(fwd, rev, batch).total + 256 + pauli_seed_ws_bytes(batch, n_obs_terms, false);
+  if (!adj_ws_query_ok(fwd, rev, batch, 1, n_obs_terms, n_obs)) return 0;
+  return adj_ws_with_seed(adj_layout(fwd, rev, batch).total, batch, n_obs_terms, false);
+}
+size_t qmle_adjoint_cotangent_at_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
+                                                 int n_obs_terms, int n_obs, int two_wire) {
+  if (!adj_ws_query_ok(fwd, rev, batch, 0, n_obs_terms, n_obs)) return 0;
+  return adj_ws_with_seed(adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total, batch, n_obs_terms, false);
+}
+size_t qmle_adjoint_cotangent_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
+                                              int n_obs) {
+  return qmle_adjoint_cotangent_at_workspace_bytes(fwd, rev, batch, n_obs_terms, n_obs, 0);
 }
 
 int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
@@ -883,8 +839,8 @@ int qmle_adjoint_gradient(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_
                           const qmle_adjoint_term *terms, int n_terms, float *d_grad,
                           int n_grad_slots, void *d_workspace, size_t workspace_bytes,
                           qmle_stream stream) {
-  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {obs_wire_masks, nullptr, 0, n_obs},
-                     terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream);
+  return adjoint_run({fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {obs_wire_masks, nullptr, 0, n_obs},
+                      terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream, {}});
 }
 
 int qmle_adjoint_gradient_pauli(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd,
@@ -892,24 +848,10 @@ int qmle_adjoint_gradient_pauli(qmle_plan *fwd, qmle_plan *rev, const float *d_a
                                 const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                                 const qmle_adjoint_term *terms, int n_terms, float *d_grad,
                                 int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws) return QMLE_ERR_INVALID_ARG;
-  const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-  if (rc != QMLE_OK) return rc;
-  if (ws_bytes < qmle_adjoint_pauli_workspace_bytes(fwd, rev, batch, n_obs_terms, n_obs)) return QMLE_ERR_INVALID_ARG;
-  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {nullptr, obs_terms, n_obs_terms, n_obs},
-                     terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes, stream);
-}
-
-
-size_t qmle_adjoint_cotangent_at_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch,
-                                                 int n_obs_terms, int n_obs, int two_wire) {
-  if (!fwd || !rev || batch < 1 || n_obs_terms < 0 || n_obs < 1) return 0;
-  return adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total + 256 +
-         (n_obs_terms > 0 ? pauli_seed_ws_bytes(batch, n_obs_terms, false) : 0);
-}
-size_t qmle_adjoint_cotangent_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
-                                              int n_obs) {
-  return qmle_adjoint_cotangent_at_workspace_bytes(fwd, rev, batch, n_obs_terms, n_obs, 0);
+  return adj_entry_pauli<float>(adjoint_run, qmle_adjoint_pauli_workspace_bytes,
+                                {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                 {nullptr, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad, n_grad_slots, d_ws,
+                                 ws_bytes, stream, {}});
 }
 
 int qmle_adjoint_cotangent_at(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
@@ -918,38 +860,22 @@ int qmle_adjoint_cotangent_at(qmle_plan *fwd, qmle_plan *rev, const float *d_ang
                               const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
                               const int32_t *cot_off, int cot_stride, float *d_cot, void *d_ws, size_t ws_bytes,
                               qmle_stream stream) {
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !cot_off || !d_cot || cot_stride < 1 ||
-      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
-    return QMLE_ERR_INVALID_ARG;
-  if (obs_terms) {
-    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-    if (rc != QMLE_OK) return rc;
-  }
-  if (ws_bytes < qmle_adjoint_cotangent_at_workspace_bytes(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs,
-                                                           cot_has_two_wire(rev, cot_off)))
-    return QMLE_ERR_INVALID_ARG;
-  return adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
-                     {obs_wire_masks, obs_terms, obs_terms ? n_obs_terms : 0, n_obs}, terms, n_terms, d_grad,
-                     n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot});
+  return adj_entry_cotangent_at<float>(adjoint_run, qmle_adjoint_cotangent_at_workspace_bytes,
+                                       {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                        {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
+                                        n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot}});
 }
 
-// the form with one index per 2x2: offsets 8 * index into rows of 8 * n_mat floats
 int qmle_adjoint_cotangent(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
                            int batch, const float *d_weights, const uint32_t *obs_wire_masks,
                            const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                            const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
                            const int32_t *mat_out, int n_mat, float *d_cot, void *d_ws, size_t ws_bytes,
                            qmle_stream stream) {
-  // (the argument checks of the function below first, so that a call that is bad in two ways keeps its old code)
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !mat_out || !d_cot || n_mat < 1 ||
-      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
-    return QMLE_ERR_INVALID_ARG;
-  std::vector<int32_t> off;
-  const int rc = cot_offsets_of_indices(rev, mat_out, n_mat, off);
-  if (rc != QMLE_OK) return rc;
-  return qmle_adjoint_cotangent_at(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, obs_terms,
-                                   n_obs_terms, n_obs, terms, n_terms, d_grad, n_grad_slots, off.data(), 8 * n_mat,
-                                   d_cot, d_ws, ws_bytes, stream);
+  return adj_entry_cotangent<float>(adjoint_run, qmle_adjoint_cotangent_at_workspace_bytes,
+                                    {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                     {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
+                                     n_grad_slots, d_ws, ws_bytes, stream, {mat_out, n_mat, d_cot}});
 }
 
 }  // extern "C"

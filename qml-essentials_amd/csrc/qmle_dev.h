@@ -231,118 +231,6 @@ __device__ __forceinline__ double block_sum_d(double v, double *red) {
   return t;
 }
 
-// ---- matrix cotangents of the adjoint sweeps (qmle_adjoint.hip, qmle_f64.hip) --------------------------------
-// G = M (U^+)^T for the DIM x DIM moment M[a][c] = sum conj(lambda[a]) psi[c] taken BEHIND the gate: phi = U^+ psi is
-// the state in front of it, so G[a][c] = sum conj(lambda[a]) phi[c] = sum_d M[a][d] U^+[c][d].  `ud`: the reverse
-// op's own matrix (U^+), `m`: M as (re, im) pairs, row-major.
-template <int DIM, class T, class MT, class OT>
-__device__ __forceinline__ void cot_finish(const T *__restrict__ m, const MT *__restrict__ ud, OT *__restrict__ out) {
-#pragma unroll
-  for (int a = 0; a < DIM; ++a)
-#pragma unroll
-    for (int c = 0; c < DIM; ++c) {
-      T re = 0, im = 0;
-#pragma unroll
-      for (int d = 0; d < DIM; ++d) {
-        const T mr = m[(a * DIM + d) * 2], mi = m[(a * DIM + d) * 2 + 1];
-        const T ur = (T)ud[(c * DIM + d) * 2], ui = (T)ud[(c * DIM + d) * 2 + 1];
-        re += mr * ur - mi * ui;
-        im += mr * ui + mi * ur;
-      }
-      out[(a * DIM + c) * 2] = (OT)re;
-      out[(a * DIM + c) * 2 + 1] = (OT)im;
-    }
-}
-// one row of a 4x4 moment: m[c * 2 + {0, 1}] += conj(l) p_c for the four amplitudes p_c of one value of the other wires
-template <class T, class V>
-__device__ __forceinline__ void cot_row4(T *__restrict__ m, const V l, const V p0, const V p1, const V p2, const V p3) {
-  m[0] += l.x * p0.x + l.y * p0.y; m[1] += l.x * p0.y - l.y * p0.x;
-  m[2] += l.x * p1.x + l.y * p1.y; m[3] += l.x * p1.y - l.y * p1.x;
-  m[4] += l.x * p2.x + l.y * p2.y; m[5] += l.x * p2.y - l.y * p2.x;
-  m[6] += l.x * p3.x + l.y * p3.y; m[7] += l.x * p3.y - l.y * p3.x;
-}
-__device__ __forceinline__ float wave_sum_any(float v) { return wave_sum(v); }
-__device__ __forceinline__ double wave_sum_any(double v) { return wave_sum_d(v); }
-
-// The 4x4 moment of a two-wire matrix gate on bit positions (t0, t1), row = 2 bit[t0] + bit[t1] (the LK_2Q rule):
-// partial[b][block][a * 4 + c] = sum_rest conj(lambda[a, rest]) psi[c, rest], one quad of each state per iteration,
-// any two positions; V = float2 (T = float) or double2 (T = double).  Plain 8- / 16-byte loads.
-template <class V, class T>
-__global__ void __launch_bounds__(256)
-k_adj_moment2(const V *__restrict__ psi_all, const V *__restrict__ lam_all, int n, int t0, int t1,
-              V *__restrict__ partial) {
-  __shared__ T red[4 * 32];
-  const int b = blockIdx.y;
-  const V *psi = psi_all + ((size_t)b << n), *lam = lam_all + ((size_t)b << n);
-  const uint64_t quads = n >= 2 ? (uint64_t)1 << (n - 2) : 0, b0 = (uint64_t)1 << t0, b1 = (uint64_t)1 << t1;
-  const int plo = t0 < t1 ? t0 : t1, phi = t0 < t1 ? t1 : t0;
-  T m0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, m2[8] = {0, 0, 0, 0, 0, 0, 0, 0},
-    m3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t j = ins0_64(ins0_64(q, plo), phi);
-    const V p0 = psi[j], p1 = psi[j | b1], p2 = psi[j | b0], p3 = psi[j | b0 | b1];
-    cot_row4(m0, lam[j], p0, p1, p2, p3);
-    cot_row4(m1, lam[j | b1], p0, p1, p2, p3);
-    cot_row4(m2, lam[j | b0], p0, p1, p2, p3);
-    cot_row4(m3, lam[j | b0 | b1], p0, p1, p2, p3);
-  }
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    m0[k] = wave_sum_any(m0[k]);
-    m1[k] = wave_sum_any(m1[k]);
-    m2[k] = wave_sum_any(m2[k]);
-    m3[k] = wave_sum_any(m3[k]);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      red[wv * 32 + k] = m0[k];
-      red[wv * 32 + 8 + k] = m1[k];
-      red[wv * 32 + 16 + k] = m2[k];
-      red[wv * 32 + 24 + k] = m3[k];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {  // (256 threads: four waves)
-    T re = 0, im = 0;
-    for (int i = 0; i < 4; ++i) {
-      re += red[i * 32 + threadIdx.x * 2];
-      im += red[i * 32 + threadIdx.x * 2 + 1];
-    }
-    V v;
-    v.x = re;
-    v.y = im;
-    partial[((size_t)b * gridDim.x + blockIdx.x) * 16 + threadIdx.x] = v;
-  }
-}
-// cot[b][off ..] = (sum_blocks partial[b][block]) (U^+)^T, summed in double; U^+ = the reverse op's 4x4 of sample b
-template <class V, class T>
-__global__ void __launch_bounds__(256)
-k_adj_cot2_final(const V *__restrict__ partial, int n_blocks, const T *__restrict__ mats, uint32_t mat_floats,
-                 uint32_t mat_off, T *__restrict__ cot, int cot_stride, int cot_off) {
-  __shared__ double red[16];
-  __shared__ double msum[32];
-  const int b = blockIdx.x;
-#pragma unroll 1
-  for (int e = 0; e < 16; ++e) {
-    double re = 0.0, im = 0.0;
-    for (int k = threadIdx.x; k < n_blocks; k += blockDim.x) {
-      const V v = partial[((size_t)b * n_blocks + k) * 16 + e];
-      re += v.x;
-      im += v.y;
-    }
-    const double r = block_sum_d(re, red);
-    const double s = block_sum_d(im, red);
-    if (threadIdx.x == 0) {
-      msum[2 * e] = r;
-      msum[2 * e + 1] = s;
-    }
-  }
-  if (threadIdx.x == 0)
-    cot_finish<4>((const double *)msum, mats + (size_t)b * mat_floats + mat_off, cot + (size_t)b * cot_stride + cot_off);
-}
-
 // Plan data and per-sample matrices are written before the launch and never during it: reading
 // them through the constant address space lets wave-uniform accesses compile to scalar loads
 // (s_load_dwordx4/x8/x16 into SGPRs) instead of vector loads + v_readfirstlane.
@@ -368,59 +256,6 @@ template <int N, class F> __device__ __forceinline__ void static_for(F &&f) {
 // host helpers
 // ---------------------------------------------------------------------------
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// A request for matrix cotangents beside the angle gradients of an adjoint sweep (both precisions): off[r] = offset,
-// in scalars, of reverse op r's block inside a sample's row of `stride` scalars, or -1; a block is 8 scalars (a 2x2,
-// re / im) for a one-wire matrix gate and 32 for a two-wire one.  off == nullptr: no request.
-struct CotRequest {
-  const int32_t *off;
-  int stride;
-  void *d_cot;
-};
-inline bool cot_two_wire_op(int opcode) { return opcode == QMLE_OP_MAT2 || opcode == QMLE_OP_MAT2_ROW; }
-// Does the request hold a two-wire block?  (The partial sums are then 16 complex per block, not 4.)
-inline bool cot_has_two_wire(const qmle_plan *rev, const int32_t *off) {
-  for (size_t r = 0; off && r < rev->ops.size(); ++r)
-    if (off[r] >= 0 && cot_two_wire_op(rev->ops[r].opcode)) return true;
-  return false;
-}
-// The request against the reverse tape, host only; low_of[r] <- the lowered operator of reverse op r (or -1).
-inline int cot_request_check(const qmle_plan *rev, const CotRequest &c, std::vector<int> &low_of) {
-  if (c.stride < 1 || !c.d_cot) return QMLE_ERR_INVALID_ARG;
-  low_of.assign(rev->ops.size(), -1);
-  for (size_t l = 0; l < rev->lowered_src.size(); ++l)
-    if (rev->lowered_src[l].size() == 1) low_of[rev->lowered_src[l][0]] = (int)l;
-  std::vector<std::pair<int64_t, int64_t>> blocks;
-  for (size_t r = 0; r < rev->ops.size(); ++r) {
-    if (c.off[r] < 0) continue;
-    const int oc = rev->ops[r].opcode;
-    const bool two = cot_two_wire_op(oc);
-    if (!two && oc != QMLE_OP_MAT1 && oc != QMLE_OP_MAT1_ROW) return QMLE_ERR_UNSUPPORTED;
-    const int64_t end = (int64_t)c.off[r] + (two ? 32 : 8);
-    if (end > c.stride) return QMLE_ERR_SLOT_RANGE;
-    blocks.emplace_back((int64_t)c.off[r], end);
-    // (a flagged op that was merged into a neighbour or carries a control has no moment of its own)
-    if (low_of[r] < 0 || rev->lowered[low_of[r]].kind != (two ? LK_2Q : LK_1Q) || rev->lowered[low_of[r]].nc != 0)
-      return QMLE_ERR_INVALID_ARG;
-  }
-  std::sort(blocks.begin(), blocks.end());
-  for (size_t k = 1; k < blocks.size(); ++k)
-    if (blocks[k].first < blocks[k - 1].second) return QMLE_ERR_SLOT_RANGE;
-  return QMLE_OK;
-}
-// The old form of the request, mat_out[r] = index of reverse op r's 2x2 among n_mat -> offsets 8 * index.  It
-// serves one-wire matrices only and says so itself.
-inline int cot_offsets_of_indices(const qmle_plan *rev, const int32_t *mat_out, int n_mat, std::vector<int32_t> &off) {
-  off.assign(rev->ops.size(), -1);
-  for (size_t r = 0; r < rev->ops.size(); ++r) {
-    if (mat_out[r] < 0) continue;
-    if (mat_out[r] >= n_mat) return QMLE_ERR_SLOT_RANGE;
-    const int oc = rev->ops[r].opcode;
-    if (oc != QMLE_OP_MAT1 && oc != QMLE_OP_MAT1_ROW) return QMLE_ERR_UNSUPPORTED;  // (two-wire: the _at functions)
-    off[r] = 8 * mat_out[r];
-  }
-  return QMLE_OK;
-}
 
 // exact grids by default: grid-stride persistence measured slower for pure streaming
 inline unsigned grid_for(uint64_t items, unsigned block, unsigned cap = 1u << 30) {

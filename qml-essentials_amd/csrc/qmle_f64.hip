@@ -1,4 +1,6 @@
-// libqmle_sv, complex128 engine (the reference's jax_enable_x64 mode).
+// libqmle_sv, complex128 engine (the reference's jax_enable_x64 mode): the forward run, and the adjoint sweep on its
+// streaming appliers -- f64_adjoint_run checks a call and lays out its workspace, f64_adj_round sweeps one round of
+// samples.  What that sweep has in common with the complex64 one of qmle_adjoint.hip sits in qmle_adjoint_dev.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -13,6 +15,7 @@
 #include "qmle_internal.h"
 #include "qmle_host.h"
 #include "qmle_dev.h"
+#include "qmle_adjoint_dev.h"
 #include "qmle_matrices.h"
 
 namespace {
@@ -48,9 +51,6 @@ __device__ __forceinline__ double2 zfma(double2 a, double2 b, double2 c) {  // a
   return make_double2(p.x + c.x, p.y + c.y);
 }
 #pragma clang fp contract(fast)
-struct F64Obs {
-  uint32_t mask[QMLE_MAX_QUBITS];  // bit-position masks of the Z (x) Z ... observables
-};
 
 // work items [first, first + step, ...) of ONE lowered operator on the amplitudes `s` of one state
 __device__ __forceinline__ void f64_apply(double2 *s, int n, const LoweredOp &op, const double *__restrict__ mrow,
@@ -137,7 +137,7 @@ __device__ __forceinline__ void f64_apply(double2 *s, int n, const LoweredOp &op
 __global__ void __launch_bounds__(256)
 k64_lds(const LoweredOp *__restrict__ ops, int n_ops, int n, const double *__restrict__ mats, uint32_t mat_floats,
         const double *__restrict__ consts, const double *__restrict__ angles, int n_slots, int meas,
-        F64Obs obs, int n_obs, void *__restrict__ out) {
+        ZMasks obs, int n_obs, void *__restrict__ out) {
   extern __shared__ double2 st64[];
   __shared__ double red[16];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -191,7 +191,7 @@ k64_probs(const double2 *__restrict__ states, double *__restrict__ out, uint64_t
     out[i] = states[i].x * states[i].x + states[i].y * states[i].y;
 }
 __global__ void __launch_bounds__(256)
-k64_expval(const double2 *__restrict__ states, int n, F64Obs obs, int n_obs, double *__restrict__ out) {
+k64_expval(const double2 *__restrict__ states, int n, ZMasks obs, int n_obs, double *__restrict__ out) {
   __shared__ double red[16];
   const int b = blockIdx.x, k = blockIdx.y;
   const uint64_t D = (uint64_t)1 << n;
@@ -216,17 +216,14 @@ k64_density(const double2 *__restrict__ states, int n, double2 *__restrict__ out
 }
 
 // ---- adjoint differentiation in complex128 (qmle_adjoint_gradient_f64) ------------------------
-// The complex64 sweep of qmle_adjoint.hip restated on the streaming complex128 appliers: forward state,
-// lambda = (sum_k w_k Z..Z_k) psi, then per gate of the reversed, daggered tape the overlap
-// Im <lambda| G |psi> of its generator and the inverse gate on psi and lambda -- one backward sweep for
-// every angle where x64 mode used to contract 2 P shifted circuits (tests/test_jaqsi.py:57,131-141).
-struct F64AdjTerm {
-  uint32_t xmask, zmask, pmask;  // bit positions: flipped / sign / projected onto 1
-  const double *marks;           // != nullptr: G = diag(marks)
-};
+// The streaming route of qmle_adjoint.hip on the complex128 appliers: forward state, lambda = (sum_k w_k Z..Z_k) psi,
+// then per gate of the reversed, daggered tape the overlap Im <lambda| G |psi> of its generator and the inverse gate
+// on psi and lambda -- one backward sweep for every angle where x64 mode used to contract 2 P shifted circuits
+// (tests/test_jaqsi.py:57,131-141).  The kernels here move one double2 per amplitude; the finishing kernels, the
+// two-wire moment and the host side's checks and launch pairs are those of qmle_adjoint_dev.h.
 __global__ void __launch_bounds__(256)
 k64_zsum_apply(const double2 *__restrict__ psi, double2 *__restrict__ lam, int n, const double *__restrict__ weights,
-               F64Obs obs, int n_obs) {
+               ZMasks obs, int n_obs) {
   const int b = blockIdx.y;
   const uint64_t D = (uint64_t)1 << n;
   const double *w = weights + (size_t)b * n_obs;
@@ -237,9 +234,9 @@ k64_zsum_apply(const double2 *__restrict__ psi, double2 *__restrict__ lam, int n
     lam[((size_t)b << n) + i] = make_double2(d * v.x, d * v.y);
   }
 }
-// partial[b][block] = sum_i conj(lambda_i) (X^x Z^z Pi_p psi)_i   (the phase i^n_y is applied by k64_adj_final)
+// partial[b][block] = sum_i conj(lambda_i) (X^x Z^z Pi_p psi)_i   (the phase i^n_y is applied by k_adj_final)
 __global__ void __launch_bounds__(256)
-k64_adj_overlap(const double2 *__restrict__ psi_all, const double2 *__restrict__ lam_all, int n, F64AdjTerm t,
+k64_adj_overlap(const double2 *__restrict__ psi_all, const double2 *__restrict__ lam_all, int n, AdjTerm<double> t,
                 double2 *__restrict__ partial) {
   __shared__ double red[16];
   const int b = blockIdx.y;
@@ -258,25 +255,6 @@ k64_adj_overlap(const double2 *__restrict__ psi_all, const double2 *__restrict__
   const double m = block_sum_d(im, red);
   if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = make_double2(r, m);
 }
-// grad[b][slot] = coef * Im(i^n_y * sum)
-__global__ void __launch_bounds__(256)
-k64_adj_final(const double2 *__restrict__ partial, int n_blocks, int n_y, double coef, double *__restrict__ grad,
-              int n_grad_slots, int slot) {
-  __shared__ double red[16];
-  const int b = blockIdx.x;
-  double re = 0.0, im = 0.0;
-  for (int k = threadIdx.x; k < n_blocks; k += blockDim.x) {
-    const double2 v = partial[(size_t)b * n_blocks + k];
-    re += v.x;
-    im += v.y;
-  }
-  const double r = block_sum_d(re, red);
-  const double i = block_sum_d(im, red);
-  if (threadIdx.x == 0) {
-    const int q = n_y & 3;
-    grad[(size_t)b * n_grad_slots + slot] = coef * (q == 0 ? i : q == 1 ? r : q == 2 ? -i : -r);
-  }
-}
 // The 2x2 moment of a one-wire matrix gate on bit position t (k_adj_moment of qmle_adjoint.hip, one amplitude pair
 // per iteration): partial[b][block][a * 2 + c] = sum_rest conj(lambda[a, rest]) psi[c, rest]
 __global__ void __launch_bounds__(256)
@@ -289,11 +267,7 @@ k64_adj_moment(const double2 *__restrict__ psi_all, const double2 *__restrict__ 
   double m[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t j0 = ((i & ~(tb - 1)) << 1) | (i & (tb - 1)), j1 = j0 | tb;
-    const double2 l0 = lam[j0], l1 = lam[j1], p0 = psi[j0], p1 = psi[j1];
-    m[0] += l0.x * p0.x + l0.y * p0.y; m[1] += l0.x * p0.y - l0.y * p0.x;
-    m[2] += l0.x * p1.x + l0.y * p1.y; m[3] += l0.x * p1.y - l0.y * p1.x;
-    m[4] += l1.x * p0.x + l1.y * p0.y; m[5] += l1.x * p0.y - l1.y * p0.x;
-    m[6] += l1.x * p1.x + l1.y * p1.y; m[7] += l1.x * p1.y - l1.y * p1.x;
+    cot_accumulate(m, lam[j0], lam[j1], psi[j0], psi[j1]);
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -301,27 +275,6 @@ k64_adj_moment(const double2 *__restrict__ psi_all, const double2 *__restrict__ 
     const double s = block_sum_d(m[2 * e + 1], red);
     if (threadIdx.x == 0) partial[((size_t)b * gridDim.x + blockIdx.x) * 4 + e] = make_double2(r, s);
   }
-}
-// cot[b][off ..] = (sum_blocks partial[b][block]) (U^+)^T (cot_finish); U^+ = the reverse op's matrix of sample b
-__global__ void __launch_bounds__(256)
-k64_adj_cot_final(const double2 *__restrict__ partial, int n_blocks, const double *__restrict__ mats,
-                  uint32_t mat_floats, uint32_t mat_off, double *__restrict__ cot, int cot_stride, int cot_off) {
-  __shared__ double red[16];
-  const int b = blockIdx.x;
-  double m[8];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    double re = 0.0, im = 0.0;
-    for (int k = threadIdx.x; k < n_blocks; k += blockDim.x) {
-      const double2 v = partial[((size_t)b * n_blocks + k) * 4 + e];
-      re += v.x;
-      im += v.y;
-    }
-    m[2 * e] = block_sum_d(re, red);
-    m[2 * e + 1] = block_sum_d(im, red);
-  }
-  if (threadIdx.x == 0)
-    cot_finish<2>((const double *)m, mats + (size_t)b * mat_floats + mat_off, cot + (size_t)b * cot_stride + cot_off);
 }
 
 }  // namespace
@@ -383,15 +336,6 @@ static void launch_build_matrices_f64(const qmle_plan *p, const double *d_angles
     hipLaunchKernelGGL(k_build_matrices_f64<false>, dim3(grid_for((uint64_t)batch * ng, 64)), dim3(64), 0, stream,
                        p->dev.d_build, p->dev.d_groups, ng, d_angles, p->n_slots, f64_consts(p), d_mats, p->mat_floats,
                        batch);
-}
-// <Z..Z> on wire masks (bit w = wire w) -> the kernels' position masks
-static int f64_obs(const uint32_t *wire_masks, int n_obs, int n, F64Obs &obs) {
-  std::memset(&obs, 0, sizeof(obs));
-  for (int k = 0; k < n_obs; ++k) {
-    if (!valid_wire_mask(wire_masks[k], n)) return QMLE_ERR_WIRE_RANGE;
-    obs.mask[k] = wires_to_pos(wire_masks[k], n);
-  }
-  return QMLE_OK;
 }
 
 extern "C" {
@@ -456,11 +400,10 @@ int qmle_run_batch_f64(qmle_plan *plan, const double *d_angles, int batch, int m
   if (workspace_bytes < qmle_workspace_bytes_f64(plan, batch, meas_type) || !align_workspace(ws, workspace_bytes))
     return QMLE_ERR_WORKSPACE;
   const int n = plan->n;
-  F64Obs obs;
-  std::memset(&obs, 0, sizeof(obs));
+  ZMasks obs = {};
   if (meas_type == QMLE_MEAS_EXPVAL_Z) {
     if (n_obs < 1 || n_obs > QMLE_MAX_QUBITS || !wire_masks) return QMLE_ERR_INVALID_ARG;
-    const int rc_obs = f64_obs(wire_masks, n_obs, n, obs);
+    const int rc_obs = zmasks_fill(wire_masks, n_obs, n, obs);
     if (rc_obs != QMLE_OK) return rc_obs;
   }
   if (meas_type == QMLE_MEAS_DENSITY && n > 12) return QMLE_ERR_UNSUPPORTED;
@@ -535,20 +478,19 @@ static F64AdjLayout f64_adj_layout(const qmle_plan *fwd, const qmle_plan *rev, i
 }
 
 size_t qmle_adjoint_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
-  if (!fwd || !rev || batch < 1 || fwd->n != rev->n) return 0;
+  if (!adj_ws_query_ok(fwd, rev, batch) || fwd->n != rev->n) return 0;
   return f64_adj_layout(fwd, rev, batch).total;
 }
 size_t qmle_adjoint_pauli_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_obs_terms,
                                               int n_obs) {
-  if (!fwd || !rev || batch < 1 || fwd->n != rev->n || n_obs_terms < 1 || n_obs < 1) return 0;
-  return f64_adj_layout(fwd, rev, batch).total + 256 +
-         pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true);
+  if (!adj_ws_query_ok(fwd, rev, batch, 1, n_obs_terms, n_obs) || fwd->n != rev->n) return 0;
+  return adj_ws_with_seed(f64_adj_layout(fwd, rev, batch).total, f64_in_flight(fwd->n, batch, 32), n_obs_terms, true);
 }
 size_t qmle_adjoint_cotangent_at_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                                      int n_obs_terms, int n_obs, int two_wire) {
-  if (!fwd || !rev || batch < 1 || fwd->n != rev->n || n_obs_terms < 0 || n_obs < 1) return 0;
-  return f64_adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total + 256 +
-         (n_obs_terms > 0 ? pauli_seed_ws_bytes(f64_in_flight(fwd->n, batch, 32), n_obs_terms, true) : 0);
+  if (!adj_ws_query_ok(fwd, rev, batch, 0, n_obs_terms, n_obs) || fwd->n != rev->n) return 0;
+  return adj_ws_with_seed(f64_adj_layout(fwd, rev, batch, two_wire ? 16 : 4).total, f64_in_flight(fwd->n, batch, 32),
+                          n_obs_terms, true);
 }
 size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                                   int n_obs_terms, int n_obs) {
@@ -557,123 +499,94 @@ size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qm
 
 }  // extern "C"
 
-// Both complex128 sweeps: Z-parity masks (obs_terms == nullptr) or a list of weighted Pauli words, checked by the
-// caller; they differ in the seed alone (k64_zsum_apply / the seed kernels of qmle_pauli.hip per round of samples).
-static int f64_adjoint_run(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
-                           int batch, const double *d_weights, const uint32_t *obs_wire_masks,
-                           const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
-                           const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
-                           void *d_workspace, size_t workspace_bytes, qmle_stream stream_,
-                           const CotRequest &cot = {nullptr, 0, nullptr}) {
-  const bool pauli = obs_terms != nullptr;
-  const bool want_cot = cot.off != nullptr;  // matrix cotangents beside the angle gradients
-  double *const d_cot = (double *)cot.d_cot;
-  if (!fwd || !rev || batch < 1 || !d_weights || (!pauli && !obs_wire_masks) || n_obs < 1 ||
-      (!pauli && n_obs > QMLE_MAX_QUBITS) || !terms ||
-      !d_grad || n_grad_slots < 1 || !d_workspace || fwd->n != rev->n || n_terms != (int)rev->ops.size())
-    return QMLE_ERR_INVALID_ARG;
-  if ((fwd->n_slots > 0 && !d_angles_fwd) || (rev->n_slots > 0 && !d_angles_rev)) return QMLE_ERR_INVALID_ARG;
-  const int n = fwd->n;
-  // one source gate (one generator) per operator of the reverse plan: NO_FUSION or NO_MERGE plans
-  for (const auto &srcs : rev->lowered_src)
-    if (srcs.size() != 1) return QMLE_ERR_INVALID_ARG;
-  F64Obs obs = {};
-  int rc = pauli ? QMLE_OK : f64_obs(obs_wire_masks, n_obs, n, obs);
-  if (rc != QMLE_OK) return rc;
-  for (int r = 0; r < n_terms; ++r) {
-    if (terms[r].out_slot >= n_grad_slots) return QMLE_ERR_SLOT_RANGE;
-    if (terms[r].out_slot >= 0 && terms[r].marks_off >= 0 &&
-        (size_t)terms[r].marks_off + ((size_t)1 << n) > rev->n_user_consts)
-      return QMLE_ERR_INVALID_ARG;
-  }
-  std::vector<int> low_of;  // reverse op -> its lowered operator
-  if (want_cot) {
-    rc = cot_request_check(rev, cot, low_of);
+// One round of samples [b0, b0 + s.bc) of the sweep: the forward state, the seed (`seed`, or the Z masks `z`), then
+// per gate of the reverse tape its overlap, its matrix cotangent where asked for, and the inverse gate on both states.
+static int f64_adj_round(const AdjCall<double> &c, const SweepView<double2> &s, int b0, const double *fmats,
+                         const double *rmats, const ZMasks &z, const PauliSeed *seed) {
+  const qmle_plan *fwd = c.fwd, *rev = c.rev;
+  const int n = s.n;
+  const double *fc = f64_consts(fwd), *rcst = f64_consts(rev);
+  const double *af = c.d_angles_fwd ? c.d_angles_fwd + (size_t)b0 * fwd->n_slots : nullptr;
+  const double *ar = c.d_angles_rev ? c.d_angles_rev + (size_t)b0 * rev->n_slots : nullptr;
+  const double *fm = fmats + (size_t)b0 * fwd->mat_floats, *rm = rmats + (size_t)b0 * rev->mat_floats;
+  const double *w = c.d_weights + (size_t)b0 * c.obs.n_obs;
+  const size_t half = ((size_t)1 << n) / 2;
+  const dim3 grid(grid_for(half ? half : 1, 256, 1u << 16), s.bc);
+  // forward: psi = U_N .. U_1 |0>
+  hipLaunchKernelGGL(k64_init, grid, dim3(256), 0, s.stream, s.psi, n);
+  for (const LoweredOp &op : fwd->lowered)
+    hipLaunchKernelGGL(k64_op, grid, dim3(256), 0, s.stream, s.psi, n, op, fm, fwd->mat_floats, fc, af, fwd->n_slots);
+  if (seed) {  // lambda = (sum of weighted words) psi
+    const int rc = pauli_seed_apply(seed, s.psi, s.lam, s.bc, w, s.stream);
     if (rc != QMLE_OK) return rc;
+  } else {  // lambda = (sum_k w_k Z..Z_k) psi
+    hipLaunchKernelGGL(k64_zsum_apply, grid, dim3(256), 0, s.stream, (const double2 *)s.psi, s.lam, n, w, z,
+                       c.obs.n_obs);
   }
-  const F64AdjLayout L = f64_adj_layout(fwd, rev, batch, !want_cot ? 1 : cot_has_two_wire(rev, cot.off) ? 16 : 4);
-  char *ws = (char *)d_workspace;
-  if (!align_workspace(ws, workspace_bytes) || workspace_bytes < L.total) return QMLE_ERR_WORKSPACE;
-  hipStream_t stream = (hipStream_t)stream_;
+  for (size_t r = 0; r < rev->lowered.size(); ++r) {
+    const int src = rev->lowered_src[r][0];
+    const qmle_adjoint_term &t = c.terms[src];
+    if (t.out_slot >= 0)
+      adj_launch_overlap(k64_adj_overlap, s, t, rcst, c.d_grad + (size_t)b0 * c.n_grad_slots, c.n_grad_slots);
+    if (c.cot.off && c.cot.off[src] >= 0)
+      adj_launch_cotangent(k64_adj_moment, s, rev->lowered[r], rm, rev->mat_floats,
+                           (double *)c.cot.d_cot + (size_t)b0 * c.cot.stride, c.cot.stride, c.cot.off[src]);
+    for (double2 *st : {s.psi, s.lam})
+      hipLaunchKernelGGL(k64_op, grid, dim3(256), 0, s.stream, st, n, rev->lowered[r], rm, rev->mat_floats, rcst, ar,
+                         rev->n_slots);
+  }
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+// Both complex128 sweeps and their cotangent forms: Z-parity masks or a list of weighted Pauli words, checked by the
+// entry point; they differ in the seed alone (k64_zsum_apply / the seed kernels of qmle_pauli.hip per round of samples).
+static int f64_adjoint_run(const AdjCall<double> &c) {
+  int rc = adj_check_args(c);
+  if (rc == QMLE_OK) rc = adj_check_one_source(c.rev);
+  if (rc != QMLE_OK) return rc;
+  qmle_plan *fwd = c.fwd, *rev = c.rev;
+  const int n = fwd->n;
+  const bool pauli = c.obs.obs_terms != nullptr;
+  ZMasks z = {};
+  rc = pauli ? QMLE_OK : zmasks_fill(c.obs.wire_masks, c.obs.n_obs, n, z);
+  if (rc != QMLE_OK) return rc;
+  for (int r = 0; r < c.n_terms; ++r) {
+    if (!adj_slot_in_range(c.terms[r], c.n_grad_slots)) return QMLE_ERR_SLOT_RANGE;
+    if (c.terms[r].out_slot >= 0 && !adj_marks_in_bounds(c.terms[r], n, rev->n_user_consts)) return QMLE_ERR_INVALID_ARG;
+  }
+  std::vector<int> low_of;  // (the sweep walks the lowered operators itself)
+  rc = c.cot.off ? cot_request_check(rev, c.cot, low_of) : QMLE_OK;
+  if (rc != QMLE_OK) return rc;
+  const F64AdjLayout L = f64_adj_layout(fwd, rev, c.batch, cot_partials(rev, c.cot));
+  char *ws = (char *)c.d_ws;
+  size_t ws_bytes = c.ws_bytes;
+  if (!align_workspace(ws, ws_bytes) || ws_bytes < L.total) return QMLE_ERR_WORKSPACE;
+  hipStream_t stream = (hipStream_t)c.stream;
   rc = ensure_device_plan(fwd);
   if (rc == QMLE_OK) rc = ensure_device_plan(rev);
   if (rc == QMLE_OK) rc = ensure_f64(fwd);
   if (rc == QMLE_OK) rc = ensure_f64(rev);
   if (rc != QMLE_OK) return rc;
-  const double *fc = f64_consts(fwd), *rcst = f64_consts(rev);
   double *fmats = (double *)(ws + L.fmats), *rmats = (double *)(ws + L.rmats);
-  launch_build_matrices_f64(fwd, d_angles_fwd, fmats, batch, stream);
-  launch_build_matrices_f64(rev, d_angles_rev, rmats, batch, stream);
-  HIPCHK(hipMemsetAsync(d_grad, 0, (size_t)batch * n_grad_slots * sizeof(double), stream));
-  if (want_cot) HIPCHK(hipMemsetAsync(d_cot, 0, (size_t)batch * cot.stride * sizeof(double), stream));
-  double2 *psi = (double2 *)(ws + L.psi), *lam = (double2 *)(ws + L.lam);
-  double2 *partial = (double2 *)(ws + L.partial);
-  const size_t D = (size_t)1 << n;
-  const int nb = f64_adj_blocks(n);
-  const int in_flight = f64_in_flight(n, batch, 32);
-  const unsigned gx = grid_for(D / 2 ? D / 2 : 1, 256, 1u << 16);
-  struct SeedHold {
-    PauliSeed *sd = nullptr;
-    ~SeedHold() { pauli_seed_end(sd); }
-  } seed;
+  launch_build_matrices_f64(fwd, c.d_angles_fwd, fmats, c.batch, stream);
+  launch_build_matrices_f64(rev, c.d_angles_rev, rmats, c.batch, stream);
+  HIPCHK(hipMemsetAsync(c.d_grad, 0, (size_t)c.batch * c.n_grad_slots * sizeof(double), stream));
+  if (c.cot.off) HIPCHK(hipMemsetAsync(c.cot.d_cot, 0, (size_t)c.batch * c.cot.stride * sizeof(double), stream));
+  const int in_flight = f64_in_flight(n, c.batch, 32);
+  SeedHold seed;
   if (pauli) {  // the seed's tables: behind everything the Z sweep lays out
-    const size_t need = pauli_seed_ws_bytes(in_flight, n_obs_terms, true);
-    if (workspace_bytes - L.total < need) return QMLE_ERR_WORKSPACE;
-    rc = pauli_seed_begin(&seed.sd, n, in_flight, obs_terms, n_obs_terms, n_obs, true, false, ws + L.total,
-                          workspace_bytes - L.total, stream);
+    if (ws_bytes - L.total < pauli_seed_ws_bytes(in_flight, c.obs.n_obs_terms, true)) return QMLE_ERR_WORKSPACE;
+    rc = pauli_seed_begin(&seed.sd, n, in_flight, c.obs.obs_terms, c.obs.n_obs_terms, c.obs.n_obs, true, false,
+                          ws + L.total, ws_bytes - L.total, stream);
     if (rc != QMLE_OK) return rc;
   }
-  for (int b0 = 0; b0 < batch; b0 += in_flight) {
-    const int bc = batch - b0 < in_flight ? batch - b0 : in_flight;
-    const double *af = d_angles_fwd ? d_angles_fwd + (size_t)b0 * fwd->n_slots : nullptr;
-    const double *ar = d_angles_rev ? d_angles_rev + (size_t)b0 * rev->n_slots : nullptr;
-    // forward: psi = U_N .. U_1 |0>
-    hipLaunchKernelGGL(k64_init, dim3(gx, bc), dim3(256), 0, stream, psi, n);
-    for (const LoweredOp &op : fwd->lowered)
-      hipLaunchKernelGGL(k64_op, dim3(gx, bc), dim3(256), 0, stream, psi, n, op, fmats + (size_t)b0 * fwd->mat_floats,
-                         fwd->mat_floats, fc, af, fwd->n_slots);
-    if (pauli) {  // lambda = (sum of weighted words) psi
-      rc = pauli_seed_apply(seed.sd, psi, lam, bc, d_weights + (size_t)b0 * n_obs, stream);
-      if (rc != QMLE_OK) return rc;
-    } else {  // lambda = (sum_k w_k Z..Z_k) psi
-      hipLaunchKernelGGL(k64_zsum_apply, dim3(gx, bc), dim3(256), 0, stream, (const double2 *)psi, lam, n,
-                         d_weights + (size_t)b0 * n_obs, obs, n_obs);
-    }
-    for (size_t r = 0; r < rev->lowered.size(); ++r) {
-      const qmle_adjoint_term &t = terms[rev->lowered_src[r][0]];
-      if (t.out_slot >= 0) {
-        F64AdjTerm a;
-        a.xmask = wires_to_pos(t.x_wires, n);
-        a.zmask = wires_to_pos(t.z_wires, n);
-        a.pmask = wires_to_pos(t.proj_wires, n);
-        a.marks = t.marks_off >= 0 ? rcst + t.marks_off : nullptr;
-        hipLaunchKernelGGL(k64_adj_overlap, dim3(nb, bc), dim3(256), 0, stream, (const double2 *)psi,
-                           (const double2 *)lam, n, a, partial);
-        hipLaunchKernelGGL(k64_adj_final, dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream, (const double2 *)partial, nb,
-                           t.n_y, (double)t.coef, d_grad + (size_t)b0 * n_grad_slots, n_grad_slots, t.out_slot);
-      }
-      const int c_off = want_cot ? cot.off[rev->lowered_src[r][0]] : -1;
-      if (c_off >= 0) {
-        const LoweredOp &lo = rev->lowered[r];
-        const double *mr = rmats + (size_t)b0 * rev->mat_floats;
-        double *out = d_cot + (size_t)b0 * cot.stride;
-        if (lo.kind == LK_2Q) {
-          hipLaunchKernelGGL((k_adj_moment2<double2, double>), dim3(nb, bc), dim3(256), 0, stream,
-                             (const double2 *)psi, (const double2 *)lam, n, (int)lo.t0, (int)lo.t1, partial);
-          hipLaunchKernelGGL((k_adj_cot2_final<double2, double>), dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                             (const double2 *)partial, nb, mr, rev->mat_floats, lo.mat_off, out, cot.stride, c_off);
-        } else {
-          hipLaunchKernelGGL(k64_adj_moment, dim3(nb, bc), dim3(256), 0, stream, (const double2 *)psi,
-                             (const double2 *)lam, n, (int)lo.t0, partial);
-          hipLaunchKernelGGL(k64_adj_cot_final, dim3(bc), dim3(nb >= 256 ? 256 : 64), 0, stream,
-                             (const double2 *)partial, nb, mr, rev->mat_floats, lo.mat_off, out, cot.stride, c_off);
-        }
-      }
-      for (double2 *st : {psi, lam})
-        hipLaunchKernelGGL(k64_op, dim3(gx, bc), dim3(256), 0, stream, st, n, rev->lowered[r],
-                           rmats + (size_t)b0 * rev->mat_floats, rev->mat_floats, rcst, ar, rev->n_slots);
-    }
-    HIPCHK(hipGetLastError());
+  SweepView<double2> s = {(double2 *)(ws + L.psi), (double2 *)(ws + L.lam), (double2 *)(ws + L.partial), n,
+                          f64_adj_blocks(n), 0, stream};
+  for (int b0 = 0; b0 < c.batch; b0 += in_flight) {
+    s.bc = c.batch - b0 < in_flight ? c.batch - b0 : in_flight;
+    rc = f64_adj_round(c, s, b0, fmats, rmats, z, seed.sd);
+    if (rc != QMLE_OK) return rc;
   }
   return QMLE_OK;
 }
@@ -684,8 +597,8 @@ int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_an
                               int batch, const double *d_weights, const uint32_t *obs_wire_masks, int n_obs,
                               const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
                               void *d_workspace, size_t workspace_bytes, qmle_stream stream) {
-  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, nullptr, 0, n_obs,
-                         terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream);
+  return f64_adjoint_run({fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, {obs_wire_masks, nullptr, 0, n_obs},
+                          terms, n_terms, d_grad, n_grad_slots, d_workspace, workspace_bytes, stream, {}});
 }
 
 int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
@@ -693,13 +606,10 @@ int qmle_adjoint_gradient_pauli_f64(qmle_plan *fwd, qmle_plan *rev, const double
                                     const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                                     const qmle_adjoint_term *terms, int n_terms, double *d_grad,
                                     int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws) return QMLE_ERR_INVALID_ARG;
-  const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-  if (rc != QMLE_OK) return rc;
-  if (ws_bytes < qmle_adjoint_pauli_workspace_bytes_f64(fwd, rev, batch, n_obs_terms, n_obs))
-    return QMLE_ERR_INVALID_ARG;
-  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, nullptr, obs_terms, n_obs_terms,
-                         n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes, stream);
+  return adj_entry_pauli<double>(f64_adjoint_run, qmle_adjoint_pauli_workspace_bytes_f64,
+                                 {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                  {nullptr, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad, n_grad_slots, d_ws,
+                                  ws_bytes, stream, {}});
 }
 
 int qmle_adjoint_cotangent_at_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd,
@@ -708,38 +618,22 @@ int qmle_adjoint_cotangent_at_f64(qmle_plan *fwd, qmle_plan *rev, const double *
                                   int n_obs, const qmle_adjoint_term *terms, int n_terms, double *d_grad,
                                   int n_grad_slots, const int32_t *cot_off, int cot_stride, double *d_cot, void *d_ws,
                                   size_t ws_bytes, qmle_stream stream) {
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !cot_off || !d_cot || cot_stride < 1 ||
-      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
-    return QMLE_ERR_INVALID_ARG;
-  if (obs_terms) {
-    const int rc = pauli_seed_check(fwd->n, obs_terms, n_obs_terms, n_obs);
-    if (rc != QMLE_OK) return rc;
-  }
-  if (ws_bytes < qmle_adjoint_cotangent_at_workspace_bytes_f64(fwd, rev, batch, obs_terms ? n_obs_terms : 0, n_obs,
-                                                               cot_has_two_wire(rev, cot_off)))
-    return QMLE_ERR_INVALID_ARG;
-  return f64_adjoint_run(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks, obs_terms,
-                         obs_terms ? n_obs_terms : 0, n_obs, terms, n_terms, d_grad, n_grad_slots, d_ws, ws_bytes,
-                         stream, {cot_off, cot_stride, d_cot});
+  return adj_entry_cotangent_at<double>(f64_adjoint_run, qmle_adjoint_cotangent_at_workspace_bytes_f64,
+                                        {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                         {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
+                                         n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot}});
 }
 
-// the form with one index per 2x2: offsets 8 * index into rows of 8 * n_mat doubles
 int qmle_adjoint_cotangent_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
                                int batch, const double *d_weights, const uint32_t *obs_wire_masks,
                                const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
                                const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
                                const int32_t *mat_out, int n_mat, double *d_cot, void *d_ws, size_t ws_bytes,
                                qmle_stream stream) {
-  // (the argument checks of the function below first, so that a call that is bad in two ways keeps its old code)
-  if (!fwd || !rev || fwd->n != rev->n || batch < 1 || !d_weights || !d_ws || !mat_out || !d_cot || n_mat < 1 ||
-      n_terms != (int)rev->ops.size() || (obs_wire_masks != nullptr) == (obs_terms != nullptr))
-    return QMLE_ERR_INVALID_ARG;
-  std::vector<int32_t> off;
-  const int rc = cot_offsets_of_indices(rev, mat_out, n_mat, off);
-  if (rc != QMLE_OK) return rc;
-  return qmle_adjoint_cotangent_at_f64(fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights, obs_wire_masks,
-                                       obs_terms, n_obs_terms, n_obs, terms, n_terms, d_grad, n_grad_slots, off.data(),
-                                       8 * n_mat, d_cot, d_ws, ws_bytes, stream);
+  return adj_entry_cotangent<double>(f64_adjoint_run, qmle_adjoint_cotangent_at_workspace_bytes_f64,
+                                     {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
+                                      {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
+                                      n_grad_slots, d_ws, ws_bytes, stream, {mat_out, n_mat, d_cot}});
 }
 
 }  // extern "C"

@@ -4,8 +4,12 @@
 //   qmle_tile.hip      LDS-tile passes (k_tile, k_tile2, k_reg_measure*, product passes)
 //   qmle_direct.hip    streaming passes (one gate in place, the Golomb diagonal, fills)
 //   qmle_analysis.hip  measurement / analysis kernels of resident states, samplers
-//   qmle_adjoint.hip   adjoint differentiation
-//   qmle_f64.hip       complex128 engine (its own matrix builder, constants and observable masks)
+//   qmle_adjoint.hip   adjoint differentiation in complex64: one check, one route choice, three routes (LDS, fused
+//                      tile passes, one streaming pass per gate)
+//   qmle_f64.hip       complex128 engine (its own matrix builder and constants) and its adjoint sweep
+//   qmle_adjoint_dev.h what those two sweeps share and nobody else includes: the kernels that are one text in both
+//                      precisions, a sweep's arguments and their checks, the launch pairs of the per-gate sweep, the
+//                      bodies of the extern "C" entry points
 //   qmle_gram.hip      Gram matrices of resident states
 //   qmle_evolve.hip    Hamiltonian time evolution: 2x2 / 4x4 propagators on the fixed Magnus grids (qmle_evolve_magnus)
 //                      the pulse solves with and without sensitivities, and the composition of small circuits

@@ -299,7 +299,7 @@ def test_streaming_sweep_reduction_thresholds(n, seed, monkeypatch):
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("n", [18, 19])
 def test_complex128_sweep_reduction_thresholds(n, seed):
-    """f64_adj_blocks = 128 / 256: k64_adj_final with 64 and with 256 threads"""
+    """f64_adj_blocks = 128 / 256: k_adj_final<double2, double> with 64 and with 256 threads"""
     case = R.cases()[f"threshold_n{n}"]
     compare(case, sweep(case, lowered(case), seed, x64=True)[0], seed, x64=True)
 

@@ -12,7 +12,7 @@ holds pulse leaves -- forces one route with the idioms of tests/test_gpu_adjoint
   positions 13, 6 and 0, the last one inside a float4.
 * fused refusal: with ``adjoint.REV_FLAGS = REV_FLAGS_FUSED`` both attempts of ``run_sweep`` compile the fused plan
   and the request raises ``N.Unsupported``; unforced, ``run_sweep`` returns the streaming result.
-* complex128 (``k64_adj_moment`` / ``k64_adj_cot_final``): ``x64_scope(True)``.
+* complex128 (``k64_adj_moment`` / ``k_adj_cot_final<double2, double>``): ``x64_scope(True)``.
 
 Every entry of every ``G`` and every angle column of the same sweep is compared, row by row, under both seeds.
 Tolerances are ``tests/test_gpu_adjoint_routes.tolerance(n, x64)`` times ``max(1, sum_k |w_k|)`` of the row: 4e-6 up to
