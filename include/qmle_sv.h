@@ -205,7 +205,9 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * "chunk_loop_last_run": how that run ordered its chunks -- "one_stream" (one chunk, the whole state in the
  * LDS, QMLE_NO_CHUNK_OVERLAP=1, or no room for two slots), "staged" (two streams, stage k of a chunk behind
  * stage k of the chunk before it), "free" (two streams and no order between them: the runs that fill a slot once
- * per call, see qmle_workspace_bytes), "none" before the first run.
+ * per call, see qmle_workspace_bytes), "alone" (such runs of at least four chunks whose measuring launch streams
+ * 1 GiB or more: one stream carries the measuring passes back to back and nothing else, the other every chunk's first
+ * pass and epilogue; see qmle_chunk_loop_form), "none" before the first run.
  * Every tile stage lists "fast_ops", the ops of its fast-kernel stream (the concatenated "fast_groups") as
  * [dispatch code, float offset of the op's record in the per-sample matrix row], "unit_form_ops", the indices into
  * that stream of the ops applied in unit-pivot form, and "scale_carriers", the ops that take the product of the
@@ -296,6 +298,13 @@ int qmle_plan_stats(const qmle_plan *plan, int64_t stats[8]);
  * engine keeps no record of workspaces: the token is all there is, and it belongs to the buffer it was made for. */
 size_t qmle_workspace_bytes(const qmle_plan *plan, int batch, int meas_type,
                             int n_obs, int states_in_flight);
+/* Host only (no GPU needed): how a batch run would order its chunks -- the "chunk_loop_last_run" value of
+ * qmle_plan_describe -- for a 256-byte-aligned workspace of exactly the size qmle_workspace_bytes answers for these
+ * arguments, given that the library's two streams can be made.  QMLE_NO_CHUNK_OVERLAP is read as by a run.  Of the
+ * runs that fill a workspace slot once per call, "alone" is taken by those with at least four chunks whose chunk
+ * holds 1 GiB of states or more (in_flight * 8 * 2^n): their measuring pass runs at the memory's rate, and two of
+ * them at once are slower than one after the other.  A static string; "none" for arguments no run would accept. */
+const char *qmle_chunk_loop_form(const qmle_plan *plan, int batch, int meas_type, int states_in_flight);
 
 /* simulate_and_measure over a batch: d_angles is [batch][n_slots] float32,
  * d_out as documented per qmle_meas.  obs_wires is HOST memory.  */

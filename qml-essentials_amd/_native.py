@@ -162,6 +162,7 @@ SYMBOLS = [
     ("qmle_plan_autotune", _I, [_VP, _I, _I, _I, _I, _I, _VP, C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                 C.POINTER(C.c_double)]),
     ("qmle_workspace_bytes", _SZ, [_VP, _I, _I, _I, _I]),
+    ("qmle_chunk_loop_form", C.c_char_p, [_VP, _I, _I, _I]),
     ("qmle_run_batch", _I, [_VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
     ("qmle_run_batch_w", _I, [_VP, _VP, _I, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP, C.POINTER(C.c_uint64)]),
     ("qmle_run_batch_parity", _I, [_VP, _VP, _I, C.POINTER(C.c_uint32), _I, _VP, _VP, _SZ, _VP]),
@@ -473,7 +474,8 @@ class Plan:
         (``measure_tiles_per_workgroup_last_run``, ``measured_from_registers_last_run``,
         ``wave_private_walk_last_run``, ``staging_dma_last_run``, ``last_group_lane_swap_last_run``, and
         ``chunk_loop_last_run``: ``"one_stream"``,
-        ``"staged"`` or ``"free"`` -- how the run ordered its chunks; ``"none"`` before the first run; and
+        ``"staged"``, ``"free"`` or ``"alone"`` -- how the run ordered its chunks (``chunk_loop_form`` answers the same
+        without a run); ``"none"`` before the first run; and
         ``matrices_from_map_last_run``: the matrix builder formed its angles from the affine map, not from a table):
         describe ``executed(meas)``, after the run.  Every tile stage carries ``group_product_form_last_run``: its
         last launch ran the groups that ``product_form_groups`` marks in product form; and
@@ -531,6 +533,12 @@ class Plan:
                 cache.clear()
             v = cache[key] = int(lib().qmle_workspace_bytes(self._h, batch, MEAS[meas], n_obs, states_in_flight))
         return v
+
+    def chunk_loop_form(self, batch: int, meas: str, states_in_flight: int = 0) -> str:
+        """``qmle_chunk_loop_form``: how a run of ``batch`` states on a workspace of ``workspace_bytes(batch, meas,
+        n_obs, states_in_flight)`` would order its chunks -- ``"one_stream"``, ``"staged"``, ``"free"`` or ``"alone"``
+        -- decided on the host, no GPU needed."""
+        return lib().qmle_chunk_loop_form(self._h, int(batch), MEAS[meas], int(states_in_flight)).decode()
 
     def _workspace(self, B: int, meas: str, n_obs: int, states_in_flight: int, workspace, dev):
         """Workspace tensor of the size the engine asks for.  The default asks for state buffers

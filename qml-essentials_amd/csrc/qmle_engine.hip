@@ -524,6 +524,9 @@ struct SideStreams {
   // (fill next to fill, measuring pass next to measuring pass) share the card evenly and gain nothing; one stage
   // apart, the HBM-bound pass of one chunk runs beside the vector-bound pass of the other
   hipEvent_t stage_done[2][kPipeStages] = {};
+  // measuring passes alone on s[0] (ChunkPipeline, the `alone` form): per slot, the chunk's first pass is queued on
+  // s[1] / its measuring pass is queued on s[0]
+  hipEvent_t first_done[2] = {nullptr, nullptr}, walk_done[2] = {nullptr, nullptr};
   bool ok = false;
 };
 static SideStreams *side_streams() {
@@ -537,7 +540,9 @@ static SideStreams *side_streams() {
     bool good = hipEventCreateWithFlags(&x.fork, hipEventDisableTiming) == hipSuccess;
     for (int k = 0; k < 2 && good; ++k) {
       good = hipStreamCreateWithFlags(&x.s[k], hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&x.join[k], hipEventDisableTiming) == hipSuccess;
+             hipEventCreateWithFlags(&x.join[k], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&x.first_done[k], hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&x.walk_done[k], hipEventDisableTiming) == hipSuccess;
       for (int e = 0; e < kPipeStages && good; ++e)
         good = hipEventCreateWithFlags(&x.stage_done[k][e], hipEventDisableTiming) == hipSuccess;
     }
@@ -563,9 +568,10 @@ struct BatchLayout {
 };
 // handed == NULL: the layout for chunks of `asked` states (<= 0: the default), i.e. the size query.  Otherwise the
 // layout for a workspace of *handed bytes (a caller may hand in less than the query said): fewer states per chunk,
-// then one slot instead of two; false: not even one state fits.
+// then one slot instead of two; false: not even one state fits.  side: whether the side streams exist, when the
+// caller knows (qmle_chunk_loop_form, which makes no HIP call); -1: ask for them.
 static bool batch_layout(const qmle_plan *plan, int batch, int meas_type, int asked, const size_t *handed,
-                         BatchLayout &L) {
+                         BatchLayout &L, int side = -1) {
   L.cols = ws_matrix_bytes(plan, batch);
   L.coef = L.cols + align_up((size_t)batch * (size_t)plan->fold_groups * 16 * sizeof(float2), 256);
   const size_t base = ws_mats_bytes(plan, batch);
@@ -608,7 +614,7 @@ static bool batch_layout(const qmle_plan *plan, int batch, int meas_type, int as
   if (two && handed) {
     size_t half = s;
     if (per) half = std::min(std::min(room / per / 2, dflt), (size_t)kMaxGridY);
-    two = !(plan->flags & QMLE_PLAN_NO_FUSION) && half >= 1 && side_streams() != nullptr;
+    two = !(plan->flags & QMLE_PLAN_NO_FUSION) && half >= 1 && (side < 0 ? side_streams() != nullptr : side != 0);
     if (two) s = half;
   }
   L.in_flight = (int)s;
@@ -830,7 +836,7 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
 // the angle table) comes first -- and join it again when the object goes, on the error returns too.  Without side
 // streams (one slot, or a fork that failed) every chunk runs on the caller's stream in slot 0.
 //
-// Between the two streams, two loop forms (form(), reported as chunk_loop_last_run):
+// Between the two streams, three loop forms (chunk_loop_form decides, form() is reported as chunk_loop_last_run):
 //   staged  stage k of chunk i + 1 waits, by event, for stage k of chunk i: at most one launch of each stage in flight,
 //           the chunks one stage apart.  Every run whose chunks are filled one by one.
 //   free    no event between the streams: each stream runs its chunks back to back, and the tail of one chunk's
@@ -839,17 +845,34 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
 //           steady state the staged rule only put one measuring pass behind the other).  What orders such a run: a
 //           slot is one buffer on one stream; the matrix rows, the plan's tables and the observables are read-only;
 //           output rows, partial sums, fold columns and the k_mono_coef rows are per chunk or per slot.
+//   alone   for the runs of the free form whose measuring pass is HBM-bound (a launch alone on the card takes 0.684 ms,
+//           two sharing it 1.394 ms each): s[0] carries the measuring passes and nothing else, one after
+//           the other; s[1] carries every chunk's first pass and epilogue.  Per slot k two events: first_done[k] lets the
+//           measuring pass of a chunk start behind its first pass, walk_done[k] lets the chunk's epilogue start -- and
+//           the first pass of the next chunk in that slot, which stores into the state buffer the pass reads.  The
+//           partial sums of a slot are read by the epilogue of chunk i in front of the first pass of chunk i + 2 on
+//           s[1], which the measuring pass that rewrites them waits for.  s[1] runs in order, so run_batch_chunks
+//           queues the first pass of chunk i + 1 in front of the epilogue of chunk i: behind it, it would wait for
+//           the measuring pass of chunk i and leave s[0] idle while it runs.  (Measured: a first pass is 32 workgroups
+//           of 1024 work items and 128 KiB of LDS, and no CU has that much free while a measuring pass still has
+//           workgroups to place, so it runs in the tail of the pass it was queued beside and ends 28 us behind it;
+//           the next measuring pass starts 50 us after the last one ended.  A stream of the highest priority for
+//           the first passes changes nothing.)
 class ChunkPipeline {
  public:
-  ChunkPipeline(bool two_slots, size_t n_stages, bool free_running, hipStream_t caller_stream) : caller_(caller_stream) {
-    side_ = two_slots ? side_streams() : nullptr;
+  // the parts of a chunk, in the order every form but `alone` queues them: stage 0 (with its fill), the stages behind
+  // it (of a run that takes the `alone` form: the measuring pass), the measurement behind the last stage
+  enum Part { kFirst = 0, kMeasure, kEpilogue };
+  // form: chunk_loop_form's (a fork that fails leaves the one-stream loop)
+  ChunkPipeline(int form, hipStream_t caller_stream) : caller_(caller_stream), form_(form) {
+    side_ = form != kChunkLoopOneStream ? side_streams() : nullptr;
     if (side_ && (hipEventRecord(side_->fork, caller_) != hipSuccess ||
                   hipStreamWaitEvent(side_->s[0], side_->fork, 0) != hipSuccess ||
                   hipStreamWaitEvent(side_->s[1], side_->fork, 0) != hipSuccess)) {
       (void)hipGetLastError();
       side_ = nullptr;
     }
-    piped_ = side_ && !free_running && n_stages <= (size_t)kPipeStages;
+    if (!side_) form_ = kChunkLoopOneStream;
   }
   ChunkPipeline(const ChunkPipeline &) = delete;
   ChunkPipeline &operator=(const ChunkPipeline &) = delete;
@@ -860,25 +883,43 @@ class ChunkPipeline {
         (void)hipStreamWaitEvent(caller_, side_->join[k], 0);
   }
   int slot(int chunk) const { return side_ ? chunk & 1 : 0; }
-  hipStream_t stream(int chunk) const { return side_ ? side_->s[chunk & 1] : caller_; }
-  // Staged form: stage k of chunk i starts behind stage k of chunk i - 1 (the other stream).  The result marks the
-  // stage as queued when it goes out of scope (any exit from the stage's iteration).  Free form: nothing to do.
-  struct StageQueued {
+  hipStream_t stream(int chunk, Part part) const {
+    if (!side_) return caller_;
+    return side_->s[form_ == kChunkLoopAlone ? (part == kMeasure ? 0 : 1) : chunk & 1];
+  }
+  // What a stage or a part waits for is queued here; the result marks it as queued itself when it goes out of scope
+  // (any exit from the stage's iteration / the part's function).
+  struct Queued {
     hipEvent_t ev;
     hipStream_t stream;
-    ~StageQueued() { if (ev) (void)hipEventRecord(ev, stream); }
+    ~Queued() { if (ev) (void)hipEventRecord(ev, stream); }
   };
-  StageQueued begin_stage(int chunk, size_t k) const {
-    if (piped_ && chunk > 0) (void)hipStreamWaitEvent(stream(chunk), side_->stage_done[(chunk - 1) & 1][k], 0);
-    return StageQueued{piped_ ? side_->stage_done[chunk & 1][k] : nullptr, stream(chunk)};
+  // Staged form: stage k of chunk i starts behind stage k of chunk i - 1 (the other stream).  Other forms: nothing to do.
+  Queued begin_stage(int chunk, size_t k, hipStream_t stream) const {
+    const bool piped = form_ == kChunkLoopStaged;
+    if (piped && chunk > 0) (void)hipStreamWaitEvent(stream, side_->stage_done[(chunk - 1) & 1][k], 0);
+    return Queued{piped ? side_->stage_done[chunk & 1][k] : nullptr, stream};
+  }
+  // `alone` form: the events of the chunk's slot (above).  Other forms: nothing to do.
+  Queued begin_part(int chunk, Part part) const {
+    const hipStream_t st = stream(chunk, part);
+    if (form_ != kChunkLoopAlone) return Queued{nullptr, st};
+    const int k = chunk & 1;
+    if (part == kMeasure) {
+      (void)hipStreamWaitEvent(st, side_->first_done[k], 0);
+      return Queued{side_->walk_done[k], st};
+    }
+    // (the slot's first chunk: walk_done[k] has not been recorded in this run, and the fork orders it behind earlier ones)
+    if (part == kEpilogue || chunk >= 2) (void)hipStreamWaitEvent(st, side_->walk_done[k], 0);
+    return Queued{part == kFirst ? side_->first_done[k] : nullptr, st};
   }
   // how this run orders its chunks (LastRun::chunk_loop)
-  int form() const { return !side_ ? kChunkLoopOneStream : piped_ ? kChunkLoopStaged : kChunkLoopFree; }
+  int form() const { return form_; }
 
  private:
   SideStreams *side_;
   hipStream_t caller_;
-  bool piped_;
+  int form_;
 };
 
 // Does a workspace slot still hold what the filled first pass of a chunk left in it -- zeros everywhere outside tile 0
@@ -895,6 +936,29 @@ class ChunkPipeline {
 static bool slot_stays_zeroed(const qmle_plan *plan, bool fuse_expval) {
   // (fuse_expval: QMLE_MEAS_EXPVAL_Z, and the last stage is a tile stage that measures instead of storing)
   return plan->stages.size() == 2 && plan->stages[0].kind == ST_TILE && fuse_expval;
+}
+// <Z> straight out of the last tile pass (no store of the final state, no extra read)
+static bool fuses_expval(const qmle_plan *plan, int meas_type) {
+  return meas_type == QMLE_MEAS_EXPVAL_Z && !plan->stages.empty() && plan->stages.back().kind == ST_TILE;
+}
+
+// Which loop form a batch run of the executed plan takes in layout L (ChunkPipeline is built from the answer; no HIP
+// call, no environment beyond what batch_layout read).  side: the side streams exist.
+//   one_stream  one slot (one chunk, QMLE_NO_CHUNK_OVERLAP, QMLE_PLAN_NO_FUSION, no room, no side streams), or the
+//               whole state in the LDS
+//   staged      chunks that are filled one by one
+//   alone       slots that stay zeroed, a measuring launch that streams at least 1 GiB -- route_tile's threshold for
+//               the non-temporal policy: such a pass runs at the HBM's rate, and two of them at once lose 2-3 % to the
+//               mix -- and at least four chunks: each slot is used twice, and every first pass from
+//               chunk 2 on is queued while a measuring pass runs
+//   free        the other runs whose slots stay zeroed (and staged runs of more stages than there are events)
+static int chunk_loop_form(const qmle_plan *plan, int batch, int meas_type, const BatchLayout &L, bool side) {
+  if (L.in_lds || L.slots != 2 || !side) return kChunkLoopOneStream;
+  if (!slot_stays_zeroed(plan, fuses_expval(plan, meas_type)))
+    return plan->stages.size() <= (size_t)kPipeStages ? kChunkLoopStaged : kChunkLoopFree;
+  const int chunks = (batch + L.in_flight - 1) / L.in_flight;
+  const bool hbm_bound = ((uint64_t)L.in_flight << (plan->n + 3)) >= (1ull << 30);
+  return hbm_bound && chunks >= 4 ? kChunkLoopAlone : kChunkLoopFree;
 }
 
 static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
@@ -943,6 +1007,158 @@ int qmle::run_batch_masks(qmle_plan *plan, const float *d_angles, int batch, int
   return rc;
 }
 
+// The chunks of a batch run whose states are resident in HBM: what the run's chunks share, and a chunk as three issue
+// functions -- first pass, measuring pass, epilogue -- each of which takes its stream, and what it waits for, from the
+// pipeline (ChunkPipeline::Part).  run_batch_chunks calls them chunk by chunk, or one chunk ahead with the first passes.
+struct ChunkRun {
+  qmle_plan *plan;
+  const ChunkPipeline &pipe;
+  const BatchLayout &L;
+  const ObsClass &oc;
+  const float *d_angles;
+  int batch, meas_type;
+  const uint32_t *obs_masks;
+  int n_obs;
+  void *d_out;
+  char *ws;
+  float *d_mats;
+  float2 *d_cols;
+  float *d_coef;
+  const bool fuse_expval = fuses_expval(plan, meas_type);
+  const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
+  const bool by_position = oc.single_bits || oc.semi_single;
+  const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
+  int slot_zeroed[2] = {0, 0};  // states of slot k that hold zeros outside tile 0 of stage 0
+  uint64_t filled_states = 0;   // states written by fills, all chunks
+  bool elided = false;          // a chunk ran without its fill
+
+  struct Chunk {
+    int no, b0, bc, slot;
+    float2 *stc;
+    void *d_partial;
+    const float *mats, *ang;
+    float2 *cols;
+    bool initialised;
+    TileRoute route;  // of the chunk's latest tile pass
+  };
+  Chunk chunk(int i) const {
+    Chunk c;
+    c.no = i;
+    c.b0 = i * L.in_flight;
+    c.bc = std::min(batch - c.b0, L.in_flight);
+    c.slot = pipe.slot(i);
+    const size_t D = (size_t)1 << plan->n;
+    c.stc = meas_type == QMLE_MEAS_STATE ? (float2 *)d_out + (size_t)c.b0 * D : (float2 *)(ws + L.states[c.slot]);
+    c.d_partial = ws + L.partial[c.slot];
+    c.mats = d_mats + (size_t)c.b0 * plan->mat_floats;
+    c.ang = d_angles ? d_angles + (size_t)c.b0 * plan->n_slots : nullptr;
+    c.cols = d_cols ? d_cols + (size_t)c.b0 * plan->fold_groups * 16 : nullptr;
+    c.initialised = false;
+    return c;
+  }
+
+  int stage(Chunk &c, size_t si, hipStream_t stream) {
+    const Stage &st = plan->stages[si];
+    const ChunkPipeline::Queued stage_queued = pipe.begin_stage(c.no, si, stream);
+    ProfScope prof_scope(plan, (int)si, stream);
+    if (st.kind != ST_TILE) {
+      if (!c.initialised) {
+        launch_init_zero(c.stc, plan->n, c.bc, stream);
+        c.initialised = true;
+      }
+      return run_stage_inplace(plan, st, c.stc, c.mats, c.ang, c.bc, stream);
+    }
+    const bool last = si + 1 == plan->stages.size();
+    // the last pass stores the state AND reports its tile's Meyer-Wallach sums (one row per tile), or measures
+    // <Z> instead of storing
+    const bool last_mw = fuse_mw && last, last_fused = !fuse_mw && fuse_expval && last;
+    const TileBuffers tb{c.stc, c.mats, c.ang, last_mw || last_fused ? c.d_partial : nullptr,
+                         last_fused ? obs_masks : nullptr, c.cols, d_coef + (size_t)c.b0 * 32};
+    TileRequest rq;
+    rq.batch = c.bc;
+    rq.init_zero = !c.initialised;
+    rq.meas = last_mw ? TM_STORE_MW : !last_fused ? TM_STORE : by_position ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
+    rq.n_obs = last_fused ? n_obs : 0;
+    rq.from_zero = true;
+    rq.fold_cols = c.cols != nullptr;
+    rq.multi_rows = last_mw || (last_fused && (oc.single_bits || rq.meas == TM_EXPVAL_MASKS));
+    rq.semi_single = oc.semi_single;
+    const bool reuse = !last_mw && si == 0 && reuse_zeros;
+    if (reuse) rq.zeroed_states = slot_zeroed[c.slot];
+    const int rc = launch_tile(plan, si, tb, rq, stream, &c.route);
+    note_product_form(plan, si, c.route, meas_type);
+    if (last_fused && !is_reg_measure(c.route.family)) {  // (k_reg_measure* is no tile walk: the report stays "no such pass")
+      plan->last_run.measure_tpw = 1 << c.route.row_shift;
+      plan->last_run.measure_regs = c.route.from_regs;
+      plan->last_run.wave_private = c.route.wave_private;
+      plan->last_run.staging_dma = (c.route.walk & kWalkDma) != 0;
+      plan->last_run.lane_swap = (c.route.walk & kWalkLaneSwap) != 0;
+      plan->last_run.walk_kernel = c.route.walk_kernel;
+    }
+    if (reuse && c.route.fill) {
+      slot_zeroed[c.slot] = c.bc;
+      filled_states += (uint64_t)c.bc;
+    }
+    if (reuse && c.route.fill_elided) elided = true;
+    c.initialised = true;
+    return rc;
+  }
+
+  // stage 0, with the fill if launch_tile asks for one
+  int first_pass(Chunk &c) {
+    if (plan->stages.empty()) return QMLE_OK;
+    const ChunkPipeline::Queued queued = pipe.begin_part(c.no, ChunkPipeline::kFirst);
+    return stage(c, 0, queued.stream);
+  }
+  // the stages behind it; of a run whose slots stay zeroed, the measuring pass
+  int measuring_pass(Chunk &c) {
+    const ChunkPipeline::Queued queued = pipe.begin_part(c.no, ChunkPipeline::kMeasure);
+    for (size_t si = 1; si < plan->stages.size(); ++si) {
+      const int rc = stage(c, si, queued.stream);
+      if (rc != QMLE_OK) return rc;
+    }
+    return QMLE_OK;
+  }
+  // measure the chunk
+  int epilogue(Chunk &c) {
+    const ChunkPipeline::Queued queued = pipe.begin_part(c.no, ChunkPipeline::kEpilogue);
+    const hipStream_t stream = queued.stream;
+    const int n = plan->n;
+    const size_t D = (size_t)1 << n;
+    int rc = QMLE_OK;
+    if (!c.initialised) launch_init_zero(c.stc, n, c.bc, stream);
+    if (meas_type == QMLE_MEAS_PROBS) {
+      const uint64_t tc = (uint64_t)c.bc * (D / 2);
+      launch_probs(c.stc, (float *)d_out + (size_t)c.b0 * D, tc, stream);
+    } else if (meas_type == QMLE_MEAS_EXPVAL_Z && fuse_expval) {
+      // column of the 33-float row: the bit's sum, or (masks, k_reg_measure) the observable's own
+      const bool reg_measure = is_reg_measure(c.route.family);
+      const int tiles = (1 << (n - plan->stages.back().T)) >> c.route.row_shift;
+      launch_expval_final((const float *)c.d_partial, tiles, c.bc, n_obs,
+                          by_position && !reg_measure ? oc.by_position : oc.by_index,
+                          (float *)d_out + (size_t)c.b0 * n_obs, stream);
+    } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
+      rc = oc.single_bits
+               ? run_expval(c.stc, n, c.bc, oc.by_position.bits, n_obs, (float *)d_out + (size_t)c.b0 * n_obs,
+                            c.d_partial, L.partial_bytes, stream)
+               : run_parity_pos(c.stc, n, c.bc, obs_masks, n_obs, (float *)d_out + (size_t)c.b0 * n_obs,
+                                c.d_partial, L.partial_bytes, stream);
+      if (rc != QMLE_OK) return rc;
+    } else if (meas_type == QMLE_MEAS_MEYER_WALLACH) {
+      rc = fuse_mw ? run_mw_fused(c.stc, n, c.bc, plan->stages.back(), c.route.row_shift, c.d_partial, L.partial_bytes,
+                                  (float *)d_out + (size_t)c.b0 * (n + 1), stream)
+                   : run_mw_resident(c.stc, n, c.bc, c.d_partial, L.partial_bytes,
+                                     (float *)d_out + (size_t)c.b0 * (n + 1), stream);
+      if (rc != QMLE_OK) return rc;
+    } else if (meas_type == QMLE_MEAS_DENSITY) {
+      if (n > 15) return QMLE_ERR_UNSUPPORTED;
+      launch_density(c.stc, (float2 *)d_out + (size_t)c.b0 * D * D, n, c.bc, stream);
+    }
+    HIPCHK(hipGetLastError());
+    return QMLE_OK;
+  }
+};
+
 static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, int meas_type,
                             const uint32_t *obs_masks, int n_obs, void *d_out, void *d_workspace,
                             size_t workspace_bytes, hipStream_t caller_stream, uint64_t token_in, uint64_t *token_out) {
@@ -974,124 +1190,61 @@ static int run_batch_chunks(qmle_plan *plan, const float *d_angles, int batch, i
                          caller_stream);
 
   // ---- general path: states resident in HBM, sample-major chunks ----------------
-  const size_t D = (size_t)1 << n;
-  // <Z> straight out of the last tile pass (no store of the final state, no extra read)
-  const bool fuse_expval = meas_type == QMLE_MEAS_EXPVAL_Z && !plan->stages.empty() &&
-                           plan->stages.back().kind == ST_TILE;
-  const bool fuse_mw = meas_type == QMLE_MEAS_MEYER_WALLACH && plan_mw_fusable(plan);
-  const bool by_position = oc.single_bits || oc.semi_single;
-  const bool reuse_zeros = slot_stays_zeroed(plan, fuse_expval);
-  ChunkPipeline pipe(L.slots == 2, plan->stages.size(), /*free_running=*/reuse_zeros, caller_stream);
+  ChunkPipeline pipe(chunk_loop_form(plan, batch, meas_type, L, /*side=*/L.slots == 2), caller_stream);
   plan->last_run.chunk_loop = pipe.form();
+  ChunkRun run{plan, pipe, L, oc, d_angles, batch, meas_type, obs_masks, n_obs, d_out, ws, d_mats, d_cols, d_coef};
+  const bool reuse_zeros = run.reuse_zeros;
   // Clean slots: slot_zeroed[k] states of slot k hold zeros outside tile 0 of stage 0.  The caller owns the workspace
   // between calls, so a slot's first chunk is filled -- unless the caller hands back the token of the call before
   // (qmle_run_batch_w: nobody wrote the workspace since, and this call is ordered behind that one) and the token carries
-  // this call's fingerprint: then the slots start as that call left them.  A slot is one buffer on one stream --
-  // ChunkPipeline::slot / stream -- so its chunks run in order whichever loop form this is.
+  // this call's fingerprint: then the slots start as that call left them.  A slot's first passes are queued in chunk
+  // order on one stream, and each behind the slot's measuring pass before it, whichever loop form this is.
   const uint64_t fingerprint = ws_fingerprint(plan, batch, meas_type, reuse_zeros, L, ws, workspace_bytes);
-  int slot_zeroed[2] = {0, 0};
   if (reuse_zeros && (token_in & ~(uint64_t)15) == fingerprint)
-    for (int k = 0; k < L.slots; ++k) slot_zeroed[k] = ws_token_states((token_in >> (2 * k)) & 3u, batch, L);
-  uint64_t filled_states = 0;  // states written by fills, all chunks
-  bool elided = false;         // a chunk ran without its fill
-  int chunk_no = 0;
-  for (int b0 = 0; b0 < batch; b0 += L.in_flight, ++chunk_no) {
-    const int bc = std::min(batch - b0, L.in_flight);
-    const hipStream_t stream = pipe.stream(chunk_no);
-    const int slot = pipe.slot(chunk_no);
-    float2 *stc = meas_type == QMLE_MEAS_STATE ? (float2 *)d_out + (size_t)b0 * D : (float2 *)(ws + L.states[slot]);
-    void *d_partial = ws + L.partial[slot];
-    const float *mats = d_mats + (size_t)b0 * plan->mat_floats;
-    const float *ang = d_angles ? d_angles + (size_t)b0 * plan->n_slots : nullptr;
-    float2 *cols = d_cols ? d_cols + (size_t)b0 * plan->fold_groups * 16 : nullptr;
-    bool initialised = false;
-    TileRoute route;  // of the chunk's latest tile pass
-    for (size_t si = 0; si < plan->stages.size(); ++si) {
-      const Stage &st = plan->stages[si];
-      const ChunkPipeline::StageQueued stage_queued = pipe.begin_stage(chunk_no, si);
-      ProfScope prof_scope(plan, (int)si, stream);
-      if (st.kind == ST_TILE) {
-        const bool last = si + 1 == plan->stages.size();
-        // the last pass stores the state AND reports its tile's Meyer-Wallach sums (one row per tile), or measures
-        // <Z> instead of storing
-        const bool last_mw = fuse_mw && last, last_fused = !fuse_mw && fuse_expval && last;
-        const TileBuffers tb{stc, mats, ang, last_mw || last_fused ? d_partial : nullptr, last_fused ? obs_masks : nullptr,
-                             cols, d_coef + (size_t)b0 * 32};
-        TileRequest rq;
-        rq.batch = bc;
-        rq.init_zero = !initialised;
-        rq.meas = last_mw ? TM_STORE_MW : !last_fused ? TM_STORE : by_position ? TM_EXPVAL_PARTIAL : TM_EXPVAL_MASKS;
-        rq.n_obs = last_fused ? n_obs : 0;
-        rq.from_zero = true;
-        rq.fold_cols = cols != nullptr;
-        rq.multi_rows = last_mw || (last_fused && (oc.single_bits || rq.meas == TM_EXPVAL_MASKS));
-        rq.semi_single = oc.semi_single;
-        const bool reuse = !last_mw && si == 0 && reuse_zeros;
-        if (reuse) rq.zeroed_states = slot_zeroed[slot];
-        rc = launch_tile(plan, si, tb, rq, stream, &route);
-        note_product_form(plan, si, route, meas_type);
-        if (last_fused && !is_reg_measure(route.family)) {  // (k_reg_measure* is no tile walk: the report stays "no such pass")
-          plan->last_run.measure_tpw = 1 << route.row_shift;
-          plan->last_run.measure_regs = route.from_regs;
-          plan->last_run.wave_private = route.wave_private;
-          plan->last_run.staging_dma = (route.walk & kWalkDma) != 0;
-          plan->last_run.lane_swap = (route.walk & kWalkLaneSwap) != 0;
-          plan->last_run.walk_kernel = route.walk_kernel;
-        }
-        if (reuse && route.fill) {
-          slot_zeroed[slot] = bc;
-          filled_states += (uint64_t)bc;
-        }
-        if (reuse && route.fill_elided) elided = true;
-        initialised = true;
-      } else {
-        if (!initialised) {
-          launch_init_zero(stc, n, bc, stream);
-          initialised = true;
-        }
-        rc = run_stage_inplace(plan, st, stc, mats, ang, bc, stream);
+    for (int k = 0; k < L.slots; ++k) run.slot_zeroed[k] = ws_token_states((token_in >> (2 * k)) & 3u, batch, L);
+  const int chunks = (batch + L.in_flight - 1) / L.in_flight;
+  if (pipe.form() == kChunkLoopAlone) {
+    // one chunk ahead on the stream of the first passes (ChunkPipeline)
+    ChunkRun::Chunk cur = run.chunk(0), next = cur;
+    rc = run.first_pass(cur);
+    for (int i = 0; i < chunks && rc == QMLE_OK; ++i, cur = next) {
+      if (i + 1 < chunks) {
+        next = run.chunk(i + 1);
+        rc = run.first_pass(next);
       }
-      if (rc != QMLE_OK) return rc;
+      if (rc == QMLE_OK) rc = run.measuring_pass(cur);
+      if (rc == QMLE_OK) rc = run.epilogue(cur);
     }
-    if (!initialised) launch_init_zero(stc, n, bc, stream);
-    // measure this chunk
-    if (meas_type == QMLE_MEAS_PROBS) {
-      const uint64_t tc = (uint64_t)bc * (D / 2);
-      launch_probs(stc, (float *)d_out + (size_t)b0 * D, tc, stream);
-    } else if (meas_type == QMLE_MEAS_EXPVAL_Z && fuse_expval) {
-      // column of the 33-float row: the bit's sum, or (masks, k_reg_measure) the observable's own
-      const bool reg_measure = is_reg_measure(route.family);
-      const int tiles = (1 << (n - plan->stages.back().T)) >> route.row_shift;
-      launch_expval_final((const float *)d_partial, tiles, bc, n_obs, by_position && !reg_measure ? oc.by_position : oc.by_index,
-                          (float *)d_out + (size_t)b0 * n_obs, stream);
-    } else if (meas_type == QMLE_MEAS_EXPVAL_Z) {
-      rc = oc.single_bits
-               ? run_expval(stc, n, bc, oc.by_position.bits, n_obs, (float *)d_out + (size_t)b0 * n_obs,
-                            d_partial, L.partial_bytes, stream)
-               : run_parity_pos(stc, n, bc, obs_masks, n_obs, (float *)d_out + (size_t)b0 * n_obs,
-                                d_partial, L.partial_bytes, stream);
-      if (rc != QMLE_OK) return rc;
-    } else if (meas_type == QMLE_MEAS_MEYER_WALLACH) {
-      rc = fuse_mw ? run_mw_fused(stc, n, bc, plan->stages.back(), route.row_shift, d_partial, L.partial_bytes,
-                                  (float *)d_out + (size_t)b0 * (n + 1), stream)
-                   : run_mw_resident(stc, n, bc, d_partial, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
-      if (rc != QMLE_OK) return rc;
-    } else if (meas_type == QMLE_MEAS_DENSITY) {
-      if (n > 15) return QMLE_ERR_UNSUPPORTED;
-      launch_density(stc, (float2 *)d_out + (size_t)b0 * D * D, n, bc, stream);
+  } else {
+    for (int i = 0; i < chunks && rc == QMLE_OK; ++i) {
+      ChunkRun::Chunk c = run.chunk(i);
+      rc = run.first_pass(c);
+      if (rc == QMLE_OK) rc = run.measuring_pass(c);
+      if (rc == QMLE_OK) rc = run.epilogue(c);
     }
-    HIPCHK(hipGetLastError());
   }
+  if (rc != QMLE_OK) return rc;
   // what qmle_plan_describe reports as stage 0's written bytes (a report: nothing in the engine reads it): the fills
   // and tile-0 stores of this run per state when fills were left out, else 0 = the fresh-buffer figure
-  if (elided)
+  if (run.elided)
     plan->last_run.stage0_written =
-        ((filled_states << (n + 3)) + ((uint64_t)batch << (plan->stages[0].T + 3))) / (uint64_t)batch;
+        ((run.filled_states << (n + 3)) + ((uint64_t)batch << (plan->stages[0].T + 3))) / (uint64_t)batch;
   uint64_t codes = 0;
   if (reuse_zeros)
-    for (int k = 0; k < L.slots; ++k) codes |= ws_token_code(slot_zeroed[k], batch, L) << (2 * k);
+    for (int k = 0; k < L.slots; ++k) codes |= ws_token_code(run.slot_zeroed[k], batch, L) << (2 * k);
   *token_out = codes ? fingerprint | codes : 0;  // (no zeros to hand on: no token)
   return QMLE_OK;
+}
+
+// chunk_loop_form for a 256-byte-aligned workspace of the size the query answers, given that the side streams exist
+const char *qmle_chunk_loop_form(const qmle_plan *plan, int batch, int meas_type, int states_in_flight) {
+  if (!plan || batch < 1 || meas_type < QMLE_MEAS_STATE || meas_type > QMLE_MEAS_MEYER_WALLACH)
+    return kChunkLoopNames[kChunkLoopNone];
+  const size_t bytes = qmle_workspace_bytes(plan, batch, meas_type, 0, states_in_flight);
+  const qmle_plan *exec = qmle_plan_executed(const_cast<qmle_plan *>(plan), meas_type);
+  BatchLayout L;
+  if (!batch_layout(exec, batch, meas_type, 0, &bytes, L, /*side=*/1)) return kChunkLoopNames[kChunkLoopNone];
+  return kChunkLoopNames[chunk_loop_form(exec, batch, meas_type, L, /*side=*/true)];
 }
 
 // Apply the plan's passes IN PLACE to resident states (no |0..0> initialisation, no

@@ -261,8 +261,8 @@ struct DevicePlan {  // lazily created by the first run on a device
 };
 
 // How a batch run ordered its chunks (ChunkPipeline, qmle_engine.hip; LastRun::chunk_loop)
-enum { kChunkLoopNone = 0, kChunkLoopOneStream, kChunkLoopStaged, kChunkLoopFree };
-constexpr const char *kChunkLoopNames[] = {"none", "one_stream", "staged", "free"};
+enum { kChunkLoopNone = 0, kChunkLoopOneStream, kChunkLoopStaged, kChunkLoopFree, kChunkLoopAlone };
+constexpr const char *kChunkLoopNames[] = {"none", "one_stream", "staged", "free", "alone"};
 
 // What the plan's last run did (describe_plan's *_last_run keys).  Report only: the engine writes it from
 // the routes launch_tile returns (TileRoute, qmle_host.h) and never reads it.  run_batch_masks resets all of it first.

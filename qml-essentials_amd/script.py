@@ -117,9 +117,9 @@ class CompiledCall:
         """``run(workspace, token) -> (out, workspace, token)`` on the workspace this call keeps.
 
         One ``(workspace tensor, token)`` pair is kept, for the latest ``(batch, measurement, n_obs)`` on the current
-        stream, and only when the executed plan reports that run's chunk loop as ``"free"``: the runs whose workspace
-        slots stay zeroed, so that the next call fills nothing (``qmle_run_batch_w``).  Every other run leaves nothing
-        behind and allocates as before.  Only one call per process holds a pair at a time.  The pair goes when the key
+        stream, and only when the executed plan reports that run's chunk loop as ``"free"`` or ``"alone"``: the runs
+        whose workspace slots stay zeroed, so that the next call fills nothing (``qmle_run_batch_w``).  Every other run
+        leaves nothing behind and allocates as before.  Only one call per process holds a pair at a time.  The pair goes when the key
         changes (before the new run allocates), when the autotuner re-schedules the plan (``Plan.run`` then answers with
         a workspace and token of its own) and on any exception."""
         # only <Z> out of a tiled plan's last pass can leave zeroed slots behind: everything else runs as it always
@@ -139,7 +139,7 @@ class CompiledCall:
         del kept
         out, ws_used, tok = run(ws, tok)
         if tok and (free is None or ws_used is not ws):  # (a token of 0: the run left nothing to keep)
-            free = self.plan.executed(kind).describe()["stages"][-1].get("chunk_loop_last_run") == "free"
+            free = self.plan.executed(kind).describe()["stages"][-1].get("chunk_loop_last_run") in ("free", "alone")
         if tok and free:
             # one kept workspace per process: the call that held the last one lets go of it
             last = CompiledCall._holder() if CompiledCall._holder is not None else None
