@@ -518,6 +518,23 @@ size_t qmle_meyer_wallach_workspace_bytes(int n_qubits, int batch);
  * bench.py's bytes-moved accounting): the passes of the tile scheme from 12 qubits on, one
  * cache-resident sweep per wire below */
 int qmle_meyer_wallach_reads(int n_qubits);
+/* Host only (no GPU needed): what a Meyer-Wallach call decides, as JSON written like qmle_plan_tile_route's (returns
+ * the bytes needed, or an error < 0).  plan == NULL: qmle_meyer_wallach on `batch` resident states of `n_qubits`
+ * ("route": "standalone").  Otherwise (n_qubits is ignored) the QMLE_MEAS_MEYER_WALLACH epilogue of a batch run of
+ * the plan it executes on a chunk of `batch` states: behind the last tile pass ("route": "fused"; `row_shift`: a row
+ * of that pass covers 2^row_shift tiles, the "row_shift" of qmle_plan_tile_route for meas 5; QMLE_MW_FUSE_TILED is
+ * not read), or on the stored states where that pass cannot report its tile ("route": "resident").  `request_flags`:
+ * QMLE_ROUTE_NO_MW_LEAN, nothing else.  Keys: "fusable", "lean" (the first later read reports positions 0..3);
+ * "first": the stand-alone first read, or null; "reads": the later reads, in launch order; a read is {"kind":
+ * "first" | "later" | "later_low", "lo", "lo2" (its tile: positions 0..3, lo..lo+3, lo2..lo2+3), "q" (2^q tiles per
+ * workgroup), "rows" (per state), "stride" (floats per row), "nt" (at least 1 GiB per launch: streamed past the
+ * caches)}; "positions"[p]: {"read": the later read that reports position p's cross terms, -1: the first read or the
+ * producing pass, "col": its column there}; "finish": "whole-state" | "columns" | "per-position" (fused),
+ * "standalone", "per-wire-sweeps" (below 12 qubits); "slices" of the finish; "regions": [{"name", "offset", "bytes",
+ * "doubles"}], what the call places in its workspace; "end": the bytes the call checks its workspace against;
+ * "total_bytes": what the size query reports for it (>= "end"). */
+int qmle_meyer_wallach_describe(const qmle_plan *plan, int n_qubits, int batch, int row_shift, unsigned request_flags,
+                                char *buf, size_t cap);
 /* Host only, no device work: out[i] = the i-th value of
  * numpy.random.Generator(numpy.random.Philox(key=key)).uniform(low, high, n).astype(float32),
  * bit for bit (Philox4x64-10, numpy's counter and double conventions).  The parameter sampler

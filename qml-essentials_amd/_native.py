@@ -204,6 +204,7 @@ SYMBOLS = [
     ("qmle_meyer_wallach", _I, [_VP, _I, _I, _VP, _VP, _VP, _SZ, _VP]),
     ("qmle_meyer_wallach_workspace_bytes", _SZ, [_I, _I]),
     ("qmle_meyer_wallach_reads", _I, [_I]),
+    ("qmle_meyer_wallach_describe", _I, [_VP, _I, _I, _I, C.c_uint, C.c_char_p, _SZ]),
     ("qmle_philox_uniform_f32", _I, [_VP, C.c_uint64, C.c_double, C.c_double, _VP]),
     ("qmle_philox_uniform_f32_device", _I, [_VP, C.c_uint64, C.c_double, C.c_double, _VP, _VP]),
     ("qmle_philox_uniform_f32_device_key", _I, [_VP, C.c_uint64, C.c_double, C.c_double, _VP, _VP]),
@@ -1354,6 +1355,17 @@ def meyer_wallach(states, return_purities: bool = False):
                                    C.c_void_p(ws.data_ptr()), wsb, _stream_ptr()),
           "qmle_meyer_wallach")
     return (out, pur) if return_purities else out
+
+
+def mw_describe(n_qubits: int, batch: int = 1, plan: Optional["Plan"] = None, row_shift: int = 0, flags: int = 0) -> dict:
+    """``qmle_meyer_wallach_describe`` as a dict (host only): the reads, the source of every position, the finish and
+    the workspace regions of ``meyer_wallach`` on resident states, or of the Meyer-Wallach epilogue of ``plan``."""
+    h = plan._h if plan is not None else None
+    need = lib().qmle_meyer_wallach_describe(h, int(n_qubits), int(batch), int(row_shift), int(flags), None, 0)
+    check(min(need, 0), "qmle_meyer_wallach_describe")
+    buf = C.create_string_buffer(need + 1)
+    lib().qmle_meyer_wallach_describe(h, int(n_qubits), int(batch), int(row_shift), int(flags), buf, need + 1)
+    return json.loads(buf.value.decode())
 
 
 def mw_reads(n_qubits: int) -> int:

@@ -957,7 +957,7 @@ static int chunk_loop_form(const qmle_plan *plan, int batch, int meas_type, cons
   if (!slot_stays_zeroed(plan, fuses_expval(plan, meas_type)))
     return plan->stages.size() <= (size_t)kPipeStages ? kChunkLoopStaged : kChunkLoopFree;
   const int chunks = (batch + L.in_flight - 1) / L.in_flight;
-  const bool hbm_bound = ((uint64_t)L.in_flight << (plan->n + 3)) >= (1ull << 30);
+  const bool hbm_bound = launch_streams_past_caches((uint64_t)L.in_flight, plan->n);
   return hbm_bound && chunks >= 4 ? kChunkLoopAlone : kChunkLoopFree;
 }
 

@@ -4,6 +4,8 @@
 //   qmle_tile.hip      LDS-tile passes (k_tile, k_tile2, k_reg_measure*, product passes)
 //   qmle_direct.hip    streaming passes (one gate in place, the Golomb diagonal, fills)
 //   qmle_analysis.hip  measurement / analysis kernels of resident states, samplers
+//   qmle_mw.hip        Meyer-Wallach: read kernels of resident states, the sums behind a producing tile pass, and
+//                      their host path (one plan of the reads, one workspace layout per route, three finishes)
 //   qmle_adjoint.hip   adjoint differentiation in complex64: one check, one route choice, three routes (LDS, fused
 //                      tile passes, one streaming pass per gate)
 //   qmle_f64.hip       complex128 engine (its own matrix builder and constants) and its adjoint sweep
@@ -113,6 +115,8 @@ inline bool align_workspace(char *&ws, size_t &bytes) {
   bytes -= mis;
   return true;
 }
+// At least 1 GiB per launch streams past the caches: `states` states of n qubits, 8 bytes an amplitude.
+inline bool launch_streams_past_caches(uint64_t states, int n) { return (states << (n + 3)) >= (1ull << 30); }
 // FNV-1a over a byte range; `h`: the hash so far, to run several ranges into one value
 inline uint64_t fnv1a(const void *data, size_t bytes, uint64_t h = 1469598103934665603ull) {
   const unsigned char *c = (const unsigned char *)data;
@@ -224,6 +228,8 @@ void launch_expval_final(const float *partial, int n_rows, int batch, int n_obs,
                          float *d_out, hipStream_t stream);
 void launch_probs(const float2 *states, float *d_out, uint64_t total_chunks, hipStream_t stream);
 void launch_density(const float2 *states, float2 *d_out, int n, int batch, hipStream_t stream);
+
+// ---- qmle_mw.hip ----
 // Meyer-Wallach behind the pass that produced the state (QMLE_MEAS_MEYER_WALLACH): `last` left one
 // row per tile at the start of `ws` (TM_STORE_MW / TM_MW_ONLY); d_out [batch][n + 1] = (Q, purities by wire)
 bool mw_fusable(int n, const Stage &last);

@@ -2175,7 +2175,7 @@ static TileRoute route_reg_measure(const qmle_plan *p, const Stage &st, TileFami
       // live amplitudes per launch >= 1 GiB: stream them past the caches (0.427 -> 0.38 ms per
       // 256 states of K2; k_direct_1q's measurements say the opposite below the cache size)
       const int n_live = p->n - __builtin_popcount(st.zero_in);
-      r.nt = ((uint64_t)batch << (n_live + 3)) >= (1ull << 30);
+      r.nt = launch_streams_past_caches((uint64_t)batch, n_live);
     }
   }
   r.grid_x = 1u << (n_outer - q);
@@ -2245,7 +2245,7 @@ TileRoute route_tile(const qmle_plan *p, size_t si, const TileRequest &rq) {
   // (the initialising pass only writes, and what it writes is read back by the next pass: plain
   // stores are 1.5 us per 2^24-amplitude state faster there, 22.9 vs 24.4)
   r.nt = st.T < p->n && !(from_zero && st.zero_in) && !init_zero &&
-         ((uint64_t)batch << (p->n + 3)) >= (1ull << 30);
+         launch_streams_past_caches((uint64_t)batch, p->n);
   r.mw_lean = meas == TM_STORE_MW && !rq.no_mw_lean && mw_lean_layout(p->n, st);
   // the state this pass stores is read back by the later reads only after >= 1 GiB more has been written: streaming
   // stores keep it from lingering dirty in the Infinity Cache, where its write-back would run into the first
@@ -2254,7 +2254,7 @@ TileRoute route_tile(const qmle_plan *p, size_t si, const TileRequest &rq) {
   // behind it): whatever reads them next -- the stand-alone Meyer-Wallach reads, a <Z> sweep, the caller -- finds
   // HBM idle instead of a write-back in progress.
   if ((meas == TM_STORE_MW || (meas == TM_STORE && !st.next_tile && !init_zero)) && st.T < p->n &&
-      ((uint64_t)batch << (p->n + 3)) >= (1ull << 30))
+      launch_streams_past_caches((uint64_t)batch, p->n))
     r.nt = true;
   // 16x16 Kraus superoperators: separate instantiation, so that the common kernel keeps its register budget
   for (int g = st.grp_begin; g < st.grp_end; ++g)
@@ -2312,7 +2312,7 @@ TileRoute route_tile(const qmle_plan *p, size_t si, const TileRequest &rq) {
       const int n_out = n_live + 4 * G;  // amplitudes written per state = 2^n_out
       // >= 1 GiB written per launch: non-temporal stores (the pass itself is no faster, the
       // measuring pass that follows is: 3.13 -> 2.99 ms per K2 step)
-      r.nt = ((uint64_t)batch << (n_out + 3)) >= (1ull << 30);
+      r.nt = launch_streams_past_caches((uint64_t)batch, n_out);
       return r;
     }
     r.family = TF_TILE_PRODUCT;

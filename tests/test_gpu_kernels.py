@@ -351,6 +351,40 @@ def test_meyer_wallach_lds_tile_path(n):
     assert np.abs(q.cpu().numpy() - want_q).max() < 1e-6
 
 
+@pytest.mark.parametrize("n", [5, 12, 17])
+def test_meyer_wallach_workspace_of_the_reported_size(n):
+    """qmle_meyer_wallach through the raw ABI on a workspace of exactly the reported size, of one byte less (the
+    reported size has always held padding, and a call one byte short was accepted before too) and of exactly the bytes
+    the call places (the description's "end"): QMLE_OK and the same numbers each time; one byte below "end" is
+    QMLE_ERR_WORKSPACE (tests/test_mw_layout_cpu.py has the refusals that need no GPU)."""
+    import ctypes as C
+
+    import torch
+
+    from qml_essentials_amd import _native as N
+
+    B = 3
+    rng = np.random.default_rng(n)
+    st = rng.normal(size=(B, 2**n)) + 1j * rng.normal(size=(B, 2**n))
+    st /= np.linalg.norm(st, axis=1, keepdims=True)
+    dev = torch.from_numpy(st.astype(np.complex64)).cuda()
+    total = int(N.lib().qmle_meyer_wallach_workspace_bytes(n, B))
+    end = N.mw_describe(n, B)["end"]
+    assert end < total
+    ws = torch.empty(total, dtype=torch.uint8, device="cuda")
+    got = []
+    for handed in (total, total - 1, end, end - 1):
+        q = torch.zeros(B, dtype=torch.float32, device="cuda")
+        pur = torch.zeros((B, n), dtype=torch.float32, device="cuda")
+        rc = N.lib().qmle_meyer_wallach(C.c_void_p(dev.data_ptr()), n, B, C.c_void_p(q.data_ptr()),
+                                        C.c_void_p(pur.data_ptr()), C.c_void_p(ws.data_ptr()), handed, N._stream_ptr())
+        assert rc == (-7 if handed == end - 1 else 0), (handed, rc)
+        got.append(np.concatenate([q.cpu().numpy()[:, None], pur.cpu().numpy()], axis=1))
+    want_p = np.stack([OA.qubit_purities_pure(s, n) for s in st])
+    assert np.abs(got[0][:, 1:] - want_p).max() < 1e-6
+    assert np.array_equal(got[0], got[1]) and np.array_equal(got[0], got[2]) and not got[3].any()
+
+
 @pytest.mark.parametrize("n", [3, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24])
 def test_meyer_wallach_out_of_the_producing_pass(n, monkeypatch):
     """QMLE_MEAS_MEYER_WALLACH: the plan's last tile pass reports its own tile's sums from LDS
