@@ -221,7 +221,10 @@ qmle_plan *qmle_plan_executed(qmle_plan *plan, int meas_type);
  * closing diagonal (see qmle_group_product_form_measured); "measured_form_last_run": the last batch run did so for
  * its last stage and ran those records (false on every other stage and after every other kind of run).
  * "walk_kernel_last_run" (last stage): the fused <Z> pass of the last batch run ran in the straight-line kernel of
- * measuring walks whose groups all run in product form (see "walk_kernel" of qmle_plan_tile_route). */
+ * measuring walks whose groups all run in product form (see "walk_kernel" of qmle_plan_tile_route).
+ * "mw_finish_last_run" (last stage): the finish of the last batch run's Meyer-Wallach calls behind the producing
+ * pass -- "whole-state", "columns" or "per-position", the "finish" of qmle_meyer_wallach_describe -- and "" when
+ * that run made no such call (another measurement, or the stand-alone reads of the stored states). */
 int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 /* Host only (no GPU needed): how tile stage `stage` of `plan` would run for a request -- the launch policy of the
  * tile passes as JSON, written like qmle_plan_describe (returns the bytes needed, or an error < 0: no tile stage
@@ -245,6 +248,7 @@ int qmle_plan_describe(const qmle_plan *plan, char *buf, size_t cap);
 #define QMLE_ROUTE_SEMI_SINGLE    32u  /* each observable meets the last tile in at most one position */
 #define QMLE_ROUTE_NO_MULTI_ZIN   64u  /* as if QMLE_NO_MULTI_ZIN were set */
 #define QMLE_ROUTE_NO_MW_LEAN     128u /* as if QMLE_MW_NO_LEAN were set */
+#define QMLE_ROUTE_MW_PER_POSITION 256u /* as if QMLE_MW_FINISH_PER_POSITION were set (qmle_meyer_wallach_describe) */
 int qmle_plan_tile_route(const qmle_plan *plan, int stage, int batch, int meas, int n_obs, unsigned request_flags,
                          char *buf, size_t cap);
 /* Host only: the matrix builder's unit-pivot chain for `n` given 2x2 matrices u[i] = {m00, m01, m10, m11} as
@@ -524,13 +528,15 @@ int qmle_meyer_wallach_reads(int n_qubits);
  * the plan it executes on a chunk of `batch` states: behind the last tile pass ("route": "fused"; `row_shift`: a row
  * of that pass covers 2^row_shift tiles, the "row_shift" of qmle_plan_tile_route for meas 5; QMLE_MW_FUSE_TILED is
  * not read), or on the stored states where that pass cannot report its tile ("route": "resident").  `request_flags`:
- * QMLE_ROUTE_NO_MW_LEAN, nothing else.  Keys: "fusable", "lean" (the first later read reports positions 0..3);
+ * QMLE_ROUTE_NO_MW_LEAN and QMLE_ROUTE_MW_PER_POSITION (a tiled state's call takes the per-position finish whatever
+ * its shape; "total_bytes" does not change with it), nothing else.  Keys: "fusable", "lean" (the first later read reports positions 0..3);
  * "first": the stand-alone first read, or null; "reads": the later reads, in launch order; a read is {"kind":
  * "first" | "later" | "later_low", "lo", "lo2" (its tile: positions 0..3, lo..lo+3, lo2..lo2+3), "q" (2^q tiles per
  * workgroup), "rows" (per state), "stride" (floats per row), "nt" (at least 1 GiB per launch: streamed past the
  * caches)}; "positions"[p]: {"read": the later read that reports position p's cross terms, -1: the first read or the
  * producing pass, "col": its column there}; "finish": "whole-state" | "columns" | "per-position" (fused),
- * "standalone", "per-wire-sweeps" (below 12 qubits); "slices" of the finish; "regions": [{"name", "offset", "bytes",
+ * "standalone", "per-wire-sweeps" (below 12 qubits); "slices" of the finish; "finish_threads": the block size the
+ * fused route's finish launches with (its first kernel; 0 on the other routes); "regions": [{"name", "offset", "bytes",
  * "doubles"}], what the call places in its workspace; "end": the bytes the call checks its workspace against;
  * "total_bytes": what the size query reports for it (>= "end"). */
 int qmle_meyer_wallach_describe(const qmle_plan *plan, int n_qubits, int batch, int row_shift, unsigned request_flags,

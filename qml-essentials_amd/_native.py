@@ -459,6 +459,7 @@ class Plan:
     # ``tile_route``'s ``flags`` (QMLE_ROUTE_*)
     ROUTE_INIT_ZERO, ROUTE_FROM_ZERO, ROUTE_FOLD_COLS, ROUTE_MULTI_ROWS = 1, 2, 4, 8
     ROUTE_ZEROS_IN_PLACE, ROUTE_SEMI_SINGLE, ROUTE_NO_MULTI_ZIN, ROUTE_NO_MW_LEAN = 16, 32, 64, 128
+    ROUTE_MW_PER_POSITION = 256  # (``mw_describe`` only: as if QMLE_MW_FINISH_PER_POSITION were set)
 
     def tile_route(self, stage: int, batch: int, meas: int = 0, n_obs: int = 0, flags: int = 0) -> dict:
         """``qmle_plan_tile_route`` as a dict: how tile stage ``stage`` would run for this request -- kernel family
@@ -477,7 +478,9 @@ class Plan:
         ``chunk_loop_last_run``: ``"one_stream"``,
         ``"staged"``, ``"free"`` or ``"alone"`` -- how the run ordered its chunks (``chunk_loop_form`` answers the same
         without a run); ``"none"`` before the first run; and
-        ``matrices_from_map_last_run``: the matrix builder formed its angles from the affine map, not from a table):
+        ``matrices_from_map_last_run``: the matrix builder formed its angles from the affine map, not from a table; and
+        ``mw_finish_last_run``: ``"whole-state"``, ``"columns"`` or ``"per-position"``, the finish of that run's
+        Meyer-Wallach calls behind the producing pass, ``""`` when it made none):
         describe ``executed(meas)``, after the run.  Every tile stage carries ``group_product_form_last_run``: its
         last launch ran the groups that ``product_form_groups`` marks in product form; and
         ``measured_form_last_run``, true on the last stage when the last batch run built the records of its

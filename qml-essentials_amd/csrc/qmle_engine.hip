@@ -825,7 +825,8 @@ static int run_batch_lds(qmle_plan *plan, const BatchLayout &L, const float *d_m
     int rc = launch_tile(plan, 0, tb, rq, stream, &route);
     note_product_form(plan, 0, route, meas_type);
     if (rc == QMLE_OK && meas_type == QMLE_MEAS_MEYER_WALLACH)
-      rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream);
+      rc = run_mw_fused(nullptr, n, bc, st, 0, rows, L.partial_bytes, (float *)d_out + (size_t)b0 * (n + 1), stream,
+                        &plan->last_run.mw_finish);
     if (rc != QMLE_OK) return rc;
   }
   return QMLE_OK;
@@ -1146,7 +1147,7 @@ struct ChunkRun {
       if (rc != QMLE_OK) return rc;
     } else if (meas_type == QMLE_MEAS_MEYER_WALLACH) {
       rc = fuse_mw ? run_mw_fused(c.stc, n, c.bc, plan->stages.back(), c.route.row_shift, c.d_partial, L.partial_bytes,
-                                  (float *)d_out + (size_t)c.b0 * (n + 1), stream)
+                                  (float *)d_out + (size_t)c.b0 * (n + 1), stream, &plan->last_run.mw_finish)
                    : run_mw_resident(c.stc, n, c.bc, c.d_partial, L.partial_bytes,
                                      (float *)d_out + (size_t)c.b0 * (n + 1), stream);
       if (rc != QMLE_OK) return rc;

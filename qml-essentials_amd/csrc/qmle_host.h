@@ -25,7 +25,7 @@
 // position masks and their range check, aligning a caller's workspace, FNV-1a); align_up, grid_for and
 // kMaxGridY sit in qmle_dev.h.
 //
-// Environment switches: the library reads these nine and no others (tests/test_abi_cpu.py).  Unset,
+// Environment switches: the library reads these ten and no others (tests/test_abi_cpu.py).  Unset,
 // each one leaves the measured default in place.
 //   QMLE_NO_CHUNK_OVERLAP=1  batch chunks run on the caller's stream alone instead of alternating
 //                            between two internal streams.  Read per call.  bench.py (k2_one_stream,
@@ -44,6 +44,10 @@
 //                            never).  Read per launch.  tests.
 //   QMLE_MW_NO_LEAN=1        the producing pass reports Meyer-Wallach positions 0..3 itself instead of
 //                            the first later read.  Read per call.  tests.
+//   QMLE_MW_FINISH_PER_POSITION=1  a fused Meyer-Wallach call on a tiled state takes the per-position finish
+//                            whatever its shape (unset: only where the rows are too wide for the columns
+//                            finish); whole-state plans ignore it.
+//                            Read per call.  tests.
 //   QMLE_RNG_THREADS=<k>     host threads of the Philox parameter sampler (qmle_rng.cpp).  Read per
 //                            call.  Shared hosts.
 #pragma once
@@ -239,8 +243,9 @@ bool mw_lean(int n, const Stage &last);
 bool mw_lean_layout(int n, const Stage &last);
 bool mw_no_lean_switch();
 size_t mw_fused_ws_bytes(int n, int batch, const Stage &last);
+// (a row covers 2^row_shift tiles; *finish_run, when given: the MwFinish the call queued, for LastRun::mw_finish)
 int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int row_shift, void *ws,
-                 size_t ws_bytes, float *d_out, hipStream_t stream);  // a row covers 2^row_shift tiles
+                 size_t ws_bytes, float *d_out, hipStream_t stream, int *finish_run = nullptr);
 size_t mw_resident_ws_bytes(int n, int batch);
 int run_mw_resident(const float2 *states, int n, int batch, void *ws, size_t ws_bytes, float *d_out,
                     hipStream_t stream);

@@ -264,6 +264,10 @@ struct DevicePlan {  // lazily created by the first run on a device
 enum { kChunkLoopNone = 0, kChunkLoopOneStream, kChunkLoopStaged, kChunkLoopFree, kChunkLoopAlone };
 constexpr const char *kChunkLoopNames[] = {"none", "one_stream", "staged", "free", "alone"};
 
+// How a fused Meyer-Wallach call finished (mw_fused_finish, qmle_mw.hip; LastRun::mw_finish)
+enum MwFinish { kMwFinishNone = 0, kMwFinishWholeState, kMwFinishColumns, kMwFinishPerPosition };
+constexpr const char *kMwFinishNames[] = {"", "whole-state", "columns", "per-position"};
+
 // What the plan's last run did (describe_plan's *_last_run keys).  Report only: the engine writes it from
 // the routes launch_tile returns (TileRoute, qmle_host.h) and never reads it.  run_batch_masks resets all of it first.
 struct LastRun {
@@ -290,6 +294,9 @@ struct LastRun {
   // the last batch run's builder wrote measured-mode records (no closing diagonals) for the closing-free
   // groups of its last stage, and that stage's launch ran its product-form groups
   bool measured_form = false;
+  // the finish of the last batch run's fused Meyer-Wallach calls (run_mw_fused reports it); kMwFinishNone: that run
+  // made no such call
+  int mw_finish = kMwFinishNone;
 };
 
 }  // namespace qmle

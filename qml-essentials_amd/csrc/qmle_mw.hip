@@ -742,20 +742,20 @@ uint32_t mw_most_rows(uint32_t rows_first, const MwReads &rd) {
   return most;
 }
 
-// ---- the finishes of a fused call ----
-enum MwFinish { kMwFinishWholeState, kMwFinishColumns, kMwFinishPerPosition };
-const char *const kMwFinishNames[] = {"whole-state", "columns", "per-position"};
-
+// ---- the finishes of a fused call (MwFinish, kMwFinishNames: qmle_internal.h) ----
 // whole-state: one row per state, every position local to the producing tile (k_mw_whole_state_finish);
 // columns: k_mw_colsum + k_mw_finish_cols, while the row matrices are narrow enough for their thread = column maps;
-// per-position: k_mw_purity_fused over slices of the rows (+ k_mw_purity_final) + k_mw_pack.
+// per-position: k_mw_purity_fused over slices of the rows (+ k_mw_purity_final) + k_mw_pack -- the general one, valid
+// for every tiled state; per_position asks for it wherever it is (QMLE_MW_FINISH_PER_POSITION, tests).
 // lg: a row of the producing pass covers 2^lg tiles.
-MwFinish mw_fused_finish(int n, int T, int lg, const MwReads &rd) {
+constexpr int kMwWholeStateThreads = 64, kMwColsumThreads = 256;  // the block sizes those kernels are written for
+MwFinish mw_fused_finish(int n, int T, int lg, const MwReads &rd, bool per_position) {
   const uint32_t rows_first = (1u << (n - T)) >> lg;
   if (T == n && rows_first == 1) return kMwFinishWholeState;
   int colsum_w0 = kMwFusedRowA + (n - T - lg > 0 ? n - T - lg : 0), colsum_w = colsum_w0;
   for (int r = 0; r < rd.n_later; ++r) colsum_w += rd.stride[r];
-  if (T < n && 3 * T + 5 <= kMwFusedRowA && colsum_w0 <= 64 && colsum_w <= kMwColsMax) return kMwFinishColumns;
+  if (T < n && !per_position && 3 * T + 5 <= kMwFusedRowA && colsum_w0 <= 64 && colsum_w <= kMwColsMax)
+    return kMwFinishColumns;
   return kMwFinishPerPosition;
 }
 
@@ -789,6 +789,7 @@ struct MwLayout {
   MwRegion packed_q, packed_pur;       // run_mw_resident: Q and the purities by wire, before they are packed
   MwFinish finish = kMwFinishPerPosition;
   int slices = 1;    // of the finish
+  int finish_threads = 0;  // of the finish's first launch (fused route; 0: no such finish)
   size_t end = 0;    // where the last region ends: what a run checks its workspace against
   size_t total = 0;  // what the size query reports, >= end
 };
@@ -826,8 +827,8 @@ MwLayout mw_layout_standalone(int n, int batch, const MwReads &rd, bool packed) 
 // The producing pass wrote `first` (one row per 2^row_shift tiles, room for one per tile).  The regions follow the
 // call's own reads and finish; the total is sized for every call on these (n, batch, tile): either row length of the
 // first later read, any row_shift and either of the two finishes of a tiled state -- QMLE_MW_NO_LEAN is read per
-// call, after the workspace was sized.
-MwLayout mw_layout_fused(int n, int batch, const MwReads &rd, int T, int row_shift) {
+// call, after the workspace was sized, and so is QMLE_MW_FINISH_PER_POSITION (per_position).
+MwLayout mw_layout_fused(int n, int batch, const MwReads &rd, int T, int row_shift, bool per_position) {
   MwLayout L;
   const size_t B = (size_t)batch;
   const uint32_t tiles = 1u << (n - T);
@@ -835,17 +836,21 @@ MwLayout mw_layout_fused(int n, int batch, const MwReads &rd, int T, int row_shi
   for (int r = 0; r < rd.n_later; ++r) mw_place(L, L.later[r], B * rd.rows[r] * rd.stride[r] * sizeof(float));
   const size_t rows_end = L.end;
   const uint32_t most = mw_most_rows(tiles >> row_shift, rd);
-  L.finish = mw_fused_finish(n, T, row_shift, rd);
+  L.finish = mw_fused_finish(n, T, row_shift, rd, per_position);
   if (L.finish == kMwFinishColumns) {
     L.slices = mw_colsum_slices(most);
+    L.finish_threads = kMwColsumThreads;
     const int n_signed = n - T - row_shift > 0 ? n - T - row_shift : 0;
     mw_place(L, L.colsum[0], B * L.slices * (kMwFusedRowA + n_signed) * sizeof(double), sizeof(double));
     for (int r = 0; r < rd.n_later; ++r)
       mw_place(L, L.colsum[1 + r], B * L.slices * rd.stride[r] * sizeof(double), sizeof(double));
   } else if (L.finish == kMwFinishPerPosition) {
     L.slices = mw_purity_slices(most, batch, n);
+    L.finish_threads = most / L.slices >= 1024 ? 1024 : most / L.slices >= 256 ? 256 : 64;
     mw_place(L, L.pur, B * QMLE_MAX_QUBITS * sizeof(float));
     mw_place(L, L.partial, L.slices > 1 ? B * n * L.slices * 4 * sizeof(double) : 0, sizeof(double));
+  } else {
+    L.finish_threads = kMwWholeStateThreads;
   }
   size_t low_rows = 0;  // (either row length fits)
   for (int r = 0; r < rd.n_later; ++r) low_rows += B * rd.rows[r] * (kMwRowLaterLow - rd.stride[r]) * sizeof(float);
@@ -1003,19 +1008,18 @@ int mw_finish_columns(const MwFusedArgs &pa, int batch, int n_later, const MwLay
   }
   const int n_mats = 1 + n_later;
   for (int m = 0; m < n_mats; ++m) ca.out[m] = (double *)(ws + L.colsum[m].off);
-  hipLaunchKernelGGL(k_mw_colsum, dim3(L.slices, batch, n_mats), dim3(256), 0, stream, ca);
+  hipLaunchKernelGGL(k_mw_colsum, dim3(L.slices, batch, n_mats), dim3(L.finish_threads), 0, stream, ca);
   hipLaunchKernelGGL(k_mw_finish_cols, dim3(batch), dim3(1024), 0, stream, pa, ca, n_mats, d_out);
   HIPCHK(hipGetLastError());
   return QMLE_OK;
 }
 
-int mw_finish_per_position(const MwFusedArgs &pa, int batch, uint32_t most_rows, const MwLayout &L, char *ws,
-                           float *d_out, hipStream_t stream) {
+int mw_finish_per_position(const MwFusedArgs &pa, int batch, const MwLayout &L, char *ws, float *d_out,
+                           hipStream_t stream) {
   const int n = pa.n, slices = L.slices;
   float *d_pur = (float *)(ws + L.pur.off);
   double *d_part = (double *)(ws + L.partial.off);
-  const int threads = most_rows / slices >= 1024 ? 1024 : most_rows / slices >= 256 ? 256 : 64;
-  hipLaunchKernelGGL(k_mw_purity_fused, dim3(batch, n, slices), dim3(threads), 0, stream, pa, d_pur, d_part);
+  hipLaunchKernelGGL(k_mw_purity_fused, dim3(batch, n, slices), dim3(L.finish_threads), 0, stream, pa, d_pur, d_part);
   if (slices > 1)
     hipLaunchKernelGGL(k_mw_purity_final, dim3((batch * n + 63) / 64), dim3(64), 0, stream, (const double *)d_part, n,
                        batch, slices, d_pur);
@@ -1063,7 +1067,7 @@ std::string mw_describe(const char *route, int n, int batch, bool fusable, bool 
   }
   js += "],\"positions\":[";
   for (int p = 0; p < n; ++p) js_add(js, "%s{\"read\":%d,\"col\":%d}", p ? "," : "", rd.src_read[p], rd.src_col[p]);
-  js_add(js, "],\"finish\":\"%s\",\"slices\":%d,\"regions\":[", finish, L.slices);
+  js_add(js, "],\"finish\":\"%s\",\"slices\":%d,\"finish_threads\":%d,\"regions\":[", finish, L.slices, L.finish_threads);
   bool any = false;
   if (L.first.bytes) js_region(js, "first", -1, L.first, false, any);
   for (int r = 0; r < rd.n_later; ++r) js_region(js, "later", r, L.later[r], false, any);
@@ -1102,31 +1106,37 @@ bool mw_lean_layout(int n, const Stage &last) {
   return rd.ok && rd.n_later >= 1;
 }
 
+// A tiled state takes the per-position finish whatever its shape (QMLE_MW_FINISH_PER_POSITION=1: the tests of that
+// finish at sizes whose own finish is the columns one).  Read per call; the workspace holds either finish.
+static bool mw_per_position_switch() { return std::getenv("QMLE_MW_FINISH_PER_POSITION") != nullptr; }
+
 size_t mw_fused_ws_bytes(int n, int batch, const Stage &last) {
-  return mw_layout_fused(n, batch, mw_reads_fused(n, batch, last, false), last.T, 0).total;
+  return mw_layout_fused(n, batch, mw_reads_fused(n, batch, last, false), last.T, 0, false).total;
 }
 
 // rows_first = ws (filled by the producing pass: [batch][tiles][kMwFusedRowA]); the later reads' rows and
-// the finish's regions follow it.  d_out [batch][n + 1] = (Q, purities by wire).
+// the finish's regions follow it.  d_out [batch][n + 1] = (Q, purities by wire).  *finish_run: the finish it queued.
 int run_mw_fused(const float2 *states, int n, int batch, const Stage &last, int row_shift, void *ws_,
-                 size_t ws_bytes, float *d_out, hipStream_t stream) {
+                 size_t ws_bytes, float *d_out, hipStream_t stream, int *finish_run) {
   if (batch < 1 || batch > kMaxGridY) return QMLE_ERR_INVALID_ARG;
   const bool lean = last.T < n && mw_lean(n, last);
   const MwReads rd = mw_reads_fused(n, batch, last, lean);
   if (!rd.ok) return QMLE_ERR_INTERNAL;
-  const MwLayout L = mw_layout_fused(n, batch, rd, last.T, row_shift);
+  const MwLayout L = mw_layout_fused(n, batch, rd, last.T, row_shift, mw_per_position_switch());
   if (ws_bytes < L.end) return QMLE_ERR_WORKSPACE;
   char *ws = (char *)ws_;
   const MwFusedArgs pa = mw_fused_args(n, last, row_shift, lean, rd, L, ws);
   const int rc = mw_issue_later_reads(states, n, batch, rd, L, ws, stream);
   if (rc != QMLE_OK) return rc;
+  if (finish_run) *finish_run = L.finish;
   switch (L.finish) {
     case kMwFinishWholeState:
-      hipLaunchKernelGGL(k_mw_whole_state_finish, dim3((batch + 63) / 64), dim3(64), 0, stream, pa, batch, d_out);
+      hipLaunchKernelGGL(k_mw_whole_state_finish, dim3((batch + L.finish_threads - 1) / L.finish_threads),
+                         dim3(L.finish_threads), 0, stream, pa, batch, d_out);
       HIPCHK(hipGetLastError());
       return QMLE_OK;
     case kMwFinishColumns: return mw_finish_columns(pa, batch, rd.n_later, L, ws, d_out, stream);
-    default: return mw_finish_per_position(pa, batch, mw_most_rows(pa.rows_first, rd), L, ws, d_out, stream);
+    default: return mw_finish_per_position(pa, batch, L, ws, d_out, stream);
   }
 }
 
@@ -1184,7 +1194,7 @@ int qmle_meyer_wallach_describe(const qmle_plan *plan, int n_qubits, int batch, 
     if (row_shift > n - last->T) return QMLE_ERR_INVALID_ARG;
     const bool lean = mw_lean_layout(n, *last) && !(request_flags & QMLE_ROUTE_NO_MW_LEAN);
     const MwReads rd = mw_reads_fused(n, batch, *last, lean);
-    const MwLayout L = mw_layout_fused(n, batch, rd, last->T, row_shift);
+    const MwLayout L = mw_layout_fused(n, batch, rd, last->T, row_shift, request_flags & QMLE_ROUTE_MW_PER_POSITION);
     js = mw_describe("fused", n, batch, true, lean, false, rd, L, kMwFinishNames[L.finish]);
   } else {
     const MwReads rd = n >= kMwT ? mw_reads_standalone(n, batch) : MwReads{};

@@ -2130,7 +2130,8 @@ std::string describe_plan(const qmle_plan *p) {
          << ",\"last_group_lane_swap_last_run\":" << (p->last_run.lane_swap ? "true" : "false")
          << ",\"chunk_loop_last_run\":\"" << kChunkLoopNames[p->last_run.chunk_loop] << "\""
          << ",\"matrices_from_map_last_run\":" << (p->last_run.matrices_from_map ? "true" : "false")
-         << ",\"walk_kernel_last_run\":" << (p->last_run.walk_kernel ? "true" : "false");
+         << ",\"walk_kernel_last_run\":" << (p->last_run.walk_kernel ? "true" : "false")
+         << ",\"mw_finish_last_run\":\"" << kMwFinishNames[p->last_run.mw_finish] << "\"";
     os << ",\"src_ops\":[";
     for (size_t i = 0; i < st.src_ops.size(); ++i) os << (i ? "," : "") << st.src_ops[i];
     os << "]}";

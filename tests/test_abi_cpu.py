@@ -51,7 +51,7 @@ def test_plan_validation_errors_map_to_valueerror():
 
 
 def test_native_library_reads_only_the_documented_switches():
-    """libqmle_sv reads the nine environment switches documented in csrc/qmle_host.h and no
+    """libqmle_sv reads the ten environment switches documented in csrc/qmle_host.h and no
     others: the A/B switches of finished experiments stay deleted."""
     csrc = os.path.join(ROOT, "qml-essentials_amd", "csrc")
     names = set()
@@ -61,7 +61,7 @@ def test_native_library_reads_only_the_documented_switches():
             names |= set(re.findall(r'getenv\("(QMLE_[A-Z0-9_]*)"\)', open(path).read()))
     survivors = {"QMLE_NO_CHUNK_OVERLAP", "QMLE_MW_FUSE_TILED", "QMLE_NO_TOP_FIRST", "QMLE_FORCE_CAND",
                  "QMLE_PAD_HIGH", "QMLE_NO_MULTI_ZIN", "QMLE_K1_CTRL_BURST", "QMLE_MW_NO_LEAN",
-                 "QMLE_RNG_THREADS"}
+                 "QMLE_MW_FINISH_PER_POSITION", "QMLE_RNG_THREADS"}
     assert names == survivors, names ^ survivors
     host_h = open(os.path.join(csrc, "qmle_host.h")).read()
     for name in survivors:

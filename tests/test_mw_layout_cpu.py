@@ -164,8 +164,11 @@ def test_description_of_the_fused_route(plans):
     """The same invariants behind a producing pass, with and without the lean split, for every plan of the table;
     ``fusable`` means fewer later reads than the stand-alone route; the three finishes all occur.  The smallest shape
     of the table whose finish is "per-position" is one Hardware-Efficient layer at n = 29 (tile of 12 positions, 17
-    signed totals: more than the column kernels' 64-column map holds): 2^29 amplitudes, beyond what a GPU test of a
-    few seconds can run, so no GPU test reaches that finish."""
+    signed totals: more than the column kernels' 64-column map holds); tests/test_gpu_mw_finishes.py runs that finish
+    there (test_fused_route_at_its_natural_sizes) and, with QMLE_MW_FINISH_PER_POSITION=1, at n = 15..26
+    (test_per_position_finish_forced).  With QMLE_ROUTE_MW_PER_POSITION every tiled plan of the table describes that
+    finish, with and without the lean split, inside the workspace that was sized without the flag."""
+    PP = N.Plan.ROUTE_MW_PER_POSITION
     finishes, smallest = set(), None
     for name, (n, plan) in plans.items():
         route = last_tile_route(plan, 1)
@@ -176,8 +179,9 @@ def test_description_of_the_fused_route(plans):
                 d = N.mw_describe(0, b, plan=plan, flags=flags)
                 assert d["total_bytes"] <= b * (-(-one["total_bytes"] // 256) * 256), (name, b)
                 if d["route"] == "resident":
-                    assert not d["fusable"]
+                    assert not d["fusable"] and d["finish_threads"] == 0
                     check_description(d, n, b)
+                    assert N.mw_describe(0, b, plan=plan, flags=flags | PP) == d  # nothing to switch
                     continue
                 assert d["route"] == "fused" and d["fusable"] and route is not None and d["first"] is None
                 check_description(d, n, b, tile_bits=set(stage["bits"]))
@@ -187,6 +191,24 @@ def test_description_of_the_fused_route(plans):
                 if d["finish"] == "per-position" and b == 1 and (smallest is None or n < smallest[0]):
                     smallest = (n, name)
                 assert (d["finish"] == "whole-state") == (stage["T"] == n)
+                assert d["finish_threads"] == 64 or d["finish"] != "whole-state"
+                assert d["finish_threads"] == 256 or d["finish"] != "columns"
+                # the same call with the per-position finish asked for
+                f = N.mw_describe(0, b, plan=plan, flags=flags | PP)
+                check_description(f, n, b, tile_bits=set(stage["bits"]))
+                assert f["finish"] == ("whole-state" if stage["T"] == n else "per-position"), (name, b, f["finish"])
+                assert f["end"] <= f["total_bytes"] == d["total_bytes"], (name, b)
+                assert f["total_bytes"] <= b * (-(-one["total_bytes"] // 256) * 256), (name, b)
+                assert (f["reads"], f["positions"], f["lean"]) == (d["reads"], d["positions"], d["lean"])
+                if f["finish"] == "per-position":
+                    most = max([2 ** (n - stage["T"])] + [r["rows"] for r in f["reads"]])
+                    per = most // f["slices"]
+                    assert f["finish_threads"] == (1024 if per >= 1024 else 256 if per >= 256 else 64), (name, b)
+                    names = [g["name"] for g in f["regions"]]
+                    assert "purities" in names and ("partial" in names) == (f["slices"] > 1), (name, b, names)
+                    assert not any(g.startswith("colsum") for g in names)
+                if d["finish"] == "per-position":
+                    assert f == d
     assert finishes == {"whole-state", "columns", "per-position"}
     assert smallest == (29, "he1_n29"), smallest
 
