@@ -405,6 +405,23 @@ int qmle_apply_inplace_f64(qmle_plan *plan, const double *d_angles, int batch, v
                            void *d_workspace, size_t workspace_bytes, qmle_stream stream);
 size_t qmle_apply_inplace_f64_workspace_bytes(const qmle_plan *plan, int batch);
 
+/* ---- dense matrices on three and four wires (products of gates, a user's Operation(wires, matrix), evolved
+ * unitaries of three- and four-wire Hamiltonians) -- no plan, one streaming pass ---------------------------------
+ * Applies one dense 2^k x 2^k matrix, k = 3 or 4, in place to `batch` resident states [batch][2^n]: complex64
+ * (f64 = 0, float32 arithmetic) or complex128 (f64 = 1).  One read and one write of the state.
+ * wires: HOST array of k wires in operation order -- the first wire is the most significant bit of the matrix index
+ * (operations.embed_matrix), wire w is bit position n - 1 - w.  d_mats: DEVICE, complex128 row-major, [1][d][d]
+ * (per_sample = 0: one matrix for every state) or [batch][d][d] (per_sample = 1: state b takes matrix b); rounded to
+ * float32 for complex64 states.  The matrix need not be unitary.  Any batch >= 1 (the library splits launches).
+ * Status codes, all before any device work: QMLE_ERR_UNSUPPORTED for k outside {3, 4} (matrices on five or more
+ * wires are not served; one and two wires go through a plan); QMLE_ERR_INVALID_ARG for NULL pointers, batch < 1,
+ * n < k, n > QMLE_MAX_QUBITS, f64 or per_sample outside {0, 1}; QMLE_ERR_WIRE_RANGE for a wire outside 0..n-1;
+ * QMLE_ERR_DUPLICATE_WIRES.  The pass is no part of a plan: the adjoint sweep, compiled calls and the
+ * density-matrix path do not take it (gradients through such gates, noisy tapes and compiled calls stay refused by
+ * the front end). */
+int qmle_apply_matrix(void *d_states, int n_qubits, int batch, int f64, const int32_t *wires, int k,
+                      const void *d_mats, int per_sample, qmle_stream stream);
+
 /* Optional per-pass HIP-event timing (bench.py's live roofline measurement): between
  * begin and end every pass launch of this plan is bracketed by an event pair on the
  * launch stream.  end() synchronises, fills stage_ms[i] / stage_launches[i] (i = pass
@@ -786,6 +803,23 @@ int qmle_evolve_lanes(int rows, int n_steps);
 int qmle_evolve_magnus_jac(const double *h_terms, int n_terms, int dim, const double *d_coef, const double *d_h,
                            const double *d_dcoef, const double *d_dh, int rows, int n_dirs, int order, int n_steps,
                            int lanes_per_row, void *d_out, qmle_stream stream);
+
+/* qmle_evolve_magnus for dim = 8 and 16 (Hamiltonians on three and four wires): the same grids, node order, float64
+ * arithmetic, series cut (ceil(norm / 0.5) parts) and NaN rule (a row whose h * |sum_i c_i H_i|, largest absolute row
+ * sum, exceeds 2^15 or is not finite comes back as NaN; its neighbours do not).  d_coef, d_h, rows, order, n_steps as
+ * there.  Differences: d_terms is a DEVICE pointer, complex128 [n_terms][dim][dim] row-major, n_terms 1..16 (taken as
+ * Hermitian: the real diagonal and the entries above it are read); d_out is complex128 [rows][dim * dim].
+ * lanes_per_row: a row's steps are cut into that many contiguous runs; a run takes dim lanes (one per column of U)
+ * and a row's runs share a wave, so the allowed values are those with lanes * dim <= 64 -- {1, 4, 8} at dim 8,
+ * {1, 4} at dim 16; 0: the library chooses (qmle_evolve_wide_lanes: the widest allowed split that fills the card and
+ * leaves every run a step).  The result depends on the split through rounding only.
+ * QMLE_ERR_UNSUPPORTED for dim outside {8, 16} (dim 2 and 4: qmle_evolve_magnus; 32 and up are not served) or order
+ * outside {2, 4}; QMLE_ERR_INVALID_ARG for NULL pointers, n_terms outside 1..16, rows < 1, n_steps < 1, another
+ * lanes_per_row or rows * lanes * dim beyond 2^31 -- all before any device work.  There is no derivative form:
+ * gradients through evolved gates on more than two wires are not served. */
+int qmle_evolve_magnus_wide(const void *d_terms, int n_terms, int dim, const double *d_coef, const double *d_h, int rows,
+                            int order, int n_steps, int lanes_per_row, void *d_out, qmle_stream stream);
+int qmle_evolve_wide_lanes(int rows, int n_steps, int dim);
 
 /* ---- pulse-level gates (pulses.PulseGates.RX / RY): every pulse solve of a tape in one launch -----------------------
  * U[s] of dU/dt = -i (cx(t) X + cy(t) Y) U on [0, S], U(0) = I, for n_solves independent 2x2 solves on the fixed

@@ -213,6 +213,7 @@ SYMBOLS = [
     ("qmle_plan_set_consts_f64", _I, [_VP, C.POINTER(C.c_double), _I]),
     ("qmle_apply_inplace_f64", _I, [_VP, _VP, _I, _VP, _VP, _SZ, _VP]),
     ("qmle_apply_inplace_f64_workspace_bytes", _SZ, [_VP, _I]),
+    ("qmle_apply_matrix", _I, [_VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _VP]),
     ("qmle_histogram", _I, [_VP, C.c_int64, _I, _F, _F, _VP, _VP]),
     ("qmle_adjoint_gradient", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), _I, _VP, _I,
                                    _VP, _I, _VP, _SZ, _VP]),
@@ -251,6 +252,8 @@ SYMBOLS = [
     ("qmle_evolve_magnus", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
     ("qmle_evolve_lanes", _I, [_I, _I]),
     ("qmle_evolve_magnus_jac", _I, [_VP, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP]),
+    ("qmle_evolve_magnus_wide", _I, [_VP, _I, _I, _VP, _VP, _I, _I, _I, _I, _VP, _VP]),
+    ("qmle_evolve_wide_lanes", _I, [_I, _I, _I]),
     ("qmle_pulse_unitaries", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _I, _VP, _VP, _VP, _VP]),
     ("qmle_pulse_unitaries_jac", _I, [_VP, _I, _I, _I, C.c_double, C.c_double, _I, _I, _I, _VP, _VP]),
     ("qmle_compose_circuits", _I, [_VP, _I, _VP, _I, _VP, _I, _VP, C.c_int64, _I, _VP, C.c_int64, _VP, C.c_int64, _VP,
@@ -1018,6 +1021,55 @@ def evolve_magnus(h_terms, coef, h, order: int, lanes_per_row: int = 0, complex6
                                    0 if complex64 else 1, C.c_void_p(out.data_ptr()), _stream_ptr()),
           "qmle_evolve_magnus")
     return out
+
+
+def evolve_magnus_wide(h_terms, coef, h, order: int, lanes_per_row: int = 0):
+    """:func:`evolve_magnus` for ``d`` = 8 or 16 (``qmle_evolve_magnus_wide``): ``h_terms`` ``[n_terms, d, d]``
+    Hermitian, a host array or a CUDA tensor -- the kernel reads them from device memory --, ``coef`` and ``h`` as
+    there.  Returns ``[rows, d, d]`` complex128 on the device."""
+    torch = require_gpu()
+    H = _device_tensor(h_terms, torch.complex128)
+    if H.dim() != 3 or H.shape[1] != H.shape[2]:
+        raise ValueError(f"evolve_magnus_wide: terms must be [n_terms, d, d], got {tuple(H.shape)}")
+    coef, h = _device_tensor(coef, torch.float64), _device_tensor(h, torch.float64)
+    n_terms, d = int(H.shape[0]), int(H.shape[1])
+    per_step = 2 if order == 4 else 1
+    if coef.dim() != 3 or coef.shape[2] != n_terms or coef.shape[1] % per_step or h.shape != (coef.shape[0],):
+        raise ValueError(f"evolve_magnus_wide: coef {tuple(coef.shape)} / h {tuple(h.shape)} do not fit {n_terms} "
+                         f"term(s) of order {order}")
+    rows, n_steps = int(coef.shape[0]), int(coef.shape[1]) // per_step
+    out = torch.empty((rows, d, d), dtype=torch.complex128, device=current_device())
+    check(lib().qmle_evolve_magnus_wide(C.c_void_p(H.data_ptr()), n_terms, d, C.c_void_p(coef.data_ptr()),
+                                        C.c_void_p(h.data_ptr()), rows, int(order), n_steps, int(lanes_per_row),
+                                        C.c_void_p(out.data_ptr()), _stream_ptr()),
+          "qmle_evolve_magnus_wide")
+    return out
+
+
+def apply_matrix(states, wires: Sequence[int], mats):
+    """One dense matrix on 3 or 4 wires, in place on resident ``states`` ``[B, 2^n]`` (complex64 or complex128 CUDA,
+    contiguous) -- ``qmle_apply_matrix``.  ``mats``: ``[d, d]`` (one matrix for every state) or ``[B, d, d]`` (one
+    per state), a host array or a CUDA tensor; the first wire is the most significant bit of its index."""
+    torch = require_gpu()
+    if states.dtype not in (torch.complex64, torch.complex128) or not states.is_cuda or not states.is_contiguous() \
+            or states.dim() != 2:
+        raise ValueError("apply_matrix: states must be a contiguous complex64 / complex128 CUDA tensor [B, 2^n]")
+    B, D = int(states.shape[0]), int(states.shape[1])
+    n = D.bit_length() - 1
+    if 1 << n != D:
+        raise ValueError(f"apply_matrix: state length {D} is not a power of two")
+    wires = [int(w) for w in wires]
+    k, d = len(wires), 1 << len(wires)
+    M = _device_tensor(mats, torch.complex128)
+    if M.device != states.device:
+        M = M.to(states.device)
+    per_sample = M.dim() == 3
+    if tuple(M.shape) != ((B, d, d) if per_sample else (d, d)):
+        raise ValueError(f"apply_matrix: matrices of shape {tuple(M.shape)} do not fit {k} wire(s) and {B} state(s)")
+    check(lib().qmle_apply_matrix(C.c_void_p(states.data_ptr()), n, B, 1 if states.dtype == torch.complex128 else 0,
+                                  _i32(wires), k, C.c_void_p(M.data_ptr()), 1 if per_sample else 0, _stream_ptr()),
+          "qmle_apply_matrix")
+    return states
 
 
 EVOLVE_MAX_DIRS = 64  # qmle_evolve_magnus_jac: directions per call

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <atomic>
 #include <new>
+#include <type_traits>
 #include <utility>
 
 #include "qmle_internal.h"
@@ -257,6 +258,147 @@ __global__ void __launch_bounds__(256) k_fill_zero(float4 *__restrict__ p, uint6
   if (k < count) st4<false>(p + k, make_float4(0.f, 0.f, 0.f, 0.f));
 }
 
+// ---------------------------------------------------------------------------
+// dense 2^K x 2^K matrix on K = 3 or 4 wires (qmle_apply_matrix): one read and one write of the state, one group of
+// 2^K amplitudes per thread, found by zero-bit insertion like k_direct_1q's pairs.
+//
+// Index order.  The kernel numbers a group's amplitudes by the ASCENDING target positions sp[0] < sp[1] < ... (bit b
+// of the internal index e <-> position sp[b]) whatever order the caller's wires have; the block that stages the
+// matrix in LDS permutes its rows and columns to that order (mbit[b] = the bit of the caller's matrix index that
+// position sp[b] carries), so every wire order costs the same and runs the same code.
+//
+// Layout of a group's loads.  Thread bit 0 is the lowest position that is NOT a target, so with all targets on
+// positions >= 1 the 64 lanes of a load instruction read 64 neighbouring amplitudes (512 B, whole lines).  A target on
+// position 0 would leave every lane half of a 16-byte pair per instruction: there (PAIR) the complex64 kernel reads
+// and writes the pair (e, e + 1) as one float4, 2^(K-1) of them per group; complex128 amplitudes are 16 bytes anyway.
+// Further targets on positions 1 / 2 make the lanes' float4s 32 / 64 bytes apart: the rest of a line is then taken
+// by the following loads of the same lane and must be found in cache (profiles/wide_gates.md has what that costs,
+// and why the host keeps such gates off the non-temporal instantiations).  The matrix sits in LDS as float2 / double2
+// in internal order, read at wave-uniform addresses.
+// ---------------------------------------------------------------------------
+struct ApplyWires {
+  int sp[4];    // ascending target bit positions
+  int mbit[4];  // position sp[b] <-> this bit of the caller's matrix index
+};
+typedef double vd2 __attribute__((ext_vector_type(2)));
+template <bool NT> __device__ __forceinline__ float2 ld2(const float2 *p) {
+  if (NT) {
+    const v2f v = __builtin_nontemporal_load(reinterpret_cast<const v2f *>(p));
+    return make_float2(v.x, v.y);
+  }
+  return *p;
+}
+template <bool NT> __device__ __forceinline__ void st2(float2 *p, float2 v) {
+  if (NT) {
+    const v2f w = {v.x, v.y};
+    __builtin_nontemporal_store(w, reinterpret_cast<v2f *>(p));
+  } else {
+    *p = v;
+  }
+}
+template <bool NT> __device__ __forceinline__ double2 ldd2(const double2 *p) {
+  if (NT) {
+    const vd2 v = __builtin_nontemporal_load(reinterpret_cast<const vd2 *>(p));
+    return make_double2(v.x, v.y);
+  }
+  return *p;
+}
+template <bool NT> __device__ __forceinline__ void std2(double2 *p, double2 v) {
+  if (NT) {
+    const vd2 w = {v.x, v.y};
+    __builtin_nontemporal_store(w, reinterpret_cast<vd2 *>(p));
+  } else {
+    *p = v;
+  }
+}
+
+// One work item per (sample, group); a block belongs to one sample (blocks_per_state blocks each), so a per-sample
+// matrix is staged once per block and sample.  groups = 2^(n - K).
+template <int K, bool F64, bool PAIR, bool NT>
+__global__ void __launch_bounds__(256)
+k_apply_matrix(void *__restrict__ states, int n, const ApplyWires W, const double2 *__restrict__ mats, int per_sample,
+               uint32_t blocks_per_state, uint64_t groups) {
+  constexpr int D = 1 << K;
+  using amp_t = std::conditional_t<F64, double2, float2>;
+  __shared__ amp_t m[D * D];
+  const uint32_t sample = blockIdx.x / blocks_per_state, blk = blockIdx.x - sample * blocks_per_state;
+  const double2 *__restrict__ src = mats + (per_sample ? (size_t)sample * (D * D) : 0);
+  for (int t = threadIdx.x; t < D * D; t += 256) {
+    const int a = t / D, b = t % D;  // internal (row, column) -> the caller's
+    int ra = 0, rb = 0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+      ra |= ((a >> q) & 1) << W.mbit[q];
+      rb |= ((b >> q) & 1) << W.mbit[q];
+    }
+    const double2 v = src[ra * D + rb];
+    if constexpr (F64) m[t] = v;
+    else m[t] = make_float2((float)v.x, (float)v.y);
+  }
+  __syncthreads();
+  const uint64_t g = (uint64_t)blk * 256u + threadIdx.x;
+  if (g >= groups) return;
+  uint64_t base = g;
+#pragma unroll
+  for (int q = 0; q < K; ++q) base = ins0_64(base, W.sp[q]);
+  base += (uint64_t)sample << n;
+  uint64_t off[D];  // (compile-time indices: scalars after unrolling)
+#pragma unroll
+  for (int e = 0; e < D; ++e) {
+    uint64_t o = 0;
+#pragma unroll
+    for (int q = 0; q < K; ++q) o |= (uint64_t)((e >> q) & 1) << W.sp[q];
+    off[e] = o;
+  }
+  if constexpr (F64) {
+    double2 *st = (double2 *)states + base;
+    double2 v[D];
+#pragma unroll
+    for (int e = 0; e < D; ++e) v[e] = ldd2<NT>(st + off[e]);
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      double xr = 0.0, xi = 0.0;
+#pragma unroll
+      for (int b = 0; b < D; ++b) {
+        const double2 c = m[a * D + b];
+        xr = fma(c.x, v[b].x, xr), xr = fma(-c.y, v[b].y, xr);
+        xi = fma(c.x, v[b].y, xi), xi = fma(c.y, v[b].x, xi);
+      }
+      std2<NT>(st + off[a], make_double2(xr, xi));
+    }
+  } else if constexpr (PAIR) {  // sp[0] == 0: amplitudes (e, e + 1), e even, are one float4
+    float4 *st = (float4 *)((float2 *)states + base);
+    float2 v[D];
+#pragma unroll
+    for (int e = 0; e < D; e += 2) {
+      const float4 p = ld4<NT>(st + (off[e] >> 1));
+      v[e] = make_float2(p.x, p.y), v[e + 1] = make_float2(p.z, p.w);
+    }
+#pragma unroll
+    for (int a = 0; a < D; a += 2) {
+      float2 x = make_float2(0.f, 0.f), y = make_float2(0.f, 0.f);
+#pragma unroll
+      for (int b = 0; b < D; ++b) {
+        x = cfma(m[a * D + b], v[b], x);
+        y = cfma(m[(a + 1) * D + b], v[b], y);
+      }
+      st4<NT>(st + (off[a] >> 1), make_float4(x.x, x.y, y.x, y.y));
+    }
+  } else {
+    float2 *st = (float2 *)states + base;
+    float2 v[D];
+#pragma unroll
+    for (int e = 0; e < D; ++e) v[e] = ld2<NT>(st + off[e]);
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+      float2 x = make_float2(0.f, 0.f);
+#pragma unroll
+      for (int b = 0; b < D; ++b) x = cfma(m[a * D + b], v[b], x);
+      st2<NT>(st + off[a], x);
+    }
+  }
+}
+
 template <int MODE>
 void launch_direct_mode(bool diag, bool nt, dim3 grid, hipStream_t stream, float4 *st, int n,
                         int pt, int pc, const float *mats, uint32_t mat_floats,
@@ -378,3 +520,65 @@ void launch_fill_zero(float2 *states, uint64_t count, hipStream_t stream) {
 }
 
 }  // namespace qmle
+
+extern "C" {
+
+int qmle_apply_matrix(void *d_states, int n_qubits, int batch, int f64, const int32_t *wires, int k, const void *d_mats,
+                      int per_sample, qmle_stream stream_) {
+  if (k != 3 && k != 4) return QMLE_ERR_UNSUPPORTED;
+  if (!d_states || !wires || !d_mats || batch < 1 || n_qubits < k || n_qubits > QMLE_MAX_QUBITS || (f64 != 0 && f64 != 1) ||
+      (per_sample != 0 && per_sample != 1))
+    return QMLE_ERR_INVALID_ARG;
+  for (int i = 0; i < k; ++i)
+    if (wires[i] < 0 || wires[i] >= n_qubits) return QMLE_ERR_WIRE_RANGE;
+  for (int i = 0; i < k; ++i)
+    for (int j = 0; j < i; ++j)
+      if (wires[i] == wires[j]) return QMLE_ERR_DUPLICATE_WIRES;
+  const int n = n_qubits;
+  // wire i (the first is the most significant bit of the matrix index: bit k - 1 - i) sits on position n - 1 - wire
+  std::pair<int, int> by_pos[4];
+  for (int i = 0; i < k; ++i) by_pos[i] = {n - 1 - wires[i], k - 1 - i};
+  std::sort(by_pos, by_pos + k);
+  ApplyWires W{};
+  for (int q = 0; q < k; ++q) W.sp[q] = by_pos[q].first, W.mbit[q] = by_pos[q].second;
+  const uint64_t groups = (uint64_t)1 << (n - k);
+  const uint64_t blocks_per_state = (groups + 255u) / 256u;  // <= 2^21
+  const size_t amp = f64 ? sizeof(double2) : sizeof(float2);
+  // Non-temporal accesses for states far beyond the Infinity Cache (as launch_direct) -- but only where every load
+  // instruction takes whole 128-byte lines.  A target below that leaves the rest of a lane's line to a later load of the
+  // same group, which must find it in cache: streamed, a line would come from HBM once per instruction that touches it.
+  const bool whole_lines = ((size_t)amp << W.sp[0]) >= 128;
+  const bool nt = whole_lines && ((size_t)batch << n) * amp >= ((size_t)1 << 30);
+  const bool pair = !f64 && W.sp[0] == 0;
+  hipStream_t stream = (hipStream_t)stream_;
+  const uint64_t per_launch = std::max<uint64_t>(1, ((uint64_t)1 << 30) / blocks_per_state);  // samples: grid.x <= 2^30
+  for (uint64_t b0 = 0; b0 < (uint64_t)batch; b0 += per_launch) {
+    const uint64_t nb = std::min<uint64_t>(per_launch, (uint64_t)batch - b0);
+    char *st = (char *)d_states + ((size_t)b0 << n) * amp;
+    const double2 *mats = (const double2 *)d_mats + (per_sample ? (size_t)b0 << (2 * k) : 0);
+    const dim3 grid((unsigned)(nb * blocks_per_state)), block(256);
+#define QMLE_APPLY_LAUNCH(K_, F_, P_, N_)                                                                       \
+  hipLaunchKernelGGL((k_apply_matrix<K_, F_, P_, N_>), grid, block, 0, stream, (void *)st, n, W, mats, per_sample, \
+                     (uint32_t)blocks_per_state, groups)
+#define QMLE_APPLY_BY_NT(K_, F_, P_)              \
+  do {                                            \
+    if (nt) QMLE_APPLY_LAUNCH(K_, F_, P_, true);  \
+    else QMLE_APPLY_LAUNCH(K_, F_, P_, false);    \
+  } while (0)
+#define QMLE_APPLY_BY_FORM(K_)                       \
+  do {                                               \
+    if (f64) QMLE_APPLY_BY_NT(K_, true, false);      \
+    else if (pair) QMLE_APPLY_LAUNCH(K_, false, true, false); /* position 0 is a target: never whole lines */ \
+    else QMLE_APPLY_BY_NT(K_, false, false);         \
+  } while (0)
+    if (k == 3) QMLE_APPLY_BY_FORM(3);
+    else QMLE_APPLY_BY_FORM(4);
+#undef QMLE_APPLY_BY_FORM
+#undef QMLE_APPLY_BY_NT
+#undef QMLE_APPLY_LAUNCH
+    HIPCHK(hipGetLastError());
+  }
+  return QMLE_OK;
+}
+
+}  // extern "C"

@@ -183,8 +183,7 @@ struct SeriesCut {
   double inv_parts;
   int n_series;       // terms behind the column itself
 };
-__host__ __device__ __forceinline__ SeriesCut series_cut(const Herm<4> &G) {
-  const double nu = herm_row_norm(G);
+__host__ __device__ __forceinline__ SeriesCut series_cut_norm(double nu) {
   SeriesCut c;
   c.ok = nu <= kEvolveMaxNorm;  // (false for a NaN)
   c.parts = c.ok && nu > kEvolveTheta ? (int)ceil(nu / kEvolveTheta) : 1;
@@ -194,6 +193,7 @@ __host__ __device__ __forceinline__ SeriesCut series_cut(const Herm<4> &G) {
   for (double bound = nu_part; c.n_series < 24 && bound >= 1e-19; ++c.n_series) bound *= nu_part / (double)(c.n_series + 1);
   return c;
 }
+__host__ __device__ __forceinline__ SeriesCut series_cut(const Herm<4> &G) { return series_cut_norm(herm_row_norm(G)); }
 
 // U <- exp(-i G) U, column by column (see the head of this file)
 __host__ __device__ __forceinline__ void apply_exp(const Herm<4> &G, CMat<4> &U) {
@@ -983,6 +983,210 @@ __global__ __launch_bounds__(kEvolveThreads) void k_evolve_magnus_jac(const Evol
     }
 }
 
+// ---- 8x8 and 16x16: the table-driven solve on three and four wires -----------------------------------------------------
+// k_evolve_magnus's scheme, node order, norm rule and series cut (series_cut_norm) at DIM = 8 and 16, where neither U
+// nor the exponent fits a lane's registers.  ONE COLUMN of U per lane, as k_evolve_magnus_jac at DIM = 4: exp(Omega) U
+// acts on columns independently, so the DIM neighbouring lanes of a run of steps share the exponent and differ in
+// their column.  The exponent G = h sum_j a_j sum_i c_i(t_j) H_i of the current factor lives in LDS, one region per
+// run: lane c of the run forms row c -- from the real diagonal and the entries above it, the rest by conjugation, so G
+// is Hermitian to the bit --, stores the part on and above the diagonal (packed, DIM (DIM + 1) / 2 complex128) and
+// reports its absolute row sum; the largest of the run is the norm.  The terms come from device memory,
+// [n_terms][DIM][DIM] complex128: 16 of them are 64 KiB at DIM = 16.
+// Registers.  A lane keeps its column v and the running Taylor term t (2 DIM doubles each) and forms the next term row
+// by row, reading G at addresses its run shares.  At DIM = 16 three such vectors, the reads in flight and the
+// addresses do not fit the 256 registers of two waves per SIMD, so the upper half of the next term is parked in the
+// run's region behind G (one 16-byte slot per lane and row, lanes adjacent) until the product is complete: v, t and
+// half a term stay in registers.  The packed G is what makes room for that: 8 runs x (136 + 128 + 1) x 16 bytes are
+// 33 KiB per workgroup of 128 threads, four workgroups per CU.  The regions are one element apart from a multiple of
+// the bank cycle, so the runs of a wave read different banks.
+// Combine: a run writes its partial product into its region, column by column, as a plain DIM x DIM matrix (the
+// region holds one); run r then multiplies the matrix of run r + delta of its own row onto its column -- log2(lanes)
+// rounds, later run on the left; a run without such a partner in a round sits the multiplication out.
+// A run's lanes and the runs of a row share a wave (lanes * DIM <= 64), the lanes of a run take the same branches
+// (the cut follows from the shared norm), and nothing in LDS is shared between waves: the build, the series and the
+// combine are ordered by wave-level fences, never by a workgroup barrier -- runs of unequal length and rows of unequal
+// norm sit in one workgroup.
+constexpr int kWideThreads = 128;
+
+template <int DIM> struct WideLds {
+  static constexpr int KEEP = DIM > 8 ? DIM / 2 : DIM;     // rows of the next term that stay in registers
+  static constexpr int PACKED = DIM * (DIM + 1) / 2;       // G on and above the diagonal
+  static constexpr int STAGE = PACKED;                     // the parked rows start here: [(i - KEEP) * DIM + column]
+  static constexpr int USED = PACKED + (DIM - KEEP) * DIM;
+  static constexpr int REGION = (USED > DIM * DIM ? USED : DIM * DIM) + 1;
+  static constexpr int RUNS = kWideThreads / DIM;
+  // entry (i, j), i <= j, of the packed G
+  static constexpr int at(int i, int j) { return i * DIM - i * (i - 1) / 2 + (j - i); }
+};
+
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Row `c` of G = sum_i w_i H_i: its entries from the diagonal on into the run's region -> its absolute row sum (the
+// norm rule of herm_row_norm)
+template <int DIM>
+__device__ __forceinline__ double wide_build_row(const double2 *__restrict__ terms, int n_terms, const double *__restrict__ c0,
+                                                 const double *__restrict__ c1, double w0, double w1, int c, double2 *G) {
+  double gr[DIM], gi[DIM];
+#pragma unroll
+  for (int j = 0; j < DIM; ++j) gr[j] = gi[j] = 0.0;
+  for (int t = 0; t < n_terms; ++t) {
+    double w = w0 * c0[t];
+    if (c1) w = fma(w1, c1[t], w);
+    const double2 *__restrict__ H = terms + (size_t)t * (DIM * DIM);
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) {
+      const int at = j >= c ? c * DIM + j : j * DIM + c;  // on and above the diagonal as stored, below: the conjugate
+      const double2 e = H[at];
+      gr[j] = fma(w, e.x, gr[j]);
+      gi[j] = j == c ? 0.0 : fma(j > c ? w : -w, e.y, gi[j]);
+    }
+  }
+  double row = 0.0;
+  double2 *mine = G + (c * DIM - c * (c - 1) / 2 - c);  // entry (c, j) at mine[j]
+#pragma unroll
+  for (int j = 0; j < DIM; ++j) {
+    row += fabs(gr[j]) + fabs(gi[j]);
+    if (j >= c) mine[j] = make_double2(gr[j], gi[j]);
+  }
+  return row;
+}
+
+// the lane's column: v <- exp(-i G) v for the run's packed G, by the series of apply_exp -> false (nothing changed)
+// when the norm is not finite or beyond kEvolveMaxNorm
+template <int DIM>
+__device__ __forceinline__ bool wide_step(double2 *G, int col, double row_sum, double (&vr)[DIM], double (&vi)[DIM]) {
+  using W = WideLds<DIM>;
+  double nu = row_sum;
+#pragma unroll
+  for (int m = 1; m < DIM; m <<= 1) {  // the largest of the run's DIM lanes (a NaN stays)
+    const double o = __shfl_xor(nu, m, kWave);
+    nu = (o > nu || o != o) ? o : nu;
+  }
+  const SeriesCut cut = series_cut_norm(nu);
+  if (!cut.ok) return false;
+  double2 *stage = G + W::STAGE + col;
+  for (int p = 0; p < cut.parts; ++p) {
+    // the running term: rows below KEEP in registers, the others in the lane's parked slots (every round reads
+    // them from there, the first one included: one form of the loop, no pointer that is a register in one round
+    // and LDS in the next)
+    double tr[DIM], ti[DIM];
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      if (i < W::KEEP) tr[i] = vr[i], ti[i] = vi[i];
+      else stage[(i - W::KEEP) * DIM] = make_double2(vr[i], vi[i]);
+    }
+    for (int k = 1; k <= cut.n_series; ++k) {
+      const double f = cut.inv_parts / (double)k;  // term <- (-i G / parts) term / k
+#pragma unroll
+      for (int i = W::KEEP; i < DIM; ++i) {
+        const double2 a = stage[(i - W::KEEP) * DIM];
+        tr[i] = a.x, ti[i] = a.y;
+      }
+      double nr[W::KEEP], ni[W::KEEP];
+#pragma unroll
+      for (int i = 0; i < DIM; ++i) {
+        double xr = 0.0, xi = 0.0;
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+          const double2 g = G[i <= j ? W::at(i, j) : W::at(j, i)];
+          const double gy = i <= j ? g.y : -g.y;
+          xr = fma(g.x, tr[j], xr);
+          xr = fma(-gy, ti[j], xr);
+          xi = fma(g.x, ti[j], xi);
+          xi = fma(gy, tr[j], xi);
+        }
+        const double ar = f * xi, ai = -f * xr;
+        vr[i] += ar;
+        vi[i] += ai;
+        if (i < W::KEEP) nr[i < W::KEEP ? i : 0] = ar, ni[i < W::KEEP ? i : 0] = ai;  // (no index beyond the array, dead or not)
+        else stage[(i - W::KEEP) * DIM] = make_double2(ar, ai);
+        // (a row's reads stay with its row: hoisted, the DIM * DIM reads of a product spill)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int i = 0; i < W::KEEP; ++i) tr[i] = nr[i], ti[i] = ni[i];
+    }
+  }
+  return true;
+}
+
+// One work item per (row, run of the steps, column lane); a block holds kWideThreads / (lanes * DIM) rows.
+template <int DIM, int ORDER>
+__global__ __launch_bounds__(kWideThreads, 2) void k_evolve_wide(const double2 *__restrict__ terms, int n_terms,
+                                                                 const double *__restrict__ coef,
+                                                                 const double *__restrict__ h_rows, int rows, int n_steps,
+                                                                 int lanes, double2 *__restrict__ out) {
+  using W = WideLds<DIM>;
+  constexpr int NODES = ORDER == 4 ? 2 : 1;
+  __shared__ double2 lds[W::RUNS * W::REGION];
+  const long long gid = (long long)blockIdx.x * kWideThreads + threadIdx.x;
+  const int col = (int)(gid & (DIM - 1));
+  const long long item = gid / DIM, row_ll = item / lanes;
+  const int run = (int)(item - row_ll * lanes), block_run = (int)(threadIdx.x / DIM);
+  const bool live = row_ll < rows;  // (a row's lanes are live or idle together: lanes * DIM divides the block)
+  const int row = live ? (int)row_ll : rows - 1;
+  const int s_begin = (int)((long long)run * n_steps / lanes), s_end = (int)((long long)(run + 1) * n_steps / lanes);
+  const double h = h_rows[row];
+  const size_t node_stride = (size_t)NODES * n_terms;
+  const double *__restrict__ c = coef + ((size_t)row * n_steps + s_begin) * node_stride;
+  double2 *G = lds + block_run * W::REGION;
+  double vr[DIM], vi[DIM];
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) vr[i] = i == col ? 1.0 : 0.0, vi[i] = 0.0;
+  int bad = 0;
+  for (int s = s_begin; s < s_end; ++s, c += node_stride) {
+#pragma nounroll
+    for (int half = 0; half < NODES; ++half) {  // order 4: Omega_a first, then Omega_b -- the weights exchanged
+      const double w1 = ORDER == 2 ? h : h * (half ? kA2 : kA1), w2 = h * (half ? kA1 : kA2);
+      wave_lds_fence();  // (the run has finished reading the previous factor)
+      const double row_sum = wide_build_row<DIM>(terms, n_terms, c, ORDER == 4 ? c + n_terms : nullptr, w1, w2, col, G);
+      wave_lds_fence();
+      bad |= wide_step<DIM>(G, col, row_sum, vr, vi) ? 0 : 1;
+    }
+  }
+  for (int delta = 1; delta < lanes; delta <<= 1) {  // run 0 ends with the row
+    wave_lds_fence();
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) G[i * DIM + col] = make_double2(vr[i], vi[i]);
+    wave_lds_fence();
+    // only a run whose later run lies inside its row multiplies: that run shares its wave, so the fences above order
+    // its columns before these reads; the others keep a product nobody uses (the predicate is uniform across a run)
+    const bool in_row = run + delta < lanes;
+    const int later_bad = __shfl(bad, (int)((threadIdx.x + delta * DIM) & (kWave - 1)));
+    if (in_row) {
+      const double2 *L = lds + (block_run + delta) * W::REGION;
+      double yr[DIM], yi[DIM];
+#pragma unroll
+      for (int i = 0; i < DIM; ++i) {
+        double xr = 0.0, xi = 0.0;
+#pragma unroll
+        for (int j = 0; j < DIM; ++j) {
+          const double2 g = L[i * DIM + j];
+          xr = fma(g.x, vr[j], xr);
+          xr = fma(-g.y, vi[j], xr);
+          xi = fma(g.x, vi[j], xi);
+          xi = fma(g.y, vr[j], xi);
+        }
+        yr[i] = xr;
+        yi[i] = xi;
+        __builtin_amdgcn_sched_barrier(0);  // (as in wide_step)
+      }
+#pragma unroll
+      for (int i = 0; i < DIM; ++i) vr[i] = yr[i], vi[i] = yi[i];
+      bad |= later_bad;
+    }
+  }
+  if (!live || run != 0) return;
+  const double nan = __builtin_nan("");
+  double2 *__restrict__ o = out + (size_t)row * (DIM * DIM);
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) o[i * DIM + col] = bad ? make_double2(nan, nan) : make_double2(vr[i], vi[i]);
+}
+
 // ---- composition of small circuits ------------------------------------------------------------------------------------
 // The product rule of qoc.circuit_unitaries on the device: per circuit and candidate U = I, dU_p = 0 and per op
 // dU_p <- M dU_p + dM_p U, U <- M U.  Left multiplication acts on every column on its own and dU_p needs only U and
@@ -1192,6 +1396,18 @@ int evolve_auto_lanes(int rows, int n_steps) {
   return lanes;
 }
 
+// the allowed lanes_per_row of the wide solve: a row's runs times DIM column lanes share a wave
+bool wide_lanes_allowed(int dim, int lanes) { return lanes == 1 || lanes == 4 || (lanes == 8 && dim == 8); }
+// lanes_per_row = 0, as evolve_auto_lanes: the widest allowed split that stays within the card's lanes and leaves
+// every run a step
+int evolve_wide_auto_lanes(int rows, int n_steps, int dim) {
+  const long long fill = 256ll * 4 * 2 * kWave;
+  int lanes = 1;
+  for (int cand : {4, 8})
+    if (wide_lanes_allowed(dim, cand) && (long long)rows * cand * dim <= fill && cand <= n_steps) lanes = cand;
+  return lanes;
+}
+
 template <int DIM> void pack_terms(const double *h_terms, int n_terms, EvolveTerms &T) {
   for (int t = 0; t < n_terms; ++t) {
     const double *H = h_terms + (size_t)t * DIM * DIM * 2;  // complex128, row-major
@@ -1282,6 +1498,37 @@ int qmle_evolve_magnus(const double *h_terms, int n_terms, int dim, const double
   else if (dim == 2) QMLE_EVOLVE_LAUNCH(2, 4);
   else if (order == 2) QMLE_EVOLVE_LAUNCH(4, 2);
   else QMLE_EVOLVE_LAUNCH(4, 4);
+#undef QMLE_EVOLVE_LAUNCH
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
+
+int qmle_evolve_wide_lanes(int rows, int n_steps, int dim) {
+  if (dim != 8 && dim != 16) return QMLE_ERR_UNSUPPORTED;
+  if (rows < 1 || n_steps < 1) return QMLE_ERR_INVALID_ARG;
+  return evolve_wide_auto_lanes(rows, n_steps, dim);
+}
+
+int qmle_evolve_magnus_wide(const void *d_terms, int n_terms, int dim, const double *d_coef, const double *d_h, int rows,
+                            int order, int n_steps, int lanes_per_row, void *d_out, qmle_stream stream_) {
+  if (dim != 8 && dim != 16) return QMLE_ERR_UNSUPPORTED;
+  if (order != 2 && order != 4) return QMLE_ERR_UNSUPPORTED;
+  if (!d_terms || !d_coef || !d_h || !d_out || n_terms < 1 || n_terms > kEvolveMaxTerms || rows < 1 || n_steps < 1)
+    return QMLE_ERR_INVALID_ARG;
+  if ((long long)n_steps * (order == 4 ? 2 : 1) * n_terms > (1ll << 31) - 1) return QMLE_ERR_INVALID_ARG;
+  if (lanes_per_row != 0 && !wide_lanes_allowed(dim, lanes_per_row)) return QMLE_ERR_INVALID_ARG;
+  const int lanes = lanes_per_row ? lanes_per_row : evolve_wide_auto_lanes(rows, n_steps, dim);
+  const long long items = (long long)rows * lanes * dim;
+  if (items > (1ll << 31) - kWideThreads) return QMLE_ERR_INVALID_ARG;
+  hipStream_t stream = (hipStream_t)stream_;
+  const dim3 grid(grid_for((uint64_t)items, kWideThreads)), block(kWideThreads);
+#define QMLE_EVOLVE_LAUNCH(D, O)                                                                                   \
+  hipLaunchKernelGGL((k_evolve_wide<D, O>), grid, block, 0, stream, (const double2 *)d_terms, n_terms, d_coef, d_h, \
+                     rows, n_steps, lanes, (double2 *)d_out)
+  if (dim == 8 && order == 2) QMLE_EVOLVE_LAUNCH(8, 2);
+  else if (dim == 8) QMLE_EVOLVE_LAUNCH(8, 4);
+  else if (order == 2) QMLE_EVOLVE_LAUNCH(16, 2);
+  else QMLE_EVOLVE_LAUNCH(16, 4);
 #undef QMLE_EVOLVE_LAUNCH
   HIPCHK(hipGetLastError());
   return QMLE_OK;

@@ -25,8 +25,14 @@ evolution time and the interval ends keep their tangents, the node times ``t0 + 
 values -- so a coefficient function's own time dependence carries the moving-node term -- and every ``f_i(params_i,
 t)`` is evaluated under ``batching.elementwise_tangents()``, ONE call with the array of node times (no per-node
 fallback).  A coefficient the recorder cannot track raises ``NotImplementedError`` before any device work.  Adaptive
-solver names run the doubling as always, then one Jacobian launch on the accepted grid.  Matrices larger than 4x4 are
-out of scope.
+solver names run the doubling as always, then one Jacobian launch on the accepted grid.
+
+Wires.  Hamiltonians on one and two wires are solved by ``qmle_evolve_magnus``, on three and four wires (8x8, 16x16) by
+``qmle_evolve_magnus_wide``; five wires and more are refused.  The evolved gate of a three- or four-wire Hamiltonian
+is an explicit matrix on that many wires: ``simulation.simulate_and_measure`` runs it through ``qmle_apply_matrix``
+between the plans of the gates around it.  Gradients through such gates are out of scope: the Jacobian solve serves
+1 or 2 wires and says so, and every consumer that lowers a whole tape (the adjoint sweep, the parameter shift,
+compiled calls, noisy tapes) refuses the gate as it refuses any explicit matrix on more than two wires.
 
 Pulse-level gates (:mod:`pulses`) do not come through ``evolve``: their RX / RY leaves are solved by a kernel of their
 own that evaluates the envelopes on the device, all leaves of a tape in one launch.  They share the solver defaults
@@ -262,12 +268,15 @@ class Evolution:
 
     @staticmethod
     def _solve(H: np.ndarray, coef: np.ndarray, h: np.ndarray, order: int) -> np.ndarray:
-        """[rows, d, d] complex128 on the host: one launch of the solver kernel."""
-        if H.shape[-1] not in (2, 4):
+        """[rows, d, d] complex128 on the host: one launch of the solver kernel (``qmle_evolve_magnus`` on one and
+        two wires, ``qmle_evolve_magnus_wide`` on three and four)."""
+        if H.shape[-1] not in (2, 4, 8, 16):
             raise NotImplementedError(f"evolve(): Hamiltonians on {H.shape[-1]}x{H.shape[-1]} matrices are not "
-                                      "supported (1 or 2 wires)")
+                                      "supported (at most 4 wires, 16x16)")
         if H.shape[0] > N.EVOLVE_MAX_TERMS:
             raise NotImplementedError(f"evolve(): at most {N.EVOLVE_MAX_TERMS} terms, got {H.shape[0]}")
+        if H.shape[-1] > 4:
+            return N.evolve_magnus_wide(H, coef, h, order).cpu().numpy()
         return N.evolve_magnus(H, coef, h, order).cpu().numpy()
 
     @staticmethod

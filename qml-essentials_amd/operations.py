@@ -272,6 +272,20 @@ class Operation:
         return ("MAT1" if k == 1 else "MAT2"), self.wires, [], blob
 
 
+WIDE_MATRIX_WIRES = (3, 4)  # explicit matrices on this many wires run through qmle_apply_matrix
+
+
+def is_wide_matrix_gate(op_) -> bool:
+    """An explicit matrix on 3 or 4 wires, batch-constant ``[d, d]`` or per-sample ``[B, d, d]``: a product of gates,
+    its dagger or power, a user's ``Operation(wires, matrix)``, the evolved unitary of a three- or four-wire
+    Hamiltonian.  :meth:`Operation.lower` refuses it (no plan holds it); ``simulation.simulate_and_measure`` cuts
+    the tape at it.  The named three-wire gates (``CCX``, ``CSWAP``) are opcodes and no such gate."""
+    if not isinstance(op_, Operation) or isinstance(op_, KrausChannel) or op_._native is not None:
+        return False
+    m = op_._matrix
+    return len(op_.wires) in WIDE_MATRIX_WIRES and isinstance(m, np.ndarray) and m.ndim in (2, 3)
+
+
 def _neg(x):
     return -x if not isinstance(x, np.ndarray) else -x
 

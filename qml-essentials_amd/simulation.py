@@ -18,8 +18,8 @@ import numpy as np
 
 from . import _native as N
 from . import pulses
-from .operations import (_CONJ_NEGATE, Barrier, KrausChannel, Operation, conj_lower, pauli_terms,
-                         z_parity_mask)
+from .operations import (_CONJ_NEGATE, Barrier, KrausChannel, Operation, conj_lower, is_wide_matrix_gate,
+                         pauli_terms, z_parity_mask)
 
 MEAS_TYPES = ("expval", "probs", "state", "density")
 _PLAN_CACHE: "OrderedDict[tuple, N.Plan]" = OrderedDict()
@@ -401,7 +401,11 @@ def clear_plan_cache() -> None:
 def _tape_batch(tape: Sequence[Operation]) -> int:
     b = 1
     for op in tape:
-        for p in list(op.parameters) + list(op.matrix_columns()):  # (a per-sample matrix: its entries)
+        if is_wide_matrix_gate(op):  # (a per-sample 8x8 / 16x16 matrix counts by its leading axis, not by 128 / 512 columns)
+            cols = [op._matrix[:, 0, 0]] if op._matrix.ndim == 3 else []
+        else:
+            cols = list(op.parameters) + list(op.matrix_columns())  # (a per-sample matrix: its entries)
+        for p in cols:
             if isinstance(p, np.ndarray) and p.ndim > 0:
                 if b not in (1, p.shape[0]):
                     raise ValueError(f"inconsistent batch sizes on the tape: {b} vs {p.shape[0]}")
@@ -491,6 +495,123 @@ def sample_shots(probs, n_qubits: int, type: str, obs: Sequence[Operation], shot
     return N.probs_diag_expval(est, specs)
 
 
+def split_at_wide_gates(tape: Sequence[Operation]):
+    """-> ``(segments, positions)``: ``positions`` are the tape indices of the explicit matrices on 3 or 4 wires
+    (``operations.is_wide_matrix_gate``), ``segments[i]`` the operations before wide gate ``i`` and behind the one
+    before it (``len(positions) + 1`` lists, any of them possibly empty).  A tape without such a gate is one segment."""
+    segments, positions = [[]], []
+    for i, o in enumerate(tape):
+        if is_wide_matrix_gate(o):
+            positions.append(i)
+            segments.append([])
+        else:
+            segments[-1].append(o)
+    return segments, positions
+
+
+def _measure_resident(states, n_qubits: int, type: str, obs):
+    """``type`` of resident states [B, 2^n], complex64 (float32 results) or complex128 (float64), with the
+    stand-alone measurement kernels -- what a plan's last pass measures when the whole tape is one plan."""
+    torch = N.require_gpu()
+    B, x64 = states.shape[0], states.dtype == torch.complex128
+    if type == "state":
+        return states
+    if type == "probs":
+        return states.real ** 2 + states.imag ** 2 if x64 else N.probs(states)
+    if type == "density":
+        return states[:, :, None] * states.conj()[:, None, :] if x64 else N.density(states)
+    obs = list(obs)
+    if not obs:
+        return torch.empty((B, 0), dtype=torch.float64 if x64 else torch.float32, device=states.device)
+    masks = [z_parity_mask(o) for o in obs]
+    if x64:
+        if all(m is not None for m in masks):
+            return _x64_observables(states, n_qubits, obs, masks)
+        return observables_expval(states, n_qubits, obs)
+    if all(m is not None and len(m) == 1 for m in masks):
+        return N.expval_z(states, [m[0] for m in masks])
+    return observables_expval(states, n_qubits, obs)
+
+
+def _simulate_segmented(tape: Sequence[Operation], n_qubits: int, type: str, obs, B: int, shots, key,
+                        row_offset: int, as_tensor: bool):
+    """A noise-free tape that holds explicit matrices on 3 or 4 wires.  No plan holds such a gate, so the tape is
+    cut at them (:func:`split_at_wide_gates`): the first segment runs as a plan from |0..0> to ``"state"``, every
+    later one in place on the resident states (``apply_inplace`` / ``apply_inplace64``); an empty segment launches
+    nothing (an empty first one leaves |0..0>); every wide gate runs through ``qmle_apply_matrix``, one matrix for
+    all samples or one per sample; the result is measured from the resident states (:func:`_measure_resident`;
+    shots from their probabilities).  The states of all samples are resident whatever is measured, so the batch is
+    cut as for a ``"state"`` run -- here: the angle tables and the per-sample matrices stay on the host and every
+    chunk uploads its own rows."""
+    torch = N.require_gpu()
+    from . import memory
+    from .utils import x64_enabled
+
+    x64 = x64_enabled()
+    sampled = shots is not None and type in ("probs", "expval")
+    segments, positions = split_at_wide_gates(tape)
+    flags = (PLAN_FLAGS or 0) | N.PLAN_NO_MERGE if x64 else None  # (x64: gate by gate, as simulate_and_measure)
+    plans = []
+    for i, seg in enumerate(segments):
+        low = LoweredTape(seg, n_qubits)
+        if not low.ops:  # (nothing but barriers, or nothing)
+            plans.append(None)
+            continue
+        # (the table stays on the host: a chunk uploads its own rows)
+        plans.append((get_plan(low, flags), low.angle_table(B, dtype=np.float64 if x64 else np.float32) if low.n_slots else None))
+    gates = []
+    for pos in positions:
+        o = tape[pos]
+        m, k = np.asarray(o._matrix, dtype=np.complex128), len(o.wires)
+        if m.shape[-2:] != (2 ** k, 2 ** k):
+            raise ValueError(f"{o.name}: matrix shape {m.shape[-2:]} does not match {k} wire(s)")
+        if m.ndim == 3 and m.shape[0] != B:
+            raise ValueError(f"{o.name}: one matrix per sample needs {B} matrices, got {m.shape[0]}")
+        # one matrix for every sample: on the device once; one per sample: on the host, a chunk uploads its own
+        gates.append((list(o.wires), np.ascontiguousarray(m) if m.ndim == 3 else torch.from_numpy(np.ascontiguousarray(m)).cuda()))
+
+    def run(lo: int, hi: int):
+        real = torch.float64 if x64 else torch.float32
+
+        def angles_of(table):  # the chunk's rows of a segment's table, or None for a segment without an angle slot
+            return None if table is None else torch.from_numpy(np.ascontiguousarray(table[lo:hi])).cuda()
+
+        if plans[0] is None:  # a wide gate opens the tape: |0..0> without a plan
+            states = torch.zeros((hi - lo, 1 << n_qubits), dtype=torch.complex128 if x64 else torch.complex64,
+                                 device=N.current_device())
+            states[:, 0] = 1.0
+        else:
+            plan, table = plans[0]
+            angles = angles_of(table)
+            if angles is None:  # (no angle slot: the table only carries the batch size)
+                angles = torch.zeros((hi - lo, 1), dtype=real, device=N.current_device())
+            states = plan.run64(angles, "state") if x64 else plan.run(angles, "state")
+        for (wires, mats), later in zip(gates, plans[1:]):
+            N.apply_matrix(states, wires, mats[lo:hi] if isinstance(mats, np.ndarray) else mats)
+            if later is None:
+                continue
+            plan, table = later
+            angles = angles_of(table)
+            for b0 in range(0, hi - lo, 65535):  # (one launch of the in-place call takes this many states)
+                sl = slice(b0, min(hi - lo, b0 + 65535))
+                (N.apply_inplace64 if x64 else N.apply_inplace)(plan, None if angles is None else angles[sl], states[sl])
+        if sampled:
+            probs = _measure_resident(states, n_qubits, "probs", [])
+            return sample_shots(probs.float() if x64 else probs, n_qubits, type, obs, shots, key, row_offset + lo)
+        return _measure_resident(states, n_qubits, type, obs)
+
+    general = x64 and type == "expval" and any(z_parity_mask(o) is None for o in obs)
+    chunk = memory.compute_chunk_size(n_qubits, B, "state", False, len(obs), n_ops=len(tape), x64=x64,
+                                      general_obs=general)
+    if chunk >= B:
+        res = run(0, B)
+        return res if as_tensor else N.to_host(res)
+    parts = [run(lo, min(B, lo + chunk)) for lo in range(0, B, chunk)] if as_tensor else None
+    if as_tensor:
+        return torch.cat(parts, dim=0)
+    return memory.execute_chunked(run, B, chunk)
+
+
 def simulate_and_measure(tape: Sequence[Operation], n_qubits: int, type: str,
                          obs: Sequence[Operation] = (), use_density: bool = False,
                          shots: Optional[int] = None, key=None, batch: Optional[int] = None,
@@ -504,6 +625,12 @@ def simulate_and_measure(tape: Sequence[Operation], n_qubits: int, type: str,
     torch = N.require_gpu()
     B = int(batch) if batch is not None else _tape_batch(tape)
     sampled = shots is not None and type in ("probs", "expval")
+    if any(is_wide_matrix_gate(o) for o in tape):
+        if any(isinstance(o, KrausChannel) for o in tape):
+            raise NotImplementedError("explicit matrices on 3 or 4 wires (products of gates, evolved unitaries of "
+                                      "three- and four-wire Hamiltonians) are not available on noisy tapes: the "
+                                      "density-matrix path has no pass for them")
+        return _simulate_segmented(tape, n_qubits, type, obs, B, shots, key, row_offset, as_tensor)
     if any(isinstance(o, KrausChannel) for o in tape):
         from .utils import x64_enabled
 
