@@ -422,6 +422,24 @@ size_t qmle_apply_inplace_f64_workspace_bytes(const qmle_plan *plan, int batch);
 int qmle_apply_matrix(void *d_states, int n_qubits, int batch, int f64, const int32_t *wires, int k,
                       const void *d_mats, int per_sample, qmle_stream stream);
 
+/* ---- matrix cotangents of a dense gate on three or four wires (the adjoint sweep's share of such a gate) --------
+ * For psi and lambda, the sweep's states BEHIND a gate U on `wires` (k = 3 or 4, wire order and matrix index as for
+ * qmle_apply_matrix), writes d_cot[b][a][c] = G[a][c] with
+ *     M[a][c] = sum_rest conj(lambda[a, rest]) psi[c, rest],   G = M (U^+)^T,
+ * so that dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta.  d_psi, d_lam: DEVICE, [batch][2^n], complex64 (f64 = 0) or
+ * complex128 (f64 = 1); both are read once and never written.  d_cot: DEVICE, [batch][d][d] in the states' precision.
+ * d_mats: DEVICE, complex128, the FORWARD matrix, [1][d][d] (per_sample = 0) or [batch][d][d] (per_sample = 1);
+ * NULL: d_cot receives M itself.  The moment is a product on the matrix cores (v_mfma_f32_16x16x4_f32 /
+ * v_mfma_f64_16x16x4_f64) with per-block partial sums in the workspace and one finishing kernel that adds them in
+ * double in a fixed order: no atomics, the same bits from call to call.  Any batch >= 1 (the library splits
+ * launches).  Status codes as qmle_apply_matrix, all before any device work, NULL d_psi / d_lam / d_cot / d_ws being
+ * QMLE_ERR_INVALID_ARG; a workspace smaller than qmle_wide_moment_workspace_bytes (0 for arguments the call would
+ * refuse) is QMLE_ERR_WORKSPACE. */
+int qmle_wide_moment(const void *d_psi, const void *d_lam, int n_qubits, int batch, int f64, const int32_t *wires,
+                     int k, const void *d_mats, int per_sample, void *d_cot, void *d_ws, size_t ws_bytes,
+                     qmle_stream stream);
+size_t qmle_wide_moment_workspace_bytes(int n_qubits, int batch, int k, int f64);
+
 /* Optional per-pass HIP-event timing (bench.py's live roofline measurement): between
  * begin and end every pass launch of this plan is bracketed by an event pair on the
  * launch stream.  end() synchronises, fills stage_ms[i] / stage_launches[i] (i = pass
@@ -736,6 +754,28 @@ int qmle_adjoint_cotangent_at_f64(qmle_plan *fwd, qmle_plan *rev, const double *
                                   size_t ws_bytes, qmle_stream stream);
 size_t qmle_adjoint_cotangent_at_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch,
                                                      int n_obs_terms, int n_obs, int two_wire);
+
+/* ---- the adjoint sweep over one segment of a reverse tape, on states the caller holds -------------------------
+ * d_pair: DEVICE, [2][batch][2^n] -- psi of every sample, then lambda of every sample -- complex64
+ * (qmle_adjoint_segment) or complex128 (_f64), both states as they stand BEHIND the segment.  No forward run and no
+ * seed: per op of `rev` (a QMLE_PLAN_NO_FUSION plan of the reversed, daggered segment; any other plan is
+ * QMLE_ERR_UNSUPPORTED, as is n < 3) the generator overlap of terms[r] into d_grad[b][out_slot], the one- or two-wire
+ * matrix cotangent into d_cot[b][cot_off[r] ..] (cot_off NULL: none; the rules and codes of
+ * qmle_adjoint_cotangent_at), then the op on all 2 * batch states.  On return psi and lambda stand in FRONT of the
+ * segment.  d_grad [batch][n_grad_slots] and d_cot [batch][cot_stride] are NOT zeroed: only the slots and blocks
+ * that the terms name are written, so out_slot may be a column of a whole tape's gradient.  2 * batch <= 65535
+ * (QMLE_ERR_INVALID_ARG above).  A workspace smaller than the query's answer (two_wire: a two-wire cotangent is
+ * among the request) is QMLE_ERR_WORKSPACE.  All codes are decided before any device work. */
+int qmle_adjoint_segment(qmle_plan *rev, const float *d_angles_rev, int batch, void *d_pair,
+                         const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
+                         const int32_t *cot_off, int cot_stride, float *d_cot, void *d_ws, size_t ws_bytes,
+                         qmle_stream stream);
+size_t qmle_adjoint_segment_workspace_bytes(const qmle_plan *rev, int batch, int two_wire);
+int qmle_adjoint_segment_f64(qmle_plan *rev, const double *d_angles_rev, int batch, void *d_pair,
+                             const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
+                             const int32_t *cot_off, int cot_stride, double *d_cot, void *d_ws, size_t ws_bytes,
+                             qmle_stream stream);
+size_t qmle_adjoint_segment_workspace_bytes_f64(const qmle_plan *rev, int batch, int two_wire);
 
 /* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
  * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:

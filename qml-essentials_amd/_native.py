@@ -214,6 +214,8 @@ SYMBOLS = [
     ("qmle_apply_inplace_f64", _I, [_VP, _VP, _I, _VP, _VP, _SZ, _VP]),
     ("qmle_apply_inplace_f64_workspace_bytes", _SZ, [_VP, _I]),
     ("qmle_apply_matrix", _I, [_VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _VP]),
+    ("qmle_wide_moment", _I, [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_wide_moment_workspace_bytes", _SZ, [_I, _I, _I, _I]),
     ("qmle_histogram", _I, [_VP, C.c_int64, _I, _F, _F, _VP, _VP]),
     ("qmle_adjoint_gradient", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), _I, _VP, _I,
                                    _VP, _I, _VP, _SZ, _VP]),
@@ -239,6 +241,11 @@ SYMBOLS = [
     ("qmle_adjoint_cotangent_at_f64", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm),
                                            _I, _I, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
     ("qmle_adjoint_cotangent_at_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I, _I]),
+    ("qmle_adjoint_segment", _I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ, _VP]),
+    ("qmle_adjoint_segment_workspace_bytes", _SZ, [_VP, _I, _I]),
+    ("qmle_adjoint_segment_f64", _I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ,
+                                      _VP]),
+    ("qmle_adjoint_segment_workspace_bytes_f64", _SZ, [_VP, _I, _I]),
     ("qmle_sample_counts", _I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _SZ,
                                 _VP]),
     ("qmle_sample_workspace_bytes", _SZ, [_I, _I]),
@@ -680,10 +687,11 @@ class Plan:
         check(rc, "qmle_run_batch_map")
         return out
 
-    def run64(self, angles, meas: str, wire_groups: Sequence[Sequence[int]] = ()):
+    def run64(self, angles, meas: str, wire_groups: Sequence[Sequence[int]] = (), out=None):
         """complex128 execution of the plan (the reference's ``jax_enable_x64`` mode):
         ``angles`` float64 [B, n_slots]; returns complex128 states / density matrices, float64
-        probabilities, or float64 ``<Z..Z>`` of every wire group [B, len(wire_groups)]."""
+        probabilities, or float64 ``<Z..Z>`` of every wire group [B, len(wire_groups)].  ``out``: a contiguous
+        tensor of that shape and dtype that receives the result."""
         torch = require_gpu()
         if meas not in MEAS:
             raise ValueError(f"Unknown measurement type: {meas!r}")  # simulation.py:271
@@ -700,10 +708,12 @@ class Plan:
             for w in g:
                 m |= 1 << int(w)
             masks[k] = m
-        out = {"state": lambda: torch.empty((B, D), dtype=torch.complex128, device=dev),
-               "probs": lambda: torch.empty((B, D), dtype=torch.float64, device=dev),
-               "expval": lambda: torch.empty((B, n_obs), dtype=torch.float64, device=dev),
-               "density": lambda: torch.empty((B, D, D), dtype=torch.complex128, device=dev)}[meas]()
+        shape, dtype = {"state": ((B, D), torch.complex128), "probs": ((B, D), torch.float64),
+                        "expval": ((B, n_obs), torch.float64), "density": ((B, D, D), torch.complex128)}[meas]
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_cuda or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous CUDA tensor {shape} of {dtype}")
         wsb = int(lib().qmle_workspace_bytes_f64(self._h, B, MEAS[meas]))
         ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
         check(lib().qmle_run_batch_f64(self._h, C.c_void_p(angles.data_ptr()), B, MEAS[meas], masks, n_obs,
@@ -1072,6 +1082,43 @@ def apply_matrix(states, wires: Sequence[int], mats):
     return states
 
 
+def wide_moment(psi, lam, wires: Sequence[int], mats=None):
+    """The matrix cotangent of a dense gate on 3 or 4 wires from the sweep's states BEHIND it -- ``qmle_wide_moment``.
+    ``psi``, ``lam``: ``[B, 2^n]`` contiguous CUDA tensors of one complex dtype, read and never written.  ``mats``: the
+    FORWARD matrix, ``[d, d]`` or ``[B, d, d]`` (host array or CUDA tensor), the first wire the most significant bit
+    of its index; None returns the moment ``M[a][c] = sum_rest conj(lam[a, rest]) psi[c, rest]`` itself.
+    -> ``G = M (U^+)^T``, ``[B, d, d]`` in the states' dtype: ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``."""
+    torch = require_gpu()
+    for t in (psi, lam):
+        if t.dtype not in (torch.complex64, torch.complex128) or not t.is_cuda or not t.is_contiguous() or t.dim() != 2:
+            raise ValueError("wide_moment: states must be contiguous complex64 / complex128 CUDA tensors [B, 2^n]")
+    if psi.dtype != lam.dtype or psi.shape != lam.shape or psi.device != lam.device:
+        raise ValueError("wide_moment: psi and lam must agree in dtype, shape and device")
+    B, D = int(psi.shape[0]), int(psi.shape[1])
+    n = D.bit_length() - 1
+    if 1 << n != D:
+        raise ValueError(f"wide_moment: state length {D} is not a power of two")
+    wires = [int(w) for w in wires]
+    k, d = len(wires), 1 << len(wires)
+    f64 = 1 if psi.dtype == torch.complex128 else 0
+    M, per_sample = None, False
+    if mats is not None:
+        M = _device_tensor(mats, torch.complex128)
+        if M.device != psi.device:
+            M = M.to(psi.device)
+        per_sample = M.dim() == 3
+        if tuple(M.shape) != ((B, d, d) if per_sample else (d, d)):
+            raise ValueError(f"wide_moment: matrices of shape {tuple(M.shape)} do not fit {k} wire(s) and {B} state(s)")
+    out = torch.empty((B, d, d), dtype=psi.dtype, device=psi.device)
+    ws = torch.empty(max(1, int(lib().qmle_wide_moment_workspace_bytes(n, B, k, f64))), dtype=torch.uint8,
+                     device=psi.device)
+    check(lib().qmle_wide_moment(C.c_void_p(psi.data_ptr()), C.c_void_p(lam.data_ptr()), n, B, f64, _i32(wires), k,
+                                 C.c_void_p(M.data_ptr()) if M is not None else None, 1 if per_sample else 0,
+                                 C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+                                 _stream_ptr()), "qmle_wide_moment")
+    return out
+
+
 EVOLVE_MAX_DIRS = 64  # qmle_evolve_magnus_jac: directions per call
 
 
@@ -1337,11 +1384,12 @@ def pauli_reads(n_qubits: int, terms, f64: bool = False) -> int:
     return r
 
 
-def apply_pauli_sum(states, terms, weights):
+def apply_pauli_sum(states, terms, weights, out=None):
     """``out[b] = (sum_t weights[b, o_t] * coef_t * P_t) states[b]`` over the ``terms`` ``(coef, x_wire_mask,
     z_wire_mask, o)`` -- H psi for a weighted sum of observables, the seed of the adjoint sweep.  complex64 states
     and float32 weights (``qmle_apply_pauli_sum``) or complex128 and float64 (``qmle_apply_pauli_sum_f64``), chosen
-    by the states' dtype; ``weights`` ``[B, n_obs]``; any batch size; owns its workspace.  Returns a new tensor."""
+    by the states' dtype; ``weights`` ``[B, n_obs]``; any batch size; owns its workspace.  Returns a new tensor, or
+    ``out`` (contiguous, the states' shape, dtype and device, no memory in common with them) when given."""
     torch = require_gpu()
     if states.dtype not in (torch.complex64, torch.complex128) or not states.is_cuda:
         raise ValueError("states must be a complex64 / complex128 CUDA tensor [B, 2^n]")
@@ -1357,7 +1405,10 @@ def apply_pauli_sum(states, terms, weights):
     if weights.dim() != 2 or weights.shape[0] != B:
         raise ValueError(f"weights must be [{B}, n_obs], got {tuple(weights.shape)}")
     n_obs = int(weights.shape[1])
-    out = torch.empty_like(states)
+    if out is None:
+        out = torch.empty_like(states)
+    elif out.shape != states.shape or out.dtype != states.dtype or out.device != states.device or not out.is_contiguous():
+        raise ValueError("out must be a contiguous tensor of the states' shape, dtype and device")
     if B == 0:
         return out
     if not terms or n_obs == 0:
@@ -1640,3 +1691,45 @@ def adjoint_cotangent_at(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights,
         (cot_off, cot_stride), "cot_off holds one entry per reverse op, and the row holds at least one block",
         (int(cot_stride),), (int(bool(two_wire)),))
 
+
+ADJOINT_SEGMENT_MAX_BATCH = 32767  # psi and lambda of a sample share a launch: 2 B <= 65535
+
+
+def adjoint_segment(rev: Plan, angles_rev, pair, terms, grad, cot_off=None, cot=None, two_wire: bool = False):
+    """The sweep over one segment of a reverse tape on states the caller holds -- ``qmle_adjoint_segment`` / ``_f64``.
+    ``pair``: ``[2 B, 2^n]`` contiguous complex CUDA tensor, psi of every sample and then lambda of every sample, as
+    they stand BEHIND the segment; on return they stand in front of it.  ``rev``: the reversed, daggered NO_FUSION
+    plan, ``angles_rev`` ``[B, n_slots]`` in the matching real dtype, ``terms`` as for :func:`adjoint_gradient`.
+    ``grad`` ``[B, n_grad_slots]`` and ``cot`` ``[B, cot_stride]`` (with ``cot_off`` as for
+    :func:`adjoint_cotangent_at`; None: no matrix cotangents) are written IN PLACE, and only the slots and blocks
+    the terms name.  At most ``ADJOINT_SEGMENT_MAX_BATCH`` samples per call."""
+    torch = require_gpu()
+    f64 = pair.dtype == torch.complex128
+    ft = torch.float64 if f64 else torch.float32
+    if pair.dtype not in (torch.complex64, torch.complex128) or not pair.is_cuda or not pair.is_contiguous() \
+            or pair.dim() != 2 or pair.shape[0] % 2:
+        raise ValueError("adjoint_segment: pair must be a contiguous complex CUDA tensor [2 B, 2^n]")
+    B = int(pair.shape[0]) // 2
+    if int(pair.shape[1]) != 1 << rev.n_qubits:
+        raise ValueError(f"adjoint_segment: states of length {int(pair.shape[1])} do not fit {rev.n_qubits} qubits")
+    if grad.dtype != ft or not grad.is_contiguous() or grad.dim() != 2 or int(grad.shape[0]) != B:
+        raise ValueError(f"adjoint_segment: grad must be a contiguous [{B}, n_grad_slots] tensor of {ft}")
+    if angles_rev.dtype != ft or not angles_rev.is_contiguous() or int(angles_rev.shape[0]) != B:
+        raise ValueError(f"adjoint_segment: the angle table must be a contiguous [{B}, n_slots] tensor of {ft}")
+    if (cot_off is None) != (cot is None):
+        raise ValueError("adjoint_segment: cot_off and cot come together")
+    if cot is not None and (cot.dtype != ft or not cot.is_contiguous() or cot.dim() != 2 or int(cot.shape[0]) != B
+                            or len(cot_off) != len(terms)):
+        raise ValueError(f"adjoint_segment: cot must be a contiguous [{B}, cot_stride] tensor of {ft}, cot_off one "
+                         "entry per reverse op")
+    suffix = "_f64" if f64 else ""
+    what = "qmle_adjoint_segment" + suffix
+    wsq = getattr(lib(), "qmle_adjoint_segment_workspace_bytes" + suffix)
+    ws = torch.empty(max(1, int(wsq(rev._h, B, int(bool(two_wire))))), dtype=torch.uint8, device=pair.device)
+    check(getattr(lib(), what)(
+        rev._h, C.c_void_p(angles_rev.data_ptr()), B, C.c_void_p(pair.data_ptr()), _adjoint_term_array(terms), len(terms),
+        C.c_void_p(grad.data_ptr()), int(grad.shape[1]),
+        (C.c_int32 * len(cot_off))(*[int(m) for m in cot_off]) if cot is not None else None,
+        int(cot.shape[1]) if cot is not None else 0, C.c_void_p(cot.data_ptr()) if cot is not None else None,
+        C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
+    return grad

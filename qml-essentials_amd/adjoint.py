@@ -14,6 +14,12 @@ matrix cotangent ``G[a][c] = sum_rest conj(lambda[a, rest]) phi[c, rest]`` on th
 solver's Jacobian -- forms ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta``.  :func:`adjoint_slot_and_matrices_gradient` does the same for
 matrix gates on two wires (``MAT2`` / ``MAT2_ROW``: 4x4 cotangents) beside the one-wire ones.
 
+Explicit matrices on THREE AND FOUR wires are no part of any plan.  A tape that holds them is swept segment by
+segment (:func:`plan_segments`, :func:`segmented_gradient`): the forward run of ``simulation.segmented_forward``
+and the seed leave psi and lambda resident, ``qmle_adjoint_segment`` sweeps the gates between two wide gates on
+them, ``qmle_wide_moment`` reports a wide gate's 8x8 / 16x16 cotangent and ``qmle_apply_matrix`` undoes the gate
+on both states.
+
 This module only prepares the REVERSED, DAGGERED tape and the generator table; the sweep itself
 runs in the engine.
 """
@@ -25,7 +31,8 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as N
-from .simulation import LoweredTape, _Lowered, get_plan
+from .operations import is_wide_matrix_gate
+from .simulation import LoweredTape, _Lowered, get_plan, split_at_wide_gates
 
 # rotation gates exp(-i theta/2 P): generator Pauli word per wire, (control?, word)
 _ROT = {"RX": (False, "X"), "RY": (False, "Y"), "RZ": (False, "Z"),
@@ -319,3 +326,190 @@ def adjoint_slot_and_matrices_gradient(low: LoweredTape, n_qubits: int, batch: i
     ``dC/dtheta = 2 Re sum_ac G[a][c] dU[a][c]/dtheta`` with ``U`` as the tape holds it."""
     g, cot = _sweep(low, n_qubits, batch, obs_groups, weights, want, want_mat, x64, obs_terms, two_wire=True)
     return g, (cot if cot is not None else [])
+
+
+# ---- tapes with explicit matrices on three and four wires: the sweep segment by segment ----------------------------
+class SweepSegment(NamedTuple):
+    """The gates between two wide gates, as the segment sweep takes them."""
+    low: LoweredTape        # the segment, forward
+    rev: LoweredTape        # its reversed, daggered tape (``build_reverse(..., two_wire=True)``)
+    terms: tuple            # one generator term per reverse op; ``out_slot`` is a COLUMN OF THE WHOLE TAPE's gradient
+    columns: np.ndarray     # segment-local angle slot -> column of the whole tape's gradient
+    perm: np.ndarray        # reverse slot j reads the segment's forward column perm[j] ...
+    sign: np.ndarray        # ... times sign[j]
+    cot_off: tuple          # per reverse op: offset of its block in the whole tape's cotangent row, or -1
+    two_wire: bool          # a 4x4 block is among them
+
+
+class WideGate(NamedTuple):
+    """An explicit matrix on three or four wires between two segments."""
+    wires: tuple
+    matrix: np.ndarray      # complex128, [d, d] or one per sample [B, d, d]
+    flagged: bool           # its matrix cotangent is asked for
+    mat_index: int          # its number among the flagged matrix gates of the tape, or -1
+
+
+class SegmentedSweep(NamedTuple):
+    segments: tuple         # ``len(gates) + 1`` entries: SweepSegment, or None for a segment without an op
+    gates: tuple            # WideGate
+    n_slots: int            # angle slots of the whole tape, in tape order, wide gates skipped
+    mat_dims: tuple         # per flagged matrix gate in tape order: 2, 4, 8 or 16
+    mat_off: tuple          # one- and two-wire ones: offset of the block in the cotangent row; wide ones: -1
+    cot_stride: int         # scalars per cotangent row
+
+
+def plan_segments(tape, n_qubits: int, want: Sequence[bool], want_mat: Optional[Sequence[bool]] = None,
+                  x64: bool = False) -> SegmentedSweep:
+    """Host only: the sweep of a tape that holds explicit matrices on 3 or 4 wires, cut at them
+    (``simulation.split_at_wide_gates``).  ``want[s]``: angle slot ``s`` of the whole tape needs a derivative --
+    slots are numbered in tape order as ``LoweredTape`` numbers them, wide gates holding none.  ``want_mat``: one
+    flag per ENTRY of ``tape``; True on a one- or two-wire matrix gate (``MAT1``, ``MAT1_ROW``, ``MAT2``,
+    ``MAT2_ROW``) or on a wide gate asks for its matrix cotangent.  Empty segments are kept as None."""
+    want_mat = [False] * len(tape) if want_mat is None else [bool(f) for f in want_mat]
+    if len(want_mat) != len(tape):
+        raise ValueError("want_mat holds one flag per tape entry")
+    segs, positions = split_at_wide_gates(tape)
+    bounds = [-1] + list(positions) + [len(tape)]
+    flagged = [i for i, f in enumerate(want_mat) if f]  # tape order = the numbering of the cotangents
+    mat_index = {i: k for k, i in enumerate(flagged)}
+    mat_dims, mat_off, stride = [], [], 0
+    for i in flagged:
+        o = tape[i]
+        d = 2 ** len(o.wires)
+        mat_dims.append(d)
+        if is_wide_matrix_gate(o):
+            mat_off.append(-1)
+        else:
+            mat_off.append(stride)
+            stride += 2 * d * d
+    segments, slot0 = [], 0
+    for k, seg in enumerate(segs):
+        low = LoweredTape(seg, n_qubits)
+        if not low.ops:
+            segments.append(None)
+            continue
+        if slot0 + low.n_slots > len(want):
+            raise ValueError(f"want holds {len(want)} flags, the tape has more angle slots")
+        # the flags of the segment's lowered ops (a Barrier lowers to nothing) and the cotangent each one reports
+        entries = [i for i in range(bounds[k] + 1, bounds[k + 1]) if tape[i].lower(n_qubits) is not None]
+        local_mat = [want_mat[i] for i in entries]
+        local_idx = [mat_index[i] for i in entries if want_mat[i]]
+        rev_ops, terms, rev_src, rev_sign, mat_out, dims = build_reverse(
+            low, _op_blobs(low, x64), list(want[slot0:slot0 + low.n_slots]), local_mat, two_wire=True)
+        rev = LoweredTape(rev_ops, n_qubits)
+        terms = tuple((t[0] + slot0 if t[0] >= 0 else t[0],) + tuple(t[1:]) for t in patch_marks(rev, terms))
+        segments.append(SweepSegment(
+            low, rev, terms, np.arange(slot0, slot0 + low.n_slots), np.asarray(rev_src, dtype=np.int64),
+            np.asarray(rev_sign, dtype=np.float64),
+            tuple(mat_off[local_idx[m]] if m >= 0 else -1 for m in mat_out), 4 in dims))
+        slot0 += low.n_slots
+    if slot0 != len(want):
+        raise ValueError(f"want holds {len(want)} flags, the tape has {slot0} angle slots")
+    gates = tuple(WideGate(tuple(tape[i].wires), np.asarray(tape[i]._matrix, dtype=np.complex128), want_mat[i],
+                           mat_index.get(i, -1)) for i in positions)
+    return SegmentedSweep(tuple(segments), gates, slot0, tuple(mat_dims), tuple(mat_off), max(1, stride))
+
+
+def tape_slot_count(tape, n_qubits: int) -> int:
+    """Angle slots of a tape in the numbering of :func:`plan_segments` (host only)."""
+    n = 0
+    for o in tape:
+        low = None if is_wide_matrix_gate(o) else o.lower(n_qubits)
+        n += len(low[2]) if low is not None else 0
+    return n
+
+
+def _z_seed_terms(obs_groups):
+    """Z parities as the x = 0 words of the Pauli seed: ``[(coef, x_wire_mask, z_wire_mask, column)]``."""
+    return [(1.0, 0, sum(1 << int(q) for q in grp), k) for k, grp in enumerate(obs_groups)]
+
+
+def segmented_gradient(tape, n_qubits: int, batch: int, obs_groups, weights: np.ndarray, want: Sequence[bool],
+                       want_mat: Optional[Sequence[bool]] = None, x64: bool = False,
+                       obs_terms=None) -> Tuple[np.ndarray, List[np.ndarray]]:
+    """:func:`adjoint_slot_and_matrices_gradient` for a tape that holds explicit matrices on 3 or 4 wires:
+    d/d(angle slot) of ``sum_k weights[b, k] <O_k>`` and the matrix cotangents of the flagged gates (``want`` and
+    ``want_mat`` as for :func:`plan_segments`) -> ``(slot gradients [K * B, n_slots], [G_k])``, one ``[K * B, d, d]``
+    complex array per flagged gate in tape order, d = 2, 4, 8 or 16, in the index convention of the gate's own
+    matrix.  ``weights`` ``[K * B, n_obs]``, sample-minor.  Observables: Z-parity wire groups ``obs_groups`` or, with
+    ``obs_groups`` None, the Pauli term list ``obs_terms``; both seed the sweep through ``qmle_apply_pauli_sum``.
+
+    Per chunk of samples: the forward run writes psi into the first half of a ``[2 K B, 2^n]`` tensor, the seed writes
+    lambda into the second half; then, from the last wide gate to the first, ``qmle_adjoint_segment`` sweeps the
+    segment behind the gate, ``qmle_wide_moment`` reports the gate's cotangent if it is flagged, and
+    ``qmle_apply_matrix`` applies its dagger to all states; the first segment is swept last.  A wide gate that
+    nothing is asked of is simply inverted.  complex64, or complex128 with ``x64``.  The batch is cut so that psi,
+    lambda and the workspaces fit, as for a ``"state"`` run with two states per sample and cotangent."""
+    torch = N.require_gpu()
+    from . import memory
+    from .simulation import segmented_forward, segmented_plans
+
+    ft, fn, ct = (torch.float64, np.float64, torch.complex128) if x64 else (torch.float32, np.float32, torch.complex64)
+    sw = plan_segments(tape, n_qubits, want, want_mat, x64)
+    weights = np.ascontiguousarray(weights, dtype=fn)
+    B, n_obs = int(batch), int(weights.shape[1])
+    K = int(weights.shape[0]) // max(1, B)
+    if weights.shape[0] != K * B:
+        raise ValueError(f"weights must be [K * {B}, n_obs], got {weights.shape}")
+    w3 = weights.reshape(K, B, n_obs)
+    seed = list(obs_terms) if obs_groups is None else _z_seed_terms(obs_groups)
+    plans, fwd_gates = segmented_plans(tape, n_qubits, B, x64)
+    tables = [None if sg is None or not sg.low.n_slots else sg.low.angle_table(B, dtype=np.float64 if x64 else np.float32)
+              for sg in sw.segments]
+    grad = np.zeros((K, B, max(1, sw.n_slots)), dtype=fn)
+    rows = np.zeros((K, B, sw.cot_stride), dtype=fn)
+    wide = {g.mat_index: np.zeros((K, B, 2 ** len(g.wires), 2 ** len(g.wires)), dtype=np.complex128 if x64 else np.complex64)
+            for g in sw.gates if g.flagged}
+    dev = N.current_device()
+
+    def sweep_segment(i: int, lo: int, hi: int, pair, g_dev, c_dev):
+        sg = sw.segments[i]
+        if sg is None:
+            return
+        if tables[i] is None:
+            a_r = torch.zeros((K * (hi - lo), 1), dtype=ft, device=dev)
+        else:
+            a_f = torch.from_numpy(np.ascontiguousarray(tables[i][lo:hi])).to(dev).repeat(K, 1)
+            a_r = (a_f.index_select(1, torch.from_numpy(sg.perm).to(dev))
+                   * torch.from_numpy(sg.sign).to(device=dev, dtype=ft)).contiguous()
+        has_cot = any(o >= 0 for o in sg.cot_off)
+        N.adjoint_segment(get_plan(sg.rev, REV_FLAGS), a_r, pair, list(sg.terms), g_dev,
+                          cot_off=list(sg.cot_off) if has_cot else None, cot=c_dev if has_cot else None,
+                          two_wire=sg.two_wire)
+
+    def run(lo: int, hi: int):
+        bc = hi - lo
+        pair = torch.empty((2 * K * bc, 1 << n_qubits), dtype=ct, device=dev)
+        segmented_forward(plans, fwd_gates, n_qubits, lo, hi, x64, out=pair[:bc])
+        for k in range(1, K):  # K cotangents per sample: the forward state once, K copies
+            pair[k * bc:(k + 1) * bc].copy_(pair[:bc])
+        w = torch.from_numpy(np.ascontiguousarray(w3[:, lo:hi].reshape(K * bc, n_obs))).to(dev)
+        N.apply_pauli_sum(pair[:K * bc], seed, w, out=pair[K * bc:])
+        g_dev = torch.zeros((K * bc, max(1, sw.n_slots)), dtype=ft, device=dev)
+        c_dev = torch.zeros((K * bc, sw.cot_stride), dtype=ft, device=dev)
+        for i in range(len(sw.gates) - 1, -1, -1):
+            gate = sw.gates[i]
+            sweep_segment(i + 1, lo, hi, pair, g_dev, c_dev)
+            per_sample = gate.matrix.ndim == 3
+            m = torch.from_numpy(np.ascontiguousarray(gate.matrix[lo:hi] if per_sample else gate.matrix)).to(dev)
+            if gate.flagged:
+                cot = N.wide_moment(pair[:K * bc], pair[K * bc:], gate.wires, m.repeat(K, 1, 1) if per_sample else m)
+                wide[gate.mat_index][:, lo:hi] = cot.cpu().numpy().reshape((K, bc) + tuple(cot.shape[1:]))
+            md = m.conj().transpose(-1, -2).contiguous()
+            N.apply_matrix(pair, gate.wires, md.repeat(2 * K, 1, 1) if per_sample else md)  # (lambda's half: the same rows)
+        sweep_segment(0, lo, hi, pair, g_dev, c_dev)
+        grad[:, lo:hi] = g_dev.cpu().numpy().reshape(K, bc, -1)
+        rows[:, lo:hi] = c_dev.cpu().numpy().reshape(K, bc, -1)
+
+    chunk = memory.compute_chunk_size(n_qubits, 2 * K * B, "state", False, n_obs, n_ops=len(tape), x64=x64)
+    chunk = max(1, min(B, chunk // (2 * K), N.ADJOINT_SEGMENT_MAX_BATCH // K))
+    for lo in range(0, B, chunk):
+        run(lo, min(B, lo + chunk))
+    cots = []
+    for k, (d, off) in enumerate(zip(sw.mat_dims, sw.mat_off)):
+        if off < 0:
+            cots.append(wide[k].reshape(K * B, d, d))
+        else:
+            blk = rows[:, :, off:off + 2 * d * d].reshape(K * B, d, d, 2)
+            cots.append(blk[..., 0] + 1j * blk[..., 1])
+    return grad.reshape(K * B, -1)[:, : sw.n_slots], cots

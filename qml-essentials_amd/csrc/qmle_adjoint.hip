@@ -708,6 +708,15 @@ static int adj_launch_tile_stage(const AdjCtx &x, const Stage &st, size_t stage_
                        ft.d_coef_of + ft.term_begin[stage_i], c.d_grad, c.n_grad_slots);
   return QMLE_OK;
 }
+// the reverse plan's matrices for [psi; lambda] as one batch of 2B states (the angles of psi's half and of lambda's)
+static int adj_build_pair_matrices(const AdjCall<float> &c, float *mats, float *ang2, hipStream_t stream) {
+  if (c.rev->n_slots > 0) {
+    const size_t ab = (size_t)c.batch * c.rev->n_slots * sizeof(float);
+    HIPCHK(hipMemcpyAsync(ang2, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, stream));
+    HIPCHK(hipMemcpyAsync((char *)ang2 + ab, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, stream));
+  }
+  return launch_build_matrices(c.rev, ang2, mats, 2 * c.batch, stream);
+}
 // psi = U_N .. U_1 |0>, lambda = (the observables) psi, zeroed outputs, and the reverse plan's matrices for [psi;
 // lambda] as one batch of 2B states
 static int adj_prepare_states(const AdjCtx &x, float2 *psi, float2 *lam, float *mats, float *ang2) {
@@ -727,34 +736,26 @@ static int adj_prepare_states(const AdjCtx &x, float2 *psi, float2 *lam, float *
   }
   rc = x.zero_outputs();
   if (rc != QMLE_OK) return rc;
-  if (c.rev->n_slots > 0) {  // (the angles of psi's half and of lambda's half)
-    const size_t ab = (size_t)c.batch * c.rev->n_slots * sizeof(float);
-    HIPCHK(hipMemcpyAsync(ang2, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, x.stream()));
-    HIPCHK(hipMemcpyAsync((char *)ang2 + ab, c.d_angles_rev, ab, hipMemcpyDeviceToDevice, x.stream()));
-  }
-  return launch_build_matrices(c.rev, ang2, mats, 2 * c.batch, x.stream());
+  return adj_build_pair_matrices(c, mats, ang2, x.stream());
 }
-static int adj_run_stages(const AdjCtx &x, bool fused) {
+// The stage loop of routes 2 and 3 on the resident states s.psi and s.lam (lambda directly behind psi): per stage the
+// gradients of its gates, the matrix cotangents asked for, then the stage itself on all 2B states.  It writes only the
+// gradient slots and cotangent blocks its terms name, and leaves psi and lambda in front of the reverse tape's last op.
+static int adj_stage_loop(const AdjCtx &x, bool fused, const SweepView<float2> &s, const float *mats, const float *ang2) {
   const AdjCall<float> &c = x.c;
   qmle_plan *rev = c.rev;
   const int n = rev->n;
-  float2 *psi = (float2 *)(x.ws + x.L.states);
-  float *mats = (float *)(x.ws + x.L.mats);
-  float *ang2 = (float *)(x.ws + x.L.ang2);
-  const SweepView<float2> s = {psi, (float2 *)(x.ws + x.L.lam), (float2 *)(x.ws + x.L.partial), n, adj_blocks(n),
-                               c.batch, x.stream()};
-  int rc = adj_prepare_states(x, s.psi, s.lam, mats, ang2);
-  if (rc != QMLE_OK) return rc;
   FusedTables ft;
   if (fused) {
-    rc = adj_fused_tables(rev, c.terms, ft);
+    const int rc = adj_fused_tables(rev, c.terms, ft);
     if (rc != QMLE_OK) return rc;
   }
   size_t si = 0;
   for (const Stage &st : rev->stages) {
     const size_t stage_i = si++;
+    int rc;
     if (fused && st.kind == ST_TILE) {
-      rc = adj_launch_tile_stage(x, st, stage_i, ft, psi, mats, ang2);
+      rc = adj_launch_tile_stage(x, st, stage_i, ft, s.psi, mats, ang2);
       if (rc != QMLE_OK) return rc;
       continue;
     }
@@ -769,11 +770,21 @@ static int adj_run_stages(const AdjCtx &x, bool fused) {
     if (x.want_cot() && c.cot.off[r] >= 0)
       adj_launch_cotangent(k_adj_moment, s, rev->lowered[x.low_of[r]], (const float *)mats, rev->mat_floats,
                            (float *)c.cot.d_cot, c.cot.stride, c.cot.off[r]);
-    rc = run_stage_inplace(rev, st, psi, mats, ang2, 2 * c.batch, x.stream());
+    rc = run_stage_inplace(rev, st, s.psi, mats, ang2, 2 * c.batch, x.stream());
     if (rc != QMLE_OK) return rc;
   }
   HIPCHK(hipGetLastError());
   return QMLE_OK;
+}
+static int adj_run_stages(const AdjCtx &x, bool fused) {
+  const AdjCall<float> &c = x.c;
+  float *mats = (float *)(x.ws + x.L.mats);
+  float *ang2 = (float *)(x.ws + x.L.ang2);
+  const SweepView<float2> s = {(float2 *)(x.ws + x.L.states), (float2 *)(x.ws + x.L.lam), (float2 *)(x.ws + x.L.partial),
+                               c.rev->n, adj_blocks(c.rev->n), c.batch, x.stream()};
+  const int rc = adj_prepare_states(x, s.psi, s.lam, mats, ang2);
+  if (rc != QMLE_OK) return rc;
+  return adj_stage_loop(x, fused, s, mats, ang2);
 }
 
 // Both complex64 sweeps and their cotangent forms: the checks, the workspace, the route.
@@ -812,7 +823,63 @@ static int adjoint_run(const AdjCall<float> &c) {
   return adj_run_stages(x, fused);
 }
 
+// ---- one segment of a reverse tape on states the caller holds (qmle_adjoint_segment) ---------------------------
+// No forward run, no seed, no zeroed outputs: the matrices of the 2B states, then the stage loop of the streaming
+// route.  The workspace: the matrix rows, the doubled angles, the partial sums.
+struct AdjSegLayout { size_t mats, ang2, partial, total; };
+static AdjSegLayout adj_seg_layout(const qmle_plan *rev, int batch, int cot) {
+  AdjSegLayout L;
+  L.mats = 0;
+  L.ang2 = ws_mats_bytes(rev, 2 * batch);
+  L.partial = L.ang2 + align_up((size_t)2 * batch * (rev->n_slots ? rev->n_slots : 1) * sizeof(float), 256);
+  L.total = L.partial + align_up((size_t)batch * adj_blocks(rev->n) * sizeof(float2) * cot, 256) + 256;
+  return L;
+}
+static int adjoint_segment_run(const AdjCall<float> &c, float2 *pair) {
+  qmle_plan *rev = c.rev;
+  if (!rev || !pair || c.batch < 1 || c.batch > kMaxGridY / 2 || !c.terms || !c.d_grad || c.n_grad_slots < 1 || !c.d_ws ||
+      c.n_terms != (int)rev->ops.size() || (rev->n_slots > 0 && !c.d_angles_rev) || (c.cot.off && !c.cot.d_cot))
+    return QMLE_ERR_INVALID_ARG;
+  // one streaming pass per gate on LIVE states: fused tile passes and runs from |0..0> only are other plans
+  if (!(rev->flags & QMLE_PLAN_NO_FUSION) || (rev->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) || rev->n < 3)
+    return QMLE_ERR_UNSUPPORTED;
+  for (const Stage &st : rev->stages)
+    if (st.src_ops.size() != 1) return QMLE_ERR_INVALID_ARG;
+  int rc = adj_check_one_source(rev);
+  if (rc != QMLE_OK) return rc;
+  AdjCtx x = {c, (char *)c.d_ws, c.ws_bytes, {}, {}, {}};
+  rc = x.want_cot() ? cot_request_check(rev, c.cot, x.low_of) : QMLE_OK;
+  if (rc != QMLE_OK) return rc;
+  for (int r = 0; r < c.n_terms; ++r) {
+    if (!adj_slot_in_range(c.terms[r], c.n_grad_slots)) return QMLE_ERR_SLOT_RANGE;
+    if (c.terms[r].out_slot >= 0 && !adj_marks_in_bounds(c.terms[r], rev->n, rev->consts.size())) return QMLE_ERR_INVALID_ARG;
+  }
+  const AdjSegLayout L = adj_seg_layout(rev, c.batch, cot_partials(rev, c.cot));
+  if (!align_workspace(x.ws, x.ws_bytes) || x.ws_bytes < L.total) return QMLE_ERR_WORKSPACE;
+  rc = ensure_device_plan(rev);
+  if (rc != QMLE_OK) return rc;
+  float *mats = (float *)(x.ws + L.mats), *ang2 = (float *)(x.ws + L.ang2);
+  const SweepView<float2> s = {pair, pair + ((size_t)c.batch << rev->n), (float2 *)(x.ws + L.partial), rev->n,
+                               adj_blocks(rev->n), c.batch, x.stream()};
+  rc = adj_build_pair_matrices(c, mats, ang2, x.stream());
+  if (rc != QMLE_OK) return rc;
+  return adj_stage_loop(x, false, s, mats, ang2);
+}
+
 extern "C" {
+
+size_t qmle_adjoint_segment_workspace_bytes(const qmle_plan *rev, int batch, int two_wire) {
+  if (!rev || batch < 1) return 0;
+  return adj_seg_layout(rev, batch, two_wire ? 16 : 4).total + 256;
+}
+int qmle_adjoint_segment(qmle_plan *rev, const float *d_angles_rev, int batch, void *d_pair,
+                         const qmle_adjoint_term *terms, int n_terms, float *d_grad, int n_grad_slots,
+                         const int32_t *cot_off, int cot_stride, float *d_cot, void *d_ws, size_t ws_bytes,
+                         qmle_stream stream) {
+  return adjoint_segment_run({nullptr, rev, nullptr, d_angles_rev, batch, nullptr, {}, terms, n_terms, d_grad,
+                              n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot}},
+                             (float2 *)d_pair);
+}
 
 size_t qmle_adjoint_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch) {
   if (!adj_ws_query_ok(fwd, rev, batch)) return 0;

@@ -1,5 +1,5 @@
-// What the two adjoint sweeps share: qmle_adjoint.hip (complex64) and qmle_f64.hip (complex128) include this, no
-// other unit does.  Device side: the kernels and helpers that are the same text in both precisions (V = float2 with
+// What the two adjoint sweeps share: qmle_adjoint.hip (complex64) and qmle_f64.hip (complex128) include this, and
+// qmle_wide.hip (the moment of a three- or four-wire gate) for cot_finish_entry; no other unit does.  Device side: the kernels and helpers that are the same text in both precisions (V = float2 with
 // T = float, or double2 with T = double).  Host side: a sweep's arguments, their checks, the launch pairs of the
 // per-gate sweep and the bodies of the extern "C" entry points.  What differs between the precisions on purpose stays
 // in the units: the kernels that move float4 against double2, the layouts, the block counts, the routes.
@@ -36,20 +36,27 @@ template <class T> __device__ __forceinline__ T adj_phase(int n_y, T re, T im) {
 // G = M (U^+)^T for the DIM x DIM moment M[a][c] = sum conj(lambda[a]) psi[c] taken BEHIND the gate: phi = U^+ psi is
 // the state in front of it, so G[a][c] = sum conj(lambda[a]) phi[c] = sum_d M[a][d] U^+[c][d].  `ud`: the reverse
 // op's own matrix (U^+), `m`: M as (re, im) pairs, row-major.
+// One entry of that product: (re, im) = G[a][c].
+template <int DIM, class T, class MT>
+__device__ __forceinline__ void cot_finish_entry(const T *__restrict__ m, const MT *__restrict__ ud, int a, int c, T &re,
+                                                 T &im) {
+  re = 0, im = 0;
+#pragma unroll
+  for (int d = 0; d < DIM; ++d) {
+    const T mr = m[(a * DIM + d) * 2], mi = m[(a * DIM + d) * 2 + 1];
+    const T ur = (T)ud[(c * DIM + d) * 2], ui = (T)ud[(c * DIM + d) * 2 + 1];
+    re += mr * ur - mi * ui;
+    im += mr * ui + mi * ur;
+  }
+}
 template <int DIM, class T, class MT, class OT>
 __device__ __forceinline__ void cot_finish(const T *__restrict__ m, const MT *__restrict__ ud, OT *__restrict__ out) {
 #pragma unroll
   for (int a = 0; a < DIM; ++a)
 #pragma unroll
     for (int c = 0; c < DIM; ++c) {
-      T re = 0, im = 0;
-#pragma unroll
-      for (int d = 0; d < DIM; ++d) {
-        const T mr = m[(a * DIM + d) * 2], mi = m[(a * DIM + d) * 2 + 1];
-        const T ur = (T)ud[(c * DIM + d) * 2], ui = (T)ud[(c * DIM + d) * 2 + 1];
-        re += mr * ur - mi * ui;
-        im += mr * ui + mi * ur;
-      }
+      T re, im;
+      cot_finish_entry<DIM>(m, ud, a, c, re, im);
       out[(a * DIM + c) * 2] = (OT)re;
       out[(a * DIM + c) * 2 + 1] = (OT)im;
     }

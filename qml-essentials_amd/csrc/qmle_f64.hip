@@ -499,15 +499,39 @@ size_t qmle_adjoint_cotangent_workspace_bytes_f64(const qmle_plan *fwd, const qm
 
 }  // extern "C"
 
+// The stage loop of the sweep on the resident states s.psi and s.lam of samples [b0, b0 + s.bc): per gate of the
+// reverse tape its overlap, its matrix cotangent where asked for, and the inverse gate on both states.  It writes only
+// the gradient slots and cotangent blocks its terms name.  rm: the reverse plan's matrix rows of sample b0 on.
+static int f64_adj_stage_loop(const AdjCall<double> &c, const SweepView<double2> &s, int b0, const double *rm) {
+  const qmle_plan *rev = c.rev;
+  const int n = s.n;
+  const double *rcst = f64_consts(rev);
+  const double *ar = c.d_angles_rev ? c.d_angles_rev + (size_t)b0 * rev->n_slots : nullptr;
+  const size_t half = ((size_t)1 << n) / 2;
+  const dim3 grid(grid_for(half ? half : 1, 256, 1u << 16), s.bc);
+  for (size_t r = 0; r < rev->lowered.size(); ++r) {
+    const int src = rev->lowered_src[r][0];
+    const qmle_adjoint_term &t = c.terms[src];
+    if (t.out_slot >= 0)
+      adj_launch_overlap(k64_adj_overlap, s, t, rcst, c.d_grad + (size_t)b0 * c.n_grad_slots, c.n_grad_slots);
+    if (c.cot.off && c.cot.off[src] >= 0)
+      adj_launch_cotangent(k64_adj_moment, s, rev->lowered[r], rm, rev->mat_floats,
+                           (double *)c.cot.d_cot + (size_t)b0 * c.cot.stride, c.cot.stride, c.cot.off[src]);
+    for (double2 *st : {s.psi, s.lam})
+      hipLaunchKernelGGL(k64_op, grid, dim3(256), 0, s.stream, st, n, rev->lowered[r], rm, rev->mat_floats, rcst, ar,
+                         rev->n_slots);
+  }
+  HIPCHK(hipGetLastError());
+  return QMLE_OK;
+}
 // One round of samples [b0, b0 + s.bc) of the sweep: the forward state, the seed (`seed`, or the Z masks `z`), then
-// per gate of the reverse tape its overlap, its matrix cotangent where asked for, and the inverse gate on both states.
+// the stage loop.
 static int f64_adj_round(const AdjCall<double> &c, const SweepView<double2> &s, int b0, const double *fmats,
                          const double *rmats, const ZMasks &z, const PauliSeed *seed) {
   const qmle_plan *fwd = c.fwd, *rev = c.rev;
   const int n = s.n;
-  const double *fc = f64_consts(fwd), *rcst = f64_consts(rev);
+  const double *fc = f64_consts(fwd);
   const double *af = c.d_angles_fwd ? c.d_angles_fwd + (size_t)b0 * fwd->n_slots : nullptr;
-  const double *ar = c.d_angles_rev ? c.d_angles_rev + (size_t)b0 * rev->n_slots : nullptr;
   const double *fm = fmats + (size_t)b0 * fwd->mat_floats, *rm = rmats + (size_t)b0 * rev->mat_floats;
   const double *w = c.d_weights + (size_t)b0 * c.obs.n_obs;
   const size_t half = ((size_t)1 << n) / 2;
@@ -523,20 +547,7 @@ static int f64_adj_round(const AdjCall<double> &c, const SweepView<double2> &s, 
     hipLaunchKernelGGL(k64_zsum_apply, grid, dim3(256), 0, s.stream, (const double2 *)s.psi, s.lam, n, w, z,
                        c.obs.n_obs);
   }
-  for (size_t r = 0; r < rev->lowered.size(); ++r) {
-    const int src = rev->lowered_src[r][0];
-    const qmle_adjoint_term &t = c.terms[src];
-    if (t.out_slot >= 0)
-      adj_launch_overlap(k64_adj_overlap, s, t, rcst, c.d_grad + (size_t)b0 * c.n_grad_slots, c.n_grad_slots);
-    if (c.cot.off && c.cot.off[src] >= 0)
-      adj_launch_cotangent(k64_adj_moment, s, rev->lowered[r], rm, rev->mat_floats,
-                           (double *)c.cot.d_cot + (size_t)b0 * c.cot.stride, c.cot.stride, c.cot.off[src]);
-    for (double2 *st : {s.psi, s.lam})
-      hipLaunchKernelGGL(k64_op, grid, dim3(256), 0, s.stream, st, n, rev->lowered[r], rm, rev->mat_floats, rcst, ar,
-                         rev->n_slots);
-  }
-  HIPCHK(hipGetLastError());
-  return QMLE_OK;
+  return f64_adj_stage_loop(c, s, b0, rm);
 }
 
 // Both complex128 sweeps and their cotangent forms: Z-parity masks or a list of weighted Pauli words, checked by the
@@ -591,7 +602,61 @@ static int f64_adjoint_run(const AdjCall<double> &c) {
   return QMLE_OK;
 }
 
+// ---- one segment of a reverse tape on states the caller holds (qmle_adjoint_segment_f64) ------------------------
+// The workspace: the reverse plan's matrix rows, the partial sums.
+struct F64SegLayout { size_t rmats, partial, total; };
+static F64SegLayout f64_seg_layout(const qmle_plan *rev, int batch, int cot) {
+  F64SegLayout L;
+  L.rmats = 0;
+  L.partial = f64_mats_bytes(rev, batch);
+  L.total = L.partial + align_up((size_t)batch * f64_adj_blocks(rev->n) * sizeof(double2) * cot, 256) + 512;
+  return L;
+}
+static int f64_adjoint_segment_run(const AdjCall<double> &c, double2 *pair) {
+  qmle_plan *rev = c.rev;
+  if (!rev || !pair || c.batch < 1 || c.batch > kMaxGridY / 2 || !c.terms || !c.d_grad || c.n_grad_slots < 1 || !c.d_ws ||
+      c.n_terms != (int)rev->ops.size() || (rev->n_slots > 0 && !c.d_angles_rev) || (c.cot.off && !c.cot.d_cot))
+    return QMLE_ERR_INVALID_ARG;
+  if (!(rev->flags & QMLE_PLAN_NO_FUSION) || (rev->flags & QMLE_PLAN_INTERNAL_ZERO_RUN) || rev->n < 3)
+    return QMLE_ERR_UNSUPPORTED;
+  int rc = adj_check_one_source(rev);
+  if (rc != QMLE_OK) return rc;
+  std::vector<int> low_of;
+  rc = c.cot.off ? cot_request_check(rev, c.cot, low_of) : QMLE_OK;
+  if (rc != QMLE_OK) return rc;
+  for (int r = 0; r < c.n_terms; ++r) {
+    if (!adj_slot_in_range(c.terms[r], c.n_grad_slots)) return QMLE_ERR_SLOT_RANGE;
+    if (c.terms[r].out_slot >= 0 && !adj_marks_in_bounds(c.terms[r], rev->n, rev->n_user_consts)) return QMLE_ERR_INVALID_ARG;
+  }
+  const F64SegLayout L = f64_seg_layout(rev, c.batch, cot_partials(rev, c.cot));
+  char *ws = (char *)c.d_ws;
+  size_t ws_bytes = c.ws_bytes;
+  if (!align_workspace(ws, ws_bytes) || ws_bytes < L.total) return QMLE_ERR_WORKSPACE;
+  rc = ensure_device_plan(rev);
+  if (rc == QMLE_OK) rc = ensure_f64(rev);
+  if (rc != QMLE_OK) return rc;
+  hipStream_t stream = (hipStream_t)c.stream;
+  double *rmats = (double *)(ws + L.rmats);
+  launch_build_matrices_f64(rev, c.d_angles_rev, rmats, c.batch, stream);
+  const SweepView<double2> s = {pair, pair + ((size_t)c.batch << rev->n), (double2 *)(ws + L.partial), rev->n,
+                                f64_adj_blocks(rev->n), c.batch, stream};
+  return f64_adj_stage_loop(c, s, 0, rmats);
+}
+
 extern "C" {
+
+size_t qmle_adjoint_segment_workspace_bytes_f64(const qmle_plan *rev, int batch, int two_wire) {
+  if (!rev || batch < 1) return 0;
+  return f64_seg_layout(rev, batch, two_wire ? 16 : 4).total;
+}
+int qmle_adjoint_segment_f64(qmle_plan *rev, const double *d_angles_rev, int batch, void *d_pair,
+                             const qmle_adjoint_term *terms, int n_terms, double *d_grad, int n_grad_slots,
+                             const int32_t *cot_off, int cot_stride, double *d_cot, void *d_ws, size_t ws_bytes,
+                             qmle_stream stream) {
+  return f64_adjoint_segment_run({nullptr, rev, nullptr, d_angles_rev, batch, nullptr, {}, terms, n_terms, d_grad,
+                                  n_grad_slots, d_ws, ws_bytes, stream, {cot_off, cot_stride, d_cot}},
+                                 (double2 *)d_pair);
+}
 
 int qmle_adjoint_gradient_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
                               int batch, const double *d_weights, const uint32_t *obs_wire_masks, int n_obs,

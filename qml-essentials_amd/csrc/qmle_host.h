@@ -7,11 +7,14 @@
 //   qmle_mw.hip        Meyer-Wallach: read kernels of resident states, the sums behind a producing tile pass, and
 //                      their host path (one plan of the reads, one workspace layout per route, three finishes)
 //   qmle_adjoint.hip   adjoint differentiation in complex64: one check, one route choice, three routes (LDS, fused
-//                      tile passes, one streaming pass per gate)
+//                      tile passes, one streaming pass per gate); the stage loop of the last two on states the
+//                      caller holds (qmle_adjoint_segment)
 //   qmle_f64.hip       complex128 engine (its own matrix builder and constants) and its adjoint sweep
-//   qmle_adjoint_dev.h what those two sweeps share and nobody else includes: the kernels that are one text in both
-//                      precisions, a sweep's arguments and their checks, the launch pairs of the per-gate sweep, the
-//                      bodies of the extern "C" entry points
+//   qmle_adjoint_dev.h what those two sweeps share: the kernels that are one text in both precisions, a sweep's
+//                      arguments and their checks, the launch pairs of the per-gate sweep, the bodies of the
+//                      extern "C" entry points (qmle_wide.hip takes cot_finish_entry from it, nobody else includes it)
+//   qmle_wide.hip      the matrix cotangent of a dense gate on three or four wires (qmle_wide_moment): the moment of
+//                      psi and lambda on the matrix cores, per-block partials, one finishing kernel
 //   qmle_gram.hip      Gram matrices of resident states
 //   qmle_evolve.hip    Hamiltonian time evolution: 2x2 / 4x4 propagators on the fixed Magnus grids (qmle_evolve_magnus)
 //                      the pulse solves with and without sensitivities, and the composition of small circuits

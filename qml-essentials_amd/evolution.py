@@ -30,9 +30,14 @@ solver names run the doubling as always, then one Jacobian launch on the accepte
 Wires.  Hamiltonians on one and two wires are solved by ``qmle_evolve_magnus``, on three and four wires (8x8, 16x16) by
 ``qmle_evolve_magnus_wide``; five wires and more are refused.  The evolved gate of a three- or four-wire Hamiltonian
 is an explicit matrix on that many wires: ``simulation.simulate_and_measure`` runs it through ``qmle_apply_matrix``
-between the plans of the gates around it.  Gradients through such gates are out of scope: the Jacobian solve serves
-1 or 2 wires and says so, and every consumer that lowers a whole tape (the adjoint sweep, the parameter shift,
-compiled calls, noisy tapes) refuses the gate as it refuses any explicit matrix on more than two wires.
+between the plans of the gates around it.  The Jacobian solve serves 1 or 2 wires and says so, and every consumer
+that lowers a whole tape (the parameter shift, compiled calls, noisy tapes, the adjoint sweep by default) refuses the
+gate as it refuses any explicit matrix on more than two wires.  ``Script.vjp(..., wide_gates=True,
+through_evolve=True)`` records inside ``gradient_trace(wide=True)``: a STATIC evolved gate on three or four wires
+whose time depends on a leaf is then one step ``U = exp(-i t H)`` with ``dU/dt = -i H U`` (:func:`static_jacobian`),
+formed on the host from ``H`` and the solver's ``U`` -- the exact derivative of the exponential, which differs from
+the derivative of the solver's truncated series by that series' own 1e-13.  A ``ParametrizedHamiltonian`` on three or
+four wires that depends on a leaf stays refused: ``qmle_evolve_magnus_wide`` has no Jacobian form.
 
 Pulse-level gates (:mod:`pulses`) do not come through ``evolve``: their RX / RY leaves are solved by a kernel of their
 own that evaluates the envelopes on the device, all leaves of a tape in one launch.  They share the solver defaults
@@ -55,21 +60,37 @@ _FIRST_GRID = 32  # step doubling starts here
 
 
 _gradient_trace = 0  # > 0 while a tape is recorded for Script.vjp(through_evolve=True)
+_wide_trace = 0      # > 0 while that caller also sweeps tapes with three- and four-wire gates (wide_gates=True)
 
 _TRACKED = ("sums, products, quotients, powers with a constant exponent and sin, cos, tan, exp, expm1, log, log1p, "
             "sqrt, square, reciprocal, sinh, cosh, tanh, arctan of one tracked value")
 
 
 @contextlib.contextmanager
-def gradient_trace():
+def gradient_trace(wide: bool = False):
     """While active, ``evolve`` keeps the tangents of its arguments and records gates that carry the Jacobian of
-    their solve (module docstring).  Only a caller that asks the adjoint sweep for matrix cotangents enters it."""
-    global _gradient_trace
+    their solve (module docstring).  Only a caller that asks the adjoint sweep for matrix cotangents enters it.
+    ``wide``: the caller's sweep serves explicit matrices on three and four wires, so a static evolved gate on that
+    many wires is recorded with its Jacobian too."""
+    global _gradient_trace, _wide_trace
     _gradient_trace += 1
+    _wide_trace += int(bool(wide))
     try:
         yield
     finally:
         _gradient_trace -= 1
+        _wide_trace -= int(bool(wide))
+
+
+def static_jacobian(H: np.ndarray, U: np.ndarray) -> np.ndarray:
+    """``dU/dt = -i H U`` of the one-step evolution ``U = exp(-i t H)``: ``H`` ``[d, d]``, ``U`` ``[rows, d, d]``
+    -> ``[rows, d, d]`` complex128.  Host only."""
+    return -1j * np.einsum("ab,rbc->rac", np.asarray(H, dtype=np.complex128), np.asarray(U, dtype=np.complex128))
+
+
+WIDE_JACOBIAN_LIMIT = ("evolve(): a ParametrizedHamiltonian on three or four wires that depends on a differentiated "
+                       "argument is not differentiated: the Jacobian solve (qmle_evolve_magnus_jac) serves 1 or 2 "
+                       "wires, and wide_gates=True adds static Hamiltonians (Hermitian.evolve()) on 3 or 4 wires only")
 
 
 class EvolvedGate(Operation):
@@ -326,12 +347,32 @@ class Evolution:
         return EvolvedGate(out[:, 0], wires, name, out[:, 1:1 + len(directions)], list(directions), steps)
 
     @classmethod
+    def _static_wide_jacobian(cls, H: np.ndarray, t, rows: int, wires, name) -> Operation:
+        """The :class:`EvolvedGate` of a static Hamiltonian on three or four wires whose time depends on a leaf: the
+        solver's ``U`` and, per leaf element ``e`` the time depends on, ``dU/de = (dt/de) (-i H U)``."""
+        _vals, terms = _tracked_table(t, rows, 1, "the time t")
+        directions: dict = {}
+        for lid, idx, _coef in terms:
+            directions.setdefault((lid, int(idx[0])), len(directions))
+        if len(directions) > N.EVOLVE_MAX_DIRS:
+            raise NotImplementedError(f"evolve(): {name or 'the gate'} depends on {len(directions)} leaf elements; at "
+                                      f"most {N.EVOLVE_MAX_DIRS} per evolved gate are differentiated")
+        dt = np.zeros((rows, max(1, len(directions))))
+        for lid, idx, coef in terms:
+            dt[:, directions[lid, int(idx[0])]] += coef[:, 0]
+        U = cls._solve(H, np.ones((rows, 1, 1)), _per_row(t, rows), 2)
+        jac = dt[:, :, None, None] * static_jacobian(H[0], U)[:, None]
+        return EvolvedGate(U, wires, name, jac[:, :len(directions)], list(directions), 1)
+
+    @classmethod
     def _evolve_static(cls, hermitian: Hermitian, name: Optional[str]) -> Callable:
         H = np.asarray(hermitian.matrix, dtype=np.complex128)[None]
 
         def _apply(t, wires=0) -> Operation:
             rows = _rows_of([t])
             h = _per_row(t, rows)
+            if _gradient_trace and _wide_trace and H.shape[-1] in (8, 16) and _tangent_state([t]) is None:
+                return cls._static_wide_jacobian(H, t, rows, wires, name)
             if _gradient_trace and _tangent_state([t]) is None:  # one step of order 2, dcoef = 0, dh = dt
                 return cls._with_jacobian(H, [(np.ones((rows, 1)), [])], _tracked_table(t, rows, 1, "the time t"), 2,
                                           wires, name, 1)
@@ -388,6 +429,8 @@ class Evolution:
                 return cls._with_jacobian(H, tables, step, order, wires, name, n_steps, failed)
 
             tracked = _gradient_trace and _tangent_state(list(params) + span) is None
+            if tracked and _wide_trace and H.shape[-1] in (8, 16):  # (before any device work)
+                raise NotImplementedError(WIDE_JACOBIAN_LIMIT)
             steps = magnus_steps
             if solver in ("magnus2", "magnus4"):
                 if tracked:

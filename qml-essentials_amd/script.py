@@ -17,7 +17,8 @@ import numpy as np
 from . import _native as N
 from . import distributed, memory, pulses, simulation
 from .batching import Batched, to_numpy
-from .operations import MAX_PAULI_WIRES, KrausChannel, Operation, PauliRot, pauli_terms, z_parity_mask
+from .operations import (MAX_PAULI_WIRES, KrausChannel, Operation, PauliRot, is_wide_matrix_gate, pauli_terms,
+                         z_parity_mask)
 from .tape import batch_context, recording
 from .utils import PRNGKey
 
@@ -444,7 +445,7 @@ class Script:
     }
 
     def _trace_for_gradient(self, obs, args, kwargs, in_axes, argnums, skip_channels: bool = False,
-                            mat_ops: Optional[list] = None, through_evolve: bool = False):
+                            mat_ops: Optional[list] = None, through_evolve: bool = False, wide_gates: bool = False):
         """Record the tape with the ``argnums`` arguments as differentiable leaves.  Returns
         ``(tape, lowered tape, n_qubits, B, slots, leaf_shapes, batched)`` where ``slots`` lists
         ``(angle slot, shift rule, tangent terms)`` for every angle that depends on a leaf.
@@ -455,7 +456,10 @@ class Script:
         gate is then solved with its sensitivities here and does not count as "non-linear".  Only a caller that
         asks the sweep for matrix cotangents passes it (:meth:`vjp`).
         ``through_evolve``: the tape is recorded inside ``evolution.gradient_trace()``, so that evolved gates whose
-        arguments depend on a leaf are solved with their Jacobian and want a matrix cotangent too."""
+        arguments depend on a leaf are solved with their Jacobian and want a matrix cotangent too.
+        ``wide_gates``: a tape that holds explicit matrices on 3 or 4 wires is not lowered as a whole (the lowered
+        tape comes back as None); slots keep tape order, wide gates holding none, and ``mat_ops`` then receives
+        ``(index of the tape entry, operation)``."""
         kwargs = {} if kwargs is None else kwargs
         args = tuple(to_numpy(a) for a in args)
         batched = in_axes is not None
@@ -484,7 +488,7 @@ class Script:
         if through_evolve:
             from . import evolution
 
-            with evolution.gradient_trace():
+            with evolution.gradient_trace(wide=wide_gates):
                 tape = self._record_for_engine(*wrapped, **kwargs)
         else:
             tape = self._record_for_engine(*wrapped, **kwargs)
@@ -492,17 +496,31 @@ class Script:
         gates = [o for o in tape if not isinstance(o, KrausChannel)] if skip_channels else tape
         if mat_ops is not None:  # U and dU/d(arguments) of every pulse leaf that depends on a leaf: one launch group
             pulses.resolve_for_gradient(gates)
-        low = simulation.LoweredTape(gates, n_qubits)
+        segmented = wide_gates and any(is_wide_matrix_gate(o) for o in gates)
+        if segmented and any(isinstance(o, KrausChannel) for o in gates):
+            from .adjoint import AdjointUnsupported
+
+            raise AdjointUnsupported("adjoint differentiation of noisy circuits (explicit matrices on 3 or 4 wires are "
+                                     "not available on noisy tapes)")
+        low = None if segmented else simulation.LoweredTape(gates, n_qubits)
 
         # differentiable slots: (slot, rule, tangent terms)
         slots, s, k_op = [], 0, -1
-        for op_ in gates:
+        for k_entry, op_ in enumerate(gates):
+            if segmented and is_wide_matrix_gate(op_):  # no angle slot; a cotangent where its Jacobian is known
+                if mat_ops is not None and getattr(op_, "wants_matrix_cotangent", False):
+                    mat_ops.append((k_entry, op_))
+                elif op_.__dict__.get("_matrix_tangent", []) is None:
+                    raise NotImplementedError(
+                        f"{op_.name}: parameter is a non-linear function of the arguments; "
+                        "cannot apply the chain rule")
+                continue
             lowered = op_.lower(n_qubits)
             if lowered is None:
                 continue
             k_op += 1
             if mat_ops is not None and getattr(op_, "wants_matrix_cotangent", False):
-                mat_ops.append((k_op, op_))  # (its lowered parameters are matrix entries, not angles)
+                mat_ops.append((k_entry if segmented else k_op, op_))  # (its lowered parameters are matrix entries, not angles)
                 s += len(lowered[2])
                 continue
             tans = op_.parameter_tangents
@@ -519,7 +537,8 @@ class Script:
 
     def vjp(self, obs: List[Operation], cotangent, *, args: tuple = (),
             kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
-            argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False, through_evolve: bool = False):
+            argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False, through_evolve: bool = False,
+            wide_gates: bool = False):
         """Gradient of ``sum_k cotangent[b, k] * <obs_k>_b`` with respect to the array arguments
         ``argnums`` by ADJOINT differentiation: one backward sweep for all angles
         (:mod:`adjoint`).  ``obs``: at most 32 Z / Z-parity observables seed the sweep from their wire masks.
@@ -548,7 +567,19 @@ class Script:
         grid (``qmle_evolve_magnus_jac``) and contributes ``2 Re sum_ac G[a][c] dU[a][c]/d(leaf element)`` like a pulse
         leaf; an evolved gate that is a constant for this gradient is just inverted by the sweep.  Evolved gates on one
         and on two wires are served (2x2 and 4x4 cotangents from ``adjoint.adjoint_slot_and_matrices_gradient``);
-        Hamiltonians on more wires are refused by ``evolve()`` itself."""
+        Hamiltonians on more wires are refused by ``evolve()`` itself.
+
+        ``wide_gates=True`` serves tapes that hold explicit matrices on three or four wires (``op.prod(...)``,
+        ``A @ B``, a user's ``Operation(wires, matrix)``, evolved unitaries of 8x8 and 16x16 Hamiltonians, one matrix
+        for all samples or one per sample): the sweep runs segment by segment between them
+        (``adjoint.segmented_gradient``) and gives the gradient of every ordinary angle, of pulse leaves and of one-
+        and two-wire evolved gates on the same tape, for Z and Pauli seeds and K-stacked cotangents, in complex64 and
+        x64.  A wide gate that is a constant of the gradient is simply inverted.  With ``through_evolve=True`` as
+        well, a STATIC evolved gate on three or four wires, ``Hermitian(H, wires).evolve()(t)`` with ``t`` depending
+        on a leaf, is differentiated from ``dU/dt = -i H U``.  Still refused: a ``ParametrizedHamiltonian`` on three
+        or four wires that depends on a leaf (the wide solver has no Jacobian form), matrices on five or more wires,
+        noisy tapes; ``Script.gradient``, compiled calls, ``Model`` and the torch bridge do not take such tapes.
+        Without the keyword every refusal is what it was."""
         from . import adjoint
 
         if not obs:
@@ -561,10 +592,13 @@ class Script:
                 "H psi for sums of Pauli words (got " + ", ".join(kinds) + ")")
         mat_ops: list = []
         tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
-            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops, through_evolve=through_evolve)
+            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops, through_evolve=through_evolve, wide_gates=wide_gates)
         if any(isinstance(o, KrausChannel) for o in tape):
             raise adjoint.AdjointUnsupported("adjoint differentiation of noisy circuits")
+        segmented = low is None  # (wide_gates=True and a wide gate on the tape: the sweep segment by segment)
         for o in tape:  # without through_evolve evolved gates stay out of scope: nothing differentiates one
+            if segmented and is_wide_matrix_gate(o):  # (constant or carrying its Jacobian: _trace_for_gradient)
+                continue
             m = getattr(o, "_matrix", None)
             per_sample = not isinstance(o, pulses.PulseRotation) and getattr(o, "_native", None) is None \
                 and isinstance(m, np.ndarray) and m.ndim == 3
@@ -590,14 +624,23 @@ class Script:
         K = int(w.size // (B * len(obs)))  # K > 1: ``cotangent`` is (K, B, n_obs) -- K cotangents, ONE trace and sweep
         stacked = K > 1 or w.ndim == 3
         w = w.reshape(K * B, len(obs))
-        want = [False] * low.n_slots
+        want = [False] * (adjoint.tape_slot_count(tape, n_qubits) if segmented else low.n_slots)
         for s_, _rule, _t, _name in slots:
             want[s_] = True
         grads = {k: np.zeros((K, B) + tuple(shp)) for k, shp in leaf_shapes.items()}
         # a per-sample matrix that nothing is asked of (an evolved gate that is a constant for this gradient) still
         # needs the form of the reverse tape that inverts it
-        row_ops = through_evolve and any(name in ("MAT1_ROW", "MAT2_ROW") for name, _w, _s, _off in low.ops)
-        if mat_ops or (row_ops and slots):  # angle slots and matrix cotangents from ONE sweep
+        row_ops = not segmented and through_evolve and any(name in ("MAT1_ROW", "MAT2_ROW")
+                                                           for name, _w, _s, _off in low.ops)
+        if segmented:
+            cots = []
+            if mat_ops or slots:  # one [K * B, d, d] per flagged tape entry, d = 2, 4, 8 or 16
+                want_mat = [False] * len(tape)
+                for k_entry, _o in mat_ops:
+                    want_mat[k_entry] = True
+                d, cots = adjoint.segmented_gradient(tape, n_qubits, B, masks, w, want, want_mat, x64=x64,
+                                                     obs_terms=obs_terms)
+        elif mat_ops or (row_ops and slots):  # angle slots and matrix cotangents from ONE sweep
             want_mat = [False] * len(low.ops)
             for k_op, _o in mat_ops:
                 want_mat[k_op] = True
@@ -608,19 +651,19 @@ class Script:
                 d, cot = adjoint.adjoint_slot_and_matrix_gradient(low, n_qubits, B, masks, w, want, want_mat, x64=x64,
                                                                   obs_terms=obs_terms)  # [K * B, n_mat, 2, 2]
                 cots = [cot[:, m] for m in range(len(mat_ops))]
-            for m, ((_k, o), terms) in enumerate(zip(mat_ops, mat_terms)):
-                jac = np.asarray(o.jacobian, dtype=np.complex128)  # [B or 1, D, d, d]: D = 5 for a pulse leaf
-                jac = jac.reshape(jac.shape[0], jac.shape[1], -1)
-                g_m = np.asarray(cots[m], dtype=np.complex128).reshape(K, B, jac.shape[-1])  # (the op's own d * d)
-                # dC/d(slot) = 2 Re sum_ac G[a][c] dU[a][c]/d(slot)  -> [K, B, D]
-                per_slot = 2.0 * np.real(np.einsum("kbe,bse->kbs", g_m,
-                                                   np.broadcast_to(jac, (B,) + jac.shape[1:])))
-                for lid, slot, flat, coef in terms:
-                    g = grads[lid].reshape(K, B, -1)
-                    g[:, :, int(flat)] += per_slot[:, :, slot] * np.asarray(coef, dtype=np.float64).reshape(1, -1)
         elif slots:
             d = adjoint.adjoint_slot_gradient(low, n_qubits, B, masks, w, want, x64=x64,
                                               obs_terms=obs_terms)  # [K * B, n_slots]
+        for m, ((_k, o), terms) in enumerate(zip(mat_ops, mat_terms)):
+            jac = np.asarray(o.jacobian, dtype=np.complex128)  # [B or 1, D, d, d]: D = 5 for a pulse leaf
+            jac = jac.reshape(jac.shape[0], jac.shape[1], -1)
+            g_m = np.asarray(cots[m], dtype=np.complex128).reshape(K, B, jac.shape[-1])  # (the op's own d * d)
+            # dC/d(slot) = 2 Re sum_ac G[a][c] dU[a][c]/d(slot)  -> [K, B, D]
+            per_slot = 2.0 * np.real(np.einsum("kbe,bse->kbs", g_m,
+                                               np.broadcast_to(jac, (B,) + jac.shape[1:])))
+            for lid, slot, flat, coef in terms:
+                g = grads[lid].reshape(K, B, -1)
+                g[:, :, int(flat)] += per_slot[:, :, slot] * np.asarray(coef, dtype=np.float64).reshape(1, -1)
         if slots:
             d = d.reshape(K, B, -1)
             for s_, _rule, tangent, _name in slots:

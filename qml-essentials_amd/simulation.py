@@ -533,22 +533,12 @@ def _measure_resident(states, n_qubits: int, type: str, obs):
     return observables_expval(states, n_qubits, obs)
 
 
-def _simulate_segmented(tape: Sequence[Operation], n_qubits: int, type: str, obs, B: int, shots, key,
-                        row_offset: int, as_tensor: bool):
-    """A noise-free tape that holds explicit matrices on 3 or 4 wires.  No plan holds such a gate, so the tape is
-    cut at them (:func:`split_at_wide_gates`): the first segment runs as a plan from |0..0> to ``"state"``, every
-    later one in place on the resident states (``apply_inplace`` / ``apply_inplace64``); an empty segment launches
-    nothing (an empty first one leaves |0..0>); every wide gate runs through ``qmle_apply_matrix``, one matrix for
-    all samples or one per sample; the result is measured from the resident states (:func:`_measure_resident`;
-    shots from their probabilities).  The states of all samples are resident whatever is measured, so the batch is
-    cut as for a ``"state"`` run -- here: the angle tables and the per-sample matrices stay on the host and every
-    chunk uploads its own rows."""
+def segmented_plans(tape: Sequence[Operation], n_qubits: int, B: int, x64: bool):
+    """What a forward run of a tape with wide gates needs -> ``(plans, gates)``: per segment of
+    :func:`split_at_wide_gates` ``(plan, host angle table or None)`` or None for an empty one; per wide gate
+    ``(wires, matrices)`` -- one matrix for every sample: on the device once; one per sample: on the host, a chunk
+    uploads its own."""
     torch = N.require_gpu()
-    from . import memory
-    from .utils import x64_enabled
-
-    x64 = x64_enabled()
-    sampled = shots is not None and type in ("probs", "expval")
     segments, positions = split_at_wide_gates(tape)
     flags = (PLAN_FLAGS or 0) | N.PLAN_NO_MERGE if x64 else None  # (x64: gate by gate, as simulate_and_measure)
     plans = []
@@ -567,34 +557,65 @@ def _simulate_segmented(tape: Sequence[Operation], n_qubits: int, type: str, obs
             raise ValueError(f"{o.name}: matrix shape {m.shape[-2:]} does not match {k} wire(s)")
         if m.ndim == 3 and m.shape[0] != B:
             raise ValueError(f"{o.name}: one matrix per sample needs {B} matrices, got {m.shape[0]}")
-        # one matrix for every sample: on the device once; one per sample: on the host, a chunk uploads its own
         gates.append((list(o.wires), np.ascontiguousarray(m) if m.ndim == 3 else torch.from_numpy(np.ascontiguousarray(m)).cuda()))
+    return plans, gates
 
-    def run(lo: int, hi: int):
-        real = torch.float64 if x64 else torch.float32
 
-        def angles_of(table):  # the chunk's rows of a segment's table, or None for a segment without an angle slot
-            return None if table is None else torch.from_numpy(np.ascontiguousarray(table[lo:hi])).cuda()
+def segmented_forward(plans, gates, n_qubits: int, lo: int, hi: int, x64: bool, out=None):
+    """The states of samples ``[lo, hi)`` behind the whole tape of :func:`segmented_plans`, resident: the first
+    segment from |0..0>, then every wide gate and the segment behind it in place.  ``out``: a contiguous
+    ``[hi - lo, 2^n]`` tensor of the run's complex dtype that receives them (the adjoint sweep's psi half)."""
+    torch = N.require_gpu()
+    real = torch.float64 if x64 else torch.float32
 
-        if plans[0] is None:  # a wide gate opens the tape: |0..0> without a plan
+    def angles_of(table):  # the chunk's rows of a segment's table, or None for a segment without an angle slot
+        return None if table is None else torch.from_numpy(np.ascontiguousarray(table[lo:hi])).cuda()
+
+    if plans[0] is None:  # a wide gate opens the tape: |0..0> without a plan
+        if out is None:
             states = torch.zeros((hi - lo, 1 << n_qubits), dtype=torch.complex128 if x64 else torch.complex64,
                                  device=N.current_device())
-            states[:, 0] = 1.0
         else:
-            plan, table = plans[0]
-            angles = angles_of(table)
-            if angles is None:  # (no angle slot: the table only carries the batch size)
-                angles = torch.zeros((hi - lo, 1), dtype=real, device=N.current_device())
-            states = plan.run64(angles, "state") if x64 else plan.run(angles, "state")
-        for (wires, mats), later in zip(gates, plans[1:]):
-            N.apply_matrix(states, wires, mats[lo:hi] if isinstance(mats, np.ndarray) else mats)
-            if later is None:
-                continue
-            plan, table = later
-            angles = angles_of(table)
-            for b0 in range(0, hi - lo, 65535):  # (one launch of the in-place call takes this many states)
-                sl = slice(b0, min(hi - lo, b0 + 65535))
-                (N.apply_inplace64 if x64 else N.apply_inplace)(plan, None if angles is None else angles[sl], states[sl])
+            states = out.zero_()
+        states[:, 0] = 1.0
+    else:
+        plan, table = plans[0]
+        angles = angles_of(table)
+        if angles is None:  # (no angle slot: the table only carries the batch size)
+            angles = torch.zeros((hi - lo, 1), dtype=real, device=N.current_device())
+        states = plan.run64(angles, "state", out=out) if x64 else plan.run(angles, "state", out=out)
+    for (wires, mats), later in zip(gates, plans[1:]):
+        N.apply_matrix(states, wires, mats[lo:hi] if isinstance(mats, np.ndarray) else mats)
+        if later is None:
+            continue
+        plan, table = later
+        angles = angles_of(table)
+        for b0 in range(0, hi - lo, 65535):  # (one launch of the in-place call takes this many states)
+            sl = slice(b0, min(hi - lo, b0 + 65535))
+            (N.apply_inplace64 if x64 else N.apply_inplace)(plan, None if angles is None else angles[sl], states[sl])
+    return states
+
+
+def _simulate_segmented(tape: Sequence[Operation], n_qubits: int, type: str, obs, B: int, shots, key,
+                        row_offset: int, as_tensor: bool):
+    """A noise-free tape that holds explicit matrices on 3 or 4 wires.  No plan holds such a gate, so the tape is
+    cut at them (:func:`split_at_wide_gates`): the first segment runs as a plan from |0..0> to ``"state"``, every
+    later one in place on the resident states (``apply_inplace`` / ``apply_inplace64``); an empty segment launches
+    nothing (an empty first one leaves |0..0>); every wide gate runs through ``qmle_apply_matrix``, one matrix for
+    all samples or one per sample; the result is measured from the resident states (:func:`_measure_resident`;
+    shots from their probabilities).  The states of all samples are resident whatever is measured, so the batch is
+    cut as for a ``"state"`` run -- here: the angle tables and the per-sample matrices stay on the host and every
+    chunk uploads its own rows."""
+    torch = N.require_gpu()
+    from . import memory
+    from .utils import x64_enabled
+
+    x64 = x64_enabled()
+    sampled = shots is not None and type in ("probs", "expval")
+    plans, gates = segmented_plans(tape, n_qubits, B, x64)
+
+    def run(lo: int, hi: int):
+        states = segmented_forward(plans, gates, n_qubits, lo, hi, x64)
         if sampled:
             probs = _measure_resident(states, n_qubits, "probs", [])
             return sample_shots(probs.float() if x64 else probs, n_qubits, type, obs, shots, key, row_offset + lo)
