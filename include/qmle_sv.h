@@ -777,6 +777,63 @@ int qmle_adjoint_segment_f64(qmle_plan *rev, const double *d_angles_rev, int bat
                              qmle_stream stream);
 size_t qmle_adjoint_segment_workspace_bytes_f64(const qmle_plan *rev, int batch, int two_wire);
 
+/* ---- adjoint differentiation of NOISY tapes: one backward sweep over vec(rho) ----------------------------------
+ * The tape acts on rho (vec(rho): a 2n-wire register, ket wires 0..n-1, bra wires n..2n-1) as U rho U^+ for a gate and
+ * sum K rho K^+ for a channel; C = sum_k w_k Tr(O_k rho).  A channel has no usable inverse, so the forward states are
+ * kept and only the observable moves backwards: Lambda_L = sum_k w_k O_k, Lambda_{j-1} = A_j^+ Lambda_j with A_j the
+ * doubled operator of tape entry j, and for a gate exp(-i theta G / 2) with rho_j the state behind it
+ *   dC/dtheta = Im <lambda_j| G_ket |v_j>,   v = vec(rho), lambda = vec(Lambda), G on the ket wires only.
+ * `fwd`: a QMLE_PLAN_NO_FUSION | QMLE_PLAN_TAPE_ORDER plan of the doubled tape (Rot already split into its three
+ * rotations), `rev`: such a plan of its reversed, daggered tape; any other plan is QMLE_ERR_UNSUPPORTED.  A STEP names
+ * one differentiable source gate: the ops [fwd_first, fwd_first + fwd_count) of `fwd` (its ket operator, its bra
+ * operator and the channels behind it on the same wires) and [rev_first, ..) of `rev`, which the call does NOT run
+ * through the plans: two kernels apply the gate pair from the sample's angle (column angle_slot of d_angles_fwd) and
+ * the channels as ONE superoperator -- d_chan + chan_off: [4][4][re, im] for a one-wire gate, [16][16][re, im] for a
+ * two-wire one, DEVICE, in the precision of the call, row index = the step's wires in ASCENDING order, first wire most
+ * significant; chan_off = -1: no channel -- to 4 or 16 amplitudes per work item in registers.  Forward, a step reads
+ * checkpoint k and writes checkpoint k + 1; backward it reads lambda and checkpoint k, writes lambda and reports
+ * term.coef Im i^n_y <lambda'| X^x Z^z Pi_p |v_mid> into d_grad[row][term.out_slot] (`term` as for
+ * qmle_adjoint_gradient, wires of the ket half only): five state-sized transfers per step.  Everything outside the
+ * steps runs one operator per pass: forward in place on the newest checkpoint, backward on lambda alone.
+ * opcode: QMLE_OP_RX / RY / RZ (wires[1] = -1) or CRX / CRY / CRZ / CPHASE / RXX / RYY / RZZ / RZX; steps in tape order.
+ * n_cot cotangents per sample: d_weights [n_cot * batch][n_obs], d_angles_rev [n_cot * batch][rev slots] and
+ * d_grad [n_cot * batch][n_grad_slots] (zeroed by the call) are sample-minor, row r of lambda reads checkpoint row
+ * r % batch; checkpoints are stored once per sample.  n_cot * batch <= 65535.
+ * The seed: exactly one of obs_wire_masks (Z parities of the n system wires) and obs_terms (Pauli words of the n
+ * system wires with the limits of qmle_apply_pauli_sum, at most 96 of them) is non-NULL, else QMLE_ERR_INVALID_ARG.
+ * All codes are decided before any device work: QMLE_ERR_INVALID_ARG also for NULL pointers, 2n < 4, overlapping
+ * steps, a generator outside its step's ket wires; QMLE_ERR_WIRE_COUNT / WIRE_RANGE / DUPLICATE_WIRES / SLOT_RANGE for a
+ * step's wires and slots; a workspace smaller than the query's answer is QMLE_ERR_WORKSPACE.  The workspace holds
+ * (n_steps + 1) * batch checkpoints and n_cot * batch rows of lambda beside the plans' matrix rows. */
+typedef struct qmle_density_step {
+  int32_t opcode;
+  int32_t wires[2];              /* ket wires of the source gate, in the gate's own order */
+  int32_t angle_slot;
+  int32_t chan_off;              /* offset in scalars into d_chan, or -1 */
+  int32_t fwd_first, fwd_count;
+  int32_t rev_first, rev_count;
+  qmle_adjoint_term term;
+} qmle_density_step;
+int qmle_adjoint_density(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
+                         int batch, int n_cot, const float *d_weights, const uint32_t *obs_wire_masks,
+                         const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                         const qmle_density_step *steps, int n_steps, const float *d_chan, int n_chan, float *d_grad,
+                         int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_density_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_cot,
+                                            int n_steps);
+int qmle_adjoint_density_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
+                             int batch, int n_cot, const double *d_weights, const uint32_t *obs_wire_masks,
+                             const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                             const qmle_density_step *steps, int n_steps, const double *d_chan, int n_chan,
+                             double *d_grad, int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream);
+size_t qmle_adjoint_density_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_cot,
+                                                int n_steps);
+/* host only: the modelled state-sized reads and writes of a call per sample -- forward 1 (checkpoint 0) + 2 per
+ * operator outside the steps + 2 per step; backward, times n_cot, 1 (the seed) + 2 per operator behind the tape's
+ * first step + 3 per step -- or a negative status for arguments the call would refuse. */
+long long qmle_adjoint_density_transfers(const qmle_plan *fwd, const qmle_plan *rev, const qmle_density_step *steps,
+                                         int n_steps, int n_cot, int f64);
+
 /* ---- Gram matrices of resident states (quantum geometric tensor) ---------------------------
  * G[g][r][s] = sum_k conj(a[g][r][k]) * b[g][s][k] for g < n_groups, r < rows_a, s < rows_b:
  * d_out complex128, row-major [n_groups][rows_a][rows_b].  Row r of group g starts at amplitude

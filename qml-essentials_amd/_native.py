@@ -246,6 +246,13 @@ SYMBOLS = [
     ("qmle_adjoint_segment_f64", _I, [_VP, _VP, _I, _VP, _VP, _I, _VP, _I, C.POINTER(C.c_int32), _I, _VP, _VP, _SZ,
                                       _VP]),
     ("qmle_adjoint_segment_workspace_bytes_f64", _SZ, [_VP, _I, _I]),
+    ("qmle_adjoint_density", _I, [_VP, _VP, _VP, _VP, _I, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm), _I,
+                                  _I, _VP, _I, _VP, _I, _VP, _I, _VP, _SZ, _VP]),
+    ("qmle_adjoint_density_workspace_bytes", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_density_f64", _I, [_VP, _VP, _VP, _VP, _I, _I, _VP, C.POINTER(C.c_uint32), C.POINTER(QmlePauliTerm),
+                                      _I, _I, _VP, _I, _VP, _I, _VP, _I, _VP, _SZ, _VP]),
+    ("qmle_adjoint_density_workspace_bytes_f64", _SZ, [_VP, _VP, _I, _I, _I]),
+    ("qmle_adjoint_density_transfers", C.c_longlong, [_VP, _VP, _VP, _I, _I, _I]),
     ("qmle_sample_counts", _I, [_VP, _I, _I, _I, C.c_uint64, C.c_uint64, _VP, _VP, _VP, _SZ,
                                 _VP]),
     ("qmle_sample_workspace_bytes", _SZ, [_I, _I]),
@@ -1733,3 +1740,76 @@ def adjoint_segment(rev: Plan, angles_rev, pair, terms, grad, cot_off=None, cot=
         int(cot.shape[1]) if cot is not None else 0, C.c_void_p(cot.data_ptr()) if cot is not None else None,
         C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
     return grad
+
+
+class DensityStep(C.Structure):
+    _fields_ = [("opcode", C.c_int32), ("wires", C.c_int32 * 2), ("angle_slot", C.c_int32), ("chan_off", C.c_int32),
+                ("fwd_first", C.c_int32), ("fwd_count", C.c_int32), ("rev_first", C.c_int32), ("rev_count", C.c_int32),
+                ("term", AdjointTerm)]
+
+
+def density_step_array(steps):
+    """``[(opcode, (w0, w1 | -1), angle_slot, chan_off, fwd_first, fwd_count, rev_first, rev_count, term)]`` -> a ctypes
+    array of ``qmle_density_step`` (``term`` as for :func:`adjoint_gradient`)."""
+    arr = (DensityStep * max(1, len(steps)))()
+    for i, (code, wires, slot, chan_off, f0, fc, r0, rc, term) in enumerate(steps):
+        a = arr[i]
+        a.opcode, a.angle_slot, a.chan_off = int(code), int(slot), int(chan_off)
+        a.wires[0], a.wires[1] = int(wires[0]), int(wires[1])
+        a.fwd_first, a.fwd_count, a.rev_first, a.rev_count = int(f0), int(fc), int(r0), int(rc)
+        (a.term.out_slot, a.term.x_wires, a.term.z_wires, a.term.proj_wires, a.term.n_y, a.term.coef,
+         a.term.marks_off) = term
+    return arr
+
+
+def adjoint_density_transfers(fwd: Plan, rev: Plan, steps, n_cot: int = 1, f64: bool = False) -> int:
+    """Host only: the modelled state-sized reads and writes per sample of :func:`adjoint_density`
+    (``qmle_adjoint_density_transfers``)."""
+    got = int(lib().qmle_adjoint_density_transfers(fwd._h, rev._h, density_step_array(steps), len(steps), int(n_cot),
+                                                   int(bool(f64))))
+    if got < 0:
+        check(got, "qmle_adjoint_density_transfers")
+    return got
+
+
+def adjoint_density_workspace_bytes(fwd: Plan, rev: Plan, batch: int, n_cot: int, n_steps: int, f64: bool = False) -> int:
+    """Host only: the workspace :func:`adjoint_density` allocates for ``batch`` samples and ``n_cot`` cotangents each
+    (0: arguments the call would refuse)."""
+    wsq = getattr(lib(), "qmle_adjoint_density_workspace_bytes" + ("_f64" if f64 else ""))
+    return int(wsq(fwd._h, rev._h, int(batch), int(n_cot), int(n_steps)))
+
+
+def adjoint_density(fwd: Plan, rev: Plan, angles_fwd, angles_rev, weights, wire_groups, steps, chan, n_grad_slots: int,
+                    n_cot: int = 1, obs_terms=None):
+    """The backward sweep of a NOISY tape over vec(rho) -- ``qmle_adjoint_density`` / ``_f64`` (float64 tensors in: the
+    complex128 sweep).  ``fwd`` / ``rev``: ``PLAN_NO_FUSION | PLAN_TAPE_ORDER`` plans of the doubled primitive tape and
+    of its reversed, daggered tape on ``2 n`` wires; ``angles_fwd`` ``[B, fwd slots]``, ``angles_rev`` and ``weights``
+    ``[n_cot * B, ..]``, sample-minor; ``steps`` as for :func:`density_step_array`; ``chan``: the steps' superoperators,
+    a real tensor of the call's precision (or None).  The observables name the ``n`` system wires: Z parities
+    ``wire_groups`` or, with ``wire_groups`` None, the term list ``obs_terms``.  -> ``[n_cot * B, n_grad_slots]``."""
+    torch = require_gpu()
+    f64 = weights.dtype == torch.float64
+    ft, dev = torch.float64 if f64 else torch.float32, weights.device
+    if (wire_groups is None) == (obs_terms is None):
+        raise ValueError("pass either wire_groups or obs_terms")
+    if weights.dim() != 2 or angles_fwd.dtype != ft or angles_rev.dtype != ft or (chan is not None and chan.dtype != ft):
+        raise ValueError(f"adjoint_density: weights [n_cot * B, n_obs], angle tables and superoperators of {ft}")
+    rows, n_obs = int(weights.shape[0]), int(weights.shape[1])
+    B = int(angles_fwd.shape[0])
+    if rows != int(n_cot) * B or int(angles_rev.shape[0]) != rows:
+        raise ValueError(f"adjoint_density: weights and reverse angles need {int(n_cot)} * {B} rows")
+    n = fwd.n_qubits // 2
+    masks = _wire_group_masks(wire_groups, n) if wire_groups is not None else None
+    oarr = pauli_term_array(obs_terms) if obs_terms is not None else None
+    suffix = "_f64" if f64 else ""
+    wsq = getattr(lib(), "qmle_adjoint_density_workspace_bytes" + suffix)
+    out = torch.empty((rows, int(n_grad_slots)), dtype=ft, device=dev)
+    ws = torch.empty(max(1, int(wsq(fwd._h, rev._h, B, int(n_cot), len(steps)))), dtype=torch.uint8, device=dev)
+    what = "qmle_adjoint_density" + suffix
+    check(getattr(lib(), what)(
+        fwd._h, rev._h, C.c_void_p(angles_fwd.data_ptr()), C.c_void_p(angles_rev.data_ptr()), B, int(n_cot),
+        C.c_void_p(weights.data_ptr()), masks, oarr, len(obs_terms) if obs_terms is not None else 0, n_obs,
+        density_step_array(steps), len(steps), C.c_void_p(chan.data_ptr()) if chan is not None else None,
+        int(chan.numel()) if chan is not None else 0, C.c_void_p(out.data_ptr()), int(n_grad_slots),
+        C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()), _stream_ptr()), what)
+    return out

@@ -20,6 +20,11 @@ and the seed leave psi and lambda resident, ``qmle_adjoint_segment`` sweeps the 
 them, ``qmle_wide_moment`` reports a wide gate's 8x8 / 16x16 cotangent and ``qmle_apply_matrix`` undoes the gate
 on both states.
 
+NOISY tapes (Kraus channels on one and two wires) have a sweep of their own over vec(rho): a channel has no usable
+inverse, so the forward states are kept and only the observable is pulled back (:func:`plan_density`,
+:func:`density_gradient`, ``qmle_adjoint_density``): one step per wanted angle -- the gate pair and the channels behind it
+on its wires -- at five state-sized transfers, the K cotangents of a Jacobian sharing one set of forward states.
+
 This module only prepares the REVERSED, DAGGERED tape and the generator table; the sweep itself
 runs in the engine.
 """
@@ -513,3 +518,248 @@ def segmented_gradient(tape, n_qubits: int, batch: int, obs_groups, weights: np.
             blk = rows[:, :, off:off + 2 * d * d].reshape(K * B, d, d, 2)
             cots.append(blk[..., 0] + 1j * blk[..., 1])
     return grad.reshape(K * B, -1)[:, : sw.n_slots], cots
+
+
+# ---- noisy tapes: one backward sweep over vec(rho), forward states kept ------------------------------
+# one operator per pass, in tape order: the steps name ranges of the tape's ops
+DENSITY_FLAGS = N.PLAN_NO_FUSION | N.PLAN_FORCE_GLOBAL | N.PLAN_NO_ABSORB | N.PLAN_TAPE_ORDER
+_STEP_GATES = tuple(_ROT) + ("CPhase", "ControlledPhaseShift")
+# the model of a call's state-sized reads and writes (``qmle_adjoint_density_transfers`` counts the same on its plans)
+STEP_TRANSFERS_FWD, STEP_TRANSFERS_BWD, FREE_TRANSFERS = 2, 3, 2
+
+
+class DensitySweep(NamedTuple):
+    """What :func:`plan_density` makes of a noisy tape (host only)."""
+    fwd: LoweredTape        # the doubled primitive tape: Rot split, every step's channels right behind its gate pair
+    rev: LoweredTape        # its reversed, daggered tape (``build_reverse``)
+    rev_src: np.ndarray     # reverse slot j holds MINUS forward column rev_src[j]
+    steps: tuple            # ``N.density_step_array`` entries, tape order; ``term[0]`` is a slot of the SOURCE tape
+    chan: np.ndarray        # float64: the steps' superoperators, [d, d, (re, im)] each, wires ascending
+    n_slots: int            # angle slots of the source tape (``LoweredTape`` of the tape without its channels)
+    n_free_fwd: int         # operators outside the steps
+    n_free_bwd: int         # ... of which behind the first step: the backward sweep runs their daggers
+    n_qubits: int
+
+    @property
+    def checkpoints(self) -> int:
+        """State buffers per SAMPLE (never per cotangent): the working state in front of the first step and one
+        behind every step."""
+        return len(self.steps) + 1
+
+    def transfers(self, n_cot: int = 1) -> int:
+        """Modelled state-sized reads and writes per sample: forward once, backward per cotangent."""
+        f = 1 + FREE_TRANSFERS * self.n_free_fwd + STEP_TRANSFERS_FWD * len(self.steps)
+        b = 1 + (FREE_TRANSFERS * self.n_free_bwd + STEP_TRANSFERS_BWD * len(self.steps) if self.steps else 0)
+        return f + int(n_cot) * b
+
+    def sample_bytes(self, n_cot: int = 1, x64: bool = False) -> int:
+        """Bytes one sample keeps resident: its checkpoints and ``n_cot`` rows of lambda."""
+        return (self.checkpoints + int(n_cot)) * ((16 if x64 else 8) << (2 * self.n_qubits))
+
+
+def density_rounds(batch: int, need, max_bytes: int, max_samples: Optional[int] = None) -> List[int]:
+    """The batch cut into rounds that fit ``max_bytes`` (and count at most ``max_samples``: the rows of lambda of one
+    engine call are one launch's grid rows).  ``need``: bytes per sample (an int: the need grows linearly), or a
+    function ``samples -> bytes`` (:func:`density_call_bytes`: the library's own workspace and the call's tables).  One
+    sample that does not fit is refused with the bytes it needs."""
+    cost = need if callable(need) else (lambda bc: bc * int(need))
+    if cost(1) > max_bytes:
+        raise AdjointUnsupported(f"adjoint differentiation of this noisy circuit keeps {cost(1)} bytes of forward "
+                                 f"states, lambda and workspace per sample resident; the budget is {max_bytes} bytes "
+                                 "(recomputation schemes are not served)")
+    cap = batch if max_samples is None else max(1, min(batch, int(max_samples)))
+    per, over = 1, cap + 1  # the largest count that fits, by bisection (the need grows with the count)
+    if cost(cap) <= max_bytes:
+        per = cap
+    while over - per > 1 and per < cap:
+        mid = (per + over) // 2
+        per, over = (mid, over) if cost(mid) <= max_bytes else (per, mid)
+    return [min(per, batch - lo) for lo in range(0, batch, per)]
+
+
+def density_call_bytes(sw: "DensitySweep", fwd_plan, rev_plan, samples: int, n_cot: int, n_obs: int,
+                       x64: bool = False) -> int:
+    """Device bytes of one ``qmle_adjoint_density`` call on ``samples`` samples: the library's workspace (checkpoints,
+    lambda, the plans' matrix rows, the partial sums -- its own query, host only) and the tables beside it (angles of
+    both tapes, weights, gradient rows, the steps' superoperators)."""
+    real = 8 if x64 else 4
+    rows = int(samples) * int(n_cot)
+    ws = N.adjoint_density_workspace_bytes(fwd_plan, rev_plan, int(samples), int(n_cot), len(sw.steps), f64=x64)
+    tables = (int(samples) * max(1, sw.fwd.n_slots) + rows * (max(1, sw.rev.n_slots) + int(n_obs) + max(1, sw.n_slots))
+              + sw.chan.size) * real
+    return int(ws) + int(tables)
+
+
+_LAST_SWEEP: list = [None]
+
+
+def last_density_sweep() -> Optional["DensitySweep"]:
+    """Report only: the plan of the last :func:`density_gradient` call (what a benchmark counts transfers on)."""
+    return _LAST_SWEEP[0]
+
+
+def _embed(m: np.ndarray, wires, target) -> np.ndarray:
+    """The operator ``m`` on ``wires`` (first wire most significant) as an operator on ``target`` (a superset)."""
+    k, t = len(wires), len(target)
+    order = list(wires) + [w for w in target if w not in wires]
+    full = np.kron(m, np.eye(2 ** (t - k))).reshape([2] * (2 * t))
+    perm = [order.index(w) for w in target]
+    return full.transpose(perm + [t + p for p in perm]).reshape(2 ** t, 2 ** t)
+
+
+def plan_density(tape, n_qubits: int, want: Sequence[bool], x64: bool = False) -> DensitySweep:
+    """Host only: the sweep of a tape that holds Kraus channels on one and two wires.  ``want[s]``: angle slot ``s``
+    of the source tape (numbered as ``LoweredTape`` numbers them, channels holding none) needs a derivative.  Every
+    wanted rotation becomes a STEP: its ket and bra operators and the channels that follow it on its wires -- pulled
+    forward past the operators on other wires that ``simulation.doubled_tape`` emitted in between -- as one
+    superoperator.  Refused, naming the operation: channels on three or four wires, full-register diagonal encodings,
+    per-sample matrices (pulse and evolved gates), explicit matrices on three or four wires."""
+    from .simulation import _WideChannel, doubled_tape
+
+    n = int(n_qubits)
+    for o in tape:
+        if is_wide_matrix_gate(o):
+            raise AdjointUnsupported(f"adjoint differentiation of noisy circuits: {o.name} is an explicit matrix on "
+                                     f"{len(o.wires)} wires")
+    prims = []  # (name, wires, params, blob, source slot | None, is_channel)
+    slot = 0
+    items = doubled_tape(tape, n)
+    i = 0
+    while i < len(items):
+        it = items[i]
+        if isinstance(it, _WideChannel):
+            raise AdjointUnsupported(f"adjoint differentiation of noisy circuits: a channel on {len(it.wires)} wires "
+                                     "(_WideChannel) is applied as a Kraus sum, which the sweep does not pull back")
+        name, wires, params, blob = it.lower(2 * n)
+        if name == "DIAG_ALL":
+            raise AdjointUnsupported("adjoint differentiation of noisy circuits: DIAG_ALL (a full-register diagonal "
+                                     "encoding) is not served")
+        if name in ("MAT1_ROW", "MAT2_ROW"):
+            raise AdjointUnsupported(f"adjoint differentiation of noisy circuits: {name} (a per-sample matrix: pulse "
+                                     "and evolved gates) is not served")
+        if wires and min(wires) < n <= max(wires):  # a channel's superoperator spans both halves
+            prims.append((name, list(wires), [], blob, None, True))
+            i += 1
+            continue
+        bname, bwires, bparams, bblob = items[i + 1].lower(2 * n)  # conj(U) on the bra wires: right behind U
+        if name == "Rot":
+            for j, g in enumerate(("RZ", "RY", "RZ")):
+                prims.append((g, list(wires), [params[j]], None, slot + j, False))
+                prims.append((g, list(bwires), [bparams[j]], None, None, False))
+        else:
+            if len(params) > 1:
+                raise AdjointUnsupported(f"{name}: more than one angle per gate")
+            prims.append((name, list(wires), list(params), blob, slot if params else None, False))
+            prims.append((bname, list(bwires), list(bparams), bblob, None, False))
+        slot += len(params)
+        i += 2
+    if slot != len(want):
+        raise ValueError(f"want holds {len(want)} flags, the tape has {slot} angle slots")
+    # steps: the wanted rotations with the channels behind them on their wires
+    used, seq, spans = [False] * len(prims), [], []  # spans: (first index in seq, count, channel prims, ket prim)
+    for i, p in enumerate(prims):
+        if used[i]:
+            continue
+        used[i] = True
+        seq.append(p)
+        if p[4] is None or not want[p[4]] or p[5]:
+            continue
+        if p[0] not in _STEP_GATES:
+            raise AdjointUnsupported(f"no adjoint rule for {p[0]}")
+        used[i + 1] = True
+        seq.append(prims[i + 1])
+        mine, chans = set(p[1]) | set(prims[i + 1][1]), []
+        for j in range(i + 2, len(prims)):
+            if used[j]:
+                continue
+            q = prims[j]
+            if q[5] and set(q[1]) <= mine:
+                used[j] = True
+                seq.append(q)
+                chans.append(q)
+            elif mine & set(q[1]):
+                break
+        spans.append((len(seq) - 2 - len(chans), 2 + len(chans), chans, p))
+    fwd = LoweredTape([_Lowered((p[0], p[1], p[2], p[3])) for p in seq], 2 * n)
+    fslot = {}  # index in seq -> forward slot of the doubled tape
+    for k, (_name, _w, slots, _off) in enumerate(fwd.ops):
+        if slots:
+            fslot[k] = slots[0]
+    want2 = [False] * fwd.n_slots
+    for first, _cnt, _ch, _p in spans:
+        want2[fslot[first]] = True
+    rev_ops, terms, rev_src = build_reverse(fwd, _op_blobs(fwd, x64), want2)
+    rev = LoweredTape(rev_ops, 2 * n)
+    R = len(seq)
+    assert len(rev_ops) == R, "the doubled primitive tape reverses operator by operator"
+    steps, blobs, off = [], [], 0
+    for first, cnt, chans, p in spans:
+        ket = sorted(p[1])
+        target = ket + [w + n for w in ket]
+        chan_off = -1
+        if chans:
+            c = np.eye(2 ** len(target), dtype=np.complex128)
+            for q in chans:
+                m = np.asarray(q[3], dtype=np.float64).reshape(-1, 2)
+                d = 2 ** len(q[1])
+                c = _embed((m[:, 0] + 1j * m[:, 1]).reshape(d, d), q[1], target) @ c
+            blobs.append(np.stack([c.real, c.imag], axis=-1).reshape(-1))
+            chan_off, off = off, off + blobs[-1].size
+        t = terms[R - 1 - first]
+        steps.append((N.OPCODES[p[0]], (p[1][0], p[1][1] if len(p[1]) > 1 else -1), fslot[first], chan_off, first, cnt,
+                      R - first - cnt, cnt, (p[4],) + tuple(t[1:])))
+    in_step = sum(s[5] for s in steps)
+    behind = sum(1 for k in range(R) if steps and k >= steps[0][4]) - in_step
+    return DensitySweep(fwd, rev, np.asarray(rev_src if rev_src else [0], dtype=np.int64), tuple(steps),
+                        np.concatenate(blobs) if blobs else np.zeros(0), slot, R - in_step, behind, n)
+
+
+def density_gradient(tape, n_qubits: int, batch: int, obs_groups, weights: np.ndarray, want: Sequence[bool],
+                     x64: bool = False, obs_terms=None, max_bytes: Optional[int] = None) -> np.ndarray:
+    """:func:`adjoint_slot_gradient` for a tape with Kraus channels on one and two wires: d/d(angle slot) of
+    ``sum_k weights[b, k] Tr(O_k rho)`` -> ``[K * B, n_slots]`` (``weights`` ``[K * B, n_obs]``, sample-minor; columns
+    that are not wanted stay zero), by ``qmle_adjoint_density``: the forward states of every step stay resident, the
+    observable alone is pulled back, and K cotangents share one forward run.  Observables: Z-parity wire groups
+    ``obs_groups`` or, with ``obs_groups`` None, the Pauli term list ``obs_terms``, both on the ``n_qubits`` system
+    wires.  The batch is cut into rounds so that checkpoints, lambda and workspace (:func:`density_call_bytes`) fit
+    ``max_bytes`` (default: ``memory.available_memory_bytes()``); a sample that does not fit alone raises :class:`AdjointUnsupported`."""
+    torch = N.require_gpu()
+    from . import memory
+
+    ft, fn = (torch.float64, np.float64) if x64 else (torch.float32, np.float32)
+    sw = plan_density(tape, n_qubits, want, x64)
+    weights = np.ascontiguousarray(weights, dtype=fn)
+    B, n_obs = int(batch), int(weights.shape[1])
+    K = int(weights.shape[0]) // max(1, B)
+    if weights.shape[0] != K * B or K < 1:
+        raise ValueError(f"weights must be [K * {B}, n_obs], got {weights.shape}")
+    budget = int(memory.available_memory_bytes() if max_bytes is None else max_bytes)
+    _LAST_SWEEP[0] = sw
+    grad = np.zeros((K, B, max(1, sw.n_slots)), dtype=fn)
+    if not sw.steps:
+        return grad.reshape(K * B, -1)[:, : sw.n_slots]
+    dev = N.current_device()
+    fwd_plan, rev_plan = get_plan(sw.fwd, DENSITY_FLAGS), get_plan(sw.rev, DENSITY_FLAGS)
+    # checkpoints, lambda AND workspace: the rounds are sized by what a call of that many samples really allocates
+    rounds = density_rounds(B, lambda bc: density_call_bytes(sw, fwd_plan, rev_plan, bc, K, n_obs, x64), budget,
+                            max_samples=max(1, N.MAX_ROWS // K))
+    table = sw.fwd.angle_table(B, dtype=np.float64 if x64 else np.float32)
+    chan = torch.from_numpy(sw.chan.astype(fn)).to(dev) if sw.chan.size else None
+    perm = torch.from_numpy(sw.rev_src).to(dev)
+    w3 = weights.reshape(K, B, n_obs)
+    lo = 0
+    for bc in rounds:
+        hi = lo + bc
+        a_f = torch.from_numpy(np.ascontiguousarray(table[lo:hi])).to(dev)
+        if sw.rev.n_slots:
+            a_r = (-a_f.index_select(1, perm)).repeat(K, 1).contiguous()
+        else:
+            a_r = torch.zeros((K * bc, 1), dtype=ft, device=dev)
+        if not sw.fwd.n_slots:
+            a_f = torch.zeros((bc, 1), dtype=ft, device=dev)
+        w = torch.from_numpy(np.ascontiguousarray(w3[:, lo:hi].reshape(K * bc, n_obs))).to(dev)
+        g = N.adjoint_density(fwd_plan, rev_plan, a_f, a_r, w, obs_groups, list(sw.steps), chan, max(1, sw.n_slots),
+                              n_cot=K, obs_terms=obs_terms)
+        grad[:, lo:hi] = g.cpu().numpy().reshape(K, bc, -1)
+        lo = hi
+    return grad.reshape(K * B, -1)[:, : sw.n_slots]

@@ -18,6 +18,7 @@
 #include "qmle_host.h"
 #include "qmle_dev.h"
 #include "qmle_adjoint_dev.h"
+#include "qmle_density_dev.h"
 #include "qmle_tile_dev.h"
 
 namespace {
@@ -943,6 +944,46 @@ int qmle_adjoint_cotangent(qmle_plan *fwd, qmle_plan *rev, const float *d_angles
                                     {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
                                      {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
                                      n_grad_slots, d_ws, ws_bytes, stream, {mat_out, n_mat, d_cot}});
+}
+
+}  // extern "C"
+
+// ---- the adjoint sweep of a noisy tape on vec(rho) (qmle_adjoint_density; the sweep itself: qmle_density_dev.h) ----
+// what the sweep runs between two steps: the plan's stages, one operator each
+struct DensUnitF32 {
+  static size_t count(const qmle_plan *p) { return p->stages.size(); }
+  static int src(const qmle_plan *p, size_t k) { return p->stages[k].src_ops.size() == 1 ? p->stages[k].src_ops[0] : -1; }
+  static int ensure(qmle_plan *p) { return ensure_device_plan(p); }
+  static size_t mats_bytes(const qmle_plan *p, int rows) { return ws_mats_bytes(p, rows); }
+  static int build(const qmle_plan *p, const float *angles, float *mats, int rows, hipStream_t stream) {
+    return launch_build_matrices(p, angles, mats, rows, stream);
+  }
+  static int apply(qmle_plan *p, size_t k, float2 *states, const float *mats, const float *angles, int rows,
+                   hipStream_t stream) {
+    return run_stage_inplace(p, p->stages[k], states, mats, angles, rows, stream);
+  }
+};
+
+extern "C" {
+
+size_t qmle_adjoint_density_workspace_bytes(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_cot,
+                                            int n_steps) {
+  return dens_workspace_bytes<float2, DensUnitF32>(fwd, rev, batch, n_cot, n_steps);
+}
+int qmle_adjoint_density(qmle_plan *fwd, qmle_plan *rev, const float *d_angles_fwd, const float *d_angles_rev,
+                         int batch, int n_cot, const float *d_weights, const uint32_t *obs_wire_masks,
+                         const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                         const qmle_density_step *steps, int n_steps, const float *d_chan, int n_chan, float *d_grad,
+                         int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
+  return dens_run<float2, float, DensUnitF32>({fwd, rev, d_angles_fwd, d_angles_rev, batch, n_cot, d_weights,
+                                               {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, steps, n_steps, d_chan,
+                                               n_chan, d_grad, n_grad_slots, d_ws, ws_bytes, stream});
+}
+// (both precisions walk the same tape: the stages of a NO_FUSION plan are its operators)
+long long qmle_adjoint_density_transfers(const qmle_plan *fwd, const qmle_plan *rev, const qmle_density_step *steps,
+                                         int n_steps, int n_cot, int f64) {
+  if (f64 != 0 && f64 != 1) return QMLE_ERR_INVALID_ARG;
+  return dens_transfers<DensUnitF32>(fwd, rev, steps, n_steps, n_cot);
 }
 
 }  // extern "C"

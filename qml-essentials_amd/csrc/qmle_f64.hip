@@ -16,6 +16,7 @@
 #include "qmle_host.h"
 #include "qmle_dev.h"
 #include "qmle_adjoint_dev.h"
+#include "qmle_density_dev.h"
 #include "qmle_matrices.h"
 
 namespace {
@@ -699,6 +700,47 @@ int qmle_adjoint_cotangent_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_a
                                      {fwd, rev, d_angles_fwd, d_angles_rev, batch, d_weights,
                                       {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, terms, n_terms, d_grad,
                                       n_grad_slots, d_ws, ws_bytes, stream, {mat_out, n_mat, d_cot}});
+}
+
+}  // extern "C"
+
+// ---- the adjoint sweep of a noisy tape on vec(rho), complex128 (the sweep itself: qmle_density_dev.h) ------------
+// what the sweep runs between two steps: the plan's lowered operators, one streaming launch each
+struct DensUnitF64 {
+  static size_t count(const qmle_plan *p) { return p->lowered.size(); }
+  static int src(const qmle_plan *p, size_t k) { return p->lowered_src[k].size() == 1 ? p->lowered_src[k][0] : -1; }
+  static int ensure(qmle_plan *p) {
+    const int rc = ensure_device_plan(p);
+    return rc != QMLE_OK ? rc : ensure_f64(p);
+  }
+  static size_t mats_bytes(const qmle_plan *p, int rows) { return f64_mats_bytes(p, rows); }
+  static int build(const qmle_plan *p, const double *angles, double *mats, int rows, hipStream_t stream) {
+    launch_build_matrices_f64(p, angles, mats, rows, stream);
+    return QMLE_OK;
+  }
+  static int apply(qmle_plan *p, size_t k, double2 *states, const double *mats, const double *angles, int rows,
+                   hipStream_t stream) {
+    const size_t half = ((size_t)1 << p->n) / 2;
+    hipLaunchKernelGGL(k64_op, dim3(grid_for(half, 256, 1u << 16), rows), dim3(256), 0, stream, states, p->n,
+                       p->lowered[k], mats, p->mat_floats, f64_consts(p), angles, p->n_slots);
+    return QMLE_OK;
+  }
+};
+
+extern "C" {
+
+size_t qmle_adjoint_density_workspace_bytes_f64(const qmle_plan *fwd, const qmle_plan *rev, int batch, int n_cot,
+                                                int n_steps) {
+  return dens_workspace_bytes<double2, DensUnitF64>(fwd, rev, batch, n_cot, n_steps);
+}
+int qmle_adjoint_density_f64(qmle_plan *fwd, qmle_plan *rev, const double *d_angles_fwd, const double *d_angles_rev,
+                             int batch, int n_cot, const double *d_weights, const uint32_t *obs_wire_masks,
+                             const qmle_pauli_term *obs_terms, int n_obs_terms, int n_obs,
+                             const qmle_density_step *steps, int n_steps, const double *d_chan, int n_chan,
+                             double *d_grad, int n_grad_slots, void *d_ws, size_t ws_bytes, qmle_stream stream) {
+  return dens_run<double2, double, DensUnitF64>({fwd, rev, d_angles_fwd, d_angles_rev, batch, n_cot, d_weights,
+                                                 {obs_wire_masks, obs_terms, n_obs_terms, n_obs}, steps, n_steps,
+                                                 d_chan, n_chan, d_grad, n_grad_slots, d_ws, ws_bytes, stream});
 }
 
 }  // extern "C"

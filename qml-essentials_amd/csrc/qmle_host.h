@@ -13,6 +13,8 @@
 //   qmle_adjoint_dev.h what those two sweeps share: the kernels that are one text in both precisions, a sweep's
 //                      arguments and their checks, the launch pairs of the per-gate sweep, the bodies of the
 //                      extern "C" entry points (qmle_wide.hip takes cot_finish_entry from it, nobody else includes it)
+//   qmle_density_dev.h the adjoint sweep of a NOISY tape over vec(rho) (qmle_adjoint_density / _f64), one text for those
+//                      two units: the step kernels, the seeds, the checks, the walk of the two plans
 //   qmle_wide.hip      the matrix cotangent of a dense gate on three or four wires (qmle_wide_moment): the moment of
 //                      psi and lambda on the matrix cores, per-block partials, one finishing kernel
 //   qmle_gram.hip      Gram matrices of resident states

@@ -652,7 +652,7 @@ class Model:
     def gradient(self, params=None, inputs=None, enc_params=None, wrt="params",
                  force_mean: bool = False, data_reupload=None,
                  method: str = "parameter-shift", cotangent=None, pulse_params=None,
-                 gate_mode: str = "unitary") -> np.ndarray:
+                 gate_mode: str = "unitary", noisy: bool = False) -> np.ndarray:
         """d<Z_q>/d``wrt`` for every output qubit by the parameter-shift rule
         (:meth:`script.Script.gradient`); ``wrt`` in {"params", "inputs", "enc_params"}.
 
@@ -680,6 +680,12 @@ class Model:
         gradients from ONE trace and ONE sweep.  ``Model(x64=True)`` / ``x64_scope`` take the complex128 sweep.
         Not served in pulse mode: noise, a batch axis in ``pulse_params``, the torch bridge and the compiled
         device path.
+
+        ``noisy=True`` (with ``method="adjoint"``) differentiates a model WITH ``noise_params`` by one backward sweep
+        over vec(rho) (``Script.vjp(noisy=True)``, ``adjoint.density_gradient``): ``wrt`` = ``params``, ``inputs``,
+        ``enc_params`` or a tuple, with ``force_mean``, an explicit ``cotangent``, or the full Jacobian, whose
+        ``n_outputs`` one-hot cotangents share one forward run.  Without the keyword a noisy model is refused by the
+        adjoint as before; ``method="auto"`` never picks this route.
         """
         from .utils import x64_enabled, x64_scope
 
@@ -688,7 +694,9 @@ class Model:
                 return self.gradient(params=params, inputs=inputs, enc_params=enc_params, wrt=wrt,
                                      force_mean=force_mean, data_reupload=data_reupload,
                                      method=method, cotangent=cotangent, pulse_params=pulse_params,
-                                     gate_mode=gate_mode)
+                                     gate_mode=gate_mode, noisy=noisy)
+        if noisy and method != "adjoint":
+            raise ValueError("noisy=True needs method='adjoint'")
         many = isinstance(wrt, (tuple, list))
         wrts = tuple(wrt) if many else (wrt,)
         pulse = gate_mode == "pulse"
@@ -755,10 +763,11 @@ class Model:
         if method == "adjoint":  # (x64 mode: Script.vjp runs the complex128 sweep, qmle_adjoint_gradient_f64)
             n_out = len(obs)
             ax = in_axes if B > 1 else None
+            opt = {"noisy": True} if noisy else {}
             if cotangent is not None or force_mean:
                 w = (np.full((B, n_out), 1.0 / n_out) if cotangent is None
                      else np.asarray(cotangent, dtype=np.float64).reshape(B, n_out))
-                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums)
+                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums, **opt)
                 jacs = [(g if B > 1 else g[None])[:, None] for g in gs]  # (B, 1, *leaf)
                 force_mean = True                              # the output axis is already reduced
             else:
@@ -766,7 +775,7 @@ class Model:
                 # n_out * B states (round 5; before: n_out calls, each re-recording the tape)
                 w = np.zeros((n_out, B, n_out))
                 w[np.arange(n_out), :, np.arange(n_out)] = 1.0
-                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums)
+                gs = self.script.vjp(obs, w, args=args, kwargs=kwargs, in_axes=ax, argnums=argnums, **opt)
                 jacs = [np.moveaxis(g if B > 1 else g[:, None], 0, 1) for g in gs]   # (B, n_out, *leaf)
         else:
             (jac,) = self.script.gradient(obs, args=args, kwargs=kwargs,

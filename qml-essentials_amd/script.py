@@ -538,7 +538,7 @@ class Script:
     def vjp(self, obs: List[Operation], cotangent, *, args: tuple = (),
             kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
             argnums: Tuple[int, ...] = (0,), pauli_seed: bool = False, through_evolve: bool = False,
-            wide_gates: bool = False):
+            wide_gates: bool = False, noisy: bool = False):
         """Gradient of ``sum_k cotangent[b, k] * <obs_k>_b`` with respect to the array arguments
         ``argnums`` by ADJOINT differentiation: one backward sweep for all angles
         (:mod:`adjoint`).  ``obs``: at most 32 Z / Z-parity observables seed the sweep from their wire masks.
@@ -579,7 +579,16 @@ class Script:
         on a leaf, is differentiated from ``dU/dt = -i H U``.  Still refused: a ``ParametrizedHamiltonian`` on three
         or four wires that depends on a leaf (the wide solver has no Jacobian form), matrices on five or more wires,
         noisy tapes; ``Script.gradient``, compiled calls, ``Model`` and the torch bridge do not take such tapes.
-        Without the keyword every refusal is what it was."""
+        Without the keyword every refusal is what it was.
+
+        ``noisy=True`` serves a tape that holds Kraus channels on one and two wires: the sweep runs over vec(rho) with
+        the forward states kept (``adjoint.density_gradient``, ``qmle_adjoint_density``) and gives the gradient of
+        every ordinary angle for Z / parity seeds, ``pauli_seed=True``, ``(K, B, n_obs)`` cotangents (K cotangents
+        share one forward run) and ``in_axes``, in complex64 and x64.  Refused with ``AdjointUnsupported``, naming the
+        operation: channels on three or four wires, full-register diagonal encodings, per-sample matrices (pulse and
+        evolved gates, also with ``through_evolve``), explicit matrices on three or four wires; derivatives with
+        respect to noise strengths are not formed.  A tape without a channel takes the pure-state sweep as before, and
+        without the keyword a noisy tape is refused as it always was."""
         from . import adjoint
 
         if not obs:
@@ -592,9 +601,14 @@ class Script:
                 "H psi for sums of Pauli words (got " + ", ".join(kinds) + ")")
         mat_ops: list = []
         tape, low, n_qubits, B, slots, leaf_shapes, batched = self._trace_for_gradient(
-            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops, through_evolve=through_evolve, wide_gates=wide_gates)
-        if any(isinstance(o, KrausChannel) for o in tape):
+            obs, args, kwargs, in_axes, argnums, mat_ops=mat_ops, through_evolve=through_evolve, wide_gates=wide_gates,
+            **({"skip_channels": True} if noisy else {}))
+        on_rho = any(isinstance(o, KrausChannel) for o in tape)  # (noisy=True: the sweep over vec(rho))
+        if on_rho and not noisy:
             raise adjoint.AdjointUnsupported("adjoint differentiation of noisy circuits")
+        if on_rho and mat_ops:
+            raise adjoint.AdjointUnsupported(f"adjoint differentiation of noisy circuits: {mat_ops[0][1].name} (a pulse "
+                                             "or evolved gate: a per-sample matrix) is not served")
         segmented = low is None  # (wide_gates=True and a wide gate on the tape: the sweep segment by segment)
         for o in tape:  # without through_evolve evolved gates stay out of scope: nothing differentiates one
             if segmented and is_wide_matrix_gate(o):  # (constant or carrying its Jacobian: _trace_for_gradient)
@@ -632,7 +646,10 @@ class Script:
         # needs the form of the reverse tape that inverts it
         row_ops = not segmented and through_evolve and any(name in ("MAT1_ROW", "MAT2_ROW")
                                                            for name, _w, _s, _off in low.ops)
-        if segmented:
+        if on_rho:
+            if slots:
+                d = adjoint.density_gradient(tape, n_qubits, B, masks, w, want, x64=x64, obs_terms=obs_terms)
+        elif segmented:
             cots = []
             if mat_ops or slots:  # one [K * B, d, d] per flagged tape entry, d = 2, 4, 8 or 16
                 want_mat = [False] * len(tape)
