@@ -440,6 +440,37 @@ int qmle_wide_moment(const void *d_psi, const void *d_lam, int n_qubits, int bat
                      qmle_stream stream);
 size_t qmle_wide_moment_workspace_bytes(int n_qubits, int batch, int k, int f64);
 
+/* ---- Kraus maps on three and four wires of a resident vec(rho): wide gates and wide channels of a noisy tape -----
+ * rho -> sum_m K_m rho K_m^+ on k = 3 or 4 SYSTEM wires, in place, one read and one write of vec(rho) per call.  With
+ * one unitary K it is an explicit matrix gate on a noisy tape, with a Kraus set a channel.
+ * d_rho: DEVICE, [batch][4^n], vec(rho)[i * 2^n + j] = rho[i, j] (a register of 2n wires, the ket wires first),
+ * complex64 (f64 = 0, float32 arithmetic) or complex128 (f64 = 1).  n_qubits: the number of SYSTEM qubits,
+ * k <= n and 2n <= QMLE_MAX_QUBITS.  wires: HOST array of k system wires in operation order, the first one the most
+ * significant bit of the operator index (as for qmle_apply_matrix); the ket bit of wire w sits on position
+ * 2n - 1 - w of the register, the bra bit on n - 1 - w.  d_ops: DEVICE, complex128 row-major, [n_ops][d][d], d = 2^k
+ * (per_sample = 0), or [batch][d][d] with n_ops = 1 (per_sample = 1: sample b takes operator b); rounded to float32
+ * for complex64.  The operators need not be unitary nor sum to a trace-preserving map.
+ * form: 1 = sandwich: every d x d block R of rho on the target bits becomes sum_m K_m R K_m^+ by two products per
+ * operator on the matrix cores (2 d n_ops complex multiply-adds per amplitude); 2 = superoperator: the library
+ * builds S = sum_m K_m (x) conj(K_m) (d^2 x d^2, index order of KrausChannel.superoperator up to the permutation
+ * that sorts the wires, summed in float64 in the order of m) into the workspace and applies vec(R') = S vec(R)
+ * (d^2 multiply-adds per amplitude whatever n_ops is); 0 = automatic: the sandwich for per_sample = 1, for one
+ * operator at k = 3 and for up to four at k = 4 -- where the measured times of the two cross (profiles/density_wide.md;
+ * their arithmetic breaks even later, at n_ops = d / 2).  qmle_density_apply_wide_form returns what 0 selects
+ * (host only), or the status the call would return for these three arguments.
+ * No atomics, fixed summation orders: the same bits from call to call.  Any batch >= 1 (the library splits launches).
+ * Status codes, all before any device work: QMLE_ERR_UNSUPPORTED for k outside {3, 4}; QMLE_ERR_INVALID_ARG for NULL
+ * pointers, batch < 1, n < k, 2n > QMLE_MAX_QUBITS, f64 / per_sample / form out of range, n_ops < 1, per_sample = 1
+ * with n_ops != 1 or with form = 2, form = 1 with more than d^2 operators; QMLE_ERR_WIRE_RANGE;
+ * QMLE_ERR_DUPLICATE_WIRES; QMLE_ERR_WORKSPACE for a workspace smaller than the query's answer (0 for arguments
+ * the call would refuse).  Not served: five or more wires, the adjoint sweep (qmle_adjoint_density knows no such
+ * step), compiled calls. */
+int qmle_density_apply_wide(void *d_rho, int n_qubits, int batch, int f64, const int32_t *wires, int k,
+                            const void *d_ops, int n_ops, int per_sample, int form, void *d_ws, size_t ws_bytes,
+                            qmle_stream stream);
+size_t qmle_density_apply_wide_workspace_bytes(int n_qubits, int batch, int k, int n_ops, int f64, int form);
+int qmle_density_apply_wide_form(int k, int n_ops, int per_sample);
+
 /* Optional per-pass HIP-event timing (bench.py's live roofline measurement): between
  * begin and end every pass launch of this plan is bracketed by an event pair on the
  * launch stream.  end() synchronises, fills stage_ms[i] / stage_launches[i] (i = pass

@@ -216,6 +216,9 @@ SYMBOLS = [
     ("qmle_apply_matrix", _I, [_VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _VP]),
     ("qmle_wide_moment", _I, [_VP, _VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _VP, _VP, _SZ, _VP]),
     ("qmle_wide_moment_workspace_bytes", _SZ, [_I, _I, _I, _I]),
+    ("qmle_density_apply_wide", _I, [_VP, _I, _I, _I, C.POINTER(C.c_int32), _I, _VP, _I, _I, _I, _VP, _SZ, _VP]),
+    ("qmle_density_apply_wide_workspace_bytes", _SZ, [_I, _I, _I, _I, _I, _I]),
+    ("qmle_density_apply_wide_form", _I, [_I, _I, _I]),
     ("qmle_histogram", _I, [_VP, C.c_int64, _I, _F, _F, _VP, _VP]),
     ("qmle_adjoint_gradient", _I, [_VP, _VP, _VP, _VP, _I, _VP, C.POINTER(C.c_uint32), _I, _VP, _I,
                                    _VP, _I, _VP, _SZ, _VP]),
@@ -1124,6 +1127,43 @@ def wide_moment(psi, lam, wires: Sequence[int], mats=None):
                                  C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
                                  _stream_ptr()), "qmle_wide_moment")
     return out
+
+
+DENSITY_WIDE_FORMS = {"auto": 0, "sandwich": 1, "superoperator": 2}
+
+
+def density_apply_wide(rho_vec, n_qubits: int, wires: Sequence[int], ops, per_sample: bool = False, form: str = "auto"):
+    """``rho -> sum_m K_m rho K_m^+`` on 3 or 4 system wires, in place on resident ``rho_vec`` ``[B, 4^n]`` (complex64
+    or complex128 CUDA, contiguous; ``vec(rho)[i * 2^n + j] = rho[i, j]``) -- ``qmle_density_apply_wide``, one read and
+    one write of vec(rho).  ``ops``: ``[n_ops, d, d]`` or ``[d, d]`` (one Kraus set, or one matrix, for every sample),
+    or with ``per_sample`` ``[B, d, d]`` (sample b takes matrix b); a host array or a CUDA tensor; the first wire is
+    the most significant bit of the operator index.  ``form``: ``"auto"``, ``"sandwich"`` or ``"superoperator"``."""
+    torch = require_gpu()
+    if rho_vec.dtype not in (torch.complex64, torch.complex128) or not rho_vec.is_cuda or not rho_vec.is_contiguous() \
+            or rho_vec.dim() != 2:
+        raise ValueError("density_apply_wide: rho_vec must be a contiguous complex64 / complex128 CUDA tensor [B, 4^n]")
+    if form not in DENSITY_WIDE_FORMS:
+        raise ValueError(f"density_apply_wide: form must be one of {sorted(DENSITY_WIDE_FORMS)}, got {form!r}")
+    B, n = int(rho_vec.shape[0]), int(n_qubits)
+    if int(rho_vec.shape[1]) != 1 << (2 * n):
+        raise ValueError(f"density_apply_wide: vec(rho) of length {int(rho_vec.shape[1])} does not fit {n} qubit(s)")
+    wires = [int(w) for w in wires]
+    k, d = len(wires), 1 << len(wires)
+    M = _device_tensor(ops, torch.complex128)
+    if M.device != rho_vec.device:
+        M = M.to(rho_vec.device)
+    if M.dim() == 2:
+        M = M[None]
+    if M.dim() != 3 or tuple(M.shape[1:]) != (d, d) or (per_sample and M.shape[0] != B):
+        raise ValueError(f"density_apply_wide: operators of shape {tuple(M.shape)} do not fit {k} wire(s) and {B} sample(s)")
+    M = M.contiguous()
+    n_ops, f64, fcode = (1 if per_sample else int(M.shape[0])), (1 if rho_vec.dtype == torch.complex128 else 0), DENSITY_WIDE_FORMS[form]
+    ws = torch.empty(max(1, int(lib().qmle_density_apply_wide_workspace_bytes(n, B, k, n_ops, f64, fcode))), dtype=torch.uint8,
+                     device=rho_vec.device)
+    check(lib().qmle_density_apply_wide(C.c_void_p(rho_vec.data_ptr()), n, B, f64, _i32(wires), k, C.c_void_p(M.data_ptr()),
+                                        n_ops, 1 if per_sample else 0, fcode, C.c_void_p(ws.data_ptr()),
+                                        C.c_size_t(ws.numel()), _stream_ptr()), "qmle_density_apply_wide")
+    return rho_vec
 
 
 EVOLVE_MAX_DIRS = 64  # qmle_evolve_magnus_jac: directions per call

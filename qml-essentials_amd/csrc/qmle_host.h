@@ -17,6 +17,8 @@
 //                      two units: the step kernels, the seeds, the checks, the walk of the two plans
 //   qmle_wide.hip      the matrix cotangent of a dense gate on three or four wires (qmle_wide_moment): the moment of
 //                      psi and lambda on the matrix cores, per-block partials, one finishing kernel
+//   qmle_density_wide.hip  Kraus maps on three or four system wires of a resident vec(rho) (qmle_density_apply_wide):
+//                      wide gates and wide channels of a noisy tape, a 12-position LDS tile, two forms on the matrix cores
 //   qmle_gram.hip      Gram matrices of resident states
 //   qmle_evolve.hip    Hamiltonian time evolution: 2x2 / 4x4 propagators on the fixed Magnus grids (qmle_evolve_magnus)
 //                      the pulse solves with and without sensitivities, and the composition of small circuits

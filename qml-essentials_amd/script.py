@@ -62,8 +62,8 @@ class CompiledCall:
             if type == "state" or self.n_qubits > simulation.MAX_DENSITY_QUBITS:
                 raise NotAffine("noisy tape")  # (the recorded path raises the reference's messages)
             tape = simulation.doubled_tape(tape, self.n_qubits)
-            if any(isinstance(it, simulation._WideChannel) for it in tape):
-                raise NotAffine("wide channel")
+            if any(isinstance(it, (simulation._WideChannel, simulation._WideGate)) for it in tape):
+                raise NotAffine("wide channel")  # (and wide gates: neither is an operator of a plan)
             n_reg = 2 * self.n_qubits
         self.n_register = n_reg
         low = simulation.LoweredTape(tape, n_reg)
@@ -348,35 +348,40 @@ class Script:
 
     def execute(self, type: str = "expval", obs: Optional[List[Operation]] = None, *,
                 args: tuple = (), kwargs: Optional[dict] = None, in_axes: Optional[Tuple] = None,
-                shots: Optional[int] = None, key=None, as_tensor: bool = False):
-        """Execute the circuit; with ``in_axes`` the result has a leading batch axis."""
+                shots: Optional[int] = None, key=None, as_tensor: bool = False, wide_gates: bool = False):
+        """Execute the circuit; with ``in_axes`` the result has a leading batch axis.  ``wide_gates=True`` serves a
+        noisy tape that holds explicit matrices on three or four wires (``op.prod(...)``, ``A @ B``,
+        ``Operation(wires, matrix)``, evolved unitaries of 8x8 / 16x16 Hamiltonians) beside Kraus channels: every
+        measurement type but ``"state"``, shots, complex64 and x64, un-batched and with ``in_axes``.  Without it such a
+        tape is refused; on a noise-free tape the keyword changes nothing.  Still refused with it: matrices and
+        channels on five or more wires, ``vjp(noisy=True)`` through wide gates or wide channels, ``gradient``."""
         from .tape import captured_call
 
         with captured_call(lambda: dict(kind="script", script=self, type=type, obs=obs, args=args,
                                         kwargs=kwargs, in_axes=in_axes, shots=shots)) as cap:
-            cap["result"] = self._execute(type, obs, args, kwargs, in_axes, shots, key, as_tensor)
+            cap["result"] = self._execute(type, obs, args, kwargs, in_axes, shots, key, as_tensor, wide_gates)
         return cap["result"]
 
-    def _execute(self, type, obs, args, kwargs, in_axes, shots, key, as_tensor):
+    def _execute(self, type, obs, args, kwargs, in_axes, shots, key, as_tensor, wide_gates=False):
         obs = [] if obs is None else obs
         kwargs = {} if kwargs is None else kwargs
         if shots is not None and key is None:
             key = PRNGKey(0)  # script.py:189-190
         if in_axes is not None:
-            return self._execute_batched(type, obs, args, kwargs, in_axes, shots, key, as_tensor)
+            return self._execute_batched(type, obs, args, kwargs, in_axes, shots, key, as_tensor, wide_gates)
         tape = self._record_for_engine(*[to_numpy(a) for a in args], **kwargs)
         pulses.resolve(tape)  # every pulse leaf of the tape in one launch
         n_qubits = self._n_qubits or simulation.infer_n_qubits(tape, obs)
         res = simulation.simulate_and_measure(
             tape, n_qubits, type, obs, simulation.uses_density(tape, type), shots=shots, key=key,
-            as_tensor=as_tensor,
+            as_tensor=as_tensor, **({"wide_gates": True} if wide_gates else {}),
         )
         if simulation._tape_batch(tape) == 1:
             res = res[0]
         return res
 
     def _execute_batched(self, type, obs, args, kwargs, in_axes, shots=None, key=None,
-                         as_tensor: bool = False):
+                         as_tensor: bool = False, wide_gates: bool = False):
         if len(in_axes) != len(args):
             raise ValueError(
                 f"in_axes has {len(in_axes)} entries but args has {len(args)}. "
@@ -400,6 +405,7 @@ class Script:
             return simulation.simulate_and_measure(
                 tape, n_qubits, type, obs, simulation.uses_density(tape, type), shots=shots,
                 key=key, batch=end - start, as_tensor=as_tensor, row_offset=start,
+                **({"wide_gates": True} if wide_gates else {}),  # (said only where asked for: the call is as it was otherwise)
             ), n_qubits, len(tape)
 
         # memory-aware chunking needs n_qubits / n_ops: probe with one sample's structure

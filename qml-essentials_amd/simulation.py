@@ -82,7 +82,9 @@ def _conj_tangents(op_: Operation, name: str) -> list:
 
 class _WideChannel:
     """A channel on 3 or 4 wires: too wide for one dense engine operator (its superoperator
-    spans 6-8 wires), applied as the Kraus sum with one engine call per operator."""
+    spans 6-8 wires).  :func:`_evolve_density` applies it with one call of ``qmle_density_apply_wide`` (one read and
+    one write of vec(rho)); :meth:`kraus_plans` is the route before that pass existed -- one engine call per Kraus
+    operator -- kept for tools/density_wide_bench.py to measure against."""
 
     __slots__ = ("kraus", "wires")
 
@@ -107,6 +109,19 @@ class _WideChannel:
             yield [_Lowered(("MAT4", wk, [], blob(K))), _Lowered(("MAT4", wb, [], blob(np.conj(K))))]
 
 
+class _WideGate:
+    """An explicit matrix on 3 or 4 wires (``operations.is_wide_matrix_gate``) on a noisy tape: ``[d, d]``, or
+    ``[B, d, d]`` with one matrix per sample.  No plan holds it; :func:`_evolve_density` applies
+    ``rho -> U rho U^+`` with two ``qmle_apply_matrix`` passes over the 2n-wire register, U on the ket wires and
+    conj(U) on the bra wires: measured against the one-pass sandwich form of ``qmle_density_apply_wide`` they are
+    ahead at n = 12 in complex64 (profiles/density_wide.md, leg 2), so the gate takes them."""
+
+    __slots__ = ("matrix", "wires")
+
+    def __init__(self, matrix, wires):
+        self.matrix, self.wires = np.asarray(matrix, dtype=np.complex128), list(wires)
+
+
 def doubled_tape(tape: Sequence[Operation], n_qubits: int) -> list:
     """The tape acting on vec(rho), a pure "state" of a 2n-wire register whose first n wires
     carry the row (ket) index and whose last n wires carry the column (bra) index, so that
@@ -116,7 +131,9 @@ def doubled_tape(tape: Sequence[Operation], n_qubits: int) -> list:
       (``rho -> U rho U^+``, ``simulation.py:106-128`` + ``operations.py:485-512``);
     * channel {K} on wires w -> the dense superoperator ``sum_K K (x) conj(K)`` on
       ``[w.., n + w..]`` (``operations.py:1552-1578``): a 4x4 operator for 1-wire channels,
-      a 16x16 one for 2-wire channels; 3- and 4-wire channels become a :class:`_WideChannel`.
+      a 16x16 one for 2-wire channels; 3- and 4-wire channels become a :class:`_WideChannel`;
+    * an explicit matrix on 3 or 4 wires -> a :class:`_WideGate`, behind the pending channel products that share a
+      wire with it.
     """
     out: list = []
     # Channels that follow one another on the same wires -- the five or six channels a noisy model puts
@@ -152,6 +169,13 @@ def doubled_tape(tape: Sequence[Operation], n_qubits: int) -> list:
             else:
                 flush(set(w))
                 pending[w] = S
+            continue
+        if is_wide_matrix_gate(op_):
+            m, k = np.asarray(op_._matrix), len(op_.wires)
+            if m.shape[-2:] != (2 ** k, 2 ** k):
+                raise ValueError(f"{op_.name}: matrix shape {m.shape[-2:]} does not match {k} wire(s)")
+            flush(set(op_.wires))
+            out.append(_WideGate(m, op_.wires))
             continue
         low = op_.lower(n_qubits)
         if low is None:
@@ -208,10 +232,16 @@ def _evolve_density(tape: Sequence[Operation], n_qubits: int, B: int, x64: bool 
             seg = []
         if item is None:
             break
-        acc = torch.zeros_like(rho_vec)
-        for pair in item.kraus_plans(n_qubits):
-            acc += _apply_segment(pair, n2, B, rho_vec.clone(), x64)
-        rho_vec = acc
+        if isinstance(item, _WideGate):  # rho -> U rho U^+: one operator, the same for every sample or one per sample
+            per_sample = item.matrix.ndim == 3
+            if per_sample and item.matrix.shape[0] != B:
+                raise ValueError(f"one matrix per sample needs {B} matrices, got {item.matrix.shape[0]}")
+            mats = torch.from_numpy(np.ascontiguousarray(item.matrix)).cuda()
+            N.apply_matrix(rho_vec, item.wires, mats)
+            N.apply_matrix(rho_vec, [w + n_qubits for w in item.wires], mats.conj().resolve_conj())
+        else:  # _WideChannel: the whole Kraus set in one pass
+            N.density_apply_wide(rho_vec, n_qubits, item.wires, np.stack([np.asarray(K, dtype=np.complex128)
+                                                                          for K in item.kraus]))
     return rho_vec
 
 
@@ -636,22 +666,24 @@ def _simulate_segmented(tape: Sequence[Operation], n_qubits: int, type: str, obs
 def simulate_and_measure(tape: Sequence[Operation], n_qubits: int, type: str,
                          obs: Sequence[Operation] = (), use_density: bool = False,
                          shots: Optional[int] = None, key=None, batch: Optional[int] = None,
-                         as_tensor: bool = False, row_offset: int = 0):
+                         as_tensor: bool = False, row_offset: int = 0, wide_gates: bool = False):
     """Run the tape from |0..0> and measure.  Returns ``(B, ...)`` (numpy unless
     ``as_tensor``); the caller strips the batch axis for un-batched execution.  With
     ``shots`` the exact probabilities are sampled on the device (``probs`` / ``expval``
-    only; other types stay exact, ``simulation.py:191-201``)."""
+    only; other types stay exact, ``simulation.py:191-201``).  ``wide_gates=True`` serves a NOISY tape that holds
+    explicit matrices on 3 or 4 wires (:class:`_WideGate`); on any other tape it changes nothing."""
     if type not in MEAS_TYPES:
         raise ValueError(f"Unknown measurement type: {type!r}")
     torch = N.require_gpu()
     B = int(batch) if batch is not None else _tape_batch(tape)
     sampled = shots is not None and type in ("probs", "expval")
     if any(is_wide_matrix_gate(o) for o in tape):
-        if any(isinstance(o, KrausChannel) for o in tape):
+        if any(isinstance(o, KrausChannel) for o in tape) and not wide_gates:
             raise NotImplementedError("explicit matrices on 3 or 4 wires (products of gates, evolved unitaries of "
                                       "three- and four-wire Hamiltonians) are not available on noisy tapes: the "
                                       "density-matrix path has no pass for them")
-        return _simulate_segmented(tape, n_qubits, type, obs, B, shots, key, row_offset, as_tensor)
+        if not any(isinstance(o, KrausChannel) for o in tape):
+            return _simulate_segmented(tape, n_qubits, type, obs, B, shots, key, row_offset, as_tensor)
     if any(isinstance(o, KrausChannel) for o in tape):
         from .utils import x64_enabled
 
