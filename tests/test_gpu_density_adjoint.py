@@ -20,6 +20,7 @@ from qml_essentials_amd.simulation import LoweredTape
 from qml_essentials_amd.utils import x64_scope
 
 import density_adjoint_reference as DR
+from density_factorised_reference import ONE_WIRE, TWO_WIRE, one_wire_channel as _one_wire_channel
 import noise_reference as NR
 
 pytestmark = pytest.mark.gpu
@@ -61,15 +62,6 @@ def _angles(rng):
     return Batched(rng.uniform(0, 2 * np.pi, size=(B,)), [])
 
 
-def _one_wire_channel(kind, q):
-    {"bitflip": lambda: op.BitFlip(0.1, wires=q), "phaseflip": lambda: op.PhaseFlip(0.15, wires=q),
-     "depol": lambda: op.DepolarizingChannel(0.05, wires=q), "amp": lambda: op.AmplitudeDamping(0.3, wires=q),
-     "phase": lambda: op.PhaseDamping(0.2, wires=q)}[kind]()
-
-
-ONE_WIRE = {"RX": op.RX, "RY": op.RY, "RZ": op.RZ}
-TWO_WIRE = {"CRX": op.CRX, "CRY": op.CRY, "CRZ": op.CRZ, "CPhase": op.ControlledPhaseShift, "RXX": op.RXX,
-            "RYY": op.RYY, "RZZ": op.RZZ, "RZX": op.RZX}
 # (gate, wires, channel kind or "pair", n): every wire of n = 2 and n = 3 carries a one-wire step, so bit positions 0 / 1
 # and the pair (q, q + n) at every distance occur; control and target in both orders, adjacent and at the ends
 STEP_CASES = ([(g, (q,), ch, n) for n in (2, 3) for q in range(n)
